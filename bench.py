@@ -7,12 +7,16 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; rank 0 print
     rank 0's line and fails if any rank fails.  No PyTorch anywhere: the one collective (the episode-metric all-reduce) is
     the engine's own RCCL call behind the C ABI (adc_engine_metrics_allreduce), brought up by adcraft_amd/comm.py.
   * A "step" is one pass of the hot path (one BiddingSimulation.step for every resident env) over device-resident
-    synthetic actions.
+    synthetic actions.  The timed steps start from the same engine state in every run (the untimed steps before them are
+    undone), so `--dump-outputs DIR` writes the same last-step outputs from run to run and from build to build.
+  * A plain run does only what the headline needs: set-up, clock spin, W warm-up steps, K timed steps.  `--full` adds
+    everything else the line can carry (roofline and kernel times, env-group and unspun figures, episode metric, CPU
+    baseline, the configs under "also", host_step).
   * Workload.  N = 1: BASELINE.json configs[1] (cfg2: 4096 envs x 256 keywords, dense stationary law) is `value`; the
     largest single-GPU config (cfg3: 16384 x 1024, sparse volume) and the per-GPU shards of the 8-GPU configs are measured in
-    the same run and reported under "also".  N > 1: every GPU holds the BASELINE configs[3] shard (cfg4: 65536 x 1024 over
+    the same run (--full) and reported under "also".  N > 1: every GPU holds the BASELINE configs[3] shard (cfg4: 65536 x 1024 over
     8 GPUs = 8192 x 1024 per GPU), envs shard with no data-path collective ("weak" scaling), the metric vector is
-    all-reduced once per 60-step episode inside the timed region; configs[4] (cfg5: drift) is under "also".
+    all-reduced once per 60-step episode inside the timed region; configs[4] (cfg5: drift) is under "also" (--full).
 """
 import argparse
 import json
@@ -37,6 +41,8 @@ VALU_PEAK_4CYCLE_LANE_OPS = 256 * 4 * 16 * 2.4e9
 BYTES_PER_U = {False: 56, True: 68}   # 36 B read + 20 B written per keyword-step (+12 B drift write-back)
 BYTES_PER_ENV = 26
 MAX_DAYS = 60
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240601      # ... the env rows kept where the outputs are larger
 # the three intervals between the engine's HIP events; the IMPLICIT kernels add their metric sums in their own output phase, so
 # the third interval holds no kernel here (what it shows is the cost of recording an event pair)
 KERNEL_NAMES = ("k_step_implicit_fast", "k_tail_or_flag + the budget-exact kernels (k_step_click_walk, k_step_exact_rows, k_step_rest_of_day, k_rest_walk)",
@@ -99,7 +105,37 @@ def pmc_notes(cfg_name):
     return rec
 
 
-def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_baseline, collective_alone=False):
+def dump_outputs(out, dump_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the timed path's last step hands its caller (StepEngine.fetch), one DIR/<name>.npy each, in float32
+    (counts, flags, days, cost, revenue: exact) or float64 (reward, cumulative profit).  Where they would exceed limit_bytes, the
+    same fixed, seeded sample of env rows is kept in every array; env_index.npy names the rows kept (all of them otherwise)"""
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in out.items()}
+    n_envs = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // n_envs for a in arrays.values()) + 8          # (+ the row's entry in env_index)
+    keep = min(n_envs, (limit_bytes - 128 * (len(arrays) + 1)) // row_bytes)   # (.npy headers: 128 bytes a file)
+    rows = np.arange(n_envs) if keep == n_envs else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_envs, keep, replace=False))
+    arrays["env_index"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a if name == "env_index" or keep == n_envs else a[rows])
+
+
+def restore_set_up_state(eng, rng_state, planes, drift):
+    """the engine back to its state right after the set-up (episodes at day 0, the config's keyword parameters, the stream position
+    rng_state), so that the untimed steps run before the timed ones (clock spin, --full passes) leave no trace in what those compute:
+    reset() with seeds clears the episodes and any pending drift, the stream position is put back (over the seeds' keys), and with
+    drift on the parameters too (only drift moves them)"""
+    eng.reset(seeds=np.zeros(eng.num_envs, np.uint64))
+    eng.set_rng_state(*rng_state)
+    if drift:
+        eng.set_all_params(planes)
+
+
+def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_baseline, collective_alone=False, full=False,
+               dump_dir=None):
+    """one config.  Every run: set-up, the clock spin, the engine back to its state after the set-up, the W warm-up steps, the K
+    timed steps (what ms_per_step and value time).  full: also the passes behind the roofline, env-group and episode figures (run
+    between the set-up and the restore) and the CPU baseline."""
     from adcraft_amd import _ffi, synthetic, distributed as D
     from adcraft_amd.engine import StepEngine
 
@@ -112,6 +148,7 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
     eng.reset()
     eng.sample_actions(0.30, 1.00, args.budget)  # actions resident in HBM before the timed region
     eng.metrics_enable(True)
+    rng0 = eng.get_rng_state()                   # the stream position the timed steps start from (restore_set_up_state)
     red = D.MetricReducer(eng, rank, world)      # world > 1: the engine's RCCL communicator (collective bring-up)
     collective_error = None
     if collective_alone and world == 1:
@@ -122,27 +159,35 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
         except Exception as exc:                 # no usable librccl on this box: say so in the line, keep measuring the steps
             collective_error = f"{type(exc).__name__}: {exc}"
     with_collective = world > 1 or (collective_alone and collective_error is None)
-    # stationary keywords: the ideal (max expected) profit per keyword is constant over the episode
-    ideal_nk = eng.ideal_profit(2048)            # (with drift on this is the episode-start value)
-    ideal_k, ideal_pos_k = ideal_nk.sum(axis=0), np.where(ideal_nk <= 0, 1.0, ideal_nk).sum(axis=0)
+    ideal_k = ideal_pos_k = None
+    if with_collective or full:
+        # stationary keywords: the ideal (max expected) profit per keyword is constant over the episode
+        ideal_nk = eng.ideal_profit(2048)        # (with drift on this is the episode-start value)
+        ideal_k, ideal_pos_k = ideal_nk.sum(axis=0), np.where(ideal_nk <= 0, 1.0, ideal_nk).sum(axis=0)
 
     def barrier():
         eng.synchronize()
         red.barrier()
 
-    for _ in range(warmup):
-        eng.step_device()
-    red.metric_sums(ideal_k * warmup, ideal_pos_k * warmup)       # also brings the collective path up outside the timed region
-    barrier()
-    # (the line also carries what the contract's flags alone measure - K steps right behind the W warm-up steps, before the
-    #  clock spin below - so that the driver-shaped figure stays comparable with rounds that had no spin)
-    t_u = time.perf_counter()
-    for _ in range(steps):
-        eng.step_device()
-    barrier()
-    unspun_ms = (time.perf_counter() - t_u) / steps * 1e3
+    def warm_up():
+        for _ in range(warmup):
+            eng.step_device()
+        if with_collective or full:
+            red.metric_sums(ideal_k * warmup, ideal_pos_k * warmup)   # also brings the collective path up outside the timed region
+        barrier()
+
+    if full:
+        warm_up()
+        # (the line also carries what the contract's flags alone measure - K steps right behind the W warm-up steps, before
+        #  the clock spin below - so that the driver-shaped figure stays comparable with rounds that had no spin)
+        t_u = time.perf_counter()
+        for _ in range(steps):
+            eng.step_device()
+        barrier()
+        unspun_ms = (time.perf_counter() - t_u) / steps * 1e3
     # a short timed region starts on clocks that are still ramping (a 20-step region measured 6 % slower than a 200-step one): more
-    # UNTIMED steps until the device has been busy for args.spin_seconds; the driver's --warmup steps above stay what they are
+    # UNTIMED steps until the device has been busy for args.spin_seconds; the engine is put back to its state after the set-up
+    # before the driver's --warmup steps, so the timed steps compute the same whatever the spin ran
     spin_steps, t_spin = 0, time.perf_counter()
     while time.perf_counter() - t_spin < args.spin_seconds:
         for _ in range(16):
@@ -150,26 +195,29 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
         eng.synchronize()
         spin_steps += 16
     barrier()
-    # where the engine runs the step as env groups on several streams, the same K steps as ONE group (the schedule the kernel
-    # times below are taken on): the figure the full-batch kernel's duration is to be read against
-    eng.set_env_groups(1)
-    barrier()
-    t_g = time.perf_counter()
-    for _ in range(steps):
-        eng.step_device()
-    barrier()
-    one_group_ms = (time.perf_counter() - t_g) / steps * 1e3
-    eng.set_env_groups(int(os.environ.get("ADCRAFT_STREAM_GROUPS", "0")))      # (back to the engine's choice, or the environment's)
-    # kernel times: a separate, UNTIMED pass of the same length with HIP events around every step (four event records per step
-    # keep a step's small tail kernels from overlapping the next step's launch: ~16 us of every step) ...
-    eng.profile_enable(True, every=1)
-    eng.profile_read()
-    for _ in range(steps):
-        eng.step_device()
-    barrier()
-    kernel_ms, launches = eng.profile_read()
-    eng.profile_enable(False)
-    # ... and the timed region itself records no event at all
+    if full:
+        # where the engine runs the step as env groups on several streams, the same K steps as ONE group (the schedule the kernel
+        # times below are taken on): the figure the full-batch kernel's duration is to be read against
+        eng.set_env_groups(1)
+        barrier()
+        t_g = time.perf_counter()
+        for _ in range(steps):
+            eng.step_device()
+        barrier()
+        one_group_ms = (time.perf_counter() - t_g) / steps * 1e3
+        eng.set_env_groups(int(os.environ.get("ADCRAFT_STREAM_GROUPS", "0")))      # (back to the engine's choice, or the environment's)
+        # kernel times: a separate, UNTIMED pass of the same length with HIP events around every step (four event records per step
+        # keep a step's small tail kernels from overlapping the next step's launch: ~16 us of every step) ...
+        eng.profile_enable(True, every=1)
+        eng.profile_read()
+        for _ in range(steps):
+            eng.step_device()
+        barrier()
+        kernel_ms, launches = eng.profile_read()
+        eng.profile_enable(False)
+    restore_set_up_state(eng, rng0, planes, drift)
+    warm_up()
+    # the timed region itself records no event (but the pair around it)
     eng.metrics_reset()
     records_before = eng.profile_records()
     eng.comm_stats(reset=True)
@@ -189,7 +237,10 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
     region_gpu_ms = eng.region_end()
     records_in_timed_region = eng.profile_records() - records_before
     coll_calls, coll_ms_local, coll_ms_allreduce = eng.comm_stats(reset=True)
-    profit_c, ideal, ideal_pos, sc = red.metric_sums(ideal_k * steps, ideal_pos_k * steps)
+    if dump_dir is not None:
+        dump_outputs(eng.fetch(), dump_dir)
+    if full:
+        profit_c, ideal, ideal_pos, sc = red.metric_sums(ideal_k * steps, ideal_pos_k * steps)
     own_elapsed = elapsed
     elapsed = float(red.allreduce([elapsed], op="max")[0])          # the slowest rank's time
     per_rank = red.allreduce(np.eye(world)[rank] * own_elapsed)     # every rank's own time, next to the slowest
@@ -197,12 +248,6 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
     n_gpus = ranks_in_comm if red.backend == "rccl" else world
 
     units = float(world) * N * K * steps
-    b_alg = BYTES_PER_U[drift] * N * K + BYTES_PER_ENV * N            # algorithmic bytes per launch (one GPU)
-    dom = int(np.argmax(kernel_ms))              # the dominant kernel of the step
-    step_kernel = eng.step_kernel_name()         # (which of the keyword-parallel kernels the engine chose for this workload)
-    k_ms = kernel_ms[dom] / max(launches, 1)
-    achieved = b_alg / (k_ms * 1e-3) / 1e9 if launches else None
-    notes = pmc_notes(cfg_name) if dom == 0 else {}
     res = {
         "value": units / elapsed, "ms_per_step": elapsed / steps * 1e3, "steps": steps,
         "env_steps_per_s": float(world) * N * steps / elapsed, "n_gpus": n_gpus,
@@ -211,48 +256,58 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
                     f"{MAX_DAYS}-step episodes with auto-reset",
         "envs_per_gpu": N, "keywords": K,
         "clock_spin_steps": spin_steps,
-        "ms_per_step_before_clock_spin": unspun_ms,
-        "env_groups": {"timed_region": groups, "profiled_pass": 1, "ms_per_step_as_one_group": one_group_ms,
-                       "note": (f"the timed steps (all but the first, which follows a barrier) ran as {groups} contiguous env groups of {N // groups} envs, each on its own HIP stream "
-                                "(adc_engine_env_groups): one group's small kernels run under another's keyword-parallel pass and consecutive "
-                                "steps of different groups overlap, so ms_per_step can be BELOW roofline.kernel_ms - that is the duration "
-                                "of the kernel launched over all envs at once, as the profiled pass (always one group) launches it. "
-                                "ADCRAFT_STREAM_GROUPS=1 runs the timed region the same way") if groups > 1 else
-                               "one launch per kernel over all envs, in the timed region as in the profiled pass"},
         "timed_region": {"host_ms_per_step": own_elapsed / steps * 1e3, "gpu_ms_per_step": region_gpu_ms / steps,
                          "method": "host clock between two barriers (the contract's figure) | one HIP event pair on the engine's stream "
                                    "around the same region"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                     "traffic": notes.get("hbm_bytes_per_launch"),
-                     "traffic_source": (notes.get("source_note") if notes.get("hbm_bytes_per_launch") else notes.get("stale")),
-                     "kernel": step_kernel if dom == 0 else KERNEL_NAMES[dom], "kernel_ms": k_ms, "launches": int(launches), "launches_in_timed_region": steps if groups == 1 else 1 + (steps - 1) * groups,
-                     "envs_per_launch": {"profiled_pass": N, "timed_region": N // groups},
-                     "event_records_in_timed_region": int(records_in_timed_region),
-                     "kernel_ms_method": f"HIP events on the engine's stream around every step of a separate, untimed pass of {steps} steps "
-                                         "run between the warm-up and the timed region (same process, same state; the timed region itself "
-                                         "records no event); rocprofv3 --kernel-trace --stats of the same command: profiles/",
-                     "all_kernels_ms": {n: m / max(launches, 1) for n, m in zip((step_kernel,) + KERNEL_NAMES[1:], kernel_ms)},
-                     "algorithmic_bytes_per_launch": b_alg},
     }
-    valu = notes.get("valu")
-    if valu and launches:
-        # the bound that actually binds on dense keyword sets: VALU issue.  Instruction count: builder-side PMC (see `source`);
-        # time: live, this run.  peak = one wave64 instruction per 2 cycles per SIMD-32 at 2.4 GHz - reachable only by the
-        # full-rate opcodes (profiles/r02_issue_rates.md: compares, converts, min/max, integer multiplies cost 4 cycles)
-        lane_ops = valu["wave_instructions_per_launch"] * 64.0 / (k_ms * 1e-3)
-        res["roofline_valu"] = {"bound": "valu", "achieved": lane_ops, "peak": VALU_PEAK_LANE_OPS, "unit": "lane-instructions/s",
-                                "frac": lane_ops / VALU_PEAK_LANE_OPS,
-                                "peak_4cycle": VALU_PEAK_4CYCLE_LANE_OPS, "frac_4cycle": lane_ops / VALU_PEAK_4CYCLE_LANE_OPS,
-                                "peaks": "peak: one wave64 instruction per 2 cycles per SIMD (packed / pure add-fma streams only); peak_4cycle: "
-                                         "per 4 cycles - what compares, converts, min/max, integer multiplies and selects cost, i.e. the rate "
-                                         "this kernel's instruction mix can reach (profiles/r02_issue_rates.md)",
-                                "kernel": step_kernel, "kernel_ms": k_ms,
-                                "valu_wave_instructions_per_launch": valu["wave_instructions_per_launch"],
-                                "valu_lane_instructions_per_auction": valu.get("valu_lane_instructions_per_auction"),
-                                "source": "instruction count: " + str(notes.get("source_note")) + "; kernel time: HIP events in this run"}
-    elif notes.get("stale"):
-        res["roofline_valu"] = {"bound": "valu", "achieved": None, "frac": None, "note": notes["stale"]}
+    if full:
+        b_alg = BYTES_PER_U[drift] * N * K + BYTES_PER_ENV * N            # algorithmic bytes per launch (one GPU)
+        dom = int(np.argmax(kernel_ms))              # the dominant kernel of the step
+        step_kernel = eng.step_kernel_name()         # (which of the keyword-parallel kernels the engine chose for this workload)
+        k_ms = kernel_ms[dom] / max(launches, 1)
+        achieved = b_alg / (k_ms * 1e-3) / 1e9 if launches else None
+        notes = pmc_notes(cfg_name) if dom == 0 else {}
+        res.update({
+            "ms_per_step_before_clock_spin": unspun_ms,
+            "env_groups": {"timed_region": groups, "profiled_pass": 1, "ms_per_step_as_one_group": one_group_ms,
+                           "note": (f"the timed steps (all but the first, which follows a barrier) ran as {groups} contiguous env groups of {N // groups} envs, each on its own HIP stream "
+                                    "(adc_engine_env_groups): one group's small kernels run under another's keyword-parallel pass and consecutive "
+                                    "steps of different groups overlap, so ms_per_step can be BELOW roofline.kernel_ms - that is the duration "
+                                    "of the kernel launched over all envs at once, as the profiled pass (always one group) launches it. "
+                                    "ADCRAFT_STREAM_GROUPS=1 runs the timed region the same way") if groups > 1 else
+                                   "one launch per kernel over all envs, in the timed region as in the profiled pass"},
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                         "traffic": notes.get("hbm_bytes_per_launch"),
+                         "traffic_source": (notes.get("source_note") if notes.get("hbm_bytes_per_launch") else notes.get("stale")),
+                         "kernel": step_kernel if dom == 0 else KERNEL_NAMES[dom], "kernel_ms": k_ms, "launches": int(launches), "launches_in_timed_region": steps if groups == 1 else 1 + (steps - 1) * groups,
+                         "envs_per_launch": {"profiled_pass": N, "timed_region": N // groups},
+                         "event_records_in_timed_region": int(records_in_timed_region),
+                         "kernel_ms_method": f"HIP events on the engine's stream around every step of a separate, untimed pass of {steps} steps "
+                                             "run before the timed region (same process; the engine is then put back to its state after the "
+                                             "set-up and warmed up again; the timed region itself records no event); rocprofv3 --kernel-trace "
+                                             "--stats of the same command: profiles/",
+                         "all_kernels_ms": {n: m / max(launches, 1) for n, m in zip((step_kernel,) + KERNEL_NAMES[1:], kernel_ms)},
+                         "algorithmic_bytes_per_launch": b_alg},
+        })
+        valu = notes.get("valu")
+        if valu and launches:
+            # the bound that actually binds on dense keyword sets: VALU issue.  Instruction count: builder-side PMC (see `source`);
+            # time: live, this run.  peak = one wave64 instruction per 2 cycles per SIMD-32 at 2.4 GHz - reachable only by the
+            # full-rate opcodes (profiles/r02_issue_rates.md: compares, converts, min/max, integer multiplies cost 4 cycles)
+            lane_ops = valu["wave_instructions_per_launch"] * 64.0 / (k_ms * 1e-3)
+            res["roofline_valu"] = {"bound": "valu", "achieved": lane_ops, "peak": VALU_PEAK_LANE_OPS, "unit": "lane-instructions/s",
+                                    "frac": lane_ops / VALU_PEAK_LANE_OPS,
+                                    "peak_4cycle": VALU_PEAK_4CYCLE_LANE_OPS, "frac_4cycle": lane_ops / VALU_PEAK_4CYCLE_LANE_OPS,
+                                    "peaks": "peak: one wave64 instruction per 2 cycles per SIMD (packed / pure add-fma streams only); peak_4cycle: "
+                                             "per 4 cycles - what compares, converts, min/max, integer multiplies and selects cost, i.e. the rate "
+                                             "this kernel's instruction mix can reach (profiles/r02_issue_rates.md)",
+                                    "kernel": step_kernel, "kernel_ms": k_ms,
+                                    "valu_wave_instructions_per_launch": valu["wave_instructions_per_launch"],
+                                    "valu_lane_instructions_per_auction": valu.get("valu_lane_instructions_per_auction"),
+                                    "source": "instruction count: " + str(notes.get("source_note")) + "; kernel time: HIP events in this run"}
+        elif notes.get("stale"):
+            res["roofline_valu"] = {"bound": "valu", "achieved": None, "frac": None, "note": notes["stale"]}
     if world > 1:
         res["ms_per_step_by_rank"] = [float(x) / steps * 1e3 for x in per_rank]
     if with_collective or collective_error:
@@ -268,11 +323,12 @@ def run_config(cfg_name, args, rank, world, local_rank, steps, warmup, with_cpu_
         }
         if collective_error:
             res["collective"] = {"error": collective_error}
-    akncp_ncp = D.episode_metrics(profit_c, ideal, ideal_pos, sc)
-    res["episode_metric"] = {"AKNCP": akncp_ncp["AKNCP"], "NCP": akncp_ncp["NCP"], "profit_dollars": akncp_ncp["profit"],
-                             "env_steps": akncp_ncp["env_steps"], "episodes": akncp_ncp["episodes"],
-                             "note": "synthetic uniform bids, not a trained agent; envs pooled by keyword index"}
-    if with_cpu_baseline:
+    if full:
+        akncp_ncp = D.episode_metrics(profit_c, ideal, ideal_pos, sc)
+        res["episode_metric"] = {"AKNCP": akncp_ncp["AKNCP"], "NCP": akncp_ncp["NCP"], "profit_dollars": akncp_ncp["profit"],
+                                 "env_steps": akncp_ncp["env_steps"], "episodes": akncp_ncp["episodes"],
+                                 "note": "synthetic uniform bids, not a trained agent; envs pooled by keyword index"}
+    if full and with_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg_name, planes, K, args.cpu_seconds)
     red.close()
     if collective_alone and world == 1 and collective_error is None:
@@ -350,14 +406,15 @@ def run_rank(args):
     line_out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
     main_cfg = args.config or ("cfg2" if world == 1 else "cfg4")
-    also_cfgs = [] if args.no_also or args.config else (["cfg3", "cfg4", "cfg5"] if world == 1 else ["cfg5"])
+    also_cfgs = [] if not args.full or args.no_also or args.config else (["cfg3", "cfg4", "cfg5"] if world == 1 else ["cfg5"])
     main = run_config(main_cfg, args, rank, world, local_rank, args.steps, args.warmup, with_cpu_baseline=(world == 1 and rank == 0 and not args.no_cpu_baseline),
-                      collective_alone=(args.config == "cfg4" and not args.no_collective_alone))
+                      collective_alone=(args.config == "cfg4" and not args.no_collective_alone), full=args.full,
+                      dump_dir=args.dump_outputs if rank == 0 else None)
     also = {}
     for c in also_cfgs:
         # (cfg4 at N = 1: the N > 1 workload's per-GPU shard - with its collective, on a one-rank communicator, so that its cost is on record)
         r = run_config(c, args, rank, world, local_rank, max(60 if c == "cfg4" else 50, min(args.steps, 100)), max(10, min(args.warmup, 20)),
-                       with_cpu_baseline=False, collective_alone=(c == "cfg4" and not args.no_collective_alone))
+                       with_cpu_baseline=False, collective_alone=(c == "cfg4" and not args.no_collective_alone), full=True)
         also[c] = {k: r[k] for k in ("value", "ms_per_step", "steps", "workload", "roofline", "episode_metric", "collective", "timed_region",
                                      "clock_spin_steps", "ms_per_step_before_clock_spin", "ms_per_step_by_rank", "env_groups") if k in r}
         if "roofline_valu" in r:
@@ -376,16 +433,15 @@ def run_rank(args):
                                       "(adc_engine_metrics_allreduce)") if world > 1 else "none (single GPU)",
                        # N = 1 measures BASELINE configs[1] (cfg2); N > 1 measures the 8-GPU config's per-GPU shard (cfg4):
                        # the one-GPU point of that weak-scaling curve is also.cfg4.value of the N = 1 line
-                       "weak_scaling_reference": "also.cfg4.value of the N=1 line (same per-GPU shard as the N>1 runs)"},
+                       "weak_scaling_reference": "also.cfg4.value of the N=1 --full line (same per-GPU shard as the N>1 runs)"},
             "env_steps_per_s": main["env_steps_per_s"],
-            "roofline": main["roofline"],
         }
-        for k in ("timed_region", "clock_spin_steps", "ms_per_step_before_clock_spin", "env_groups", "ms_per_step_by_rank", "collective", "roofline_valu", "episode_metric", "cpu_baseline"):
+        for k in ("roofline", "timed_region", "clock_spin_steps", "ms_per_step_before_clock_spin", "env_groups", "ms_per_step_by_rank", "collective", "roofline_valu", "episode_metric", "cpu_baseline"):
             if k in main:
                 line[k] = main[k]
         if also:
             line["also"] = also
-        if world == 1 and not args.no_also and not args.config:
+        if args.full and world == 1 and not args.no_also and not args.config:
             line["host_step"] = host_step(local_rank)
         print(json.dumps(line), file=line_out, flush=True)
 
@@ -464,11 +520,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default=None, help="measure only this config (cfg2, cfg3, cfg4, cfg5) instead of the contract's workload")
     ap.add_argument("--budget", type=float, default=1.0e9, help="per-env daily budget in dollars (default: non-binding)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary configs")
+    ap.add_argument("--full", action="store_true", help="also what the headline figure does not need: the passes behind roofline, "
+                    "roofline_valu, env_groups and ms_per_step_before_clock_spin, the episode metric, the CPU baseline, the configs "
+                    "under also and host_step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last one "
+                    "as DIR/<name>.npy (float32 / float64; a fixed sample of env rows where they exceed 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary configs")
     ap.add_argument("--cpu-seconds", type=float, default=14.0)
-    ap.add_argument("--spin-seconds", type=float, default=0.25, help="untimed steps for this long after the warm-up, so that a short timed "
-                    "region does not start on ramping clocks (0: none)")
+    ap.add_argument("--spin-seconds", type=float, default=0.25, help="untimed steps for this long after the set-up (undone before the "
+                    "warm-up), so that a short timed region does not start on ramping clocks (0: none)")
     ap.add_argument("--no-collective-alone", action="store_true", help="N = 1: do not bring up the one-rank RCCL communicator for cfg4")
     ap.add_argument("--rehearse", action="store_true", help="no GPU work: launch, id hand-over and reduction only (CPU test)")
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)

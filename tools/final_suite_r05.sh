@@ -20,19 +20,19 @@ json.dump(out, open("profiles/pmc_traffic.json", "w"), indent=1)     # (on the b
 PY
 echo "pmc done"
 # the driver's command (its shape: --steps 20 --warmup 5), the default invocation, then the same workloads alone under the kernel trace
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_shape.json 2> $OUT/bench.err || exit 1
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2>> $OUT/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_shape.json 2> $OUT/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2>> $OUT/bench.err || exit 1
 echo "bench done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg2 -o kt -- python3 bench.py --no-also --no-cpu-baseline > $OUT/bench_cfg2_under_rocprof.json 2> $OUT/kt_cfg2.err || exit 1
-ADCRAFT_STREAM_GROUPS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg2_one_group -o kt -- python3 bench.py --no-also --no-cpu-baseline > $OUT/bench_cfg2_one_group_under_rocprof.json 2> $OUT/kt_cfg2_one_group.err || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg3 -o kt -- python3 bench.py --config cfg3 --no-cpu-baseline > $OUT/bench_cfg3_under_rocprof.json 2> $OUT/kt_cfg3.err || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg4 -o kt -- python3 bench.py --config cfg4 --no-cpu-baseline --steps 120 > $OUT/bench_cfg4_under_rocprof.json 2> $OUT/kt_cfg4.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg2 -o kt -- python3 bench.py --full --no-also --no-cpu-baseline > $OUT/bench_cfg2_under_rocprof.json 2> $OUT/kt_cfg2.err || exit 1
+ADCRAFT_STREAM_GROUPS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg2_one_group -o kt -- python3 bench.py --full --no-also --no-cpu-baseline > $OUT/bench_cfg2_one_group_under_rocprof.json 2> $OUT/kt_cfg2_one_group.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg3 -o kt -- python3 bench.py --full --config cfg3 --no-cpu-baseline > $OUT/bench_cfg3_under_rocprof.json 2> $OUT/kt_cfg3.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_cfg4 -o kt -- python3 bench.py --full --config cfg4 --no-cpu-baseline --steps 120 > $OUT/bench_cfg4_under_rocprof.json 2> $OUT/kt_cfg4.err || exit 1
 echo "kernel traces done"
 
 rm -rf $OUT/pmc/*_fetch $OUT/pmc/*_write $OUT/pmc/*_sq $OUT/kt_cfg2/*kernel_trace.csv $OUT/kt_cfg2_one_group/*kernel_trace.csv $OUT/kt_cfg3/*kernel_trace.csv $OUT/kt_cfg4/*kernel_trace.csv
 fi
 if [ $PART = timings ]; then
-for b in 1000 10 1; do timeout -k 10 200 python3 bench.py --config cfg2 --budget $b --no-cpu-baseline > $OUT/bench_budget$b.json 2>> $OUT/bench.err || exit 1; done
+for b in 1000 10 1; do timeout -k 10 200 python3 bench.py --full --config cfg2 --budget $b --no-cpu-baseline > $OUT/bench_budget$b.json 2>> $OUT/bench.err || exit 1; done
 timeout -k 10 200 python3 tools/exp_binding.py > $OUT/binding.txt 2>&1 || exit 1
 timeout -k 10 200 python3 tools/exp_binding_wide.py > $OUT/binding_wide.txt 2>&1 || exit 1
 timeout -k 10 400 python3 tools/exp_binding_wide_float.py > $OUT/binding_wide_float.txt 2>&1 || exit 1

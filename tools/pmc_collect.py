@@ -24,7 +24,7 @@ acc = collections.defaultdict(list)
 for name, counters in PASSES.items():
     d = os.path.join(out, f"{cfg}_{name}")
     cmd = ["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", "pmc", "--", "python3", "bench.py", "--config", cfg,
-           "--steps", "12", "--warmup", "2", "--spin-seconds", "0", "--no-cpu-baseline"]
+           "--steps", "12", "--warmup", "2", "--spin-seconds", "0", "--no-cpu-baseline", "--full"]
     with open(os.path.join(out, f"{cfg}_{name}.log"), "w") as log:
         # (one env group: every dispatch of the kernel is the full batch - the launch `roofline.kernel_ms` and the algorithmic bytes are per)
         subprocess.check_call(cmd, stdout=log, stderr=subprocess.STDOUT, env=dict(os.environ, ADCRAFT_STREAM_GROUPS="1"))

@@ -20,7 +20,7 @@ PASSES = {"sq": ["SQ_WAVES", "SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_WAVE_CY
 acc = collections.defaultdict(list)
 for name, counters in PASSES.items():
     d = os.path.join(out, name)
-    cmd = ["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", "pmc", "--", "python3", "bench.py", *bench_args]
+    cmd = ["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", d, "-o", "pmc", "--", "python3", "bench.py", "--full", *bench_args]
     with open(os.path.join(out, f"{name}.log"), "w") as log:
         subprocess.check_call(cmd, stdout=log, stderr=subprocess.STDOUT)
     for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):

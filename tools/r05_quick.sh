@@ -14,5 +14,5 @@ for v in product "$@"; do
   done
 done
 unset ADCRAFT_HIP_LIB ADCRAFT_ALLOW_STALE_LIB
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit 1
 python3 tools/bench_summary.py $OUT/bench.json

@@ -160,6 +160,7 @@ def lib():
         "adc_auction_word_brackets": ([f32, f32, f32, f32, vp], C.c_int),
         "adc_check_win_brackets": ([i64, vp, vp, vp, vp, vp, vp, vp], i64),
         "adc_sample_random_keyword": ([C.c_uint64, C.c_uint32, C.c_uint32, vp], C.c_int),
+        "adc_explicit_curve_host": ([C.c_uint64, C.c_uint32, i32, i32, f32, f32, f32, vp, i32, vp, vp, vp], C.c_int),
         "adc_debug_win_brackets_device": ([C.c_int, i64, vp, vp, vp, vp, vp], C.c_int),
         "adc_debug_philox_device": ([C.c_int, i64, vp, vp, vp], C.c_int),
         "adc_debug_walk_stats": ([vp, vp, C.c_int], C.c_int),

@@ -42,6 +42,8 @@
 //        flat observations/actions, nth_price_auction.
 //   parts/kernels_policy.inc      the callers of the step on the device: the zero-margin agent, the per-step ideal profit on
 //        the curves' contender lists (k_curve_contenders, k_ideal_from_contenders), the oracle bidder, per-env AKNCP / NCP.
+//   parts/kernel_explicit_curves.inc  the bid curves and ideal profit of EXPLICIT keywords (k_explicit_curves: the two middle
+//        normals of a keyword's cost samples by a radix select; k_explicit_curve_points); the policy kernels read them too.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //
 // No CPU path exists in this library.
@@ -73,6 +75,7 @@ namespace adck {
 #include "parts/kernel_explicit_fast.inc"
 #include "parts/kernels_misc.inc"
 #include "parts/kernels_policy.inc"
+#include "parts/kernel_explicit_curves.inc"
 }  // namespace adck
 using namespace adck;
 

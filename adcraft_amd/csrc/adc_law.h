@@ -722,6 +722,50 @@ ADC_HD float explicit_cost(uint32_t w, float bid)
     return v < 4.4f ? v : 4.4f;
 }
 
+// ---- EXPLICIT bid curves (get_explicit_kw_bid_cpc_impressions, experiment_metrics.py:10-17) ----------------------------------
+// A keyword's curve is drawn ONCE: n standard normals (sample i = normal_from_word of word i % 4 of draw(key, i / 4, ST_METRIC, k,
+// tick)), of which only the two middle order statistics z_lo = z_((n-1)/2), z_hi = z_(n/2) are kept.  For a fixed bid b the cost
+// c(z) = clamp(mu_b + sigma_b z, 0, 4.4) is non-decreasing in z, so (c(z_lo) + c(z_hi)) / 2 is exactly np.median of the n costs
+// (src/lib.rs:54-67; mu_b = sqrt(b)/4 + 2.2, sigma_b = 1e-10 + sqrt(b)/6, float64, computed by the host once per grid point).
+// The reference draws fresh costs for every bid; here the grid's bids share one set of normals (comonotone medians, each with the
+// reference's distribution).  The words' order is taken from the values themselves (float_order_key), not from the raw bits.
+struct CurvePoint { double ir, cpc; };
+
+// an unsigned key that orders floats as their values (no NaN here: normal_from_word never returns one)
+ADC_HD uint32_t float_order_key(float f)
+{
+    const uint32_t u = float_to_bits(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+ADC_HD float float_from_order_key(uint32_t k) { return bits_to_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+ADC_HD double explicit_cost_at(double mu, double sigma, float z)
+{
+    const double c = mu + sigma * (double)z;              // (two roundings: built with -ffp-contract=off, no fma)
+    return c > 0.0 ? (c < 4.4 ? c : 4.4) : 0.0;
+}
+
+// the cost law at one grid bid (src/lib.rs:54-67): the host computes it once per grid point, in this operation order
+ADC_HD void explicit_cost_law(double bid, double &mu, double &sigma)
+{
+    const double sq = sqrt(bid);
+    mu = sq / 4.0 + 2.2;
+    sigma = 1e-10 + sq / 6.0;
+}
+
+// (ir, cpc) of one grid point.  ir is threshold_sigmoid (src/lib.rs:93-105) in float64, the operations of adc_threshold_sigmoid;
+// the exponential is the platform's (ocml on the device, libm on the host).  cpc is exact: the mean of the two middle costs.
+ADC_HD CurvePoint explicit_curve_point(float thresh, float a, float b, float z_lo, float z_hi, double bid, double mu, double sigma)
+{
+    const double halver = 2.0 + 1e-10;
+    double th = halver * (double)thresh;
+    th = (th < 0.0 ? 0.0 : (th > 1.0 ? 1.0 : th)) / halver;
+    const double r = 1.0 / (1.0 + exp(-(double)b * (bid - (double)a)));
+    double ir = (1.0 + 2.0 * th) * r - th;
+    ir = ir < 0.0 ? 0.0 : (ir > 1.0 ? 1.0 : ir);
+    return CurvePoint{ir, (explicit_cost_at(mu, sigma, z_lo) + explicit_cost_at(mu, sigma, z_hi)) * 0.5};
+}
+
 // drift coefficient: uniform(-a, a), adcraft/gymnasium_kw_env.py:132-135
 ADC_HD float drift_coeff(uint32_t w, float a) { return fma32(2.0f * a, unit_closed24(w), -a); }
 

@@ -228,7 +228,7 @@ inline PolicyView policy_group_view(const adc_engine *e, int g, int G)
     auto at = [](auto *&ptr, size_t off) { if (ptr) ptr += off; };
     at(p.ave_rpc, ok); at(p.n_rpc, ok); at(p.ave_sctr, ok); at(p.n_sctr, ok); at(p.max_bid, ok);
     at(p.key, o); at(p.tick, o);
-    at(p.curve, ok * (size_t)p.n_bids);
+    at(p.curve, ok * (size_t)p.n_bids); at(p.xcurve, ok);
     at(p.ideal, ok); at(p.best, ok); at(p.sum_ideal, ok); at(p.sum_ideal_pos, ok);
     at(p.contender, ok * (size_t)p.cont_cap); at(p.n_contenders, ok); at(p.cont_pos, ok);
     return p;
@@ -1674,12 +1674,75 @@ ADC_EXPORT int adc_engine_metrics_read(adc_engine *e, int64_t *keyword_profit_ce
     return ADC_OK;
 }
 
+namespace {
+// the bid curves exist for the two single-competitor models; the reference's estimator on the default ImplicitKeyword's bidder pool
+// sorts s x n bids and divides by n (an impression rate above 1), and no notebook uses it that way
+int curves_model_check(const adc_engine *e, const char *what)
+{
+    if (e->v.model == ADC_MODEL_IMPLICIT || e->v.model == ADC_MODEL_EXPLICIT) return ADC_OK;
+    return fail(ADC_EINVAL, std::string(what) + " is defined for IMPLICIT and EXPLICIT keywords (IMPLICIT_GENERAL: the reference's estimator "
+                                                "on a bidder pool gives impression rates above 1)");
+}
+// EXPLICIT: the grid and its cost law, [3][n_bids] = bid, mu_b, sigma_b (adc::explicit_cost_law, float64 on the host)
+std::vector<double> explicit_grid3(const double *bid_grid, int n_bids)
+{
+    std::vector<double> g(3 * (size_t)n_bids);
+    for (int i = 0; i < n_bids; ++i) {
+        g[i] = bid_grid[i];
+        adc::explicit_cost_law(bid_grid[i], g[n_bids + i], g[2 * (size_t)n_bids + i]);
+    }
+    return g;
+}
+void launch_explicit_curves(const adc_engine *e, int n_samples, const double *d_grid3, int n_bids, double *ideal_out, float4 *curve_out)
+{
+    const size_t nk = (size_t)e->v.N * e->v.K;
+    const dim3 grid(ideal_grid((long long)nk, e->num_cus)), block(kWave * kIdealWaves);
+    if (n_samples <= kCachedSamples)
+        hipLaunchKernelGGL(k_explicit_curves<true>, grid, block, 0, e->stream, e->v, n_samples, n_bids, d_grid3, d_grid3 + n_bids,
+                           d_grid3 + 2 * (size_t)n_bids, ideal_out, curve_out, (long long)nk);
+    else
+        hipLaunchKernelGGL(k_explicit_curves<false>, grid, block, 0, e->stream, e->v, n_samples, n_bids, d_grid3, d_grid3 + n_bids,
+                           d_grid3 + 2 * (size_t)n_bids, ideal_out, curve_out, (long long)nk);
+}
+// the per-step ideal on the cached curves: contender lists or (ADCRAFT_IDEAL_FULL_SCAN) the whole grid, for the engine's model
+void launch_ideal_step(const View &v, const PolicyView &p, hipStream_t st, bool full_scan)
+{
+    const size_t nk = (size_t)v.N * v.K;
+    if (v.model == ADC_MODEL_EXPLICIT) {
+        if (full_scan) hipLaunchKernelGGL(k_ideal_from_curves<ADC_MODEL_EXPLICIT>, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, v, p, v.metrics_on);
+        else hipLaunchKernelGGL(k_ideal_from_contenders<ADC_MODEL_EXPLICIT>, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, v, p, v.metrics_on);
+    } else {
+        if (full_scan) hipLaunchKernelGGL(k_ideal_from_curves<ADC_MODEL_IMPLICIT>, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, v, p, v.metrics_on);
+        else hipLaunchKernelGGL(k_ideal_from_contenders<ADC_MODEL_IMPLICIT>, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, v, p, v.metrics_on);
+    }
+}
+}  // namespace
+
 ADC_EXPORT int adc_engine_ideal_profit(adc_engine *e, int n_samples, const double *bid_grid, int n_bids, double *host_nk)
 {
     ENGINE_GUARD(e);
-    if (e->v.model != ADC_MODEL_IMPLICIT) return fail(ADC_EINVAL, "ideal profit is defined for IMPLICIT keywords");
+    if (int rc = curves_model_check(e, "ideal profit")) return rc;
     if (n_samples <= 0 || !host_nk || !bid_grid || n_bids <= 0) return fail(ADC_EINVAL, "bad arguments");
     const size_t nk = (size_t)e->v.N * e->v.K;
+    if (e->v.model == ADC_MODEL_EXPLICIT) {
+        if (n_samples > (1 << 20)) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for EXPLICIT keywords");
+        if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
+        const std::vector<double> g3 = explicit_grid3(bid_grid, n_bids);
+        double *d_out = nullptr, *d_grid = nullptr;
+        HIP_TRY(hipMalloc((void **)&d_out, nk * 8));
+        hipError_t err = hipMalloc((void **)&d_grid, g3.size() * 8);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_grid, g3.data(), g3.size() * 8, hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) {
+            launch_explicit_curves(e, n_samples, d_grid, n_bids, d_out, (float4 *)nullptr);
+            err = hipGetLastError();
+        }
+        if (err == hipSuccess) err = hipMemcpyAsync(host_nk, d_out, nk * 8, hipMemcpyDeviceToHost, e->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+        (void)hipFree(d_out);
+        (void)hipFree(d_grid);
+        HIP_TRY(err);
+        return ADC_OK;
+    }
     if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
     double *d_out = nullptr, *d_grid = nullptr;
     HIP_TRY(hipMalloc((void **)&d_out, nk * 8));
@@ -2031,8 +2094,9 @@ ADC_EXPORT int adc_engine_get_actions(adc_engine *e, float *bids_nk, float *budg
 ADC_EXPORT int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const double *bid_grid, int n_bids)
 {
     ENGINE_GUARD(e);
-    if (e->v.model != ADC_MODEL_IMPLICIT) return fail(ADC_EINVAL, "bid curves are defined for IMPLICIT keywords");
+    if (int rc = curves_model_check(e, "bid curves")) return rc;
     if (n_samples <= 0 || !bid_grid || n_bids <= 0) return fail(ADC_EINVAL, "bad arguments");
+    const bool xp = e->v.model == ADC_MODEL_EXPLICIT;
     const size_t nk = (size_t)e->v.N * e->v.K;
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (n_samples > (1 << 20)) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for cached curves");
@@ -2044,14 +2108,23 @@ ADC_EXPORT int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const d
         // contender lists: 24 bytes per distinct grid point that can be the argmax (typically half of the grid); curves with more
         // points than a list holds are evaluated on the whole grid
         const int cap = std::min(n_bids, 256);
-        if (hipMalloc(&curve, nk * n_bids * sizeof(uint2)) != hipSuccess || hipMalloc(&grid, (size_t)n_bids * 8) != hipSuccess ||
+        // (EXPLICIT: 16 bytes per keyword instead of 8 per grid point, and the grid's cost law beside the grid)
+        const size_t curve_bytes = xp ? nk * sizeof(float4) : nk * n_bids * sizeof(uint2);
+        if (hipMalloc(&curve, curve_bytes) != hipSuccess || hipMalloc(&grid, (size_t)n_bids * 8 * (xp ? 3 : 1)) != hipSuccess ||
             hipMalloc(&cont, nk * cap * sizeof(ContenderEntry)) != hipSuccess ||
             hipMalloc(&ncont, nk * sizeof(uint16_t)) != hipSuccess || hipMalloc(&cpos, nk * sizeof(uint16_t)) != hipSuccess) {
             (void)hipFree(curve); (void)hipFree(grid); (void)hipFree(cont); (void)hipFree(ncont); (void)hipFree(cpos);
             return fail(ADC_ENOMEM, "bid curves need ~30 bytes x num_envs x num_keywords x n_bids of device memory");
         }
         e->curve_allocs = {curve, grid, cont, ncont, cpos};
-        e->pol.curve = (uint2 *)curve; e->pol.grid = (double *)grid; e->pol.n_bids = n_bids;
+        if (xp) {
+            e->pol.xcurve = (float4 *)curve;
+            e->pol.grid_mu = (double *)grid + n_bids;
+            e->pol.grid_sigma = (double *)grid + 2 * (size_t)n_bids;
+        } else {
+            e->pol.curve = (uint2 *)curve;
+        }
+        e->pol.grid = (double *)grid; e->pol.n_bids = n_bids;
         e->pol.contender = (ContenderEntry *)cont; e->pol.n_contenders = (uint16_t *)ncont;
         e->pol.cont_pos = (uint16_t *)cpos; e->pol.cont_cap = cap;
         e->have_curves = true;
@@ -2059,15 +2132,24 @@ ADC_EXPORT int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const d
     e->pol.n_samples = n_samples;
     int rc = ensure_ideal_buffers(e);
     if (rc) return rc;
+    if (xp) {
+        const std::vector<double> g3 = explicit_grid3(bid_grid, n_bids);
+        HIP_TRY(hipMemcpyAsync(e->pol.grid, g3.data(), g3.size() * 8, hipMemcpyHostToDevice, e->stream));
+        launch_explicit_curves(e, n_samples, e->pol.grid, n_bids, (double *)nullptr, e->pol.xcurve);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(e->stream));       // (g3 is a host temporary)
+    } else {
     HIP_TRY(hipMemcpyAsync(e->pol.grid, bid_grid, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream));
     const int lim = ideal_bins_kept(bid_grid, n_bids);
     hipLaunchKernelGGL(k_ideal_profit, dim3(ideal_grid((long long)nk, e->num_cus)), dim3(kWave * kIdealWaves), ideal_lds_bytes(lim), e->stream, e->v, n_samples, n_bids, e->pol.grid,
                        (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, e->pol.curve, lim, (long long)nk);
     HIP_TRY(hipGetLastError());
+    }
     // which grid points can be the argmax at all (k_curve_contenders): the per-step ideal then evaluates only those
     HIP_TRY(hipMemsetAsync(e->pol.cont_pos, 0, nk * sizeof(uint16_t), e->stream));
     if (n_bids <= kContenderLines) {
-        hipLaunchKernelGGL(k_curve_contenders, dim3((unsigned)nk), dim3(kWave), sizeof(ContenderScratch), e->stream, e->v, e->pol);
+        if (xp) hipLaunchKernelGGL(k_curve_contenders<ADC_MODEL_EXPLICIT>, dim3((unsigned)nk), dim3(kWave), sizeof(ContenderScratch), e->stream, e->v, e->pol);
+        else hipLaunchKernelGGL(k_curve_contenders<ADC_MODEL_IMPLICIT>, dim3((unsigned)nk), dim3(kWave), sizeof(ContenderScratch), e->stream, e->v, e->pol);
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemsetAsync(e->pol.n_contenders, 0xFF, nk * sizeof(uint16_t), e->stream));       // kContenderAll: the whole grid
@@ -2081,6 +2163,19 @@ ADC_EXPORT int adc_engine_bid_curves_fetch(adc_engine *e, double *impression_rat
     ENGINE_GUARD(e);
     if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
     const size_t n = (size_t)e->v.N * e->v.K * e->pol.n_bids;
+    if (e->v.model == ADC_MODEL_EXPLICIT) {          // the points evaluated on the device, by the function every ideal kernel calls
+        double *d = nullptr;
+        if (hipMalloc((void **)&d, 2 * n * 8) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc failed");
+        const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)e->num_cus * 64));
+        hipLaunchKernelGGL(k_explicit_curve_points, dim3(blocks), dim3(256), 0, e->stream, e->v, e->pol, d, d + n);
+        hipError_t err = hipGetLastError();
+        if (err == hipSuccess && impression_rate_host) err = hipMemcpyAsync(impression_rate_host, d, n * 8, hipMemcpyDeviceToHost, e->stream);
+        if (err == hipSuccess && cpc_host) err = hipMemcpyAsync(cpc_host, d + n, n * 8, hipMemcpyDeviceToHost, e->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+        (void)hipFree(d);
+        HIP_TRY(err);
+        return ADC_OK;
+    }
     std::vector<uint2> packed(n);
     HIP_TRY(hipMemcpyAsync(packed.data(), e->pol.curve, n * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2114,11 +2209,9 @@ int ideal_step_chained(adc_engine *e)
     if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
     const bool full_scan = e->ideal_full_scan;
     const int rc = launch_chained(e, [&](const View &v, const PolicyView &p, hipStream_t st, float *, float *) {
-        const size_t nk = (size_t)v.N * v.K;
         // the reference evaluates env.keyword_params as they stand before the step, i.e. with the last update_keywords applied
         if (v.drift_on) hipLaunchKernelGGL(k_materialize_drift, dim3(v.N), dim3(256), 0, st, v);
-        if (full_scan) hipLaunchKernelGGL(k_ideal_from_curves, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, v, p, v.metrics_on);
-        else hipLaunchKernelGGL(k_ideal_from_contenders, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, v, p, v.metrics_on);
+        launch_ideal_step(v, p, st, full_scan);
     });
     if (!rc && e->v.drift_on) e->drift_applied = true;
     return rc;
@@ -2143,8 +2236,7 @@ ADC_EXPORT int adc_engine_ideal_step(adc_engine *e, double *ideal_host_nk, int32
     const size_t nk = (size_t)e->v.N * e->v.K;
     // the reference evaluates env.keyword_params as they stand before the step, i.e. with the last update_keywords applied
     if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
-    if (e->ideal_full_scan) hipLaunchKernelGGL(k_ideal_from_curves, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, e->stream, e->v, e->pol, e->v.metrics_on);
-    else hipLaunchKernelGGL(k_ideal_from_contenders, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, e->stream, e->v, e->pol, e->v.metrics_on);
+    launch_ideal_step(e->v, e->pol, e->stream, e->ideal_full_scan);
     HIP_TRY(hipGetLastError());
     if (ideal_host_nk) HIP_TRY(hipMemcpyAsync(ideal_host_nk, e->pol.ideal, nk * 8, hipMemcpyDeviceToHost, e->stream));
     if (best_index_host_nk) HIP_TRY(hipMemcpyAsync(best_index_host_nk, e->pol.best, nk * 4, hipMemcpyDeviceToHost, e->stream));

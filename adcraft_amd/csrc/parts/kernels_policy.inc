@@ -36,6 +36,10 @@ struct PolicyView {
     uint16_t *n_contenders;
     uint16_t *cont_pos;
     int cont_cap;
+    // EXPLICIT keywords (k_explicit_curves): instead of `curve`, per keyword {z_lo, z_hi, impression intercept, impression slope}
+    // (16 bytes, [N*K]) and per grid point the cost law's mu_b, sigma_b ([n_bids]); every point is recomputed from them
+    float4 *xcurve;
+    double *grid_mu, *grid_sigma;
 };
 constexpr unsigned short kContenderAll = 0xFFFFu;
 constexpr double kMarginMax = 1.0e6;          // margins (sctr x rev_mean, dollars) beyond this evaluate the whole grid
@@ -132,9 +136,27 @@ __global__ __launch_bounds__(256) void k_agent_step(View v, PolicyView p, const 
     }
 }
 
+struct CurveLine { double s, c; };          // slope = impression rate, zero crossing = cpc
+// an EXPLICIT keyword's cached curve: every kernel reads its points through at(), i.e. adc::explicit_curve_point
+struct ExplicitCurve {
+    float thresh, a, b, z_lo, z_hi;
+    const double *grid, *mu, *sigma;
+    __device__ __forceinline__ CurveLine at(int bi) const
+    {
+        const adc::CurvePoint q = adc::explicit_curve_point(thresh, a, b, z_lo, z_hi, grid[bi], mu[bi], sigma[bi]);
+        return CurveLine{q.ir, q.cpc};
+    }
+};
+__device__ __forceinline__ ExplicitCurve explicit_curve(const View &v, const PolicyView &p, size_t o)
+{
+    const float4 c = p.xcurve[o];
+    return ExplicitCurve{v.imp_thresh, c.z, c.w, c.x, c.y, p.grid, p.grid_mu, p.grid_sigma};
+}
+
 // get_max_expected_bid_profits (experiment_metrics.py:40-61) for the CURRENT parameters against the cached curves:
 // profit(b) = max(vol_mean * IR(b) * bctr * (sctr * rev_mean - cpc(b)), 0); ideal = max(0, max_b), best = argmax_b
 // (first index of the maximum, as np.argmax).  One wavefront per keyword.
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_ideal_from_curves(View v, PolicyView p, int accumulate)
 {
     const int lane = threadIdx.x & 63;
@@ -143,13 +165,22 @@ __global__ __launch_bounds__(256) void k_ideal_from_curves(View v, PolicyView p,
     const int env = (int)(o / v.K), k = (int)(o - (size_t)env * v.K);
     const double vol_mean = param_at(v, ADC_P_VOL_MEAN, env, k), bctr = param_at(v, ADC_P_BCTR, env, k);
     const double margin = (double)param_at(v, ADC_P_SCTR, env, k) * (double)param_at(v, ADC_P_REV_MEAN, env, k);
+    double best = -1.0;
+    int best_i = 0x7FFFFFFF;
+    if constexpr (MODEL == ADC_MODEL_EXPLICIT) {
+        const ExplicitCurve cv = explicit_curve(v, p, o);
+        for (int bi = lane; bi < p.n_bids; bi += kWave) {
+            const CurveLine l = cv.at(bi);
+            double pr = vol_mean * l.s * bctr * (margin - l.c);
+            pr = pr > 0.0 ? pr : 0.0;
+            if (pr > best) { best = pr; best_i = bi; }
+        }
+    } else {
     const uint2 *curve = p.curve + o * p.n_bids;
     const double n_samples = (double)p.n_samples;
     // idx / n: a power-of-two n (the notebooks' 2048) divides exactly by multiplying with its reciprocal
     const bool pow2 = (p.n_samples & (p.n_samples - 1)) == 0;
     const double inv_n = 1.0 / n_samples;
-    double best = -1.0;
-    int best_i = 0x7FFFFFFF;
     // HBM-bound stream of 8 bytes per grid point: every lane issues all the loads of a 320-point chunk before it
     // computes (5 x 512 B per wavefront in flight; one load at a time reached 2.9 TB/s)
     constexpr int kPer = 5;
@@ -172,6 +203,7 @@ __global__ __launch_bounds__(256) void k_ideal_from_curves(View v, PolicyView p,
             pr = pr > 0.0 ? pr : 0.0;
             if (pr > best) { best = pr; best_i = bi; }      // a lane's indices ascend: keeps its first maximum
         }
+    }
     }
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) {
@@ -210,7 +242,6 @@ __global__ __launch_bounds__(256) void k_ideal_from_curves(View v, PolicyView p,
 // between two sampled competitor bids: same count, same sum) can only be won by their FIRST point (strict comparison): the
 // later ones are dropped.  No positive profit -> index 0, as the scan's.  A margin outside [0, kMarginMax] (or not finite), or a
 // curve with more distinct lines than the lists hold -> the whole grid.
-struct CurveLine { double s, c; };          // slope = impression rate, zero crossing = cpc
 
 __device__ __forceinline__ CurveLine curve_line(uint2 pt, double n_samples, double inv_n, bool pow2)
 {
@@ -255,17 +286,58 @@ struct ContenderScratch {
 };
 static_assert(sizeof(ContenderScratch) <= 7 * 1280, "k_curve_contenders: seven LDS blocks per wavefront");
 
+template <int MODEL>
 __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     ContenderScratch &w = *reinterpret_cast<ContenderScratch *>(lds_raw);
     const int lane = threadIdx.x;
     const size_t o = blockIdx.x;
+    constexpr double kRel = 1.0e-9, kAbs = 1.0e-12;
+    const unsigned long long lt = lanemask_lt();
+
+    int n_lines = 0;
+    if constexpr (MODEL == ADC_MODEL_EXPLICIT) {
+        // the distinct lines with a positive slope, in grid order.  The elimination below needs ascending slopes: a curve whose impression
+        // rate ever falls along the grid (a negative slope parameter, an unsorted grid, rounding) is evaluated on the whole grid
+        const ExplicitCurve cv = explicit_curve(v, p, o);
+        CurveLine ls[kContenderChunks];
+#pragma unroll
+        for (int ch = 0; ch < kContenderChunks; ++ch) {
+            const int b = ch * kWave + lane;
+            ls[ch] = b < p.n_bids ? cv.at(b) : CurveLine{0.0, 0.0};
+        }
+        bool falls = false;
+        double carry_s = 0.0, carry_c = 0.0;            // the previous chunk's last line
+#pragma unroll
+        for (int ch = 0; ch < kContenderChunks; ++ch) {
+            const int b = ch * kWave + lane;
+            if (ch * kWave >= p.n_bids) break;                  // (wave-uniform)
+            double ps = __shfl_up(ls[ch].s, 1, kWave), pc = __shfl_up(ls[ch].c, 1, kWave);
+            if (lane == 0) { ps = carry_s; pc = carry_c; }
+            carry_s = __shfl(ls[ch].s, kWave - 1, kWave);
+            carry_c = __shfl(ls[ch].c, kWave - 1, kWave);
+            const CurveLine l = ls[ch];
+            bool keep = false;
+            if (b < p.n_bids) {
+                falls |= b > 0 && !(l.s >= ps);
+                keep = !(b > 0 && l.s == ps && l.c == pc) && l.s > 0.0 && l.c == l.c;
+            }
+            const unsigned long long m = __ballot(keep);
+            if (keep) {
+                const int at = n_lines + (int)__popcll(m & lt);
+                w.s[at] = l.s; w.c[at] = l.c; w.b[at] = (unsigned short)b;
+            }
+            n_lines += (int)__popcll(m);
+        }
+        if (__ballot(falls)) {
+            if (lane == 0) { p.cont_pos[o] = 0; p.n_contenders[o] = kContenderAll; }
+            return;
+        }
+    } else {
     const uint2 *curve = p.curve + o * p.n_bids;
     const double n_samples = (double)p.n_samples, inv_n = 1.0 / n_samples;
     const bool pow2 = (p.n_samples & (p.n_samples - 1)) == 0;
-    constexpr double kRel = 1.0e-9, kAbs = 1.0e-12;
-    const unsigned long long lt = lanemask_lt();
 
     // the distinct lines with a positive slope, in grid order (= slope order).  All of the curve's points are requested before the first is
     // used (the compaction below carries a count from chunk to chunk: chunk by chunk the loads would be five HBM round trips in a row)
@@ -276,7 +348,6 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
         pts[ch] = b < p.n_bids ? curve[b] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         pvs[ch] = b > 0 && b < p.n_bids ? curve[b - 1] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
     }
-    int n_lines = 0;
 #pragma unroll
     for (int ch = 0; ch < kContenderChunks; ++ch) {
         const int b = ch * kWave + lane;
@@ -294,6 +365,7 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
             w.s[at] = l.s; w.c[at] = l.c; w.b[at] = (unsigned short)b;
         }
         n_lines += (int)__popcll(m);
+    }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -429,12 +501,14 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
     ContenderEntry *out = p.contender + o * p.cont_cap;
     for (int r = lane; r < n_out; r += kWave) {
         const int i = w.keep[r];
-        const uint2 pt = curve[w.b[i]];
+        uint2 pt = make_uint2(0u, 0u);                          // (EXPLICIT: the point is recomputed from its grid index)
+        if constexpr (MODEL == ADC_MODEL_IMPLICIT) pt = p.curve[o * p.n_bids + w.b[i]];
         out[r] = ContenderEntry{w.lo[i], w.hi[i], pt.x, pt.y, (unsigned int)w.b[i], 0u};
     }
 }
 
 // get_max_expected_bid_profits on the lines within reach of the envelope at today's margin: one LANE per keyword
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_ideal_from_contenders(View v, PolicyView p, int accumulate)
 {
     const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -447,8 +521,12 @@ __global__ __launch_bounds__(256) void k_ideal_from_contenders(View v, PolicyVie
     const int count = p.n_contenders[o];
     double best = -1.0;
     int best_i = 0x7FFFFFFF;
+    ExplicitCurve cv{};
+    if constexpr (MODEL == ADC_MODEL_EXPLICIT) cv = explicit_curve(v, p, o);
     auto eval = [&](uint2 pt, int bi) {
-        const CurveLine l = curve_line(pt, n_samples, inv_n, pow2);
+        CurveLine l;
+        if constexpr (MODEL == ADC_MODEL_EXPLICIT) l = cv.at(bi);          // (EXPLICIT entries carry no point: recomputed from bi)
+        else l = curve_line(pt, n_samples, inv_n, pow2);
         double pr = vol_mean * l.s * bctr * (margin - l.c);          // the operation order of k_ideal_from_curves / the reference
         pr = pr > 0.0 ? pr : 0.0;
         if (pr > best) { best = pr; best_i = bi; }                   // ascending indices: keeps the first maximum
@@ -459,7 +537,10 @@ __global__ __launch_bounds__(256) void k_ideal_from_contenders(View v, PolicyVie
     const double scale = vol_mean * bctr;
     const bool plain = scale == 0.0 || (scale >= 1.0e-200 && scale <= 1.0e200);
     if (count == kContenderAll || !plain || !(margin >= 0.0 && margin <= kMarginMax)) {
-        for (int bi = 0; bi < p.n_bids; ++bi) eval(curve[bi], bi);
+        for (int bi = 0; bi < p.n_bids; ++bi) {
+            if constexpr (MODEL == ADC_MODEL_EXPLICIT) eval(make_uint2(0u, 0u), bi);
+            else eval(curve[bi], bi);
+        }
     } else {
         // (the scan's answer when nothing is positive is index 0 with profit 0: any point's clamped profit is >= 0, and a point
         // with no impressions has exactly 0 - no need to read grid point 0 itself)

@@ -379,7 +379,8 @@ class StepEngine:
 
     def ideal_profit(self, n_samples=2048, bid_grid=None):
         """max expected profit per keyword from the current parameters (experiment_metrics.py:20-61), dollars [N, K];
-        bid_grid defaults to the notebooks' np.arange(0.01, 3.00, 0.01)"""
+        bid_grid defaults to the notebooks' np.arange(0.01, 3.00, 0.01).  IMPLICIT and EXPLICIT keywords (EXPLICIT: the
+        curves of bid_curves_build, get_explicit_kw_bid_cpc_impressions' law; n_samples <= 2^20)"""
         grid = np.ascontiguousarray(np.arange(0.01, 3.00, 0.01) if bid_grid is None else bid_grid, dtype=np.float64)
         out = np.zeros((self.num_envs, self.num_keywords), dtype=np.float64)
         check(self._lib.adc_engine_ideal_profit(self._h, int(n_samples), grid.ctypes.data, grid.size, out.ctypes.data))
@@ -394,13 +395,15 @@ class StepEngine:
 
     # ---- device-resident callers of the step: per-step ideal profit and the baseline bidders --------------------
     def bid_curves_build(self, n_samples=2048, bid_grid=None):
-        """cache get_implicit_kw_bid_cpc_impressions of every keyword on the device (experiment_metrics.py:20-37)"""
+        """cache the bid curves of every keyword on the device: get_implicit_kw_bid_cpc_impressions (experiment_metrics.py:20-37,
+        8 bytes per grid point) or, for EXPLICIT keywords, get_explicit_kw_bid_cpc_impressions (:10-17: the two middle normals
+        of the n_samples cost draws and the keyword's impression parameters, 16 bytes per keyword)"""
         grid = np.ascontiguousarray(np.arange(0.01, 3.00, 0.01) if bid_grid is None else bid_grid, dtype=np.float64)
         check(self._lib.adc_engine_bid_curves_build(self._h, int(n_samples), grid.ctypes.data, grid.size))
         self._bid_grid = grid
 
     def bid_curves_fetch(self):
-        """the cached curves as host arrays (impression_rate, cpc), each [N, K, n_bids]"""
+        """the cached curves as host arrays (impression_rate, cpc), each [N, K, n_bids]: the doubles the ideal kernels evaluate"""
         nb = self._bid_grid.size
         ir = np.zeros((self.num_envs, self.num_keywords, nb), np.float64)
         cpc = np.zeros((self.num_envs, self.num_keywords, nb), np.float64)
@@ -409,7 +412,7 @@ class StepEngine:
 
     def bid_curves_contenders(self):
         """(count [N, K] (65535 = the whole grid), grid indices [N, K, cap], margin intervals [N, K, cap, 2]) of the curve points
-        the per-step ideal chooses from"""
+        the per-step ideal chooses from (IMPLICIT and EXPLICIT curves)"""
         cap = C.c_int32(0)
         check(self._lib.adc_engine_bid_curves_contenders(self._h, None, None, C.byref(cap)))
         n = np.zeros((self.num_envs, self.num_keywords), np.uint16)
@@ -418,8 +421,8 @@ class StepEngine:
         return n, ent[..., 4].astype(np.int32), ent[..., 0:2].copy().view(np.float32)
 
     def ideal_step(self, fetch=True):
-        """get_max_expected_bid_profits for the current parameters against the cached curves; with metrics enabled
-        the ideal is also accumulated.  Returns (ideal [N, K] dollars, argmax index [N, K]) or None if not fetch."""
+        """get_max_expected_bid_profits for the current parameters against the cached curves (IMPLICIT or EXPLICIT); with
+        metrics enabled the ideal is also accumulated.  Returns (ideal [N, K] dollars, argmax index [N, K]) or None if not fetch."""
         if not fetch:
             check(self._lib.adc_engine_ideal_step(self._h, None, None))
             return None
@@ -717,3 +720,15 @@ class ReplayTape:
         if self.drift is not None:
             assert self.drift.size == 3 * self.vol.size, "drift_uniforms must be [3][num_envs][num_keywords]"
             self.struct.drift_uniforms = self.drift.ctypes.data
+
+
+def explicit_curve_host(key, tick, keyword, n_samples, a, b, bid_grid, impression_thresh=0.05):
+    """the host twin of an EXPLICIT keyword's cached curve (adc_explicit_curve_host): the draws of the env stream (key, tick)
+    that bid_curves_build makes for keyword `keyword`, sorted on the CPU.  Returns (impression_rate, cpc, (z_lo, z_hi))."""
+    grid = np.ascontiguousarray(bid_grid, dtype=np.float64)
+    ir = np.zeros(grid.size, np.float64)
+    cpc = np.zeros(grid.size, np.float64)
+    z = np.zeros(2, np.float64)
+    check(_ffi.lib().adc_explicit_curve_host(int(key), int(tick), int(keyword), int(n_samples), float(impression_thresh), float(a),
+                                             float(b), grid.ctypes.data, grid.size, ir.ctypes.data, cpc.ctypes.data, z.ctypes.data))
+    return ir, cpc, (float(z[0]), float(z[1]))

@@ -88,3 +88,12 @@ def bid_curves_from_samples(competitor_bids, bid_array, n_samples=None):
 def get_implicit_kw_bid_cpc_impressions(implicit_keyword, bid_array, n_samples=2048):
     """the reference's estimator: bid curves from n_samples draws of the keyword's competitor bid"""
     return bid_curves_from_samples(implicit_keyword.sample_bids(n_samples), bid_array, n_samples)
+
+
+def get_explicit_kw_bid_cpc_impressions(explicit_keyword, bid_array, n_samples=2048):
+    """the reference's estimator for an ExplicitKeyword (experiment_metrics.py:10-17): the impression rate at every grid bid
+    and the median of n_samples sampled costs per click.  StepEngine.bid_curves_build caches the same law for every
+    keyword of an engine, with one set of draws shared by the grid's bids."""
+    impression_rate = np.array([explicit_keyword.impression_rate(b) for b in bid_array])
+    med_cost_per_bid = np.array([np.median(explicit_keyword.cost_per_buyside_click(bid, n_samples)) for bid in bid_array])
+    return impression_rate, med_cost_per_bid

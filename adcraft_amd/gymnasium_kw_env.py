@@ -27,6 +27,7 @@ import numpy as np
 
 from . import gymnasium_kw_utils as utils
 from . import _ffi
+from . import rust
 from . import spaces as _spaces
 from ._ffi import MODEL_EXPLICIT, MODEL_IMPLICIT, P_BCTR, P_SCTR, P_VOL_MEAN
 
@@ -81,7 +82,8 @@ class _Lazy:
 
 class KeywordView:
     """Read-only view of one keyword's current parameters, with the few methods experiment code calls on
-    the reference's Keyword objects (buyside_ctr, sellside_paid_ctr, sample_bids, sample_volume)."""
+    the reference's Keyword objects (buyside_ctr, sellside_paid_ctr, sample_bids, sample_volume; EXPLICIT keywords:
+    impression_rate, cost_per_buyside_click)."""
 
     def __init__(self, env, index):
         self._env, self._k = env, index
@@ -113,6 +115,20 @@ class KeywordView:
     def sample_volume(self, n=1):
         m, s = self._p()[0]
         return np.array([int(np.floor(max(self.rng.normal(m, s), 0.0) + 0.5)) for _ in range(n)])
+
+    def impression_rate(self, bid):
+        """ExplicitKeyword.impression_rate (adcraft/synthetic_kw_classes.py:541-556): rust.threshold_sigmoid with the keyword's
+        intercept and slope and the env's impression_thresh of 0.05 (gymnasium_kw_utils.py:81)"""
+        p = self._p()
+        if self._env._implicit:
+            raise AttributeError("ImplicitKeyword has no impression_rate")
+        return rust.threshold_sigmoid(bid, {"impression_thresh": 0.05, "impression_bid_intercept": p[1], "impression_slope": p[2]})
+
+    def cost_per_buyside_click(self, bid, n=1):
+        """ExplicitKeyword.cost_per_buyside_click (adcraft/synthetic_kw_classes.py:558-580): rust.cost_create, n costs"""
+        if self._env._implicit:
+            raise AttributeError("ImplicitKeyword has no cost_per_buyside_click")
+        return rust.cost_create(bid, n)
 
 
 class BiddingSimulation(_EnvBase):

@@ -341,7 +341,9 @@ int adc_engine_metrics_reset(adc_engine *e);
 int adc_engine_metrics_read(adc_engine *e, int64_t *keyword_profit_cents_k, int64_t *scalars8);
 /* ideal (max expected) profit per keyword from the CURRENT parameters, n_samples sampled competitor bids and an
  * ascending bid grid in dollars (the notebooks use np.arange(0.01, 3.00, 0.01)); experiment_metrics.py:20-61;
- * host double [N*K] */
+ * host double [N*K].  EXPLICIT keywords: the curves of adc_engine_bid_curves_build (get_explicit_kw_bid_cpc_impressions,
+ * experiment_metrics.py:10-17), n_samples <= 2^20.  IMPLICIT_GENERAL: ADC_EINVAL (the reference's estimator on a bidder
+ * pool gives impression rates above 1). */
 int adc_engine_ideal_profit(adc_engine *e, int n_samples, const double *bid_grid, int n_bids, double *host_nk);
 /* the estimator alone, on caller-supplied competitor-bid samples (cents) of one keyword: impression rate and
  * expected cpc on the given bid grid, exactly as get_implicit_kw_bid_cpc_impressions computes them
@@ -357,9 +359,13 @@ int adc_bid_curves_from_samples(int device_id, const int32_t *samples_cents, int
 
 /* impression-rate / expected-cpc curves of every keyword on `bid_grid` from n_samples sampled competitor bids
  * (get_implicit_kw_bid_cpc_impressions, experiment_metrics.py:20-37; the notebooks build them once after reset()).
- * Kept on the device as integer numerators, 8 bytes x N x K x n_bids; n_samples <= 2^20. */
+ * Kept on the device as integer numerators, 8 bytes x N x K x n_bids; n_samples <= 2^20.
+ * EXPLICIT keywords: get_explicit_kw_bid_cpc_impressions (:10-17) - impression rate = threshold_sigmoid, cpc = the median of
+ * n_samples costs, drawn once per keyword (the grid's bids share the draws) and kept as the two middle normals with the
+ * impression intercept and slope: 16 bytes x N x K, plus 24 bytes per grid point.  IMPLICIT_GENERAL: ADC_EINVAL. */
 int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const double *bid_grid, int n_bids);
-/* the cached curves to host: impression rate and expected cpc, double [N*K][n_bids] each (either may be NULL) */
+/* the cached curves to host: impression rate and expected cpc, double [N*K][n_bids] each (either may be NULL): the values
+ * the ideal kernels evaluate (EXPLICIT: computed on the device by the same function) */
 int adc_engine_bid_curves_fetch(adc_engine *e, double *impression_rate_host, double *cpc_host);
 /* get_max_expected_bid_profits (experiment_metrics.py:40-61) for the CURRENT (drifted) parameters against the cached
  * curves: max expected profit and its argmax over the grid, per keyword; host outputs may be NULL.  With metrics
@@ -368,7 +374,7 @@ int adc_engine_bid_curves_fetch(adc_engine *e, double *impression_rate_host, dou
 /* diagnostic: per keyword, the grid points that can be the argmax of the expected profit for SOME margin sctr x rev_mean, each
  * with the margin interval on which it can (found once per adc_engine_bid_curves_build; adc_engine_ideal_step evaluates only
  * the few whose interval holds the day's margin): n_nk[N*K] (0xFFFF: the whole grid is evaluated), entries_nkc6[N*K][*cap][6]
- * = {interval lo, hi (float32 bits), curve point (2 words), grid index, 0}, ascending grid indices */
+ * = {interval lo, hi (float32 bits), curve point (2 words; EXPLICIT: 0, 0), grid index, 0}, ascending grid indices */
 int adc_engine_bid_curves_contenders(adc_engine *e, uint16_t *n_nk, uint32_t *entries_nkc6, int32_t *cap);
 int adc_engine_ideal_step(adc_engine *e, double *ideal_host_nk, int32_t *best_index_host_nk);
 /* run_oracle_agent: next action := bid_grid[argmax] of the last adc_engine_ideal_step, budget as given */
@@ -467,6 +473,12 @@ int64_t adc_check_win_brackets(int64_t n, const float *bid, const float *cost_lo
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */
 int adc_sample_random_keyword(uint64_t key, uint32_t keyword, uint32_t serial, float *out8);
+/* one EXPLICIT keyword's cached bid curve, on the host: the n_samples normals adc_engine_bid_curves_build draws for keyword
+ * `keyword` of an env whose Philox key / tick are `key` / `tick` (adc_engine_get_rng_state), sorted, and the same point function
+ * (adc_law.h explicit_curve_point) on `bid_grid`.  cpc is bit-identical to the device's; ir uses the host's exp.
+ * z_mid2_out (may be NULL): the two middle normals z_lo, z_hi.  n_samples <= 2^20. */
+int adc_explicit_curve_host(uint64_t key, uint32_t tick, int32_t keyword, int32_t n_samples, float impression_thresh, float a, float b,
+                            const double *bid_grid, int32_t n_bids, double *ir_out, double *cpc_out, double *z_mid2_out);
 /* diagnostic: the stream's generator (Philox4x32, the stream's round count) evaluated on the device for n counters ctr4[n][4]
  * and keys key2[n][2] -> out4[n][4]; tests compare it with the CPU battery's generator (oracle/stream_battery.c) */
 int adc_debug_philox_device(int device_id, int64_t n, const uint32_t *ctr4, const uint32_t *key2, uint32_t *out4);

@@ -1696,7 +1696,7 @@ std::vector<double> explicit_grid3(const double *bid_grid, int n_bids)
 void launch_explicit_curves(const adc_engine *e, int n_samples, const double *d_grid3, int n_bids, double *ideal_out, float4 *curve_out)
 {
     const size_t nk = (size_t)e->v.N * e->v.K;
-    const dim3 grid(ideal_grid((long long)nk, e->num_cus)), block(kWave * kIdealWaves);
+    const dim3 grid(ideal_grid((long long)nk, e->num_cus, kIdealWaves)), block(kWave * kIdealWaves);
     if (n_samples <= kCachedSamples)
         hipLaunchKernelGGL(k_explicit_curves<true>, grid, block, 0, e->stream, e->v, n_samples, n_bids, d_grid3, d_grid3 + n_bids,
                            d_grid3 + 2 * (size_t)n_bids, ideal_out, curve_out, (long long)nk);
@@ -1715,6 +1715,21 @@ void launch_ideal_step(const View &v, const PolicyView &p, hipStream_t st, bool 
         if (full_scan) hipLaunchKernelGGL(k_ideal_from_curves<ADC_MODEL_IMPLICIT>, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, v, p, v.metrics_on);
         else hipLaunchKernelGGL(k_ideal_from_contenders<ADC_MODEL_IMPLICIT>, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, v, p, v.metrics_on);
     }
+}
+// the IMPLICIT estimator's limits (k_ideal_profit): 0, or ADC_EINVAL naming the one passed; *lim = the bins the grid keeps
+int implicit_curve_args(int n_samples, const double *bid_grid, int n_bids, int *lim)
+{
+    if (n_samples > kIdealMaxSamples) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for IMPLICIT keywords (the estimator's 32-bit sums)");
+    *lim = ideal_bins_kept(bid_grid, n_bids);
+    if (*lim == 0) return fail(ADC_EINVAL, "bid grid: every bid must be finite and at most $20.46 (2046 cents) for IMPLICIT keywords");
+    return 0;
+}
+void launch_ideal_profit(const View &v, hipStream_t st, int num_cus, int n_samples, int n_bids, const double *d_grid, const int32_t *tape,
+                         double *ideal, double *ir, double *cpc, uint2 *packed, int lim, long long n_items)
+{
+    const int waves = ideal_waves(lim);
+    hipLaunchKernelGGL(k_ideal_profit, dim3(ideal_grid(n_items, num_cus, waves)), dim3(kWave * waves), ideal_lds_bytes(lim, waves), st, v, n_samples,
+                       n_bids, d_grid, tape, ideal, ir, cpc, packed, lim, n_items);
 }
 }  // namespace
 
@@ -1743,15 +1758,16 @@ ADC_EXPORT int adc_engine_ideal_profit(adc_engine *e, int n_samples, const doubl
         HIP_TRY(err);
         return ADC_OK;
     }
+    int lim = 0;
+    if (int rc = implicit_curve_args(n_samples, bid_grid, n_bids, &lim)) return rc;
     if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
     double *d_out = nullptr, *d_grid = nullptr;
     HIP_TRY(hipMalloc((void **)&d_out, nk * 8));
     hipError_t err = hipMalloc((void **)&d_grid, (size_t)n_bids * 8);
     if (err == hipSuccess) err = hipMemcpyAsync(d_grid, bid_grid, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream);
     if (err == hipSuccess) {
-        const int lim = ideal_bins_kept(bid_grid, n_bids);
-        hipLaunchKernelGGL(k_ideal_profit, dim3(ideal_grid((long long)nk, e->num_cus)), dim3(kWave * kIdealWaves), ideal_lds_bytes(lim), e->stream, e->v, n_samples, n_bids, d_grid,
-                           (const int32_t *)nullptr, d_out, (double *)nullptr, (double *)nullptr, (uint2 *)nullptr, lim, (long long)nk);
+        launch_ideal_profit(e->v, e->stream, e->num_cus, n_samples, n_bids, d_grid, (const int32_t *)nullptr, d_out, (double *)nullptr, (double *)nullptr,
+                            (uint2 *)nullptr, lim, (long long)nk);
         err = hipGetLastError();
     }
     if (err == hipSuccess) err = hipMemcpyAsync(host_nk, d_out, nk * 8, hipMemcpyDeviceToHost, e->stream);
@@ -1762,13 +1778,17 @@ ADC_EXPORT int adc_engine_ideal_profit(adc_engine *e, int n_samples, const doubl
     return ADC_OK;
 }
 
-// the estimator alone, on caller-supplied samples of ONE keyword (pins the kernel against the reference's
-// get_implicit_kw_bid_cpc_impressions; bid grid = 1..n_bids cents)
+// the estimator alone, on caller-supplied samples (cents, >= 0) of ONE keyword and any bid grid the estimator takes (pins the kernel
+// against the reference's get_implicit_kw_bid_cpc_impressions).  Arguments are checked before any HIP call
 ADC_EXPORT int adc_bid_curves_from_samples(int device_id, const int32_t *samples_cents, int32_t n_samples, const double *bid_grid,
                                            int32_t n_bids, double *impression_rate_out, double *cpc_out)
 {
     if (!samples_cents || n_samples <= 0 || n_bids <= 0 || !bid_grid || !impression_rate_out || !cpc_out)
         return fail(ADC_EINVAL, "bad arguments");
+    int lim = 0;
+    if (int rc = implicit_curve_args(n_samples, bid_grid, n_bids, &lim)) return rc;
+    for (int32_t i = 0; i < n_samples; ++i)
+        if (samples_cents[i] < 0) return fail(ADC_EINVAL, "a negative sample (cents)");
     HIP_TRY(hipSetDevice(device_id));
     int32_t *d_s = nullptr;
     double *d_ir = nullptr, *d_cpc = nullptr, *d_grid = nullptr;
@@ -1789,9 +1809,7 @@ ADC_EXPORT int adc_bid_curves_from_samples(int device_id, const int32_t *samples
     std::memset(&v, 0, sizeof(v));
     v.N = 1; v.K = 1; v.params = d_p; v.key = d_key; v.tick = d_tick;
     v.NP = 1;
-    const int lim = ideal_bins_kept(bid_grid, n_bids);
-    hipLaunchKernelGGL(k_ideal_profit, dim3(1), dim3(kWave * kIdealWaves), ideal_lds_bytes(lim), 0, v, n_samples, n_bids, d_grid, d_s, (double *)nullptr, d_ir, d_cpc, (uint2 *)nullptr,
-                       lim, 1LL);
+    launch_ideal_profit(v, 0, 1, n_samples, n_bids, d_grid, d_s, (double *)nullptr, d_ir, d_cpc, (uint2 *)nullptr, lim, 1LL);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(fail(ADC_EHIP, "k_ideal_profit failed"));
     if (hipMemcpy(impression_rate_out, d_ir, (size_t)n_bids * 8, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(cpc_out, d_cpc, (size_t)n_bids * 8, hipMemcpyDeviceToHost) != hipSuccess)
@@ -2097,6 +2115,8 @@ ADC_EXPORT int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const d
     if (int rc = curves_model_check(e, "bid curves")) return rc;
     if (n_samples <= 0 || !bid_grid || n_bids <= 0) return fail(ADC_EINVAL, "bad arguments");
     const bool xp = e->v.model == ADC_MODEL_EXPLICIT;
+    int lim = 0;
+    if (!xp) if (int rc = implicit_curve_args(n_samples, bid_grid, n_bids, &lim)) return rc;      // (before the cached curves are touched)
     const size_t nk = (size_t)e->v.N * e->v.K;
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (n_samples > (1 << 20)) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for cached curves");
@@ -2140,9 +2160,8 @@ ADC_EXPORT int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const d
         HIP_TRY(hipStreamSynchronize(e->stream));       // (g3 is a host temporary)
     } else {
     HIP_TRY(hipMemcpyAsync(e->pol.grid, bid_grid, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream));
-    const int lim = ideal_bins_kept(bid_grid, n_bids);
-    hipLaunchKernelGGL(k_ideal_profit, dim3(ideal_grid((long long)nk, e->num_cus)), dim3(kWave * kIdealWaves), ideal_lds_bytes(lim), e->stream, e->v, n_samples, n_bids, e->pol.grid,
-                       (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, e->pol.curve, lim, (long long)nk);
+    launch_ideal_profit(e->v, e->stream, e->num_cus, n_samples, n_bids, e->pol.grid, (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr,
+                        (double *)nullptr, e->pol.curve, lim, (long long)nk);
     HIP_TRY(hipGetLastError());
     }
     // which grid points can be the argmax at all (k_curve_contenders): the per-step ideal then evaluates only those

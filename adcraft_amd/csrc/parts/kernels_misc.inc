@@ -85,33 +85,40 @@ __global__ void k_metric_columns(View v)
 }
 
 // ---- ideal (max expected) profit of a keyword, adcraft/experiment_utils/experiment_metrics.py:20-61 ------------
-// One wavefront per keyword.  n_samples competitor bids (cents) are histogrammed in LDS; for every bid b on
-// the grid 1..n_bids cents:  idx = #(samples <= b)  (searchsorted side="right", :30),  IR = idx / n (:32),
+// One wavefront per keyword.  n_samples competitor bids (cents) are histogrammed in LDS; for every bid b of the
+// grid (any order, duplicates allowed):  idx = #(samples <= b)  (searchsorted side="right", :30),  IR = idx / n (:32),
 // idx' = min(idx, n-1) (:33),  cpc = (sum of the idx'+1 smallest samples) / (idx'+1) (:34-35) - i.e. the mean
 // of the samples <= b PLUS the next larger one (the reference's off-by-one, reproduced) - and
 // profit(b) = max(vol_mean * IR * bctr * (sctr * rev_mean - cpc), 0) (:51-57); ideal = max_b (:59).
-constexpr int kIdealBins = 1024;      // cents 0..1022, last bin = everything above
-constexpr int kIdealWaves = 4;        // keywords a workgroup has in flight (one wavefront each)
+// Supported: bids up to kIdealMaxCents (a bid of 0 or less takes no sample: idx 0, cpc = the smallest sample), n_samples up to
+// kIdealMaxSamples.  The host refuses anything else (implicit_curve_args): a grid with a higher or non-finite bid is never clamped.
+constexpr int kIdealMaxCents = 2046;  // bins 0 .. lim <= 2047 kept one by one: at most 32 per lane (a lane's 32-bit occupancy mask, below)
+constexpr int kIdealMaxSamples = 1 << 20;     // the 32-bit prefix sums: n * 2047 < 2^31; the packed numerator (+ one sample <= 1e9) < 2^32
+constexpr int kIdealWaves = 4;        // keywords a workgroup has in flight (one wavefront each; fewer where four wavefronts' tables pass 64 KB)
 #ifndef IDEAL_MIN_BLOCKS
 #define IDEAL_MIN_BLOCKS 6
 #endif
-// the grid's highest bid in cents, as the kernel turns a bid into a bin, + 1: the bins kept one by one (host side: the launch's LDS)
+// the grid's highest bid in cents, as the kernel turns a bid into a bin, + 1: the bins kept one by one (host side: the launch's LDS);
+// 0 if a bid is not finite or above kIdealMaxCents
 inline int ideal_bins_kept(const double *bid_grid, int n_bids)
 {
     int b_hi = 0;
     for (int bi = 0; bi < n_bids; ++bi) {
         const double x = std::floor(bid_grid[bi] * 100.0 + 0.5);
-        int bb = x < (double)(kIdealBins - 2) ? (x > 0.0 ? (int)x : 0) : kIdealBins - 2;
+        if (!std::isfinite(x) || x > (double)kIdealMaxCents) return 0;
+        const int bb = x > 0.0 ? (int)x : 0;
         b_hi = bb > b_hi ? bb : b_hi;
     }
-    return b_hi + 1;                    // <= kIdealBins - 1
+    return b_hi + 1;                    // <= kIdealMaxCents + 1
 }
 // LDS words (4 bytes) of one wavefront's tables for `lim` bins kept: count prefix, cent prefix, next occupied bin (16-bit)
 __host__ __device__ inline int ideal_wave_words(int lim) { return 2 * (lim + 1) + (lim + 4) / 2; }
-inline unsigned ideal_grid(long long n_items, int num_cus) { return (unsigned)std::max(1LL, std::min((n_items + 8 * kIdealWaves - 1) / (8 * kIdealWaves), (long long)num_cus * 32)); }
-inline size_t ideal_lds_bytes(int lim) { return 4 * ((size_t)adc::kLogTableIntervals + 4 + (size_t)kIdealWaves * ideal_wave_words(lim)); }
+// wavefronts per workgroup: four while their tables and the log table fit in 64 KB (lim <= 1609; the notebooks' grid: lim = 300), else three
+inline int ideal_waves(int lim) { return std::min(kIdealWaves, (65536 / 4 - adc::kLogTableIntervals - 4) / ideal_wave_words(lim)); }
+inline unsigned ideal_grid(long long n_items, int num_cus, int waves) { return (unsigned)std::max(1LL, std::min((n_items + 8 * waves - 1) / (8 * waves), (long long)num_cus * 32)); }
+inline size_t ideal_lds_bytes(int lim, int waves) { return 4 * ((size_t)adc::kLogTableIntervals + 4 + (size_t)waves * ideal_wave_words(lim)); }
 
-// A wavefront per keyword, kIdealWaves of them per workgroup, each walking keywords blockIdx.x * kIdealWaves + wave, + the grid's
+// A wavefront per keyword, ideal_waves(lim) of them per workgroup, each walking keywords blockIdx.x * chunk + wave, + the wave count
 // stride, ... (round 4 launched one 64-lane workgroup per keyword with 11 KB of LDS: 14 wavefronts per CU, 16.7 million workgroups on
 // cfg3, half of which found a keyword without volume and left).  A sample is only ever looked at as "count and sum of the samples
 // <= b" and "the next larger one" for the bids b of the grid, so the bins 0 .. lim = (the grid's highest bid in cents) + 1 are kept
@@ -124,20 +131,21 @@ __global__ __launch_bounds__(kWave * kIdealWaves, IDEAL_MIN_BLOCKS) void k_ideal
     extern __shared__ unsigned int ideal_lds[];
     float *const lognodes = reinterpret_cast<float *>(ideal_lds);          // copy of g_log_nodes (adc::LogNodes), [kLogTableIntervals + 1]
     const int lane = threadIdx.x & (kWave - 1), wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n_waves = (int)(blockDim.x / kWave);
     unsigned int *const cpre = ideal_lds + adc::kLogTableIntervals + 4 + (size_t)wv * ideal_wave_words(lim);     // count per cent value, then the inclusive prefix of the counts
-    unsigned int *const spre = cpre + (lim + 1);                           // inclusive prefix of cents (<= 2^21 * 1023 fits for n <= 2^21)
+    unsigned int *const spre = cpre + (lim + 1);                           // inclusive prefix of cents (<= 2^20 * 2047 < 2^31: kIdealMaxSamples)
     unsigned short *const nxt = reinterpret_cast<unsigned short *>(spre + (lim + 1));      // [lim + 2] smallest occupied bin >= i (kNoBin: none - the next sample is over_min)
     constexpr unsigned int kNoBin = 0xFFFFu;
-    for (int i = threadIdx.x; i <= adc::kLogTableIntervals; i += kWave * kIdealWaves) lognodes[i] = g_log_nodes[i];
+    for (int i = threadIdx.x; i <= adc::kLogTableIntervals; i += (int)blockDim.x) lognodes[i] = g_log_nodes[i];
     __syncthreads();
     // (a wavefront's tables are its own: between its phases it only has to see its own LDS writes)
     auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-    const int per = (lim + kWave) / kWave;         // bins per lane: lane l owns bins [l per, l per + per) up to lim; per <= 16
+    const int per = (lim + kWave) / kWave;         // bins per lane: lane l owns bins [l per, l per + per) up to lim; per <= 32
   // (a workgroup takes a contiguous run of keywords - neighbours of one env, whatever pattern the keyword set has - its wavefronts every
-  //  fourth of them; the grid is a few thousand workgroups, ideal_grid)
+  //  n_waves-th of them; the grid is a few thousand workgroups, ideal_grid)
   const long long chunk = (n_items + gridDim.x - 1) / gridDim.x;
   const long long item_end = min(n_items, ((long long)blockIdx.x + 1) * chunk);
-  for (long long item = (long long)blockIdx.x * chunk + wv; item < item_end; item += kIdealWaves) {
+  for (long long item = (long long)blockIdx.x * chunk + wv; item < item_end; item += n_waves) {
     const int env = (int)(item / v.K), k = (int)(item - (long long)env * v.K);
     if (!ir_out && !cpc_out && !packed_out) {
         // only the maximum is asked for: a keyword without volume or clicks (half of a sparse keyword set), or without a
@@ -227,8 +235,12 @@ __global__ __launch_bounds__(kWave * kIdealWaves, IDEAL_MIN_BLOCKS) void k_ideal
         // the reference compares float dollars: sample c/100.0 <= bid, with bid from np.arange (so e.g. its
         // "0.10" is 0.09999999999999999 and excludes 10-cent samples).  b = largest cent value that passes.
         const double bid = bid_grid[bi];
-        int b = (int)__builtin_floor(bid * 100.0 + 0.5);
-        if (b > kIdealBins - 2) b = kIdealBins - 2;
+        // (a bid at or below -0.015 - or not finite - is bin -1: idx 0, and nxt[0] = the smallest sample, searchsorted's 0 and sorted[0];
+        //  the host has refused bids above the bins kept, the upper clamp only keeps nxt[b + 1] inside this wave's table)
+        double x = __builtin_floor(bid * 100.0 + 0.5);
+        x = x > -1.0 ? x : -1.0;
+        x = x < (double)(lim - 1) ? x : (double)(lim - 1);
+        int b = (int)x;
         if (b >= 0 && !(adc::cents_to_dollars_f64(b) <= bid)) b -= 1;       // ((double)b / 100.0, the IEEE quotient, without the division sequence)
         const unsigned long long idx = b >= 0 ? cpre[b] : 0u;          // searchsorted side="right" (:30)
         const unsigned long long sum = b >= 0 ? spre[b] : 0u;

@@ -339,8 +339,10 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
     const double n_samples = (double)p.n_samples, inv_n = 1.0 / n_samples;
     const bool pow2 = (p.n_samples & (p.n_samples - 1)) == 0;
 
-    // the distinct lines with a positive slope, in grid order (= slope order).  All of the curve's points are requested before the first is
-    // used (the compaction below carries a count from chunk to chunk: chunk by chunk the loads would be five HBM round trips in a row)
+    // the distinct lines with a positive slope, in grid order.  All of the curve's points are requested before the first is used (the
+    // compaction below carries a count from chunk to chunk: chunk by chunk the loads would be five HBM round trips in a row).  The
+    // elimination below needs ascending slopes: a point's idx never falls along an ascending grid - a curve where it does (a descending or
+    // shuffled grid) is evaluated on the whole grid, as the EXPLICIT instance does
     uint2 pts[kContenderChunks], pvs[kContenderChunks];
 #pragma unroll
     for (int ch = 0; ch < kContenderChunks; ++ch) {
@@ -348,6 +350,7 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
         pts[ch] = b < p.n_bids ? curve[b] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         pvs[ch] = b > 0 && b < p.n_bids ? curve[b - 1] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
     }
+    bool falls = false;
 #pragma unroll
     for (int ch = 0; ch < kContenderChunks; ++ch) {
         const int b = ch * kWave + lane;
@@ -358,6 +361,7 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
             const uint2 pt = pts[ch], pv = pvs[ch];
             l = curve_line(pt, n_samples, inv_n, pow2);
             keep = !(pt.x == pv.x && pt.y == pv.y) && l.s > 0.0 && l.c == l.c;
+            falls |= b > 0 && (pt.y & 0x7FFFFFFFu) < (pv.y & 0x7FFFFFFFu);
         }
         const unsigned long long m = __ballot(keep);
         if (keep) {
@@ -365,6 +369,10 @@ __global__ __launch_bounds__(kWave) void k_curve_contenders(View v, PolicyView p
             w.s[at] = l.s; w.c[at] = l.c; w.b[at] = (unsigned short)b;
         }
         n_lines += (int)__popcll(m);
+    }
+    if (__ballot(falls)) {
+        if (lane == 0) { p.cont_pos[o] = 0; p.n_contenders[o] = kContenderAll; }
+        return;
     }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

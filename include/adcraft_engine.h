@@ -339,15 +339,17 @@ int adc_engine_metrics_enable(adc_engine *e, int enabled);
 int adc_engine_metrics_reset(adc_engine *e);
 /* local (this device) accumulators to host: keyword_profit_cents [K], scalars [8] */
 int adc_engine_metrics_read(adc_engine *e, int64_t *keyword_profit_cents_k, int64_t *scalars8);
-/* ideal (max expected) profit per keyword from the CURRENT parameters, n_samples sampled competitor bids and an
- * ascending bid grid in dollars (the notebooks use np.arange(0.01, 3.00, 0.01)); experiment_metrics.py:20-61;
- * host double [N*K].  EXPLICIT keywords: the curves of adc_engine_bid_curves_build (get_explicit_kw_bid_cpc_impressions,
+/* ideal (max expected) profit per keyword from the CURRENT parameters, n_samples sampled competitor bids and a
+ * bid grid in dollars (the notebooks use np.arange(0.01, 3.00, 0.01)); experiment_metrics.py:20-61;
+ * host double [N*K].  IMPLICIT keywords: n_samples <= 2^20; every bid finite and at most $20.46 (2046 cents; any order, a bid
+ * of 0 or less takes no sample) - otherwise ADC_EINVAL, never a clamped bid.  EXPLICIT keywords: the curves of adc_engine_bid_curves_build (get_explicit_kw_bid_cpc_impressions,
  * experiment_metrics.py:10-17), n_samples <= 2^20.  IMPLICIT_GENERAL: ADC_EINVAL (the reference's estimator on a bidder
  * pool gives impression rates above 1). */
 int adc_engine_ideal_profit(adc_engine *e, int n_samples, const double *bid_grid, int n_bids, double *host_nk);
 /* the estimator alone, on caller-supplied competitor-bid samples (cents) of one keyword: impression rate and
  * expected cpc on the given bid grid, exactly as get_implicit_kw_bid_cpc_impressions computes them
- * (experiment_metrics.py:28-37, including its inclusive running-mean index) */
+ * (experiment_metrics.py:28-37, including its inclusive running-mean index).  Samples >= 0, n_samples <= 2^20 and the IMPLICIT
+ * grid limits of adc_engine_ideal_profit, all checked before any HIP call (ADC_EINVAL). */
 int adc_bid_curves_from_samples(int device_id, const int32_t *samples_cents, int32_t n_samples, const double *bid_grid,
                                 int32_t n_bids, double *impression_rate_out, double *cpc_out);
 
@@ -359,7 +361,7 @@ int adc_bid_curves_from_samples(int device_id, const int32_t *samples_cents, int
 
 /* impression-rate / expected-cpc curves of every keyword on `bid_grid` from n_samples sampled competitor bids
  * (get_implicit_kw_bid_cpc_impressions, experiment_metrics.py:20-37; the notebooks build them once after reset()).
- * Kept on the device as integer numerators, 8 bytes x N x K x n_bids; n_samples <= 2^20.
+ * Kept on the device as integer numerators, 8 bytes x N x K x n_bids; n_samples <= 2^20, bids as for adc_engine_ideal_profit.
  * EXPLICIT keywords: get_explicit_kw_bid_cpc_impressions (:10-17) - impression rate = threshold_sigmoid, cpc = the median of
  * n_samples costs, drawn once per keyword (the grid's bids share the draws) and kept as the two middle normals with the
  * impression intercept and slope: 16 bytes x N x K, plus 24 bytes per grid point.  IMPLICIT_GENERAL: ADC_EINVAL. */

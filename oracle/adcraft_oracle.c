@@ -288,6 +288,16 @@ ORC_API int32_t orc_competitor_cents_from_v(uint32_t v, float loc, float scale)
     if (!(c < 1.0e9f)) c = 1.0e9f;
     return (int32_t)c;
 }
+/* the n competitor samples (cents) the ideal-profit estimator draws for keyword k of an env at (key, tick): sample i is word
+ * i % 4 of call (i / 4, ST_METRIC, k, tick), through orc_competitor_cents_from_v of its top 24 bits (k_ideal_profit's order) */
+ORC_API void orc_metric_competitor_cents(uint64_t key, uint32_t tick, uint32_t k, int64_t n, float loc, float scale, int32_t *out)
+{
+    for (int64_t q = 0; 4 * q < n; ++q) {
+        uint32_t w[4];
+        draw(key, (uint32_t)q, ST_METRIC, k, tick, w);
+        for (int64_t j = 0; j < 4 && 4 * q + j < n; ++j) out[4 * q + j] = orc_competitor_cents_from_v(w[j] >> 8, loc, scale);
+    }
+}
 /* checker: number of v in [1, 2^24) at which the Laplace deviate z(v) DEcreases (must be 0: the thresholds of
  * k_step_implicit_fast rest on z, hence loc + |scale| z and its rounding to cents, being monotone in v) */
 ORC_API int64_t orc_check_deviate_monotone(void)

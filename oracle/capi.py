@@ -81,6 +81,8 @@ def lib():
         L.orc_check_deviate_monotone.argtypes = []
         L.orc_competitor_cents_from_v.restype = C.c_int32
         L.orc_competitor_cents_from_v.argtypes = [C.c_uint32, C.c_float, C.c_float]
+        L.orc_metric_competitor_cents.restype = None
+        L.orc_metric_competitor_cents.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, C.c_float, C.c_float, C.c_void_p]
         L.orc_neg_log_u24.restype = C.c_float
         L.orc_neg_log_u24.argtypes = [C.c_uint32]
         L.orc_auction_outcome.restype = C.c_int32
@@ -134,6 +136,13 @@ def philox(ctr, key, rounds=None):
     else:
         lib().orc_philox4x32_r(c.ctypes.data, k.ctypes.data, int(rounds), o.ctypes.data)
     return o
+
+
+def metric_competitor_cents(key, tick, k, n, loc, scale):
+    """int32 [n]: the competitor samples k_ideal_profit draws for keyword k of an env whose stream is at (key, tick)"""
+    out = np.zeros(int(n), dtype=np.int32)
+    lib().orc_metric_competitor_cents(int(key), int(tick), int(k), int(n), float(loc), float(scale), out.ctypes.data)
+    return out
 
 
 def nth_price_auction(bid, other_bids, n=2, num_winners=2):

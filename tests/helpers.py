@@ -91,3 +91,27 @@ def assert_outcome_lists(got, ref, K, env=0):
     share = np.asarray(got["impression_share"], dtype=np.float64).reshape(-1, K)[env]
     assert share.tolist() == ref["impression_share"]
     np.testing.assert_allclose(np.asarray(got["profit"], dtype=np.float64).reshape(-1, K)[env], ref["profit"], rtol=0, atol=1e-9)
+
+
+# ---- the IMPLICIT estimator written out plainly (get_implicit_kw_bid_cpc_impressions, experiment_metrics.py:20-37) ----
+def exact_implicit_curve(cents, bid_grid):
+    """(ir, cpc) of integer competitor samples (cents) on a float64 bid grid, exactly: idx = #(c / 100.0 <= bid) - the reference's
+    float-dollar comparison, literally -, ir = idx / n, S = the integer sum of the min(idx, n - 1) + 1 smallest samples,
+    cpc = (float(S) / 100.0) / (min(idx, n - 1) + 1).  No running float cumsum: the bits a correct kernel must produce."""
+    c = np.sort(np.asarray(cents, dtype=np.int64).ravel())
+    n = c.size
+    grid = np.asarray(bid_grid, dtype=np.float64)
+    idx = np.searchsorted(c / 100.0, grid, side="right")
+    ir = idx / n
+    m = np.minimum(idx, n - 1)
+    csum = np.concatenate([[0], np.cumsum(c)])          # int64: exact
+    cpc = (csum[m + 1].astype(np.float64) / 100.0) / (m + 1).astype(np.float64)
+    return ir, cpc
+
+
+def exact_profit(planes, env, k, ir, cpc):
+    """(profit per grid point, ideal, first argmax) of keyword (env, k): max_expected_bid_profits' operations in its order"""
+    vol, bctr = float(planes[0, env, k]), float(planes[4, env, k])
+    margin = float(planes[5, env, k]) * float(planes[6, env, k])
+    ep = np.maximum(vol * ir * bctr * (margin - cpc), 0.0)
+    return ep, max(0.0, float(ep.max())), int(np.argmax(ep))

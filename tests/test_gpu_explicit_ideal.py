@@ -112,7 +112,8 @@ def test_ideal_step_under_drift_is_the_reference_formula(amd):
     e.close()
 
 
-@pytest.mark.parametrize("case", ["notebook", "few_samples", "coarse_grid", "fine_grid", "long_grid", "extremes"])
+@pytest.mark.parametrize("case", ["notebook", "few_samples", "coarse_grid", "fine_grid", "long_grid", "extremes", "descending_grid",
+                                  "shuffled_grid"])
 def test_contender_lists_give_the_full_scans_ideal_bit_for_bit(amd, monkeypatch, case):
     N, K, days = 24, 160, 12
     n_samples, grid = 2048, None
@@ -126,6 +127,10 @@ def test_contender_lists_give_the_full_scans_ideal_bit_for_bit(amd, monkeypatch,
         grid = GRIDS["fine"]
     elif case == "long_grid":
         grid = GRIDS["long"]                               # more points than the lists take: the whole grid, still identical
+    elif case == "descending_grid":
+        grid = NOTEBOOK[::-1].copy()                       # the impression rate falls along the grid: the whole grid
+    elif case == "shuffled_grid":
+        grid = np.random.default_rng(3).permutation(NOTEBOOK)
     elif case == "extremes":
         planes[5, 0] = 0.0                                 # no conversions
         planes[5, 1] = 1.0
@@ -157,6 +162,8 @@ def test_contender_lists_give_the_full_scans_ideal_bit_for_bit(amd, monkeypatch,
         assert np.array_equal(b_full, b_fast)
     if case == "long_grid":
         assert (count == 65535).all()
+    elif case in ("descending_grid", "shuffled_grid"):
+        assert (count == 65535).mean() > 0.9
     elif case == "extremes":
         assert (count[7] == 65535).all()
     else:

@@ -58,6 +58,16 @@ ADC_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 #endif
 }
 
+// a ^ (b & c)
+ADC_HD uint32_t xor_and(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x78);      // truth table of S0 ^ (S1 & S2): 0xF0 ^ (0xCC & 0xAA)
+#else
+    return a ^ (b & c);
+#endif
+}
+
 ADC_HD void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1)
 {
     const uint64_t a = (uint64_t)0xD2511F53u * c0;          // v_mad_u64_u32: both halves in one op
@@ -86,6 +96,37 @@ ADC_HD U4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_
 ADC_HD U4 draw(uint64_t key, uint32_t index, uint32_t stage, uint32_t keyword, uint32_t tick)
 {
     return philox4x32(index, stage, keyword, tick, (uint32_t)key, (uint32_t)(key >> 32));
+}
+
+// Round 1 of philox4x32(index, stage, keyword, tick, k0, k1) splits into a half that depends on the index (c0's product) and
+// one that depends on (stage, keyword, k0) alone (c2's product): {hi(M1 keyword) ^ stage ^ k0, lo(M1 keyword)}.  A kernel
+// that draws many calls of one keyword keeps that half per keyword (philox_kw_half) and starts each call from it
+// (philox4x32_kw): the same bits, one multiply and one xor fewer per call.
+struct KwHalf { uint32_t c0, c1; };
+
+ADC_HD KwHalf philox_kw_half(uint32_t stage, uint32_t keyword, uint32_t k0)
+{
+    const uint64_t b = (uint64_t)0xCD9E8D57u * keyword;
+    return KwHalf{xor3((uint32_t)(b >> 32), stage, k0), (uint32_t)b};
+}
+
+ADC_HD U4 philox4x32_kw(uint32_t index, KwHalf h, uint32_t tick, uint32_t k0, uint32_t k1)
+{
+    const uint64_t a = (uint64_t)0xD2511F53u * index;
+    uint32_t c0 = h.c0, c1 = h.c1, c2 = xor3((uint32_t)(a >> 32), tick, k1), c3 = (uint32_t)a;
+#pragma unroll
+    for (int r = 1; r < kPhiloxRounds; ++r) {
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+        philox_round(c0, c1, c2, c3, k0, k1);
+    }
+    return U4{c0, c1, c2, c3};
+}
+
+// draw(key, index, stage, keyword, tick) with h = philox_kw_half(stage, keyword, (uint32_t)key)
+ADC_HD U4 draw_kw(uint64_t key, uint32_t index, KwHalf h, uint32_t tick)
+{
+    return philox4x32_kw(index, h, tick, (uint32_t)key, (uint32_t)(key >> 32));
 }
 
 // the volume word of keyword k: one call serves four consecutive keywords
@@ -376,7 +417,9 @@ ADC_HD float laplace_deviate_from_v(uint32_t v24, Tab tab)
     const uint32_t neg_mask = 0u - (v24 >> 23);                                  // all ones on the positive side
     const uint32_t mag = (v24 ^ neg_mask) & 0x007FFFFFu;
     const float e = neg_log_f24(fma32((float)mag, 2.0f, 1.0f), tab);            // 2 mag + 1 < 2^24: exact in float32; e > 0
-    return bits_to_float(float_to_bits(e) ^ (~neg_mask & 0x80000000u));         // negative side: -e
+    // negative side: -e, i.e. the bits of -e (= r of neg_log_f24) with neg_mask's sign bit xored in: one v_bitop3 where
+    // the compiler otherwise emits xor / cndmask / xor
+    return bits_to_float(xor_and(float_to_bits(-e), neg_mask, 0x80000000u));
 }
 
 // round(100 X) with its sign, clamped to +-1e9: non-decreasing in v.  |.| of it is the competitor's bid in cents.

@@ -13,21 +13,27 @@
 //   * tiles with few auctions per keyword (sparse keyword sets) skip the intervals - finding them costs more than the
 //     ~20 auctions they would serve - and resolve each auction from its sampled competitor bid (DIRECT).
 // Both forms are the same law (the oracle only knows the auction-by-auction form); results are identical bit for bit.
-constexpr int kQueueCap = 128;    // per-wave ring of deferred clicked wins (entries), power of two; drained whenever 64 wait
+constexpr int kQueueCap = 128;    // per-wave queue of deferred clicked wins (entries): drained whenever 64 wait, so <= 63 + 64 ever do
 constexpr int kDenseVolumePerKeyword = 24;     // tiles averaging at least this many auctions per non-empty keyword use intervals
 
 // per keyword, two 16-byte records in separate arrays (a wave's consecutive keywords then cover every LDS bank once per
-// ds_read_b128; one 32-byte record per keyword is a built-in 2-way bank conflict)
-struct KwLawA {
+// ds_read_b128; one 32-byte record per keyword is a built-in 2-way bank conflict).  16-byte aligned: a record that is only
+// 4-byte aligned (as `win` was after off[257]) is read as two ds_read2_b32, each with its own address add.
+struct alignas(16) KwLawA {
     unsigned int m_click, t_conv; // rescale multiplier of the click sub-interval; saturated conversion threshold
     float loc, scale;             // competitor-bid law
 };
-struct KwLawB {
+struct alignas(16) KwLawB {
     float mu, sd;                 // revenue law
-    unsigned int t_click;         // saturated click threshold           (DIRECT stage A)
-    int bid_c;                    // the bid in cents                    (DIRECT stage A)
+    union {
+        struct {
+            unsigned int t_click; // saturated click threshold           (DIRECT stage A)
+            int bid_c;            // the bid in cents                    (DIRECT stage A)
+        } d;
+        adc::KwHalf conv;         // interval form: the keyword's half of round 1 of its ST_CONV draws (stage B, adc::draw_kw)
+    };
 };
-union KwWin {                     // per keyword, 16 B
+union alignas(16) KwWin {                     // per keyword, 16 B
     adc::WinIntervals iv;                                   // interval form
     struct { unsigned int m_noclick, pad0, pad1, pad2; } d; // DIRECT form
 };
@@ -40,21 +46,26 @@ static_assert(adc::kVolumeMax < (1 << kClkShift), "three counts of up to kVolume
 // (Keyword sets with few auctions per keyword - the engine's volume hint - go to k_step_implicit_sparse, kernel_sparse.inc; this
 // kernel still decides per tile: a tile that happens to be sparse is resolved auction by auction from the sampled competitor bid.)
 struct FastShared {
-    int off[kFastBlock + 1];        // exclusive prefix of the keywords' full work items (+ the total)
-    int vol[kFastBlock];
-    KwWin win[kFastBlock];
-    KwLawA law_a[kFastBlock];
-    KwLawB law_b[kFastBlock];
-    unsigned long long a_cnt[kFastBlock], a_cost[kFastBlock], a_rev[kFastBlock];
-    adc::LogTableEntry logtab[adc::kLogTableIntervals];     // copy of g_log_table
-    float normtab[adc::kNormTableEntries + 1];              // node values of g_norm_table (+ the p = 1/2 node)
+    // (the queue first: its two arrays then sit 2048 bytes apart at a 256-byte aligned offset, and a push's pair of writes is
+    // one ds_write2st64_b32 on the slot's address, with no constant to add)
     union {
-        uint2 queue[kFastBlock / kWave][kQueueCap];         // phase 2: {keyword-in-tile << 24 | auction index, word or cost}
-        struct {                                            // phase 1 (before the rings are used)
+        struct {                                            // phase 2: per wave, entry e = {tag[e], word[e]}
+            unsigned int tag[kFastBlock / kWave][kQueueCap];    //   keyword-in-tile << 24 | auction index
+            unsigned int word[kFastBlock / kWave][kQueueCap];   //   the auction word (DIRECT: the price)
+        } queue;
+        struct {                                            // phase 1 (before the queues are used)
             unsigned int volw[kFastBlock];                  // volume words of the tile's keywords
             int wave_tot[kFastBlock / kWave], wave_vol[kFastBlock / kWave], wave_live[kFastBlock / kWave];
         };
     };
+    KwWin win[kFastBlock];
+    KwLawA law_a[kFastBlock];
+    KwLawB law_b[kFastBlock];
+    unsigned long long a_cnt[kFastBlock], a_cost[kFastBlock], a_rev[kFastBlock];      // (stage B reaches all three from &a_cnt[u])
+    adc::LogTableEntry logtab[adc::kLogTableIntervals];     // copy of g_log_table
+    float normtab[adc::kNormTableEntries + 1];              // node values of g_norm_table (+ the p = 1/2 node)
+    int off[kFastBlock + 1];        // exclusive prefix of the keywords' full work items (+ the total)
+    int vol[kFastBlock];
 };
 // what the listing variant keeps on top of that (envs that list their clicked wins for k_step_click_walk, see resolve_click)
 template <bool LISTS>
@@ -216,9 +227,18 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         const adc::AuctionLaw law = adc::make_auction_law(bctr);
         const int bid_c = (int)adc::bid_to_cents(bid);
         sh.law_a[tid] = KwLawA{law.m_click, adc::saturate_threshold(adc::bernoulli_threshold(sctr)), loc, scale};
-        sh.law_b[tid] = KwLawB{mu, sd, law.t32, bid_c};
-        if (dense) sh.win[tid].iv = adc::win_intervals(bid_c, loc, scale, t_click, law, sh.logtab);
-        else sh.win[tid].d.m_noclick = law.m_noclick;
+        KwLawB lb;
+        lb.mu = mu;
+        lb.sd = sd;
+        if (dense) {
+            lb.conv = adc::philox_kw_half(adc::ST_CONV, kw_base + (uint32_t)tid, (uint32_t)key);
+            sh.win[tid].iv = adc::win_intervals(bid_c, loc, scale, t_click, law, sh.logtab);
+        } else {
+            lb.d.t_click = law.t32;
+            lb.d.bid_c = bid_c;
+            sh.win[tid].d.m_noclick = law.m_noclick;
+        }
+        sh.law_b[tid] = lb;
     }
     FDBG_ADD(1, FDBG_T() - t_law);
     __syncthreads();
@@ -229,7 +249,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         if (i < wv) wave_base += t;
         total += t;
     }
-    __syncthreads();                    // (wave_tot / volw share memory with the rings: everybody has read them)
+    __syncthreads();                    // (wave_tot / volw share memory with the queues: everybody has read them)
     sh.off[tid] = wave_base + incl - nch;
     if (tid == 0) sh.off[kFastBlock] = total;
     __syncthreads();
@@ -242,37 +262,50 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     // (their LDS records and accumulators then fall on distinct banks, and the same keyword is rarely hit twice by one
     // stage-B batch), and the lane finds its next keyword by comparing with a bound it holds in a register.  The keywords'
     // tails (V mod chunk auctions) follow in one last round, one keyword per lane.
-    // Control flow is wave-uniform (idle lanes carry an empty law) so that the deferred-click ring below can be maintained
+    // Control flow is wave-uniform (idle lanes carry an empty law) so that the deferred-click queue below can be maintained
     // with ballots.  Stage A (every auction): one Philox call per FOUR auctions (one word each); the word is classified
     // (lost / won / won and clicked).  Stage B (clicked wins only, ~1/4 of auctions): the (keyword, auction, word) is pushed
-    // to a per-wave LDS ring; whenever 64 are waiting, all 64 lanes evaluate the price paid and draw the conversion /
+    // to a per-wave LDS queue; whenever 64 are waiting, all 64 lanes evaluate the price paid and draw the conversion /
     // revenue call together - full wavefronts instead of the lanes that happen to click.
-    uint2 *const ring = sh.queue[__builtin_amdgcn_readfirstlane(wv)];      // (wave-uniform: keep the base scalar)
-    unsigned int qhead = 0, qtail = 0;
+    // The queue is linear, not a ring: entries sit at [0, qtail); a drain resolves [0, 64) and moves the 0..63 entries
+    // behind them down to [0, qtail - 64) (one read and one write per lane, per 64 clicked wins), so that a push is
+    // mbcnt_lo, mbcnt_hi and one address (qtail goes into its scalar base), plus the tag: no wrap mask, no head.
+    // Tags and words are two arrays of 4-byte entries: consecutive slots, conflict-free, and no register pair to build (two
+    // ds_write_b32 at an 8-byte stride are each a 2-way bank conflict - measured +19 % kernel time).
+    const int wq = __builtin_amdgcn_readfirstlane(wv);                      // (wave-uniform: keep the bases scalar)
+    unsigned int *const qtag = sh.queue.tag[wq];
+    unsigned int *const qword = sh.queue.word[wq];
+    unsigned int qtail = 0;
 
     // direct: the entry carries the price (stage A had to sample it); otherwise the auction word
-    auto resolve_click = [&](unsigned int pos, bool direct) {
-        const uint2 ent = ring[pos & (kQueueCap - 1)];
+    auto resolve_click = [&](bool direct) {
+        const uint2 ent = make_uint2(qtag[lane], qword[lane]);
         const unsigned int uu = ent.x >> 24;
+        // the keyword's accumulators by one byte offset (left to itself, hipcc forms it as uu * 16 - uu * 8 from the law records' address)
+        unsigned int acc_off = uu * (unsigned int)sizeof(unsigned long long);
+        asm volatile("" : "+v"(acc_off));
+        unsigned long long *const acc = (unsigned long long *)((char *)sh.a_cnt + acc_off);      // a_cnt[uu]; a_cost, a_rev follow at kFastBlock strides
         const KwLawA ka = sh.law_a[uu];
+        const KwLawB kb = sh.law_b[uu];
         unsigned int price = ent.y;
         if (!direct) {
             unsigned int vv = adc::mulhi32(ent.y, ka.m_click);                        // a click: the offset is the word itself
             vv = vv < 0x00FFFFFFu ? vv : 0x00FFFFFFu;
             price = (unsigned int)adc::competitor_cents_from_v(vv, ka.loc, ka.scale, sh.logtab);
         }
-        const adc::U4 w2 = adc::draw(key, ent.x & 0x00FFFFFFu, adc::ST_CONV, kw_base + uu, tick);
+        // (interval form: the draw starts from the keyword's half of round 1, kept in law_b by phase 1 - the same bits)
+        const adc::U4 w2 = direct ? adc::draw(key, ent.x & 0x00FFFFFFu, adc::ST_CONV, kw_base + uu, tick)
+                                  : adc::draw_kw(key, ent.x & 0x00FFFFFFu, kb.conv, tick);
         const bool conv = adc::bernoulli32(w2.x, ka.t_conv);
         unsigned long long cnt = 1ull << kClkShift;
         if (conv) {
-            const KwLawB kb = sh.law_b[uu];
             float x = adc::fma32(kb.sd, normal_tab_nodes(w2.y, sh.normtab), kb.mu);
             x = x > 0.01f ? x : 0.01f;
-            atomicAdd(&sh.a_rev[uu], (unsigned long long)adc::money_to_cents(x));
+            atomicAdd(acc + 2 * kFastBlock, (unsigned long long)(unsigned int)adc::money_to_cents(x));      // a_rev[uu] (>= 1 cent: no sign to extend)
             cnt |= 1ull << kConvShift;
         }
-        atomicAdd(&sh.a_cnt[uu], cnt);
-        atomicAdd(&sh.a_cost[uu], (unsigned long long)price);
+        atomicAdd(acc, cnt);
+        atomicAdd(acc + kFastBlock, (unsigned long long)price);
         if constexpr (LISTS) { if (raw.emit) {
             // (block-uniform) the env's budget bound yesterday: list the clicked win for k_step_click_walk, by sub-timestep
             // (adc::cell_range inverted: the quotient estimated in float32 - exact operands below 2^24 - and fixed up)
@@ -301,12 +334,15 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         } }
     };
     auto drain = [&](bool direct) {
-        while (qtail - qhead >= (unsigned int)kWave) {      // checked after every push: <= 63 + 64 entries wait (ring holds 128)
+        if (qtail >= (unsigned int)kWave) {                 // checked after every push: <= 63 + 64 entries wait
             [[maybe_unused]] const unsigned long long tb = FDBG_T();
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            resolve_click(qhead + lane, direct);
-            qhead += kWave;
+            resolve_click(direct);
+            // the entries behind the batch move down (a lane reads and writes only its own slots: no entry is overwritten
+            // before its lane has read it)
+            qtail -= kWave;
+            if ((unsigned int)lane < qtail) { qtag[lane] = qtag[kWave + lane]; qword[lane] = qword[kWave + lane]; }
             FDBG_ADD(4, FDBG_T() - tb);
             FDBG_ADD(7, 1);
         }
@@ -314,9 +350,8 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     auto push = [&](bool click, unsigned int tagj, unsigned int payload) {
         const unsigned long long m = __builtin_amdgcn_ballot_w64(click);     // (the mask itself: __ballot() goes through an int)
         const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-        // (one ds_write_b64 per entry: consecutive 8-byte slots are conflict-free; two ds_write_b32 at an 8-byte stride are
-        // each a 2-way bank conflict - measured +19 % kernel time)
-        if (click) ring[(rank + qtail) & (kQueueCap - 1)] = make_uint2(tagj, payload);
+        // (qtail in the scalar base rather than mbcnt_lo's addend: a VOP3 reads one SGPR, and the mask already is one)
+        if (click) { (qtag + qtail)[rank] = tagj; (qword + qtail)[rank] = payload; }
         qtail += __popcll(m);
     };
     // one work item: auctions j0 .. j0 + n - 1 of keyword u (n == chunk unless TAIL)
@@ -347,8 +382,8 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         if (!dense) {
             const KwLawA ka = sh.law_a[u];
             const KwLawB kb = sh.law_b[u];
-            const adc::AuctionLaw law{kb.t_click, ka.m_click, sh.win[u].d.m_noclick};
-            const int bid_c = n > 0 ? kb.bid_c : 0;                                 // (bid 0 never wins)
+            const adc::AuctionLaw law{kb.d.t_click, ka.m_click, sh.win[u].d.m_noclick};
+            const int bid_c = n > 0 ? kb.d.bid_c : 0;                               // (bid 0 never wins)
             for (int i = 0; i < chunk; i += 4) {
                 if (TAIL && __builtin_amdgcn_ballot_w64(i < n) == 0ull) break;
                 const adc::U4 w = adc::draw(key, (uint32_t)(j0 + i) >> 2, adc::ST_AUCTION, kw, tick);
@@ -391,7 +426,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if ((unsigned int)lane < qtail - qhead) resolve_click(qhead + lane, !dense);      // fewer than 64 left
+    if ((unsigned int)lane < qtail) resolve_click(!dense);      // fewer than 64 left
     [[maybe_unused]] const unsigned long long t_p3 = FDBG_T();
     FDBG_ADD(3, t_p3 - t_p2);
     __syncthreads();

@@ -95,6 +95,13 @@ def lib():
         "adc_engine_agent_act": ([vp, f32, vp], C.c_int),
         "adc_engine_agent_step": ([vp, f32], C.c_int),
         "adc_engine_agent_state": ([vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_interp_init": ([vp, C.c_double, C.c_double, vp, i32, i32, vp], C.c_int),
+        "adc_engine_interp_set_allowed_bids": ([vp, vp, i32], C.c_int),
+        "adc_engine_interp_update": ([vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_interp_act": ([vp, f32, vp], C.c_int),
+        "adc_engine_interp_step": ([vp, f32], C.c_int),
+        "adc_engine_interp_state": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_interp_entries": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "adc_engine_get_actions": ([vp, vp, vp], C.c_int),
         "adc_engine_metrics_read_nk": ([vp, vp, vp, vp], C.c_int),
         "adc_engine_run_days": ([vp, C.c_int, i32, f32], C.c_int),
@@ -160,6 +167,9 @@ def lib():
         "adc_auction_word_brackets": ([f32, f32, f32, f32, vp], C.c_int),
         "adc_check_win_brackets": ([i64, vp, vp, vp, vp, vp, vp, vp], i64),
         "adc_sample_random_keyword": ([C.c_uint64, C.c_uint32, C.c_uint32, vp], C.c_int),
+        "adc_interp_act_host": ([f32, i32, f32, i32, C.c_double, C.c_double, C.c_double, vp, i32, i32, vp, vp, i32, vp, vp,
+                                 C.c_double, vp, vp, vp, vp, vp], C.c_int),
+        "adc_interp_key_host": ([f32], C.c_double),
         "adc_explicit_curve_host": ([C.c_uint64, C.c_uint32, i32, i32, f32, f32, f32, vp, i32, vp, vp, vp], C.c_int),
         "adc_debug_win_brackets_device": ([C.c_int, i64, vp, vp, vp, vp, vp], C.c_int),
         "adc_debug_philox_device": ([C.c_int, i64, vp, vp, vp], C.c_int),

@@ -1,5 +1,5 @@
 """Mirror of adcraft/baselines/interpolated_expectations.py for the part the paper's experiments use:
-``NaiveZeroMarginStrategy`` (:442-515).  The caches and the bid rule live in the HIP engine
+``NaiveZeroMarginStrategy`` (:442-515) and ``NaiveInterpolationStrategy`` (:298-439).  The caches and the bid rule live in the HIP engine
 (``k_agent_step``, adcraft_amd/csrc/parts/kernels_policy.inc), one agent per env; this class is the reference's
 Python surface over it (same constructor, ``update_all_caches(prev_action, prev_observation)``, ``sample_action()``,
 ``caches``, ``max_bids``), usable with any env that returns the reference's observation dict.
@@ -64,6 +64,93 @@ class NaiveZeroMarginStrategy:
             return [dict(ave_rpc=float(st["ave_rpc"][n, k]), num_rpc_obs=int(st["num_rpc_obs"][n, k]),
                          ave_sctr=float(st["ave_sctr"][n, k]), num_sctr_obs=float(st["num_sctr_obs"][n, k]),
                          ave_cpc={}, ave_clicks={}) for k in range(self._e.num_keywords)]
+        return one(0) if self._e.num_envs == 1 else [one(n) for n in range(self._e.num_envs)]
+
+    def close(self):
+        if self._own:
+            self._e.close()
+
+
+class NaiveInterpolationStrategy:
+    """Estimates revenue per buyside click, clicks per bid and cost per bid, and samples bids believed to be profitable above
+    a threshold (reference docstring :299-314).  The caches, the interpolation, the acquisition function and the draw live in
+    the HIP engine (``k_interp_step``, adcraft_amd/csrc/parts/kernel_interp_agent.inc), one agent per env of ``engine``
+    (optional; its action buffers then receive the sampled action).
+
+    The agent draws from its own Philox stream keyed by ``seed``, not from np.random.default_rng(seed);
+    ``sample_action(replay_uniforms)`` takes the uniform rng.choice would use instead.  ``capacity``: interpolation points
+    kept per keyword (default min(300, max_days + 1)); an update that could overflow it raises ValueError."""
+
+    def __init__(self, num_keywords, profit_acquisition_threshold=-0.2, allowed_bids=np.linspace(0.01, 3.00, 300),
+                 initial_caches=None, seed=None, bid_step=0.03, *, engine=None, device_id=0, capacity=None):
+        if initial_caches is not None:
+            raise NotImplementedError("preseeded caches are not supported by the device agent")
+        self._own = engine is None
+        self._e = engine if engine is not None else StepEngine(1, int(num_keywords), device_id=device_id)
+        if self._e.num_keywords != int(num_keywords):
+            raise ValueError("engine.num_keywords != num_keywords")
+        self.observation_keys = ["impressions", "buyside_clicks", "cost", "sellside_conversions", "revenue"]
+        self.profit_acquisition_threshold = profit_acquisition_threshold
+        self.bid_step = bid_step
+        self._allowed_bids = np.array(allowed_bids, dtype=np.float64).reshape(-1)
+        seeds = None if seed is None else (np.full(self._e.num_envs, seed, dtype=np.uint64) + np.arange(self._e.num_envs, dtype=np.uint64))
+        self._e.interp_init(profit_acquisition_threshold, bid_step, self._allowed_bids, 0 if capacity is None else int(capacity), seeds)
+
+    @property
+    def allowed_bids(self):
+        return self._allowed_bids
+
+    @allowed_bids.setter
+    def allowed_bids(self, bids):
+        g = np.array(bids, dtype=np.float64).reshape(-1)
+        self._e.interp_set_allowed_bids(g)
+        self._allowed_bids = g
+
+    def update_all_caches(self, prev_action, prev_observations):
+        """:400-403; observations of shape [K] (one env) or [N, K]"""
+        o = prev_observations
+        self._e.interp_update(prev_action["keyword_bids"], o["buyside_clicks"], o["cost"], o["sellside_conversions"], o["revenue"])
+
+    def sample_action(self, replay_uniforms=None):
+        """:405-439 -> {"budget", "keyword_bids"}: the agent's float64 budget and its grid bids (arrays squeezed for one env)"""
+        self._e.interp_act(0.0, replay_uniforms)
+        st = self._e.interp_state()
+        idx = st["bid_index"]
+        bids = np.where(idx >= 0, self._allowed_bids[np.maximum(idx, 0)], 0.01)
+        if self._e.num_envs == 1:
+            return {"budget": float(st["budget"][0]), "keyword_bids": bids[0]}
+        return {"budget": st["budget"], "keyword_bids": bids}
+
+    @property
+    def profit_beliefs(self):
+        v = self._e.interp_state()["profit_beliefs"]
+        return float(v[0]) if self._e.num_envs == 1 else v
+
+    @property
+    def cost_beliefs(self):
+        v = self._e.interp_state()["cost_beliefs"]
+        return float(v[0]) if self._e.num_envs == 1 else v
+
+    @property
+    def caches(self):
+        """list (one env) or list of lists of the reference's cache dicts.  ave_cpc / ave_clicks hold only keys in
+        $0.01-$3.00, the ones the agent interpolates; bids outside that range are remembered only through the largest key."""
+        st, ent = self._e.interp_state(), self._e.interp_entries()
+
+        def key(c):
+            return str(round(c / 100.0, 2))
+
+        def one(n):
+            out = []
+            for k in range(self._e.num_keywords):
+                clicks = {key(int(ent["clicks_cent"][n, k, i])): [float(ent["ave_clicks"][n, k, i]), int(ent["clicks_count"][n, k, i])]
+                          for i in range(ent["n_clicks"][n, k])}
+                cpc = {key(int(ent["cpc_cent"][n, k, i])): [float(ent["ave_cpc"][n, k, i]), int(ent["cpc_count"][n, k, i])]
+                       for i in range(ent["n_cpc"][n, k])}
+                out.append(dict(ave_rpc=float(st["ave_rpc"][n, k]), num_rpc_obs=int(st["num_rpc_obs"][n, k]),
+                                ave_sctr=float(st["ave_sctr"][n, k]), num_sctr_obs=float(st["num_sctr_obs"][n, k]),
+                                ave_cpc=cpc, ave_clicks=clicks))
+            return out
         return one(0) if self._e.num_envs == 1 else [one(n) for n in range(self._e.num_envs)]
 
     def close(self):

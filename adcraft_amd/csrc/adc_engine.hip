@@ -44,6 +44,8 @@
 //        the curves' contender lists (k_curve_contenders, k_ideal_from_contenders), the oracle bidder, per-env AKNCP / NCP.
 //   parts/kernel_explicit_curves.inc  the bid curves and ideal profit of EXPLICIT keywords (k_explicit_curves: the two middle
 //        normals of a keyword's cost samples by a radix select; k_explicit_curve_points); the policy kernels read them too.
+//   parts/kernel_interp_agent.inc the interpolation agent (NaiveInterpolationStrategy): its caches, update and act
+//        (k_interp_step); the per-keyword act itself is adc_interp.h, shared with the host twin.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //
 // No CPU path exists in this library.
@@ -62,6 +64,7 @@
 
 #include "../../include/adcraft_engine.h"
 #include "adc_law.h"
+#include "adc_interp.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -76,6 +79,7 @@ namespace adck {
 #include "parts/kernels_misc.inc"
 #include "parts/kernels_policy.inc"
 #include "parts/kernel_explicit_curves.inc"
+#include "parts/kernel_interp_agent.inc"
 }  // namespace adck
 using namespace adck;
 

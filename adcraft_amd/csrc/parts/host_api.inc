@@ -67,6 +67,9 @@ struct adc_engine {
     float *d_flat_actions = nullptr;
     PolicyView pol{};                   // baseline policies + per-step ideal (allocated on first use)
     bool have_agent = false, have_curves = false, have_ideal = false;
+    InterpView ip{};                    // the interpolation agent (adc_engine_interp_init; allocated there)
+    bool have_interp = false;
+    long long interp_updates = 0;       // updates since adc_engine_interp_init: each may add one point per keyword and list
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
     // two consecutive days of the device-resident loop captured as one hipGraph (adc_engine_run_days)
     hipGraphExec_t day_graph = nullptr;
@@ -74,7 +77,7 @@ struct adc_engine {
     int day_graph_policy = -1, day_graph_parity = 0;
     float day_graph_budget = 0.0f;
     // everything the captured kernel nodes bake in by value: the graph is re-captured when any of it differs
-    struct GraphKey { View v; PolicyView pol; bool have_agent, have_curves, have_ideal, lists, rest, direct; float mean_volume_hint; int fast_tiles_per_wg; } day_graph_key{};
+    struct GraphKey { View v; PolicyView pol; InterpView ip; bool have_agent, have_curves, have_ideal, have_interp, lists, rest, direct; float mean_volume_hint; int fast_tiles_per_wg; } day_graph_key{};
     std::vector<void *> curve_allocs;   // ir / cpc / grid (re-allocated when the grid size changes)
     // the communicator of the episode-metric all-reduce (parts/comm_api.inc); null = this engine is alone
     void *comm = nullptr;
@@ -2311,6 +2314,231 @@ ADC_EXPORT int adc_engine_metrics_akncp_ncp(adc_engine *e, double days, double *
     return rc;
 }
 
+// ---- NaiveInterpolationStrategy, one agent per env (parts/kernel_interp_agent.inc) ---------------------------------------
+namespace {
+// the agent's view of the env group that starts at env e0: every per-keyword and per-env array moves to that env; the
+// slot-major lists keep the engine's stride
+inline InterpView interp_view_from(const adc_engine *e, size_t e0)
+{
+    InterpView p = e->ip;
+    const size_t o = e0, ok = o * (size_t)e->v.K;
+    auto at = [](auto *&ptr, size_t off) { if (ptr) ptr += off; };
+    at(p.ave_rpc, ok); at(p.n_rpc, ok); at(p.ave_sctr, ok); at(p.n_sctr, ok); at(p.max_obs, ok); at(p.last_bid, ok); at(p.last_index, ok);
+    at(p.n_clk, ok); at(p.n_cpc, ok); at(p.clk_cent, ok); at(p.clk_ave, ok); at(p.clk_cnt, ok);
+    at(p.cpc_cent, ok); at(p.cpc_ave, ok); at(p.cpc_cnt, ok); at(p.kw_cost, ok); at(p.kw_profit, ok);
+    at(p.budget, o); at(p.profit, o); at(p.cost, o); at(p.key, o); at(p.tick, o);
+    return p;
+}
+// `more` further updates fit the lists (a capacity of 300 holds every cent)
+inline bool interp_room(const adc_engine *e, long long more)
+{
+    return e->ip.cap >= adc::kInterpCents || e->interp_updates + more <= (long long)e->ip.cap;
+}
+inline int interp_grid_check(const double *bids, int n)
+{
+    if (!bids || n < 1 || n > adc::kInterpMaxBids) return fail(ADC_EINVAL, "allowed_bids must hold 1 to 2048 values");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(bids[i])) return fail(ADC_EINVAL, "allowed_bids must be finite");
+    return ADC_OK;
+}
+int interp_step_chained(adc_engine *e, float budget_override)
+{
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    // counted before anything is enqueued, so that a launch failing partway leaves the count high, never low (a captured day
+    // is counted where its graph is launched)
+    if (!e->in_capture) e->interp_updates += 1;
+    return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
+        const InterpView p = interp_view_from(e, (size_t)(d_budget - e->d_budget));      // (the group's first env)
+        hipLaunchKernelGGL(k_interp_step, dim3((unsigned)v.N), dim3(256), 0, st, v, p, (const float *)nullptr, v.clk, v.cost,
+                           v.conv, v.rev, 1, 1, (const double *)nullptr, budget_override, d_bids, d_budget);
+    });
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_interp_init(adc_engine *e, double threshold, double bid_step, const double *allowed_bids, int32_t n_bids,
+                                      int32_t capacity, const uint64_t *seeds_n)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!std::isfinite(threshold) || !std::isfinite(bid_step)) return fail(ADC_EINVAL, "threshold and bid_step must be finite");
+    if (int rc = interp_grid_check(allowed_bids, n_bids)) return rc;
+    if (capacity < 0 || capacity > adc::kInterpCents) return fail(ADC_EINVAL, "capacity must be 0 (default) to 300");
+    ENGINE_GUARD(e);
+    const int cap = capacity > 0 ? capacity : std::min(adc::kInterpCents, std::max(1, e->v.max_days + 1));
+    const size_t N = e->v.N, nk = N * e->v.K;
+    if (e->have_interp && cap != e->ip.cap) return fail(ADC_EINVAL, "the capacity is fixed by the first adc_engine_interp_init");
+    if (!e->have_interp) {
+        InterpView &p = e->ip;
+        const size_t slots = nk * (size_t)cap;
+        int rc;
+        if ((rc = dev_alloc(e, &p.ave_rpc, nk)) || (rc = dev_alloc(e, &p.n_rpc, nk)) || (rc = dev_alloc(e, &p.ave_sctr, nk)) ||
+            (rc = dev_alloc(e, &p.n_sctr, nk)) || (rc = dev_alloc(e, &p.max_obs, nk)) || (rc = dev_alloc(e, &p.last_bid, nk)) ||
+            (rc = dev_alloc(e, &p.last_index, nk)) ||
+            (rc = dev_alloc(e, &p.n_clk, nk)) || (rc = dev_alloc(e, &p.n_cpc, nk)) || (rc = dev_alloc(e, &p.clk_cent, slots)) ||
+            (rc = dev_alloc(e, &p.clk_ave, slots)) || (rc = dev_alloc(e, &p.clk_cnt, slots)) || (rc = dev_alloc(e, &p.cpc_cent, slots)) ||
+            (rc = dev_alloc(e, &p.cpc_ave, slots)) || (rc = dev_alloc(e, &p.cpc_cnt, slots)) || (rc = dev_alloc(e, &p.kw_cost, nk)) ||
+            (rc = dev_alloc(e, &p.kw_profit, nk)) || (rc = dev_alloc(e, &p.budget, N)) || (rc = dev_alloc(e, &p.profit, N)) ||
+            (rc = dev_alloc(e, &p.cost, N)) || (rc = dev_alloc(e, &p.key, N)) || (rc = dev_alloc(e, &p.tick, N)))
+            return rc;
+        double *grid = nullptr;
+        if ((rc = dev_alloc(e, &grid, (size_t)adc::kInterpMaxBids))) return rc;
+        p.grid = grid;
+        p.cap = cap;
+        p.slot_stride = nk;
+        e->have_interp = true;
+    }
+    e->ip.threshold = threshold;
+    e->ip.bid_step = bid_step;
+    e->ip.n_bids = n_bids;
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(e->ip.grid), allowed_bids, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream));
+    e->interp_updates = 0;
+    uint64_t *d_seeds = nullptr;
+    if (seeds_n) { HIP_TRY(hipMalloc((void **)&d_seeds, N * 8)); HIP_TRY(hipMemcpyAsync(d_seeds, seeds_n, N * 8, hipMemcpyHostToDevice, e->stream)); }
+    hipLaunchKernelGGL(k_interp_init, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->ip, e->v.K,
+                       d_seeds, e->cfg.seed, e->cfg.env_id_base);
+    hipError_t err = hipGetLastError();
+    hipError_t err2 = hipStreamSynchronize(e->stream);
+    if (d_seeds) (void)hipFree(d_seeds);
+    HIP_TRY(err);
+    HIP_TRY(err2);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_interp_set_allowed_bids(adc_engine *e, const double *bids, int32_t n)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = interp_grid_check(bids, n)) return rc;
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    ENGINE_GUARD(e);
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(e->ip.grid), bids, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->ip.n_bids = n;
+    return ADC_OK;
+}
+
+namespace {
+// update (host arrays: all five or none) and/or act on the engine's stream; host inputs are staged through temporaries
+int interp_launch(adc_engine *e, const double *prev_bids_nk, const int32_t *clicks_nk, const float *cost_nk, const int32_t *conv_nk,
+                  const float *rev_nk, int do_update, int do_act, const double *replay_u_nk, float budget_override)
+{
+    const size_t nk = (size_t)e->v.N * e->v.K;
+    std::vector<float> bids32;
+    if (do_update && prev_bids_nk) {
+        bids32.resize(nk);
+        for (size_t i = 0; i < nk; ++i) bids32[i] = (float)prev_bids_nk[i];       // torch.Tensor([prev_bid])
+    }
+    float *d_bid = nullptr, *d_cost = nullptr, *d_rev = nullptr;
+    int32_t *d_clk = nullptr, *d_conv = nullptr;
+    double *d_u = nullptr;
+    auto done = [&](hipError_t err) {
+        hipError_t e2 = hipStreamSynchronize(e->stream);
+        (void)hipFree(d_bid); (void)hipFree(d_cost); (void)hipFree(d_rev); (void)hipFree(d_clk); (void)hipFree(d_conv); (void)hipFree(d_u);
+        if (err != hipSuccess) return fail(ADC_EHIP, hipGetErrorString(err));
+        if (e2 != hipSuccess) return fail(ADC_EHIP, hipGetErrorString(e2));
+        return (int)ADC_OK;
+    };
+    hipError_t err = hipSuccess;
+    if (do_update && prev_bids_nk) {
+        if (hipMalloc((void **)&d_bid, nk * 4) != hipSuccess || hipMalloc((void **)&d_clk, nk * 4) != hipSuccess ||
+            hipMalloc((void **)&d_cost, nk * 4) != hipSuccess || hipMalloc((void **)&d_conv, nk * 4) != hipSuccess ||
+            hipMalloc((void **)&d_rev, nk * 4) != hipSuccess) { (void)done(hipSuccess); return fail(ADC_ENOMEM, "hipMalloc failed"); }
+        err = hipMemcpyAsync(d_bid, bids32.data(), nk * 4, hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_clk, clicks_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_cost, cost_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_conv, conv_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
+        if (err == hipSuccess) err = hipMemcpyAsync(d_rev, rev_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
+    }
+    if (err == hipSuccess && replay_u_nk && do_act) {
+        if (hipMalloc((void **)&d_u, nk * 8) != hipSuccess) { (void)done(hipSuccess); return fail(ADC_ENOMEM, "hipMalloc failed"); }
+        err = hipMemcpyAsync(d_u, replay_u_nk, nk * 8, hipMemcpyHostToDevice, e->stream);
+    }
+    if (err == hipSuccess) {
+        if (do_update) e->interp_updates += 1;        // (before the launch: a failure leaves the count high, never low)
+        hipLaunchKernelGGL(k_interp_step, dim3((unsigned)e->v.N), dim3(256), 0, e->stream, e->v, e->ip, (const float *)d_bid,
+                           d_clk ? d_clk : e->v.clk, d_cost ? d_cost : e->v.cost, d_conv ? d_conv : e->v.conv, d_rev ? d_rev : e->v.rev,
+                           do_update, do_act, (const double *)d_u, budget_override, e->d_bids, e->d_budget);
+        err = hipGetLastError();
+    }
+    return done(err);
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_interp_update(adc_engine *e, const double *prev_bids_nk, const int32_t *clicks_nk, const float *cost_nk,
+                                        const int32_t *conversions_nk, const float *revenue_nk)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const int given = (prev_bids_nk != nullptr) + (clicks_nk != nullptr) + (cost_nk != nullptr) + (conversions_nk != nullptr) +
+                      (revenue_nk != nullptr);
+    if (given != 0 && given != 5) return fail(ADC_EINVAL, "pass all of prev_bids/clicks/cost/conversions/revenue, or none");
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    if (prev_bids_nk) {
+        const size_t nk = (size_t)e->v.N * e->v.K;
+        for (size_t i = 0; i < nk; ++i)
+            if (!std::isfinite(prev_bids_nk[i])) return fail(ADC_EINVAL, "previous bids must be finite");
+    }
+    if (!interp_room(e, 1)) return fail(ADC_EINVAL, "the interpolation agent's capacity is full: one more update could overflow it");
+    ENGINE_GUARD(e);
+    return interp_launch(e, prev_bids_nk, clicks_nk, cost_nk, conversions_nk, revenue_nk, 1, 0, nullptr, 0.0f);
+}
+
+ADC_EXPORT int adc_engine_interp_act(adc_engine *e, float budget_override, const double *replay_uniforms_nk)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    ENGINE_GUARD(e);
+    return interp_launch(e, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, replay_uniforms_nk, budget_override);
+}
+
+ADC_EXPORT int adc_engine_interp_step(adc_engine *e, float budget_override)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    if (!interp_room(e, 1)) return fail(ADC_EINVAL, "the interpolation agent's capacity is full: one more update could overflow it");
+    ENGINE_GUARD_STEP(e);
+    return interp_step_chained(e, budget_override);
+}
+
+ADC_EXPORT int adc_engine_interp_state(adc_engine *e, float *ave_rpc_nk, int32_t *num_rpc_obs_nk, float *ave_sctr_nk,
+                                       int32_t *num_sctr_obs_nk, double *max_observed_nk, int32_t *bid_index_nk, double *budget_n, double *profit_beliefs_n,
+                                       double *cost_beliefs_n)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    const size_t n = (size_t)e->v.N, nk = n * e->v.K;
+    const InterpView &p = e->ip;
+    if (ave_rpc_nk) HIP_TRY(hipMemcpyAsync(ave_rpc_nk, p.ave_rpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (num_rpc_obs_nk) HIP_TRY(hipMemcpyAsync(num_rpc_obs_nk, p.n_rpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (ave_sctr_nk) HIP_TRY(hipMemcpyAsync(ave_sctr_nk, p.ave_sctr, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (num_sctr_obs_nk) HIP_TRY(hipMemcpyAsync(num_sctr_obs_nk, p.n_sctr, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (max_observed_nk) HIP_TRY(hipMemcpyAsync(max_observed_nk, p.max_obs, nk * 8, hipMemcpyDeviceToHost, e->stream));
+    if (bid_index_nk) HIP_TRY(hipMemcpyAsync(bid_index_nk, p.last_index, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (budget_n) HIP_TRY(hipMemcpyAsync(budget_n, p.budget, n * 8, hipMemcpyDeviceToHost, e->stream));
+    if (profit_beliefs_n) HIP_TRY(hipMemcpyAsync(profit_beliefs_n, p.profit, n * 8, hipMemcpyDeviceToHost, e->stream));
+    if (cost_beliefs_n) HIP_TRY(hipMemcpyAsync(cost_beliefs_n, p.cost, n * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_interp_entries(adc_engine *e, int32_t *capacity, int32_t *n_clicks_nk, uint16_t *clicks_cent_cnk,
+                                         float *ave_clicks_cnk, int32_t *clicks_count_cnk, int32_t *n_cpc_nk, uint16_t *cpc_cent_cnk,
+                                         double *ave_cpc_cnk, int32_t *cpc_count_cnk)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+    const InterpView &p = e->ip;
+    const size_t nk = (size_t)e->v.N * e->v.K, slots = nk * (size_t)p.cap;
+    if (capacity) *capacity = p.cap;
+    if (n_clicks_nk) HIP_TRY(hipMemcpyAsync(n_clicks_nk, p.n_clk, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (clicks_cent_cnk) HIP_TRY(hipMemcpyAsync(clicks_cent_cnk, p.clk_cent, slots * 2, hipMemcpyDeviceToHost, e->stream));
+    if (ave_clicks_cnk) HIP_TRY(hipMemcpyAsync(ave_clicks_cnk, p.clk_ave, slots * 4, hipMemcpyDeviceToHost, e->stream));
+    if (clicks_count_cnk) HIP_TRY(hipMemcpyAsync(clicks_count_cnk, p.clk_cnt, slots * 4, hipMemcpyDeviceToHost, e->stream));
+    if (n_cpc_nk) HIP_TRY(hipMemcpyAsync(n_cpc_nk, p.n_cpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
+    if (cpc_cent_cnk) HIP_TRY(hipMemcpyAsync(cpc_cent_cnk, p.cpc_cent, slots * 2, hipMemcpyDeviceToHost, e->stream));
+    if (ave_cpc_cnk) HIP_TRY(hipMemcpyAsync(ave_cpc_cnk, p.cpc_ave, slots * 8, hipMemcpyDeviceToHost, e->stream));
+    if (cpc_count_cnk) HIP_TRY(hipMemcpyAsync(cpc_count_cnk, p.cpc_cnt, slots * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
 // ---- `days` days of the device-resident loop in one call.  Optionally (adc_engine_day_graph_enable) two consecutive
 // days (both step parities) are captured once as a hipGraph and replayed.  Measured on MI355X at 1-256 envs x 100
 // keywords (tools/measure_small_loop.py): 28-50 us per day either way - the 7 dependent kernels of a day are bound by
@@ -2322,6 +2550,9 @@ int one_day(adc_engine *e, int policy, float budget)
     // (the policy kernels and the step are one chain: from the third day on they run group by group where the engine groups at all)
     if (policy == ADC_POLICY_ZERO_MARGIN) {
         if ((rc = agent_step_chained(e, budget))) return rc;
+        if (e->have_curves && (rc = ideal_step_chained(e))) return rc;
+    } else if (policy == ADC_POLICY_INTERPOLATION) {
+        if ((rc = interp_step_chained(e, budget))) return rc;
         if (e->have_curves && (rc = ideal_step_chained(e))) return rc;
     } else if (policy == ADC_POLICY_ORACLE) {
         if ((rc = ideal_step_chained(e))) return rc;
@@ -2342,9 +2573,14 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
 {
     ENGINE_GUARD(e);
     if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
-    if (policy != ADC_POLICY_FIXED_ACTIONS && policy != ADC_POLICY_ZERO_MARGIN && policy != ADC_POLICY_ORACLE)
+    if (policy != ADC_POLICY_FIXED_ACTIONS && policy != ADC_POLICY_ZERO_MARGIN && policy != ADC_POLICY_ORACLE &&
+        policy != ADC_POLICY_INTERPOLATION)
         return fail(ADC_EINVAL, "unknown policy");
     if (policy == ADC_POLICY_ZERO_MARGIN && !e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
+    if (policy == ADC_POLICY_INTERPOLATION) {
+        if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+        if (days > 0 && !interp_room(e, days)) return fail(ADC_EINVAL, "the interpolation agent's capacity would overflow within these days");
+    }
     if (policy == ADC_POLICY_ORACLE && !e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
     if (days < 0) return fail(ADC_EINVAL, "days < 0");
     int rc;
@@ -2369,6 +2605,7 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
     const adc_engine::StepPlan plan = e->v.model == ADC_MODEL_IMPLICIT ? plan_step(e) : adc_engine::StepPlan{false, false, false};
     now.v = e->v; now.pol = e->pol;
     now.have_agent = e->have_agent; now.have_curves = e->have_curves; now.have_ideal = e->have_ideal;
+    now.ip = e->ip; now.have_interp = e->have_interp;
     now.mean_volume_hint = e->mean_volume_hint; now.fast_tiles_per_wg = e->fast_tiles_per_wg;
     now.lists = plan.lists;                 // (which variant of the fast pass launch_step picks)
     now.rest = plan.rest;                   // (... and whether k_step_rest_of_day follows the row kernel)
@@ -2416,6 +2653,7 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
         if ((rc = join_groups(e))) return rc;
         e->last_groups = 1;
         e->needs_fork = e->api_since_step = true;
+        if (policy == ADC_POLICY_INTERPOLATION) e->interp_updates += 2;     // (counted before the launch: a failed one errs on the safe side)
         HIP_TRY(hipGraphLaunch(e->day_graph, e->stream));
         e->step_serial += 2;
         e->stream_steps += 2;

@@ -466,13 +466,74 @@ class StepEngine:
                                                                                       "num_sctr_obs", "max_bids"))))
         return st
 
+    # ---- NaiveInterpolationStrategy, one agent per env (parts/kernel_interp_agent.inc) ----------------------------------
+    def interp_init(self, threshold=-0.2, bid_step=0.03, allowed_bids=None, capacity=0, seeds=None):
+        """empty caches, own last bid 0.01; capacity 0 = min(300, max_days + 1) interpolation points per keyword"""
+        g = np.ascontiguousarray(np.linspace(0.01, 3.00, 300) if allowed_bids is None else allowed_bids, dtype=np.float64).reshape(-1)
+        sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
+        check(self._lib.adc_engine_interp_init(self._h, float(threshold), float(bid_step), g.ctypes.data, int(g.size), int(capacity),
+                                               None if sd is None else sd.ctypes.data))
+
+    def interp_set_allowed_bids(self, allowed_bids):
+        g = np.ascontiguousarray(allowed_bids, dtype=np.float64).reshape(-1)
+        check(self._lib.adc_engine_interp_set_allowed_bids(self._h, g.ctypes.data, int(g.size)))
+
+    def interp_update(self, prev_bids=None, clicks=None, cost=None, conversions=None, revenue=None):
+        """host arrays [N, K] (all five), or none = the agent's own last bids and the engine's last observation"""
+        if all(x is None for x in (prev_bids, clicks, cost, conversions, revenue)):
+            check(self._lib.adc_engine_interp_update(self._h, None, None, None, None, None))
+            return
+        shape = (self.num_envs, self.num_keywords)
+        b = np.ascontiguousarray(np.asarray(prev_bids, dtype=np.float64).reshape(shape))
+        c = np.ascontiguousarray(np.asarray(clicks).reshape(shape), dtype=np.int32)
+        x = np.ascontiguousarray(np.asarray(cost).reshape(shape), dtype=np.float32)
+        v = np.ascontiguousarray(np.asarray(conversions).reshape(shape), dtype=np.int32)
+        r = np.ascontiguousarray(np.asarray(revenue).reshape(shape), dtype=np.float32)
+        check(self._lib.adc_engine_interp_update(self._h, b.ctypes.data, c.ctypes.data, x.ctypes.data, v.ctypes.data, r.ctypes.data))
+
+    def interp_act(self, budget_override=0.0, replay_uniforms=None):
+        u = None
+        if replay_uniforms is not None:
+            u = np.ascontiguousarray(np.asarray(replay_uniforms, dtype=np.float64).reshape(self.num_envs, self.num_keywords))
+        check(self._lib.adc_engine_interp_act(self._h, float(budget_override), None if u is None else u.ctypes.data))
+
+    def interp_step(self, budget_override=0.0):
+        check(self._lib.adc_engine_interp_step(self._h, float(budget_override)))
+
+    def interp_state(self):
+        """rpc / sctr caches, max_observed and the last bid's grid index (-1: none) [N, K]; the last act's budget, profit_beliefs, cost_beliefs [N] (float64)"""
+        shape, n = (self.num_envs, self.num_keywords), self.num_envs
+        st = dict(ave_rpc=np.zeros(shape, np.float32), num_rpc_obs=np.zeros(shape, np.int32), ave_sctr=np.zeros(shape, np.float32),
+                  num_sctr_obs=np.zeros(shape, np.int32), max_observed=np.zeros(shape, np.float64), bid_index=np.zeros(shape, np.int32),
+                  budget=np.zeros(n, np.float64),
+                  profit_beliefs=np.zeros(n, np.float64), cost_beliefs=np.zeros(n, np.float64))
+        check(self._lib.adc_engine_interp_state(self._h, *(st[k].ctypes.data for k in (
+            "ave_rpc", "num_rpc_obs", "ave_sctr", "num_sctr_obs", "max_observed", "bid_index", "budget", "profit_beliefs",
+            "cost_beliefs"))))
+        return st
+
+    def interp_entries(self):
+        """the interpolation points: dict of [N, K] list lengths and [N, K, capacity] slots (ascending cents in the first n)"""
+        cap = C.c_int32(0)
+        check(self._lib.adc_engine_interp_entries(self._h, C.byref(cap), *([None] * 8)))
+        c, shape = cap.value, (self.num_envs, self.num_keywords)
+        st = dict(n_clicks=np.zeros(shape, np.int32), clicks_cent=np.zeros((c,) + shape, np.uint16), ave_clicks=np.zeros((c,) + shape, np.float32),
+                  clicks_count=np.zeros((c,) + shape, np.int32), n_cpc=np.zeros(shape, np.int32), cpc_cent=np.zeros((c,) + shape, np.uint16),
+                  ave_cpc=np.zeros((c,) + shape, np.float64), cpc_count=np.zeros((c,) + shape, np.int32))
+        check(self._lib.adc_engine_interp_entries(self._h, None, *(st[k].ctypes.data for k in (
+            "n_clicks", "clicks_cent", "ave_clicks", "clicks_count", "n_cpc", "cpc_cent", "ave_cpc", "cpc_count"))))
+        for k in ("clicks_cent", "ave_clicks", "clicks_count", "cpc_cent", "ave_cpc", "cpc_count"):
+            st[k] = np.moveaxis(st[k], 0, -1)
+        st["capacity"] = c
+        return st
+
     def get_actions(self):
         bids = np.zeros((self.num_envs, self.num_keywords), np.float32)
         budget = np.zeros(self.num_envs, np.float32)
         check(self._lib.adc_engine_get_actions(self._h, bids.ctypes.data, budget.ctypes.data))
         return bids, budget
 
-    POLICIES = {"fixed": 0, "zero_margin": 1, "oracle": 2}
+    POLICIES = {"fixed": 0, "zero_margin": 1, "oracle": 2, "interpolation": 3}
 
     # ---- multi-GPU: the episode-metric all-reduce (RCCL behind the C ABI; adcraft_amd/comm.py brings it up) ----------
     def comm_unique_id(self):

@@ -399,16 +399,51 @@ int adc_engine_agent_step(adc_engine *e, float budget_override);
 /* caches to host (any pointer may be NULL): ave_rpc, num_rpc_obs, ave_sctr, num_sctr_obs, max_bids, each [N*K] */
 int adc_engine_agent_state(adc_engine *e, float *ave_rpc_nk, int32_t *num_rpc_obs_nk, float *ave_sctr_nk,
                            int32_t *num_sctr_obs_nk, double *max_bids_nk);
+/* NaiveInterpolationStrategy (adcraft/baselines/interpolated_expectations.py:298-439), one agent per env.  Its caches: the
+ * rpc / sctr cache of the zero-margin agent, and per keyword two lists of interpolation points in cents 1..300 (keys outside
+ * $0.01-$3.00 are only remembered through max_observed, the largest key seen): every observation creates or updates a
+ * float32 mean of the clicks, an observation with clicks > 0 a float64 mean of cost / clicks.  Device memory: 24 bytes per
+ * keyword and slot of capacity, plus 56 bytes per keyword.  The lists gain at most one point per update, so `capacity`
+ * slots hold them while the updates since init number at most `capacity`; 0 = min(300, max_days + 1), at most 300 (which
+ * never overflows).  An update that could overflow is refused with ADC_EINVAL before anything is enqueued; run_days checks
+ * all of its days up front.
+ * init: empty caches, own last bid 0.01 (the notebooks' first previous_action), the agent's Philox stream (stage 13) keyed by
+ * seeds_n (NULL: derived from adc_config.seed and the env id).  threshold = profit_acquisition_threshold; allowed_bids: 1 to
+ * 2048 finite values in any order.  Calling it again resets the agent; the capacity stays what the first call fixed. */
+int adc_engine_interp_init(adc_engine *e, double profit_acquisition_threshold, double bid_step, const double *allowed_bids,
+                           int32_t n_bids, int32_t capacity, const uint64_t *seeds_n);
+/* agent.allowed_bids = bids (the notebooks grow the grid every day); same rules as at init */
+int adc_engine_interp_set_allowed_bids(adc_engine *e, const double *bids, int32_t n);
+/* update_all_caches (:400-403) with one observation per keyword: host arrays [N*K] (all five: the previous bids, finite, keyed
+ * as float32; clicks, cost, conversions, revenue), or all NULL = the agent's own last bids and the engine's last observation
+ * where it lies on the device */
+int adc_engine_interp_update(adc_engine *e, const double *prev_bids_nk, const int32_t *clicks_nk, const float *cost_nk,
+                             const int32_t *conversions_nk, const float *revenue_nk);
+/* sample_action (:405-439) into the engine's action buffers: the bid as the env rounds it (to cents, >= 0.01), the budget as
+ * the env rounds the agent's (cents, float32) or budget_override if > 0.  replay_uniforms_nk (host double [N*K], nullable):
+ * the rng.random() value rng.choice uses for each keyword instead of the agent's stream (read only where a draw happens). */
+int adc_engine_interp_act(adc_engine *e, float budget_override, const double *replay_uniforms_nk);
+/* update from the device (own last bids, last observation) + act, one launch, no host sync (the closed loop's per-step call) */
+int adc_engine_interp_step(adc_engine *e, float budget_override);
+/* caches to host (any pointer may be NULL): [N*K] ave_rpc, num_rpc_obs, ave_sctr, num_sctr_obs, max_observed, the grid index
+ * of the last act's bid (-1: no draw, bid 0.01); [N] the last act's float64 budget, profit_beliefs, cost_beliefs */
+int adc_engine_interp_state(adc_engine *e, float *ave_rpc_nk, int32_t *num_rpc_obs_nk, float *ave_sctr_nk, int32_t *num_sctr_obs_nk,
+                            double *max_observed_nk, int32_t *bid_index_nk, double *budget_n, double *profit_beliefs_n, double *cost_beliefs_n);
+/* the interpolation points to host (any pointer may be NULL), slot-major [capacity][N*K], ascending cents in the first
+ * n_*_nk slots: the clicks list (cent, ave_clicks, count) and the cpc list (cent, ave_cpc, count) */
+int adc_engine_interp_entries(adc_engine *e, int32_t *capacity, int32_t *n_clicks_nk, uint16_t *clicks_cent_cnk, float *ave_clicks_cnk,
+                              int32_t *clicks_count_cnk, int32_t *n_cpc_nk, uint16_t *cpc_cent_cnk, double *ave_cpc_cnk,
+                              int32_t *cpc_count_cnk);
 /* the engine's device action buffers to host (what a policy above, adc_engine_sample_actions or
  * adc_engine_set_flat_actions_device last wrote) */
 int adc_engine_get_actions(adc_engine *e, float *bids_nk, float *budget_n);
 /* `days` consecutive days of the device-resident loop in one call: per day, the policy writes the action
  * (FIXED_ACTIONS: whatever the action buffers hold; ZERO_MARGIN: adc_engine_agent_step, plus adc_engine_ideal_step when
- * curves are built; ORACLE: adc_engine_ideal_step + adc_engine_policy_oracle), then the env steps.  Asynchronous on
+ * curves are built; INTERPOLATION: the same with adc_engine_interp_step; ORACLE: adc_engine_ideal_step + adc_engine_policy_oracle), then the env steps.  Asynchronous on
  * the engine's stream.  adc_engine_day_graph_enable(e, 1) makes it replay pairs of days from a captured hipGraph
  * (same results; measured no faster on MI355X - the dependent kernels of a day are latency-, not launch-bound - and an engine
  * whose chain of days runs as env groups, see adc_engine_env_groups, keeps the plain chain, which is the faster of the two). */
-enum adc_policy { ADC_POLICY_FIXED_ACTIONS = 0, ADC_POLICY_ZERO_MARGIN = 1, ADC_POLICY_ORACLE = 2 };
+enum adc_policy { ADC_POLICY_FIXED_ACTIONS = 0, ADC_POLICY_ZERO_MARGIN = 1, ADC_POLICY_ORACLE = 2, ADC_POLICY_INTERPOLATION = 3 };
 int adc_engine_run_days(adc_engine *e, int policy, int32_t days, float budget);
 int adc_engine_day_graph_enable(adc_engine *e, int enabled);
 /* per (env, keyword) metric sums to host (any pointer may be NULL): profit in cents, ideal, ideal with <= 0 -> 1;
@@ -481,6 +516,17 @@ int adc_sample_random_keyword(uint64_t key, uint32_t keyword, uint32_t serial, f
  * z_mid2_out (may be NULL): the two middle normals z_lo, z_hi.  n_samples <= 2^20. */
 int adc_explicit_curve_host(uint64_t key, uint32_t tick, int32_t keyword, int32_t n_samples, float impression_thresh, float a, float b,
                             const double *bid_grid, int32_t n_bids, double *ir_out, double *cpc_out, double *z_mid2_out);
+/* one keyword's act of the interpolation agent, on the host: the same code as the device's (adc_interp.h).  The cache is given
+ * as the device keeps it (interpolation points in ascending cents 1..300; every cpc cent also a clicks cent); u = the uniform
+ * rng.choice uses.  Out: margin_out / cost_out [n_bids] over the whole grid (get_expected_profit_per_bid_from_cache), *index_out
+ * (-1: no draw), *bid_out (0.01 without a draw) and *mass_out (nullable: np.sum of the acquisition function up to end_index) */
+int adc_interp_act_host(float ave_rpc, int32_t num_rpc_obs, float ave_sctr, int32_t num_sctr_obs, double max_observed,
+                        double profit_acquisition_threshold, double bid_step, const double *allowed_bids, int32_t n_bids,
+                        int32_t n_clicks, const uint16_t *clicks_cent, const float *ave_clicks, int32_t n_cpc, const uint16_t *cpc_cent,
+                        const double *ave_cpc, double u, double *margin_out, double *cost_out, double *bid_out, int32_t *index_out,
+                        double *mass_out);
+/* the cache key of a bid: float(bidstr(bid)) = round(float(float32 bid), 2) */
+double adc_interp_key_host(float bid);
 /* diagnostic: the stream's generator (Philox4x32, the stream's round count) evaluated on the device for n counters ctr4[n][4]
  * and keys key2[n][2] -> out4[n][4]; tests compare it with the CPU battery's generator (oracle/stream_battery.c) */
 int adc_debug_philox_device(int device_id, int64_t n, const uint32_t *ctr4, const uint32_t *key2, uint32_t *out4);

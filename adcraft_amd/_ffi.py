@@ -114,6 +114,8 @@ def lib():
         "adc_engine_generate_explicit_keywords": ([vp, C.c_uint32, vp], C.c_int),
         "adc_engine_set_limits": ([vp, i32, f64], C.c_int),
         "adc_engine_set_drift": ([vp, i32, f32, f32, f32], C.c_int),
+        "adc_engine_set_drift_mask": ([vp, vp], C.c_int),
+        "adc_engine_set_env_drift": ([vp, vp], C.c_int),
         "adc_engine_get_rng_state": ([vp, vp, vp], C.c_int),
         "adc_engine_set_rng_state": ([vp, vp, vp], C.c_int),
         "adc_engine_get_episode_state": ([vp, vp, vp], C.c_int),

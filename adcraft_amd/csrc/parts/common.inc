@@ -69,6 +69,10 @@ struct View {
     int64_t *cum_cents;       // [N] IMPLICIT
     double *cum;              // [N] EXPLICIT
     uint8_t *drift_pending;   // [N]
+    const uint32_t *drift_bits;   // [N][ceil(K/32)] the keywords that move at update_keywords(), bit k & 31 of word k >> 5 of the env's row
+                                  // (whole words per env); null = every keyword (adc_engine_set_drift_mask)
+    const float *drift_rate;      // [N][3] the env's drift magnitudes vol, ctr, cvr; null = drift_vol / drift_ctr / drift_cvr above
+                                  // (adc_engine_set_env_drift)
     uint8_t *exact_hint;      // [N] the budget bound on the previous step (a scheduling hint, never a result).  IMPLICIT: 1 = the fast pass also
                               // lists its clicked wins for k_step_click_walk, 2 = skip the fast pass, the row kernel computes the env alone,
                               // 3 / 4 (within a step) = the fast pass ran and k_step_click_walk handed the env to the row kernel: because the
@@ -321,13 +325,62 @@ __device__ __forceinline__ void apply_drift_coefficients(float uv, float uc, flo
     sctr = adc::clamp01(sctr * (1.0f + us));
 }
 
-// pending drift of one keyword (adcraft/gymnasium_kw_env.py:132-158); `tick_of_draw` = tick of the
-// step whose update_keywords() this is
-__device__ __forceinline__ void drift_keyword(const View &v, uint64_t key, uint32_t tick_of_draw, int k,
-                                              float &vol_mean, float vol_std, float &bctr, float &sctr)
+// View::drift_bits and View::drift_rate are read from the kernel-argument segment where they are used, inside the drift
+// branch: every kernel with a drift site takes the engine view `v` as its first argument, at offset 0, so the helpers below
+// must only be given that `v`.  (Read through `v`, the two pointers are loaded with the rest of the view at the kernel's entry
+// and hold scalar registers through the whole kernel: the row kernels have none to spare and spill more - 4 to 12 bytes of
+// scratch per lane more in k_step_exact_rows.)  kernel_sparse.inc re-reads its pointers the same way.
+typedef const __attribute__((address_space(4))) View DriftArgView;
+__device__ __forceinline__ DriftArgView *drift_args()
 {
-    const adc::U4 w = adc::draw(key, 0u, adc::ST_DRIFT, (uint32_t)k, tick_of_draw);
-    apply_drift_coefficients(adc::drift_coeff(w.x, v.drift_vol), adc::drift_coeff(w.y, v.drift_ctr), adc::drift_coeff(w.z, v.drift_cvr),
-                             vol_mean, vol_std, bctr, sctr);
+    DriftArgView *p = (DriftArgView *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
 }
 
+// does keyword k of env `env` (of the view) move at update_keywords()?  Every drift site asks this first, inside its drift
+// branch: an unselected keyword keeps vol_mean, bctr and sctr as they are (its draw is simply not taken; nothing else moves)
+__device__ __forceinline__ bool drift_selected(const View &v, int env, int k)
+{
+    const uint32_t *bits = drift_args()->drift_bits;
+    if (!bits) return true;
+    const unsigned int words = ((unsigned int)v.K + 31u) >> 5;       // (N * words < 2^31: N * K does)
+    return ((bits[(unsigned int)env * words + ((unsigned int)k >> 5)] >> (k & 31)) & 1u) != 0u;
+}
+
+// the env's three drift magnitudes (View::drift_rate, or the engine's scalars)
+__device__ __forceinline__ void drift_magnitudes(const View &v, int env, float &a_vol, float &a_ctr, float &a_cvr)
+{
+    const float *rate = drift_args()->drift_rate;
+    if (rate) {
+        const float *r = rate + (size_t)env * 3;
+        a_vol = r[0]; a_ctr = r[1]; a_cvr = r[2];
+    } else {
+        a_vol = v.drift_vol; a_ctr = v.drift_ctr; a_cvr = v.drift_cvr;
+    }
+}
+
+// pending drift of one keyword (adcraft/gymnasium_kw_env.py:132-158); `tick_of_draw` = tick of the
+// step whose update_keywords() this is.  false: the keyword is not selected and nothing was changed (no write-back needed)
+__device__ __forceinline__ bool drift_keyword(const View &v, int env, uint64_t key, uint32_t tick_of_draw, int k,
+                                              float &vol_mean, float vol_std, float &bctr, float &sctr)
+{
+    if (!drift_selected(v, env, k)) return false;
+    float a_vol, a_ctr, a_cvr;
+    drift_magnitudes(v, env, a_vol, a_ctr, a_cvr);
+    const adc::U4 w = adc::draw(key, 0u, adc::ST_DRIFT, (uint32_t)k, tick_of_draw);
+    apply_drift_coefficients(adc::drift_coeff(w.x, a_vol), adc::drift_coeff(w.y, a_ctr), adc::drift_coeff(w.z, a_cvr),
+                             vol_mean, vol_std, bctr, sctr);
+    return true;
+}
+
+// ... read from the parameter planes and written back there (a selected keyword only)
+__device__ __forceinline__ void drift_keyword_planes(const View &v, int env, uint64_t key, uint32_t tick_of_draw, int k)
+{
+    if (!drift_selected(v, env, k)) return;
+    float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k), sc = param_at(v, ADC_P_SCTR, env, k);
+    drift_keyword(v, env, key, tick_of_draw, k, vm, param_at(v, ADC_P_VOL_STD, env, k), bc, sc);
+    param_at(v, ADC_P_VOL_MEAN, env, k) = vm;
+    param_at(v, ADC_P_BCTR, env, k) = bc;
+    param_at(v, ADC_P_SCTR, env, k) = sc;
+}

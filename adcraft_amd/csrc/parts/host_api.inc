@@ -56,6 +56,8 @@ struct adc_engine {
     float mean_volume_hint = -1.0f;     // mean of the vol_mean plane (< 0: unknown); a scheduling hint only, results never depend on it
     bool volume_hint_dirty = true;      // keyword parameters changed since the hint was taken
     double *d_hint_sum = nullptr;
+    uint32_t *d_drift_bits = nullptr;   // [N][ceil(K/32)] adc_engine_set_drift_mask's selection, allocated at its first non-null call (View::drift_bits)
+    float *d_drift_rate = nullptr;      // [N][3] adc_engine_set_env_drift's magnitudes, allocated at its first non-null call (View::drift_rate)
     unsigned short *d_counts_u16 = nullptr;     // [3][N*K] compact counts (adc_step_out.counts_u16), allocated on first use
     int *d_counts_overflow = nullptr;
     adc_step_out checked_out = {};              // outputs_device_addressable's memo
@@ -205,6 +207,7 @@ inline View group_view(const adc_engine *e, int g, int G, int *e0_out)
     auto at = [](auto *&ptr, size_t off) { if (ptr) ptr += off; };
     at(v.params, ok);
     at(v.key, o); at(v.tick, o); at(v.day, o); at(v.cum_cents, o); at(v.cum, o); at(v.drift_pending, o); at(v.exact_hint, o);
+    at(v.drift_bits, o * ((K + 31) / 32)); at(v.drift_rate, o * 3);
     at(v.flag_list, o); at(v.xover_list, o); at(v.retry_list, o);
     at(v.click_rec, o * kClickSegments * (size_t)v.click_cap); at(v.click_count, o * adc::kTimesteps); at(v.click_tick, o);
     at(v.click_row_hint, o); at(v.click_price_hint, o);
@@ -1078,6 +1081,51 @@ ADC_EXPORT int adc_engine_set_drift(adc_engine *e, int32_t enabled, float drift_
     e->v.drift_on = enabled ? 1 : 0;
     e->v.drift_vol = drift_vol; e->v.drift_ctr = drift_ctr; e->v.drift_cvr = drift_cvr;
     if (!enabled) HIP_TRY(hipMemsetAsync(e->v.drift_pending, 0, (size_t)e->v.N, e->stream));
+    return ADC_OK;
+}
+
+namespace {
+// what adc_engine_set_drift_mask / adc_engine_set_env_drift do before they swap: the pending update_keywords() of every env is
+// the one the previous step scheduled, so it moves the planes under the selection and magnitudes in force when it was
+// scheduled; then nothing in flight reads the old device copy when it is overwritten
+int settle_pending_drift(adc_engine *e)
+{
+    if (e->v.drift_on) {
+        materialize_drift(e);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_set_drift_mask(adc_engine *e, const uint8_t *mask_nk)
+{
+    ENGINE_GUARD(e);
+    { const int rc = settle_pending_drift(e); if (rc) return rc; }
+    if (!mask_nk) { e->v.drift_bits = nullptr; return ADC_OK; }
+    const size_t N = (size_t)e->v.N, K = (size_t)e->v.K, W = (K + 31) / 32;
+    std::vector<uint32_t> bits(N * W, 0u);
+    for (size_t n = 0; n < N; ++n)
+        for (size_t k = 0; k < K; ++k)
+            if (mask_nk[n * K + k]) bits[n * W + k / 32] |= 1u << (k % 32);
+    if (!e->d_drift_bits) { const int rc = dev_alloc(e, &e->d_drift_bits, N * W); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(e->d_drift_bits, bits.data(), N * W * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->v.drift_bits = e->d_drift_bits;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_set_env_drift(adc_engine *e, const float *rates_n3)
+{
+    ENGINE_GUARD(e);
+    { const int rc = settle_pending_drift(e); if (rc) return rc; }
+    if (!rates_n3) { e->v.drift_rate = nullptr; return ADC_OK; }
+    const size_t N = (size_t)e->v.N;
+    if (!e->d_drift_rate) { const int rc = dev_alloc(e, &e->d_drift_rate, N * 3); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(e->d_drift_rate, rates_n3, N * 3 * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->v.drift_rate = e->d_drift_rate;
     return ADC_OK;
 }
 

@@ -325,11 +325,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 4 : ONE ? kRowsMinBlocksOne :
 
     for (int k = tid; k < K; k += BLOCK) {
         if (drift) {
-            float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k), sc = param_at(v, ADC_P_SCTR, env, k);
-            drift_keyword(v, key, tick - 1u, k, vm, param_at(v, ADC_P_VOL_STD, env, k), bc, sc);
-            param_at(v, ADC_P_VOL_MEAN, env, k) = vm;
-            param_at(v, ADC_P_BCTR, env, k) = bc;
-            param_at(v, ADC_P_SCTR, env, k) = sc;
+            drift_keyword_planes(v, env, key, tick - 1u, k);
         }
         s_vol[k] = adc::volume_from_word(adc::volume_word(key, (uint32_t)k, tick), param_at(v, ADC_P_VOL_MEAN, env, k),
                                          param_at(v, ADC_P_VOL_STD, env, k), g_norm_table);
@@ -958,11 +954,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 6 : FRESH ? kRestFreshBlocks 
         bool whole = false;
         if (k < K) {
             if (drift) {
-                float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k), sc = param_at(v, ADC_P_SCTR, env, k);
-                drift_keyword(v, key, tick - 1u, k, vm, param_at(v, ADC_P_VOL_STD, env, k), bc, sc);
-                param_at(v, ADC_P_VOL_MEAN, env, k) = vm;
-                param_at(v, ADC_P_BCTR, env, k) = bc;
-                param_at(v, ADC_P_SCTR, env, k) = sc;
+                drift_keyword_planes(v, env, key, tick - 1u, k);
             }
             vol = adc::volume_from_word(adc::volume_word(key, (uint32_t)k, tick), param_at(v, ADC_P_VOL_MEAN, env, k),
                                         param_at(v, ADC_P_VOL_STD, env, k), g_norm_table);

@@ -98,12 +98,7 @@ __global__ __launch_bounds__(kWave) void k_step_exact(View v, const float *__res
         const bool fast_skipped = MODEL == ADC_MODEL_IMPLICIT_GENERAL && !TAPE && fast_ran && v.exact_hint[env] != 0;
         if (MODEL != ADC_MODEL_IMPLICIT && !TAPE && !replay && (!fast_ran || fast_skipped) && v.drift_on && v.drift_pending[env]) {
             for (int k = lane; k < K; k += kWave) {
-                float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k),
-                      sc = param_at(v, ADC_P_SCTR, env, k);
-                drift_keyword(v, key, tick - 1u, k, vm, param_at(v, ADC_P_VOL_STD, env, k), bc, sc);
-                param_at(v, ADC_P_VOL_MEAN, env, k) = vm;
-                param_at(v, ADC_P_BCTR, env, k) = bc;
-                param_at(v, ADC_P_SCTR, env, k) = sc;
+                drift_keyword_planes(v, env, key, tick - 1u, k);
             }
         }
         for (int k = lane; k < K; k += kWave) {
@@ -503,6 +498,7 @@ __global__ __launch_bounds__(kWave) void k_step_exact(View v, const float *__res
         // update_keywords() with the recorded coefficient vectors (gymnasium_kw_env.py:132-158, called at :246)
         const size_t NK = (size_t)v.N * K;
         for (int k = lane; k < K; k += kWave) {
+            if (!drift_selected(v, env, k)) continue;       // (the selection gates the recorded coefficients too)
             const size_t i = (size_t)env * K + k;
             float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k), sc = param_at(v, ADC_P_SCTR, env, k);
             apply_drift_coefficients(tp.drift_uniforms[i], tp.drift_uniforms[NK + i], tp.drift_uniforms[2 * NK + i],

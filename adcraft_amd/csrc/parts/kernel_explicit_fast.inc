@@ -40,8 +40,7 @@ __global__ __launch_bounds__(256) void k_step_explicit_fast(View v, const float 
         float vol_mean = param_at(v, ADC_P_VOL_MEAN, env, k);
         const float vol_std = param_at(v, ADC_P_VOL_STD, env, k);
         float bctr = param_at(v, ADC_P_BCTR, env, k), sctr = param_at(v, ADC_P_SCTR, env, k);
-        if (drift) {
-            drift_keyword(v, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr);
+        if (drift && drift_keyword(v, env, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr)) {
             param_at(v, ADC_P_VOL_MEAN, env, k) = vol_mean;
             param_at(v, ADC_P_BCTR, env, k) = bctr;
             param_at(v, ADC_P_SCTR, env, k) = sctr;
@@ -163,8 +162,7 @@ __global__ __launch_bounds__(256) void k_step_general_fast(View v, const float *
         float vol_mean = param_at(v, ADC_P_VOL_MEAN, env, k);
         const float vol_std = param_at(v, ADC_P_VOL_STD, env, k);
         float bctr = param_at(v, ADC_P_BCTR, env, k), sctr = param_at(v, ADC_P_SCTR, env, k);
-        if (drift) {
-            drift_keyword(v, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr);
+        if (drift && drift_keyword(v, env, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr)) {
             param_at(v, ADC_P_VOL_MEAN, env, k) = vol_mean;
             param_at(v, ADC_P_BCTR, env, k) = bctr;
             param_at(v, ADC_P_SCTR, env, k) = sctr;
@@ -278,8 +276,7 @@ __global__ __launch_bounds__(256) void k_step_general_small(View v, const float 
     float vol_mean = param_at(v, ADC_P_VOL_MEAN, env, k), bctr = param_at(v, ADC_P_BCTR, env, k), sctr = param_at(v, ADC_P_SCTR, env, k);
     const float vol_std = param_at(v, ADC_P_VOL_STD, env, k);
     if (v.drift_on && v.drift_pending[env]) {
-        drift_keyword(v, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr);
-        if (lane == 0) {
+        if (drift_keyword(v, env, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr) && lane == 0) {
             param_at(v, ADC_P_VOL_MEAN, env, k) = vol_mean;
             param_at(v, ADC_P_BCTR, env, k) = bctr;
             param_at(v, ADC_P_SCTR, env, k) = sctr;
@@ -481,8 +478,7 @@ __global__ __launch_bounds__(KMAX, KMAX == kXDayK ? 5 : 4) void k_step_float_day
     if (valid) {
         float vol_mean = param_at(v, ADC_P_VOL_MEAN, env, k), bctr = param_at(v, ADC_P_BCTR, env, k), sctr = param_at(v, ADC_P_SCTR, env, k);
         const float vol_std = param_at(v, ADC_P_VOL_STD, env, k);
-        if (hinted && v.drift_on && v.drift_pending[env]) {
-            drift_keyword(v, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr);
+        if (hinted && v.drift_on && v.drift_pending[env] && drift_keyword(v, env, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr)) {
             param_at(v, ADC_P_VOL_MEAN, env, k) = vol_mean;
             param_at(v, ADC_P_BCTR, env, k) = bctr;
             param_at(v, ADC_P_SCTR, env, k) = sctr;

@@ -178,8 +178,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     }
     float vol_mean = raw.vol_mean, bctr = raw.bctr, sctr = raw.sctr;
     const float vol_std = raw.vol_std, loc = raw.loc, scale = raw.scale, mu = raw.mu, sd = raw.sd, bid = raw.bid;
-    if (valid && raw.drift) {
-        drift_keyword(v, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr);
+    if (valid && raw.drift && drift_keyword(v, env, key, tick - 1u, k, vol_mean, vol_std, bctr, sctr)) {
         param_at(v, ADC_P_VOL_MEAN, env, k) = vol_mean;
         param_at(v, ADC_P_BCTR, env, k) = bctr;
         param_at(v, ADC_P_SCTR, env, k) = sctr;

@@ -156,10 +156,11 @@ __global__ __launch_bounds__(kFastBlock, ADC_SPARSE_WAVES) void k_step_implicit_
         const int env = tile_index / tiles;
         const int k0 = (tile_index - env * tiles) * kFastBlock;
         const bool valid = k0 + (int)tid < v.K;
-        if (valid && h.drift) {               // update_keywords() of the previous step, volume part (gymnasium_kw_env.py:136-141)
+        if (valid && h.drift && drift_selected(v, env, k0 + (int)tid)) {      // update_keywords() of the previous step, volume part (gymnasium_kw_env.py:136-141)
             const adc::U4 w = adc::draw(h.key, 0u, adc::ST_DRIFT, (uint32_t)(k0 + (int)tid), h.tick - 1u);
-            float unused_b = 0.0f, unused_s = 0.0f;
-            apply_drift_coefficients(adc::drift_coeff(w.x, v.drift_vol), 0.0f, 0.0f, p.vol_mean, p.vol_std, unused_b, unused_s);
+            float a_vol, a_ctr, a_cvr, unused_b = 0.0f, unused_s = 0.0f;
+            drift_magnitudes(v, env, a_vol, a_ctr, a_cvr);
+            apply_drift_coefficients(adc::drift_coeff(w.x, a_vol), 0.0f, 0.0f, p.vol_mean, p.vol_std, unused_b, unused_s);
             lane_elem(v.params + ((size_t)env * v.K + k0) + ADC_P_VOL_MEAN * plane, tid) = p.vol_mean;
         }
         unsigned int *const scratch = reinterpret_cast<unsigned int *>(ring);
@@ -218,10 +219,11 @@ __global__ __launch_bounds__(kFastBlock, ADC_SPARSE_WAVES) void k_step_implicit_
     // and a path on which the next tile's loads look issued but not delivered puts the wait for them there - behind the stores)
     if (!head.skip) {                           // (block-uniform; a skipped env contributes nothing to acc_*)
     // ---- phase 1: one lane per keyword ---------------------------------------------------------
-    if (valid && head.drift) {                  // update_keywords() of the previous step, the two rates (gymnasium_kw_env.py:142-158)
+    if (valid && head.drift && drift_selected(v, env, k0 + (int)tid)) {      // update_keywords() of the previous step, the two rates (gymnasium_kw_env.py:142-158)
         const adc::U4 w = adc::draw(key, 0u, adc::ST_DRIFT, (uint32_t)(k0 + (int)tid), tick - 1u);
-        float unused_m = 0.0f;
-        apply_drift_coefficients(0.0f, adc::drift_coeff(w.y, v.drift_ctr), adc::drift_coeff(w.z, v.drift_cvr), unused_m, 0.0f, raw.bctr, raw.sctr);
+        float a_vol, a_ctr, a_cvr, unused_m = 0.0f;
+        drift_magnitudes(v, env, a_vol, a_ctr, a_cvr);
+        apply_drift_coefficients(0.0f, adc::drift_coeff(w.y, a_ctr), adc::drift_coeff(w.z, a_cvr), unused_m, 0.0f, raw.bctr, raw.sctr);
         float *row = v.params + ((size_t)env * v.K + k0);
         lane_elem(row + ADC_P_BCTR * plane, tid) = raw.bctr;
         lane_elem(row + ADC_P_SCTR * plane, tid) = raw.sctr;

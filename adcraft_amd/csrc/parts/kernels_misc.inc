@@ -10,11 +10,7 @@ __global__ void k_materialize_drift(View v)
     const uint64_t key = v.key[env];
     const uint32_t tick = v.tick[env];
     for (int k = threadIdx.x; k < v.K; k += blockDim.x) {
-        float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k), sc = param_at(v, ADC_P_SCTR, env, k);
-        drift_keyword(v, key, tick - 1u, k, vm, param_at(v, ADC_P_VOL_STD, env, k), bc, sc);
-        param_at(v, ADC_P_VOL_MEAN, env, k) = vm;
-        param_at(v, ADC_P_BCTR, env, k) = bc;
-        param_at(v, ADC_P_SCTR, env, k) = sc;
+        drift_keyword_planes(v, env, key, tick - 1u, k);
     }
     __syncthreads();
     if (threadIdx.x == 0) v.drift_pending[env] = 0;
@@ -27,11 +23,7 @@ __global__ void k_force_drift(View v)
     const uint64_t key = v.key[env];
     const uint32_t tick = v.tick[env];
     for (int k = threadIdx.x; k < v.K; k += blockDim.x) {
-        float vm = param_at(v, ADC_P_VOL_MEAN, env, k), bc = param_at(v, ADC_P_BCTR, env, k), sc = param_at(v, ADC_P_SCTR, env, k);
-        drift_keyword(v, key, tick, k, vm, param_at(v, ADC_P_VOL_STD, env, k), bc, sc);
-        param_at(v, ADC_P_VOL_MEAN, env, k) = vm;
-        param_at(v, ADC_P_BCTR, env, k) = bc;
-        param_at(v, ADC_P_SCTR, env, k) = sc;
+        drift_keyword_planes(v, env, key, tick, k);
     }
     __syncthreads();
     if (threadIdx.x == 0) v.tick[env] = tick + 1u;    // the draw must not be reused by the next step

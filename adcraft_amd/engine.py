@@ -194,6 +194,32 @@ class StepEngine:
     def set_drift(self, enabled, drift=(0.03, 0.03, 0.03)):
         check(self._lib.adc_engine_set_drift(self._h, 1 if enabled else 0, float(drift[0]), float(drift[1]), float(drift[2])))
 
+    def set_drift_mask(self, mask):
+        """which keywords move at each update_keywords(): None (every keyword), bool [K] (the same for every env) or
+        [N, K].  An explicit selection (the reference's prefix rule for a partial updater_mask is
+        gymnasium_kw_utils.effective_updater_mask); the pending update moves under the selection it was scheduled with.
+        Does not switch drift on: set_drift does."""
+        if mask is None:
+            check(self._lib.adc_engine_set_drift_mask(self._h, None))
+            return
+        m = np.asarray(mask)
+        if m.shape not in ((self.num_keywords,), (self.num_envs, self.num_keywords)):
+            raise ValueError(f"drift mask must have shape ({self.num_keywords},) or ({self.num_envs}, {self.num_keywords}), got {m.shape}")
+        m = np.ascontiguousarray(np.broadcast_to(m.astype(bool), (self.num_envs, self.num_keywords)), dtype=np.uint8)
+        check(self._lib.adc_engine_set_drift_mask(self._h, m.ctypes.data))
+
+    def set_env_drift(self, rates):
+        """per-env drift magnitudes (vol, ctr, cvr - updater_params' numbers): None (set_drift's scalars), [3] (every env)
+        or [N, 3]; the pending update moves under the magnitudes it was scheduled with"""
+        if rates is None:
+            check(self._lib.adc_engine_set_env_drift(self._h, None))
+            return
+        r = np.asarray(rates, dtype=np.float32)
+        if r.shape not in ((3,), (self.num_envs, 3)):
+            raise ValueError(f"drift rates must have shape (3,) or ({self.num_envs}, 3), got {r.shape}")
+        r = np.ascontiguousarray(np.broadcast_to(r, (self.num_envs, 3)))
+        check(self._lib.adc_engine_set_env_drift(self._h, r.ctypes.data))
+
     def get_rng_state(self):
         k = np.zeros(self.num_envs, dtype=np.uint64)
         t = np.zeros(self.num_envs, dtype=np.uint32)
@@ -697,6 +723,20 @@ class ShardedStepEngine:
     def set_limits(self, max_days, loss_threshold):
         for p in self.parts:
             p.set_limits(max_days, loss_threshold)
+
+    def set_drift(self, enabled, drift=(0.03, 0.03, 0.03)):
+        for p in self.parts:
+            p.set_drift(enabled, drift)
+
+    def set_drift_mask(self, mask):
+        m = None if mask is None else np.asarray(mask)
+        for p, b0, b1 in self._each():
+            p.set_drift_mask(None if m is None else m if m.ndim == 1 else m[b0:b1])
+
+    def set_env_drift(self, rates):
+        r = None if rates is None else np.asarray(rates, dtype=np.float32)
+        for p, b0, b1 in self._each():
+            p.set_env_drift(None if r is None else r if r.ndim == 1 else r[b0:b1])
 
     def get_rng_state(self):
         ks, ts = zip(*(p.get_rng_state() for p in self.parts))

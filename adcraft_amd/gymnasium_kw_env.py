@@ -17,8 +17,11 @@ What differs from the reference, on purpose (DESIGN.md "quirks"):
     read-only second walk of that step (adc_engine_outcomes_replay).  step() itself does nothing for it.  An info dict
     read late (after a reset, a parameter change, or - with drift on - after the next step) carries the step's
     per-keyword totals instead and says 'per_click': 'expired';
-  * only updater_mask None or all-True is supported (the only masks the reference's configs use; a
-    partial mask mis-aligns coefficients in the reference, gymnasium_kw_env.py:136-144).
+  * nothing, as to which keywords drift: a partial updater_mask moves what the reference's update_keywords() moves
+    (gymnasium_kw_env.py:130-144 zips num_updates = sum(mask) coefficients with the keyword list, so keyword k moves iff
+    mask[k] and k < sum(mask): gymnasium_kw_utils.effective_updater_mask, SURVEY B-6).  Drift is on while that selection
+    is not empty; the selected keywords move exactly as they would under an all-True mask, the others keep their
+    parameters.
 """
 import weakref
 from typing import Dict, List, Optional
@@ -155,6 +158,7 @@ class BiddingSimulation(_EnvBase):
         self._current_text = "New start\n"
         self.updater_params = updater_params
         self.updater_mask = None
+        self._effective_mask = None       # the keywords update_keywords() moves (None: no updates)
         self.init_volumes = None
         self._device_id = int(kwargs.get("device_id", 0))      # every other extra kwarg is swallowed, like the
         self._implicit = keyword_config is not None            # reference's **kwargs (multi_agent/env.py:31)
@@ -174,19 +178,31 @@ class BiddingSimulation(_EnvBase):
         assert len(new_updater_mask) == self.num_keywords, (
             f"Updater mask length ({len(new_updater_mask)})\n"
             + "must match number of keywords ({self.num_keywords}) to be applied.")   # gymnasium_kw_env.py:107-110
-        m = [bool(x) for x in new_updater_mask]
-        if any(m) and not all(m):
-            raise NotImplementedError("only updater_mask=None or all-True is supported (see module docstring)")
+        was_on = self._drift_on()
         self.updater_mask = list(new_updater_mask)
-        self.num_updates = int(np.sum(self.updater_mask))
+        self.num_updates = int(np.sum(self.updater_mask))                               # :112
+        self._effective_mask = utils.effective_updater_mask(self.updater_mask)
         if self._engine is not None:
-            self._engine.set_drift(all(m) and len(m) > 0, self._drift_coeffs())
+            # the update the last step scheduled still moves under the old mask (the engine applies it before it swaps);
+            # the last step's unread per-click lists are formatted before that, from the parameters that step ran with
+            self._settle_last_outcomes(was_on)
+            self._apply_drift_settings()
+            if was_on:
+                self._params_dirty = True
+                self._epoch += 1
+
+    def _apply_drift_settings(self):
+        """the engine's drift switch and selection from the effective mask: None and all-True select every keyword (no
+        selection on the device), an empty selection keeps drift off"""
+        eff = self._effective_mask
+        self._engine.set_drift_mask(None if eff is None or eff.all() else eff)
+        self._engine.set_drift(self._drift_on(), self._drift_coeffs())
 
     def _drift_coeffs(self):
         return tuple(float(v[1]) for v in self.updater_params)
 
     def _drift_on(self):
-        return self.updater_mask is not None and len(self.updater_mask) > 0 and all(self.updater_mask)
+        return self._effective_mask is not None and bool(self._effective_mask.any())
 
     def update_keywords(self) -> None:
         """gymnasium_kw_env.py:114-158, on the device (engine drift stream)"""
@@ -199,14 +215,14 @@ class BiddingSimulation(_EnvBase):
         self._params_dirty = True
         self._epoch += 1
 
-    def _settle_last_outcomes(self):
+    def _settle_last_outcomes(self, drift_on=None):
         """With drift on, the last step's update_keywords() is still pending on the device and its per-click lists are regenerated
         from the parameters that step ran with.  Whatever is about to write the drifted parameters into the planes (reading
         keyword_params, update_keywords()) first formats the last step's info["bidding_outcomes"] - if that info dict is still
         alive and unread - so the text a caller reads afterwards is that step's own."""
         ref = self._last_outcomes
         lazy = ref() if ref is not None else None
-        if lazy is not None and self._drift_on():
+        if lazy is not None and (self._drift_on() if drift_on is None else drift_on):
             str(lazy)
         self._last_outcomes = None
 
@@ -245,6 +261,9 @@ class BiddingSimulation(_EnvBase):
                                       device_id=self._device_id, max_days=self.max_days,
                                       loss_threshold=self.loss_threshold, drift=self._drift_coeffs(),
                                       drift_enabled=self._drift_on(), seed=0 if seed is None else seed)
+            eff = self._effective_mask
+            if eff is not None and self._drift_on() and not eff.all():
+                self._engine.set_drift_mask(eff)
 
     # ------------------------------------------------------------------ reset / step
     def reset(self, *, seed: Optional[int] = None, options: Optional[dict] = None):

@@ -164,3 +164,17 @@ def experiment_keyword_config(mean_volume, conversion_rate, **extra):
            "mean_volume": mean_volume, "conversion_rate": conversion_rate}
     cfg.update(extra)
     return cfg
+
+
+def effective_updater_mask(updater_mask):
+    """The keywords the reference's update_keywords() moves under `updater_mask` (gymnasium_kw_env.py:130-144, SURVEY B-6):
+    it draws num_updates = sum(mask) coefficients per quantity and zips them with the keyword list, so only keywords
+    0..num_updates-1 are visited, and keyword k moves iff mask[k] and k < sum(mask), with the k-th coefficients.
+    `updater_mask`: [K], or [N, K] (the rule row by row); None -> None.  Returns a bool array of the same shape."""
+    if updater_mask is None:
+        return None
+    m = np.asarray(updater_mask)
+    if m.ndim not in (1, 2):
+        raise ValueError(f"updater_mask must be [K] or [N, K], got shape {m.shape}")
+    n = np.sum(m, axis=-1, keepdims=True)
+    return m.astype(bool) & (np.arange(m.shape[-1]) < n)

@@ -41,17 +41,18 @@ class BiddingSimulationVectorEnv:
         keyword come back per step; step() raises OverflowError if a count exceeds 65535).  Dict observations only.
         copy: False (default) returns observation arrays that are views of the engine's page-locked I/O buffers -
         valid until the next step(), counts as int32 (the reference's int64 costs a 3x8 MB conversion per step at
-        4096 x 256); True returns fresh arrays with the reference's dtypes (int64 counts)."""
+        4096 x 256); True returns fresh arrays with the reference's dtypes (int64 counts).
+        updater_mask: None (no drift), [K] (every env) or [N, K]; each row is translated by the reference's rule
+        (gymnasium_kw_utils.effective_updater_mask: keyword k moves iff mask[k] and k < sum(mask)), and drift is on while any
+        env selects a keyword.  updater_params: the reference's [["vol", a], ["ctr", a], ["cvr", a]] (every env), N such
+        lists, or an [N, 3] array of the three magnitudes.  set_updater_mask / set_updater_params change either between
+        steps: the update the last step scheduled still moves under the settings it was scheduled with."""
         self.num_envs, self.num_keywords = int(num_envs), int(num_keywords)
         self.keyword_config = keyword_config
         self.budget = np.full(self.num_envs, float(budget), dtype=np.float32)
         self.loss_threshold, self.max_days = float(loss_threshold), int(max_days)
-        self.updater_params = [list(p) for p in updater_params]
-        if updater_mask is not None:
-            assert len(updater_mask) == self.num_keywords
-            if any(updater_mask) and not all(updater_mask):
-                raise NotImplementedError("only updater_mask=None or all-True is supported")
-        self.updater_mask = updater_mask
+        self.updater_params, self._rates = updater_params, self._drift_rates(updater_params)
+        self.updater_mask, self._effective = updater_mask, self._effective_mask(updater_mask)
         self.single_action_space = _spaces.get_action_space(self.num_keywords)
         self.single_observation_space = _spaces.get_observation_space(self.num_keywords, float(budget))
         self.action_space, self.observation_space = self.single_action_space, self.single_observation_space
@@ -70,16 +71,69 @@ class BiddingSimulationVectorEnv:
     def _ensure_engine(self, seed):
         if self._engine is None:
             from .engine import ShardedStepEngine, StepEngine
-            drift_on = self.updater_mask is not None and len(self.updater_mask) > 0 and all(self.updater_mask)
             make = StepEngine if self._shards <= 1 else (lambda *a, **k: ShardedStepEngine(*a, shards=self._shards, **k))
             self._engine = make(self.num_envs, self.num_keywords,
                                       MODEL_IMPLICIT if self._implicit else MODEL_EXPLICIT,
                                       device_id=self._device_id, max_days=self.max_days,
                                       loss_threshold=self.loss_threshold,
-                                      drift=tuple(float(p[1]) for p in self.updater_params), drift_enabled=drift_on,
+                                      drift=self._drift_scalars(), drift_enabled=self._drift_on(),
                                       auto_reset=self.autoreset, env_id_base=self._env_id_base,
                                       seed=0 if seed is None else seed, compact_counts=self._compact)
+            if self._rates.ndim == 2:
+                self._engine.set_env_drift(self._rates)
+            if self._drift_on() and not self._effective.all():
+                self._engine.set_drift_mask(self._effective)
         return self._engine
+
+    # ------------------------------------------------------------------ drift (update_keywords after every step)
+    def _effective_mask(self, mask):
+        """[N, K] bool: the keywords each env's update_keywords() moves (None: no updates)"""
+        if mask is None:
+            return None
+        m = np.asarray(mask)
+        assert m.shape in ((self.num_keywords,), (self.num_envs, self.num_keywords)), (
+            f"updater_mask must have shape ({self.num_keywords},) or ({self.num_envs}, {self.num_keywords}), got {m.shape}")
+        return np.broadcast_to(utils.effective_updater_mask(m), (self.num_envs, self.num_keywords))
+
+    def _drift_rates(self, params):
+        """the three magnitudes: [3] from the reference's list of [name, value] pairs (every env), [N, 3] from N such lists
+        or an [N, 3] array"""
+        a = np.asarray(params, dtype=object)
+        if a.shape == (3, 2) and all(isinstance(x, str) for x in a[:, 0]):
+            return np.asarray(a[:, 1], dtype=np.float32)
+        r = np.asarray(a[:, :, 1] if a.ndim == 3 and a.shape[1:] == (3, 2) else params, dtype=np.float32)
+        if r.shape != (self.num_envs, 3):
+            raise ValueError(f"updater_params: the reference's three [name, value] pairs, {self.num_envs} such lists or an "
+                             f"[{self.num_envs}, 3] array; got shape {np.shape(params)}")
+        return r
+
+    def _drift_on(self):
+        return self._effective is not None and bool(self._effective.any())
+
+    def _drift_scalars(self):
+        return tuple(float(x) for x in (self._rates if self._rates.ndim == 1 else self._rates[0]))
+
+    def _apply_drift_settings(self):
+        eng = self._engine
+        if eng is None:
+            return
+        eff = self._effective
+        # (the first of these applies the pending update under the old settings; the later ones find nothing pending)
+        eng.set_drift_mask(None if eff is None or eff.all() else eff)
+        eng.set_env_drift(self._rates if self._rates.ndim == 2 else None)
+        eng.set_drift(self._drift_on(), self._drift_scalars())
+
+    def set_updater_mask(self, mask):
+        """a new updater_mask, [K] or [N, K] (see __init__); takes effect from the update of the next step"""
+        effective = self._effective_mask(mask)
+        self.updater_mask, self._effective = mask, effective
+        self._apply_drift_settings()
+
+    def set_updater_params(self, params):
+        """new drift magnitudes, in any form __init__ takes; takes effect from the update of the next step"""
+        rates = self._drift_rates(params)
+        self.updater_params, self._rates = params, rates
+        self._apply_drift_settings()
 
     @property
     def engine(self):

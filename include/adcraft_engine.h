@@ -205,6 +205,17 @@ int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const uint64_t *see
  * (gymnasium_kw_env.py:105-112,318-325) */
 int adc_engine_set_limits(adc_engine *e, int32_t max_days, double loss_threshold);
 int adc_engine_set_drift(adc_engine *e, int32_t enabled, float drift_vol, float drift_ctr, float drift_cvr);
+/* which keywords drift at each update_keywords(), per env: mask_nk[N][K] (nonzero = moves), NULL = every keyword.
+ * A selected keyword moves exactly as without a selection (same draw, same magnitudes); an unselected one keeps vol_mean,
+ * bctr and sctr bit for bit.  An explicit selection: the reference's prefix rule for a partial updater_mask
+ * (gymnasium_kw_env.py:130-144, keyword k moves iff mask[k] and k < sum(mask)) is the caller's to apply.
+ * The update the last step scheduled is first applied under the selection in force when it was scheduled.
+ * Persists across resets; does not switch drift on (adc_engine_set_drift does). */
+int adc_engine_set_drift_mask(adc_engine *e, const uint8_t *mask_nk);
+/* per-env drift magnitudes rates_n3[N][3] = vol, ctr, cvr (updater_params' numbers), NULL = adc_engine_set_drift's scalars.
+ * While set they override those scalars (adc_engine_set_drift still switches drift on and off).  The pending update is first
+ * applied under the magnitudes in force when it was scheduled.  Persists across resets. */
+int adc_engine_set_env_drift(adc_engine *e, const float *rates_n3);
 
 /* random-stream state of every env: Philox key [N] and step counter ("tick") [N]; with the episode state
  * below this is everything needed to checkpoint / resume an engine (the parameters come from get_params) */

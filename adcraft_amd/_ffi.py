@@ -12,7 +12,11 @@ ADC_OK, ADC_EINVAL, ADC_EHIP, ADC_ENOMEM, ADC_ESTATE, ADC_ETYPE, ADC_ERCCL = 0, 
 MODEL_IMPLICIT, MODEL_EXPLICIT, MODEL_IMPLICIT_GENERAL = 0, 1, 2
 P_VOL_MEAN, P_VOL_STD, P_A, P_B, P_BCTR, P_SCTR, P_REV_MEAN, P_REV_STD, P_COUNT = range(9)
 (BUF_PARAMS, BUF_BIDS, BUF_BUDGET, BUF_IMPRESSIONS, BUF_CLICKS, BUF_CONVERSIONS, BUF_COST, BUF_REVENUE, BUF_REWARD,
- BUF_CUM_PROFIT, BUF_DAYS, BUF_TERMINATED, BUF_TRUNCATED, BUF_METRIC_PROFIT, BUF_METRIC_SCALARS, BUF_FLAT_OBS) = range(16)
+ BUF_CUM_PROFIT, BUF_DAYS, BUF_TERMINATED, BUF_TRUNCATED, BUF_METRIC_PROFIT, BUF_METRIC_SCALARS, BUF_FLAT_OBS,
+ BUF_ROLLOUT_ACTION, BUF_ROLLOUT_LOGP, BUF_ROLLOUT_VALUE, BUF_ROLLOUT_REWARD, BUF_ROLLOUT_TERMINATED, BUF_ROLLOUT_TRUNCATED,
+ BUF_ROLLOUT_OBS) = range(23)
+MLP_TANH, MLP_RELU = 0, 1
+ROLLOUT_OBS = 1
 
 
 class EngineError(RuntimeError):
@@ -41,6 +45,13 @@ class StepOut(C.Structure):
 
 class Quantiles(C.Structure):
     _fields_ = [("buckets", C.c_int32 * 7), ("mins", C.c_void_p * 7), ("medians", C.c_void_p * 7), ("maxs", C.c_void_p * 7)]
+
+
+class MLPConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("activation", C.c_int32), ("n_policy_layers", C.c_int32),
+                ("policy_widths", C.c_int32 * 4), ("n_value_layers", C.c_int32), ("value_widths", C.c_int32 * 4),
+                ("normalize", C.c_int32), ("clamp_log_std", C.c_int32), ("log_std_lo", C.c_float), ("log_std_hi", C.c_float),
+                ("bid_clip_hi", C.c_float), ("deterministic", C.c_int32)]
 
 
 class Tape(C.Structure):
@@ -172,6 +183,25 @@ def lib():
         "adc_interp_act_host": ([f32, i32, f32, i32, C.c_double, C.c_double, C.c_double, vp, i32, i32, vp, vp, i32, vp, vp,
                                  C.c_double, vp, vp, vp, vp, vp], C.c_int),
         "adc_interp_key_host": ([f32], C.c_double),
+        "adc_engine_mlp_init": ([vp, C.POINTER(MLPConfig), vp], C.c_int),
+        "adc_engine_mlp_set_layer": ([vp, i32, i32, vp, vp], C.c_int),
+        "adc_engine_mlp_set_norm": ([vp, vp, vp], C.c_int),
+        "adc_engine_mlp_set_log_std": ([vp, vp], C.c_int),
+        "adc_engine_mlp_set_deterministic": ([vp, i32], C.c_int),
+        "adc_engine_mlp_act": ([vp, f32, vp], C.c_int),
+        "adc_engine_mlp_step": ([vp, f32], C.c_int),
+        "adc_engine_mlp_last": ([vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_bootstrap_value": ([vp, vp], C.c_int),
+        "adc_engine_rollout_enable": ([vp, i32, i32], C.c_int),
+        "adc_engine_rollout_reset": ([vp], C.c_int),
+        "adc_engine_rollout_fetch": ([vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_mlp_config_check": ([C.POINTER(MLPConfig), i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_mlp_act_host": ([C.POINTER(MLPConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
+                              vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_mlp_math_host": ([i32, f32], f32),
+        "adc_mlp_math_sweep_host": ([i32, f32, f32, vp, vp], i64),
+        "adc_mlp_agent_key_host": ([u64], u64),
+        "adc_mlp_default_agent_key_host": ([u64, u64], u64),
         "adc_explicit_curve_host": ([C.c_uint64, C.c_uint32, i32, i32, f32, f32, f32, vp, i32, vp, vp, vp], C.c_int),
         "adc_debug_win_brackets_device": ([C.c_int, i64, vp, vp, vp, vp, vp], C.c_int),
         "adc_debug_philox_device": ([C.c_int, i64, vp, vp, vp], C.c_int),

@@ -1,0 +1,138 @@
+"""A learned bidder for the device: the small fully connected policy (and value) networks the paper trains with PPO / A2C /
+TD3 (`fcnet_hiddens [32, 32]` on FlatArrayWrapper observations), held as plain float32 arrays and evaluated by the HIP engine
+(StepEngine.mlp_init / mlp_act / mlp_step / run_days("mlp"); the arithmetic is csrc/adc_mlp.h).
+
+The observation is the flat row `buyside_clicks[K] | cost[K] | cumulative_profit | days_passed | impressions[K] | revenue[K] |
+sellside_conversions[K]` (D = 5K+2); the action is `[budget, bids...]` (A = K+1).  The policy network ends in A means (with a
+free `log_std[A]`) or in 2A values, means then log-stds."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _ffi
+
+ACTIVATIONS = {"tanh": _ffi.MLP_TANH, "relu": _ffi.MLP_RELU}
+MAX_LAYERS, MAX_WIDTH = 4, 256
+
+
+def _layers(pairs, what):
+    out = []
+    for w, b in pairs:
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if w.ndim != 2 or w.shape[1] != b.size:
+            raise ValueError(f"{what}: a layer is (W [n_in, n_out], b [n_out])")
+        if out and out[-1][0].shape[1] != w.shape[0]:
+            raise ValueError(f"{what}: layer inputs do not match the previous layer's outputs")
+        out.append((w, b))
+    return out
+
+
+class MLPPolicy:
+    """layers / value_layers: lists of (W [n_in, n_out], b [n_out]) - input-major, i.e. torch's `weight.T`.  log_std [A]: the
+    free log standard deviations when the policy ends in A means (default zeros); shift / scale [D]: x' = (x - shift) * scale;
+    log_std_clamp (lo, hi); bid_clip: upper clip of the bids in dollars; deterministic: act on the means."""
+
+    def __init__(self, layers, activation="tanh", value_layers=(), log_std=None, shift=None, scale=None, log_std_clamp=None,
+                 bid_clip=None, deterministic=False):
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"unknown activation {activation!r}: 'tanh' or 'relu'")
+        self.activation = activation
+        self.layers = _layers(layers, "policy network")
+        self.value_layers = _layers(value_layers, "value network")
+        if not 1 <= len(self.layers) <= MAX_LAYERS or len(self.value_layers) > MAX_LAYERS:
+            raise ValueError(f"a network has at most {MAX_LAYERS} layers (and the policy network at least one)")
+        for net in (self.layers, self.value_layers):
+            if any(w.shape[1] > MAX_WIDTH for w, _ in net[:-1]):
+                raise ValueError(f"hidden widths are at most {MAX_WIDTH}")
+        if self.value_layers and (self.value_layers[-1][0].shape[1] != 1 or self.value_layers[0][0].shape[0] != self.input_size):
+            raise ValueError("the value network maps the policy's input to one output")
+        if (shift is None) != (scale is None):
+            raise ValueError("pass both shift and scale, or neither")
+        vec = lambda x, n: None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32), (n,)))
+        self.shift, self.scale = vec(shift, self.input_size), vec(scale, self.input_size)
+        self.log_std = None
+        if self.input_size % 5 == 2 and self.output_size == self.num_keywords + 1:
+            self.log_std = vec(0.0 if log_std is None else log_std, self.output_size)
+        elif log_std is not None:
+            raise ValueError("log_std belongs to a policy that ends in K+1 means")
+        self.log_std_clamp = None if log_std_clamp is None else (float(log_std_clamp[0]), float(log_std_clamp[1]))
+        self.bid_clip = None if bid_clip is None else float(bid_clip)
+        self.deterministic = bool(deterministic)
+
+    input_size = property(lambda self: self.layers[0][0].shape[0])
+    output_size = property(lambda self: self.layers[-1][0].shape[1])
+    num_keywords = property(lambda self: (self.input_size - 2) // 5)
+
+    def shapes(self):
+        """what StepEngine.mlp_init fixes and mlp_set_weights must find again: every layer's shape, the head's free log_std,
+        whether there is a normalisation"""
+        return ([w.shape for w, _ in self.layers], [w.shape for w, _ in self.value_layers], self.log_std is not None,
+                self.shift is not None)
+
+    @classmethod
+    def from_arrays(cls, layers, **kw):
+        return cls(layers, **kw)
+
+    @classmethod
+    def from_torch(cls, module, value_module=None, **kw):
+        """a torch.nn.Sequential that is exactly Linear, act, Linear, act, ..., Linear with act = Tanh or ReLU (one kind for
+        the policy and the value network): what the engine evaluates.  Any other structure - an activation after the last
+        Linear, two Linear in a row, a leading activation - is refused, not converted into a different function."""
+        import torch
+
+        def unpack(seq, what):
+            mods = list(seq)
+            if len(mods) % 2 == 0 or not all(isinstance(m, torch.nn.Linear) for m in mods[0::2]):
+                for m in mods:
+                    if not isinstance(m, (torch.nn.Linear, torch.nn.Tanh, torch.nn.ReLU)):
+                        raise ValueError(f"unsupported module {type(m).__name__}: Linear, Tanh and ReLU only")
+                raise ValueError(f"{what}: the modules must alternate Linear, activation, ..., and begin and end with a Linear")
+            pairs, acts = [], set()
+            for m in mods[0::2]:
+                bias = m.bias.detach() if m.bias is not None else torch.zeros(m.out_features)
+                pairs.append((m.weight.detach().cpu().numpy().T.copy(), bias.cpu().numpy().copy()))
+            for m in mods[1::2]:
+                if isinstance(m, torch.nn.Tanh):
+                    acts.add("tanh")
+                elif isinstance(m, torch.nn.ReLU):
+                    acts.add("relu")
+                elif isinstance(m, torch.nn.Linear):
+                    raise ValueError(f"{what}: two Linear modules in a row (an activation goes between them)")
+                else:
+                    raise ValueError(f"unsupported module {type(m).__name__}: Linear, Tanh and ReLU only")
+            return pairs, acts
+
+        pairs, acts = unpack(module, "policy network")
+        vpairs, vacts = unpack(value_module, "value network") if value_module is not None else ([], set())
+        acts |= vacts
+        if len(acts) > 1:
+            raise ValueError("one kind of activation per policy")
+        if acts and kw.setdefault("activation", next(iter(acts))) not in acts:
+            raise ValueError(f"activation={kw['activation']!r} is not what the modules hold")
+        return cls(pairs, value_layers=vpairs, **kw)
+
+    def config(self, num_keywords, deterministic=None):
+        """the engine's adc_mlp_config for an engine of num_keywords keywords (ValueError when the shapes do not fit)"""
+        c = _ffi.MLPConfig()
+        c.struct_size = C.sizeof(_ffi.MLPConfig)
+        c.activation = ACTIVATIONS[self.activation]
+        c.n_policy_layers, c.n_value_layers = len(self.layers), len(self.value_layers)
+        for i, (w, _) in enumerate(self.layers):
+            c.policy_widths[i] = w.shape[1]
+        for i, (w, _) in enumerate(self.value_layers):
+            c.value_widths[i] = w.shape[1]
+        c.normalize = 0 if self.shift is None else 1
+        c.clamp_log_std = 0 if self.log_std_clamp is None else 1
+        c.log_std_lo, c.log_std_hi = self.log_std_clamp or (0.0, 0.0)
+        c.bid_clip_hi = self.bid_clip or 0.0
+        c.deterministic = 1 if (self.deterministic if deterministic is None else deterministic) else 0
+        if self.input_size != 5 * int(num_keywords) + 2:
+            raise ValueError(f"the policy reads {self.input_size} inputs, the engine's observation has {5 * int(num_keywords) + 2}")
+        msg = C.c_char_p()
+        if _ffi.lib().adc_mlp_config_check(C.byref(c), int(num_keywords), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad MLP configuration").decode())
+        return c
+
+
+__all__ = ["MLPPolicy"]

@@ -15,15 +15,18 @@ from . import experiment_metrics as em
 
 def run_baseline_episode(engine, policy="zero_margin", steps=None, budget=100000.0, default_rpc=1.0, agent_seeds=None,
                          n_samples=2048, bid_grid=None, curves=True, per_keyword_sums=True, profit_acquisition_threshold=-0.2,
-                         allowed_bids=None, bid_step=0.03, capacity=0):
+                         allowed_bids=None, bid_step=0.03, capacity=0, mlp=None, deterministic=None):
     """One episode of `steps` days (default: the engine's max_days) for every env of `engine` (already reset, keywords
     set).  policy: "zero_margin" (NaiveZeroMarginStrategy), "interpolation" (NaiveInterpolationStrategy with
-    profit_acquisition_threshold, allowed_bids (default np.linspace(0.01, 3.00, 300)), bid_step, capacity) or "oracle"
-    (bid the argmax of the expected profit).
+    profit_acquisition_threshold, allowed_bids (default np.linspace(0.01, 3.00, 300)), bid_step, capacity), "oracle"
+    (bid the argmax of the expected profit) or "mlp" (a learned agent: mlp = an MLPPolicy, deterministic = act on the means;
+    budget <= 0 leaves the budget to the policy's own first action component).
     Returns dict(kw_profit_sum [N, K], ideal_sum [N, K], AKNCP [N], NCP [N]).  per_keyword_sums=False: only AKNCP and NCP,
     reduced on the device (the per-env median over the keywords included): 2 N numbers cross the bus, not 3 N K."""
-    if policy not in ("zero_margin", "interpolation", "oracle"):
-        raise ValueError("policy must be 'zero_margin', 'interpolation' or 'oracle'")
+    if policy not in ("zero_margin", "interpolation", "oracle", "mlp"):
+        raise ValueError("policy must be 'zero_margin', 'interpolation', 'oracle' or 'mlp'")
+    if policy == "mlp" and mlp is None:
+        raise ValueError("policy 'mlp' needs mlp=<MLPPolicy>")
     steps = int(engine.max_days if steps is None else steps)
     if curves:
         engine.bid_curves_build(n_samples, bid_grid)           # irs, cpcs = get_implicit_kw_bid_cpc_impressions(...) per keyword
@@ -33,6 +36,8 @@ def run_baseline_episode(engine, policy="zero_margin", steps=None, budget=100000
         engine.agent_init(default_rpc, agent_seeds)
     elif policy == "interpolation":
         engine.interp_init(profit_acquisition_threshold, bid_step, allowed_bids, capacity, agent_seeds)
+    elif policy == "mlp":
+        engine.mlp_init(mlp, agent_seeds, deterministic)
     engine.run_days(policy, steps, budget)     # agent / ideal profit / step for every day, one host call
     n = float(steps)
     if not per_keyword_sums:

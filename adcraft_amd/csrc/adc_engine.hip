@@ -65,6 +65,7 @@
 #include "../../include/adcraft_engine.h"
 #include "adc_law.h"
 #include "adc_interp.h"
+#include "adc_mlp.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -80,6 +81,7 @@ namespace adck {
 #include "parts/kernels_policy.inc"
 #include "parts/kernel_explicit_curves.inc"
 #include "parts/kernel_interp_agent.inc"
+#include "parts/kernel_mlp_policy.inc"
 }  // namespace adck
 using namespace adck;
 

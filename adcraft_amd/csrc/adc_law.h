@@ -42,7 +42,7 @@ namespace adc {
 //           auction j, highest first (top_laplace_bids: order statistics instead of one draw per bidder);
 //           call (j, ST_GCLICK) = {click, conversion, revenue} words of auction j.
 enum Stage : uint32_t { ST_VOL = 0, ST_AUCTION = 1, ST_DRIFT = 2, ST_XPHANTOM = 3, ST_XREV = 4, ST_ACTION = 5, ST_METRIC = 6, ST_CONV = 7, ST_KEYGEN = 8, ST_AGENT = 9,
-                        ST_GBIDDERS = 10, ST_GBID = 11, ST_GCLICK = 12, ST_INTERP = 13 };
+                        ST_GBIDDERS = 10, ST_GBID = 11, ST_GCLICK = 12, ST_INTERP = 13, ST_MLP = 14 };
 constexpr int kTimesteps = 24;          // adcraft/bidding_simulation.py:213
 constexpr int kVolumeMax = 1 << 20;
 constexpr float kMoneyMaxCents = 1.0e9f;

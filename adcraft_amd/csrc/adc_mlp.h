@@ -1,0 +1,233 @@
+// adc_mlp.h - the law of the device-resident MLP policy: a fully connected policy network (and an optional value network) on
+// the flat observation, a diagonal Gaussian head, and the conversion of the sampled action into the env's cent bids.  Shared
+// by the device kernel (parts/kernel_mlp_policy.inc) and the host twin adc_mlp_act_host (adc_shims.cpp), so that CPU tests
+// run the very operations the GPU runs; tests/mlp_ref.py restates these comments in numpy, bit for bit.
+//
+// Every float32 value below is the result of ONE correctly rounded IEEE operation (build with -ffp-contract=off: no fused
+// multiply-add is meant anywhere in this file); "f64" marks the few places that compute in float64 and round once.
+//
+//   input      x[j], j < D = 5K+2: the flat observation (buyside_clicks[K] | cost[K] | cumulative_profit | days_passed |
+//              impressions[K] | revenue[K] | sellside_conversions[K]) as float32; all zeros on the first day of an episode.
+//              With normalisation: x[j] = (x[j] - shift[j]) * scale[j] (a subtraction, then a product).
+//   sum8(n, t) the sum of n float32 terms t(0) .. t(n-1): eight chains, chain c = ((0 + t(c)) + t(c+8)) + t(c+16) + ... over
+//              the j = c (mod 8) in ascending order, starting from +0; then ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)).
+//   layer      y[h] = act(sum8(n_in, j -> W[j][h] * x[j]) + b[h]); act = tanh or relu between layers, none after the last.
+//              relu(v) = v > 0 ? v : +0 (a NaN becomes +0).
+//   exp64(x)   f64, |x| <= 700: n = rint(x * 1.4426950408889634); r = (x - n * 0.693145751953125) - n * 1.4286068203094173e-06;
+//              q = c14; q = q * r + c13; ... ; q = q * r + c2 (c_k = 1.0 / k!, k! exact); p = r + (r * r) * q; result
+//              (1 + p) * 2^n.  p alone is exp(r) - 1 ("expm1 polynomial").
+//   tanh(x)    float32 -> float32, odd: a = |x| as f64; a >= 10: 1; 2a < 0.34: m = expm1 polynomial of r = 2a, t = m / (m + 2);
+//              otherwise e = exp64(2a), t = 1 - 2 / (e + 1); result = float32(t) with x's sign.  NaN -> NaN.
+//   exp(x)     float32 -> float32: float32(exp64(min(max(x, -87), 88))).  NaN -> NaN.
+//   head       the policy network's output o[]: A = K+1 means (then log_std[a] is a free parameter vector) or 2A values, means
+//              then log-stds.  Optional clamp: ls = ls < lo ? lo : ls; ls = ls > hi ? hi : ls.
+//   agent key  mix64(seed ^ 0x1F83D9ABFB41BD6B) from a per-env seed, or mix64(engine seed ^ mix64(global env id + 0x5BE0CD19137E2179))
+//              without one; mix64 = splitmix64: x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+//              x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31 (64-bit wrap-around).  The tick starts at 0; every act adds 1.
+//   sample     z[a] = normal_from_word(word a % 4 of draw(agent key, a / 4, ST_MLP, 0, agent tick)), or handed in (replay), or
+//              0 (deterministic).  action a[a] = mean + exp(ls) * z (a product, then a sum); deterministic: a = mean.
+//   log-prob   sum8(A, a -> (-((z * z) * 0.5)) - ls[a]) - float32(A) * 0.91893853 (= float32(log(2 pi) / 2)).
+//   value      the value network's single output on the same (normalised) input; +0 without one.
+//   to the env flat action order [budget, bids...]: bid k from v = a[1 + k]: v > 0.01 ? v : 0.01 (NaN -> 0.01); with an upper clip
+//              hi > 0: v < hi ? v : hi; then cents c = rint(f64(v) * 100) clamped to [1, 1e9], bid = float32(c / 100).
+//              budget = a[0] > 0.01 ? a[0] : 0.01, or budget_override when that is > 0.
+#pragma once
+#include "adc_law.h"
+
+namespace adc {
+
+constexpr int kMlpMaxLayers = 4;
+constexpr int kMlpMaxWidth = 256;          // widest hidden layer; the output layer may be as wide as 2 (K + 1)
+constexpr int kMlpChains = 8;
+constexpr int kMlpTanh = 0, kMlpRelu = 1;
+
+// one step of a chain: acc + w * x, two roundings
+ADC_HD float mlp_mac(float acc, float w, float x)
+{
+    const float p = w * x;
+    return acc + p;
+}
+// the join of the eight chains (float addition commutes, so a butterfly over lanes c ^ 1, c ^ 2, c ^ 4 gives these very bits)
+ADC_HD float mlp_join8(float s0, float s1, float s2, float s3, float s4, float s5, float s6, float s7)
+{
+    return ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
+}
+
+// exp(r) - 1 for |r| <= 0.35, float64: r + r^2 * sum_{k = 2..14} r^(k-2) / k!
+ADC_HD double mlp_expm1_poly(double r)
+{
+    double q = 1.0 / 87178291200.0;
+    q = q * r + 1.0 / 6227020800.0;
+    q = q * r + 1.0 / 479001600.0;
+    q = q * r + 1.0 / 39916800.0;
+    q = q * r + 1.0 / 3628800.0;
+    q = q * r + 1.0 / 362880.0;
+    q = q * r + 1.0 / 40320.0;
+    q = q * r + 1.0 / 5040.0;
+    q = q * r + 1.0 / 720.0;
+    q = q * r + 1.0 / 120.0;
+    q = q * r + 1.0 / 24.0;
+    q = q * r + 1.0 / 6.0;
+    q = q * r + 1.0 / 2.0;
+    return r + (r * r) * q;
+}
+
+ADC_HD double mlp_bits_to_double(uint64_t u)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __longlong_as_double((long long)u);
+#else
+    union { uint64_t u; double d; } v; v.u = u; return v.d;
+#endif
+}
+
+// float64 exp for |x| <= 700
+ADC_HD double mlp_exp64(double x)
+{
+    const double n = __builtin_rint(x * 1.4426950408889634);
+    const double r = (x - n * 0.693145751953125) - n * 1.4286068203094173e-06;
+    const double p = mlp_expm1_poly(r);
+    return (1.0 + p) * mlp_bits_to_double((uint64_t)((long long)n + 1023) << 52);
+}
+
+ADC_HD float mlp_tanh(float x)
+{
+    if (x != x) return x;
+    const double a = __builtin_fabs((double)x);
+    double t;
+    if (a >= 10.0) t = 1.0;
+    else if (a + a < 0.34) {
+        const double m = mlp_expm1_poly(a + a);
+        t = m / (m + 2.0);
+    } else {
+        const double e = mlp_exp64(a + a);
+        t = 1.0 - 2.0 / (e + 1.0);
+    }
+    return __builtin_copysignf((float)t, x);
+}
+
+ADC_HD float mlp_exp(float x)
+{
+    if (x != x) return x;
+    x = x < -87.0f ? -87.0f : x;
+    x = x > 88.0f ? 88.0f : x;
+    return (float)mlp_exp64((double)x);
+}
+
+ADC_HD float mlp_act(float v, int activation)
+{
+    if (activation == kMlpTanh) return mlp_tanh(v);
+    return v > 0.0f ? v : 0.0f;
+}
+
+ADC_HD float mlp_normalize(float x, float shift, float scale)
+{
+    const float d = x - shift;
+    return d * scale;
+}
+
+ADC_HD float mlp_clamp_log_std(float ls, int clamp, float lo, float hi)
+{
+    if (clamp) {
+        ls = ls < lo ? lo : ls;
+        ls = ls > hi ? hi : ls;
+    }
+    return ls;
+}
+
+// the standard normal of action component a from the four words of draw(key, a / 4, ST_MLP, 0, tick)
+ADC_HD float mlp_normal(uint64_t key, uint32_t tick, int a)
+{
+    const U4 w = draw(key, (uint32_t)(a >> 2), ST_MLP, 0u, tick);
+    const int h = a & 3;
+    return normal_from_word(h == 0 ? w.x : h == 1 ? w.y : h == 2 ? w.z : w.w);
+}
+
+ADC_HD float mlp_sample(float mean, float ls, float z, int deterministic)
+{
+    if (deterministic) return mean;
+    const float p = mlp_exp(ls) * z;
+    return mean + p;
+}
+
+// one term of the log-probability's sum8
+ADC_HD float mlp_logp_term(float z, float ls)
+{
+    const float h = (z * z) * 0.5f;
+    return (-h) - ls;
+}
+ADC_HD float mlp_logp_finish(float sum, int A)
+{
+    const float c = (float)A * 0.918938517570495605f;
+    return sum - c;
+}
+
+// the env's bid (float32 of whole cents / 100) from an action component
+ADC_HD float mlp_bid(float v, float clip_hi)
+{
+    v = v > 0.01f ? v : 0.01f;
+    if (clip_hi > 0.0f) v = v < clip_hi ? v : clip_hi;
+    double c = __builtin_rint((double)v * 100.0);
+    c = c >= 1.0 ? c : 1.0;
+    c = c < 1.0e9 ? c : 1.0e9;
+    return (float)(c / 100.0);
+}
+ADC_HD float mlp_budget(float v, float budget_override)
+{
+    if (budget_override > 0.0f) return budget_override;
+    return v > 0.01f ? v : 0.01f;
+}
+
+// element j of the flat observation row from the engine's output arrays of one env (what k_flatten_obs writes)
+ADC_HD float mlp_obs_at(int j, int K, const int32_t *clk, const float *cost, const int32_t *imp, const float *rev, const int32_t *conv,
+                        double cum_profit, int32_t days)
+{
+    if (j < K) return (float)clk[j];
+    if (j < 2 * K) return cost[j - K];
+    if (j == 2 * K) return (float)cum_profit;
+    if (j == 2 * K + 1) return (float)days;
+    j -= 2 * K + 2;
+    if (j < K) return (float)imp[j];
+    if (j < 2 * K) return rev[j - K];
+    return (float)conv[j - 2 * K];
+}
+
+// splitmix64
+ADC_HD uint64_t mlp_mix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+// the agent's Philox key from its per-env seed
+ADC_HD uint64_t mlp_agent_key(uint64_t seed) { return mlp_mix64(seed ^ 0x1F83D9ABFB41BD6Bull); }
+// ... and without per-env seeds: from the engine's seed and the env's global id (env_id_base + env)
+ADC_HD uint64_t mlp_default_agent_key(uint64_t engine_seed, uint64_t global_env_id)
+{
+    return mlp_mix64(engine_seed ^ mlp_mix64(global_env_id + 0x5BE0CD19137E2179ull));
+}
+
+// weights are stored chain-major in blocks of 32 inputs: W[j][h] of a layer with n_out outputs sits at
+// (((j / 32) * n_out + h) * 8 + j % 8) * 4 + (j / 8) % 4, rows padded to a multiple of 32 with zeros that are never read: one
+// 16-byte load gives a lane four consecutive steps of its chain, and the eight lanes of one neuron read 128 consecutive bytes
+ADC_HD size_t mlp_weight_index(int j, int h, int n_out)
+{
+    return ((((size_t)(j >> 5) * (size_t)n_out + (size_t)h) * 8u + (size_t)(j & 7)) << 2) + (size_t)((j >> 3) & 3);
+}
+ADC_HD size_t mlp_weight_count(int n_in, int n_out) { return (size_t)((n_in + 31) >> 5) * (size_t)n_out * 32u; }
+
+// chain c of sum8 for one neuron, on the host's side of the law (the kernel runs the same mlp_mac steps, one chain per lane)
+template <class X>
+ADC_HD float mlp_neuron(const float *W, const float *b, int n_in, int n_out, int h, const X &x)
+{
+    float s[kMlpChains];
+    for (int c = 0; c < kMlpChains; ++c) {
+        float acc = 0.0f;
+        for (int j = c; j < n_in; j += kMlpChains) acc = mlp_mac(acc, W[mlp_weight_index(j, h, n_out)], x(j));
+        s[c] = acc;
+    }
+    return mlp_join8(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]) + b[h];
+}
+
+}  // namespace adc

@@ -8,11 +8,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <thread>
 #include <vector>
 
 #include "../../include/adcraft_engine.h"
 #include "adc_law.h"
 #include "adc_interp.h"
+#include "adc_mlp.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -236,4 +238,151 @@ ADC_EXPORT int adc_interp_act_host(float ave_rpc, int32_t n_rpc, float ave_sctr,
     if (mass_out) *mass_out = pk.mass;
     *bid_out = pk.index >= 0 ? grid[pk.index] : 0.01;
     return ADC_OK;
+}
+
+// ---- the MLP policy on the host (adc_mlp.h: the code parts/kernel_mlp_policy.inc runs) -------------------------------------
+// the checks adc_engine_mlp_init makes on a configuration for an engine of num_keywords keywords; message (nullable) names the first failure
+ADC_EXPORT int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const char **message)
+{
+    const char *msg = nullptr;
+    const int A = num_keywords + 1;
+    if (!cfg || cfg->struct_size != sizeof(adc_mlp_config)) msg = "adc_mlp_config: NULL or struct_size mismatch";
+    else if (num_keywords < 1) msg = "num_keywords < 1";
+    else if (cfg->activation != ADC_MLP_TANH && cfg->activation != ADC_MLP_RELU) msg = "unknown activation";
+    else if (cfg->n_policy_layers < 1 || cfg->n_policy_layers > adc::kMlpMaxLayers) msg = "the policy network has 1 to 4 layers";
+    else if (cfg->n_value_layers < 0 || cfg->n_value_layers > adc::kMlpMaxLayers) msg = "the value network has 0 to 4 layers";
+    else if (cfg->clamp_log_std && !(cfg->log_std_lo <= cfg->log_std_hi)) msg = "log_std clamp: lo <= hi";
+    else {
+        for (int l = 0; l + 1 < cfg->n_policy_layers && !msg; ++l)
+            if (cfg->policy_widths[l] < 1 || cfg->policy_widths[l] > adc::kMlpMaxWidth) msg = "hidden widths are 1 to 256";
+        for (int l = 0; l + 1 < cfg->n_value_layers && !msg; ++l)
+            if (cfg->value_widths[l] < 1 || cfg->value_widths[l] > adc::kMlpMaxWidth) msg = "hidden widths are 1 to 256";
+        const int P = cfg->policy_widths[cfg->n_policy_layers - 1];
+        if (!msg && P != A && P != 2 * A) msg = "the policy network ends in num_keywords + 1 outputs (means) or twice that (means, log-stds)";
+        if (!msg && cfg->n_value_layers > 0 && cfg->value_widths[cfg->n_value_layers - 1] != 1) msg = "the value network ends in one output";
+    }
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+namespace {
+// one network of the law on a host input row; weights given [n_in][n_out] row-major, re-laid chain-major as the device holds them
+std::vector<float> mlp_forward_host(const float *x0, int D, int layers, const int32_t *widths, const float *const *w, const float *const *b, int activation)
+{
+    std::vector<float> x(x0, x0 + D);
+    for (int l = 0; l < layers; ++l) {
+        const int n_in = (int)x.size(), n_out = widths[l];
+        std::vector<float> cm(adc::mlp_weight_count(n_in, n_out), 0.0f), y((size_t)n_out);
+        for (int j = 0; j < n_in; ++j)
+            for (int h = 0; h < n_out; ++h) cm[adc::mlp_weight_index(j, h, n_out)] = w[l][(size_t)j * n_out + h];
+        const float *xp = x.data();
+        for (int h = 0; h < n_out; ++h) {
+            const float v = adc::mlp_neuron(cm.data(), b[l], n_in, n_out, h, [&](int j) { return xp[j]; });
+            y[(size_t)h] = l + 1 < layers ? adc::mlp_act(v, activation) : v;
+        }
+        x.swap(y);
+    }
+    return x;
+}
+}  // namespace
+
+ADC_EXPORT int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords, const float *obs_d, const float *const *policy_w,
+                                const float *const *policy_b, const float *const *value_w, const float *const *value_b, const float *shift_d,
+                                const float *scale_d, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,
+                                float budget_override, float *mean_a, float *log_std_out_a, float *action_a, float *logp, float *value,
+                                float *bids_k, float *budget)
+{
+    if (adc_mlp_config_check(cfg, num_keywords, nullptr) != ADC_OK) return ADC_EINVAL;
+    const int K = num_keywords, A = K + 1, D = 5 * K + 2;
+    const int P = cfg->policy_widths[cfg->n_policy_layers - 1];
+    const bool two_heads = P == 2 * A;
+    if (!policy_w || !policy_b || (cfg->n_value_layers > 0 && (!value_w || !value_b)) || (cfg->normalize && (!shift_d || !scale_d)) ||
+        (!two_heads && !log_std_a))
+        return ADC_EINVAL;
+    const int activation = cfg->activation == ADC_MLP_TANH ? adc::kMlpTanh : adc::kMlpRelu;
+    std::vector<float> x((size_t)D, 0.0f);
+    for (int j = 0; j < D; ++j) {
+        float xj = obs_d ? obs_d[j] : 0.0f;
+        if (cfg->normalize) xj = adc::mlp_normalize(xj, shift_d[j], scale_d[j]);
+        x[(size_t)j] = xj;
+    }
+    float v = 0.0f;
+    if (cfg->n_value_layers > 0) v = mlp_forward_host(x.data(), D, cfg->n_value_layers, cfg->value_widths, value_w, value_b, activation)[0];
+    const std::vector<float> o = mlp_forward_host(x.data(), D, cfg->n_policy_layers, cfg->policy_widths, policy_w, policy_b, activation);
+    std::vector<float> term((size_t)A);
+    for (int a = 0; a < A; ++a) {
+        const float mean = o[(size_t)a];
+        const float ls = adc::mlp_clamp_log_std(two_heads ? o[(size_t)(A + a)] : log_std_a[a], cfg->clamp_log_std != 0, cfg->log_std_lo, cfg->log_std_hi);
+        float z = 0.0f;
+        if (!cfg->deterministic) z = normals_a ? normals_a[a] : adc::mlp_normal(agent_key, tick, a);
+        const float act = adc::mlp_sample(mean, ls, z, cfg->deterministic != 0);
+        if (mean_a) mean_a[a] = mean;
+        if (log_std_out_a) log_std_out_a[a] = ls;
+        if (action_a) action_a[a] = act;
+        if (a == 0) { if (budget) *budget = adc::mlp_budget(act, budget_override); }
+        else if (bids_k) bids_k[a - 1] = adc::mlp_bid(act, cfg->bid_clip_hi);
+        term[(size_t)a] = adc::mlp_logp_term(z, ls);
+    }
+    float s[adc::kMlpChains];
+    for (int c = 0; c < adc::kMlpChains; ++c) {
+        float acc = 0.0f;
+        for (int a = c; a < A; a += adc::kMlpChains) acc = acc + term[(size_t)a];
+        s[c] = acc;
+    }
+    if (logp) *logp = adc::mlp_logp_finish(adc::mlp_join8(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]), A);
+    if (value) *value = v;
+    return ADC_OK;
+}
+
+ADC_EXPORT float adc_mlp_math_host(int32_t fn, float x) { return fn == 0 ? adc::mlp_tanh(x) : adc::mlp_exp(x); }
+
+ADC_EXPORT uint64_t adc_mlp_agent_key_host(uint64_t seed) { return adc::mlp_agent_key(seed); }
+ADC_EXPORT uint64_t adc_mlp_default_agent_key_host(uint64_t engine_seed, uint64_t global_env_id) { return adc::mlp_default_agent_key(engine_seed, global_env_id); }
+
+ADC_EXPORT int64_t adc_mlp_math_sweep_host(int32_t fn, float lo, float hi, double *out3, int64_t *violations4)
+{
+    if (!(lo <= hi) || (fn != 0 && fn != 1)) return -1;
+    // floats in value order: key = bits of a positive float, or the negation of a negative one's magnitude bits
+    auto key_of = [](float f) { const uint32_t u = adc::float_to_bits(f); return (u & 0x80000000u) ? -(int64_t)(u & 0x7FFFFFFFu) : (int64_t)u; };
+    auto float_of = [](int64_t k) { return adc::bits_to_float(k < 0 ? (0x80000000u | (uint32_t)(-k)) : (uint32_t)k); };
+    const int64_t k0 = key_of(lo), k1 = key_of(hi), total = k1 - k0 + 1;
+    const int T = 8;
+    struct Part { double max_abs = 0.0, max_ulp = 0.0, max_mag = 0.0; int64_t bad[4] = {0, 0, 0, 0}; };
+    std::vector<Part> parts((size_t)T);
+    std::vector<std::thread> threads;
+    auto eval = [fn](float x) { return fn == 0 ? adc::mlp_tanh(x) : adc::mlp_exp(x); };
+    for (int t = 0; t < T; ++t) {
+        threads.emplace_back([&, t]() {
+            Part &p = parts[(size_t)t];
+            const int64_t a = k0 + total * t / T, b = k0 + total * (t + 1) / T;      // keys [a, b); the first compares with its predecessor
+            float prev = a > k0 ? eval(float_of(a - 1)) : -__builtin_inff();
+            for (int64_t k = a; k < b; ++k) {
+                if (k == 0 && a != 0) continue;                                       // (-0 and +0 share key 0: taken once)
+                const float x = float_of(k);
+                const float y = eval(x);
+                const double exact = fn == 0 ? std::tanh((double)x) : std::exp((double)x);
+                const double err = std::fabs((double)y - exact);
+                if (err > p.max_abs) p.max_abs = err;
+                int ex;
+                (void)std::frexp(exact, &ex);
+                const double ulp = std::ldexp(1.0, std::max(ex - 24, -149));
+                if (err / ulp > p.max_ulp) p.max_ulp = err / ulp;
+                if (std::fabs((double)y) > p.max_mag) p.max_mag = std::fabs((double)y);
+                if (fn == 0 && eval(-x) != -y) p.bad[0] += 1;
+                if (y < prev) p.bad[1] += 1;
+                if (fn == 0 && std::fabs(y) > 1.0f) p.bad[2] += 1;
+                if (y != y) p.bad[3] += 1;
+                prev = y;
+            }
+        });
+    }
+    for (auto &th : threads) th.join();
+    Part all;
+    for (const Part &p : parts) {
+        all.max_abs = std::max(all.max_abs, p.max_abs); all.max_ulp = std::max(all.max_ulp, p.max_ulp); all.max_mag = std::max(all.max_mag, p.max_mag);
+        for (int i = 0; i < 4; ++i) all.bad[i] += p.bad[i];
+    }
+    if (out3) { out3[0] = all.max_abs; out3[1] = all.max_ulp; out3[2] = all.max_mag; }
+    if (violations4) for (int i = 0; i < 4; ++i) violations4[i] = all.bad[i];
+    return total;
 }

@@ -72,6 +72,18 @@ struct adc_engine {
     InterpView ip{};                    // the interpolation agent (adc_engine_interp_init; allocated there)
     bool have_interp = false;
     long long interp_updates = 0;       // updates since adc_engine_interp_init: each may add one point per keyword and list
+    MlpView mp{};                       // the MLP policy (adc_engine_mlp_init; allocated there)
+    bool have_mlp = false;
+    adc_mlp_config mlp_cfg{};
+    bool mlp_layer_set[2][4] = {{false, false, false, false}, {false, false, false, false}};      // [network][layer] uploaded since init
+    bool mlp_norm_set = false, mlp_log_std_set = false;
+    float *mlp_boot = nullptr;          // [N] adc_engine_mlp_bootstrap_value's device result
+    std::vector<void *> mlp_allocs;     // weights, vectors and last-act arrays (re-allocated by every adc_engine_mlp_init)
+    // the rollout record (adc_engine_rollout_enable): [T][N][...] arrays, ro_t days recorded so far
+    int ro_T = 0, ro_t = 0, ro_fields = 0;
+    float *ro_action = nullptr, *ro_logp = nullptr, *ro_value = nullptr, *ro_reward = nullptr, *ro_obs = nullptr;
+    uint8_t *ro_term = nullptr, *ro_trunc = nullptr;
+    std::vector<void *> ro_allocs;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
     // two consecutive days of the device-resident loop captured as one hipGraph (adc_engine_run_days)
     hipGraphExec_t day_graph = nullptr;
@@ -752,6 +764,8 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     if (e->h_binding) (void)hipHostFree(e->h_binding);
     if (e->h_direct) (void)hipHostFree(e->h_direct);
     for (void *p : e->curve_allocs) (void)hipFree(p);
+    for (void *p : e->mlp_allocs) (void)hipFree(p);
+    for (void *p : e->ro_allocs) (void)hipFree(p);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1553,6 +1567,22 @@ ADC_EXPORT int adc_engine_device_buffer(adc_engine *e, int buffer_id, void **dpt
     case ADC_BUF_FLAT_OBS:
         if (!v.flat_obs) return fail(ADC_ESTATE, "flat observations are not enabled (adc_engine_flat_obs_enable)");
         p = v.flat_obs; b = N * (5 * K + 2) * 4; break;
+    case ADC_BUF_ROLLOUT_ACTION: case ADC_BUF_ROLLOUT_LOGP: case ADC_BUF_ROLLOUT_VALUE: case ADC_BUF_ROLLOUT_REWARD:
+    case ADC_BUF_ROLLOUT_TERMINATED: case ADC_BUF_ROLLOUT_TRUNCATED: case ADC_BUF_ROLLOUT_OBS: {
+        if (e->ro_T == 0) return fail(ADC_ESTATE, "the rollout record is not enabled (adc_engine_rollout_enable)");
+        const size_t tn = (size_t)e->ro_T * N;
+        if (buffer_id == ADC_BUF_ROLLOUT_ACTION) { p = e->ro_action; b = tn * (size_t)e->mp.A * 4; }
+        else if (buffer_id == ADC_BUF_ROLLOUT_LOGP) { p = e->ro_logp; b = tn * 4; }
+        else if (buffer_id == ADC_BUF_ROLLOUT_VALUE) { p = e->ro_value; b = tn * 4; }
+        else if (buffer_id == ADC_BUF_ROLLOUT_REWARD) { p = e->ro_reward; b = tn * 4; }
+        else if (buffer_id == ADC_BUF_ROLLOUT_TERMINATED) { p = e->ro_term; b = tn; }
+        else if (buffer_id == ADC_BUF_ROLLOUT_TRUNCATED) { p = e->ro_trunc; b = tn; }
+        else {
+            if (!e->ro_obs) return fail(ADC_ESTATE, "the record was enabled without ADC_ROLLOUT_OBS");
+            p = e->ro_obs; b = tn * (size_t)e->mp.D * 4;
+        }
+        break;
+    }
     default: return fail(ADC_EINVAL, "unknown buffer id");
     }
     *dptr = p;
@@ -2587,6 +2617,336 @@ ADC_EXPORT int adc_engine_interp_entries(adc_engine *e, int32_t *capacity, int32
     return ADC_OK;
 }
 
+// ---- the MLP policy, one agent per env (parts/kernel_mlp_policy.inc) ------------------------------------------------------
+namespace {
+template <typename T>
+int mlp_alloc(adc_engine *e, std::vector<void *> &owner, T **p, size_t count)
+{
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(T), sizeof(T));
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(ADC_ENOMEM, "hipMalloc failed (MLP policy)"); }
+    owner.push_back(q);
+    if (hipMemsetAsync(q, 0, bytes, e->stream) != hipSuccess) return fail(ADC_EHIP, "hipMemsetAsync failed");
+    *p = static_cast<T *>(q);
+    return ADC_OK;
+}
+inline void mlp_free(adc_engine *e, std::vector<void *> &owner)
+{
+    if (!owner.empty()) (void)hipStreamSynchronize(e->stream);
+    for (void *q : owner) (void)hipFree(q);
+    owner.clear();
+}
+// the agent's view of the env group that starts at env e0
+inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
+{
+    MlpView p = e->mp;
+    const size_t oa = e0 * (size_t)p.A;
+    p.key += e0; p.tick += e0; p.mean += oa; p.ls += oa; p.action += oa; p.logp += e0; p.value += e0;
+    return p;
+}
+void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode, const float *replay_z, float budget_override, float *d_bids,
+                       float *d_budget, const MlpRecordSlot &rec, float *value_out)
+{
+    hipLaunchKernelGGL(k_mlp_policy, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+                       budget_override, d_bids, d_budget, rec, value_out);
+}
+int mlp_ready(const adc_engine *e)
+{
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    for (int l = 0; l < e->mp.pol.layers; ++l)
+        if (!e->mlp_layer_set[0][l]) return fail(ADC_ESTATE, "a policy layer has not been uploaded (adc_engine_mlp_set_layer)");
+    for (int l = 0; l < e->mp.val.layers; ++l)
+        if (!e->mlp_layer_set[1][l]) return fail(ADC_ESTATE, "a value layer has not been uploaded (adc_engine_mlp_set_layer)");
+    if (e->mlp_cfg.normalize && !e->mlp_norm_set) return fail(ADC_ESTATE, "the normalisation vectors have not been uploaded (adc_engine_mlp_set_norm)");
+    if (!e->mp.two_heads && !e->mlp_log_std_set) return fail(ADC_ESTATE, "log_std has not been uploaded (adc_engine_mlp_set_log_std)");
+    return ADC_OK;
+}
+inline bool rollout_room(const adc_engine *e, long long more) { return e->ro_T == 0 || (long long)e->ro_t + more <= (long long)e->ro_T; }
+// the record's slot t for the envs from e0 on (all null when `record` is false)
+inline MlpRecordSlot rollout_slot(const adc_engine *e, bool record, int t, size_t e0)
+{
+    MlpRecordSlot r{nullptr, nullptr, nullptr, nullptr};
+    if (!record) return r;
+    const size_t n = (size_t)e->v.N, row = (size_t)t * n + e0;
+    r.action = e->ro_action + row * (size_t)e->mp.A;
+    r.logp = e->ro_logp + row;
+    r.value = e->ro_value + row;
+    if (e->ro_obs) r.obs = e->ro_obs + row * (size_t)e->mp.D;
+    return r;
+}
+// act on the engine's last observation, group by group inside a chain; `record`: also into slot ro_t of the record
+// (the callers have checked mlp_ready)
+int mlp_act_chained(adc_engine *e, float budget_override, bool record)
+{
+    const int t = e->ro_t;
+    return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
+        const size_t e0 = (size_t)(d_budget - e->d_budget);       // (the group's first env)
+        mlp_launch_kernel(v, mlp_view_from(e, e0), st, 0, nullptr, budget_override, d_bids, d_budget, rollout_slot(e, record, t, e0), nullptr);
+    });
+}
+int mlp_record_outcome_chained(adc_engine *e)
+{
+    const int t = e->ro_t;
+    const int rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *, float *d_budget) {
+        const size_t row = (size_t)t * (size_t)e->v.N + (size_t)(d_budget - e->d_budget);
+        hipLaunchKernelGGL(k_mlp_record_outcome, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->ro_reward + row, e->ro_term + row,
+                           e->ro_trunc + row);
+    });
+    if (!rc) e->ro_t += 1;
+    return rc;
+}
+// one day of the learned agent: act (+ the per-step ideal profit when asked for and curves are built), the env's step, the record
+int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
+{
+    const bool record = e->ro_T > 0;
+    if (record && !rollout_room(e, 1)) return fail(ADC_EINVAL, "the rollout record is full: adc_engine_rollout_reset before recording another day");
+    int rc;
+    if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
+    if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
+    if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
+    return record ? mlp_record_outcome_chained(e) : ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const char *why = nullptr;
+    if (adc_mlp_config_check(cfg, e->v.K, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    const int K = e->v.K, A = K + 1, D = 5 * K + 2;
+    const int P = cfg->policy_widths[cfg->n_policy_layers - 1];
+    if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
+    ENGINE_GUARD(e);
+    mlp_free(e, e->mlp_allocs);
+    e->have_mlp = false;
+    MlpView p{};
+    const size_t N = e->v.N;
+    int rc;
+    auto net = [&](MlpNet &n, int layers, const int32_t *widths) {
+        n.layers = layers;
+        int n_in = D;
+        for (int l = 0; l < layers; ++l) {
+            float *w = nullptr, *b = nullptr;
+            if ((rc = mlp_alloc(e, e->mlp_allocs, &w, adc::mlp_weight_count(n_in, widths[l]))) || (rc = mlp_alloc(e, e->mlp_allocs, &b, (size_t)widths[l])))
+                return rc;
+            n.W[l] = w; n.b[l] = b; n.n_in[l] = n_in; n.n_out[l] = widths[l];
+            n_in = widths[l];
+        }
+        return (int)ADC_OK;
+    };
+    if ((rc = net(p.pol, cfg->n_policy_layers, cfg->policy_widths)) || (rc = net(p.val, cfg->n_value_layers, cfg->value_widths))) return rc;
+    float *shift = nullptr, *scale = nullptr, *log_std = nullptr;
+    if (cfg->normalize) {
+        if ((rc = mlp_alloc(e, e->mlp_allocs, &shift, (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &scale, (size_t)D))) return rc;
+    }
+    if ((rc = mlp_alloc(e, e->mlp_allocs, &log_std, (size_t)A))) return rc;
+    p.shift = shift; p.scale = scale; p.log_std = log_std;
+    p.activation = cfg->activation == ADC_MLP_TANH ? adc::kMlpTanh : adc::kMlpRelu;
+    p.two_heads = P == 2 * A;
+    p.clamp = cfg->clamp_log_std != 0; p.ls_lo = cfg->log_std_lo; p.ls_hi = cfg->log_std_hi;
+    p.clip_hi = cfg->bid_clip_hi;
+    p.deterministic = cfg->deterministic != 0;
+    p.A = A; p.D = D; p.P = P;
+    if ((rc = mlp_alloc(e, e->mlp_allocs, &p.key, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.tick, N)) ||
+        (rc = mlp_alloc(e, e->mlp_allocs, &p.mean, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.ls, N * A)) ||
+        (rc = mlp_alloc(e, e->mlp_allocs, &p.action, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.logp, N)) ||
+        (rc = mlp_alloc(e, e->mlp_allocs, &p.value, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_boot, N)))
+        return rc;
+    e->mp = p;
+    e->mlp_cfg = *cfg;
+    std::memset(e->mlp_layer_set, 0, sizeof(e->mlp_layer_set));
+    e->mlp_norm_set = e->mlp_log_std_set = false;
+    uint64_t *d_seeds = nullptr;
+    hipError_t err = hipSuccess;
+    if (seeds_n) {
+        HIP_TRY(hipMalloc((void **)&d_seeds, N * 8));
+        err = hipMemcpyAsync(d_seeds, seeds_n, N * 8, hipMemcpyHostToDevice, e->stream);
+    }
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_mlp_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, e->mp, (int)N, d_seeds, e->cfg.seed, e->cfg.env_id_base);
+        err = hipGetLastError();
+    }
+    const hipError_t err2 = hipStreamSynchronize(e->stream);
+    (void)hipFree(d_seeds);
+    HIP_TRY(err);
+    HIP_TRY(err2);
+    e->have_mlp = true;
+    // (a record sized for another action width does not survive a re-initialisation)
+    if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (network != 0 && network != 1) return fail(ADC_EINVAL, "network: 0 (policy) or 1 (value)");
+    const MlpNet &n = network == 0 ? e->mp.pol : e->mp.val;
+    if (layer < 0 || layer >= n.layers) return fail(ADC_EINVAL, "no such layer");
+    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
+    ENGINE_GUARD(e);
+    const int n_in = n.n_in[layer], n_out = n.n_out[layer];
+    std::vector<float> w(adc::mlp_weight_count(n_in, n_out), 0.0f);
+    for (int j = 0; j < n_in; ++j)
+        for (int h = 0; h < n_out; ++h) w[adc::mlp_weight_index(j, h, n_out)] = weights_in_out[(size_t)j * n_out + h];
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(n.W[layer]), w.data(), w.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(n.b[layer]), bias_out, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mlp_layer_set[network][layer] = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, const float *scale_d)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (!e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
+    if (!shift_d || !scale_d) return fail(ADC_EINVAL, "shift or scale is NULL");
+    ENGINE_GUARD(e);
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.shift), shift_d, (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.scale), scale_d, (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mlp_norm_set = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_log_std(adc_engine *e, const float *log_std_a)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (!log_std_a) return fail(ADC_EINVAL, "log_std is NULL");
+    ENGINE_GUARD(e);
+    HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.log_std), log_std_a, (size_t)e->mp.A * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mlp_log_std_set = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_deterministic(adc_engine *e, int32_t deterministic)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    ENGINE_GUARD(e);
+    e->mp.deterministic = deterministic != 0;
+    e->mlp_cfg.deterministic = deterministic != 0;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = mlp_ready(e)) return rc;
+    ENGINE_GUARD(e);
+    float *d_z = nullptr;
+    const size_t na = (size_t)e->v.N * (size_t)e->mp.A;
+    hipError_t err = hipSuccess;
+    if (replay_normals_na) {
+        if (hipMalloc((void **)&d_z, na * 4) != hipSuccess) { (void)hipGetLastError(); return fail(ADC_ENOMEM, "hipMalloc failed"); }
+        err = hipMemcpyAsync(d_z, replay_normals_na, na * 4, hipMemcpyHostToDevice, e->stream);
+    }
+    if (err == hipSuccess) {
+        mlp_launch_kernel(e->v, e->mp, e->stream, 0, d_z, budget_override, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, nullptr);
+        err = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(e->stream);
+    (void)hipFree(d_z);
+    HIP_TRY(err);
+    HIP_TRY(e2);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_step(adc_engine *e, float budget_override)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
+    if (int rc = mlp_ready(e)) return rc;
+    ENGINE_GUARD_STEP(e);
+    return mlp_day(e, budget_override, /* with_ideal = */ false);
+}
+
+ADC_EXPORT int adc_engine_mlp_last(adc_engine *e, float *mean_na, float *log_std_na, float *action_na, float *logp_n, float *value_n)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    const size_t n = (size_t)e->v.N, na = n * (size_t)e->mp.A;
+    if (mean_na) HIP_TRY(hipMemcpyAsync(mean_na, e->mp.mean, na * 4, hipMemcpyDeviceToHost, e->stream));
+    if (log_std_na) HIP_TRY(hipMemcpyAsync(log_std_na, e->mp.ls, na * 4, hipMemcpyDeviceToHost, e->stream));
+    if (action_na) HIP_TRY(hipMemcpyAsync(action_na, e->mp.action, na * 4, hipMemcpyDeviceToHost, e->stream));
+    if (logp_n) HIP_TRY(hipMemcpyAsync(logp_n, e->mp.logp, n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (value_n) HIP_TRY(hipMemcpyAsync(value_n, e->mp.value, n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_bootstrap_value(adc_engine *e, float *value_n)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!value_n) return fail(ADC_EINVAL, "value_n is NULL");
+    if (int rc = mlp_ready(e)) return rc;
+    if (e->mp.val.layers == 0) return fail(ADC_ESTATE, "the policy has no value network");
+    ENGINE_GUARD(e);
+    mlp_launch_kernel(e->v, e->mp, e->stream, 1, nullptr, 0.0f, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, e->mlp_boot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(value_n, e->mlp_boot, (size_t)e->v.N * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t fields)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (horizon < 0 || horizon > (1 << 20)) return fail(ADC_EINVAL, "horizon: 0 (off) to 2^20 days");
+    if (fields & ~ADC_ROLLOUT_OBS) return fail(ADC_EINVAL, "unknown rollout field");
+    ENGINE_GUARD(e);
+    mlp_free(e, e->ro_allocs);
+    e->ro_T = e->ro_t = 0;
+    e->ro_obs = nullptr;
+    if (horizon == 0) return ADC_OK;
+    const size_t tn = (size_t)horizon * (size_t)e->v.N;
+    int rc;
+    if ((rc = mlp_alloc(e, e->ro_allocs, &e->ro_action, tn * (size_t)e->mp.A)) || (rc = mlp_alloc(e, e->ro_allocs, &e->ro_logp, tn)) ||
+        (rc = mlp_alloc(e, e->ro_allocs, &e->ro_value, tn)) || (rc = mlp_alloc(e, e->ro_allocs, &e->ro_reward, tn)) ||
+        (rc = mlp_alloc(e, e->ro_allocs, &e->ro_term, tn)) || (rc = mlp_alloc(e, e->ro_allocs, &e->ro_trunc, tn)) ||
+        ((fields & ADC_ROLLOUT_OBS) && (rc = mlp_alloc(e, e->ro_allocs, &e->ro_obs, tn * (size_t)e->mp.D)))) {
+        mlp_free(e, e->ro_allocs);
+        e->ro_obs = nullptr;
+        return rc;
+    }
+    e->ro_T = horizon;
+    e->ro_fields = fields;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
+{
+    ENGINE_GUARD(e);
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
+    e->ro_t = 0;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_rollout_fetch(adc_engine *e, int32_t *days_recorded, float *action_tna, float *logp_tn, float *value_tn, float *reward_tn,
+                                        uint8_t *terminated_tn, uint8_t *truncated_tn, float *obs_tnd)
+{
+    ENGINE_GUARD(e);
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
+    if (obs_tnd && !e->ro_obs) return fail(ADC_ESTATE, "the record was enabled without ADC_ROLLOUT_OBS");
+    if (days_recorded) *days_recorded = e->ro_t;
+    const size_t tn = (size_t)e->ro_t * (size_t)e->v.N;
+    if (tn > 0) {
+        if (action_tna) HIP_TRY(hipMemcpyAsync(action_tna, e->ro_action, tn * (size_t)e->mp.A * 4, hipMemcpyDeviceToHost, e->stream));
+        if (logp_tn) HIP_TRY(hipMemcpyAsync(logp_tn, e->ro_logp, tn * 4, hipMemcpyDeviceToHost, e->stream));
+        if (value_tn) HIP_TRY(hipMemcpyAsync(value_tn, e->ro_value, tn * 4, hipMemcpyDeviceToHost, e->stream));
+        if (reward_tn) HIP_TRY(hipMemcpyAsync(reward_tn, e->ro_reward, tn * 4, hipMemcpyDeviceToHost, e->stream));
+        if (terminated_tn) HIP_TRY(hipMemcpyAsync(terminated_tn, e->ro_term, tn, hipMemcpyDeviceToHost, e->stream));
+        if (truncated_tn) HIP_TRY(hipMemcpyAsync(truncated_tn, e->ro_trunc, tn, hipMemcpyDeviceToHost, e->stream));
+        if (obs_tnd) HIP_TRY(hipMemcpyAsync(obs_tnd, e->ro_obs, tn * (size_t)e->mp.D * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
 // ---- `days` days of the device-resident loop in one call.  Optionally (adc_engine_day_graph_enable) two consecutive
 // days (both step parities) are captured once as a hipGraph and replayed.  Measured on MI355X at 1-256 envs x 100
 // keywords (tools/measure_small_loop.py): 28-50 us per day either way - the 7 dependent kernels of a day are bound by
@@ -2605,6 +2965,8 @@ int one_day(adc_engine *e, int policy, float budget)
     } else if (policy == ADC_POLICY_ORACLE) {
         if ((rc = ideal_step_chained(e))) return rc;
         if ((rc = policy_oracle_chained(e, budget))) return rc;
+    } else if (policy == ADC_POLICY_MLP) {
+        return mlp_day(e, budget, /* with_ideal = */ true);
     }
     return launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true);
 }
@@ -2622,8 +2984,12 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
     ENGINE_GUARD(e);
     if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
     if (policy != ADC_POLICY_FIXED_ACTIONS && policy != ADC_POLICY_ZERO_MARGIN && policy != ADC_POLICY_ORACLE &&
-        policy != ADC_POLICY_INTERPOLATION)
+        policy != ADC_POLICY_INTERPOLATION && policy != ADC_POLICY_MLP)
         return fail(ADC_EINVAL, "unknown policy");
+    if (policy == ADC_POLICY_MLP) {
+        if (int ready = mlp_ready(e)) return ready;
+        if (days > 0 && !rollout_room(e, days)) return fail(ADC_EINVAL, "the rollout record would overflow within these days: adc_engine_rollout_reset first");
+    }
     if (policy == ADC_POLICY_ZERO_MARGIN && !e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
     if (policy == ADC_POLICY_INTERPOLATION) {
         if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
@@ -2633,7 +2999,7 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
     if (days < 0) return fail(ADC_EINVAL, "days < 0");
     int rc;
     // profiling brackets kernels with events on the stream: keep that path un-captured
-    bool use_graph = e->day_graph_enabled && !e->profiling && days >= 4;
+    bool use_graph = e->day_graph_enabled && !e->profiling && days >= 4 && policy != ADC_POLICY_MLP;    // (the learned agent's days are never captured)
     if (use_graph && e->v.model == ADC_MODEL_IMPLICIT && e->volume_hint_dirty && !(e->fast_tiles_per_wg && e->fast_variant)) {
         if ((rc = refresh_volume_hint(e))) return rc;        // (synchronises: must not happen inside a capture)
     }

@@ -559,7 +559,82 @@ class StepEngine:
         check(self._lib.adc_engine_get_actions(self._h, bids.ctypes.data, budget.ctypes.data))
         return bids, budget
 
-    POLICIES = {"fixed": 0, "zero_margin": 1, "oracle": 2, "interpolation": 3}
+    # ---- the MLP policy, one agent per env (parts/kernel_mlp_policy.inc; baselines/mlp_policy.py builds `policy`) ----------
+    def mlp_init(self, policy, seeds=None, deterministic=None):
+        """shapes and options of an MLPPolicy, then its weights; deterministic (if given) overrides the policy's own flag"""
+        cfg = policy.config(self.num_keywords, deterministic)
+        sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
+        check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
+        self._mlp = policy
+        self.mlp_set_weights(policy)
+
+    def mlp_set_weights(self, policy):
+        """upload every layer, the normalisation vectors and log_std of `policy` (same shapes as at mlp_init): a trainer's
+        update between days; nothing else of the agent changes"""
+        if getattr(self, "_mlp", None) is None:
+            raise _ffi.EngineStateError("mlp_init has not been called")
+        if policy.shapes() != self._mlp.shapes():
+            raise ValueError(f"mlp_set_weights: the policy's shapes {policy.shapes()} are not those given to mlp_init "
+                             f"{self._mlp.shapes()} (layers, value layers, free log_std, normalisation)")
+        for net, layers in ((0, policy.layers), (1, policy.value_layers)):
+            for i, (w, b) in enumerate(layers):
+                check(self._lib.adc_engine_mlp_set_layer(self._h, net, i, w.ctypes.data, b.ctypes.data))
+        if policy.shift is not None:
+            check(self._lib.adc_engine_mlp_set_norm(self._h, policy.shift.ctypes.data, policy.scale.ctypes.data))
+        if policy.log_std is not None:
+            check(self._lib.adc_engine_mlp_set_log_std(self._h, policy.log_std.ctypes.data))
+
+    def mlp_set_deterministic(self, on=True):
+        check(self._lib.adc_engine_mlp_set_deterministic(self._h, 1 if on else 0))
+
+    def mlp_act(self, budget_override=0.0, replay_normals=None):
+        z = None
+        if replay_normals is not None:
+            z = np.ascontiguousarray(np.asarray(replay_normals, dtype=np.float32).reshape(self.num_envs, self.num_keywords + 1))
+        check(self._lib.adc_engine_mlp_act(self._h, float(budget_override), None if z is None else z.ctypes.data))
+
+    def mlp_step(self, budget_override=0.0):
+        """act + the env's step on the device (recorded when rollout_enable is on)"""
+        check(self._lib.adc_engine_mlp_step(self._h, float(budget_override)))
+
+    def mlp_last(self):
+        """the last act: mean, log_std, action [N, K+1] (flat action order: budget, bids), logp, value [N]"""
+        n, a = self.num_envs, self.num_keywords + 1
+        st = dict(mean=np.zeros((n, a), np.float32), log_std=np.zeros((n, a), np.float32), action=np.zeros((n, a), np.float32),
+                  logp=np.zeros(n, np.float32), value=np.zeros(n, np.float32))
+        check(self._lib.adc_engine_mlp_last(self._h, *(st[k].ctypes.data for k in ("mean", "log_std", "action", "logp", "value"))))
+        return st
+
+    def mlp_bootstrap_value(self):
+        v = np.zeros(self.num_envs, np.float32)
+        check(self._lib.adc_engine_mlp_bootstrap_value(self._h, v.ctypes.data))
+        return v
+
+    def rollout_enable(self, horizon, obs=False):
+        check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
+        self._rollout_obs = bool(obs) and int(horizon) > 0
+
+    def rollout_reset(self):
+        check(self._lib.adc_engine_rollout_reset(self._h))
+
+    def rollout_fetch(self, bootstrap=False):
+        """the recorded days so far: dict of action [T, N, K+1], logp, value, reward [T, N] (float32), terminated, truncated
+        [T, N] (bool), obs [T, N, 5K+2] when recorded; bootstrap=True adds bootstrap_value [N]"""
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        T, n, a = t.value, self.num_envs, self.num_keywords + 1
+        st = dict(action=np.zeros((T, n, a), np.float32), logp=np.zeros((T, n), np.float32), value=np.zeros((T, n), np.float32),
+                  reward=np.zeros((T, n), np.float32), terminated=np.zeros((T, n), np.uint8), truncated=np.zeros((T, n), np.uint8))
+        if getattr(self, "_rollout_obs", False):
+            st["obs"] = np.zeros((T, n, 5 * self.num_keywords + 2), np.float32)
+        check(self._lib.adc_engine_rollout_fetch(self._h, None, *(st[k].ctypes.data for k in (
+            "action", "logp", "value", "reward", "terminated", "truncated")), st["obs"].ctypes.data if "obs" in st else None))
+        st["terminated"], st["truncated"] = st["terminated"].astype(bool), st["truncated"].astype(bool)
+        if bootstrap:
+            st["bootstrap_value"] = self.mlp_bootstrap_value()
+        return st
+
+    POLICIES = {"fixed": 0, "zero_margin": 1, "oracle": 2, "interpolation": 3, "mlp": 4}
 
     # ---- multi-GPU: the episode-metric all-reduce (RCCL behind the C ABI; adcraft_amd/comm.py brings it up) ----------
     def comm_unique_id(self):

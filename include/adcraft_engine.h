@@ -131,7 +131,15 @@ typedef enum adc_buffer {
     ADC_BUF_TRUNCATED = 12,
     ADC_BUF_METRIC_PROFIT = 13,/* int64 [K]  sum over local envs and steps of keyword profit, cents (valid after metrics_read) */
     ADC_BUF_METRIC_SCALARS = 14,/* int64 [8]  {profit_cents, env_steps, episodes, truncations, auctions, 0,0,0} */
-    ADC_BUF_FLAT_OBS = 15      /* float [N][5K+2] FlatArrayWrapper layout (adcraft/wrappers/flat_array.py:74-80) */
+    ADC_BUF_FLAT_OBS = 15,     /* float [N][5K+2] FlatArrayWrapper layout (adcraft/wrappers/flat_array.py:74-80) */
+    /* the rollout record of the MLP policy (adc_engine_rollout_enable), horizon T, A = K + 1, D = 5K + 2 */
+    ADC_BUF_ROLLOUT_ACTION = 16,    /* float [T][N][A] unclipped actions, flat action order [budget, bids...] */
+    ADC_BUF_ROLLOUT_LOGP = 17,      /* float [T][N] */
+    ADC_BUF_ROLLOUT_VALUE = 18,     /* float [T][N] */
+    ADC_BUF_ROLLOUT_REWARD = 19,    /* float [T][N] */
+    ADC_BUF_ROLLOUT_TERMINATED = 20,/* uint8 [T][N] */
+    ADC_BUF_ROLLOUT_TRUNCATED = 21, /* uint8 [T][N] */
+    ADC_BUF_ROLLOUT_OBS = 22        /* float [T][N][D] the (normalised) network input; only with ADC_ROLLOUT_OBS */
 } adc_buffer;
 
 /* replay ("tape") variate source: the variates the reference drew, in the order it drew them
@@ -454,7 +462,8 @@ int adc_engine_get_actions(adc_engine *e, float *bids_nk, float *budget_n);
  * the engine's stream.  adc_engine_day_graph_enable(e, 1) makes it replay pairs of days from a captured hipGraph
  * (same results; measured no faster on MI355X - the dependent kernels of a day are latency-, not launch-bound - and an engine
  * whose chain of days runs as env groups, see adc_engine_env_groups, keeps the plain chain, which is the faster of the two). */
-enum adc_policy { ADC_POLICY_FIXED_ACTIONS = 0, ADC_POLICY_ZERO_MARGIN = 1, ADC_POLICY_ORACLE = 2, ADC_POLICY_INTERPOLATION = 3 };
+enum adc_policy { ADC_POLICY_FIXED_ACTIONS = 0, ADC_POLICY_ZERO_MARGIN = 1, ADC_POLICY_ORACLE = 2, ADC_POLICY_INTERPOLATION = 3,
+                  ADC_POLICY_MLP = 4 /* adc_engine_mlp_step per day, plus adc_engine_ideal_step when curves are built; never captured */ };
 int adc_engine_run_days(adc_engine *e, int policy, int32_t days, float budget);
 int adc_engine_day_graph_enable(adc_engine *e, int enabled);
 /* per (env, keyword) metric sums to host (any pointer may be NULL): profit in cents, ideal, ideal with <= 0 -> 1;
@@ -464,6 +473,59 @@ int adc_engine_metrics_read_nk(adc_engine *e, int64_t *profit_cents_nk, double *
  * bitonic sort per env in LDS; numpy's median convention), ncp_n[N]; 2 N doubles cross the bus instead of 3 N K.
  * num_keywords <= 4096. */
 int adc_engine_metrics_akncp_ncp(adc_engine *e, double days, double *akncp_n, double *ncp_n);
+
+/* ---- the MLP policy: a learned agent on the device (parts/kernel_mlp_policy.inc; the law is csrc/adc_mlp.h) -----------
+ * A fully connected policy network - and optionally a value network - of up to 4 Linear layers each, hidden widths up to 256,
+ * tanh or relu between them, evaluated per env and day on the flat observation (the FlatArrayWrapper row, read from the
+ * engine's output arrays; all zeros on the first day of an episode, also right after an auto-reset).  The policy network
+ * ends in A = K + 1 means (flat action order [budget, bids...]) with a free log_std[A] vector, or in 2A values, means then
+ * log-stds.  action = mean + exp(log_std) * z with z from the agent's own Philox stream (stage 14; the env's stream does
+ * not move), or action = mean (deterministic), or z handed in (replay).  Bids go to the env as max(action, 0.01), clipped
+ * above when bid_clip_hi > 0, rounded to cents; the budget as max(action[0], 0.01) or budget_override when that is > 0.
+ * Every operation is a fixed sequence of correctly rounded float32 / float64 operations: adc_mlp_act_host gives the same
+ * bits on the host. */
+enum adc_mlp_activation { ADC_MLP_TANH = 0, ADC_MLP_RELU = 1 };
+typedef struct adc_mlp_config {
+    uint32_t struct_size;          /* sizeof(adc_mlp_config) */
+    int32_t activation;            /* adc_mlp_activation */
+    int32_t n_policy_layers;       /* 1..4 */
+    int32_t policy_widths[4];      /* outputs of each policy layer; the last is A or 2A */
+    int32_t n_value_layers;        /* 0 (no value network; values are 0) or 1..4 */
+    int32_t value_widths[4];       /* outputs of each value layer; the last is 1 */
+    int32_t normalize;             /* nonzero: x = (x - shift[j]) * scale[j] (adc_engine_mlp_set_norm) */
+    int32_t clamp_log_std;         /* nonzero: log_std clamped to [log_std_lo, log_std_hi] */
+    float log_std_lo, log_std_hi;
+    float bid_clip_hi;             /* > 0: bids clipped above at this many dollars */
+    int32_t deterministic;         /* nonzero: action = mean, no draws */
+} adc_mlp_config;
+/* shapes and options; every weight, bias and vector starts at zero and must be uploaded before the first act.  seeds_n (may be
+ * NULL: keyed by the engine seed and the global env id) seeds the agents' streams, tick 0.  A second call re-initialises. */
+int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n);
+/* one Linear layer: network 0 = policy, 1 = value; weights_in_out is [n_in][n_out] row-major (input-major: torch's
+ * weight.T), bias [n_out].  May be called again at any time between days (a trainer's update); nothing else changes. */
+int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out);
+int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, const float *scale_d);
+int adc_engine_mlp_set_log_std(adc_engine *e, const float *log_std_a);
+int adc_engine_mlp_set_deterministic(adc_engine *e, int32_t deterministic);
+/* act on the observation the last step left: actions into the engine's action buffers; replay_normals_na (may be NULL)
+ * replaces the draws.  Every act moves the agents' ticks on by one.  Not recorded. */
+int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na);
+/* act + the env's step on the device (chain-compatible, like adc_engine_step_device); recorded when a rollout record is on */
+int adc_engine_mlp_step(adc_engine *e, float budget_override);
+/* the last act's means, clamped log-stds, unclipped actions [N][A], log-probabilities and values [N] (any may be NULL) */
+int adc_engine_mlp_last(adc_engine *e, float *mean_na, float *log_std_na, float *action_na, float *logp_n, float *value_n);
+/* the value network on the observation the last step left (zeros for an env that has just been reset): the bootstrap value */
+int adc_engine_mlp_bootstrap_value(adc_engine *e, float *value_n);
+/* the rollout record: per recorded day t < horizon and env the unclipped action [A], log-probability, value, reward (float32
+ * of the step's float64 reward), terminated, truncated and - with ADC_ROLLOUT_OBS - the network's input [D]; arrays laid out
+ * [T][N][...], on the device (ADC_BUF_ROLLOUT_*) and fetched to the host.  adc_engine_mlp_step and adc_engine_run_days
+ * (ADC_POLICY_MLP) record; a day past the horizon is refused until adc_engine_rollout_reset.  horizon 0 turns it off. */
+enum adc_rollout_fields { ADC_ROLLOUT_OBS = 1 };
+int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t fields);
+int adc_engine_rollout_reset(adc_engine *e);
+/* *days_recorded and the first that many days of every array asked for (any pointer may be NULL) */
+int adc_engine_rollout_fetch(adc_engine *e, int32_t *days_recorded, float *action_tna, float *logp_tn, float *value_tn, float *reward_tn,
+                             uint8_t *terminated_tn, uint8_t *truncated_tn, float *obs_tnd);
 
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
@@ -538,6 +600,26 @@ int adc_interp_act_host(float ave_rpc, int32_t num_rpc_obs, float ave_sctr, int3
                         double *mass_out);
 /* the cache key of a bid: float(bidstr(bid)) = round(float(float32 bid), 2) */
 double adc_interp_key_host(float bid);
+/* one env's act of the MLP policy, on the host: the same code as the device's (adc_mlp.h).  obs_d: the flat observation row
+ * (NULL: zeros, the first day).  policy_w[l] / value_w[l]: [n_in][n_out] row-major as for adc_engine_mlp_set_layer.  Normals:
+ * normals_a when given, else drawn from (agent_key, tick) unless cfg->deterministic.  Out (any may be NULL): mean_a, log_std_a,
+ * action_a [A], *logp, *value, bids_k [K] (cent bids as the env gets them), *budget. */
+int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords, const float *obs_d, const float *const *policy_w,
+                     const float *const *policy_b, const float *const *value_w, const float *const *value_b, const float *shift_d,
+                     const float *scale_d, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,
+                     float budget_override, float *mean_a, float *log_std_out_a, float *action_a, float *logp, float *value,
+                     float *bids_k, float *budget);
+/* the checks adc_engine_mlp_init makes on a configuration for num_keywords keywords; *message (may be NULL) names the failure */
+int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const char **message);
+/* the law's own tanh (fn 0) and exp (fn 1) at one float32, and a sweep over every float32 in [lo, hi] against the host's float64
+ * libm: out3 = {maximum absolute error, maximum error in float32 ulps of the exact value, |result| maximum}; violations4 =
+ * {f(-x) != -f(x) (tanh only), f(x) < f(previous x), |tanh| > 1, NaN results}.  Returns the number of values swept. */
+float adc_mlp_math_host(int32_t fn, float x);
+int64_t adc_mlp_math_sweep_host(int32_t fn, float lo, float hi, double *out3, int64_t *violations4);
+/* the agent key adc_engine_mlp_init derives from a per-env seed */
+uint64_t adc_mlp_agent_key_host(uint64_t seed);
+/* ... and the one it derives without seeds, from the engine's seed and the env's global id (env_id_base + env) */
+uint64_t adc_mlp_default_agent_key_host(uint64_t engine_seed, uint64_t global_env_id);
 /* diagnostic: the stream's generator (Philox4x32, the stream's round count) evaluated on the device for n counters ctr4[n][4]
  * and keys key2[n][2] -> out4[n][4]; tests compare it with the CPU battery's generator (oracle/stream_battery.c) */
 int adc_debug_philox_device(int device_id, int64_t n, const uint32_t *ctr4, const uint32_t *key2, uint32_t *out4);

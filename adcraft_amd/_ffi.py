@@ -16,6 +16,8 @@ P_VOL_MEAN, P_VOL_STD, P_A, P_B, P_BCTR, P_SCTR, P_REV_MEAN, P_REV_STD, P_COUNT 
  BUF_ROLLOUT_ACTION, BUF_ROLLOUT_LOGP, BUF_ROLLOUT_VALUE, BUF_ROLLOUT_REWARD, BUF_ROLLOUT_TERMINATED, BUF_ROLLOUT_TRUNCATED,
  BUF_ROLLOUT_OBS) = range(23)
 MLP_TANH, MLP_RELU = 0, 1
+ES_CENTERED_RANK, ES_RAW = 0, 1
+ES_ADAM, ES_SGD = 0, 1
 ROLLOUT_OBS = 1
 
 
@@ -52,6 +54,16 @@ class MLPConfig(C.Structure):
                 ("policy_widths", C.c_int32 * 4), ("n_value_layers", C.c_int32), ("value_widths", C.c_int32 * 4),
                 ("normalize", C.c_int32), ("clamp_log_std", C.c_int32), ("log_std_lo", C.c_float), ("log_std_hi", C.c_float),
                 ("bid_clip_hi", C.c_float), ("deterministic", C.c_int32)]
+
+
+class ESConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sigma", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("l2", C.c_float), ("shaping", C.c_int32), ("optimiser", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ESStats(C.Structure):
+    _fields_ = [("generation", C.c_int64), ("fitness_mean", C.c_double), ("fitness_max", C.c_double), ("fitness_min", C.c_double),
+                ("grad_norm", C.c_double), ("theta_norm", C.c_double)]
 
 
 class Tape(C.Structure):
@@ -195,6 +207,20 @@ def lib():
         "adc_engine_rollout_enable": ([vp, i32, i32], C.c_int),
         "adc_engine_rollout_reset": ([vp], C.c_int),
         "adc_engine_rollout_fetch": ([vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_population": ([vp, i32, vp], C.c_int),
+        "adc_engine_mlp_set_member_layer": ([vp, i32, i32, vp, vp], C.c_int),
+        "adc_engine_mlp_param_count": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_mlp_get_params": ([vp, vp], C.c_int),
+        "adc_engine_mlp_get_member_params": ([vp, i32, vp], C.c_int),
+        "adc_engine_es_init": ([vp, C.POINTER(ESConfig)], C.c_int),
+        "adc_engine_es_perturb": ([vp], C.c_int),
+        "adc_engine_es_fitness": ([vp, vp], C.c_int),
+        "adc_engine_es_update": ([vp, vp, C.POINTER(ESStats)], C.c_int),
+        "adc_engine_es_state_get": ([vp, vp, vp, vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_es_state_set": ([vp, vp, vp, vp, i64], C.c_int),
+        "adc_es_config_check": ([C.POINTER(ESConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_es_noise_host": ([u64, C.c_uint32, C.c_uint32, i64, i64, vp], C.c_int),
+        "adc_es_update_host": ([C.POINTER(ESConfig), u64, i32, i64, vp, i64, vp, vp, vp, vp], C.c_int),
         "adc_mlp_config_check": ([C.POINTER(MLPConfig), i32, C.POINTER(C.c_char_p)], C.c_int),
         "adc_mlp_act_host": ([C.POINTER(MLPConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
                               vp, vp, vp, vp, vp, vp, vp], C.c_int),

@@ -46,6 +46,8 @@
 //        normals of a keyword's cost samples by a radix select; k_explicit_curve_points); the policy kernels read them too.
 //   parts/kernel_interp_agent.inc the interpolation agent (NaiveInterpolationStrategy): its caches, update and act
 //        (k_interp_step); the per-keyword act itself is adc_interp.h, shared with the host twin.
+//   parts/kernel_mlp_policy.inc   the learned agent: a fully connected policy (and value) network per env, or per member of a population.
+//   parts/kernel_es.inc           policy populations and the evolution strategy: perturbation, returns, gradient estimate + Adam (adc_es.h).
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //
 // No CPU path exists in this library.
@@ -66,6 +68,7 @@
 #include "adc_law.h"
 #include "adc_interp.h"
 #include "adc_mlp.h"
+#include "adc_es.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -82,6 +85,7 @@ namespace adck {
 #include "parts/kernel_explicit_curves.inc"
 #include "parts/kernel_interp_agent.inc"
 #include "parts/kernel_mlp_policy.inc"
+#include "parts/kernel_es.inc"
 }  // namespace adck
 using namespace adck;
 

@@ -43,6 +43,7 @@ namespace adc {
 //           call (j, ST_GCLICK) = {click, conversion, revenue} words of auction j.
 enum Stage : uint32_t { ST_VOL = 0, ST_AUCTION = 1, ST_DRIFT = 2, ST_XPHANTOM = 3, ST_XREV = 4, ST_ACTION = 5, ST_METRIC = 6, ST_CONV = 7, ST_KEYGEN = 8, ST_AGENT = 9,
                         ST_GBIDDERS = 10, ST_GBID = 11, ST_GCLICK = 12, ST_INTERP = 13, ST_MLP = 14 };
+// (stage 15 is the evolution strategy's parameter noise under its own key: adc_es.h ST_ES)
 constexpr int kTimesteps = 24;          // adcraft/bidding_simulation.py:213
 constexpr int kVolumeMax = 1 << 20;
 constexpr float kMoneyMaxCents = 1.0e9f;

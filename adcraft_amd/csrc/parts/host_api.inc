@@ -79,6 +79,21 @@ struct adc_engine {
     bool mlp_norm_set = false, mlp_log_std_set = false;
     float *mlp_boot = nullptr;          // [N] adc_engine_mlp_bootstrap_value's device result
     std::vector<void *> mlp_allocs;     // weights, vectors and last-act arrays (re-allocated by every adc_engine_mlp_init)
+    // a population of policies (adc_engine_mlp_population) and the evolution strategy over it (adc_engine_es_init; parts/kernel_es.inc)
+    ParamLayout pl{};                   // the flat parameter order of the policy network (set by adc_engine_mlp_init)
+    float *mlp_flat = nullptr;          // [P] staging of one flat parameter vector
+    int pop_M = 0;
+    std::vector<int32_t> pop_map;       // [N] env -> member (host copy)
+    std::vector<int32_t> pop_count;     // [M] envs per member
+    std::vector<void *> pop_allocs;     // the members' layers and the device map (freed by mlp_init and by a new population)
+    bool have_es = false, es_accumulate = false;
+    adc_es_config es_cfg{};
+    uint64_t es_key = 0;
+    int64_t es_generation = 0;
+    long long es_days = 0;              // days stepped since the last adc_engine_es_perturb
+    float *es_theta = nullptr, *es_m = nullptr, *es_v = nullptr, *es_grad = nullptr;     // [P]
+    double *es_du = nullptr, *es_return = nullptr;                                        // [M / 2], [N]
+    std::vector<void *> es_allocs;
     // the rollout record (adc_engine_rollout_enable): [T][N][...] arrays, ro_t days recorded so far
     int ro_T = 0, ro_t = 0, ro_fields = 0;
     float *ro_action = nullptr, *ro_logp = nullptr, *ro_value = nullptr, *ro_reward = nullptr, *ro_obs = nullptr;
@@ -765,6 +780,8 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     if (e->h_direct) (void)hipHostFree(e->h_direct);
     for (void *p : e->curve_allocs) (void)hipFree(p);
     for (void *p : e->mlp_allocs) (void)hipFree(p);
+    for (void *p : e->pop_allocs) (void)hipFree(p);
+    for (void *p : e->es_allocs) (void)hipFree(p);
     for (void *p : e->ro_allocs) (void)hipFree(p);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -2642,13 +2659,19 @@ inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
     MlpView p = e->mp;
     const size_t oa = e0 * (size_t)p.A;
     p.key += e0; p.tick += e0; p.mean += oa; p.ls += oa; p.action += oa; p.logp += e0; p.value += e0;
+    if (p.member) p.member += e0;
     return p;
 }
 void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode, const float *replay_z, float budget_override, float *d_bids,
                        float *d_budget, const MlpRecordSlot &rec, float *value_out)
 {
-    hipLaunchKernelGGL(k_mlp_policy, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
-                       budget_override, d_bids, d_budget, rec, value_out);
+    // (two instantiations: without a population the kernel is the single-policy code, untouched by the members' addressing)
+    if (p.member)
+        hipLaunchKernelGGL(k_mlp_policy<true>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+                           budget_override, d_bids, d_budget, rec, value_out);
+    else
+        hipLaunchKernelGGL(k_mlp_policy<false>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+                           budget_override, d_bids, d_budget, rec, value_out);
 }
 int mlp_ready(const adc_engine *e)
 {
@@ -2695,6 +2718,15 @@ int mlp_record_outcome_chained(adc_engine *e)
     if (!rc) e->ro_t += 1;
     return rc;
 }
+// the evolution strategy's side of a stepped day: every env's reward added to its return of the generation
+int es_accumulate_chained(adc_engine *e)
+{
+    const int rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *, float *d_budget) {
+        hipLaunchKernelGGL(k_es_accumulate, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->es_return + (size_t)(d_budget - e->d_budget));
+    });
+    if (!rc) e->es_days += 1;
+    return rc;
+}
 // one day of the learned agent: act (+ the per-step ideal profit when asked for and curves are built), the env's step, the record
 int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
 {
@@ -2704,7 +2736,43 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
     if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
     if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
-    return record ? mlp_record_outcome_chained(e) : ADC_OK;
+    if (record && (rc = mlp_record_outcome_chained(e))) return rc;
+    return e->es_accumulate ? es_accumulate_chained(e) : ADC_OK;
+}
+// a population and the strategy over it go with the policy they belong to
+void population_drop(adc_engine *e)
+{
+    mlp_free(e, e->pop_allocs);
+    mlp_free(e, e->es_allocs);
+    e->pop_M = 0;
+    e->pop_map.clear();
+    e->pop_count.clear();
+    e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0;
+    e->have_es = e->es_accumulate = false;
+    e->es_days = 0;
+}
+inline unsigned es_quad_blocks(int P) { return (unsigned)(((P + 3) / 4 + kEsBlock - 1) / kEsBlock); }
+ParamStore centre_store(const adc_engine *e)
+{
+    ParamStore s{};
+    for (int l = 0; l < e->mp.pol.layers; ++l) { s.W[l] = const_cast<float *>(e->mp.pol.W[l]); s.b[l] = const_cast<float *>(e->mp.pol.b[l]); }
+    return s;
+}
+ParamStore member_store(const adc_engine *e, int member)
+{
+    ParamStore s{};
+    float *base = const_cast<float *>(e->mp.pop) + (size_t)member * e->mp.pop_stride;
+    for (int l = 0; l < e->pl.layers; ++l) { s.W[l] = base + e->pl.offW[l]; s.b[l] = base + e->pl.offb[l]; }
+    return s;
+}
+// the store's parameters in the flat order, to the host
+int params_fetch(adc_engine *e, const ParamStore &s, float *flat)
+{
+    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, s, e->mlp_flat, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(flat, e->mlp_flat, (size_t)e->pl.P * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
 }
 }  // namespace
 
@@ -2717,6 +2785,7 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     const int P = cfg->policy_widths[cfg->n_policy_layers - 1];
     if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
     ENGINE_GUARD(e);
+    population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
     mlp_free(e, e->mlp_allocs);
     e->have_mlp = false;
     MlpView p{};
@@ -2747,6 +2816,25 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     p.clip_hi = cfg->bid_clip_hi;
     p.deterministic = cfg->deterministic != 0;
     p.A = A; p.D = D; p.P = P;
+    // the flat parameter order, and a member's block: its layers one after the other, each starting on a 16-byte boundary
+    ParamLayout pl{};
+    pl.layers = p.pol.layers;
+    {
+        size_t off = 0;
+        int flat = 0;
+        for (int l = 0; l < pl.layers; ++l) {
+            pl.n_in[l] = p.pol.n_in[l]; pl.n_out[l] = p.pol.n_out[l];
+            pl.flat0[l] = flat;
+            flat += pl.n_in[l] * pl.n_out[l] + pl.n_out[l];
+            pl.offW[l] = (uint32_t)off; off += adc::mlp_weight_count(pl.n_in[l], pl.n_out[l]);
+            pl.offb[l] = (uint32_t)off; off += ((size_t)pl.n_out[l] + 3u) & ~(size_t)3u;
+            p.pop_offW[l] = pl.offW[l]; p.pop_offb[l] = pl.offb[l];
+        }
+        pl.P = flat;
+        pl.stride = (uint32_t)off;
+        e->pl = pl;
+        if ((rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_flat, (size_t)flat))) return rc;
+    }
     if ((rc = mlp_alloc(e, e->mlp_allocs, &p.key, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.tick, N)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &p.mean, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.ls, N * A)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &p.action, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.logp, N)) ||
@@ -2889,6 +2977,266 @@ ADC_EXPORT int adc_engine_mlp_bootstrap_value(adc_engine *e, float *value_n)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(value_n, e->mlp_boot, (size_t)e->v.N * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+// ---- policy populations: per-member weights of the policy network (parts/kernel_es.inc) ---------------------------------------
+ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const int32_t *member_of_env_n)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    const int N = e->v.N, M = members;
+    if (M < 0 || M > 65536) return fail(ADC_EINVAL, "members: 0 (off) to 65536");
+    std::vector<int32_t> map((size_t)N), count((size_t)M, 0);
+    if (M > 0) {
+        if (!member_of_env_n && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs when no member_of_env map is given");
+        for (int env = 0; env < N; ++env) {
+            const int32_t m = member_of_env_n ? member_of_env_n[env] : env / (N / M);
+            if (m < 0 || m >= M) return fail(ADC_EINVAL, "member_of_env names a member outside [0, members)");
+            map[(size_t)env] = m;
+            count[(size_t)m] += 1;
+        }
+    }
+    ENGINE_GUARD(e);
+    if (M == 0) { population_drop(e); return ADC_OK; }
+    // (the new population is allocated before the old one goes: a failure leaves the engine as it was)
+    void *block = nullptr, *d_map = nullptr;
+    if (hipMalloc(&block, (size_t)M * e->pl.stride * 4) != hipSuccess || hipMalloc(&d_map, (size_t)N * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        if (block) (void)hipFree(block);
+        return fail(ADC_ENOMEM, "hipMalloc failed (policy population)");
+    }
+    population_drop(e);
+    e->pop_allocs.push_back(block);
+    e->pop_allocs.push_back(d_map);
+    HIP_TRY(hipMemsetAsync(block, 0, (size_t)M * e->pl.stride * 4, e->stream));       // (the never-read padding too)
+    HIP_TRY(hipMemcpyAsync(d_map, map.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    // every member starts as the centre
+    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e),
+                       e->mlp_flat, 1);
+    hipLaunchKernelGGL(k_es_perturb, dim3(es_quad_blocks(e->pl.P), (unsigned)((M + 1) / 2)), dim3(kEsBlock), 0, e->stream, e->pl, e->mlp_flat,
+                       static_cast<float *>(block), (size_t)e->pl.stride, M, 0, (uint64_t)0, 0u, 0.0f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mp.member = static_cast<const int32_t *>(d_map);
+    e->mp.pop = static_cast<const float *>(block);
+    e->mp.pop_stride = e->pl.stride;
+    e->pop_M = M;
+    e->pop_map.swap(map);
+    e->pop_count.swap(count);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_member_layer(adc_engine *e, int32_t member, int32_t layer, const float *weights_in_out, const float *bias_out)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (e->pop_M == 0) return fail(ADC_ESTATE, "adc_engine_mlp_population has not been called");
+    if (member < 0 || member >= e->pop_M) return fail(ADC_EINVAL, "no such member");
+    if (layer < 0 || layer >= e->pl.layers) return fail(ADC_EINVAL, "no such layer");
+    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
+    ENGINE_GUARD(e);
+    const int n_in = e->pl.n_in[layer], n_out = e->pl.n_out[layer];
+    std::vector<float> w(adc::mlp_weight_count(n_in, n_out), 0.0f);
+    for (int j = 0; j < n_in; ++j)
+        for (int h = 0; h < n_out; ++h) w[adc::mlp_weight_index(j, h, n_out)] = weights_in_out[(size_t)j * n_out + h];
+    const ParamStore s = member_store(e, member);
+    HIP_TRY(hipMemcpyAsync(s.W[layer], w.data(), w.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s.b[layer], bias_out, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_param_count(adc_engine *e, int64_t *count)
+{
+    if (!e || !count) return fail(ADC_EINVAL, "engine handle or count is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    *count = e->pl.P;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_get_params(adc_engine *e, float *flat_p)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (!flat_p) return fail(ADC_EINVAL, "flat_p is NULL");
+    ENGINE_GUARD(e);
+    return params_fetch(e, centre_store(e), flat_p);
+}
+
+ADC_EXPORT int adc_engine_mlp_get_member_params(adc_engine *e, int32_t member, float *flat_p)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (e->pop_M == 0) return fail(ADC_ESTATE, "adc_engine_mlp_population has not been called");
+    if (member < 0 || member >= e->pop_M) return fail(ADC_EINVAL, "no such member");
+    if (!flat_p) return fail(ADC_EINVAL, "flat_p is NULL");
+    ENGINE_GUARD(e);
+    return params_fetch(e, member_store(e, member), flat_p);
+}
+
+// ---- the evolution strategy over a population (the law is csrc/adc_es.h) ---------------------------------------------------
+namespace {
+int es_ready(const adc_engine *e)
+{
+    if (!e->have_es) return fail(ADC_ESTATE, "adc_engine_es_init has not been called");
+    return ADC_OK;
+}
+int es_members_have_envs(const adc_engine *e)
+{
+    for (int32_t c : e->pop_count)
+        if (c == 0) return fail(ADC_EINVAL, "a member of the population has no env: it has no fitness");
+    return ADC_OK;
+}
+// a member's fitness: the float64 mean of its envs' returns, envs ascending (the envs' streams have been joined by the guard)
+int es_fitness_fetch(adc_engine *e, double *fitness_m)
+{
+    const size_t N = (size_t)e->v.N;
+    std::vector<double> ret(N);
+    HIP_TRY(hipMemcpyAsync(ret.data(), e->es_return, N * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int m = 0; m < e->pop_M; ++m) fitness_m[m] = 0.0;
+    for (size_t env = 0; env < N; ++env) fitness_m[e->pop_map[env]] = fitness_m[e->pop_map[env]] + ret[env];
+    for (int m = 0; m < e->pop_M; ++m) fitness_m[m] = fitness_m[m] / (double)e->pop_count[(size_t)m];
+    return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_es_init(adc_engine *e, const adc_es_config *cfg)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const char *why = nullptr;
+    if (adc_es_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if (int rc = mlp_ready(e)) return rc;
+    if (e->pop_M == 0) return fail(ADC_ESTATE, "the evolution strategy needs a population (adc_engine_mlp_population)");
+    if (e->pop_M & 1) return fail(ADC_EINVAL, "the evolution strategy needs an even number of members (antithetic pairs)");
+    ENGINE_GUARD(e);
+    const size_t P = (size_t)e->pl.P;
+    std::vector<void *> fresh;
+    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
+    double *du = nullptr, *ret = nullptr;
+    int rc;
+    if ((rc = mlp_alloc(e, fresh, &theta, P)) || (rc = mlp_alloc(e, fresh, &m, P)) || (rc = mlp_alloc(e, fresh, &v, P)) ||
+        (rc = mlp_alloc(e, fresh, &grad, P)) || (rc = mlp_alloc(e, fresh, &du, (size_t)e->pop_M / 2)) ||
+        (rc = mlp_alloc(e, fresh, &ret, (size_t)e->v.N))) {
+        mlp_free(e, fresh);
+        return rc;
+    }
+    mlp_free(e, e->es_allocs);
+    e->es_allocs.swap(fresh);
+    e->es_theta = theta; e->es_m = m; e->es_v = v; e->es_grad = grad; e->es_du = du; e->es_return = ret;
+    e->es_cfg = *cfg;
+    e->es_key = adc::es_key(cfg->seed ? cfg->seed : e->cfg.seed);
+    e->es_generation = 0;
+    e->es_days = 0;
+    e->es_accumulate = false;
+    // theta starts as the centre policy
+    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e),
+                       e->es_theta, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->have_es = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_es_perturb(adc_engine *e)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = es_ready(e)) return rc;
+    ENGINE_GUARD(e);
+    hipLaunchKernelGGL(k_es_perturb, dim3(es_quad_blocks(e->pl.P), (unsigned)(e->pop_M / 2)), dim3(kEsBlock), 0, e->stream, e->pl, e->es_theta,
+                       const_cast<float *>(e->mp.pop), e->mp.pop_stride, e->pop_M, 1, e->es_key, (uint32_t)e->es_generation, e->es_cfg.sigma);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(e->es_return, 0, (size_t)e->v.N * 8, e->stream));
+    e->es_days = 0;
+    e->es_accumulate = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_es_fitness(adc_engine *e, double *fitness_m)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!fitness_m) return fail(ADC_EINVAL, "fitness_m is NULL");
+    if (int rc = es_ready(e)) return rc;
+    if (int rc = es_members_have_envs(e)) return rc;
+    ENGINE_GUARD(e);
+    return es_fitness_fetch(e, fitness_m);
+}
+
+ADC_EXPORT int adc_engine_es_update(adc_engine *e, const double *fitness_m, adc_es_stats *stats)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = es_ready(e)) return rc;
+    if (int rc = es_members_have_envs(e)) return rc;
+    if (!fitness_m && e->es_days == 0) return fail(ADC_EINVAL, "no day has been stepped since adc_engine_es_perturb and no fitness was handed in");
+    ENGINE_GUARD(e);
+    const int M = e->pop_M;
+    const size_t P = (size_t)e->pl.P;
+    std::vector<double> fit((size_t)M), du;
+    if (fitness_m) std::copy(fitness_m, fitness_m + M, fit.begin());
+    else if (int rc = es_fitness_fetch(e, fit.data())) return rc;
+    adc::es_shape(e->es_cfg.shaping == ADC_ES_RAW ? adc::kEsRaw : adc::kEsCenteredRank, fit.data(), M, du);
+    const uint32_t t = (uint32_t)(e->es_generation + 1);
+    adc::EsStep step{};
+    step.optimiser = e->es_cfg.optimiser == ADC_ES_SGD ? adc::kEsSgd : adc::kEsAdam;
+    step.lr = e->es_cfg.lr; step.beta1 = e->es_cfg.beta1; step.beta2 = e->es_cfg.beta2; step.eps = e->es_cfg.eps; step.l2 = e->es_cfg.l2;
+    step.c1 = adc::es_bias_correction(step.beta1, t);
+    step.c2 = adc::es_bias_correction(step.beta2, t);
+    HIP_TRY(hipMemcpyAsync(e->es_du, du.data(), du.size() * 8, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_es_update, dim3((unsigned)(((e->pl.P + 3) / 4 + kEsUpdQuads - 1) / kEsUpdQuads)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e), e->es_theta, e->es_m,
+                       e->es_v, e->es_grad, e->es_du, M, e->es_key, (uint32_t)e->es_generation, e->es_cfg.sigma, step);
+    HIP_TRY(hipGetLastError());
+    std::vector<float> g(P), th(P);
+    HIP_TRY(hipMemcpyAsync(g.data(), e->es_grad, P * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(th.data(), e->es_theta, P * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->es_generation += 1;
+    e->es_accumulate = false;
+    e->es_days = 0;
+    if (stats) {
+        double sum = 0.0, mx = fit[0], mn = fit[0], gg = 0.0, tt = 0.0;
+        for (double f : fit) { sum += f; mx = f > mx ? f : mx; mn = f < mn ? f : mn; }
+        for (size_t p = 0; p < P; ++p) { gg += (double)g[p] * (double)g[p]; tt += (double)th[p] * (double)th[p]; }
+        stats->generation = e->es_generation;
+        stats->fitness_mean = sum / (double)M; stats->fitness_max = mx; stats->fitness_min = mn;
+        stats->grad_norm = std::sqrt(gg); stats->theta_norm = std::sqrt(tt);
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_es_state_get(adc_engine *e, float *theta_p, float *m_p, float *v_p, int64_t *generation)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = es_ready(e)) return rc;
+    ENGINE_GUARD(e);
+    const size_t bytes = (size_t)e->pl.P * 4;
+    if (theta_p) HIP_TRY(hipMemcpyAsync(theta_p, e->es_theta, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (m_p) HIP_TRY(hipMemcpyAsync(m_p, e->es_m, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (v_p) HIP_TRY(hipMemcpyAsync(v_p, e->es_v, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (generation) *generation = e->es_generation;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_es_state_set(adc_engine *e, const float *theta_p, const float *m_p, const float *v_p, int64_t generation)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = es_ready(e)) return rc;
+    if (!theta_p || !m_p || !v_p) return fail(ADC_EINVAL, "theta, m or v is NULL");
+    if (generation < 0 || generation > 0x7FFFFFFFll) return fail(ADC_EINVAL, "generation: 0 to 2^31 - 1");
+    ENGINE_GUARD(e);
+    const size_t bytes = (size_t)e->pl.P * 4;
+    HIP_TRY(hipMemcpyAsync(e->es_theta, theta_p, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->es_m, m_p, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->es_v, v_p, bytes, hipMemcpyHostToDevice, e->stream));
+    // (the centre's chain-major copy follows theta, so that evaluation without a population sees it)
+    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e),
+                       e->es_theta, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->es_generation = generation;
+    e->es_accumulate = false;
+    e->es_days = 0;
     return ADC_OK;
 }
 

@@ -28,6 +28,12 @@ struct MlpView {
     uint32_t *tick;                         // [N]
     float *mean, *ls, *action;              // [N][A] of the last act
     float *logp, *value;                    // [N]
+    // a population (adc_engine_mlp_population): env -> member, and the members' policy layers at pop + member * pop_stride
+    // (+ pop_offW[l] / pop_offb[l]), each layer in the layout of W / b above.  member == null: every env runs `pol`.
+    const int32_t *member;                  // [N]
+    const float *pop;
+    size_t pop_stride;                      // floats
+    uint32_t pop_offW[adc::kMlpMaxLayers], pop_offb[adc::kMlpMaxLayers];
 };
 
 // where one recorded day goes: the slot's rows of the view's first env (null: that field is off)
@@ -88,21 +94,27 @@ __device__ __forceinline__ void mlp_layer(const float *__restrict__ W, const flo
     __syncthreads();
 }
 
-// one network on the input row at `lds`; leaves its outputs at out_last
-__device__ __forceinline__ void mlp_network(const MlpNet &net, int activation, float *lds, int D, float *out_last)
+// one network on the input row at `lds`; leaves its outputs at out_last.  kPop: the layers are a member's (at mbase), not net's own
+template <bool kPop>
+__device__ __forceinline__ void mlp_network(const MlpNet &net, const MlpView &p, const float *mbase, int activation, float *lds, int D,
+                                            float *out_last)
 {
     const float *in = lds;
     float *h0 = lds + D, *h1 = h0 + adc::kMlpMaxWidth;
     for (int l = 0; l < net.layers; ++l) {
         const bool last = l + 1 == net.layers;
         float *out = last ? out_last : ((l & 1) ? h1 : h0);
-        mlp_layer(net.W[l], net.b[l], net.n_in[l], net.n_out[l], in, out, last ? -1 : activation);
+        const float *W = kPop ? mbase + p.pop_offW[l] : net.W[l];
+        const float *b = kPop ? mbase + p.pop_offb[l] : net.b[l];
+        mlp_layer(W, b, net.n_in[l], net.n_out[l], in, out, last ? -1 : activation);
         in = out;
     }
 }
 
 // mode 0: act (policy and value networks, sample, actions, record);  mode 1: the value network alone into value_out (the
-// bootstrap value of the observation the last step left) - no draw, no tick, nothing else written
+// bootstrap value of the observation the last step left) - no draw, no tick, nothing else written.
+// kPop: the env's policy layers are its member's (two instantiations, so that the single-policy kernel is the code it was)
+template <bool kPop>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int mode, const float *__restrict__ replay_z,
                                                           float budget_override, float *__restrict__ bids, float *__restrict__ budgets,
                                                           MlpRecordSlot rec, float *__restrict__ value_out)
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
     float *out = mlp_lds + D + 2 * adc::kMlpMaxWidth;
     if (p.val.layers > 0) {
         // (the value network's single output lands in the first float of `out`, which the policy network overwrites afterwards)
-        mlp_network(p.val, p.activation, mlp_lds, D, out);
+        mlp_network<false>(p.val, p, nullptr, p.activation, mlp_lds, D, out);
         if (tid == 0) s_value = out[0];
         __syncthreads();
     } else if (tid == 0) s_value = 0.0f;
@@ -135,7 +147,7 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         if (tid == 0) value_out[env] = s_value;
         return;
     }
-    mlp_network(p.pol, p.activation, mlp_lds, D, out);
+    mlp_network<kPop>(p.pol, p, kPop ? p.pop + (size_t)p.member[env] * p.pop_stride : nullptr, p.activation, mlp_lds, D, out);
     // heads, sample, the env's action; the log-probability's terms replace the means in LDS
     const uint64_t key = p.key[env];
     const uint32_t tick = p.tick[env];

@@ -566,6 +566,7 @@ class StepEngine:
         sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
         check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
         self._mlp = policy
+        self._members = 0                   # (a population does not survive a re-initialisation)
         self.mlp_set_weights(policy)
 
     def mlp_set_weights(self, policy):
@@ -609,6 +610,97 @@ class StepEngine:
         v = np.zeros(self.num_envs, np.float32)
         check(self._lib.adc_engine_mlp_bootstrap_value(self._h, v.ctypes.data))
         return v
+
+    # ---- policy populations and the evolution strategy over them (parts/kernel_es.inc; baselines/es_trainer.py drives it) ------
+    def mlp_population(self, members, member_of_env=None):
+        """`members` copies of the policy network's layers, each starting as the centre policy; member_of_env [N] (default
+        env // (N // members)) says whose weights an env runs.  0 turns the population off.  The value network, log_std and
+        the normalisation stay shared."""
+        m = None if member_of_env is None else np.ascontiguousarray(member_of_env, dtype=np.int32)
+        if m is not None and m.shape != (self.num_envs,):
+            raise ValueError("member_of_env: one member per env")
+        check(self._lib.adc_engine_mlp_population(self._h, int(members), None if m is None else m.ctypes.data))
+        self._members = int(members)
+
+    def mlp_set_member(self, member, policy):
+        """the policy layers of `policy` (same shapes as at mlp_init) into one member"""
+        if getattr(self, "_mlp", None) is None:
+            raise _ffi.EngineStateError("mlp_init has not been called")
+        if [w.shape for w, _ in policy.layers] != [w.shape for w, _ in self._mlp.layers]:
+            raise ValueError("mlp_set_member: the policy's layer shapes are not those given to mlp_init")
+        for i, (w, b) in enumerate(policy.layers):
+            check(self._lib.adc_engine_mlp_set_member_layer(self._h, int(member), i, w.ctypes.data, b.ctypes.data))
+
+    def mlp_param_count(self):
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_mlp_param_count(self._h, C.byref(n)))
+        return n.value
+
+    def mlp_params(self):
+        """the centre policy's parameters in the flat order (layers in order, W input-major then b)"""
+        flat = np.zeros(self.mlp_param_count(), np.float32)
+        check(self._lib.adc_engine_mlp_get_params(self._h, flat.ctypes.data))
+        return flat
+
+    def mlp_member_params(self, member):
+        flat = np.zeros(self.mlp_param_count(), np.float32)
+        check(self._lib.adc_engine_mlp_get_member_params(self._h, int(member), flat.ctypes.data))
+        return flat
+
+    ES_SHAPINGS = {"centered_rank": _ffi.ES_CENTERED_RANK, "raw": _ffi.ES_RAW}
+    ES_OPTIMISERS = {"adam": _ffi.ES_ADAM, "sgd": _ffi.ES_SGD}
+
+    @classmethod
+    def es_config(cls, sigma=0.02, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, l2=0.0, shaping="centered_rank", optimiser="adam", seed=0):
+        c = _ffi.ESConfig()
+        c.struct_size = C.sizeof(_ffi.ESConfig)
+        c.sigma, c.lr, c.beta1, c.beta2, c.eps, c.l2 = sigma, lr, beta1, beta2, eps, l2
+        c.shaping, c.optimiser, c.seed = cls.ES_SHAPINGS[shaping], cls.ES_OPTIMISERS[optimiser], int(seed)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_es_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad ES configuration").decode())
+        return c
+
+    def es_init(self, **options):
+        """an evolution strategy over the population (csrc/adc_es.h); options as es_config's.  theta starts as the centre."""
+        cfg = self.es_config(**options)
+        check(self._lib.adc_engine_es_init(self._h, C.byref(cfg)))
+
+    def es_perturb(self):
+        """members = theta +- sigma * noise of the current generation; returns zeroed; accumulation on"""
+        check(self._lib.adc_engine_es_perturb(self._h))
+
+    def es_fitness(self):
+        """[members] float64: the mean over a member's envs of the reward summed over the days since es_perturb"""
+        f = np.zeros(getattr(self, "_members", 0), np.float64)
+        check(self._lib.adc_engine_es_fitness(self._h, f.ctypes.data))
+        return f
+
+    def es_update(self, fitness=None):
+        """one generation's step from the device's fitness (or `fitness` [members]); dict of generation, fitness_mean / max /
+        min, grad_norm, theta_norm"""
+        f = None if fitness is None else np.ascontiguousarray(fitness, dtype=np.float64)
+        members = getattr(self, "_members", 0)
+        if f is not None and members and f.shape != (members,):
+            raise ValueError("fitness: one value per member")
+        st = _ffi.ESStats()
+        check(self._lib.adc_engine_es_update(self._h, None if f is None else f.ctypes.data, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _ffi.ESStats._fields_}
+
+    def es_state(self, state=None):
+        """get (no argument): dict of theta, m, v [P] float32 and generation; set: such a dict - the run continues bit for bit"""
+        if state is None:
+            P = self.mlp_param_count()
+            st = dict(theta=np.zeros(P, np.float32), m=np.zeros(P, np.float32), v=np.zeros(P, np.float32))
+            g = C.c_int64(0)
+            check(self._lib.adc_engine_es_state_get(self._h, st["theta"].ctypes.data, st["m"].ctypes.data, st["v"].ctypes.data, C.byref(g)))
+            st["generation"] = g.value
+            return st
+        P = self.mlp_param_count()
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in ("theta", "m", "v")]
+        if any(a.shape != (P,) for a in arr):
+            raise ValueError(f"es_state: theta, m and v have {P} entries")
+        check(self._lib.adc_engine_es_state_set(self._h, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["generation"])))
 
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))

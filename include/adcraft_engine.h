@@ -527,6 +527,58 @@ int adc_engine_rollout_reset(adc_engine *e);
 int adc_engine_rollout_fetch(adc_engine *e, int32_t *days_recorded, float *action_tna, float *logp_tn, float *value_tn, float *reward_tn,
                              uint8_t *terminated_tn, uint8_t *truncated_tn, float *obs_tnd);
 
+/* ---- policy populations: per-member weights of the policy network (parts/kernel_es.inc) ------------------------------------
+ * After adc_engine_mlp_init, `members` = M > 0 gives the engine M copies of the POLICY network's layers (weights and biases),
+ * each starting as the centre policy (what adc_engine_mlp_set_layer uploaded), and every env the member it evaluates:
+ * member_of_env_n[N] with entries in [0, M), or NULL for env / (N / M) (M must then divide N).  The value network, log_std,
+ * the normalisation vectors and the clamps stay shared by all members.  M = 0 turns the population off (the default: every
+ * env runs the centre).  Acts, steps, the rollout record, adc_engine_mlp_last and adc_engine_mlp_bootstrap_value work
+ * unchanged.  A population does not survive adc_engine_mlp_init, and a new population drops the evolution strategy over the
+ * old one.  adc_engine_mlp_set_layer keeps writing the centre alone.
+ * The flat parameter order (length P, adc_engine_mlp_param_count): the policy layers in order, each W[j][h] input-major
+ * (index j * n_out + h) followed by its b[h]. */
+int adc_engine_mlp_population(adc_engine *e, int32_t members, const int32_t *member_of_env_n);
+int adc_engine_mlp_set_member_layer(adc_engine *e, int32_t member, int32_t layer, const float *weights_in_out, const float *bias_out);
+int adc_engine_mlp_param_count(adc_engine *e, int64_t *count);
+int adc_engine_mlp_get_params(adc_engine *e, float *flat_p);                              /* the centre */
+int adc_engine_mlp_get_member_params(adc_engine *e, int32_t member, float *flat_p);
+
+/* ---- an evolution strategy on the device (OpenAI-ES; the law is csrc/adc_es.h) ----------------------------------------------
+ * Over a population of an even number of members: adc_engine_es_perturb writes member 2i / 2i + 1 = theta +- sigma * eps(i, g)
+ * from counter-addressed noise (Philox stage 15 under the strategy's own key; never stored), zeroes every env's return and
+ * turns accumulation on: every day stepped by adc_engine_mlp_step / adc_engine_run_days(ADC_POLICY_MLP) adds the env's float64
+ * reward to its return (through auto-resets too: fitness is the reward summed over the generation's days).  A member's fitness
+ * is the float64 mean of its envs' returns.  adc_engine_es_update shapes the fitness (the device's, or fitness_m[M] handed in),
+ * forms the gradient estimate with the noise regenerated, takes an Adam or SGD ascent step on theta, rebuilds the centre policy
+ * from it (so evaluation without a population and adc_engine_mlp_get_params see the new theta), moves the generation on by one
+ * and turns accumulation off.  theta starts as the centre policy at adc_engine_es_init; later adc_engine_mlp_set_layer calls do
+ * not reach it (adc_engine_es_state_set does). */
+enum adc_es_shaping { ADC_ES_CENTERED_RANK = 0, ADC_ES_RAW = 1 };
+enum adc_es_optimiser { ADC_ES_ADAM = 0, ADC_ES_SGD = 1 };
+typedef struct adc_es_config {
+    uint32_t struct_size;          /* sizeof(adc_es_config) */
+    float sigma;                   /* > 0: the perturbation's standard deviation */
+    float lr;                      /* >= 0 */
+    float beta1, beta2, eps;       /* Adam: 0 <= beta < 1, eps > 0 */
+    float l2;                      /* >= 0: gradient g - l2 * theta */
+    int32_t shaping;               /* adc_es_shaping */
+    int32_t optimiser;             /* adc_es_optimiser */
+    uint64_t seed;                 /* the noise's seed; 0: the engine's seed */
+} adc_es_config;
+typedef struct adc_es_stats {
+    int64_t generation;            /* after the update */
+    double fitness_mean, fitness_max, fitness_min;
+    double grad_norm, theta_norm;  /* Euclidean norms of the (decayed) gradient estimate and of the new theta */
+} adc_es_stats;
+int adc_engine_es_init(adc_engine *e, const adc_es_config *cfg);
+int adc_engine_es_perturb(adc_engine *e);
+int adc_engine_es_fitness(adc_engine *e, double *fitness_m);
+/* fitness_m may be NULL (the device's fitness: at least one day must have been stepped since the perturbation); stats may be NULL */
+int adc_engine_es_update(adc_engine *e, const double *fitness_m, adc_es_stats *stats);
+/* theta, the Adam moments [P] and the generation: a run resumed from them continues bit for bit (get: any pointer may be NULL) */
+int adc_engine_es_state_get(adc_engine *e, float *theta_p, float *m_p, float *v_p, int64_t *generation);
+int adc_engine_es_state_set(adc_engine *e, const float *theta_p, const float *m_p, const float *v_p, int64_t generation);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be
@@ -609,6 +661,14 @@ int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords, const floa
                      const float *scale_d, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,
                      float budget_override, float *mean_a, float *log_std_out_a, float *action_a, float *logp, float *value,
                      float *bids_k, float *budget);
+/* the evolution strategy on the host: the same code as the device's (adc_es.h).  `seed` is the effective seed (the
+ * configuration's, or the engine's when that is 0).  noise: eps(pair, generation)[p0 .. p0 + n).  update: one generation's
+ * shaping, gradient estimate and step on theta / m / v [n_params] in place from fitness_m[members]; `generation` is the one
+ * whose noise the members carried (the state's generation before the update); grad_p (may be NULL) receives the estimate. */
+int adc_es_config_check(const adc_es_config *cfg, const char **message);
+int adc_es_noise_host(uint64_t seed, uint32_t pair, uint32_t generation, int64_t p0, int64_t n, float *eps_n);
+int adc_es_update_host(const adc_es_config *cfg, uint64_t seed, int32_t members, int64_t n_params, const double *fitness_m, int64_t generation,
+                       float *theta_p, float *m_p, float *v_p, float *grad_p);
 /* the checks adc_engine_mlp_init makes on a configuration for num_keywords keywords; *message (may be NULL) names the failure */
 int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const char **message);
 /* the law's own tanh (fn 0) and exp (fn 1) at one float32, and a sweep over every float32 in [lo, hi] against the host's float64

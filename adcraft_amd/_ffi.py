@@ -19,6 +19,7 @@ MLP_TANH, MLP_RELU = 0, 1
 ES_CENTERED_RANK, ES_RAW = 0, 1
 ES_ADAM, ES_SGD = 0, 1
 ROLLOUT_OBS = 1
+PG_ADAM, PG_SGD = 0, 1
 
 
 class EngineError(RuntimeError):
@@ -64,6 +65,19 @@ class ESConfig(C.Structure):
 class ESStats(C.Structure):
     _fields_ = [("generation", C.c_int64), ("fitness_mean", C.c_double), ("fitness_max", C.c_double), ("fitness_min", C.c_double),
                 ("grad_norm", C.c_double), ("theta_norm", C.c_double)]
+
+
+class PGConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_float), ("lambda_", C.c_float), ("eps_clip", C.c_float), ("vf_coef", C.c_float),
+                ("ent_coef", C.c_float), ("reward_scale", C.c_float), ("normalize_advantages", C.c_int32), ("max_grad_norm", C.c_float),
+                ("optimiser", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("minibatch_envs", C.c_int32)]
+
+
+class PGStats(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("samples", C.c_int64), ("policy_loss", C.c_double), ("value_loss", C.c_double),
+                ("entropy", C.c_double), ("approx_kl", C.c_double), ("clip_fraction", C.c_double), ("grad_norm", C.c_double),
+                ("explained_variance", C.c_double)]
 
 
 class Tape(C.Structure):
@@ -204,6 +218,7 @@ def lib():
         "adc_engine_mlp_step": ([vp, f32], C.c_int),
         "adc_engine_mlp_last": ([vp, vp, vp, vp, vp, vp], C.c_int),
         "adc_engine_mlp_bootstrap_value": ([vp, vp], C.c_int),
+        "adc_engine_mlp_agent_state": ([vp, vp, vp], C.c_int),
         "adc_engine_rollout_enable": ([vp, i32, i32], C.c_int),
         "adc_engine_rollout_reset": ([vp], C.c_int),
         "adc_engine_rollout_fetch": ([vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp], C.c_int),
@@ -221,6 +236,20 @@ def lib():
         "adc_es_config_check": ([C.POINTER(ESConfig), C.POINTER(C.c_char_p)], C.c_int),
         "adc_es_noise_host": ([u64, C.c_uint32, C.c_uint32, i64, i64, vp], C.c_int),
         "adc_es_update_host": ([C.POINTER(ESConfig), u64, i32, i64, vp, i64, vp, vp, vp, vp], C.c_int),
+        "adc_engine_pg_init": ([vp, C.POINTER(PGConfig)], C.c_int),
+        "adc_engine_pg_param_count": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_pg_advantages": ([vp], C.c_int),
+        "adc_engine_pg_advantages_fetch": ([vp, vp, vp], C.c_int),
+        "adc_engine_pg_minibatch": ([vp, i32, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_pg_update": ([vp, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_pg_state_get": ([vp, vp, vp, vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_pg_state_set": ([vp, vp, vp, vp, i64], C.c_int),
+        "adc_pg_config_check": ([C.POINTER(PGConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_pg_gae_host": ([C.POINTER(PGConfig), i32, i32, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_pg_param_count_host": ([C.POINTER(MLPConfig), i32, C.POINTER(i64)], C.c_int),
+        "adc_pg_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(PGConfig), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                              C.POINTER(PGStats)], C.c_int),
+        "adc_pg_step_host": ([C.POINTER(PGConfig), i64, i64, vp, vp, vp, vp], C.c_int),
         "adc_mlp_config_check": ([C.POINTER(MLPConfig), i32, C.POINTER(C.c_char_p)], C.c_int),
         "adc_mlp_act_host": ([C.POINTER(MLPConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
                               vp, vp, vp, vp, vp, vp, vp], C.c_int),

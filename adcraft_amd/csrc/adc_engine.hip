@@ -48,7 +48,9 @@
 //        (k_interp_step); the per-keyword act itself is adc_interp.h, shared with the host twin.
 //   parts/kernel_mlp_policy.inc   the learned agent: a fully connected policy (and value) network per env, or per member of a population.
 //   parts/kernel_es.inc           policy populations and the evolution strategy: perturbation, returns, gradient estimate + Adam (adc_es.h).
+//   parts/kernel_pg.inc           policy-gradient training: GAE, the networks' backward pass, the weight gradient, the step (adc_pg.h).
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
+//   parts/pg_api.inc              the entry points of policy-gradient training.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -69,6 +71,7 @@
 #include "adc_interp.h"
 #include "adc_mlp.h"
 #include "adc_es.h"
+#include "adc_pg.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -86,8 +89,10 @@ namespace adck {
 #include "parts/kernel_interp_agent.inc"
 #include "parts/kernel_mlp_policy.inc"
 #include "parts/kernel_es.inc"
+#include "parts/kernel_pg.inc"
 }  // namespace adck
 using namespace adck;
 
 #include "parts/host_api.inc"
+#include "parts/pg_api.inc"
 #include "parts/comm_api.inc"

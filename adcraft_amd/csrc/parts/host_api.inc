@@ -99,6 +99,21 @@ struct adc_engine {
     float *ro_action = nullptr, *ro_logp = nullptr, *ro_value = nullptr, *ro_reward = nullptr, *ro_obs = nullptr;
     uint8_t *ro_term = nullptr, *ro_trunc = nullptr;
     std::vector<void *> ro_allocs;
+    bool ro_deterministic = false;      // a recorded day was collected with the deterministic policy: its log-probabilities mean nothing
+    // policy-gradient training over the record (adc_engine_pg_init; parts/kernel_pg.inc, parts/pg_api.inc)
+    bool have_pg = false, pg_adv_ready = false;
+    adc_pg_config pg_cfg{};
+    int64_t pg_steps = 0;               // optimiser steps taken
+    int pg_mb = 0;                      // envs of a minibatch (the scratch's capacity)
+    adc::PgShape pg_shape{};
+    PgLayout pg_lay{};
+    int pg_maxw = 0;
+    float *pg_theta = nullptr, *pg_m = nullptr, *pg_v = nullptr, *pg_grad = nullptr;    // [Q]
+    float *pg_adv = nullptr, *pg_ret = nullptr;                                          // [T][N]
+    float *pg_acts = nullptr, *pg_deltas = nullptr, *pg_pieces = nullptr;                // [T * minibatch envs][...]
+    double *pg_part = nullptr, *pg_sums = nullptr;                                       // chunk partials; the law's ten sums
+    double *pg_gpart = nullptr;                                                          // [chunks][Q] the weight gradient's partials
+    std::vector<void *> pg_allocs;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
     // two consecutive days of the device-resident loop captured as one hipGraph (adc_engine_run_days)
     hipGraphExec_t day_graph = nullptr;
@@ -783,6 +798,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->pop_allocs) (void)hipFree(p);
     for (void *p : e->es_allocs) (void)hipFree(p);
     for (void *p : e->ro_allocs) (void)hipFree(p);
+    for (void *p : e->pg_allocs) (void)hipFree(p);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -2715,7 +2731,7 @@ int mlp_record_outcome_chained(adc_engine *e)
         hipLaunchKernelGGL(k_mlp_record_outcome, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->ro_reward + row, e->ro_term + row,
                            e->ro_trunc + row);
     });
-    if (!rc) e->ro_t += 1;
+    if (!rc) { e->ro_t += 1; e->pg_adv_ready = false; }
     return rc;
 }
 // the evolution strategy's side of a stepped day: every env's reward added to its return of the generation
@@ -2733,11 +2749,19 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     const bool record = e->ro_T > 0;
     if (record && !rollout_room(e, 1)) return fail(ADC_EINVAL, "the rollout record is full: adc_engine_rollout_reset before recording another day");
     int rc;
+    if (record && e->mp.deterministic) e->ro_deterministic = true;
     if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
     if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
     if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
     if (record && (rc = mlp_record_outcome_chained(e))) return rc;
     return e->es_accumulate ? es_accumulate_chained(e) : ADC_OK;
+}
+// the policy-gradient trainer goes with the policy and the record it was sized for
+void pg_drop(adc_engine *e)
+{
+    mlp_free(e, e->pg_allocs);
+    e->have_pg = e->pg_adv_ready = false;
+    e->pg_steps = 0;
 }
 // a population and the strategy over it go with the policy they belong to
 void population_drop(adc_engine *e)
@@ -2786,6 +2810,7 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
     ENGINE_GUARD(e);
     population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
+    pg_drop(e);
     mlp_free(e, e->mlp_allocs);
     e->have_mlp = false;
     MlpView p{};
@@ -2962,6 +2987,16 @@ ADC_EXPORT int adc_engine_mlp_last(adc_engine *e, float *mean_na, float *log_std
     if (action_na) HIP_TRY(hipMemcpyAsync(action_na, e->mp.action, na * 4, hipMemcpyDeviceToHost, e->stream));
     if (logp_n) HIP_TRY(hipMemcpyAsync(logp_n, e->mp.logp, n * 4, hipMemcpyDeviceToHost, e->stream));
     if (value_n) HIP_TRY(hipMemcpyAsync(value_n, e->mp.value, n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_agent_state(adc_engine *e, uint64_t *keys_n, uint32_t *ticks_n)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (keys_n) HIP_TRY(hipMemcpyAsync(keys_n, e->mp.key, (size_t)e->v.N * 8, hipMemcpyDeviceToHost, e->stream));
+    if (ticks_n) HIP_TRY(hipMemcpyAsync(ticks_n, e->mp.tick, (size_t)e->v.N * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ADC_OK;
 }
@@ -3247,9 +3282,11 @@ ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t
     if (horizon < 0 || horizon > (1 << 20)) return fail(ADC_EINVAL, "horizon: 0 (off) to 2^20 days");
     if (fields & ~ADC_ROLLOUT_OBS) return fail(ADC_EINVAL, "unknown rollout field");
     ENGINE_GUARD(e);
+    pg_drop(e);                         // (its advantages and scratch were sized for the old record)
     mlp_free(e, e->ro_allocs);
     e->ro_T = e->ro_t = 0;
     e->ro_obs = nullptr;
+    e->ro_deterministic = false;
     if (horizon == 0) return ADC_OK;
     const size_t tn = (size_t)horizon * (size_t)e->v.N;
     int rc;
@@ -3271,6 +3308,8 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     ENGINE_GUARD(e);
     if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
     e->ro_t = 0;
+    e->ro_deterministic = false;
+    e->pg_adv_ready = false;
     return ADC_OK;
 }
 

@@ -1,0 +1,318 @@
+// kernel_pg.inc - policy-gradient training on the device: advantages from the rollout record, the forward recompute and the
+// backward pass of the policy and value networks per sample, the weight gradient over samples, the statistics' sums and the
+// optimiser step that rebuilds the policy kernel's chain-major layers.  The arithmetic is adc_pg.h's law, the code the host
+// twins adc_pg_gae_host / adc_pg_grad_host / adc_pg_step_host run.
+// (part of the single translation unit adc_engine.hip)
+// -------------------------------------------------------------------------------------------------
+// Shape.  k_pg_sample is k_mlp_policy's shape run both ways: one workgroup of 256 lanes per sample, every layer's activations
+// in LDS, eight adjacent lanes per neuron with the butterfly join; the transposed pass reads the same chain-major weights with
+// the roles of j and h swapped (a neuron's eight lanes read eight outputs' weights, 128 bytes apart - the layers are a few
+// hundred KB and stay in L2).  It leaves every layer's input activations and deltas in a scratch buffer.  k_pg_wgrad then is
+// X^T . Delta over samples in the law's chunk order: a workgroup owns a 16 x 16 tile of one layer's parameters (its bias the
+// row j = n_in with x = 1) and ONE chunk of 1024 samples, stages 64 samples' 16 inputs and 16 deltas in LDS at a time, and every
+// lane carries its parameter's float64 chain - one fused multiply-add per sample, exact products - and writes the chunk's
+// partial; k_pg_grad_join adds a parameter's partials in chunk order.  No atomics; all stores are plain vector stores.
+struct PgView {
+    adc::PgShape sh;
+    adc::PgLoss loss;
+    MlpNet net[2];                          // the device's chain-major layers: [0] policy, [1] value
+    const float *log_std;                   // [A] (free head)
+    const float *obs, *action, *logp, *value;       // the record: [T][N][D], [T][N][A], [T][N], [T][N]
+    const float *adv, *ret;                 // [T][N]
+    int N, n0, B;                           // the engine's envs; the minibatch's first env and env count
+    float *acts, *deltas, *pieces;          // scratch [S][na], [S][nd], [S][kPgPieces]
+    int na, nd;
+    int maxw;                               // the widest layer output of either network
+};
+
+// one term of the gradient: a layer's weights and bias, or log_std's row (n_in = 0)
+struct PgTerm {
+    const float *X;                         // the layer's input: the record's obs rows (obs != 0) or the scratch activations
+    size_t ldx;
+    int n_in, n_out, d_off, flat0, obs;
+};
+
+// the flat order against the device's stores (the terms in flat order)
+struct PgLayout {
+    int nterms, Q;
+    int flat0[adc::kPgMaxTerms], n_in[adc::kPgMaxTerms], n_out[adc::kPgMaxTerms];
+    float *W[adc::kPgMaxTerms], *b[adc::kPgMaxTerms];
+};
+
+constexpr int kPgBlock = 256;
+
+__host__ __device__ inline size_t pg_lds_floats(const adc::PgShape &sh, int maxw)
+{
+    size_t n = (size_t)sh.D + 2u * (size_t)maxw + 3u * (size_t)sh.A;
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < sh.layers[net]; ++l) n += (size_t)sh.n_out[net][l];
+    return n;
+}
+
+__device__ __forceinline__ float *pg_param_slot(const PgLayout &L, int p)
+{
+    int i = 0;
+    while (i + 1 < L.nterms && p >= L.flat0[i + 1]) ++i;
+    const int r = p - L.flat0[i], n_out = L.n_out[i], nw = L.n_in[i] * n_out;
+    return r >= nw ? L.b[i] + (r - nw) : L.W[i] + adc::mlp_weight_index(r / n_out, r % n_out, n_out);
+}
+
+// to_flat: flat[p] = the stores' parameter p; else the stores' parameter p = flat[p]
+__global__ __launch_bounds__(kPgBlock) void k_pg_params_copy(PgLayout L, float *__restrict__ flat, int to_flat)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= L.Q) return;
+    float *slot = pg_param_slot(L, p);
+    if (to_flat) flat[p] = *slot;
+    else *slot = flat[p];
+}
+
+// one lane per env, walking the record backwards
+__global__ void k_pg_gae(int N, int T, const float *__restrict__ reward, const uint8_t *__restrict__ term, const uint8_t *__restrict__ trunc,
+                         const float *__restrict__ value, const float *__restrict__ boot, float gamma, float gl, float reward_scale,
+                         float *__restrict__ adv_out, float *__restrict__ ret_out)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N) return;
+    float adv = 0.0f, next = boot[env];
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t i = (size_t)t * (size_t)N + (size_t)env;
+        const float v = value[i];
+        const float a = adc::pg_gae_day(reward[i], reward_scale, term[i] | trunc[i], v, next, gamma, gl, adv);
+        adv_out[i] = a;
+        ret_out[i] = a + v;
+        next = v;
+    }
+}
+
+// a chunk's partial of the law's chunked sum, one lane per (chunk, column): src[i * stride + col], i in the chunk.
+// mode 0: f64(x);  1: (f64(x) - mean)^2, the square rounded;  2: f64(x) * f64(x), exact
+__global__ void k_pg_chunk_sums(const float *__restrict__ src, long long n, int stride, int cols, int mode, double mean, double *__restrict__ part)
+{
+    const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long chunks = (n + adc::kPgChunk - 1) / adc::kPgChunk;
+    if (lane >= chunks * cols) return;
+    const long long chunk = lane / cols;
+    const int col = (int)(lane % cols);
+    const long long i0 = chunk * adc::kPgChunk, i1 = i0 + adc::kPgChunk < n ? i0 + adc::kPgChunk : n;
+    double acc = 0.0;
+    for (long long i = i0; i < i1; ++i) {
+        const float x = src[(size_t)i * (size_t)stride + (size_t)col];
+        acc = mode == 0 ? acc + (double)x : mode == 1 ? adc::pg_chain_sqdev(acc, x, mean) : adc::pg_chain_mac(acc, x, x);
+    }
+    part[lane] = acc;
+}
+// ... and the partials joined in chunk order, one lane per column
+__global__ void k_pg_join(const double *__restrict__ part, long long chunks, int cols, double *__restrict__ out)
+{
+    const int col = threadIdx.x;
+    if (col >= cols) return;
+    double total = 0.0;
+    for (long long c = 0; c < chunks; ++c) total = total + part[c * cols + col];
+    out[col] = total;
+}
+
+__global__ void k_pg_normalize(float *__restrict__ adv, long long n, double mean, double std)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) adv[i] = adc::pg_normalized(adv[i], mean, std);
+}
+
+// the transposed pass of one layer: dnew[j] = act'(y[j]) * sum8(n_out, h -> W[j][h] * dcur[h]) for the n inputs of the layer
+__device__ __forceinline__ void pg_layer_back(const float *__restrict__ W, int n, int n_out, const float *y, const float *dcur, float *dnew,
+                                              int activation, float *__restrict__ g_out)
+{
+    const int tid = threadIdx.x;
+    const int pairs = n * adc::kMlpChains;
+    for (int p0 = 0; p0 < pairs; p0 += kPgBlock) {
+        const int pi = p0 + tid;
+        const bool on = pi < pairs;
+        const int j = on ? pi >> 3 : 0, c = pi & 7;
+        float acc = 0.0f;
+        if (on)
+            for (int h = c; h < n_out; h += adc::kMlpChains) acc = adc::mlp_mac(acc, W[adc::mlp_weight_index(j, h, n_out)], dcur[h]);
+        float s = acc;
+        s = s + __shfl_xor(s, 1, 64);
+        s = s + __shfl_xor(s, 2, 64);
+        s = s + __shfl_xor(s, 4, 64);           // adc::mlp_join8
+        if (on && c == 0) {
+            const float d = adc::pg_hidden_delta(y[j], s, activation);
+            dnew[j] = d;
+            g_out[j] = d;
+        }
+    }
+    __syncthreads();
+}
+
+// forward, head, loss and backward of sample blockIdx.x = t * B + (env - n0)
+__global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
+{
+    extern __shared__ __align__(16) float pg_lds[];
+    __shared__ float s_g, s_dv;
+    const adc::PgShape &sh = p.sh;
+    const int tid = threadIdx.x, A = sh.A, D = sh.D;
+    const size_t s = blockIdx.x;
+    const size_t row = (s / (size_t)p.B) * (size_t)p.N + (size_t)p.n0 + s % (size_t)p.B;
+    float *x = pg_lds, *ybase = x + D;
+    float *y[2][adc::kMlpMaxLayers];
+    {
+        float *q = ybase;
+        for (int net = 0; net < 2; ++net)
+            for (int l = 0; l < sh.layers[net]; ++l) { y[net][l] = q; q += sh.n_out[net][l]; }
+        ybase = q;
+    }
+    float *d0 = ybase, *d1 = d0 + p.maxw, *zs = d1 + p.maxw, *sds = zs + A, *lss = sds + A;
+    for (int j = tid; j < D; j += kPgBlock) x[j] = p.obs[row * (size_t)D + j];
+    __syncthreads();
+    float *acts = p.acts + s * (size_t)p.na, *deltas = p.deltas + s * (size_t)p.nd;
+    // forward, every layer's activations kept (and the hidden ones written out for the weight gradient)
+    {
+        int ao = 0;
+        for (int net = 0; net < 2; ++net) {
+            const float *in = x;
+            for (int l = 0; l < sh.layers[net]; ++l) {
+                const bool last = l + 1 == sh.layers[net];
+                const int n_out = sh.n_out[net][l];
+                mlp_layer(p.net[net].W[l], p.net[net].b[l], adc::pg_n_in(sh, net, l), n_out, in, y[net][l], last ? -1 : sh.activation);
+                if (!last) {
+                    for (int h = tid; h < n_out; h += kPgBlock) acts[ao + h] = y[net][l][h];
+                    ao += n_out;
+                }
+                in = y[net][l];
+            }
+        }
+    }
+    // head: z, sd, ls of every component; the log-probability's terms in d0
+    const float *o = y[0][sh.layers[0] - 1];
+    for (int a = tid; a < A; a += kPgBlock) {
+        const float raw = sh.two_heads ? o[A + a] : p.log_std[a];
+        const float ls = adc::mlp_clamp_log_std(raw, sh.clamp, sh.ls_lo, sh.ls_hi);
+        const float sd = adc::mlp_exp(ls);
+        const float z = adc::pg_z(p.action[row * (size_t)A + a], o[a], sd);
+        zs[a] = z; sds[a] = sd; lss[a] = ls;
+        d0[a] = adc::mlp_logp_term(z, ls);
+    }
+    __syncthreads();
+    if (tid < kWave) {       // the first eight lanes: the chains of the two sum8 over the components
+        const int c = tid & 7;
+        float st = 0.0f, sl = 0.0f;
+        if (tid < adc::kMlpChains)
+            for (int a = c; a < A; a += adc::kMlpChains) { st = st + d0[a]; sl = sl + lss[a]; }
+        st = st + __shfl_xor(st, 1, 64); sl = sl + __shfl_xor(sl, 1, 64);
+        st = st + __shfl_xor(st, 2, 64); sl = sl + __shfl_xor(sl, 2, 64);
+        st = st + __shfl_xor(st, 4, 64); sl = sl + __shfl_xor(sl, 4, 64);
+        if (tid == 0) {
+            const float logp = adc::mlp_logp_finish(st, A), entropy = adc::pg_entropy_finish(sl, A);
+            const float logp_old = p.logp[row], ret = p.ret[row];
+            const float ratio = adc::mlp_exp(logp - logp_old);
+            float pol_loss, val_loss;
+            int clipped;
+            const float g = adc::pg_surrogate(ratio, p.adv[row], p.loss.eps_clip, pol_loss, clipped);
+            const float V = sh.layers[1] ? y[1][sh.layers[1] - 1][0] : 0.0f;
+            const float dv = adc::pg_dvalue(V, ret, p.loss.vf_coef, val_loss);
+            s_g = g; s_dv = dv;
+            float *pc = p.pieces + s * (size_t)adc::kPgPieces;
+            pc[adc::kPgPolLoss] = pol_loss; pc[adc::kPgValLoss] = val_loss; pc[adc::kPgEntropy] = entropy; pc[adc::kPgKl] = logp_old - logp;
+            pc[adc::kPgClipped] = clipped ? 1.0f : 0.0f; pc[adc::kPgRet] = ret; pc[adc::kPgErr] = ret - p.value[row]; pc[7] = 0.0f;
+        }
+    }
+    __syncthreads();
+    // where a network's deltas go in the sample's scratch row
+    int doff[2][adc::kMlpMaxLayers], dfree = 0;
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < sh.layers[net]; ++l) { doff[net][l] = dfree; dfree += sh.n_out[net][l]; }
+    // the policy network's output deltas (means, then log-stds; the free vector's go to their own row), then its hidden layers'
+    {
+        const float g = s_g;
+        const int L = sh.layers[0];
+        float *gout = deltas + doff[0][L - 1];
+        for (int a = tid; a < A; a += kPgBlock) {
+            const float raw = sh.two_heads ? o[A + a] : p.log_std[a];
+            const float dm = adc::pg_dmean(g, zs[a], sds[a]);
+            const float dl = adc::pg_dls(g, zs[a], p.loss.ent_coef, adc::pg_clamp_moved(raw, sh.clamp, sh.ls_lo, sh.ls_hi));
+            d0[a] = dm; gout[a] = dm;
+            if (sh.two_heads) { d0[A + a] = dl; gout[A + a] = dl; }
+            else deltas[dfree + a] = dl;
+        }
+        __syncthreads();
+        float *dcur = d0, *dnew = d1;
+        for (int l = L - 2; l >= 0; --l) {
+            pg_layer_back(p.net[0].W[l + 1], sh.n_out[0][l], sh.n_out[0][l + 1], y[0][l], dcur, dnew, sh.activation, deltas + doff[0][l]);
+            float *t = dcur; dcur = dnew; dnew = t;
+        }
+    }
+    if (sh.layers[1] > 0) {
+        const int L = sh.layers[1];
+        if (tid == 0) { d0[0] = s_dv; deltas[doff[1][L - 1]] = s_dv; }
+        __syncthreads();
+        float *dcur = d0, *dnew = d1;
+        for (int l = L - 2; l >= 0; --l) {
+            pg_layer_back(p.net[1].W[l + 1], sh.n_out[1][l], sh.n_out[1][l + 1], y[1][l], dcur, dnew, sh.activation, deltas + doff[1][l]);
+            float *t = dcur; dcur = dnew; dnew = t;
+        }
+    }
+}
+
+// one term's partials: gpart[chunk][flat0 + j * n_out + h] = the chunk's chain of x_s[j] * delta_s[h]; a 16 x 16 tile (blockIdx.x)
+// and a chunk (blockIdx.y) per workgroup
+constexpr int kPgTile = 16, kPgSlab = 64;
+__global__ __launch_bounds__(kPgBlock) void k_pg_wgrad(PgTerm t, long long S, int B, int N, int n0, const float *__restrict__ deltas, int nd,
+                                                       double *__restrict__ gpart, int Q)
+{
+    __shared__ float xs[kPgSlab][kPgTile + 1], ds[kPgSlab][kPgTile + 1];
+    const int tid = threadIdx.x, jj = tid >> 4, hh = tid & 15;
+    const int tiles_h = (t.n_out + kPgTile - 1) / kPgTile;
+    const int j0 = ((int)blockIdx.x / tiles_h) * kPgTile, h0 = ((int)blockIdx.x % tiles_h) * kPgTile;
+    const int jx = j0 + hh, hx = h0 + hh;       // (the column this lane stages)
+    double part = 0.0;
+    const long long c0 = (long long)blockIdx.y * adc::kPgChunk, c1 = c0 + adc::kPgChunk < S ? c0 + adc::kPgChunk : S;
+    for (long long s0 = c0; s0 < c1; s0 += kPgSlab) {
+        const int n = c1 - s0 < kPgSlab ? (int)(c1 - s0) : kPgSlab;
+#pragma unroll
+        for (int pass = 0; pass < kPgSlab / kPgTile; ++pass) {
+            const int si = pass * kPgTile + jj;
+            if (si < n) {
+                const long long s = s0 + si;
+                float xv = 1.0f;                // (the bias row j = n_in; rows beyond it are never stored)
+                if (jx < t.n_in) {
+                    const uint32_t su = (uint32_t)s, day = su / (uint32_t)B;          // (S < 2^31: 32-bit division)
+                    const size_t row = t.obs ? (size_t)day * (size_t)N + (size_t)n0 + (size_t)(su - day * (uint32_t)B) : (size_t)s;
+                    xv = t.X[row * t.ldx + (size_t)jx];
+                }
+                xs[si][hh] = xv;
+                ds[si][hh] = hx < t.n_out ? deltas[(size_t)s * (size_t)nd + (size_t)(t.d_off + hx)] : 0.0f;
+            }
+        }
+        __syncthreads();
+        for (int i = 0; i < n; ++i) part = adc::pg_chain_mac(part, xs[i][jj], ds[i][hh]);
+        __syncthreads();
+    }
+    const int j = j0 + jj, h = h0 + hh;
+    if (j <= t.n_in && h < t.n_out) gpart[(size_t)blockIdx.y * (size_t)Q + (size_t)t.flat0 + (size_t)j * (size_t)t.n_out + (size_t)h] = part;
+}
+
+// a parameter's partials joined in chunk order: grad[p] = float32(total / S)
+__global__ __launch_bounds__(kPgBlock) void k_pg_grad_join(const double *__restrict__ gpart, int chunks, int Q, long long S, float *__restrict__ grad)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= Q) return;
+    double total = 0.0;
+    for (int c = 0; c < chunks; ++c) total = total + gpart[(size_t)c * (size_t)Q + (size_t)p];
+    grad[p] = adc::pg_grad_finish(total, S);
+}
+
+// the (clipped) gradient's step on theta, and the device's chain-major layers and log_std rebuilt from the new theta
+__global__ __launch_bounds__(kPgBlock) void k_pg_update(PgLayout L, float *__restrict__ theta, float *__restrict__ mom_m, float *__restrict__ mom_v,
+                                                        const float *__restrict__ grad, int clip, float scale, adc::EsStep step)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= L.Q) return;
+    float g = grad[p];
+    if (clip) g = g * scale;
+    float m = mom_m[p], v = mom_v[p];
+    const float t1 = adc::pg_apply(step, theta[p], g, m, v);
+    theta[p] = t1;
+    mom_m[p] = m;
+    mom_v[p] = v;
+    *pg_param_slot(L, p) = t1;
+}

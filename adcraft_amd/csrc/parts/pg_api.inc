@@ -1,0 +1,311 @@
+// pg_api.inc - the extern "C" entry points of policy-gradient training (include/adcraft_engine.h; the kernels are
+// parts/kernel_pg.inc, the law csrc/adc_pg.h).  Everything here runs on the engine's own stream behind ENGINE_GUARD, that is
+// after the env groups have joined: results do not depend on how the days were grouped.
+// (part of the single translation unit adc_engine.hip)
+namespace {
+int pg_ready(const adc_engine *e)
+{
+    if (!e->have_pg) return fail(ADC_ESTATE, "adc_engine_pg_init has not been called (or the policy / the record was re-initialised since)");
+    return ADC_OK;
+}
+// what a policy-gradient call needs of the engine's state, checked at init and again at every call
+int pg_state_check(const adc_engine *e)
+{
+    if (int rc = mlp_ready(e)) return rc;
+    if (e->pop_M != 0) return fail(ADC_ESTATE, "policy-gradient training with a population active is not supported (adc_engine_mlp_population(0) first)");
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "policy-gradient training needs a rollout record (adc_engine_rollout_enable)");
+    if (!e->ro_obs) return fail(ADC_ESTATE, "policy-gradient training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
+    return ADC_OK;
+}
+int pg_record_check(const adc_engine *e)
+{
+    if (e->ro_t == 0) return fail(ADC_ESTATE, "no day has been recorded (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)");
+    if (e->ro_deterministic)
+        return fail(ADC_ESTATE, "the record holds days collected with the deterministic policy: their log-probabilities mean nothing "
+                                "(adc_engine_mlp_set_deterministic(0), adc_engine_rollout_reset, collect again)");
+    return ADC_OK;
+}
+inline long long pg_chunks(long long n) { return (n + adc::kPgChunk - 1) / adc::kPgChunk; }
+
+// the law's chunked sum of `cols` columns of src into out[0 .. cols)
+int pg_csum_launch(adc_engine *e, const float *src, long long n, int stride, int cols, int mode, double mean, double *out)
+{
+    const long long chunks = pg_chunks(n), lanes = chunks * cols;
+    hipLaunchKernelGGL(k_pg_chunk_sums, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, e->stream, src, n, stride, cols, mode, mean, e->pg_part);
+    hipLaunchKernelGGL(k_pg_join, dim3(1), dim3(64), 0, e->stream, e->pg_part, chunks, cols, out);
+    HIP_TRY(hipGetLastError());
+    return ADC_OK;
+}
+
+adc::EsStep pg_step_of(const adc_pg_config &c, int64_t steps_taken)
+{
+    adc::EsStep step{};
+    step.optimiser = c.optimiser == ADC_PG_SGD ? adc::kEsSgd : adc::kEsAdam;
+    step.lr = c.lr; step.beta1 = c.beta1; step.beta2 = c.beta2; step.eps = c.eps; step.l2 = 0.0f;
+    step.c1 = adc::es_bias_correction(step.beta1, (uint32_t)(steps_taken + 1));
+    step.c2 = adc::es_bias_correction(step.beta2, (uint32_t)(steps_taken + 1));
+    return step;
+}
+
+int pg_advantages_run(adc_engine *e)
+{
+    const int N = e->v.N, T = e->ro_t;
+    const long long n = (long long)T * N;
+    if (e->mp.val.layers > 0)
+        mlp_launch_kernel(e->v, e->mp, e->stream, 1, nullptr, 0.0f, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, e->mlp_boot);
+    else HIP_TRY(hipMemsetAsync(e->mlp_boot, 0, (size_t)N * 4, e->stream));
+    const adc_pg_config &c = e->pg_cfg;
+    hipLaunchKernelGGL(k_pg_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, N, T, e->ro_reward, e->ro_term, e->ro_trunc, e->ro_value,
+                       e->mlp_boot, c.gamma, c.gamma * c.lambda, c.reward_scale, e->pg_adv, e->pg_ret);
+    HIP_TRY(hipGetLastError());
+    if (c.normalize_advantages) {
+        double sum = 0.0, sq = 0.0;
+        if (int rc = pg_csum_launch(e, e->pg_adv, n, 1, 1, 0, 0.0, e->pg_sums)) return rc;
+        HIP_TRY(hipMemcpyAsync(&sum, e->pg_sums, 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const double mean = sum / (double)n;
+        if (int rc = pg_csum_launch(e, e->pg_adv, n, 1, 1, 1, mean, e->pg_sums)) return rc;
+        HIP_TRY(hipMemcpyAsync(&sq, e->pg_sums, 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const double sd = std::sqrt(sq / (double)n);
+        hipLaunchKernelGGL(k_pg_normalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->pg_adv, n, mean, sd);
+        HIP_TRY(hipGetLastError());
+    }
+    e->pg_adv_ready = true;
+    return ADC_OK;
+}
+
+// one gradient and one step over the recorded days of the envs [n0, n0 + B)
+int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
+{
+    const adc::PgShape &sh = e->pg_shape;
+    const int N = e->v.N, T = e->ro_t, na = adc::pg_acts_floats(sh), nd = adc::pg_deltas_floats(sh);
+    const long long S = (long long)T * B;
+    PgView p{};
+    p.sh = sh;
+    p.loss = adc::PgLoss{e->pg_cfg.eps_clip, e->pg_cfg.vf_coef, e->pg_cfg.ent_coef};
+    p.net[0] = e->mp.pol; p.net[1] = e->mp.val;
+    p.log_std = e->mp.log_std;
+    p.obs = e->ro_obs; p.action = e->ro_action; p.logp = e->ro_logp; p.value = e->ro_value;
+    p.adv = e->pg_adv; p.ret = e->pg_ret;
+    p.N = N; p.n0 = n0; p.B = B;
+    p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
+    p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
+    hipLaunchKernelGGL(k_pg_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p);
+    // the gradient's terms in the flat order
+    {
+        int flat = 0, ao = 0, dof = 0;
+        auto launch = [&](const float *X, size_t ldx, int n_in, int n_out, int obs) {
+            PgTerm t{X, ldx, n_in, n_out, dof, flat, obs};
+            const unsigned tiles = (unsigned)(((n_in + 1 + kPgTile - 1) / kPgTile) * ((n_out + kPgTile - 1) / kPgTile));
+            hipLaunchKernelGGL(k_pg_wgrad, dim3(tiles, (unsigned)pg_chunks(S)), dim3(kPgBlock), 0, e->stream, t, S, B, N, n0, e->pg_deltas, nd,
+                               e->pg_gpart, e->pg_lay.Q);
+            flat += (n_in + 1) * n_out;
+        };
+        for (int net = 0; net < 2; ++net)
+            for (int l = 0; l < sh.layers[net]; ++l) {
+                const int n_in = adc::pg_n_in(sh, net, l), n_out = sh.n_out[net][l];
+                if (l == 0) launch(e->ro_obs, (size_t)sh.D, n_in, n_out, 1);
+                else { launch(e->pg_acts + ao, (size_t)na, n_in, n_out, 0); ao += n_in; }
+                dof += n_out;
+            }
+        if (!sh.two_heads) launch(nullptr, 0, 0, sh.A, 0);
+    }
+    const int Q = e->pg_lay.Q;
+    hipLaunchKernelGGL(k_pg_grad_join, dim3((unsigned)((Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, e->pg_gpart, (int)pg_chunks(S), Q, S,
+                       e->pg_grad);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    if ((rc = pg_csum_launch(e, e->pg_pieces, S, adc::kPgPieces, 7, 0, 0.0, e->pg_sums)) ||
+        (rc = pg_csum_launch(e, e->pg_pieces + adc::kPgRet, S, adc::kPgPieces, 2, 2, 0.0, e->pg_sums + 7)) ||
+        (rc = pg_csum_launch(e, e->pg_grad, Q, 1, 1, 2, 0.0, e->pg_sums + 9)))
+        return rc;
+    double sums[adc::kPgSums];
+    HIP_TRY(hipMemcpyAsync(sums, e->pg_sums, sizeof(sums), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const adc::PgStatsOut st = adc::pg_stats_finish(sums, S);
+    const bool clip = e->pg_cfg.max_grad_norm > 0.0f;
+    const float scale = clip ? adc::pg_clip_scale(e->pg_cfg.max_grad_norm, st.grad_norm) : 1.0f;
+    hipLaunchKernelGGL(k_pg_update, dim3((unsigned)((Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, e->pg_lay, e->pg_theta, e->pg_m,
+                       e->pg_v, e->pg_grad, clip ? 1 : 0, scale, pg_step_of(e->pg_cfg, e->pg_steps));
+    HIP_TRY(hipGetLastError());
+    e->pg_steps += 1;
+    if (out) *out = st;
+    return ADC_OK;
+}
+
+void pg_stats_fill(adc_pg_stats *stats, const adc::PgStatsOut &o, int64_t steps, int64_t samples)
+{
+    stats->steps = steps; stats->samples = samples;
+    stats->policy_loss = o.policy_loss; stats->value_loss = o.value_loss; stats->entropy = o.entropy; stats->approx_kl = o.approx_kl;
+    stats->clip_fraction = o.clip_fraction; stats->grad_norm = o.grad_norm; stats->explained_variance = o.explained_variance;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_pg_init(adc_engine *e, const adc_pg_config *cfg)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const char *why = nullptr;
+    if (adc_pg_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if (int rc = pg_state_check(e)) return rc;
+    const int N = e->v.N, mb = cfg->minibatch_envs == 0 ? N : cfg->minibatch_envs;
+    if (mb > N || N % mb != 0) return fail(ADC_EINVAL, "minibatch_envs must divide num_envs");
+    if (pg_chunks((long long)e->ro_T * mb) > 65535) return fail(ADC_EINVAL, "horizon x minibatch_envs: at most 65535 x 1024 samples in a minibatch");
+    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K);
+    int maxw = 1;
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < sh.layers[net]; ++l) maxw = std::max(maxw, sh.n_out[net][l]);
+    if (pg_lds_floats(sh, maxw) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for policy-gradient training (LDS)");
+    ENGINE_GUARD(e);
+    // the flat order against the device's stores
+    PgLayout lay{};
+    {
+        int flat = 0, i = 0;
+        for (int net = 0; net < 2; ++net) {
+            const MlpNet &n = net == 0 ? e->mp.pol : e->mp.val;
+            for (int l = 0; l < sh.layers[net]; ++l, ++i) {
+                lay.flat0[i] = flat; lay.n_in[i] = n.n_in[l]; lay.n_out[i] = n.n_out[l];
+                lay.W[i] = const_cast<float *>(n.W[l]); lay.b[i] = const_cast<float *>(n.b[l]);
+                flat += (n.n_in[l] + 1) * n.n_out[l];
+            }
+        }
+        if (!sh.two_heads) {
+            lay.flat0[i] = flat; lay.n_in[i] = 0; lay.n_out[i] = sh.A; lay.W[i] = nullptr; lay.b[i] = const_cast<float *>(e->mp.log_std);
+            flat += sh.A; ++i;
+        }
+        lay.nterms = i; lay.Q = flat;
+    }
+    const size_t Q = (size_t)lay.Q, tn = (size_t)e->ro_T * (size_t)N, smax = (size_t)e->ro_T * (size_t)mb;
+    const size_t parts = (size_t)pg_chunks((long long)std::max(tn, Q)) * 8u + 8u;
+    // (the new state is allocated before the old one goes: a failure leaves the engine as it was)
+    std::vector<void *> fresh;
+    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *adv = nullptr, *ret = nullptr, *acts = nullptr, *deltas = nullptr, *pieces = nullptr;
+    double *part = nullptr, *sums = nullptr, *gpart = nullptr;
+    int rc;
+    if ((rc = mlp_alloc(e, fresh, &theta, Q)) || (rc = mlp_alloc(e, fresh, &m, Q)) || (rc = mlp_alloc(e, fresh, &v, Q)) ||
+        (rc = mlp_alloc(e, fresh, &grad, Q)) || (rc = mlp_alloc(e, fresh, &adv, tn)) || (rc = mlp_alloc(e, fresh, &ret, tn)) ||
+        (rc = mlp_alloc(e, fresh, &acts, smax * (size_t)adc::pg_acts_floats(sh))) || (rc = mlp_alloc(e, fresh, &deltas, smax * (size_t)adc::pg_deltas_floats(sh))) ||
+        (rc = mlp_alloc(e, fresh, &pieces, smax * (size_t)adc::kPgPieces)) || (rc = mlp_alloc(e, fresh, &part, parts)) ||
+        (rc = mlp_alloc(e, fresh, &gpart, (size_t)pg_chunks((long long)smax) * Q)) ||
+        (rc = mlp_alloc(e, fresh, &sums, (size_t)16))) {
+        // (rc and its message are mlp_alloc's: ADC_ENOMEM for a refused allocation, ADC_EHIP for a failed memset; no test provokes either)
+        mlp_free(e, fresh);
+        return rc;
+    }
+    pg_drop(e);
+    e->pg_allocs.swap(fresh);
+    e->pg_theta = theta; e->pg_m = m; e->pg_v = v; e->pg_grad = grad; e->pg_adv = adv; e->pg_ret = ret;
+    e->pg_acts = acts; e->pg_deltas = deltas; e->pg_pieces = pieces; e->pg_part = part; e->pg_sums = sums; e->pg_gpart = gpart;
+    e->pg_cfg = *cfg; e->pg_mb = mb; e->pg_shape = sh; e->pg_lay = lay; e->pg_maxw = maxw;
+    // theta starts as the device's weights
+    hipLaunchKernelGGL(k_pg_params_copy, dim3((unsigned)((lay.Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, lay, e->pg_theta, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->have_pg = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_param_count(adc_engine *e, int64_t *count)
+{
+    if (!e || !count) return fail(ADC_EINVAL, "engine handle or count is NULL");
+    if (int rc = pg_ready(e)) return rc;
+    *count = e->pg_lay.Q;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_advantages(adc_engine *e)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pg_ready(e)) || (rc = pg_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    ENGINE_GUARD(e);
+    return pg_advantages_run(e);
+}
+
+ADC_EXPORT int adc_engine_pg_advantages_fetch(adc_engine *e, float *adv_tn, float *ret_tn)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = pg_ready(e)) return rc;
+    if (!e->pg_adv_ready) return fail(ADC_ESTATE, "adc_engine_pg_advantages has not been called since the last recorded day");
+    ENGINE_GUARD(e);
+    const size_t bytes = (size_t)e->ro_t * (size_t)e->v.N * 4;
+    if (adv_tn) HIP_TRY(hipMemcpyAsync(adv_tn, e->pg_adv, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (ret_tn) HIP_TRY(hipMemcpyAsync(ret_tn, e->pg_ret, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_minibatch(adc_engine *e, int32_t env_begin, int32_t env_count, adc_pg_stats *stats)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pg_ready(e)) || (rc = pg_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if (!e->pg_adv_ready) return fail(ADC_ESTATE, "adc_engine_pg_advantages has not been called since the last recorded day");
+    if (env_begin < 0 || env_count < 1 || (long long)env_begin + env_count > e->v.N) return fail(ADC_EINVAL, "the env range is not inside [0, num_envs)");
+    if (env_count > e->pg_mb) return fail(ADC_EINVAL, "env_count exceeds the configuration's minibatch_envs (the scratch was sized for it)");
+    ENGINE_GUARD(e);
+    adc::PgStatsOut o;
+    if ((rc = pg_minibatch_run(e, env_begin, env_count, &o))) return rc;
+    if (stats) pg_stats_fill(stats, o, e->pg_steps, (int64_t)e->ro_t * env_count);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats *stats)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pg_ready(e)) || (rc = pg_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
+    ENGINE_GUARD(e);
+    if ((rc = pg_advantages_run(e))) return rc;
+    const int N = e->v.N, mb = e->pg_mb, count = N / mb;
+    adc::PgStatsOut mean{};
+    for (int ep = 0; ep < epochs; ++ep) {
+        adc::PgStatsOut acc{};
+        for (int i = 0; i < count; ++i) {
+            adc::PgStatsOut o;
+            if ((rc = pg_minibatch_run(e, i * mb, mb, &o))) return rc;
+            acc.policy_loss = acc.policy_loss + o.policy_loss; acc.value_loss = acc.value_loss + o.value_loss; acc.entropy = acc.entropy + o.entropy;
+            acc.approx_kl = acc.approx_kl + o.approx_kl; acc.clip_fraction = acc.clip_fraction + o.clip_fraction;
+            acc.grad_norm = acc.grad_norm + o.grad_norm; acc.explained_variance = acc.explained_variance + o.explained_variance;
+        }
+        const double c = (double)count;
+        mean = adc::PgStatsOut{acc.policy_loss / c, acc.value_loss / c, acc.entropy / c, acc.approx_kl / c, acc.clip_fraction / c, acc.grad_norm / c,
+                               acc.explained_variance / c};
+    }
+    if (stats) pg_stats_fill(stats, mean, e->pg_steps, (int64_t)e->ro_t * mb);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_state_get(adc_engine *e, float *theta_q, float *m_q, float *v_q, int64_t *steps)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = pg_ready(e)) return rc;
+    ENGINE_GUARD(e);
+    const size_t bytes = (size_t)e->pg_lay.Q * 4;
+    if (theta_q) HIP_TRY(hipMemcpyAsync(theta_q, e->pg_theta, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (m_q) HIP_TRY(hipMemcpyAsync(m_q, e->pg_m, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (v_q) HIP_TRY(hipMemcpyAsync(v_q, e->pg_v, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (steps) *steps = e->pg_steps;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_state_set(adc_engine *e, const float *theta_q, const float *m_q, const float *v_q, int64_t steps)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = pg_ready(e)) return rc;
+    if (!theta_q || !m_q || !v_q) return fail(ADC_EINVAL, "theta, m or v is NULL");
+    if (steps < 0 || steps >= 0x7FFFFFFFll) return fail(ADC_EINVAL, "steps: 0 to 2^31 - 2");
+    ENGINE_GUARD(e);
+    const size_t bytes = (size_t)e->pg_lay.Q * 4;
+    HIP_TRY(hipMemcpyAsync(e->pg_theta, theta_q, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->pg_m, m_q, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->pg_v, v_q, bytes, hipMemcpyHostToDevice, e->stream));
+    // (the device's layers and log_std follow theta, so that the next act and the next recorded day see it)
+    hipLaunchKernelGGL(k_pg_params_copy, dim3((unsigned)((e->pg_lay.Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, e->pg_lay, e->pg_theta, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pg_steps = steps;
+    return ADC_OK;
+}

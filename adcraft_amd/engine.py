@@ -606,6 +606,12 @@ class StepEngine:
         check(self._lib.adc_engine_mlp_last(self._h, *(st[k].ctypes.data for k in ("mean", "log_std", "action", "logp", "value"))))
         return st
 
+    def mlp_agent_state(self):
+        """(keys uint64 [N], ticks uint32 [N]) of the agents' own streams; every act moves a tick on by one"""
+        k, t = np.zeros(self.num_envs, np.uint64), np.zeros(self.num_envs, np.uint32)
+        check(self._lib.adc_engine_mlp_agent_state(self._h, k.ctypes.data, t.ctypes.data))
+        return k, t
+
     def mlp_bootstrap_value(self):
         v = np.zeros(self.num_envs, np.float32)
         check(self._lib.adc_engine_mlp_bootstrap_value(self._h, v.ctypes.data))
@@ -701,6 +707,77 @@ class StepEngine:
         if any(a.shape != (P,) for a in arr):
             raise ValueError(f"es_state: theta, m and v have {P} entries")
         check(self._lib.adc_engine_es_state_set(self._h, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["generation"])))
+
+    # ---- policy-gradient training over the rollout record (parts/kernel_pg.inc; baselines/pg_trainer.py drives it) ----------
+    PG_OPTIMISERS = {"adam": _ffi.PG_ADAM, "sgd": _ffi.PG_SGD}
+
+    @classmethod
+    def pg_config(cls, gamma=0.99, lam=0.95, eps_clip=0.2, vf_coef=0.5, ent_coef=0.0, reward_scale=1.0, normalize_advantages=True,
+                  max_grad_norm=0.5, optimiser="adam", lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, minibatch_envs=0):
+        """an adc_pg_config (csrc/adc_pg.h); eps_clip <= 0: no clip; max_grad_norm 0: off; minibatch_envs 0: all envs"""
+        c = _ffi.PGConfig()
+        c.struct_size = C.sizeof(_ffi.PGConfig)
+        c.gamma, c.lambda_, c.eps_clip, c.vf_coef, c.ent_coef, c.reward_scale = gamma, lam, eps_clip, vf_coef, ent_coef, reward_scale
+        c.normalize_advantages, c.max_grad_norm = 1 if normalize_advantages else 0, max_grad_norm
+        if optimiser not in cls.PG_OPTIMISERS:
+            raise ValueError(f"unknown optimiser {optimiser!r}: 'adam' or 'sgd'")
+        c.optimiser, c.lr, c.beta1, c.beta2, c.eps, c.minibatch_envs = cls.PG_OPTIMISERS[optimiser], lr, beta1, beta2, eps, int(minibatch_envs)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_pg_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad policy-gradient configuration").decode())
+        return c
+
+    def pg_init(self, **options):
+        """policy-gradient training of the policy given to mlp_init over the rollout record (rollout_enable(T, obs=True) first);
+        options as pg_config's.  theta starts as the device's weights."""
+        cfg = self.pg_config(**options)
+        check(self._lib.adc_engine_pg_init(self._h, C.byref(cfg)))
+
+    def pg_param_count(self):
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_pg_param_count(self._h, C.byref(n)))
+        return n.value
+
+    def pg_advantages(self, fetch=False):
+        """GAE over the recorded days; fetch=True returns (adv, ret) [T, N] float32"""
+        check(self._lib.adc_engine_pg_advantages(self._h))
+        if not fetch:
+            return None
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        adv, ret = np.zeros((t.value, self.num_envs), np.float32), np.zeros((t.value, self.num_envs), np.float32)
+        check(self._lib.adc_engine_pg_advantages_fetch(self._h, adv.ctypes.data, ret.ctypes.data))
+        return adv, ret
+
+    @staticmethod
+    def _pg_stats(st):
+        return {k: getattr(st, k) for k, _ in _ffi.PGStats._fields_}
+
+    def pg_minibatch(self, env_begin, env_count):
+        """one gradient and one optimiser step over every recorded day of the envs [env_begin, env_begin + env_count)"""
+        st = _ffi.PGStats()
+        check(self._lib.adc_engine_pg_minibatch(self._h, int(env_begin), int(env_count), C.byref(st)))
+        return self._pg_stats(st)
+
+    def pg_update(self, epochs=1):
+        """advantages, then `epochs` x the minibatches in ascending env order; the last epoch's statistics"""
+        st = _ffi.PGStats()
+        check(self._lib.adc_engine_pg_update(self._h, int(epochs), C.byref(st)))
+        return self._pg_stats(st)
+
+    def pg_state(self, state=None):
+        """get (no argument): dict of theta, m, v [Q] float32 and steps; set: such a dict - the run continues bit for bit"""
+        Q = self.pg_param_count()
+        if state is None:
+            st = dict(theta=np.zeros(Q, np.float32), m=np.zeros(Q, np.float32), v=np.zeros(Q, np.float32))
+            n = C.c_int64(0)
+            check(self._lib.adc_engine_pg_state_get(self._h, st["theta"].ctypes.data, st["m"].ctypes.data, st["v"].ctypes.data, C.byref(n)))
+            st["steps"] = n.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in ("theta", "m", "v")]
+        if any(a.shape != (Q,) for a in arr):
+            raise ValueError(f"pg_state: theta, m and v have {Q} entries")
+        check(self._lib.adc_engine_pg_state_set(self._h, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
 
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))

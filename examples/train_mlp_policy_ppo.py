@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Train a learned bidder on the device with PPO (or A2C), next to the zero-margin baseline.
+
+The `[32, 32]` tanh policy of examples/evaluate_mlp_policy.py plus a value network of the same shape (built in numpy here:
+nothing but numpy and the engine is loaded) is trained on the sparse keyword law: every iteration records one episode of
+`run_days("mlp")` under the stochastic policy and updates both networks from it on the device - advantages, backward pass,
+PPO-clip loss, Adam - so no observation, action or gradient crosses the bus.  Every few iterations the policy is evaluated
+deterministically on held-out keyword sets and its episode return and NCP are printed beside the zero-margin agent's.
+
+Usage: python examples/train_mlp_policy_ppo.py [--iterations 100] [--algo ppo|a2c] [--num-envs 4096] [--num-keywords 100]
+"""
+import argparse
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, ".")
+from adcraft_amd import synthetic  # noqa: E402
+from adcraft_amd.baselines import pg_trainer  # noqa: E402
+from adcraft_amd.baselines.es_trainer import default_policy  # noqa: E402
+from adcraft_amd.closed_loop import run_baseline_episode  # noqa: E402
+from adcraft_amd.engine import StepEngine  # noqa: E402
+
+
+def with_value_network(policy, hidden, seed=1):
+    """the policy plus a value network of the same hidden sizes, drawn like its own layers"""
+    rng = np.random.default_rng(seed)
+    layers, n_in = [], policy.input_size
+    for n_out in list(hidden) + [1]:
+        b = 1.0 / np.sqrt(n_in)
+        layers.append((rng.uniform(-b, b, (n_in, n_out)).astype(np.float32), np.zeros(n_out, np.float32)))
+        n_in = n_out
+    policy.value_layers = layers
+    return policy
+
+
+def evaluate(name, policy, planes, days, budget):
+    """(mean episode return, mean NCP) of an agent on the held-out keyword sets"""
+    N, K = planes.shape[1:]
+    e = StepEngine(N, K, max_days=days, seed=70)
+    e.set_all_params(planes)
+    e.reset()
+    r = run_baseline_episode(e, name, steps=days, budget=budget, default_rpc=1.0, mlp=policy, deterministic=True, per_keyword_sums=False)
+    ret = np.asarray(e.fetch()["cumulative_profit"], np.float64).mean()
+    e.close()
+    return ret, float(np.mean(r["NCP"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iterations", type=int, default=100)
+    ap.add_argument("--algo", choices=["ppo", "a2c"], default="ppo")
+    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--num-keywords", type=int, default=100)
+    ap.add_argument("--days", type=int, default=60)
+    ap.add_argument("--mean-volume", type=float, default=8.0)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--reward-scale", type=float, default=0.1)
+    ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
+    ap.add_argument("--eval-envs", type=int, default=1024)
+    args = ap.parse_args()
+    N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
+    held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
+    zm = evaluate("zero_margin", None, held_out, days, budget)
+    print(f"{args.algo}: {N} envs x {K} keywords, {days} days per iteration; held-out: {args.eval_envs} envs")
+    print(f"{'iteration':>10} {'kl':>9} {'ev':>7} {'return':>10} {'NCP':>8}   zero-margin: return {zm[0]:.2f} NCP {zm[1]:.3f}")
+    eng = StepEngine(N, K, max_days=days, seed=7)
+    eng.set_all_params(synthetic.implicit_keyword_planes(N, K, seed=1, mean_volume=args.mean_volume))
+    eng.reset()
+    config = getattr(pg_trainer, args.algo)(lr=args.lr, reward_scale=args.reward_scale)
+    trainer = pg_trainer.PGTrainer(eng, with_value_network(default_policy(K, days=days), (32, 32)), days, **config)
+    rng = np.random.default_rng(5)
+    ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
+    print(f"{0:>10} {'':>9} {'':>7} {ret:10.2f} {ncp:8.3f}")
+    t0 = time.perf_counter()
+    for it in range(1, args.iterations + 1):
+        stats = trainer.iteration(days, budget, reset=True, reset_seeds=rng.integers(0, 2 ** 63, N).astype(np.uint64))
+        if it % args.every == 0 or it == args.iterations:
+            ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
+            print(f"{it:>10} {stats['approx_kl']:9.5f} {stats['explained_variance']:7.3f} {ret:10.2f} {ncp:8.3f}", flush=True)
+    eng.close()
+    print(f"{args.iterations} iterations in {time.perf_counter() - t0:.2f} s (evaluations included)")
+
+
+if __name__ == "__main__":
+    main()

@@ -516,6 +516,8 @@ int adc_engine_mlp_step(adc_engine *e, float budget_override);
 int adc_engine_mlp_last(adc_engine *e, float *mean_na, float *log_std_na, float *action_na, float *logp_n, float *value_n);
 /* the value network on the observation the last step left (zeros for an env that has just been reset): the bootstrap value */
 int adc_engine_mlp_bootstrap_value(adc_engine *e, float *value_n);
+/* the agents' own streams: key and tick [N] of every env's agent (either may be NULL); every act moves a tick on by one */
+int adc_engine_mlp_agent_state(adc_engine *e, uint64_t *keys_n, uint32_t *ticks_n);
 /* the rollout record: per recorded day t < horizon and env the unclipped action [A], log-probability, value, reward (float32
  * of the step's float64 reward), terminated, truncated and - with ADC_ROLLOUT_OBS - the network's input [D]; arrays laid out
  * [T][N][...], on the device (ADC_BUF_ROLLOUT_*) and fetched to the host.  adc_engine_mlp_step and adc_engine_run_days
@@ -578,6 +580,54 @@ int adc_engine_es_update(adc_engine *e, const double *fitness_m, adc_es_stats *s
 /* theta, the Adam moments [P] and the generation: a run resumed from them continues bit for bit (get: any pointer may be NULL) */
 int adc_engine_es_state_get(adc_engine *e, float *theta_p, float *m_p, float *v_p, int64_t *generation);
 int adc_engine_es_state_set(adc_engine *e, const float *theta_p, const float *m_p, const float *v_p, int64_t generation);
+
+/* ---- policy-gradient training on the device: GAE, the networks' backward pass, PPO-clip / A2C (the law is csrc/adc_pg.h) --------
+ * The consumer of the rollout record: with a record enabled with ADC_ROLLOUT_OBS and days recorded by adc_engine_mlp_step /
+ * adc_engine_run_days(ADC_POLICY_MLP) under a stochastic policy, adc_engine_pg_advantages computes returns and advantages from
+ * the record and the bootstrap value, adc_engine_pg_minibatch takes one gradient of the PPO-clip loss over every recorded day of
+ * an env range and one Adam / SGD step, and writes the new parameters into the device's policy layers, value layers and log_std
+ * (adc_engine_mlp_act, the next recorded day and adc_engine_mlp_get_params see them at once).  Nothing of the record leaves the
+ * device.  Training takes no random draws: the envs' and agents' streams do not move.  The flat parameter order theta[Q]
+ * (adc_engine_pg_param_count): the policy layers as in adc_engine_mlp_get_params, then the value layers in the same form, then
+ * log_std[A] when the head is the free vector.  theta starts as the device's weights at adc_engine_pg_init; later
+ * adc_engine_mlp_set_layer calls do not reach it (adc_engine_pg_state_set does).  Refused (ADC_ESTATE / ADC_EINVAL, the engine
+ * stays usable): before adc_engine_mlp_init and its uploads, without a record or without ADC_ROLLOUT_OBS, with no day recorded,
+ * with a population active, with a record that holds days collected deterministically. */
+enum adc_pg_optimiser { ADC_PG_ADAM = 0, ADC_PG_SGD = 1 };
+typedef struct adc_pg_config {
+    uint32_t struct_size;          /* sizeof(adc_pg_config) */
+    float gamma, lambda;           /* in [0, 1] */
+    float eps_clip;                /* PPO's clip range; <= 0: no clip (the vanilla policy gradient; one epoch of it is A2C) */
+    float vf_coef, ent_coef;       /* >= 0 */
+    float reward_scale;            /* finite, != 0: rewards are multiplied by it before GAE */
+    int32_t normalize_advantages;  /* over all recorded samples */
+    float max_grad_norm;           /* > 0: clip the gradient's global norm; 0: off */
+    int32_t optimiser;             /* adc_pg_optimiser */
+    float lr;                      /* >= 0 */
+    float beta1, beta2, eps;       /* Adam: 0 <= beta < 1, eps > 0 */
+    int32_t minibatch_envs;        /* envs of a minibatch (whole trajectories); must divide num_envs; 0: all */
+} adc_pg_config;
+typedef struct adc_pg_stats {
+    int64_t steps;                 /* optimiser steps taken so far */
+    int64_t samples;               /* samples of the (last) minibatch */
+    double policy_loss, value_loss, entropy, approx_kl, clip_fraction;
+    double grad_norm;              /* before the clip */
+    double explained_variance;     /* of the value function at collection, over the minibatch */
+} adc_pg_stats;
+int adc_engine_pg_init(adc_engine *e, const adc_pg_config *cfg);
+int adc_engine_pg_param_count(adc_engine *e, int64_t *count);
+/* returns and advantages of the recorded days (the bootstrap value is evaluated here); fetch: [T][N] each, either may be NULL */
+int adc_engine_pg_advantages(adc_engine *e);
+int adc_engine_pg_advantages_fetch(adc_engine *e, float *adv_tn, float *ret_tn);
+/* one gradient and one optimiser step over every recorded day of the envs [env_begin, env_begin + env_count), env_count at most
+ * the configuration's minibatch_envs; needs adc_engine_pg_advantages since the last recorded day.  stats may be NULL */
+int adc_engine_pg_minibatch(adc_engine *e, int32_t env_begin, int32_t env_count, adc_pg_stats *stats);
+/* advantages once, then `epochs` times the minibatches in ascending env order; stats (may be NULL): the last epoch's, averaged over
+ * its minibatches in order (steps: the total so far) */
+int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats *stats);
+/* theta, the Adam moments [Q] and the step count: a run resumed from them continues bit for bit (get: any pointer may be NULL) */
+int adc_engine_pg_state_get(adc_engine *e, float *theta_q, float *m_q, float *v_q, int64_t *steps);
+int adc_engine_pg_state_set(adc_engine *e, const float *theta_q, const float *m_q, const float *v_q, int64_t steps);
 
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
@@ -669,6 +719,20 @@ int adc_es_config_check(const adc_es_config *cfg, const char **message);
 int adc_es_noise_host(uint64_t seed, uint32_t pair, uint32_t generation, int64_t p0, int64_t n, float *eps_n);
 int adc_es_update_host(const adc_es_config *cfg, uint64_t seed, int32_t members, int64_t n_params, const double *fitness_m, int64_t generation,
                        float *theta_p, float *m_p, float *v_p, float *grad_p);
+/* policy-gradient training on the host: the same code as the device's (adc_pg.h).  gae: returns and advantages [T][N] from a
+ * record's arrays and the bootstrap values.  param_count: the length Q of the flat order.  grad: the loss pieces and the flat
+ * gradient grad_q of `count` samples handed in as arrays (obs_sd [count][D] the recorded network input, action_sa [count][A]);
+ * sums10 (may be NULL) receives the law's ten sums, stats (may be NULL) the statistics.  step: the norm clip and one optimiser
+ * step on theta / m / v [n_params] in place; steps_taken is the count before the step. */
+int adc_pg_config_check(const adc_pg_config *cfg, const char **message);
+int adc_pg_gae_host(const adc_pg_config *cfg, int32_t days, int32_t num_envs, const float *reward_tn, const uint8_t *terminated_tn,
+                    const uint8_t *truncated_tn, const float *value_tn, const float *bootstrap_n, float *adv_tn, float *ret_tn);
+int adc_pg_param_count_host(const adc_mlp_config *mlp, int32_t num_keywords, int64_t *count);
+int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_pg_config *cfg, const float *theta_q, int64_t count,
+                     const float *obs_sd, const float *action_sa, const float *logp_old_s, const float *adv_s, const float *ret_s,
+                     const float *value_old_s, float *grad_q, double *sums10, adc_pg_stats *stats);
+int adc_pg_step_host(const adc_pg_config *cfg, int64_t n_params, int64_t steps_taken, const float *grad_q, float *theta_q, float *m_q,
+                     float *v_q);
 /* the checks adc_engine_mlp_init makes on a configuration for num_keywords keywords; *message (may be NULL) names the failure */
 int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const char **message);
 /* the law's own tanh (fn 0) and exp (fn 1) at one float32, and a sweep over every float32 in [lo, hi] against the host's float64

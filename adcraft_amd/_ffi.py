@@ -20,6 +20,7 @@ ES_CENTERED_RANK, ES_RAW = 0, 1
 ES_ADAM, ES_SGD = 0, 1
 ROLLOUT_OBS = 1
 PG_ADAM, PG_SGD = 0, 1
+TD3_ADAM, TD3_SGD = 0, 1
 
 
 class EngineError(RuntimeError):
@@ -78,6 +79,20 @@ class PGStats(C.Structure):
     _fields_ = [("steps", C.c_int64), ("samples", C.c_int64), ("policy_loss", C.c_double), ("value_loss", C.c_double),
                 ("entropy", C.c_double), ("approx_kl", C.c_double), ("clip_fraction", C.c_double), ("grad_norm", C.c_double),
                 ("explained_variance", C.c_double)]
+
+
+class TD3Config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_float), ("tau", C.c_float), ("policy_delay", C.c_int32),
+                ("target_noise", C.c_float), ("target_noise_clip", C.c_float), ("action_lo", C.c_float), ("action_hi", C.c_float),
+                ("reward_scale", C.c_float), ("batch_size", C.c_int32), ("capacity", C.c_int32), ("n_critic_layers", C.c_int32),
+                ("critic_widths", C.c_int32 * 4), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("optimiser", C.c_int32), ("max_grad_norm", C.c_float), ("seed", C.c_uint64)]
+
+
+class TD3Stats(C.Structure):
+    _fields_ = [("updates", C.c_int64), ("actor_steps", C.c_int64), ("buffer_size", C.c_int64), ("samples", C.c_int64),
+                ("critic_loss", C.c_double), ("q1_mean", C.c_double), ("q2_mean", C.c_double), ("y_mean", C.c_double),
+                ("actor_loss", C.c_double), ("critic_grad_norm", C.c_double), ("actor_grad_norm", C.c_double)]
 
 
 class Tape(C.Structure):
@@ -250,6 +265,27 @@ def lib():
         "adc_pg_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(PGConfig), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                               C.POINTER(PGStats)], C.c_int),
         "adc_pg_step_host": ([C.POINTER(PGConfig), i64, i64, vp, vp, vp, vp], C.c_int),
+        "adc_engine_td3_init": ([vp, C.POINTER(TD3Config)], C.c_int),
+        "adc_engine_td3_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
+        "adc_engine_td3_set_action_norm": ([vp, vp, vp], C.c_int),
+        "adc_engine_td3_sync_targets": ([vp], C.c_int),
+        "adc_engine_td3_store": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_buffer_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_buffer_fetch": ([vp, i64, i64, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_td3_buffer_load": ([vp, i64, i64, vp, vp, vp, vp, vp, i64], C.c_int),
+        "adc_engine_td3_batch_size": ([vp, C.POINTER(i32)], C.c_int),
+        "adc_engine_td3_batch_indices": ([vp, i64, vp], C.c_int),
+        "adc_engine_td3_update": ([vp, i32, C.POINTER(TD3Stats)], C.c_int),
+        "adc_engine_td3_param_counts": ([vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_state_get": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_state_set": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64], C.c_int),
+        "adc_td3_config_check": ([C.POINTER(TD3Config), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_td3_param_counts_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_td3_batch_indices_host": ([u64, i64, i64, i32, vp], C.c_int),
+        "adc_td3_target_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), u64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp], C.c_int),
+        "adc_td3_critic_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), vp, vp, vp, i32, vp, vp, vp, vp, vp], C.c_int),
+        "adc_td3_actor_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), vp, vp, vp, vp, i32, vp, vp, vp], C.c_int),
+        "adc_td3_polyak_host": ([f32, i64, vp, vp], C.c_int),
         "adc_mlp_config_check": ([C.POINTER(MLPConfig), i32, C.POINTER(C.c_char_p)], C.c_int),
         "adc_mlp_act_host": ([C.POINTER(MLPConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
                               vp, vp, vp, vp, vp, vp, vp], C.c_int),

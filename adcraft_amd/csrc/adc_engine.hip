@@ -49,8 +49,10 @@
 //   parts/kernel_mlp_policy.inc   the learned agent: a fully connected policy (and value) network per env, or per member of a population.
 //   parts/kernel_es.inc           policy populations and the evolution strategy: perturbation, returns, gradient estimate + Adam (adc_es.h).
 //   parts/kernel_pg.inc           policy-gradient training: GAE, the networks' backward pass, the weight gradient, the step (adc_pg.h).
+//   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_api.inc              the entry points of policy-gradient training.
+//   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -72,6 +74,7 @@
 #include "adc_mlp.h"
 #include "adc_es.h"
 #include "adc_pg.h"
+#include "adc_td3.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -90,9 +93,11 @@ namespace adck {
 #include "parts/kernel_mlp_policy.inc"
 #include "parts/kernel_es.inc"
 #include "parts/kernel_pg.inc"
+#include "parts/kernel_td3.inc"
 }  // namespace adck
 using namespace adck;
 
 #include "parts/host_api.inc"
 #include "parts/pg_api.inc"
+#include "parts/td3_api.inc"
 #include "parts/comm_api.inc"

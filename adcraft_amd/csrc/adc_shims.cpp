@@ -17,6 +17,7 @@
 #include "adc_mlp.h"
 #include "adc_es.h"
 #include "adc_pg.h"
+#include "adc_td3.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -583,5 +584,186 @@ ADC_EXPORT int adc_pg_step_host(const adc_pg_config *cfg, int64_t n_params, int6
         const float g = clip ? grad_q[p] * scale : grad_q[p];
         theta_q[p] = adc::pg_apply(step, theta_q[p], g, m_q[p], v_q[p]);
     }
+    return ADC_OK;
+}
+
+// ---- off-policy (TD3) training on the host (adc_td3.h: the code parts/kernel_td3.inc runs) --------------------------------------
+ADC_EXPORT int adc_td3_config_check(const adc_td3_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    const float inf = __builtin_inff();
+    if (!cfg || cfg->struct_size != sizeof(adc_td3_config)) msg = "adc_td3_config: NULL or struct_size mismatch";
+    else if (!(cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) msg = "gamma: 0 to 1";
+    else if (!(cfg->tau > 0.0f && cfg->tau <= 1.0f)) msg = "tau: above 0, at most 1";
+    else if (cfg->policy_delay < 1) msg = "policy_delay >= 1";
+    else if (!(cfg->target_noise >= 0.0f && cfg->target_noise < inf)) msg = "target_noise >= 0";
+    else if (!(cfg->target_noise_clip >= 0.0f && cfg->target_noise_clip < inf)) msg = "target_noise_clip >= 0";
+    else if (cfg->action_lo != cfg->action_lo || cfg->action_hi != cfg->action_hi) msg = "action_lo / action_hi must not be NaN (hi <= lo: no clamp)";
+    else if (!(cfg->reward_scale != 0.0f && cfg->reward_scale > -inf && cfg->reward_scale < inf)) msg = "reward_scale must be finite and not 0";
+    else if (cfg->batch_size < 1 || cfg->batch_size > (1 << 20)) msg = "batch_size: 1 to 2^20";
+    else if (cfg->capacity < 1 || cfg->capacity > (1 << 30)) msg = "capacity: 1 to 2^30";
+    else if (cfg->n_critic_layers < 1 || cfg->n_critic_layers > adc::kMlpMaxLayers) msg = "n_critic_layers: 1 to 4";
+    else if (cfg->critic_widths[cfg->n_critic_layers - 1] != 1) msg = "the last critic layer has one output";
+    else if (!(cfg->actor_lr >= 0.0f && cfg->actor_lr < inf)) msg = "actor_lr >= 0";
+    else if (!(cfg->critic_lr >= 0.0f && cfg->critic_lr < inf)) msg = "critic_lr >= 0";
+    else if (cfg->optimiser != ADC_TD3_ADAM && cfg->optimiser != ADC_TD3_SGD) msg = "unknown optimiser";
+    else if (cfg->optimiser == ADC_TD3_ADAM && (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f)))
+        msg = "Adam: 0 <= beta1, beta2 < 1";
+    else if (cfg->optimiser == ADC_TD3_ADAM && !(cfg->eps > 0.0f)) msg = "Adam: eps > 0";
+    else if (!(cfg->max_grad_norm >= 0.0f && cfg->max_grad_norm < inf)) msg = "max_grad_norm >= 0 (0: off)";
+    else
+        for (int l = 0; l + 1 < cfg->n_critic_layers; ++l)
+            if (cfg->critic_widths[l] < 1 || cfg->critic_widths[l] > adc::kMlpMaxWidth) msg = "hidden critic widths: 1 to 256";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+namespace {
+// the shape two configurations give, or false: a bad configuration or a two-headed policy
+bool td3_host_shape(const adc_mlp_config *mlp, int32_t K, const adc_td3_config *cfg, bool norm, adc::Td3Shape *sh)
+{
+    if (adc_mlp_config_check(mlp, K, nullptr) != ADC_OK || adc_td3_config_check(cfg, nullptr) != ADC_OK) return false;
+    if (mlp->policy_widths[mlp->n_policy_layers - 1] != K + 1) return false;
+    *sh = adc::td3_shape_of(*mlp, K, *cfg, norm ? 1 : 0);
+    return true;
+}
+// one network's gradient terms in the flat order: g[flat0 ...] = float32(csum over the batch / count)
+void td3_net_grad_host(const adc::Td3Net &net, int64_t count, const float *X0, size_t ldx0, const float *ys, size_t ny, size_t y_off, const float *deltas,
+                       size_t nd, size_t d_off, float *g)
+{
+    size_t q = 0, lo = 0;
+    for (int l = 0; l < net.layers; ++l) {
+        const int n_in = adc::td3_n_in(net, l), n_out = net.n_out[l];
+        const float *X = l == 0 ? X0 : ys + y_off + lo - (size_t)n_in;
+        const size_t ldx = l == 0 ? ldx0 : ny;
+        for (int j = 0; j <= n_in; ++j)
+            for (int h = 0; h < n_out; ++h) {
+                const double total = adc::pg_csum(count, [&](double part, int64_t s) {
+                    return adc::pg_chain_mac(part, j < n_in ? X[(size_t)s * ldx + (size_t)j] : 1.0f, deltas[(size_t)s * nd + d_off + lo + (size_t)h]);
+                });
+                g[q++] = adc::pg_grad_finish(total, count);
+            }
+        lo += (size_t)n_out;
+    }
+}
+}  // namespace
+
+ADC_EXPORT int adc_td3_param_counts_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, int64_t *actor_p, int64_t *critic_qc)
+{
+    adc::Td3Shape sh;
+    if (!td3_host_shape(mlp, num_keywords, cfg, false, &sh)) return ADC_EINVAL;
+    if (actor_p) *actor_p = adc::td3_params(sh.pol);
+    if (critic_qc) *critic_qc = adc::td3_params(sh.q);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_batch_indices_host(uint64_t seed, int64_t update, int64_t size, int32_t count, int32_t *idx_b)
+{
+    if (update < 0 || update >= 0xFFFFFFFFll || size < 1 || size > (1ll << 30) || count < 1 || !idx_b) return ADC_EINVAL;
+    const uint64_t key = adc::td3_key(seed);
+    for (int32_t b = 0; b < count; ++b) idx_b[b] = (int32_t)adc::td3_batch_index(key, (uint32_t)b, (uint32_t)update, (uint32_t)size);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
+                                   const float *theta_target_p, const float *psi_target_q, const float *shift_a, const float *scale_a, int32_t count,
+                                   const float *x2_bd, const float *r_b, const uint8_t *done_b, float *y_b)
+{
+    adc::Td3Shape sh;
+    if (!td3_host_shape(mlp, num_keywords, cfg, shift_a != nullptr, &sh)) return ADC_EINVAL;
+    if ((shift_a == nullptr) != (scale_a == nullptr) || update < 0 || update >= 0xFFFFFFFFll || count < 1 || !theta_target_p || !psi_target_q || !x2_bd ||
+        !r_b || !done_b || !y_b)
+        return ADC_EINVAL;
+    const adc::Td3Law law = adc::td3_law_of(*cfg);
+    const uint64_t key = adc::td3_key(seed);
+    const size_t D = (size_t)sh.D, A = (size_t)sh.A, Qc = (size_t)adc::td3_params(sh.q);
+    std::vector<float> row(D + A), yp((size_t)adc::td3_outs(sh.pol)), yq((size_t)adc::td3_outs(sh.q));
+    for (int32_t b = 0; b < count; ++b) {
+        std::copy(x2_bd + (size_t)b * D, x2_bd + (size_t)(b + 1) * D, row.begin());
+        adc::td3_forward_host(sh.pol, sh.activation, theta_target_p, row.data(), yp.data());
+        const float *mu = yp.data() + adc::td3_hidden(sh.pol);
+        for (int a = 0; a < sh.A; ++a) {
+            const float ap = adc::td3_target_action(mu[a], adc::td3_noise(key, a, (uint32_t)b, (uint32_t)update), law);
+            row[D + (size_t)a] = adc::td3_action_norm(ap, shift_a, scale_a, a, sh.norm);
+        }
+        float q[2];
+        for (int i = 0; i < 2; ++i) {
+            adc::td3_forward_host(sh.q, sh.activation, psi_target_q + (size_t)i * Qc, row.data(), yq.data());
+            q[i] = yq[(size_t)adc::td3_hidden(sh.q)];
+        }
+        y_b[b] = adc::td3_y(r_b[b], done_b[b], adc::td3_min(q[0], q[1]), law);
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_critic_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *psi_q,
+                                        const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, const float *a_ba, const float *y_b,
+                                        float *grad_q, double *sums6)
+{
+    adc::Td3Shape sh;
+    if (!td3_host_shape(mlp, num_keywords, cfg, shift_a != nullptr, &sh)) return ADC_EINVAL;
+    if ((shift_a == nullptr) != (scale_a == nullptr) || count < 1 || !psi_q || !x_bd || !a_ba || !y_b || !grad_q) return ADC_EINVAL;
+    const size_t S = (size_t)count, D = (size_t)sh.D, A = (size_t)sh.A, DA = D + A, Qc = (size_t)adc::td3_params(sh.q), no = (size_t)adc::td3_outs(sh.q),
+                 nh = (size_t)adc::td3_hidden(sh.q);
+    std::vector<float> xin(S * DA), ys(S * 2 * no), deltas(S * 2 * no), pieces(S * adc::kTd3Pieces, 0.0f);
+    for (size_t s = 0; s < S; ++s) {
+        float *row = xin.data() + s * DA;
+        std::copy(x_bd + s * D, x_bd + (s + 1) * D, row);
+        for (int a = 0; a < sh.A; ++a) row[D + (size_t)a] = adc::td3_action_norm(a_ba[s * A + (size_t)a], shift_a, scale_a, a, sh.norm);
+        for (size_t i = 0; i < 2; ++i) {
+            float *y = ys.data() + s * 2 * no + i * no, *d = deltas.data() + s * 2 * no + i * no;
+            adc::td3_forward_host(sh.q, sh.activation, psi_q + i * Qc, row, y);
+            float loss;
+            d[nh] = adc::td3_critic_delta(y[nh], y_b[s], loss);
+            pieces[s * adc::kTd3Pieces + adc::kTd3Loss1 + i] = loss;
+            pieces[s * adc::kTd3Pieces + adc::kTd3Q1 + i] = y[nh];
+            adc::td3_backward_host(sh.q, sh.activation, psi_q + i * Qc, y, d);
+        }
+        pieces[s * adc::kTd3Pieces + adc::kTd3Y] = y_b[s];
+    }
+    for (size_t i = 0; i < 2; ++i)
+        td3_net_grad_host(sh.q, count, xin.data(), DA, ys.data(), 2 * no, i * no, deltas.data(), 2 * no, i * no, grad_q + i * Qc);
+    if (sums6) {
+        for (int c = 0; c < 5; ++c) sums6[c] = adc::pg_csum(count, [&](double part, int64_t s) { return part + (double)pieces[(size_t)s * adc::kTd3Pieces + (size_t)c]; });
+        sums6[5] = adc::pg_csum((int64_t)(2 * Qc), [&](double part, int64_t p) { return adc::pg_chain_mac(part, grad_q[p], grad_q[p]); });
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p,
+                                       const float *psi_q, const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p,
+                                       double *sums2)
+{
+    adc::Td3Shape sh;
+    if (!td3_host_shape(mlp, num_keywords, cfg, shift_a != nullptr, &sh)) return ADC_EINVAL;
+    if ((shift_a == nullptr) != (scale_a == nullptr) || count < 1 || !theta_p || !psi_q || !x_bd || !grad_p) return ADC_EINVAL;
+    const size_t S = (size_t)count, D = (size_t)sh.D, A = (size_t)sh.A, po = (size_t)adc::td3_outs(sh.pol), ph = (size_t)adc::td3_hidden(sh.pol),
+                 no = (size_t)adc::td3_outs(sh.q), nh = (size_t)adc::td3_hidden(sh.q);
+    std::vector<float> ys(S * po), deltas(S * po), row(D + A), yq(no), dq(no), qpi(S);
+    for (size_t s = 0; s < S; ++s) {
+        float *y = ys.data() + s * po, *d = deltas.data() + s * po;
+        std::copy(x_bd + s * D, x_bd + (s + 1) * D, row.begin());
+        adc::td3_forward_host(sh.pol, sh.activation, theta_p, row.data(), y);
+        for (int a = 0; a < sh.A; ++a) row[D + (size_t)a] = adc::td3_action_norm(y[ph + (size_t)a], shift_a, scale_a, a, sh.norm);
+        adc::td3_forward_host(sh.q, sh.activation, psi_q, row.data(), yq.data());
+        qpi[s] = yq[nh];
+        dq[nh] = 1.0f;
+        adc::td3_backward_host(sh.q, sh.activation, psi_q, yq.data(), dq.data());
+        adc::td3_input_delta_host(sh.q, psi_q, dq.data(), sh.D, sh.A, d + ph);
+        for (int a = 0; a < sh.A; ++a) d[ph + (size_t)a] = adc::td3_dmu(d[ph + (size_t)a], sh.norm ? scale_a[a] : 0.0f, sh.norm);
+        adc::td3_backward_host(sh.pol, sh.activation, theta_p, y, d);
+    }
+    td3_net_grad_host(sh.pol, count, x_bd, D, ys.data(), po, 0, deltas.data(), po, 0, grad_p);
+    if (sums2) {
+        sums2[0] = adc::pg_csum(count, [&](double part, int64_t s) { return part + (double)qpi[(size_t)s]; });
+        sums2[1] = adc::pg_csum((int64_t)adc::td3_params(sh.pol), [&](double part, int64_t p) { return adc::pg_chain_mac(part, grad_p[p], grad_p[p]); });
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_polyak_host(float tau, int64_t n, const float *param_n, float *target_n)
+{
+    if (!(tau > 0.0f && tau <= 1.0f) || n < 1 || !param_n || !target_n) return ADC_EINVAL;
+    for (int64_t p = 0; p < n; ++p) target_n[p] = adc::td3_polyak(target_n[p], param_n[p], tau);
     return ADC_OK;
 }

@@ -114,6 +114,27 @@ struct adc_engine {
     double *pg_part = nullptr, *pg_sums = nullptr;                                       // chunk partials; the law's ten sums
     double *pg_gpart = nullptr;                                                          // [chunks][Q] the weight gradient's partials
     std::vector<void *> pg_allocs;
+    // off-policy training over a replay ring filled from the record (adc_engine_td3_init; parts/kernel_td3.inc, parts/td3_api.inc)
+    bool have_td3 = false, td3_norm_set = false, td3_gap = false;
+    bool td3_critic_set[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    adc_td3_config td3_cfg{};
+    adc::Td3Shape td3_shape{};
+    uint64_t td3_key = 0;
+    int64_t td3_updates = 0, td3_actor_steps = 0, td3_written = 0;    // critic updates, actor steps, transitions stored so far
+    int td3_stored_t = 0;               // the record's days [0, td3_stored_t) are in the ring
+    int td3_Qc = 0, td3_P = 0;          // parameters of one critic, of the actor
+    PgLayout td3_lay[4] = {};           // the flat orders against the stores: theta, psi, target theta, target psi
+    MlpNet td3_q[2] = {}, td3_q_t[2] = {}, td3_pol_t{};
+    float *td3_a_shift = nullptr, *td3_a_scale = nullptr;             // [A]
+    Td3Ring td3_ring{};
+    float *td3_flat[4] = {nullptr, nullptr, nullptr, nullptr};        // theta [P], psi [2 Qc], target theta, target psi
+    float *td3_mom[4] = {nullptr, nullptr, nullptr, nullptr};         // Adam: m theta, v theta, m psi, v psi
+    float *td3_grad = nullptr, *td3_ybuf = nullptr, *td3_xin = nullptr, *td3_acts = nullptr, *td3_deltas = nullptr, *td3_pieces = nullptr;
+    int32_t *td3_idx = nullptr;         // [B] adc_engine_td3_batch_indices' device result
+    double *td3_part = nullptr, *td3_sums = nullptr, *td3_gpart = nullptr;
+    std::vector<void *> td3_allocs;
+    // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
+    uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
     // two consecutive days of the device-resident loop captured as one hipGraph (adc_engine_run_days)
     hipGraphExec_t day_graph = nullptr;
@@ -594,6 +615,7 @@ int launch_step(adc_engine *e, const float *d_bids, const float *d_budget, const
     e->api_since_step = !lazy_join;
     e->last_step = tape ? 2 : 1;
     e->stream_steps = tape ? 0 : e->stream_steps + 1;
+    e->env_moves += 1;
     e->drift_applied = false;
     if (tape) {
         e->step_kernel = "k_step_exact";
@@ -799,6 +821,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->es_allocs) (void)hipFree(p);
     for (void *p : e->ro_allocs) (void)hipFree(p);
     for (void *p : e->pg_allocs) (void)hipFree(p);
+    for (void *p : e->td3_allocs) (void)hipFree(p);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1102,6 +1125,7 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
     e->have_reset = true;
     e->last_step = 0;
     e->stream_steps = 0;
+    e->env_moves += 1;
     return ADC_OK;
 }
 
@@ -1232,6 +1256,7 @@ ADC_EXPORT int adc_engine_set_episode_state(adc_engine *e, const int32_t *day_n,
     e->have_reset = true;
     e->last_step = 0;
     e->stream_steps = 0;
+    e->env_moves += 1;
     return ADC_OK;
 }
 
@@ -2731,7 +2756,7 @@ int mlp_record_outcome_chained(adc_engine *e)
         hipLaunchKernelGGL(k_mlp_record_outcome, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->ro_reward + row, e->ro_term + row,
                            e->ro_trunc + row);
     });
-    if (!rc) { e->ro_t += 1; e->pg_adv_ready = false; }
+    if (!rc) { e->ro_t += 1; e->pg_adv_ready = false; e->ro_moves = e->env_moves; }
     return rc;
 }
 // the evolution strategy's side of a stepped day: every env's reward added to its return of the generation
@@ -2750,6 +2775,8 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     if (record && !rollout_room(e, 1)) return fail(ADC_EINVAL, "the rollout record is full: adc_engine_rollout_reset before recording another day");
     int rc;
     if (record && e->mp.deterministic) e->ro_deterministic = true;
+    // (a day recorded after the envs moved outside the record does not follow the unstored day before it)
+    if (record && e->have_td3 && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
     if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
     if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
     if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
@@ -2762,6 +2789,15 @@ void pg_drop(adc_engine *e)
     mlp_free(e, e->pg_allocs);
     e->have_pg = e->pg_adv_ready = false;
     e->pg_steps = 0;
+}
+// ... and so does the off-policy trainer (its ring holds rows of that policy's input and action widths)
+void td3_drop(adc_engine *e)
+{
+    mlp_free(e, e->td3_allocs);
+    e->have_td3 = e->td3_norm_set = e->td3_gap = false;
+    std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));
+    e->td3_updates = e->td3_actor_steps = e->td3_written = 0;
+    e->td3_stored_t = 0;
 }
 // a population and the strategy over it go with the policy they belong to
 void population_drop(adc_engine *e)
@@ -2811,6 +2847,7 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     ENGINE_GUARD(e);
     population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
     pg_drop(e);
+    td3_drop(e);
     mlp_free(e, e->mlp_allocs);
     e->have_mlp = false;
     MlpView p{};
@@ -3283,6 +3320,7 @@ ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t
     if (fields & ~ADC_ROLLOUT_OBS) return fail(ADC_EINVAL, "unknown rollout field");
     ENGINE_GUARD(e);
     pg_drop(e);                         // (its advantages and scratch were sized for the old record)
+    td3_drop(e);
     mlp_free(e, e->ro_allocs);
     e->ro_T = e->ro_t = 0;
     e->ro_obs = nullptr;
@@ -3310,6 +3348,8 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     e->ro_t = 0;
     e->ro_deterministic = false;
     e->pg_adv_ready = false;
+    e->td3_stored_t = 0;
+    e->td3_gap = false;
     return ADC_OK;
 }
 
@@ -3421,6 +3461,7 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
         }
         const uint32_t serial0 = e->step_serial;
         const long long stream_steps0 = e->stream_steps;
+        const uint64_t env_moves0 = e->env_moves;
         const int last_step0 = e->last_step;
         hipGraph_t graph = nullptr;
         if ((rc = join_groups(e))) return rc;           // (the plain day above may have run as env groups: nothing of it may still be in flight on their streams)
@@ -3434,6 +3475,7 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
         e->step_serial = serial0;                       // nothing ran: the capture only recorded the launches
         e->stream_steps = stream_steps0;
         e->last_step = last_step0;
+        e->env_moves = env_moves0;
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         HIP_TRY(cap);
         const hipError_t inst = hipGraphInstantiate(&e->day_graph, graph, nullptr, nullptr, 0);
@@ -3458,6 +3500,7 @@ ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, floa
         HIP_TRY(hipGraphLaunch(e->day_graph, e->stream));
         e->step_serial += 2;
         e->stream_steps += 2;
+        e->env_moves += 2;
         e->last_step = 1;
         e->drift_applied = false;
         days -= 2;

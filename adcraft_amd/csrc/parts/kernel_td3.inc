@@ -1,0 +1,236 @@
+// kernel_td3.inc - off-policy training on the device: the replay ring filled from the rollout record, the TD3 target, the twin
+// critics' forward and backward pass, the deterministic policy gradient through critic 1's input, and Polyak averaging.  The
+// arithmetic is adc_td3.h's law, the code the host twins adc_td3_target_host / adc_td3_critic_grad_host /
+// adc_td3_actor_grad_host run.
+// (part of the single translation unit adc_engine.hip)
+// -------------------------------------------------------------------------------------------------
+// Shape.  The batch kernels are k_pg_sample's shape: one workgroup of 256 lanes per batch element, the element's input row
+// [x | an] and every layer's activations in LDS, eight adjacent lanes per neuron with the butterfly join (mlp_layer one way,
+// pg_layer_back the other).  Every workgroup derives its ring slot from the batch's counter-addressed draw, so no index
+// buffer is written first.  The critic kernel leaves the gathered rows, the hidden activations and the deltas in scratch; the
+// weight gradient over the batch is k_pg_wgrad / k_pg_grad_join unchanged (X = the gathered rows for a first layer), the
+// optimiser step k_pg_update on a PgLayout over the critics' (or the policy's) chain-major stores.  All LDS is the dynamic
+// region (no static words in front of it).  No atomics; all stores are plain vector stores.
+struct Td3Ring {
+    float *x, *a, *r, *x2;                  // [C][D], [C][A], [C], [C][D]
+    uint8_t *done;                          // [C]
+};
+
+struct Td3View {
+    adc::Td3Shape sh;
+    adc::Td3Law law;
+    MlpNet pol, pol_t, q[2], q_t[2];        // chain-major layers: the live actor, its target, the critics, their targets
+    const float *a_shift, *a_scale;         // [A] (sh.norm)
+    Td3Ring ring;
+    uint32_t size, update;                  // the ring's size; the update's number
+    uint64_t key;
+    float *ybuf;                            // [B]
+    float *xin;                             // [B][D + A] the gathered rows
+    float *acts, *deltas, *pieces;          // scratch [B][na], [B][nd], [B][kTd3Pieces]
+    int na, nd, maxw;
+};
+
+// floats of LDS: row | the actor's outputs | one critic's outputs | two delta buffers | a dump row
+__host__ __device__ inline size_t td3_lds_floats(const adc::Td3Shape &sh)
+{
+    return (size_t)(sh.D + sh.A) + (size_t)adc::td3_outs(sh.pol) + (size_t)adc::td3_outs(sh.q) + 3u * (size_t)adc::td3_max_width(sh) + 4u;
+}
+
+// a network forward on the LDS row `in`, every layer's outputs kept at ys (layers in order); the hidden ones written to g_acts
+__device__ __forceinline__ void td3_forward(const MlpNet &net, int activation, const float *in, float *ys, float *__restrict__ g_acts)
+{
+    const int tid = threadIdx.x;
+    float *y = ys;
+    int ao = 0;
+    for (int l = 0; l < net.layers; ++l) {
+        const bool last = l + 1 == net.layers;
+        const int n_out = net.n_out[l];
+        mlp_layer(net.W[l], net.b[l], net.n_in[l], n_out, in, y, last ? -1 : activation);
+        if (!last && g_acts) {
+            for (int h = tid; h < n_out; h += kPgBlock) g_acts[ao + h] = y[h];
+            ao += n_out;
+        }
+        in = y; y += n_out;
+    }
+}
+
+// the hidden deltas of a network whose last layer's deltas are in dcur, last to first; g_deltas: the sample's deltas of this
+// network (layers in order), or null: only LDS (dump receives what pg_layer_back writes out).  Returns where layer 0's deltas are.
+__device__ __forceinline__ float *td3_backward(const MlpNet &net, int activation, const float *ys, float *dcur, float *dnew, float *g_deltas,
+                                               float *dump)
+{
+    int off[adc::kMlpMaxLayers], o = 0;
+    for (int l = 0; l < net.layers; ++l) { off[l] = o; o += net.n_out[l]; }
+    for (int l = net.layers - 2; l >= 0; --l) {
+        pg_layer_back(net.W[l + 1], net.n_out[l], net.n_out[l + 1], ys + off[l], dcur, dnew, activation, g_deltas ? g_deltas + off[l] : dump);
+        float *t = dcur; dcur = dnew; dnew = t;
+    }
+    return dcur;
+}
+
+// dmu[a] = -(din[D + a] * a_scale[a]): the first critic layer's deltas carried to the action inputs, no activation derivative
+__device__ __forceinline__ void td3_input_back(const float *__restrict__ W, int j0, int n, int n_out, const float *dcur, float *dnew,
+                                               const float *__restrict__ scale, int norm, float *__restrict__ g_out)
+{
+    const int tid = threadIdx.x;
+    const int pairs = n * adc::kMlpChains;
+    for (int p0 = 0; p0 < pairs; p0 += kPgBlock) {
+        const int pi = p0 + tid;
+        const bool on = pi < pairs;
+        const int a = on ? pi >> 3 : 0, c = pi & 7;
+        float acc = 0.0f;
+        if (on)
+            for (int h = c; h < n_out; h += adc::kMlpChains) acc = adc::mlp_mac(acc, W[adc::mlp_weight_index(j0 + a, h, n_out)], dcur[h]);
+        float s = acc;
+        s = s + __shfl_xor(s, 1, 64);
+        s = s + __shfl_xor(s, 2, 64);
+        s = s + __shfl_xor(s, 4, 64);           // adc::mlp_join8
+        if (on && c == 0) {
+            const float d = adc::td3_dmu(s, norm ? scale[a] : 0.0f, norm);
+            dnew[a] = d;
+            g_out[a] = d;
+        }
+    }
+    __syncthreads();
+}
+
+// sample s = (t - t0) * N + n of the recorded days [t0, t1) into slot (written + s) mod C
+__global__ __launch_bounds__(kPgBlock) void k_td3_store(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
+                                                        const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                        const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                        const uint8_t *__restrict__ ro_trunc, int t0, int t1, Td3Ring ring,
+                                                        unsigned long long written, unsigned long long C)
+{
+    const int tid = threadIdx.x, N = v.N, K = v.K;
+    const unsigned long long s = blockIdx.x, count = (unsigned long long)(t1 - t0) * (unsigned long long)N;
+    if (s >= count || s + C < count) return;            // (a later sample of this store lands on the same slot)
+    const int t = t0 + (int)(s / (unsigned long long)N), env = (int)(s % (unsigned long long)N);
+    const size_t slot = (size_t)((written + s) % C), row = (size_t)t * (size_t)N + (size_t)env;
+    for (int j = tid; j < D; j += kPgBlock) ring.x[slot * (size_t)D + j] = ro_obs[row * (size_t)D + j];
+    for (int a = tid; a < A; a += kPgBlock) ring.a[slot * (size_t)A + a] = ro_action[row * (size_t)A + a];
+    if (tid == 0) {
+        ring.r[slot] = ro_reward[row];
+        ring.done[slot] = (uint8_t)((ro_term[row] | ro_trunc[row]) ? 1 : 0);
+    }
+    if (t + 1 < t1) {
+        const size_t next = row + (size_t)N;
+        for (int j = tid; j < D; j += kPgBlock) ring.x2[slot * (size_t)D + j] = ro_obs[next * (size_t)D + j];
+    } else {
+        // the input row an act would read now (k_mlp_policy's prologue)
+        const bool first = v.day[env] == 0;
+        const size_t o = (size_t)env * K;
+        const double cum = v.cum_profit[env];
+        const int32_t days = v.day_out[env];
+        for (int j = tid; j < D; j += kPgBlock) {
+            float xj = first ? 0.0f : adc::mlp_obs_at(j, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
+            if (shift) xj = adc::mlp_normalize(xj, shift[j], scale[j]);
+            ring.x2[slot * (size_t)D + j] = xj;
+        }
+    }
+}
+
+__global__ void k_td3_indices(uint64_t key, uint32_t update, uint32_t size, int B, int32_t *__restrict__ out)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) out[b] = (int32_t)adc::td3_batch_index(key, (uint32_t)b, update, size);
+}
+
+// y of batch element blockIdx.x
+__global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
+{
+    extern __shared__ __align__(16) float td3_lds[];
+    const adc::Td3Shape &sh = p.sh;
+    const int tid = threadIdx.x, A = sh.A, D = sh.D;
+    const uint32_t b = blockIdx.x;
+    float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *words = yq + adc::td3_outs(sh.q) + 3 * p.maxw;
+    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    for (int j = tid; j < D; j += kPgBlock) row[j] = p.ring.x2[slot * (size_t)D + j];
+    __syncthreads();
+    td3_forward(p.pol_t, sh.activation, row, yp, nullptr);
+    const float *mu = yp + adc::td3_hidden(sh.pol);
+    for (int a = tid; a < A; a += kPgBlock) {
+        const float ap = adc::td3_target_action(mu[a], adc::td3_noise(p.key, a, b, p.update), p.law);
+        row[D + a] = adc::td3_action_norm(ap, p.a_shift, p.a_scale, a, sh.norm);
+    }
+    __syncthreads();
+    const int qlast = adc::td3_hidden(sh.q);
+    for (int i = 0; i < 2; ++i) {
+        td3_forward(p.q_t[i], sh.activation, row, yq, nullptr);
+        if (tid == 0) words[i] = yq[qlast];
+        __syncthreads();
+    }
+    if (tid == 0) p.ybuf[b] = adc::td3_y(p.ring.r[slot], p.ring.done[slot], adc::td3_min(words[0], words[1]), p.law);
+}
+
+// forward and backward of both critics on batch element blockIdx.x
+__global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
+{
+    extern __shared__ __align__(16) float td3_lds[];
+    const adc::Td3Shape &sh = p.sh;
+    const int tid = threadIdx.x, A = sh.A, D = sh.D, DA = D + A;
+    const uint32_t b = blockIdx.x;
+    float *row = td3_lds, *yq = row + DA + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
+    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    float *xin = p.xin + (size_t)b * (size_t)DA;
+    for (int j = tid; j < DA; j += kPgBlock) {
+        const float xj = j < D ? p.ring.x[slot * (size_t)D + j]
+                               : adc::td3_action_norm(p.ring.a[slot * (size_t)A + (j - D)], p.a_shift, p.a_scale, j - D, sh.norm);
+        row[j] = xj;
+        xin[j] = xj;
+    }
+    __syncthreads();
+    const int nh = adc::td3_hidden(sh.q), no = adc::td3_outs(sh.q);
+    float *acts = p.acts + (size_t)b * (size_t)p.na, *deltas = p.deltas + (size_t)b * (size_t)p.nd, *pc = p.pieces + (size_t)b * adc::kTd3Pieces;
+    for (int i = 0; i < 2; ++i) {
+        td3_forward(p.q[i], sh.activation, row, yq, acts + i * nh);
+        if (tid == 0) {
+            const float y = p.ybuf[b], q = yq[nh];
+            float loss;
+            const float d = adc::td3_critic_delta(q, y, loss);
+            pc[adc::kTd3Loss1 + i] = loss; pc[adc::kTd3Q1 + i] = q;
+            if (i == 0) { pc[adc::kTd3Y] = y; pc[adc::kTd3QPi] = 0.0f; pc[6] = 0.0f; pc[7] = 0.0f; }
+            d0[0] = d;
+            deltas[i * no + nh] = d;
+        }
+        __syncthreads();
+        td3_backward(p.q[i], sh.activation, yq, d0, d1, deltas + i * no, dump);
+    }
+}
+
+// the actor's forward, critic 1 on [x | norm(mu)], its backward through to the action inputs, the actor's backward
+__global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample(Td3View p)
+{
+    extern __shared__ __align__(16) float td3_lds[];
+    const adc::Td3Shape &sh = p.sh;
+    const int tid = threadIdx.x, A = sh.A, D = sh.D;
+    const uint32_t b = blockIdx.x;
+    float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
+    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    for (int j = tid; j < D; j += kPgBlock) row[j] = p.ring.x[slot * (size_t)D + j];
+    __syncthreads();
+    float *acts = p.acts + (size_t)b * (size_t)p.na, *deltas = p.deltas + (size_t)b * (size_t)p.nd;
+    td3_forward(p.pol, sh.activation, row, yp, acts);
+    const int ph = adc::td3_hidden(sh.pol), qh = adc::td3_hidden(sh.q);
+    for (int a = tid; a < A; a += kPgBlock) row[D + a] = adc::td3_action_norm(yp[ph + a], p.a_shift, p.a_scale, a, sh.norm);
+    __syncthreads();
+    td3_forward(p.q[0], sh.activation, row, yq, nullptr);
+    if (tid == 0) {
+        p.pieces[(size_t)b * adc::kTd3Pieces + adc::kTd3QPi] = yq[qh];
+        d0[0] = 1.0f;
+    }
+    __syncthreads();
+    float *dq = td3_backward(p.q[0], sh.activation, yq, d0, d1, nullptr, dump);
+    float *dm = dq == d0 ? d1 : d0;
+    td3_input_back(p.q[0].W[0], D, A, sh.q.n_out[0], dq, dm, p.a_scale, sh.norm, deltas + ph);
+    td3_backward(p.pol, sh.activation, yp, dm, dq, deltas, dump);
+}
+
+// target = target + tau * (param - target) on the flat vectors, the targets' chain-major stores rebuilt from the result
+__global__ __launch_bounds__(kPgBlock) void k_td3_polyak(PgLayout L, float *__restrict__ target, const float *__restrict__ param, float tau)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= L.Q) return;
+    const float t1 = adc::td3_polyak(target[p], param[p], tau);
+    target[p] = t1;
+    *pg_param_slot(L, p) = t1;
+}

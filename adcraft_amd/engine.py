@@ -585,6 +585,13 @@ class StepEngine:
         if policy.log_std is not None:
             check(self._lib.adc_engine_mlp_set_log_std(self._h, policy.log_std.ctypes.data))
 
+    def mlp_set_log_std(self, log_std):
+        """the free log_std vector [K + 1] alone (the exploration noise of an off-policy trainer); nothing else changes"""
+        ls = np.ascontiguousarray(log_std, dtype=np.float32)
+        if ls.shape != (self.num_keywords + 1,):
+            raise ValueError("mlp_set_log_std: K + 1 entries")
+        check(self._lib.adc_engine_mlp_set_log_std(self._h, ls.ctypes.data))
+
     def mlp_set_deterministic(self, on=True):
         check(self._lib.adc_engine_mlp_set_deterministic(self._h, 1 if on else 0))
 
@@ -778,6 +785,132 @@ class StepEngine:
         if any(a.shape != (Q,) for a in arr):
             raise ValueError(f"pg_state: theta, m and v have {Q} entries")
         check(self._lib.adc_engine_pg_state_set(self._h, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
+
+    # ---- off-policy (TD3) training over a replay ring filled from the record (parts/kernel_td3.inc; baselines/td3_trainer.py) ----
+    TD3_OPTIMISERS = {"adam": _ffi.TD3_ADAM, "sgd": _ffi.TD3_SGD}
+
+    @classmethod
+    def td3_config(cls, gamma=0.99, tau=0.005, policy_delay=2, target_noise=0.2, target_noise_clip=0.5, action_lo=0.0, action_hi=0.0,
+                   reward_scale=1.0, batch_size=256, capacity=100000, critic_widths=(256, 256, 1), actor_lr=1e-3, critic_lr=1e-3,
+                   beta1=0.9, beta2=0.999, eps=1e-8, optimiser="adam", max_grad_norm=0.0, seed=0):
+        """an adc_td3_config (csrc/adc_td3.h) with Fujimoto et al.'s defaults; critic_widths: the outputs of every critic layer,
+        the last 1; action_hi <= action_lo: the target action is not clamped; max_grad_norm 0: off; seed 0: the engine's"""
+        c = _ffi.TD3Config()
+        c.struct_size = C.sizeof(_ffi.TD3Config)
+        c.gamma, c.tau, c.policy_delay, c.target_noise, c.target_noise_clip = gamma, tau, int(policy_delay), target_noise, target_noise_clip
+        c.action_lo, c.action_hi, c.reward_scale, c.batch_size, c.capacity = action_lo, action_hi, reward_scale, int(batch_size), int(capacity)
+        widths = [int(w) for w in critic_widths]
+        if not 1 <= len(widths) <= 4:
+            raise ValueError("critic_widths: 1 to 4 layers")
+        c.n_critic_layers = len(widths)
+        for i, w in enumerate(widths):
+            c.critic_widths[i] = w
+        if optimiser not in cls.TD3_OPTIMISERS:
+            raise ValueError(f"unknown optimiser {optimiser!r}: 'adam' or 'sgd'")
+        c.actor_lr, c.critic_lr, c.beta1, c.beta2, c.eps = actor_lr, critic_lr, beta1, beta2, eps
+        c.optimiser, c.max_grad_norm, c.seed = cls.TD3_OPTIMISERS[optimiser], max_grad_norm, int(seed)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_td3_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad TD3 configuration").decode())
+        return c
+
+    def td3_init(self, **options):
+        """TD3 on the policy given to mlp_init (free log_std head) over the rollout record (rollout_enable(T, obs=True) first);
+        options as td3_config's.  theta starts as the device's policy; the critics are uploaded with td3_set_critics."""
+        cfg = self.td3_config(**options)
+        check(self._lib.adc_engine_td3_init(self._h, C.byref(cfg)))
+
+    def td3_set_critics(self, critics, action_norm=None, sync_targets=True):
+        """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs; action_norm: (shift, scale) [A]
+        for the critics' action inputs; sync_targets: the targets become copies of the actor and the critics"""
+        if len(critics) != 2:
+            raise ValueError("td3_set_critics: two critics")
+        for i, layers in enumerate(critics):
+            for l, (w, b) in enumerate(layers):
+                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+                check(self._lib.adc_engine_td3_set_critic_layer(self._h, i, l, w.ctypes.data, b.ctypes.data))
+        if action_norm is not None:
+            sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in action_norm)
+            if sh.shape != (self.num_keywords + 1,) or sc.shape != sh.shape:
+                raise ValueError("action_norm: shift and scale of K + 1 entries")
+            check(self._lib.adc_engine_td3_set_action_norm(self._h, sh.ctypes.data, sc.ctypes.data))
+        if sync_targets:
+            check(self._lib.adc_engine_td3_sync_targets(self._h))
+
+    def td3_sync_targets(self):
+        check(self._lib.adc_engine_td3_sync_targets(self._h))
+
+    def td3_store(self):
+        """the record's days not yet stored, into the ring; returns the transitions appended"""
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_td3_store(self._h, C.byref(n)))
+        return n.value
+
+    def td3_buffer(self, fetch=True):
+        """dict of size, written, capacity and (fetch=True) the ring's slots [0, size): x [size, D], a [size, A], r [size],
+        done [size] (bool), x2 [size, D]"""
+        sz, wr, cap = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self._lib.adc_engine_td3_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap)))
+        st = dict(size=sz.value, written=wr.value, capacity=cap.value)
+        if fetch:
+            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
+            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
+                      x2=np.zeros((n, D), np.float32))
+            if n:
+                check(self._lib.adc_engine_td3_buffer_fetch(self._h, 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
+            st["done"] = st["done"].astype(bool)
+        return st
+
+    def td3_buffer_load(self, buf, slot=0, written=None):
+        """the arrays of a td3_buffer() dict (or one of its kind) into the slots from `slot` on; written (default: the dict's, or
+        slot + the count) becomes the ring's count of transitions stored so far"""
+        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
+        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
+        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
+        n = r.shape[0]
+        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
+            raise ValueError("td3_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
+        if written is None:
+            written = buf.get("written", slot + n)
+        check(self._lib.adc_engine_td3_buffer_load(self._h, int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data, x2.ctypes.data,
+                                                   int(written)))
+
+    def td3_batch_indices(self, update):
+        """the ring slots update number `update` reads at the ring's current size: [batch_size] int32"""
+        b = C.c_int32(0)
+        check(self._lib.adc_engine_td3_batch_size(self._h, C.byref(b)))       # (the engine says how many slots it will write)
+        idx = np.zeros(b.value, np.int32)
+        check(self._lib.adc_engine_td3_batch_indices(self._h, int(update), idx.ctypes.data))
+        return idx
+
+    def td3_update(self, updates=1):
+        """`updates` critic updates and the delayed actor / target steps among them; the statistics of the last"""
+        st = _ffi.TD3Stats()
+        check(self._lib.adc_engine_td3_update(self._h, int(updates), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _ffi.TD3Stats._fields_}
+
+    def td3_param_counts(self):
+        p, q = C.c_int64(0), C.c_int64(0)
+        check(self._lib.adc_engine_td3_param_counts(self._h, C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    TD3_STATE = ("theta", "psi", "theta_target", "psi_target", "m_theta", "v_theta", "m_psi", "v_psi")
+
+    def td3_state(self, state=None):
+        """get (no argument): dict of theta, theta_target, m_theta, v_theta [P], psi, psi_target, m_psi, v_psi [2 Qc] float32,
+        updates and actor_steps; set: such a dict - with the ring (td3_buffer / td3_buffer_load) the run continues bit for bit"""
+        P, Q = self.td3_param_counts()
+        size = lambda k: Q if "psi" in k else P
+        if state is None:
+            st = {k: np.zeros(size(k), np.float32) for k in self.TD3_STATE}
+            u, a = C.c_int64(0), C.c_int64(0)
+            check(self._lib.adc_engine_td3_state_get(self._h, *(st[k].ctypes.data for k in self.TD3_STATE), C.byref(u), C.byref(a)))
+            st["updates"], st["actor_steps"] = u.value, a.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.TD3_STATE]
+        if any(a.shape != (size(k),) for k, a in zip(self.TD3_STATE, arr)):
+            raise ValueError(f"td3_state: the actor's vectors have {P} entries, the critics' {Q}")
+        check(self._lib.adc_engine_td3_state_set(self._h, *(a.ctypes.data for a in arr), int(state["updates"]), int(state["actor_steps"])))
 
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))

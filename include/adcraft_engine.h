@@ -629,6 +629,86 @@ int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats *stats);
 int adc_engine_pg_state_get(adc_engine *e, float *theta_q, float *m_q, float *v_q, int64_t *steps);
 int adc_engine_pg_state_set(adc_engine *e, const float *theta_q, const float *m_q, const float *v_q, int64_t steps);
 
+/* ---- off-policy training on the device: a replay ring, twin critics, TD3 (the law is csrc/adc_td3.h) --------------------------
+ * The actor is the policy network given to adc_engine_mlp_init with the free log_std[A] head; its mean is TD3's deterministic
+ * action, and the stochastic act mean + exp(log_std) * z is the exploration (set log_std = log(sigma); TD3 never trains it; a
+ * value network is ignored).  Two Q networks on [x | an] - x the recorded network input, an the action, normalised when
+ * adc_engine_td3_set_action_norm uploaded a shift and a scale - and target copies of the actor and of both critics live on the
+ * device.  adc_engine_td3_store appends the record's days not yet stored to a ring of `capacity` transitions (x, a, r, done, x'),
+ * adc_engine_td3_update takes critic updates on counter-addressed minibatches, every policy_delay-th followed by the actor's
+ * step through critic 1's input gradient and the Polyak step of the targets; the new actor is written into the device's policy
+ * layers (adc_engine_mlp_act, the next recorded day and adc_engine_mlp_get_params see it at once).  No transition leaves the
+ * device.  Training draws from its own key alone: the envs' and the agents' streams do not move.  Flat orders: theta[P] as
+ * adc_engine_mlp_get_params; psi[2 Qc] critic 1's layers (each W input-major, then b), then critic 2's
+ * (adc_engine_td3_param_counts).  theta starts as the device's policy at adc_engine_td3_init; later adc_engine_mlp_set_layer
+ * calls do not reach it (adc_engine_td3_state_set does).  The trainer does not survive adc_engine_mlp_init or
+ * adc_engine_rollout_enable.  Refused (ADC_ESTATE / ADC_EINVAL, the engine stays usable): before adc_engine_mlp_init and its
+ * uploads, a two-headed policy, without a record or without ADC_ROLLOUT_OBS, with a population active, with a policy-gradient
+ * trainer alive (and adc_engine_pg_init with this one alive), a store with no unstored day or after the envs were stepped or
+ * reset outside the record, an update before every critic layer was uploaded or with an empty ring. */
+enum adc_td3_optimiser { ADC_TD3_ADAM = 0, ADC_TD3_SGD = 1 };
+typedef struct adc_td3_config {
+    uint32_t struct_size;          /* sizeof(adc_td3_config) */
+    float gamma;                   /* in [0, 1] */
+    float tau;                     /* in (0, 1]: the targets' Polyak rate */
+    int32_t policy_delay;          /* >= 1: critic updates per actor step */
+    float target_noise;            /* >= 0: the smoothing noise's standard deviation */
+    float target_noise_clip;       /* >= 0 */
+    float action_lo, action_hi;    /* hi > lo: the target action is clamped to [lo, hi] */
+    float reward_scale;            /* finite, != 0 */
+    int32_t batch_size;            /* 1 .. 2^20 */
+    int32_t capacity;              /* 1 .. 2^30 transitions */
+    int32_t n_critic_layers;       /* 1..4 */
+    int32_t critic_widths[4];      /* outputs of each critic layer; hidden ones <= 256, the last is 1 */
+    float actor_lr, critic_lr;     /* >= 0 */
+    float beta1, beta2, eps;       /* Adam: 0 <= beta < 1, eps > 0 */
+    int32_t optimiser;             /* adc_td3_optimiser */
+    float max_grad_norm;           /* > 0: clip each gradient's global norm; 0: off */
+    uint64_t seed;                 /* of the batches and the target noise; 0: the engine's seed */
+} adc_td3_config;
+typedef struct adc_td3_stats {
+    int64_t updates;               /* critic updates taken so far */
+    int64_t actor_steps;           /* actor (and target) steps taken so far */
+    int64_t buffer_size;           /* transitions in the ring */
+    int64_t samples;               /* batch elements of an update */
+    double critic_loss;            /* of the call's last update: the sum of the two critics' mean 0.5 (Q - y)^2 */
+    double q1_mean, q2_mean, y_mean;
+    double actor_loss;             /* -mean Q1(x, mu(x)) of the call's last actor step (0 when it took none) */
+    double critic_grad_norm;       /* before the clip */
+    double actor_grad_norm;        /* of the call's last actor step, before the clip (0 when it took none) */
+} adc_td3_stats;
+int adc_engine_td3_init(adc_engine *e, const adc_td3_config *cfg);
+/* one Linear layer of critic 0 or 1: weights_in_out [n_in][n_out] row-major, bias [n_out].  The targets do not follow until
+ * adc_engine_td3_sync_targets */
+int adc_engine_td3_set_critic_layer(adc_engine *e, int32_t critic, int32_t layer, const float *weights_in_out, const float *bias_out);
+/* an[a] = (action[a] - shift_a[a]) * scale_a[a] for the critics' action inputs; without this call an = action */
+int adc_engine_td3_set_action_norm(adc_engine *e, const float *shift_a, const float *scale_a);
+/* the target actor and the target critics become copies of the actor and the critics */
+int adc_engine_td3_sync_targets(adc_engine *e);
+/* the record's days not yet stored, into the ring; *stored (may be NULL): the transitions appended */
+int adc_engine_td3_store(adc_engine *e, int64_t *stored);
+int adc_engine_td3_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity);
+/* `count` slots from `slot` on (inside [0, size)): x [count][D], a [count][A], r [count], done [count] (bytes), x2 [count][D]; any
+ * pointer may be NULL */
+int adc_engine_td3_buffer_fetch(adc_engine *e, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done, float *x2);
+/* the same arrays into the slots from `slot` on (inside [0, capacity)), then written = `written` (>= slot + count: the ring then
+ * holds min(written, capacity) transitions): a resumed run, or a known buffer */
+int adc_engine_td3_buffer_load(adc_engine *e, int64_t slot, int64_t count, const float *x, const float *a, const float *r, const uint8_t *done,
+                               const float *x2, int64_t written);
+/* the ring slots update number `update` reads at the ring's current size: idx_b [batch_size] (adc_engine_td3_batch_size) */
+int adc_engine_td3_batch_size(adc_engine *e, int32_t *batch_size);
+int adc_engine_td3_batch_indices(adc_engine *e, int64_t update, int32_t *idx_b);
+/* `updates` >= 1 critic updates (and the actor steps that fall among them); stats may be NULL */
+int adc_engine_td3_update(adc_engine *e, int32_t updates, adc_td3_stats *stats);
+int adc_engine_td3_param_counts(adc_engine *e, int64_t *actor_p, int64_t *critics_2qc);
+/* theta, target theta [P]; psi, target psi [2 Qc]; the Adam moments of theta [P] and of psi [2 Qc]; the counters: with the ring
+ * (adc_engine_td3_buffer_fetch / _load) a resumed run continues bit for bit (get: any pointer may be NULL) */
+int adc_engine_td3_state_get(adc_engine *e, float *theta_p, float *psi_q, float *theta_target_p, float *psi_target_q, float *m_theta_p,
+                             float *v_theta_p, float *m_psi_q, float *v_psi_q, int64_t *updates, int64_t *actor_steps);
+int adc_engine_td3_state_set(adc_engine *e, const float *theta_p, const float *psi_q, const float *theta_target_p, const float *psi_target_q,
+                             const float *m_theta_p, const float *v_theta_p, const float *m_psi_q, const float *v_psi_q, int64_t updates,
+                             int64_t actor_steps);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be
@@ -733,6 +813,25 @@ int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_
                      const float *value_old_s, float *grad_q, double *sums10, adc_pg_stats *stats);
 int adc_pg_step_host(const adc_pg_config *cfg, int64_t n_params, int64_t steps_taken, const float *grad_q, float *theta_q, float *m_q,
                      float *v_q);
+/* off-policy training on the host: the same code as the device's (adc_td3.h).  `seed` is the effective seed (the configuration's,
+ * or the engine's when that is 0).  The batch arrays hold the gathered elements in order: x_bd / x2_bd [count][D], a_ba [count][A].
+ * shift_a / scale_a: the action normalisation, both NULL for none.  target: y_b [count] from the target actor theta_target_p and
+ * the target critics psi_target_q.  critic_grad: grad_q [2 Qc] and sums6 (may be NULL) = the chunked sums of the two loss pieces,
+ * Q1, Q2, y and of grad^2.  actor_grad: grad_p [P] and sums2 (may be NULL) = the chunked sums of Q1(x, mu(x)) and of grad^2.  The
+ * optimiser step is adc_pg_step_host. */
+int adc_td3_config_check(const adc_td3_config *cfg, const char **message);
+int adc_td3_param_counts_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, int64_t *actor_p, int64_t *critic_qc);
+int adc_td3_batch_indices_host(uint64_t seed, int64_t update, int64_t size, int32_t count, int32_t *idx_b);
+int adc_td3_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
+                        const float *theta_target_p, const float *psi_target_q, const float *shift_a, const float *scale_a, int32_t count,
+                        const float *x2_bd, const float *r_b, const uint8_t *done_b, float *y_b);
+int adc_td3_critic_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *psi_q,
+                             const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, const float *a_ba, const float *y_b,
+                             float *grad_q, double *sums6);
+int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p,
+                            const float *psi_q, const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p,
+                            double *sums2);
+int adc_td3_polyak_host(float tau, int64_t n, const float *param_n, float *target_n);
 /* the checks adc_engine_mlp_init makes on a configuration for num_keywords keywords; *message (may be NULL) names the failure */
 int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const char **message);
 /* the law's own tanh (fn 0) and exp (fn 1) at one float32, and a sweep over every float32 in [lo, hi] against the host's float64

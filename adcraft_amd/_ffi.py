@@ -242,6 +242,10 @@ def lib():
         "adc_engine_mlp_param_count": ([vp, C.POINTER(i64)], C.c_int),
         "adc_engine_mlp_get_params": ([vp, vp], C.c_int),
         "adc_engine_mlp_get_member_params": ([vp, i32, vp], C.c_int),
+        "adc_engine_mlp_learners": ([vp, i32], C.c_int),
+        "adc_engine_mlp_set_learner_layer": ([vp, i32, i32, i32, vp, vp], C.c_int),
+        "adc_engine_mlp_set_learner_log_std": ([vp, i32, vp], C.c_int),
+        "adc_engine_mlp_get_learner_params": ([vp, i32, vp], C.c_int),
         "adc_engine_es_init": ([vp, C.POINTER(ESConfig)], C.c_int),
         "adc_engine_es_perturb": ([vp], C.c_int),
         "adc_engine_es_fitness": ([vp, vp], C.c_int),
@@ -259,6 +263,16 @@ def lib():
         "adc_engine_pg_update": ([vp, i32, C.POINTER(PGStats)], C.c_int),
         "adc_engine_pg_state_get": ([vp, vp, vp, vp, C.POINTER(i64)], C.c_int),
         "adc_engine_pg_state_set": ([vp, vp, vp, vp, i64], C.c_int),
+        "adc_pg_pop_config_check": ([C.POINTER(PGConfig), i32, i32, i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_pg_pop_init": ([vp, C.POINTER(PGConfig), i32], C.c_int),
+        "adc_engine_pg_pop_advantages": ([vp], C.c_int),
+        "adc_engine_pg_pop_advantages_fetch": ([vp, vp, vp], C.c_int),
+        "adc_engine_pg_pop_minibatch": ([vp, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_pg_pop_update": ([vp, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_pg_pop_state_get": ([vp, i32, vp, vp, vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_pg_pop_state_set": ([vp, i32, vp, vp, vp, i64], C.c_int),
+        "adc_engine_pg_pop_set_config": ([vp, i32, C.POINTER(PGConfig)], C.c_int),
+        "adc_engine_pg_pop_copy": ([vp, i32, i32], C.c_int),
         "adc_pg_config_check": ([C.POINTER(PGConfig), C.POINTER(C.c_char_p)], C.c_int),
         "adc_pg_gae_host": ([C.POINTER(PGConfig), i32, i32, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "adc_pg_param_count_host": ([C.POINTER(MLPConfig), i32, C.POINTER(i64)], C.c_int),

@@ -92,4 +92,73 @@ class PGTrainer:
         return self.engine.pg_state(state)
 
 
-__all__ = ["PGTrainer", "ppo", "a2c", "flat_params", "policy_from_flat"]
+class PGPopulationTrainer:
+    """M independent PPO / A2C learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its
+    own policy network, value network, log_std, optimiser state and hyperparameters, and every launch of an update covers all
+    members (StepEngine.pg_pop_*).  What a member computes is bit for bit what PGTrainer computes on an engine of its n envs.
+
+    engine: a StepEngine that has been reset; policies: one MLPPolicy (every member starts from it) or M of equal shape - M is
+    then the number of configs, or of policies; configs: one dict of ppo() / a2c() kind shared by all members or M of them;
+    `epochs` and `minibatches` (of a member's envs) must be equal in all of them.  agent_seeds: [N] as PGTrainer's."""
+
+    def __init__(self, engine, policies, horizon, configs, agent_seeds=None):
+        policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
+        configs = [configs] if isinstance(configs, dict) else list(configs)
+        if not policies or not configs:
+            raise ValueError("PGPopulationTrainer: at least one policy and one configuration")
+        members = max(len(policies), len(configs))
+        if len(policies) not in (1, members) or len(configs) not in (1, members):
+            raise ValueError(f"PGPopulationTrainer: {len(policies)} policies and {len(configs)} configurations: each is one (shared) or one per member")
+        if any(p.shapes() != policies[0].shapes() for p in policies):
+            raise ValueError("PGPopulationTrainer: the members' policies must have equal shapes (layers, value layers, free log_std, normalisation)")
+        for p in policies[1:]:
+            if p.shift is not None and not (np.array_equal(p.shift, policies[0].shift) and np.array_equal(p.scale, policies[0].scale)):
+                raise ValueError("PGPopulationTrainer: the normalisation vectors are shared by all members: the policies' must be equal")
+        cfgs = [ppo(**c) for c in configs]
+        self.epochs, minibatches = int(cfgs[0].pop("epochs")), int(cfgs[0].pop("minibatches"))
+        for c in cfgs[1:]:
+            if (int(c.pop("epochs")), int(c.pop("minibatches"))) != (self.epochs, minibatches):
+                raise ValueError("PGPopulationTrainer: epochs and minibatches must be equal in all members' configurations (the members move in lock-step)")
+        if members < 1 or engine.num_envs % members:
+            raise ValueError("the number of members must divide the engine's envs")
+        n = engine.num_envs // members
+        if minibatches < 1 or n % minibatches:
+            raise ValueError("minibatches must divide the envs of a member")
+        self.engine, self.members, self.horizon = engine, members, int(horizon)
+        self._templates = policies if len(policies) == members else policies * members
+        self.configs = [dict(c, minibatch_envs=n // minibatches) for c in cfgs]
+        engine.mlp_init(policies[0], seeds=agent_seeds, deterministic=False)
+        engine.mlp_learners(members)
+        if len(policies) > 1:
+            for m, pol in enumerate(policies):
+                engine.mlp_set_learner(m, pol)
+        engine.rollout_enable(self.horizon, obs=True)
+        engine.pg_pop_init(self.configs)
+        self.history = []
+
+    def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
+        """(reset), `days` (default: the horizon) recorded days of run_days("mlp"), the update; returns the M members' statistics"""
+        e = self.engine
+        if reset:
+            e.reset(seeds=reset_seeds)
+        e.rollout_reset()
+        e.run_days("mlp", self.horizon if days is None else int(days), budget)
+        stats = e.pg_pop_update(self.epochs)
+        self.history.append(stats)
+        return stats
+
+    def policy(self, member):
+        """an MLPPolicy holding one member's trained policy layers, value layers and log_std"""
+        return policy_from_flat(self._templates[member], self.engine.pg_pop_state(member)["theta"])
+
+    def returns(self):
+        """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days (from the
+        record's reward array alone)"""
+        r = self.engine.rollout_fetch()["reward"].astype(np.float64).sum(axis=0)
+        return r.reshape(self.members, -1).mean(axis=1)
+
+    def state(self, member, state=None):
+        return self.engine.pg_pop_state(member, state)
+
+
+__all__ = ["PGPopulationTrainer", "PGTrainer", "ppo", "a2c", "flat_params", "policy_from_flat"]

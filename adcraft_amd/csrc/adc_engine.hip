@@ -48,10 +48,11 @@
 //        (k_interp_step); the per-keyword act itself is adc_interp.h, shared with the host twin.
 //   parts/kernel_mlp_policy.inc   the learned agent: a fully connected policy (and value) network per env, or per member of a population.
 //   parts/kernel_es.inc           policy populations and the evolution strategy: perturbation, returns, gradient estimate + Adam (adc_es.h).
-//   parts/kernel_pg.inc           policy-gradient training: GAE, the networks' backward pass, the weight gradient, the step (adc_pg.h).
+//   parts/kernel_pg.inc           policy-gradient training: GAE, the networks' backward pass, the weight gradient, the step (adc_pg.h);
+//        the k_pg_pop_* twins run the same bodies for all members of a learner population in one launch.
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
-//   parts/pg_api.inc              the entry points of policy-gradient training.
+//   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //
 // No CPU path exists in this library.

@@ -478,6 +478,28 @@ ADC_EXPORT int adc_pg_config_check(const adc_pg_config *cfg, const char **messag
     return msg ? ADC_EINVAL : ADC_OK;
 }
 
+// the configurations of a learner population: `count` = 1 (shared by all members) or `members` of them
+ADC_EXPORT int adc_pg_pop_config_check(const adc_pg_config *cfgs, int32_t count, int32_t num_envs, int32_t members, const char **message)
+{
+    const char *msg = nullptr;
+    if (!cfgs) msg = "adc_pg_config array is NULL";
+    else if (num_envs < 1 || members < 1 || num_envs % members != 0) msg = "members must be positive and divide num_envs";
+    else if (count != 1 && count != members) msg = "count: 1 (one configuration shared by all members) or the number of members";
+    else {
+        const int n = num_envs / members;
+        for (int i = 0; i < count && !msg; ++i) {
+            if (adc_pg_config_check(cfgs + i, &msg) != ADC_OK) break;
+            if (cfgs[i].minibatch_envs != cfgs[0].minibatch_envs) msg = "minibatch_envs must be equal in all members' configurations (their minibatches run in the same launches)";
+        }
+        if (!msg) {
+            const int mb = cfgs[0].minibatch_envs == 0 ? n : cfgs[0].minibatch_envs;
+            if (mb > n || n % mb != 0) msg = "minibatch_envs must divide the envs of a member (num_envs / members)";
+        }
+    }
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
 ADC_EXPORT int adc_pg_gae_host(const adc_pg_config *cfg, int32_t days, int32_t num_envs, const float *reward_tn, const uint8_t *terminated_tn,
                                const uint8_t *truncated_tn, const float *value_tn, const float *bootstrap_n, float *adv_tn, float *ret_tn)
 {

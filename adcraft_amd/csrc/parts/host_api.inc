@@ -94,6 +94,14 @@ struct adc_engine {
     float *es_theta = nullptr, *es_m = nullptr, *es_v = nullptr, *es_grad = nullptr;     // [P]
     double *es_du = nullptr, *es_return = nullptr;                                        // [M / 2], [N]
     std::vector<void *> es_allocs;
+    // learners (adc_engine_mlp_learners): every member's own policy layers, value layers and log_std in one block, a member's
+    // part lrn_stride floats long; lrn_lay is member 0's stores against the trainer's flat order theta[Q]
+    int lrn_M = 0, lrn_n = 0;           // members; envs of a member
+    float *lrn_block = nullptr, *lrn_flat = nullptr;    // [M][lrn_stride]; [Q] staging of one flat parameter vector
+    size_t lrn_stride = 0;
+    MlpLearner *lrn_tab = nullptr;      // [M] on the device (MlpView::learners)
+    PgLayout lrn_lay{};
+    std::vector<void *> lrn_allocs;
     // the rollout record (adc_engine_rollout_enable): [T][N][...] arrays, ro_t days recorded so far
     int ro_T = 0, ro_t = 0, ro_fields = 0;
     float *ro_action = nullptr, *ro_logp = nullptr, *ro_value = nullptr, *ro_reward = nullptr, *ro_obs = nullptr;
@@ -114,6 +122,15 @@ struct adc_engine {
     double *pg_part = nullptr, *pg_sums = nullptr;                                       // chunk partials; the law's ten sums
     double *pg_gpart = nullptr;                                                          // [chunks][Q] the weight gradient's partials
     std::vector<void *> pg_allocs;
+    // ... and of a learner population (adc_engine_pg_pop_init; it shares the scratch fields above, sized for all members at once:
+    // pg_theta / pg_m / pg_v / pg_grad are [M][Q], pg_acts / pg_deltas / pg_pieces [M][T * minibatch envs][...], pg_sums [M][16])
+    bool have_pg_pop = false;
+    std::vector<adc_pg_config> pgp_cfg;         // [M]
+    std::vector<int64_t> pgp_steps;             // [M]
+    std::vector<PgMember> pgp_mem;              // [M] the host's copy of pgp_dmem
+    std::vector<double> pgp_host_sums;          // [M][16]
+    PgMember *pgp_dmem = nullptr;
+    size_t pgp_part_stride = 0;                 // doubles of chunk partials per member
     // off-policy training over a replay ring filled from the record (adc_engine_td3_init; parts/kernel_td3.inc, parts/td3_api.inc)
     bool have_td3 = false, td3_norm_set = false, td3_gap = false;
     bool td3_critic_set[2][4] = {{false, false, false, false}, {false, false, false, false}};
@@ -818,6 +835,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->curve_allocs) (void)hipFree(p);
     for (void *p : e->mlp_allocs) (void)hipFree(p);
     for (void *p : e->pop_allocs) (void)hipFree(p);
+    for (void *p : e->lrn_allocs) (void)hipFree(p);
     for (void *p : e->es_allocs) (void)hipFree(p);
     for (void *p : e->ro_allocs) (void)hipFree(p);
     for (void *p : e->pg_allocs) (void)hipFree(p);
@@ -2706,12 +2724,16 @@ inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
 void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode, const float *replay_z, float budget_override, float *d_bids,
                        float *d_budget, const MlpRecordSlot &rec, float *value_out)
 {
-    // (two instantiations: without a population the kernel is the single-policy code, untouched by the members' addressing)
-    if (p.member)
-        hipLaunchKernelGGL(k_mlp_policy<true>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+    // (three instantiations: without members the kernel is the single-policy code, untouched by the members' addressing; learners
+    // have no pop_stride)
+    if (p.member && p.pop_stride == 0)
+        hipLaunchKernelGGL(k_mlp_policy<2>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+                           budget_override, d_bids, d_budget, rec, value_out);
+    else if (p.member)
+        hipLaunchKernelGGL(k_mlp_policy<1>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
                            budget_override, d_bids, d_budget, rec, value_out);
     else
-        hipLaunchKernelGGL(k_mlp_policy<false>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+        hipLaunchKernelGGL(k_mlp_policy<0>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
                            budget_override, d_bids, d_budget, rec, value_out);
 }
 int mlp_ready(const adc_engine *e)
@@ -2787,8 +2809,10 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
 void pg_drop(adc_engine *e)
 {
     mlp_free(e, e->pg_allocs);
-    e->have_pg = e->pg_adv_ready = false;
+    e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
     e->pg_steps = 0;
+    e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();
+    e->pgp_dmem = nullptr;
 }
 // ... and so does the off-policy trainer (its ring holds rows of that policy's input and action widths)
 void td3_drop(adc_engine *e)
@@ -2798,6 +2822,15 @@ void td3_drop(adc_engine *e)
     std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));
     e->td3_updates = e->td3_actor_steps = e->td3_written = 0;
     e->td3_stored_t = 0;
+}
+// learners and the population trainer over them go with the policy they belong to (the engine is back to the centre policy)
+void learners_drop(adc_engine *e)
+{
+    if (e->have_pg_pop) pg_drop(e);
+    mlp_free(e, e->lrn_allocs);
+    if (e->lrn_M != 0) { e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; }
+    e->lrn_M = e->lrn_n = 0;
+    e->lrn_block = e->lrn_flat = nullptr; e->lrn_tab = nullptr; e->lrn_stride = 0;
 }
 // a population and the strategy over it go with the policy they belong to
 void population_drop(adc_engine *e)
@@ -2846,6 +2879,7 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
     ENGINE_GUARD(e);
     population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
+    learners_drop(e);
     pg_drop(e);
     td3_drop(e);
     mlp_free(e, e->mlp_allocs);
@@ -3070,7 +3104,7 @@ ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const i
         }
     }
     ENGINE_GUARD(e);
-    if (M == 0) { population_drop(e); return ADC_OK; }
+    if (M == 0) { population_drop(e); return ADC_OK; }      // (learners, if any, stay: there is no population to turn off then)
     // (the new population is allocated before the old one goes: a failure leaves the engine as it was)
     void *block = nullptr, *d_map = nullptr;
     if (hipMalloc(&block, (size_t)M * e->pl.stride * 4) != hipSuccess || hipMalloc(&d_map, (size_t)N * 4) != hipSuccess) {
@@ -3078,6 +3112,7 @@ ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const i
         if (block) (void)hipFree(block);
         return fail(ADC_ENOMEM, "hipMalloc failed (policy population)");
     }
+    learners_drop(e);                   // (the two kinds of members exclude each other)
     population_drop(e);
     e->pop_allocs.push_back(block);
     e->pop_allocs.push_back(d_map);
@@ -3145,6 +3180,154 @@ ADC_EXPORT int adc_engine_mlp_get_member_params(adc_engine *e, int32_t member, f
     if (!flat_p) return fail(ADC_EINVAL, "flat_p is NULL");
     ENGINE_GUARD(e);
     return params_fetch(e, member_store(e, member), flat_p);
+}
+
+// ---- learners: per-member policy layers, value layers and log_std (the population trainer's members; parts/pg_api.inc) ----------
+namespace {
+int learners_ready(const adc_engine *e, int32_t member)
+{
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (e->lrn_M == 0) return fail(ADC_ESTATE, "adc_engine_mlp_learners has not been called");
+    if (member < 0 || member >= e->lrn_M) return fail(ADC_EINVAL, "no such member");
+    return ADC_OK;
+}
+inline unsigned pg_blocks(int Q) { return (unsigned)((Q + kPgBlock - 1) / kPgBlock); }
+}  // namespace
+
+ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    const int N = e->v.N, M = members;
+    if (M < 0 || M > 65535) return fail(ADC_EINVAL, "members: 0 (off) to 65535");
+    if (M > 0 && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs");
+    ENGINE_GUARD(e);
+    if (M == 0) { learners_drop(e); return ADC_OK; }
+    // a member's block: the policy layers, the value layers, log_std, each starting on a 16-byte boundary; the flat order against it
+    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K);
+    size_t offW[2][adc::kMlpMaxLayers] = {}, offb[2][adc::kMlpMaxLayers] = {}, off_ls = 0;       // floats from the member's base
+    PgLayout lay{};
+    size_t off = 0;
+    {
+        int flat = 0, i = 0;
+        for (int net = 0; net < 2; ++net) {
+            const MlpNet &n = net == 0 ? e->mp.pol : e->mp.val;
+            for (int l = 0; l < n.layers; ++l, ++i) {
+                offW[net][l] = off; off += adc::mlp_weight_count(n.n_in[l], n.n_out[l]);
+                offb[net][l] = off; off += ((size_t)n.n_out[l] + 3u) & ~(size_t)3u;
+                lay.flat0[i] = flat; lay.n_in[i] = n.n_in[l]; lay.n_out[i] = n.n_out[l];
+                flat += (n.n_in[l] + 1) * n.n_out[l];
+            }
+        }
+        if (!sh.two_heads) {
+            off_ls = off; off += ((size_t)sh.A + 3u) & ~(size_t)3u;
+            lay.flat0[i] = flat; lay.n_in[i] = 0; lay.n_out[i] = sh.A;
+            flat += sh.A; ++i;
+        }
+        lay.nterms = i; lay.Q = flat;
+    }
+    const size_t stride = off;
+    // (the new members are allocated before the old ones go: a failure leaves the engine as it was)
+    std::vector<void *> fresh;
+    float *block = nullptr, *flat = nullptr;
+    int32_t *d_map = nullptr;
+    MlpLearner *d_tab = nullptr;
+    int rc;
+    if ((rc = mlp_alloc(e, fresh, &block, (size_t)M * stride)) || (rc = mlp_alloc(e, fresh, &flat, (size_t)lay.Q)) ||
+        (rc = mlp_alloc(e, fresh, &d_map, (size_t)N)) || (rc = mlp_alloc(e, fresh, &d_tab, (size_t)M))) {
+        mlp_free(e, fresh);
+        return rc;
+    }
+    population_drop(e);                 // (the two kinds of members exclude each other)
+    learners_drop(e);
+    e->lrn_allocs.swap(fresh);
+    std::vector<MlpLearner> tab((size_t)M);
+    for (size_t m = 0; m < (size_t)M; ++m) {
+        float *base = block + m * stride;
+        tab[m].net[0] = e->mp.pol; tab[m].net[1] = e->mp.val;       // (the shapes; the stores are the member's own)
+        for (int net = 0; net < 2; ++net)
+            for (int l = 0; l < tab[m].net[net].layers; ++l) { tab[m].net[net].W[l] = base + offW[net][l]; tab[m].net[net].b[l] = base + offb[net][l]; }
+        tab[m].log_std = sh.two_heads ? nullptr : base + off_ls;
+    }
+    {
+        int i = 0;
+        for (int net = 0; net < 2; ++net)
+            for (int l = 0; l < tab[0].net[net].layers; ++l, ++i) {
+                lay.W[i] = const_cast<float *>(tab[0].net[net].W[l]); lay.b[i] = const_cast<float *>(tab[0].net[net].b[l]);
+            }
+        if (!sh.two_heads) { lay.W[i] = nullptr; lay.b[i] = const_cast<float *>(tab[0].log_std); }
+    }
+    std::vector<int32_t> map((size_t)N);
+    for (int env = 0; env < N; ++env) map[(size_t)env] = env / (N / M);
+    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), (size_t)M * sizeof(MlpLearner), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(d_map, map.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    // every member starts as the centre: the centre's stores to the flat order, the flat order to every member's stores
+    {
+        PgLayout centre = lay;
+        int i = 0;
+        for (int net = 0; net < 2; ++net) {
+            const MlpNet &n = net == 0 ? e->mp.pol : e->mp.val;
+            for (int l = 0; l < n.layers; ++l, ++i) { centre.W[i] = const_cast<float *>(n.W[l]); centre.b[i] = const_cast<float *>(n.b[l]); }
+        }
+        if (!sh.two_heads) centre.b[i] = const_cast<float *>(e->mp.log_std);
+        hipLaunchKernelGGL(k_pg_params_copy, dim3(pg_blocks(lay.Q)), dim3(kPgBlock), 0, e->stream, centre, flat, 1);
+        hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks(lay.Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, lay, stride, 0, flat, (size_t)0, 0);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));       // (tab and map are the host's until here)
+    e->lrn_M = M; e->lrn_n = N / M;
+    e->lrn_block = block; e->lrn_flat = flat; e->lrn_stride = stride; e->lrn_tab = d_tab; e->lrn_lay = lay;
+    e->mp.member = d_map; e->mp.learners = d_tab; e->mp.pop_stride = 0;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_learner_layer(adc_engine *e, int32_t member, int32_t network, int32_t layer, const float *weights_in_out,
+                                                const float *bias_out)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = learners_ready(e, member)) return rc;
+    if (network != 0 && network != 1) return fail(ADC_EINVAL, "network: 0 (policy) or 1 (value)");
+    const MlpNet &n = network == 0 ? e->mp.pol : e->mp.val;
+    if (layer < 0 || layer >= n.layers) return fail(ADC_EINVAL, "no such layer");
+    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
+    ENGINE_GUARD(e);
+    const int n_in = n.n_in[layer], n_out = n.n_out[layer], term = (network == 0 ? 0 : e->mp.pol.layers) + layer;
+    std::vector<float> w(adc::mlp_weight_count(n_in, n_out), 0.0f);
+    for (int j = 0; j < n_in; ++j)
+        for (int h = 0; h < n_out; ++h) w[adc::mlp_weight_index(j, h, n_out)] = weights_in_out[(size_t)j * n_out + h];
+    const size_t base = (size_t)member * e->lrn_stride;
+    HIP_TRY(hipMemcpyAsync(e->lrn_lay.W[term] + base, w.data(), w.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->lrn_lay.b[term] + base, bias_out, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_set_learner_log_std(adc_engine *e, int32_t member, const float *log_std_a)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = learners_ready(e, member)) return rc;
+    if (e->mp.two_heads) return fail(ADC_EINVAL, "a two-headed policy has no log_std vector");
+    if (!log_std_a) return fail(ADC_EINVAL, "log_std is NULL");
+    ENGINE_GUARD(e);
+    float *dst = e->lrn_lay.b[e->lrn_lay.nterms - 1] + (size_t)member * e->lrn_stride;
+    HIP_TRY(hipMemcpyAsync(dst, log_std_a, (size_t)e->mp.A * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_get_learner_params(adc_engine *e, int32_t member, float *theta_q)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = learners_ready(e, member)) return rc;
+    if (!theta_q) return fail(ADC_EINVAL, "theta_q is NULL");
+    ENGINE_GUARD(e);
+    const int Q = e->lrn_lay.Q;
+    hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks(Q), 1u), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, (int)member, e->lrn_flat,
+                       (size_t)0, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(theta_q, e->lrn_flat, (size_t)Q * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
 }
 
 // ---- the evolution strategy over a population (the law is csrc/adc_es.h) ---------------------------------------------------

@@ -17,6 +17,12 @@ struct MlpNet {
     int layers;                             // 0: no such network
 };
 
+// one learner's own stores (adc_engine_mlp_learners): every layer chain-major as above
+struct MlpLearner {
+    MlpNet net[2];                          // [0] policy, [1] value
+    const float *log_std;                   // [A] (free head; null with two heads)
+};
+
 struct MlpView {
     MlpNet pol, val;
     const float *shift, *scale;             // [D] or null: no normalisation
@@ -30,8 +36,13 @@ struct MlpView {
     float *logp, *value;                    // [N]
     // a population (adc_engine_mlp_population): env -> member, and the members' policy layers at pop + member * pop_stride
     // (+ pop_offW[l] / pop_offb[l]), each layer in the layout of W / b above.  member == null: every env runs `pol`.
+    // Learners (adc_engine_mlp_learners): env -> member as well, and `learners[member]` names the member's own policy layers,
+    // value layers and log_std (pop_stride is 0 then: that is how the host tells the two kinds apart).
     const int32_t *member;                  // [N]
-    const float *pop;
+    union {
+        const float *pop;
+        const MlpLearner *learners;       // [M], on the device
+    };
     size_t pop_stride;                      // floats
     uint32_t pop_offW[adc::kMlpMaxLayers], pop_offb[adc::kMlpMaxLayers];
 };
@@ -113,8 +124,10 @@ __device__ __forceinline__ void mlp_network(const MlpNet &net, const MlpView &p,
 
 // mode 0: act (policy and value networks, sample, actions, record);  mode 1: the value network alone into value_out (the
 // bootstrap value of the observation the last step left) - no draw, no tick, nothing else written.
-// kPop: the env's policy layers are its member's (two instantiations, so that the single-policy kernel is the code it was)
-template <bool kPop>
+// kMembers 0: every env runs `pol`;  1: the env's policy layers are its member's (a population);  2: the policy layers, the
+// value layers and log_std are the env's learner's.  (Three instantiations, so that the single-policy kernel and the
+// population's are the code they were.)
+template <int kMembers>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int mode, const float *__restrict__ replay_z,
                                                           float budget_override, float *__restrict__ bids, float *__restrict__ budgets,
                                                           MlpRecordSlot rec, float *__restrict__ value_out)
@@ -137,9 +150,11 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
     }
     __syncthreads();
     float *out = mlp_lds + D + 2 * adc::kMlpMaxWidth;
+    const MlpLearner *lm = kMembers == 2 ? p.learners + p.member[env] : nullptr;
     if (p.val.layers > 0) {
         // (the value network's single output lands in the first float of `out`, which the policy network overwrites afterwards)
-        mlp_network<false>(p.val, p, nullptr, p.activation, mlp_lds, D, out);
+        if (kMembers == 2) mlp_network<false>(lm->net[1], p, nullptr, p.activation, mlp_lds, D, out);
+        else mlp_network<false>(p.val, p, nullptr, p.activation, mlp_lds, D, out);
         if (tid == 0) s_value = out[0];
         __syncthreads();
     } else if (tid == 0) s_value = 0.0f;
@@ -147,13 +162,14 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         if (tid == 0) value_out[env] = s_value;
         return;
     }
-    mlp_network<kPop>(p.pol, p, kPop ? p.pop + (size_t)p.member[env] * p.pop_stride : nullptr, p.activation, mlp_lds, D, out);
+    if (kMembers == 2) mlp_network<false>(lm->net[0], p, nullptr, p.activation, mlp_lds, D, out);
+    else mlp_network<kMembers == 1>(p.pol, p, kMembers == 1 ? p.pop + (size_t)p.member[env] * p.pop_stride : nullptr, p.activation, mlp_lds, D, out);
     // heads, sample, the env's action; the log-probability's terms replace the means in LDS
     const uint64_t key = p.key[env];
     const uint32_t tick = p.tick[env];
     for (int a = tid; a < A; a += kMlpBlock) {
         const float mean = out[a];
-        const float ls = adc::mlp_clamp_log_std(p.two_heads ? out[A + a] : p.log_std[a], p.clamp, p.ls_lo, p.ls_hi);
+        const float ls = adc::mlp_clamp_log_std(p.two_heads ? out[A + a] : (kMembers == 2 ? lm->log_std : p.log_std)[a], p.clamp, p.ls_lo, p.ls_hi);
         float z = 0.0f;
         if (!p.deterministic) z = replay_z ? replay_z[(size_t)env * A + a] : adc::mlp_normal(key, tick, a);
         const float act = adc::mlp_sample(mean, ls, z, p.deterministic);

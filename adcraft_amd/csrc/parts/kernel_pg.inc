@@ -12,6 +12,12 @@
 // row j = n_in with x = 1) and ONE chunk of 1024 samples, stages 64 samples' 16 inputs and 16 deltas in LDS at a time, and every
 // lane carries its parameter's float64 chain - one fused multiply-add per sample, exact products - and writes the chunk's
 // partial; k_pg_grad_join adds a parameter's partials in chunk order.  No atomics; all stores are plain vector stores.
+//
+// Learner populations (adc_engine_pg_pop_*).  Every kernel has a k_pg_pop_* twin whose launch covers all M members: the member is
+// one more grid dimension, what is a member's own (its layers, its loss constants, its step) is read from the device tables
+// MlpLearner[M] / PgMember[M], and the member's samples, scratch rows, partials and parameters are the solo kernel's with a base
+// moved to the member's block.  The bodies are shared (pg_sample_body, pg_wgrad_body, ...): a member runs the solo code on its own
+// envs [m n, (m + 1) n) in its own order, so its bits are a solo engine's, whatever M and the other members are.
 struct PgView {
     adc::PgShape sh;
     adc::PgLoss loss;
@@ -37,6 +43,17 @@ struct PgLayout {
     int nterms, Q;
     int flat0[adc::kPgMaxTerms], n_in[adc::kPgMaxTerms], n_out[adc::kPgMaxTerms];
     float *W[adc::kPgMaxTerms], *b[adc::kPgMaxTerms];
+};
+
+// what is a member's own in a learner population, indexed by member on the device (its layers are MlpLearner's)
+struct PgMember {
+    adc::PgLoss loss;
+    float gamma, gl, reward_scale;          // GAE; gl = gamma * lambda (the host's float32 product, as the solo launch gets it)
+    int normalize;
+    double mean, sd;                        // the advantage normalisation's moments (set between its passes)
+    int clip;                               // the next update: clip on / off, the clip scale, the step's constants
+    float scale;
+    adc::EsStep step;
 };
 
 constexpr int kPgBlock = 256;
@@ -66,6 +83,18 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_params_copy(PgLayout L, float *
     if (to_flat) flat[p] = *slot;
     else *slot = flat[p];
 }
+// the same for the members member0 + blockIdx.y of a learner population: L is member 0's stores, a member's are `stride` floats
+// further each; the member's flat vector is flat + blockIdx.y * flat_stride (flat_stride 0: one vector for all of them)
+__global__ __launch_bounds__(kPgBlock) void k_pg_pop_params_copy(PgLayout L, size_t stride, int member0, float *__restrict__ flat, size_t flat_stride,
+                                                                 int to_flat)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= L.Q) return;
+    float *slot = pg_param_slot(L, p) + (size_t)(member0 + (int)blockIdx.y) * stride;
+    float *f = flat + (size_t)blockIdx.y * flat_stride + p;
+    if (to_flat) *f = *slot;
+    else *slot = *f;
+}
 
 // one lane per env, walking the record backwards
 __global__ void k_pg_gae(int N, int T, const float *__restrict__ reward, const uint8_t *__restrict__ term, const uint8_t *__restrict__ trunc,
@@ -74,6 +103,26 @@ __global__ void k_pg_gae(int N, int T, const float *__restrict__ reward, const u
 {
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= N) return;
+    float adv = 0.0f, next = boot[env];
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t i = (size_t)t * (size_t)N + (size_t)env;
+        const float v = value[i];
+        const float a = adc::pg_gae_day(reward[i], reward_scale, term[i] | trunc[i], v, next, gamma, gl, adv);
+        adv_out[i] = a;
+        ret_out[i] = a + v;
+        next = v;
+    }
+}
+
+// ... with the env's member's gamma, gamma * lambda and reward_scale (envs_per_member envs each, in env order)
+__global__ void k_pg_pop_gae(int N, int T, int envs_per_member, const PgMember *__restrict__ mem, const float *__restrict__ reward,
+                             const uint8_t *__restrict__ term, const uint8_t *__restrict__ trunc, const float *__restrict__ value,
+                             const float *__restrict__ boot, float *__restrict__ adv_out, float *__restrict__ ret_out)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N) return;
+    const PgMember &c = mem[env / envs_per_member];
+    const float gamma = c.gamma, gl = c.gl, reward_scale = c.reward_scale;
     float adv = 0.0f, next = boot[env];
     for (int t = T - 1; t >= 0; --t) {
         const size_t i = (size_t)t * (size_t)N + (size_t)env;
@@ -118,6 +167,47 @@ __global__ void k_pg_normalize(float *__restrict__ adv, long long n, double mean
     if (i < n) adv[i] = adc::pg_normalized(adv[i], mean, std);
 }
 
+// the chunked sums of every member at once (blockIdx.y = member): term i < n of the member is row
+// member * mstep + (inner ? (i / inner) * outer + i % inner : i) of src - the member's own order, whatever lies between its rows
+// (inner = its envs, outer = N for the [T][N] advantages: i = t * n + local env).  mode as k_pg_chunk_sums, the mean the member's.
+__global__ void k_pg_pop_chunk_sums(const float *__restrict__ src, int n, int inner, int outer, size_t mstep, int stride, int cols, int mode,
+                                    const PgMember *__restrict__ mem, double *__restrict__ part, size_t part_stride)
+{
+    const int lane = blockIdx.x * blockDim.x + threadIdx.x, member = blockIdx.y;
+    const int chunks = (n + adc::kPgChunk - 1) / adc::kPgChunk;
+    if (lane >= chunks * cols) return;
+    const int chunk = lane / cols, col = lane % cols;
+    const int i0 = chunk * adc::kPgChunk, i1 = i0 + adc::kPgChunk < n ? i0 + adc::kPgChunk : n;
+    const double mean = mode == 1 ? mem[member].mean : 0.0;
+    const size_t base = (size_t)member * mstep;
+    double acc = 0.0;
+    for (int i = i0; i < i1; ++i) {
+        const size_t row = base + (inner ? (size_t)(i / inner) * (size_t)outer + (size_t)(i % inner) : (size_t)i);
+        const float x = src[row * (size_t)stride + (size_t)col];
+        acc = mode == 0 ? acc + (double)x : mode == 1 ? adc::pg_chain_sqdev(acc, x, mean) : adc::pg_chain_mac(acc, x, x);
+    }
+    part[(size_t)member * part_stride + (size_t)lane] = acc;
+}
+// ... joined in chunk order, one workgroup per member, one lane per column: out[member * out_stride + col]
+__global__ void k_pg_pop_join(const double *__restrict__ part, size_t part_stride, int chunks, int cols, double *__restrict__ out, int out_stride)
+{
+    const int col = threadIdx.x, member = blockIdx.x;
+    if (col >= cols) return;
+    const double *mine = part + (size_t)member * part_stride;
+    double total = 0.0;
+    for (int c = 0; c < chunks; ++c) total = total + mine[(size_t)c * cols + col];
+    out[(size_t)member * out_stride + col] = total;
+}
+
+// one lane per recorded sample t * N + env; the env's member's moments, members that do not normalise left as they are
+__global__ void k_pg_pop_normalize(float *__restrict__ adv, long long n, int N, int envs_per_member, const PgMember *__restrict__ mem)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PgMember &c = mem[(int)(i % N) / envs_per_member];
+    if (c.normalize) adv[i] = adc::pg_normalized(adv[i], c.mean, c.sd);
+}
+
 // the transposed pass of one layer: dnew[j] = act'(y[j]) * sum8(n_out, h -> W[j][h] * dcur[h]) for the n inputs of the layer
 __device__ __forceinline__ void pg_layer_back(const float *__restrict__ W, int n, int n_out, const float *y, const float *dcur, float *dnew,
                                               int activation, float *__restrict__ g_out)
@@ -144,15 +234,16 @@ __device__ __forceinline__ void pg_layer_back(const float *__restrict__ W, int n
     __syncthreads();
 }
 
-// forward, head, loss and backward of sample blockIdx.x = t * B + (env - n0)
-__global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
+// forward, head, loss and backward of sample s = t * B + (env - n0) with the layers `nets`, log_std and the loss constants given;
+// the sample's scratch rows are row `slot` of p.acts / p.deltas / p.pieces
+__device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *nets, const float *log_std, const adc::PgLoss &loss, int n0, size_t s,
+                                               size_t slot)
 {
     extern __shared__ __align__(16) float pg_lds[];
     __shared__ float s_g, s_dv;
     const adc::PgShape &sh = p.sh;
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
-    const size_t s = blockIdx.x;
-    const size_t row = (s / (size_t)p.B) * (size_t)p.N + (size_t)p.n0 + s % (size_t)p.B;
+    const size_t row = (s / (size_t)p.B) * (size_t)p.N + (size_t)n0 + s % (size_t)p.B;
     float *x = pg_lds, *ybase = x + D;
     float *y[2][adc::kMlpMaxLayers];
     {
@@ -164,7 +255,7 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
     float *d0 = ybase, *d1 = d0 + p.maxw, *zs = d1 + p.maxw, *sds = zs + A, *lss = sds + A;
     for (int j = tid; j < D; j += kPgBlock) x[j] = p.obs[row * (size_t)D + j];
     __syncthreads();
-    float *acts = p.acts + s * (size_t)p.na, *deltas = p.deltas + s * (size_t)p.nd;
+    float *acts = p.acts + slot * (size_t)p.na, *deltas = p.deltas + slot * (size_t)p.nd;
     // forward, every layer's activations kept (and the hidden ones written out for the weight gradient)
     {
         int ao = 0;
@@ -173,7 +264,7 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
             for (int l = 0; l < sh.layers[net]; ++l) {
                 const bool last = l + 1 == sh.layers[net];
                 const int n_out = sh.n_out[net][l];
-                mlp_layer(p.net[net].W[l], p.net[net].b[l], adc::pg_n_in(sh, net, l), n_out, in, y[net][l], last ? -1 : sh.activation);
+                mlp_layer(nets[net].W[l], nets[net].b[l], adc::pg_n_in(sh, net, l), n_out, in, y[net][l], last ? -1 : sh.activation);
                 if (!last) {
                     for (int h = tid; h < n_out; h += kPgBlock) acts[ao + h] = y[net][l][h];
                     ao += n_out;
@@ -185,7 +276,7 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
     // head: z, sd, ls of every component; the log-probability's terms in d0
     const float *o = y[0][sh.layers[0] - 1];
     for (int a = tid; a < A; a += kPgBlock) {
-        const float raw = sh.two_heads ? o[A + a] : p.log_std[a];
+        const float raw = sh.two_heads ? o[A + a] : log_std[a];
         const float ls = adc::mlp_clamp_log_std(raw, sh.clamp, sh.ls_lo, sh.ls_hi);
         const float sd = adc::mlp_exp(ls);
         const float z = adc::pg_z(p.action[row * (size_t)A + a], o[a], sd);
@@ -207,11 +298,11 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
             const float ratio = adc::mlp_exp(logp - logp_old);
             float pol_loss, val_loss;
             int clipped;
-            const float g = adc::pg_surrogate(ratio, p.adv[row], p.loss.eps_clip, pol_loss, clipped);
+            const float g = adc::pg_surrogate(ratio, p.adv[row], loss.eps_clip, pol_loss, clipped);
             const float V = sh.layers[1] ? y[1][sh.layers[1] - 1][0] : 0.0f;
-            const float dv = adc::pg_dvalue(V, ret, p.loss.vf_coef, val_loss);
+            const float dv = adc::pg_dvalue(V, ret, loss.vf_coef, val_loss);
             s_g = g; s_dv = dv;
-            float *pc = p.pieces + s * (size_t)adc::kPgPieces;
+            float *pc = p.pieces + slot * (size_t)adc::kPgPieces;
             pc[adc::kPgPolLoss] = pol_loss; pc[adc::kPgValLoss] = val_loss; pc[adc::kPgEntropy] = entropy; pc[adc::kPgKl] = logp_old - logp;
             pc[adc::kPgClipped] = clipped ? 1.0f : 0.0f; pc[adc::kPgRet] = ret; pc[adc::kPgErr] = ret - p.value[row]; pc[7] = 0.0f;
         }
@@ -227,9 +318,9 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
         const int L = sh.layers[0];
         float *gout = deltas + doff[0][L - 1];
         for (int a = tid; a < A; a += kPgBlock) {
-            const float raw = sh.two_heads ? o[A + a] : p.log_std[a];
+            const float raw = sh.two_heads ? o[A + a] : log_std[a];
             const float dm = adc::pg_dmean(g, zs[a], sds[a]);
-            const float dl = adc::pg_dls(g, zs[a], p.loss.ent_coef, adc::pg_clamp_moved(raw, sh.clamp, sh.ls_lo, sh.ls_hi));
+            const float dl = adc::pg_dls(g, zs[a], loss.ent_coef, adc::pg_clamp_moved(raw, sh.clamp, sh.ls_lo, sh.ls_hi));
             d0[a] = dm; gout[a] = dm;
             if (sh.two_heads) { d0[A + a] = dl; gout[A + a] = dl; }
             else deltas[dfree + a] = dl;
@@ -237,7 +328,7 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
         __syncthreads();
         float *dcur = d0, *dnew = d1;
         for (int l = L - 2; l >= 0; --l) {
-            pg_layer_back(p.net[0].W[l + 1], sh.n_out[0][l], sh.n_out[0][l + 1], y[0][l], dcur, dnew, sh.activation, deltas + doff[0][l]);
+            pg_layer_back(nets[0].W[l + 1], sh.n_out[0][l], sh.n_out[0][l + 1], y[0][l], dcur, dnew, sh.activation, deltas + doff[0][l]);
             float *t = dcur; dcur = dnew; dnew = t;
         }
     }
@@ -247,17 +338,31 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
         __syncthreads();
         float *dcur = d0, *dnew = d1;
         for (int l = L - 2; l >= 0; --l) {
-            pg_layer_back(p.net[1].W[l + 1], sh.n_out[1][l], sh.n_out[1][l + 1], y[1][l], dcur, dnew, sh.activation, deltas + doff[1][l]);
+            pg_layer_back(nets[1].W[l + 1], sh.n_out[1][l], sh.n_out[1][l + 1], y[1][l], dcur, dnew, sh.activation, deltas + doff[1][l]);
             float *t = dcur; dcur = dnew; dnew = t;
         }
     }
 }
 
+__global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
+{
+    pg_sample_body(p, p.net, p.log_std, p.loss, p.n0, blockIdx.x, blockIdx.x);
+}
+// sample blockIdx.x of member blockIdx.y's minibatch: the member's layers and loss constants, its envs from member * envs_per_member
+// on, its scratch rows from member * gridDim.x on (p.net, p.log_std and p.loss are not read)
+__global__ __launch_bounds__(kPgBlock) void k_pg_pop_sample(PgView p, const MlpLearner *__restrict__ learners, const PgMember *__restrict__ mem,
+                                                            int envs_per_member)
+{
+    const int member = blockIdx.y;
+    pg_sample_body(p, learners[member].net, learners[member].log_std, mem[member].loss, p.n0 + member * envs_per_member, blockIdx.x,
+                   (size_t)member * gridDim.x + blockIdx.x);
+}
+
 // one term's partials: gpart[chunk][flat0 + j * n_out + h] = the chunk's chain of x_s[j] * delta_s[h]; a 16 x 16 tile (blockIdx.x)
 // and a chunk (blockIdx.y) per workgroup
 constexpr int kPgTile = 16, kPgSlab = 64;
-__global__ __launch_bounds__(kPgBlock) void k_pg_wgrad(PgTerm t, long long S, int B, int N, int n0, const float *__restrict__ deltas, int nd,
-                                                       double *__restrict__ gpart, int Q)
+__device__ __forceinline__ void pg_wgrad_body(const PgTerm &t, long long S, int B, int N, int n0, const float *__restrict__ deltas, int nd,
+                                              double *__restrict__ gpart, int Q)
 {
     __shared__ float xs[kPgSlab][kPgTile + 1], ds[kPgSlab][kPgTile + 1];
     const int tid = threadIdx.x, jj = tid >> 4, hh = tid & 15;
@@ -290,6 +395,19 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_wgrad(PgTerm t, long long S, in
     const int j = j0 + jj, h = h0 + hh;
     if (j <= t.n_in && h < t.n_out) gpart[(size_t)blockIdx.y * (size_t)Q + (size_t)t.flat0 + (size_t)j * (size_t)t.n_out + (size_t)h] = part;
 }
+__global__ __launch_bounds__(kPgBlock) void k_pg_wgrad(PgTerm t, long long S, int B, int N, int n0, const float *__restrict__ deltas, int nd,
+                                                       double *__restrict__ gpart, int Q)
+{
+    pg_wgrad_body(t, S, B, N, n0, deltas, nd, gpart, Q);
+}
+// member blockIdx.z's tile and chunk: its envs, its S scratch rows, its gridDim.y chunks of partials
+__global__ __launch_bounds__(kPgBlock) void k_pg_pop_wgrad(PgTerm t, long long S, int B, int N, int n0, int envs_per_member,
+                                                           const float *__restrict__ deltas, int nd, double *__restrict__ gpart, int Q)
+{
+    const size_t member = blockIdx.z, row0 = member * (size_t)S;
+    if (!t.obs && t.X) t.X += row0 * t.ldx;
+    pg_wgrad_body(t, S, B, N, n0 + (int)member * envs_per_member, deltas + row0 * (size_t)nd, nd, gpart + member * gridDim.y * (size_t)Q, Q);
+}
 
 // a parameter's partials joined in chunk order: grad[p] = float32(total / S)
 __global__ __launch_bounds__(kPgBlock) void k_pg_grad_join(const double *__restrict__ gpart, int chunks, int Q, long long S, float *__restrict__ grad)
@@ -299,6 +417,16 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_grad_join(const double *__restr
     double total = 0.0;
     for (int c = 0; c < chunks; ++c) total = total + gpart[(size_t)c * (size_t)Q + (size_t)p];
     grad[p] = adc::pg_grad_finish(total, S);
+}
+// ... of every member (blockIdx.y): its `chunks` rows of partials, its row of grad
+__global__ __launch_bounds__(kPgBlock) void k_pg_pop_grad_join(const double *__restrict__ gpart, int chunks, int Q, long long S, float *__restrict__ grad)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= Q) return;
+    const double *mine = gpart + (size_t)blockIdx.y * (size_t)chunks * (size_t)Q;
+    double total = 0.0;
+    for (int c = 0; c < chunks; ++c) total = total + mine[(size_t)c * (size_t)Q + (size_t)p];
+    grad[(size_t)blockIdx.y * (size_t)Q + (size_t)p] = adc::pg_grad_finish(total, S);
 }
 
 // the (clipped) gradient's step on theta, and the device's chain-major layers and log_std rebuilt from the new theta
@@ -315,4 +443,23 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_update(PgLayout L, float *__res
     mom_m[p] = m;
     mom_v[p] = v;
     *pg_param_slot(L, p) = t1;
+}
+// ... of every member (blockIdx.y) with its own clip scale and step constants (PgMember, set by the host before the launch);
+// theta, the moments and grad are [M][Q], L member 0's stores and a member's `stride` floats further each
+__global__ __launch_bounds__(kPgBlock) void k_pg_pop_update(PgLayout L, size_t stride, float *__restrict__ theta, float *__restrict__ mom_m,
+                                                            float *__restrict__ mom_v, const float *__restrict__ grad,
+                                                            const PgMember *__restrict__ mem)
+{
+    const int p = blockIdx.x * kPgBlock + threadIdx.x;
+    if (p >= L.Q) return;
+    const size_t member = blockIdx.y, i = member * (size_t)L.Q + (size_t)p;
+    const PgMember &c = mem[member];
+    float g = grad[i];
+    if (c.clip) g = g * c.scale;
+    float m = mom_m[i], v = mom_v[i];
+    const float t1 = adc::pg_apply(c.step, theta[i], g, m, v);
+    theta[i] = t1;
+    mom_m[i] = m;
+    mom_v[i] = v;
+    *(pg_param_slot(L, p) + member * stride) = t1;
 }

@@ -13,6 +13,7 @@ int pg_state_check(const adc_engine *e)
 {
     if (int rc = mlp_ready(e)) return rc;
     if (e->pop_M != 0) return fail(ADC_ESTATE, "policy-gradient training with a population active is not supported (adc_engine_mlp_population(0) first)");
+    if (e->lrn_M != 0) return fail(ADC_ESTATE, "learners are active: they train through adc_engine_pg_pop_init (adc_engine_mlp_learners(0) first)");
     if (e->ro_T == 0) return fail(ADC_ESTATE, "policy-gradient training needs a rollout record (adc_engine_rollout_enable)");
     if (!e->ro_obs) return fail(ADC_ESTATE, "policy-gradient training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
     return ADC_OK;
@@ -308,5 +309,349 @@ ADC_EXPORT int adc_engine_pg_state_set(adc_engine *e, const float *theta_q, cons
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->pg_steps = steps;
+    return ADC_OK;
+}
+
+// ---- learner populations: M PPO / A2C learners in lock-step, every launch over all members (include/adcraft_engine.h) ----------
+namespace {
+int pgp_ready(const adc_engine *e)
+{
+    if (!e->have_pg_pop)
+        return fail(ADC_ESTATE, "adc_engine_pg_pop_init has not been called (or the policy, the learners or the record were re-initialised since)");
+    return ADC_OK;
+}
+int pgp_state_check(const adc_engine *e)
+{
+    if (int rc = mlp_ready(e)) return rc;
+    if (e->lrn_M == 0) return fail(ADC_ESTATE, "population training needs learners (adc_engine_mlp_learners)");
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "policy-gradient training needs a rollout record (adc_engine_rollout_enable)");
+    if (!e->ro_obs) return fail(ADC_ESTATE, "policy-gradient training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
+    return ADC_OK;
+}
+int pgp_member_check(const adc_engine *e, int32_t member)
+{
+    if (member < 0 || member >= e->lrn_M) return fail(ADC_EINVAL, "no such member");
+    return ADC_OK;
+}
+// a member's constants from its configuration (what changes per call - moments, clip scale, step - is set where it is computed)
+void pgp_member_fill(PgMember &m, const adc_pg_config &c)
+{
+    m.loss = adc::PgLoss{c.eps_clip, c.vf_coef, c.ent_coef};
+    m.gamma = c.gamma; m.gl = c.gamma * c.lambda; m.reward_scale = c.reward_scale;
+    m.normalize = c.normalize_advantages != 0;
+}
+int pgp_members_upload(adc_engine *e)
+{
+    HIP_TRY(hipMemcpyAsync(e->pgp_dmem, e->pgp_mem.data(), e->pgp_mem.size() * sizeof(PgMember), hipMemcpyHostToDevice, e->stream));
+    return ADC_OK;
+}
+// the members' sums [M][16] in one copy
+int pgp_sums_fetch(adc_engine *e)
+{
+    HIP_TRY(hipMemcpyAsync(e->pgp_host_sums.data(), e->pg_sums, e->pgp_host_sums.size() * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+// every member's chunked sum of `cols` columns into pg_sums[member * 16 + at ...]
+int pgp_csum_launch(adc_engine *e, const float *src, int n, int inner, int outer, size_t mstep, int stride, int cols, int mode, int at)
+{
+    const int chunks = (int)pg_chunks(n), lanes = chunks * cols, M = e->lrn_M;
+    hipLaunchKernelGGL(k_pg_pop_chunk_sums, dim3((unsigned)((lanes + 255) / 256), (unsigned)M), dim3(256), 0, e->stream, src, n, inner, outer, mstep, stride,
+                       cols, mode, e->pgp_dmem, e->pg_part, e->pgp_part_stride);
+    hipLaunchKernelGGL(k_pg_pop_join, dim3((unsigned)M), dim3(64), 0, e->stream, e->pg_part, e->pgp_part_stride, chunks, cols, e->pg_sums + at, 16);
+    HIP_TRY(hipGetLastError());
+    return ADC_OK;
+}
+
+int pgp_advantages_run(adc_engine *e)
+{
+    const int N = e->v.N, T = e->ro_t, M = e->lrn_M, n = e->lrn_n;
+    const long long tn = (long long)T * N;
+    int rc;
+    if (e->mp.val.layers > 0)
+        mlp_launch_kernel(e->v, e->mp, e->stream, 1, nullptr, 0.0f, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, e->mlp_boot);
+    else HIP_TRY(hipMemsetAsync(e->mlp_boot, 0, (size_t)N * 4, e->stream));
+    hipLaunchKernelGGL(k_pg_pop_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, N, T, n, e->pgp_dmem, e->ro_reward, e->ro_term, e->ro_trunc,
+                       e->ro_value, e->mlp_boot, e->pg_adv, e->pg_ret);
+    HIP_TRY(hipGetLastError());
+    bool any = false;
+    for (const PgMember &m : e->pgp_mem) any = any || m.normalize;
+    if (any) {
+        // the law's two passes per member over its T n samples in its own order i = t * n + local env; the moments finished on
+        // the host as the solo path's are, all members' in one copy each way
+        const int cnt = T * n;
+        if ((rc = pgp_csum_launch(e, e->pg_adv, cnt, n, N, (size_t)n, 1, 1, 0, 0)) || (rc = pgp_sums_fetch(e))) return rc;
+        for (int m = 0; m < M; ++m) e->pgp_mem[(size_t)m].mean = e->pgp_host_sums[(size_t)m * 16] / (double)cnt;
+        if ((rc = pgp_members_upload(e)) || (rc = pgp_csum_launch(e, e->pg_adv, cnt, n, N, (size_t)n, 1, 1, 1, 0)) || (rc = pgp_sums_fetch(e))) return rc;
+        for (int m = 0; m < M; ++m) e->pgp_mem[(size_t)m].sd = std::sqrt(e->pgp_host_sums[(size_t)m * 16] / (double)cnt);
+        if ((rc = pgp_members_upload(e))) return rc;
+        hipLaunchKernelGGL(k_pg_pop_normalize, dim3((unsigned)((tn + 255) / 256)), dim3(256), 0, e->stream, e->pg_adv, tn, N, n, e->pgp_dmem);
+        HIP_TRY(hipGetLastError());
+    }
+    e->pg_adv_ready = true;
+    return ADC_OK;
+}
+
+// minibatch `index` of every member: one gradient and one step each, in the same launches
+int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
+{
+    const adc::PgShape &sh = e->pg_shape;
+    const int N = e->v.N, T = e->ro_t, M = e->lrn_M, n = e->lrn_n, B = e->pg_mb, n0 = index * B;
+    const int na = adc::pg_acts_floats(sh), nd = adc::pg_deltas_floats(sh), Q = e->lrn_lay.Q;
+    const long long S = (long long)T * B;
+    const unsigned chunks = (unsigned)pg_chunks(S);
+    PgView p{};
+    p.sh = sh;
+    p.obs = e->ro_obs; p.action = e->ro_action; p.logp = e->ro_logp; p.value = e->ro_value;
+    p.adv = e->pg_adv; p.ret = e->pg_ret;
+    p.N = N; p.n0 = n0; p.B = B;
+    p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
+    p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
+    hipLaunchKernelGGL(k_pg_pop_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p,
+                       e->lrn_tab, e->pgp_dmem, n);
+    {
+        int flat = 0, ao = 0, dof = 0;
+        auto launch = [&](const float *X, size_t ldx, int n_in, int n_out, int obs) {
+            PgTerm t{X, ldx, n_in, n_out, dof, flat, obs};
+            const unsigned tiles = (unsigned)(((n_in + 1 + kPgTile - 1) / kPgTile) * ((n_out + kPgTile - 1) / kPgTile));
+            hipLaunchKernelGGL(k_pg_pop_wgrad, dim3(tiles, chunks, (unsigned)M), dim3(kPgBlock), 0, e->stream, t, S, B, N, n0, n, e->pg_deltas, nd, e->pg_gpart, Q);
+            flat += (n_in + 1) * n_out;
+        };
+        for (int net = 0; net < 2; ++net)
+            for (int l = 0; l < sh.layers[net]; ++l) {
+                const int n_in = adc::pg_n_in(sh, net, l), n_out = sh.n_out[net][l];
+                if (l == 0) launch(e->ro_obs, (size_t)sh.D, n_in, n_out, 1);
+                else { launch(e->pg_acts + ao, (size_t)na, n_in, n_out, 0); ao += n_in; }
+                dof += n_out;
+            }
+        if (!sh.two_heads) launch(nullptr, 0, 0, sh.A, 0);
+    }
+    hipLaunchKernelGGL(k_pg_pop_grad_join, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->pg_gpart, (int)chunks, Q, S, e->pg_grad);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    if ((rc = pgp_csum_launch(e, e->pg_pieces, (int)S, 0, 0, (size_t)S, adc::kPgPieces, 7, 0, 0)) ||
+        (rc = pgp_csum_launch(e, e->pg_pieces + adc::kPgRet, (int)S, 0, 0, (size_t)S, adc::kPgPieces, 2, 2, 7)) ||
+        (rc = pgp_csum_launch(e, e->pg_grad, Q, 0, 0, (size_t)Q, 1, 1, 2, 9)) || (rc = pgp_sums_fetch(e)))
+        return rc;
+    // the statistics, the clip scale and the step's constants of every member on the host, as the solo path's are; up in one copy
+    for (int m = 0; m < M; ++m) {
+        const adc_pg_config &c = e->pgp_cfg[(size_t)m];
+        PgMember &pm = e->pgp_mem[(size_t)m];
+        const adc::PgStatsOut st = adc::pg_stats_finish(e->pgp_host_sums.data() + (size_t)m * 16, S);
+        pm.clip = c.max_grad_norm > 0.0f;
+        pm.scale = pm.clip ? adc::pg_clip_scale(c.max_grad_norm, st.grad_norm) : 1.0f;
+        pm.step = pg_step_of(c, e->pgp_steps[(size_t)m]);
+        if (out_m) out_m[m] = st;
+    }
+    if ((rc = pgp_members_upload(e))) return rc;
+    hipLaunchKernelGGL(k_pg_pop_update, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, e->pg_theta, e->pg_m, e->pg_v,
+                       e->pg_grad, e->pgp_dmem);
+    HIP_TRY(hipGetLastError());
+    // (no wait here, as in the solo path: whoever writes the host's table next has waited for the stream since this upload - the
+    //  sums' fetch of the next minibatch or normalisation pass, or adc_engine_pg_pop_set_config's own wait)
+    for (int m = 0; m < M; ++m) e->pgp_steps[(size_t)m] += 1;
+    return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_pg_pop_init(adc_engine *e, const adc_pg_config *cfgs, int32_t count)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = pgp_state_check(e)) return rc;
+    const int N = e->v.N, M = e->lrn_M, n = e->lrn_n;
+    const char *why = nullptr;
+    if (adc_pg_pop_config_check(cfgs, count, N, M, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if (e->have_td3) return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: one trainer at a time owns the policy's weights");
+    if (e->have_pg) return fail(ADC_ESTATE, "a single-learner trainer is alive on this engine (adc_engine_pg_init)");
+    const int mb = cfgs[0].minibatch_envs == 0 ? n : cfgs[0].minibatch_envs;
+    if (pg_chunks((long long)e->ro_T * n) > 65535) return fail(ADC_EINVAL, "horizon x envs of a member: at most 65535 x 1024 samples");
+    if (pg_chunks((long long)e->ro_T * mb) > 65535) return fail(ADC_EINVAL, "horizon x minibatch_envs: at most 65535 x 1024 samples in a minibatch");
+    // (the member is the grid's y or z: adc_engine_mlp_learners admits at most 65535)
+    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K);
+    int maxw = 1;
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < sh.layers[net]; ++l) maxw = std::max(maxw, sh.n_out[net][l]);
+    if (pg_lds_floats(sh, maxw) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for policy-gradient training (LDS)");
+    ENGINE_GUARD(e);
+    const size_t Q = (size_t)e->lrn_lay.Q, tn = (size_t)e->ro_T * (size_t)N, smax = (size_t)e->ro_T * (size_t)mb, Ms = (size_t)M;
+    const size_t part_stride = (size_t)pg_chunks((long long)std::max((size_t)e->ro_T * (size_t)n, Q)) * 8u + 8u;
+    // (the new state is allocated before the old one goes: a failure leaves the engine as it was)
+    std::vector<void *> fresh;
+    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *adv = nullptr, *ret = nullptr, *acts = nullptr, *deltas = nullptr, *pieces = nullptr;
+    double *part = nullptr, *sums = nullptr, *gpart = nullptr;
+    PgMember *dmem = nullptr;
+    int rc;
+    if ((rc = mlp_alloc(e, fresh, &theta, Ms * Q)) || (rc = mlp_alloc(e, fresh, &m, Ms * Q)) || (rc = mlp_alloc(e, fresh, &v, Ms * Q)) ||
+        (rc = mlp_alloc(e, fresh, &grad, Ms * Q)) || (rc = mlp_alloc(e, fresh, &adv, tn)) || (rc = mlp_alloc(e, fresh, &ret, tn)) ||
+        (rc = mlp_alloc(e, fresh, &acts, Ms * smax * (size_t)adc::pg_acts_floats(sh))) ||
+        (rc = mlp_alloc(e, fresh, &deltas, Ms * smax * (size_t)adc::pg_deltas_floats(sh))) ||
+        (rc = mlp_alloc(e, fresh, &pieces, Ms * smax * (size_t)adc::kPgPieces)) || (rc = mlp_alloc(e, fresh, &part, Ms * part_stride)) ||
+        (rc = mlp_alloc(e, fresh, &gpart, Ms * (size_t)pg_chunks((long long)smax) * Q)) || (rc = mlp_alloc(e, fresh, &sums, Ms * 16u)) ||
+        (rc = mlp_alloc(e, fresh, &dmem, Ms))) {
+        mlp_free(e, fresh);
+        return rc;
+    }
+    pg_drop(e);
+    e->pg_allocs.swap(fresh);
+    e->pg_theta = theta; e->pg_m = m; e->pg_v = v; e->pg_grad = grad; e->pg_adv = adv; e->pg_ret = ret;
+    e->pg_acts = acts; e->pg_deltas = deltas; e->pg_pieces = pieces; e->pg_part = part; e->pg_sums = sums; e->pg_gpart = gpart;
+    e->pg_mb = mb; e->pg_shape = sh; e->pg_maxw = maxw;
+    e->pgp_dmem = dmem; e->pgp_part_stride = part_stride;
+    e->pgp_cfg.assign(Ms, cfgs[0]);
+    if (count > 1) e->pgp_cfg.assign(cfgs, cfgs + M);
+    e->pgp_steps.assign(Ms, 0);
+    e->pgp_mem.assign(Ms, PgMember{});
+    e->pgp_host_sums.assign(Ms * 16u, 0.0);
+    for (size_t i = 0; i < Ms; ++i) pgp_member_fill(e->pgp_mem[i], e->pgp_cfg[i]);
+    if ((rc = pgp_members_upload(e))) return rc;
+    // every member's theta starts as its device weights
+    hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks((int)Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, 0, e->pg_theta, Q, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->have_pg_pop = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_advantages(adc_engine *e)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    ENGINE_GUARD(e);
+    return pgp_advantages_run(e);
+}
+
+ADC_EXPORT int adc_engine_pg_pop_advantages_fetch(adc_engine *e, float *adv_tn, float *ret_tn)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = pgp_ready(e)) return rc;
+    if (!e->pg_adv_ready) return fail(ADC_ESTATE, "adc_engine_pg_pop_advantages has not been called since the last recorded day");
+    ENGINE_GUARD(e);
+    const size_t bytes = (size_t)e->ro_t * (size_t)e->v.N * 4;
+    if (adv_tn) HIP_TRY(hipMemcpyAsync(adv_tn, e->pg_adv, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (ret_tn) HIP_TRY(hipMemcpyAsync(ret_tn, e->pg_ret, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_minibatch(adc_engine *e, int32_t index, adc_pg_stats *stats_m)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if (!e->pg_adv_ready) return fail(ADC_ESTATE, "adc_engine_pg_pop_advantages has not been called since the last recorded day");
+    if (index < 0 || index >= e->lrn_n / e->pg_mb) return fail(ADC_EINVAL, "no such minibatch: 0 to envs of a member / minibatch_envs - 1");
+    ENGINE_GUARD(e);
+    std::vector<adc::PgStatsOut> o((size_t)e->lrn_M);
+    if ((rc = pgp_minibatch_run(e, index, o.data()))) return rc;
+    if (stats_m)
+        for (int m = 0; m < e->lrn_M; ++m) pg_stats_fill(stats_m + m, o[(size_t)m], e->pgp_steps[(size_t)m], (int64_t)e->ro_t * e->pg_mb);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_stats *stats_m)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
+    ENGINE_GUARD(e);
+    if ((rc = pgp_advantages_run(e))) return rc;
+    const int M = e->lrn_M, count = e->lrn_n / e->pg_mb;
+    std::vector<adc::PgStatsOut> o((size_t)M), acc((size_t)M), mean((size_t)M);
+    for (int ep = 0; ep < epochs; ++ep) {
+        acc.assign((size_t)M, adc::PgStatsOut{});
+        for (int i = 0; i < count; ++i) {
+            if ((rc = pgp_minibatch_run(e, i, o.data()))) return rc;
+            for (size_t m = 0; m < (size_t)M; ++m) {
+                adc::PgStatsOut &a = acc[m];
+                a.policy_loss = a.policy_loss + o[m].policy_loss; a.value_loss = a.value_loss + o[m].value_loss; a.entropy = a.entropy + o[m].entropy;
+                a.approx_kl = a.approx_kl + o[m].approx_kl; a.clip_fraction = a.clip_fraction + o[m].clip_fraction;
+                a.grad_norm = a.grad_norm + o[m].grad_norm; a.explained_variance = a.explained_variance + o[m].explained_variance;
+            }
+        }
+        const double c = (double)count;
+        for (size_t m = 0; m < (size_t)M; ++m) {
+            const adc::PgStatsOut &a = acc[m];
+            mean[m] = adc::PgStatsOut{a.policy_loss / c, a.value_loss / c, a.entropy / c, a.approx_kl / c, a.clip_fraction / c, a.grad_norm / c,
+                                      a.explained_variance / c};
+        }
+    }
+    if (stats_m)
+        for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, mean[(size_t)m], e->pgp_steps[(size_t)m], (int64_t)e->ro_t * e->pg_mb);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_state_get(adc_engine *e, int32_t member, float *theta_q, float *m_q, float *v_q, int64_t *steps)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_member_check(e, member))) return rc;
+    ENGINE_GUARD(e);
+    const size_t Q = (size_t)e->lrn_lay.Q, bytes = Q * 4, at = (size_t)member * Q;
+    if (theta_q) HIP_TRY(hipMemcpyAsync(theta_q, e->pg_theta + at, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (m_q) HIP_TRY(hipMemcpyAsync(m_q, e->pg_m + at, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (v_q) HIP_TRY(hipMemcpyAsync(v_q, e->pg_v + at, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (steps) *steps = e->pgp_steps[(size_t)member];
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_state_set(adc_engine *e, int32_t member, const float *theta_q, const float *m_q, const float *v_q, int64_t steps)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_member_check(e, member))) return rc;
+    if (!theta_q || !m_q || !v_q) return fail(ADC_EINVAL, "theta, m or v is NULL");
+    if (steps < 0 || steps >= 0x7FFFFFFFll) return fail(ADC_EINVAL, "steps: 0 to 2^31 - 2");
+    ENGINE_GUARD(e);
+    const size_t Q = (size_t)e->lrn_lay.Q, bytes = Q * 4, at = (size_t)member * Q;
+    HIP_TRY(hipMemcpyAsync(e->pg_theta + at, theta_q, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->pg_m + at, m_q, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->pg_v + at, v_q, bytes, hipMemcpyHostToDevice, e->stream));
+    // (the member's layers and log_std follow its theta, so that the next act and the next recorded day see it)
+    hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks((int)Q), 1u), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, (int)member,
+                       e->pg_theta + at, (size_t)0, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pgp_steps[(size_t)member] = steps;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_set_config(adc_engine *e, int32_t member, const adc_pg_config *cfg)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_member_check(e, member))) return rc;
+    const char *why = nullptr;
+    if (adc_pg_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if ((cfg->minibatch_envs == 0 ? e->lrn_n : cfg->minibatch_envs) != e->pg_mb)
+        return fail(ADC_EINVAL, "minibatch_envs may not change: the members' minibatches run in the same launches (the scratch was sized for it)");
+    ENGINE_GUARD(e);
+    HIP_TRY(hipStreamSynchronize(e->stream));       // (an upload of the host's table may still be in flight)
+    e->pgp_cfg[(size_t)member] = *cfg;
+    pgp_member_fill(e->pgp_mem[(size_t)member], *cfg);
+    if ((rc = pgp_members_upload(e))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pg_adv_ready = false;            // (advantages computed under the old gamma, lambda, reward_scale or normalisation are stale)
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pg_pop_copy(adc_engine *e, int32_t src, int32_t dst)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_member_check(e, src)) || (rc = pgp_member_check(e, dst))) return rc;
+    if (src == dst) return ADC_OK;
+    ENGINE_GUARD(e);
+    const size_t Q = (size_t)e->lrn_lay.Q, bytes = Q * 4, from = (size_t)src * Q, to = (size_t)dst * Q;
+    HIP_TRY(hipMemcpyAsync(e->pg_theta + to, e->pg_theta + from, bytes, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->pg_m + to, e->pg_m + from, bytes, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->pg_v + to, e->pg_v + from, bytes, hipMemcpyDeviceToDevice, e->stream));
+    hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks((int)Q), 1u), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, (int)dst, e->pg_theta + to,
+                       (size_t)0, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pgp_steps[(size_t)dst] = e->pgp_steps[(size_t)src];
     return ADC_OK;
 }

@@ -16,6 +16,7 @@ int td3_state_check(const adc_engine *e)
     if (int rc = mlp_ready(e)) return rc;
     if (e->mp.two_heads) return fail(ADC_ESTATE, "TD3 needs the policy with the free log_std head: a two-headed policy (2A outputs) is not supported");
     if (e->pop_M != 0) return fail(ADC_ESTATE, "off-policy training with a population active is not supported (adc_engine_mlp_population(0) first)");
+    if (e->lrn_M != 0) return fail(ADC_ESTATE, "off-policy training with learners active is not supported (adc_engine_mlp_learners(0) first)");
     if (e->ro_T == 0) return fail(ADC_ESTATE, "off-policy training needs a rollout record (adc_engine_rollout_enable)");
     if (!e->ro_obs) return fail(ADC_ESTATE, "off-policy training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
     return ADC_OK;

@@ -567,6 +567,7 @@ class StepEngine:
         check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
         self._mlp = policy
         self._members = 0                   # (a population does not survive a re-initialisation)
+        self._learners = 0
         self.mlp_set_weights(policy)
 
     def mlp_set_weights(self, policy):
@@ -634,6 +635,8 @@ class StepEngine:
             raise ValueError("member_of_env: one member per env")
         check(self._lib.adc_engine_mlp_population(self._h, int(members), None if m is None else m.ctypes.data))
         self._members = int(members)
+        if int(members) > 0:
+            self._learners = 0              # (a population drops learners)
 
     def mlp_set_member(self, member, policy):
         """the policy layers of `policy` (same shapes as at mlp_init) into one member"""
@@ -659,6 +662,43 @@ class StepEngine:
         flat = np.zeros(self.mlp_param_count(), np.float32)
         check(self._lib.adc_engine_mlp_get_member_params(self._h, int(member), flat.ctypes.data))
         return flat
+
+    # ---- learners: per-member policy layers, value layers and log_std (the members pg_pop_* trains) ----------------------------
+    def mlp_learners(self, members):
+        """`members` learners, each with its own policy layers, value layers and log_std, each starting as the centre policy;
+        member m owns the envs [m N / M, (m + 1) N / M).  0 turns the mode off.  Excludes mlp_population."""
+        check(self._lib.adc_engine_mlp_learners(self._h, int(members)))
+        self._learners = int(members)
+        if int(members) > 0:
+            self._members = 0
+
+    def mlp_set_learner(self, member, policy):
+        """every layer of both networks and log_std of `policy` (same shapes as at mlp_init) into one learner"""
+        if getattr(self, "_mlp", None) is None:
+            raise _ffi.EngineStateError("mlp_init has not been called")
+        if policy.shapes() != self._mlp.shapes():
+            raise ValueError(f"mlp_set_learner: the policy's shapes {policy.shapes()} are not those given to mlp_init {self._mlp.shapes()}")
+        for net, layers in ((0, policy.layers), (1, policy.value_layers)):
+            for i, (w, b) in enumerate(layers):
+                check(self._lib.adc_engine_mlp_set_learner_layer(self._h, int(member), net, i, w.ctypes.data, b.ctypes.data))
+        if policy.log_std is not None:
+            check(self._lib.adc_engine_mlp_set_learner_log_std(self._h, int(member), policy.log_std.ctypes.data))
+
+    def mlp_learner_params(self, member):
+        """one learner's parameters in the trainer's flat order theta[Q]: policy layers, value layers, log_std"""
+        theta = np.zeros(self.mlp_learner_param_count(), np.float32)
+        check(self._lib.adc_engine_mlp_get_learner_params(self._h, int(member), theta.ctypes.data))
+        return theta
+
+    def mlp_learner_param_count(self):
+        """Q: the parameters of both networks and log_std of the policy given to mlp_init"""
+        if getattr(self, "_mlp", None) is None:
+            raise _ffi.EngineStateError("mlp_init has not been called")
+        q = C.c_int64(0)
+        cfg = self._mlp.config(self.num_keywords)
+        if self._lib.adc_pg_param_count_host(C.byref(cfg), self.num_keywords, C.byref(q)) != _ffi.ADC_OK:
+            raise ValueError("bad policy configuration")
+        return q.value
 
     ES_SHAPINGS = {"centered_rank": _ffi.ES_CENTERED_RANK, "raw": _ffi.ES_RAW}
     ES_OPTIMISERS = {"adam": _ffi.ES_ADAM, "sgd": _ffi.ES_SGD}
@@ -785,6 +825,71 @@ class StepEngine:
         if any(a.shape != (Q,) for a in arr):
             raise ValueError(f"pg_state: theta, m and v have {Q} entries")
         check(self._lib.adc_engine_pg_state_set(self._h, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
+
+    # ---- learner populations: M PPO / A2C learners in lock-step (parts/pg_api.inc; baselines/pg_trainer.py PGPopulationTrainer) ----
+    @classmethod
+    def pg_pop_configs(cls, configs, num_envs, members):
+        """(ctypes array, count) from one dict of pg_config's options or `members` of them, checked by adc_pg_pop_config_check"""
+        if isinstance(configs, dict):
+            configs = [configs]
+        built = [cls.pg_config(**c) for c in configs]
+        arr = (_ffi.PGConfig * len(built))(*built)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_pg_pop_config_check(arr, len(built), int(num_envs), int(members), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad population configuration").decode())
+        return arr, len(built)
+
+    def pg_pop_init(self, configs):
+        """population training of the learners (mlp_learners, rollout_enable(T, obs=True) first); configs: one dict of
+        pg_config's options shared by all members, or one per member.  Every member's theta starts as its device weights."""
+        arr, count = self.pg_pop_configs(configs, self.num_envs, max(getattr(self, "_learners", 0), 1))
+        check(self._lib.adc_engine_pg_pop_init(self._h, arr, count))
+
+    def pg_pop_advantages(self, fetch=False):
+        """GAE per env under its member's configuration; fetch=True returns (adv, ret) [T, N] float32"""
+        check(self._lib.adc_engine_pg_pop_advantages(self._h))
+        if not fetch:
+            return None
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        adv, ret = np.zeros((t.value, self.num_envs), np.float32), np.zeros((t.value, self.num_envs), np.float32)
+        check(self._lib.adc_engine_pg_pop_advantages_fetch(self._h, adv.ctypes.data, ret.ctypes.data))
+        return adv, ret
+
+    def pg_pop_minibatch(self, index):
+        """minibatch `index` of every member in the same launches; a list of M statistics dicts"""
+        st = (_ffi.PGStats * max(getattr(self, "_learners", 0), 1))()
+        check(self._lib.adc_engine_pg_pop_minibatch(self._h, int(index), st))
+        return [self._pg_stats(x) for x in st]
+
+    def pg_pop_update(self, epochs=1):
+        """advantages, then `epochs` x the minibatches ascending, all members at once; a list of M statistics dicts"""
+        st = (_ffi.PGStats * max(getattr(self, "_learners", 0), 1))()
+        check(self._lib.adc_engine_pg_pop_update(self._h, int(epochs), st))
+        return [self._pg_stats(x) for x in st]
+
+    def pg_pop_state(self, member, state=None):
+        """one member's state.  get (no state): dict of theta, m, v [Q] float32 and steps; set: such a dict"""
+        Q = self.mlp_learner_param_count()
+        if state is None:
+            st = dict(theta=np.zeros(Q, np.float32), m=np.zeros(Q, np.float32), v=np.zeros(Q, np.float32))
+            n = C.c_int64(0)
+            check(self._lib.adc_engine_pg_pop_state_get(self._h, int(member), st["theta"].ctypes.data, st["m"].ctypes.data, st["v"].ctypes.data, C.byref(n)))
+            st["steps"] = n.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in ("theta", "m", "v")]
+        if any(a.shape != (Q,) for a in arr):
+            raise ValueError(f"pg_pop_state: theta, m and v have {Q} entries")
+        check(self._lib.adc_engine_pg_pop_state_set(self._h, int(member), arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
+
+    def pg_pop_set_config(self, member, **options):
+        """a member's hyperparameters from the next call on (options as pg_config's; minibatch_envs may not change)"""
+        cfg = self.pg_config(**options)
+        check(self._lib.adc_engine_pg_pop_set_config(self._h, int(member), C.byref(cfg)))
+
+    def pg_pop_copy(self, src, dst):
+        """weights, optimiser moments and step count of member src into member dst, on the device"""
+        check(self._lib.adc_engine_pg_pop_copy(self._h, int(src), int(dst)))
 
     # ---- off-policy (TD3) training over a replay ring filled from the record (parts/kernel_td3.inc; baselines/td3_trainer.py) ----
     TD3_OPTIMISERS = {"adam": _ffi.TD3_ADAM, "sgd": _ffi.TD3_SGD}

@@ -545,6 +545,24 @@ int adc_engine_mlp_param_count(adc_engine *e, int64_t *count);
 int adc_engine_mlp_get_params(adc_engine *e, float *flat_p);                              /* the centre */
 int adc_engine_mlp_get_member_params(adc_engine *e, int32_t member, float *flat_p);
 
+/* ---- learners: per-member policy layers, value layers and log_std (the members of adc_engine_pg_pop_*) -------------------------
+ * A second kind of population, for learners that train: `members` = M > 0 (M must divide num_envs, at most 65535) gives every
+ * member its own policy layers, value layers and - with the free head - log_std[A], each starting as the centre (what
+ * adc_engine_mlp_set_layer / _set_log_std uploaded); env -> member is env / (N / M), so member m owns the envs
+ * [m N / M, (m + 1) N / M).  The normalisation vectors, the clamps, the activation and the shapes stay shared.  M = 0 turns the
+ * mode off.  Acts, adc_engine_mlp_step, adc_engine_run_days(ADC_POLICY_MLP), the rollout record, adc_engine_mlp_last and
+ * adc_engine_mlp_bootstrap_value work unchanged, every env under its member's networks: what member m's envs compute is, bit
+ * for bit, what an engine of N / M envs at env_id_base + m N / M computes under that member's weights.  This mode and
+ * adc_engine_mlp_population exclude each other: starting one drops the other with the strategy or trainer over it;
+ * adc_engine_mlp_init drops both.  adc_engine_mlp_set_layer and adc_engine_mlp_set_log_std keep writing the centre alone.
+ * adc_engine_mlp_get_learner_params: the member's parameters in the trainer's flat order theta[Q] (adc_pg_param_count_host): the
+ * policy layers, the value layers, then log_std. */
+int adc_engine_mlp_learners(adc_engine *e, int32_t members);
+/* network: 0 policy, 1 value; weights [n_in][n_out] input-major as adc_engine_mlp_set_layer's */
+int adc_engine_mlp_set_learner_layer(adc_engine *e, int32_t member, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out);
+int adc_engine_mlp_set_learner_log_std(adc_engine *e, int32_t member, const float *log_std_a);
+int adc_engine_mlp_get_learner_params(adc_engine *e, int32_t member, float *theta_q);
+
 /* ---- an evolution strategy on the device (OpenAI-ES; the law is csrc/adc_es.h) ----------------------------------------------
  * Over a population of an even number of members: adc_engine_es_perturb writes member 2i / 2i + 1 = theta +- sigma * eps(i, g)
  * from counter-addressed noise (Philox stage 15 under the strategy's own key; never stored), zeroes every env's return and
@@ -628,6 +646,37 @@ int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats *stats);
 /* theta, the Adam moments [Q] and the step count: a run resumed from them continues bit for bit (get: any pointer may be NULL) */
 int adc_engine_pg_state_get(adc_engine *e, float *theta_q, float *m_q, float *v_q, int64_t *steps);
 int adc_engine_pg_state_set(adc_engine *e, const float *theta_q, const float *m_q, const float *v_q, int64_t steps);
+
+/* ---- learner populations: M independent PPO / A2C learners in lock-step on one engine -------------------------------------------
+ * Over learners (adc_engine_mlp_learners): member m trains its own networks on the recorded days of its own envs
+ * [m n, (m + 1) n), n = N / M, under its own adc_pg_config, and every kernel launch of an update covers all members: the
+ * launches and host round trips of an update do not grow with M.  The law is csrc/adc_pg.h as it is: everything member m
+ * computes - advantages, returns, gradient, theta / m / v after every step, statistics - is bit for bit what adc_engine_pg_*
+ * computes on an engine of n envs at env_id_base + m n with the same parameter planes, agent seeds, initial weights and
+ * configuration.  Sample s of the member's minibatch i is day s / mb, env m n + i mb + s % mb; the chunked sums run over the
+ * member's own samples in that order, the advantage normalisation over its T n samples at index t n + local env.
+ * adc_pg_pop_config_check (host only): every configuration passes adc_pg_config_check; count is 1 (shared) or `members`;
+ * minibatch_envs is equal in all and divides num_envs / members (0: all of a member's envs); every other field may differ per
+ * member.  adc_engine_pg_pop_init needs learners, a record with ADC_ROLLOUT_OBS and no other trainer alive (adc_engine_pg_init
+ * and adc_engine_td3_init in turn refuse while learners are active); every member's theta starts as its device weights; a
+ * refused allocation is ADC_ENOMEM and leaves the engine as it was.  The trainer does not survive adc_engine_mlp_init,
+ * adc_engine_mlp_learners or adc_engine_rollout_enable. */
+int adc_pg_pop_config_check(const adc_pg_config *cfgs, int32_t count, int32_t num_envs, int32_t members, const char **message);
+int adc_engine_pg_pop_init(adc_engine *e, const adc_pg_config *cfgs, int32_t count);
+/* GAE with the env's member's gamma, lambda and reward_scale; the normalisation per member that asks for it */
+int adc_engine_pg_pop_advantages(adc_engine *e);
+int adc_engine_pg_pop_advantages_fetch(adc_engine *e, float *adv_tn, float *ret_tn);       /* [T][N] each, either may be NULL */
+/* minibatch `index` (0 .. n / minibatch_envs - 1) of every member: one gradient and one optimiser step each; stats_m[M] or NULL */
+int adc_engine_pg_pop_minibatch(adc_engine *e, int32_t index, adc_pg_stats *stats_m);
+/* advantages once, then `epochs` times the minibatches ascending; stats_m[M] (may be NULL) filled as adc_engine_pg_update fills its one */
+int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_stats *stats_m);
+/* one member's theta, Adam moments [Q] and step count (get: any pointer may be NULL); set also rebuilds the member's layers */
+int adc_engine_pg_pop_state_get(adc_engine *e, int32_t member, float *theta_q, float *m_q, float *v_q, int64_t *steps);
+int adc_engine_pg_pop_state_set(adc_engine *e, int32_t member, const float *theta_q, const float *m_q, const float *v_q, int64_t steps);
+/* a member's hyperparameters from the next call on (minibatch_envs may not change); advantages must be computed again */
+int adc_engine_pg_pop_set_config(adc_engine *e, int32_t member, const adc_pg_config *cfg);
+/* theta, moments and step count of src into dst on the device, and dst's layers and log_std rebuilt (its configuration stays) */
+int adc_engine_pg_pop_copy(adc_engine *e, int32_t src, int32_t dst);
 
 /* ---- off-policy training on the device: a replay ring, twin critics, TD3 (the law is csrc/adc_td3.h) --------------------------
  * The actor is the policy network given to adc_engine_mlp_init with the free log_std[A] head; its mean is TD3's deterministic

@@ -293,6 +293,22 @@ def lib():
         "adc_engine_td3_param_counts": ([vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "adc_engine_td3_state_get": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "adc_engine_td3_state_set": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64], C.c_int),
+        "adc_td3_pop_config_check": ([C.POINTER(TD3Config), i32, i32, i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_td3_pop_init": ([vp, C.POINTER(TD3Config), i32], C.c_int),
+        "adc_engine_td3_pop_set_critic_layer": ([vp, i32, i32, i32, vp, vp], C.c_int),
+        "adc_engine_td3_pop_set_action_norm": ([vp, vp, vp], C.c_int),
+        "adc_engine_td3_pop_sync_targets": ([vp, i32], C.c_int),
+        "adc_engine_td3_pop_store": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_pop_buffer_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)], C.c_int),
+        "adc_engine_td3_pop_buffer_fetch": ([vp, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_td3_pop_buffer_load": ([vp, i32, i64, i64, vp, vp, vp, vp, vp, i64], C.c_int),
+        "adc_engine_td3_pop_batch_indices": ([vp, i32, i64, vp], C.c_int),
+        "adc_engine_td3_pop_update": ([vp, i32, C.POINTER(TD3Stats)], C.c_int),
+        "adc_engine_td3_pop_param_counts": ([vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_pop_state_get": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_pop_state_set": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64], C.c_int),
+        "adc_engine_td3_pop_set_config": ([vp, i32, C.POINTER(TD3Config)], C.c_int),
+        "adc_engine_td3_pop_copy": ([vp, i32, i32, i32], C.c_int),
         "adc_td3_config_check": ([C.POINTER(TD3Config), C.POINTER(C.c_char_p)], C.c_int),
         "adc_td3_param_counts_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "adc_td3_batch_indices_host": ([u64, i64, i64, i32, vp], C.c_int),

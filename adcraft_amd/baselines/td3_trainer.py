@@ -110,4 +110,98 @@ class TD3Trainer:
         return self.engine.td3_state(state)
 
 
-__all__ = ["TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]
+class TD3PopulationTrainer:
+    """M independent TD3 learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
+    actor, exploration sigma, twin critics, targets, optimiser state, hyperparameters and replay ring, and every launch of a
+    store or an update covers all members (StepEngine.td3_pop_*).  What a member computes is bit for bit what TD3Trainer
+    computes on an engine of its n envs.
+
+    engine: a StepEngine that has been reset; policies: one MLPPolicy (every member starts from it) or M of equal shape;
+    sigmas: one exploration sigma or M, or None: every configuration's exploration_sigma (default 0.1); configs: one dict of
+    TD3Trainer's keyword options (td3()'s keys and StepEngine.td3_config's, plus critic_seed, critics, action_norm) shared by
+    all members or M of them - M is `members`, or the largest of the three counts.  critic_hidden, batch_size, capacity, policy_delay, learning_starts (transitions of a member's ring),
+    updates_per_iteration and action_norm must be equal in all configurations: the members move together."""
+
+    SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
+
+    def __init__(self, engine, policies, sigmas, configs, horizon=10, agent_seeds=None, members=None):
+        policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
+        configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
+        own = [c.pop("exploration_sigma", 0.1) for c in configs]
+        sigmas = own if sigmas is None else [float(sigmas)] if np.isscalar(sigmas) else [float(s) for s in sigmas]
+        members = max(len(policies), len(sigmas), len(configs)) if members is None else int(members)
+        if any(len(x) not in (1, members) for x in (policies, sigmas, configs)) or not policies or not sigmas or not configs:
+            raise ValueError("TD3PopulationTrainer: policies, sigmas and configs are each one (shared) or one per member")
+        if any(p.log_std is None for p in policies):
+            raise ValueError("TD3 needs policies that end in K + 1 means with the free log_std vector")
+        if any(p.shapes() != policies[0].shapes() for p in policies):
+            raise ValueError("TD3PopulationTrainer: the members' policies must have equal shapes")
+        for p in policies[1:]:
+            if p.shift is not None and not (np.array_equal(p.shift, policies[0].shift) and np.array_equal(p.scale, policies[0].scale)):
+                raise ValueError("TD3PopulationTrainer: the normalisation vectors are shared by all members: the policies' must be equal")
+        if engine.num_envs % members:
+            raise ValueError("the number of members must divide the engine's envs")
+        policies, sigmas, configs = (x if len(x) == members else x * members for x in (policies, sigmas, configs))
+        K = policies[0].num_keywords
+        cfgs = [dict(dict(critic_hidden=(256, 256), learning_starts=10000, updates_per_iteration=64), **c) for c in configs]
+        for c in cfgs[1:]:
+            if any(tuple(np.atleast_1d(c[k])) != tuple(np.atleast_1d(cfgs[0][k])) for k in self.SHARED):
+                raise ValueError("TD3PopulationTrainer: critic_hidden, learning_starts and updates_per_iteration must be equal in all configurations")
+        hidden = tuple(cfgs[0]["critic_hidden"])
+        self.learning_starts, self.updates_per_iteration = int(cfgs[0]["learning_starts"]), int(cfgs[0]["updates_per_iteration"])
+        critics, norms, seeds = [c.pop("critics", None) for c in cfgs], [c.pop("action_norm", None) for c in cfgs], [c.pop("critic_seed", m) for m, c in enumerate(cfgs)]
+        for n in norms[1:]:
+            if (n is None) != (norms[0] is None) or (n is not None and not all(np.array_equal(a, b) for a, b in zip(n, norms[0]))):
+                raise ValueError("TD3PopulationTrainer: the critics' action normalisation is shared by all members")
+        self.engine, self.members, self.horizon = engine, members, int(horizon)
+        self._templates = []
+        for pol, sigma in zip(policies, sigmas):
+            t = copy.copy(pol)
+            t.log_std = np.full(K + 1, np.log(sigma), np.float32)
+            self._templates.append(t)
+        self.configs = [dict({k: v for k, v in c.items() if k not in self.SHARED}, critic_widths=hidden + (1,)) for c in cfgs]
+        engine.mlp_init(self._templates[0], seeds=agent_seeds, deterministic=False)
+        engine.mlp_learners(members)
+        for m in range(1, members):
+            engine.mlp_set_learner(m, self._templates[m])
+        engine.rollout_enable(self.horizon, obs=True)
+        engine.td3_pop_init(self.configs)
+        for m in range(members):
+            engine.td3_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]), action_norm=norms[0] if m == 0 else None)
+        self.history = []
+
+    def set_exploration(self, sigma, member=None):
+        """the collection noise's standard deviation of one member (None: of all) from the next day on"""
+        for m in range(self.members) if member is None else [int(member)]:
+            self._templates[m].log_std = np.full(self._templates[m].num_keywords + 1, np.log(sigma), np.float32)
+            self.engine.mlp_set_learner_log_std(m, self._templates[m].log_std)
+
+    def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
+        """(reset), `days` (default: the horizon) recorded days of run_days("mlp"), the store, and - once every ring holds
+        learning_starts transitions - updates_per_iteration updates; returns the M members' statistics, or only the rings' size
+        before that"""
+        e = self.engine
+        if reset:
+            e.reset(seeds=reset_seeds)
+        e.rollout_reset()
+        e.run_days("mlp", self.horizon if days is None else int(days), budget)
+        e.td3_pop_store()
+        size = e.td3_pop_buffer(fetch=False)["size"]
+        stats = e.td3_pop_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
+        self.history.append(stats)
+        return stats
+
+    def policy(self, member):
+        """an MLPPolicy holding one member's trained actor (its log_std the member's exploration's)"""
+        return policy_from_actor(self._templates[member], self.engine.td3_pop_state(member)["theta"])
+
+    def returns(self):
+        """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days"""
+        r = self.engine.rollout_fetch()["reward"].astype(np.float64).sum(axis=0)
+        return r.reshape(self.members, -1).mean(axis=1)
+
+    def state(self, member, state=None):
+        return self.engine.td3_pop_state(member, state)
+
+
+__all__ = ["TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]

@@ -51,9 +51,11 @@
 //   parts/kernel_pg.inc           policy-gradient training: GAE, the networks' backward pass, the weight gradient, the step (adc_pg.h);
 //        the k_pg_pop_* twins run the same bodies for all members of a learner population in one launch.
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
+//   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
+//   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -95,10 +97,12 @@ namespace adck {
 #include "parts/kernel_es.inc"
 #include "parts/kernel_pg.inc"
 #include "parts/kernel_td3.inc"
+#include "parts/kernel_td3_pop.inc"
 }  // namespace adck
 using namespace adck;
 
 #include "parts/host_api.inc"
 #include "parts/pg_api.inc"
 #include "parts/td3_api.inc"
+#include "parts/td3_pop_api.inc"
 #include "parts/comm_api.inc"

@@ -150,6 +150,19 @@ struct adc_engine {
     int32_t *td3_idx = nullptr;         // [B] adc_engine_td3_batch_indices' device result
     double *td3_part = nullptr, *td3_sums = nullptr, *td3_gpart = nullptr;
     std::vector<void *> td3_allocs;
+    // ... and of a TD3 learner population (adc_engine_td3_pop_init; parts/kernel_td3_pop.inc, parts/td3_pop_api.inc).  It shares the
+    // fields above, sized for all members at once: td3_flat / td3_mom are [M][P] or [M][2 Qc], the scratch [M][B][...], td3_sums
+    // [M][16]; td3_cfg holds the fields all members share, td3_lay member 0's stores, the counters count for all (lock-step)
+    bool have_td3_pop = false;
+    std::vector<adc_td3_config> tp_cfg;         // [M]
+    std::vector<Td3Member> tp_mem;              // [M] the host's copy of tp_dmem
+    std::vector<Td3PopStep> tp_steps;           // [updates of a block][critic, actor][M] the host's copy of tp_dsteps
+    std::vector<double> tp_host_sums;           // [M][16]
+    std::vector<uint8_t> tp_critic_set;         // [M][2][4] uploaded since init
+    Td3Member *tp_dmem = nullptr;
+    Td3PopStep *tp_dsteps = nullptr;
+    size_t tp_stride[4] = {0, 0, 0, 0};         // floats between two members' stores, per flat vector (theta's: lrn_stride)
+    size_t tp_part_stride = 0;                  // doubles of chunk partials per member
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -2798,7 +2811,7 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     int rc;
     if (record && e->mp.deterministic) e->ro_deterministic = true;
     // (a day recorded after the envs moved outside the record does not follow the unstored day before it)
-    if (record && e->have_td3 && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
+    if (record && (e->have_td3 || e->have_td3_pop) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
     if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
     if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
     if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
@@ -2818,15 +2831,18 @@ void pg_drop(adc_engine *e)
 void td3_drop(adc_engine *e)
 {
     mlp_free(e, e->td3_allocs);
-    e->have_td3 = e->td3_norm_set = e->td3_gap = false;
+    e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
     std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));
     e->td3_updates = e->td3_actor_steps = e->td3_written = 0;
     e->td3_stored_t = 0;
+    e->tp_cfg.clear(); e->tp_mem.clear(); e->tp_steps.clear(); e->tp_host_sums.clear(); e->tp_critic_set.clear();
+    e->tp_dmem = nullptr; e->tp_dsteps = nullptr;
 }
 // learners and the population trainer over them go with the policy they belong to (the engine is back to the centre policy)
 void learners_drop(adc_engine *e)
 {
     if (e->have_pg_pop) pg_drop(e);
+    if (e->have_td3_pop) td3_drop(e);
     mlp_free(e, e->lrn_allocs);
     if (e->lrn_M != 0) { e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; }
     e->lrn_M = e->lrn_n = 0;

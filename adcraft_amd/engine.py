@@ -684,6 +684,13 @@ class StepEngine:
         if policy.log_std is not None:
             check(self._lib.adc_engine_mlp_set_learner_log_std(self._h, int(member), policy.log_std.ctypes.data))
 
+    def mlp_set_learner_log_std(self, member, log_std):
+        """one learner's free log_std vector [K + 1] alone (its exploration noise under td3_pop_*); the next act reads it"""
+        ls = np.ascontiguousarray(log_std, dtype=np.float32)
+        if ls.shape != (self.num_keywords + 1,):
+            raise ValueError("mlp_set_learner_log_std: K + 1 entries")
+        check(self._lib.adc_engine_mlp_set_learner_log_std(self._h, int(member), ls.ctypes.data))
+
     def mlp_learner_params(self, member):
         """one learner's parameters in the trainer's flat order theta[Q]: policy layers, value layers, log_std"""
         theta = np.zeros(self.mlp_learner_param_count(), np.float32)
@@ -1016,6 +1023,132 @@ class StepEngine:
         if any(a.shape != (size(k),) for k, a in zip(self.TD3_STATE, arr)):
             raise ValueError(f"td3_state: the actor's vectors have {P} entries, the critics' {Q}")
         check(self._lib.adc_engine_td3_state_set(self._h, *(a.ctypes.data for a in arr), int(state["updates"]), int(state["actor_steps"])))
+
+    # ---- TD3 learner populations: M off-policy learners in lock-step (parts/td3_pop_api.inc; baselines/td3_trainer.py TD3PopulationTrainer) ----
+    @classmethod
+    def td3_pop_configs(cls, configs, num_envs, members):
+        """(ctypes array, count) from one dict of td3_config's options or `members` of them, checked by adc_td3_pop_config_check"""
+        if isinstance(configs, dict):
+            configs = [configs]
+        built = [cls.td3_config(**c) for c in configs]
+        arr = (_ffi.TD3Config * len(built))(*built)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_td3_pop_config_check(arr, len(built), int(num_envs), int(members), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad population configuration").decode())
+        return arr, len(built)
+
+    def _td3_pop_members(self):
+        return max(getattr(self, "_learners", 0), 1)
+
+    def td3_pop_init(self, configs):
+        """population TD3 of the learners (mlp_learners, rollout_enable(T, obs=True) first); configs: one dict of td3_config's
+        options shared by all members, or one per member (batch_size, capacity, critic_widths and policy_delay equal in all).
+        Every member's theta starts as its device policy; the critics are uploaded with td3_pop_set_critics."""
+        arr, count = self.td3_pop_configs(configs, self.num_envs, self._td3_pop_members())
+        check(self._lib.adc_engine_td3_pop_init(self._h, arr, count))
+
+    def td3_pop_set_critics(self, member, critics, action_norm=None, sync_targets=True):
+        """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs); action_norm: (shift, scale) [A],
+        shared by all members; sync_targets: the member's targets become copies of its actor and critics"""
+        if len(critics) != 2:
+            raise ValueError("td3_pop_set_critics: two critics")
+        for i, layers in enumerate(critics):
+            for l, (w, b) in enumerate(layers):
+                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+                check(self._lib.adc_engine_td3_pop_set_critic_layer(self._h, int(member), i, l, w.ctypes.data, b.ctypes.data))
+        if action_norm is not None:
+            sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in action_norm)
+            if sh.shape != (self.num_keywords + 1,) or sc.shape != sh.shape:
+                raise ValueError("action_norm: shift and scale of K + 1 entries")
+            check(self._lib.adc_engine_td3_pop_set_action_norm(self._h, sh.ctypes.data, sc.ctypes.data))
+        if sync_targets:
+            check(self._lib.adc_engine_td3_pop_sync_targets(self._h, int(member)))
+
+    def td3_pop_sync_targets(self, member=None):
+        """member None: every member's targets"""
+        check(self._lib.adc_engine_td3_pop_sync_targets(self._h, -1 if member is None else int(member)))
+
+    def td3_pop_store(self):
+        """the record's days not yet stored, into every member's ring; returns the transitions each member appended"""
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_td3_pop_store(self._h, C.byref(n)))
+        return n.value
+
+    def td3_pop_buffer(self, member=None, fetch=True):
+        """dict of size, written, capacity, batch_size (the members' rings move together) and - for a member, fetch=True - its
+        ring's slots [0, size) as td3_buffer's"""
+        sz, wr, cap, b = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(self._lib.adc_engine_td3_pop_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap), C.byref(b)))
+        st = dict(size=sz.value, written=wr.value, capacity=cap.value, batch_size=b.value)
+        if fetch and member is not None:
+            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
+            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
+                      x2=np.zeros((n, D), np.float32))
+            if n:
+                check(self._lib.adc_engine_td3_pop_buffer_fetch(self._h, int(member), 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
+            st["done"] = st["done"].astype(bool)
+        return st
+
+    def td3_pop_buffer_load(self, member, buf, slot=0, written=None):
+        """the arrays of a td3_pop_buffer(member) dict (or one of its kind) into the member's slots from `slot` on; written
+        becomes the count of transitions stored so far of every member's ring"""
+        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
+        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
+        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
+        n = r.shape[0]
+        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
+            raise ValueError("td3_pop_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
+        if written is None:
+            written = buf.get("written", slot + n)
+        check(self._lib.adc_engine_td3_pop_buffer_load(self._h, int(member), int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data,
+                                                       x2.ctypes.data, int(written)))
+
+    def td3_pop_batch_indices(self, member, update):
+        """the slots of the member's ring its update number `update` reads at the ring's current size: [batch_size] int32"""
+        idx = np.zeros(self.td3_pop_buffer(fetch=False)["batch_size"], np.int32)
+        check(self._lib.adc_engine_td3_pop_batch_indices(self._h, int(member), int(update), idx.ctypes.data))
+        return idx
+
+    def td3_pop_update(self, updates=1, stats=True):
+        """`updates` critic updates of every member and the delayed actor / target steps among them, all members in the same
+        launches; a list of M statistics dicts (stats=False: None, and the call fetches nothing)"""
+        if not stats:
+            check(self._lib.adc_engine_td3_pop_update(self._h, int(updates), None))
+            return None
+        st = (_ffi.TD3Stats * self._td3_pop_members())()
+        check(self._lib.adc_engine_td3_pop_update(self._h, int(updates), st))
+        return [{k: getattr(x, k) for k, _ in _ffi.TD3Stats._fields_} for x in st]
+
+    def td3_pop_param_counts(self):
+        """(P, 2 Qc): the entries of a member's actor vectors and of its critics' vectors"""
+        p, q = C.c_int64(0), C.c_int64(0)
+        check(self._lib.adc_engine_td3_pop_param_counts(self._h, C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    def td3_pop_state(self, member, state=None):
+        """one member's state as td3_state's (the counters are the population's).  get (no state): the dict; set: such a dict"""
+        P, Q = self.td3_pop_param_counts()
+        size = lambda k: Q if "psi" in k else P
+        if state is None:
+            st = {k: np.zeros(size(k), np.float32) for k in self.TD3_STATE}
+            u, a = C.c_int64(0), C.c_int64(0)
+            check(self._lib.adc_engine_td3_pop_state_get(self._h, int(member), *(st[k].ctypes.data for k in self.TD3_STATE), C.byref(u), C.byref(a)))
+            st["updates"], st["actor_steps"] = u.value, a.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.TD3_STATE]
+        if any(a.shape != (size(k),) for k, a in zip(self.TD3_STATE, arr)):
+            raise ValueError(f"td3_pop_state: the actor's vectors have {P} entries, the critics' {Q}")
+        check(self._lib.adc_engine_td3_pop_state_set(self._h, int(member), *(a.ctypes.data for a in arr), int(state["updates"]), int(state["actor_steps"])))
+
+    def td3_pop_set_config(self, member, **options):
+        """a member's hyperparameters from the next update on (options as td3_config's; the shared fields may not change)"""
+        cfg = self.td3_config(**options)
+        check(self._lib.adc_engine_td3_pop_set_config(self._h, int(member), C.byref(cfg)))
+
+    def td3_pop_copy(self, src, dst, with_ring=False):
+        """actor, critics, targets and optimiser moments of member src into member dst on the device (with_ring: its ring too);
+        dst keeps its configuration, envs and exploration"""
+        check(self._lib.adc_engine_td3_pop_copy(self._h, int(src), int(dst), 1 if with_ring else 0))
 
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))

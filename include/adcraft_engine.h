@@ -758,6 +758,58 @@ int adc_engine_td3_state_set(adc_engine *e, const float *theta_p, const float *p
                              const float *m_theta_p, const float *v_theta_p, const float *m_psi_q, const float *v_psi_q, int64_t updates,
                              int64_t actor_steps);
 
+/* ---- TD3 learner populations: M independent off-policy learners in lock-step on one engine ------------------------------------
+ * Over learners (adc_engine_mlp_learners, M >= 1, the free log_std head): member m has its own actor (its learner's policy layers),
+ * exploration sigma (its learner's log_std: adc_engine_mlp_set_learner_log_std, read by the next act), twin critics, target
+ * networks, optimiser moments, adc_td3_config and replay ring of `capacity` transitions; it collects on its own envs
+ * [m n, (m + 1) n), n = N / M, and all members store and update together, every kernel launch covering all of them: the
+ * launches and host round trips of an update do not grow with M.  The law is csrc/adc_td3.h as it is: everything member m
+ * computes - ring contents, batch indices, targets, both gradients, theta, psi, both targets, all four moment vectors,
+ * statistics - is bit for bit what adc_engine_td3_* computes on an engine of n envs at env_id_base + m n with the same
+ * parameter planes, engine seed, agent seeds, initial actor and critics, log_std and configuration.  A member's ring slot of
+ * sample s = (t - t0) n + local env is (written + s) mod capacity; its td3 key is that of its own seed (0: the engine's); the
+ * chunks of the float64 sums are 1024 consecutive batch elements of the member.  written, size, updates and actor_steps are
+ * single counters: the members move together.
+ * adc_td3_pop_config_check (host only): every configuration passes adc_td3_config_check; count is 1 (shared) or `members`;
+ * members divides num_envs and is at most 65535; batch_size, capacity, n_critic_layers, critic_widths and policy_delay are
+ * equal in all; every other field may differ per member.  The network shapes, the activation, the observation normalisation and
+ * the critics' action normalisation are shared.  adc_engine_td3_pop_init needs learners, the free log_std head, a record with
+ * ADC_ROLLOUT_OBS and no other trainer alive (ADC_ESTATE otherwise; adc_engine_td3_init keeps refusing an engine with
+ * learners); every member's theta starts as its device policy; a refused allocation is ADC_ENOMEM and leaves the engine as it
+ * was.  The trainer does not survive adc_engine_mlp_init, adc_engine_mlp_learners or adc_engine_rollout_enable.  With no
+ * member clipping (max_grad_norm 0 in all) adc_engine_td3_pop_update only enqueues kernels - the optimiser constants of up to 64
+ * updates go up in one copy in front of them - and ends with one copy of the statistics; when any member clips, all members'
+ * squared norms come down in one copy per step and their scales go up in one. */
+int adc_td3_pop_config_check(const adc_td3_config *cfgs, int32_t count, int32_t num_envs, int32_t members, const char **message);
+int adc_engine_td3_pop_init(adc_engine *e, const adc_td3_config *cfgs, int32_t count);
+/* as adc_engine_td3_set_critic_layer, for one member */
+int adc_engine_td3_pop_set_critic_layer(adc_engine *e, int32_t member, int32_t critic, int32_t layer, const float *weights_in_out, const float *bias_out);
+int adc_engine_td3_pop_set_action_norm(adc_engine *e, const float *shift_a, const float *scale_a);       /* shared by all members */
+/* the member's targets become copies of its actor and critics; member -1: every member's */
+int adc_engine_td3_pop_sync_targets(adc_engine *e, int32_t member);
+/* the record's days not yet stored into every member's ring; *stored_per_member (may be NULL): the transitions each member appended */
+int adc_engine_td3_pop_store(adc_engine *e, int64_t *stored_per_member);
+int adc_engine_td3_pop_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity, int32_t *batch_size);   /* any may be NULL */
+/* one member's ring: as adc_engine_td3_buffer_fetch / _load (load sets the one `written` all members share) */
+int adc_engine_td3_pop_buffer_fetch(adc_engine *e, int32_t member, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done, float *x2);
+int adc_engine_td3_pop_buffer_load(adc_engine *e, int32_t member, int64_t slot, int64_t count, const float *x, const float *a, const float *r,
+                                   const uint8_t *done, const float *x2, int64_t written);
+int adc_engine_td3_pop_batch_indices(adc_engine *e, int32_t member, int64_t update, int32_t *idx_b);
+/* `updates` >= 1 critic updates of every member (and the actor steps that fall among them); stats_m[M] or NULL */
+int adc_engine_td3_pop_update(adc_engine *e, int32_t updates, adc_td3_stats *stats_m);
+int adc_engine_td3_pop_param_counts(adc_engine *e, int64_t *actor_p, int64_t *critics_2qc);      /* of one member */
+/* one member's vectors as adc_engine_td3_state_get / _set; the counters are the population's (set: the last call's stand) */
+int adc_engine_td3_pop_state_get(adc_engine *e, int32_t member, float *theta_p, float *psi_q, float *theta_target_p, float *psi_target_q,
+                                 float *m_theta_p, float *v_theta_p, float *m_psi_q, float *v_psi_q, int64_t *updates, int64_t *actor_steps);
+int adc_engine_td3_pop_state_set(adc_engine *e, int32_t member, const float *theta_p, const float *psi_q, const float *theta_target_p,
+                                 const float *psi_target_q, const float *m_theta_p, const float *v_theta_p, const float *m_psi_q, const float *v_psi_q,
+                                 int64_t updates, int64_t actor_steps);
+/* a member's hyperparameters from the next update on (the shared fields may not change) */
+int adc_engine_td3_pop_set_config(adc_engine *e, int32_t member, const adc_td3_config *cfg);
+/* actor, critics, all targets and moments of src into dst on the device - with_ring: its ring too - and dst's stores rebuilt; dst
+ * keeps its configuration, its envs and its log_std.  The primitive of population-based training; no scheduler sits on top */
+int adc_engine_td3_pop_copy(adc_engine *e, int32_t src, int32_t dst, int32_t with_ring);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be

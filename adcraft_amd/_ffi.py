@@ -21,6 +21,7 @@ ES_ADAM, ES_SGD = 0, 1
 ROLLOUT_OBS = 1
 PG_ADAM, PG_SGD = 0, 1
 TD3_ADAM, TD3_SGD = 0, 1
+PBT_PG, PBT_TD3 = 0, 1
 
 
 class EngineError(RuntimeError):
@@ -93,6 +94,16 @@ class TD3Stats(C.Structure):
     _fields_ = [("updates", C.c_int64), ("actor_steps", C.c_int64), ("buffer_size", C.c_int64), ("samples", C.c_int64),
                 ("critic_loss", C.c_double), ("q1_mean", C.c_double), ("q2_mean", C.c_double), ("y_mean", C.c_double),
                 ("actor_loss", C.c_double), ("critic_grad_norm", C.c_double), ("actor_grad_norm", C.c_double)]
+
+
+class PBTConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("replace_count", C.c_int32), ("fitness_ema", C.c_float), ("factor_lo", C.c_float),
+                ("factor_hi", C.c_float), ("log_factor_lo", C.c_float), ("log_factor_hi", C.c_float), ("tuned_mask", C.c_uint32),
+                ("lo", C.c_float * 8), ("hi", C.c_float * 8), ("with_ring", C.c_int32), ("seed", C.c_uint64)]
+
+
+class PBTResult(C.Structure):
+    _fields_ = [("fitness", C.c_double), ("smoothed", C.c_double), ("rank", C.c_int32), ("src", C.c_int32), ("hp", C.c_float * 8)]
 
 
 class Tape(C.Structure):
@@ -310,6 +321,16 @@ def lib():
         "adc_engine_td3_pop_set_config": ([vp, i32, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_pop_copy": ([vp, i32, i32, i32], C.c_int),
         "adc_td3_config_check": ([C.POINTER(TD3Config), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_pbt_config_check": ([C.POINTER(PBTConfig), i32, i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_pbt_init": ([vp, C.POINTER(PBTConfig)], C.c_int),
+        "adc_engine_pbt_fitness": ([vp, vp], C.c_int),
+        "adc_engine_pbt_exploit": ([vp, vp], C.c_int),
+        "adc_engine_pbt_step": ([vp, vp, C.POINTER(PBTResult)], C.c_int),
+        "adc_engine_pbt_state_get": ([vp, C.POINTER(i64), vp], C.c_int),
+        "adc_engine_pbt_state_set": ([vp, i64, vp], C.c_int),
+        "adc_pbt_fitness_host": ([i32, i32, i32, vp, vp], C.c_int),
+        "adc_pbt_plan_host": ([C.POINTER(PBTConfig), u64, i32, i64, vp, vp, vp, vp, vp], C.c_int),
+        "adc_pbt_explore_host": ([C.POINTER(PBTConfig), i32, C.c_uint32, vp, vp, vp], C.c_int),
         "adc_td3_param_counts_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "adc_td3_batch_indices_host": ([u64, i64, i64, i32, vp], C.c_int),
         "adc_td3_target_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), u64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp], C.c_int),

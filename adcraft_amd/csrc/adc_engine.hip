@@ -52,10 +52,12 @@
 //        the k_pg_pop_* twins run the same bodies for all members of a learner population in one launch.
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
+//   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
+//   parts/pbt_api.inc             the entry points of the population-based training scheduler over either kind of population.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -78,6 +80,7 @@
 #include "adc_es.h"
 #include "adc_pg.h"
 #include "adc_td3.h"
+#include "adc_pbt.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -98,6 +101,7 @@ namespace adck {
 #include "parts/kernel_pg.inc"
 #include "parts/kernel_td3.inc"
 #include "parts/kernel_td3_pop.inc"
+#include "parts/kernel_pbt.inc"
 }  // namespace adck
 using namespace adck;
 
@@ -105,4 +109,5 @@ using namespace adck;
 #include "parts/pg_api.inc"
 #include "parts/td3_api.inc"
 #include "parts/td3_pop_api.inc"
+#include "parts/pbt_api.inc"
 #include "parts/comm_api.inc"

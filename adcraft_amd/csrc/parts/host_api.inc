@@ -163,6 +163,17 @@ struct adc_engine {
     Td3PopStep *tp_dsteps = nullptr;
     size_t tp_stride[4] = {0, 0, 0, 0};         // floats between two members' stores, per flat vector (theta's: lrn_stride)
     size_t tp_part_stride = 0;                  // doubles of chunk partials per member
+    // the population-based training scheduler over the live pg_pop or td3_pop trainer (parts/pbt_api.inc; the law is adc_pbt.h).
+    // Its device arrays are the trainer's allocations (pg_allocs / td3_allocs): they go with it
+    bool have_pbt = false;
+    int pbt_kind = 0;                           // adc_pbt_kind
+    adc_pbt_config pbt_cfg{};
+    uint64_t pbt_key = 0;
+    int64_t pbt_round = 0;
+    std::vector<double> pbt_s, pbt_host_fit;    // [M] the smoothed fitness; the fetched fitness
+    std::vector<PbtPair> pbt_pairs;             // [M] the host's copy of pbt_dpairs
+    double *pbt_ret = nullptr, *pbt_fit = nullptr;      // [N] the envs' returns, [M] the members' fitness
+    PbtPair *pbt_dpairs = nullptr;
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -2818,9 +2829,19 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     if (record && (rc = mlp_record_outcome_chained(e))) return rc;
     return e->es_accumulate ? es_accumulate_chained(e) : ADC_OK;
 }
+// the scheduler of population-based training goes with the population trainer it sits on
+void pbt_forget(adc_engine *e, int kind)
+{
+    if (!e->have_pbt || e->pbt_kind != kind) return;
+    e->have_pbt = false;
+    e->pbt_round = 0;
+    e->pbt_s.clear(); e->pbt_host_fit.clear(); e->pbt_pairs.clear();
+    e->pbt_ret = e->pbt_fit = nullptr; e->pbt_dpairs = nullptr;
+}
 // the policy-gradient trainer goes with the policy and the record it was sized for
 void pg_drop(adc_engine *e)
 {
+    pbt_forget(e, ADC_PBT_PG);
     mlp_free(e, e->pg_allocs);
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
     e->pg_steps = 0;
@@ -2830,6 +2851,7 @@ void pg_drop(adc_engine *e)
 // ... and so does the off-policy trainer (its ring holds rows of that policy's input and action widths)
 void td3_drop(adc_engine *e)
 {
+    pbt_forget(e, ADC_PBT_TD3);
     mlp_free(e, e->td3_allocs);
     e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
     std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));

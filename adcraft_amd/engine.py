@@ -1150,6 +1150,92 @@ class StepEngine:
         dst keeps its configuration, envs and exploration"""
         check(self._lib.adc_engine_td3_pop_copy(self._h, int(src), int(dst), 1 if with_ring else 0))
 
+    # ---- population-based training over the live pg_pop / td3_pop trainer (parts/pbt_api.inc; baselines/pbt.py PBTScheduler) ----
+    PBT_IDS = {"pg": ("lr", "ent_coef", "eps_clip", "vf_coef"), "td3": ("actor_lr", "critic_lr", "target_noise", "tau", "sigma")}
+    PBT_KINDS = {"pg": _ffi.PBT_PG, "td3": _ffi.PBT_TD3}
+
+    @classmethod
+    def pbt_config(cls, kind, members, replace_count, tuned=(), bounds=None, factors=(0.8, 1.25), fitness_ema=0.0, with_ring=False, seed=0,
+                   check=True):
+        """an adc_pbt_config (csrc/adc_pbt.h) for a "pg" or "td3" population of `members`; tuned: names from PBT_IDS[kind];
+        bounds: {name: (lo, hi)} for every tuned name ("sigma": in sigma units, stored as float32 logarithms); factors: the
+        two perturbation factors; seed 0: the engine's; check: run adc_pbt_config_check here (pbt_init leaves it to the engine,
+        which knows the population)"""
+        if kind not in cls.PBT_IDS:
+            raise ValueError(f"unknown population kind {kind!r}: 'pg' or 'td3'")
+        ids, bounds = cls.PBT_IDS[kind], dict(bounds or {})
+        c = _ffi.PBTConfig()
+        c.struct_size = C.sizeof(_ffi.PBTConfig)
+        c.replace_count, c.fitness_ema, c.with_ring, c.seed = int(replace_count), fitness_ema, 1 if with_ring else 0, int(seed)
+        lo_f, hi_f = (float(x) for x in factors)
+        if not (lo_f > 0 and hi_f > 0):
+            raise ValueError("factors: two positive numbers")
+        c.factor_lo, c.factor_hi = lo_f, hi_f
+        c.log_factor_lo, c.log_factor_hi = np.float32(np.log(lo_f)), np.float32(np.log(hi_f))
+        for name in tuned:
+            if name not in ids:
+                raise ValueError(f"{name!r} is not a tunable hyperparameter of a {kind} population: {ids}")
+            if name not in bounds:
+                raise ValueError(f"bounds: (lo, hi) for {name!r}")
+            h, (lo, hi) = ids.index(name), bounds[name]
+            c.tuned_mask |= 1 << h
+            if name == "sigma":
+                if not (lo > 0 and hi > 0):
+                    raise ValueError("bounds of sigma: positive")
+                lo, hi = np.float32(np.log(lo)), np.float32(np.log(hi))
+            c.lo[h], c.hi[h] = lo, hi
+        msg = C.c_char_p()
+        if check and _ffi.lib().adc_pbt_config_check(C.byref(c), int(members), cls.PBT_KINDS[kind], C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad PBT configuration").decode())
+        return c
+
+    def pbt_init(self, kind, **options):
+        """a population-based training scheduler over the live pg_pop ("pg") or td3_pop ("td3") trainer; options as pbt_config's
+        (members is the learners' count).  It goes when that trainer goes."""
+        cfg = self.pbt_config(kind, max(getattr(self, "_learners", 0), 1), check=False, **options)
+        check(self._lib.adc_engine_pbt_init(self._h, C.byref(cfg)))
+        self._pbt_kind = kind
+
+    def pbt_fitness(self):
+        """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days, reduced on the device"""
+        f = np.zeros(max(getattr(self, "_learners", 0), 1), np.float64)
+        check(self._lib.adc_engine_pbt_fitness(self._h, f.ctypes.data))
+        return f
+
+    def pbt_exploit(self, src_of_member):
+        """the batched copy alone: member m becomes a copy of member src_of_member[m] (m itself or -1: kept) in a fixed number of
+        launches; no destination may also be a source"""
+        src = np.ascontiguousarray(src_of_member, dtype=np.int32)
+        if src.shape != (max(getattr(self, "_learners", 0), 1),):
+            raise ValueError("pbt_exploit: one source per member")
+        check(self._lib.adc_engine_pbt_exploit(self._h, src.ctypes.data))
+
+    def pbt_step(self, fitness=None):
+        """one round: fitness (the device's, or `fitness` [M]), smoothing, plan, exploit, explore.  A dict of fitness, smoothed
+        [M] float64, rank, src [M] int32 (src -1: kept) and hp [M, 8] float32 (the members' hyperparameters by id after the round)"""
+        M = max(getattr(self, "_learners", 0), 1)
+        f = None if fitness is None else np.ascontiguousarray(fitness, dtype=np.float64)
+        if f is not None and f.shape != (M,):
+            raise ValueError("fitness: one value per member")
+        res = (_ffi.PBTResult * M)()
+        check(self._lib.adc_engine_pbt_step(self._h, None if f is None else f.ctypes.data, res))
+        return dict(fitness=np.array([r.fitness for r in res], np.float64), smoothed=np.array([r.smoothed for r in res], np.float64),
+                    rank=np.array([r.rank for r in res], np.int32), src=np.array([r.src for r in res], np.int32),
+                    hp=np.array([list(r.hp) for r in res], np.float32))
+
+    def pbt_state(self, state=None):
+        """get (no argument): dict of round and smoothed [M] float64; set: such a dict - with the trainer's own state the
+        scheduler continues bit for bit"""
+        M = max(getattr(self, "_learners", 0), 1)
+        if state is None:
+            r, s = C.c_int64(0), np.zeros(M, np.float64)
+            check(self._lib.adc_engine_pbt_state_get(self._h, C.byref(r), s.ctypes.data))
+            return dict(round=r.value, smoothed=s)
+        s = np.ascontiguousarray(state["smoothed"], dtype=np.float64)
+        if s.shape != (M,):
+            raise ValueError("pbt_state: one smoothed fitness per member")
+        check(self._lib.adc_engine_pbt_state_set(self._h, int(state["round"]), s.ctypes.data))
+
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
         self._rollout_obs = bool(obs) and int(horizon) > 0

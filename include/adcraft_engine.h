@@ -807,8 +807,60 @@ int adc_engine_td3_pop_state_set(adc_engine *e, int32_t member, const float *the
 /* a member's hyperparameters from the next update on (the shared fields may not change) */
 int adc_engine_td3_pop_set_config(adc_engine *e, int32_t member, const adc_td3_config *cfg);
 /* actor, critics, all targets and moments of src into dst on the device - with_ring: its ring too - and dst's stores rebuilt; dst
- * keeps its configuration, its envs and its log_std.  The primitive of population-based training; no scheduler sits on top */
+ * keeps its configuration, its envs and its log_std.  The primitive of population-based training (the scheduler: adc_engine_pbt_*) */
 int adc_engine_td3_pop_copy(adc_engine *e, int32_t src, int32_t dst, int32_t with_ring);
+
+/* ---- population-based training on the device: fitness, exploit, explore (the law is csrc/adc_pbt.h) ---------------------------
+ * A scheduler (Jaderberg et al. 2017: truncation selection, copy, perturb) over a live learner population - adc_engine_pg_pop_*
+ * (kind ADC_PBT_PG) or adc_engine_td3_pop_* (kind ADC_PBT_TD3); it goes whenever that trainer goes.  A round
+ * (adc_engine_pbt_step) is, in order: the members' fitness (reduced from the rollout record's reward on the device, only M
+ * doubles leave it; or fitness_m handed in), its smoothing, the plan (ranking, donor draw, explored values: on the host, from
+ * those M doubles), the exploit (ONE batched copy of every replaced member from its donor: weights, optimiser moments, the
+ * rebuild of the destination's stores; TD3: all four vectors, all four moment vectors and, with_ring, the ring), the explore
+ * (every replaced member's new hyperparameters into the host-mastered member table, which goes up in one copy; TD3's sigma:
+ * the destination's log_std from the donor's, in the log domain, inside the exploit's launch), round + 1.  The launches and host
+ * round trips of a round do not grow with M or replace_count: one wait before the plan, one at the end.
+ * Hyperparameter ids - PG: 0 lr, 1 ent_coef, 2 eps_clip, 3 vf_coef; TD3: 0 actor_lr, 1 critic_lr, 2 target_noise, 3 tau,
+ * 4 sigma (lo / hi / the result's hp in log units; see adc_pbt_result).  A replaced member keeps its envs, its agents' keys and
+ * ticks, its untuned hyperparameters and (TD3) its seed; it gets its donor's smoothed fitness and (PG) step count.
+ * adc_pbt_config_check (host only): struct_size; 2 <= members; 1 <= replace_count <= members / 2; 0 <= fitness_ema < 1; the
+ * factors positive and finite, the log factors finite; tuned_mask inside the kind's ids; for every tuned id lo <= hi, both
+ * inside what the trainer's own configuration check admits (so an explored configuration is always a legal one); with_ring 0
+ * for PG.  Refused (the engine stays usable): adc_engine_pbt_init without a population trainer (ADC_ESTATE) or with a bad
+ * configuration (ADC_EINVAL); adc_engine_pbt_fitness and a step without fitness_m with no day recorded (ADC_ESTATE);
+ * adc_engine_pbt_exploit with a destination that is also a source (ADC_EINVAL). */
+enum adc_pbt_kind { ADC_PBT_PG = 0, ADC_PBT_TD3 = 1 };
+typedef struct adc_pbt_config {
+    uint32_t struct_size;          /* sizeof(adc_pbt_config) */
+    int32_t replace_count;         /* q: the q worst members are replaced by copies of members among the q best */
+    float fitness_ema;             /* in [0, 1): the smoothing's weight of the past; 0: none */
+    float factor_lo, factor_hi;    /* > 0, finite: the two perturbation factors */
+    float log_factor_lo, log_factor_hi;    /* their float32 logarithms (TD3's sigma moves in the log domain) */
+    uint32_t tuned_mask;           /* bit h: hyperparameter id h is explored */
+    float lo[8], hi[8];            /* the explored value's bounds per id */
+    int32_t with_ring;             /* TD3: the exploit copies the donor's ring too */
+    uint64_t seed;                 /* of the donor draw and the factor bits; 0: the engine's seed */
+} adc_pbt_config;
+typedef struct adc_pbt_result {
+    double fitness;                /* the round's fitness of the member */
+    double smoothed;               /* after the round (a replaced member: its donor's) */
+    int32_t rank;                  /* the round's ranking: 0 the worst */
+    int32_t src;                   /* the donor the member was replaced from; -1: kept */
+    float hp[8];                   /* the member's hyperparameters by id after the round; TD3's id 4: the log-domain shift its
+                                      log_std got from its donor's before the clamp (0: kept) */
+} adc_pbt_result;
+int adc_pbt_config_check(const adc_pbt_config *cfg, int32_t members, int32_t kind, const char **message);
+int adc_engine_pbt_init(adc_engine *e, const adc_pbt_config *cfg);
+/* fitness_m[M] float64 of the recorded days so far */
+int adc_engine_pbt_fitness(adc_engine *e, double *fitness_m);
+/* the batched copy alone: member m becomes a copy of member src_of_m[m] (src_of_m[m] == m or -1: kept), as adc_engine_pg_pop_copy
+ * / adc_engine_td3_pop_copy (with_ring from the configuration) would make it pair by pair, in a fixed number of launches */
+int adc_engine_pbt_exploit(adc_engine *e, const int32_t *src_of_m);
+/* one round; fitness_m[M] may be NULL (the device's, from the record); result_m[M] may be NULL */
+int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_pbt_result *result_m);
+/* round and smoothed fitness [M]: a run resumed from them (with the trainer's own state) continues bit for bit (get: either may be NULL) */
+int adc_engine_pbt_state_get(adc_engine *e, int64_t *round, double *smoothed_m);
+int adc_engine_pbt_state_set(adc_engine *e, int64_t round, const double *smoothed_m);
 
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
@@ -933,6 +985,16 @@ int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, con
                             const float *psi_q, const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p,
                             double *sums2);
 int adc_td3_polyak_host(float tau, int64_t n, const float *param_n, float *target_n);
+/* the scheduler of population-based training on the host: the same code as adc_engine_pbt_step runs (adc_pbt.h).  `seed` is the
+ * effective seed (the configuration's, or the engine's when that is 0).  fitness: fitness_m[members] from a record's reward
+ * [days][num_envs].  plan: smoothed_m holds s of the rounds before (not read in round 0) and receives this round's s, before any
+ * copy; rank_m, src_m (-1: kept) and bits_m (the replaced member's factor bits w.y, 0 for the others) receive the plan.  explore:
+ * out_hp8 for a replaced member from its donor's values donor_hp8, its own values own_hp8 and its factor bits (TD3's id 4: one
+ * log_std component). */
+int adc_pbt_fitness_host(int32_t days, int32_t num_envs, int32_t members, const float *reward_tn, double *fitness_m);
+int adc_pbt_plan_host(const adc_pbt_config *cfg, uint64_t seed, int32_t members, int64_t round, const double *fitness_m, double *smoothed_m,
+                      int32_t *rank_m, int32_t *src_m, uint32_t *bits_m);
+int adc_pbt_explore_host(const adc_pbt_config *cfg, int32_t kind, uint32_t bits, const float *donor_hp8, const float *own_hp8, float *out_hp8);
 /* the checks adc_engine_mlp_init makes on a configuration for num_keywords keywords; *message (may be NULL) names the failure */
 int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const char **message);
 /* the law's own tanh (fn 0) and exp (fn 1) at one float32, and a sweep over every float32 in [lo, hi] against the host's float64

@@ -58,9 +58,11 @@ def a2c(**overrides):
 class PGTrainer:
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (collected stochastically whatever its
     own flag says); horizon: the days of one rollout.  config: ppo() / a2c() or keywords of their kind - `epochs`,
-    `minibatches` (must divide the engine's envs) and StepEngine.pg_config's options."""
+    `minibatches` (must divide the engine's envs) and StepEngine.pg_config's options.  normalize_observations: a running
+    mean / std filter of the raw observation on the device (StepEngine.obs_norm_*; the policy must normalise: its shift / scale
+    are where the filter starts), updated after every PPO / A2C update; obs_norm: dict(min_std=..., count_cap=...)."""
 
-    def __init__(self, engine, policy, horizon, agent_seeds=None, **config):
+    def __init__(self, engine, policy, horizon, agent_seeds=None, normalize_observations=False, obs_norm=None, **config):
         cfg = ppo(**config)
         self.epochs, minibatches = int(cfg.pop("epochs")), int(cfg.pop("minibatches"))
         if minibatches < 1 or engine.num_envs % minibatches:
@@ -70,6 +72,9 @@ class PGTrainer:
         engine.mlp_init(policy, seeds=agent_seeds, deterministic=False)
         engine.rollout_enable(self.horizon, obs=True)
         engine.pg_init(**self.config)
+        self.normalize_observations = bool(normalize_observations)
+        if self.normalize_observations:
+            engine.obs_norm_init(**dict(obs_norm or {}))
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -81,12 +86,23 @@ class PGTrainer:
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         stats = e.pg_update(self.epochs)
+        if self.normalize_observations:     # (after the update: its bootstrap value is evaluated under the vectors of the record)
+            e.obs_norm_update()
         self.history.append(stats)
         return stats
 
     def policy(self):
-        """an MLPPolicy holding the trained policy layers, value layers and log_std"""
-        return policy_from_flat(self._template, self.engine.pg_state()["theta"])
+        """an MLPPolicy holding the trained policy layers, value layers and log_std (and, with normalize_observations, the
+        filter's current shift and scale: it evaluates as the trainer's does)"""
+        out = policy_from_flat(self._template, self.engine.pg_state()["theta"])
+        if self.normalize_observations:
+            st = self.engine.obs_norm_state()
+            out.shift, out.scale = st["shift"], st["scale"]
+        return out
+
+    def obs_norm_state(self, state=None):
+        """the filter's state (StepEngine.obs_norm_state); with state() a run resumes bit for bit"""
+        return self.engine.obs_norm_state(0, state)
 
     def state(self, state=None):
         return self.engine.pg_state(state)
@@ -99,9 +115,11 @@ class PGPopulationTrainer:
 
     engine: a StepEngine that has been reset; policies: one MLPPolicy (every member starts from it) or M of equal shape - M is
     then the number of configs, or of policies; configs: one dict of ppo() / a2c() kind shared by all members or M of them;
-    `epochs` and `minibatches` (of a member's envs) must be equal in all of them.  agent_seeds: [N] as PGTrainer's."""
+    `epochs` and `minibatches` (of a member's envs) must be equal in all of them.  agent_seeds: [N] as PGTrainer's.
+    normalize_observations: one running observation filter PER MEMBER, fed from the member's own envs (the members' policies
+    may then carry different shift / scale: each member starts from its own); obs_norm: dict(min_std=..., count_cap=...)."""
 
-    def __init__(self, engine, policies, horizon, configs, agent_seeds=None):
+    def __init__(self, engine, policies, horizon, configs, agent_seeds=None, normalize_observations=False, obs_norm=None):
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         configs = [configs] if isinstance(configs, dict) else list(configs)
         if not policies or not configs:
@@ -111,7 +129,10 @@ class PGPopulationTrainer:
             raise ValueError(f"PGPopulationTrainer: {len(policies)} policies and {len(configs)} configurations: each is one (shared) or one per member")
         if any(p.shapes() != policies[0].shapes() for p in policies):
             raise ValueError("PGPopulationTrainer: the members' policies must have equal shapes (layers, value layers, free log_std, normalisation)")
+        self.normalize_observations = bool(normalize_observations)
         for p in policies[1:]:
+            if self.normalize_observations:
+                break
             if p.shift is not None and not (np.array_equal(p.shift, policies[0].shift) and np.array_equal(p.scale, policies[0].scale)):
                 raise ValueError("PGPopulationTrainer: the normalisation vectors are shared by all members: the policies' must be equal")
         cfgs = [ppo(**c) for c in configs]
@@ -134,6 +155,13 @@ class PGPopulationTrainer:
                 engine.mlp_set_learner(m, pol)
         engine.rollout_enable(self.horizon, obs=True)
         engine.pg_pop_init(self.configs)
+        if self.normalize_observations:
+            engine.obs_norm_init(per_member=True, **dict(obs_norm or {}))
+            if len(policies) > 1:
+                for m, pol in enumerate(policies):
+                    st = engine.obs_norm_state(m)
+                    st["shift"], st["scale"] = pol.shift, pol.scale
+                    engine.obs_norm_state(m, st)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -144,12 +172,22 @@ class PGPopulationTrainer:
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         stats = e.pg_pop_update(self.epochs)
+        if self.normalize_observations:
+            e.obs_norm_update()
         self.history.append(stats)
         return stats
 
     def policy(self, member):
-        """an MLPPolicy holding one member's trained policy layers, value layers and log_std"""
-        return policy_from_flat(self._templates[member], self.engine.pg_pop_state(member)["theta"])
+        """an MLPPolicy holding one member's trained policy layers, value layers and log_std (and, with normalize_observations,
+        the member's filter's current shift and scale)"""
+        out = policy_from_flat(self._templates[member], self.engine.pg_pop_state(member)["theta"])
+        if self.normalize_observations:
+            st = self.engine.obs_norm_state(member)
+            out.shift, out.scale = st["shift"], st["scale"]
+        return out
+
+    def obs_norm_state(self, member, state=None):
+        return self.engine.obs_norm_state(member, state)
 
     def returns(self):
         """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days (from the

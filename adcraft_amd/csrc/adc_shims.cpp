@@ -19,6 +19,7 @@
 #include "adc_pg.h"
 #include "adc_td3.h"
 #include "adc_pbt.h"
+#include "adc_norm.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -453,6 +454,38 @@ ADC_EXPORT int adc_es_update_host(const adc_es_config *cfg, uint64_t seed, int32
             if (grad_p) grad_p[p] = g;
         }
     }
+    return ADC_OK;
+}
+
+// ---- the running observation normaliser on the host (adc_norm.h: the code parts/kernel_obs_norm.inc runs) -----------------------
+ADC_EXPORT int adc_obs_norm_config_check(const adc_obs_norm_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    if (!cfg || cfg->struct_size != sizeof(adc_obs_norm_config)) msg = "adc_obs_norm_config: NULL or struct_size mismatch";
+    else if (!(cfg->min_std > 0.0 && cfg->min_std < (double)__builtin_inff())) msg = "min_std must be finite and > 0";
+    else if (cfg->count_cap < 0) msg = "count_cap >= 0 (0: no forgetting)";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+ADC_EXPORT int adc_obs_norm_host(const adc_obs_norm_config *cfg, int64_t S, int32_t D, const float *x_sd, int64_t *count, double *mean_d, double *m2_d,
+                                 float *shift_d, float *scale_d)
+{
+    if (adc_obs_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (S < 1 || D < 1 || !x_sd || !count || !mean_d || !m2_d || !shift_d || !scale_d || *count < 0) return ADC_EINVAL;
+    const adc::NormConfig c{cfg->min_std, cfg->count_cap};
+    const int64_t count0 = *count;
+    int64_t cnt = count0;
+    for (int32_t j = 0; j < D; ++j) {
+        const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::norm_chain_sum(part, x_sd[(size_t)i * (size_t)D + (size_t)j]); });
+        const double qx = adc::pg_csum(S, [&](double part, int64_t i) {
+            const float x = x_sd[(size_t)i * (size_t)D + (size_t)j];
+            return adc::pg_chain_mac(part, x, x);
+        });
+        cnt = count0;
+        adc::norm_finish(c, sx, qx, S, cnt, mean_d[j], m2_d[j], shift_d[j], scale_d[j]);
+    }
+    *count = cnt;
     return ADC_OK;
 }
 

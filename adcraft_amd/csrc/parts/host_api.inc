@@ -174,6 +174,18 @@ struct adc_engine {
     std::vector<PbtPair> pbt_pairs;             // [M] the host's copy of pbt_dpairs
     double *pbt_ret = nullptr, *pbt_fit = nullptr;      // [N] the envs' returns, [M] the members' fitness
     PbtPair *pbt_dpairs = nullptr;
+    // the running observation normaliser fed from the record (adc_engine_obs_norm_init; parts/kernel_obs_norm.inc,
+    // parts/obs_norm_api.inc; the law is adc_norm.h)
+    bool have_on = false;
+    adc_obs_norm_config on_cfg{};
+    int on_M = 0;                       // normalisers: 1 (shared) or the learners' count (per_member)
+    int on_t0 = 0;                      // the record's days [0, on_t0) have been consumed
+    ObsNormView on_view{};              // count, mean, M2 and the vectors the policy kernel reads ([on_M][D] each)
+    const float *on_shared_shift = nullptr, *on_shared_scale = nullptr;     // the policy's own [D] vectors (mp.shift / mp.scale without per-member ones)
+    double *on_part = nullptr;          // [on_M][chunks][2][D] chunk partials, grown on demand
+    size_t on_part_doubles = 0;
+    int32_t *on_src = nullptr;          // [on_M] adc_engine_obs_norm_copy's donors
+    std::vector<void *> on_allocs;
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -864,6 +876,8 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->ro_allocs) (void)hipFree(p);
     for (void *p : e->pg_allocs) (void)hipFree(p);
     for (void *p : e->td3_allocs) (void)hipFree(p);
+    for (void *p : e->on_allocs) (void)hipFree(p);
+    if (e->on_part) (void)hipFree(e->on_part);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -2860,9 +2874,25 @@ void td3_drop(adc_engine *e)
     e->tp_cfg.clear(); e->tp_mem.clear(); e->tp_steps.clear(); e->tp_host_sums.clear(); e->tp_critic_set.clear();
     e->tp_dmem = nullptr; e->tp_dsteps = nullptr;
 }
+// the observation normaliser goes with the policy, the learners and the record it was set up for; the policy kernel is back to
+// the policy's own vectors, which hold what adc_engine_mlp_set_norm last wrote
+void obs_norm_drop(adc_engine *e)
+{
+    if (!e->have_on) return;
+    if (e->on_cfg.per_member) { e->mp.shift = e->on_shared_shift; e->mp.scale = e->on_shared_scale; e->mp.norm_stride = 0; }
+    mlp_free(e, e->on_allocs);
+    if (e->on_part) { (void)hipFree(e->on_part); e->on_part = nullptr; }
+    e->on_part_doubles = 0;
+    e->have_on = false;
+    e->on_M = e->on_t0 = 0;
+    e->on_view = ObsNormView{};
+    e->on_shared_shift = e->on_shared_scale = nullptr;
+    e->on_src = nullptr;
+}
 // learners and the population trainer over them go with the policy they belong to (the engine is back to the centre policy)
 void learners_drop(adc_engine *e)
 {
+    obs_norm_drop(e);
     if (e->have_pg_pop) pg_drop(e);
     if (e->have_td3_pop) td3_drop(e);
     mlp_free(e, e->lrn_allocs);
@@ -3025,6 +3055,18 @@ ADC_EXPORT int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, cons
     if (!e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
     if (!shift_d || !scale_d) return fail(ADC_EINVAL, "shift or scale is NULL");
     ENGINE_GUARD(e);
+    if (e->have_on && e->on_cfg.per_member) {
+        // per-member vectors are in force: every member's row, and the policy's own vectors (the running moments are not touched)
+        const size_t D = (size_t)e->mp.D;
+        for (int m = 0; m < e->on_M; ++m) {
+            HIP_TRY(hipMemcpyAsync(e->on_view.shift + (size_t)m * D, shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->on_view.scale + (size_t)m * D, scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->on_shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->on_shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return ADC_OK;
+    }
     HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.shift), shift_d, (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.scale), scale_d, (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3542,6 +3584,7 @@ ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t
     ENGINE_GUARD(e);
     pg_drop(e);                         // (its advantages and scratch were sized for the old record)
     td3_drop(e);
+    obs_norm_drop(e);
     mlp_free(e, e->ro_allocs);
     e->ro_T = e->ro_t = 0;
     e->ro_obs = nullptr;
@@ -3567,6 +3610,7 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     ENGINE_GUARD(e);
     if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
     e->ro_t = 0;
+    e->on_t0 = 0;
     e->ro_deterministic = false;
     e->pg_adv_ready = false;
     e->td3_stored_t = 0;

@@ -26,6 +26,7 @@ struct MlpLearner {
 struct MlpView {
     MlpNet pol, val;
     const float *shift, *scale;             // [D] or null: no normalisation
+    size_t norm_stride;                     // floats between two learners' vectors (adc_engine_obs_norm_init, per_member); 0: shared
     const float *log_std;                   // [A] free parameter vector (head of A outputs)
     int activation, two_heads, clamp, deterministic;
     float ls_lo, ls_hi, clip_hi;
@@ -141,9 +142,11 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         const size_t o = (size_t)env * K;
         const double cum = v.cum_profit[env];
         const int32_t days = v.day_out[env];
+        // (learners may have a normaliser each: the env's member's row of the vectors; the stride is 0 whenever they are shared)
+        const size_t no = kMembers == 2 ? (size_t)p.member[env] * p.norm_stride : 0;
         for (int j = tid; j < D; j += kMlpBlock) {
             float xj = first ? 0.0f : adc::mlp_obs_at(j, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
-            if (p.shift) xj = adc::mlp_normalize(xj, p.shift[j], p.scale[j]);
+            if (p.shift) xj = adc::mlp_normalize(xj, p.shift[no + j], p.scale[no + j]);
             mlp_lds[j] = xj;
             if (mode == 0 && rec.obs) rec.obs[(size_t)env * D + j] = xj;
         }

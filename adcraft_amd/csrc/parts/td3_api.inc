@@ -164,6 +164,8 @@ ADC_EXPORT int adc_engine_td3_init(adc_engine *e, const adc_td3_config *cfg)
     if (adc_td3_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     if (int rc = td3_state_check(e)) return rc;
     if (e->have_pg) return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
+    if (e->have_on)
+        return fail(ADC_ESTATE, "a running observation normaliser is alive on this engine: the replay ring would hold inputs normalised by older vectors");
     const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, *cfg, 0);
     if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for off-policy training (LDS)");
     ENGINE_GUARD(e);

@@ -183,6 +183,8 @@ ADC_EXPORT int adc_engine_td3_pop_init(adc_engine *e, const adc_td3_config *cfgs
     if (e->have_td3) return fail(ADC_ESTATE, "a single-learner off-policy (TD3) trainer is alive on this engine (adc_engine_td3_init)");
     if (e->have_pg || e->have_pg_pop)
         return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
+    if (e->have_on)
+        return fail(ADC_ESTATE, "a running observation normaliser is alive on this engine: the replay ring would hold inputs normalised by older vectors");
     const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, cfgs[0], 0);
     if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for off-policy training (LDS)");
     ENGINE_GUARD(e);

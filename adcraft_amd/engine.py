@@ -1236,6 +1236,54 @@ class StepEngine:
             raise ValueError("pbt_state: one smoothed fitness per member")
         check(self._lib.adc_engine_pbt_state_set(self._h, int(state["round"]), s.ctypes.data))
 
+    # ---- the running observation normaliser fed from the record (parts/kernel_obs_norm.inc; the law is csrc/adc_norm.h) ----------
+    @classmethod
+    def obs_norm_config(cls, per_member=False, min_std=1e-2, count_cap=0):
+        """an adc_obs_norm_config: min_std the floor of the standard deviation; count_cap > 0 bounds the running count (the
+        horizon a drifting env needs), 0: off"""
+        c = _ffi.ObsNormConfig()
+        c.struct_size = C.sizeof(_ffi.ObsNormConfig)
+        c.per_member, c.min_std, c.count_cap = 1 if per_member else 0, float(min_std), int(count_cap)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_obs_norm_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad observation normaliser configuration").decode())
+        return c
+
+    def obs_norm_init(self, **options):
+        """a running mean / std filter of the raw observation, starting from the vectors in force (mlp_init with a normalising
+        policy first; per_member=True: one per learner, mlp_learners first); options as obs_norm_config's"""
+        cfg = self.obs_norm_config(**options)
+        check(self._lib.adc_engine_obs_norm_init(self._h, C.byref(cfg)))
+        self._obs_norm_members = max(getattr(self, "_learners", 0), 1) if cfg.per_member else 1
+
+    def obs_norm_update(self):
+        """merge the recorded days not yet consumed into the running moments and write the new shift / scale where the next
+        act reads them (after the trainer's update, before the next rollout_reset)"""
+        check(self._lib.adc_engine_obs_norm_update(self._h))
+
+    def obs_norm_state(self, member=0, state=None):
+        """one normaliser's state (member 0: the shared one).  get (no state): dict of count, mean, M2 [D] float64, shift, scale
+        [D] float32; set: such a dict - with the trainer's own state the run continues bit for bit"""
+        D = 5 * self.num_keywords + 2
+        if state is None:
+            st = dict(mean=np.zeros(D, np.float64), M2=np.zeros(D, np.float64), shift=np.zeros(D, np.float32), scale=np.zeros(D, np.float32))
+            n = C.c_int64(0)
+            check(self._lib.adc_engine_obs_norm_state_get(self._h, int(member), C.byref(n), *(st[k].ctypes.data for k in ("mean", "M2", "shift", "scale"))))
+            st["count"] = n.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=t) for k, t in (("mean", np.float64), ("M2", np.float64), ("shift", np.float32), ("scale", np.float32))]
+        if any(a.shape != (D,) for a in arr):
+            raise ValueError(f"obs_norm_state: mean, M2, shift and scale have {D} entries")
+        check(self._lib.adc_engine_obs_norm_state_set(self._h, int(member), int(state["count"]), *(a.ctypes.data for a in arr)))
+
+    def obs_norm_copy(self, src_of_member):
+        """every member's normaliser becomes that of member src_of_member[m] (m itself or -1: kept) in one launch; no
+        destination may also be a source (pbt_exploit's convention)"""
+        src = np.ascontiguousarray(src_of_member, dtype=np.int32)
+        if src.shape != (getattr(self, "_obs_norm_members", 1),):
+            raise ValueError("obs_norm_copy: one source per member")
+        check(self._lib.adc_engine_obs_norm_copy(self._h, src.ctypes.data))
+
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
         self._rollout_obs = bool(obs) and int(horizon) > 0

@@ -7,7 +7,12 @@ nothing but numpy and the engine is loaded) is trained on the sparse keyword law
 PPO-clip loss, Adam - so no observation, action or gradient crosses the bus.  Every few iterations the policy is evaluated
 deterministically on held-out keyword sets and its episode return and NCP are printed beside the zero-margin agent's.
 
+With --normalize-observations the hand-set input scaling is replaced by a running mean / std filter of the raw observation
+that lives on the device too (StepEngine.obs_norm_*): it starts from identity vectors (shift 0, scale 1) and is updated from
+every iteration's record after the PPO / A2C update.
+
 Usage: python examples/train_mlp_policy_ppo.py [--iterations 100] [--algo ppo|a2c] [--num-envs 4096] [--num-keywords 100]
+                                               [--normalize-observations]
 """
 import argparse
 import sys
@@ -59,6 +64,7 @@ def main():
     ap.add_argument("--reward-scale", type=float, default=0.1)
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
+    ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device, from identity vectors")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
@@ -69,7 +75,10 @@ def main():
     eng.set_all_params(synthetic.implicit_keyword_planes(N, K, seed=1, mean_volume=args.mean_volume))
     eng.reset()
     config = getattr(pg_trainer, args.algo)(lr=args.lr, reward_scale=args.reward_scale)
-    trainer = pg_trainer.PGTrainer(eng, with_value_network(default_policy(K, days=days), (32, 32)), days, **config)
+    policy = with_value_network(default_policy(K, days=days), (32, 32))
+    if args.normalize_observations:
+        policy.shift, policy.scale = np.zeros_like(policy.shift), np.ones_like(policy.scale)
+    trainer = pg_trainer.PGTrainer(eng, policy, days, normalize_observations=args.normalize_observations, **config)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
     print(f"{0:>10} {'':>9} {'':>7} {ret:10.2f} {ncp:8.3f}")

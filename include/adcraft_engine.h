@@ -862,6 +862,52 @@ int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_pbt_result *
 int adc_engine_pbt_state_get(adc_engine *e, int64_t *round, double *smoothed_m);
 int adc_engine_pbt_state_set(adc_engine *e, int64_t round, const double *smoothed_m);
 
+/* ---- the running observation normaliser on the device (the law is csrc/adc_norm.h) ------------------------------------------
+ * The mean and variance of the RAW observation, column by column, kept as (count, mean, M2) and merged batch by batch from the
+ * rollout record's network inputs (one read of the record, back to raw space through the vectors the rows were collected
+ * under); after every update the policy's shift / scale are float32(mean) and float32(1 / max(std, min_std)), written in place
+ * where the policy kernel reads them.  What Stable-Baselines3's VecNormalize and RLlib's MeanStdFilter do around an env, without
+ * the record leaving the device.  per_member: with learners active every learner has its own normaliser, fed from its own envs
+ * in its own order (member m's result is bit for bit a single engine's of its envs), and its own [D] vectors, each starting as
+ * the policy's; the act / step / bootstrap path then reads the env's member's.  `member` below is 0 for the shared normaliser.
+ * An update consumes the recorded days [t0, T) not yet consumed (t0: the day count at the previous update, 0 after
+ * adc_engine_rollout_reset and at the first init) and is ordered after the env groups' streams as adc_engine_pg_advantages is.
+ * A trainer calls it AFTER its PPO / A2C update and before the next adc_engine_rollout_reset: the update's bootstrap value is
+ * then evaluated under the vectors the record was collected with.  adc_engine_mlp_set_norm between two updates makes the days
+ * recorded before it samples under the wrong vectors: reset the record first.
+ * adc_obs_norm_config_check (host only): struct_size; min_std finite and > 0; count_cap >= 0 (0: no forgetting).
+ * adc_engine_obs_norm_init is refused (the engine stays usable): before adc_engine_mlp_init and its uploads (ADC_ESTATE); a policy
+ * initialised without normalisation (ADC_EINVAL); a current scale that is not finite or not > 0 (ADC_EINVAL); per_member without
+ * learners (ADC_ESTATE); a TD3 trainer, single or population, alive (ADC_ESTATE: its ring holds inputs normalised by older
+ * vectors - and adc_engine_td3_init / adc_engine_td3_pop_init are refused while a normaliser is alive).
+ * adc_engine_obs_norm_update is refused (ADC_ESTATE): no record or no ADC_ROLLOUT_OBS; no day recorded since the last update or
+ * adc_engine_rollout_reset.  The normaliser does not survive adc_engine_mlp_init, adc_engine_mlp_learners or
+ * adc_engine_rollout_enable (the policy kernel is back to the policy's own vectors).  While it lives adc_engine_mlp_set_norm
+ * keeps writing the shared vectors - every member's with per-member vectors - and leaves the running moments alone.
+ * state_get / state_set: count, mean[D], M2[D] (float64), shift[D], scale[D] (float32) of one normaliser (get: any may be NULL);
+ * a run resumed from them, together with the trainer's own state, continues bit for bit.
+ * adc_engine_obs_norm_copy: adc_engine_pbt_exploit's convention (src_of_m[m] == m or -1: kept): every replaced member's count,
+ * mean, M2, shift and scale become its donor's, in ONE launch whatever M is; a destination that is also a source is refused
+ * (ADC_EINVAL), so is a shared normaliser (ADC_ESTATE). */
+typedef struct adc_obs_norm_config {
+    uint32_t struct_size;          /* sizeof(adc_obs_norm_config) */
+    int32_t per_member;            /* one normaliser and one pair of vectors per learner (needs adc_engine_mlp_learners) */
+    double min_std;                /* > 0, finite: the floor of the standard deviation (scale <= 1 / min_std) */
+    int64_t count_cap;             /* > 0: the running count never exceeds it (M2 scaled down with it); 0: off */
+} adc_obs_norm_config;
+int adc_obs_norm_config_check(const adc_obs_norm_config *cfg, const char **message);
+int adc_engine_obs_norm_init(adc_engine *e, const adc_obs_norm_config *cfg);
+int adc_engine_obs_norm_update(adc_engine *e);
+int adc_engine_obs_norm_state_get(adc_engine *e, int32_t member, int64_t *count, double *mean_d, double *m2_d, float *shift_d, float *scale_d);
+int adc_engine_obs_norm_state_set(adc_engine *e, int32_t member, int64_t count, const double *mean_d, const double *m2_d, const float *shift_d,
+                                  const float *scale_d);
+int adc_engine_obs_norm_copy(adc_engine *e, const int32_t *src_of_m);
+/* one update on the host: the same code as the device's (adc_norm.h).  x_sd [S][D]: the batch's (already normalised) rows in
+ * the law's sample order; shift_d / scale_d hold the vectors the rows were collected under and receive the new ones; *count,
+ * mean_d, m2_d hold the running moments and receive the merged ones. */
+int adc_obs_norm_host(const adc_obs_norm_config *cfg, int64_t S, int32_t D, const float *x_sd, int64_t *count, double *mean_d, double *m2_d,
+                      float *shift_d, float *scale_d);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be

@@ -59,6 +59,9 @@ class PBTScheduler:
         if self.kind == "pg" and getattr(tr, "normalize_observations", False):
             # (a copied network takes its donor's observation filter with it: one launch, whatever the number of members)
             self.engine.obs_norm_copy(res["src"])
+        if self.kind == "pg" and getattr(tr, "normalize_rewards", False):
+            # (... and its donor's reward normaliser; the fitness above came from the raw recorded reward)
+            self.engine.rew_norm_copy(res["src"])
         old_log_std = [t.log_std.copy() for t in tr._templates] if self.kind == "td3" and "sigma" in self.tuned else None
         for m, src in enumerate(res["src"]):
             if src < 0:

@@ -55,14 +55,43 @@ def a2c(**overrides):
     return cfg
 
 
+def _rew_norm_options(normalize_rewards, rew_norm):
+    if rew_norm is not None and not isinstance(rew_norm, dict):
+        raise TypeError("rew_norm: a dict of min_std, clip, count_cap")
+    if rew_norm and not normalize_rewards:
+        raise ValueError("rew_norm given without normalize_rewards=True")
+    unknown = set(rew_norm or {}) - {"min_std", "clip", "count_cap"}
+    if unknown:
+        raise ValueError(f"rew_norm: unknown option(s) {sorted(unknown)}: min_std, clip, count_cap")
+
+
+def _rew_norm_state(engine, member, state, envs=None):
+    """get / set of one normaliser's moments and multiplier together with its envs' running returns (all envs, or the `envs`
+    of a member)"""
+    sl = slice(None) if envs is None else slice(member * envs, (member + 1) * envs)
+    if state is None:
+        st = engine.rew_norm_state(member)
+        st["returns"] = engine.rew_norm_returns()[sl].copy()
+        return st
+    engine.rew_norm_state(member, state)
+    g = engine.rew_norm_returns()
+    g[sl] = np.asarray(state["returns"], dtype=np.float64)
+    engine.rew_norm_returns(g)
+
+
 class PGTrainer:
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (collected stochastically whatever its
     own flag says); horizon: the days of one rollout.  config: ppo() / a2c() or keywords of their kind - `epochs`,
     `minibatches` (must divide the engine's envs) and StepEngine.pg_config's options.  normalize_observations: a running
     mean / std filter of the raw observation on the device (StepEngine.obs_norm_*; the policy must normalise: its shift / scale
-    are where the filter starts), updated after every PPO / A2C update; obs_norm: dict(min_std=..., count_cap=...)."""
+    are where the filter starts), updated after every PPO / A2C update; obs_norm: dict(min_std=..., count_cap=...).
+    normalize_rewards: the reward in GAE is divided by the running standard deviation of the discounted return, kept on the
+    device (StepEngine.rew_norm_*) and updated from every rollout BEFORE its PPO / A2C update; rew_norm: dict(min_std=...,
+    clip=..., count_cap=...)."""
 
-    def __init__(self, engine, policy, horizon, agent_seeds=None, normalize_observations=False, obs_norm=None, **config):
+    def __init__(self, engine, policy, horizon, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
+                 rew_norm=None, **config):
+        _rew_norm_options(normalize_rewards, rew_norm)
         cfg = ppo(**config)
         self.epochs, minibatches = int(cfg.pop("epochs")), int(cfg.pop("minibatches"))
         if minibatches < 1 or engine.num_envs % minibatches:
@@ -75,6 +104,9 @@ class PGTrainer:
         self.normalize_observations = bool(normalize_observations)
         if self.normalize_observations:
             engine.obs_norm_init(**dict(obs_norm or {}))
+        self.normalize_rewards = bool(normalize_rewards)
+        if self.normalize_rewards:
+            engine.rew_norm_init(**dict(rew_norm or {}))
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -85,6 +117,8 @@ class PGTrainer:
             e.reset(seeds=reset_seeds)
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
+        if self.normalize_rewards:          # (before the update: this record's rewards are scaled by statistics that include them)
+            e.rew_norm_update()
         stats = e.pg_update(self.epochs)
         if self.normalize_observations:     # (after the update: its bootstrap value is evaluated under the vectors of the record)
             e.obs_norm_update()
@@ -104,6 +138,11 @@ class PGTrainer:
         """the filter's state (StepEngine.obs_norm_state); with state() a run resumes bit for bit"""
         return self.engine.obs_norm_state(0, state)
 
+    def rew_norm_state(self, state=None):
+        """the reward normaliser's state: StepEngine.rew_norm_state's dict plus `returns`, the envs' running discounted returns
+        [N]; with state() a run resumes bit for bit"""
+        return _rew_norm_state(self.engine, 0, state)
+
     def state(self, state=None):
         return self.engine.pg_state(state)
 
@@ -117,9 +156,13 @@ class PGPopulationTrainer:
     then the number of configs, or of policies; configs: one dict of ppo() / a2c() kind shared by all members or M of them;
     `epochs` and `minibatches` (of a member's envs) must be equal in all of them.  agent_seeds: [N] as PGTrainer's.
     normalize_observations: one running observation filter PER MEMBER, fed from the member's own envs (the members' policies
-    may then carry different shift / scale: each member starts from its own); obs_norm: dict(min_std=..., count_cap=...)."""
+    may then carry different shift / scale: each member starts from its own); obs_norm: dict(min_std=..., count_cap=...).
+    normalize_rewards: one running reward normaliser PER MEMBER (PGTrainer's), fed from the member's own envs under the
+    member's own gamma; rew_norm: dict(min_std=..., clip=..., count_cap=...)."""
 
-    def __init__(self, engine, policies, horizon, configs, agent_seeds=None, normalize_observations=False, obs_norm=None):
+    def __init__(self, engine, policies, horizon, configs, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
+                 rew_norm=None):
+        _rew_norm_options(normalize_rewards, rew_norm)
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         configs = [configs] if isinstance(configs, dict) else list(configs)
         if not policies or not configs:
@@ -162,6 +205,9 @@ class PGPopulationTrainer:
                     st = engine.obs_norm_state(m)
                     st["shift"], st["scale"] = pol.shift, pol.scale
                     engine.obs_norm_state(m, st)
+        self.normalize_rewards = bool(normalize_rewards)
+        if self.normalize_rewards:
+            engine.rew_norm_init(per_member=True, **dict(rew_norm or {}))
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -171,6 +217,8 @@ class PGPopulationTrainer:
             e.reset(seeds=reset_seeds)
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
+        if self.normalize_rewards:
+            e.rew_norm_update()
         stats = e.pg_pop_update(self.epochs)
         if self.normalize_observations:
             e.obs_norm_update()
@@ -188,6 +236,10 @@ class PGPopulationTrainer:
 
     def obs_norm_state(self, member, state=None):
         return self.engine.obs_norm_state(member, state)
+
+    def rew_norm_state(self, member, state=None):
+        """member's reward normaliser (PGTrainer.rew_norm_state's dict; `returns` holds the member's own envs')"""
+        return _rew_norm_state(self.engine, member, state, self.engine.num_envs // self.members)
 
     def returns(self):
         """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days (from the

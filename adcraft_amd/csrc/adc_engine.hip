@@ -54,12 +54,15 @@
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
 //   parts/kernel_obs_norm.inc     the running observation normaliser: the record's batch moments in one pass, the merge, the new vectors (adc_norm.h).
+//   parts/kernel_rew_norm.inc     the running reward normaliser: the discounted returns' scan, their moments, the merge, the multiplier;
+//        the GAE kernels under a multiplier and a clip (adc_rew_norm.h).
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over either kind of population.
 //   parts/obs_norm_api.inc        the entry points of the running observation normaliser.
+//   parts/rew_norm_api.inc        the entry points of the running reward normaliser.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -84,6 +87,7 @@
 #include "adc_td3.h"
 #include "adc_pbt.h"
 #include "adc_norm.h"
+#include "adc_rew_norm.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -106,6 +110,7 @@ namespace adck {
 #include "parts/kernel_td3_pop.inc"
 #include "parts/kernel_pbt.inc"
 #include "parts/kernel_obs_norm.inc"
+#include "parts/kernel_rew_norm.inc"
 }  // namespace adck
 using namespace adck;
 
@@ -115,4 +120,5 @@ using namespace adck;
 #include "parts/td3_pop_api.inc"
 #include "parts/pbt_api.inc"
 #include "parts/obs_norm_api.inc"
+#include "parts/rew_norm_api.inc"
 #include "parts/comm_api.inc"

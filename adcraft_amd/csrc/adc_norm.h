@@ -39,19 +39,11 @@ struct NormConfig {
 // one chain step of sx (qx's is pg_chain_mac(part, x, x))
 ADC_HD double norm_chain_sum(double part, float x) { return part + (double)x; }
 
-// everything after the chunks are joined, for one column: sx, qx over S samples under (shift, scale) merged into (count, mean, M2);
-// the new vectors
-ADC_HD void norm_finish(const NormConfig &c, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &shift, float &scale)
+// the batch's raw-space moments (mb, M2b over S samples) merged into the running (count, mean, M2), then the forgetting: the law's
+// "merge" and "forgetting" steps (adc_rew_norm.h's return moments go through the same code)
+ADC_HD void norm_merge(const NormConfig &c, double mb, double M2b, int64_t S, int64_t &count, double &mean, double &M2)
 {
     const double fs = (double)S;
-    const double mx = sx / fs;
-    const double qm = qx / fs, mm = mx * mx;
-    double vx = qm - mm;
-    vx = vx > 0.0 ? vx : 0.0;
-    const double sc = (double)scale;
-    const double mr = mx / sc, mb = (double)shift + mr;
-    const double sc2 = sc * sc, vb = vx / sc2;
-    const double M2b = vb * fs;
     if (count == 0) {
         mean = mb;
         M2 = M2b;
@@ -70,6 +62,22 @@ ADC_HD void norm_finish(const NormConfig &c, double sx, double qx, int64_t S, in
         M2 = M2 * f;
         count = c.count_cap;
     }
+}
+
+// everything after the chunks are joined, for one column: sx, qx over S samples under (shift, scale) merged into (count, mean, M2);
+// the new vectors
+ADC_HD void norm_finish(const NormConfig &c, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &shift, float &scale)
+{
+    const double fs = (double)S;
+    const double mx = sx / fs;
+    const double qm = qx / fs, mm = mx * mx;
+    double vx = qm - mm;
+    vx = vx > 0.0 ? vx : 0.0;
+    const double sc = (double)scale;
+    const double mr = mx / sc, mb = (double)shift + mr;
+    const double sc2 = sc * sc, vb = vx / sc2;
+    const double M2b = vb * fs;
+    norm_merge(c, mb, M2b, S, count, mean, M2);
     const double var = M2 / (double)count;
     double sd = __builtin_sqrt(var);
     sd = sd < c.min_std ? c.min_std : sd;

@@ -20,6 +20,7 @@
 #include "adc_td3.h"
 #include "adc_pbt.h"
 #include "adc_norm.h"
+#include "adc_rew_norm.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -547,6 +548,74 @@ ADC_EXPORT int adc_pg_gae_host(const adc_pg_config *cfg, int32_t days, int32_t n
             const size_t i = (size_t)t * N + n;
             const float v = value_tn[i];
             const float a = adc::pg_gae_day(reward_tn[i], cfg->reward_scale, terminated_tn[i] | truncated_tn[i], v, next, cfg->gamma, gl, adv);
+            adv_tn[i] = a;
+            ret_tn[i] = a + v;
+            next = v;
+        }
+    }
+    if (cfg->normalize_advantages) {
+        const int64_t cnt = (int64_t)days * num_envs;
+        const double mean = adc::pg_csum(cnt, [&](double part, int64_t i) { return part + (double)adv_tn[i]; }) / (double)cnt;
+        const double var = adc::pg_csum(cnt, [&](double part, int64_t i) { return adc::pg_chain_sqdev(part, adv_tn[i], mean); }) / (double)cnt;
+        const double sd = std::sqrt(var);
+        for (int64_t i = 0; i < cnt; ++i) adv_tn[i] = adc::pg_normalized(adv_tn[i], mean, sd);
+    }
+    return ADC_OK;
+}
+
+// ---- the running reward normaliser on the host (adc_rew_norm.h: the code parts/kernel_rew_norm.inc runs) ------------------------
+ADC_EXPORT int adc_rew_norm_config_check(const adc_rew_norm_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    if (!cfg || cfg->struct_size != sizeof(adc_rew_norm_config)) msg = "adc_rew_norm_config: NULL or struct_size mismatch";
+    else if (!(cfg->min_std > 0.0 && cfg->min_std < (double)__builtin_inff())) msg = "min_std must be finite and > 0";
+    else if (!(cfg->clip >= 0.0f && cfg->clip < __builtin_inff())) msg = "clip must be finite and >= 0 (0: off)";
+    else if (cfg->count_cap < 0) msg = "count_cap >= 0 (0: no forgetting)";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+ADC_EXPORT int adc_rew_norm_host(const adc_rew_norm_config *cfg, int32_t days, int32_t num_envs, const float *gamma_n, const float *reward_tn,
+                                 const uint8_t *terminated_tn, const uint8_t *truncated_tn, int64_t *count, double *mean, double *m2, float *scale,
+                                 double *carry_n)
+{
+    if (adc_rew_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (days < 1 || num_envs < 1 || !gamma_n || !reward_tn || !terminated_tn || !truncated_tn || !count || !mean || !m2 || !scale || !carry_n || *count < 0)
+        return ADC_EINVAL;
+    const size_t N = (size_t)num_envs;
+    const int64_t S = (int64_t)days * num_envs;
+    std::vector<double> g((size_t)S);
+    for (size_t n = 0; n < N; ++n) {
+        double G = carry_n[n];
+        for (int t = 0; t < days; ++t) {
+            const size_t i = (size_t)t * N + n;
+            g[i] = adc::rew_norm_scan_day(G, gamma_n[n], reward_tn[i], terminated_tn[i] | truncated_tn[i]);
+        }
+        carry_n[n] = G;
+    }
+    const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sum(part, g[(size_t)i]); });
+    const double qx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sq(part, g[(size_t)i]); });
+    adc::rew_norm_finish(adc::NormConfig{cfg->min_std, cfg->count_cap}, sx, qx, S, *count, *mean, *m2, *scale);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_pg_gae_norm_host(const adc_pg_config *cfg, int32_t days, int32_t num_envs, const float *reward_tn, const uint8_t *terminated_tn,
+                                    const uint8_t *truncated_tn, const float *value_tn, const float *bootstrap_n, const float *scale_n, float clip,
+                                    float *adv_tn, float *ret_tn)
+{
+    if (adc_pg_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (days < 1 || num_envs < 1 || !reward_tn || !terminated_tn || !truncated_tn || !value_tn || !bootstrap_n || !scale_n || !adv_tn || !ret_tn ||
+        !(clip >= 0.0f))
+        return ADC_EINVAL;
+    const size_t N = (size_t)num_envs;
+    const float gl = cfg->gamma * cfg->lambda;
+    for (size_t n = 0; n < N; ++n) {
+        float adv = 0.0f, next = bootstrap_n[n];
+        for (int t = days - 1; t >= 0; --t) {
+            const size_t i = (size_t)t * N + n;
+            const float v = value_tn[i];
+            const float a = adc::rew_norm_gae_day(reward_tn[i], cfg->reward_scale, scale_n[n], clip, terminated_tn[i] | truncated_tn[i], v, next, cfg->gamma,
+                                                  gl, adv);
             adv_tn[i] = a;
             ret_tn[i] = a + v;
             next = v;

@@ -186,6 +186,17 @@ struct adc_engine {
     size_t on_part_doubles = 0;
     int32_t *on_src = nullptr;          // [on_M] adc_engine_obs_norm_copy's donors
     std::vector<void *> on_allocs;
+    // the running reward normaliser fed from the record (adc_engine_rew_norm_init; parts/kernel_rew_norm.inc,
+    // parts/rew_norm_api.inc; the law is adc_rew_norm.h).  It lives with the PPO / A2C trainer whose gamma it discounts by
+    bool have_rn = false;
+    adc_rew_norm_config rn_cfg{};
+    int rn_M = 0;                       // normalisers: 1 (shared) or the learners' count (per_member)
+    int rn_t0 = 0;                      // the record's days [0, rn_t0) have been consumed
+    RewNormView rn_view{};              // count, mean, M2, the multiplier the GAE kernels read ([rn_M] each); the envs' carry [N]
+    double *rn_g = nullptr;             // [rn_M][S] the discounted returns of an update, in the law's sample order (at most ro_T x N)
+    double *rn_part = nullptr;          // [rn_M][chunks][2] chunk partials
+    int32_t *rn_src = nullptr;          // [rn_M] adc_engine_rew_norm_copy's donors
+    std::vector<void *> rn_allocs;
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -877,6 +888,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->pg_allocs) (void)hipFree(p);
     for (void *p : e->td3_allocs) (void)hipFree(p);
     for (void *p : e->on_allocs) (void)hipFree(p);
+    for (void *p : e->rn_allocs) (void)hipFree(p);
     if (e->on_part) (void)hipFree(e->on_part);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1171,6 +1183,12 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
     // the observation reset() returns is all zeros (gymnasium_kw_env.py:329-344): device-resident callers read it
     if (err == hipSuccess) {
         hipLaunchKernelGGL(k_clear_obs, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->v, d_mask);
+        err = hipGetLastError();
+    }
+    // (a reset env's running discounted return ends with its episode; nothing is enqueued without a reward normaliser)
+    if (err == hipSuccess && e->have_rn) {
+        hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
+                           e->rn_view.G);
         err = hipGetLastError();
     }
     hipError_t err2 = hipStreamSynchronize(e->stream);
@@ -2852,9 +2870,22 @@ void pbt_forget(adc_engine *e, int kind)
     e->pbt_s.clear(); e->pbt_host_fit.clear(); e->pbt_pairs.clear();
     e->pbt_ret = e->pbt_fit = nullptr; e->pbt_dpairs = nullptr;
 }
+// the reward normaliser goes with the policy-gradient trainer whose gamma it discounts by (the GAE kernels are back to
+// k_pg_gae / k_pg_pop_gae)
+void rew_norm_drop(adc_engine *e)
+{
+    if (!e->have_rn) return;
+    mlp_free(e, e->rn_allocs);
+    e->have_rn = false;
+    e->rn_M = e->rn_t0 = 0;
+    e->rn_view = RewNormView{};
+    e->rn_g = e->rn_part = nullptr;
+    e->rn_src = nullptr;
+}
 // the policy-gradient trainer goes with the policy and the record it was sized for
 void pg_drop(adc_engine *e)
 {
+    rew_norm_drop(e);
     pbt_forget(e, ADC_PBT_PG);
     mlp_free(e, e->pg_allocs);
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
@@ -2893,6 +2924,7 @@ void obs_norm_drop(adc_engine *e)
 void learners_drop(adc_engine *e)
 {
     obs_norm_drop(e);
+    rew_norm_drop(e);
     if (e->have_pg_pop) pg_drop(e);
     if (e->have_td3_pop) td3_drop(e);
     mlp_free(e, e->lrn_allocs);
@@ -3611,6 +3643,7 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
     e->ro_t = 0;
     e->on_t0 = 0;
+    e->rn_t0 = 0;
     e->ro_deterministic = false;
     e->pg_adv_ready = false;
     e->td3_stored_t = 0;

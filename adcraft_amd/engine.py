@@ -1284,6 +1284,62 @@ class StepEngine:
             raise ValueError("obs_norm_copy: one source per member")
         check(self._lib.adc_engine_obs_norm_copy(self._h, src.ctypes.data))
 
+    # ---- the running reward normaliser fed from the record (parts/kernel_rew_norm.inc; the law is csrc/adc_rew_norm.h) ----------
+    @classmethod
+    def rew_norm_config(cls, per_member=False, min_std=1e-2, clip=10.0, count_cap=0):
+        """an adc_rew_norm_config: min_std the floor of the discounted return's standard deviation; clip > 0 bounds the
+        normalised reward to [-clip, clip], 0: off; count_cap > 0 bounds the running count (the horizon a drifting env needs),
+        0: off.  The defaults are configuration (VecNormalize's clip), not measurements."""
+        c = _ffi.RewNormConfig()
+        c.struct_size = C.sizeof(_ffi.RewNormConfig)
+        c.per_member, c.min_std, c.clip, c.count_cap = 1 if per_member else 0, float(min_std), float(clip), int(count_cap)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_rew_norm_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad reward normaliser configuration").decode())
+        return c
+
+    def rew_norm_init(self, **options):
+        """a running filter of the discounted return's variance whose reciprocal standard deviation multiplies the reward in
+        GAE (pg_init or pg_pop_init first: it discounts by their gamma; per_member=True: one per learner of a population);
+        options as rew_norm_config's"""
+        cfg = self.rew_norm_config(**options)
+        check(self._lib.adc_engine_rew_norm_init(self._h, C.byref(cfg)))
+        self._rew_norm_members = max(getattr(self, "_learners", 0), 1) if cfg.per_member else 1
+
+    def rew_norm_update(self):
+        """merge the recorded days not yet consumed into the running moments and write the new multiplier where the next
+        advantages call reads it (before the trainer's update)"""
+        check(self._lib.adc_engine_rew_norm_update(self._h))
+
+    def rew_norm_state(self, member=0, state=None):
+        """one normaliser's state (member 0: the shared one).  get (no state): dict of count, mean, M2 (float64), scale
+        (float32); set: such a dict - with rew_norm_returns and the trainer's own state the run continues bit for bit"""
+        if state is None:
+            n, mean, m2, sc = C.c_int64(0), C.c_double(0.0), C.c_double(0.0), C.c_float(0.0)
+            check(self._lib.adc_engine_rew_norm_state_get(self._h, int(member), C.byref(n), C.byref(mean), C.byref(m2), C.byref(sc)))
+            return dict(count=n.value, mean=np.float64(mean.value), M2=np.float64(m2.value), scale=np.float32(sc.value))
+        check(self._lib.adc_engine_rew_norm_state_set(self._h, int(member), int(state["count"]), float(state["mean"]), float(state["M2"]),
+                                                      float(np.float32(state["scale"]))))
+
+    def rew_norm_returns(self, values=None):
+        """the envs' running discounted returns [N] float64 (the scan's carry).  get (no argument) or set"""
+        if values is None:
+            g = np.zeros(self.num_envs, np.float64)
+            check(self._lib.adc_engine_rew_norm_returns_get(self._h, g.ctypes.data))
+            return g
+        g = np.ascontiguousarray(values, dtype=np.float64)
+        if g.shape != (self.num_envs,):
+            raise ValueError("rew_norm_returns: one value per env")
+        check(self._lib.adc_engine_rew_norm_returns_set(self._h, g.ctypes.data))
+
+    def rew_norm_copy(self, src_of_member):
+        """every member's reward normaliser becomes that of member src_of_member[m] (m itself or -1: kept) in one launch; no
+        destination may also be a source (pbt_exploit's convention).  The envs' running returns stay."""
+        src = np.ascontiguousarray(src_of_member, dtype=np.int32)
+        if src.shape != (getattr(self, "_rew_norm_members", 1),):
+            raise ValueError("rew_norm_copy: one source per member")
+        check(self._lib.adc_engine_rew_norm_copy(self._h, src.ctypes.data))
+
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
         self._rollout_obs = bool(obs) and int(horizon) > 0

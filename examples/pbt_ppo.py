@@ -51,7 +51,7 @@ def run(args, with_pbt):
     eng.reset()
     lrs = np.logspace(np.log10(LR_LO), np.log10(LR_HI), M)
     configs = [pg_trainer.ppo(lr=float(lr), reward_scale=args.reward_scale, epochs=args.epochs, minibatches=args.minibatches) for lr in lrs]
-    trainer = pg_trainer.PGPopulationTrainer(eng, [member_policy(K, days, hidden, m) for m in range(M)], days, configs)
+    trainer = pg_trainer.PGPopulationTrainer(eng, [member_policy(K, days, hidden, m) for m in range(M)], days, configs, normalize_rewards=args.normalize_rewards)
     scheduler = PBTScheduler(trainer, replace_fraction=0.25, tuned=("lr",), bounds={"lr": (LR_LO, LR_HI)}, factors=(0.8, 1.25), fitness_ema=0.5,
                              every=args.every, seed=11) if with_pbt else None
     rng = np.random.default_rng(5)
@@ -84,6 +84,7 @@ def main():
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--reward-scale", type=float, default=0.1)
     ap.add_argument("--print-every", type=int, default=8)
+    ap.add_argument("--normalize-rewards", action="store_true", help="one running reward normaliser per member, on the device")
     args = ap.parse_args()
     print(f"{args.members} PPO learners x {args.envs_per_member} envs x {args.num_keywords} keywords on one engine, lr {LR_LO:.0e} .. {LR_HI:.0e}, "
           f"{args.days} days per iteration, {args.iterations} iterations")

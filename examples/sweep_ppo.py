@@ -60,6 +60,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--reward-scale", type=float, default=0.1)
+    ap.add_argument("--normalize-rewards", action="store_true", help="one running reward normaliser per member, on the device")
     ap.add_argument("--regimes", action="store_true", help="deal the grid over the paper's six regimes: one learner per (regime, cell)")
     args = ap.parse_args()
     K, days, n, budget, hidden = args.num_keywords, args.days, args.envs_per_member, 100000.0, (32, 32)
@@ -80,7 +81,7 @@ def main():
     policies = [member_policy(K, days, hidden, seed) for _, _, _, seed in cells]
     configs = [pg_trainer.ppo(lr=lr, ent_coef=ent, reward_scale=args.reward_scale, epochs=args.epochs, minibatches=args.minibatches)
                for _, lr, ent, _ in cells]
-    trainer = pg_trainer.PGPopulationTrainer(eng, policies, days, configs)
+    trainer = pg_trainer.PGPopulationTrainer(eng, policies, days, configs, normalize_rewards=args.normalize_rewards)
     print(f"{M} learners x {n} envs x {K} keywords on one engine, {days} days per iteration, {args.epochs} epochs x {args.minibatches} minibatches")
     print("member  " + " ".join(f"{m:>8d}" for m in range(M)))
     if args.regimes:

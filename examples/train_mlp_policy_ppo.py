@@ -9,10 +9,12 @@ deterministically on held-out keyword sets and its episode return and NCP are pr
 
 With --normalize-observations the hand-set input scaling is replaced by a running mean / std filter of the raw observation
 that lives on the device too (StepEngine.obs_norm_*): it starts from identity vectors (shift 0, scale 1) and is updated from
-every iteration's record after the PPO / A2C update.
+every iteration's record after the PPO / A2C update.  With --normalize-rewards the reward in GAE is divided by the running
+standard deviation of the discounted return (StepEngine.rew_norm_*), updated from every iteration's record before the update;
+--reward-scale then only sets where the first iteration starts.
 
 Usage: python examples/train_mlp_policy_ppo.py [--iterations 100] [--algo ppo|a2c] [--num-envs 4096] [--num-keywords 100]
-                                               [--normalize-observations]
+                                               [--normalize-observations] [--normalize-rewards]
 """
 import argparse
 import sys
@@ -65,6 +67,7 @@ def main():
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device, from identity vectors")
+    ap.add_argument("--normalize-rewards", action="store_true", help="divide the reward by the running std of the discounted return, on the device")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
@@ -78,7 +81,8 @@ def main():
     policy = with_value_network(default_policy(K, days=days), (32, 32))
     if args.normalize_observations:
         policy.shift, policy.scale = np.zeros_like(policy.shift), np.ones_like(policy.scale)
-    trainer = pg_trainer.PGTrainer(eng, policy, days, normalize_observations=args.normalize_observations, **config)
+    trainer = pg_trainer.PGTrainer(eng, policy, days, normalize_observations=args.normalize_observations,
+                                   normalize_rewards=args.normalize_rewards, **config)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
     print(f"{0:>10} {'':>9} {'':>7} {ret:10.2f} {ncp:8.3f}")

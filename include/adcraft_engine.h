@@ -908,6 +908,61 @@ int adc_engine_obs_norm_copy(adc_engine *e, const int32_t *src_of_m);
 int adc_obs_norm_host(const adc_obs_norm_config *cfg, int64_t S, int32_t D, const float *x_sd, int64_t *count, double *mean_d, double *m2_d,
                       float *shift_d, float *scale_d);
 
+/* ---- the running reward normaliser on the device (the law is csrc/adc_rew_norm.h) ----------------------------------------------
+ * The variance of the discounted return, kept as (count, mean, M2) in float64 and merged batch by batch from the rollout record's
+ * rewards; after every update the reward multiplier `scale` is float32(1 / max(std, min_std)), written in place where the GAE
+ * kernel reads it: under a live normaliser adc_engine_pg_advantages / _pg_update (and the _pg_pop_ calls) compute
+ * r = reward * reward_scale * scale, clipped to [-clip, clip] when clip > 0, and go on as before.  What Stable-Baselines3's
+ * VecNormalize(norm_reward=True) does around an env, without the record leaving the device.  The discount is the trainer's own
+ * gamma (adc_pg_config.gamma; under a population the env's member's, as in force when the update runs).  Every env carries its
+ * running discounted return G across updates and rollouts; a day that ends an episode zeroes it after its sample, and so does
+ * adc_engine_reset for the envs it resets.  per_member: every learner of a population has its own normaliser, fed from its own
+ * envs in its own order (member m's result is bit for bit a single engine's of its envs); otherwise one is shared by all envs.
+ * `member` below is 0 for the shared normaliser.
+ * An update consumes the recorded days [t0, T) not yet consumed (t0: the day count at the previous update, 0 after
+ * adc_engine_rollout_reset and at init), is three launches whatever the number of members is, synchronises nothing, and marks the
+ * advantages stale.  A trainer calls it BEFORE its PPO / A2C update: the record's rewards are scaled by statistics that include
+ * them.
+ * adc_rew_norm_config_check (host only): struct_size; min_std finite and > 0; clip finite and >= 0 (0: off); count_cap >= 0.
+ * adc_engine_rew_norm_init is refused (ADC_ESTATE, the engine stays usable): without a live PPO / A2C trainer (adc_engine_pg_init
+ * or adc_engine_pg_pop_init: it needs their gamma); per_member without a learner population; while a TD3 trainer lives (and
+ * adc_engine_td3_init / adc_engine_td3_pop_init are refused while a normaliser lives).
+ * adc_engine_rew_norm_update is refused (ADC_ESTATE): no record; no day recorded since the last update or adc_engine_rollout_reset.
+ * The normaliser does not survive adc_engine_pg_init, adc_engine_pg_pop_init, adc_engine_mlp_init, adc_engine_mlp_learners or
+ * adc_engine_rollout_enable.  adc_engine_pg_pop_set_config keeps working: a changed gamma is the one the next update uses.
+ * state_get / state_set: count, mean, M2 (float64), scale (float32) of one normaliser (get: any may be NULL); returns_get / _set:
+ * the envs' carry G [N] (float64).  A run resumed from them, together with the trainer's own state, continues bit for bit.
+ * adc_engine_rew_norm_copy: adc_engine_pbt_exploit's convention (src_of_m[m] == m or -1: kept): every replaced member's count,
+ * mean, M2 and scale become its donor's, in ONE launch whatever M is; a destination that is also a source is refused
+ * (ADC_EINVAL), so is a shared normaliser (ADC_ESTATE).  The carry is the envs' and is not copied. */
+typedef struct adc_rew_norm_config {
+    uint32_t struct_size;          /* sizeof(adc_rew_norm_config) */
+    int32_t per_member;            /* one normaliser per learner (needs adc_engine_pg_pop_init) */
+    double min_std;                /* > 0, finite: the floor of the standard deviation (scale <= 1 / min_std) */
+    float clip;                    /* > 0: the normalised reward is clipped to [-clip, clip]; 0: off */
+    int64_t count_cap;             /* > 0: the running count never exceeds it (M2 scaled down with it); 0: off */
+} adc_rew_norm_config;
+int adc_rew_norm_config_check(const adc_rew_norm_config *cfg, const char **message);
+int adc_engine_rew_norm_init(adc_engine *e, const adc_rew_norm_config *cfg);
+int adc_engine_rew_norm_update(adc_engine *e);
+int adc_engine_rew_norm_state_get(adc_engine *e, int32_t member, int64_t *count, double *mean, double *m2, float *scale);
+int adc_engine_rew_norm_state_set(adc_engine *e, int32_t member, int64_t count, double mean, double m2, float scale);
+int adc_engine_rew_norm_returns_get(adc_engine *e, double *g_n);
+int adc_engine_rew_norm_returns_set(adc_engine *e, const double *g_n);
+int adc_engine_rew_norm_copy(adc_engine *e, const int32_t *src_of_m);
+/* one update of one normaliser on the host: the same code as the device's (adc_rew_norm.h).  reward_tn, terminated_tn,
+ * truncated_tn [days][num_envs]: the normaliser's envs' days not yet consumed; gamma_n [num_envs]: every env's discount; carry_n
+ * [num_envs] holds the envs' running returns and receives the new ones; *count, *mean, *m2 hold the running moments and receive
+ * the merged ones; *scale receives the new multiplier. */
+int adc_rew_norm_host(const adc_rew_norm_config *cfg, int32_t days, int32_t num_envs, const float *gamma_n, const float *reward_tn,
+                      const uint8_t *terminated_tn, const uint8_t *truncated_tn, int64_t *count, double *mean, double *m2, float *scale,
+                      double *carry_n);
+/* adc_pg_gae_host under a normaliser: scale_n [num_envs] is every env's multiplier, clip as adc_rew_norm_config's.  With every
+ * scale 1 and clip 0 it gives adc_pg_gae_host's bits. */
+int adc_pg_gae_norm_host(const adc_pg_config *cfg, int32_t days, int32_t num_envs, const float *reward_tn, const uint8_t *terminated_tn,
+                         const uint8_t *truncated_tn, const float *value_tn, const float *bootstrap_n, const float *scale_n, float clip,
+                         float *adv_tn, float *ret_tn);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be

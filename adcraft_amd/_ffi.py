@@ -114,6 +114,11 @@ class RewNormConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("per_member", C.c_int32), ("min_std", C.c_double), ("clip", C.c_float), ("count_cap", C.c_int64)]
 
 
+class TD3NormConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("observations", C.c_int32), ("rewards", C.c_int32), ("per_member", C.c_int32), ("obs_min_std", C.c_double),
+                ("obs_count_cap", C.c_int64), ("rew_min_std", C.c_double), ("rew_count_cap", C.c_int64), ("rew_clip", C.c_float)]
+
+
 class Tape(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("volumes", "bid_cents", "x_impressions", "x_cost", "click", "conv", "rev_cents")]
                 + [(n, C.c_int64) for n in ("len_bid", "len_ximp", "len_xcost", "len_click", "len_conv", "len_rev")]
@@ -354,6 +359,17 @@ def lib():
         "adc_engine_rew_norm_returns_get": ([vp, vp], C.c_int),
         "adc_engine_rew_norm_returns_set": ([vp, vp], C.c_int),
         "adc_engine_rew_norm_copy": ([vp, vp], C.c_int),
+        "adc_td3_norm_config_check": ([C.POINTER(TD3NormConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_td3_norm_init": ([vp, C.POINTER(TD3NormConfig)], C.c_int),
+        "adc_engine_td3_norm_update": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_td3_norm_state_get": ([vp, i32, C.POINTER(i64), vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32)], C.c_int),
+        "adc_engine_td3_norm_state_set": ([vp, i32, i64, vp, vp, vp, vp, i64, f64, f64, f32], C.c_int),
+        "adc_engine_td3_norm_returns_get": ([vp, vp], C.c_int),
+        "adc_engine_td3_norm_returns_set": ([vp, vp], C.c_int),
+        "adc_engine_td3_norm_copy": ([vp, vp], C.c_int),
+        "adc_td3_norm_obs_host": ([C.POINTER(TD3NormConfig), i64, i32, vp, C.POINTER(i64), vp, vp, vp, vp], C.c_int),
+        "adc_td3_norm_rew_host": ([C.POINTER(TD3NormConfig), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32), vp], C.c_int),
+        "adc_td3_y_norm_host": ([C.POINTER(TD3Config), i32, vp, vp, vp, f32, f32, vp], C.c_int),
         "adc_rew_norm_host": ([C.POINTER(RewNormConfig), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32), vp], C.c_int),
         "adc_pg_gae_norm_host": ([C.POINTER(PGConfig), i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp], C.c_int),
         "adc_td3_param_counts_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), C.POINTER(i64), C.POINTER(i64)], C.c_int),

@@ -62,6 +62,10 @@ class PBTScheduler:
         if self.kind == "pg" and getattr(tr, "normalize_rewards", False):
             # (... and its donor's reward normaliser; the fitness above came from the raw recorded reward)
             self.engine.rew_norm_copy(res["src"])
+        if self.kind == "td3" and (getattr(tr, "normalize_observations", False) or getattr(tr, "normalize_rewards", False)):
+            # (a copied TD3 learner takes its donor's observation vectors, moments and reward multiplier with it: one launch; its envs'
+            # running returns stay, and the fitness above came from the raw recorded reward)
+            self.engine.td3_norm_copy(res["src"])
         old_log_std = [t.log_std.copy() for t in tr._templates] if self.kind == "td3" and "sigma" in self.tuned else None
         for m, src in enumerate(res["src"]):
             if src < 0:

@@ -56,20 +56,67 @@ def policy_from_actor(policy, theta):
     return out
 
 
+NORM_OPTIONS = ("obs_min_std", "obs_count_cap", "rew_min_std", "rew_count_cap", "rew_clip")
+
+
+def _norm_options(policies, normalize_observations, normalize_rewards, norm):
+    """the checks on the normalisers' arguments that need no device"""
+    if norm is not None and not isinstance(norm, dict):
+        raise TypeError("norm: a dict of " + ", ".join(NORM_OPTIONS))
+    if norm and not (normalize_observations or normalize_rewards):
+        raise ValueError("norm given without normalize_observations=True or normalize_rewards=True")
+    unknown = set(norm or {}) - set(NORM_OPTIONS)
+    if unknown:
+        raise ValueError(f"norm: unknown option(s) {sorted(unknown)}: " + ", ".join(NORM_OPTIONS))
+    if normalize_observations and any(p.shift is None for p in policies):
+        raise ValueError("normalize_observations needs a policy with normalisation vectors (shift / scale): they are the filter's start")
+    return dict(norm or {})
+
+
+def _with_vectors(policy, state):
+    """`policy` with the observation filter's current vectors"""
+    if "shift" in state:
+        policy.shift, policy.scale = state["shift"].copy(), state["scale"].copy()
+    return policy
+
+
+def _norm_state(engine, member, state, envs=None):
+    """StepEngine.td3_norm_state's dict plus `returns`, the (member's) envs' running discounted returns, when rewards are normalised"""
+    n = engine.num_envs if envs is None else envs
+    sl = slice(0, n) if envs is None else slice(member * n, (member + 1) * n)
+    if state is None:
+        st = engine.td3_norm_state(member)
+        if "rew_count" in st:
+            st["returns"] = engine.td3_norm_returns()[sl].copy()
+        return st
+    engine.td3_norm_state(member, state)
+    if "returns" in state:
+        g = engine.td3_norm_returns()
+        g[sl] = state["returns"]
+        engine.td3_norm_returns(g)
+
+
 class TD3Trainer:
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (K + 1 means, free log_std; a value network
     is ignored); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection;
     exploration_sigma: the standard deviation of the collection noise; learning_starts: transitions the ring must hold before
     the first update; updates_per_iteration: critic updates after every collection.  config: td3()'s other keys and
     StepEngine.td3_config's options, plus critic_seed (random_critics' seed), critics (two lists of layers, instead) and
-    action_norm ((shift, scale) [K + 1] for the critics' action inputs)."""
+    action_norm ((shift, scale) [K + 1] for the critics' action inputs).
+
+    normalize_observations / normalize_rewards: running normalisers on the device (StepEngine.td3_norm_*; csrc/adc_td3_norm.h).
+    The record and the ring then hold raw observations and raw rewards and every batch is normalised as it is sampled, with the
+    statistics updated from every collection BEFORE its updates; norm: dict(obs_min_std=..., obs_count_cap=..., rew_min_std=...,
+    rew_count_cap=..., rew_clip=...).  What they gain in learning has not been measured."""
 
     def __init__(self, engine, policy, critic_hidden=(256, 256), horizon=10, exploration_sigma=0.1, learning_starts=10000, updates_per_iteration=64,
-                 agent_seeds=None, **config):
+                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, **config):
+        norm = _norm_options([policy], normalize_observations, normalize_rewards, norm)
         if policy.log_std is None:
             raise ValueError("TD3 needs a policy that ends in K + 1 means with the free log_std vector")
+        self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
         cfg = dict(config)
-        critics, norm = cfg.pop("critics", None), cfg.pop("action_norm", None)
+        critics, action_norm = cfg.pop("critics", None), cfg.pop("action_norm", None)
         critic_seed = cfg.pop("critic_seed", 0)
         self.engine, self.horizon = engine, int(horizon)
         self.learning_starts, self.updates_per_iteration = int(learning_starts), int(updates_per_iteration)
@@ -79,7 +126,9 @@ class TD3Trainer:
         engine.mlp_init(self._template, seeds=agent_seeds, deterministic=False)
         engine.rollout_enable(self.horizon, obs=True)
         engine.td3_init(**self.config)
-        engine.td3_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed), action_norm=norm)
+        engine.td3_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed), action_norm=action_norm)
+        if self.normalize_observations or self.normalize_rewards:
+            engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self.history = []
 
     def set_exploration(self, sigma):
@@ -97,17 +146,25 @@ class TD3Trainer:
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.td3_store()
+        if self.normalize_observations or self.normalize_rewards:
+            e.td3_norm_update()             # (the batches below are scaled by statistics that include the newest days)
         size = e.td3_buffer(fetch=False)["size"]
         stats = e.td3_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
         self.history.append(stats)
         return stats
 
     def policy(self):
-        """an MLPPolicy holding the trained actor (its log_std the exploration's)"""
-        return policy_from_actor(self._template, self.engine.td3_state()["theta"])
+        """an MLPPolicy holding the trained actor (its log_std the exploration's; under a running observation normaliser its
+        shift / scale are the current vectors)"""
+        pol = policy_from_actor(self._template, self.engine.td3_state()["theta"])
+        return _with_vectors(pol, self.engine.td3_norm_state()) if self.normalize_observations else pol
 
     def state(self, state=None):
         return self.engine.td3_state(state)
+
+    def norm_state(self, state=None):
+        """the normalisers' state: StepEngine.td3_norm_state's dict plus `returns`, the envs' running discounted returns; get or set"""
+        return _norm_state(self.engine, 0, state)
 
 
 class TD3PopulationTrainer:
@@ -120,12 +177,19 @@ class TD3PopulationTrainer:
     sigmas: one exploration sigma or M, or None: every configuration's exploration_sigma (default 0.1); configs: one dict of
     TD3Trainer's keyword options (td3()'s keys and StepEngine.td3_config's, plus critic_seed, critics, action_norm) shared by
     all members or M of them - M is `members`, or the largest of the three counts.  critic_hidden, batch_size, capacity, policy_delay, learning_starts (transitions of a member's ring),
-    updates_per_iteration and action_norm must be equal in all configurations: the members move together."""
+    updates_per_iteration and action_norm must be equal in all configurations: the members move together.
+
+    normalize_observations / normalize_rewards: every member has its own running normalisers (TD3Trainer's, per member: a
+    member's statistics are bit for bit a single trainer's of its envs; the reward's discount is the member's own gamma); norm as
+    TD3Trainer's."""
 
     SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
 
-    def __init__(self, engine, policies, sigmas, configs, horizon=10, agent_seeds=None, members=None):
+    def __init__(self, engine, policies, sigmas, configs, horizon=10, agent_seeds=None, members=None, normalize_observations=False,
+                 normalize_rewards=False, norm=None):
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
+        norm = _norm_options(policies, normalize_observations, normalize_rewards, norm)
+        self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
         configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
         own = [c.pop("exploration_sigma", 0.1) for c in configs]
         sigmas = own if sigmas is None else [float(sigmas)] if np.isscalar(sigmas) else [float(s) for s in sigmas]
@@ -168,6 +232,8 @@ class TD3PopulationTrainer:
         engine.td3_pop_init(self.configs)
         for m in range(members):
             engine.td3_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]), action_norm=norms[0] if m == 0 else None)
+        if self.normalize_observations or self.normalize_rewards:
+            engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self.history = []
 
     def set_exploration(self, sigma, member=None):
@@ -186,14 +252,18 @@ class TD3PopulationTrainer:
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.td3_pop_store()
+        if self.normalize_observations or self.normalize_rewards:
+            e.td3_norm_update()             # (one call for all members, whatever their number)
         size = e.td3_pop_buffer(fetch=False)["size"]
         stats = e.td3_pop_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
         self.history.append(stats)
         return stats
 
     def policy(self, member):
-        """an MLPPolicy holding one member's trained actor (its log_std the member's exploration's)"""
-        return policy_from_actor(self._templates[member], self.engine.td3_pop_state(member)["theta"])
+        """an MLPPolicy holding one member's trained actor (its log_std the member's exploration's; under running observation
+        normalisers its shift / scale are the member's current vectors)"""
+        pol = policy_from_actor(self._templates[member], self.engine.td3_pop_state(member)["theta"])
+        return _with_vectors(pol, self.engine.td3_norm_state(member)) if self.normalize_observations else pol
 
     def returns(self):
         """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days"""
@@ -202,6 +272,10 @@ class TD3PopulationTrainer:
 
     def state(self, member, state=None):
         return self.engine.td3_pop_state(member, state)
+
+    def norm_state(self, member, state=None):
+        """member's normalisers (TD3Trainer.norm_state's dict; `returns` holds the member's own envs')"""
+        return _norm_state(self.engine, member, state, self.engine.num_envs // self.members)
 
 
 __all__ = ["TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]

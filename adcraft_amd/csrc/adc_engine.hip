@@ -56,6 +56,8 @@
 //   parts/kernel_obs_norm.inc     the running observation normaliser: the record's batch moments in one pass, the merge, the new vectors (adc_norm.h).
 //   parts/kernel_rew_norm.inc     the running reward normaliser: the discounted returns' scan, their moments, the merge, the multiplier;
 //        the GAE kernels under a multiplier and a clip (adc_rew_norm.h).
+//   parts/kernel_td3_norm.inc     the TD3 learners' running normalisers over raw rows: the observation finish, the returns' scan under
+//        the TD3 discount, the batched copy (adc_td3_norm.h); the batch kernels of kernel_td3 / kernel_td3_pop normalise as they gather.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
@@ -63,6 +65,7 @@
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over either kind of population.
 //   parts/obs_norm_api.inc        the entry points of the running observation normaliser.
 //   parts/rew_norm_api.inc        the entry points of the running reward normaliser.
+//   parts/td3_norm_api.inc        the entry points of the TD3 learners' running normalisers.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -88,6 +91,7 @@
 #include "adc_pbt.h"
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
+#include "adc_td3_norm.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -111,6 +115,7 @@ namespace adck {
 #include "parts/kernel_pbt.inc"
 #include "parts/kernel_obs_norm.inc"
 #include "parts/kernel_rew_norm.inc"
+#include "parts/kernel_td3_norm.inc"
 }  // namespace adck
 using namespace adck;
 
@@ -121,4 +126,5 @@ using namespace adck;
 #include "parts/pbt_api.inc"
 #include "parts/obs_norm_api.inc"
 #include "parts/rew_norm_api.inc"
+#include "parts/td3_norm_api.inc"
 #include "parts/comm_api.inc"

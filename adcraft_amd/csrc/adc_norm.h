@@ -85,4 +85,22 @@ ADC_HD void norm_finish(const NormConfig &c, double sx, double qx, int64_t S, in
     scale = (float)(1.0 / sd);
 }
 
+// norm_finish for RAW rows (adc_td3_norm.h: the TD3 learners' record and ring hold the flat observation itself): the batch's
+// moments are raw-space moments as they stand, there is no back-conversion through the vectors in force
+ADC_HD void norm_finish_raw(const NormConfig &c, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &shift, float &scale)
+{
+    const double fs = (double)S;
+    const double mx = sx / fs;
+    const double qm = qx / fs, mm = mx * mx;
+    double vx = qm - mm;
+    vx = vx > 0.0 ? vx : 0.0;
+    const double M2b = vx * fs;
+    norm_merge(c, mx, M2b, S, count, mean, M2);
+    const double var = M2 / (double)count;
+    double sd = __builtin_sqrt(var);
+    sd = sd < c.min_std ? c.min_std : sd;
+    shift = (float)mean;
+    scale = (float)(1.0 / sd);
+}
+
 }  // namespace adc

@@ -21,6 +21,7 @@
 #include "adc_pbt.h"
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
+#include "adc_td3_norm.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -628,6 +629,76 @@ ADC_EXPORT int adc_pg_gae_norm_host(const adc_pg_config *cfg, int32_t days, int3
         const double sd = std::sqrt(var);
         for (int64_t i = 0; i < cnt; ++i) adv_tn[i] = adc::pg_normalized(adv_tn[i], mean, sd);
     }
+    return ADC_OK;
+}
+
+// ---- the TD3 learners' running normalisers on the host (adc_td3_norm.h: the code parts/kernel_td3_norm.inc runs) ----------------
+ADC_EXPORT int adc_td3_norm_config_check(const adc_td3_norm_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    if (!cfg || cfg->struct_size != sizeof(adc_td3_norm_config)) msg = "adc_td3_norm_config: NULL or struct_size mismatch";
+    else if (!cfg->observations && !cfg->rewards) msg = "observations or rewards: at least one must be nonzero";
+    else if (!(cfg->obs_min_std > 0.0 && cfg->obs_min_std < (double)__builtin_inff())) msg = "obs_min_std must be finite and > 0";
+    else if (cfg->obs_count_cap < 0) msg = "obs_count_cap >= 0 (0: no forgetting)";
+    else if (!(cfg->rew_min_std > 0.0 && cfg->rew_min_std < (double)__builtin_inff())) msg = "rew_min_std must be finite and > 0";
+    else if (cfg->rew_count_cap < 0) msg = "rew_count_cap >= 0 (0: no forgetting)";
+    else if (!(cfg->rew_clip >= 0.0f && cfg->rew_clip < __builtin_inff())) msg = "rew_clip must be finite and >= 0 (0: off)";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_norm_obs_host(const adc_td3_norm_config *cfg, int64_t S, int32_t D, const float *x_sd, int64_t *count, double *mean_d, double *m2_d,
+                                     float *shift_d, float *scale_d)
+{
+    if (adc_td3_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (S < 1 || D < 1 || !x_sd || !count || !mean_d || !m2_d || !shift_d || !scale_d || *count < 0) return ADC_EINVAL;
+    const adc::NormConfig c{cfg->obs_min_std, cfg->obs_count_cap};
+    const int64_t count0 = *count;
+    int64_t cnt = count0;
+    for (int32_t j = 0; j < D; ++j) {
+        const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::norm_chain_sum(part, x_sd[(size_t)i * (size_t)D + (size_t)j]); });
+        const double qx = adc::pg_csum(S, [&](double part, int64_t i) {
+            const float x = x_sd[(size_t)i * (size_t)D + (size_t)j];
+            return adc::pg_chain_mac(part, x, x);
+        });
+        cnt = count0;
+        adc::norm_finish_raw(c, sx, qx, S, cnt, mean_d[j], m2_d[j], shift_d[j], scale_d[j]);
+    }
+    *count = cnt;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_norm_rew_host(const adc_td3_norm_config *cfg, int32_t days, int32_t num_envs, const float *gamma_n, const float *reward_tn,
+                                     const uint8_t *terminated_tn, const uint8_t *truncated_tn, int64_t *count, double *mean, double *m2, float *scale,
+                                     double *carry_n)
+{
+    if (adc_td3_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (days < 1 || num_envs < 1 || !gamma_n || !reward_tn || !terminated_tn || !truncated_tn || !count || !mean || !m2 || !scale || !carry_n || *count < 0)
+        return ADC_EINVAL;
+    const size_t N = (size_t)num_envs;
+    const int64_t S = (int64_t)days * num_envs;
+    std::vector<double> g((size_t)S);
+    for (size_t n = 0; n < N; ++n) {
+        double G = carry_n[n];
+        for (int t = 0; t < days; ++t) {
+            const size_t i = (size_t)t * N + n;
+            g[i] = adc::rew_norm_scan_day(G, gamma_n[n], reward_tn[i], terminated_tn[i] | truncated_tn[i]);
+        }
+        carry_n[n] = G;
+    }
+    const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sum(part, g[(size_t)i]); });
+    const double qx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sq(part, g[(size_t)i]); });
+    adc::rew_norm_finish(adc::NormConfig{cfg->rew_min_std, cfg->rew_count_cap}, sx, qx, S, *count, *mean, *m2, *scale);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_y_norm_host(const adc_td3_config *td3, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, float scale, float clip,
+                                   float *y_b)
+{
+    if (adc_td3_config_check(td3, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (count < 1 || !r_b || !done_b || !q_b || !y_b || !(clip >= 0.0f)) return ADC_EINVAL;
+    const adc::Td3Law law = adc::td3_law_of(*td3);
+    for (int32_t b = 0; b < count; ++b) y_b[b] = adc::td3_y_norm(r_b[b], done_b[b], q_b[b], law, scale, clip);
     return ADC_OK;
 }
 

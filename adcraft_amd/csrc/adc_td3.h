@@ -148,6 +148,22 @@ ADC_HD float td3_y(float r, int done, float q, const Td3Law &w)
     const float gq = w.gamma * q, gqn = gq * nt;
     return rs + gqn;
 }
+// td3_y under a running reward normaliser (adc_td3_norm.h): rs = r * reward_scale; rs = rs * scale (the learner's normaliser's
+// current multiplier); with clip > 0: rs = rs < -clip ? -clip : rs; rs = rs > clip ? clip : rs (a NaN passes).  The rest is
+// td3_y, operation for operation; with scale = 1 and clip = 0 these are td3_y's bits (the product with 1.0f is exact).
+ADC_HD float td3_y_norm(float r, int done, float q, const Td3Law &w, float scale, float clip)
+{
+    const float rs0 = r * w.reward_scale;
+    float rs = rs0 * scale;
+    if (clip > 0.0f) {
+        const float nc = -clip;
+        rs = rs < nc ? nc : rs;
+        rs = rs > clip ? clip : rs;
+    }
+    const float nt = done ? 0.0f : 1.0f;
+    const float gq = w.gamma * q, gqn = gq * nt;
+    return rs + gqn;
+}
 ADC_HD float td3_critic_delta(float q, float y, float &loss)
 {
     const float d = q - y, sq = d * d;

@@ -197,6 +197,18 @@ struct adc_engine {
     double *rn_part = nullptr;          // [rn_M][chunks][2] chunk partials
     int32_t *rn_src = nullptr;          // [rn_M] adc_engine_rew_norm_copy's donors
     std::vector<void *> rn_allocs;
+    // the TD3 learners' running normalisers (adc_engine_td3_norm_init; parts/kernel_td3_norm.inc, parts/td3_norm_api.inc; the law is
+    // adc_td3_norm.h).  They live with the TD3 trainer; tn_raw: the record's obs rows (and so the ring's) are raw observations
+    bool have_tn = false, tn_raw = false;
+    adc_td3_norm_config tn_cfg{};
+    int tn_M = 0;                       // normalisers: 1 (shared) or the learners' count (per_member)
+    int tn_t0 = 0;                      // the record's days [0, tn_t0) have been consumed
+    ObsNormView tn_on{};                // the observation part ([tn_M][D] each; count null: the part does not live)
+    RewNormView tn_rn{};                // the reward part ([tn_M] each, the envs' carry [N]; count null: the part does not live)
+    const float *tn_shared_shift = nullptr, *tn_shared_scale = nullptr;     // the policy's own [D] vectors (per-member vectors in force)
+    double *tn_on_part = nullptr, *tn_g = nullptr, *tn_rn_part = nullptr;   // chunk partials [tn_M][chunks][2][D]; returns [ro_T][N]; [tn_M][chunks][2]
+    int32_t *tn_src = nullptr;          // [tn_M] adc_engine_td3_norm_copy's donors
+    std::vector<void *> tn_allocs;
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -1189,6 +1201,12 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
     if (err == hipSuccess && e->have_rn) {
         hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
                            e->rn_view.G);
+        err = hipGetLastError();
+    }
+    // (... and so does the TD3 learners' reward normaliser's carry)
+    if (err == hipSuccess && e->have_tn && e->tn_rn.G) {
+        hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
+                           e->tn_rn.G);
         err = hipGetLastError();
     }
     hipError_t err2 = hipStreamSynchronize(e->stream);
@@ -2807,8 +2825,9 @@ inline bool rollout_room(const adc_engine *e, long long more) { return e->ro_T =
 // the record's slot t for the envs from e0 on (all null when `record` is false)
 inline MlpRecordSlot rollout_slot(const adc_engine *e, bool record, int t, size_t e0)
 {
-    MlpRecordSlot r{nullptr, nullptr, nullptr, nullptr};
+    MlpRecordSlot r{nullptr, nullptr, nullptr, nullptr, 0};
     if (!record) return r;
+    r.raw_obs = e->tn_raw ? 1 : 0;
     const size_t n = (size_t)e->v.N, row = (size_t)t * n + e0;
     r.action = e->ro_action + row * (size_t)e->mp.A;
     r.logp = e->ro_logp + row;
@@ -2893,9 +2912,25 @@ void pg_drop(adc_engine *e)
     e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();
     e->pgp_dmem = nullptr;
 }
+// the TD3 learners' normalisers go with their trainer: the record is back to network inputs, the policy kernel to the policy's own
+// vectors, which hold what adc_engine_mlp_set_norm last wrote
+void td3_norm_drop(adc_engine *e)
+{
+    if (!e->have_tn) return;
+    if (e->tn_shared_shift) { e->mp.shift = e->tn_shared_shift; e->mp.scale = e->tn_shared_scale; e->mp.norm_stride = 0; }
+    mlp_free(e, e->tn_allocs);
+    e->have_tn = e->tn_raw = false;
+    e->tn_M = e->tn_t0 = 0;
+    e->tn_on = ObsNormView{};
+    e->tn_rn = RewNormView{};
+    e->tn_shared_shift = e->tn_shared_scale = nullptr;
+    e->tn_on_part = e->tn_g = e->tn_rn_part = nullptr;
+    e->tn_src = nullptr;
+}
 // ... and so does the off-policy trainer (its ring holds rows of that policy's input and action widths)
 void td3_drop(adc_engine *e)
 {
+    td3_norm_drop(e);
     pbt_forget(e, ADC_PBT_TD3);
     mlp_free(e, e->td3_allocs);
     e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
@@ -2925,6 +2960,8 @@ void learners_drop(adc_engine *e)
 {
     obs_norm_drop(e);
     rew_norm_drop(e);
+    // (a solo TD3 trainer survives learners and a population, refused while they are active; so do its normalisers, or its raw ring
+    //  would be sampled without them afterwards.  A TD3 population's go with it, below)
     if (e->have_pg_pop) pg_drop(e);
     if (e->have_td3_pop) td3_drop(e);
     mlp_free(e, e->lrn_allocs);
@@ -3096,6 +3133,18 @@ ADC_EXPORT int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, cons
         }
         HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->on_shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->on_shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return ADC_OK;
+    }
+    if (e->have_tn && e->tn_shared_shift) {
+        // the TD3 learners' per-member vectors are in force: every member's row, and the policy's own vectors
+        const size_t D = (size_t)e->mp.D;
+        for (int m = 0; m < e->tn_M; ++m) {
+            HIP_TRY(hipMemcpyAsync(e->tn_on.shift + (size_t)m * D, shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->tn_on.scale + (size_t)m * D, scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->tn_shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->tn_shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         return ADC_OK;
     }
@@ -3644,6 +3693,7 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     e->ro_t = 0;
     e->on_t0 = 0;
     e->rn_t0 = 0;
+    e->tn_t0 = 0;
     e->ro_deterministic = false;
     e->pg_adv_ready = false;
     e->td3_stored_t = 0;

@@ -53,6 +53,7 @@ struct MlpRecordSlot {
     float *action;                          // [N][A]
     float *logp, *value;                    // [N]
     float *obs;                             // [N][D]
+    int raw_obs;                            // the obs row is the flat observation before normalisation (adc_engine_td3_norm_init); 0: the network's input
 };
 
 constexpr int kMlpBlock = 256;
@@ -146,9 +147,10 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         const size_t no = kMembers == 2 ? (size_t)p.member[env] * p.norm_stride : 0;
         for (int j = tid; j < D; j += kMlpBlock) {
             float xj = first ? 0.0f : adc::mlp_obs_at(j, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
+            const float raw = xj;
             if (p.shift) xj = adc::mlp_normalize(xj, p.shift[no + j], p.scale[no + j]);
             mlp_lds[j] = xj;
-            if (mode == 0 && rec.obs) rec.obs[(size_t)env * D + j] = xj;
+            if (mode == 0 && rec.obs) rec.obs[(size_t)env * D + j] = rec.raw_obs ? raw : xj;
         }
     }
     __syncthreads();

@@ -21,6 +21,14 @@ struct Td3View {
     adc::Td3Law law;
     MlpNet pol, pol_t, q[2], q_t[2];        // chain-major layers: the live actor, its target, the critics, their targets
     const float *a_shift, *a_scale;         // [A] (sh.norm)
+    // the running normalisers (adc_engine_td3_norm_init; adc_td3_norm.h).  n_shift non-null: the ring's x / x' are raw and are
+    // normalised as they are gathered, with the vectors at n_shift / n_scale + member * n_stride.  r_scale non-null: the target is
+    // td3_y_norm under the multiplier r_scale[member * r_stride] and r_clip.  Both null: the kernels' loads and bits are what they were
+    const float *n_shift, *n_scale;         // [D] or [M][D]
+    size_t n_stride;                        // floats between two members' vectors; 0: shared
+    const float *r_scale;                   // [1] or [M]
+    int r_stride;                           // 1: a multiplier per member; 0: shared
+    float r_clip;
     Td3Ring ring;
     uint32_t size, update;                  // the ring's size; the update's number
     uint64_t key;
@@ -144,7 +152,13 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
     const uint32_t b = blockIdx.x;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *words = yq + adc::td3_outs(sh.q) + 3 * p.maxw;
     const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
-    for (int j = tid; j < D; j += kPgBlock) row[j] = p.ring.x2[slot * (size_t)D + j];
+    // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
+    const float r_mult = p.r_scale ? p.r_scale[0] : 1.0f;
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = p.ring.x2[slot * (size_t)D + j];
+        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        row[j] = xj;
+    }
     __syncthreads();
     td3_forward(p.pol_t, sh.activation, row, yp, nullptr);
     const float *mu = yp + adc::td3_hidden(sh.pol);
@@ -159,7 +173,11 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
         if (tid == 0) words[i] = yq[qlast];
         __syncthreads();
     }
-    if (tid == 0) p.ybuf[b] = adc::td3_y(p.ring.r[slot], p.ring.done[slot], adc::td3_min(words[0], words[1]), p.law);
+    if (tid == 0) {
+        const float q = adc::td3_min(words[0], words[1]);
+        p.ybuf[b] = p.r_scale ? adc::td3_y_norm(p.ring.r[slot], p.ring.done[slot], q, p.law, r_mult, p.r_clip)
+                              : adc::td3_y(p.ring.r[slot], p.ring.done[slot], q, p.law);
+    }
 }
 
 // forward and backward of both critics on batch element blockIdx.x
@@ -173,8 +191,9 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
     const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
     float *xin = p.xin + (size_t)b * (size_t)DA;
     for (int j = tid; j < DA; j += kPgBlock) {
-        const float xj = j < D ? p.ring.x[slot * (size_t)D + j]
-                               : adc::td3_action_norm(p.ring.a[slot * (size_t)A + (j - D)], p.a_shift, p.a_scale, j - D, sh.norm);
+        float xj = j < D ? p.ring.x[slot * (size_t)D + j]
+                         : adc::td3_action_norm(p.ring.a[slot * (size_t)A + (j - D)], p.a_shift, p.a_scale, j - D, sh.norm);
+        if (p.n_shift && j < D) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
         row[j] = xj;
         xin[j] = xj;
     }
@@ -206,7 +225,11 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample(Td3View p)
     const uint32_t b = blockIdx.x;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
     const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
-    for (int j = tid; j < D; j += kPgBlock) row[j] = p.ring.x[slot * (size_t)D + j];
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = p.ring.x[slot * (size_t)D + j];
+        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        row[j] = xj;
+    }
     __syncthreads();
     float *acts = p.acts + (size_t)b * (size_t)p.na, *deltas = p.deltas + (size_t)b * (size_t)p.nd;
     td3_forward(p.pol, sh.activation, row, yp, acts);

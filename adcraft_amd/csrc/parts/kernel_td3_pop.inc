@@ -61,7 +61,8 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_store(View v, const float 
 
 // The batch kernels: batch element blockIdx.x of member blockIdx.y.  p carries what the members share (the shapes, the action
 // normalisation, the ring's size, the update's number, the scratch for all members, na / nd / maxw); p.pol, p.pol_t, p.q, p.q_t,
-// p.law, p.key and p.ring are not read.  A member's scratch rows start at member * gridDim.x.
+// p.law, p.key and p.ring are not read.  A member's scratch rows start at member * gridDim.x.  Under a running normaliser
+// (p.n_shift / p.r_scale non-null) the member's vectors are at member * p.n_stride, its multiplier at member * p.r_stride.
 
 // y of the element
 __global__ __launch_bounds__(kPgBlock) void k_td3_pop_target(Td3View p, const Td3Member *__restrict__ mem)
@@ -75,7 +76,14 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_target(Td3View p, const Td
     const Td3Ring ring = me.ring;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *words = yq + adc::td3_outs(sh.q) + 3 * p.maxw;
     const size_t slot = adc::td3_batch_index(key, b, p.update, p.size);
-    for (int j = tid; j < D; j += kPgBlock) row[j] = ring.x2[slot * (size_t)D + j];
+    const size_t nv = (size_t)blockIdx.y * p.n_stride;          // (the member's row of the normaliser's vectors; 0 whenever they are shared)
+    // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
+    const float r_mult = p.r_scale ? p.r_scale[(size_t)blockIdx.y * (size_t)p.r_stride] : 1.0f;
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = ring.x2[slot * (size_t)D + j];
+        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
+        row[j] = xj;
+    }
     __syncthreads();
     td3_forward(me.pol_t, sh.activation, row, yp, nullptr);
     const float *mu = yp + adc::td3_hidden(sh.pol);
@@ -91,8 +99,12 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_target(Td3View p, const Td
         if (tid == 0) words[i] = yq[qlast];
         __syncthreads();
     }
-    if (tid == 0)
-        p.ybuf[(size_t)blockIdx.y * gridDim.x + b] = adc::td3_y(ring.r[slot], ring.done[slot], adc::td3_min(words[0], words[1]), law);
+    if (tid == 0) {
+        const float q = adc::td3_min(words[0], words[1]);
+        p.ybuf[(size_t)blockIdx.y * gridDim.x + b] =
+            p.r_scale ? adc::td3_y_norm(ring.r[slot], ring.done[slot], q, law, r_mult, p.r_clip)
+                      : adc::td3_y(ring.r[slot], ring.done[slot], q, law);
+    }
 }
 
 // forward and backward of both of the member's critics on the element
@@ -108,9 +120,11 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_critic_sample(Td3View p, c
     float *row = td3_lds, *yq = row + DA + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
     const size_t slot = adc::td3_batch_index(me.key, b, p.update, p.size);
     float *xin = p.xin + at * (size_t)DA;
+    const size_t nv = (size_t)blockIdx.y * p.n_stride;
     for (int j = tid; j < DA; j += kPgBlock) {
-        const float xj = j < D ? ring.x[slot * (size_t)D + j]
-                               : adc::td3_action_norm(ring.a[slot * (size_t)A + (j - D)], p.a_shift, p.a_scale, j - D, sh.norm);
+        float xj = j < D ? ring.x[slot * (size_t)D + j]
+                         : adc::td3_action_norm(ring.a[slot * (size_t)A + (j - D)], p.a_shift, p.a_scale, j - D, sh.norm);
+        if (p.n_shift && j < D) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
         row[j] = xj;
         xin[j] = xj;
     }
@@ -146,7 +160,12 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_actor_sample(Td3View p, co
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
     const size_t slot = adc::td3_batch_index(me.key, b, p.update, p.size);
     const float *rx = me.ring.x;
-    for (int j = tid; j < D; j += kPgBlock) row[j] = rx[slot * (size_t)D + j];
+    const size_t nv = (size_t)blockIdx.y * p.n_stride;
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = rx[slot * (size_t)D + j];
+        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
+        row[j] = xj;
+    }
     __syncthreads();
     float *acts = p.acts + at * (size_t)p.na, *deltas = p.deltas + at * (size_t)p.nd;
     td3_forward(pol, sh.activation, row, yp, acts);

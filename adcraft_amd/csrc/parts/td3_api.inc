@@ -69,6 +69,13 @@ adc::EsStep td3_step_of(const adc_td3_config &c, float lr, int64_t steps_taken)
     step.c2 = adc::es_bias_correction(step.beta2, (uint32_t)(steps_taken + 1));
     return step;
 }
+// the running normalisers' side of a batch kernel's view (all null without adc_engine_td3_norm_init: the kernels are what they were)
+void td3_norm_fill(const adc_engine *e, Td3View &p)
+{
+    if (!e->have_tn) return;
+    if (e->tn_raw) { p.n_shift = e->mp.shift; p.n_scale = e->mp.scale; p.n_stride = e->mp.norm_stride; }
+    if (e->tn_rn.count) { p.r_scale = e->tn_rn.scale; p.r_stride = e->tn_cfg.per_member ? 1 : 0; p.r_clip = e->tn_cfg.rew_clip; }
+}
 Td3View td3_view(const adc_engine *e)
 {
     Td3View p{};
@@ -83,6 +90,7 @@ Td3View td3_view(const adc_engine *e)
     p.key = e->td3_key;
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(e->td3_shape);
+    td3_norm_fill(e, p);
     return p;
 }
 // the weight gradient's partials of one network over the batch: its first layer's X is the gathered rows
@@ -284,7 +292,9 @@ ADC_EXPORT int adc_engine_td3_store(adc_engine *e, int64_t *stored)
                                 "one the envs hold (adc_engine_rollout_reset, collect again)");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;
-    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->mp.shift, e->mp.scale, e->mp.D, e->mp.A, e->ro_obs,
+    // (raw rows under a running observation normaliser: the last day's x' is the raw row an act would read now)
+    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->tn_raw ? nullptr : e->mp.shift,
+                       e->tn_raw ? nullptr : e->mp.scale, e->mp.D, e->mp.A, e->ro_obs,
                        e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
                        (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());

@@ -136,6 +136,7 @@ int tp_one_update(adc_engine *e, int index, bool stats_wanted, bool last, bool l
     p.size = (uint32_t)td3_size(e); p.update = (uint32_t)e->td3_updates;
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(sh);
+    td3_norm_fill(e, p);
     p.na = 2 * nh; p.nd = 2 * no;
     hipLaunchKernelGGL(k_td3_pop_target, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
     hipLaunchKernelGGL(k_td3_pop_critic_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
@@ -334,7 +335,8 @@ ADC_EXPORT int adc_engine_td3_pop_store(adc_engine *e, int64_t *stored_per_membe
                                 "one the envs hold (adc_engine_rollout_reset, collect again)");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;
-    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->mp.shift, e->mp.scale, e->mp.D, e->mp.A,
+    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn_raw ? nullptr : e->mp.shift,
+                       e->tn_raw ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
                        e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
                        (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());

@@ -565,6 +565,7 @@ class StepEngine:
         cfg = policy.config(self.num_keywords, deterministic)
         sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
         check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
+        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
         self._mlp = policy
         self._members = 0                   # (a population does not survive a re-initialisation)
         self._learners = 0
@@ -613,6 +614,14 @@ class StepEngine:
                   logp=np.zeros(n, np.float32), value=np.zeros(n, np.float32))
         check(self._lib.adc_engine_mlp_last(self._h, *(st[k].ctypes.data for k in ("mean", "log_std", "action", "logp", "value"))))
         return st
+
+    def mlp_set_norm(self, shift, scale):
+        """the policy's normalisation vectors [5K + 2] (every member's under per-member normalisers; running moments are left alone)"""
+        D = 5 * self.num_keywords + 2
+        sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in (shift, scale))
+        if sh.shape != (D,) or sc.shape != (D,):
+            raise ValueError(f"mlp_set_norm: shift and scale have {D} entries")
+        check(self._lib.adc_engine_mlp_set_norm(self._h, sh.ctypes.data, sc.ctypes.data))
 
     def mlp_agent_state(self):
         """(keys uint64 [N], ticks uint32 [N]) of the agents' own streams; every act moves a tick on by one"""
@@ -931,6 +940,7 @@ class StepEngine:
         options as td3_config's.  theta starts as the device's policy; the critics are uploaded with td3_set_critics."""
         cfg = self.td3_config(**options)
         check(self._lib.adc_engine_td3_init(self._h, C.byref(cfg)))
+        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
 
     def td3_set_critics(self, critics, action_norm=None, sync_targets=True):
         """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs; action_norm: (shift, scale) [A]
@@ -1046,6 +1056,7 @@ class StepEngine:
         Every member's theta starts as its device policy; the critics are uploaded with td3_pop_set_critics."""
         arr, count = self.td3_pop_configs(configs, self.num_envs, self._td3_pop_members())
         check(self._lib.adc_engine_td3_pop_init(self._h, arr, count))
+        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
 
     def td3_pop_set_critics(self, member, critics, action_norm=None, sync_targets=True):
         """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs); action_norm: (shift, scale) [A],
@@ -1340,8 +1351,98 @@ class StepEngine:
             raise ValueError("rew_norm_copy: one source per member")
         check(self._lib.adc_engine_rew_norm_copy(self._h, src.ctypes.data))
 
+    # ---- the TD3 learners' running normalisers (parts/kernel_td3_norm.inc; the law is csrc/adc_td3_norm.h) ------------------------
+    @classmethod
+    def td3_norm_config(cls, observations=False, rewards=False, per_member=False, obs_min_std=1e-2, obs_count_cap=0, rew_min_std=1e-2, rew_count_cap=0,
+                        rew_clip=10.0):
+        """an adc_td3_norm_config: which parts live (at least one); the min_std floor the standard deviations; the count_cap > 0
+        bound the running counts, 0: off; rew_clip > 0 bounds the normalised reward, 0: off.  The defaults are configuration
+        (VecNormalize's clip), not measurements."""
+        c = _ffi.TD3NormConfig()
+        c.struct_size = C.sizeof(_ffi.TD3NormConfig)
+        c.observations, c.rewards, c.per_member = 1 if observations else 0, 1 if rewards else 0, 1 if per_member else 0
+        c.obs_min_std, c.obs_count_cap, c.rew_min_std, c.rew_count_cap, c.rew_clip = float(obs_min_std), int(obs_count_cap), float(rew_min_std), int(rew_count_cap), float(rew_clip)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_td3_norm_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad TD3 normaliser configuration").decode())
+        return c
+
+    def td3_norm_init(self, **options):
+        """running normalisers for the live TD3 trainer (td3_init or td3_pop_init first, the record and the ring still empty):
+        with observations the record and the ring hold RAW observations from here on and every batch is normalised as it is
+        sampled; with rewards the target's reward is multiplied by the reciprocal running standard deviation of the discounted
+        return.  per_member=True: one per learner of a population.  Options as td3_norm_config's"""
+        cfg = self.td3_norm_config(**options)
+        check(self._lib.adc_engine_td3_norm_init(self._h, C.byref(cfg)))
+        self._td3_norm = dict(members=max(getattr(self, "_learners", 0), 1) if cfg.per_member else 1, observations=bool(cfg.observations),
+                              rewards=bool(cfg.rewards))
+
+    def _td3_norm_info(self):
+        """what td3_norm_init set up; without one the engine itself says what is missing"""
+        info = getattr(self, "_td3_norm", None)
+        if info is None:
+            check(self._lib.adc_engine_td3_norm_state_get(self._h, 0, *([None] * 9)))
+            info = dict(members=1, observations=True, rewards=True)
+        return info
+
+    def td3_norm_update(self):
+        """merge the recorded days not yet consumed into the running moments and write the new vectors and multiplier where the
+        next act and the next td3_update read them (after the store, before the updates); returns the samples consumed"""
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_td3_norm_update(self._h, C.byref(n)))
+        return n.value
+
+    def td3_norm_state(self, member=0, state=None):
+        """one normaliser's state (member 0: the shared one).  get (no state): dict of the living parts - obs_count, obs_mean,
+        obs_M2 [D] float64, shift, scale [D] float32; rew_count, rew_mean, rew_M2 (float64), rew_scale (float32); set: such a dict -
+        with td3_norm_returns, the trainer's state and the ring the run continues bit for bit"""
+        D, info = 5 * self.num_keywords + 2, self._td3_norm_info()
+        okeys = (("obs_mean", np.float64), ("obs_M2", np.float64), ("shift", np.float32), ("scale", np.float32))
+        if state is None:
+            st = {}
+            optr = [None] * 4
+            n, rn, mean, m2, sc = C.c_int64(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0), C.c_float(0.0)
+            if info["observations"]:
+                st.update({k: np.zeros(D, t) for k, t in okeys})
+                optr = [st[k].ctypes.data for k, _ in okeys]
+            rptr = [C.byref(rn), C.byref(mean), C.byref(m2), C.byref(sc)] if info["rewards"] else [None] * 4
+            check(self._lib.adc_engine_td3_norm_state_get(self._h, int(member), C.byref(n) if info["observations"] else None, *optr, *rptr))
+            if info["observations"]:
+                st["obs_count"] = n.value
+            if info["rewards"]:
+                st.update(rew_count=rn.value, rew_mean=np.float64(mean.value), rew_M2=np.float64(m2.value), rew_scale=np.float32(sc.value))
+            return st
+        arr = [None] * 4
+        if info["observations"]:
+            arr = [np.ascontiguousarray(state[k], dtype=t) for k, t in okeys]
+            if any(a.shape != (D,) for a in arr):
+                raise ValueError(f"td3_norm_state: obs_mean, obs_M2, shift and scale have {D} entries")
+        rew = (int(state["rew_count"]), float(state["rew_mean"]), float(state["rew_M2"]), float(np.float32(state["rew_scale"]))) if info["rewards"] else (0, 0.0, 0.0, 1.0)
+        check(self._lib.adc_engine_td3_norm_state_set(self._h, int(member), int(state["obs_count"]) if info["observations"] else 0,
+                                                      *(None if a is None else a.ctypes.data for a in arr), *rew))
+
+    def td3_norm_returns(self, values=None):
+        """the envs' running discounted returns [N] float64 (the reward part's carry).  get (no argument) or set"""
+        if values is None:
+            g = np.zeros(self.num_envs, np.float64)
+            check(self._lib.adc_engine_td3_norm_returns_get(self._h, g.ctypes.data))
+            return g
+        g = np.ascontiguousarray(values, dtype=np.float64)
+        if g.shape != (self.num_envs,):
+            raise ValueError("td3_norm_returns: one value per env")
+        check(self._lib.adc_engine_td3_norm_returns_set(self._h, g.ctypes.data))
+
+    def td3_norm_copy(self, src_of_member):
+        """every member's normalisers become those of member src_of_member[m] (m itself or -1: kept) in one launch; no
+        destination may also be a source (pbt_exploit's convention).  The envs' running returns stay."""
+        src = np.ascontiguousarray(src_of_member, dtype=np.int32)
+        if src.shape != (self._td3_norm_info()["members"],):
+            raise ValueError("td3_norm_copy: one source per member")
+        check(self._lib.adc_engine_td3_norm_copy(self._h, src.ctypes.data))
+
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
+        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
         self._rollout_obs = bool(obs) and int(horizon) > 0
 
     def rollout_reset(self):

@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--mean-volume", type=float, default=8.0)
     ap.add_argument("--iterations", type=int, default=60)
     ap.add_argument("--updates", type=int, default=100, help="critic updates per iteration")
+    ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter per member; the rings hold raw rows")
+    ap.add_argument("--normalize-rewards", action="store_true", help="per member, the reward divided by the discounted return's running standard deviation")
     ap.add_argument("--solo", action="store_true", help="afterwards, the same grid as solo trainers one after another (wall time)")
     args = ap.parse_args()
     K, days, n = args.num_keywords, args.days, args.envs_per_member
@@ -70,7 +72,8 @@ def main():
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(np.concatenate([member_planes] * M, axis=1))
     eng.reset()
-    trainer = td3_trainer.TD3PopulationTrainer(eng, policy, [s for _, _, s in cells], configs, horizon=days)
+    trainer = td3_trainer.TD3PopulationTrainer(eng, policy, [s for _, _, s in cells], configs, horizon=days,
+                                               normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards)
     print(f"{M} TD3 learners x {n} envs x {K} keywords on one engine, {days} days and {args.updates} updates per iteration")
     print("member    " + " ".join(f"{m:>8d}" for m in range(M)))
     print("actor_lr  " + " ".join(f"{a:8.0e}" for a, _, _ in cells))
@@ -94,7 +97,8 @@ def main():
             e = StepEngine(n, K, max_days=days, seed=7)
             e.set_all_params(member_planes)
             e.reset()
-            tr = td3_trainer.TD3Trainer(e, policy, horizon=days, exploration_sigma=sigma, **cfg)
+            tr = td3_trainer.TD3Trainer(e, policy, horizon=days, exploration_sigma=sigma, normalize_observations=args.normalize_observations,
+                                        normalize_rewards=args.normalize_rewards, **cfg)
             c = curves_of(lambda seeds: tr.iteration(days, BUDGET, reset=True, reset_seeds=seeds),
                           lambda: [e.rollout_fetch()["reward"].astype(np.float64).sum(axis=0).mean()], args.iterations, n)
             solo_last.append(c[-5:].mean())

@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.99)
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
+    ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device; the ring holds raw rows")
+    ap.add_argument("--normalize-rewards", action="store_true", help="the reward divided by the discounted return's running standard deviation")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
@@ -71,7 +73,8 @@ def main():
                              learning_starts=args.warmup_iterations * days * N, updates_per_iteration=args.updates, batch_size=args.batch_size,
                              reward_scale=args.reward_scale, gamma=args.gamma, actor_lr=args.actor_lr, action_lo=0.01, action_hi=3.0,
                              action_norm=(np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32)))
-    trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days), horizon=days, **config)
+    trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days), horizon=days, normalize_observations=args.normalize_observations,
+                                     normalize_rewards=args.normalize_rewards, **config)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
     print(f"{0:>10} {'':>12} {'':>9} {ret:10.2f} {ncp:8.3f}")

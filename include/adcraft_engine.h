@@ -963,6 +963,79 @@ int adc_pg_gae_norm_host(const adc_pg_config *cfg, int32_t days, int32_t num_env
                          const uint8_t *truncated_tn, const float *value_tn, const float *bootstrap_n, const float *scale_n, float clip,
                          float *adv_tn, float *ret_tn);
 
+/* ---- running observation and reward normalisers for the TD3 learners (the law is csrc/adc_td3_norm.h) ---------------------------
+ * The replay ring outlives the statistics, so it may not depend on them.  While a normaliser with `observations` lives the rollout
+ * record's obs rows are the RAW flat observation (zeros on an episode's first day) - the policy network itself is still fed
+ * (x - shift) * scale - and so are the ring's x / x' rows: adc_engine_rollout_fetch, adc_engine_td3_buffer_fetch / _load (and the
+ * _td3_pop_ ones) and a PBT round's ring copy carry raw rows.  The TD3 batch kernels normalise x and x' as they gather them, with
+ * the learner's CURRENT vectors, and - with `rewards` - compute the target from r * reward_scale * scale, clipped to
+ * [-rew_clip, rew_clip] when rew_clip > 0; the multiplier is read on the device, no host round trip lies between an update of the
+ * normaliser and the next TD3 update.  Without `observations` the record and the ring hold network inputs as before; without
+ * adc_engine_td3_norm_init every call launches the kernels it launched and computes the bits it computed.
+ * The observation moments are those of the raw rows (count, mean[D], M2[D] in float64); after an update shift = float32(mean),
+ * scale = float32(1 / max(std, obs_min_std)) are written in place where the policy kernel and the batch kernels read them.  The
+ * reward moments are adc_rew_norm.h's (the variance of the discounted return, a per-env float64 carry G that a day ending an
+ * episode and adc_engine_reset zero) with the TD3 learner's gamma - under a population the env's member's, as in force when the
+ * update runs.  per_member: every learner of a TD3 population has its own normalisers (and its own [D] vectors, each starting as
+ * the policy's), fed from its own envs in its own order: member m's result is bit for bit a single engine's of its envs.
+ * `member` below is 0 for the shared normaliser.
+ * adc_engine_td3_norm_update consumes the recorded days [t0, T) not yet consumed (its own cursor t0: 0 at init and after
+ * adc_engine_rollout_reset), enqueues at most five launches whatever the number of members is and synchronises nothing; *samples
+ * (may be NULL) receives the samples a normaliser consumed.  A trainer calls it after the store and BEFORE its TD3 updates: the
+ * batch is scaled by statistics that include the newest days.
+ * adc_td3_norm_config_check (host only): struct_size; observations or rewards nonzero; the min_std finite and > 0; the count_cap
+ * >= 0 (0: no forgetting); rew_clip finite and >= 0 (0: off).
+ * adc_engine_td3_norm_init is refused, the engine staying usable: without a live adc_engine_td3_init / _td3_pop_init trainer
+ * (ADC_ESTATE); per_member without a TD3 population (ADC_EINVAL); `observations` on a policy initialised without normalisation
+ * (ADC_EINVAL); a day recorded since adc_engine_rollout_reset or a transition in the ring (ADC_ESTATE: they hold network inputs).
+ * adc_engine_td3_norm_update is refused (ADC_ESTATE) with no unconsumed day.  The normaliser ends with its trainer -
+ * adc_engine_mlp_init, adc_engine_rollout_enable, a new adc_engine_td3_init / _td3_pop_init, and for a population's trainer
+ * adc_engine_mlp_learners / adc_engine_mlp_population - and the record is back to network inputs.  A single-learner trainer
+ * survives adc_engine_mlp_learners and adc_engine_mlp_population (its calls are refused while they are active) and so do its
+ * normalisers: after adc_engine_mlp_learners(0) / _mlp_population(0) the run continues on its raw ring, bit for bit.  adc_engine_obs_norm_init / adc_engine_rew_norm_init keep refusing a TD3 trainer, and
+ * adc_engine_pg_init is refused while one lives.  While the normaliser lives adc_engine_mlp_set_norm keeps writing the shared
+ * vectors - every member's with per-member ones - and leaves the moments alone; with raw rings its effect on sampled rows is
+ * immediate.
+ * state_get / state_set: one normaliser's observation part (count, mean[D], M2[D], shift[D], scale[D]) and reward part (count,
+ * mean, M2, scale); get: any may be NULL; set: the pointers of a part that does not live are not read; counts >= 0, scales finite and > 0, shift and the means
+ * finite, M2 finite and >= 0 (ADC_EINVAL).  returns_get / _set: the
+ * envs' carry G [N] (needs `rewards`).  A run resumed from them, the trainer's state and the ring continues bit for bit.
+ * adc_engine_td3_norm_copy: adc_engine_pbt_exploit's convention (src_of_m[m] == m or -1: kept): every replaced member's moments,
+ * vectors and multiplier become its donor's, in ONE launch whatever M is; a destination that is also a source is refused
+ * (ADC_EINVAL), so is a shared normaliser (ADC_ESTATE).  The carry is the envs' and is not copied. */
+typedef struct adc_td3_norm_config {
+    uint32_t struct_size;          /* sizeof(adc_td3_norm_config) */
+    int32_t observations, rewards; /* which parts live; at least one nonzero */
+    int32_t per_member;            /* needs adc_engine_td3_pop_*: one normaliser per learner */
+    double obs_min_std;            /* > 0, finite: the floor of a column's standard deviation */
+    int64_t obs_count_cap;         /* > 0: the running count never exceeds it (M2 scaled down with it); 0: off */
+    double rew_min_std;            /* > 0, finite: the floor of the discounted return's standard deviation */
+    int64_t rew_count_cap;
+    float rew_clip;                /* > 0: the normalised reward is clipped to [-rew_clip, rew_clip]; 0: off */
+} adc_td3_norm_config;
+int adc_td3_norm_config_check(const adc_td3_norm_config *cfg, const char **message);
+int adc_engine_td3_norm_init(adc_engine *e, const adc_td3_norm_config *cfg);
+int adc_engine_td3_norm_update(adc_engine *e, int64_t *samples);
+int adc_engine_td3_norm_state_get(adc_engine *e, int32_t member, int64_t *obs_count, double *obs_mean_d, double *obs_m2_d, float *shift_d, float *scale_d,
+                                  int64_t *rew_count, double *rew_mean, double *rew_m2, float *rew_scale);
+int adc_engine_td3_norm_state_set(adc_engine *e, int32_t member, int64_t obs_count, const double *obs_mean_d, const double *obs_m2_d, const float *shift_d,
+                                  const float *scale_d, int64_t rew_count, double rew_mean, double rew_m2, float rew_scale);
+int adc_engine_td3_norm_returns_get(adc_engine *e, double *g_n);
+int adc_engine_td3_norm_returns_set(adc_engine *e, const double *g_n);
+int adc_engine_td3_norm_copy(adc_engine *e, const int32_t *src_of_member_m);
+/* the host twins: the same code as the device's.  obs: one update of one normaliser's observation part from the batch's RAW rows
+ * x_sd [S][D] in the law's sample order; *count, mean_d, m2_d hold the running moments and receive the merged ones, shift_d /
+ * scale_d receive the new vectors.  rew: adc_rew_norm_host's arguments under cfg's rew_min_std / rew_count_cap (gamma_n: every
+ * env's TD3 discount).  y_norm: y_b [count] = td3_y_norm of r_b, done_b and q_b (the smaller target critic's value) under td3's
+ * gamma and reward_scale, the multiplier `scale` and `clip`; with scale 1 and clip 0 these are the plain TD3 target's bits. */
+int adc_td3_norm_obs_host(const adc_td3_norm_config *cfg, int64_t S, int32_t D, const float *x_sd, int64_t *count, double *mean_d, double *m2_d,
+                          float *shift_d, float *scale_d);
+int adc_td3_norm_rew_host(const adc_td3_norm_config *cfg, int32_t days, int32_t num_envs, const float *gamma_n, const float *reward_tn,
+                          const uint8_t *terminated_tn, const uint8_t *truncated_tn, int64_t *count, double *mean, double *m2, float *scale,
+                          double *carry_n);
+int adc_td3_y_norm_host(const adc_td3_config *td3, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, float scale, float clip,
+                        float *y_b);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be

@@ -483,10 +483,31 @@ ADC_HD int32_t auction_outcome(uint32_t w, const AuctionLaw &a, float loc, float
 // logarithm; the competitor's bid itself is only evaluated for the clicked wins, which pay it.  These functions find the
 // intervals EXACTLY (the oracle resolves every auction the long way; parity is bit for bit).
 
+// the hardware's exp2 / rcp (estimates only: no result depends on their last bits)
+ADC_HD float fast_exp2(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_exp2f(x);
+#else
+    return exp2f(x);
+#endif
+}
+ADC_HD float fast_rcp(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(x);
+#else
+    return 1.0f / x;
+#endif
+}
+ADC_HD float min_num(float a, float b) { return __builtin_fminf(a, b); }       // the non-NaN operand if one is NaN
+ADC_HD float max_num(float a, float b) { return __builtin_fmaxf(a, b); }
+
 // min{v in [0, 2^24] : signed_cents_from_v(v) >= target}.  A float estimate of the answer, a window around it that is
 // verified at both ends, bisection inside; if the estimate was off (degenerate parameters) the bisection runs over the
-// whole range instead - the result never depends on the estimate.
-ADC_HD uint32_t lower_bound_v(int32_t target, float loc, float scale, const LogTableEntry *tab)
+// whole range instead - the result never depends on the estimate.  About ten dependent evaluations of S: the fallback of
+// lower_bound_v below, and the reference its tests compare with.
+ADC_HD uint32_t lower_bound_v_bisect(int32_t target, float loc, float scale, const LogTableEntry *tab, bool *whole_range = nullptr)
 {
     const float s = __builtin_fabsf(scale);
     const float x_t = ((float)target - 0.5f) * 0.01f;                    // 100 x rounds to >= target from about here
@@ -509,14 +530,157 @@ ADC_HD uint32_t lower_bound_v(int32_t target, float loc, float scale, const LogT
     uint32_t lo = est > half ? est - half : 0u;
     uint32_t hi = est + half < 0x01000000u ? est + half : 0x01000000u;
     // wanted: S(lo - 1) < target (or lo == 0) and S(hi) >= target (or hi == 2^24)
+    const uint32_t lo_w = lo, hi_w = hi;
     if (lo > 0u && !(signed_cents_from_v(lo - 1u, loc, scale, tab) < target)) lo = 0u;
     if (hi < 0x01000000u && !(signed_cents_from_v(hi, loc, scale, tab) >= target)) hi = 0x01000000u;
+    if (whole_range) *whole_range = lo != lo_w || hi != hi_w;           // (diagnostic: the window did not hold the bound)
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
         if (signed_cents_from_v(mid, loc, scale, tab) >= target) hi = mid;
         else lo = mid + 1u;
     }
     return lo;
+}
+
+// ---- the same bound in four evaluations --------------------------------------------------------------------------
+// S(v) = C(fl(|scale| z(v) + loc)) with C(x) = clamp(rint(fl(100 x))) non-decreasing in the float x, so "S(v) >= target" is
+// "fl(|scale| z(v) + loc) >= X" for X = the smallest float whose cents reach the target, i.e. (round to nearest)
+// |scale| z(v) + loc >= the midpoint of X and the float below it, i.e. z(v) >= Z.  lower_bound_window computes Z (the float
+// X is found by trying the neighbours of (target - 1/2) / 100), the float estimate of v from exp2 as before, ONE evaluation
+// of the table deviate z at the estimate, and the Newton step on the table's own chord (z is linear in v inside a table
+// interval).  What is left is the rounding of Z and of z(est): the crossing c is known to about half a unit of v, so the
+// minimum is rint(c) or rint(c) + 1 (on the benchmark's laws: always, see profiles/pr_fast_law_setup.txt; ceil(c) alone
+// is right for 93 % of keywords, which would send nearly every wave of 64 to the neighbourhood stage).
+// Nothing here has to be right: lower_bound_v takes a value only on the pair of evaluations that DEFINES the minimum.
+template <typename Tab>
+ADC_HD float laplace_deviate_and_slope(uint32_t v24, Tab tab, float &dz_dv)
+{
+    const uint32_t neg_mask = 0u - (v24 >> 23);
+    const uint32_t mag = (v24 ^ neg_mask) & 0x007FFFFFu;
+    const uint32_t bits = float_to_bits(fma32((float)mag, 2.0f, 1.0f));         // the operations of laplace_deviate_from_v / neg_log_f24
+    const float ef = (float)((int)(bits >> 23) - 151);
+    const uint32_t mant = bits & 0x007FFFFFu;
+    const LogTableEntry t = log_entry(tab, mant >> 15);
+    float r = fma32(t.slope, (float)(mant & 0x7FFFu), t.value);
+    r = fma32(ef, -2.12194440e-4f, r);
+    r = fma32(ef, 0.693359375f, r);
+    // one v is two units of 2 mag + 1 = 2^(24 - k) mantissa units for 2 mag + 1 in [2^k, 2^(k+1)); both sides rise with v
+    dz_dv = t.slope * bits_to_float((278u - (bits >> 23)) << 23);
+    return bits_to_float(xor_and(float_to_bits(r), neg_mask, 0x80000000u));
+}
+
+// b in [-1, 2^24) such that the minimum is expected to be b + 1 or b + 2 (only the cost depends on it)
+ADC_HD int32_t lower_bound_window(int32_t target, float loc, float scale, const LogTableEntry *tab)
+{
+    const float tf = (float)target;
+    const float xs = (tf - 0.5f) * 0.01f;                                   // |xs| >= 0.005: a normal float
+    const float ulp = bits_to_float(float_to_bits(xs) & 0x7F800000u) * 1.1920928955078125e-07f;
+    const bool ge0 = __builtin_rintf(xs * 100.0f) >= tf;
+    const float x1 = ge0 ? xs - ulp : xs + ulp;
+    const bool ge1 = __builtin_rintf(x1 * 100.0f) >= tf;
+    // below = the last float short of the target, X = below + ulp: (ge0, ge1) = (1,0): x1; (1,1): x1 - ulp; (0,1): xs; (0,0): x1
+    const float below = ge0 ? (ge1 ? x1 - ulp : x1) : (ge1 ? xs : x1);
+    const float inv_s = fast_rcp(__builtin_fabsf(scale));
+    const float z_t = fma32(ulp, 0.5f, below - loc) * inv_s;                 // Z
+    const float mag_f = max_num(min_num(fast_exp2(fma32(__builtin_fabsf(z_t), -1.44269504f, 23.0f)), 8388607.0f), 0.0f);
+    const uint32_t mag = (uint32_t)mag_f;                                    // (NaN -> a bound; any estimate will do)
+    const uint32_t est = z_t < 0.0f ? mag : 0x00FFFFFFu - mag;
+    float dz_dv;
+    const float z_e = laplace_deviate_and_slope(est, tab, dz_dv);
+    const float step = __builtin_rintf((z_t - z_e) * fast_rcp(dz_dv));       // rint(c) - est
+    const int32_t b = (int32_t)est + (int32_t)max_num(min_num(step, 16777216.0f), -16777216.0f) - 1;
+    return b < -1 ? -1 : b > 0x00FFFFFF ? 0x00FFFFFF : b;                    // minimum 0 or 1 ... 2^24: still inside a window
+}
+
+// "S(i) >= target" for any integer i, with the conventions of the definition at both ends: nothing below 0 reaches the
+// target, everything from 2^24 on does.  (S itself is only ever evaluated inside [0, 2^24).)
+ADC_HD bool bound_reached(int32_t i, int32_t target, float loc, float scale, const LogTableEntry *tab)
+{
+    const uint32_t v = (uint32_t)(i < 0 ? 0 : i > 0x00FFFFFF ? 0x00FFFFFF : i);
+    const bool g = signed_cents_from_v(v, loc, scale, tab) >= target;
+    return i < 0 ? false : i > 0x00FFFFFF ? true : g;
+}
+
+// true if the condition holds in any lane of the wave (the host has one lane): the rare stages below are entered by whole
+// waves, so the common path carries no divergent branch
+ADC_HD bool any_lane(bool c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(c) != 0ull;
+#else
+    return c;
+#endif
+}
+
+// The stages of lower_bound_v.  With G = bound_reached, the minimum is the one i with G(i) and not G(i - 1) (S is monotone):
+//   kBoundAccepted   the three independent evaluations G(b), G(b + 1), G(b + 2) hold such a pair, at b + 1 or b + 2;
+//   kBoundNeighbour  they do not: G(b) says the minimum is at or below b, not G(b + 2) above b + 2, and three more
+//                    independent evaluations on that side hold the pair - the minimum is within b - 2 .. b + 5;
+//   kBoundBisected   lower_bound_v_bisect.
+// Every stage returns a verified minimum, so the result is lower_bound_v_bisect's whatever the window was.
+enum BoundStage : int { kBoundAccepted = 0, kBoundNeighbour = 1, kBoundBisected = 2 };
+
+struct BoundTrial { int32_t b; bool g0, g1, g2; };
+
+ADC_HD BoundTrial bound_trial(int32_t b, int32_t target, float loc, float scale, const LogTableEntry *tab)
+{
+    return BoundTrial{b, bound_reached(b, target, loc, scale, tab), bound_reached(b + 1, target, loc, scale, tab),
+                      bound_reached(b + 2, target, loc, scale, tab)};
+}
+ADC_HD bool bound_open(const BoundTrial &t) { return t.g0 || !t.g2; }
+ADC_HD uint32_t bound_accepted(const BoundTrial &t) { return (uint32_t)(t.b + (t.g1 ? 1 : 2)); }      // (if not bound_open)
+
+// the trial left the bound open (in this lane or another of its wave): the neighbourhood, then the bisection
+ADC_HD uint32_t lower_bound_finish(const BoundTrial &t, int32_t target, float loc, float scale, const LogTableEntry *tab, int &stage)
+{
+    uint32_t v = bound_accepted(t);
+    bool open = bound_open(t);
+    if (open) {
+        // below: G at b - 3 .. b - 1, G(b) known true; above: G at b + 3 .. b + 5, G(b + 2) known false.  `first` = the first
+        // of the four consecutive i from `from` on with G(i); it is the minimum if G(i - 1) is known (and then false)
+        const bool down = t.g0;
+        const int32_t from = t.b + (down ? -3 : 3);
+        const bool h0 = bound_reached(from, target, loc, scale, tab), h1 = bound_reached(from + 1, target, loc, scale, tab),
+                   h2 = bound_reached(from + 2, target, loc, scale, tab);
+        const int first = h0 ? 0 : h1 ? 1 : h2 ? 2 : 3;
+        if (down ? first != 0 : first != 3) { v = (uint32_t)(from + first); open = false; stage = kBoundNeighbour; }
+    }
+    if (any_lane(open)) {
+        if (open) { v = lower_bound_v_bisect(target, loc, scale, tab); stage = kBoundBisected; }
+    }
+    return v;
+}
+
+ADC_HD uint32_t lower_bound_v_staged(int32_t target, float loc, float scale, const LogTableEntry *tab, int &stage)
+{
+    const BoundTrial t = bound_trial(lower_bound_window(target, loc, scale, tab), target, loc, scale, tab);
+    stage = kBoundAccepted;
+    if (any_lane(bound_open(t))) return lower_bound_finish(t, target, loc, scale, tab, stage);
+    return bound_accepted(t);
+}
+
+// min{v in [0, 2^24] : signed_cents_from_v(v) >= target}: one evaluation for the window, three independent ones to accept
+ADC_HD uint32_t lower_bound_v(int32_t target, float loc, float scale, const LogTableEntry *tab)
+{
+    int stage;
+    return lower_bound_v_staged(target, loc, scale, tab, stage);
+}
+
+// both bounds of a keyword (targets 1 - bid and bid), written side by side: the two windows first, then the six accepting
+// evaluations - independent chains for the scheduler instead of two searches one after the other.  stage = the later of the two.
+ADC_HD void lower_bound_pair(int32_t bid_c, float loc, float scale, const LogTableEntry *tab, uint32_t &w_lo, uint32_t &w_hi, int &stage)
+{
+    const int32_t b_lo = lower_bound_window(1 - bid_c, loc, scale, tab), b_hi = lower_bound_window(bid_c, loc, scale, tab);
+    const BoundTrial t_lo = bound_trial(b_lo, 1 - bid_c, loc, scale, tab), t_hi = bound_trial(b_hi, bid_c, loc, scale, tab);
+    w_lo = bound_accepted(t_lo);
+    w_hi = bound_accepted(t_hi);
+    stage = kBoundAccepted;
+    if (any_lane(bound_open(t_lo) || bound_open(t_hi))) {
+        int s_lo = kBoundAccepted, s_hi = kBoundAccepted;
+        w_lo = lower_bound_finish(t_lo, 1 - bid_c, loc, scale, tab, s_lo);
+        w_hi = lower_bound_finish(t_hi, bid_c, loc, scale, tab, s_hi);
+        stage = s_lo > s_hi ? s_lo : s_hi;
+    }
 }
 
 // min{d in [0, range] : min(mulhi(d, m), 2^24 - 1) >= W} for W in [0, 2^24]; `range` (<= 2^32) if no offset reaches W.
@@ -537,10 +701,9 @@ ADC_HD uint64_t offset_reaching(uint32_t W, uint32_t m, uint64_t range)
 // (w - n_lo) < n_w (unsigned 32-bit arithmetic; widths fit because the word 2^32 - 1 never wins)
 struct WinIntervals { uint32_t c_lo, c_w, n_lo, n_w; };
 
-ADC_HD WinIntervals win_intervals(int32_t bid_c, float loc, float scale, uint64_t t_click, const AuctionLaw &law, const LogTableEntry *tab)
+// from the two bounds w_lo = lower_bound_v(1 - bid), w_hi = lower_bound_v(bid):  bid > |cents|  <=>  -(bid - 1) <= S <= bid - 1
+ADC_HD WinIntervals win_intervals_of_bounds(uint32_t w_lo, uint32_t w_hi, uint64_t t_click, const AuctionLaw &law)
 {
-    const uint32_t w_lo = lower_bound_v(1 - bid_c, loc, scale, tab);     // bid > |cents|  <=>  -(bid - 1) <= S <= bid - 1
-    const uint32_t w_hi = lower_bound_v(bid_c, loc, scale, tab);
     WinIntervals r{0u, 0u, 0u, 0u};
     if (!(w_lo < w_hi)) return r;
     const uint64_t top = 0xFFFFFFFFull;                                  // words at or above it never win
@@ -553,6 +716,22 @@ ADC_HD WinIntervals win_intervals(int32_t bid_c, float loc, float scale, uint64_
     b = b < top ? b : top;
     if (a < b) { r.n_lo = (uint32_t)a; r.n_w = (uint32_t)(b - a); }
     return r;
+}
+
+// SIDE_BY_SIDE = false: one bound after the other (the same values; for kernels that have no registers to spare for eight
+// chains at once and set up a keyword's law rarely)
+template <bool SIDE_BY_SIDE = true>
+ADC_HD WinIntervals win_intervals(int32_t bid_c, float loc, float scale, uint64_t t_click, const AuctionLaw &law, const LogTableEntry *tab)
+{
+    uint32_t w_lo, w_hi;
+    if constexpr (SIDE_BY_SIDE) {
+        int stage;
+        lower_bound_pair(bid_c, loc, scale, tab, w_lo, w_hi, stage);
+    } else {
+        w_lo = lower_bound_v(1 - bid_c, loc, scale, tab);
+        w_hi = lower_bound_v(bid_c, loc, scale, tab);
+    }
+    return win_intervals_of_bounds(w_lo, w_hi, t_click, law);
 }
 
 // ---- conservative brackets of the two win intervals (keyword sets with few auctions per keyword) -------------------
@@ -574,24 +753,6 @@ ADC_HD WinIntervals win_intervals(int32_t bid_c, float loc, float scale, uint64_
 struct WinBrackets { WinIntervals out, in; };
 constexpr float kWordSlack = 4096.0f;
 
-ADC_HD float fast_exp2(float x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_exp2f(x);
-#else
-    return exp2f(x);
-#endif
-}
-ADC_HD float fast_rcp(float x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_rcpf(x);
-#else
-    return 1.0f / x;
-#endif
-}
-ADC_HD float min_num(float a, float b) { return __builtin_fminf(a, b); }       // the non-NaN operand if one is NaN
-ADC_HD float max_num(float a, float b) { return __builtin_fmaxf(a, b); }
 ADC_HD uint32_t sat_sub(uint32_t a, uint32_t b)                                                      // v_sub_u32 ... clamp
 {
 #if defined(__clang__)
@@ -652,7 +813,9 @@ ADC_HD void clicked_win_interval(int32_t bid_c, float loc, float scale, uint64_t
 {
     lo = 0u;
     width = 0u;
-    const uint32_t w_lo = lower_bound_v(1 - bid_c, loc, scale, tab), w_hi = lower_bound_v(bid_c, loc, scale, tab);
+    uint32_t w_lo, w_hi;
+    int stage;
+    lower_bound_pair(bid_c, loc, scale, tab, w_lo, w_hi, stage);
     if (!(w_lo < w_hi)) return;
     const uint64_t a = offset_reaching(w_lo, law.m_click, t_click);
     uint64_t b = offset_reaching(w_hi, law.m_click, t_click);

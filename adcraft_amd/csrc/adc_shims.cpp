@@ -177,6 +177,77 @@ ADC_EXPORT int64_t adc_check_win_brackets(int64_t n, const float *bid, const flo
     return bad;
 }
 
+// ---- the win bounds of a keyword on the host: adc_law.h lower_bound_v (window, three accepting evaluations, neighbourhood,
+// bisection) next to lower_bound_v_bisect (the verified-window bisection alone: the reference), for tests/test_win_bound_host.py
+template <typename F>
+static void shim_parallel_for(int64_t n, F body)          // body(i0, i1) on up to 8 threads
+{
+    const int T = n < 4096 ? 1 : 8;
+    std::vector<std::thread> threads;
+    for (int t = 0; t < T; ++t) threads.emplace_back([=]() { body(n * t / T, n * (t + 1) / T); });
+    for (auto &th : threads) th.join();
+}
+
+ADC_EXPORT int adc_lower_bound_v_host(int64_t n, const int32_t *target, const float *loc, const float *scale, uint32_t *v_out, uint8_t *stage_out)
+{
+    if (n < 0 || (n > 0 && (!target || !loc || !scale || !v_out))) return ADC_EINVAL;
+    const adc::LogTableEntry *table = host_log_table();
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            int stage = 0;
+            v_out[i] = adc::lower_bound_v_staged(target[i], loc[i], scale[i], table, stage);
+            if (stage_out) stage_out[i] = (uint8_t)stage;
+        }
+    });
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_lower_bound_v_bisect_host(int64_t n, const int32_t *target, const float *loc, const float *scale, uint32_t *v_out,
+                                             uint8_t *whole_range_out)
+{
+    if (n < 0 || (n > 0 && (!target || !loc || !scale || !v_out))) return ADC_EINVAL;
+    const adc::LogTableEntry *table = host_log_table();
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            bool whole = false;
+            v_out[i] = adc::lower_bound_v_bisect(target[i], loc[i], scale[i], table, &whole);
+            if (whole_range_out) whole_range_out[i] = whole ? 1 : 0;
+        }
+    });
+    return ADC_OK;
+}
+
+// adc::win_intervals for n keywords (bid in cents, as the kernels hold it); bisect != 0: the same intervals from the two
+// lower_bound_v_bisect bounds.  stage_out (nullable): the later stage of the keyword's two bounds (0 accepted, 1 neighbourhood,
+// 2 bisection; with bisect != 0: 1 if either bound's window failed and the bisection ran over the whole range, else 0)
+ADC_EXPORT int adc_win_intervals_host(int64_t n, const int32_t *bid_c, const float *cost_loc, const float *cost_scale, const float *buyside_ctr,
+                                      int32_t bisect, uint32_t *out4, uint8_t *stage_out)
+{
+    if (n < 0 || (n > 0 && (!bid_c || !cost_loc || !cost_scale || !buyside_ctr || !out4))) return ADC_EINVAL;
+    const adc::LogTableEntry *table = host_log_table();
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const adc::AuctionLaw law = adc::make_auction_law(buyside_ctr[i]);
+            const uint64_t t_click = adc::bernoulli_threshold(buyside_ctr[i]);
+            uint32_t w_lo, w_hi;
+            int stage = 0;
+            if (bisect) {
+                bool a = false, b = false;
+                w_lo = adc::lower_bound_v_bisect(1 - bid_c[i], cost_loc[i], cost_scale[i], table, &a);
+                w_hi = adc::lower_bound_v_bisect(bid_c[i], cost_loc[i], cost_scale[i], table, &b);
+                stage = (a || b) ? 1 : 0;
+            } else {
+                adc::lower_bound_pair(bid_c[i], cost_loc[i], cost_scale[i], table, w_lo, w_hi, stage);
+            }
+            const adc::WinIntervals r = adc::win_intervals_of_bounds(w_lo, w_hi, t_click, law);
+            uint32_t *o = out4 + 4 * i;
+            o[0] = r.c_lo; o[1] = r.c_w; o[2] = r.n_lo; o[3] = r.n_w;
+            if (stage_out) stage_out[i] = (uint8_t)stage;
+        }
+    });
+    return ADC_OK;
+}
+
 // adcraft/gymnasium_kw_utils.py:113-156 (sample_random_keywords), one keyword: what k_generate_explicit_keywords writes
 ADC_EXPORT int adc_sample_random_keyword(uint64_t key, uint32_t keyword, uint32_t serial, float *out8)
 {

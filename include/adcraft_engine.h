@@ -1088,6 +1088,18 @@ int adc_auction_word_intervals(float bid, float cost_loc, float cost_scale, floa
 int adc_auction_word_brackets(float bid, float cost_loc, float cost_scale, float buyside_ctr, uint32_t *out8);
 int64_t adc_check_win_brackets(int64_t n, const float *bid, const float *cost_loc, const float *cost_scale, const float *buyside_ctr,
                                const uint32_t *brackets8, int64_t *first_bad, double *ambiguous_words);
+/* diagnostic: the two bounds those intervals come from, W(target) = min{v in [0, 2^24] : signed cents of the competitor's bid at
+ * the 24-bit uniform v >= target} (adc_law.h), for n (target, loc, scale) on the host.  adc_lower_bound_v_host is the kernels'
+ * routine (a window from one table evaluation, three accepting evaluations, a neighbourhood, then the bisection); stage_n (may be
+ * NULL) says where each bound was settled: 0 accepted, 1 neighbourhood, 2 bisection.  adc_lower_bound_v_bisect_host is the
+ * verified-window bisection alone, the reference; whole_range_n (may be NULL): 1 where its window did not hold the bound.
+ * adc_win_intervals_host: out4 of adc_auction_word_intervals for n keywords with the bid in cents, from either routine
+ * (bisect != 0: the reference; stage_n then holds 1 where either bound's window failed). */
+int adc_lower_bound_v_host(int64_t n, const int32_t *target_n, const float *loc_n, const float *scale_n, uint32_t *v_n, uint8_t *stage_n);
+int adc_lower_bound_v_bisect_host(int64_t n, const int32_t *target_n, const float *loc_n, const float *scale_n, uint32_t *v_n,
+                                  uint8_t *whole_range_n);
+int adc_win_intervals_host(int64_t n, const int32_t *bid_cents_n, const float *cost_loc_n, const float *cost_scale_n,
+                           const float *buyside_ctr_n, int32_t bisect, uint32_t *out4_n, uint8_t *stage_n);
 /* one keyword of the default constructor's keyword set, on the host: exactly what adc_engine_generate_explicit_keywords writes for
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */

@@ -247,6 +247,7 @@ def lib():
         "adc_lower_bound_v_host": ([i64, vp, vp, vp, vp, vp], C.c_int),
         "adc_lower_bound_v_bisect_host": ([i64, vp, vp, vp, vp, vp], C.c_int),
         "adc_win_intervals_host": ([i64, vp, vp, vp, vp, i32, vp, vp], C.c_int),
+        "adc_fast_schedule_host": ([vp, i32, i32, vp, i64, vp, vp], i64),
         "adc_sample_random_keyword": ([C.c_uint64, C.c_uint32, C.c_uint32, vp], C.c_int),
         "adc_interp_act_host": ([f32, i32, f32, i32, C.c_double, C.c_double, C.c_double, vp, i32, i32, vp, vp, i32, vp, vp,
                                  C.c_double, vp, vp, vp, vp, vp], C.c_int),

@@ -83,6 +83,7 @@
 
 #include "../../include/adcraft_engine.h"
 #include "adc_law.h"
+#include "adc_fast_schedule.h"
 #include "adc_interp.h"
 #include "adc_mlp.h"
 #include "adc_es.h"

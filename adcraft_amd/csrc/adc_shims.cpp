@@ -13,6 +13,7 @@
 
 #include "../../include/adcraft_engine.h"
 #include "adc_law.h"
+#include "adc_fast_schedule.h"
 #include "adc_interp.h"
 #include "adc_mlp.h"
 #include "adc_es.h"
@@ -246,6 +247,103 @@ ADC_EXPORT int adc_win_intervals_host(int64_t n, const int32_t *bid_c, const flo
         }
     });
     return ADC_OK;
+}
+
+// ---- the host twin of k_step_implicit_fast's phase-2 schedule (adc_fast_schedule.h: the helpers the kernel calls) ------------
+// For tile number tile_index (env x tiles-per-env + tile: it only rotates which wave takes which part of the items) of tile_kw
+// keywords with the given volumes: every (pass, wave, round, lane) slot the kernel issues, as rows of
+// seven int32 {pass, wave, round, lane, keyword, first auction, count} (an idle slot: keyword -1, count 0); pass 0 = full items,
+// 1 = the tails' whole calls, 2 = the partial calls.  Returns the number of rows (the first `cap` of them are written; slots7 may be
+// NULL with cap 0), or a negative adc_status.  totals2 (nullable) = {wave-call-slots issued: Philox calls, counted once per wave
+// that runs them; calls that hold at least one auction, summed over the keywords}; info2 (nullable) = {chunk_shift, dense}.
+ADC_EXPORT int64_t adc_fast_schedule_host(const int32_t *vol_k, int32_t tile_kw, int32_t tile_index, int32_t *slots7, int64_t cap, int64_t *totals2,
+                                          int32_t *info2)
+{
+    constexpr int B = adc::kFastTileLanes, WL = adc::kFastWaveLanes, NW = adc::kFastTileWaves;
+    if (!vol_k || tile_kw < 1 || tile_kw > B || tile_index < 0 || cap < 0 || (cap > 0 && !slots7)) return ADC_EINVAL;
+    int V[B];
+    int64_t volume = 0, needed = 0;
+    int live = 0;
+    for (int t = 0; t < B; ++t) {
+        V[t] = t < tile_kw ? vol_k[t] : 0;
+        if (V[t] < 0 || V[t] > adc::kVolumeMax) return ADC_EINVAL;
+        volume += V[t];
+        live += V[t] > 0;
+        needed += adc::fast_calls_needed(V[t]);
+    }
+    const int tile_volume = (int)volume;                        // (<= 256 * 2^20)
+    const int chunk_shift = adc::fast_chunk_shift(tile_volume);
+    // the two prefixes as the kernel forms them: one packed scan per wave of 64 keywords, the waves' totals added unpacked
+    std::vector<int> off((size_t)B + 1), first_call((size_t)B);
+    std::vector<unsigned char> tail_kw((size_t)(adc::kFastTailCallsMax * B));
+    int total = 0, total2 = 0;
+    for (int w = 0; w < NW; ++w) {
+        int packed = 0;
+        for (int lane = 0; lane < WL; ++lane) {
+            const int t = w * WL + lane;
+            const int nch = adc::fast_full_items(V[t], chunk_shift), ntc = adc::fast_tail_calls(V[t], chunk_shift);
+            packed += adc::fast_pack_counts(nch, ntc);
+            off[(size_t)t] = total + adc::fast_packed_items(packed) - nch;
+            first_call[(size_t)t] = total2 + adc::fast_packed_calls(packed) - ntc;
+            for (int c = 0; c < adc::kFastTailCallsMax; ++c)
+                if (c < ntc) tail_kw[(size_t)(first_call[(size_t)t] + c)] = (unsigned char)t;
+        }
+        total += adc::fast_packed_items(packed);
+        total2 += adc::fast_packed_calls(packed);
+    }
+    off[(size_t)B] = total;
+    int64_t rows = 0, issued = 0;
+    auto emit = [&](int pass, int w, int r, int lane, int u, int j0, int n) {
+        if (rows < cap) {
+            int32_t *o = slots7 + 7 * rows;
+            o[0] = pass; o[1] = w; o[2] = r; o[3] = lane; o[4] = n > 0 ? u : -1; o[5] = n > 0 ? j0 : 0; o[6] = n;
+        }
+        rows += 1;
+    };
+    for (int pass = 0; pass < 2; ++pass) {
+        const int shift = pass == 0 ? chunk_shift : adc::kFastCallShift;
+        const int ptotal = pass == 0 ? total : total2;
+        for (int w = 0; w < NW; ++w) {
+            const int part = adc::fast_wave_part(w, tile_index);
+            const int rounds = adc::fast_wave_rounds(ptotal, part), base = adc::fast_wave_base(ptotal, part);
+            issued += (int64_t)rounds << (shift - adc::kFastCallShift);
+            for (int lane = 0; lane < WL; ++lane) {
+                const int first = adc::fast_lane_first(base, rounds, lane, ptotal);
+                int u = 0, u_end = 0;
+                if (pass == 0) {
+                    for (int s = B / 2; s > 0; s >>= 1)
+                        if (off[(size_t)(u + s)] <= first) u += s;
+                    u_end = off[(size_t)u + 1];
+                }
+                for (int r = 0; r < rounds; ++r) {
+                    const int item = first + r;
+                    const bool has = adc::fast_item_exists(item, ptotal);
+                    int j0 = 0;
+                    if (pass == 0) {
+                        while (has && item >= u_end) { u += 1; u_end = off[(size_t)u + 1]; }
+                        if (has) j0 = (item - off[(size_t)u]) << shift;
+                    } else if (has) {
+                        u = tail_kw[(size_t)item];
+                        j0 = adc::fast_tail_first(V[u], chunk_shift) + ((item - first_call[(size_t)u]) << shift);
+                    }
+                    emit(pass, w, r, lane, u, j0, has ? 1 << shift : 0);
+                }
+            }
+        }
+    }
+    for (int w = 0; w < NW; ++w) {                              // (a wave none of whose keywords has a partial call issues nothing)
+        bool any = false;
+        for (int lane = 0; lane < WL; ++lane) any = any || adc::fast_partial_count(V[w * WL + lane]) != 0;
+        if (!any) continue;
+        issued += 1;
+        for (int lane = 0; lane < WL; ++lane) {
+            const int t = w * WL + lane;
+            emit(2, w, 0, lane, t, adc::fast_partial_first(V[t]), adc::fast_partial_count(V[t]));
+        }
+    }
+    if (totals2) { totals2[0] = issued; totals2[1] = needed; }
+    if (info2) { info2[0] = chunk_shift; info2[1] = adc::fast_tile_dense(tile_volume, live) ? 1 : 0; }
+    return rows;
 }
 
 // adcraft/gymnasium_kw_utils.py:113-156 (sample_random_keywords), one keyword: what k_generate_explicit_keywords writes

@@ -30,9 +30,12 @@ __device__ unsigned long long g_dbg[16];
 __device__ unsigned long long g_fdbg[256][8];       // k_step_implicit_fast, wave 0 of each workgroup, spread over 256 rows
 #define FDBG_T() __builtin_amdgcn_s_memtime()
 #define FDBG_ADD(i, x) fdbg[i] += (x)
+__device__ unsigned long long g_fslots[256][2];     // k_step_implicit_fast, every wave: Philox calls issued in phase 2 | calls that hold an auction
+#define FSLOT_ADD(i, x) fslots[i] += (x)
 #else
 #define FDBG_T() 0ull
 #define FDBG_ADD(i, x) (void)0
+#define FSLOT_ADD(i, x) (void)0
 #endif
 
 // an env whose budget-bound day k_step_exact_rows hands to k_step_rest_of_day: where the walk stands

@@ -3877,4 +3877,20 @@ extern "C" __attribute__((visibility("default"))) int adc_debug_read(unsigned lo
     }
     return 0;
 }
+
+// k_step_implicit_fast, all waves since the last reset: out2 = {Philox calls issued in phase 2 (wave-call-slots), calls that hold at
+// least one auction (lane-calls: 64 of them fill a slot)}
+extern "C" __attribute__((visibility("default"))) int adc_debug_read_fast_slots(unsigned long long *out2, int reset)
+{
+    hipDeviceSynchronize();
+    static unsigned long long rows[256][2];
+    hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_fslots), sizeof(rows));
+    out2[0] = out2[1] = 0;
+    for (int r = 0; r < 256; ++r) { out2[0] += rows[r][0]; out2[1] += rows[r][1]; }
+    if (reset) {
+        std::memset(rows, 0, sizeof(rows));
+        hipMemcpyToSymbol(HIP_SYMBOL(g_fslots), rows, sizeof(rows));
+    }
+    return 0;
+}
 #endif

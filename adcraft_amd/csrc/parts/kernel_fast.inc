@@ -14,7 +14,8 @@
 //     ~20 auctions they would serve - and resolve each auction from its sampled competitor bid (DIRECT).
 // Both forms are the same law (the oracle only knows the auction-by-auction form); results are identical bit for bit.
 constexpr int kQueueCap = 128;    // per-wave queue of deferred clicked wins (entries): drained whenever 64 wait, so <= 63 + 64 ever do
-constexpr int kDenseVolumePerKeyword = 24;     // tiles averaging at least this many auctions per non-empty keyword use intervals
+constexpr int kDenseVolumePerKeyword = adc::kDenseVolumePerKeyword;      // (adc_fast_schedule.h: the schedule of phase 2 and this test, shared with the host twin)
+static_assert(kFastBlock == adc::kFastTileLanes && kWave == adc::kFastWaveLanes, "adc_fast_schedule.h describes this workgroup");
 
 // per keyword, two 16-byte records in separate arrays (a wave's consecutive keywords then cover every LDS bank once per
 // ds_read_b128; one 32-byte record per keyword is a built-in 2-way bank conflict).  16-byte aligned: a record that is only
@@ -41,6 +42,12 @@ union alignas(16) KwWin {                     // per keyword, 16 B
 // counts of a keyword-day packed in one 64-bit LDS accumulator: impressions | clicks << 21 | conversions << 42
 // (each is at most the day's volume <= 2^20 = adc::kVolumeMax)
 constexpr int kClkShift = 21, kConvShift = 42;
+// sh.vol[u] holds the keyword's volume in its low 21 bits and, above them, the exclusive prefix of the keywords' tail calls (at
+// most 3 per keyword: 768 in a tile) - a second prefix array would take the listing variant over five workgroups' worth of LDS
+constexpr int kVolBits = 21;
+constexpr int kVolMask = (1 << kVolBits) - 1;
+constexpr int kTailCallsMax = adc::kFastTailCallsMax * kFastBlock;
+static_assert(adc::kVolumeMax <= kVolMask && kTailCallsMax < (1 << (31 - kVolBits)), "volume and tail-call prefix share a word");
 static_assert(adc::kVolumeMax < (1 << kClkShift), "three counts of up to kVolumeMax must fit 21 bits each");
 
 // (Keyword sets with few auctions per keyword - the engine's volume hint - go to k_step_implicit_sparse, kernel_sparse.inc; this
@@ -65,7 +72,8 @@ struct FastShared {
     adc::LogTableEntry logtab[adc::kLogTableIntervals];     // copy of g_log_table
     float normtab[adc::kNormTableEntries + 1];              // node values of g_norm_table (+ the p = 1/2 node)
     int off[kFastBlock + 1];        // exclusive prefix of the keywords' full work items (+ the total)
-    int vol[kFastBlock];
+    int vol[kFastBlock];            // volume | the same prefix of the keywords' tail calls << kVolBits
+    unsigned char tail_kw[kTailCallsMax];       // the keyword of every tail call, in the prefix's order (what pass 1 finds its keyword by)
 };
 // what the listing variant keeps on top of that (envs that list their clicked wins for k_step_click_walk, see resolve_click)
 template <bool LISTS>
@@ -124,6 +132,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     const int tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
     [[maybe_unused]] unsigned long long fdbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    [[maybe_unused]] unsigned long long fslots[2] = {0, 0};      // (ADC_EXP_TIMING) calls issued by this wave | calls needed by this lane's keywords
 
     auto load_tile = [&](int tile_index) {
         FastRaw r{};
@@ -163,8 +172,11 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     const int tile = tile_index - env * tiles;
     const int k = tile * tile_kw + tid;
     const bool valid = tid < tile_kw && k < v.K;
-    const uint64_t key = raw.key;
-    const uint32_t tick = raw.tick;
+    // (block-uniform, and said so: the Philox round keys derived from them then stay in SGPRs - each is one operand of a v_bitop3 -
+    // whatever the compiler makes of the tile loop's carried loads; as vector values they take 13 VGPRs through phase 2)
+    const uint64_t key = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(raw.key >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)raw.key);
+    const uint32_t tick = (uint32_t)__builtin_amdgcn_readfirstlane((int)raw.tick);
     const uint32_t kw_base = (uint32_t)(tile * tile_kw);
     if (LISTS && raw.emit && tid == 0) v.click_tick[env] = tick + 1u;      // (every tile of the env writes the same value)
     if constexpr (LISTS) { if (raw.emit && !NARROW && tid < adc::kTimesteps) ls.row_count[tid] = 0u; }      // (before phase 1's barriers)
@@ -193,7 +205,6 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         const float t = __builtin_truncf(x);
         V = (int)t + ((x - t) >= 0.5f ? 1 : 0);
     }
-    sh.vol[tid] = V;
     if constexpr (LISTS) {
         if (raw.emit) {                         // (block-uniform) auctions of the sub-timesteps up to the env's row hint (adc::cell_range)
             const int rows = (int)v.click_row_hint[env], s = V / adc::kTimesteps;
@@ -211,14 +222,16 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     int tile_volume = 0, tile_live = 0;
 #pragma unroll
     for (int i = 0; i < kFastBlock / kWave; ++i) { tile_volume += sh.wave_vol[i]; tile_live += sh.wave_live[i]; }
-    const bool dense = tile_volume >= kDenseVolumePerKeyword * tile_live;          // (block-uniform)
+    const bool dense = adc::fast_tile_dense(tile_volume, tile_live);               // (block-uniform)
     // work-item size: 16 auctions when the tile has plenty of them; 8 or 4 on sparse tiles, so that the items still
     // number about two per lane.  Results do not depend on it: every draw is addressed by (auction, keyword).
-    const int chunk_shift = tile_volume >= 32 * kFastBlock ? 4 : tile_volume >= 16 * kFastBlock ? 3 : 2;
-    const int chunk = 1 << chunk_shift;
-    const int nch = V >> chunk_shift;      // FULL items; the last V mod chunk auctions are the keyword's tail
-    const int incl = wave_scan_i32(nch);
+    const int chunk_shift = adc::fast_chunk_shift(tile_volume);
+    const int nch = adc::fast_full_items(V, chunk_shift);       // FULL items; the last V mod chunk auctions are the keyword's tail
+    const int ntc = adc::fast_tail_calls(V, chunk_shift);       // the whole calls of that tail, dealt as items of one call
+    // (both prefixes in one scan: adc::fast_pack_counts - a wave's full items stay below 2^23, its tail calls below 2^8)
+    const int incl = wave_scan_i32(adc::fast_pack_counts(nch, ntc));
     if (lane == 63) sh.wave_tot[wv] = incl;
+    FSLOT_ADD(1, (unsigned long long)adc::fast_calls_needed(V));
     // the keyword's law (only keywords with auctions need one)
     [[maybe_unused]] const unsigned long long t_law = FDBG_T();
     if (V > 0) {
@@ -241,26 +254,42 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     }
     FDBG_ADD(1, FDBG_T() - t_law);
     __syncthreads();
-    int wave_base = 0, total = 0;
+    int wave_base = 0, total = 0, wave_base2 = 0, total2 = 0;
 #pragma unroll
     for (int i = 0; i < kFastBlock / kWave; ++i) {
         const int t = sh.wave_tot[i];
-        if (i < wv) wave_base += t;
-        total += t;
+        if (i < wv) { wave_base += adc::fast_packed_items(t); wave_base2 += adc::fast_packed_calls(t); }
+        total += adc::fast_packed_items(t);
+        total2 += adc::fast_packed_calls(t);
     }
     __syncthreads();                    // (wave_tot / volw share memory with the queues: everybody has read them)
-    sh.off[tid] = wave_base + incl - nch;
+    sh.off[tid] = wave_base + adc::fast_packed_items(incl) - nch;
+    {
+        const int first_call = wave_base2 + adc::fast_packed_calls(incl) - ntc;
+        sh.vol[tid] = V | (first_call << kVolBits);
+#pragma unroll
+        for (int c = 0; c < adc::kFastTailCallsMax; ++c)
+            if (c < ntc) sh.tail_kw[first_call + c] = (unsigned char)tid;
+    }
     if (tid == 0) sh.off[kFastBlock] = total;
     __syncthreads();
     [[maybe_unused]] const unsigned long long t_p2 = FDBG_T();
     FDBG_ADD(0, t_p2 - t_start);
 
     // ---- phase 2: work items of `chunk` consecutive auctions of one keyword ------------------------
-    // Full items are dealt lane-major: lane l resolves items [l R, (l+1) R) of the tile's R x 256 (R = rounds), so a lane
-    // stays on one keyword for several rounds, the 64 lanes of a wave are on ~64 different, consecutive keywords at any time
-    // (their LDS records and accumulators then fall on distinct banks, and the same keyword is rarely hit twice by one
-    // stage-B batch), and the lane finds its next keyword by comparing with a bound it holds in a register.  The keywords'
-    // tails (V mod chunk auctions) follow in one last round, one keyword per lane.
+    // Full items are dealt lane-major and per wave (adc_fast_schedule.h): the tile's ceil(total / 64) wave-rounds are split
+    // over the four waves, R_w each (they differ by at most one; w = the part the wave takes in this tile, rotated from
+    // tile to tile), and lane l of wave w resolves the items
+    // [base_w + l R_w, base_w + (l + 1) R_w), so a lane stays on one keyword for several rounds, the 64 lanes of a wave are on
+    // ~64 different, consecutive keywords at any time (their LDS records and accumulators then fall on distinct banks, and the
+    // same keyword is rarely hit twice by one stage-B batch), and the lane finds its next keyword by comparing with a bound it
+    // holds in a register.  No wave runs a round for another wave's items: a workgroup-wide round count issued up to three
+    // wave-rounds of empty slots per tile, and an empty slot costs what a full one does (below).
+    // The keywords' tails (V mod chunk auctions) follow at the granularity of a Philox call: their whole calls are dealt as
+    // items of four auctions by the same scheme over a second prefix (a tail call finds its keyword in tail_kw, and its place
+    // in the keyword's tail by the prefix kept in the high bits of vol), and what is left - V mod 4 auctions - runs
+    // last, one keyword per lane, as a single call.  (One keyword per lane for the whole tail was four calls in every wave
+    // for a mean of 1.9 calls of work per lane.)
     // Control flow is wave-uniform (idle lanes carry an empty law) so that the deferred-click queue below can be maintained
     // with ballots.  Stage A (every auction): one Philox call per FOUR auctions (one word each); the word is classified
     // (lost / won / won and clicked).  Stage B (clicked wins only, ~1/4 of auctions): the (keyword, auction, word) is pushed
@@ -314,7 +343,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             if (j < ls.jcut[uu] || price <= ls.price_cut) {
                 // the click's sub-timestep and index in its cell: adc::cell_range inverted, the quotient estimated in float32
                 // (exact operands below 2^24) and fixed up
-                const int V = sh.vol[uu];
+                const int V = sh.vol[uu] & kVolMask;
                 const int s = V / adc::kTimesteps, first = V - (adc::kTimesteps - 1) * s;
                 int row = 0, jc = j;
                 if (j >= first) {
@@ -354,7 +383,8 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         qtail += __popcll(m);
     };
     // one work item: auctions j0 .. j0 + n - 1 of keyword u (n == chunk unless TAIL)
-    auto run_item = [&](auto tail_tag, int u, int j0, int n) {
+    // (`calls4` = 4 x the Philox calls of the item: chunk for a full item, 4 for a tail call and for the partial call)
+    auto run_item = [&](auto tail_tag, int u, int j0, int n, int calls4) {
         constexpr bool TAIL = decltype(tail_tag)::value;
         const uint32_t kw = kw_base + (uint32_t)u;
         const unsigned int tagj0 = ((unsigned int)u << 24) | (unsigned int)j0;
@@ -363,8 +393,9 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             adc::WinIntervals iv = sh.win[u].iv;
             if (n == 0) iv.c_w = iv.n_w = 0u;                                       // a lane without an item resolves nothing
             asm volatile("" : "+v"(iv.c_w), "+v"(iv.n_w));      // (opaque: hipcc otherwise turns the zero width into `has-item && ...` on every compare)
-            for (int i = 0; i < chunk; i += 4) {
+            for (int i = 0; i < calls4; i += 4) {
                 if (TAIL && __builtin_amdgcn_ballot_w64(i < n) == 0ull) break;
+                FSLOT_ADD(0, 1ull);
                 const adc::U4 w = adc::draw(key, (uint32_t)(j0 + i) >> 2, adc::ST_AUCTION, kw, tick);
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
@@ -383,8 +414,9 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             const KwLawB kb = sh.law_b[u];
             const adc::AuctionLaw law{kb.d.t_click, ka.m_click, sh.win[u].d.m_noclick};
             const int bid_c = n > 0 ? kb.d.bid_c : 0;                               // (bid 0 never wins)
-            for (int i = 0; i < chunk; i += 4) {
+            for (int i = 0; i < calls4; i += 4) {
                 if (TAIL && __builtin_amdgcn_ballot_w64(i < n) == 0ull) break;
+                FSLOT_ADD(0, 1ull);
                 const adc::U4 w = adc::draw(key, (uint32_t)(j0 + i) >> 2, adc::ST_AUCTION, kw, tick);
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
@@ -402,26 +434,49 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         if (imp) atomicAdd(&sh.a_cnt[u], (unsigned long long)imp);
     };
 
-    const int rounds = (total + kFastBlock - 1) / kFastBlock;
-    {
-        // this lane's full items: [first, last); u = the keyword of the current one, u_end = where that keyword's items end
-        const int first = min(tid * rounds, total), last = min(first + rounds, total);
-        int u = 0;
+    // the full items (pass 0), then the tails' whole calls (pass 1): one loop, so that the item's code exists once
+#pragma nounroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const int shift = pass == 0 ? chunk_shift : adc::kFastCallShift;
+        const int ptotal = pass == 0 ? total : total2;
+        // R_w, base_w: wave-uniform.  The wave takes the part (w + tile index) mod 4, so that the waves with the shorter counts are
+        // not the same wave - the same SIMD - in every workgroup of the CU (measured: that alone is worth more than the slots saved)
+        const int part = adc::fast_wave_part(wq, tile_index);
+        const int rounds = __builtin_amdgcn_readfirstlane(adc::fast_wave_rounds(ptotal, part));
+        const int base = __builtin_amdgcn_readfirstlane(adc::fast_wave_base(ptotal, part));
+        if (rounds == 0) continue;
+        // this lane's items: `rounds` from `first`, as far as there are any; u = the keyword of the current one, u_end = where
+        // that keyword's full items end
+        const int first = adc::fast_lane_first(base, rounds, lane, ptotal);
+        int u = 0, u_end = 0;
+        if (pass == 0) {
 #pragma unroll
-        for (int s = kFastBlock / 2; s > 0; s >>= 1)
-            if (sh.off[u + s] <= first) u += s;
-        int u_end = sh.off[u + 1];
+            for (int s = kFastBlock / 2; s > 0; s >>= 1)
+                if (sh.off[u + s] <= first) u += s;
+            u_end = sh.off[u + 1];
+        }
         for (int r = 0; r < rounds; ++r) {
             const int item = first + r;
-            const bool has = item < last;
+            const bool has = adc::fast_item_exists(item, ptotal);
             [[maybe_unused]] const unsigned long long t_item = FDBG_T();
-            while (has && item >= u_end) { u += 1; u_end = sh.off[u + 1]; }         // (keywords without full items are skipped)
-            const int j0 = has ? (item - sh.off[u]) << chunk_shift : 0;
+            int j0 = 0;
+            if (pass == 0) {
+                while (has && item >= u_end) { u += 1; u_end = sh.off[u + 1]; }     // (keywords without full items are skipped)
+                if (has) j0 = (item - sh.off[u]) << shift;
+            } else if (has) {
+                u = sh.tail_kw[item];
+                const int vw = sh.vol[u];
+                j0 = adc::fast_tail_first(vw & kVolMask, chunk_shift) + ((item - (int)((unsigned int)vw >> kVolBits)) << shift);
+            }
             FDBG_ADD(2, FDBG_T() - t_item);
-            run_item(std::false_type{}, u, j0, has ? chunk : 0);
+            run_item(std::false_type{}, u, j0, has ? 1 << shift : 0, 1 << shift);
         }
-        // the tails: keyword `tid`, auctions (V >> shift << shift) .. V - 1
-        if (__syncthreads_or((V & (chunk - 1)) != 0)) run_item(std::true_type{}, tid, (V >> chunk_shift) << chunk_shift, V & (chunk - 1));
+    }
+    // the partial calls: keyword `tid`, its last V mod 4 auctions
+    // (the volume read back: nothing of phase 1 stays in a register over the passes above)
+    if (__syncthreads_or(adc::fast_partial_count(V) != 0)) {
+        const int Vt = sh.vol[tid] & kVolMask;
+        run_item(std::true_type{}, tid, adc::fast_partial_first(Vt), adc::fast_partial_count(Vt), 1 << adc::kFastCallShift);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -475,6 +530,11 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
 #ifdef ADC_EXP_TIMING
     // slots 8..15 (cycles of wave 0, summed over workgroups): phase 1 | law setup | item search | phase 2 | stage B | phase 3 | tiles | stage-B batches
     if (tid == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_fdbg[blockIdx.x & 255][i], fdbg[i]);
+    // every wave: Philox calls it issued in phase 2 (wave-call-slots) | calls that hold an auction, summed over its keywords
+    {
+        const unsigned long long needed = (unsigned long long)wave_sum_i64((long long)fslots[1]);
+        if (lane == 0) { atomicAdd(&g_fslots[blockIdx.x & 255][0], fslots[0]); atomicAdd(&g_fslots[blockIdx.x & 255][1], needed); }
+    }
 #endif
 }
 

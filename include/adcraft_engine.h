@@ -1100,6 +1100,16 @@ int adc_lower_bound_v_bisect_host(int64_t n, const int32_t *target_n, const floa
                                   uint8_t *whole_range_n);
 int adc_win_intervals_host(int64_t n, const int32_t *bid_cents_n, const float *cost_loc_n, const float *cost_scale_n,
                            const float *buyside_ctr_n, int32_t bisect, uint32_t *out4_n, uint8_t *stage_n);
+/* diagnostic: how the budget-free IMPLICIT pass deals one tile's auctions to its lanes, on the host (the schedule arithmetic the
+ * kernel calls, csrc/adc_fast_schedule.h).  vol_k = the volumes of the tile's tile_kw (1..256) keywords; tile_index (>= 0) = env x
+ * tiles per env + tile, which only rotates the parts of the item range among the four waves.  Every issue slot becomes a
+ * row of seven int32 {pass, wave, round, lane, keyword, first auction, count}; an idle slot has keyword -1 and count 0.  Pass 0 = full
+ * work items, 1 = the whole Philox calls of the keywords' tails, 2 = the partial calls (the last V mod 4 auctions).  Returns the
+ * number of rows, of which the first `cap` are written (slots7 may be NULL with cap 0), or a negative adc_status.  totals2 (may be
+ * NULL) = {wave-call-slots issued: Philox calls, one per wave that runs them; calls that hold at least one auction, over all
+ * keywords - 64 of these fill a slot}; info2 (may be NULL) = {log2 of the work-item size, 1 if the tile uses word intervals}. */
+int64_t adc_fast_schedule_host(const int32_t *vol_k, int32_t tile_kw, int32_t tile_index, int32_t *slots7, int64_t cap, int64_t *totals2,
+                               int32_t *info2);
 /* one keyword of the default constructor's keyword set, on the host: exactly what adc_engine_generate_explicit_keywords writes for
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */

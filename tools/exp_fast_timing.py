@@ -24,6 +24,11 @@ for _ in range(5):
     eng.step_device()
 eng.synchronize()
 L.adc_debug_read(out, 1)
+has_slots = hasattr(L, "adc_debug_read_fast_slots")      # (a timing build from before the slot counters has none)
+slots = (C.c_ulonglong * 2)()
+if has_slots:
+    L.adc_debug_read_fast_slots.argtypes = [C.c_void_p, C.c_int]
+    L.adc_debug_read_fast_slots(slots, 1)
 eng.profile_enable(True)
 eng.profile_read()
 steps = 20
@@ -32,6 +37,8 @@ for _ in range(steps):
 eng.synchronize()
 kernel_ms, launches = eng.profile_read()
 L.adc_debug_read(out, 0)
+if has_slots:
+    L.adc_debug_read_fast_slots(slots, 0)
 v = np.array(list(out), dtype=np.float64)[8:]
 waves = v[6]
 print(cfg, "kernel ms per step [fast, tail+rows, metric]:", [round(float(x) / steps, 4) for x in kernel_ms])
@@ -40,3 +47,7 @@ tot = v[0] + v[3] + v[5]
 for i, n in enumerate(names):
     print(f"{n:40s} {v[i] / waves:10.0f} cycles per wave   {100 * v[i] / tot:5.1f} %")
 print(f"stage-B batches per wave {v[7] / waves:.2f}; cycles per batch {v[4] / max(v[7], 1):.0f}; waves per step {waves / steps:.0f}")
+issued, needed = float(slots[0]), float(slots[1])
+if has_slots:
+    print(f"phase 2, all waves: wave-call-slots issued per tile {issued / max(waves, 1):.2f}; calls that hold an auction / 64 per tile {needed / 64 / max(waves, 1):.2f}; "
+          f"issued over needed {64 * issued / max(needed, 1):.4f}")

@@ -53,19 +53,16 @@
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
-//   parts/kernel_obs_norm.inc     the running observation normaliser: the record's batch moments in one pass, the merge, the new vectors (adc_norm.h).
-//   parts/kernel_rew_norm.inc     the running reward normaliser: the discounted returns' scan, their moments, the merge, the multiplier;
-//        the GAE kernels under a multiplier and a clip (adc_rew_norm.h).
-//   parts/kernel_td3_norm.inc     the TD3 learners' running normalisers over raw rows: the observation finish, the returns' scan under
-//        the TD3 discount, the batched copy (adc_td3_norm.h); the batch kernels of kernel_td3 / kernel_td3_pop normalise as they gather.
+//   parts/kernel_norm.inc         the running normalisers, one set of kernels: the record's batch moments of the observations in one pass,
+//        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
+//        the learner's discount, their moments, the merge, the multiplier, the GAE kernels under a multiplier and a clip (adc_rew_norm.h);
+//        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop normalise as they gather.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over either kind of population.
-//   parts/obs_norm_api.inc        the entry points of the running observation normaliser.
-//   parts/rew_norm_api.inc        the entry points of the running reward normaliser.
-//   parts/td3_norm_api.inc        the entry points of the TD3 learners' running normalisers.
+//   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners' - over shared helpers.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -114,9 +111,7 @@ namespace adck {
 #include "parts/kernel_td3.inc"
 #include "parts/kernel_td3_pop.inc"
 #include "parts/kernel_pbt.inc"
-#include "parts/kernel_obs_norm.inc"
-#include "parts/kernel_rew_norm.inc"
-#include "parts/kernel_td3_norm.inc"
+#include "parts/kernel_norm.inc"
 }  // namespace adck
 using namespace adck;
 
@@ -125,7 +120,5 @@ using namespace adck;
 #include "parts/td3_api.inc"
 #include "parts/td3_pop_api.inc"
 #include "parts/pbt_api.inc"
-#include "parts/obs_norm_api.inc"
-#include "parts/rew_norm_api.inc"
-#include "parts/td3_norm_api.inc"
+#include "parts/norm_api.inc"
 #include "parts/comm_api.inc"

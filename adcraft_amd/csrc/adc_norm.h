@@ -2,7 +2,7 @@
 // column, kept as (count, mean, M2) and merged batch by batch from the rollout record (Chan, Golub, LeVeque 1979: the parallel
 // update of the moments; what Stable-Baselines3's VecNormalize and RLlib's MeanStdFilter keep around an env), and the float32
 // vectors shift / scale that adc_mlp.h's x = (x - shift) * scale reads.  Shared by the device kernels
-// (parts/kernel_obs_norm.inc) and the host twin adc_obs_norm_host (adc_shims.cpp); tests/norm_ref.py restates these comments in
+// (parts/kernel_norm.inc) and the host twin adc_obs_norm_host (adc_shims.cpp); tests/norm_ref.py restates these comments in
 // numpy, bit for bit.
 //
 // Every float64 value below is the result of ONE correctly rounded IEEE operation (-ffp-contract=off; float64 division and
@@ -64,43 +64,48 @@ ADC_HD void norm_merge(const NormConfig &c, double mb, double M2b, int64_t S, in
     }
 }
 
-// everything after the chunks are joined, for one column: sx, qx over S samples under (shift, scale) merged into (count, mean, M2);
-// the new vectors
-ADC_HD void norm_finish(const NormConfig &c, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &shift, float &scale)
+// the law's "moments": sx, qx over S samples into the batch's mean and its variance, clamped at 0 (a NaN becomes 0)
+ADC_HD void norm_batch_moments(double sx, double qx, int64_t S, double &mx, double &vx)
 {
     const double fs = (double)S;
-    const double mx = sx / fs;
+    mx = sx / fs;
     const double qm = qx / fs, mm = mx * mx;
-    double vx = qm - mm;
+    vx = qm - mm;
     vx = vx > 0.0 ? vx : 0.0;
-    const double sc = (double)scale;
-    const double mr = mx / sc, mb = (double)shift + mr;
-    const double sc2 = sc * sc, vb = vx / sc2;
-    const double M2b = vb * fs;
-    norm_merge(c, mb, M2b, S, count, mean, M2);
-    const double var = M2 / (double)count;
-    double sd = __builtin_sqrt(var);
-    sd = sd < c.min_std ? c.min_std : sd;
-    shift = (float)mean;
-    scale = (float)(1.0 / sd);
 }
 
-// norm_finish for RAW rows (adc_td3_norm.h: the TD3 learners' record and ring hold the flat observation itself): the batch's
-// moments are raw-space moments as they stand, there is no back-conversion through the vectors in force
-ADC_HD void norm_finish_raw(const NormConfig &c, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &shift, float &scale)
+// the law's "raw space": the moments of rows normalised by a column's (shift, scale) taken back through those vectors
+ADC_HD void norm_to_raw(float shift, float scale, double &mx, double &vx)
 {
-    const double fs = (double)S;
-    const double mx = sx / fs;
-    const double qm = qx / fs, mm = mx * mx;
-    double vx = qm - mm;
-    vx = vx > 0.0 ? vx : 0.0;
-    const double M2b = vx * fs;
-    norm_merge(c, mx, M2b, S, count, mean, M2);
+    const double sc = (double)scale;
+    const double mr = mx / sc;
+    mx = (double)shift + mr;
+    const double sc2 = sc * sc;
+    vx = vx / sc2;
+}
+
+// the law's scale: 1 / max(sqrt(M2 / count), min_std), as the float32 the kernels multiply by
+ADC_HD float norm_scale(const NormConfig &c, int64_t count, double M2)
+{
     const double var = M2 / (double)count;
     double sd = __builtin_sqrt(var);
     sd = sd < c.min_std ? c.min_std : sd;
+    return (float)(1.0 / sd);
+}
+
+// everything after the chunks are joined, for one column: sx, qx over S samples merged into (count, mean, M2); the new vectors.
+// The rows were normalised by (shift, scale), or - raw (adc_td3_norm.h: the TD3 learners' record and ring hold the flat observation
+// itself) - the batch's moments are raw-space moments as they stand and there is no back-conversion
+ADC_HD void norm_finish(const NormConfig &c, bool raw, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &shift,
+                        float &scale)
+{
+    double mb, vb;
+    norm_batch_moments(sx, qx, S, mb, vb);
+    if (!raw) norm_to_raw(shift, scale, mb, vb);
+    const double M2b = vb * (double)S;
+    norm_merge(c, mb, M2b, S, count, mean, M2);
     shift = (float)mean;
-    scale = (float)(1.0 / sd);
+    scale = norm_scale(c, count, M2);
 }
 
 }  // namespace adc

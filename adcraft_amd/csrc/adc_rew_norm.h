@@ -1,7 +1,7 @@
 // adc_rew_norm.h - the law of the running reward normaliser: the variance of the DISCOUNTED RETURN, kept as (count, mean, M2) and
 // merged batch by batch from the rollout record's rewards (what Stable-Baselines3's VecNormalize(norm_reward=True) keeps around an
 // env: the reward is divided by the running standard deviation of the discounted return, never centred), and the float32
-// multiplier `scale` that the GAE kernels read.  Shared by the device kernels (parts/kernel_rew_norm.inc) and the host twins
+// multiplier `scale` that the GAE kernels read.  Shared by the device kernels (parts/kernel_norm.inc) and the host twins
 // adc_rew_norm_host / adc_pg_gae_norm_host (adc_shims.cpp); tests/rew_norm_ref.py restates these comments in numpy, bit for bit.
 //
 // Every float64 value below is the result of ONE correctly rounded IEEE operation (-ffp-contract=off; float64 division and
@@ -53,17 +53,11 @@ ADC_HD double rew_norm_chain_sq(double part, double g)
 // everything after the chunks are joined: sx, qx over S samples merged into (count, mean, M2); the new multiplier
 ADC_HD void rew_norm_finish(const NormConfig &c, double sx, double qx, int64_t S, int64_t &count, double &mean, double &M2, float &scale)
 {
-    const double fs = (double)S;
-    const double mb = sx / fs;
-    const double qm = qx / fs, mm = mb * mb;
-    double vb = qm - mm;
-    vb = vb > 0.0 ? vb : 0.0;
-    const double M2b = vb * fs;
+    double mb, vb;
+    norm_batch_moments(sx, qx, S, mb, vb);
+    const double M2b = vb * (double)S;
     norm_merge(c, mb, M2b, S, count, mean, M2);
-    const double var = M2 / (double)count;
-    double sd = __builtin_sqrt(var);
-    sd = sd < c.min_std ? c.min_std : sd;
-    scale = (float)(1.0 / sd);
+    scale = norm_scale(c, count, M2);
 }
 
 // GAE, one day of one env under a normaliser's multiplier and clip (pg_gae_day's product with 1.0f is exact)

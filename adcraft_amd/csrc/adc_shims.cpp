@@ -628,7 +628,49 @@ ADC_EXPORT int adc_es_update_host(const adc_es_config *cfg, uint64_t seed, int32
     return ADC_OK;
 }
 
-// ---- the running observation normaliser on the host (adc_norm.h: the code parts/kernel_obs_norm.inc runs) -----------------------
+namespace {
+// the observation moments of S rows of D columns merged into the running state, column by column (adc_norm.h); raw: the rows are raw
+// observations (adc_td3_norm.h)
+void obs_norm_columns(const adc::NormConfig &c, bool raw, int64_t S, int32_t D, const float *x_sd, int64_t *count, double *mean_d, double *m2_d,
+                      float *shift_d, float *scale_d)
+{
+    const int64_t count0 = *count;
+    int64_t cnt = count0;
+    for (int32_t j = 0; j < D; ++j) {
+        const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::norm_chain_sum(part, x_sd[(size_t)i * (size_t)D + (size_t)j]); });
+        const double qx = adc::pg_csum(S, [&](double part, int64_t i) {
+            const float x = x_sd[(size_t)i * (size_t)D + (size_t)j];
+            return adc::pg_chain_mac(part, x, x);
+        });
+        cnt = count0;
+        adc::norm_finish(c, raw, sx, qx, S, cnt, mean_d[j], m2_d[j], shift_d[j], scale_d[j]);
+    }
+    *count = cnt;
+}
+
+// the discounted returns of `days` days of num_envs envs, their moments merged into the running state, the envs' carry advanced
+// (adc_rew_norm.h)
+void rew_norm_days(const adc::NormConfig &c, int32_t days, int32_t num_envs, const float *gamma_n, const float *reward_tn, const uint8_t *terminated_tn,
+                   const uint8_t *truncated_tn, int64_t *count, double *mean, double *m2, float *scale, double *carry_n)
+{
+    const size_t N = (size_t)num_envs;
+    const int64_t S = (int64_t)days * num_envs;
+    std::vector<double> g((size_t)S);
+    for (size_t n = 0; n < N; ++n) {
+        double G = carry_n[n];
+        for (int t = 0; t < days; ++t) {
+            const size_t i = (size_t)t * N + n;
+            g[i] = adc::rew_norm_scan_day(G, gamma_n[n], reward_tn[i], terminated_tn[i] | truncated_tn[i]);
+        }
+        carry_n[n] = G;
+    }
+    const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sum(part, g[(size_t)i]); });
+    const double qx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sq(part, g[(size_t)i]); });
+    adc::rew_norm_finish(c, sx, qx, S, *count, *mean, *m2, *scale);
+}
+}  // namespace
+
+// ---- the running observation normaliser on the host (adc_norm.h: the code parts/kernel_norm.inc runs) ---------------------------
 ADC_EXPORT int adc_obs_norm_config_check(const adc_obs_norm_config *cfg, const char **message)
 {
     const char *msg = nullptr;
@@ -644,19 +686,7 @@ ADC_EXPORT int adc_obs_norm_host(const adc_obs_norm_config *cfg, int64_t S, int3
 {
     if (adc_obs_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
     if (S < 1 || D < 1 || !x_sd || !count || !mean_d || !m2_d || !shift_d || !scale_d || *count < 0) return ADC_EINVAL;
-    const adc::NormConfig c{cfg->min_std, cfg->count_cap};
-    const int64_t count0 = *count;
-    int64_t cnt = count0;
-    for (int32_t j = 0; j < D; ++j) {
-        const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::norm_chain_sum(part, x_sd[(size_t)i * (size_t)D + (size_t)j]); });
-        const double qx = adc::pg_csum(S, [&](double part, int64_t i) {
-            const float x = x_sd[(size_t)i * (size_t)D + (size_t)j];
-            return adc::pg_chain_mac(part, x, x);
-        });
-        cnt = count0;
-        adc::norm_finish(c, sx, qx, S, cnt, mean_d[j], m2_d[j], shift_d[j], scale_d[j]);
-    }
-    *count = cnt;
+    obs_norm_columns(adc::NormConfig{cfg->min_std, cfg->count_cap}, /* raw = */ false, S, D, x_sd, count, mean_d, m2_d, shift_d, scale_d);
     return ADC_OK;
 }
 
@@ -733,7 +763,7 @@ ADC_EXPORT int adc_pg_gae_host(const adc_pg_config *cfg, int32_t days, int32_t n
     return ADC_OK;
 }
 
-// ---- the running reward normaliser on the host (adc_rew_norm.h: the code parts/kernel_rew_norm.inc runs) ------------------------
+// ---- the running reward normaliser on the host (adc_rew_norm.h: the code parts/kernel_norm.inc runs) ----------------------------
 ADC_EXPORT int adc_rew_norm_config_check(const adc_rew_norm_config *cfg, const char **message)
 {
     const char *msg = nullptr;
@@ -752,20 +782,7 @@ ADC_EXPORT int adc_rew_norm_host(const adc_rew_norm_config *cfg, int32_t days, i
     if (adc_rew_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
     if (days < 1 || num_envs < 1 || !gamma_n || !reward_tn || !terminated_tn || !truncated_tn || !count || !mean || !m2 || !scale || !carry_n || *count < 0)
         return ADC_EINVAL;
-    const size_t N = (size_t)num_envs;
-    const int64_t S = (int64_t)days * num_envs;
-    std::vector<double> g((size_t)S);
-    for (size_t n = 0; n < N; ++n) {
-        double G = carry_n[n];
-        for (int t = 0; t < days; ++t) {
-            const size_t i = (size_t)t * N + n;
-            g[i] = adc::rew_norm_scan_day(G, gamma_n[n], reward_tn[i], terminated_tn[i] | truncated_tn[i]);
-        }
-        carry_n[n] = G;
-    }
-    const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sum(part, g[(size_t)i]); });
-    const double qx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sq(part, g[(size_t)i]); });
-    adc::rew_norm_finish(adc::NormConfig{cfg->min_std, cfg->count_cap}, sx, qx, S, *count, *mean, *m2, *scale);
+    rew_norm_days(adc::NormConfig{cfg->min_std, cfg->count_cap}, days, num_envs, gamma_n, reward_tn, terminated_tn, truncated_tn, count, mean, m2, scale, carry_n);
     return ADC_OK;
 }
 
@@ -801,7 +818,7 @@ ADC_EXPORT int adc_pg_gae_norm_host(const adc_pg_config *cfg, int32_t days, int3
     return ADC_OK;
 }
 
-// ---- the TD3 learners' running normalisers on the host (adc_td3_norm.h: the code parts/kernel_td3_norm.inc runs) ----------------
+// ---- the TD3 learners' running normalisers on the host (adc_td3_norm.h: the code parts/kernel_norm.inc runs) --------------------
 ADC_EXPORT int adc_td3_norm_config_check(const adc_td3_norm_config *cfg, const char **message)
 {
     const char *msg = nullptr;
@@ -821,19 +838,7 @@ ADC_EXPORT int adc_td3_norm_obs_host(const adc_td3_norm_config *cfg, int64_t S, 
 {
     if (adc_td3_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
     if (S < 1 || D < 1 || !x_sd || !count || !mean_d || !m2_d || !shift_d || !scale_d || *count < 0) return ADC_EINVAL;
-    const adc::NormConfig c{cfg->obs_min_std, cfg->obs_count_cap};
-    const int64_t count0 = *count;
-    int64_t cnt = count0;
-    for (int32_t j = 0; j < D; ++j) {
-        const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::norm_chain_sum(part, x_sd[(size_t)i * (size_t)D + (size_t)j]); });
-        const double qx = adc::pg_csum(S, [&](double part, int64_t i) {
-            const float x = x_sd[(size_t)i * (size_t)D + (size_t)j];
-            return adc::pg_chain_mac(part, x, x);
-        });
-        cnt = count0;
-        adc::norm_finish_raw(c, sx, qx, S, cnt, mean_d[j], m2_d[j], shift_d[j], scale_d[j]);
-    }
-    *count = cnt;
+    obs_norm_columns(adc::NormConfig{cfg->obs_min_std, cfg->obs_count_cap}, /* raw = */ true, S, D, x_sd, count, mean_d, m2_d, shift_d, scale_d);
     return ADC_OK;
 }
 
@@ -844,20 +849,7 @@ ADC_EXPORT int adc_td3_norm_rew_host(const adc_td3_norm_config *cfg, int32_t day
     if (adc_td3_norm_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
     if (days < 1 || num_envs < 1 || !gamma_n || !reward_tn || !terminated_tn || !truncated_tn || !count || !mean || !m2 || !scale || !carry_n || *count < 0)
         return ADC_EINVAL;
-    const size_t N = (size_t)num_envs;
-    const int64_t S = (int64_t)days * num_envs;
-    std::vector<double> g((size_t)S);
-    for (size_t n = 0; n < N; ++n) {
-        double G = carry_n[n];
-        for (int t = 0; t < days; ++t) {
-            const size_t i = (size_t)t * N + n;
-            g[i] = adc::rew_norm_scan_day(G, gamma_n[n], reward_tn[i], terminated_tn[i] | truncated_tn[i]);
-        }
-        carry_n[n] = G;
-    }
-    const double sx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sum(part, g[(size_t)i]); });
-    const double qx = adc::pg_csum(S, [&](double part, int64_t i) { return adc::rew_norm_chain_sq(part, g[(size_t)i]); });
-    adc::rew_norm_finish(adc::NormConfig{cfg->rew_min_std, cfg->rew_count_cap}, sx, qx, S, *count, *mean, *m2, *scale);
+    rew_norm_days(adc::NormConfig{cfg->rew_min_std, cfg->rew_count_cap}, days, num_envs, gamma_n, reward_tn, terminated_tn, truncated_tn, count, mean, m2, scale, carry_n);
     return ADC_OK;
 }
 

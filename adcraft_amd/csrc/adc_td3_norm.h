@@ -1,7 +1,7 @@
 // adc_td3_norm.h - the law of the running observation and reward normalisers of the off-policy (TD3) learners.  The replay ring
 // outlives the statistics, so nothing in it may depend on them: the rollout record and the ring hold RAW observations and raw
 // rewards, and a batch is normalised when it is sampled, with the vectors and the multiplier in force at that moment (what
-// Stable-Baselines3's VecNormalize does around a replay buffer).  Shared by the device kernels (parts/kernel_td3_norm.inc, the
+// Stable-Baselines3's VecNormalize does around a replay buffer).  Shared by the device kernels (parts/kernel_norm.inc, the
 // batch kernels of parts/kernel_td3.inc / kernel_td3_pop.inc) and the host twins adc_td3_norm_obs_host / adc_td3_norm_rew_host /
 // adc_td3_y_norm_host (adc_shims.cpp); tests/td3_norm_ref.py restates these comments in numpy, bit for bit.
 //
@@ -29,7 +29,7 @@
 //     merge    (mx, M2b, S) into (count, mean, M2), and the forgetting under obs_count_cap: adc_norm.h's norm_merge.
 //     vectors  var = M2 / f64(count);  sd = sqrt(var);  sd = sd < obs_min_std ? obs_min_std : sd;  shift = f32(mean);
 //              scale = f32(1.0 / sd), written in place where the policy kernel and the batch kernels read them.
-//              (adc_norm.h norm_finish_raw.)
+//              (adc_norm.h norm_finish, raw.)
 //
 //   reward moments: adc_rew_norm.h's law - the per-env float64 carry G (the env's, not a member's), the scan, the float64
 //              chunked moments, rew_norm_finish - with the TD3 learner's gamma as the discount (adc_td3_config.gamma; under a

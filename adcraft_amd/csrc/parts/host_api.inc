@@ -3,6 +3,23 @@
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
+// a set of running normalisers fed from the rollout record (parts/kernel_norm.inc, parts/norm_api.inc): an observation part, a
+// reward part, or both; a part that does not live has a null count
+struct NormSet {
+    bool live = false;
+    int M = 0;                          // normalisers: 1 (shared) or the learners' count (per_member)
+    int t0 = 0;                         // the record's days [0, t0) have been consumed
+    ObsNormView obs{};                  // count, mean, M2 and the vectors the policy kernel reads ([M][D] each)
+    const float *shared_shift = nullptr, *shared_scale = nullptr;   // per-member vectors are in force: the policy's own [D] vectors
+    double *obs_part = nullptr;         // [M][chunks][2][D] chunk partials
+    size_t obs_part_grown = 0;          // doubles of an obs_part grown on demand, which is then not one of `allocs`
+    RewNormView rew{};                  // count, mean, M2, the multiplier ([M] each); the envs' carry [N]
+    double *g = nullptr;                // [M][S] the discounted returns of an update, in the law's sample order (at most ro_T x N)
+    double *rew_part = nullptr;         // [M][chunks][2] chunk partials
+    int32_t *src = nullptr;             // [M] the copy's donors
+    std::vector<void *> allocs;
+};
+
 struct adc_engine {
     adc_config cfg;
     View v;
@@ -174,41 +191,15 @@ struct adc_engine {
     std::vector<PbtPair> pbt_pairs;             // [M] the host's copy of pbt_dpairs
     double *pbt_ret = nullptr, *pbt_fit = nullptr;      // [N] the envs' returns, [M] the members' fitness
     PbtPair *pbt_dpairs = nullptr;
-    // the running observation normaliser fed from the record (adc_engine_obs_norm_init; parts/kernel_obs_norm.inc,
-    // parts/obs_norm_api.inc; the law is adc_norm.h)
-    bool have_on = false;
+    // the running normalisers fed from the record (parts/kernel_norm.inc, parts/norm_api.inc).  on: the observation normaliser of
+    // the PPO / A2C learners (adc_engine_obs_norm_init; the law is adc_norm.h).  rn: their reward normaliser (adc_engine_rew_norm_init;
+    // adc_rew_norm.h), which lives with the trainer whose gamma it discounts by.  tn: the TD3 learners' normalisers
+    // (adc_engine_td3_norm_init; adc_td3_norm.h), which live with the TD3 trainer; while tn.obs lives the record's obs rows (and so
+    // the ring's) are raw observations
+    NormSet on, rn, tn;
     adc_obs_norm_config on_cfg{};
-    int on_M = 0;                       // normalisers: 1 (shared) or the learners' count (per_member)
-    int on_t0 = 0;                      // the record's days [0, on_t0) have been consumed
-    ObsNormView on_view{};              // count, mean, M2 and the vectors the policy kernel reads ([on_M][D] each)
-    const float *on_shared_shift = nullptr, *on_shared_scale = nullptr;     // the policy's own [D] vectors (mp.shift / mp.scale without per-member ones)
-    double *on_part = nullptr;          // [on_M][chunks][2][D] chunk partials, grown on demand
-    size_t on_part_doubles = 0;
-    int32_t *on_src = nullptr;          // [on_M] adc_engine_obs_norm_copy's donors
-    std::vector<void *> on_allocs;
-    // the running reward normaliser fed from the record (adc_engine_rew_norm_init; parts/kernel_rew_norm.inc,
-    // parts/rew_norm_api.inc; the law is adc_rew_norm.h).  It lives with the PPO / A2C trainer whose gamma it discounts by
-    bool have_rn = false;
     adc_rew_norm_config rn_cfg{};
-    int rn_M = 0;                       // normalisers: 1 (shared) or the learners' count (per_member)
-    int rn_t0 = 0;                      // the record's days [0, rn_t0) have been consumed
-    RewNormView rn_view{};              // count, mean, M2, the multiplier the GAE kernels read ([rn_M] each); the envs' carry [N]
-    double *rn_g = nullptr;             // [rn_M][S] the discounted returns of an update, in the law's sample order (at most ro_T x N)
-    double *rn_part = nullptr;          // [rn_M][chunks][2] chunk partials
-    int32_t *rn_src = nullptr;          // [rn_M] adc_engine_rew_norm_copy's donors
-    std::vector<void *> rn_allocs;
-    // the TD3 learners' running normalisers (adc_engine_td3_norm_init; parts/kernel_td3_norm.inc, parts/td3_norm_api.inc; the law is
-    // adc_td3_norm.h).  They live with the TD3 trainer; tn_raw: the record's obs rows (and so the ring's) are raw observations
-    bool have_tn = false, tn_raw = false;
     adc_td3_norm_config tn_cfg{};
-    int tn_M = 0;                       // normalisers: 1 (shared) or the learners' count (per_member)
-    int tn_t0 = 0;                      // the record's days [0, tn_t0) have been consumed
-    ObsNormView tn_on{};                // the observation part ([tn_M][D] each; count null: the part does not live)
-    RewNormView tn_rn{};                // the reward part ([tn_M] each, the envs' carry [N]; count null: the part does not live)
-    const float *tn_shared_shift = nullptr, *tn_shared_scale = nullptr;     // the policy's own [D] vectors (per-member vectors in force)
-    double *tn_on_part = nullptr, *tn_g = nullptr, *tn_rn_part = nullptr;   // chunk partials [tn_M][chunks][2][D]; returns [ro_T][N]; [tn_M][chunks][2]
-    int32_t *tn_src = nullptr;          // [tn_M] adc_engine_td3_norm_copy's donors
-    std::vector<void *> tn_allocs;
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -856,6 +847,8 @@ int fetch(adc_engine *e, adc_step_out *out, bool sync = true)
     return ADC_OK;
 }
 
+void norm_set_drop(adc_engine *e, NormSet &s);      // (defined below, next to mlp_free)
+
 }  // namespace
 
 ADC_EXPORT int adc_abi_version(void) { return ADC_ABI_VERSION; }
@@ -899,9 +892,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->ro_allocs) (void)hipFree(p);
     for (void *p : e->pg_allocs) (void)hipFree(p);
     for (void *p : e->td3_allocs) (void)hipFree(p);
-    for (void *p : e->on_allocs) (void)hipFree(p);
-    for (void *p : e->rn_allocs) (void)hipFree(p);
-    if (e->on_part) (void)hipFree(e->on_part);
+    for (NormSet *s : {&e->on, &e->rn, &e->tn}) norm_set_drop(e, *s);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1197,16 +1188,12 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
         hipLaunchKernelGGL(k_clear_obs, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->v, d_mask);
         err = hipGetLastError();
     }
-    // (a reset env's running discounted return ends with its episode; nothing is enqueued without a reward normaliser)
-    if (err == hipSuccess && e->have_rn) {
+    // (a reset env's running discounted return ends with its episode, the PPO / A2C learners' and the TD3 learners'; nothing is
+    //  enqueued without a reward normaliser)
+    for (const NormSet *s : {&e->rn, &e->tn}) {
+        if (err != hipSuccess || !s->rew.G) continue;
         hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
-                           e->rn_view.G);
-        err = hipGetLastError();
-    }
-    // (... and so does the TD3 learners' reward normaliser's carry)
-    if (err == hipSuccess && e->have_tn && e->tn_rn.G) {
-        hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
-                           e->tn_rn.G);
+                           s->rew.G);
         err = hipGetLastError();
     }
     hipError_t err2 = hipStreamSynchronize(e->stream);
@@ -2786,6 +2773,15 @@ inline void mlp_free(adc_engine *e, std::vector<void *> &owner)
     for (void *q : owner) (void)hipFree(q);
     owner.clear();
 }
+// a set of normalisers goes - with the policy, the learners, the trainer or the record it was set up for, or with the engine: the
+// policy kernel is back to the policy's own vectors, which hold what adc_engine_mlp_set_norm last wrote
+void norm_set_drop(adc_engine *e, NormSet &s)
+{
+    if (s.shared_shift) { e->mp.shift = s.shared_shift; e->mp.scale = s.shared_scale; e->mp.norm_stride = 0; }
+    mlp_free(e, s.allocs);
+    if (s.obs_part_grown) (void)hipFree(s.obs_part);
+    s = NormSet{};
+}
 // the agent's view of the env group that starts at env e0
 inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
 {
@@ -2827,7 +2823,7 @@ inline MlpRecordSlot rollout_slot(const adc_engine *e, bool record, int t, size_
 {
     MlpRecordSlot r{nullptr, nullptr, nullptr, nullptr, 0};
     if (!record) return r;
-    r.raw_obs = e->tn_raw ? 1 : 0;
+    r.raw_obs = e->tn.obs.count ? 1 : 0;
     const size_t n = (size_t)e->v.N, row = (size_t)t * n + e0;
     r.action = e->ro_action + row * (size_t)e->mp.A;
     r.logp = e->ro_logp + row;
@@ -2889,22 +2885,10 @@ void pbt_forget(adc_engine *e, int kind)
     e->pbt_s.clear(); e->pbt_host_fit.clear(); e->pbt_pairs.clear();
     e->pbt_ret = e->pbt_fit = nullptr; e->pbt_dpairs = nullptr;
 }
-// the reward normaliser goes with the policy-gradient trainer whose gamma it discounts by (the GAE kernels are back to
-// k_pg_gae / k_pg_pop_gae)
-void rew_norm_drop(adc_engine *e)
-{
-    if (!e->have_rn) return;
-    mlp_free(e, e->rn_allocs);
-    e->have_rn = false;
-    e->rn_M = e->rn_t0 = 0;
-    e->rn_view = RewNormView{};
-    e->rn_g = e->rn_part = nullptr;
-    e->rn_src = nullptr;
-}
 // the policy-gradient trainer goes with the policy and the record it was sized for
 void pg_drop(adc_engine *e)
 {
-    rew_norm_drop(e);
+    norm_set_drop(e, e->rn);            // (it discounts by this trainer's gamma; the GAE kernels are back to k_pg_gae / k_pg_pop_gae)
     pbt_forget(e, ADC_PBT_PG);
     mlp_free(e, e->pg_allocs);
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
@@ -2912,25 +2896,10 @@ void pg_drop(adc_engine *e)
     e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();
     e->pgp_dmem = nullptr;
 }
-// the TD3 learners' normalisers go with their trainer: the record is back to network inputs, the policy kernel to the policy's own
-// vectors, which hold what adc_engine_mlp_set_norm last wrote
-void td3_norm_drop(adc_engine *e)
-{
-    if (!e->have_tn) return;
-    if (e->tn_shared_shift) { e->mp.shift = e->tn_shared_shift; e->mp.scale = e->tn_shared_scale; e->mp.norm_stride = 0; }
-    mlp_free(e, e->tn_allocs);
-    e->have_tn = e->tn_raw = false;
-    e->tn_M = e->tn_t0 = 0;
-    e->tn_on = ObsNormView{};
-    e->tn_rn = RewNormView{};
-    e->tn_shared_shift = e->tn_shared_scale = nullptr;
-    e->tn_on_part = e->tn_g = e->tn_rn_part = nullptr;
-    e->tn_src = nullptr;
-}
 // ... and so does the off-policy trainer (its ring holds rows of that policy's input and action widths)
 void td3_drop(adc_engine *e)
 {
-    td3_norm_drop(e);
+    norm_set_drop(e, e->tn);            // (the record is back to network inputs)
     pbt_forget(e, ADC_PBT_TD3);
     mlp_free(e, e->td3_allocs);
     e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
@@ -2940,26 +2909,11 @@ void td3_drop(adc_engine *e)
     e->tp_cfg.clear(); e->tp_mem.clear(); e->tp_steps.clear(); e->tp_host_sums.clear(); e->tp_critic_set.clear();
     e->tp_dmem = nullptr; e->tp_dsteps = nullptr;
 }
-// the observation normaliser goes with the policy, the learners and the record it was set up for; the policy kernel is back to
-// the policy's own vectors, which hold what adc_engine_mlp_set_norm last wrote
-void obs_norm_drop(adc_engine *e)
-{
-    if (!e->have_on) return;
-    if (e->on_cfg.per_member) { e->mp.shift = e->on_shared_shift; e->mp.scale = e->on_shared_scale; e->mp.norm_stride = 0; }
-    mlp_free(e, e->on_allocs);
-    if (e->on_part) { (void)hipFree(e->on_part); e->on_part = nullptr; }
-    e->on_part_doubles = 0;
-    e->have_on = false;
-    e->on_M = e->on_t0 = 0;
-    e->on_view = ObsNormView{};
-    e->on_shared_shift = e->on_shared_scale = nullptr;
-    e->on_src = nullptr;
-}
 // learners and the population trainer over them go with the policy they belong to (the engine is back to the centre policy)
 void learners_drop(adc_engine *e)
 {
-    obs_norm_drop(e);
-    rew_norm_drop(e);
+    norm_set_drop(e, e->on);
+    norm_set_drop(e, e->rn);
     // (a solo TD3 trainer survives learners and a population, refused while they are active; so do its normalisers, or its raw ring
     //  would be sampled without them afterwards.  A TD3 population's go with it, below)
     if (e->have_pg_pop) pg_drop(e);
@@ -3124,27 +3078,16 @@ ADC_EXPORT int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, cons
     if (!e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
     if (!shift_d || !scale_d) return fail(ADC_EINVAL, "shift or scale is NULL");
     ENGINE_GUARD(e);
-    if (e->have_on && e->on_cfg.per_member) {
+    for (const NormSet *s : {&e->on, &e->tn}) {
+        if (!s->shared_shift) continue;
         // per-member vectors are in force: every member's row, and the policy's own vectors (the running moments are not touched)
         const size_t D = (size_t)e->mp.D;
-        for (int m = 0; m < e->on_M; ++m) {
-            HIP_TRY(hipMemcpyAsync(e->on_view.shift + (size_t)m * D, shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(e->on_view.scale + (size_t)m * D, scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        for (int m = 0; m < s->M; ++m) {
+            HIP_TRY(hipMemcpyAsync(s->obs.shift + (size_t)m * D, shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(s->obs.scale + (size_t)m * D, scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
         }
-        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->on_shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->on_shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return ADC_OK;
-    }
-    if (e->have_tn && e->tn_shared_shift) {
-        // the TD3 learners' per-member vectors are in force: every member's row, and the policy's own vectors
-        const size_t D = (size_t)e->mp.D;
-        for (int m = 0; m < e->tn_M; ++m) {
-            HIP_TRY(hipMemcpyAsync(e->tn_on.shift + (size_t)m * D, shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(e->tn_on.scale + (size_t)m * D, scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        }
-        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->tn_shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->tn_shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(const_cast<float *>(s->shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(const_cast<float *>(s->shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         return ADC_OK;
     }
@@ -3665,7 +3608,7 @@ ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t
     ENGINE_GUARD(e);
     pg_drop(e);                         // (its advantages and scratch were sized for the old record)
     td3_drop(e);
-    obs_norm_drop(e);
+    norm_set_drop(e, e->on);
     mlp_free(e, e->ro_allocs);
     e->ro_T = e->ro_t = 0;
     e->ro_obs = nullptr;
@@ -3691,9 +3634,7 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     ENGINE_GUARD(e);
     if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
     e->ro_t = 0;
-    e->on_t0 = 0;
-    e->rn_t0 = 0;
-    e->tn_t0 = 0;
+    for (NormSet *s : {&e->on, &e->rn, &e->tn}) s->t0 = 0;
     e->ro_deterministic = false;
     e->pg_adv_ready = false;
     e->td3_stored_t = 0;

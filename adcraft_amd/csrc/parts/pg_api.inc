@@ -56,9 +56,9 @@ int pg_advantages_run(adc_engine *e)
         mlp_launch_kernel(e->v, e->mp, e->stream, 1, nullptr, 0.0f, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, e->mlp_boot);
     else HIP_TRY(hipMemsetAsync(e->mlp_boot, 0, (size_t)N * 4, e->stream));
     const adc_pg_config &c = e->pg_cfg;
-    if (e->have_rn)       // (the reward times the running normaliser's multiplier, clipped: adc_rew_norm.h)
+    if (e->rn.live)       // (the reward times the running normaliser's multiplier, clipped: adc_rew_norm.h)
         hipLaunchKernelGGL(k_rew_norm_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, N, T, e->ro_reward, e->ro_term, e->ro_trunc, e->ro_value,
-                           e->mlp_boot, c.gamma, c.gamma * c.lambda, c.reward_scale, e->rn_view.scale, e->rn_cfg.clip, e->pg_adv, e->pg_ret);
+                           e->mlp_boot, c.gamma, c.gamma * c.lambda, c.reward_scale, e->rn.rew.scale, e->rn_cfg.clip, e->pg_adv, e->pg_ret);
     else
         hipLaunchKernelGGL(k_pg_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, N, T, e->ro_reward, e->ro_term, e->ro_trunc, e->ro_value,
                            e->mlp_boot, c.gamma, c.gamma * c.lambda, c.reward_scale, e->pg_adv, e->pg_ret);
@@ -375,9 +375,9 @@ int pgp_advantages_run(adc_engine *e)
     if (e->mp.val.layers > 0)
         mlp_launch_kernel(e->v, e->mp, e->stream, 1, nullptr, 0.0f, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, e->mlp_boot);
     else HIP_TRY(hipMemsetAsync(e->mlp_boot, 0, (size_t)N * 4, e->stream));
-    if (e->have_rn)       // (the reward times the env's normaliser's multiplier, clipped: adc_rew_norm.h)
+    if (e->rn.live)       // (the reward times the env's normaliser's multiplier, clipped: adc_rew_norm.h)
         hipLaunchKernelGGL(k_rew_norm_pop_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, N, T, n, e->pgp_dmem, e->ro_reward, e->ro_term,
-                           e->ro_trunc, e->ro_value, e->mlp_boot, e->rn_view.scale, N / e->rn_M, e->rn_cfg.clip, e->pg_adv, e->pg_ret);
+                           e->ro_trunc, e->ro_value, e->mlp_boot, e->rn.rew.scale, N / e->rn.M, e->rn_cfg.clip, e->pg_adv, e->pg_ret);
     else
         hipLaunchKernelGGL(k_pg_pop_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, N, T, n, e->pgp_dmem, e->ro_reward, e->ro_term, e->ro_trunc,
                            e->ro_value, e->mlp_boot, e->pg_adv, e->pg_ret);

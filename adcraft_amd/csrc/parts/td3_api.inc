@@ -72,9 +72,9 @@ adc::EsStep td3_step_of(const adc_td3_config &c, float lr, int64_t steps_taken)
 // the running normalisers' side of a batch kernel's view (all null without adc_engine_td3_norm_init: the kernels are what they were)
 void td3_norm_fill(const adc_engine *e, Td3View &p)
 {
-    if (!e->have_tn) return;
-    if (e->tn_raw) { p.n_shift = e->mp.shift; p.n_scale = e->mp.scale; p.n_stride = e->mp.norm_stride; }
-    if (e->tn_rn.count) { p.r_scale = e->tn_rn.scale; p.r_stride = e->tn_cfg.per_member ? 1 : 0; p.r_clip = e->tn_cfg.rew_clip; }
+    if (!e->tn.live) return;
+    if (e->tn.obs.count) { p.n_shift = e->mp.shift; p.n_scale = e->mp.scale; p.n_stride = e->mp.norm_stride; }
+    if (e->tn.rew.count) { p.r_scale = e->tn.rew.scale; p.r_stride = e->tn_cfg.per_member ? 1 : 0; p.r_clip = e->tn_cfg.rew_clip; }
 }
 Td3View td3_view(const adc_engine *e)
 {
@@ -171,9 +171,9 @@ ADC_EXPORT int adc_engine_td3_init(adc_engine *e, const adc_td3_config *cfg)
     const char *why = nullptr;
     if (adc_td3_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     if (int rc = td3_state_check(e)) return rc;
-    if (e->have_rn) return fail(ADC_ESTATE, "a running reward normaliser is alive on this engine: it belongs to the policy-gradient trainer");
+    if (e->rn.live) return fail(ADC_ESTATE, "a running reward normaliser is alive on this engine: it belongs to the policy-gradient trainer");
     if (e->have_pg) return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
-    if (e->have_on)
+    if (e->on.live)
         return fail(ADC_ESTATE, "a running observation normaliser is alive on this engine: the replay ring would hold inputs normalised by older vectors");
     const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, *cfg, 0);
     if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for off-policy training (LDS)");
@@ -293,8 +293,8 @@ ADC_EXPORT int adc_engine_td3_store(adc_engine *e, int64_t *stored)
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;
     // (raw rows under a running observation normaliser: the last day's x' is the raw row an act would read now)
-    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->tn_raw ? nullptr : e->mp.shift,
-                       e->tn_raw ? nullptr : e->mp.scale, e->mp.D, e->mp.A, e->ro_obs,
+    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
+                       e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A, e->ro_obs,
                        e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
                        (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());

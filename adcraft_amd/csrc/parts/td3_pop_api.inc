@@ -182,10 +182,10 @@ ADC_EXPORT int adc_engine_td3_pop_init(adc_engine *e, const adc_td3_config *cfgs
     const char *why = nullptr;
     if (adc_td3_pop_config_check(cfgs, count, N, M, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     if (e->have_td3) return fail(ADC_ESTATE, "a single-learner off-policy (TD3) trainer is alive on this engine (adc_engine_td3_init)");
-    if (e->have_rn) return fail(ADC_ESTATE, "a running reward normaliser is alive on this engine: it belongs to the policy-gradient trainer");
+    if (e->rn.live) return fail(ADC_ESTATE, "a running reward normaliser is alive on this engine: it belongs to the policy-gradient trainer");
     if (e->have_pg || e->have_pg_pop)
         return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
-    if (e->have_on)
+    if (e->on.live)
         return fail(ADC_ESTATE, "a running observation normaliser is alive on this engine: the replay ring would hold inputs normalised by older vectors");
     const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, cfgs[0], 0);
     if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for off-policy training (LDS)");
@@ -335,8 +335,8 @@ ADC_EXPORT int adc_engine_td3_pop_store(adc_engine *e, int64_t *stored_per_membe
                                 "one the envs hold (adc_engine_rollout_reset, collect again)");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;
-    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn_raw ? nullptr : e->mp.shift,
-                       e->tn_raw ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
+    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
+                       e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
                        e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
                        (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());

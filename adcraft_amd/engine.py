@@ -1247,7 +1247,7 @@ class StepEngine:
             raise ValueError("pbt_state: one smoothed fitness per member")
         check(self._lib.adc_engine_pbt_state_set(self._h, int(state["round"]), s.ctypes.data))
 
-    # ---- the running observation normaliser fed from the record (parts/kernel_obs_norm.inc; the law is csrc/adc_norm.h) ----------
+    # ---- the running observation normaliser fed from the record (parts/kernel_norm.inc; the law is csrc/adc_norm.h) --------------
     @classmethod
     def obs_norm_config(cls, per_member=False, min_std=1e-2, count_cap=0):
         """an adc_obs_norm_config: min_std the floor of the standard deviation; count_cap > 0 bounds the running count (the
@@ -1295,7 +1295,7 @@ class StepEngine:
             raise ValueError("obs_norm_copy: one source per member")
         check(self._lib.adc_engine_obs_norm_copy(self._h, src.ctypes.data))
 
-    # ---- the running reward normaliser fed from the record (parts/kernel_rew_norm.inc; the law is csrc/adc_rew_norm.h) ----------
+    # ---- the running reward normaliser fed from the record (parts/kernel_norm.inc; the law is csrc/adc_rew_norm.h) --------------
     @classmethod
     def rew_norm_config(cls, per_member=False, min_std=1e-2, clip=10.0, count_cap=0):
         """an adc_rew_norm_config: min_std the floor of the discounted return's standard deviation; clip > 0 bounds the
@@ -1351,7 +1351,7 @@ class StepEngine:
             raise ValueError("rew_norm_copy: one source per member")
         check(self._lib.adc_engine_rew_norm_copy(self._h, src.ctypes.data))
 
-    # ---- the TD3 learners' running normalisers (parts/kernel_td3_norm.inc; the law is csrc/adc_td3_norm.h) ------------------------
+    # ---- the TD3 learners' running normalisers (parts/kernel_norm.inc; the law is csrc/adc_td3_norm.h) ----------------------------
     @classmethod
     def td3_norm_config(cls, observations=False, rewards=False, per_member=False, obs_min_std=1e-2, obs_count_cap=0, rew_min_std=1e-2, rew_count_cap=0,
                         rew_clip=10.0):

@@ -1,4 +1,4 @@
-"""GPU tests of the TD3 learners' running observation and reward normalisers (parts/kernel_td3_norm.inc, parts/td3_norm_api.inc,
+"""GPU tests of the TD3 learners' running observation and reward normalisers (parts/kernel_norm.inc, parts/norm_api.inc,
 the sample-time normalisation of parts/kernel_td3.inc / kernel_td3_pop.inc) against the numpy restatement tests/td3_norm_ref.py
 and the host twins, bit for bit: there is no tolerance anywhere.  None of these entry points exists before this feature: every
 test here fails on the parent commit.
@@ -216,6 +216,66 @@ def test_moments_equal_the_host_twin_and_the_restatement(amd, cap):
     assert got[1]["scale"] != F(1.0) and not _same(got[0]["shift"], pol.shift) and np.any(got[1]["returns"] != 0)
     with pytest.raises(_ffi.EngineStateError, match="no day has been recorded"):
         e.td3_norm_update()
+    e.close()
+
+
+# ---- 2b. raw observation moments across tile and chunk boundaries ------------------------------------------------------------------
+@pytest.mark.parametrize("members", [0, 2])
+def test_raw_moments_across_column_tiles_and_chunks(amd, members):
+    """8 envs a normaliser x 60 keywords x 130 days: D = 302 is two 256-column tiles, the second partial; S = 1040 is two
+    1024-sample chunks, the second partial.  One collect, one update: the raw finish and the scan equal the restatement and the
+    host twins.  members = 2: per-member normalisers of two learners over 16 envs, the same S for each"""
+    from adcraft_amd import _ffi
+    n, kw, days, M = 8, 60, 130, max(members, 1)
+    d = 5 * kw + 2
+    rng = np.random.default_rng(25)
+    pols = [_policy(rng, kw, sigma=(0.2, 0.05)[m]) for m in range(M)]
+    crits = [T3.random_critics_for_tests(rng, kw, WIDTHS) for _ in range(M)]
+    gammas = [F(0.97), F(0.9)][:M]
+    opts = [_options(capacity=2048, gamma=float(g)) for g in gammas]
+    if members:
+        e = _population(amd, pols, crits, opts, norm=dict(BOTH, per_member=True), planes=_planes(M * n, kw), horizon=days)
+    else:
+        e = _solo(amd, pols[0], crits[0], opts[0], planes=_planes(n, kw), horizon=days, norm=BOTH)
+    assert _collect(e, days, pop=bool(members)) == days * n
+    assert e.td3_norm_update() == days * n
+    rec = e.rollout_fetch()
+    assert (rec["terminated"] | rec["truncated"]).any() and (rec["obs"][0] == 0).all() and np.abs(rec["obs"]).max() > 10.0
+    for m in range(M):
+        rows = NR.member_rows(rec["obs"], m, n)
+        assert rows.shape == (1040, 302)
+        rew = tuple(rec[k][:, m * n:(m + 1) * n] for k in ("reward", "terminated", "truncated"))
+        o, r = TN.obs_fresh(d, pols[m].shift, pols[m].scale), TN.rew_fresh(n)
+        got = _norm_state(e, m, n)
+        _assert_norm(got, (TN.obs_update(o, rows), TN.rew_update(r, *rew, gammas[m])), ("restatement", m))
+        _assert_norm(got, (TN.twin_obs(_ffi.lib(), o, rows), TN.twin_rew(_ffi.lib(), r, *rew, gammas[m])), ("twin", m))
+        assert got[0]["count"] == days * n and not _same(got[0]["shift"], pols[m].shift) and got[1]["scale"] != F(1.0)
+    e.close()
+
+
+# ---- 2c. the batched copy with one part absent -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("part", ["rewards", "observations"])
+def test_copy_with_one_part_absent(amd, part):
+    """3 members x 2 envs with the rewards' part alone, then with the observations' alone: after an update (the members differ)
+    td3_norm_copy([2, -1, 2]) makes member 0's state member 2's, bit for bit, and leaves members 1 and 2 and the envs' carry alone"""
+    M, n = 3, 2
+    pols, crits = _members(27, M)
+    opts = [_options(gamma=float(F(0.9 + 0.03 * m))) for m in range(M)]
+    e = _population(amd, pols, crits, opts, norm={part: True, "per_member": True}, planes=_planes(M * n, K))
+    assert _collect(e, pop=True) == T * n
+    assert e.td3_norm_update() == T * n
+    before = [_norm_state(e, m, n) for m in range(M)]
+    carry = e.td3_norm_returns() if part == "rewards" else None
+    which = 1 if part == "rewards" else 0
+    same = (lambda a, b: TN.rew_same(a, b, returns=False)) if part == "rewards" else TN.obs_same
+    assert all(st[1 - which] is None for st in before) and not same(before[0][which], before[2][which])
+    e.td3_norm_copy([2, -1, 2])
+    after = [_norm_state(e, m, n) for m in range(M)]
+    assert same(after[0][which], before[2][which]), "member 0 is its donor"
+    for m in (1, 2):
+        _assert_norm(after[m], before[m], ("untouched", m))
+    if part == "rewards":
+        assert np.any(carry != 0) and _same(e.td3_norm_returns(), carry), "the carry is the envs' and stays"
     e.close()
 
 

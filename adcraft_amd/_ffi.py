@@ -82,6 +82,15 @@ class PGStats(C.Structure):
                 ("explained_variance", C.c_double)]
 
 
+class PGKLConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kl_coef", C.c_float), ("kl_target", C.c_float), ("adaptive", C.c_int32),
+                ("factor_up", C.c_float), ("factor_down", C.c_float), ("vf_clip", C.c_float)]
+
+
+class PGKLStats(C.Structure):
+    _fields_ = [("kl", C.c_double), ("vf_clip_fraction", C.c_double), ("kl_coef", C.c_float), ("kl_coef_next", C.c_float)]
+
+
 class TD3Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_float), ("tau", C.c_float), ("policy_delay", C.c_int32),
                 ("target_noise", C.c_float), ("target_noise_clip", C.c_float), ("action_lo", C.c_float), ("action_hi", C.c_float),
@@ -307,6 +316,15 @@ def lib():
         "adc_pg_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(PGConfig), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                               C.POINTER(PGStats)], C.c_int),
         "adc_pg_step_host": ([C.POINTER(PGConfig), i64, i64, vp, vp, vp, vp], C.c_int),
+        "adc_pg_kl_config_check": ([C.POINTER(PGKLConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_pg_kl_init": ([vp, C.POINTER(PGKLConfig), i32], C.c_int),
+        "adc_engine_pg_kl_stats": ([vp, C.POINTER(PGKLStats)], C.c_int),
+        "adc_engine_pg_kl_coef_get": ([vp, i32, C.POINTER(f32)], C.c_int),
+        "adc_engine_pg_kl_coef_set": ([vp, i32, f32], C.c_int),
+        "adc_engine_pg_kl_old_dist_fetch": ([vp, vp, vp], C.c_int),
+        "adc_pg_kl_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(PGConfig), vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(PGKLConfig), f32, vp, vp, i32,
+                                 vp, vp, vp, C.POINTER(PGStats), C.POINTER(PGKLStats)], C.c_int),
+        "adc_pg_kl_adapt_host": ([C.POINTER(PGKLConfig), f32, f64, C.POINTER(f32)], C.c_int),
         "adc_engine_td3_init": ([vp, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_td3_set_action_norm": ([vp, vp, vp], C.c_int),

@@ -55,6 +55,44 @@ def a2c(**overrides):
     return cfg
 
 
+def rllib_ppo(**overrides):
+    """The PPO configuration of the paper's experiments (RLlib's PPO as the reference's sem_ppo_config sets it), as far as this
+    trainer expresses it: gamma 0.995, lambda 0.95, lr 1e-4, clip range 0.5, 20 epochs, and RLlib's loss terms - the adaptive KL
+    penalty (kl_coeff 1.0, kl_target 0.01) and the value-loss clip (vf_clip_param 10.0) - through `kl_penalty`.  vf_coef is 2.0
+    because our value loss carries a factor 0.5 that RLlib's does not (csrc/adc_pg_kl.h): RLlib's vf_loss_coeff 1.0.
+    What it does NOT reproduce: RLlib's minibatches are 64 samples drawn from a shuffled train batch, ours are whole
+    trajectories of env ranges in ascending order (`minibatches` stays this trainer's own, 4); RLlib does not normalise
+    advantages per update the way normalize_advantages does, and clips gradients only when asked to; per-minibatch details of
+    its learner (its KL is the mean over the minibatches of an epoch it sampled, ours over the last epoch's env ranges) differ
+    accordingly."""
+    cfg = ppo(gamma=0.995, lam=0.95, lr=1e-4, eps_clip=0.5, epochs=20, vf_coef=2.0,
+              kl_penalty=dict(kl_coef=1.0, kl_target=0.01, adaptive=True, vf_clip=10.0))
+    cfg.update(overrides)
+    return cfg
+
+
+_KL_KEYS = {"kl_coef", "kl_target", "adaptive", "vf_clip", "factor_up", "factor_down"}
+
+
+def _kl_options(kl_penalty, members=None):
+    """kl_penalty checked: None, a dict of StepEngine.pg_kl_config's options, or (members given) a list of one dict per member"""
+    if kl_penalty is None:
+        return None
+    many = isinstance(kl_penalty, (list, tuple))
+    if many and members is None:
+        raise TypeError("kl_penalty: a dict of kl_coef, kl_target, adaptive, vf_clip (a list only for a population)")
+    items = list(kl_penalty) if many else [kl_penalty]
+    if many and len(items) != members:
+        raise ValueError(f"kl_penalty: {len(items)} dicts for {members} members: one dict (shared) or one per member")
+    for o in items:
+        if not isinstance(o, dict):
+            raise TypeError("kl_penalty: a dict of kl_coef, kl_target, adaptive, vf_clip")
+        unknown = set(o) - _KL_KEYS
+        if unknown:
+            raise ValueError(f"kl_penalty: unknown option(s) {sorted(unknown)}: {', '.join(sorted(_KL_KEYS))}")
+    return [dict(o) for o in items] if many else dict(items[0])
+
+
 def _rew_norm_options(normalize_rewards, rew_norm):
     if rew_norm is not None and not isinstance(rew_norm, dict):
         raise TypeError("rew_norm: a dict of min_std, clip, count_cap")
@@ -87,12 +125,20 @@ class PGTrainer:
     are where the filter starts), updated after every PPO / A2C update; obs_norm: dict(min_std=..., count_cap=...).
     normalize_rewards: the reward in GAE is divided by the running standard deviation of the discounted return, kept on the
     device (StepEngine.rew_norm_*) and updated from every rollout BEFORE its PPO / A2C update; rew_norm: dict(min_std=...,
-    clip=..., count_cap=...)."""
+    clip=..., count_cap=...).  kl_penalty: dict(kl_coef=..., kl_target=..., adaptive=..., vf_clip=...) adds RLlib's analytic KL
+    penalty with its adaptive coefficient and the value-loss clip to the loss (StepEngine.pg_kl_*; csrc/adc_pg_kl.h);
+    iteration() then also returns `kl`, `kl_coef` (the one the update used) and `vf_clip_fraction`, and state() carries the
+    coefficient."""
 
     def __init__(self, engine, policy, horizon, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
-                 rew_norm=None, **config):
+                 rew_norm=None, kl_penalty=None, **config):
         _rew_norm_options(normalize_rewards, rew_norm)
         cfg = ppo(**config)
+        if kl_penalty is None:                  # (a preset carries it among its keys: rllib_ppo())
+            kl_penalty = cfg.pop("kl_penalty", None)
+        else:
+            cfg.pop("kl_penalty", None)
+        self.kl_penalty = _kl_options(kl_penalty)
         self.epochs, minibatches = int(cfg.pop("epochs")), int(cfg.pop("minibatches"))
         if minibatches < 1 or engine.num_envs % minibatches:
             raise ValueError("minibatches must divide the engine's envs")
@@ -107,6 +153,8 @@ class PGTrainer:
         self.normalize_rewards = bool(normalize_rewards)
         if self.normalize_rewards:
             engine.rew_norm_init(**dict(rew_norm or {}))
+        if self.kl_penalty is not None:
+            engine.pg_kl_init(**self.kl_penalty)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -120,6 +168,9 @@ class PGTrainer:
         if self.normalize_rewards:          # (before the update: this record's rewards are scaled by statistics that include them)
             e.rew_norm_update()
         stats = e.pg_update(self.epochs)
+        if self.kl_penalty is not None:
+            kl = e.pg_kl_stats()
+            stats.update(kl=kl["kl"], kl_coef=kl["kl_coef"], vf_clip_fraction=kl["vf_clip_fraction"])
         if self.normalize_observations:     # (after the update: its bootstrap value is evaluated under the vectors of the record)
             e.obs_norm_update()
         self.history.append(stats)
@@ -144,7 +195,15 @@ class PGTrainer:
         return _rew_norm_state(self.engine, 0, state)
 
     def state(self, state=None):
-        return self.engine.pg_state(state)
+        """the trainer's state (StepEngine.pg_state's dict; with kl_penalty also `kl_coef`); set: the run continues bit for bit"""
+        if state is None:
+            st = self.engine.pg_state()
+            if self.kl_penalty is not None:
+                st["kl_coef"] = self.engine.pg_kl_coef(0)
+            return st
+        self.engine.pg_state(state)
+        if self.kl_penalty is not None and "kl_coef" in state:
+            self.engine.pg_kl_coef(0, state["kl_coef"])
 
 
 class PGPopulationTrainer:
@@ -158,10 +217,11 @@ class PGPopulationTrainer:
     normalize_observations: one running observation filter PER MEMBER, fed from the member's own envs (the members' policies
     may then carry different shift / scale: each member starts from its own); obs_norm: dict(min_std=..., count_cap=...).
     normalize_rewards: one running reward normaliser PER MEMBER (PGTrainer's), fed from the member's own envs under the
-    member's own gamma; rew_norm: dict(min_std=..., clip=..., count_cap=...)."""
+    member's own gamma; rew_norm: dict(min_std=..., clip=..., count_cap=...).  kl_penalty: PGTrainer's dict shared by all
+    members, or a list of one per member; every member has its own coefficient that adapts on its own either way."""
 
     def __init__(self, engine, policies, horizon, configs, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
-                 rew_norm=None):
+                 rew_norm=None, kl_penalty=None):
         _rew_norm_options(normalize_rewards, rew_norm)
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         configs = [configs] if isinstance(configs, dict) else list(configs)
@@ -179,6 +239,12 @@ class PGPopulationTrainer:
             if p.shift is not None and not (np.array_equal(p.shift, policies[0].shift) and np.array_equal(p.scale, policies[0].scale)):
                 raise ValueError("PGPopulationTrainer: the normalisation vectors are shared by all members: the policies' must be equal")
         cfgs = [ppo(**c) for c in configs]
+        preset = [c.pop("kl_penalty", None) for c in cfgs]             # (a preset carries it among its keys: rllib_ppo())
+        if kl_penalty is None and any(p is not None for p in preset):
+            if any(p is None for p in preset):
+                raise ValueError("PGPopulationTrainer: kl_penalty in some members' configurations and not in others")
+            kl_penalty = preset if len(preset) == members else preset[0]
+        self.kl_penalty = _kl_options(kl_penalty, members)
         self.epochs, minibatches = int(cfgs[0].pop("epochs")), int(cfgs[0].pop("minibatches"))
         for c in cfgs[1:]:
             if (int(c.pop("epochs")), int(c.pop("minibatches"))) != (self.epochs, minibatches):
@@ -208,6 +274,10 @@ class PGPopulationTrainer:
         self.normalize_rewards = bool(normalize_rewards)
         if self.normalize_rewards:
             engine.rew_norm_init(per_member=True, **dict(rew_norm or {}))
+        if isinstance(self.kl_penalty, list):
+            engine.pg_kl_init(per_member=self.kl_penalty)
+        elif self.kl_penalty is not None:
+            engine.pg_kl_init(**self.kl_penalty)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -220,6 +290,9 @@ class PGPopulationTrainer:
         if self.normalize_rewards:
             e.rew_norm_update()
         stats = e.pg_pop_update(self.epochs)
+        if self.kl_penalty is not None:
+            for st, kl in zip(stats, e.pg_kl_stats()):
+                st.update(kl=kl["kl"], kl_coef=kl["kl_coef"], vf_clip_fraction=kl["vf_clip_fraction"])
         if self.normalize_observations:
             e.obs_norm_update()
         self.history.append(stats)
@@ -248,7 +321,15 @@ class PGPopulationTrainer:
         return r.reshape(self.members, -1).mean(axis=1)
 
     def state(self, member, state=None):
-        return self.engine.pg_pop_state(member, state)
+        """one member's state (StepEngine.pg_pop_state's dict; with kl_penalty also `kl_coef`)"""
+        if state is None:
+            st = self.engine.pg_pop_state(member)
+            if self.kl_penalty is not None:
+                st["kl_coef"] = self.engine.pg_kl_coef(member)
+            return st
+        self.engine.pg_pop_state(member, state)
+        if self.kl_penalty is not None and "kl_coef" in state:
+            self.engine.pg_kl_coef(member, state["kl_coef"])
 
 
-__all__ = ["PGPopulationTrainer", "PGTrainer", "ppo", "a2c", "flat_params", "policy_from_flat"]
+__all__ = ["PGPopulationTrainer", "PGTrainer", "ppo", "a2c", "rllib_ppo", "flat_params", "policy_from_flat"]

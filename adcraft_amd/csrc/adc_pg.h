@@ -280,8 +280,13 @@ inline PgStatsOut pg_stats_finish(const double *sums, int64_t S)
 // ---- the host's side of a sample: forward, head, loss, backward (the kernel runs the same steps, lanes over neurons) -------------
 // theta: flat order.  acts / deltas: pg_acts_floats / pg_deltas_floats values, networks and layers in order (the free log_std's
 // A "deltas" last); pieces: kPgPieces floats
-inline void pg_sample_host(const PgShape &sh, const PgLoss &loss, const float *theta, const float *x, const float *action, float logp_old,
-                           float adv, float ret, float value_old, float *acts, float *deltas, float *pieces)
+// `addon` is PgNoAddon, or adc_pg_kl.h's PgKlSampleHost: the KL penalty and the value-loss clip of one sample
+struct PgNoAddon {
+    static constexpr bool on = false;
+};
+template <class Addon>
+inline void pg_sample_host_with(const PgShape &sh, const PgLoss &loss, const float *theta, const float *x, const float *action, float logp_old,
+                                float adv, float ret, float value_old, float *acts, float *deltas, float *pieces, const Addon &addon)
 {
     const int A = sh.A;
     auto sum8 = [](int n, auto term) {
@@ -346,7 +351,10 @@ inline void pg_sample_host(const PgShape &sh, const PgLoss &loss, const float *t
     int clipped;
     const float g = pg_surrogate(ratio, adv, loss.eps_clip, pol_loss, clipped);
     const float V = sh.layers[1] ? outs[1][0] : 0.0f;
-    const float dV = pg_dvalue(V, ret, loss.vf_coef, val_loss);
+    float dV;
+    if constexpr (Addon::on) dV = addon.value(V, ret, loss.vf_coef, val_loss);
+    else dV = pg_dvalue(V, ret, loss.vf_coef, val_loss);
+    if constexpr (Addon::on) addon.measure(sum8, A, o, lss.data(), sds.data());
     pieces[kPgPolLoss] = pol_loss; pieces[kPgValLoss] = val_loss; pieces[kPgEntropy] = entropy; pieces[kPgKl] = logp_old - logp;
     pieces[kPgClipped] = clipped ? 1.0f : 0.0f; pieces[kPgRet] = ret; pieces[kPgErr] = ret - value_old; pieces[7] = 0.0f;
     // output deltas
@@ -354,7 +362,8 @@ inline void pg_sample_host(const PgShape &sh, const PgLoss &loss, const float *t
         float *dp = dl[0][sh.layers[0] - 1];
         for (int a = 0; a < A; ++a) {
             dp[a] = pg_dmean(g, zs[(size_t)a], sds[(size_t)a]);
-            const float d = pg_dls(g, zs[(size_t)a], loss.ent_coef, moved[(size_t)a]);
+            float d = pg_dls(g, zs[(size_t)a], loss.ent_coef, moved[(size_t)a]);
+            if constexpr (Addon::on) addon.penalise(a, o[a], sds[(size_t)a], moved[(size_t)a], dp[a], d);
             if (sh.two_heads) dp[A + a] = d; else d_free[a] = d;
         }
         if (sh.layers[1]) dl[1][sh.layers[1] - 1][0] = dV;
@@ -369,6 +378,11 @@ inline void pg_sample_host(const PgShape &sh, const PgLoss &loss, const float *t
                 dl[net][l][j] = pg_hidden_delta(y[net][l][j], s, sh.activation);
             }
         }
+}
+inline void pg_sample_host(const PgShape &sh, const PgLoss &loss, const float *theta, const float *x, const float *action, float logp_old,
+                           float adv, float ret, float value_old, float *acts, float *deltas, float *pieces)
+{
+    pg_sample_host_with(sh, loss, theta, x, action, logp_old, adv, ret, value_old, acts, deltas, pieces, PgNoAddon{});
 }
 
 }  // namespace adc

@@ -18,6 +18,7 @@
 #include "adc_mlp.h"
 #include "adc_es.h"
 #include "adc_pg.h"
+#include "adc_pg_kl.h"
 #include "adc_td3.h"
 #include "adc_pbt.h"
 #include "adc_norm.h"
@@ -870,9 +871,12 @@ ADC_EXPORT int adc_pg_param_count_host(const adc_mlp_config *mlp, int32_t num_ke
     return ADC_OK;
 }
 
-ADC_EXPORT int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_pg_config *cfg, const float *theta_q, int64_t count,
-                                const float *obs_sd, const float *action_sa, const float *logp_old_s, const float *adv_s, const float *ret_s,
-                                const float *value_old_s, float *grad_q, double *sums10, adc_pg_stats *stats)
+namespace {
+// the gradient of `count` samples; addon_of(s): the sample's add-on (adc::PgNoAddon, or adc_pg_kl.h's)
+template <class AddonOf>
+int pg_grad_host_run(const adc_mlp_config *mlp, int32_t num_keywords, const adc_pg_config *cfg, const float *theta_q, int64_t count, const float *obs_sd,
+                     const float *action_sa, const float *logp_old_s, const float *adv_s, const float *ret_s, const float *value_old_s, float *grad_q,
+                     double *sums10, adc_pg_stats *stats, AddonOf addon_of)
 {
     if (adc_mlp_config_check(mlp, num_keywords, nullptr) != ADC_OK || adc_pg_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
     if (count < 1 || count > 0x7FFFFFFFll || !theta_q || !obs_sd || !action_sa || !logp_old_s || !adv_s || !ret_s || !value_old_s || !grad_q) return ADC_EINVAL;
@@ -881,8 +885,8 @@ ADC_EXPORT int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords,
     const size_t S = (size_t)count, na = (size_t)adc::pg_acts_floats(sh), nd = (size_t)adc::pg_deltas_floats(sh), D = (size_t)sh.D, A = (size_t)sh.A;
     std::vector<float> acts(S * std::max<size_t>(na, 1)), deltas(S * nd), pieces(S * adc::kPgPieces);
     for (size_t s = 0; s < S; ++s)
-        adc::pg_sample_host(sh, loss, theta_q, obs_sd + s * D, action_sa + s * A, logp_old_s[s], adv_s[s], ret_s[s], value_old_s[s],
-                            acts.data() + s * na, deltas.data() + s * nd, pieces.data() + s * adc::kPgPieces);
+        adc::pg_sample_host_with(sh, loss, theta_q, obs_sd + s * D, action_sa + s * A, logp_old_s[s], adv_s[s], ret_s[s], value_old_s[s],
+                                 acts.data() + s * na, deltas.data() + s * nd, pieces.data() + s * adc::kPgPieces, addon_of(s));
     // the gradient's terms in the flat order: every layer (its bias the row j = n_in with x = 1), then log_std's row
     size_t q = 0, ao = 0, dof = 0;
     auto term = [&](const float *X, size_t ldx, int n_in, size_t d_off, int n_out) {
@@ -918,6 +922,66 @@ ADC_EXPORT int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords,
         stats->policy_loss = o.policy_loss; stats->value_loss = o.value_loss; stats->entropy = o.entropy; stats->approx_kl = o.approx_kl;
         stats->clip_fraction = o.clip_fraction; stats->grad_norm = o.grad_norm; stats->explained_variance = o.explained_variance;
     }
+    return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_pg_config *cfg, const float *theta_q, int64_t count,
+                                const float *obs_sd, const float *action_sa, const float *logp_old_s, const float *adv_s, const float *ret_s,
+                                const float *value_old_s, float *grad_q, double *sums10, adc_pg_stats *stats)
+{
+    return pg_grad_host_run(mlp, num_keywords, cfg, theta_q, count, obs_sd, action_sa, logp_old_s, adv_s, ret_s, value_old_s, grad_q, sums10, stats,
+                            [](size_t) { return adc::PgNoAddon{}; });
+}
+
+// ---- the KL penalty and the value-loss clip on the host (adc_pg_kl.h: the code parts/kernel_pg_kl.inc runs) ---------------------
+ADC_EXPORT int adc_pg_kl_config_check(const adc_pg_kl_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    const float inf = __builtin_inff();
+    if (!cfg || cfg->struct_size != sizeof(adc_pg_kl_config)) msg = "adc_pg_kl_config: NULL or struct_size mismatch";
+    else if (!(cfg->kl_coef >= 0.0f && cfg->kl_coef < inf)) msg = "kl_coef >= 0 and finite";
+    else if (cfg->adaptive && !(cfg->kl_target > 0.0f && cfg->kl_target < inf)) msg = "kl_target > 0 and finite when adaptive";
+    else if (cfg->factor_up != 0.0f && !(cfg->factor_up > 1.0f && cfg->factor_up < inf)) msg = "factor_up > 1 and finite (0: 1.5)";
+    else if (cfg->factor_down != 0.0f && !(cfg->factor_down > 0.0f && cfg->factor_down < 1.0f)) msg = "factor_down in (0, 1) (0: 0.5)";
+    else if (!(cfg->vf_clip >= 0.0f && cfg->vf_clip < inf)) msg = "vf_clip >= 0 and finite (0: off)";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+ADC_EXPORT int adc_pg_kl_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_pg_config *cfg, const float *theta_q, int64_t count,
+                                   const float *obs_sd, const float *action_sa, const float *logp_old_s, const float *adv_s, const float *ret_s,
+                                   const float *value_old_s, const adc_pg_kl_config *kl, float kl_coef, const float *mean_old_sa, const float *ls_old,
+                                   int32_t ls_old_per_sample, float *grad_q, double *sums10, double *sums_kl2, adc_pg_stats *stats,
+                                   adc_pg_kl_stats *kl_stats)
+{
+    if (adc_pg_kl_config_check(kl, nullptr) != ADC_OK || !(kl_coef >= 0.0f && kl_coef < __builtin_inff()) || !mean_old_sa || !ls_old) return ADC_EINVAL;
+    if (count < 1 || count > 0x7FFFFFFFll || adc_mlp_config_check(mlp, num_keywords, nullptr) != ADC_OK) return ADC_EINVAL;
+    const size_t S = (size_t)count, A = (size_t)num_keywords + 1u;
+    std::vector<float> pk(S * adc::kPgKlPieces);
+    const adc::PgKl law{kl_coef, kl->vf_clip};
+    const int rc = pg_grad_host_run(mlp, num_keywords, cfg, theta_q, count, obs_sd, action_sa, logp_old_s, adv_s, ret_s, value_old_s, grad_q, sums10, stats,
+                                    [&](size_t s) {
+                                        return adc::PgKlSampleHost{law, mean_old_sa + s * A, ls_old_per_sample ? ls_old + s * A : ls_old,
+                                                                   pk.data() + s * adc::kPgKlPieces};
+                                    });
+    if (rc != ADC_OK) return rc;
+    double sums[adc::kPgKlPieces];
+    for (int c = 0; c < adc::kPgKlPieces; ++c)
+        sums[c] = adc::pg_csum(count, [&](double part, int64_t s) { return part + (double)pk[(size_t)s * adc::kPgKlPieces + (size_t)c]; });
+    if (sums_kl2) std::copy(sums, sums + adc::kPgKlPieces, sums_kl2);
+    if (kl_stats) {
+        kl_stats->kl = sums[adc::kPgKlKl] / (double)count;
+        kl_stats->vf_clip_fraction = sums[adc::kPgKlVfClipped] / (double)count;
+        kl_stats->kl_coef = kl_stats->kl_coef_next = kl_coef;
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_pg_kl_adapt_host(const adc_pg_kl_config *kl, float coef, double kl_mean, float *coef_next)
+{
+    if (adc_pg_kl_config_check(kl, nullptr) != ADC_OK || !coef_next) return ADC_EINVAL;
+    *coef_next = adc::pg_kl_adapt(adc::pg_kl_adapt_of(*kl), coef, kl_mean);
     return ADC_OK;
 }
 

@@ -148,6 +148,16 @@ struct adc_engine {
     std::vector<double> pgp_host_sums;          // [M][16]
     PgMember *pgp_dmem = nullptr;
     size_t pgp_part_stride = 0;                 // doubles of chunk partials per member
+    // the KL penalty / value-loss clip add-on of the live PPO / A2C trainer (adc_engine_pg_kl_init; parts/kernel_pg_kl.inc,
+    // parts/pg_kl_api.inc; the law is adc_pg_kl.h).  Its device arrays are the trainer's allocations (pg_allocs): they go with it
+    bool kl_live = false;
+    std::vector<adc_pg_kl_config> kl_cfg;       // [members] (1 for a single learner)
+    std::vector<float> kl_coef;                 // [members] the coefficients: the add-on's whole state
+    std::vector<adc_pg_kl_stats> kl_stats;      // [members] of the last minibatch / update
+    std::vector<PgKlMember> kl_mem;             // [members] the host's copy of kl_dmem (a population's)
+    PgKlMember *kl_dmem = nullptr;
+    float *kl_mean_old = nullptr, *kl_ls_old = nullptr;     // the snapshot: [T][N][A]; [T][N][A] (two heads) or [members][A]
+    float *kl_pieces = nullptr;                 // [members][T * minibatch envs][kPgKlPieces]
     // off-policy training over a replay ring filled from the record (adc_engine_td3_init; parts/kernel_td3.inc, parts/td3_api.inc)
     bool have_td3 = false, td3_norm_set = false, td3_gap = false;
     bool td3_critic_set[2][4] = {{false, false, false, false}, {false, false, false, false}};
@@ -2885,11 +2895,19 @@ void pbt_forget(adc_engine *e, int kind)
     e->pbt_s.clear(); e->pbt_host_fit.clear(); e->pbt_pairs.clear();
     e->pbt_ret = e->pbt_fit = nullptr; e->pbt_dpairs = nullptr;
 }
+// the KL add-on ends (its arrays stay the trainer's until that goes: a later adc_engine_pg_kl_init finds them)
+void kl_forget(adc_engine *e)
+{
+    e->kl_live = false;
+    e->kl_cfg.clear(); e->kl_coef.clear(); e->kl_stats.clear(); e->kl_mem.clear();
+}
 // the policy-gradient trainer goes with the policy and the record it was sized for
 void pg_drop(adc_engine *e)
 {
     norm_set_drop(e, e->rn);            // (it discounts by this trainer's gamma; the GAE kernels are back to k_pg_gae / k_pg_pop_gae)
     pbt_forget(e, ADC_PBT_PG);
+    kl_forget(e);
+    e->kl_dmem = nullptr; e->kl_mean_old = e->kl_ls_old = e->kl_pieces = nullptr;      // (its arrays are among pg_allocs)
     mlp_free(e, e->pg_allocs);
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
     e->pg_steps = 0;
@@ -2914,6 +2932,7 @@ void learners_drop(adc_engine *e)
 {
     norm_set_drop(e, e->on);
     norm_set_drop(e, e->rn);
+    kl_forget(e);                       // (as the reward normaliser: a solo trainer survives, its add-ons do not)
     // (a solo TD3 trainer survives learners and a population, refused while they are active; so do its normalisers, or its raw ring
     //  would be sampled without them afterwards.  A TD3 population's go with it, below)
     if (e->have_pg_pop) pg_drop(e);

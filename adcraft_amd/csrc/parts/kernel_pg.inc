@@ -31,6 +31,15 @@ struct PgView {
     int maxw;                               // the widest layer output of either network
 };
 
+// the KL penalty / value-clip add-on's side of a sample (adc_pg_kl.h; parts/kernel_pg_kl.inc): the snapshot of the collecting
+// distribution and the add-on's own pieces
+struct PgKlView {
+    const float *mean_old;                  // [T][N][A]
+    const float *ls_old;                    // [T][N][A] (two heads) or the clamped log_std vector(s) [A] / [M][A] (free head)
+    int ls_per_sample;
+    float *pieces;                          // scratch [S][kPgKlPieces]
+};
+
 // one term of the gradient: a layer's weights and bias, or log_std's row (n_in = 0)
 struct PgTerm {
     const float *X;                         // the layer's input: the record's obs rows (obs != 0) or the scratch activations
@@ -58,9 +67,10 @@ struct PgMember {
 
 constexpr int kPgBlock = 256;
 
-__host__ __device__ inline size_t pg_lds_floats(const adc::PgShape &sh, int maxw)
+// (kl: the add-on's instantiation keeps the sample's mean_old / ls_old rows as well)
+__host__ __device__ inline size_t pg_lds_floats(const adc::PgShape &sh, int maxw, bool kl = false)
 {
-    size_t n = (size_t)sh.D + 2u * (size_t)maxw + 3u * (size_t)sh.A;
+    size_t n = (size_t)sh.D + 2u * (size_t)maxw + (kl ? 5u : 3u) * (size_t)sh.A;
     for (int net = 0; net < 2; ++net)
         for (int l = 0; l < sh.layers[net]; ++l) n += (size_t)sh.n_out[net][l];
     return n;
@@ -235,9 +245,12 @@ __device__ __forceinline__ void pg_layer_back(const float *__restrict__ W, int n
 }
 
 // forward, head, loss and backward of sample s = t * B + (env - n0) with the layers `nets`, log_std and the loss constants given;
-// the sample's scratch rows are row `slot` of p.acts / p.deltas / p.pieces
+// the sample's scratch rows are row `slot` of p.acts / p.deltas / p.pieces.  kKl: with adc_pg_kl.h's KL penalty and value-loss clip
+// (k, kl; ls_old_at: where the member's vector starts in k.ls_old with the free head) - the instantiation without is the code
+// it was before there was one
+template <bool kKl>
 __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *nets, const float *log_std, const adc::PgLoss &loss, int n0, size_t s,
-                                               size_t slot)
+                                               size_t slot, const PgKlView &k, const adc::PgKl &kl, size_t ls_old_at)
 {
     extern __shared__ __align__(16) float pg_lds[];
     __shared__ float s_g, s_dv;
@@ -253,6 +266,7 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
         ybase = q;
     }
     float *d0 = ybase, *d1 = d0 + p.maxw, *zs = d1 + p.maxw, *sds = zs + A, *lss = sds + A;
+    float *mos = lss + A, *los = mos + A;   // (kKl only: the LDS region ends at lss + A otherwise)
     for (int j = tid; j < D; j += kPgBlock) x[j] = p.obs[row * (size_t)D + j];
     __syncthreads();
     float *acts = p.acts + slot * (size_t)p.na, *deltas = p.deltas + slot * (size_t)p.nd;
@@ -282,16 +296,30 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
         const float z = adc::pg_z(p.action[row * (size_t)A + a], o[a], sd);
         zs[a] = z; sds[a] = sd; lss[a] = ls;
         d0[a] = adc::mlp_logp_term(z, ls);
+        if constexpr (kKl) {     // the collecting distribution's row, and the KL's terms in d1
+            const float mo = k.mean_old[row * (size_t)A + a];
+            const float lo = k.ls_per_sample ? k.ls_old[row * (size_t)A + a] : k.ls_old[ls_old_at + a];
+            mos[a] = mo; los[a] = lo;
+            d1[a] = adc::pg_kl_term(o[a], ls, sd, mo, lo, adc::mlp_exp(lo));
+        }
     }
     __syncthreads();
-    if (tid < kWave) {       // the first eight lanes: the chains of the two sum8 over the components
+    if (tid < kWave) {       // the first eight lanes: the chains of the two (kKl: three) sum8 over the components
         const int c = tid & 7;
-        float st = 0.0f, sl = 0.0f;
+        float st = 0.0f, sl = 0.0f, sk = 0.0f;
         if (tid < adc::kMlpChains)
-            for (int a = c; a < A; a += adc::kMlpChains) { st = st + d0[a]; sl = sl + lss[a]; }
+            for (int a = c; a < A; a += adc::kMlpChains) {
+                st = st + d0[a]; sl = sl + lss[a];
+                if constexpr (kKl) sk = sk + d1[a];
+            }
         st = st + __shfl_xor(st, 1, 64); sl = sl + __shfl_xor(sl, 1, 64);
         st = st + __shfl_xor(st, 2, 64); sl = sl + __shfl_xor(sl, 2, 64);
         st = st + __shfl_xor(st, 4, 64); sl = sl + __shfl_xor(sl, 4, 64);
+        if constexpr (kKl) {
+            sk = sk + __shfl_xor(sk, 1, 64);
+            sk = sk + __shfl_xor(sk, 2, 64);
+            sk = sk + __shfl_xor(sk, 4, 64);
+        }
         if (tid == 0) {
             const float logp = adc::mlp_logp_finish(st, A), entropy = adc::pg_entropy_finish(sl, A);
             const float logp_old = p.logp[row], ret = p.ret[row];
@@ -300,7 +328,13 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
             int clipped;
             const float g = adc::pg_surrogate(ratio, p.adv[row], loss.eps_clip, pol_loss, clipped);
             const float V = sh.layers[1] ? y[1][sh.layers[1] - 1][0] : 0.0f;
-            const float dv = adc::pg_dvalue(V, ret, loss.vf_coef, val_loss);
+            float dv;
+            if constexpr (kKl) {
+                int vf_clipped;
+                dv = adc::pg_kl_dvalue(V, ret, loss.vf_coef, kl.vf_clip, val_loss, vf_clipped);
+                float *pk = k.pieces + slot * (size_t)adc::kPgKlPieces;
+                pk[adc::kPgKlKl] = sk; pk[adc::kPgKlVfClipped] = vf_clipped ? 1.0f : 0.0f;
+            } else dv = adc::pg_dvalue(V, ret, loss.vf_coef, val_loss);
             s_g = g; s_dv = dv;
             float *pc = p.pieces + slot * (size_t)adc::kPgPieces;
             pc[adc::kPgPolLoss] = pol_loss; pc[adc::kPgValLoss] = val_loss; pc[adc::kPgEntropy] = entropy; pc[adc::kPgKl] = logp_old - logp;
@@ -319,8 +353,14 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
         float *gout = deltas + doff[0][L - 1];
         for (int a = tid; a < A; a += kPgBlock) {
             const float raw = sh.two_heads ? o[A + a] : log_std[a];
-            const float dm = adc::pg_dmean(g, zs[a], sds[a]);
-            const float dl = adc::pg_dls(g, zs[a], loss.ent_coef, adc::pg_clamp_moved(raw, sh.clamp, sh.ls_lo, sh.ls_hi));
+            const int moved = adc::pg_clamp_moved(raw, sh.clamp, sh.ls_lo, sh.ls_hi);
+            float dm = adc::pg_dmean(g, zs[a], sds[a]);
+            float dl = adc::pg_dls(g, zs[a], loss.ent_coef, moved);
+            if constexpr (kKl)
+                if (kl.coef != 0.0f) {          // (wave-uniform; a zero coefficient adds nothing: adc_pg.h's bits)
+                    dm = adc::pg_kl_add(dm, kl.coef, adc::pg_kl_dmean(o[a], sds[a], mos[a]));
+                    dl = adc::pg_kl_add(dl, kl.coef, adc::pg_kl_dls(o[a], sds[a], mos[a], adc::mlp_exp(los[a]), moved));
+                }
             d0[a] = dm; gout[a] = dm;
             if (sh.two_heads) { d0[A + a] = dl; gout[A + a] = dl; }
             else deltas[dfree + a] = dl;
@@ -346,7 +386,7 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
 
 __global__ __launch_bounds__(kPgBlock) void k_pg_sample(PgView p)
 {
-    pg_sample_body(p, p.net, p.log_std, p.loss, p.n0, blockIdx.x, blockIdx.x);
+    pg_sample_body<false>(p, p.net, p.log_std, p.loss, p.n0, blockIdx.x, blockIdx.x, PgKlView{}, adc::PgKl{}, 0);
 }
 // sample blockIdx.x of member blockIdx.y's minibatch: the member's layers and loss constants, its envs from member * envs_per_member
 // on, its scratch rows from member * gridDim.x on (p.net, p.log_std and p.loss are not read)
@@ -354,8 +394,8 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_pop_sample(PgView p, const MlpL
                                                             int envs_per_member)
 {
     const int member = blockIdx.y;
-    pg_sample_body(p, learners[member].net, learners[member].log_std, mem[member].loss, p.n0 + member * envs_per_member, blockIdx.x,
-                   (size_t)member * gridDim.x + blockIdx.x);
+    pg_sample_body<false>(p, learners[member].net, learners[member].log_std, mem[member].loss, p.n0 + member * envs_per_member, blockIdx.x,
+                          (size_t)member * gridDim.x + blockIdx.x, PgKlView{}, adc::PgKl{}, 0);
 }
 
 // one term's partials: gpart[chunk][flat0 + j * n_out + h] = the chunk's chain of x_s[j] * delta_s[h]; a 16 x 16 tile (blockIdx.x)

@@ -69,7 +69,7 @@ int pbt_exploit_launch(adc_engine *e, int npairs)
     HIP_TRY(hipGetLastError());
     return ADC_OK;
 }
-// what the host keeps per member follows the donor
+// what the host keeps per member follows the donor (a live KL add-on's coefficients are then uploaded by the caller: kl_copy)
 void pbt_bookkeeping(adc_engine *e, int npairs)
 {
     const size_t per = 2u * adc::kMlpMaxLayers;
@@ -154,6 +154,8 @@ ADC_EXPORT int adc_engine_pbt_exploit(adc_engine *e, const int32_t *src_of_m)
     if (int rc = pbt_exploit_launch(e, npairs)) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     pbt_bookkeeping(e, npairs);
+    if (e->pbt_kind == ADC_PBT_PG)
+        if (int rc = kl_copy(e, npairs, [&](int j, int &d, int &f) { d = e->pbt_pairs[(size_t)j].dst; f = e->pbt_pairs[(size_t)j].src; })) return rc;
     return ADC_OK;
 }
 
@@ -201,6 +203,8 @@ ADC_EXPORT int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_p
     if ((rc = e->pbt_kind == ADC_PBT_PG ? pgp_members_upload(e) : tp_members_upload(e))) return rc;
     if (e->pbt_kind == ADC_PBT_PG) e->pg_adv_ready = false;       // (as adc_engine_pg_pop_set_config leaves it)
     pbt_bookkeeping(e, npairs);
+    if (e->pbt_kind == ADC_PBT_PG && (rc = kl_copy(e, npairs, [&](int j, int &d, int &f) { d = e->pbt_pairs[(size_t)j].dst; f = e->pbt_pairs[(size_t)j].src; })))
+        return rc;
     for (int j = 0; j < npairs; ++j) e->pbt_s[(size_t)e->pbt_pairs[(size_t)j].dst] = e->pbt_s[(size_t)e->pbt_pairs[(size_t)j].src];
     e->pbt_round += 1;
     HIP_TRY(hipStreamSynchronize(e->stream));

@@ -76,6 +76,8 @@ int pg_advantages_run(adc_engine *e)
         hipLaunchKernelGGL(k_pg_normalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, e->pg_adv, n, mean, sd);
         HIP_TRY(hipGetLastError());
     }
+    if (e->kl_live)       // (the start of an update: the collecting distribution, adc_pg_kl.h)
+        if (int rc = kl_snapshot_launch(e)) return rc;
     e->pg_adv_ready = true;
     return ADC_OK;
 }
@@ -96,7 +98,12 @@ int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
     p.N = N; p.n0 = n0; p.B = B;
     p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
     p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
-    hipLaunchKernelGGL(k_pg_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p);
+    const bool kl = e->kl_live;
+    if (kl)
+        hipLaunchKernelGGL(k_pg_kl_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float), e->stream, p, kl_view(e),
+                           adc::PgKl{e->kl_coef[0], e->kl_cfg[0].vf_clip});
+    else
+        hipLaunchKernelGGL(k_pg_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p);
     // the gradient's terms in the flat order
     {
         int flat = 0, ao = 0, dof = 0;
@@ -123,11 +130,13 @@ int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
     int rc;
     if ((rc = pg_csum_launch(e, e->pg_pieces, S, adc::kPgPieces, 7, 0, 0.0, e->pg_sums)) ||
         (rc = pg_csum_launch(e, e->pg_pieces + adc::kPgRet, S, adc::kPgPieces, 2, 2, 0.0, e->pg_sums + 7)) ||
-        (rc = pg_csum_launch(e, e->pg_grad, Q, 1, 1, 2, 0.0, e->pg_sums + 9)))
+        (rc = pg_csum_launch(e, e->pg_grad, Q, 1, 1, 2, 0.0, e->pg_sums + 9)) ||
+        (kl && (rc = pg_csum_launch(e, e->kl_pieces, S, adc::kPgKlPieces, adc::kPgKlPieces, 0, 0.0, e->pg_sums + adc::kPgSums))))
         return rc;
-    double sums[adc::kPgSums];
-    HIP_TRY(hipMemcpyAsync(sums, e->pg_sums, sizeof(sums), hipMemcpyDeviceToHost, e->stream));
+    double sums[adc::kPgSums + adc::kPgKlPieces];       // (the add-on's two sums are appended only while it lives)
+    HIP_TRY(hipMemcpyAsync(sums, e->pg_sums, (size_t)(adc::kPgSums + (kl ? adc::kPgKlPieces : 0)) * 8, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    if (kl) kl_stats_minibatch(e, 0, sums + adc::kPgSums, S);
     const adc::PgStatsOut st = adc::pg_stats_finish(sums, S);
     const bool clip = e->pg_cfg.max_grad_norm > 0.0f;
     const float scale = clip ? adc::pg_clip_scale(e->pg_cfg.max_grad_norm, st.grad_norm) : 1.0f;
@@ -266,11 +275,14 @@ ADC_EXPORT int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats 
     if ((rc = pg_advantages_run(e))) return rc;
     const int N = e->v.N, mb = e->pg_mb, count = N / mb;
     adc::PgStatsOut mean{};
+    KlEpoch kl;
     for (int ep = 0; ep < epochs; ++ep) {
         adc::PgStatsOut acc{};
+        kl.begin(e);
         for (int i = 0; i < count; ++i) {
             adc::PgStatsOut o;
             if ((rc = pg_minibatch_run(e, i * mb, mb, &o))) return rc;
+            kl.add(e);
             acc.policy_loss = acc.policy_loss + o.policy_loss; acc.value_loss = acc.value_loss + o.value_loss; acc.entropy = acc.entropy + o.entropy;
             acc.approx_kl = acc.approx_kl + o.approx_kl; acc.clip_fraction = acc.clip_fraction + o.clip_fraction;
             acc.grad_norm = acc.grad_norm + o.grad_norm; acc.explained_variance = acc.explained_variance + o.explained_variance;
@@ -279,6 +291,7 @@ ADC_EXPORT int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats 
         mean = adc::PgStatsOut{acc.policy_loss / c, acc.value_loss / c, acc.entropy / c, acc.approx_kl / c, acc.clip_fraction / c, acc.grad_norm / c,
                                acc.explained_variance / c};
     }
+    if (e->kl_live && (rc = kl_update_end(e, kl, count))) return rc;
     if (stats) pg_stats_fill(stats, mean, e->pg_steps, (int64_t)e->ro_t * mb);
     return ADC_OK;
 }
@@ -396,6 +409,8 @@ int pgp_advantages_run(adc_engine *e)
         hipLaunchKernelGGL(k_pg_pop_normalize, dim3((unsigned)((tn + 255) / 256)), dim3(256), 0, e->stream, e->pg_adv, tn, N, n, e->pgp_dmem);
         HIP_TRY(hipGetLastError());
     }
+    if (e->kl_live)
+        if ((rc = kl_snapshot_launch(e))) return rc;
     e->pg_adv_ready = true;
     return ADC_OK;
 }
@@ -415,8 +430,13 @@ int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
     p.N = N; p.n0 = n0; p.B = B;
     p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
     p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
-    hipLaunchKernelGGL(k_pg_pop_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p,
-                       e->lrn_tab, e->pgp_dmem, n);
+    const bool kl = e->kl_live;
+    if (kl)
+        hipLaunchKernelGGL(k_pg_pop_kl_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float), e->stream, p,
+                           kl_view(e), e->lrn_tab, e->pgp_dmem, e->kl_dmem, n);
+    else
+        hipLaunchKernelGGL(k_pg_pop_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p,
+                           e->lrn_tab, e->pgp_dmem, n);
     {
         int flat = 0, ao = 0, dof = 0;
         auto launch = [&](const float *X, size_t ldx, int n_in, int n_out, int obs) {
@@ -439,7 +459,8 @@ int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
     int rc;
     if ((rc = pgp_csum_launch(e, e->pg_pieces, (int)S, 0, 0, (size_t)S, adc::kPgPieces, 7, 0, 0)) ||
         (rc = pgp_csum_launch(e, e->pg_pieces + adc::kPgRet, (int)S, 0, 0, (size_t)S, adc::kPgPieces, 2, 2, 7)) ||
-        (rc = pgp_csum_launch(e, e->pg_grad, Q, 0, 0, (size_t)Q, 1, 1, 2, 9)) || (rc = pgp_sums_fetch(e)))
+        (rc = pgp_csum_launch(e, e->pg_grad, Q, 0, 0, (size_t)Q, 1, 1, 2, 9)) ||
+        (kl && (rc = pgp_csum_launch(e, e->kl_pieces, (int)S, 0, 0, (size_t)S, adc::kPgKlPieces, adc::kPgKlPieces, 0, adc::kPgSums))) || (rc = pgp_sums_fetch(e)))
         return rc;
     // the statistics, the clip scale and the step's constants of every member on the host, as the solo path's are; up in one copy
     for (int m = 0; m < M; ++m) {
@@ -450,6 +471,7 @@ int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
         pm.scale = pm.clip ? adc::pg_clip_scale(c.max_grad_norm, st.grad_norm) : 1.0f;
         pm.step = pg_step_of(c, e->pgp_steps[(size_t)m]);
         if (out_m) out_m[m] = st;
+        if (kl) kl_stats_minibatch(e, m, e->pgp_host_sums.data() + (size_t)m * 16 + adc::kPgSums, S);
     }
     if ((rc = pgp_members_upload(e))) return rc;
     hipLaunchKernelGGL(k_pg_pop_update, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, e->pg_theta, e->pg_m, e->pg_v,
@@ -567,10 +589,13 @@ ADC_EXPORT int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_st
     if ((rc = pgp_advantages_run(e))) return rc;
     const int M = e->lrn_M, count = e->lrn_n / e->pg_mb;
     std::vector<adc::PgStatsOut> o((size_t)M), acc((size_t)M), mean((size_t)M);
+    KlEpoch kl;
     for (int ep = 0; ep < epochs; ++ep) {
         acc.assign((size_t)M, adc::PgStatsOut{});
+        kl.begin(e);
         for (int i = 0; i < count; ++i) {
             if ((rc = pgp_minibatch_run(e, i, o.data()))) return rc;
+            kl.add(e);
             for (size_t m = 0; m < (size_t)M; ++m) {
                 adc::PgStatsOut &a = acc[m];
                 a.policy_loss = a.policy_loss + o[m].policy_loss; a.value_loss = a.value_loss + o[m].value_loss; a.entropy = a.entropy + o[m].entropy;
@@ -585,6 +610,7 @@ ADC_EXPORT int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_st
                                       a.explained_variance / c};
         }
     }
+    if (e->kl_live && (rc = kl_update_end(e, kl, count))) return rc;       // (every member's adaptation: one small upload)
     if (stats_m)
         for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, mean[(size_t)m], e->pgp_steps[(size_t)m], (int64_t)e->ro_t * e->pg_mb);
     return ADC_OK;
@@ -661,5 +687,6 @@ ADC_EXPORT int adc_engine_pg_pop_copy(adc_engine *e, int32_t src, int32_t dst)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->pgp_steps[(size_t)dst] = e->pgp_steps[(size_t)src];
+    if ((rc = kl_copy(e, 1, [&](int, int &d, int &f) { d = dst; f = src; }))) return rc;      // (the donor's KL coefficient)
     return ADC_OK;
 }

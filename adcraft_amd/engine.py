@@ -907,6 +907,60 @@ class StepEngine:
         """weights, optimiser moments and step count of member src into member dst, on the device"""
         check(self._lib.adc_engine_pg_pop_copy(self._h, int(src), int(dst)))
 
+    # ---- PPO's adaptive KL penalty and value-loss clip (parts/kernel_pg_kl.inc; the law is csrc/adc_pg_kl.h) ----------------------
+    @classmethod
+    def pg_kl_config(cls, kl_coef=0.2, kl_target=0.01, adaptive=True, vf_clip=0.0, factor_up=0.0, factor_down=0.0):
+        """an adc_pg_kl_config: kl_coef the starting coefficient of the analytic KL(pi_old || pi_new) in the loss; adaptive: after
+        every update it is multiplied by factor_up (0: 1.5) when the last epoch's mean KL exceeds 2 kl_target, by factor_down
+        (0: 0.5) when it is below 0.5 kl_target; vf_clip > 0 caps a sample's squared value error (0: off).  The defaults are
+        RLlib's PPO's (kl_coeff 0.2, kl_target 0.01), configuration, not measurements."""
+        c = _ffi.PGKLConfig()
+        c.struct_size = C.sizeof(_ffi.PGKLConfig)
+        c.kl_coef, c.kl_target, c.adaptive = float(kl_coef), float(kl_target), 1 if adaptive else 0
+        c.factor_up, c.factor_down, c.vf_clip = float(factor_up), float(factor_down), float(vf_clip)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_pg_kl_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad KL penalty configuration").decode())
+        return c
+
+    def pg_kl_init(self, per_member=None, **options):
+        """the KL penalty and the value-loss clip on the live PPO / A2C trainer (pg_init or pg_pop_init first); options as
+        pg_kl_config's, shared by all learners - or per_member: a list of such dicts, one per learner of a population"""
+        if per_member is not None and options:
+            raise ValueError("pg_kl_init: options shared by all members, or per_member, not both")
+        built = [self.pg_kl_config(**o) for o in per_member] if per_member is not None else [self.pg_kl_config(**options)]
+        arr = (_ffi.PGKLConfig * len(built))(*built)
+        check(self._lib.adc_engine_pg_kl_init(self._h, arr, len(built)))
+        self._pg_kl_members = max(getattr(self, "_learners", 0), 1)
+
+    def pg_kl_stats(self):
+        """of the last minibatch or update: dict of kl, vf_clip_fraction, kl_coef (used), kl_coef_next - a list of them, one
+        per learner, under a population"""
+        st = (_ffi.PGKLStats * getattr(self, "_pg_kl_members", 1))()
+        check(self._lib.adc_engine_pg_kl_stats(self._h, st))
+        out = [{k: getattr(x, k) for k, _ in _ffi.PGKLStats._fields_} for x in st]
+        return out if getattr(self, "_learners", 0) else out[0]
+
+    def pg_kl_coef(self, member=0, value=None):
+        """a learner's KL coefficient (float32), the add-on's whole state.  get (no value) or set"""
+        if value is None:
+            c = C.c_float(0.0)
+            check(self._lib.adc_engine_pg_kl_coef_get(self._h, int(member), C.byref(c)))
+            return np.float32(c.value)
+        check(self._lib.adc_engine_pg_kl_coef_set(self._h, int(member), float(np.float32(value))))
+
+    def pg_kl_old_dist(self):
+        """the snapshot the last advantages call took: (mean_old [T, N, A], ls_old [T, N, A] with two heads, else [members, A])"""
+        self.pg_kl_coef(0)                      # (refused here, by the add-on's own message, when it does not live)
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        A = self.num_keywords + 1
+        mean = np.zeros((t.value, self.num_envs, A), np.float32)
+        two = self._mlp.log_std is None
+        ls = np.zeros((t.value, self.num_envs, A) if two else (getattr(self, "_pg_kl_members", 1), A), np.float32)
+        check(self._lib.adc_engine_pg_kl_old_dist_fetch(self._h, mean.ctypes.data, ls.ctypes.data))
+        return mean, ls
+
     # ---- off-policy (TD3) training over a replay ring filled from the record (parts/kernel_td3.inc; baselines/td3_trainer.py) ----
     TD3_OPTIMISERS = {"adam": _ffi.TD3_ADAM, "sgd": _ffi.TD3_SGD}
 

@@ -13,8 +13,14 @@ every iteration's record after the PPO / A2C update.  With --normalize-rewards t
 standard deviation of the discounted return (StepEngine.rew_norm_*), updated from every iteration's record before the update;
 --reward-scale then only sets where the first iteration starts.
 
+With --kl-penalty COEF the loss gains RLlib's analytic KL penalty between the collecting and the current policy, whose
+coefficient adapts to --kl-target after every update, and with --vf-clip C a sample's squared value error is capped at C
+(StepEngine.pg_kl_*; csrc/adc_pg_kl.h).  --rllib takes the whole configuration of the paper's PPO agent as far as this trainer
+expresses it (pg_trainer.rllib_ppo(): its docstring says what it leaves out); --lr and --reward-scale then apply only when given.
+
 Usage: python examples/train_mlp_policy_ppo.py [--iterations 100] [--algo ppo|a2c] [--num-envs 4096] [--num-keywords 100]
                                                [--normalize-observations] [--normalize-rewards]
+                                               [--kl-penalty COEF [--kl-target T]] [--vf-clip C] [--rllib]
 """
 import argparse
 import sys
@@ -62,8 +68,12 @@ def main():
     ap.add_argument("--num-keywords", type=int, default=100)
     ap.add_argument("--days", type=int, default=60)
     ap.add_argument("--mean-volume", type=float, default=8.0)
-    ap.add_argument("--lr", type=float, default=1e-3)
-    ap.add_argument("--reward-scale", type=float, default=0.1)
+    ap.add_argument("--lr", type=float, default=None, help="default 1e-3 (--rllib: the preset's 1e-4)")
+    ap.add_argument("--reward-scale", type=float, default=None, help="default 0.1 (--rllib: 1)")
+    ap.add_argument("--kl-penalty", type=float, default=None, metavar="COEF", help="the starting coefficient of the adaptive KL penalty")
+    ap.add_argument("--kl-target", type=float, default=0.01, metavar="T", help="the KL the coefficient adapts to")
+    ap.add_argument("--vf-clip", type=float, default=0.0, metavar="C", help="cap of a sample's squared value error (0: off)")
+    ap.add_argument("--rllib", action="store_true", help="the paper's PPO configuration (pg_trainer.rllib_ppo())")
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device, from identity vectors")
@@ -72,12 +82,23 @@ def main():
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
     zm = evaluate("zero_margin", None, held_out, days, budget)
-    print(f"{args.algo}: {N} envs x {K} keywords, {days} days per iteration; held-out: {args.eval_envs} envs")
-    print(f"{'iteration':>10} {'kl':>9} {'ev':>7} {'return':>10} {'NCP':>8}   zero-margin: return {zm[0]:.2f} NCP {zm[1]:.3f}")
+    print(f"{'rllib_ppo' if args.rllib else args.algo}: {N} envs x {K} keywords, {days} days per iteration; held-out: {args.eval_envs} envs")
+    print(f"{'iteration':>10} {'kl':>9} {'kl coef':>9} {'ev':>7} {'return':>10} {'NCP':>8}   zero-margin: return {zm[0]:.2f} NCP {zm[1]:.3f}")
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(synthetic.implicit_keyword_planes(N, K, seed=1, mean_volume=args.mean_volume))
     eng.reset()
-    config = getattr(pg_trainer, args.algo)(lr=args.lr, reward_scale=args.reward_scale)
+    if args.rllib:
+        config = pg_trainer.rllib_ppo(**{k: v for k, v in (("lr", args.lr), ("reward_scale", args.reward_scale)) if v is not None})
+    else:
+        config = getattr(pg_trainer, args.algo)(lr=1e-3 if args.lr is None else args.lr, reward_scale=0.1 if args.reward_scale is None else args.reward_scale)
+    kl = dict(config.get("kl_penalty") or {})
+    if args.kl_penalty is not None:
+        kl.update(kl_coef=args.kl_penalty, kl_target=args.kl_target, adaptive=True)
+    if args.vf_clip > 0:
+        kl["vf_clip"] = args.vf_clip
+    if kl and "kl_coef" not in kl:          # (the value clip alone: no penalty)
+        kl.update(kl_coef=0.0, adaptive=False)
+    config["kl_penalty"] = kl or None
     policy = with_value_network(default_policy(K, days=days), (32, 32))
     if args.normalize_observations:
         policy.shift, policy.scale = np.zeros_like(policy.shift), np.ones_like(policy.scale)
@@ -85,13 +106,14 @@ def main():
                                    normalize_rewards=args.normalize_rewards, **config)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
-    print(f"{0:>10} {'':>9} {'':>7} {ret:10.2f} {ncp:8.3f}")
+    print(f"{0:>10} {'':>9} {'':>9} {'':>7} {ret:10.2f} {ncp:8.3f}")
     t0 = time.perf_counter()
     for it in range(1, args.iterations + 1):
         stats = trainer.iteration(days, budget, reset=True, reset_seeds=rng.integers(0, 2 ** 63, N).astype(np.uint64))
         if it % args.every == 0 or it == args.iterations:
             ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
-            print(f"{it:>10} {stats['approx_kl']:9.5f} {stats['explained_variance']:7.3f} {ret:10.2f} {ncp:8.3f}", flush=True)
+            kl, coef = (stats["kl"], f"{stats['kl_coef']:9.4g}") if "kl" in stats else (stats["approx_kl"], f"{'':>9}")     # (the analytic KL under the add-on)
+            print(f"{it:>10} {kl:9.5f} {coef} {stats['explained_variance']:7.3f} {ret:10.2f} {ncp:8.3f}", flush=True)
     eng.close()
     print(f"{args.iterations} iterations in {time.perf_counter() - t0:.2f} s (evaluations included)")
 

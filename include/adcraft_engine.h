@@ -678,6 +678,51 @@ int adc_engine_pg_pop_set_config(adc_engine *e, int32_t member, const adc_pg_con
 /* theta, moments and step count of src into dst on the device, and dst's layers and log_std rebuilt (its configuration stays) */
 int adc_engine_pg_pop_copy(adc_engine *e, int32_t src, int32_t dst);
 
+/* ---- PPO with an adaptive KL penalty and a value-loss clip (the law is csrc/adc_pg_kl.h) ----------------------------------------
+ * An add-on to a live PPO / A2C trainer (adc_engine_pg_init or adc_engine_pg_pop_init), attached after it as the reward
+ * normaliser is: the loss gains kl_coef * mean KL(pi_old || pi_new), the analytic KL divergence between the diagonal Gaussian that
+ * collected a sample and the current one, and a sample whose squared value error exceeds vf_clip has the value loss 0.5 vf_clip
+ * and passes no gradient to the value network - RLlib's PPO loss (our value loss carries a factor 0.5 RLlib's does not: its
+ * vf_loss_coeff 1.0 with vf_clip_param c is vf_coef 2.0 with vf_clip c here).  adc_pg_config, adc_pg_stats and every existing
+ * entry point keep their layout and meaning; without adc_engine_pg_kl_init every call launches the kernels it launched.
+ * The old distribution is a snapshot: while the add-on lives adc_engine_pg_advantages / _pg_pop_advantages (and so _pg_update /
+ * _pg_pop_update, once at their start) also run the policy network alone over all recorded rows under the parameters then in
+ * force and keep mean_old [T][N][A] and ls_old ([T][N][A] with two heads; with the free head the clamped log_std vector [A], one
+ * per member under a population [M][A]) - bit for bit what the act computed.  adc_engine_pg_kl_old_dist_fetch copies them out.
+ * The coefficient is the add-on's whole state.  adc_engine_pg_update / _pg_pop_update adapt it once at their end when
+ * `adaptive`: kl, the float64 mean KL of the last epoch (the mean over its minibatches, as adc_pg_stats is), above 2 kl_target:
+ * coef *= factor_up; below 0.5 kl_target: coef *= factor_down.  adc_engine_pg_minibatch / _pg_pop_minibatch never adapt: a
+ * caller that drives minibatches itself uses _coef_set.  kl_coef == 0 adds nothing to the gradient (the trainer's own bits) and
+ * still measures the KL.  Under a population every member has its own coefficient that adapts on its own, also when the settings
+ * are shared (count 1); the adaptation of all members is one small upload, adc_engine_pg_pop_copy and a PBT round's copy give
+ * the destination its donor's coefficient (it is not a tuned PBT hyperparameter).  With adc_engine_pg_state_get / _set (or the
+ * _pg_pop_ ones) and _coef_get / _coef_set a resumed run continues bit for bit.
+ * adc_engine_pg_kl_init is refused with ADC_ESTATE (the engine stays usable) without a live PPO / A2C trainer or while a TD3
+ * trainer lives, with ADC_EINVAL when count is neither 1 nor the number of members (1 for adc_engine_pg_init) or a configuration
+ * fails adc_pg_kl_config_check; it marks the advantages stale (a minibatch needs the snapshot).  The add-on does not survive
+ * adc_engine_pg_init, adc_engine_pg_pop_init, adc_engine_mlp_init, adc_engine_mlp_learners or adc_engine_rollout_enable.
+ * adc_engine_pg_kl_stats: of the last minibatch or update, [1] or [M]: kl and vf_clip_fraction as adc_pg_stats' fields are
+ * formed, kl_coef the coefficient the gradient used, kl_coef_next the one the next call uses. */
+typedef struct adc_pg_kl_config {
+    uint32_t struct_size;          /* sizeof(adc_pg_kl_config) */
+    float kl_coef;                 /* >= 0, finite: the starting coefficient */
+    float kl_target;               /* > 0 and finite when adaptive */
+    int32_t adaptive;              /* 0: the coefficient stays */
+    float factor_up, factor_down;  /* > 1 and finite; in (0, 1); 0 means 1.5 / 0.5 */
+    float vf_clip;                 /* >= 0, finite: the cap of a sample's squared value error; 0: off */
+} adc_pg_kl_config;
+typedef struct adc_pg_kl_stats {
+    double kl, vf_clip_fraction;
+    float kl_coef, kl_coef_next;
+} adc_pg_kl_stats;
+int adc_pg_kl_config_check(const adc_pg_kl_config *cfg, const char **message);           /* host only */
+int adc_engine_pg_kl_init(adc_engine *e, const adc_pg_kl_config *cfgs, int32_t count);
+int adc_engine_pg_kl_stats(adc_engine *e, adc_pg_kl_stats *stats_m);
+int adc_engine_pg_kl_coef_get(adc_engine *e, int32_t member, float *coef);
+int adc_engine_pg_kl_coef_set(adc_engine *e, int32_t member, float coef);
+/* the snapshot of the last advantages call: mean_old_tna [T][N][A]; ls_old [T][N][A] (two heads) or [members][A] (either may be NULL) */
+int adc_engine_pg_kl_old_dist_fetch(adc_engine *e, float *mean_old_tna, float *ls_old);
+
 /* ---- off-policy training on the device: a replay ring, twin critics, TD3 (the law is csrc/adc_td3.h) --------------------------
  * The actor is the policy network given to adc_engine_mlp_init with the free log_std[A] head; its mean is TD3's deterministic
  * action, and the stochastic act mean + exp(log_std) * z is the exploration (set log_std = log(sigma); TD3 never trains it; a
@@ -1162,6 +1207,17 @@ int adc_pg_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_
                      const float *value_old_s, float *grad_q, double *sums10, adc_pg_stats *stats);
 int adc_pg_step_host(const adc_pg_config *cfg, int64_t n_params, int64_t steps_taken, const float *grad_q, float *theta_q, float *m_q,
                      float *v_q);
+/* adc_pg_grad_host under the KL penalty and the value-loss clip (adc_pg_kl.h): kl's vf_clip, the coefficient kl_coef (the
+ * configuration's own is not read), the collecting distribution mean_old_sa [count][A] and ls_old ([count][A] when
+ * ls_old_per_sample, else the vector [A]).  sums_kl2 (may be NULL) receives the chunked sums of the per-sample KL and of the
+ * value-clipped flags, kl_stats (may be NULL) the statistics (kl_coef_next = kl_coef).  adapt: the coefficient after an update
+ * whose last epoch's mean KL was kl_mean. */
+int adc_pg_kl_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_pg_config *cfg, const float *theta_q, int64_t count,
+                        const float *obs_sd, const float *action_sa, const float *logp_old_s, const float *adv_s, const float *ret_s,
+                        const float *value_old_s, const adc_pg_kl_config *kl, float kl_coef, const float *mean_old_sa, const float *ls_old,
+                        int32_t ls_old_per_sample, float *grad_q, double *sums10, double *sums_kl2, adc_pg_stats *stats,
+                        adc_pg_kl_stats *kl_stats);
+int adc_pg_kl_adapt_host(const adc_pg_kl_config *kl, float coef, double kl_mean, float *coef_next);
 /* off-policy training on the host: the same code as the device's (adc_td3.h).  `seed` is the effective seed (the configuration's,
  * or the engine's when that is 0).  The batch arrays hold the gathered elements in order: x_bd / x2_bd [count][D], a_ba [count][A].
  * shift_a / scale_a: the action normalisation, both NULL for none.  target: y_b [count] from the target actor theta_target_p and

@@ -87,6 +87,14 @@ class PGKLConfig(C.Structure):
                 ("factor_up", C.c_float), ("factor_down", C.c_float), ("vf_clip", C.c_float)]
 
 
+class PGShuffleConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("minibatch_samples", C.c_int32), ("seed", C.c_uint64), ("target_kl", C.c_float)]
+
+
+class PGShuffleStats(C.Structure):
+    _fields_ = [("epochs_begun", C.c_int32), ("minibatches_evaluated", C.c_int32), ("steps_taken", C.c_int32), ("stopped", C.c_int32)]
+
+
 class PGKLStats(C.Structure):
     _fields_ = [("kl", C.c_double), ("vf_clip_fraction", C.c_double), ("kl_coef", C.c_float), ("kl_coef_next", C.c_float)]
 
@@ -325,6 +333,14 @@ def lib():
         "adc_pg_kl_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(PGConfig), vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(PGKLConfig), f32, vp, vp, i32,
                                  vp, vp, vp, C.POINTER(PGStats), C.POINTER(PGKLStats)], C.c_int),
         "adc_pg_kl_adapt_host": ([C.POINTER(PGKLConfig), f32, f64, C.POINTER(f32)], C.c_int),
+        "adc_pg_shuffle_config_check": ([C.POINTER(PGShuffleConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_pg_shuffle_init": ([vp, C.POINTER(PGShuffleConfig), i32], C.c_int),
+        "adc_engine_pg_shuffle_epoch": ([vp], C.c_int),
+        "adc_engine_pg_shuffle_minibatch": ([vp, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_pg_shuffle_order_fetch": ([vp, vp, vp], C.c_int),
+        "adc_engine_pg_shuffle_stats": ([vp, C.POINTER(PGShuffleStats)], C.c_int),
+        "adc_pg_shuffle_order_host": ([C.c_uint64, i64, C.c_uint32, vp], C.c_int),
+        "adc_pg_shuffle_stop_host": ([f64, f32, C.POINTER(i32)], C.c_int),
         "adc_engine_td3_init": ([vp, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_td3_set_action_norm": ([vp, vp, vp], C.c_int),

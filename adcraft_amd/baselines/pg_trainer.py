@@ -55,18 +55,21 @@ def a2c(**overrides):
     return cfg
 
 
-def rllib_ppo(**overrides):
+def rllib_ppo(minibatch_size=None, **overrides):
     """The PPO configuration of the paper's experiments (RLlib's PPO as the reference's sem_ppo_config sets it), as far as this
     trainer expresses it: gamma 0.995, lambda 0.95, lr 1e-4, clip range 0.5, 20 epochs, and RLlib's loss terms - the adaptive KL
     penalty (kl_coeff 1.0, kl_target 0.01) and the value-loss clip (vf_clip_param 10.0) - through `kl_penalty`.  vf_coef is 2.0
     because our value loss carries a factor 0.5 that RLlib's does not (csrc/adc_pg_kl.h): RLlib's vf_loss_coeff 1.0.
-    What it does NOT reproduce: RLlib's minibatches are 64 samples drawn from a shuffled train batch, ours are whole
-    trajectories of env ranges in ascending order (`minibatches` stays this trainer's own, 4); RLlib does not normalise
-    advantages per update the way normalize_advantages does, and clips gradients only when asked to; per-minibatch details of
-    its learner (its KL is the mean over the minibatches of an epoch it sampled, ours over the last epoch's env ranges) differ
-    accordingly."""
+    minibatch_size=64 is the reference's sgd_minibatch_size: minibatches of 64 samples drawn from a new shuffle of the train
+    batch every epoch (csrc/adc_pg_shuffle.h) instead of `minibatches` env ranges; without it the preset keeps this trainer's
+    own 4 env-range minibatches.  With it RLlib's KL - the mean over the minibatches of an epoch - is what ours is.  What
+    remains a configuration choice rather than a difference of the learner: RLlib does not normalise advantages per update
+    (normalize_advantages=False) and clips gradients only when asked to (max_grad_norm=0)."""
     cfg = ppo(gamma=0.995, lam=0.95, lr=1e-4, eps_clip=0.5, epochs=20, vf_coef=2.0,
               kl_penalty=dict(kl_coef=1.0, kl_target=0.01, adaptive=True, vf_clip=10.0))
+    if minibatch_size is not None:
+        del cfg["minibatches"]
+        cfg["minibatch_size"] = int(minibatch_size)
     cfg.update(overrides)
     return cfg
 
@@ -91,6 +94,20 @@ def _kl_options(kl_penalty, members=None):
         if unknown:
             raise ValueError(f"kl_penalty: unknown option(s) {sorted(unknown)}: {', '.join(sorted(_KL_KEYS))}")
     return [dict(o) for o in items] if many else dict(items[0])
+
+
+def _shuffle_options(config, minibatch_size, target_kl, shuffle_seed):
+    """(minibatches or None, the add-on's options or None) of a trainer's configuration: minibatch_size takes the role of
+    `minibatches`, which then may be left out; giving both is an error"""
+    if minibatch_size is not None and "minibatches" in config:
+        raise ValueError("minibatches (env ranges) and minibatch_size (shuffled samples) are two ways to cut an update: give one")
+    if minibatch_size is None:
+        if target_kl is not None or shuffle_seed:
+            raise ValueError("target_kl and shuffle_seed belong to shuffled minibatches: give minibatch_size")
+        return None
+    if int(minibatch_size) < 1:
+        raise ValueError("minibatch_size >= 1")
+    return dict(minibatch_samples=int(minibatch_size), seed=int(shuffle_seed), target_kl=float(target_kl or 0.0))
 
 
 def _rew_norm_options(normalize_rewards, rew_norm):
@@ -128,11 +145,16 @@ class PGTrainer:
     clip=..., count_cap=...).  kl_penalty: dict(kl_coef=..., kl_target=..., adaptive=..., vf_clip=...) adds RLlib's analytic KL
     penalty with its adaptive coefficient and the value-loss clip to the loss (StepEngine.pg_kl_*; csrc/adc_pg_kl.h);
     iteration() then also returns `kl`, `kl_coef` (the one the update used) and `vf_clip_fraction`, and state() carries the
-    coefficient."""
+    coefficient.  minibatch_size: minibatches of that many samples drawn from a new shuffle of the record every epoch
+    (StepEngine.pg_shuffle_*; csrc/adc_pg_shuffle.h) instead of `minibatches` env ranges - give one of the two; target_kl: an
+    update ends before the step of the first minibatch whose approx_kl exceeds 1.5 target_kl (Stable-Baselines3's rule);
+    shuffle_seed: 0 is the engine's seed.  iteration() then also returns `stopped`, `epochs_begun` and `steps_taken`; the
+    order's tick is the optimiser step count, so state() already carries all a resume needs."""
 
     def __init__(self, engine, policy, horizon, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
-                 rew_norm=None, kl_penalty=None, **config):
+                 rew_norm=None, kl_penalty=None, minibatch_size=None, target_kl=None, shuffle_seed=0, **config):
         _rew_norm_options(normalize_rewards, rew_norm)
+        self.shuffle = _shuffle_options(config, minibatch_size, target_kl, shuffle_seed)
         cfg = ppo(**config)
         if kl_penalty is None:                  # (a preset carries it among its keys: rllib_ppo())
             kl_penalty = cfg.pop("kl_penalty", None)
@@ -140,6 +162,8 @@ class PGTrainer:
             cfg.pop("kl_penalty", None)
         self.kl_penalty = _kl_options(kl_penalty)
         self.epochs, minibatches = int(cfg.pop("epochs")), int(cfg.pop("minibatches"))
+        if self.shuffle is not None:            # (env ranges stay available through StepEngine.pg_minibatch, one env at a time)
+            minibatches = engine.num_envs
         if minibatches < 1 or engine.num_envs % minibatches:
             raise ValueError("minibatches must divide the engine's envs")
         self.engine, self._template, self.horizon = engine, policy, int(horizon)
@@ -155,6 +179,8 @@ class PGTrainer:
             engine.rew_norm_init(**dict(rew_norm or {}))
         if self.kl_penalty is not None:
             engine.pg_kl_init(**self.kl_penalty)
+        if self.shuffle is not None:
+            engine.pg_shuffle_init(**self.shuffle)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -171,6 +197,9 @@ class PGTrainer:
         if self.kl_penalty is not None:
             kl = e.pg_kl_stats()
             stats.update(kl=kl["kl"], kl_coef=kl["kl_coef"], vf_clip_fraction=kl["vf_clip_fraction"])
+        if self.shuffle is not None:
+            sh = e.pg_shuffle_stats()
+            stats.update(stopped=bool(sh["stopped"]), epochs_begun=sh["epochs_begun"], steps_taken=sh["steps_taken"])
         if self.normalize_observations:     # (after the update: its bootstrap value is evaluated under the vectors of the record)
             e.obs_norm_update()
         self.history.append(stats)
@@ -218,7 +247,10 @@ class PGPopulationTrainer:
     may then carry different shift / scale: each member starts from its own); obs_norm: dict(min_std=..., count_cap=...).
     normalize_rewards: one running reward normaliser PER MEMBER (PGTrainer's), fed from the member's own envs under the
     member's own gamma; rew_norm: dict(min_std=..., clip=..., count_cap=...).  kl_penalty: PGTrainer's dict shared by all
-    members, or a list of one per member; every member has its own coefficient that adapts on its own either way."""
+    members, or a list of one per member; every member has its own coefficient that adapts on its own either way.
+    `minibatch_size` (equal in all members, instead of `minibatches`), `target_kl` and `shuffle_seed` in the members'
+    configurations: PGTrainer's shuffled minibatches, every member with its own seed and stopping on its own while the others
+    go on."""
 
     def __init__(self, engine, policies, horizon, configs, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
                  rew_norm=None, kl_penalty=None):
@@ -238,7 +270,13 @@ class PGPopulationTrainer:
                 break
             if p.shift is not None and not (np.array_equal(p.shift, policies[0].shift) and np.array_equal(p.scale, policies[0].scale)):
                 raise ValueError("PGPopulationTrainer: the normalisation vectors are shared by all members: the policies' must be equal")
-        cfgs = [ppo(**c) for c in configs]
+        shuffles = [_shuffle_options(c, c.get("minibatch_size"), c.get("target_kl"), c.get("shuffle_seed", 0)) for c in configs]
+        if any(s is None for s in shuffles) and any(s is not None for s in shuffles):
+            raise ValueError("PGPopulationTrainer: minibatch_size in some members' configurations and not in others")
+        self.shuffle = None if shuffles[0] is None else shuffles
+        if self.shuffle is not None and len({s["minibatch_samples"] for s in shuffles}) != 1:
+            raise ValueError("PGPopulationTrainer: minibatch_size must be equal in all members' configurations (the members move in lock-step)")
+        cfgs = [ppo(**{k: v for k, v in c.items() if k not in ("minibatch_size", "target_kl", "shuffle_seed")}) for c in configs]
         preset = [c.pop("kl_penalty", None) for c in cfgs]             # (a preset carries it among its keys: rllib_ppo())
         if kl_penalty is None and any(p is not None for p in preset):
             if any(p is None for p in preset):
@@ -252,6 +290,8 @@ class PGPopulationTrainer:
         if members < 1 or engine.num_envs % members:
             raise ValueError("the number of members must divide the engine's envs")
         n = engine.num_envs // members
+        if self.shuffle is not None:
+            minibatches = n
         if minibatches < 1 or n % minibatches:
             raise ValueError("minibatches must divide the envs of a member")
         self.engine, self.members, self.horizon = engine, members, int(horizon)
@@ -278,6 +318,8 @@ class PGPopulationTrainer:
             engine.pg_kl_init(per_member=self.kl_penalty)
         elif self.kl_penalty is not None:
             engine.pg_kl_init(**self.kl_penalty)
+        if self.shuffle is not None:
+            engine.pg_shuffle_init(per_member=self.shuffle * (members if len(self.shuffle) == 1 else 1))
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -293,6 +335,9 @@ class PGPopulationTrainer:
         if self.kl_penalty is not None:
             for st, kl in zip(stats, e.pg_kl_stats()):
                 st.update(kl=kl["kl"], kl_coef=kl["kl_coef"], vf_clip_fraction=kl["vf_clip_fraction"])
+        if self.shuffle is not None:
+            for st, sh in zip(stats, e.pg_shuffle_stats()):
+                st.update(stopped=bool(sh["stopped"]), epochs_begun=sh["epochs_begun"], steps_taken=sh["steps_taken"])
         if self.normalize_observations:
             e.obs_norm_update()
         self.history.append(stats)

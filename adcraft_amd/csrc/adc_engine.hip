@@ -52,6 +52,8 @@
 //        the k_pg_pop_* twins run the same bodies for all members of a learner population in one launch.
 //   parts/kernel_pg_kl.inc        the PPO learners' KL penalty and value-loss clip: the snapshot of the collecting distribution, the
 //        sample pass's instantiations under the add-on (adc_pg_kl.h).
+//   parts/kernel_pg_shuffle.inc   the PPO learners' shuffled sample-level minibatches: an epoch's order and record rows by a counter-addressed
+//        permutation, the gathered instantiations of the sample pass and the weight gradient (adc_pg_shuffle.h).
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
@@ -61,6 +63,7 @@
 //        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop normalise as they gather.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_kl_api.inc           the entry points of the KL penalty / value-clip add-on and what pg_api.inc calls of it.
+//   parts/pg_shuffle_api.inc      the entry points of the shuffled minibatches / target-KL stop add-on, the updates under it.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
@@ -89,6 +92,7 @@
 #include "adc_es.h"
 #include "adc_pg.h"
 #include "adc_pg_kl.h"
+#include "adc_pg_shuffle.h"
 #include "adc_td3.h"
 #include "adc_pbt.h"
 #include "adc_norm.h"
@@ -113,6 +117,7 @@ namespace adck {
 #include "parts/kernel_es.inc"
 #include "parts/kernel_pg.inc"
 #include "parts/kernel_pg_kl.inc"
+#include "parts/kernel_pg_shuffle.inc"
 #include "parts/kernel_td3.inc"
 #include "parts/kernel_td3_pop.inc"
 #include "parts/kernel_pbt.inc"
@@ -122,6 +127,7 @@ using namespace adck;
 
 #include "parts/host_api.inc"
 #include "parts/pg_kl_api.inc"
+#include "parts/pg_shuffle_api.inc"
 #include "parts/pg_api.inc"
 #include "parts/td3_api.inc"
 #include "parts/td3_pop_api.inc"

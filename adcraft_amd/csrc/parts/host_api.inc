@@ -130,6 +130,7 @@ struct adc_engine {
     adc_pg_config pg_cfg{};
     int64_t pg_steps = 0;               // optimiser steps taken
     int pg_mb = 0;                      // envs of a minibatch (the scratch's capacity)
+    size_t pg_slots = 0;                // samples of a minibatch the scratch holds per member: T * pg_mb, more under shuffled minibatches
     adc::PgShape pg_shape{};
     PgLayout pg_lay{};
     int pg_maxw = 0;
@@ -157,7 +158,19 @@ struct adc_engine {
     std::vector<PgKlMember> kl_mem;             // [members] the host's copy of kl_dmem (a population's)
     PgKlMember *kl_dmem = nullptr;
     float *kl_mean_old = nullptr, *kl_ls_old = nullptr;     // the snapshot: [T][N][A]; [T][N][A] (two heads) or [members][A]
-    float *kl_pieces = nullptr;                 // [members][T * minibatch envs][kPgKlPieces]
+    float *kl_pieces = nullptr;                 // [members][pg_slots][kPgKlPieces]
+    // the shuffled sample-level minibatches / target-KL stop add-on of the live PPO / A2C trainer (adc_engine_pg_shuffle_init;
+    // parts/kernel_pg_shuffle.inc, parts/pg_shuffle_api.inc; the law is adc_pg_shuffle.h).  Its device arrays are the trainer's too
+    bool sh_live = false, sh_epoch_ready = false;
+    int sh_mb = 0;                              // minibatch_samples
+    uint32_t sh_ns = 0;                         // positions per member of the order last drawn
+    std::vector<adc_pg_shuffle_config> sh_cfg;  // [members]
+    std::vector<PgShuffleMember> sh_mem;        // [members] the host's copy of sh_dmem: the keys, the ticks of the order last drawn
+    std::vector<adc_pg_shuffle_stats> sh_stats; // [members] of the update in progress / the last one
+    std::vector<uint8_t> sh_evaluated;          // [members] the member was live when the last minibatch ran
+    std::vector<int64_t> sh_last_count;         // [members] samples of the member's last evaluated minibatch
+    PgShuffleMember *sh_dmem = nullptr;
+    uint32_t *sh_order = nullptr, *sh_rows = nullptr;       // [members][T_max * envs of a member] each, packed [members][sh_ns]
     // off-policy training over a replay ring filled from the record (adc_engine_td3_init; parts/kernel_td3.inc, parts/td3_api.inc)
     bool have_td3 = false, td3_norm_set = false, td3_gap = false;
     bool td3_critic_set[2][4] = {{false, false, false, false}, {false, false, false, false}};
@@ -2901,6 +2914,13 @@ void kl_forget(adc_engine *e)
     e->kl_live = false;
     e->kl_cfg.clear(); e->kl_coef.clear(); e->kl_stats.clear(); e->kl_mem.clear();
 }
+// the shuffled-minibatches add-on ends (its arrays stay the trainer's until that goes, as the KL add-on's do)
+void sh_forget(adc_engine *e)
+{
+    e->sh_live = e->sh_epoch_ready = false;
+    e->sh_mb = 0; e->sh_ns = 0;
+    e->sh_cfg.clear(); e->sh_mem.clear(); e->sh_stats.clear(); e->sh_evaluated.clear(); e->sh_last_count.clear();
+}
 // the policy-gradient trainer goes with the policy and the record it was sized for
 void pg_drop(adc_engine *e)
 {
@@ -2908,6 +2928,8 @@ void pg_drop(adc_engine *e)
     pbt_forget(e, ADC_PBT_PG);
     kl_forget(e);
     e->kl_dmem = nullptr; e->kl_mean_old = e->kl_ls_old = e->kl_pieces = nullptr;      // (its arrays are among pg_allocs)
+    sh_forget(e);
+    e->sh_dmem = nullptr; e->sh_order = e->sh_rows = nullptr;
     mlp_free(e, e->pg_allocs);
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
     e->pg_steps = 0;
@@ -2933,6 +2955,7 @@ void learners_drop(adc_engine *e)
     norm_set_drop(e, e->on);
     norm_set_drop(e, e->rn);
     kl_forget(e);                       // (as the reward normaliser: a solo trainer survives, its add-ons do not)
+    sh_forget(e);
     // (a solo TD3 trainer survives learners and a population, refused while they are active; so do its normalisers, or its raw ring
     //  would be sampled without them afterwards.  A TD3 population's go with it, below)
     if (e->have_pg_pop) pg_drop(e);

@@ -63,6 +63,7 @@ struct PgMember {
     int clip;                               // the next update: clip on / off, the clip scale, the step's constants
     float scale;
     adc::EsStep step;
+    int stopped;                            // shuffled minibatches: the member's update has stopped (k_pg_pop_update_live passes it by)
 };
 
 constexpr int kPgBlock = 256;
@@ -247,16 +248,20 @@ __device__ __forceinline__ void pg_layer_back(const float *__restrict__ W, int n
 // forward, head, loss and backward of sample s = t * B + (env - n0) with the layers `nets`, log_std and the loss constants given;
 // the sample's scratch rows are row `slot` of p.acts / p.deltas / p.pieces.  kKl: with adc_pg_kl.h's KL penalty and value-loss clip
 // (k, kl; ls_old_at: where the member's vector starts in k.ls_old with the free head) - the instantiation without is the code
-// it was before there was one
-template <bool kKl>
+// it was before there was one.  kGather: the sample's record row is grows[s] (adc_pg_shuffle.h; parts/kernel_pg_shuffle.inc),
+// n0 and p.B are not read - again the instantiations without are the code they were
+template <bool kKl, bool kGather = false>
 __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *nets, const float *log_std, const adc::PgLoss &loss, int n0, size_t s,
-                                               size_t slot, const PgKlView &k, const adc::PgKl &kl, size_t ls_old_at)
+                                               size_t slot, const PgKlView &k, const adc::PgKl &kl, size_t ls_old_at,
+                                               const uint32_t *__restrict__ grows = nullptr)
 {
     extern __shared__ __align__(16) float pg_lds[];
     __shared__ float s_g, s_dv;
     const adc::PgShape &sh = p.sh;
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
-    const size_t row = (s / (size_t)p.B) * (size_t)p.N + (size_t)n0 + s % (size_t)p.B;
+    size_t row;
+    if constexpr (kGather) row = (size_t)grows[s];
+    else row = (s / (size_t)p.B) * (size_t)p.N + (size_t)n0 + s % (size_t)p.B;
     float *x = pg_lds, *ybase = x + D;
     float *y[2][adc::kMlpMaxLayers];
     {
@@ -401,8 +406,10 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_pop_sample(PgView p, const MlpL
 // one term's partials: gpart[chunk][flat0 + j * n_out + h] = the chunk's chain of x_s[j] * delta_s[h]; a 16 x 16 tile (blockIdx.x)
 // and a chunk (blockIdx.y) per workgroup
 constexpr int kPgTile = 16, kPgSlab = 64;
+// (kGather: the observation term's record row of sample s is grows[s]; B, N and n0 are not read)
+template <bool kGather = false>
 __device__ __forceinline__ void pg_wgrad_body(const PgTerm &t, long long S, int B, int N, int n0, const float *__restrict__ deltas, int nd,
-                                              double *__restrict__ gpart, int Q)
+                                              double *__restrict__ gpart, int Q, const uint32_t *__restrict__ grows = nullptr)
 {
     __shared__ float xs[kPgSlab][kPgTile + 1], ds[kPgSlab][kPgTile + 1];
     const int tid = threadIdx.x, jj = tid >> 4, hh = tid & 15;
@@ -420,8 +427,12 @@ __device__ __forceinline__ void pg_wgrad_body(const PgTerm &t, long long S, int 
                 const long long s = s0 + si;
                 float xv = 1.0f;                // (the bias row j = n_in; rows beyond it are never stored)
                 if (jx < t.n_in) {
-                    const uint32_t su = (uint32_t)s, day = su / (uint32_t)B;          // (S < 2^31: 32-bit division)
-                    const size_t row = t.obs ? (size_t)day * (size_t)N + (size_t)n0 + (size_t)(su - day * (uint32_t)B) : (size_t)s;
+                    size_t row;
+                    if constexpr (kGather) row = t.obs ? (size_t)grows[s] : (size_t)s;
+                    else {
+                        const uint32_t su = (uint32_t)s, day = su / (uint32_t)B;      // (S < 2^31: 32-bit division)
+                        row = t.obs ? (size_t)day * (size_t)N + (size_t)n0 + (size_t)(su - day * (uint32_t)B) : (size_t)s;
+                    }
                     xv = t.X[row * t.ldx + (size_t)jx];
                 }
                 xs[si][hh] = xv;
@@ -486,9 +497,8 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_update(PgLayout L, float *__res
 }
 // ... of every member (blockIdx.y) with its own clip scale and step constants (PgMember, set by the host before the launch);
 // theta, the moments and grad are [M][Q], L member 0's stores and a member's `stride` floats further each
-__global__ __launch_bounds__(kPgBlock) void k_pg_pop_update(PgLayout L, size_t stride, float *__restrict__ theta, float *__restrict__ mom_m,
-                                                            float *__restrict__ mom_v, const float *__restrict__ grad,
-                                                            const PgMember *__restrict__ mem)
+__device__ __forceinline__ void pg_pop_update_body(const PgLayout &L, size_t stride, float *__restrict__ theta, float *__restrict__ mom_m,
+                                                   float *__restrict__ mom_v, const float *__restrict__ grad, const PgMember *__restrict__ mem)
 {
     const int p = blockIdx.x * kPgBlock + threadIdx.x;
     if (p >= L.Q) return;
@@ -502,4 +512,10 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_pop_update(PgLayout L, size_t s
     mom_m[i] = m;
     mom_v[i] = v;
     *(pg_param_slot(L, p) + member * stride) = t1;
+}
+__global__ __launch_bounds__(kPgBlock) void k_pg_pop_update(PgLayout L, size_t stride, float *__restrict__ theta, float *__restrict__ mom_m,
+                                                            float *__restrict__ mom_v, const float *__restrict__ grad,
+                                                            const PgMember *__restrict__ mem)
+{
+    pg_pop_update_body(L, stride, theta, mom_m, mom_v, grad, mem);
 }

@@ -78,16 +78,23 @@ int pg_advantages_run(adc_engine *e)
     }
     if (e->kl_live)       // (the start of an update: the collecting distribution, adc_pg_kl.h)
         if (int rc = kl_snapshot_launch(e)) return rc;
+    if (e->sh_live) sh_update_begin(e);
     e->pg_adv_ready = true;
     return ADC_OK;
 }
 
-// one gradient and one step over the recorded days of the envs [n0, n0 + B)
-int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
+// one gradient and one step over the recorded days of the envs [n0, n0 + B) - or, g given (shuffled minibatches: adc_pg_shuffle.h),
+// over the g->S samples whose record rows are g->rows, with the early stop before the step
+int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out, const PgGather *g)
 {
     const adc::PgShape &sh = e->pg_shape;
     const int N = e->v.N, T = e->ro_t, na = adc::pg_acts_floats(sh), nd = adc::pg_deltas_floats(sh);
-    const long long S = (long long)T * B;
+    const long long S = g ? g->S : (long long)T * B;
+    if (g && e->sh_stats[0].stopped) {      // (the update has stopped: nothing to launch - the lock-step argument is the population's)
+        e->sh_evaluated[0] = 0;
+        if (out) *out = adc::PgStatsOut{};
+        return ADC_OK;
+    }
     PgView p{};
     p.sh = sh;
     p.loss = adc::PgLoss{e->pg_cfg.eps_clip, e->pg_cfg.vf_coef, e->pg_cfg.ent_coef};
@@ -99,7 +106,12 @@ int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
     p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
     p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
     const bool kl = e->kl_live;
-    if (kl)
+    if (g && kl)
+        hipLaunchKernelGGL(k_pg_gather_kl_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float), e->stream, p,
+                           kl_view(e), adc::PgKl{e->kl_coef[0], e->kl_cfg[0].vf_clip}, g->rows);
+    else if (g)
+        hipLaunchKernelGGL(k_pg_gather_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p, g->rows);
+    else if (kl)
         hipLaunchKernelGGL(k_pg_kl_sample, dim3((unsigned)S), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float), e->stream, p, kl_view(e),
                            adc::PgKl{e->kl_coef[0], e->kl_cfg[0].vf_clip});
     else
@@ -110,8 +122,12 @@ int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
         auto launch = [&](const float *X, size_t ldx, int n_in, int n_out, int obs) {
             PgTerm t{X, ldx, n_in, n_out, dof, flat, obs};
             const unsigned tiles = (unsigned)(((n_in + 1 + kPgTile - 1) / kPgTile) * ((n_out + kPgTile - 1) / kPgTile));
-            hipLaunchKernelGGL(k_pg_wgrad, dim3(tiles, (unsigned)pg_chunks(S)), dim3(kPgBlock), 0, e->stream, t, S, B, N, n0, e->pg_deltas, nd,
-                               e->pg_gpart, e->pg_lay.Q);
+            if (g)
+                hipLaunchKernelGGL(k_pg_gather_wgrad, dim3(tiles, (unsigned)pg_chunks(S)), dim3(kPgBlock), 0, e->stream, t, S, g->rows, e->pg_deltas, nd,
+                                   e->pg_gpart, e->pg_lay.Q);
+            else
+                hipLaunchKernelGGL(k_pg_wgrad, dim3(tiles, (unsigned)pg_chunks(S)), dim3(kPgBlock), 0, e->stream, t, S, B, N, n0, e->pg_deltas, nd,
+                                   e->pg_gpart, e->pg_lay.Q);
             flat += (n_in + 1) * n_out;
         };
         for (int net = 0; net < 2; ++net)
@@ -138,6 +154,10 @@ int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out)
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (kl) kl_stats_minibatch(e, 0, sums + adc::kPgSums, S);
     const adc::PgStatsOut st = adc::pg_stats_finish(sums, S);
+    if (g && !sh_minibatch_evaluated(e, 0, st.approx_kl, S)) {     // (stops here: no step, the count stays)
+        if (out) *out = st;
+        return ADC_OK;
+    }
     const bool clip = e->pg_cfg.max_grad_norm > 0.0f;
     const float scale = clip ? adc::pg_clip_scale(e->pg_cfg.max_grad_norm, st.grad_norm) : 1.0f;
     hipLaunchKernelGGL(k_pg_update, dim3((unsigned)((Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, e->pg_lay, e->pg_theta, e->pg_m,
@@ -211,7 +231,7 @@ ADC_EXPORT int adc_engine_pg_init(adc_engine *e, const adc_pg_config *cfg)
     e->pg_allocs.swap(fresh);
     e->pg_theta = theta; e->pg_m = m; e->pg_v = v; e->pg_grad = grad; e->pg_adv = adv; e->pg_ret = ret;
     e->pg_acts = acts; e->pg_deltas = deltas; e->pg_pieces = pieces; e->pg_part = part; e->pg_sums = sums; e->pg_gpart = gpart;
-    e->pg_cfg = *cfg; e->pg_mb = mb; e->pg_shape = sh; e->pg_lay = lay; e->pg_maxw = maxw;
+    e->pg_cfg = *cfg; e->pg_mb = mb; e->pg_slots = smax; e->pg_shape = sh; e->pg_lay = lay; e->pg_maxw = maxw;
     // theta starts as the device's weights
     hipLaunchKernelGGL(k_pg_params_copy, dim3((unsigned)((lay.Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, lay, e->pg_theta, 1);
     HIP_TRY(hipGetLastError());
@@ -260,7 +280,7 @@ ADC_EXPORT int adc_engine_pg_minibatch(adc_engine *e, int32_t env_begin, int32_t
     if (env_count > e->pg_mb) return fail(ADC_EINVAL, "env_count exceeds the configuration's minibatch_envs (the scratch was sized for it)");
     ENGINE_GUARD(e);
     adc::PgStatsOut o;
-    if ((rc = pg_minibatch_run(e, env_begin, env_count, &o))) return rc;
+    if ((rc = pg_minibatch_run(e, env_begin, env_count, &o, nullptr))) return rc;
     if (stats) pg_stats_fill(stats, o, e->pg_steps, (int64_t)e->ro_t * env_count);
     return ADC_OK;
 }
@@ -273,6 +293,7 @@ ADC_EXPORT int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats 
     if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
     ENGINE_GUARD(e);
     if ((rc = pg_advantages_run(e))) return rc;
+    if (e->sh_live) return sh_update_run(e, epochs, stats);
     const int N = e->v.N, mb = e->pg_mb, count = N / mb;
     adc::PgStatsOut mean{};
     KlEpoch kl;
@@ -281,7 +302,7 @@ ADC_EXPORT int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats 
         kl.begin(e);
         for (int i = 0; i < count; ++i) {
             adc::PgStatsOut o;
-            if ((rc = pg_minibatch_run(e, i * mb, mb, &o))) return rc;
+            if ((rc = pg_minibatch_run(e, i * mb, mb, &o, nullptr))) return rc;
             kl.add(e);
             acc.policy_loss = acc.policy_loss + o.policy_loss; acc.value_loss = acc.value_loss + o.value_loss; acc.entropy = acc.entropy + o.entropy;
             acc.approx_kl = acc.approx_kl + o.approx_kl; acc.clip_fraction = acc.clip_fraction + o.clip_fraction;
@@ -291,7 +312,7 @@ ADC_EXPORT int adc_engine_pg_update(adc_engine *e, int32_t epochs, adc_pg_stats 
         mean = adc::PgStatsOut{acc.policy_loss / c, acc.value_loss / c, acc.entropy / c, acc.approx_kl / c, acc.clip_fraction / c, acc.grad_norm / c,
                                acc.explained_variance / c};
     }
-    if (e->kl_live && (rc = kl_update_end(e, kl, count))) return rc;
+    if (e->kl_live && (rc = kl_update_end(e, kl))) return rc;
     if (stats) pg_stats_fill(stats, mean, e->pg_steps, (int64_t)e->ro_t * mb);
     return ADC_OK;
 }
@@ -411,17 +432,20 @@ int pgp_advantages_run(adc_engine *e)
     }
     if (e->kl_live)
         if ((rc = kl_snapshot_launch(e))) return rc;
+    if (e->sh_live) sh_update_begin(e);
     e->pg_adv_ready = true;
     return ADC_OK;
 }
 
-// minibatch `index` of every member: one gradient and one step each, in the same launches
-int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
+// minibatch `index` of every member: one gradient and one step each, in the same launches - or, g given (shuffled minibatches), over
+// the g->S samples of every member whose record rows are g->rows + member * g->stride; a member whose update has stopped is covered
+// by the launches and left as it is
+int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m, const PgGather *g)
 {
     const adc::PgShape &sh = e->pg_shape;
     const int N = e->v.N, T = e->ro_t, M = e->lrn_M, n = e->lrn_n, B = e->pg_mb, n0 = index * B;
     const int na = adc::pg_acts_floats(sh), nd = adc::pg_deltas_floats(sh), Q = e->lrn_lay.Q;
-    const long long S = (long long)T * B;
+    const long long S = g ? g->S : (long long)T * B;
     const unsigned chunks = (unsigned)pg_chunks(S);
     PgView p{};
     p.sh = sh;
@@ -431,7 +455,13 @@ int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
     p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
     p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
     const bool kl = e->kl_live;
-    if (kl)
+    if (g && kl)
+        hipLaunchKernelGGL(k_pg_pop_gather_kl_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float),
+                           e->stream, p, kl_view(e), e->lrn_tab, e->pgp_dmem, e->kl_dmem, g->rows, g->stride);
+    else if (g)
+        hipLaunchKernelGGL(k_pg_pop_gather_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw) * sizeof(float), e->stream, p,
+                           e->lrn_tab, e->pgp_dmem, g->rows, g->stride);
+    else if (kl)
         hipLaunchKernelGGL(k_pg_pop_kl_sample, dim3((unsigned)S, (unsigned)M), dim3(kPgBlock), pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float), e->stream, p,
                            kl_view(e), e->lrn_tab, e->pgp_dmem, e->kl_dmem, n);
     else
@@ -442,7 +472,11 @@ int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
         auto launch = [&](const float *X, size_t ldx, int n_in, int n_out, int obs) {
             PgTerm t{X, ldx, n_in, n_out, dof, flat, obs};
             const unsigned tiles = (unsigned)(((n_in + 1 + kPgTile - 1) / kPgTile) * ((n_out + kPgTile - 1) / kPgTile));
-            hipLaunchKernelGGL(k_pg_pop_wgrad, dim3(tiles, chunks, (unsigned)M), dim3(kPgBlock), 0, e->stream, t, S, B, N, n0, n, e->pg_deltas, nd, e->pg_gpart, Q);
+            if (g)
+                hipLaunchKernelGGL(k_pg_pop_gather_wgrad, dim3(tiles, chunks, (unsigned)M), dim3(kPgBlock), 0, e->stream, t, S, g->rows, g->stride, e->pg_deltas,
+                                   nd, e->pg_gpart, Q);
+            else
+                hipLaunchKernelGGL(k_pg_pop_wgrad, dim3(tiles, chunks, (unsigned)M), dim3(kPgBlock), 0, e->stream, t, S, B, N, n0, n, e->pg_deltas, nd, e->pg_gpart, Q);
             flat += (n_in + 1) * n_out;
         };
         for (int net = 0; net < 2; ++net)
@@ -470,10 +504,20 @@ int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m)
         pm.clip = c.max_grad_norm > 0.0f;
         pm.scale = pm.clip ? adc::pg_clip_scale(c.max_grad_norm, st.grad_norm) : 1.0f;
         pm.step = pg_step_of(c, e->pgp_steps[(size_t)m]);
-        if (out_m) out_m[m] = st;
-        if (kl) kl_stats_minibatch(e, m, e->pgp_host_sums.data() + (size_t)m * 16 + adc::kPgSums, S);
+        const bool over = g && e->sh_stats[(size_t)m].stopped;     // (stopped before this minibatch: its statistics are none, as solo)
+        if (out_m) out_m[m] = over ? adc::PgStatsOut{} : st;
+        if (kl && !over) kl_stats_minibatch(e, m, e->pgp_host_sums.data() + (size_t)m * 16 + adc::kPgSums, S);
+        if (g) pm.stopped = sh_minibatch_evaluated(e, m, st.approx_kl, S) ? 0 : 1;
     }
     if ((rc = pgp_members_upload(e))) return rc;
+    if (g) {
+        hipLaunchKernelGGL(k_pg_pop_update_live, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, e->pg_theta, e->pg_m,
+                           e->pg_v, e->pg_grad, e->pgp_dmem);
+        HIP_TRY(hipGetLastError());
+        for (int m = 0; m < M; ++m)
+            if (!e->pgp_mem[(size_t)m].stopped) e->pgp_steps[(size_t)m] += 1;
+        return ADC_OK;
+    }
     hipLaunchKernelGGL(k_pg_pop_update, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, e->pg_theta, e->pg_m, e->pg_v,
                        e->pg_grad, e->pgp_dmem);
     HIP_TRY(hipGetLastError());
@@ -525,7 +569,7 @@ ADC_EXPORT int adc_engine_pg_pop_init(adc_engine *e, const adc_pg_config *cfgs, 
     e->pg_allocs.swap(fresh);
     e->pg_theta = theta; e->pg_m = m; e->pg_v = v; e->pg_grad = grad; e->pg_adv = adv; e->pg_ret = ret;
     e->pg_acts = acts; e->pg_deltas = deltas; e->pg_pieces = pieces; e->pg_part = part; e->pg_sums = sums; e->pg_gpart = gpart;
-    e->pg_mb = mb; e->pg_shape = sh; e->pg_maxw = maxw;
+    e->pg_mb = mb; e->pg_slots = smax; e->pg_shape = sh; e->pg_maxw = maxw;
     e->pgp_dmem = dmem; e->pgp_part_stride = part_stride;
     e->pgp_cfg.assign(Ms, cfgs[0]);
     if (count > 1) e->pgp_cfg.assign(cfgs, cfgs + M);
@@ -573,7 +617,7 @@ ADC_EXPORT int adc_engine_pg_pop_minibatch(adc_engine *e, int32_t index, adc_pg_
     if (index < 0 || index >= e->lrn_n / e->pg_mb) return fail(ADC_EINVAL, "no such minibatch: 0 to envs of a member / minibatch_envs - 1");
     ENGINE_GUARD(e);
     std::vector<adc::PgStatsOut> o((size_t)e->lrn_M);
-    if ((rc = pgp_minibatch_run(e, index, o.data()))) return rc;
+    if ((rc = pgp_minibatch_run(e, index, o.data(), nullptr))) return rc;
     if (stats_m)
         for (int m = 0; m < e->lrn_M; ++m) pg_stats_fill(stats_m + m, o[(size_t)m], e->pgp_steps[(size_t)m], (int64_t)e->ro_t * e->pg_mb);
     return ADC_OK;
@@ -587,6 +631,7 @@ ADC_EXPORT int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_st
     if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
     ENGINE_GUARD(e);
     if ((rc = pgp_advantages_run(e))) return rc;
+    if (e->sh_live) return sh_update_run(e, epochs, stats_m);
     const int M = e->lrn_M, count = e->lrn_n / e->pg_mb;
     std::vector<adc::PgStatsOut> o((size_t)M), acc((size_t)M), mean((size_t)M);
     KlEpoch kl;
@@ -594,7 +639,7 @@ ADC_EXPORT int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_st
         acc.assign((size_t)M, adc::PgStatsOut{});
         kl.begin(e);
         for (int i = 0; i < count; ++i) {
-            if ((rc = pgp_minibatch_run(e, i, o.data()))) return rc;
+            if ((rc = pgp_minibatch_run(e, i, o.data(), nullptr))) return rc;
             kl.add(e);
             for (size_t m = 0; m < (size_t)M; ++m) {
                 adc::PgStatsOut &a = acc[m];
@@ -610,7 +655,7 @@ ADC_EXPORT int adc_engine_pg_pop_update(adc_engine *e, int32_t epochs, adc_pg_st
                                       a.explained_variance / c};
         }
     }
-    if (e->kl_live && (rc = kl_update_end(e, kl, count))) return rc;       // (every member's adaptation: one small upload)
+    if (e->kl_live && (rc = kl_update_end(e, kl))) return rc;       // (every member's adaptation: one small upload)
     if (stats_m)
         for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, mean[(size_t)m], e->pgp_steps[(size_t)m], (int64_t)e->ro_t * e->pg_mb);
     return ADC_OK;

@@ -46,21 +46,31 @@ void kl_stats_minibatch(adc_engine *e, int m, const double *sums2, long long S)
 }
 
 // an update's running means of the members' minibatch statistics, and its end: the last epoch's means, the adaptation
+// (live: under shuffled minibatches, the members whose update has not stopped - a stopped member keeps the sums and the count of
+//  the last epoch it began; NULL: all members)
 struct KlEpoch {
     std::vector<double> kl, frac;
-    void begin(const adc_engine *e) { kl.assign(e->kl_stats.size(), 0.0); frac.assign(e->kl_stats.size(), 0.0); }
-    void add(const adc_engine *e)
+    std::vector<int> n;
+    void begin(const adc_engine *e, const uint8_t *live = nullptr)
     {
-        for (size_t m = 0; m < kl.size(); ++m) { kl[m] = kl[m] + e->kl_stats[m].kl; frac[m] = frac[m] + e->kl_stats[m].vf_clip_fraction; }
+        const size_t M = e->kl_stats.size();
+        kl.resize(M, 0.0); frac.resize(M, 0.0); n.resize(M, 0);
+        for (size_t m = 0; m < M; ++m)
+            if (!live || live[m]) { kl[m] = 0.0; frac[m] = 0.0; n[m] = 0; }
+    }
+    void add(const adc_engine *e, const uint8_t *live = nullptr)
+    {
+        for (size_t m = 0; m < kl.size(); ++m)
+            if (!live || live[m]) { kl[m] = kl[m] + e->kl_stats[m].kl; frac[m] = frac[m] + e->kl_stats[m].vf_clip_fraction; n[m] += 1; }
     }
 };
-int kl_update_end(adc_engine *e, const KlEpoch &last, int minibatches)
+int kl_update_end(adc_engine *e, const KlEpoch &last)
 {
     bool changed = false;
     for (size_t m = 0; m < e->kl_stats.size(); ++m) {
         adc_pg_kl_stats &st = e->kl_stats[m];
-        st.kl = last.kl[m] / (double)minibatches;
-        st.vf_clip_fraction = last.frac[m] / (double)minibatches;
+        st.kl = last.kl[m] / (double)last.n[m];
+        st.vf_clip_fraction = last.frac[m] / (double)last.n[m];
         st.kl_coef = e->kl_coef[m];
         st.kl_coef_next = adc::pg_kl_adapt(adc::pg_kl_adapt_of(e->kl_cfg[m]), e->kl_coef[m], st.kl);
         changed = changed || st.kl_coef_next != e->kl_coef[m];
@@ -107,7 +117,7 @@ ADC_EXPORT int adc_engine_pg_kl_init(adc_engine *e, const adc_pg_kl_config *cfgs
         PgKlMember *dmem = nullptr;
         int rc;
         if ((rc = mlp_alloc(e, e->pg_allocs, &mean_old, tna)) || (rc = mlp_alloc(e, e->pg_allocs, &ls_old, sh.two_heads ? tna : (size_t)M * (size_t)sh.A)) ||
-            (rc = mlp_alloc(e, e->pg_allocs, &pieces, (size_t)M * (size_t)e->ro_T * (size_t)e->pg_mb * (size_t)adc::kPgKlPieces)) ||
+            (rc = mlp_alloc(e, e->pg_allocs, &pieces, (size_t)M * e->pg_slots * (size_t)adc::kPgKlPieces)) ||
             (rc = mlp_alloc(e, e->pg_allocs, &dmem, (size_t)M)))
             return rc;
         e->kl_mean_old = mean_old; e->kl_ls_old = ls_old; e->kl_pieces = pieces; e->kl_dmem = dmem;

@@ -961,6 +961,64 @@ class StepEngine:
         check(self._lib.adc_engine_pg_kl_old_dist_fetch(self._h, mean.ctypes.data, ls.ctypes.data))
         return mean, ls
 
+    # ---- PPO's shuffled sample-level minibatches and target-KL early stop (parts/kernel_pg_shuffle.inc; csrc/adc_pg_shuffle.h) ----
+    @classmethod
+    def pg_shuffle_config(cls, minibatch_samples=64, seed=0, target_kl=0.0):
+        """an adc_pg_shuffle_config: minibatch_samples recorded samples per minibatch, drawn from a new permutation of a learner's
+        samples every epoch (RLlib's sgd_minibatch_size, Stable-Baselines3's batch_size); seed 0: the engine's; target_kl > 0 ends
+        an update before the step of the first minibatch whose approx_kl exceeds 1.5 target_kl (0: never)"""
+        c = _ffi.PGShuffleConfig()
+        c.struct_size = C.sizeof(_ffi.PGShuffleConfig)
+        c.minibatch_samples, c.seed, c.target_kl = int(minibatch_samples), int(seed), float(target_kl)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_pg_shuffle_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad shuffled-minibatch configuration").decode())
+        return c
+
+    def pg_shuffle_init(self, per_member=None, **options):
+        """shuffled sample-level minibatches on the live PPO / A2C trainer (pg_init or pg_pop_init first); options as
+        pg_shuffle_config's, shared by all learners - or per_member: a list of such dicts, one per learner of a population
+        (minibatch_samples equal in all).  pg_update / pg_pop_update then run over them and honour target_kl."""
+        if per_member is not None and options:
+            raise ValueError("pg_shuffle_init: options shared by all members, or per_member, not both")
+        built = [self.pg_shuffle_config(**o) for o in per_member] if per_member is not None else [self.pg_shuffle_config(**options)]
+        arr = (_ffi.PGShuffleConfig * len(built))(*built)
+        check(self._lib.adc_engine_pg_shuffle_init(self._h, arr, len(built)))
+        self._pg_shuffle_members = max(getattr(self, "_learners", 0), 1)
+
+    def pg_shuffle_epoch(self):
+        """draw the order of a new epoch for every learner (after pg_advantages / pg_pop_advantages)"""
+        check(self._lib.adc_engine_pg_shuffle_epoch(self._h))
+
+    def pg_shuffle_minibatch(self, index):
+        """minibatch `index` of the epoch's order: one gradient and - unless target_kl stops the learner - one step; the
+        statistics dict, a list of them under a population"""
+        st = (_ffi.PGStats * getattr(self, "_pg_shuffle_members", 1))()
+        check(self._lib.adc_engine_pg_shuffle_minibatch(self._h, int(index), st))
+        out = [self._pg_stats(x) for x in st]
+        return out if getattr(self, "_learners", 0) else out[0]
+
+    def pg_shuffle_order(self):
+        """the order last drawn: (order, rows), uint32 [members, n_s] each - position i holds sample order[m, i] of learner m,
+        which is row rows[m, i] of the record flattened to [T * N].  Refused once the advantages are stale (a day recorded,
+        rollout_reset, a changed configuration): the order belongs to the days recorded when it was drawn"""
+        self.pg_shuffle_stats()                 # (refused here, by the add-on's own message, when it does not live)
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        M = getattr(self, "_pg_shuffle_members", 1)
+        n_s = t.value * (self.num_envs // M)
+        order, rows = np.zeros((M, n_s), np.uint32), np.zeros((M, n_s), np.uint32)
+        check(self._lib.adc_engine_pg_shuffle_order_fetch(self._h, order.ctypes.data, rows.ctypes.data))
+        return order, rows
+
+    def pg_shuffle_stats(self):
+        """of the last update (or the one in progress): dict of epochs_begun, minibatches_evaluated, steps_taken, stopped - a list
+        of them, one per learner, under a population"""
+        st = (_ffi.PGShuffleStats * getattr(self, "_pg_shuffle_members", 1))()
+        check(self._lib.adc_engine_pg_shuffle_stats(self._h, st))
+        out = [{k: getattr(x, k) for k, _ in _ffi.PGShuffleStats._fields_} for x in st]
+        return out if getattr(self, "_learners", 0) else out[0]
+
     # ---- off-policy (TD3) training over a replay ring filled from the record (parts/kernel_td3.inc; baselines/td3_trainer.py) ----
     TD3_OPTIMISERS = {"adam": _ffi.TD3_ADAM, "sgd": _ffi.TD3_SGD}
 

@@ -18,9 +18,14 @@ coefficient adapts to --kl-target after every update, and with --vf-clip C a sam
 (StepEngine.pg_kl_*; csrc/adc_pg_kl.h).  --rllib takes the whole configuration of the paper's PPO agent as far as this trainer
 expresses it (pg_trainer.rllib_ppo(): its docstring says what it leaves out); --lr and --reward-scale then apply only when given.
 
+With --minibatch-size S an update's minibatches are S samples drawn from a new shuffle of the record every epoch instead of four
+env ranges (StepEngine.pg_shuffle_*; csrc/adc_pg_shuffle.h), and --target-kl T ends an update before the step of the first
+minibatch whose approx_kl exceeds 1.5 T.  --rllib turns on the reference's minibatch size of 64 unless --minibatch-size says otherwise.
+
 Usage: python examples/train_mlp_policy_ppo.py [--iterations 100] [--algo ppo|a2c] [--num-envs 4096] [--num-keywords 100]
                                                [--normalize-observations] [--normalize-rewards]
                                                [--kl-penalty COEF [--kl-target T]] [--vf-clip C] [--rllib]
+                                               [--minibatch-size S [--target-kl T]]
 """
 import argparse
 import sys
@@ -74,6 +79,8 @@ def main():
     ap.add_argument("--kl-target", type=float, default=0.01, metavar="T", help="the KL the coefficient adapts to")
     ap.add_argument("--vf-clip", type=float, default=0.0, metavar="C", help="cap of a sample's squared value error (0: off)")
     ap.add_argument("--rllib", action="store_true", help="the paper's PPO configuration (pg_trainer.rllib_ppo())")
+    ap.add_argument("--minibatch-size", type=int, default=None, metavar="S", help="shuffled minibatches of S samples (--rllib: 64)")
+    ap.add_argument("--target-kl", type=float, default=None, metavar="T", help="end an update when a minibatch's approx_kl exceeds 1.5 T")
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device, from identity vectors")
@@ -87,8 +94,10 @@ def main():
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(synthetic.implicit_keyword_planes(N, K, seed=1, mean_volume=args.mean_volume))
     eng.reset()
+    if args.target_kl is not None and args.minibatch_size is None and not args.rllib:
+        ap.error("--target-kl needs --minibatch-size")
     if args.rllib:
-        config = pg_trainer.rllib_ppo(**{k: v for k, v in (("lr", args.lr), ("reward_scale", args.reward_scale)) if v is not None})
+        config = pg_trainer.rllib_ppo(minibatch_size=64 if args.minibatch_size is None else args.minibatch_size, **{k: v for k, v in (("lr", args.lr), ("reward_scale", args.reward_scale)) if v is not None})
     else:
         config = getattr(pg_trainer, args.algo)(lr=1e-3 if args.lr is None else args.lr, reward_scale=0.1 if args.reward_scale is None else args.reward_scale)
     kl = dict(config.get("kl_penalty") or {})
@@ -99,6 +108,11 @@ def main():
     if kl and "kl_coef" not in kl:          # (the value clip alone: no penalty)
         kl.update(kl_coef=0.0, adaptive=False)
     config["kl_penalty"] = kl or None
+    if args.minibatch_size is not None and not args.rllib:
+        del config["minibatches"]
+        config["minibatch_size"] = args.minibatch_size
+    if args.target_kl is not None:
+        config["target_kl"] = args.target_kl
     policy = with_value_network(default_policy(K, days=days), (32, 32))
     if args.normalize_observations:
         policy.shift, policy.scale = np.zeros_like(policy.shift), np.ones_like(policy.scale)

@@ -723,6 +723,52 @@ int adc_engine_pg_kl_coef_set(adc_engine *e, int32_t member, float coef);
 /* the snapshot of the last advantages call: mean_old_tna [T][N][A]; ls_old [T][N][A] (two heads) or [members][A] (either may be NULL) */
 int adc_engine_pg_kl_old_dist_fetch(adc_engine *e, float *mean_old_tna, float *ls_old);
 
+/* ---- PPO with shuffled sample-level minibatches and target-KL early stopping (the law is csrc/adc_pg_shuffle.h) ----------------
+ * An add-on to a live PPO / A2C trainer (adc_engine_pg_init or adc_engine_pg_pop_init), attached after it in either order with
+ * the KL add-on and the normalisers.  Without it a minibatch is every recorded day of a contiguous env range; with it a member's
+ * n_s = T * n recorded samples (n its envs) are visited in a new pseudo-random order every epoch and a minibatch is
+ * minibatch_samples consecutive positions of that order - RLlib's sgd_minibatch_size, Stable-Baselines3's batch_size - the last
+ * of an epoch possibly short.  The order is a counter-addressed permutation (a 4-round Feistel network over the engine's Philox
+ * stream with cycle walking): no sort, no state; its tick is the low 32 bits of the member's optimiser step count when the order
+ * is drawn, so adc_engine_pg_state_get / _set (and the _pg_pop_ ones) carry all a bit-for-bit resume needs, and
+ * adc_engine_pg_pop_copy and a PBT round need nothing new.  adc_pg_config, adc_pg_stats, adc_pg_kl_* and every existing entry
+ * point keep their layout and meaning; without adc_engine_pg_shuffle_init every call launches the kernels it launched, and while
+ * the add-on lives adc_engine_pg_minibatch / _pg_pop_minibatch over env ranges keep working.
+ * While the add-on lives adc_engine_pg_update / _pg_pop_update run: the advantages once (and the KL add-on's snapshot), then per
+ * epoch a new order and its ceil(n_s / minibatch_samples) minibatches.  target_kl > 0: a minibatch whose approx_kl (adc_pg_stats)
+ * exceeds 1.5 target_kl ends the member's update BEFORE its optimiser step - the step count does not advance; under a population
+ * the other members go on in the same launches and the stopped member's parameters and moments stay bit for bit.  The statistics
+ * of an update are the means over the evaluated minibatches of the last epoch the member began, the stopping one included (so is
+ * what the KL add-on adapts on); adc_pg_stats.samples is the last evaluated minibatch's count.
+ * A caller may drive the minibatches itself: adc_engine_pg_advantages / _pg_pop_advantages (begins an update: no member has
+ * stopped, no order is drawn), adc_engine_pg_shuffle_epoch (a new order for every member), adc_engine_pg_shuffle_minibatch(index)
+ * in any order of indices; a member that has stopped is left as it is until the next advantages, and its adc_pg_stats of a later
+ * minibatch are zero but for steps and samples (solo nothing is launched for it; under a population the launches cover it).
+ * adc_engine_pg_shuffle_init makes sure the scratch holds max(horizon x minibatch_envs, minibatch_samples) samples per member
+ * (allocated before the old arrays go: a refused allocation leaves the engine as it was).  It is refused with ADC_ESTATE (the
+ * engine stays usable) without a live PPO / A2C trainer or while a TD3 trainer lives, with ADC_EINVAL when count is neither 1 nor
+ * the number of members, the members' minibatch_samples differ, minibatch_samples exceeds horizon x envs of a member, or a
+ * configuration fails adc_pg_shuffle_config_check.  adc_engine_pg_shuffle_minibatch is refused with ADC_ESTATE before the
+ * advantages or before adc_engine_pg_shuffle_epoch since them, with ADC_EINVAL for an index outside the epoch.  The add-on does
+ * not survive what the KL add-on does not survive. */
+typedef struct adc_pg_shuffle_config {
+    uint32_t struct_size;          /* sizeof(adc_pg_shuffle_config) */
+    int32_t minibatch_samples;     /* >= 1; equal in all members; at most horizon x envs of a member */
+    uint64_t seed;                 /* 0: the engine's */
+    float target_kl;               /* >= 0, finite; 0: never stop */
+} adc_pg_shuffle_config;
+typedef struct adc_pg_shuffle_stats {
+    int32_t epochs_begun, minibatches_evaluated, steps_taken, stopped;      /* of the last update */
+} adc_pg_shuffle_stats;
+int adc_pg_shuffle_config_check(const adc_pg_shuffle_config *cfg, const char **message);      /* host only */
+int adc_engine_pg_shuffle_init(adc_engine *e, const adc_pg_shuffle_config *cfgs, int32_t count);      /* count 1 or members */
+int adc_engine_pg_shuffle_epoch(adc_engine *e);                /* draw the order of a new epoch for every member */
+int adc_engine_pg_shuffle_minibatch(adc_engine *e, int32_t index, adc_pg_stats *stats_m);     /* [1] or [M]; honours target_kl */
+/* the order last drawn: the sample indices and their record rows, [members][n_s] each (either may be NULL), n_s of the days recorded;
+ * ADC_ESTATE once the advantages are stale (a day recorded, adc_engine_rollout_reset, a changed configuration) or before an order */
+int adc_engine_pg_shuffle_order_fetch(adc_engine *e, uint32_t *order, uint32_t *rows);
+int adc_engine_pg_shuffle_stats(adc_engine *e, adc_pg_shuffle_stats *stats_m);         /* [1] or [M] */
+
 /* ---- off-policy training on the device: a replay ring, twin critics, TD3 (the law is csrc/adc_td3.h) --------------------------
  * The actor is the policy network given to adc_engine_mlp_init with the free log_std[A] head; its mean is TD3's deterministic
  * action, and the stochastic act mean + exp(log_std) * z is the exploration (set log_std = log(sigma); TD3 never trains it; a
@@ -1218,6 +1264,10 @@ int adc_pg_kl_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const a
                         int32_t ls_old_per_sample, float *grad_q, double *sums10, double *sums_kl2, adc_pg_stats *stats,
                         adc_pg_kl_stats *kl_stats);
 int adc_pg_kl_adapt_host(const adc_pg_kl_config *kl, float coef, double kl_mean, float *coef_next);
+/* adc_pg_shuffle.h on the host: the order of n_s samples for `tick` under the shuffle key of `seed` (order_out [n_s]: position i
+ * holds sample sigma(i)); whether a minibatch with approx_kl ends the update under target_kl (*stop 1 or 0) */
+int adc_pg_shuffle_order_host(uint64_t seed, int64_t n_s, uint32_t tick, uint32_t *order_out);
+int adc_pg_shuffle_stop_host(double approx_kl, float target_kl, int32_t *stop);
 /* off-policy training on the host: the same code as the device's (adc_td3.h).  `seed` is the effective seed (the configuration's,
  * or the engine's when that is 0).  The batch arrays hold the gathered elements in order: x_bd / x2_bd [count][D], a_ba [count][A].
  * shift_a / scale_a: the action normalisation, both NULL for none.  target: y_b [count] from the target actor theta_target_p and

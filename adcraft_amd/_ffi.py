@@ -341,6 +341,9 @@ def lib():
         "adc_engine_pg_shuffle_stats": ([vp, C.POINTER(PGShuffleStats)], C.c_int),
         "adc_pg_shuffle_order_host": ([C.c_uint64, i64, C.c_uint32, vp], C.c_int),
         "adc_pg_shuffle_stop_host": ([f64, f32, C.POINTER(i32)], C.c_int),
+        "adc_pg_decide_host": ([C.POINTER(PGConfig), f32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)], C.c_int),
+        "adc_engine_pg_update_queued": ([vp, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_pg_pop_update_queued": ([vp, i32, C.POINTER(PGStats)], C.c_int),
         "adc_engine_td3_init": ([vp, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_td3_set_action_norm": ([vp, vp, vp], C.c_int),

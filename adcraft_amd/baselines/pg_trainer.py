@@ -55,7 +55,7 @@ def a2c(**overrides):
     return cfg
 
 
-def rllib_ppo(minibatch_size=None, **overrides):
+def rllib_ppo(minibatch_size=None, queued_update=False, **overrides):
     """The PPO configuration of the paper's experiments (RLlib's PPO as the reference's sem_ppo_config sets it), as far as this
     trainer expresses it: gamma 0.995, lambda 0.95, lr 1e-4, clip range 0.5, 20 epochs, and RLlib's loss terms - the adaptive KL
     penalty (kl_coeff 1.0, kl_target 0.01) and the value-loss clip (vf_clip_param 10.0) - through `kl_penalty`.  vf_coef is 2.0
@@ -64,12 +64,16 @@ def rllib_ppo(minibatch_size=None, **overrides):
     batch every epoch (csrc/adc_pg_shuffle.h) instead of `minibatches` env ranges; without it the preset keeps this trainer's
     own 4 env-range minibatches.  With it RLlib's KL - the mean over the minibatches of an epoch - is what ours is.  What
     remains a configuration choice rather than a difference of the learner: RLlib does not normalise advantages per update
-    (normalize_advantages=False) and clips gradients only when asked to (max_grad_norm=0)."""
+    (normalize_advantages=False) and clips gradients only when asked to (max_grad_norm=0).
+    queued_update=True: the trainers run every update as one chain on the device with one host wait (StepEngine.pg_update's
+    queued=True) - with 64-sample minibatches an update is hundreds of small steps, and the bits are the same."""
     cfg = ppo(gamma=0.995, lam=0.95, lr=1e-4, eps_clip=0.5, epochs=20, vf_coef=2.0,
               kl_penalty=dict(kl_coef=1.0, kl_target=0.01, adaptive=True, vf_clip=10.0))
     if minibatch_size is not None:
         del cfg["minibatches"]
         cfg["minibatch_size"] = int(minibatch_size)
+    if queued_update:
+        cfg["queued_update"] = True
     cfg.update(overrides)
     return cfg
 
@@ -149,11 +153,13 @@ class PGTrainer:
     (StepEngine.pg_shuffle_*; csrc/adc_pg_shuffle.h) instead of `minibatches` env ranges - give one of the two; target_kl: an
     update ends before the step of the first minibatch whose approx_kl exceeds 1.5 target_kl (Stable-Baselines3's rule);
     shuffle_seed: 0 is the engine's seed.  iteration() then also returns `stopped`, `epochs_begun` and `steps_taken`; the
-    order's tick is the optimiser step count, so state() already carries all a resume needs."""
+    order's tick is the optimiser step count, so state() already carries all a resume needs.  queued_update: every update is
+    enqueued as one chain with one host wait (StepEngine.pg_update(queued=True)): the same bits, no host round trip per step."""
 
     def __init__(self, engine, policy, horizon, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
-                 rew_norm=None, kl_penalty=None, minibatch_size=None, target_kl=None, shuffle_seed=0, **config):
+                 rew_norm=None, kl_penalty=None, minibatch_size=None, target_kl=None, shuffle_seed=0, queued_update=False, **config):
         _rew_norm_options(normalize_rewards, rew_norm)
+        self.queued_update = bool(queued_update)
         self.shuffle = _shuffle_options(config, minibatch_size, target_kl, shuffle_seed)
         cfg = ppo(**config)
         if kl_penalty is None:                  # (a preset carries it among its keys: rllib_ppo())
@@ -193,7 +199,7 @@ class PGTrainer:
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         if self.normalize_rewards:          # (before the update: this record's rewards are scaled by statistics that include them)
             e.rew_norm_update()
-        stats = e.pg_update(self.epochs)
+        stats = e.pg_update(self.epochs, queued=True) if self.queued_update else e.pg_update(self.epochs)
         if self.kl_penalty is not None:
             kl = e.pg_kl_stats()
             stats.update(kl=kl["kl"], kl_coef=kl["kl_coef"], vf_clip_fraction=kl["vf_clip_fraction"])
@@ -250,13 +256,16 @@ class PGPopulationTrainer:
     members, or a list of one per member; every member has its own coefficient that adapts on its own either way.
     `minibatch_size` (equal in all members, instead of `minibatches`), `target_kl` and `shuffle_seed` in the members'
     configurations: PGTrainer's shuffled minibatches, every member with its own seed and stopping on its own while the others
-    go on."""
+    go on.  queued_update (or `queued_update` in the members' configurations, as rllib_ppo(queued_update=True) carries it): every
+    update is enqueued as one chain with one host wait (StepEngine.pg_pop_update(queued=True)): the same bits."""
 
     def __init__(self, engine, policies, horizon, configs, agent_seeds=None, normalize_observations=False, obs_norm=None, normalize_rewards=False,
-                 rew_norm=None, kl_penalty=None):
+                 rew_norm=None, kl_penalty=None, queued_update=False):
         _rew_norm_options(normalize_rewards, rew_norm)
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         configs = [configs] if isinstance(configs, dict) else list(configs)
+        self.queued_update = bool(queued_update) or any(c.get("queued_update") for c in configs)      # (one chain covers all members)
+        configs = [{k: v for k, v in c.items() if k != "queued_update"} for c in configs]
         if not policies or not configs:
             raise ValueError("PGPopulationTrainer: at least one policy and one configuration")
         members = max(len(policies), len(configs))
@@ -331,7 +340,7 @@ class PGPopulationTrainer:
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         if self.normalize_rewards:
             e.rew_norm_update()
-        stats = e.pg_pop_update(self.epochs)
+        stats = e.pg_pop_update(self.epochs, queued=True) if self.queued_update else e.pg_pop_update(self.epochs)
         if self.kl_penalty is not None:
             for st, kl in zip(stats, e.pg_kl_stats()):
                 st.update(kl=kl["kl"], kl_coef=kl["kl_coef"], vf_clip_fraction=kl["vf_clip_fraction"])

@@ -54,6 +54,8 @@
 //        sample pass's instantiations under the add-on (adc_pg_kl.h).
 //   parts/kernel_pg_shuffle.inc   the PPO learners' shuffled sample-level minibatches: an epoch's order and record rows by a counter-addressed
 //        permutation, the gathered instantiations of the sample pass and the weight gradient (adc_pg_shuffle.h).
+//   parts/kernel_pg_queued.inc    the PPO / A2C learners' queued update: the stop and the clip scale decided on the device (k_pg_decide), the
+//        chain's kernels that read a member's control block and pass a stopped member by.
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
@@ -118,6 +120,7 @@ namespace adck {
 #include "parts/kernel_pg.inc"
 #include "parts/kernel_pg_kl.inc"
 #include "parts/kernel_pg_shuffle.inc"
+#include "parts/kernel_pg_queued.inc"
 #include "parts/kernel_td3.inc"
 #include "parts/kernel_td3_pop.inc"
 #include "parts/kernel_pbt.inc"

@@ -234,7 +234,9 @@ inline double pg_csum(int64_t n, Term step)      // step(part, i) -> part advanc
 }
 
 // ---- clip and step ----------------------------------------------------------------------------------------------------------------
-inline float pg_clip_scale(float max_grad_norm, double norm)
+// (ADC_HD: k_pg_decide of parts/kernel_pg_queued.inc takes the host's decision on the device - one float64 sum, one float64
+//  quotient, one comparison, one rounding to float32: the host's bits)
+ADC_HD float pg_clip_scale(float max_grad_norm, double norm)
 {
     const double q = (double)max_grad_norm / (norm + 1e-6);
     return (float)(q < 1.0 ? q : 1.0);
@@ -261,6 +263,10 @@ ADC_HD float pg_apply(const EsStep &s, float theta, float g, float &m, float &v)
 struct PgStatsOut {
     double policy_loss, value_loss, entropy, approx_kl, clip_fraction, grad_norm, explained_variance;
 };
+// the two statistics a step's decisions need - the target-KL stop and the norm clip - on either side: one float64 division, one
+// float64 square root (correctly rounded on the device as on the host: no fast-math)
+ADC_HD double pg_stats_approx_kl(const double *sums, int64_t S) { return sums[kPgKl] / (double)S; }
+ADC_HD double pg_stats_grad_norm(const double *sums) { return __builtin_sqrt(sums[9]); }
 inline PgStatsOut pg_stats_finish(const double *sums, int64_t S)
 {
     const double n = (double)S;
@@ -268,12 +274,12 @@ inline PgStatsOut pg_stats_finish(const double *sums, int64_t S)
     o.policy_loss = sums[kPgPolLoss] / n;
     o.value_loss = sums[kPgValLoss] / n;
     o.entropy = sums[kPgEntropy] / n;
-    o.approx_kl = sums[kPgKl] / n;
+    o.approx_kl = pg_stats_approx_kl(sums, S);
     o.clip_fraction = sums[kPgClipped] / n;
     const double mr = sums[kPgRet] / n, me = sums[kPgErr] / n, qr = sums[7] / n, qe = sums[8] / n;
     const double vr = qr - mr * mr, ve = qe - me * me;
     o.explained_variance = 1.0 - ve / vr;
-    o.grad_norm = std::sqrt(sums[9]);
+    o.grad_norm = pg_stats_grad_norm(sums);
     return o;
 }
 

@@ -33,6 +33,7 @@
 #pragma once
 #include "adc_law.h"
 #include "adc_mlp.h"
+#include "adc_pg.h"
 #include <cstdint>
 
 namespace adc {
@@ -81,6 +82,26 @@ ADC_HD bool pg_shuffle_stop(double approx_kl, float target_kl)
     if (!(target_kl > 0.0f)) return false;
     const double bound = 1.5 * (double)target_kl;
     return approx_kl > bound;
+}
+
+// what the end of a minibatch decides before its optimiser step, from the minibatch's sums (adc_pg.h's kPgSums) over S samples: the
+// early stop above (stop_rule: shuffled minibatches are live - env-block minibatches never stop), then the norm clip's scale.  The
+// host-driven update takes it on the host between two launches, the queued update (parts/kernel_pg_queued.inc: k_pg_decide) on the
+// device: the same code, the same bits.  A stopping minibatch takes no step: its clip is off and its scale 1.
+struct PgDecision {
+    int stop, clip;
+    float scale;
+};
+ADC_HD PgDecision pg_decide(float max_grad_norm, float target_kl, int stop_rule, const double *sums, int64_t S)
+{
+    PgDecision d{0, 0, 1.0f};
+    if (stop_rule && pg_shuffle_stop(pg_stats_approx_kl(sums, S), target_kl)) {
+        d.stop = 1;
+        return d;
+    }
+    d.clip = max_grad_norm > 0.0f;
+    if (d.clip) d.scale = pg_clip_scale(max_grad_norm, pg_stats_grad_norm(sums));
+    return d;
 }
 
 }  // namespace adc

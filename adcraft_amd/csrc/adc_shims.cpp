@@ -1013,6 +1013,20 @@ ADC_EXPORT int adc_pg_shuffle_stop_host(double approx_kl, float target_kl, int32
     return ADC_OK;
 }
 
+// the host twin of k_pg_decide (parts/kernel_pg_queued.inc): adc_pg_shuffle.h's pg_decide on a live member's minibatch
+ADC_EXPORT int adc_pg_decide_host(const adc_pg_config *cfg, float target_kl, const double *sums10, int64_t count, int32_t *evaluated, int32_t *stop,
+                                  int32_t *clip, float *scale)
+{
+    if (adc_pg_config_check(cfg, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (!sums10 || count < 1 || !(target_kl >= 0.0f && target_kl < __builtin_inff())) return ADC_EINVAL;
+    const adc::PgDecision d = adc::pg_decide(cfg->max_grad_norm, target_kl, 1, sums10, count);
+    if (evaluated) *evaluated = 1;
+    if (stop) *stop = d.stop;
+    if (clip) *clip = d.clip;
+    if (scale) *scale = d.scale;
+    return ADC_OK;
+}
+
 ADC_EXPORT int adc_pg_step_host(const adc_pg_config *cfg, int64_t n_params, int64_t steps_taken, const float *grad_q, float *theta_q, float *m_q,
                                 float *v_q)
 {

@@ -171,6 +171,12 @@ struct adc_engine {
     std::vector<int64_t> sh_last_count;         // [members] samples of the member's last evaluated minibatch
     PgShuffleMember *sh_dmem = nullptr;
     uint32_t *sh_order = nullptr, *sh_rows = nullptr;       // [members][T_max * envs of a member] each, packed [members][sh_ns]
+    // the queued update of the live PPO / A2C trainer (adc_engine_pg_update_queued / _pg_pop_update_queued; parts/kernel_pg_queued.inc,
+    // parts/pg_api.inc): one device block - the members' decision constants | step tables | the epochs' shuffle rows | control
+    // blocks | the log - and its pinned twin on the host, allocated at the first queued update and grown on demand; the device
+    // block is one of the trainer's allocations (pg_allocs), the host's goes in pg_drop
+    uint8_t *pq_dev = nullptr, *pq_host = nullptr;
+    size_t pq_bytes = 0;
     // off-policy training over a replay ring filled from the record (adc_engine_td3_init; parts/kernel_td3.inc, parts/td3_api.inc)
     bool have_td3 = false, td3_norm_set = false, td3_gap = false;
     bool td3_critic_set[2][4] = {{false, false, false, false}, {false, false, false, false}};
@@ -914,6 +920,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->es_allocs) (void)hipFree(p);
     for (void *p : e->ro_allocs) (void)hipFree(p);
     for (void *p : e->pg_allocs) (void)hipFree(p);
+    if (e->pq_host) (void)hipHostFree(e->pq_host);
     for (void *p : e->td3_allocs) (void)hipFree(p);
     for (NormSet *s : {&e->on, &e->rn, &e->tn}) norm_set_drop(e, *s);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
@@ -2931,6 +2938,8 @@ void pg_drop(adc_engine *e)
     sh_forget(e);
     e->sh_dmem = nullptr; e->sh_order = e->sh_rows = nullptr;
     mlp_free(e, e->pg_allocs);
+    if (e->pq_host) (void)hipHostFree(e->pq_host);      // (the queued update's pinned twin; its device block was among pg_allocs)
+    e->pq_dev = e->pq_host = nullptr; e->pq_bytes = 0;
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
     e->pg_steps = 0;
     e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();

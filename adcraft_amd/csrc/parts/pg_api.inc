@@ -735,3 +735,298 @@ ADC_EXPORT int adc_engine_pg_pop_copy(adc_engine *e, int32_t src, int32_t dst)
     if ((rc = kl_copy(e, 1, [&](int, int &d, int &f) { d = dst; f = src; }))) return rc;      // (the donor's KL coefficient)
     return ADC_OK;
 }
+
+// ---- the queued update: a whole update enqueued as one chain, one wait (include/adcraft_engine.h; parts/kernel_pg_queued.inc) --------
+// After the advantages nothing of an update needs the host but two decisions per step - the target-KL stop and the norm clip's scale -
+// and k_pg_decide takes them on the device by the host's law (adc_pg_shuffle.h: pg_decide).  What the host-driven update learns
+// step by step is known in advance or not needed until the end: a member that has not stopped has taken s0 + epoch * minibatches
+// steps when an epoch begins, so every epoch's tick is host-known (a stopped member's order is never read); the step's constants
+// are a table over the steps s0 ... s0 + epochs * minibatches - 1, indexed on the device by the steps the member has taken; the
+// statistics are finished after the one wait from the log of raw sums, by the code of the host-driven loops.
+namespace {
+// the sections of the device block (and of its pinned twin), byte offsets: [0, ctl) goes up in one copy, [ctl, end) comes down in one
+struct PqPlan {
+    int M, epochs, count, cap;          // members; epochs; minibatches of an epoch; minibatches of the update = rows of a member's step table
+    size_t law, steps, ticks, ctl, log, end;
+};
+inline size_t pq_up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+PqPlan pq_plan(int M, int epochs, int count, bool shuffle)
+{
+    PqPlan p{};
+    p.M = M; p.epochs = epochs; p.count = count; p.cap = epochs * count;
+    const size_t Ms = (size_t)M, cap = (size_t)p.cap;
+    size_t at = 0;
+    p.law = at; at = pq_up16(at + Ms * sizeof(PgQLaw));
+    p.steps = at; at = pq_up16(at + Ms * cap * sizeof(adc::EsStep));
+    p.ticks = at; at = pq_up16(at + (shuffle ? (size_t)epochs * Ms * sizeof(PgShuffleMember) : 0u));
+    p.ctl = at; at = pq_up16(at + Ms * sizeof(PgQCtl));
+    p.log = at; at += cap * Ms * sizeof(PgQRow);
+    p.end = at;
+    return p;
+}
+// the block and its twin hold `bytes` (the new pair is allocated before the old one goes: a refusal leaves the engine as it was)
+int pq_reserve(adc_engine *e, size_t bytes)
+{
+    if (bytes <= e->pq_bytes) return ADC_OK;
+    std::vector<void *> fresh;
+    uint8_t *dev = nullptr;
+    void *host = nullptr;
+    if (int rc = mlp_alloc(e, fresh, &dev, bytes)) { mlp_free(e, fresh); return rc; }
+    if (hipHostMalloc(&host, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        mlp_free(e, fresh);
+        return fail(ADC_ENOMEM, "hipHostMalloc failed (the queued update's log)");
+    }
+    if (const hipError_t err = hipStreamSynchronize(e->stream); err != hipSuccess) {       // (nothing old has gone yet)
+        mlp_free(e, fresh);
+        (void)hipHostFree(host);
+        return fail(ADC_EHIP, std::string("hipStreamSynchronize(e->stream): ") + hipGetErrorString(err));
+    }
+    sh_replace(e, e->pq_dev, dev);
+    e->pg_allocs.push_back(dev);
+    if (e->pq_host) (void)hipHostFree(e->pq_host);
+    e->pq_host = static_cast<uint8_t *>(host);
+    e->pq_bytes = bytes;
+    return ADC_OK;
+}
+// a member's step table: pg_step_of(c, s0 + i) for i < cap.  es_bias_correction's product beta^t is t products from 1 in order, so
+// the next row's is this row's times beta - the same chain, the same bits, without walking it from 1 for every row
+void pq_steps_fill(adc::EsStep *out, const adc_pg_config &c, int64_t s0, int cap)
+{
+    adc::EsStep step = pg_step_of(c, s0);
+    double p1 = 1.0, p2 = 1.0;
+    for (uint32_t k = 0, t = (uint32_t)(s0 + 1); k < t; ++k) { p1 = p1 * (double)step.beta1; p2 = p2 * (double)step.beta2; }
+    for (int i = 0; i < cap; ++i) {
+        step.c1 = (float)(1.0 - p1); step.c2 = (float)(1.0 - p2);
+        out[i] = step;
+        p1 = p1 * (double)step.beta1; p2 = p2 * (double)step.beta2;
+    }
+}
+
+// pg_minibatch_run / pgp_minibatch_run without the host in the middle: minibatch `index` of an epoch (g given: the gathered one) of
+// every member, its decision and its step enqueued; row `serial` of the log takes its sums
+int pq_minibatch_enqueue(adc_engine *e, const PqPlan &pl, int index, int serial, const PgGather *g)
+{
+    const adc::PgShape &sh = e->pg_shape;
+    const bool pop = e->have_pg_pop, kl = e->kl_live;
+    const int N = e->v.N, T = e->ro_t, M = pl.M, n = sh_member_envs(e), B = g ? 1 : e->pg_mb, n0 = g ? 0 : index * B;
+    const int na = adc::pg_acts_floats(sh), nd = adc::pg_deltas_floats(sh), Q = pop ? e->lrn_lay.Q : e->pg_lay.Q;
+    const long long S = g ? g->S : (long long)T * B;
+    const unsigned chunks = (unsigned)pg_chunks(S);
+    const PgQCtl *ctl = reinterpret_cast<const PgQCtl *>(e->pq_dev + pl.ctl);
+    PgView p{};
+    p.sh = sh;
+    if (!pop) {
+        p.loss = adc::PgLoss{e->pg_cfg.eps_clip, e->pg_cfg.vf_coef, e->pg_cfg.ent_coef};
+        p.net[0] = e->mp.pol; p.net[1] = e->mp.val;
+        p.log_std = e->mp.log_std;
+    }
+    p.obs = e->ro_obs; p.action = e->ro_action; p.logp = e->ro_logp; p.value = e->ro_value;
+    p.adv = e->pg_adv; p.ret = e->pg_ret;
+    p.N = N; p.n0 = n0; p.B = B;
+    p.acts = e->pg_acts; p.deltas = e->pg_deltas; p.pieces = e->pg_pieces;
+    p.na = na; p.nd = nd; p.maxw = e->pg_maxw;
+    const size_t lds = pg_lds_floats(sh, e->pg_maxw, kl) * sizeof(float);
+    const dim3 sgrid((unsigned)S, (unsigned)M), blk(kPgBlock);
+    if (pop) {
+        if (g && kl)
+            hipLaunchKernelGGL(k_pg_pop_q_gather_kl_sample, sgrid, blk, lds, e->stream, p, kl_view(e), e->lrn_tab, e->pgp_dmem, e->kl_dmem, g->rows, g->stride, ctl);
+        else if (g)
+            hipLaunchKernelGGL(k_pg_pop_q_gather_sample, sgrid, blk, lds, e->stream, p, e->lrn_tab, e->pgp_dmem, g->rows, g->stride, ctl);
+        else if (kl)
+            hipLaunchKernelGGL(k_pg_pop_q_kl_sample, sgrid, blk, lds, e->stream, p, kl_view(e), e->lrn_tab, e->pgp_dmem, e->kl_dmem, n, ctl);
+        else
+            hipLaunchKernelGGL(k_pg_pop_q_sample, sgrid, blk, lds, e->stream, p, e->lrn_tab, e->pgp_dmem, n, ctl);
+    } else {
+        const adc::PgKl klc = kl ? adc::PgKl{e->kl_coef[0], e->kl_cfg[0].vf_clip} : adc::PgKl{};
+        if (g && kl) hipLaunchKernelGGL(k_pg_q_gather_kl_sample, sgrid, blk, lds, e->stream, p, kl_view(e), klc, g->rows, ctl);
+        else if (g) hipLaunchKernelGGL(k_pg_q_gather_sample, sgrid, blk, lds, e->stream, p, g->rows, ctl);
+        else if (kl) hipLaunchKernelGGL(k_pg_q_kl_sample, sgrid, blk, lds, e->stream, p, kl_view(e), klc, ctl);
+        else hipLaunchKernelGGL(k_pg_q_sample, sgrid, blk, lds, e->stream, p, ctl);
+    }
+    // the gradient's terms in the flat order
+    {
+        int flat = 0, ao = 0, dof = 0;
+        auto launch = [&](const float *X, size_t ldx, int n_in, int n_out, int obs) {
+            PgTerm t{X, ldx, n_in, n_out, dof, flat, obs};
+            const unsigned tiles = (unsigned)(((n_in + 1 + kPgTile - 1) / kPgTile) * ((n_out + kPgTile - 1) / kPgTile));
+            if (pop && g)
+                hipLaunchKernelGGL(k_pg_pop_q_gather_wgrad, dim3(tiles, chunks, (unsigned)M), blk, 0, e->stream, t, S, g->rows, g->stride, e->pg_deltas, nd,
+                                   e->pg_gpart, Q, ctl);
+            else if (pop)
+                hipLaunchKernelGGL(k_pg_pop_q_wgrad, dim3(tiles, chunks, (unsigned)M), blk, 0, e->stream, t, S, B, N, n0, n, e->pg_deltas, nd, e->pg_gpart, Q, ctl);
+            else if (g)
+                hipLaunchKernelGGL(k_pg_q_gather_wgrad, dim3(tiles, chunks), blk, 0, e->stream, t, S, g->rows, e->pg_deltas, nd, e->pg_gpart, Q, ctl);
+            else
+                hipLaunchKernelGGL(k_pg_q_wgrad, dim3(tiles, chunks), blk, 0, e->stream, t, S, B, N, n0, e->pg_deltas, nd, e->pg_gpart, Q, ctl);
+            flat += (n_in + 1) * n_out;
+        };
+        for (int net = 0; net < 2; ++net)
+            for (int l = 0; l < sh.layers[net]; ++l) {
+                const int n_in = adc::pg_n_in(sh, net, l), n_out = sh.n_out[net][l];
+                if (l == 0) launch(e->ro_obs, (size_t)sh.D, n_in, n_out, 1);
+                else { launch(e->pg_acts + ao, (size_t)na, n_in, n_out, 0); ao += n_in; }
+                dof += n_out;
+            }
+        if (!sh.two_heads) launch(nullptr, 0, 0, sh.A, 0);
+    }
+    hipLaunchKernelGGL(k_pg_q_grad_join, dim3(pg_blocks(Q), (unsigned)M), blk, 0, e->stream, e->pg_gpart, (int)chunks, Q, S, e->pg_grad, ctl);
+    // the statistics' sums of every member into pg_sums[member * 16 + at ...], as pgp_csum_launch / pg_csum_launch order them
+    const size_t part_stride = pop ? e->pgp_part_stride : (size_t)0;
+    auto csum = [&](const float *src, int cnt, int stride, int cols, int mode, int at) {
+        const int ch = (int)pg_chunks(cnt), lanes = ch * cols;
+        hipLaunchKernelGGL(k_pg_q_chunk_sums, dim3((unsigned)((lanes + 255) / 256), (unsigned)M), dim3(256), 0, e->stream, src, cnt, (size_t)cnt, stride, cols,
+                           mode, e->pg_part, part_stride, ctl);
+        hipLaunchKernelGGL(k_pg_q_join, dim3((unsigned)M), dim3(64), 0, e->stream, e->pg_part, part_stride, ch, cols, e->pg_sums + at, 16, ctl);
+    };
+    csum(e->pg_pieces, (int)S, adc::kPgPieces, 7, 0, 0);
+    csum(e->pg_pieces + adc::kPgRet, (int)S, adc::kPgPieces, 2, 2, 7);
+    csum(e->pg_grad, Q, 1, 1, 2, 9);
+    if (kl) csum(e->kl_pieces, (int)S, adc::kPgKlPieces, adc::kPgKlPieces, 0, adc::kPgSums);
+    hipLaunchKernelGGL(k_pg_decide, dim3((unsigned)M), dim3(kWave), 0, e->stream, e->pg_sums, adc::kPgSums + (kl ? adc::kPgKlPieces : 0), (int)S, g ? 1 : 0,
+                       reinterpret_cast<const PgQLaw *>(e->pq_dev + pl.law), reinterpret_cast<PgQCtl *>(e->pq_dev + pl.ctl),
+                       reinterpret_cast<PgQRow *>(e->pq_dev + pl.log) + (size_t)serial * (size_t)M);
+    const adc::EsStep *steps = reinterpret_cast<const adc::EsStep *>(e->pq_dev + pl.steps);
+    if (pop)
+        hipLaunchKernelGGL(k_pg_pop_q_update, dim3(pg_blocks(Q), (unsigned)M), blk, 0, e->stream, e->lrn_lay, e->lrn_stride, e->pg_theta, e->pg_m, e->pg_v,
+                           e->pg_grad, ctl, steps, pl.cap);
+    else
+        hipLaunchKernelGGL(k_pg_q_update, dim3(pg_blocks(Q)), blk, 0, e->stream, e->pg_lay, e->pg_theta, e->pg_m, e->pg_v, e->pg_grad, ctl, steps);
+    HIP_TRY(hipGetLastError());
+    return ADC_OK;
+}
+
+// adc_engine_pg_update_queued / _pg_pop_update_queued after the advantages
+int pq_update_run(adc_engine *e, int epochs, adc_pg_stats *stats_m)
+{
+    const bool pop = e->have_pg_pop, shuffle = e->sh_live, kl = e->kl_live;
+    const int M = sh_members(e), n = sh_member_envs(e), N = e->v.N;
+    const uint32_t n_s = (uint32_t)e->ro_t * (uint32_t)n;
+    if (shuffle) e->sh_ns = n_s;
+    const int count = shuffle ? sh_minibatches(e) : n / e->pg_mb;
+    if ((long long)epochs * count > (1ll << 22)) return fail(ADC_EINVAL, "epochs x minibatches: at most 2^22 steps in one queued update (its log and step tables)");
+    const PqPlan pl = pq_plan(M, epochs, count, shuffle);
+    int rc;
+    if ((rc = pq_reserve(e, pl.end))) return rc;
+    auto steps0 = [&](int m) { return pop ? e->pgp_steps[(size_t)m] : e->pg_steps; };
+    // 2. the tables, up once
+    std::memset(e->pq_host, 0, pl.log);
+    PgQLaw *law = reinterpret_cast<PgQLaw *>(e->pq_host + pl.law);
+    adc::EsStep *steps = reinterpret_cast<adc::EsStep *>(e->pq_host + pl.steps);
+    PgShuffleMember *ticks = reinterpret_cast<PgShuffleMember *>(e->pq_host + pl.ticks);
+    for (int m = 0; m < M; ++m) {
+        const adc_pg_config &c = pop ? e->pgp_cfg[(size_t)m] : e->pg_cfg;
+        law[m] = PgQLaw{c.max_grad_norm, shuffle ? e->sh_cfg[(size_t)m].target_kl : 0.0f};
+        pq_steps_fill(steps + (size_t)m * (size_t)pl.cap, c, steps0(m), pl.cap);
+        if (shuffle)
+            for (int ep = 0; ep < epochs; ++ep) {       // (a live member has taken exactly ep * count steps of this update when epoch ep begins)
+                PgShuffleMember &t = ticks[(size_t)ep * (size_t)M + (size_t)m];
+                t.key = e->sh_mem[(size_t)m].key;
+                t.tick = (uint32_t)((uint64_t)(steps0(m) + (int64_t)ep * count) & 0xFFFFFFFFull);
+            }
+    }
+    HIP_TRY(hipMemcpyAsync(e->pq_dev, e->pq_host, pl.log, hipMemcpyHostToDevice, e->stream));
+    if (pop && (rc = pgp_members_upload(e))) return rc;
+    // 3. every epoch's order and every minibatch's kernels, no wait
+    for (int ep = 0; ep < epochs; ++ep) {
+        if (shuffle) {
+            hipLaunchKernelGGL(k_pg_shuffle_rows, dim3((n_s + 255u) / 256u, (unsigned)M), dim3(256), 0, e->stream,
+                               reinterpret_cast<const PgShuffleMember *>(e->pq_dev + pl.ticks) + (size_t)ep * (size_t)M, n_s, adc::pg_shuffle_half_bits(n_s),
+                               (uint32_t)n, (uint32_t)N, e->sh_order, e->sh_rows);
+            HIP_TRY(hipGetLastError());
+        }
+        for (int j = 0; j < count; ++j) {
+            const PgGather g = shuffle ? sh_gather(e, j) : PgGather{};
+            if ((rc = pq_minibatch_enqueue(e, pl, j, ep * count + j, shuffle ? &g : nullptr))) return rc;
+        }
+    }
+    // 4., 5. the control blocks and the log down in one copy, the one wait
+    HIP_TRY(hipMemcpyAsync(e->pq_host + pl.ctl, e->pq_dev + pl.ctl, pl.end - pl.ctl, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    // the host-driven loops over the log: adc_engine_pg_update's / _pg_pop_update's, or sh_update_run's under shuffled minibatches
+    const PgQCtl *ctl = reinterpret_cast<const PgQCtl *>(e->pq_host + pl.ctl);
+    const PgQRow *log = reinterpret_cast<const PgQRow *>(e->pq_host + pl.log);
+    std::vector<adc::PgStatsOut> acc((size_t)M), mean((size_t)M);
+    std::vector<int> cnt((size_t)M, 0);
+    std::vector<int64_t> taken((size_t)M, 0);
+    std::vector<uint8_t> live((size_t)M, 1);
+    KlEpoch klep;
+    bool agree = true;
+    if (!shuffle) {
+        for (int ep = 0; ep < epochs; ++ep) {
+            acc.assign((size_t)M, adc::PgStatsOut{});
+            klep.begin(e);
+            for (int j = 0; j < count; ++j) {
+                for (int m = 0; m < M; ++m) {
+                    const PgQRow &r = log[((size_t)ep * (size_t)count + (size_t)j) * (size_t)M + (size_t)m];
+                    agree = agree && r.evaluated == 1;
+                    if (kl) kl_stats_minibatch(e, m, r.sums + adc::kPgSums, r.count);
+                    sh_stats_add(acc[(size_t)m], adc::pg_stats_finish(r.sums, r.count));
+                    taken[(size_t)m] += 1;
+                }
+                klep.add(e);
+            }
+            for (int m = 0; m < M; ++m) mean[(size_t)m] = sh_stats_mean(acc[(size_t)m], count);
+        }
+    } else {
+        for (int ep = 0; ep < epochs && !sh_all_stopped(e); ++ep) {
+            for (int m = 0; m < M; ++m) {
+                live[(size_t)m] = !e->sh_stats[(size_t)m].stopped;
+                if (live[(size_t)m]) { e->sh_stats[(size_t)m].epochs_begun += 1; acc[(size_t)m] = adc::PgStatsOut{}; cnt[(size_t)m] = 0; }
+            }
+            klep.begin(e, live.data());
+            for (int j = 0; j < count && !sh_all_stopped(e); ++j) {
+                for (int m = 0; m < M; ++m) {
+                    const PgQRow &r = log[((size_t)ep * (size_t)count + (size_t)j) * (size_t)M + (size_t)m];
+                    const bool over = e->sh_stats[(size_t)m].stopped != 0;
+                    agree = agree && (r.evaluated != 0) == !over;
+                    if (over) { e->sh_evaluated[(size_t)m] = 0; continue; }
+                    if (kl) kl_stats_minibatch(e, m, r.sums + adc::kPgSums, r.count);
+                    const adc::PgStatsOut st = adc::pg_stats_finish(r.sums, r.count);
+                    if (sh_minibatch_evaluated(e, m, st.approx_kl, r.count)) taken[(size_t)m] += 1;
+                    sh_stats_add(acc[(size_t)m], st);
+                    cnt[(size_t)m] += 1;
+                }
+                klep.add(e, e->sh_evaluated.data());
+            }
+            for (int m = 0; m < M; ++m)
+                if (live[(size_t)m]) mean[(size_t)m] = sh_stats_mean(acc[(size_t)m], cnt[(size_t)m]);
+        }
+        e->sh_epoch_ready = false;      // (the chain drew every epoch's order over the last one's: none of them is kept for a later call)
+    }
+    for (int m = 0; m < M; ++m) {
+        agree = agree && ctl[m].taken == taken[(size_t)m] && (ctl[m].stopped != 0) == (shuffle && e->sh_stats[(size_t)m].stopped);
+        if (pop) e->pgp_steps[(size_t)m] += taken[(size_t)m];
+        else e->pg_steps += taken[(size_t)m];
+    }
+    // (one law, two sides: a difference would mean the device took steps the host's statistics do not describe - never silently)
+    if (!agree) return fail(ADC_EHIP, "the queued update's device decisions and their replay on the host disagree");
+    if (kl && (rc = kl_update_end(e, klep, true))) return rc;
+    if (stats_m)
+        for (int m = 0; m < M; ++m)
+            pg_stats_fill(stats_m + m, mean[(size_t)m], steps0(m), shuffle ? e->sh_last_count[(size_t)m] : (int64_t)e->ro_t * e->pg_mb);
+    return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_pg_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats *stats)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pg_ready(e)) || (rc = pg_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
+    ENGINE_GUARD(e);
+    if ((rc = pg_advantages_run(e))) return rc;
+    return pq_update_run(e, epochs, stats);
+}
+
+ADC_EXPORT int adc_engine_pg_pop_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats *stats_m)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = pgp_ready(e)) || (rc = pgp_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
+    ENGINE_GUARD(e);
+    if ((rc = pgp_advantages_run(e))) return rc;
+    return pq_update_run(e, epochs, stats_m);
+}

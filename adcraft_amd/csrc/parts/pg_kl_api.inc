@@ -10,10 +10,11 @@ constexpr const char *kKlNotReady =
 int kl_members(const adc_engine *e) { return e->have_pg_pop ? e->lrn_M : 1; }
 
 // the members' table from the host's coefficients and configurations, up in one copy (a population's; a single learner has none)
-int kl_members_upload(adc_engine *e)
+// (idle: the caller has waited for the stream since the last upload - the queued update's one wait)
+int kl_members_upload(adc_engine *e, bool idle = false)
 {
     if (!e->have_pg_pop) return ADC_OK;
-    HIP_TRY(hipStreamSynchronize(e->stream));       // (an earlier upload of the host's table may still be in flight)
+    if (!idle) HIP_TRY(hipStreamSynchronize(e->stream));       // (an earlier upload of the host's table may still be in flight)
     for (size_t m = 0; m < e->kl_mem.size(); ++m) e->kl_mem[m].kl = adc::PgKl{e->kl_coef[m], e->kl_cfg[m].vf_clip};
     HIP_TRY(hipMemcpyAsync(e->kl_dmem, e->kl_mem.data(), e->kl_mem.size() * sizeof(PgKlMember), hipMemcpyHostToDevice, e->stream));
     return ADC_OK;
@@ -64,7 +65,7 @@ struct KlEpoch {
             if (!live || live[m]) { kl[m] = kl[m] + e->kl_stats[m].kl; frac[m] = frac[m] + e->kl_stats[m].vf_clip_fraction; n[m] += 1; }
     }
 };
-int kl_update_end(adc_engine *e, const KlEpoch &last)
+int kl_update_end(adc_engine *e, const KlEpoch &last, bool idle = false)
 {
     bool changed = false;
     for (size_t m = 0; m < e->kl_stats.size(); ++m) {
@@ -76,7 +77,7 @@ int kl_update_end(adc_engine *e, const KlEpoch &last)
         changed = changed || st.kl_coef_next != e->kl_coef[m];
         e->kl_coef[m] = st.kl_coef_next;
     }
-    return changed ? kl_members_upload(e) : ADC_OK;
+    return changed ? kl_members_upload(e, idle) : ADC_OK;
 }
 
 // dst takes its donors' coefficients (adc_engine_pg_pop_copy, a PBT round's copy): pairs of (dst, src), then one upload

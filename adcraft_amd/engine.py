@@ -822,10 +822,12 @@ class StepEngine:
         check(self._lib.adc_engine_pg_minibatch(self._h, int(env_begin), int(env_count), C.byref(st)))
         return self._pg_stats(st)
 
-    def pg_update(self, epochs=1):
-        """advantages, then `epochs` x the minibatches in ascending env order; the last epoch's statistics"""
+    def pg_update(self, epochs=1, queued=False):
+        """advantages, then `epochs` x the minibatches in ascending env order; the last epoch's statistics.  queued=True: the
+        whole update enqueued as one chain with one host wait (adc_engine_pg_update_queued) - the same bits"""
         st = _ffi.PGStats()
-        check(self._lib.adc_engine_pg_update(self._h, int(epochs), C.byref(st)))
+        update = self._lib.adc_engine_pg_update_queued if queued else self._lib.adc_engine_pg_update
+        check(update(self._h, int(epochs), C.byref(st)))
         return self._pg_stats(st)
 
     def pg_state(self, state=None):
@@ -878,10 +880,12 @@ class StepEngine:
         check(self._lib.adc_engine_pg_pop_minibatch(self._h, int(index), st))
         return [self._pg_stats(x) for x in st]
 
-    def pg_pop_update(self, epochs=1):
-        """advantages, then `epochs` x the minibatches ascending, all members at once; a list of M statistics dicts"""
+    def pg_pop_update(self, epochs=1, queued=False):
+        """advantages, then `epochs` x the minibatches ascending, all members at once; a list of M statistics dicts.
+        queued=True: one chain, one host wait (adc_engine_pg_pop_update_queued) - the same bits"""
         st = (_ffi.PGStats * max(getattr(self, "_learners", 0), 1))()
-        check(self._lib.adc_engine_pg_pop_update(self._h, int(epochs), st))
+        update = self._lib.adc_engine_pg_pop_update_queued if queued else self._lib.adc_engine_pg_pop_update
+        check(update(self._h, int(epochs), st))
         return [self._pg_stats(x) for x in st]
 
     def pg_pop_state(self, member, state=None):

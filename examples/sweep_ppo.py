@@ -61,6 +61,7 @@ def main():
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--minibatch-size", type=int, default=None, metavar="S",
                     help="shuffled minibatches of S samples of a member instead of --minibatches env ranges (csrc/adc_pg_shuffle.h)")
+    ap.add_argument("--queued-update", action="store_true", help="enqueue every update as one chain on the device, one host wait (the same bits)")
     ap.add_argument("--reward-scale", type=float, default=0.1)
     ap.add_argument("--normalize-rewards", action="store_true", help="one running reward normaliser per member, on the device")
     ap.add_argument("--regimes", action="store_true", help="deal the grid over the paper's six regimes: one learner per (regime, cell)")
@@ -87,7 +88,7 @@ def main():
         for c in configs:
             del c["minibatches"]
             c["minibatch_size"] = args.minibatch_size
-    trainer = pg_trainer.PGPopulationTrainer(eng, policies, days, configs, normalize_rewards=args.normalize_rewards)
+    trainer = pg_trainer.PGPopulationTrainer(eng, policies, days, configs, normalize_rewards=args.normalize_rewards, queued_update=args.queued_update)
     batches = f"{args.minibatches} minibatches" if args.minibatch_size is None else f"shuffled minibatches of {args.minibatch_size} samples"
     print(f"{M} learners x {n} envs x {K} keywords on one engine, {days} days per iteration, {args.epochs} epochs x {batches}")
     print("member  " + " ".join(f"{m:>8d}" for m in range(M)))

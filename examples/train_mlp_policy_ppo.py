@@ -81,6 +81,7 @@ def main():
     ap.add_argument("--rllib", action="store_true", help="the paper's PPO configuration (pg_trainer.rllib_ppo())")
     ap.add_argument("--minibatch-size", type=int, default=None, metavar="S", help="shuffled minibatches of S samples (--rllib: 64)")
     ap.add_argument("--target-kl", type=float, default=None, metavar="T", help="end an update when a minibatch's approx_kl exceeds 1.5 T")
+    ap.add_argument("--queued-update", action="store_true", help="enqueue every update as one chain on the device, one host wait (the same bits)")
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device, from identity vectors")
@@ -113,6 +114,8 @@ def main():
         config["minibatch_size"] = args.minibatch_size
     if args.target_kl is not None:
         config["target_kl"] = args.target_kl
+    if args.queued_update:
+        config["queued_update"] = True
     policy = with_value_network(default_policy(K, days=days), (32, 32))
     if args.normalize_observations:
         policy.shift, policy.scale = np.zeros_like(policy.shift), np.ones_like(policy.scale)

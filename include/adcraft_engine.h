@@ -769,6 +769,24 @@ int adc_engine_pg_shuffle_minibatch(adc_engine *e, int32_t index, adc_pg_stats *
 int adc_engine_pg_shuffle_order_fetch(adc_engine *e, uint32_t *order, uint32_t *rows);
 int adc_engine_pg_shuffle_stats(adc_engine *e, adc_pg_shuffle_stats *stats_m);         /* [1] or [M] */
 
+/* ---- the queued update: adc_engine_pg_update / _pg_pop_update enqueued as one chain, one host wait ------------------------------
+ * The same arguments, the same results: the learner state (adc_engine_pg_state_get / _pg_pop_state_get, the device's layers), the
+ * returned statistics, adc_engine_pg_shuffle_stats, adc_engine_pg_kl_stats and the adapted KL coefficients are bit for bit those
+ * of the host-driven call, with or without either add-on, the normalisers or a PBT scheduler; the two may be mixed freely from one
+ * update to the next.  The host-driven update waits for every minibatch's sums to decide two things before the step - whether
+ * the target-KL stop fires, and the norm clip's scale; here a one-wave kernel decides them on the device by the same law
+ * (adc_pg_decide_host is its host twin), every other kernel of the chain passes a stopped member by, and the host waits once, for
+ * the log of the minibatches' raw sums, from which it finishes the statistics as the host-driven loops do.  After the advantages
+ * (whose moment fetches are as they were) the call uploads its tables once - the step constants of the steps
+ * s0 ... s0 + epochs x minibatches - 1, every epoch's shuffle tick (a member that has not stopped has taken exactly
+ * s0 + epoch x minibatches steps when an epoch begins), a population's member table - and enqueues epochs x minibatches
+ * minibatches whatever stops: a stopped member's launches run and return at once.  The log, the control blocks and the tables are
+ * allocated at the first call and grown on demand (ADC_ENOMEM leaves the engine as it was); epochs x minibatches is at most 2^22.
+ * Under shuffled minibatches no order survives the call: adc_engine_pg_shuffle_minibatch / _order_fetch are refused with
+ * ADC_ESTATE until adc_engine_pg_shuffle_epoch draws one.  Otherwise refused as adc_engine_pg_update / _pg_pop_update are. */
+int adc_engine_pg_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats *stats);
+int adc_engine_pg_pop_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats *stats_m);
+
 /* ---- off-policy training on the device: a replay ring, twin critics, TD3 (the law is csrc/adc_td3.h) --------------------------
  * The actor is the policy network given to adc_engine_mlp_init with the free log_std[A] head; its mean is TD3's deterministic
  * action, and the stochastic act mean + exp(log_std) * z is the exploration (set log_std = log(sigma); TD3 never trains it; a
@@ -1268,6 +1286,14 @@ int adc_pg_kl_adapt_host(const adc_pg_kl_config *kl, float coef, double kl_mean,
  * holds sample sigma(i)); whether a minibatch with approx_kl ends the update under target_kl (*stop 1 or 0) */
 int adc_pg_shuffle_order_host(uint64_t seed, int64_t n_s, uint32_t tick, uint32_t *order_out);
 int adc_pg_shuffle_stop_host(double approx_kl, float target_kl, int32_t *stop);
+/* what the end of a minibatch decides before its optimiser step (adc_pg_shuffle.h: pg_decide - the code k_pg_decide of the queued
+ * update runs on the device): from the minibatch's ten sums sums10 over `count` samples, cfg's max_grad_norm and target_kl
+ * (>= 0, finite; 0: never stops, as without shuffled minibatches).  *evaluated 1 (a minibatch handed over is evaluated),
+ * *stop 1 when approx_kl = sums10[3] / count exceeds 1.5 target_kl - then no step: *clip 0, *scale 1 - else *clip whether
+ * max_grad_norm > 0 and *scale the norm clip's factor under grad_norm = sqrt(sums10[9]) (1 with the clip off).  Any of the four
+ * outputs may be NULL. */
+int adc_pg_decide_host(const adc_pg_config *cfg, float target_kl, const double *sums10, int64_t count, int32_t *evaluated, int32_t *stop,
+                       int32_t *clip, float *scale);
 /* off-policy training on the host: the same code as the device's (adc_td3.h).  `seed` is the effective seed (the configuration's,
  * or the engine's when that is 0).  The batch arrays hold the gathered elements in order: x_bd / x2_bd [count][D], a_ba [count][A].
  * shift_a / scale_a: the action normalisation, both NULL for none.  target: y_b [count] from the target actor theta_target_p and

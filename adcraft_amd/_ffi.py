@@ -113,6 +113,21 @@ class TD3Stats(C.Structure):
                 ("actor_loss", C.c_double), ("critic_grad_norm", C.c_double), ("actor_grad_norm", C.c_double)]
 
 
+class SACConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_float), ("tau", C.c_float), ("target_update_interval", C.c_int32),
+                ("init_alpha", C.c_float), ("target_entropy", C.c_float), ("alpha_lr", C.c_float), ("eps_sq", C.c_float),
+                ("reward_scale", C.c_float), ("batch_size", C.c_int32), ("capacity", C.c_int32), ("n_critic_layers", C.c_int32),
+                ("critic_widths", C.c_int32 * 4), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("optimiser", C.c_int32), ("max_grad_norm", C.c_float), ("seed", C.c_uint64)]
+
+
+class SACStats(C.Structure):
+    _fields_ = [("updates", C.c_int64), ("buffer_size", C.c_int64), ("samples", C.c_int64), ("critic_loss", C.c_double),
+                ("q1_mean", C.c_double), ("q2_mean", C.c_double), ("y_mean", C.c_double), ("actor_loss", C.c_double),
+                ("logp_mean", C.c_double), ("alpha", C.c_double), ("log_alpha", C.c_double), ("critic_grad_norm", C.c_double),
+                ("actor_grad_norm", C.c_double)]
+
+
 class PBTConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("replace_count", C.c_int32), ("fitness_ema", C.c_float), ("factor_lo", C.c_float),
                 ("factor_hi", C.c_float), ("log_factor_lo", C.c_float), ("log_factor_hi", C.c_float), ("tuned_mask", C.c_uint32),
@@ -274,6 +289,8 @@ def lib():
         "adc_engine_mlp_set_norm": ([vp, vp, vp], C.c_int),
         "adc_engine_mlp_set_log_std": ([vp, vp], C.c_int),
         "adc_engine_mlp_set_deterministic": ([vp, i32], C.c_int),
+        "adc_engine_mlp_set_squash": ([vp, vp, vp], C.c_int),
+        "adc_mlp_squash_host": ([i32, vp, vp, vp, vp], C.c_int),
         "adc_engine_mlp_act": ([vp, f32, vp], C.c_int),
         "adc_engine_mlp_step": ([vp, f32], C.c_int),
         "adc_engine_mlp_last": ([vp, vp, vp, vp, vp, vp], C.c_int),
@@ -358,6 +375,27 @@ def lib():
         "adc_engine_td3_param_counts": ([vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "adc_engine_td3_state_get": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
         "adc_engine_td3_state_set": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64], C.c_int),
+        "adc_engine_sac_init": ([vp, C.POINTER(SACConfig)], C.c_int),
+        "adc_engine_sac_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
+        "adc_engine_sac_sync_targets": ([vp], C.c_int),
+        "adc_engine_sac_store": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_buffer_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_buffer_fetch": ([vp, i64, i64, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_sac_buffer_load": ([vp, i64, i64, vp, vp, vp, vp, vp, i64], C.c_int),
+        "adc_engine_sac_batch_size": ([vp, C.POINTER(i32)], C.c_int),
+        "adc_engine_sac_batch_indices": ([vp, i64, vp], C.c_int),
+        "adc_engine_sac_update": ([vp, i32, C.POINTER(SACStats)], C.c_int),
+        "adc_engine_sac_param_counts": ([vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_state_get": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_state_set": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64], C.c_int),
+        "adc_sac_config_check": ([C.POINTER(SACConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_sac_param_counts_host": ([C.POINTER(MLPConfig), i32, C.POINTER(SACConfig), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_sac_logp_host": ([C.POINTER(MLPConfig), i32, f32, i32, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_sac_target_host": ([C.POINTER(MLPConfig), i32, C.POINTER(SACConfig), u64, i64, f32, vp, vp, i32, vp, vp, vp, vp, vp], C.c_int),
+        "adc_sac_critic_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(SACConfig), vp, i32, vp, vp, vp, vp, vp], C.c_int),
+        "adc_sac_actor_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(SACConfig), u64, i64, f32, vp, vp, i32, vp, vp, vp, vp], C.c_int),
+        "adc_sac_alpha_step_host": ([C.POINTER(SACConfig), i64, f64, i32, vp, C.POINTER(f32)], C.c_int),
+        "adc_sac_log_alpha_init_host": ([f32], f32),
         "adc_td3_pop_config_check": ([C.POINTER(TD3Config), i32, i32, i32, C.POINTER(C.c_char_p)], C.c_int),
         "adc_engine_td3_pop_init": ([vp, C.POINTER(TD3Config), i32], C.c_int),
         "adc_engine_td3_pop_set_critic_layer": ([vp, i32, i32, i32, vp, vp], C.c_int),

@@ -96,6 +96,7 @@
 #include "adc_pg_kl.h"
 #include "adc_pg_shuffle.h"
 #include "adc_td3.h"
+#include "adc_sac.h"
 #include "adc_pbt.h"
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
@@ -122,6 +123,7 @@ namespace adck {
 #include "parts/kernel_pg_shuffle.inc"
 #include "parts/kernel_pg_queued.inc"
 #include "parts/kernel_td3.inc"
+#include "parts/kernel_sac.inc"
 #include "parts/kernel_td3_pop.inc"
 #include "parts/kernel_pbt.inc"
 #include "parts/kernel_norm.inc"
@@ -133,6 +135,7 @@ using namespace adck;
 #include "parts/pg_shuffle_api.inc"
 #include "parts/pg_api.inc"
 #include "parts/td3_api.inc"
+#include "parts/sac_api.inc"
 #include "parts/td3_pop_api.inc"
 #include "parts/pbt_api.inc"
 #include "parts/norm_api.inc"

@@ -31,6 +31,10 @@
 //   to the env flat action order [budget, bids...]: bid k from v = a[1 + k]: v > 0.01 ? v : 0.01 (NaN -> 0.01); with an upper clip
 //              hi > 0: v < hi ? v : hi; then cents c = rint(f64(v) * 100) clamped to [1, 1e9], bid = float32(c / 100).
 //              budget = a[0] > 0.01 ? a[0] : 0.01, or budget_override when that is > 0.
+//   squash     (adc_engine_mlp_set_squash; off by default) the env is given e[a] in place of a[a]: t = tanh(a[a]);
+//              e[a] = lo[a] + half[a] * (t + 1) (a sum, a product, a sum), half[a] = 0.5 * (hi[a] - lo[a]) formed once on the
+//              host.  The bid and the budget are taken from e as above.  The recorded action, the last act's action and the
+//              log-probability stay those of the unsquashed a; a deterministic act squashes the mean.
 #pragma once
 #include "adc_law.h"
 
@@ -176,6 +180,20 @@ ADC_HD float mlp_budget(float v, float budget_override)
 {
     if (budget_override > 0.0f) return budget_override;
     return v > 0.01f ? v : 0.01f;
+}
+
+// the squashed action the env is given: lo + half * (tanh(u) + 1), three roundings after the tanh
+ADC_HD float mlp_squash_half(float lo, float hi)
+{
+    const float d = hi - lo;
+    return 0.5f * d;
+}
+ADC_HD float mlp_squash(float u, float lo, float half)
+{
+    const float t = mlp_tanh(u);
+    const float s = t + 1.0f;
+    const float p = half * s;
+    return lo + p;
 }
 
 // element j of the flat observation row from the engine's output arrays of one env (what k_flatten_obs writes)

@@ -21,6 +21,7 @@
 #include "adc_pg_kl.h"
 #include "adc_pg_shuffle.h"
 #include "adc_td3.h"
+#include "adc_sac.h"
 #include "adc_pbt.h"
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
@@ -513,6 +514,13 @@ ADC_EXPORT int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords,
 }
 
 ADC_EXPORT float adc_mlp_math_host(int32_t fn, float x) { return fn == 0 ? adc::mlp_tanh(x) : adc::mlp_exp(x); }
+
+ADC_EXPORT int adc_mlp_squash_host(int32_t count, const float *u_a, const float *lo_a, const float *hi_a, float *out_a)
+{
+    if (count < 0 || (count > 0 && (!u_a || !lo_a || !hi_a || !out_a))) return ADC_EINVAL;
+    for (int a = 0; a < count; ++a) out_a[a] = adc::mlp_squash(u_a[a], lo_a[a], adc::mlp_squash_half(lo_a[a], hi_a[a]));
+    return ADC_OK;
+}
 
 ADC_EXPORT uint64_t adc_mlp_agent_key_host(uint64_t seed) { return adc::mlp_agent_key(seed); }
 ADC_EXPORT uint64_t adc_mlp_default_agent_key_host(uint64_t engine_seed, uint64_t global_env_id) { return adc::mlp_default_agent_key(engine_seed, global_env_id); }
@@ -1250,6 +1258,212 @@ ADC_EXPORT int adc_td3_polyak_host(float tau, int64_t n, const float *param_n, f
 {
     if (!(tau > 0.0f && tau <= 1.0f) || n < 1 || !param_n || !target_n) return ADC_EINVAL;
     for (int64_t p = 0; p < n; ++p) target_n[p] = adc::td3_polyak(target_n[p], param_n[p], tau);
+    return ADC_OK;
+}
+
+// ---- soft actor-critic on the host (adc_sac.h: the code parts/kernel_sac.inc runs) ------------------------------------------------
+ADC_EXPORT int adc_sac_config_check(const adc_sac_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    const float inf = __builtin_inff();
+    if (!cfg || cfg->struct_size != sizeof(adc_sac_config)) msg = "adc_sac_config: NULL or struct_size mismatch";
+    else if (!(cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) msg = "gamma: 0 to 1";
+    else if (!(cfg->tau > 0.0f && cfg->tau <= 1.0f)) msg = "tau: above 0, at most 1";
+    else if (cfg->target_update_interval < 1) msg = "target_update_interval >= 1";
+    else if (!(cfg->init_alpha > 0.0f && cfg->init_alpha < inf)) msg = "init_alpha: above 0, finite";
+    else if (!(cfg->target_entropy > -inf && cfg->target_entropy < inf)) msg = "target_entropy must be finite";
+    else if (!(cfg->alpha_lr >= 0.0f && cfg->alpha_lr < inf)) msg = "alpha_lr >= 0 (0: alpha stays)";
+    else if (!(cfg->eps_sq > 0.0f && cfg->eps_sq < inf)) msg = "eps_sq: above 0, finite";
+    else if (!(cfg->reward_scale != 0.0f && cfg->reward_scale > -inf && cfg->reward_scale < inf)) msg = "reward_scale must be finite and not 0";
+    else if (cfg->batch_size < 1 || cfg->batch_size > (1 << 20)) msg = "batch_size: 1 to 2^20";
+    else if (cfg->capacity < 1 || cfg->capacity > (1 << 30)) msg = "capacity: 1 to 2^30";
+    else if (cfg->n_critic_layers < 1 || cfg->n_critic_layers > adc::kMlpMaxLayers) msg = "n_critic_layers: 1 to 4";
+    else if (cfg->critic_widths[cfg->n_critic_layers - 1] != 1) msg = "the last critic layer has one output";
+    else if (!(cfg->actor_lr >= 0.0f && cfg->actor_lr < inf)) msg = "actor_lr >= 0";
+    else if (!(cfg->critic_lr >= 0.0f && cfg->critic_lr < inf)) msg = "critic_lr >= 0";
+    else if (cfg->optimiser != ADC_TD3_ADAM && cfg->optimiser != ADC_TD3_SGD) msg = "unknown optimiser";
+    else if (cfg->optimiser == ADC_TD3_ADAM && (!(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f) || !(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f)))
+        msg = "Adam: 0 <= beta1, beta2 < 1";
+    else if (cfg->optimiser == ADC_TD3_ADAM && !(cfg->eps > 0.0f)) msg = "Adam: eps > 0";
+    else if (!(cfg->max_grad_norm >= 0.0f && cfg->max_grad_norm < inf)) msg = "max_grad_norm >= 0 (0: off)";
+    else
+        for (int l = 0; l + 1 < cfg->n_critic_layers; ++l)
+            if (cfg->critic_widths[l] < 1 || cfg->critic_widths[l] > adc::kMlpMaxWidth) msg = "hidden critic widths: 1 to 256";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+namespace {
+// the shape two configurations give, or false: a bad configuration, a free-head policy or one without the clamp
+bool sac_host_shape(const adc_mlp_config *mlp, int32_t K, const adc_sac_config *cfg, adc::Td3Shape *sh)
+{
+    if (adc_mlp_config_check(mlp, K, nullptr) != ADC_OK || adc_sac_config_check(cfg, nullptr) != ADC_OK) return false;
+    if (mlp->policy_widths[mlp->n_policy_layers - 1] != 2 * (K + 1) || !mlp->clamp_log_std) return false;
+    *sh = adc::sac_shape_of(*mlp, K, *cfg);
+    return true;
+}
+adc::EsStep sac_host_step(const adc_sac_config &c, float lr, int64_t steps_taken)
+{
+    adc::EsStep step{};
+    step.optimiser = c.optimiser == ADC_TD3_SGD ? adc::kEsSgd : adc::kEsAdam;
+    step.lr = lr; step.beta1 = c.beta1; step.beta2 = c.beta2; step.eps = c.eps; step.l2 = 0.0f;
+    step.c1 = adc::es_bias_correction(step.beta1, (uint32_t)(steps_taken + 1));
+    step.c2 = adc::es_bias_correction(step.beta2, (uint32_t)(steps_taken + 1));
+    return step;
+}
+}  // namespace
+
+ADC_EXPORT int adc_sac_param_counts_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, int64_t *actor_p, int64_t *critic_qc)
+{
+    adc::Td3Shape sh;
+    if (!sac_host_shape(mlp, num_keywords, cfg, &sh)) return ADC_EINVAL;
+    if (actor_p) *actor_p = adc::td3_params(sh.pol);
+    if (critic_qc) *critic_qc = adc::td3_params(sh.q);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_sac_logp_host(const adc_mlp_config *mlp, int32_t num_keywords, float eps_sq, int32_t count, const float *mean_ba, const float *raw_ba,
+                                 const float *z_ba, float *u_ba, float *t_ba, float *lp_b)
+{
+    if (adc_mlp_config_check(mlp, num_keywords, nullptr) != ADC_OK || !mlp->clamp_log_std || !(eps_sq > 0.0f) || count < 1 || !mean_ba || !raw_ba || !z_ba ||
+        !lp_b)
+        return ADC_EINVAL;
+    const int A = num_keywords + 1;
+    const adc::SacLaw law{0.0f, 0.0f, 0.0f, eps_sq, mlp->log_std_lo, mlp->log_std_hi};
+    std::vector<adc::SacHead> heads((size_t)A);
+    std::vector<float> o((size_t)2 * A);
+    for (int32_t b = 0; b < count; ++b) {
+        std::copy(mean_ba + (size_t)b * A, mean_ba + (size_t)(b + 1) * A, o.begin());
+        std::copy(raw_ba + (size_t)b * A, raw_ba + (size_t)(b + 1) * A, o.begin() + A);
+        lp_b[b] = adc::sac_heads_host(o.data(), A, 0, 0, 0, 0, law, heads.data(), z_ba + (size_t)b * A);
+        for (int a = 0; a < A; ++a) {
+            if (u_ba) u_ba[(size_t)b * A + a] = heads[(size_t)a].u;
+            if (t_ba) t_ba[(size_t)b * A + a] = heads[(size_t)a].t;
+        }
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_sac_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, uint64_t seed, int64_t update, float alpha,
+                                   const float *theta_p, const float *psi_target_q, int32_t count, const float *x2_bd, const float *r_b,
+                                   const uint8_t *done_b, float *y_b, float *lp_b)
+{
+    adc::Td3Shape sh;
+    if (!sac_host_shape(mlp, num_keywords, cfg, &sh)) return ADC_EINVAL;
+    if (update < 0 || update >= 0xFFFFFFFFll || count < 1 || !theta_p || !psi_target_q || !x2_bd || !r_b || !done_b || !y_b) return ADC_EINVAL;
+    const adc::SacLaw law = adc::sac_law_of(*mlp, *cfg);
+    const uint64_t key = adc::td3_key(seed);
+    const size_t D = (size_t)sh.D, A = (size_t)sh.A, Qc = (size_t)adc::td3_params(sh.q);
+    std::vector<float> row(D + A), yp((size_t)adc::td3_outs(sh.pol)), yq((size_t)adc::td3_outs(sh.q));
+    std::vector<adc::SacHead> heads(A);
+    for (int32_t b = 0; b < count; ++b) {
+        std::copy(x2_bd + (size_t)b * D, x2_bd + (size_t)(b + 1) * D, row.begin());
+        adc::td3_forward_host(sh.pol, sh.activation, theta_p, row.data(), yp.data());
+        const float lp = adc::sac_heads_host(yp.data() + adc::td3_hidden(sh.pol), sh.A, key, adc::ST_SAC_NEXT, (uint32_t)b, (uint32_t)update, law, heads.data(), nullptr);
+        for (size_t a = 0; a < A; ++a) row[D + a] = heads[a].t;
+        float q[2];
+        for (int i = 0; i < 2; ++i) {
+            adc::td3_forward_host(sh.q, sh.activation, psi_target_q + (size_t)i * Qc, row.data(), yq.data());
+            q[i] = yq[(size_t)adc::td3_hidden(sh.q)];
+        }
+        y_b[b] = adc::sac_y(r_b[b], done_b[b], adc::td3_min(q[0], q[1]), alpha, lp, law);
+        if (lp_b) lp_b[b] = lp;
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_sac_critic_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, const float *psi_q, int32_t count,
+                                        const float *x_bd, const float *u_ba, const float *y_b, float *grad_q, double *sums6)
+{
+    adc::Td3Shape sh;
+    if (!sac_host_shape(mlp, num_keywords, cfg, &sh)) return ADC_EINVAL;
+    if (count < 1 || !psi_q || !x_bd || !u_ba || !y_b || !grad_q) return ADC_EINVAL;
+    const size_t S = (size_t)count, D = (size_t)sh.D, A = (size_t)sh.A, DA = D + A, Qc = (size_t)adc::td3_params(sh.q), no = (size_t)adc::td3_outs(sh.q),
+                 nh = (size_t)adc::td3_hidden(sh.q);
+    std::vector<float> xin(S * DA), ys(S * 2 * no), deltas(S * 2 * no), pieces(S * adc::kTd3Pieces, 0.0f);
+    for (size_t s = 0; s < S; ++s) {
+        float *row = xin.data() + s * DA;
+        std::copy(x_bd + s * D, x_bd + (s + 1) * D, row);
+        for (size_t a = 0; a < A; ++a) row[D + a] = adc::mlp_tanh(u_ba[s * A + a]);
+        for (size_t i = 0; i < 2; ++i) {
+            float *y = ys.data() + s * 2 * no + i * no, *d = deltas.data() + s * 2 * no + i * no;
+            adc::td3_forward_host(sh.q, sh.activation, psi_q + i * Qc, row, y);
+            float loss;
+            d[nh] = adc::td3_critic_delta(y[nh], y_b[s], loss);
+            pieces[s * adc::kTd3Pieces + adc::kTd3Loss1 + i] = loss;
+            pieces[s * adc::kTd3Pieces + adc::kTd3Q1 + i] = y[nh];
+            adc::td3_backward_host(sh.q, sh.activation, psi_q + i * Qc, y, d);
+        }
+        pieces[s * adc::kTd3Pieces + adc::kTd3Y] = y_b[s];
+    }
+    for (size_t i = 0; i < 2; ++i)
+        td3_net_grad_host(sh.q, count, xin.data(), DA, ys.data(), 2 * no, i * no, deltas.data(), 2 * no, i * no, grad_q + i * Qc);
+    if (sums6) {
+        for (int c = 0; c < 5; ++c) sums6[c] = adc::pg_csum(count, [&](double part, int64_t s) { return part + (double)pieces[(size_t)s * adc::kTd3Pieces + (size_t)c]; });
+        sums6[5] = adc::pg_csum((int64_t)(2 * Qc), [&](double part, int64_t p) { return adc::pg_chain_mac(part, grad_q[p], grad_q[p]); });
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_sac_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, uint64_t seed, int64_t update, float alpha,
+                                       const float *theta_p, const float *psi_q, int32_t count, const float *x_bd, float *grad_p, float *lp_b, double *sums4)
+{
+    adc::Td3Shape sh;
+    if (!sac_host_shape(mlp, num_keywords, cfg, &sh)) return ADC_EINVAL;
+    if (update < 0 || update >= 0xFFFFFFFFll || count < 1 || !theta_p || !psi_q || !x_bd || !grad_p) return ADC_EINVAL;
+    const adc::SacLaw law = adc::sac_law_of(*mlp, *cfg);
+    const uint64_t key = adc::td3_key(seed);
+    const size_t S = (size_t)count, D = (size_t)sh.D, A = (size_t)sh.A, po = (size_t)adc::td3_outs(sh.pol), ph = (size_t)adc::td3_hidden(sh.pol),
+                 no = (size_t)adc::td3_outs(sh.q), nh = (size_t)adc::td3_hidden(sh.q), Qc = (size_t)adc::td3_params(sh.q);
+    std::vector<float> ys(S * po), deltas(S * po), row(D + A), yq(2 * no), dq(no), gq(A), loss(S), lps(S);
+    std::vector<adc::SacHead> heads(A);
+    int64_t picked2 = 0;
+    for (size_t s = 0; s < S; ++s) {
+        float *y = ys.data() + s * po, *d = deltas.data() + s * po;
+        std::copy(x_bd + s * D, x_bd + (s + 1) * D, row.begin());
+        adc::td3_forward_host(sh.pol, sh.activation, theta_p, row.data(), y);
+        const float lp = adc::sac_heads_host(y + ph, sh.A, key, adc::ST_SAC_PI, (uint32_t)s, (uint32_t)update, law, heads.data(), nullptr);
+        for (size_t a = 0; a < A; ++a) row[D + a] = heads[a].t;
+        for (size_t i = 0; i < 2; ++i) adc::td3_forward_host(sh.q, sh.activation, psi_q + i * Qc, row.data(), yq.data() + i * no);
+        const size_t pick = (size_t)adc::sac_pick(yq[nh], yq[no + nh]);
+        picked2 += (int64_t)pick;
+        const float *psi = psi_q + pick * Qc, *yk = yq.data() + pick * no;
+        dq[nh] = 1.0f;
+        adc::td3_backward_host(sh.q, sh.activation, psi, yk, dq.data());
+        adc::td3_input_delta_host(sh.q, psi, dq.data(), sh.D, sh.A, gq.data());
+        for (size_t a = 0; a < A; ++a) {
+            const adc::SacHead &h = heads[a];
+            const float z = adc::sac_noise(key, adc::ST_SAC_PI, (int)a, (uint32_t)s, (uint32_t)update);
+            const float du = adc::sac_du(h.t, h.w, gq[a], alpha, law.eps_sq);
+            d[ph + a] = du;
+            d[ph + A + a] = adc::sac_dls(du, h.sd, z, alpha, h.moved);
+        }
+        adc::td3_backward_host(sh.pol, sh.activation, theta_p, y, d);
+        loss[s] = adc::sac_pi_loss(alpha, lp, yk[nh]);
+        lps[s] = lp;
+        if (lp_b) lp_b[s] = lp;
+    }
+    td3_net_grad_host(sh.pol, count, x_bd, D, ys.data(), po, 0, deltas.data(), po, 0, grad_p);
+    if (sums4) {
+        sums4[0] = adc::pg_csum(count, [&](double part, int64_t s) { return part + (double)loss[(size_t)s]; });
+        sums4[1] = adc::pg_csum(count, [&](double part, int64_t s) { return part + (double)lps[(size_t)s]; });
+        sums4[2] = adc::pg_csum((int64_t)adc::td3_params(sh.pol), [&](double part, int64_t p) { return adc::pg_chain_mac(part, grad_p[p], grad_p[p]); });
+        sums4[3] = (double)picked2;
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT float adc_sac_log_alpha_init_host(float init_alpha) { return adc::sac_log_alpha_init(init_alpha); }
+
+ADC_EXPORT int adc_sac_alpha_step_host(const adc_sac_config *cfg, int64_t steps_taken, double lp_sum, int32_t count, float *la3, float *alpha)
+{
+    if (adc_sac_config_check(cfg, nullptr) != ADC_OK || steps_taken < 0 || steps_taken >= 0x7FFFFFFFll || count < 1 || !la3) return ADC_EINVAL;
+    float a = adc::mlp_exp(la3[0]);
+    if (cfg->alpha_lr > 0.0f) {
+        const adc::EsStep step = sac_host_step(*cfg, cfg->alpha_lr, steps_taken);
+        la3[0] = adc::sac_alpha_step(step, la3[0], adc::sac_alpha_grad(lp_sum, count, cfg->target_entropy), la3[1], la3[2], a);
+    }
+    if (alpha) *alpha = a;
     return ADC_OK;
 }
 

@@ -95,6 +95,7 @@ struct adc_engine {
     bool mlp_layer_set[2][4] = {{false, false, false, false}, {false, false, false, false}};      // [network][layer] uploaded since init
     bool mlp_norm_set = false, mlp_log_std_set = false;
     float *mlp_boot = nullptr;          // [N] adc_engine_mlp_bootstrap_value's device result
+    float *mlp_sq = nullptr;            // [2][A] the squash's lo and half (adc_engine_mlp_set_squash); mp.sq_lo names it while squash is on
     std::vector<void *> mlp_allocs;     // weights, vectors and last-act arrays (re-allocated by every adc_engine_mlp_init)
     // a population of policies (adc_engine_mlp_population) and the evolution strategy over it (adc_engine_es_init; parts/kernel_es.inc)
     ParamLayout pl{};                   // the flat parameter order of the policy network (set by adc_engine_mlp_init)
@@ -196,6 +197,13 @@ struct adc_engine {
     int32_t *td3_idx = nullptr;         // [B] adc_engine_td3_batch_indices' device result
     double *td3_part = nullptr, *td3_sums = nullptr, *td3_gpart = nullptr;
     std::vector<void *> td3_allocs;
+    // ... of a soft actor-critic learner (adc_engine_sac_init; parts/kernel_sac.inc, parts/sac_api.inc).  It shares the fields above -
+    // the ring, the critics and their targets, the scratch, td3_flat / td3_mom (no target actor: [kTd3ThetaT] stays null), the
+    // counters; td3_cfg holds the fields the shared helpers read (capacity, batch_size, the optimiser's, max_grad_norm)
+    bool have_sac = false;
+    adc_sac_config sac_cfg{};
+    adc::SacLaw sac_law{};
+    float *sac_cell = nullptr;          // {log_alpha, m, v, alpha} on the device (among td3_allocs)
     // ... and of a TD3 learner population (adc_engine_td3_pop_init; parts/kernel_td3_pop.inc, parts/td3_pop_api.inc).  It shares the
     // fields above, sized for all members at once: td3_flat / td3_mom are [M][P] or [M][2 Qc], the scratch [M][B][...], td3_sums
     // [M][16]; td3_cfg holds the fields all members share, td3_lay member 0's stores, the counters count for all (lock-step)
@@ -2832,6 +2840,9 @@ void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode
     else if (p.member)
         hipLaunchKernelGGL(k_mlp_policy<1>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
                            budget_override, d_bids, d_budget, rec, value_out);
+    else if (p.sq_lo)
+        hipLaunchKernelGGL((k_mlp_policy<0, true>), dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+                           budget_override, d_bids, d_budget, rec, value_out);
     else
         hipLaunchKernelGGL(k_mlp_policy<0>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
                            budget_override, d_bids, d_budget, rec, value_out);
@@ -2899,7 +2910,7 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     int rc;
     if (record && e->mp.deterministic) e->ro_deterministic = true;
     // (a day recorded after the envs moved outside the record does not follow the unstored day before it)
-    if (record && (e->have_td3 || e->have_td3_pop) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
+    if (record && (e->have_td3 || e->have_td3_pop || e->have_sac) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
     if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
     if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
     if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
@@ -2952,6 +2963,8 @@ void td3_drop(adc_engine *e)
     pbt_forget(e, ADC_PBT_TD3);
     mlp_free(e, e->td3_allocs);
     e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
+    e->have_sac = false;                // (a soft actor-critic learner lives in the same fields, and ends where TD3 ends)
+    e->sac_cell = nullptr;
     std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));
     e->td3_updates = e->td3_actor_steps = e->td3_written = 0;
     e->td3_stored_t = 0;
@@ -3076,8 +3089,9 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     if ((rc = mlp_alloc(e, e->mlp_allocs, &p.key, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.tick, N)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &p.mean, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.ls, N * A)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &p.action, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.logp, N)) ||
-        (rc = mlp_alloc(e, e->mlp_allocs, &p.value, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_boot, N)))
-        return rc;
+        (rc = mlp_alloc(e, e->mlp_allocs, &p.value, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_boot, N)) ||
+        (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_sq, (size_t)2 * A)))
+        return rc;                      // (squash is off after a re-initialisation: p.sq_lo is null)
     e->mp = p;
     e->mlp_cfg = *cfg;
     std::memset(e->mlp_layer_set, 0, sizeof(e->mlp_layer_set));
@@ -3171,6 +3185,29 @@ ADC_EXPORT int adc_engine_mlp_set_deterministic(adc_engine *e, int32_t determini
     return ADC_OK;
 }
 
+ADC_EXPORT int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const float *hi_a)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
+    if (e->pop_M != 0) return fail(ADC_ESTATE, "the squashed action with a population active is not supported (adc_engine_mlp_population(0) first)");
+    if (e->lrn_M != 0) return fail(ADC_ESTATE, "the squashed action with learners active is not supported (adc_engine_mlp_learners(0) first)");
+    const int A = e->mp.A;
+    std::vector<float> v((size_t)2 * A);
+    for (int a = 0; lo_a && a < A; ++a) {
+        if (!std::isfinite(lo_a[a]) || !std::isfinite(hi_a[a]) || !(hi_a[a] > lo_a[a])) return fail(ADC_EINVAL, "squash bounds: finite, hi > lo");
+        v[(size_t)a] = lo_a[a];
+        v[(size_t)(A + a)] = adc::mlp_squash_half(lo_a[a], hi_a[a]);
+        if (!std::isfinite(v[(size_t)(A + a)])) return fail(ADC_EINVAL, "squash bounds: hi - lo overflows");
+    }
+    ENGINE_GUARD(e);
+    if (!lo_a) { e->mp.sq_lo = e->mp.sq_half = nullptr; return ADC_OK; }
+    HIP_TRY(hipMemcpyAsync(e->mlp_sq, v.data(), v.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mp.sq_lo = e->mlp_sq; e->mp.sq_half = e->mlp_sq + A;
+    return ADC_OK;
+}
+
 ADC_EXPORT int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
@@ -3248,6 +3285,7 @@ ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const i
     if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
     const int N = e->v.N, M = members;
     if (M < 0 || M > 65536) return fail(ADC_EINVAL, "members: 0 (off) to 65536");
+    if (M > 0 && e->mp.sq_lo) return fail(ADC_ESTATE, "a population with the squashed action on is not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
     std::vector<int32_t> map((size_t)N), count((size_t)M, 0);
     if (M > 0) {
         if (!member_of_env_n && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs when no member_of_env map is given");
@@ -3356,6 +3394,7 @@ ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
     const int N = e->v.N, M = members;
     if (M < 0 || M > 65535) return fail(ADC_EINVAL, "members: 0 (off) to 65535");
     if (M > 0 && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs");
+    if (M > 0 && e->mp.sq_lo) return fail(ADC_ESTATE, "learners with the squashed action on are not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
     ENGINE_GUARD(e);
     if (M == 0) { learners_drop(e); return ADC_OK; }
     // a member's block: the policy layers, the value layers, log_std, each starting on a 16-byte boundary; the flat order against it

@@ -46,6 +46,8 @@ struct MlpView {
     };
     size_t pop_stride;                      // floats
     uint32_t pop_offW[adc::kMlpMaxLayers], pop_offb[adc::kMlpMaxLayers];
+    // the squashed action (adc_engine_mlp_set_squash): the env is given lo + half * (tanh(a) + 1).  null: off
+    const float *sq_lo, *sq_half;           // [A]
 };
 
 // where one recorded day goes: the slot's rows of the view's first env (null: that field is off)
@@ -129,7 +131,9 @@ __device__ __forceinline__ void mlp_network(const MlpNet &net, const MlpView &p,
 // kMembers 0: every env runs `pol`;  1: the env's policy layers are its member's (a population);  2: the policy layers, the
 // value layers and log_std are the env's learner's.  (Three instantiations, so that the single-policy kernel and the
 // population's are the code they were.)
-template <int kMembers>
+// kSquash: the env is given the squashed action (adc::mlp_squash).  Only the single-policy kernel has that form; without it the
+// three kernels compute what they computed before there was one.
+template <int kMembers, bool kSquash = false>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int mode, const float *__restrict__ replay_z,
                                                           float budget_override, float *__restrict__ bids, float *__restrict__ budgets,
                                                           MlpRecordSlot rec, float *__restrict__ value_out)
@@ -183,8 +187,9 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         p.ls[oa] = ls;
         p.action[oa] = act;
         if (rec.action) rec.action[oa] = act;
-        if (a == 0) budgets[env] = adc::mlp_budget(act, budget_override);
-        else bids[(size_t)env * K + (a - 1)] = adc::mlp_bid(act, p.clip_hi);
+        const float ea = kSquash ? adc::mlp_squash(act, p.sq_lo[a], p.sq_half[a]) : act;
+        if (a == 0) budgets[env] = adc::mlp_budget(ea, budget_override);
+        else bids[(size_t)env * K + (a - 1)] = adc::mlp_bid(ea, p.clip_hi);
         out[a] = adc::mlp_logp_term(z, ls);
     }
     __syncthreads();

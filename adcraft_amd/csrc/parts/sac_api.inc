@@ -1,0 +1,384 @@
+// sac_api.inc - the extern "C" entry points of soft actor-critic training (include/adcraft_engine.h; the kernels are
+// parts/kernel_sac.inc, the law csrc/adc_sac.h).  The learner lives in the off-policy trainer's fields (host_api.inc: the ring,
+// the critics, their targets, the scratch, the flat vectors and moments), so the helpers of td3_api.inc serve it as they are;
+// SAC and TD3 exclude each other.  Everything here runs on the engine's own stream behind ENGINE_GUARD.
+// (part of the single translation unit adc_engine.hip)
+namespace {
+int sac_ready(const adc_engine *e)
+{
+    if (!e->have_sac) return fail(ADC_ESTATE, "adc_engine_sac_init has not been called (or the policy / the record was re-initialised since)");
+    return ADC_OK;
+}
+// what a soft actor-critic call needs of the engine's state, checked at init and again at every call
+int sac_state_check(const adc_engine *e)
+{
+    if (int rc = mlp_ready(e)) return rc;
+    if (!e->mp.two_heads) return fail(ADC_ESTATE, "SAC needs the two-headed policy (2A outputs: means, log-stds): the free log_std head is not supported");
+    if (!e->mp.clamp) return fail(ADC_ESTATE, "SAC needs clamp_log_std on: the log-std head is unbounded without it");
+    if (!e->mp.sq_lo) return fail(ADC_ESTATE, "SAC needs the squashed action (adc_engine_mlp_set_squash)");
+    if (e->pop_M != 0) return fail(ADC_ESTATE, "soft actor-critic training with a population active is not supported (adc_engine_mlp_population(0) first)");
+    if (e->lrn_M != 0) return fail(ADC_ESTATE, "soft actor-critic training with learners active is not supported (adc_engine_mlp_learners(0) first)");
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "soft actor-critic training needs a rollout record (adc_engine_rollout_enable)");
+    if (!e->ro_obs) return fail(ADC_ESTATE, "soft actor-critic training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
+    return ADC_OK;
+}
+// the fields of the configuration that the shared helpers read from td3_cfg
+adc_td3_config sac_as_td3(const adc_sac_config &c)
+{
+    adc_td3_config t{};
+    t.struct_size = sizeof(t);
+    t.gamma = c.gamma; t.tau = c.tau; t.policy_delay = 1; t.reward_scale = c.reward_scale;
+    t.batch_size = c.batch_size; t.capacity = c.capacity; t.n_critic_layers = c.n_critic_layers;
+    for (int l = 0; l < 4; ++l) t.critic_widths[l] = c.critic_widths[l];
+    t.actor_lr = c.actor_lr; t.critic_lr = c.critic_lr; t.beta1 = c.beta1; t.beta2 = c.beta2; t.eps = c.eps;
+    t.optimiser = c.optimiser; t.max_grad_norm = c.max_grad_norm; t.seed = c.seed;
+    return t;
+}
+SacView sac_view(const adc_engine *e)
+{
+    SacView p{};
+    p.sh = e->td3_shape;
+    p.law = e->sac_law;
+    p.pol = e->mp.pol;
+    for (int i = 0; i < 2; ++i) { p.q[i] = e->td3_q[i]; p.q_t[i] = e->td3_q_t[i]; }
+    p.cell = e->sac_cell;
+    p.ring = e->td3_ring;
+    p.size = (uint32_t)td3_size(e); p.update = (uint32_t)e->td3_updates;
+    p.key = e->td3_key;
+    p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
+    p.maxw = adc::td3_max_width(e->td3_shape);
+    return p;
+}
+// the device's sums: [0..7] the pieces (the two critic losses, Q1, Q2, y, the actor's loss piece, lp, the picks of critic 2),
+// [8] the critics' grad^2, [9] the actor's grad^2
+int sac_one_update(adc_engine *e, bool stats_wanted, bool last)
+{
+    const adc::Td3Shape &sh = e->td3_shape;
+    const adc_sac_config &c = e->sac_cfg;
+    const int B = c.batch_size, DA = sh.D + sh.A, nh = adc::td3_hidden(sh.q), no = adc::td3_outs(sh.q), ph = adc::td3_hidden(sh.pol), po = adc::td3_outs(sh.pol);
+    const size_t lds = sac_lds_floats(sh) * sizeof(float);
+    SacView p = sac_view(e);
+    p.na = 2 * nh; p.nd = 2 * no;
+    hipLaunchKernelGGL(k_sac_target, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    hipLaunchKernelGGL(k_sac_critic_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    for (int i = 0; i < 2; ++i) td3_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
+    HIP_TRY(hipGetLastError());
+    int rc;
+    if ((rc = td3_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 8, c.critic_lr, e->td3_updates))) return rc;
+    p.na = ph; p.nd = po;
+    hipLaunchKernelGGL(k_sac_actor_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    td3_wgrad_launch(e, sh.pol, DA, p.na, 0, p.nd, 0, 0, e->td3_P, B);
+    HIP_TRY(hipGetLastError());
+    // (the pieces' sums of every update: the temperature's step reads lp's)
+    if ((rc = td3_csum_launch(e, e->td3_pieces, B, adc::kTd3Pieces, adc::kTd3Pieces, 0, e->td3_sums))) return rc;
+    if ((rc = td3_step_run(e, kTd3Theta, e->td3_mom, e->td3_P, B, stats_wanted && last, 9, c.actor_lr, e->td3_updates))) return rc;
+    if (c.alpha_lr > 0.0f)
+        hipLaunchKernelGGL(k_sac_alpha, dim3(1), dim3(64), 0, e->stream, e->sac_cell, e->td3_sums + adc::kSacLp, (long long)B, c.target_entropy,
+                           td3_step_of(e->td3_cfg, c.alpha_lr, e->td3_updates));
+    if ((e->td3_updates + 1) % c.target_update_interval == 0) {
+        const PgLayout &lay = e->td3_lay[kTd3PsiT];
+        hipLaunchKernelGGL(k_td3_polyak, dim3((unsigned)((lay.Q + kPgBlock - 1) / kPgBlock)), dim3(kPgBlock), 0, e->stream, lay, e->td3_flat[kTd3PsiT],
+                           e->td3_flat[kTd3Psi], c.tau);
+    }
+    HIP_TRY(hipGetLastError());
+    e->td3_updates += 1;
+    return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_sac_init(adc_engine *e, const adc_sac_config *cfg)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const char *why = nullptr;
+    if (adc_sac_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if (int rc = sac_state_check(e)) return rc;
+    if (e->have_pg || e->have_pg_pop)
+        return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
+    if (e->have_td3 || e->have_td3_pop)
+        return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: one trainer at a time owns the policy's weights");
+    if (e->on.live)
+        return fail(ADC_ESTATE, "a running observation normaliser is alive on this engine: the replay ring would hold inputs normalised by older vectors");
+    const adc::Td3Shape sh = adc::sac_shape_of(e->mlp_cfg, e->v.K, *cfg);
+    if (sac_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for soft actor-critic training (LDS)");
+    ENGINE_GUARD(e);
+    const int A = sh.A, D = sh.D, B = cfg->batch_size;
+    const size_t C = (size_t)cfg->capacity, P = (size_t)adc::td3_params(sh.pol), Qc = (size_t)adc::td3_params(sh.q), Q2 = 2 * Qc, Qmax = std::max(P, Q2);
+    const size_t na = (size_t)std::max(std::max(2 * adc::td3_hidden(sh.q), adc::td3_hidden(sh.pol)), 1);
+    const size_t nd = (size_t)std::max(2 * adc::td3_outs(sh.q), adc::td3_outs(sh.pol));
+    // (the new state is allocated before the old one goes: a failure leaves the engine as it was)
+    std::vector<void *> fresh;
+    int rc = ADC_OK;
+    MlpNet nets[4] = {};                    // critic 1, critic 2, target critic 1, target critic 2
+    for (int n = 0; n < 4 && !rc; ++n) {
+        nets[n].layers = sh.q.layers;
+        for (int l = 0; l < sh.q.layers && !rc; ++l) {
+            float *w = nullptr, *b = nullptr;
+            const int n_in = adc::td3_n_in(sh.q, l), n_out = sh.q.n_out[l];
+            if ((rc = mlp_alloc(e, fresh, &w, adc::mlp_weight_count(n_in, n_out))) || (rc = mlp_alloc(e, fresh, &b, (size_t)n_out))) break;
+            nets[n].W[l] = w; nets[n].b[l] = b; nets[n].n_in[l] = n_in; nets[n].n_out[l] = n_out;
+        }
+    }
+    float *flat[4] = {}, *mom[4] = {}, *grad = nullptr, *ybuf = nullptr, *xin = nullptr, *acts = nullptr, *deltas = nullptr, *pieces = nullptr, *cell = nullptr;
+    Td3Ring ring{};
+    int32_t *idx = nullptr;
+    double *part = nullptr, *sums = nullptr, *gpart = nullptr;
+    for (int w = 0; w < 4 && !rc; ++w) {
+        if (w != kTd3ThetaT) rc = mlp_alloc(e, fresh, &flat[w], (w & 1) ? Q2 : P);
+        if (!rc) rc = mlp_alloc(e, fresh, &mom[w], w < 2 ? P : Q2);
+    }
+    if (rc || (rc = mlp_alloc(e, fresh, &grad, Qmax)) || (rc = mlp_alloc(e, fresh, &ybuf, (size_t)B)) ||
+        (rc = mlp_alloc(e, fresh, &xin, (size_t)B * (size_t)(D + A))) || (rc = mlp_alloc(e, fresh, &acts, (size_t)B * na)) ||
+        (rc = mlp_alloc(e, fresh, &deltas, (size_t)B * nd)) || (rc = mlp_alloc(e, fresh, &pieces, (size_t)B * (size_t)adc::kTd3Pieces)) ||
+        (rc = mlp_alloc(e, fresh, &idx, (size_t)B)) || (rc = mlp_alloc(e, fresh, &cell, (size_t)4)) ||
+        (rc = mlp_alloc(e, fresh, &part, (size_t)pg_chunks((long long)std::max((size_t)B, Qmax)) * 8u + 8u)) || (rc = mlp_alloc(e, fresh, &sums, (size_t)16)) ||
+        (rc = mlp_alloc(e, fresh, &gpart, (size_t)pg_chunks(B) * Qmax)) || (rc = mlp_alloc(e, fresh, &ring.x, C * (size_t)D)) ||
+        (rc = mlp_alloc(e, fresh, &ring.a, C * (size_t)A)) || (rc = mlp_alloc(e, fresh, &ring.r, C)) || (rc = mlp_alloc(e, fresh, &ring.done, C)) ||
+        (rc = mlp_alloc(e, fresh, &ring.x2, C * (size_t)D))) {
+        mlp_free(e, fresh);
+        return rc;
+    }
+    td3_drop(e);
+    e->td3_allocs.swap(fresh);
+    e->sac_cfg = *cfg; e->td3_cfg = sac_as_td3(*cfg); e->td3_shape = sh; e->sac_law = adc::sac_law_of(e->mlp_cfg, *cfg);
+    e->td3_key = adc::td3_key(cfg->seed ? cfg->seed : e->cfg.seed);
+    e->td3_P = (int)P; e->td3_Qc = (int)Qc;
+    e->td3_q[0] = nets[0]; e->td3_q[1] = nets[1]; e->td3_q_t[0] = nets[2]; e->td3_q_t[1] = nets[3]; e->td3_pol_t = MlpNet{};
+    e->td3_lay[kTd3Theta] = td3_layout(&e->mp.pol, 1);
+    e->td3_lay[kTd3Psi] = td3_layout(e->td3_q, 2);
+    e->td3_lay[kTd3ThetaT] = PgLayout{};
+    e->td3_lay[kTd3PsiT] = td3_layout(e->td3_q_t, 2);
+    for (int w = 0; w < 4; ++w) { e->td3_flat[w] = flat[w]; e->td3_mom[w] = mom[w]; }
+    e->td3_a_shift = e->td3_a_scale = nullptr; e->td3_ring = ring;
+    e->td3_grad = grad; e->td3_ybuf = ybuf; e->td3_xin = xin; e->td3_acts = acts; e->td3_deltas = deltas; e->td3_pieces = pieces; e->td3_idx = idx;
+    e->td3_part = part; e->td3_sums = sums; e->td3_gpart = gpart; e->sac_cell = cell;
+    e->td3_stored_t = e->ro_t;              // (days recorded before this call are not the trainer's)
+    // theta starts as the device's policy; the target critics as copies (zeros until the critics are uploaded and synchronised)
+    const float la = adc::sac_log_alpha_init(cfg->init_alpha);
+    const float cell0[4] = {la, 0.0f, 0.0f, adc::mlp_exp(la)};
+    HIP_TRY(hipMemcpyAsync(cell, cell0, sizeof(cell0), hipMemcpyHostToDevice, e->stream));
+    td3_params_copy(e, kTd3Theta, 1);
+    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3PsiT], e->td3_flat[kTd3Psi], Q2 * 4, hipMemcpyDeviceToDevice, e->stream));
+    td3_params_copy(e, kTd3PsiT, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->have_sac = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_set_critic_layer(adc_engine *e, int32_t critic, int32_t layer, const float *weights_in_out, const float *bias_out)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (critic != 0 && critic != 1) return fail(ADC_EINVAL, "critic: 0 or 1");
+    const adc::Td3Net &q = e->td3_shape.q;
+    if (layer < 0 || layer >= q.layers) return fail(ADC_EINVAL, "no such critic layer");
+    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
+    ENGINE_GUARD(e);
+    size_t off = (size_t)critic * (size_t)e->td3_Qc;
+    for (int l = 0; l < layer; ++l) off += (size_t)(adc::td3_n_in(q, l) + 1) * (size_t)q.n_out[l];
+    const size_t nw = (size_t)adc::td3_n_in(q, layer) * (size_t)q.n_out[layer];
+    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off, weights_in_out, nw * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off + nw, bias_out, (size_t)q.n_out[layer] * 4, hipMemcpyHostToDevice, e->stream));
+    td3_params_copy(e, kTd3Psi, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->td3_critic_set[critic][layer] = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_sync_targets(adc_engine *e)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    ENGINE_GUARD(e);
+    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3PsiT], e->td3_flat[kTd3Psi], (size_t)e->td3_Qc * 8, hipMemcpyDeviceToDevice, e->stream));
+    td3_params_copy(e, kTd3PsiT, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_store(adc_engine *e, int64_t *stored)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = sac_ready(e)) || (rc = sac_state_check(e))) return rc;
+    if (e->ro_t <= e->td3_stored_t) return fail(ADC_ESTATE, "no unstored day in the record (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)");
+    if (e->td3_gap || e->env_moves != e->ro_moves)
+        return fail(ADC_ESTATE, "the envs were stepped or reset outside the record since an unstored recorded day: its next observation is not the "
+                                "one the envs hold (adc_engine_rollout_reset, collect again)");
+    ENGINE_GUARD(e);
+    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;
+    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->mp.shift, e->mp.scale, e->mp.D, e->mp.A, e->ro_obs, e->ro_action,
+                       e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
+                       (unsigned long long)e->td3_cfg.capacity);
+    HIP_TRY(hipGetLastError());
+    e->td3_written += count;
+    e->td3_stored_t = e->ro_t;
+    if (stored) *stored = count;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (size) *size = td3_size(e);
+    if (written) *written = e->td3_written;
+    if (capacity) *capacity = e->td3_cfg.capacity;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_buffer_fetch(adc_engine *e, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done, float *x2)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (slot < 0 || count < 1 || slot > td3_size(e) - count) return fail(ADC_EINVAL, "the slot range is not inside [0, size)");
+    ENGINE_GUARD(e);
+    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
+    const Td3Ring &g = e->td3_ring;
+    if (x) HIP_TRY(hipMemcpyAsync(x, g.x + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
+    if (a) HIP_TRY(hipMemcpyAsync(a, g.a + s * A, n * A * 4, hipMemcpyDeviceToHost, e->stream));
+    if (r) HIP_TRY(hipMemcpyAsync(r, g.r + s, n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (done) HIP_TRY(hipMemcpyAsync(done, g.done + s, n, hipMemcpyDeviceToHost, e->stream));
+    if (x2) HIP_TRY(hipMemcpyAsync(x2, g.x2 + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_buffer_load(adc_engine *e, int64_t slot, int64_t count, const float *x, const float *a, const float *r, const uint8_t *done,
+                                          const float *x2, int64_t written)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (!x || !a || !r || !done || !x2) return fail(ADC_EINVAL, "x, a, r, done or x2 is NULL");
+    if (slot < 0 || count < 1 || slot > (int64_t)e->td3_cfg.capacity - count) return fail(ADC_EINVAL, "the slot range is not inside [0, capacity)");
+    if (written < slot + count) return fail(ADC_EINVAL, "written: at least slot + count");
+    ENGINE_GUARD(e);
+    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
+    const Td3Ring &g = e->td3_ring;
+    HIP_TRY(hipMemcpyAsync(g.x + s * D, x, n * D * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(g.a + s * A, a, n * A * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(g.r + s, r, n * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(g.done + s, done, n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->td3_written = written;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_batch_size(adc_engine *e, int32_t *batch_size)
+{
+    if (!e || !batch_size) return fail(ADC_EINVAL, "engine handle or batch_size is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    *batch_size = e->td3_cfg.batch_size;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_batch_indices(adc_engine *e, int64_t update, int32_t *idx_b)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
+    if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
+    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_store)");
+    ENGINE_GUARD(e);
+    const int B = e->td3_cfg.batch_size;
+    hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->td3_key, (uint32_t)update, (uint32_t)td3_size(e), B, e->td3_idx);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(idx_b, e->td3_idx, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_update(adc_engine *e, int32_t updates, adc_sac_stats *stats)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    int rc;
+    if ((rc = sac_ready(e)) || (rc = sac_state_check(e))) return rc;
+    if (updates < 1 || updates > 65536) return fail(ADC_EINVAL, "updates: 1 to 65536");
+    for (int i = 0; i < 2; ++i)
+        for (int l = 0; l < e->td3_shape.q.layers; ++l)
+            if (!e->td3_critic_set[i][l]) return fail(ADC_ESTATE, "a critic layer has not been uploaded (adc_engine_sac_set_critic_layer)");
+    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_store)");
+    if (e->td3_updates + updates >= 0x7FFFFFFFll) return fail(ADC_ESTATE, "the update counter is exhausted");
+    ENGINE_GUARD(e);
+    HIP_TRY(hipMemsetAsync(e->td3_sums, 0, 16 * sizeof(double), e->stream));
+    // (without a norm clip nothing below waits: every step's Adam constants travel with its launch)
+    for (int i = 0; i < updates; ++i)
+        if ((rc = sac_one_update(e, stats != nullptr, i + 1 == updates))) return rc;
+    double sums[10] = {};
+    float cell[4] = {};
+    if (stats) {
+        HIP_TRY(hipMemcpyAsync(sums, e->td3_sums, sizeof(sums), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(cell, e->sac_cell, sizeof(cell), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (stats) {
+        const double n = (double)e->td3_cfg.batch_size;
+        const double l1 = sums[adc::kTd3Loss1] / n, l2 = sums[adc::kTd3Loss2] / n;
+        stats->updates = e->td3_updates; stats->buffer_size = td3_size(e); stats->samples = e->td3_cfg.batch_size;
+        stats->critic_loss = l1 + l2;
+        stats->q1_mean = sums[adc::kTd3Q1] / n; stats->q2_mean = sums[adc::kTd3Q2] / n; stats->y_mean = sums[adc::kTd3Y] / n;
+        stats->actor_loss = sums[adc::kSacPiLoss] / n;
+        stats->logp_mean = sums[adc::kSacLp] / n;
+        stats->alpha = cell[kSacCellAlpha]; stats->log_alpha = cell[kSacCellLogAlpha];
+        stats->critic_grad_norm = std::sqrt(sums[8]);
+        stats->actor_grad_norm = std::sqrt(sums[9]);
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_param_counts(adc_engine *e, int64_t *actor_p, int64_t *critics_2qc)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (actor_p) *actor_p = e->td3_P;
+    if (critics_2qc) *critics_2qc = 2 * (int64_t)e->td3_Qc;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_state_get(adc_engine *e, float *theta_p, float *psi_q, float *psi_target_q, float *m_theta_p, float *v_theta_p, float *m_psi_q,
+                                        float *v_psi_q, float *log_alpha3, int64_t *updates)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    ENGINE_GUARD(e);
+    const size_t pb = (size_t)e->td3_P * 4, qb = (size_t)e->td3_Qc * 8;
+    float *flat[4] = {theta_p, psi_q, nullptr, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
+    for (int w = 0; w < 4; ++w) {
+        if (flat[w]) HIP_TRY(hipMemcpyAsync(flat[w], e->td3_flat[w], (w & 1) ? qb : pb, hipMemcpyDeviceToHost, e->stream));
+        if (mom[w]) HIP_TRY(hipMemcpyAsync(mom[w], e->td3_mom[w], w < 2 ? pb : qb, hipMemcpyDeviceToHost, e->stream));
+    }
+    if (log_alpha3) HIP_TRY(hipMemcpyAsync(log_alpha3, e->sac_cell, 3 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (updates) *updates = e->td3_updates;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_sac_state_set(adc_engine *e, const float *theta_p, const float *psi_q, const float *psi_target_q, const float *m_theta_p,
+                                        const float *v_theta_p, const float *m_psi_q, const float *v_psi_q, const float *log_alpha3, int64_t updates)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = sac_ready(e)) return rc;
+    if (!theta_p || !psi_q || !psi_target_q || !m_theta_p || !v_theta_p || !m_psi_q || !v_psi_q || !log_alpha3) return fail(ADC_EINVAL, "a state vector is NULL");
+    if (updates < 0 || updates >= 0x7FFFFFFFll) return fail(ADC_EINVAL, "updates: 0 to 2^31 - 2");
+    if (!std::isfinite(log_alpha3[0])) return fail(ADC_EINVAL, "log_alpha must be finite");
+    ENGINE_GUARD(e);
+    const size_t pb = (size_t)e->td3_P * 4, qb = (size_t)e->td3_Qc * 8;
+    const float *flat[4] = {theta_p, psi_q, nullptr, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
+    for (int w = 0; w < 4; ++w) {
+        HIP_TRY(hipMemcpyAsync(e->td3_mom[w], mom[w], w < 2 ? pb : qb, hipMemcpyHostToDevice, e->stream));
+        if (!flat[w]) continue;
+        HIP_TRY(hipMemcpyAsync(e->td3_flat[w], flat[w], (w & 1) ? qb : pb, hipMemcpyHostToDevice, e->stream));
+        td3_params_copy(e, w, 0);           // (the device's policy layers, the critics and the targets follow the flat vectors)
+    }
+    const float cell[4] = {log_alpha3[0], log_alpha3[1], log_alpha3[2], adc::mlp_exp(log_alpha3[0])};
+    HIP_TRY(hipMemcpyAsync(e->sac_cell, cell, sizeof(cell), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->td3_updates = updates;
+    for (int i = 0; i < 2; ++i)
+        for (int l = 0; l < e->td3_shape.q.layers; ++l) e->td3_critic_set[i][l] = true;
+    return ADC_OK;
+}

@@ -597,6 +597,18 @@ class StepEngine:
     def mlp_set_deterministic(self, on=True):
         check(self._lib.adc_engine_mlp_set_deterministic(self._h, 1 if on else 0))
 
+    def mlp_set_squash(self, lo=None, hi=None):
+        """the squashed action: with lo / hi [K + 1] (flat action order: budget, bids) the env is given lo + 0.5 (hi - lo)
+        (tanh(u) + 1) in place of the sampled action u; the record, mlp_last and the log-probability keep u.  Both None: off"""
+        if lo is None and hi is None:
+            check(self._lib.adc_engine_mlp_set_squash(self._h, None, None))
+            return
+        if lo is None or hi is None:
+            raise ValueError("mlp_set_squash: lo and hi, or neither")
+        a = self.num_keywords + 1
+        lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
+        check(self._lib.adc_engine_mlp_set_squash(self._h, lo.ctypes.data, hi.ctypes.data))
+
     def mlp_act(self, budget_override=0.0, replay_normals=None):
         z = None
         if replay_normals is not None:
@@ -1149,6 +1161,131 @@ class StepEngine:
         if any(a.shape != (size(k),) for k, a in zip(self.TD3_STATE, arr)):
             raise ValueError(f"td3_state: the actor's vectors have {P} entries, the critics' {Q}")
         check(self._lib.adc_engine_td3_state_set(self._h, *(a.ctypes.data for a in arr), int(state["updates"]), int(state["actor_steps"])))
+
+    # ---- soft actor-critic over the same replay ring (parts/kernel_sac.inc, parts/sac_api.inc; baselines/sac_trainer.py) ----------
+    @classmethod
+    def sac_config(cls, gamma=0.99, tau=0.005, target_update_interval=1, init_alpha=1.0, target_entropy=None, alpha_lr=3e-4, eps_sq=1e-6,
+                   reward_scale=1.0, batch_size=256, capacity=100000, critic_widths=(256, 256, 1), actor_lr=3e-4, critic_lr=3e-4,
+                   beta1=0.9, beta2=0.999, eps=1e-8, optimiser="adam", max_grad_norm=0.0, seed=0, num_keywords=None):
+        """an adc_sac_config (csrc/adc_sac.h) with RLlib's SAC defaults; target_entropy None: -(num_keywords + 1); alpha_lr 0: alpha
+        stays init_alpha; critic_widths: the outputs of every critic layer, the last 1; seed 0: the engine's"""
+        c = _ffi.SACConfig()
+        c.struct_size = C.sizeof(_ffi.SACConfig)
+        if target_entropy is None:
+            if num_keywords is None:
+                raise ValueError("sac_config: target_entropy, or num_keywords for the default -(K + 1)")
+            target_entropy = -float(num_keywords + 1)
+        c.gamma, c.tau, c.target_update_interval, c.init_alpha, c.target_entropy = gamma, tau, int(target_update_interval), init_alpha, target_entropy
+        c.alpha_lr, c.eps_sq, c.reward_scale, c.batch_size, c.capacity = alpha_lr, eps_sq, reward_scale, int(batch_size), int(capacity)
+        widths = [int(w) for w in critic_widths]
+        if not 1 <= len(widths) <= 4:
+            raise ValueError("critic_widths: 1 to 4 layers")
+        c.n_critic_layers = len(widths)
+        for i, w in enumerate(widths):
+            c.critic_widths[i] = w
+        if optimiser not in cls.TD3_OPTIMISERS:
+            raise ValueError(f"unknown optimiser {optimiser!r}: 'adam' or 'sgd'")
+        c.actor_lr, c.critic_lr, c.beta1, c.beta2, c.eps = actor_lr, critic_lr, beta1, beta2, eps
+        c.optimiser, c.max_grad_norm, c.seed = cls.TD3_OPTIMISERS[optimiser], max_grad_norm, int(seed)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_sac_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad SAC configuration").decode())
+        return c
+
+    def sac_init(self, **options):
+        """SAC on the policy given to mlp_init (two heads, log-std clamp) with mlp_set_squash on, over the rollout record
+        (rollout_enable(T, obs=True) first); options as sac_config's.  theta starts as the device's policy; the critics are
+        uploaded with sac_set_critics."""
+        options.setdefault("num_keywords", self.num_keywords)
+        cfg = self.sac_config(**options)
+        check(self._lib.adc_engine_sac_init(self._h, C.byref(cfg)))
+        self._td3_norm = None
+
+    def sac_set_critics(self, critics, sync_targets=True):
+        """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs [x | tanh(u)]; sync_targets: the
+        target critics become copies of the critics"""
+        if len(critics) != 2:
+            raise ValueError("sac_set_critics: two critics")
+        for i, layers in enumerate(critics):
+            for l, (w, b) in enumerate(layers):
+                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+                check(self._lib.adc_engine_sac_set_critic_layer(self._h, i, l, w.ctypes.data, b.ctypes.data))
+        if sync_targets:
+            check(self._lib.adc_engine_sac_sync_targets(self._h))
+
+    def sac_sync_targets(self):
+        check(self._lib.adc_engine_sac_sync_targets(self._h))
+
+    def sac_store(self):
+        """the record's days not yet stored, into the ring; returns the transitions appended"""
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_sac_store(self._h, C.byref(n)))
+        return n.value
+
+    def sac_buffer(self, fetch=True):
+        """as td3_buffer: a holds the unsquashed actions u"""
+        sz, wr, cap = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self._lib.adc_engine_sac_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap)))
+        st = dict(size=sz.value, written=wr.value, capacity=cap.value)
+        if fetch:
+            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
+            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
+                      x2=np.zeros((n, D), np.float32))
+            if n:
+                check(self._lib.adc_engine_sac_buffer_fetch(self._h, 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
+            st["done"] = st["done"].astype(bool)
+        return st
+
+    def sac_buffer_load(self, buf, slot=0, written=None):
+        """as td3_buffer_load"""
+        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
+        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
+        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
+        n = r.shape[0]
+        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
+            raise ValueError("sac_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
+        if written is None:
+            written = buf.get("written", slot + n)
+        check(self._lib.adc_engine_sac_buffer_load(self._h, int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data, x2.ctypes.data,
+                                                   int(written)))
+
+    def sac_batch_indices(self, update):
+        """the ring slots update number `update` reads at the ring's current size: [batch_size] int32"""
+        b = C.c_int32(0)
+        check(self._lib.adc_engine_sac_batch_size(self._h, C.byref(b)))       # (the engine says how many slots it will write)
+        idx = np.zeros(b.value, np.int32)
+        check(self._lib.adc_engine_sac_batch_indices(self._h, int(update), idx.ctypes.data))
+        return idx
+
+    def sac_update(self, updates=1):
+        """`updates` updates (critics, actor, temperature, targets); the statistics of the last"""
+        st = _ffi.SACStats()
+        check(self._lib.adc_engine_sac_update(self._h, int(updates), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _ffi.SACStats._fields_}
+
+    def sac_param_counts(self):
+        p, q = C.c_int64(0), C.c_int64(0)
+        check(self._lib.adc_engine_sac_param_counts(self._h, C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    SAC_STATE = ("theta", "psi", "psi_target", "m_theta", "v_theta", "m_psi", "v_psi", "log_alpha")
+
+    def sac_state(self, state=None):
+        """get (no argument): dict of theta, m_theta, v_theta [P], psi, psi_target, m_psi, v_psi [2 Qc], log_alpha [3] (log_alpha and
+        its two moments) float32, and updates; set: such a dict - with the ring (sac_buffer / sac_buffer_load) the run continues bit
+        for bit"""
+        P, Q = self.sac_param_counts()
+        size = lambda k: 3 if k == "log_alpha" else Q if "psi" in k else P
+        if state is None:
+            st = {k: np.zeros(size(k), np.float32) for k in self.SAC_STATE}
+            u = C.c_int64(0)
+            check(self._lib.adc_engine_sac_state_get(self._h, *(st[k].ctypes.data for k in self.SAC_STATE), C.byref(u)))
+            st["updates"] = u.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.SAC_STATE]
+        if any(a.shape != (size(k),) for k, a in zip(self.SAC_STATE, arr)):
+            raise ValueError(f"sac_state: the actor's vectors have {P} entries, the critics' {Q}, log_alpha 3")
+        check(self._lib.adc_engine_sac_state_set(self._h, *(a.ctypes.data for a in arr), int(state["updates"])))
 
     # ---- TD3 learner populations: M off-policy learners in lock-step (parts/td3_pop_api.inc; baselines/td3_trainer.py TD3PopulationTrainer) ----
     @classmethod

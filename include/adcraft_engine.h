@@ -507,6 +507,13 @@ int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, cons
 int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, const float *scale_d);
 int adc_engine_mlp_set_log_std(adc_engine *e, const float *log_std_a);
 int adc_engine_mlp_set_deterministic(adc_engine *e, int32_t deterministic);
+/* the squashed action: with lo_a / hi_a [A] (finite, hi > lo) every later act gives the env e[a] = lo[a] + half[a] * (tanh(u[a]) + 1)
+ * in place of the sampled action u[a] (half[a] = 0.5f * (hi[a] - lo[a]) formed once here; a sum, a product, a sum after the law's
+ * tanh), and takes the bid and the budget from e as it took them from u; a deterministic act squashes the mean.  The record,
+ * adc_engine_mlp_last, the log-probability and the ticks are untouched: they keep u.  Both NULL: off, and the act is bit for bit
+ * what it was before the call.  adc_engine_mlp_init turns it off.  Refused with ADC_ESTATE while a population or learners are
+ * active, and adc_engine_mlp_population / adc_engine_mlp_learners (members > 0) are refused with ADC_ESTATE while it is on. */
+int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const float *hi_a);
 /* act on the observation the last step left: actions into the engine's action buffers; replay_normals_na (may be NULL)
  * replaces the draws.  Every act moves the agents' ticks on by one.  Not recorded. */
 int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na);
@@ -866,6 +873,77 @@ int adc_engine_td3_state_get(adc_engine *e, float *theta_p, float *psi_q, float 
 int adc_engine_td3_state_set(adc_engine *e, const float *theta_p, const float *psi_q, const float *theta_target_p, const float *psi_target_q,
                              const float *m_theta_p, const float *v_theta_p, const float *m_psi_q, const float *v_psi_q, int64_t updates,
                              int64_t actor_steps);
+
+/* ---- soft actor-critic on the device (parts/kernel_sac.inc; the law is csrc/adc_sac.h) --------------------------------------------
+ * One learner over the two-headed policy (2A outputs: means, then log-stds) with clamp_log_std on and the squashed action set
+ * (adc_engine_mlp_set_squash): the env is given lo + half (tanh(u) + 1), the record and the ring keep u, and the critics' action
+ * input is t = tanh(u) in [-1, 1].  Two Q networks on [x | t] and their target copies live on the device; there is no target
+ * actor.  adc_engine_sac_store appends the record's days not yet stored to the ring (TD3's ring and store).  One update of
+ * adc_engine_sac_update: the soft target y under the LIVE actor and the target critics; the critics' step; the actor's step on
+ * the same batch through the smaller of the two updated critics, with the reparameterised gradient through both heads; the
+ * temperature's step on log_alpha (alpha_lr > 0), taken by a kernel that writes the device cell the next update's kernels read,
+ * so that an update needs no host round trip; every target_update_interval-th update the Polyak step of the target critics.
+ * The new actor is written into the device's policy layers.  Training draws from the td3 key's stages 16, 20 and 21 alone: the
+ * envs' and the agents' streams do not move.  Flat orders: theta[P], psi[2 Qc] as adc_engine_td3_*.
+ * Without a norm clip a call of U updates only enqueues kernels - the Adam constants of step updates + 1 .. updates + U travel as
+ * launch arguments of that step's kernels, so nothing is uploaded before the chain - and waits once, for the statistics; with
+ * max_grad_norm > 0 each step fetches its norm.
+ * SAC, TD3 and the policy-gradient trainers exclude each other (ADC_ESTATE), and adc_engine_obs_norm_init, _rew_norm_init,
+ * _td3_norm_init and _pbt_init are refused over SAC.  Refused as well (ADC_ESTATE / ADC_EINVAL, the engine stays usable): a
+ * free-head policy, clamp_log_std off, squash not set, no record or no ADC_ROLLOUT_OBS, a population or learners active, an update
+ * with an empty ring or before every critic layer was uploaded, shapes whose activations do not fit 64 KB of LDS.  The trainer
+ * does not survive adc_engine_mlp_init or adc_engine_rollout_enable. */
+typedef struct adc_sac_config {
+    uint32_t struct_size;          /* sizeof(adc_sac_config) */
+    float gamma;                   /* in [0, 1] */
+    float tau;                     /* in (0, 1]: the target critics' Polyak rate */
+    int32_t target_update_interval;/* >= 1: updates per Polyak step */
+    float init_alpha;              /* > 0, finite */
+    float target_entropy;          /* finite (the usual choice: -(K + 1)) */
+    float alpha_lr;                /* >= 0; 0: alpha stays init_alpha */
+    float eps_sq;                  /* > 0: inside the squash correction's logarithm (1e-6) */
+    float reward_scale;            /* finite, != 0 */
+    int32_t batch_size;            /* 1 .. 2^20 */
+    int32_t capacity;              /* 1 .. 2^30 transitions */
+    int32_t n_critic_layers;       /* 1..4 */
+    int32_t critic_widths[4];      /* outputs of each critic layer; hidden ones <= 256, the last is 1 */
+    float actor_lr, critic_lr;     /* >= 0 */
+    float beta1, beta2, eps;       /* Adam: 0 <= beta < 1, eps > 0 */
+    int32_t optimiser;             /* adc_td3_optimiser */
+    float max_grad_norm;           /* > 0: clip each network gradient's global norm; 0: off */
+    uint64_t seed;                 /* of the batches and both noises; 0: the engine's seed */
+} adc_sac_config;
+typedef struct adc_sac_stats {
+    int64_t updates;               /* updates taken so far */
+    int64_t buffer_size;           /* transitions in the ring */
+    int64_t samples;               /* batch elements of an update */
+    double critic_loss;            /* of the call's last update: the sum of the two critics' mean 0.5 (Q - y)^2 */
+    double q1_mean, q2_mean, y_mean;
+    double actor_loss;             /* mean (alpha lp - min Q) of the call's last update */
+    double logp_mean;              /* mean lp of the actor step: the entropy estimate is its negative */
+    double alpha, log_alpha;       /* after the call's last update */
+    double critic_grad_norm, actor_grad_norm;      /* before the clip */
+} adc_sac_stats;
+int adc_engine_sac_init(adc_engine *e, const adc_sac_config *cfg);
+int adc_engine_sac_set_critic_layer(adc_engine *e, int32_t critic, int32_t layer, const float *weights_in_out, const float *bias_out);
+int adc_engine_sac_sync_targets(adc_engine *e);
+int adc_engine_sac_store(adc_engine *e, int64_t *stored);
+int adc_engine_sac_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity);
+int adc_engine_sac_buffer_fetch(adc_engine *e, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done, float *x2);
+int adc_engine_sac_buffer_load(adc_engine *e, int64_t slot, int64_t count, const float *x, const float *a, const float *r, const uint8_t *done,
+                               const float *x2, int64_t written);
+/* the ring slots update number `update` reads at the ring's current size: idx_b [batch_size] (adc_engine_sac_batch_size) */
+int adc_engine_sac_batch_size(adc_engine *e, int32_t *batch_size);
+int adc_engine_sac_batch_indices(adc_engine *e, int64_t update, int32_t *idx_b);
+/* `updates` >= 1 updates; stats may be NULL */
+int adc_engine_sac_update(adc_engine *e, int32_t updates, adc_sac_stats *stats);
+int adc_engine_sac_param_counts(adc_engine *e, int64_t *actor_p, int64_t *critics_2qc);
+/* theta [P]; psi, target psi [2 Qc]; the Adam moments of theta [P] and of psi [2 Qc]; log_alpha3 = {log_alpha, its m, its v}; the
+ * counter: with the ring a resumed run continues bit for bit (get: any pointer may be NULL) */
+int adc_engine_sac_state_get(adc_engine *e, float *theta_p, float *psi_q, float *psi_target_q, float *m_theta_p, float *v_theta_p, float *m_psi_q,
+                             float *v_psi_q, float *log_alpha3, int64_t *updates);
+int adc_engine_sac_state_set(adc_engine *e, const float *theta_p, const float *psi_q, const float *psi_target_q, const float *m_theta_p,
+                             const float *v_theta_p, const float *m_psi_q, const float *v_psi_q, const float *log_alpha3, int64_t updates);
 
 /* ---- TD3 learner populations: M independent off-policy learners in lock-step on one engine ------------------------------------
  * Over learners (adc_engine_mlp_learners, M >= 1, the free log_std head): member m has its own actor (its learner's policy layers),
@@ -1313,6 +1391,28 @@ int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, con
                             const float *psi_q, const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p,
                             double *sums2);
 int adc_td3_polyak_host(float tau, int64_t n, const float *param_n, float *target_n);
+/* soft actor-critic on the host: the same code as parts/kernel_sac.inc runs (adc_sac.h).  `seed` is the effective seed; the batch
+ * arrays hold the gathered elements in order (x_bd / x2_bd [count][D], u_ba [count][A] the ring's unsquashed actions).
+ * logp: from a head's outputs (means, raw log-stds) and given normals: u, t = tanh(u) and lp.  target: y_b (and lp_b, may be NULL)
+ * from the live actor theta_p and the target critics.  critic_grad: grad_q [2 Qc], sums6 as adc_td3_critic_grad_host.
+ * actor_grad: grad_p [P] through the smaller critic; lp_b (may be NULL) [count]; sums4 (may be NULL) = the chunked sums of the
+ * loss piece and of lp, of grad^2, and the number of elements that took critic 2.  alpha_step: one step of log_alpha (la3 = {log_alpha, m,
+ * v}, updated in place) from the chunked sum of lp over count elements with steps_taken steps before it; *alpha receives
+ * exp(log_alpha).  The networks' optimiser step is adc_pg_step_host. */
+int adc_sac_config_check(const adc_sac_config *cfg, const char **message);
+int adc_sac_param_counts_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, int64_t *actor_p, int64_t *critic_qc);
+int adc_sac_logp_host(const adc_mlp_config *mlp, int32_t num_keywords, float eps_sq, int32_t count, const float *mean_ba, const float *raw_ba,
+                      const float *z_ba, float *u_ba, float *t_ba, float *lp_b);
+int adc_sac_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, uint64_t seed, int64_t update, float alpha,
+                        const float *theta_p, const float *psi_target_q, int32_t count, const float *x2_bd, const float *r_b, const uint8_t *done_b,
+                        float *y_b, float *lp_b);
+int adc_sac_critic_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, const float *psi_q, int32_t count,
+                             const float *x_bd, const float *u_ba, const float *y_b, float *grad_q, double *sums6);
+int adc_sac_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_sac_config *cfg, uint64_t seed, int64_t update, float alpha,
+                            const float *theta_p, const float *psi_q, int32_t count, const float *x_bd, float *grad_p, float *lp_b, double *sums4);
+int adc_sac_alpha_step_host(const adc_sac_config *cfg, int64_t steps_taken, double lp_sum, int32_t count, float *la3, float *alpha);
+/* the log_alpha adc_engine_sac_init starts from */
+float adc_sac_log_alpha_init_host(float init_alpha);
 /* the scheduler of population-based training on the host: the same code as adc_engine_pbt_step runs (adc_pbt.h).  `seed` is the
  * effective seed (the configuration's, or the engine's when that is 0).  fitness: fitness_m[members] from a record's reward
  * [days][num_envs].  plan: smoothed_m holds s of the rounds before (not read in round 0) and receives this round's s, before any
@@ -1329,6 +1429,8 @@ int adc_mlp_config_check(const adc_mlp_config *cfg, int32_t num_keywords, const 
  * libm: out3 = {maximum absolute error, maximum error in float32 ulps of the exact value, |result| maximum}; violations4 =
  * {f(-x) != -f(x) (tanh only), f(x) < f(previous x), |tanh| > 1, NaN results}.  Returns the number of values swept. */
 float adc_mlp_math_host(int32_t fn, float x);
+/* the squashed action of adc_engine_mlp_set_squash on the host: out_a[a] from u_a[a] under lo_a / hi_a, count components */
+int adc_mlp_squash_host(int32_t count, const float *u_a, const float *lo_a, const float *hi_a, float *out_a);
 int64_t adc_mlp_math_sweep_host(int32_t fn, float lo, float hi, double *out3, int64_t *violations4);
 /* the agent key adc_engine_mlp_init derives from a per-env seed */
 uint64_t adc_mlp_agent_key_host(uint64_t seed);

@@ -290,6 +290,7 @@ def lib():
         "adc_engine_mlp_set_log_std": ([vp, vp], C.c_int),
         "adc_engine_mlp_set_deterministic": ([vp, i32], C.c_int),
         "adc_engine_mlp_set_squash": ([vp, vp, vp], C.c_int),
+        "adc_engine_mlp_learners_set_squash": ([vp, vp, vp], C.c_int),
         "adc_mlp_squash_host": ([i32, vp, vp, vp, vp], C.c_int),
         "adc_engine_mlp_act": ([vp, f32, vp], C.c_int),
         "adc_engine_mlp_step": ([vp, f32], C.c_int),
@@ -412,6 +413,21 @@ def lib():
         "adc_engine_td3_pop_state_set": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64], C.c_int),
         "adc_engine_td3_pop_set_config": ([vp, i32, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_pop_copy": ([vp, i32, i32, i32], C.c_int),
+        "adc_sac_pop_config_check": ([C.POINTER(SACConfig), i32, i32, i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_sac_pop_init": ([vp, C.POINTER(SACConfig), i32], C.c_int),
+        "adc_engine_sac_pop_set_critic_layer": ([vp, i32, i32, i32, vp, vp], C.c_int),
+        "adc_engine_sac_pop_sync_targets": ([vp, i32], C.c_int),
+        "adc_engine_sac_pop_store": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_pop_buffer_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)], C.c_int),
+        "adc_engine_sac_pop_buffer_fetch": ([vp, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_sac_pop_buffer_load": ([vp, i32, i64, i64, vp, vp, vp, vp, vp, i64], C.c_int),
+        "adc_engine_sac_pop_batch_indices": ([vp, i32, i64, vp], C.c_int),
+        "adc_engine_sac_pop_update": ([vp, i32, C.POINTER(SACStats)], C.c_int),
+        "adc_engine_sac_pop_param_counts": ([vp, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_pop_state_get": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_pop_state_set": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64], C.c_int),
+        "adc_engine_sac_pop_set_config": ([vp, i32, C.POINTER(SACConfig)], C.c_int),
+        "adc_engine_sac_pop_copy": ([vp, i32, i32, i32], C.c_int),
         "adc_td3_config_check": ([C.POINTER(TD3Config), C.POINTER(C.c_char_p)], C.c_int),
         "adc_pbt_config_check": ([C.POINTER(PBTConfig), i32, i32, C.POINTER(C.c_char_p)], C.c_int),
         "adc_engine_pbt_init": ([vp, C.POINTER(PBTConfig)], C.c_int),

@@ -85,3 +85,102 @@ class SACTrainer:
 
     def state(self, state=None):
         return self.engine.sac_state(state)
+
+
+class SACPopulationTrainer:
+    """M independent SAC learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
+    actor, twin critics, target critics, temperature, optimiser state, hyperparameters and replay ring, and every launch of a
+    store or an update covers all members (StepEngine.sac_pop_*).  What a member computes is bit for bit what SACTrainer computes
+    on an engine of its n envs.
+
+    engine: a StepEngine that has been reset; policies: one MLPPolicy (every member starts from it) or a list of M of equal
+    shape (2 (K + 1) outputs, log_std_clamp set); configs: one dict of SACTrainer's keyword options (sac()'s keys and
+    StepEngine.sac_config's, plus critic_seed and critics) shared by all members, or M of them - M is `members`, or the larger
+    of the two counts; action_lo / action_hi [K + 1] (or scalars): the squash bounds, shared by all members.  critic_hidden,
+    batch_size, capacity, target_update_interval, learning_starts (transitions of a member's ring) and updates_per_iteration
+    must be equal in all configurations: the members move together."""
+
+    SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
+
+    def __init__(self, engine, policies, configs, action_lo, action_hi, horizon=10, agent_seeds=None, members=None):
+        policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
+        configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
+        members = max(len(policies), len(configs)) if members is None else int(members)
+        if any(len(x) not in (1, members) for x in (policies, configs)) or not policies or not configs:
+            raise ValueError("SACPopulationTrainer: policies and configs are each one (shared) or one per member")
+        K = policies[0].num_keywords
+        A = K + 1
+        if any(p.output_size != 2 * A or p.log_std_clamp is None for p in policies):
+            raise ValueError("SAC needs policies that end in 2 (K + 1) outputs (means, log-stds) with log_std_clamp set")
+        if any(p.shapes() != policies[0].shapes() for p in policies):
+            raise ValueError("SACPopulationTrainer: the members' policies must have equal shapes")
+        for p in policies[1:]:
+            if p.shift is not None and not (np.array_equal(p.shift, policies[0].shift) and np.array_equal(p.scale, policies[0].scale)):
+                raise ValueError("SACPopulationTrainer: the normalisation vectors are shared by all members: the policies' must be equal")
+        if engine.num_envs % members:
+            raise ValueError("the number of members must divide the engine's envs")
+        policies, configs = (x if len(x) == members else x * members for x in (policies, configs))
+        cfgs = [dict(dict(critic_hidden=(256, 256), learning_starts=1500, updates_per_iteration=64), **c) for c in configs]
+        for c in cfgs[1:]:
+            if any(tuple(np.atleast_1d(c[k])) != tuple(np.atleast_1d(cfgs[0][k])) for k in self.SHARED):
+                raise ValueError("SACPopulationTrainer: critic_hidden, learning_starts and updates_per_iteration must be equal in all configurations")
+        hidden = tuple(cfgs[0]["critic_hidden"])
+        self.learning_starts, self.updates_per_iteration = int(cfgs[0]["learning_starts"]), int(cfgs[0]["updates_per_iteration"])
+        critics, seeds = [c.pop("critics", None) for c in cfgs], [c.pop("critic_seed", m) for m, c in enumerate(cfgs)]
+        self.engine, self.members, self.horizon = engine, members, int(horizon)
+        self.action_lo, self.action_hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (A,))) for v in (action_lo, action_hi))
+        self._templates = [copy.copy(p) for p in policies]
+        self._hidden = hidden
+        self.configs = [dict({k: v for k, v in c.items() if k not in self.SHARED}, critic_widths=hidden + (1,)) for c in cfgs]
+        engine.mlp_init(self._templates[0], seeds=agent_seeds, deterministic=False)
+        engine.mlp_learners(members)
+        for m in range(1, members):
+            engine.mlp_set_learner(m, self._templates[m])
+        engine.mlp_learners_set_squash(self.action_lo, self.action_hi)
+        engine.rollout_enable(self.horizon, obs=True)
+        engine.sac_pop_init(self.configs)
+        for m in range(members):
+            engine.sac_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]))
+        self.history = []
+
+    def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
+        """(reset), `days` (default: the horizon) recorded days of run_days("mlp"), the store, and - once every ring holds
+        learning_starts transitions - updates_per_iteration updates; returns the M members' statistics, or only the rings' size
+        before that"""
+        e = self.engine
+        if reset:
+            e.reset(seeds=reset_seeds)
+        e.rollout_reset()
+        e.run_days("mlp", self.horizon if days is None else int(days), budget)
+        e.sac_pop_store()
+        size = e.sac_pop_buffer(fetch=False)["size"]
+        stats = e.sac_pop_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
+        self.history.append(stats)
+        return stats
+
+    def policy(self, member):
+        """one member's trained actor with the squash bounds its actions are meant under"""
+        return SquashedPolicy(policy_from_actor(self._templates[member], self.engine.sac_pop_state(member)["theta"]), self.action_lo, self.action_hi)
+
+    def returns(self):
+        """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days"""
+        r = self.engine.rollout_fetch()["reward"].astype(np.float64).sum(axis=0)
+        return r.reshape(self.members, -1).mean(axis=1)
+
+    def state(self, member, state=None):
+        return self.engine.sac_pop_state(member, state)
+
+    def copy(self, src, dst, with_ring=False):
+        """member src's actor, critics, target critics, moments and temperature into member dst (with_ring: its ring too); dst
+        keeps its configuration, envs and seed"""
+        self.engine.sac_pop_copy(src, dst, with_ring)
+
+    def set_config(self, member, **options):
+        """a member's hyperparameters from the next update on: `options` over its current ones (StepEngine.sac_config's; the
+        shared fields may not change, init_alpha is not read again)"""
+        cfg = dict(self.configs[member], **options)
+        self.engine.sac_pop_set_config(member, **cfg)
+        self.configs[member] = cfg
+
+
+__all__ = ["SACPopulationTrainer", "SACTrainer", "SquashedPolicy", "sac"]

@@ -58,6 +58,7 @@
 //        chain's kernels that read a member's control block and pass a stopped member by.
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
+//   parts/kernel_sac_pop.inc      SAC learner populations: the k_sac_pop_* twins of kernel_sac.inc, the member one more grid dimension.
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
 //   parts/kernel_norm.inc         the running normalisers, one set of kernels: the record's batch moments of the observations in one pass,
 //        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
@@ -69,6 +70,7 @@
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
+//   parts/sac_pop_api.inc         the entry points of SAC learner populations, over td3_pop_api.inc's helpers.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over either kind of population.
 //   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners' - over shared helpers.
 //
@@ -125,6 +127,7 @@ namespace adck {
 #include "parts/kernel_td3.inc"
 #include "parts/kernel_sac.inc"
 #include "parts/kernel_td3_pop.inc"
+#include "parts/kernel_sac_pop.inc"
 #include "parts/kernel_pbt.inc"
 #include "parts/kernel_norm.inc"
 }  // namespace adck
@@ -137,6 +140,7 @@ using namespace adck;
 #include "parts/td3_api.inc"
 #include "parts/sac_api.inc"
 #include "parts/td3_pop_api.inc"
+#include "parts/sac_pop_api.inc"
 #include "parts/pbt_api.inc"
 #include "parts/norm_api.inc"
 #include "parts/comm_api.inc"

@@ -1293,6 +1293,29 @@ ADC_EXPORT int adc_sac_config_check(const adc_sac_config *cfg, const char **mess
     return msg ? ADC_EINVAL : ADC_OK;
 }
 
+ADC_EXPORT int adc_sac_pop_config_check(const adc_sac_config *cfgs, int32_t count, int32_t num_envs, int32_t members, const char **message)
+{
+    const char *msg = nullptr;
+    if (!cfgs) msg = "adc_sac_config array is NULL";
+    else if (num_envs < 1 || members < 1 || members > 65535 || num_envs % members != 0) msg = "members must be positive, at most 65535, and divide num_envs";
+    else if (count != 1 && count != members) msg = "count: 1 (one configuration shared by all members) or the number of members";
+    else
+        for (int i = 0; i < count && !msg; ++i) {
+            const adc_sac_config &c = cfgs[i], &c0 = cfgs[0];
+            if (adc_sac_config_check(&c, &msg) != ADC_OK) break;
+            if (c.batch_size != c0.batch_size) msg = "batch_size must be equal in all members' configurations (their updates run in the same launches)";
+            else if (c.capacity != c0.capacity) msg = "capacity must be equal in all members' configurations (their rings move together)";
+            else if (c.target_update_interval != c0.target_update_interval)
+                msg = "target_update_interval must be equal in all members' configurations (their target steps run in the same launches)";
+            else if (c.n_critic_layers != c0.n_critic_layers) msg = "n_critic_layers / critic_widths must be equal in all members' configurations (the critics' shape is shared)";
+            else
+                for (int l = 0; l < c.n_critic_layers; ++l)
+                    if (c.critic_widths[l] != c0.critic_widths[l]) msg = "n_critic_layers / critic_widths must be equal in all members' configurations (the critics' shape is shared)";
+        }
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
 namespace {
 // the shape two configurations give, or false: a bad configuration, a free-head policy or one without the clamp
 bool sac_host_shape(const adc_mlp_config *mlp, int32_t K, const adc_sac_config *cfg, adc::Td3Shape *sh)

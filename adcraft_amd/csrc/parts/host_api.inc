@@ -217,6 +217,15 @@ struct adc_engine {
     Td3PopStep *tp_dsteps = nullptr;
     size_t tp_stride[4] = {0, 0, 0, 0};         // floats between two members' stores, per flat vector (theta's: lrn_stride)
     size_t tp_part_stride = 0;                  // doubles of chunk partials per member
+    // ... and of a SAC learner population (adc_engine_sac_pop_init; parts/kernel_sac_pop.inc, parts/sac_pop_api.inc).  It lives in the
+    // TD3 population's fields (no target actor: [kTd3ThetaT] stays null, Td3Member::pol_t empty; tp_cfg holds what the shared helpers
+    // read of a member's configuration; tp_steps has three rows per update: critic, actor, temperature) under a flag of its own,
+    // so that nothing that asks for a TD3 population (the TD3 normalisers, the PBT scheduler) takes it for one
+    bool have_sac_pop = false;
+    std::vector<adc_sac_config> sp_cfg;         // [M]
+    std::vector<SacMember> sp_mem;              // [M] the host's copy of sp_dmem
+    SacMember *sp_dmem = nullptr;
+    float *sp_cells = nullptr;                  // [M][4] {log_alpha, m, v, alpha} on the device
     // the population-based training scheduler over the live pg_pop or td3_pop trainer (parts/pbt_api.inc; the law is adc_pbt.h).
     // Its device arrays are the trainer's allocations (pg_allocs / td3_allocs): they go with it
     bool have_pbt = false;
@@ -2833,8 +2842,11 @@ void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode
                        float *d_budget, const MlpRecordSlot &rec, float *value_out)
 {
     // (three instantiations: without members the kernel is the single-policy code, untouched by the members' addressing; learners
-    // have no pop_stride)
-    if (p.member && p.pop_stride == 0)
+    // have no pop_stride; the squashed forms are instantiations of their own)
+    if (p.member && p.pop_stride == 0 && p.sq_lo)
+        hipLaunchKernelGGL((k_mlp_policy<2, true>), dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
+                           budget_override, d_bids, d_budget, rec, value_out);
+    else if (p.member && p.pop_stride == 0)
         hipLaunchKernelGGL(k_mlp_policy<2>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
                            budget_override, d_bids, d_budget, rec, value_out);
     else if (p.member)
@@ -2910,7 +2922,7 @@ int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
     int rc;
     if (record && e->mp.deterministic) e->ro_deterministic = true;
     // (a day recorded after the envs moved outside the record does not follow the unstored day before it)
-    if (record && (e->have_td3 || e->have_td3_pop || e->have_sac) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
+    if (record && (e->have_td3 || e->have_td3_pop || e->have_sac || e->have_sac_pop) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
     if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
     if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
     if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
@@ -2970,6 +2982,9 @@ void td3_drop(adc_engine *e)
     e->td3_stored_t = 0;
     e->tp_cfg.clear(); e->tp_mem.clear(); e->tp_steps.clear(); e->tp_host_sums.clear(); e->tp_critic_set.clear();
     e->tp_dmem = nullptr; e->tp_dsteps = nullptr;
+    e->have_sac_pop = false;            // (a SAC population lives in the TD3 population's fields)
+    e->sp_cfg.clear(); e->sp_mem.clear();
+    e->sp_dmem = nullptr; e->sp_cells = nullptr;
 }
 // learners and the population trainer over them go with the policy they belong to (the engine is back to the centre policy)
 void learners_drop(adc_engine *e)
@@ -2981,9 +2996,10 @@ void learners_drop(adc_engine *e)
     // (a solo TD3 trainer survives learners and a population, refused while they are active; so do its normalisers, or its raw ring
     //  would be sampled without them afterwards.  A TD3 population's go with it, below)
     if (e->have_pg_pop) pg_drop(e);
-    if (e->have_td3_pop) td3_drop(e);
+    if (e->have_td3_pop || e->have_sac_pop) td3_drop(e);
     mlp_free(e, e->lrn_allocs);
-    if (e->lrn_M != 0) { e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; }
+    // (while learners are active a squash is theirs, adc_engine_mlp_learners_set_squash: it goes with them)
+    if (e->lrn_M != 0) { e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; e->mp.sq_lo = e->mp.sq_half = nullptr; }
     e->lrn_M = e->lrn_n = 0;
     e->lrn_block = e->lrn_flat = nullptr; e->lrn_tab = nullptr; e->lrn_stride = 0;
 }
@@ -3208,6 +3224,30 @@ ADC_EXPORT int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const
     return ADC_OK;
 }
 
+// the learners' squash: one pair of bounds for all members (k_mlp_policy<2, true>).  It lives in the single policy's fields, which
+// are free while learners are active (adc_engine_mlp_set_squash is refused then), and goes with the learners (learners_drop)
+ADC_EXPORT int adc_engine_mlp_learners_set_squash(adc_engine *e, const float *lo_a, const float *hi_a)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (e->lrn_M == 0) return fail(ADC_ESTATE, "the learners' squashed action needs learners (adc_engine_mlp_learners)");
+    if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
+    const int A = e->mp.A;
+    std::vector<float> v((size_t)2 * A);
+    for (int a = 0; lo_a && a < A; ++a) {
+        if (!std::isfinite(lo_a[a]) || !std::isfinite(hi_a[a]) || !(hi_a[a] > lo_a[a])) return fail(ADC_EINVAL, "squash bounds: finite, hi > lo");
+        v[(size_t)a] = lo_a[a];
+        v[(size_t)(A + a)] = adc::mlp_squash_half(lo_a[a], hi_a[a]);
+        if (!std::isfinite(v[(size_t)(A + a)])) return fail(ADC_EINVAL, "squash bounds: hi - lo overflows");
+    }
+    ENGINE_GUARD(e);
+    if (!lo_a) { e->mp.sq_lo = e->mp.sq_half = nullptr; return ADC_OK; }
+    HIP_TRY(hipMemcpyAsync(e->mlp_sq, v.data(), v.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->mp.sq_lo = e->mlp_sq; e->mp.sq_half = e->mlp_sq + A;
+    return ADC_OK;
+}
+
 ADC_EXPORT int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
@@ -3285,7 +3325,9 @@ ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const i
     if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
     const int N = e->v.N, M = members;
     if (M < 0 || M > 65536) return fail(ADC_EINVAL, "members: 0 (off) to 65536");
-    if (M > 0 && e->mp.sq_lo) return fail(ADC_ESTATE, "a population with the squashed action on is not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
+    // (the single policy's squash: the learners' own, on only while they are active, goes with them below)
+    if (M > 0 && e->mp.sq_lo && e->lrn_M == 0)
+        return fail(ADC_ESTATE, "a population with the squashed action on is not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
     std::vector<int32_t> map((size_t)N), count((size_t)M, 0);
     if (M > 0) {
         if (!member_of_env_n && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs when no member_of_env map is given");
@@ -3394,7 +3436,9 @@ ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
     const int N = e->v.N, M = members;
     if (M < 0 || M > 65535) return fail(ADC_EINVAL, "members: 0 (off) to 65535");
     if (M > 0 && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs");
-    if (M > 0 && e->mp.sq_lo) return fail(ADC_ESTATE, "learners with the squashed action on are not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
+    // (the single policy's squash: the learners' own, on only while they are active, goes with them below)
+    if (M > 0 && e->mp.sq_lo && e->lrn_M == 0)
+        return fail(ADC_ESTATE, "learners with the squashed action on are not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
     ENGINE_GUARD(e);
     if (M == 0) { learners_drop(e); return ADC_OK; }
     // a member's block: the policy layers, the value layers, log_std, each starting on a 16-byte boundary; the flat order against it

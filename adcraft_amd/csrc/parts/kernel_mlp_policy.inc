@@ -46,7 +46,8 @@ struct MlpView {
     };
     size_t pop_stride;                      // floats
     uint32_t pop_offW[adc::kMlpMaxLayers], pop_offb[adc::kMlpMaxLayers];
-    // the squashed action (adc_engine_mlp_set_squash): the env is given lo + half * (tanh(a) + 1).  null: off
+    // the squashed action (adc_engine_mlp_set_squash; with learners adc_engine_mlp_learners_set_squash): the env is given
+    // lo + half * (tanh(a) + 1).  null: off
     const float *sq_lo, *sq_half;           // [A]
 };
 
@@ -131,8 +132,9 @@ __device__ __forceinline__ void mlp_network(const MlpNet &net, const MlpView &p,
 // kMembers 0: every env runs `pol`;  1: the env's policy layers are its member's (a population);  2: the policy layers, the
 // value layers and log_std are the env's learner's.  (Three instantiations, so that the single-policy kernel and the
 // population's are the code they were.)
-// kSquash: the env is given the squashed action (adc::mlp_squash).  Only the single-policy kernel has that form; without it the
-// three kernels compute what they computed before there was one.
+// kSquash: the env is given the squashed action (adc::mlp_squash).  The single-policy kernel has that form
+// (adc_engine_mlp_set_squash) and the learners' kernel has it (adc_engine_mlp_learners_set_squash: one pair of bounds for all
+// members); without it the three kernels compute what they computed before there was one.
 template <int kMembers, bool kSquash = false>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int mode, const float *__restrict__ replay_z,
                                                           float budget_override, float *__restrict__ bids, float *__restrict__ budgets,

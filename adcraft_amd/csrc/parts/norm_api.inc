@@ -229,7 +229,7 @@ ADC_EXPORT int adc_engine_obs_norm_init(adc_engine *e, const adc_obs_norm_config
     if (per_member && e->lrn_M == 0) return fail(ADC_ESTATE, "per-member normalisers need learners (adc_engine_mlp_learners)");
     if (e->have_td3 || e->have_td3_pop)
         return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: its ring holds inputs normalised by older vectors");
-    if (e->have_sac) return fail(ADC_ESTATE, "a soft actor-critic trainer is alive on this engine: its ring holds inputs normalised by older vectors");
+    if (e->have_sac || e->have_sac_pop) return fail(ADC_ESTATE, "a soft actor-critic trainer is alive on this engine: its ring holds inputs normalised by older vectors");
     ENGINE_GUARD(e);
     // (a second init starts over from the policy's own vectors; the days its predecessor consumed were collected under other
     //  vectors than those and are not consumed again)

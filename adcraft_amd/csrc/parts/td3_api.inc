@@ -171,7 +171,7 @@ ADC_EXPORT int adc_engine_td3_init(adc_engine *e, const adc_td3_config *cfg)
     const char *why = nullptr;
     if (adc_td3_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     if (int rc = td3_state_check(e)) return rc;
-    if (e->have_sac) return fail(ADC_ESTATE, "a soft actor-critic trainer is alive on this engine: one trainer at a time owns the policy's weights");
+    if (e->have_sac || e->have_sac_pop) return fail(ADC_ESTATE, "a soft actor-critic trainer is alive on this engine: one trainer at a time owns the policy's weights");
     if (e->rn.live) return fail(ADC_ESTATE, "a running reward normaliser is alive on this engine: it belongs to the policy-gradient trainer");
     if (e->have_pg) return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
     if (e->on.live)

@@ -609,6 +609,18 @@ class StepEngine:
         lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
         check(self._lib.adc_engine_mlp_set_squash(self._h, lo.ctypes.data, hi.ctypes.data))
 
+    def mlp_learners_set_squash(self, lo=None, hi=None):
+        """mlp_set_squash for learners (mlp_learners first): one pair of bounds lo / hi [K + 1] shared by all members.  Both
+        None: off.  mlp_learners, mlp_population and mlp_init drop it."""
+        if lo is None and hi is None:
+            check(self._lib.adc_engine_mlp_learners_set_squash(self._h, None, None))
+            return
+        if lo is None or hi is None:
+            raise ValueError("mlp_learners_set_squash: lo and hi, or neither")
+        a = self.num_keywords + 1
+        lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
+        check(self._lib.adc_engine_mlp_learners_set_squash(self._h, lo.ctypes.data, hi.ctypes.data))
+
     def mlp_act(self, budget_override=0.0, replay_normals=None):
         z = None
         if replay_normals is not None:
@@ -1413,6 +1425,129 @@ class StepEngine:
         """actor, critics, targets and optimiser moments of member src into member dst on the device (with_ring: its ring too);
         dst keeps its configuration, envs and exploration"""
         check(self._lib.adc_engine_td3_pop_copy(self._h, int(src), int(dst), 1 if with_ring else 0))
+
+    # ---- SAC learner populations: M soft actor-critic learners in lock-step (parts/sac_pop_api.inc; baselines/sac_trainer.py SACPopulationTrainer) ----
+    @classmethod
+    def sac_pop_configs(cls, configs, num_envs, members, num_keywords=None):
+        """(ctypes array, count) from one dict of sac_config's options or `members` of them, checked by adc_sac_pop_config_check"""
+        if isinstance(configs, dict):
+            configs = [configs]
+        built = [cls.sac_config(**dict(dict(num_keywords=num_keywords), **c)) for c in configs]
+        arr = (_ffi.SACConfig * len(built))(*built)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_sac_pop_config_check(arr, len(built), int(num_envs), int(members), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad population configuration").decode())
+        return arr, len(built)
+
+    def sac_pop_init(self, configs):
+        """population SAC of the learners (mlp_learners, mlp_learners_set_squash and rollout_enable(T, obs=True) first; the
+        two-headed policy with the log-std clamp); configs: one dict of sac_config's options shared by all members, or one per
+        member (batch_size, capacity, critic_widths and target_update_interval equal in all).  Every member's theta starts as its
+        device policy; the critics are uploaded with sac_pop_set_critics."""
+        arr, count = self.sac_pop_configs(configs, self.num_envs, self._td3_pop_members(), self.num_keywords)
+        check(self._lib.adc_engine_sac_pop_init(self._h, arr, count))
+        self._td3_norm = None
+
+    def sac_pop_set_critics(self, member, critics, sync_targets=True):
+        """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs [x | tanh(u)]); sync_targets: the
+        member's target critics become copies of its critics"""
+        if len(critics) != 2:
+            raise ValueError("sac_pop_set_critics: two critics")
+        for i, layers in enumerate(critics):
+            for l, (w, b) in enumerate(layers):
+                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+                check(self._lib.adc_engine_sac_pop_set_critic_layer(self._h, int(member), i, l, w.ctypes.data, b.ctypes.data))
+        if sync_targets:
+            check(self._lib.adc_engine_sac_pop_sync_targets(self._h, int(member)))
+
+    def sac_pop_sync_targets(self, member=None):
+        """member None: every member's target critics"""
+        check(self._lib.adc_engine_sac_pop_sync_targets(self._h, -1 if member is None else int(member)))
+
+    def sac_pop_store(self):
+        """the record's days not yet stored, into every member's ring; returns the transitions each member appended"""
+        n = C.c_int64(0)
+        check(self._lib.adc_engine_sac_pop_store(self._h, C.byref(n)))
+        return n.value
+
+    def sac_pop_buffer(self, member=None, fetch=True):
+        """dict of size, written, capacity, batch_size (the members' rings move together) and - for a member, fetch=True - its
+        ring's slots [0, size) as sac_buffer's (a holds the unsquashed actions u)"""
+        sz, wr, cap, b = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(self._lib.adc_engine_sac_pop_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap), C.byref(b)))
+        st = dict(size=sz.value, written=wr.value, capacity=cap.value, batch_size=b.value)
+        if fetch and member is not None:
+            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
+            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
+                      x2=np.zeros((n, D), np.float32))
+            if n:
+                check(self._lib.adc_engine_sac_pop_buffer_fetch(self._h, int(member), 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
+            st["done"] = st["done"].astype(bool)
+        return st
+
+    def sac_pop_buffer_load(self, member, buf, slot=0, written=None):
+        """the arrays of a sac_pop_buffer(member) dict (or one of its kind) into the member's slots from `slot` on; written
+        becomes the count of transitions stored so far of every member's ring"""
+        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
+        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
+        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
+        n = r.shape[0]
+        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
+            raise ValueError("sac_pop_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
+        if written is None:
+            written = buf.get("written", slot + n)
+        check(self._lib.adc_engine_sac_pop_buffer_load(self._h, int(member), int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data,
+                                                       x2.ctypes.data, int(written)))
+
+    def sac_pop_batch_indices(self, member, update):
+        """the slots of the member's ring its update number `update` reads at the ring's current size: [batch_size] int32"""
+        idx = np.zeros(self.sac_pop_buffer(fetch=False)["batch_size"], np.int32)
+        check(self._lib.adc_engine_sac_pop_batch_indices(self._h, int(member), int(update), idx.ctypes.data))
+        return idx
+
+    def sac_pop_update(self, updates=1, stats=True):
+        """`updates` updates (critics, actor, temperature, targets) of every member, all members in the same launches; a list of
+        M statistics dicts of the last (stats=False: None, and the call fetches nothing)"""
+        if not stats:
+            check(self._lib.adc_engine_sac_pop_update(self._h, int(updates), None))
+            return None
+        st = (_ffi.SACStats * self._td3_pop_members())()
+        check(self._lib.adc_engine_sac_pop_update(self._h, int(updates), st))
+        return [{k: getattr(x, k) for k, _ in _ffi.SACStats._fields_} for x in st]
+
+    def sac_pop_param_counts(self):
+        """(P, 2 Qc): the entries of a member's actor vectors and of its critics' vectors"""
+        p, q = C.c_int64(0), C.c_int64(0)
+        check(self._lib.adc_engine_sac_pop_param_counts(self._h, C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    def sac_pop_state(self, member, state=None):
+        """one member's state as sac_state's, log_alpha [3] its temperature cell's (the counter is the population's).  get (no
+        state): the dict; set: such a dict"""
+        P, Q = self.sac_pop_param_counts()
+        size = lambda k: 3 if k == "log_alpha" else Q if "psi" in k else P
+        if state is None:
+            st = {k: np.zeros(size(k), np.float32) for k in self.SAC_STATE}
+            u = C.c_int64(0)
+            check(self._lib.adc_engine_sac_pop_state_get(self._h, int(member), *(st[k].ctypes.data for k in self.SAC_STATE), C.byref(u)))
+            st["updates"] = u.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.SAC_STATE]
+        if any(a.shape != (size(k),) for k, a in zip(self.SAC_STATE, arr)):
+            raise ValueError(f"sac_pop_state: the actor's vectors have {P} entries, the critics' {Q}, log_alpha 3")
+        check(self._lib.adc_engine_sac_pop_state_set(self._h, int(member), *(a.ctypes.data for a in arr), int(state["updates"])))
+
+    def sac_pop_set_config(self, member, **options):
+        """a member's hyperparameters from the next update on (options as sac_config's; the shared fields may not change, and
+        init_alpha is not read again: the temperature is state)"""
+        options.setdefault("num_keywords", self.num_keywords)
+        cfg = self.sac_config(**options)
+        check(self._lib.adc_engine_sac_pop_set_config(self._h, int(member), C.byref(cfg)))
+
+    def sac_pop_copy(self, src, dst, with_ring=False):
+        """actor, critics, target critics, optimiser moments and the temperature cell of member src into member dst on the device
+        (with_ring: its ring too); dst keeps its configuration, envs and seed"""
+        check(self._lib.adc_engine_sac_pop_copy(self._h, int(src), int(dst), 1 if with_ring else 0))
 
     # ---- population-based training over the live pg_pop / td3_pop trainer (parts/pbt_api.inc; baselines/pbt.py PBTScheduler) ----
     PBT_IDS = {"pg": ("lr", "ent_coef", "eps_clip", "vf_coef"), "td3": ("actor_lr", "critic_lr", "target_noise", "tau", "sigma")}

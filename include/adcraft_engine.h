@@ -514,6 +514,14 @@ int adc_engine_mlp_set_deterministic(adc_engine *e, int32_t deterministic);
  * what it was before the call.  adc_engine_mlp_init turns it off.  Refused with ADC_ESTATE while a population or learners are
  * active, and adc_engine_mlp_population / adc_engine_mlp_learners (members > 0) are refused with ADC_ESTATE while it is on. */
 int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const float *hi_a);
+/* the same squash for learners (adc_engine_mlp_learners, members > 0): one pair of bounds shared by all members; every member's
+ * act gives its envs lo + half (tanh(u) + 1), and the record, adc_engine_mlp_last, the log-probability and the ticks keep u.
+ * Accepted only while learners are active (ADC_ESTATE otherwise); both NULL: off.  It goes with the learners: dropped by
+ * adc_engine_mlp_learners (any argument), by adc_engine_mlp_population (members > 0, which ends the learners) and by
+ * adc_engine_mlp_init.  adc_engine_mlp_set_squash stays refused while learners are active, and adc_engine_mlp_learners /
+ * adc_engine_mlp_population (members > 0) stay refused while the single policy's squash is on: this is the learners' own entry
+ * point. */
+int adc_engine_mlp_learners_set_squash(adc_engine *e, const float *lo_a, const float *hi_a);
 /* act on the observation the last step left: actions into the engine's action buffers; replay_normals_na (may be NULL)
  * replaces the draws.  Every act moves the agents' ticks on by one.  Not recorded. */
 int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na);
@@ -996,6 +1004,62 @@ int adc_engine_td3_pop_set_config(adc_engine *e, int32_t member, const adc_td3_c
 /* actor, critics, all targets and moments of src into dst on the device - with_ring: its ring too - and dst's stores rebuilt; dst
  * keeps its configuration, its envs and its log_std.  The primitive of population-based training (the scheduler: adc_engine_pbt_*) */
 int adc_engine_td3_pop_copy(adc_engine *e, int32_t src, int32_t dst, int32_t with_ring);
+
+/* ---- SAC learner populations: M independent soft actor-critic learners in lock-step on one engine ------------------------------
+ * Over learners (adc_engine_mlp_learners, M >= 1) of the two-headed policy with clamp_log_std on and the learners' squash set
+ * (adc_engine_mlp_learners_set_squash: the bounds are shared): member m has its own actor (its learner's policy layers), twin
+ * critics, target critics, optimiser moments, temperature cell {log_alpha, m, v, alpha}, adc_sac_config and replay ring of
+ * `capacity` transitions; it collects on its own envs [m n, (m + 1) n), n = N / M, and all members store and update together,
+ * every kernel launch covering all of them: the launches and host round trips of a store or an update do not grow with M.  The
+ * law is csrc/adc_sac.h as it is: everything member m computes - ring contents, batch indices, y, both gradients, theta, psi,
+ * target psi, all moment vectors, the temperature cell, the statistics - is bit for bit what adc_engine_sac_* computes on an
+ * engine of n envs at env_id_base + m n with the same parameter planes, engine seed, agent seeds, initial actor and critics,
+ * squash bounds and configuration.  A member's ring slot of sample s = (t - t0) n + local env is (written + s) mod capacity; its
+ * td3 key is that of its own seed (0: the engine's); the chunks of the float64 sums are 1024 consecutive batch elements of the
+ * member.  written, size and updates are single counters: the members move together.
+ * adc_sac_pop_config_check (host only): every configuration passes adc_sac_config_check (that check's own message); count is 1
+ * (shared: only the first is read) or `members`; members divides num_envs and is at most 65535; batch_size, capacity,
+ * n_critic_layers, critic_widths and target_update_interval are equal in all; every other field may differ per member.
+ * adc_engine_sac_pop_init needs learners, the two-headed policy with the clamp on, the learners' squash, a record with
+ * ADC_ROLLOUT_OBS and no other trainer alive (ADC_ESTATE otherwise, the engine stays usable); every member's theta starts as its
+ * device policy; a refused allocation is ADC_ENOMEM and leaves the engine as it was.  adc_engine_obs_norm_init, _rew_norm_init,
+ * _td3_norm_init and _pbt_init are refused over a SAC population (ADC_ESTATE).  The trainer does not survive adc_engine_mlp_init,
+ * adc_engine_mlp_learners or adc_engine_rollout_enable.  The optimiser constants of up to 64 updates - the critics', the actors'
+ * and the temperatures' steps - go up in one copy in front of the chain: with no member clipping (max_grad_norm 0 in all)
+ * adc_engine_sac_pop_update only enqueues kernels and ends with one copy of the statistics; when any member clips, all members'
+ * squared norms come down in one copy per step and their scales go up in one.  A member with alpha_lr == 0 keeps its cell; the
+ * temperatures' launch is left out only when every member has alpha_lr == 0. */
+int adc_sac_pop_config_check(const adc_sac_config *cfgs, int32_t count, int32_t num_envs, int32_t members, const char **message);
+int adc_engine_sac_pop_init(adc_engine *e, const adc_sac_config *cfgs, int32_t count);
+/* as adc_engine_sac_set_critic_layer, for one member */
+int adc_engine_sac_pop_set_critic_layer(adc_engine *e, int32_t member, int32_t critic, int32_t layer, const float *weights_in_out, const float *bias_out);
+/* the member's target critics become copies of its critics; member -1: every member's */
+int adc_engine_sac_pop_sync_targets(adc_engine *e, int32_t member);
+/* the record's days not yet stored into every member's ring; *stored_per_member (may be NULL): the transitions each member appended */
+int adc_engine_sac_pop_store(adc_engine *e, int64_t *stored_per_member);
+int adc_engine_sac_pop_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity, int32_t *batch_size);   /* any may be NULL */
+/* one member's ring: as adc_engine_sac_buffer_fetch / _load (load sets the one `written` all members share) */
+int adc_engine_sac_pop_buffer_fetch(adc_engine *e, int32_t member, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done, float *x2);
+int adc_engine_sac_pop_buffer_load(adc_engine *e, int32_t member, int64_t slot, int64_t count, const float *x, const float *a, const float *r,
+                                   const uint8_t *done, const float *x2, int64_t written);
+int adc_engine_sac_pop_batch_indices(adc_engine *e, int32_t member, int64_t update, int32_t *idx_b);
+/* `updates` >= 1 updates of every member; stats_m[M] or NULL */
+int adc_engine_sac_pop_update(adc_engine *e, int32_t updates, adc_sac_stats *stats_m);
+int adc_engine_sac_pop_param_counts(adc_engine *e, int64_t *actor_p, int64_t *critics_2qc);      /* of one member */
+/* one member's vectors as adc_engine_sac_state_get / _set, log_alpha3 its cell's {log_alpha, m, v}; the counter is the population's
+ * (set: the last call's stands) */
+int adc_engine_sac_pop_state_get(adc_engine *e, int32_t member, float *theta_p, float *psi_q, float *psi_target_q, float *m_theta_p,
+                                 float *v_theta_p, float *m_psi_q, float *v_psi_q, float *log_alpha3, int64_t *updates);
+int adc_engine_sac_pop_state_set(adc_engine *e, int32_t member, const float *theta_p, const float *psi_q, const float *psi_target_q,
+                                 const float *m_theta_p, const float *v_theta_p, const float *m_psi_q, const float *v_psi_q,
+                                 const float *log_alpha3, int64_t updates);
+/* a member's hyperparameters from the next update on (the shared fields may not change; init_alpha is not read again: the
+ * temperature cell is state) */
+int adc_engine_sac_pop_set_config(adc_engine *e, int32_t member, const adc_sac_config *cfg);
+/* actor, critics, target critics, all moments and the temperature cell of src into dst on the device - with_ring: its ring too -
+ * and dst's stores rebuilt; dst keeps its configuration, its envs and its seed.  With adc_engine_sac_pop_set_config the primitive
+ * of a population-based training scheduler over SAC (none yet: adc_engine_pbt_init refuses a SAC population) */
+int adc_engine_sac_pop_copy(adc_engine *e, int32_t src, int32_t dst, int32_t with_ring);
 
 /* ---- population-based training on the device: fitness, exploit, explore (the law is csrc/adc_pbt.h) ---------------------------
  * A scheduler (Jaderberg et al. 2017: truncation selection, copy, perturb) over a live learner population - adc_engine_pg_pop_*

@@ -130,6 +130,36 @@ ADC_HD U4 draw_kw(uint64_t key, uint32_t index, KwHalf h, uint32_t tick)
     return philox4x32_kw(index, h, tick, (uint32_t)key, (uint32_t)(key >> 32));
 }
 
+// Round 1 reads tick and k1 only through tick ^ k1 (c2 = hi(M0 index) ^ tick ^ k1).  A kernel that holds both in scalar registers
+// folds the word once (philox_fold_tick) and hands it to draw_folded / draw_kw_folded: the call's xor then has one uniform operand
+// instead of two (a VOP3 instruction reads one SGPR; the second costs a v_mov_b32 per call).  The same bits as draw / draw_kw.
+ADC_HD uint32_t philox_fold_tick(uint64_t key, uint32_t tick) { return tick ^ (uint32_t)(key >> 32); }
+
+// rounds 2 .. kPhiloxRounds from the state after round 1 (k0, k1: the key as given to round 1)
+ADC_HD U4 philox4x32_after_round1(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 1; r < kPhiloxRounds; ++r) {
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+        philox_round(c0, c1, c2, c3, k0, k1);
+    }
+    return U4{c0, c1, c2, c3};
+}
+
+// draw_kw(key, index, h, tick) with tick_k1 = philox_fold_tick(key, tick)
+ADC_HD U4 draw_kw_folded(uint64_t key, uint32_t index, KwHalf h, uint32_t tick_k1)
+{
+    const uint64_t a = (uint64_t)0xD2511F53u * index;
+    return philox4x32_after_round1(h.c0, h.c1, (uint32_t)(a >> 32) ^ tick_k1, (uint32_t)a, (uint32_t)key, (uint32_t)(key >> 32));
+}
+
+// draw(key, index, stage, keyword, tick) with tick_k1 = philox_fold_tick(key, tick)
+ADC_HD U4 draw_folded(uint64_t key, uint32_t index, uint32_t stage, uint32_t keyword, uint32_t tick_k1)
+{
+    return draw_kw_folded(key, index, philox_kw_half(stage, keyword, (uint32_t)key), tick_k1);
+}
+
 // the volume word of keyword k: one call serves four consecutive keywords
 ADC_HD uint32_t volume_word(uint64_t key, uint32_t k, uint32_t tick)
 {
@@ -442,6 +472,19 @@ ADC_HD int32_t competitor_cents_from_v(uint32_t v24, float loc, float scale, Tab
     float c = __builtin_rintf(__builtin_fabsf(x) * 100.0f);
     c = c < kMoneyMaxCents ? c : kMoneyMaxCents;          // (NaN -> 1e9: a NaN parameter never wins)
     return (int32_t)c;
+}
+
+// competitor_cents_from_v without the clamp, for a v that win_intervals has PROVEN a win: v in [W_lo, W_hi) of a bid of bid_c
+// cents means -(bid_c - 1) <= S(v) <= bid_c - 1 with S = signed_cents_from_v, clamp included, and bid_c <= 1e9 (bid_to_cents).
+// So |S(v)| < 1e9, which the clamp turns no value into that it did not find below 1e9 already: a rounded c >= 1e9 and a NaN
+// (a NaN parameter) both come out of it as 1e9, which is no win at any bid.  The clamp therefore never acts on a win, and the
+// price is the rounded value as it stands.  Every other caller - the DIRECT form, the oracle, win_intervals itself - resolves
+// auctions that may be lost and keeps competitor_cents_from_v.  (tests/test_law_hoists_host.py: every v of the intervals' ends.)
+template <typename Tab>
+ADC_HD int32_t competitor_cents_of_proven_win(uint32_t v24, float loc, float scale, Tab tab)
+{
+    const float x = fma32(__builtin_fabsf(scale), laplace_deviate_from_v(v24, tab), loc);
+    return (int32_t)__builtin_rintf(__builtin_fabsf(x) * 100.0f);
 }
 
 // the 24-bit uniform of an auction word (click decided, offset rescaled inside its sub-interval)

@@ -252,6 +252,77 @@ ADC_EXPORT int adc_win_intervals_host(int64_t n, const int32_t *bid_c, const flo
     return ADC_OK;
 }
 
+// ---- what the dense fast pass hoists out of its stages (adc_law.h), next to the routines it replaces there: for
+// tests/test_law_hoists_host.py ----------------------------------------------------------------------------------------------
+// n calls: plain4 = adc::draw, folded4 = adc::draw_folded, kw4 = adc::draw_kw_folded from the keyword's half (four words each)
+ADC_EXPORT int adc_draw_folded_host(int64_t n, const uint64_t *key, const uint32_t *index, const uint32_t *stage, const uint32_t *keyword,
+                                    const uint32_t *tick, uint32_t *plain4, uint32_t *folded4, uint32_t *kw4)
+{
+    if (n < 0 || (n > 0 && (!key || !index || !stage || !keyword || !tick || !plain4 || !folded4 || !kw4))) return ADC_EINVAL;
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const uint32_t tick_k1 = adc::philox_fold_tick(key[i], tick[i]);
+            const adc::U4 a = adc::draw(key[i], index[i], stage[i], keyword[i], tick[i]);
+            const adc::U4 b = adc::draw_folded(key[i], index[i], stage[i], keyword[i], tick_k1);
+            const adc::U4 c = adc::draw_kw_folded(key[i], index[i], adc::philox_kw_half(stage[i], keyword[i], (uint32_t)key[i]), tick_k1);
+            uint32_t *pa = plain4 + 4 * i, *pb = folded4 + 4 * i, *pc = kw4 + 4 * i;
+            pa[0] = a.x; pa[1] = a.y; pa[2] = a.z; pa[3] = a.w;
+            pb[0] = b.x; pb[1] = b.y; pb[2] = b.z; pb[3] = b.w;
+            pc[0] = c.x; pc[1] = c.y; pc[2] = c.z; pc[3] = c.w;
+        }
+    });
+    return ADC_OK;
+}
+
+// For n keywords (bid in cents): every v of the keyword's win range [W_lo, W_hi) (adc::lower_bound_pair, what adc::win_intervals
+// is made of) if the range has at most `exhaustive_below` values, otherwise its `ends` first and last values and `samples` drawn
+// ones; and through the words, as stage B of the kernel does: the first and last word of the clicked-win interval, rescaled.  At
+// each, adc::competitor_cents_of_proven_win against adc::competitor_cents_from_v.  Returns the number of values that differ
+// (first_bad3 = {keyword, v, 0 / 1 for the word route} of the first, or -1s); *checked = values compared.
+ADC_EXPORT int64_t adc_proven_win_price_host(int64_t n, const int32_t *bid_c, const float *cost_loc, const float *cost_scale, const float *buyside_ctr,
+                                             int64_t exhaustive_below, int32_t ends, int32_t samples, uint64_t seed, int64_t *checked, int64_t *first_bad3)
+{
+    if (n < 0 || (n > 0 && (!bid_c || !cost_loc || !cost_scale || !buyside_ctr)) || ends < 0 || samples < 0) return -1;
+    const adc::LogTableEntry *table = host_log_table();
+    int64_t bad = 0, count = 0, first[3] = {-1, -1, -1};
+    uint64_t s = seed | 1ull;
+    auto next = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
+    for (int64_t i = 0; i < n; ++i) {
+        const float loc = cost_loc[i], scale = cost_scale[i];
+        auto check = [&](uint32_t v, int route) {
+            ++count;
+            if (adc::competitor_cents_of_proven_win(v, loc, scale, table) != adc::competitor_cents_from_v(v, loc, scale, table)) {
+                if (first[0] < 0) { first[0] = i; first[1] = (int64_t)v; first[2] = route; }
+                ++bad;
+            }
+        };
+        uint32_t w_lo, w_hi;
+        int stage = 0;
+        adc::lower_bound_pair(bid_c[i], loc, scale, table, w_lo, w_hi, stage);
+        if (w_lo < w_hi) {
+            const uint32_t width = w_hi - w_lo;
+            if ((int64_t)width <= exhaustive_below) {
+                for (uint32_t v = w_lo; v < w_hi; ++v) check(v, 0);
+            } else {
+                for (uint32_t e = 0; e < (uint32_t)ends && e < width; ++e) { check(w_lo + e, 0); check(w_hi - 1u - e, 0); }
+                for (int32_t k = 0; k < samples; ++k) check(w_lo + (uint32_t)(next() % width), 0);
+            }
+        }
+        const adc::AuctionLaw law = adc::make_auction_law(buyside_ctr[i]);
+        const adc::WinIntervals iv = adc::win_intervals_of_bounds(w_lo, w_hi, adc::bernoulli_threshold(buyside_ctr[i]), law);
+        if (iv.c_w != 0u) {
+            for (int e = 0; e < 2; ++e) {
+                const uint32_t word = e == 0 ? iv.c_lo : iv.c_lo + iv.c_w - 1u;
+                const uint32_t v = adc::mulhi32(word, law.m_click);
+                check(v < 0x00FFFFFFu ? v : 0x00FFFFFFu, 1);
+            }
+        }
+    }
+    if (checked) *checked = count;
+    if (first_bad3) { first_bad3[0] = first[0]; first_bad3[1] = first[1]; first_bad3[2] = first[2]; }
+    return bad;
+}
+
 // ---- the host twin of k_step_implicit_fast's phase-2 schedule (adc_fast_schedule.h: the helpers the kernel calls) ------------
 // For tile number tile_index (env x tiles-per-env + tile: it only rotates which wave takes which part of the items) of tile_kw
 // keywords with the given volumes: every (pass, wave, round, lane) slot the kernel issues, as rows of

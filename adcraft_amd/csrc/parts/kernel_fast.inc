@@ -31,7 +31,7 @@ struct alignas(16) KwLawB {
             unsigned int t_click; // saturated click threshold           (DIRECT stage A)
             int bid_c;            // the bid in cents                    (DIRECT stage A)
         } d;
-        adc::KwHalf conv;         // interval form: the keyword's half of round 1 of its ST_CONV draws (stage B, adc::draw_kw)
+        adc::KwHalf conv;         // interval form: the keyword's half of round 1 of its ST_CONV draws (stage B, adc::draw_kw_folded)
     };
 };
 union alignas(16) KwWin {                     // per keyword, 16 B
@@ -177,6 +177,11 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     const uint64_t key = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(raw.key >> 32)) << 32) |
                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)raw.key);
     const uint32_t tick = (uint32_t)__builtin_amdgcn_readfirstlane((int)raw.tick);
+    // tick ^ key_hi, all that round 1 of a Philox call reads of the two: folded here on the scalar unit, once per tile, so that the
+    // call's xor has one SGPR operand (with two, hipcc stages one in a VGPR: a v_mov_b32 per call in stage A and per clicked win
+    // in stage B).  Opaque, or the xor is re-associated into the three-input form again.
+    uint32_t tick_k1 = adc::philox_fold_tick(key, tick);
+    asm volatile("" : "+s"(tick_k1));
     const uint32_t kw_base = (uint32_t)(tile * tile_kw);
     if (LISTS && raw.emit && tid == 0) v.click_tick[env] = tick + 1u;      // (every tile of the env writes the same value)
     if constexpr (LISTS) { if (raw.emit && !NARROW && tid < adc::kTimesteps) ls.row_count[tid] = 0u; }      // (before phase 1's barriers)
@@ -313,17 +318,23 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         unsigned int acc_off = uu * (unsigned int)sizeof(unsigned long long);
         asm volatile("" : "+v"(acc_off));
         unsigned long long *const acc = (unsigned long long *)((char *)sh.a_cnt + acc_off);      // a_cnt[uu]; a_cost, a_rev follow at kFastBlock strides
-        const KwLawA ka = sh.law_a[uu];
-        const KwLawB kb = sh.law_b[uu];
+        // the keyword's 16-byte law records by that offset added to itself (a full-rate add; uu * 16 from the tag's byte is a second
+        // half-rate shift)
+        static_assert(sizeof(KwLawA) == 2 * sizeof(unsigned long long) && sizeof(KwLawB) == sizeof(KwLawA), "law records at twice the accumulators' stride");
+        unsigned int law_off;
+        asm volatile("v_add_u32 %0, %1, %1" : "=v"(law_off) : "v"(acc_off));      // (written as x + x, hipcc emits v_lshlrev_b32 x, 1)
+        const KwLawA ka = *(const KwLawA *)((const char *)sh.law_a + law_off);
+        const KwLawB kb = *(const KwLawB *)((const char *)sh.law_b + law_off);
         unsigned int price = ent.y;
         if (!direct) {
             unsigned int vv = adc::mulhi32(ent.y, ka.m_click);                        // a click: the offset is the word itself
             vv = vv < 0x00FFFFFFu ? vv : 0x00FFFFFFu;
-            price = (unsigned int)adc::competitor_cents_from_v(vv, ka.loc, ka.scale, sh.logtab);
+            // (the entry is a win by the keyword's intervals: the price needs no clamp - adc_law.h)
+            price = (unsigned int)adc::competitor_cents_of_proven_win(vv, ka.loc, ka.scale, sh.logtab);
         }
         // (interval form: the draw starts from the keyword's half of round 1, kept in law_b by phase 1 - the same bits)
-        const adc::U4 w2 = direct ? adc::draw(key, ent.x & 0x00FFFFFFu, adc::ST_CONV, kw_base + uu, tick)
-                                  : adc::draw_kw(key, ent.x & 0x00FFFFFFu, kb.conv, tick);
+        const adc::U4 w2 = direct ? adc::draw_folded(key, ent.x & 0x00FFFFFFu, adc::ST_CONV, kw_base + uu, tick_k1)
+                                  : adc::draw_kw_folded(key, ent.x & 0x00FFFFFFu, kb.conv, tick_k1);
         const bool conv = adc::bernoulli32(w2.x, ka.t_conv);
         unsigned long long cnt = 1ull << kClkShift;
         if (conv) {
@@ -388,15 +399,21 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         constexpr bool TAIL = decltype(tail_tag)::value;
         const uint32_t kw = kw_base + (uint32_t)u;
         const unsigned int tagj0 = ((unsigned int)u << 24) | (unsigned int)j0;
+        // the item's first Philox call: j0 is a multiple of 4 on all three paths (full items, tail calls, the partial call -
+        // adc_fast_schedule.h), which the compiler cannot see, so the calls of the item are j0 / 4, + 1, ...: one add per call,
+        // where (j0 + i) >> 2 is an add and a shift
+        const uint32_t call0 = (uint32_t)j0 >> adc::kFastCallShift;
         unsigned int imp = 0;
         if (dense) {
             adc::WinIntervals iv = sh.win[u].iv;
             if (n == 0) iv.c_w = iv.n_w = 0u;                                       // a lane without an item resolves nothing
             asm volatile("" : "+v"(iv.c_w), "+v"(iv.n_w));      // (opaque: hipcc otherwise turns the zero width into `has-item && ...` on every compare)
-            for (int i = 0; i < calls4; i += 4) {
+            uint32_t call = call0;
+            for (int i = 0; i < calls4; i += 4, call += 1u) {
                 if (TAIL && __builtin_amdgcn_ballot_w64(i < n) == 0ull) break;
                 FSLOT_ADD(0, 1ull);
-                const adc::U4 w = adc::draw(key, (uint32_t)(j0 + i) >> 2, adc::ST_AUCTION, kw, tick);
+                asm volatile("" : "+v"(call));      // (opaque: hipcc otherwise carries the call's 64-bit product from call to call, in two VGPRs more)
+                const adc::U4 w = adc::draw_folded(key, call, adc::ST_AUCTION, kw, tick_k1);
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
                     const uint32_t word = h == 0 ? w.x : h == 1 ? w.y : h == 2 ? w.z : w.w;
@@ -414,10 +431,12 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             const KwLawB kb = sh.law_b[u];
             const adc::AuctionLaw law{kb.d.t_click, ka.m_click, sh.win[u].d.m_noclick};
             const int bid_c = n > 0 ? kb.d.bid_c : 0;                               // (bid 0 never wins)
-            for (int i = 0; i < calls4; i += 4) {
+            uint32_t call = call0;
+            for (int i = 0; i < calls4; i += 4, call += 1u) {
                 if (TAIL && __builtin_amdgcn_ballot_w64(i < n) == 0ull) break;
                 FSLOT_ADD(0, 1ull);
-                const adc::U4 w = adc::draw(key, (uint32_t)(j0 + i) >> 2, adc::ST_AUCTION, kw, tick);
+                asm volatile("" : "+v"(call));      // (opaque: hipcc otherwise carries the call's 64-bit product from call to call, in two VGPRs more)
+                const adc::U4 w = adc::draw_folded(key, call, adc::ST_AUCTION, kw, tick_k1);
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
                     const uint32_t word = h == 0 ? w.x : h == 1 ? w.y : h == 2 ? w.z : w.w;

@@ -1351,6 +1351,18 @@ int adc_lower_bound_v_bisect_host(int64_t n, const int32_t *target_n, const floa
                                   uint8_t *whole_range_n);
 int adc_win_intervals_host(int64_t n, const int32_t *bid_cents_n, const float *cost_loc_n, const float *cost_scale_n,
                            const float *buyside_ctr_n, int32_t bisect, uint32_t *out4_n, uint8_t *stage_n);
+/* diagnostic: what the dense budget-free pass hoists out of its per-auction stages (adc_law.h), on the host, next to the routines it
+ * stands for.  adc_draw_folded_host: n Philox calls three ways, four words each - the plain draw, the draw from the folded
+ * (tick ^ key >> 32) word, and that draw started from the keyword's half of round 1; all three must agree.
+ * adc_proven_win_price_host: for n keywords (bid in cents), the competitor's price without its clamp against the clamped one at
+ * values of the keyword's win range - all of them where the range has at most exhaustive_below, else `ends` at either end and
+ * `samples` drawn with `seed` - and at the two end words of the clicked-win interval; returns how many differ (first_bad3 =
+ * {keyword, value, route} of the first or -1s, checked = values compared; both may be NULL), negative on bad arguments. */
+int adc_draw_folded_host(int64_t n, const uint64_t *key_n, const uint32_t *index_n, const uint32_t *stage_n, const uint32_t *keyword_n,
+                         const uint32_t *tick_n, uint32_t *plain4_n, uint32_t *folded4_n, uint32_t *kw4_n);
+int64_t adc_proven_win_price_host(int64_t n, const int32_t *bid_cents_n, const float *cost_loc_n, const float *cost_scale_n,
+                                  const float *buyside_ctr_n, int64_t exhaustive_below, int32_t ends, int32_t samples, uint64_t seed,
+                                  int64_t *checked, int64_t *first_bad3);
 /* diagnostic: how the budget-free IMPLICIT pass deals one tile's auctions to its lanes, on the host (the schedule arithmetic the
  * kernel calls, csrc/adc_fast_schedule.h).  vol_k = the volumes of the tile's tile_kw (1..256) keywords; tile_index (>= 0) = env x
  * tiles per env + tile, which only rotates the parts of the item range among the four waves.  Every issue slot becomes a

@@ -22,6 +22,7 @@ ROLLOUT_OBS = 1
 PG_ADAM, PG_SGD = 0, 1
 TD3_ADAM, TD3_SGD = 0, 1
 PBT_PG, PBT_TD3 = 0, 1
+PBT_SAC = 3        # (2 is unassigned)
 
 
 class EngineError(RuntimeError):
@@ -431,6 +432,7 @@ def lib():
         "adc_td3_config_check": ([C.POINTER(TD3Config), C.POINTER(C.c_char_p)], C.c_int),
         "adc_pbt_config_check": ([C.POINTER(PBTConfig), i32, i32, C.POINTER(C.c_char_p)], C.c_int),
         "adc_engine_pbt_init": ([vp, C.POINTER(PBTConfig)], C.c_int),
+        "adc_engine_pbt_init_sac": ([vp, C.POINTER(PBTConfig)], C.c_int),
         "adc_engine_pbt_fitness": ([vp, vp], C.c_int),
         "adc_engine_pbt_exploit": ([vp, vp], C.c_int),
         "adc_engine_pbt_step": ([vp, vp, C.POINTER(PBTResult)], C.c_int),

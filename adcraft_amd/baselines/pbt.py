@@ -1,5 +1,5 @@
 """Population-based training (Jaderberg et al. 2017: truncation selection, copy, perturb) over a learner population that
-trains on one engine: PGPopulationTrainer or TD3PopulationTrainer.  A round runs on the device (StepEngine.pbt_step; the law is
+trains on one engine: PGPopulationTrainer, TD3PopulationTrainer or SACPopulationTrainer.  A round runs on the device (StepEngine.pbt_step; the law is
 csrc/adc_pbt.h): the members' fitness is reduced from the rollout record there, the worst `replace_fraction` of the members
 become copies of members drawn among the best in one batched copy, and the copied members' tuned hyperparameters are the
 donors' times one of two factors, clamped to their bounds.  The launches and host round trips of a round do not grow with the
@@ -7,16 +7,19 @@ number of members."""
 import numpy as np
 
 from .pg_trainer import PGPopulationTrainer
+from .sac_trainer import SACPopulationTrainer
 from .td3_trainer import TD3PopulationTrainer
 
 
 class PBTScheduler:
-    """trainer: a PGPopulationTrainer or a TD3PopulationTrainer of at least 2 members; replace_fraction: the share of the
+    """trainer: a PGPopulationTrainer, a TD3PopulationTrainer or a SACPopulationTrainer of at least 2 members; replace_fraction: the share of the
     members replaced in a round (at least one member, at most half of them); tuned: names of the hyperparameters explored -
-    PG: lr, ent_coef, eps_clip, vf_coef; TD3: actor_lr, critic_lr, target_noise, tau, sigma (the exploration's); bounds:
+    PG: lr, ent_coef, eps_clip, vf_coef; TD3: actor_lr, critic_lr, target_noise, tau, sigma (the exploration's); SAC: actor_lr,
+    critic_lr, alpha_lr, tau, alpha (the temperature itself, on the device: it has no host mirror, and for a member with
+    alpha_lr 0 exploring it is a search over the fixed temperature), target_entropy; bounds:
     {name: (lo, hi)} for every tuned name; factors: the two perturbation factors; fitness_ema: the weight of the past in the
     smoothed fitness the members are ranked by (0: the round's fitness alone); every: a round every so many step() calls;
-    with_ring (TD3): a copied member gets its donor's replay ring too; seed 0: the engine's.
+    with_ring (TD3, SAC): a copied member gets its donor's replay ring too; seed 0: the engine's.
 
     step() follows trainer.iteration(): it reads the fitness from the days that iteration recorded."""
 
@@ -26,8 +29,10 @@ class PBTScheduler:
             self.kind = "pg"
         elif isinstance(trainer, TD3PopulationTrainer):
             self.kind = "td3"
+        elif isinstance(trainer, SACPopulationTrainer):
+            self.kind = "sac"
         else:
-            raise TypeError("PBTScheduler: a PGPopulationTrainer or a TD3PopulationTrainer")
+            raise TypeError("PBTScheduler: a PGPopulationTrainer, a TD3PopulationTrainer or a SACPopulationTrainer")
         M = trainer.members
         if M < 2:
             raise ValueError("PBTScheduler: at least 2 members")
@@ -50,7 +55,7 @@ class PBTScheduler:
     def step(self, fitness=None):
         """to be called after trainer.iteration(); every `every`-th call runs a round (fitness: [M] handed in, or None: the
         device's from the record) and returns its result, the others return None.  The trainer's configuration dicts (and, for
-        TD3's sigma, its templates' log_std) follow the round."""
+        TD3's sigma, its templates' log_std) follow the round; SAC's alpha has no host mirror."""
         self.calls += 1
         if self.calls % self.every:
             return None
@@ -73,6 +78,8 @@ class PBTScheduler:
             self.origin[m] = self.origin[src]
             for name in self.tuned:
                 h = self.ids.index(name)
+                if name == "alpha":
+                    continue                # (the temperature cell is the device's; init_alpha in the dicts is not state)
                 if name == "sigma":
                     v = (old_log_std[src] + np.float32(res["hp"][m, h])).astype(np.float32)
                     tr._templates[m].log_std = np.minimum(np.maximum(v, self._sigma_bounds[0]), self._sigma_bounds[1]).astype(np.float32)

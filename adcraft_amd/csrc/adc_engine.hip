@@ -59,7 +59,7 @@
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/kernel_sac_pop.inc      SAC learner populations: the k_sac_pop_* twins of kernel_sac.inc, the member one more grid dimension.
-//   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy (adc_pbt.h).
+//   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy, SAC's temperature cells (adc_pbt.h).
 //   parts/kernel_norm.inc         the running normalisers, one set of kernels: the record's batch moments of the observations in one pass,
 //        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
 //        the learner's discount, their moments, the merge, the multiplier, the GAE kernels under a multiplier and a clip (adc_rew_norm.h);
@@ -71,7 +71,7 @@
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training.
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
 //   parts/sac_pop_api.inc         the entry points of SAC learner populations, over td3_pop_api.inc's helpers.
-//   parts/pbt_api.inc             the entry points of the population-based training scheduler over either kind of population.
+//   parts/pbt_api.inc             the entry points of the population-based training scheduler over a PG, TD3 or SAC population.
 //   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners' - over shared helpers.
 //
 // No CPU path exists in this library.

@@ -1,9 +1,9 @@
 // adc_pbt.h - the law of the population-based training scheduler (PBT: Jaderberg et al. 2017 - truncation selection, copy,
-// perturb) over a learner population (adc_engine_pg_pop_* or adc_engine_td3_pop_*): a round's fitness, its smoothing, the
-// ranking, the donor draw and the explored hyperparameters.  Shared by the device kernel k_pbt_fitness (parts/kernel_pbt.inc),
+// perturb) over a learner population (adc_engine_pg_pop_*, adc_engine_td3_pop_* or adc_engine_sac_pop_*): a round's fitness, its
+// smoothing, the ranking, the donor draw and the explored hyperparameters.  Shared by the device kernel k_pbt_fitness (parts/kernel_pbt.inc),
 // the host flow of adc_engine_pbt_step (parts/pbt_api.inc: ranking, draw and explore run on the host, from M doubles) and the
-// host twins adc_pbt_fitness_host / adc_pbt_plan_host / adc_pbt_explore_host (adc_shims.cpp); tests/pbt_ref.py restates these
-// comments in numpy, bit for bit.
+// host twins adc_pbt_fitness_host / adc_pbt_plan_host / adc_pbt_explore_host (adc_shims.cpp); tests/pbt_ref.py (SAC:
+// tests/pbt_sac_ref.py) restates these comments in numpy, bit for bit.
 //
 // Every value below is the result of ONE correctly rounded IEEE operation (-ffp-contract=off); "f64" marks float64.
 //
@@ -22,13 +22,21 @@
 //   explore    for every hyperparameter id h in tuned_mask: v = the donor's value; f = bit h of w.y ? factor_hi : factor_lo;
 //              v' = v * f (one float32 product), then v' < lo[h] ? lo[h] : v', then v' > hi[h] ? hi[h] : v'.  Ids outside the
 //              mask keep the replaced member's own value.  ids - PG: 0 lr, 1 ent_coef, 2 eps_clip, 3 vf_coef; TD3: 0 actor_lr,
-//              1 critic_lr, 2 target_noise, 3 tau, 4 sigma.
+//              1 critic_lr, 2 target_noise, 3 tau, 4 sigma; SAC: 0 actor_lr, 1 critic_lr, 2 alpha_lr, 3 tau, 4 alpha,
+//              5 target_entropy (usually negative: the one product and the two compares need no special case).  Id 4 is, for
+//              TD3 and SAC alike, the one that lives on the device and moves in the log domain.
 //   sigma      TD3's exploration sigma is the member's learner log_std[A] on the device and moves in the log domain: every
 //              component becomes the donor's component + (bit 4 of w.y ? log_factor_hi : log_factor_lo) (one float32 sum), then
 //              clamped to [lo[4], hi[4]], both in log units, as above.  The two log factors are fields of the configuration
 //              (float32(log(factor)) is the caller's to fill): the law calls no log.
+//   alpha      SAC's temperature is the member's cell {log_alpha, m, v, alpha} on the device (adc_sac.h).  With id 4 tuned a
+//              replaced member's cell becomes: la' = the donor's log_alpha + (bit 4 of w.y ? log_factor_hi : log_factor_lo) (one
+//              float32 sum), clamped to [lo[4], hi[4]], both in log units, as above; m and v the donor's; alpha = mlp_exp(la'),
+//              the function sac_alpha_step forms it with.  For a member with alpha_lr == 0 this is the search over the fixed
+//              temperature itself.  With id 4 untuned the cell is the donor's four floats verbatim.
 //   then       a replaced member has its donor's s (and, PG, its donor's step count); it keeps its envs, its agents' keys and
-//              ticks and (TD3) its seed; round = round + 1.
+//              ticks, (TD3, SAC) its seed and every field of its configuration that is not a tuned id (SAC's init_alpha is not
+//              touched: the cell is state); round = round + 1.
 #pragma once
 #include "adc_mlp.h"
 #include <algorithm>
@@ -37,9 +45,10 @@
 namespace adc {
 
 constexpr uint32_t ST_PBT = 18;
-constexpr int kPbtPg = 0, kPbtTd3 = 1;
+constexpr int kPbtPg = 0, kPbtTd3 = 1, kPbtSac = 3;
 constexpr int kPbtMaxHp = 8;
 constexpr int kPbtPgIds = 4, kPbtTd3Ids = 5, kPbtSigma = 4;
+constexpr int kPbtSacIds = 6, kPbtAlpha = 4;
 
 ADC_HD uint64_t pbt_key(uint64_t seed) { return mlp_mix64(seed ^ 0xBB67AE8584CAA73Bull); }
 
@@ -73,6 +82,13 @@ ADC_HD float pbt_explore_log(float donor, float log_factor, float lo, float hi)
 {
     const float v = donor + log_factor;
     return pbt_clamp(v, lo, hi);
+}
+
+// a replaced SAC member's temperature cell {log_alpha, m, v, alpha} from its donor's (id 4 tuned)
+ADC_HD void pbt_explore_cell(const float donor[4], float log_factor, float lo, float hi, float out[4])
+{
+    const float la = pbt_explore_log(donor[0], log_factor, lo, hi);
+    out[0] = la; out[1] = donor[1]; out[2] = donor[2]; out[3] = mlp_exp(la);
 }
 
 // order[r] = the member of rank r (host only: M values)

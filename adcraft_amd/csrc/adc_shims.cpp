@@ -1567,14 +1567,14 @@ ADC_EXPORT int adc_pbt_config_check(const adc_pbt_config *cfg, int32_t members, 
     const char *msg = nullptr;
     const float inf = __builtin_inff();
     if (!cfg || cfg->struct_size != sizeof(adc_pbt_config)) msg = "adc_pbt_config: NULL or struct_size mismatch";
-    else if (kind != ADC_PBT_PG && kind != ADC_PBT_TD3) msg = "kind: ADC_PBT_PG or ADC_PBT_TD3";
+    else if (kind != ADC_PBT_PG && kind != ADC_PBT_TD3 && kind != ADC_PBT_SAC) msg = "kind: ADC_PBT_PG, ADC_PBT_TD3 or ADC_PBT_SAC";
     else if (members < 2) msg = "population-based training needs at least 2 members";
     else if (cfg->replace_count < 1 || cfg->replace_count > members / 2) msg = "replace_count: 1 to members / 2";
     else if (!(cfg->fitness_ema >= 0.0f && cfg->fitness_ema < 1.0f)) msg = "fitness_ema: 0 (no smoothing) to below 1";
     else if (!(cfg->factor_lo > 0.0f && cfg->factor_lo < inf) || !(cfg->factor_hi > 0.0f && cfg->factor_hi < inf)) msg = "factor_lo, factor_hi: positive and finite";
     else if (!(cfg->log_factor_lo > -inf && cfg->log_factor_lo < inf) || !(cfg->log_factor_hi > -inf && cfg->log_factor_hi < inf))
         msg = "log_factor_lo, log_factor_hi: finite";
-    else if (cfg->tuned_mask >> (kind == ADC_PBT_PG ? adc::kPbtPgIds : adc::kPbtTd3Ids)) msg = "tuned_mask names a hyperparameter id the trainer does not have";
+    else if (cfg->tuned_mask >> (kind == ADC_PBT_PG ? adc::kPbtPgIds : kind == ADC_PBT_SAC ? adc::kPbtSacIds : adc::kPbtTd3Ids)) msg = "tuned_mask names a hyperparameter id the trainer does not have";
     else if (cfg->with_ring != 0 && cfg->with_ring != 1) msg = "with_ring: 0 or 1";
     else if (kind == ADC_PBT_PG && cfg->with_ring) msg = "with_ring: a policy-gradient population has no ring";
     else
@@ -1583,8 +1583,9 @@ ADC_EXPORT int adc_pbt_config_check(const adc_pbt_config *cfg, int32_t members, 
             const float lo = cfg->lo[h], hi = cfg->hi[h];
             if (!(lo > -inf && hi < inf && lo <= hi)) msg = "lo, hi of a tuned hyperparameter: finite, lo <= hi";
             else if (kind == ADC_PBT_PG && h == 2) { if (!(hi < 1.0f)) msg = "eps_clip: hi below 1"; }
-            else if (kind == ADC_PBT_TD3 && h == 3) { if (!(lo > 0.0f && hi <= 1.0f)) msg = "tau: lo above 0, hi at most 1"; }
+            else if ((kind == ADC_PBT_TD3 || kind == ADC_PBT_SAC) && h == 3) { if (!(lo > 0.0f && hi <= 1.0f)) msg = "tau: lo above 0, hi at most 1"; }
             else if (kind == ADC_PBT_TD3 && h == adc::kPbtSigma) { }
+            else if (kind == ADC_PBT_SAC && (h == adc::kPbtAlpha || h == 5)) { }        // (log_alpha and target_entropy: any sign)
             else if (!(lo >= 0.0f)) msg = "lo of a learning rate, a coefficient or a noise: at least 0";
         }
     if (message) *message = msg;
@@ -1622,11 +1623,12 @@ ADC_EXPORT int adc_pbt_plan_host(const adc_pbt_config *cfg, uint64_t seed, int32
 
 ADC_EXPORT int adc_pbt_explore_host(const adc_pbt_config *cfg, int32_t kind, uint32_t bits, const float *donor_hp8, const float *own_hp8, float *out_hp8)
 {
-    if (!cfg || cfg->struct_size != sizeof(adc_pbt_config) || (kind != ADC_PBT_PG && kind != ADC_PBT_TD3) || !donor_hp8 || !own_hp8 || !out_hp8)
+    if (!cfg || cfg->struct_size != sizeof(adc_pbt_config) || (kind != ADC_PBT_PG && kind != ADC_PBT_TD3 && kind != ADC_PBT_SAC) || !donor_hp8 || !own_hp8 || !out_hp8)
         return ADC_EINVAL;
     for (int h = 0; h < adc::kPbtMaxHp; ++h) {
         const int up = (int)((bits >> h) & 1u);
         if (!((cfg->tuned_mask >> h) & 1u)) out_hp8[h] = own_hp8[h];
+        else if (kind == ADC_PBT_SAC && h == adc::kPbtAlpha) out_hp8[h] = own_hp8[h];      // (the temperature cell is the device's: k_pbt_exploit_cell)
         else if (kind == ADC_PBT_TD3 && h == adc::kPbtSigma)
             out_hp8[h] = adc::pbt_explore_log(donor_hp8[h], up ? cfg->log_factor_hi : cfg->log_factor_lo, cfg->lo[h], cfg->hi[h]);
         else out_hp8[h] = adc::pbt_explore(donor_hp8[h], up, cfg->factor_lo, cfg->factor_hi, cfg->lo[h], cfg->hi[h]);

@@ -226,7 +226,7 @@ struct adc_engine {
     std::vector<SacMember> sp_mem;              // [M] the host's copy of sp_dmem
     SacMember *sp_dmem = nullptr;
     float *sp_cells = nullptr;                  // [M][4] {log_alpha, m, v, alpha} on the device
-    // the population-based training scheduler over the live pg_pop or td3_pop trainer (parts/pbt_api.inc; the law is adc_pbt.h).
+    // the population-based training scheduler over the live pg_pop, td3_pop or sac_pop trainer (parts/pbt_api.inc; the law is adc_pbt.h).
     // Its device arrays are the trainer's allocations (pg_allocs / td3_allocs): they go with it
     bool have_pbt = false;
     int pbt_kind = 0;                           // adc_pbt_kind
@@ -2973,6 +2973,7 @@ void td3_drop(adc_engine *e)
 {
     norm_set_drop(e, e->tn);            // (the record is back to network inputs)
     pbt_forget(e, ADC_PBT_TD3);
+    pbt_forget(e, ADC_PBT_SAC);         // (a SAC population's scheduler: its arrays are among td3_allocs too)
     mlp_free(e, e->td3_allocs);
     e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
     e->have_sac = false;                // (a soft actor-critic learner lives in the same fields, and ends where TD3 ends)

@@ -2,7 +2,9 @@
 // fitness from the rollout record where it lies, and the exploit - every replaced member made a copy of its donor from a
 // (dst, src) table in a fixed number of launches, whatever the number of pairs.  No destination is a source (the plan's
 // selection, checked by the host for a plan handed in), so a launch reads donors and writes destinations and the pairs' order
-// cannot matter; a donor read by several destinations is only read.  No atomics; all stores are plain vector stores.
+// cannot matter; a donor read by several destinations is only read.  No atomics; all stores are plain vector stores.  Over a SAC
+// population (kind ADC_PBT_SAC) k_pbt_exploit and k_pbt_exploit_ring run as they are and k_pbt_exploit_cell copies or explores the
+// temperature cells.
 // (part of the single translation unit adc_engine.hip)
 struct PbtPair {
     int dst, src;
@@ -108,4 +110,20 @@ __global__ __launch_bounds__(kPbtBlock) void k_pbt_exploit_ring(const Td3Member 
     default: dp = d.done; sp = s.done; bytes = C; break;
     }
     pbt_copy_bytes(dp, sp, bytes, lane, lanes);
+}
+
+// SAC: one lane per pair, the temperature cells [M][4] = {log_alpha, m, v, alpha}: dst's cell is src's four floats verbatim, or -
+// the pair's `sigma` flag set (id 4 tuned) - the law's explored cell: log_alpha shifted by log_factor and clamped to [la_lo, la_hi],
+// src's m and v, alpha = mlp_exp of the new log_alpha.  One 16-byte load of the donor's cell, one 16-byte store (a cell is four
+// floats at a 16-byte boundary: the array is an allocation of its own)
+__global__ __launch_bounds__(kPbtBlock) void k_pbt_exploit_cell(int npairs, float *cells, const PbtPair *__restrict__ pairs, float la_lo, float la_hi)
+{
+    const int j = blockIdx.x * kPbtBlock + threadIdx.x;
+    if (j >= npairs) return;
+    const PbtPair pr = pairs[j];
+    const float4 s = *reinterpret_cast<const float4 *>(cells + (size_t)pr.src * 4u);
+    const float donor[4] = {s.x, s.y, s.z, s.w};
+    float out[4] = {s.x, s.y, s.z, s.w};
+    if (pr.sigma) adc::pbt_explore_cell(donor, pr.log_factor, la_lo, la_hi, out);
+    *reinterpret_cast<float4 *>(cells + (size_t)pr.dst * 4u) = make_float4(out[0], out[1], out[2], out[3]);
 }

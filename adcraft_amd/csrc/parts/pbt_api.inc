@@ -1,21 +1,26 @@
 // pbt_api.inc - the extern "C" entry points of the population-based training scheduler (include/adcraft_engine.h; the kernels are
-// parts/kernel_pbt.inc, the law csrc/adc_pbt.h) over the live learner population: adc_engine_pg_pop_* (parts/pg_api.inc) or
-// adc_engine_td3_pop_* (parts/td3_pop_api.inc).  The members' configurations are host-mastered there (pgp_cfg / tp_cfg and the
-// member tables made from them), so the plan - ranking, donor draw, explored values - runs on the host from the M doubles of the
-// fitness, with the law header's own functions; what is per replaced member on the device is one (dst, src) table.
+// parts/kernel_pbt.inc, the law csrc/adc_pbt.h) over the live learner population: adc_engine_pg_pop_* (parts/pg_api.inc),
+// adc_engine_td3_pop_* (parts/td3_pop_api.inc) or adc_engine_sac_pop_* (parts/sac_pop_api.inc; adc_engine_pbt_init_sac).  The
+// members' configurations are host-mastered there (pgp_cfg / tp_cfg / sp_cfg and the member tables made from them), so the plan -
+// ranking, donor draw, explored values - runs on the host from the M doubles of the fitness, with the law header's own functions;
+// what is per replaced member on the device is one (dst, src) table.
 // A round's launches and host round trips, whatever M and replace_count (read from this code, not from a trace):
 //   fitness   1 launch (k_pbt_fitness), 1 copy of M doubles down, 1 wait - or, with a fitness handed in, the wait alone (an
 //             upload of the host's member table may still be in flight);
 //   exploit   1 copy of the pair table up; PG: 1 launch; TD3: 4 launches (actor, critics, target actor, target critics; the
-//             actor's also writes the explored log_std), and 1 more for the five ring arrays with with_ring;
-//   explore   1 copy of the member table up;
+//             actor's also writes the explored log_std), and 1 more for the five ring arrays with with_ring; SAC: 4 launches
+//             (actor, critics, target critics - there is no target actor - and k_pbt_exploit_cell: the temperature cells, copied
+//             or explored), and 1 more for the ring with with_ring;
+//   explore   1 copy of the member table up (SAC: 2, its two member tables);
 //   then      1 wait.
+// So a round's host waits are 2 for every kind - one before the plan (the fitness fetch's, or the one in front of the host
+// tables' writes), one at the end - and adc_engine_pbt_exploit's are 2 as well (one in front, one at the end).
 // (part of the single translation unit adc_engine.hip)
 namespace {
 int pbt_ready(const adc_engine *e)
 {
     if (!e->have_pbt)
-        return fail(ADC_ESTATE, "adc_engine_pbt_init has not been called (or the population trainer under it, the learners, the policy or the record were re-initialised since)");
+        return fail(ADC_ESTATE, "adc_engine_pbt_init / adc_engine_pbt_init_sac has not been called (or the population trainer under it, the learners, the policy or the record were re-initialised since)");
     return ADC_OK;
 }
 // a member's hyperparameters by id, from and into its host-mastered configuration (TD3's sigma is not there: the device's log_std)
@@ -25,6 +30,9 @@ void pbt_hp_get(const adc_engine *e, int m, float hp[adc::kPbtMaxHp])
     if (e->pbt_kind == ADC_PBT_PG) {
         const adc_pg_config &c = e->pgp_cfg[(size_t)m];
         hp[0] = c.lr; hp[1] = c.ent_coef; hp[2] = c.eps_clip; hp[3] = c.vf_coef;
+    } else if (e->pbt_kind == ADC_PBT_SAC) {
+        const adc_sac_config &c = e->sp_cfg[(size_t)m];
+        hp[0] = c.actor_lr; hp[1] = c.critic_lr; hp[2] = c.alpha_lr; hp[3] = c.tau; hp[5] = c.target_entropy;
     } else {
         const adc_td3_config &c = e->tp_cfg[(size_t)m];
         hp[0] = c.actor_lr; hp[1] = c.critic_lr; hp[2] = c.target_noise; hp[3] = c.tau;
@@ -36,11 +44,26 @@ void pbt_hp_put(adc_engine *e, int m, const float hp[adc::kPbtMaxHp])
         adc_pg_config &c = e->pgp_cfg[(size_t)m];
         c.lr = hp[0]; c.ent_coef = hp[1]; c.eps_clip = hp[2]; c.vf_coef = hp[3];
         pgp_member_fill(e->pgp_mem[(size_t)m], c);
+    } else if (e->pbt_kind == ADC_PBT_SAC) {
+        // (as adc_engine_sac_pop_set_config: sp_cfg, tp_cfg through sac_as_td3, the member's rows of the two tables)
+        adc_sac_config &c = e->sp_cfg[(size_t)m];
+        c.actor_lr = hp[0]; c.critic_lr = hp[1]; c.alpha_lr = hp[2]; c.tau = hp[3]; c.target_entropy = hp[5];
+        e->tp_cfg[(size_t)m] = sac_as_td3(c);
+        sp_member_fill(e, (size_t)m, c);
     } else {
         adc_td3_config &c = e->tp_cfg[(size_t)m];
         c.actor_lr = hp[0]; c.critic_lr = hp[1]; c.target_noise = hp[2]; c.tau = hp[3];
         tp_member_fill(e, e->tp_mem[(size_t)m], c);
     }
+}
+// the five ring arrays of every pair's donor into its destination's, in one launch (TD3 and SAC populations: the members' rings are
+// tp_dmem's either way)
+void pbt_ring_launch(adc_engine *e, int npairs)
+{
+    const size_t C = (size_t)e->td3_cfg.capacity, most = C * (size_t)e->td3_shape.D * 4u;
+    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((most / 16u + kPbtBlock - 1) / kPbtBlock, 1), 256);
+    hipLaunchKernelGGL(k_pbt_exploit_ring, dim3(blocks, (unsigned)npairs, 5u), dim3(kPbtBlock), 0, e->stream, e->tp_dmem, e->pbt_dpairs, C, e->td3_shape.D,
+                       e->td3_shape.A);
 }
 // the first `npairs` entries of pbt_pairs: up in one copy, then every pair's copy in the same launches
 int pbt_exploit_launch(adc_engine *e, int npairs)
@@ -50,6 +73,19 @@ int pbt_exploit_launch(adc_engine *e, int npairs)
     if (e->pbt_kind == ADC_PBT_PG) {
         hipLaunchKernelGGL(k_pbt_exploit, dim3(pg_blocks(e->lrn_lay.Q), (unsigned)npairs), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, e->pg_theta,
                            e->pg_m, e->pg_v, e->pbt_dpairs, (float *)nullptr, (size_t)0, 0, 0.0f, 0.0f);
+    } else if (e->pbt_kind == ADC_PBT_SAC) {
+        // (the SAC population keeps its vectors, layouts and rings in the TD3 population's fields: the actor's and the critics'
+        // vectors with their two moment vectors each, the target critics' with none; no target actor, no log_std to explore)
+        for (int w = 0; w < 4; ++w) {
+            if (w == kTd3ThetaT) continue;
+            const PgLayout &lay = e->td3_lay[w];
+            float *mm = w < 2 ? e->td3_mom[2 * w] : nullptr, *mv = w < 2 ? e->td3_mom[2 * w + 1] : nullptr;
+            hipLaunchKernelGGL(k_pbt_exploit, dim3(pg_blocks(lay.Q), (unsigned)npairs), dim3(kPgBlock), 0, e->stream, lay, e->tp_stride[w], e->td3_flat[w], mm, mv,
+                               e->pbt_dpairs, (float *)nullptr, (size_t)0, 0, 0.0f, 0.0f);
+        }
+        hipLaunchKernelGGL(k_pbt_exploit_cell, dim3((unsigned)((npairs + kPbtBlock - 1) / kPbtBlock)), dim3(kPbtBlock), 0, e->stream, npairs, e->sp_cells,
+                           e->pbt_dpairs, e->pbt_cfg.lo[adc::kPbtAlpha], e->pbt_cfg.hi[adc::kPbtAlpha]);
+        if (e->pbt_cfg.with_ring) pbt_ring_launch(e, npairs);
     } else {
         for (int w = 0; w < 4; ++w) {
             const PgLayout &lay = e->td3_lay[w];
@@ -59,12 +95,7 @@ int pbt_exploit_launch(adc_engine *e, int npairs)
             hipLaunchKernelGGL(k_pbt_exploit, dim3(pg_blocks(lay.Q), (unsigned)npairs), dim3(kPgBlock), 0, e->stream, lay, e->tp_stride[w], e->td3_flat[w], mm, mv,
                                e->pbt_dpairs, ls, e->lrn_stride, e->td3_shape.A, e->pbt_cfg.lo[adc::kPbtSigma], e->pbt_cfg.hi[adc::kPbtSigma]);
         }
-        if (e->pbt_cfg.with_ring) {
-            const size_t C = (size_t)e->td3_cfg.capacity, most = C * (size_t)e->td3_shape.D * 4u;
-            const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((most / 16u + kPbtBlock - 1) / kPbtBlock, 1), 256);
-            hipLaunchKernelGGL(k_pbt_exploit_ring, dim3(blocks, (unsigned)npairs, 5u), dim3(kPbtBlock), 0, e->stream, e->tp_dmem, e->pbt_dpairs, C, e->td3_shape.D,
-                               e->td3_shape.A);
-        }
+        if (e->pbt_cfg.with_ring) pbt_ring_launch(e, npairs);
     }
     HIP_TRY(hipGetLastError());
     return ADC_OK;
@@ -113,6 +144,36 @@ ADC_EXPORT int adc_engine_pbt_init(adc_engine *e, const adc_pbt_config *cfg)
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->pbt_kind = kind;
+    e->pbt_cfg = *cfg;
+    e->pbt_key = adc::pbt_key(cfg->seed ? cfg->seed : e->cfg.seed);
+    e->pbt_round = 0;
+    e->pbt_s.assign((size_t)M, 0.0);
+    e->pbt_host_fit.assign((size_t)M, 0.0);
+    e->pbt_pairs.assign((size_t)M, PbtPair{});
+    e->have_pbt = true;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_pbt_init_sac(adc_engine *e, const adc_pbt_config *cfg)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_sac_pop) return fail(ADC_ESTATE, "population-based training over SAC needs a live SAC population trainer (adc_engine_sac_pop_init)");
+    const int M = e->lrn_M;
+    const char *why = nullptr;
+    if (adc_pbt_config_check(cfg, M, ADC_PBT_SAC, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    ENGINE_GUARD(e);
+    if (!e->have_pbt) {
+        // (the SAC population's arrays are td3_allocs: they are freed with it, and td3_drop forgets the scheduler)
+        double *ret = nullptr, *fit = nullptr;
+        PbtPair *pairs = nullptr;
+        int rc;
+        if ((rc = mlp_alloc(e, e->td3_allocs, &ret, (size_t)e->v.N)) || (rc = mlp_alloc(e, e->td3_allocs, &fit, (size_t)M)) ||
+            (rc = mlp_alloc(e, e->td3_allocs, &pairs, (size_t)M)))
+            return rc;
+        e->pbt_ret = ret; e->pbt_fit = fit; e->pbt_dpairs = pairs;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pbt_kind = ADC_PBT_SAC;
     e->pbt_cfg = *cfg;
     e->pbt_key = adc::pbt_key(cfg->seed ? cfg->seed : e->cfg.seed);
     e->pbt_round = 0;
@@ -182,7 +243,8 @@ ADC_EXPORT int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_p
     std::vector<uint32_t> bits(Ms);
     adc::pbt_plan(e->pbt_key, (uint32_t)e->pbt_round, q, e->pbt_s.data(), M, rank.data(), src.data(), bits.data());
     // the pair table and the explored hyperparameters (donors are never replaced: their values are the round's old ones)
-    const bool sigma = e->pbt_kind == ADC_PBT_TD3 && ((cfg.tuned_mask >> adc::kPbtSigma) & 1u);
+    // (id 4 - TD3's sigma, SAC's alpha - is the device's: the pair carries the log-domain shift, the exploit's launch applies it)
+    const bool sigma = (e->pbt_kind == ADC_PBT_TD3 || e->pbt_kind == ADC_PBT_SAC) && ((cfg.tuned_mask >> adc::kPbtSigma) & 1u);
     std::vector<float> shift(Ms, 0.0f);
     int npairs = 0;
     for (int m = 0; m < M; ++m) {
@@ -191,7 +253,7 @@ ADC_EXPORT int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_p
         pbt_hp_get(e, src[(size_t)m], donor);
         pbt_hp_get(e, m, own);
         for (int h = 0; h < adc::kPbtMaxHp; ++h) {
-            const bool tuned = ((cfg.tuned_mask >> h) & 1u) && !(e->pbt_kind == ADC_PBT_TD3 && h == adc::kPbtSigma);
+            const bool tuned = ((cfg.tuned_mask >> h) & 1u) && !(e->pbt_kind != ADC_PBT_PG && h == adc::kPbtSigma);
             out[h] = tuned ? adc::pbt_explore(donor[h], (int)((bits[(size_t)m] >> h) & 1u), cfg.factor_lo, cfg.factor_hi, cfg.lo[h], cfg.hi[h]) : own[h];
         }
         pbt_hp_put(e, m, out);
@@ -200,7 +262,7 @@ ADC_EXPORT int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_p
     }
     // exploit: every pair in the same launches; explore: the member table up in one copy
     if ((rc = pbt_exploit_launch(e, npairs))) return rc;
-    if ((rc = e->pbt_kind == ADC_PBT_PG ? pgp_members_upload(e) : tp_members_upload(e))) return rc;
+    if ((rc = e->pbt_kind == ADC_PBT_PG ? pgp_members_upload(e) : e->pbt_kind == ADC_PBT_SAC ? sp_members_upload(e) : tp_members_upload(e))) return rc;
     if (e->pbt_kind == ADC_PBT_PG) e->pg_adv_ready = false;       // (as adc_engine_pg_pop_set_config leaves it)
     pbt_bookkeeping(e, npairs);
     if (e->pbt_kind == ADC_PBT_PG && (rc = kl_copy(e, npairs, [&](int j, int &d, int &f) { d = e->pbt_pairs[(size_t)j].dst; f = e->pbt_pairs[(size_t)j].src; })))
@@ -213,7 +275,7 @@ ADC_EXPORT int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_p
             adc_pbt_result &r = result_m[m];
             r.fitness = f[(size_t)m]; r.smoothed = e->pbt_s[(size_t)m]; r.rank = rank[(size_t)m]; r.src = src[(size_t)m];
             pbt_hp_get(e, m, r.hp);
-            if (e->pbt_kind == ADC_PBT_TD3) r.hp[adc::kPbtSigma] = shift[(size_t)m];
+            if (e->pbt_kind != ADC_PBT_PG) r.hp[adc::kPbtSigma] = shift[(size_t)m];
         }
     return ADC_OK;
 }

@@ -1549,19 +1549,21 @@ class StepEngine:
         (with_ring: its ring too); dst keeps its configuration, envs and seed"""
         check(self._lib.adc_engine_sac_pop_copy(self._h, int(src), int(dst), 1 if with_ring else 0))
 
-    # ---- population-based training over the live pg_pop / td3_pop trainer (parts/pbt_api.inc; baselines/pbt.py PBTScheduler) ----
-    PBT_IDS = {"pg": ("lr", "ent_coef", "eps_clip", "vf_coef"), "td3": ("actor_lr", "critic_lr", "target_noise", "tau", "sigma")}
-    PBT_KINDS = {"pg": _ffi.PBT_PG, "td3": _ffi.PBT_TD3}
+    # ---- population-based training over the live pg_pop / td3_pop / sac_pop trainer (parts/pbt_api.inc; baselines/pbt.py PBTScheduler) ----
+    PBT_IDS = {"pg": ("lr", "ent_coef", "eps_clip", "vf_coef"), "td3": ("actor_lr", "critic_lr", "target_noise", "tau", "sigma"),
+               "sac": ("actor_lr", "critic_lr", "alpha_lr", "tau", "alpha", "target_entropy")}
+    PBT_KINDS = {"pg": _ffi.PBT_PG, "td3": _ffi.PBT_TD3, "sac": _ffi.PBT_SAC}
 
     @classmethod
     def pbt_config(cls, kind, members, replace_count, tuned=(), bounds=None, factors=(0.8, 1.25), fitness_ema=0.0, with_ring=False, seed=0,
                    check=True):
-        """an adc_pbt_config (csrc/adc_pbt.h) for a "pg" or "td3" population of `members`; tuned: names from PBT_IDS[kind];
-        bounds: {name: (lo, hi)} for every tuned name ("sigma": in sigma units, stored as float32 logarithms); factors: the
+        """an adc_pbt_config (csrc/adc_pbt.h) for a "pg", "td3" or "sac" population of `members`; tuned: names from PBT_IDS[kind];
+        bounds: {name: (lo, hi)} for every tuned name ("sigma" and "alpha": in their own units, both positive, stored as float32
+        logarithms - they live on the device and move in the log domain); factors: the
         two perturbation factors; seed 0: the engine's; check: run adc_pbt_config_check here (pbt_init leaves it to the engine,
         which knows the population)"""
         if kind not in cls.PBT_IDS:
-            raise ValueError(f"unknown population kind {kind!r}: 'pg' or 'td3'")
+            raise ValueError(f"unknown population kind {kind!r}: 'pg', 'td3' or 'sac'")
         ids, bounds = cls.PBT_IDS[kind], dict(bounds or {})
         c = _ffi.PBTConfig()
         c.struct_size = C.sizeof(_ffi.PBTConfig)
@@ -1578,9 +1580,9 @@ class StepEngine:
                 raise ValueError(f"bounds: (lo, hi) for {name!r}")
             h, (lo, hi) = ids.index(name), bounds[name]
             c.tuned_mask |= 1 << h
-            if name == "sigma":
+            if name in ("sigma", "alpha"):
                 if not (lo > 0 and hi > 0):
-                    raise ValueError("bounds of sigma: positive")
+                    raise ValueError(f"bounds of {name}: positive")
                 lo, hi = np.float32(np.log(lo)), np.float32(np.log(hi))
             c.lo[h], c.hi[h] = lo, hi
         msg = C.c_char_p()
@@ -1589,10 +1591,11 @@ class StepEngine:
         return c
 
     def pbt_init(self, kind, **options):
-        """a population-based training scheduler over the live pg_pop ("pg") or td3_pop ("td3") trainer; options as pbt_config's
-        (members is the learners' count).  It goes when that trainer goes."""
+        """a population-based training scheduler over the live pg_pop ("pg"), td3_pop ("td3") or sac_pop ("sac") trainer; options
+        as pbt_config's (members is the learners' count).  It goes when that trainer goes."""
         cfg = self.pbt_config(kind, max(getattr(self, "_learners", 0), 1), check=False, **options)
-        check(self._lib.adc_engine_pbt_init(self._h, C.byref(cfg)))
+        init = self._lib.adc_engine_pbt_init_sac if kind == "sac" else self._lib.adc_engine_pbt_init
+        check(init(self._h, C.byref(cfg)))
         self._pbt_kind = kind
 
     def pbt_fitness(self):
@@ -1611,7 +1614,8 @@ class StepEngine:
 
     def pbt_step(self, fitness=None):
         """one round: fitness (the device's, or `fitness` [M]), smoothing, plan, exploit, explore.  A dict of fitness, smoothed
-        [M] float64, rank, src [M] int32 (src -1: kept) and hp [M, 8] float32 (the members' hyperparameters by id after the round)"""
+        [M] float64, rank, src [M] int32 (src -1: kept) and hp [M, 8] float32 (the members' hyperparameters by id after the round; id 4 of "td3" and "sac":
+        the log-domain shift the member's log_std / log_alpha got from its donor's before the clamp, 0 when kept)"""
         M = max(getattr(self, "_learners", 0), 1)
         f = None if fitness is None else np.ascontiguousarray(fitness, dtype=np.float64)
         if f is not None and f.shape != (M,):

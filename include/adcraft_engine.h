@@ -1023,7 +1023,7 @@ int adc_engine_td3_pop_copy(adc_engine *e, int32_t src, int32_t dst, int32_t wit
  * adc_engine_sac_pop_init needs learners, the two-headed policy with the clamp on, the learners' squash, a record with
  * ADC_ROLLOUT_OBS and no other trainer alive (ADC_ESTATE otherwise, the engine stays usable); every member's theta starts as its
  * device policy; a refused allocation is ADC_ENOMEM and leaves the engine as it was.  adc_engine_obs_norm_init, _rew_norm_init,
- * _td3_norm_init and _pbt_init are refused over a SAC population (ADC_ESTATE).  The trainer does not survive adc_engine_mlp_init,
+ * _td3_norm_init and _pbt_init are refused over a SAC population (ADC_ESTATE; its scheduler is adc_engine_pbt_init_sac).  The trainer does not survive adc_engine_mlp_init,
  * adc_engine_mlp_learners or adc_engine_rollout_enable.  The optimiser constants of up to 64 updates - the critics', the actors'
  * and the temperatures' steps - go up in one copy in front of the chain: with no member clipping (max_grad_norm 0 in all)
  * adc_engine_sac_pop_update only enqueues kernels and ends with one copy of the statistics; when any member clips, all members'
@@ -1058,38 +1058,49 @@ int adc_engine_sac_pop_state_set(adc_engine *e, int32_t member, const float *the
 int adc_engine_sac_pop_set_config(adc_engine *e, int32_t member, const adc_sac_config *cfg);
 /* actor, critics, target critics, all moments and the temperature cell of src into dst on the device - with_ring: its ring too -
  * and dst's stores rebuilt; dst keeps its configuration, its envs and its seed.  With adc_engine_sac_pop_set_config the primitive
- * of a population-based training scheduler over SAC (none yet: adc_engine_pbt_init refuses a SAC population) */
+ * of population-based training over SAC; the scheduler is adc_engine_pbt_init_sac (kind ADC_PBT_SAC), whose exploit is the batched
+ * form of this call and whose explore also moves the temperature cell (adc_engine_pbt_init itself still refuses a SAC population) */
 int adc_engine_sac_pop_copy(adc_engine *e, int32_t src, int32_t dst, int32_t with_ring);
 
 /* ---- population-based training on the device: fitness, exploit, explore (the law is csrc/adc_pbt.h) ---------------------------
  * A scheduler (Jaderberg et al. 2017: truncation selection, copy, perturb) over a live learner population - adc_engine_pg_pop_*
- * (kind ADC_PBT_PG) or adc_engine_td3_pop_* (kind ADC_PBT_TD3); it goes whenever that trainer goes.  A round
+ * (kind ADC_PBT_PG), adc_engine_td3_pop_* (kind ADC_PBT_TD3) or adc_engine_sac_pop_* (kind ADC_PBT_SAC, started by
+ * adc_engine_pbt_init_sac); it goes whenever that trainer goes.  A round
  * (adc_engine_pbt_step) is, in order: the members' fitness (reduced from the rollout record's reward on the device, only M
  * doubles leave it; or fitness_m handed in), its smoothing, the plan (ranking, donor draw, explored values: on the host, from
  * those M doubles), the exploit (ONE batched copy of every replaced member from its donor: weights, optimiser moments, the
  * rebuild of the destination's stores; TD3: all four vectors, all four moment vectors and, with_ring, the ring), the explore
  * (every replaced member's new hyperparameters into the host-mastered member table, which goes up in one copy; TD3's sigma:
- * the destination's log_std from the donor's, in the log domain, inside the exploit's launch), round + 1.  The launches and host
- * round trips of a round do not grow with M or replace_count: one wait before the plan, one at the end.
+ * the destination's log_std from the donor's, in the log domain, inside the exploit's launch), round + 1.  SAC: the exploit covers
+ * the actor's and the critics' vectors with their moments, the target critics' vector (there is no target actor), the temperature
+ * cell and, with_ring, the ring - at most four launches, one more with the ring; the explored actor_lr, critic_lr, alpha_lr, tau and
+ * target_entropy go into the member's adc_sac_config as adc_engine_sac_pop_set_config would put them (init_alpha is not touched: the
+ * cell is state), and SAC's alpha is explored on the device: the destination's cell becomes {clamp(donor's log_alpha + log factor),
+ * donor's m, donor's v, mlp_exp(new log_alpha)} - for a member with alpha_lr == 0 a search over the fixed temperature itself; with
+ * alpha untuned the cell is the donor's verbatim.  The launches and host round trips of a round do not grow with M or
+ * replace_count: one wait before the plan, one at the end.
  * Hyperparameter ids - PG: 0 lr, 1 ent_coef, 2 eps_clip, 3 vf_coef; TD3: 0 actor_lr, 1 critic_lr, 2 target_noise, 3 tau,
- * 4 sigma (lo / hi / the result's hp in log units; see adc_pbt_result).  A replaced member keeps its envs, its agents' keys and
- * ticks, its untuned hyperparameters and (TD3) its seed; it gets its donor's smoothed fitness and (PG) step count.
+ * 4 sigma (lo / hi / the result's hp in log units; see adc_pbt_result); SAC: 0 actor_lr, 1 critic_lr, 2 alpha_lr, 3 tau, 4 alpha
+ * (log units as sigma's), 5 target_entropy.  A replaced member keeps its envs, its agents' keys and ticks, its untuned
+ * hyperparameters and (TD3, SAC) its seed; it gets its donor's smoothed fitness and (PG) step count.
  * adc_pbt_config_check (host only): struct_size; 2 <= members; 1 <= replace_count <= members / 2; 0 <= fitness_ema < 1; the
  * factors positive and finite, the log factors finite; tuned_mask inside the kind's ids; for every tuned id lo <= hi, both
- * inside what the trainer's own configuration check admits (so an explored configuration is always a legal one); with_ring 0
- * for PG.  Refused (the engine stays usable): adc_engine_pbt_init without a population trainer (ADC_ESTATE) or with a bad
- * configuration (ADC_EINVAL); adc_engine_pbt_fitness and a step without fitness_m with no day recorded (ADC_ESTATE);
+ * inside what the trainer's own configuration check admits (so an explored configuration is always a legal one: learning rates,
+ * coefficients and noises lo >= 0, tau lo > 0 and hi <= 1, PG's eps_clip hi < 1; TD3's sigma, SAC's alpha - both logarithms - and
+ * SAC's target_entropy any sign); with_ring 0 for PG; kind 2 is unassigned.  Refused (the engine stays usable):
+ * adc_engine_pbt_init without a PG or TD3 population trainer and adc_engine_pbt_init_sac without a SAC population trainer
+ * (ADC_ESTATE: a solo trainer or another kind's population is none), either with a bad configuration (ADC_EINVAL); adc_engine_pbt_fitness and a step without fitness_m with no day recorded (ADC_ESTATE);
  * adc_engine_pbt_exploit with a destination that is also a source (ADC_EINVAL). */
-enum adc_pbt_kind { ADC_PBT_PG = 0, ADC_PBT_TD3 = 1 };
+enum adc_pbt_kind { ADC_PBT_PG = 0, ADC_PBT_TD3 = 1, ADC_PBT_SAC = 3 };     /* 2 is unassigned and refused */
 typedef struct adc_pbt_config {
     uint32_t struct_size;          /* sizeof(adc_pbt_config) */
     int32_t replace_count;         /* q: the q worst members are replaced by copies of members among the q best */
     float fitness_ema;             /* in [0, 1): the smoothing's weight of the past; 0: none */
     float factor_lo, factor_hi;    /* > 0, finite: the two perturbation factors */
-    float log_factor_lo, log_factor_hi;    /* their float32 logarithms (TD3's sigma moves in the log domain) */
+    float log_factor_lo, log_factor_hi;    /* their float32 logarithms (TD3's sigma and SAC's alpha move in the log domain) */
     uint32_t tuned_mask;           /* bit h: hyperparameter id h is explored */
     float lo[8], hi[8];            /* the explored value's bounds per id */
-    int32_t with_ring;             /* TD3: the exploit copies the donor's ring too */
+    int32_t with_ring;             /* TD3, SAC: the exploit copies the donor's ring too */
     uint64_t seed;                 /* of the donor draw and the factor bits; 0: the engine's seed */
 } adc_pbt_config;
 typedef struct adc_pbt_result {
@@ -1098,14 +1109,18 @@ typedef struct adc_pbt_result {
     int32_t rank;                  /* the round's ranking: 0 the worst */
     int32_t src;                   /* the donor the member was replaced from; -1: kept */
     float hp[8];                   /* the member's hyperparameters by id after the round; TD3's id 4: the log-domain shift its
-                                      log_std got from its donor's before the clamp (0: kept) */
+                                      log_std got from its donor's before the clamp (0: kept); SAC's id 4: the same of its log_alpha */
 } adc_pbt_result;
 int adc_pbt_config_check(const adc_pbt_config *cfg, int32_t members, int32_t kind, const char **message);
 int adc_engine_pbt_init(adc_engine *e, const adc_pbt_config *cfg);
+/* the scheduler of kind ADC_PBT_SAC over the live adc_engine_sac_pop_init trainer (ADC_ESTATE without one); every call below then
+ * serves it */
+int adc_engine_pbt_init_sac(adc_engine *e, const adc_pbt_config *cfg);
 /* fitness_m[M] float64 of the recorded days so far */
 int adc_engine_pbt_fitness(adc_engine *e, double *fitness_m);
 /* the batched copy alone: member m becomes a copy of member src_of_m[m] (src_of_m[m] == m or -1: kept), as adc_engine_pg_pop_copy
- * / adc_engine_td3_pop_copy (with_ring from the configuration) would make it pair by pair, in a fixed number of launches */
+ * / adc_engine_td3_pop_copy / adc_engine_sac_pop_copy (with_ring from the configuration) would make it pair by pair, in a fixed
+ * number of launches; no sigma or temperature shift is applied */
 int adc_engine_pbt_exploit(adc_engine *e, const int32_t *src_of_m);
 /* one round; fitness_m[M] may be NULL (the device's, from the record); result_m[M] may be NULL */
 int adc_engine_pbt_step(adc_engine *e, const double *fitness_m, adc_pbt_result *result_m);

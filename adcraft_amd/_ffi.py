@@ -152,6 +152,10 @@ class TD3NormConfig(C.Structure):
                 ("obs_count_cap", C.c_int64), ("rew_min_std", C.c_double), ("rew_count_cap", C.c_int64), ("rew_clip", C.c_float)]
 
 
+class ReplayPrioConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("beta", C.c_float), ("eps", C.c_float), ("cap", C.c_float)]
+
+
 class Tape(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("volumes", "bid_cents", "x_impressions", "x_cost", "click", "conv", "rev_cents")]
                 + [(n, C.c_int64) for n in ("len_bid", "len_ximp", "len_xcost", "len_click", "len_conv", "len_rev")]
@@ -466,6 +470,18 @@ def lib():
         "adc_engine_td3_norm_copy": ([vp, vp], C.c_int),
         "adc_td3_norm_obs_host": ([C.POINTER(TD3NormConfig), i64, i32, vp, C.POINTER(i64), vp, vp, vp, vp], C.c_int),
         "adc_td3_norm_rew_host": ([C.POINTER(TD3NormConfig), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32), vp], C.c_int),
+        "adc_replay_prio_config_check": ([C.POINTER(ReplayPrioConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_replay_prio_init": ([vp, C.POINTER(ReplayPrioConfig)], C.c_int),
+        "adc_engine_replay_prio_set_beta": ([vp, f32], C.c_int),
+        "adc_engine_replay_prio_info": ([vp, i32, C.POINTER(f64), C.POINTER(f32)], C.c_int),
+        "adc_engine_replay_prio_fetch": ([vp, i32, i64, i64, vp], C.c_int),
+        "adc_engine_replay_prio_load": ([vp, i32, i64, i64, vp, f32], C.c_int),
+        "adc_engine_replay_prio_batch": ([vp, i32, i64, vp, vp], C.c_int),
+        "adc_per_tree_host": ([i64, vp, vp, vp], C.c_int),
+        "adc_per_descend_host": ([i64, vp, f64, C.POINTER(i64)], C.c_int),
+        "adc_per_sample_host": ([C.POINTER(ReplayPrioConfig), i64, i64, vp, u64, i64, i32, vp, vp], C.c_int),
+        "adc_per_priority_host": ([C.POINTER(ReplayPrioConfig), i32, vp, vp, vp], C.c_int),
+        "adc_per_leaf_update_host": ([i64, vp, C.POINTER(f32), i32, vp, vp], C.c_int),
         "adc_td3_y_norm_host": ([C.POINTER(TD3Config), i32, vp, vp, vp, f32, f32, vp], C.c_int),
         "adc_rew_norm_host": ([C.POINTER(RewNormConfig), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32), vp], C.c_int),
         "adc_pg_gae_norm_host": ([C.POINTER(PGConfig), i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp], C.c_int),

@@ -12,7 +12,7 @@ import copy
 
 import numpy as np
 
-from .td3_trainer import policy_from_actor, random_critics
+from .td3_trainer import PrioritizedReplay, policy_from_actor, random_critics
 
 
 def sac(num_keywords, **overrides):
@@ -37,16 +37,16 @@ class SquashedPolicy:
         engine.mlp_set_squash(self.action_lo, self.action_hi)
 
 
-class SACTrainer:
+class SACTrainer(PrioritizedReplay):
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (2 (K + 1) outputs, log_std_clamp set; a
     value network is ignored); action_lo / action_hi [K + 1] (or scalars): the squash bounds in the flat action order (budget,
     bids); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection; learning_starts:
     transitions the ring must hold before the first update; updates_per_iteration: updates after every collection.  config:
     sac()'s other keys and StepEngine.sac_config's options, plus critic_seed (random_critics' seed) and critics (two lists of
-    layers, instead)."""
+    layers, instead).  prioritized_replay: None, or PrioritizedReplay's dict (td3_trainer.py)."""
 
     def __init__(self, engine, policy, action_lo, action_hi, critic_hidden=(256, 256), horizon=10, learning_starts=1500, updates_per_iteration=64,
-                 agent_seeds=None, **config):
+                 agent_seeds=None, prioritized_replay=None, **config):
         A = policy.num_keywords + 1
         if policy.output_size != 2 * A or policy.log_std_clamp is None:
             raise ValueError("SAC needs a policy that ends in 2 (K + 1) outputs (means, log-stds) with log_std_clamp set")
@@ -62,6 +62,7 @@ class SACTrainer:
         engine.rollout_enable(self.horizon, obs=True)
         engine.sac_init(**self.config)
         engine.sac_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed))
+        self._prio_init(engine, prioritized_replay)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -75,6 +76,8 @@ class SACTrainer:
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.sac_store()
         size = e.sac_buffer(fetch=False)["size"]
+        if size >= self.learning_starts:
+            self._prio_anneal()
         stats = e.sac_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
         self.history.append(stats)
         return stats
@@ -84,10 +87,10 @@ class SACTrainer:
         return SquashedPolicy(policy_from_actor(self._template, self.engine.sac_state()["theta"]), self.action_lo, self.action_hi)
 
     def state(self, state=None):
-        return self.engine.sac_state(state)
+        return self._prio_state(self.engine.sac_state, 0, state)
 
 
-class SACPopulationTrainer:
+class SACPopulationTrainer(PrioritizedReplay):
     """M independent SAC learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
     actor, twin critics, target critics, temperature, optimiser state, hyperparameters and replay ring, and every launch of a
     store or an update covers all members (StepEngine.sac_pop_*).  What a member computes is bit for bit what SACTrainer computes
@@ -98,11 +101,12 @@ class SACPopulationTrainer:
     StepEngine.sac_config's, plus critic_seed and critics) shared by all members, or M of them - M is `members`, or the larger
     of the two counts; action_lo / action_hi [K + 1] (or scalars): the squash bounds, shared by all members.  critic_hidden,
     batch_size, capacity, target_update_interval, learning_starts (transitions of a member's ring) and updates_per_iteration
-    must be equal in all configurations: the members move together."""
+    must be equal in all configurations: the members move together.  prioritized_replay: None, or PrioritizedReplay's dict,
+    shared by all members (every member has its own tree)."""
 
     SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
 
-    def __init__(self, engine, policies, configs, action_lo, action_hi, horizon=10, agent_seeds=None, members=None):
+    def __init__(self, engine, policies, configs, action_lo, action_hi, horizon=10, agent_seeds=None, members=None, prioritized_replay=None):
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
         members = max(len(policies), len(configs)) if members is None else int(members)
@@ -141,6 +145,7 @@ class SACPopulationTrainer:
         engine.sac_pop_init(self.configs)
         for m in range(members):
             engine.sac_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]))
+        self._prio_init(engine, prioritized_replay)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -154,6 +159,8 @@ class SACPopulationTrainer:
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.sac_pop_store()
         size = e.sac_pop_buffer(fetch=False)["size"]
+        if size >= self.learning_starts:
+            self._prio_anneal()
         stats = e.sac_pop_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
         self.history.append(stats)
         return stats
@@ -168,7 +175,7 @@ class SACPopulationTrainer:
         return r.reshape(self.members, -1).mean(axis=1)
 
     def state(self, member, state=None):
-        return self.engine.sac_pop_state(member, state)
+        return self._prio_state(lambda s: self.engine.sac_pop_state(member, s), member, state)
 
     def copy(self, src, dst, with_ring=False):
         """member src's actor, critics, target critics, moments and temperature into member dst (with_ring: its ring too); dst

@@ -96,7 +96,55 @@ def _norm_state(engine, member, state, envs=None):
         engine.td3_norm_returns(g)
 
 
-class TD3Trainer:
+class PrioritizedReplay:
+    """the trainers' side of prioritized_replay=None | dict(alpha=0.6, beta=0.4, eps=1e-6, cap=1e6, beta_final=None,
+    beta_iterations=0): prioritised replay on the device (StepEngine.replay_prio_*; csrc/adc_per.h) for the trainer's ring(s).
+    With beta_final and beta_iterations > 0 the importance weights' exponent moves linearly from beta to beta_final over that
+    many iterations, set on the host before an iteration's updates.  A trainer's state() then carries `replay_prio` - the leaves,
+    top and the iteration count - and, set after the ring was loaded, a resumed run continues bit for bit.  What prioritisation
+    gains in learning on this env has not been measured."""
+
+    PRIO_DEFAULTS = dict(alpha=0.6, beta=0.4, eps=1e-6, cap=1e6, beta_final=None, beta_iterations=0)
+
+    def _prio_init(self, engine, prioritized_replay):
+        self.prioritized_replay, self._prio_iterations = None, 0
+        if prioritized_replay is None:
+            return
+        unknown = set(prioritized_replay) - set(self.PRIO_DEFAULTS)
+        if unknown:
+            raise ValueError(f"prioritized_replay: unknown keys {sorted(unknown)}")
+        o = dict(self.PRIO_DEFAULTS, **prioritized_replay)
+        if o["beta_final"] is not None and not 0.0 <= float(o["beta_final"]) <= 1.0:
+            raise ValueError("prioritized_replay: beta_final must be in [0, 1]")
+        engine.replay_prio_init(alpha=o["alpha"], beta=o["beta"], eps=o["eps"], cap=o["cap"])
+        self.prioritized_replay = o
+
+    def _prio_anneal(self):
+        """before an iteration's updates: iteration i of the run uses beta + min(i / beta_iterations, 1) (beta_final - beta)"""
+        o = self.prioritized_replay
+        if o is None:
+            return
+        if o["beta_final"] is not None and int(o["beta_iterations"]) > 0:
+            f = min(self._prio_iterations / float(o["beta_iterations"]), 1.0)
+            self.engine.replay_prio_set_beta(float(o["beta"]) + f * (float(o["beta_final"]) - float(o["beta"])))
+        self._prio_iterations += 1
+
+    def _prio_state(self, get_or_set, member, state):
+        """get_or_set(state): the engine's own state call; `replay_prio` rides along"""
+        if state is None:
+            st = get_or_set(None)
+            if self.prioritized_replay is not None:
+                st["replay_prio"] = dict(self.engine.replay_prio_state(member), iterations=self._prio_iterations)
+            return st
+        state = dict(state)
+        prio = state.pop("replay_prio", None)
+        get_or_set(state)
+        if prio is not None and self.prioritized_replay is not None:
+            self.engine.replay_prio_state(member, prio)
+            self._prio_iterations = int(prio.get("iterations", self._prio_iterations))
+
+
+class TD3Trainer(PrioritizedReplay):
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (K + 1 means, free log_std; a value network
     is ignored); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection;
     exploration_sigma: the standard deviation of the collection noise; learning_starts: transitions the ring must hold before
@@ -107,10 +155,12 @@ class TD3Trainer:
     normalize_observations / normalize_rewards: running normalisers on the device (StepEngine.td3_norm_*; csrc/adc_td3_norm.h).
     The record and the ring then hold raw observations and raw rewards and every batch is normalised as it is sampled, with the
     statistics updated from every collection BEFORE its updates; norm: dict(obs_min_std=..., obs_count_cap=..., rew_min_std=...,
-    rew_count_cap=..., rew_clip=...).  What they gain in learning has not been measured."""
+    rew_count_cap=..., rew_clip=...).  What they gain in learning has not been measured.
+
+    prioritized_replay: None, or PrioritizedReplay's dict."""
 
     def __init__(self, engine, policy, critic_hidden=(256, 256), horizon=10, exploration_sigma=0.1, learning_starts=10000, updates_per_iteration=64,
-                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, **config):
+                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, prioritized_replay=None, **config):
         norm = _norm_options([policy], normalize_observations, normalize_rewards, norm)
         if policy.log_std is None:
             raise ValueError("TD3 needs a policy that ends in K + 1 means with the free log_std vector")
@@ -129,6 +179,7 @@ class TD3Trainer:
         engine.td3_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed), action_norm=action_norm)
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
+        self._prio_init(engine, prioritized_replay)
         self.history = []
 
     def set_exploration(self, sigma):
@@ -149,6 +200,8 @@ class TD3Trainer:
         if self.normalize_observations or self.normalize_rewards:
             e.td3_norm_update()             # (the batches below are scaled by statistics that include the newest days)
         size = e.td3_buffer(fetch=False)["size"]
+        if size >= self.learning_starts:
+            self._prio_anneal()
         stats = e.td3_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
         self.history.append(stats)
         return stats
@@ -160,14 +213,14 @@ class TD3Trainer:
         return _with_vectors(pol, self.engine.td3_norm_state()) if self.normalize_observations else pol
 
     def state(self, state=None):
-        return self.engine.td3_state(state)
+        return self._prio_state(self.engine.td3_state, 0, state)
 
     def norm_state(self, state=None):
         """the normalisers' state: StepEngine.td3_norm_state's dict plus `returns`, the envs' running discounted returns; get or set"""
         return _norm_state(self.engine, 0, state)
 
 
-class TD3PopulationTrainer:
+class TD3PopulationTrainer(PrioritizedReplay):
     """M independent TD3 learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
     actor, exploration sigma, twin critics, targets, optimiser state, hyperparameters and replay ring, and every launch of a
     store or an update covers all members (StepEngine.td3_pop_*).  What a member computes is bit for bit what TD3Trainer
@@ -181,12 +234,12 @@ class TD3PopulationTrainer:
 
     normalize_observations / normalize_rewards: every member has its own running normalisers (TD3Trainer's, per member: a
     member's statistics are bit for bit a single trainer's of its envs; the reward's discount is the member's own gamma); norm as
-    TD3Trainer's."""
+    TD3Trainer's.  prioritized_replay: None, or PrioritizedReplay's dict, shared by all members (every member has its own tree)."""
 
     SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
 
     def __init__(self, engine, policies, sigmas, configs, horizon=10, agent_seeds=None, members=None, normalize_observations=False,
-                 normalize_rewards=False, norm=None):
+                 normalize_rewards=False, norm=None, prioritized_replay=None):
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         norm = _norm_options(policies, normalize_observations, normalize_rewards, norm)
         self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
@@ -234,6 +287,7 @@ class TD3PopulationTrainer:
             engine.td3_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]), action_norm=norms[0] if m == 0 else None)
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
+        self._prio_init(engine, prioritized_replay)
         self.history = []
 
     def set_exploration(self, sigma, member=None):
@@ -255,6 +309,8 @@ class TD3PopulationTrainer:
         if self.normalize_observations or self.normalize_rewards:
             e.td3_norm_update()             # (one call for all members, whatever their number)
         size = e.td3_pop_buffer(fetch=False)["size"]
+        if size >= self.learning_starts:
+            self._prio_anneal()
         stats = e.td3_pop_update(self.updates_per_iteration) if size >= self.learning_starts else dict(buffer_size=size, updates=None)
         self.history.append(stats)
         return stats
@@ -271,11 +327,11 @@ class TD3PopulationTrainer:
         return r.reshape(self.members, -1).mean(axis=1)
 
     def state(self, member, state=None):
-        return self.engine.td3_pop_state(member, state)
+        return self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, state)
 
     def norm_state(self, member, state=None):
         """member's normalisers (TD3Trainer.norm_state's dict; `returns` holds the member's own envs')"""
         return _norm_state(self.engine, member, state, self.engine.num_envs // self.members)
 
 
-__all__ = ["TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]
+__all__ = ["PrioritizedReplay", "TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]

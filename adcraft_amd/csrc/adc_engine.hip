@@ -59,6 +59,7 @@
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
 //   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
 //   parts/kernel_sac_pop.inc      SAC learner populations: the k_sac_pop_* twins of kernel_sac.inc, the member one more grid dimension.
+//   parts/kernel_per.inc          prioritised replay: the radix-64 sum tree's sample, weights, leaf update and node rebuild (adc_per.h).
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy, SAC's temperature cells (adc_pbt.h).
 //   parts/kernel_norm.inc         the running normalisers, one set of kernels: the record's batch moments of the observations in one pass,
 //        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
@@ -72,6 +73,7 @@
 //   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
 //   parts/sac_pop_api.inc         the entry points of SAC learner populations, over td3_pop_api.inc's helpers.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over a PG, TD3 or SAC population.
+//   parts/per_api.inc             the entry points of prioritised replay over a TD3 or SAC trainer, and what the trainers' updates call of it.
 //   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners' - over shared helpers.
 //
 // No CPU path exists in this library.
@@ -103,6 +105,7 @@
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
 #include "adc_td3_norm.h"
+#include "adc_per.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -129,6 +132,7 @@ namespace adck {
 #include "parts/kernel_td3_pop.inc"
 #include "parts/kernel_sac_pop.inc"
 #include "parts/kernel_pbt.inc"
+#include "parts/kernel_per.inc"
 #include "parts/kernel_norm.inc"
 }  // namespace adck
 using namespace adck;
@@ -142,5 +146,6 @@ using namespace adck;
 #include "parts/td3_pop_api.inc"
 #include "parts/sac_pop_api.inc"
 #include "parts/pbt_api.inc"
+#include "parts/per_api.inc"
 #include "parts/norm_api.inc"
 #include "parts/comm_api.inc"

@@ -246,6 +246,11 @@ struct adc_engine {
     adc_obs_norm_config on_cfg{};
     adc_rew_norm_config rn_cfg{};
     adc_td3_norm_config tn_cfg{};
+    // prioritised replay over the live TD3 / SAC trainer's ring(s), solo or population (adc_engine_replay_prio_init; parts/kernel_per.inc,
+    // parts/per_api.inc; the law is adc_per.h).  Its device arrays are the trainer's allocations (td3_allocs): they go with it
+    bool per_live = false;
+    adc_replay_prio_config per_cfg{};
+    PerView per{};                              // all members' trees, tops and batch buffers
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -2972,6 +2977,7 @@ void pg_drop(adc_engine *e)
 void td3_drop(adc_engine *e)
 {
     norm_set_drop(e, e->tn);            // (the record is back to network inputs)
+    e->per_live = false; e->per = PerView{};    // (prioritised replay's arrays are among td3_allocs)
     pbt_forget(e, ADC_PBT_TD3);
     pbt_forget(e, ADC_PBT_SAC);         // (a SAC population's scheduler: its arrays are among td3_allocs too)
     mlp_free(e, e->td3_allocs);

@@ -15,6 +15,12 @@ struct SacView {
     adc::SacLaw law;
     MlpNet pol, q[2], q_t[2];               // chain-major layers: the live actor, the critics, their targets
     const float *cell;                      // {log_alpha, m, v, alpha}
+    // prioritised replay (adc_engine_replay_prio_init; adc_per.h, parts/kernel_per.inc).  p_slot non-null: the element's ring slot is
+    // p_slot[element] in place of td3_batch_index, the critics' output deltas and loss pieces are weighted by p_w[element], and the
+    // critic kernel leaves |d_1|, |d_2| at p_absd[2 element].  Null: the kernels' loads and bits are what they were
+    const int32_t *p_slot;                  // [B] or [M][B]
+    const float *p_w;
+    float *p_absd;
     Td3Ring ring;
     uint32_t size, update;                  // the ring's size; the update's number
     uint64_t key;
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_target(SacView p)
     const int tid = threadIdx.x, D = sh.D;
     const uint32_t b = blockIdx.x;
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     const float alpha = p.cell[kSacCellAlpha];
     for (int j = tid; j < D; j += kPgBlock) s.row[j] = p.ring.x2[slot * (size_t)D + j];
     __syncthreads();
@@ -105,7 +111,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
     const int tid = threadIdx.x, A = sh.A, D = sh.D, DA = D + A;
     const uint32_t b = blockIdx.x;
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     float *xin = p.xin + (size_t)b * (size_t)DA;
     for (int j = tid; j < DA; j += kPgBlock) {
         const float xj = j < D ? p.ring.x[slot * (size_t)D + j] : adc::mlp_tanh(p.ring.a[slot * (size_t)A + (j - D)]);
@@ -120,7 +126,8 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
         if (tid == 0) {
             const float y = p.ybuf[b], q = s.yq[nh];
             float loss;
-            const float d = adc::td3_critic_delta(q, y, loss);
+            float d = adc::td3_critic_delta(q, y, loss);
+            if (p.p_slot) { p.p_absd[2 * (size_t)b + i] = __builtin_fabsf(d); d = p.p_w[b] * d; loss = p.p_w[b] * loss; }
             pc[adc::kTd3Loss1 + i] = loss; pc[adc::kTd3Q1 + i] = q;
             if (i == 0) { pc[adc::kTd3Y] = y; pc[adc::kSacPiLoss] = 0.0f; pc[adc::kSacLp] = 0.0f; pc[adc::kSacPick] = 0.0f; }
             s.d0[0] = d;
@@ -140,7 +147,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_actor_sample(SacView p)
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
     const uint32_t b = blockIdx.x;
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     const float alpha = p.cell[kSacCellAlpha];
     for (int j = tid; j < D; j += kPgBlock) s.row[j] = p.ring.x[slot * (size_t)D + j];
     __syncthreads();

@@ -5,7 +5,7 @@
 // scale and optimiser constants).  The arithmetic is adc_sac.h's law through the helpers kernel_sac.inc and kernel_td3.inc use
 // (td3_forward, td3_backward, td3_input_back, sac_heads, sac_lp, adc::sac_*): a member runs the solo code on its own ring under
 // its own key, so its bits are a solo engine's, whatever M and the other members are.  The batch kernels restate the solo kernels'
-// bodies rather than share them: kernel_sac.inc and its code objects stay exactly as they were.  The store, the weight gradient,
+// bodies rather than share them: kernel_sac.inc's bodies stay the solo learner's alone.  The store, the weight gradient,
 // its join, the chunked sums, the optimiser step and Polyak are k_td3_pop_store / k_pg_pop_wgrad / k_pg_pop_grad_join /
 // k_pg_pop_chunk_sums / k_pg_pop_join / k_td3_pop_step / k_td3_pop_polyak unchanged.  All LDS is the dynamic region; no atomics;
 // all stores are plain vector stores.
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_target(SacView p, const Ml
     const uint32_t b = blockIdx.x;
     const Td3Ring ring = me.ring;
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = adc::td3_batch_index(key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[(size_t)blockIdx.y * gridDim.x + b] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
     const float alpha = smem[blockIdx.y].cell[kSacCellAlpha];
     for (int j = tid; j < D; j += kPgBlock) s.row[j] = ring.x2[slot * (size_t)D + j];
     __syncthreads();
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_critic_sample(SacView p, c
     const size_t at = (size_t)blockIdx.y * gridDim.x + b;       // the element's scratch row
     const Td3Ring ring = me.ring;
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = adc::td3_batch_index(me.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(me.key, b, p.update, p.size);
     float *xin = p.xin + at * (size_t)DA;
     for (int j = tid; j < DA; j += kPgBlock) {
         const float xj = j < D ? ring.x[slot * (size_t)D + j] : adc::mlp_tanh(ring.a[slot * (size_t)A + (j - D)]);
@@ -90,7 +90,8 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_critic_sample(SacView p, c
         if (tid == 0) {
             const float y = p.ybuf[at], q = s.yq[nh];
             float loss;
-            const float d = adc::td3_critic_delta(q, y, loss);
+            float d = adc::td3_critic_delta(q, y, loss);
+            if (p.p_slot) { p.p_absd[2 * at + i] = __builtin_fabsf(d); d = p.p_w[at] * d; loss = p.p_w[at] * loss; }
             pc[adc::kTd3Loss1 + i] = loss; pc[adc::kTd3Q1 + i] = q;
             if (i == 0) { pc[adc::kTd3Y] = y; pc[adc::kSacPiLoss] = 0.0f; pc[adc::kSacLp] = 0.0f; pc[adc::kSacPick] = 0.0f; }
             s.d0[0] = d;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_actor_sample(SacView p, co
     const uint32_t b = blockIdx.x;
     const size_t at = (size_t)blockIdx.y * gridDim.x + b;
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = adc::td3_batch_index(key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[(size_t)blockIdx.y * gridDim.x + b] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
     const float alpha = smem[blockIdx.y].cell[kSacCellAlpha];
     const float *rx = me.ring.x;
     for (int j = tid; j < D; j += kPgBlock) s.row[j] = rx[slot * (size_t)D + j];

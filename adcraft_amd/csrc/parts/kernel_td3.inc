@@ -29,6 +29,12 @@ struct Td3View {
     const float *r_scale;                   // [1] or [M]
     int r_stride;                           // 1: a multiplier per member; 0: shared
     float r_clip;
+    // prioritised replay (adc_engine_replay_prio_init; adc_per.h, parts/kernel_per.inc).  p_slot non-null: the element's ring slot is
+    // p_slot[element] in place of td3_batch_index, the critics' output deltas and loss pieces are weighted by p_w[element], and the
+    // critic kernel leaves |d_1|, |d_2| at p_absd[2 element].  Null: the kernels' loads and bits are what they were
+    const int32_t *p_slot;                  // [B] or [M][B]
+    const float *p_w;
+    float *p_absd;
     Td3Ring ring;
     uint32_t size, update;                  // the ring's size; the update's number
     uint64_t key;
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
     const uint32_t b = blockIdx.x;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *words = yq + adc::td3_outs(sh.q) + 3 * p.maxw;
-    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
     const float r_mult = p.r_scale ? p.r_scale[0] : 1.0f;
     for (int j = tid; j < D; j += kPgBlock) {
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
     const int tid = threadIdx.x, A = sh.A, D = sh.D, DA = D + A;
     const uint32_t b = blockIdx.x;
     float *row = td3_lds, *yq = row + DA + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
-    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     float *xin = p.xin + (size_t)b * (size_t)DA;
     for (int j = tid; j < DA; j += kPgBlock) {
         float xj = j < D ? p.ring.x[slot * (size_t)D + j]
@@ -205,7 +211,8 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
         if (tid == 0) {
             const float y = p.ybuf[b], q = yq[nh];
             float loss;
-            const float d = adc::td3_critic_delta(q, y, loss);
+            float d = adc::td3_critic_delta(q, y, loss);
+            if (p.p_slot) { p.p_absd[2 * (size_t)b + i] = __builtin_fabsf(d); d = p.p_w[b] * d; loss = p.p_w[b] * loss; }
             pc[adc::kTd3Loss1 + i] = loss; pc[adc::kTd3Q1 + i] = q;
             if (i == 0) { pc[adc::kTd3Y] = y; pc[adc::kTd3QPi] = 0.0f; pc[6] = 0.0f; pc[7] = 0.0f; }
             d0[0] = d;
@@ -224,7 +231,7 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample(Td3View p)
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
     const uint32_t b = blockIdx.x;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
-    const size_t slot = adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     for (int j = tid; j < D; j += kPgBlock) {
         float xj = p.ring.x[slot * (size_t)D + j];
         if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);

@@ -5,7 +5,7 @@
 // member's block.  The arithmetic is adc_td3.h's law through the same helpers kernel_td3.inc uses (td3_forward, td3_backward,
 // td3_input_back): a member runs the solo code on its own ring under its own key, so its bits are a solo engine's, whatever M
 // and the other members are.  The three batch kernels restate the solo kernels' bodies rather than share them: kernel_td3.inc and
-// its code objects stay exactly as they were.  The weight gradient, its join and the chunked sums are k_pg_pop_wgrad /
+// its bodies stay the solo learner's alone.  The weight gradient, its join and the chunked sums are k_pg_pop_wgrad /
 // k_pg_pop_grad_join / k_pg_pop_chunk_sums / k_pg_pop_join unchanged.  All LDS is the dynamic region; no atomics; all stores are
 // plain vector stores.
 // (part of the single translation unit adc_engine.hip)
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_target(Td3View p, const Td
     const uint64_t key = me.key;
     const Td3Ring ring = me.ring;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *words = yq + adc::td3_outs(sh.q) + 3 * p.maxw;
-    const size_t slot = adc::td3_batch_index(key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[(size_t)blockIdx.y * gridDim.x + b] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
     const size_t nv = (size_t)blockIdx.y * p.n_stride;          // (the member's row of the normaliser's vectors; 0 whenever they are shared)
     // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
     const float r_mult = p.r_scale ? p.r_scale[(size_t)blockIdx.y * (size_t)p.r_stride] : 1.0f;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_critic_sample(Td3View p, c
     const size_t at = (size_t)blockIdx.y * gridDim.x + b;       // the element's scratch row
     const Td3Ring ring = me.ring;
     float *row = td3_lds, *yq = row + DA + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
-    const size_t slot = adc::td3_batch_index(me.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(me.key, b, p.update, p.size);
     float *xin = p.xin + at * (size_t)DA;
     const size_t nv = (size_t)blockIdx.y * p.n_stride;
     for (int j = tid; j < DA; j += kPgBlock) {
@@ -136,7 +136,8 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_critic_sample(Td3View p, c
         if (tid == 0) {
             const float y = p.ybuf[at], q = yq[nh];
             float loss;
-            const float d = adc::td3_critic_delta(q, y, loss);
+            float d = adc::td3_critic_delta(q, y, loss);
+            if (p.p_slot) { p.p_absd[2 * at + i] = __builtin_fabsf(d); d = p.p_w[at] * d; loss = p.p_w[at] * loss; }
             pc[adc::kTd3Loss1 + i] = loss; pc[adc::kTd3Q1 + i] = q;
             if (i == 0) { pc[adc::kTd3Y] = y; pc[adc::kTd3QPi] = 0.0f; pc[6] = 0.0f; pc[7] = 0.0f; }
             d0[0] = d;
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_actor_sample(Td3View p, co
     const uint32_t b = blockIdx.x;
     const size_t at = (size_t)blockIdx.y * gridDim.x + b;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
-    const size_t slot = adc::td3_batch_index(me.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(me.key, b, p.update, p.size);
     const float *rx = me.ring.x;
     const size_t nv = (size_t)blockIdx.y * p.n_stride;
     for (int j = tid; j < D; j += kPgBlock) {

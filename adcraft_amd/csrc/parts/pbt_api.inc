@@ -86,6 +86,7 @@ int pbt_exploit_launch(adc_engine *e, int npairs)
         hipLaunchKernelGGL(k_pbt_exploit_cell, dim3((unsigned)((npairs + kPbtBlock - 1) / kPbtBlock)), dim3(kPbtBlock), 0, e->stream, npairs, e->sp_cells,
                            e->pbt_dpairs, e->pbt_cfg.lo[adc::kPbtAlpha], e->pbt_cfg.hi[adc::kPbtAlpha]);
         if (e->pbt_cfg.with_ring) pbt_ring_launch(e, npairs);
+        if (e->pbt_cfg.with_ring && e->per_live) per_pairs_launch(e, npairs);     // (the leaves, nodes and tops travel with the rings)
     } else {
         for (int w = 0; w < 4; ++w) {
             const PgLayout &lay = e->td3_lay[w];
@@ -96,6 +97,7 @@ int pbt_exploit_launch(adc_engine *e, int npairs)
                                e->pbt_dpairs, ls, e->lrn_stride, e->td3_shape.A, e->pbt_cfg.lo[adc::kPbtSigma], e->pbt_cfg.hi[adc::kPbtSigma]);
         }
         if (e->pbt_cfg.with_ring) pbt_ring_launch(e, npairs);
+        if (e->pbt_cfg.with_ring && e->per_live) per_pairs_launch(e, npairs);     // (the leaves, nodes and tops travel with the rings)
     }
     HIP_TRY(hipGetLastError());
     return ADC_OK;

@@ -47,6 +47,7 @@ SacView sac_view(const adc_engine *e)
     p.key = e->td3_key;
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(e->td3_shape);
+    td3_per_fill(e, p);
     return p;
 }
 // the device's sums: [0..7] the pieces (the two critic losses, Q1, Q2, y, the actor's loss piece, lp, the picks of critic 2),
@@ -59,11 +60,13 @@ int sac_one_update(adc_engine *e, bool stats_wanted, bool last)
     const size_t lds = sac_lds_floats(sh) * sizeof(float);
     SacView p = sac_view(e);
     p.na = 2 * nh; p.nd = 2 * no;
+    int rc;
+    if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
     hipLaunchKernelGGL(k_sac_target, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     hipLaunchKernelGGL(k_sac_critic_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     for (int i = 0; i < 2; ++i) td3_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
-    int rc;
+    if (e->per_live && (rc = per_leaves_run(e))) return rc;
     if ((rc = td3_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 8, c.critic_lr, e->td3_updates))) return rc;
     p.na = ph; p.nd = po;
     hipLaunchKernelGGL(k_sac_actor_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
@@ -213,6 +216,7 @@ ADC_EXPORT int adc_engine_sac_store(adc_engine *e, int64_t *stored)
                        e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
                        (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());
+    if (e->per_live && (rc = per_store_run(e, e->td3_written, count))) return rc;
     e->td3_written += count;
     e->td3_stored_t = e->ro_t;
     if (stored) *stored = count;
@@ -264,6 +268,10 @@ ADC_EXPORT int adc_engine_sac_buffer_load(adc_engine *e, int64_t slot, int64_t c
     HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->td3_written = written;
+    if (e->per_live) {
+        if (int rc = per_loaded_run(e, 0, slot, count)) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     return ADC_OK;
 }
 
@@ -282,6 +290,7 @@ ADC_EXPORT int adc_engine_sac_batch_indices(adc_engine *e, int64_t update, int32
     if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
     if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
     if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_store)");
+    if (e->per_live) return fail(ADC_ESTATE, "prioritised replay is alive on this engine: the batch is adc_engine_replay_prio_batch's, not the uniform law's");
     ENGINE_GUARD(e);
     const int B = e->td3_cfg.batch_size;
     hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->td3_key, (uint32_t)update, (uint32_t)td3_size(e), B, e->td3_idx);

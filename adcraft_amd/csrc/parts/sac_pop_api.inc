@@ -77,12 +77,15 @@ int sp_one_update(adc_engine *e, int index, bool stats_wanted, bool last, bool a
     p.size = (uint32_t)td3_size(e); p.update = (uint32_t)e->td3_updates;
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(sh);
+    td3_per_fill(e, p);
     p.na = 2 * nh; p.nd = 2 * no;
+    int rc;
+    if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
     hipLaunchKernelGGL(k_sac_pop_target, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem, e->sp_dmem);
     hipLaunchKernelGGL(k_sac_pop_critic_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
     for (int i = 0; i < 2; ++i) tp_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
-    int rc;
+    if (e->per_live && (rc = per_leaves_run(e))) return rc;
     if ((rc = tp_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 8, 3 * index, any_clip))) return rc;
     p.na = ph; p.nd = po;
     hipLaunchKernelGGL(k_sac_pop_actor_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem, e->sp_dmem);
@@ -265,6 +268,7 @@ ADC_EXPORT int adc_engine_sac_pop_store(adc_engine *e, int64_t *stored_per_membe
                        e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
                        (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());
+    if (e->per_live && (rc = per_store_run(e, e->td3_written, count))) return rc;
     e->td3_written += count;
     e->td3_stored_t = e->ro_t;
     if (stored_per_member) *stored_per_member = count;
@@ -320,6 +324,10 @@ ADC_EXPORT int adc_engine_sac_pop_buffer_load(adc_engine *e, int32_t member, int
     HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->td3_written = written;               // (the members' rings move together: one count for all)
+    if (e->per_live) {
+        if ((rc = per_loaded_run(e, member, slot, count))) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     return ADC_OK;
 }
 
@@ -331,6 +339,7 @@ ADC_EXPORT int adc_engine_sac_pop_batch_indices(adc_engine *e, int32_t member, i
     if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
     if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
     if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_pop_store)");
+    if (e->per_live) return fail(ADC_ESTATE, "prioritised replay is alive on this engine: the batch is adc_engine_replay_prio_batch's, not the uniform law's");
     ENGINE_GUARD(e);
     const int B = e->td3_cfg.batch_size;
     hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->tp_mem[(size_t)member].key, (uint32_t)update,
@@ -496,6 +505,7 @@ ADC_EXPORT int adc_engine_sac_pop_copy(adc_engine *e, int32_t src, int32_t dst, 
         HIP_TRY(hipMemcpyAsync(d.r, s.r, C * 4, hipMemcpyDeviceToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(d.done, s.done, C, hipMemcpyDeviceToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(d.x2, s.x2, C * D * 4, hipMemcpyDeviceToDevice, e->stream));
+        if (e->per_live && (rc = per_copy_run(e, src, dst))) return rc;     // (the leaves, nodes and top travel with the ring)
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     const size_t per = 2u * adc::kMlpMaxLayers;

@@ -3,6 +3,13 @@
 // after the env groups have joined: results do not depend on how the days were grouped.
 // (part of the single translation unit adc_engine.hip)
 namespace {
+// prioritised replay's side of an update, a store, a buffer load and a member copy (parts/per_api.inc; called only while e->per_live)
+int per_sample_run(adc_engine *e, uint32_t update);
+int per_leaves_run(adc_engine *e);
+int per_store_run(adc_engine *e, int64_t written_before, int64_t count);
+int per_loaded_run(adc_engine *e, int member, int64_t slot, int64_t count);
+int per_copy_run(adc_engine *e, int src, int dst);
+void per_pairs_launch(adc_engine *e, int npairs);
 enum { kTd3Theta = 0, kTd3Psi = 1, kTd3ThetaT = 2, kTd3PsiT = 3 };
 
 int td3_ready(const adc_engine *e)
@@ -76,6 +83,13 @@ void td3_norm_fill(const adc_engine *e, Td3View &p)
     if (e->tn.obs.count) { p.n_shift = e->mp.shift; p.n_scale = e->mp.scale; p.n_stride = e->mp.norm_stride; }
     if (e->tn.rew.count) { p.r_scale = e->tn.rew.scale; p.r_stride = e->tn_cfg.per_member ? 1 : 0; p.r_clip = e->tn_cfg.rew_clip; }
 }
+// prioritised replay's side of a batch kernel's view (all null without adc_engine_replay_prio_init: the kernels are what they were)
+template <class BatchView>
+void td3_per_fill(const adc_engine *e, BatchView &p)
+{
+    if (!e->per_live) return;
+    p.p_slot = e->per.slot; p.p_w = e->per.w; p.p_absd = e->per.absd;
+}
 Td3View td3_view(const adc_engine *e)
 {
     Td3View p{};
@@ -91,6 +105,7 @@ Td3View td3_view(const adc_engine *e)
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(e->td3_shape);
     td3_norm_fill(e, p);
+    td3_per_fill(e, p);
     return p;
 }
 // the weight gradient's partials of one network over the batch: its first layer's X is the gathered rows
@@ -138,11 +153,13 @@ int td3_one_update(adc_engine *e, bool stats_wanted, bool last, bool last_actor)
     const size_t lds = td3_lds_floats(sh) * sizeof(float);
     Td3View p = td3_view(e);
     p.na = 2 * nh; p.nd = 2 * no;
+    int rc;
+    if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
     hipLaunchKernelGGL(k_td3_target, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     hipLaunchKernelGGL(k_td3_critic_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     for (int i = 0; i < 2; ++i) td3_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
-    int rc;
+    if (e->per_live && (rc = per_leaves_run(e))) return rc;
     if (stats_wanted && last && (rc = td3_csum_launch(e, e->td3_pieces, B, adc::kTd3Pieces, 5, 0, e->td3_sums))) return rc;
     if ((rc = td3_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 5, c.critic_lr, e->td3_updates))) return rc;
     if ((e->td3_updates + 1) % c.policy_delay == 0) {
@@ -299,6 +316,7 @@ ADC_EXPORT int adc_engine_td3_store(adc_engine *e, int64_t *stored)
                        e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
                        (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());
+    if (e->per_live && (rc = per_store_run(e, e->td3_written, count))) return rc;
     e->td3_written += count;
     e->td3_stored_t = e->ro_t;
     if (stored) *stored = count;
@@ -358,6 +376,10 @@ ADC_EXPORT int adc_engine_td3_buffer_load(adc_engine *e, int64_t slot, int64_t c
     HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->td3_written = written;
+    if (e->per_live) {
+        if (int rc = per_loaded_run(e, 0, slot, count)) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     return ADC_OK;
 }
 
@@ -368,6 +390,7 @@ ADC_EXPORT int adc_engine_td3_batch_indices(adc_engine *e, int64_t update, int32
     if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
     if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
     if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_td3_store)");
+    if (e->per_live) return fail(ADC_ESTATE, "prioritised replay is alive on this engine: the batch is adc_engine_replay_prio_batch's, not the uniform law's");
     ENGINE_GUARD(e);
     const int B = e->td3_cfg.batch_size;
     hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->td3_key, (uint32_t)update, (uint32_t)td3_size(e), B, e->td3_idx);

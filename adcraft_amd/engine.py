@@ -1832,6 +1832,83 @@ class StepEngine:
             raise ValueError("td3_norm_copy: one source per member")
         check(self._lib.adc_engine_td3_norm_copy(self._h, src.ctypes.data))
 
+    # ---- prioritised replay for the TD3 / SAC learners (parts/kernel_per.inc; the law is csrc/adc_per.h) -------------------------
+    @classmethod
+    def replay_prio_config(cls, alpha=0.6, beta=0.4, eps=1e-6, cap=1e6):
+        """an adc_replay_prio_config: alpha in [0, 1] the priorities' exponent, beta in [0, 1] the importance weights', eps > 0
+        added to the error (and the floor of a priority), cap > eps its ceiling.  The defaults are the usual configuration
+        (Schaul et al. 2016), not measurements."""
+        c = _ffi.ReplayPrioConfig()
+        c.struct_size = C.sizeof(_ffi.ReplayPrioConfig)
+        c.alpha, c.beta, c.eps, c.cap = float(alpha), float(beta), float(eps), float(cap)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_replay_prio_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad prioritised replay configuration").decode())
+        return c
+
+    def replay_prio_init(self, **options):
+        """prioritised replay for the live TD3 / SAC trainer, solo or population (td3_init, sac_init, td3_pop_init or sac_pop_init
+        first): batches are drawn from a sum tree on the device in proportion to the slots' priorities, the critics' loss is
+        weighted by the importance weights, the priorities follow the critics' errors.  A ring that already holds transitions is
+        fine (its slots get leaf 1).  Options as replay_prio_config's; it ends with its trainer"""
+        cfg = self.replay_prio_config(**options)
+        check(self._lib.adc_engine_replay_prio_init(self._h, C.byref(cfg)))
+
+    def replay_prio_set_beta(self, beta):
+        """the importance weights' exponent from the next update on (the host's annealing schedule)"""
+        check(self._lib.adc_engine_replay_prio_set_beta(self._h, float(beta)))
+
+    def replay_prio_info(self, member=0):
+        """dict of total (the tree's root, float64) and top (the largest leaf any update has written, float32)"""
+        total, top = C.c_double(0.0), C.c_float(0.0)
+        check(self._lib.adc_engine_replay_prio_info(self._h, int(member), C.byref(total), C.byref(top)))
+        return dict(total=np.float64(total.value), top=np.float32(top.value))
+
+    def _replay_prio_sizes(self):
+        """(ring size, batch size) of whichever off-policy trainer lives; without one the engine itself says what is missing"""
+        L, h, b, sz = self._lib, self._h, C.c_int32(0), C.c_int64(0)
+        if L.adc_engine_td3_batch_size(h, C.byref(b)) == _ffi.ADC_OK:
+            check(L.adc_engine_td3_buffer_info(h, C.byref(sz), None, None))
+        elif L.adc_engine_sac_batch_size(h, C.byref(b)) == _ffi.ADC_OK:
+            check(L.adc_engine_sac_buffer_info(h, C.byref(sz), None, None))
+        elif L.adc_engine_td3_pop_buffer_info(h, C.byref(sz), None, None, C.byref(b)) != _ffi.ADC_OK:
+            if L.adc_engine_sac_pop_buffer_info(h, C.byref(sz), None, None, C.byref(b)) != _ffi.ADC_OK:
+                check(L.adc_engine_replay_prio_info(h, 0, None, None))
+                raise RuntimeError("prioritised replay without an off-policy trainer")
+        return sz.value, b.value
+
+    def replay_prio_fetch(self, member=0, slot=0, count=None):
+        """the leaves of the slots [slot, slot + count) (default: up to the ring's size): float32"""
+        if count is None:
+            count = self._replay_prio_sizes()[0] - int(slot)
+        leaf = np.zeros(max(int(count), 0), np.float32)
+        if leaf.size or count != 0:
+            check(self._lib.adc_engine_replay_prio_fetch(self._h, int(member), int(slot), int(count), leaf.ctypes.data))
+        return leaf
+
+    def replay_prio_load(self, leaf, top, member=0, slot=0):
+        """leaves (finite, > 0) for the stored slots from `slot` on, and top; the tree's nodes are rebuilt"""
+        leaf = np.ascontiguousarray(leaf, dtype=np.float32)
+        if leaf.ndim != 1:
+            raise ValueError("replay_prio_load: leaf [count]")
+        check(self._lib.adc_engine_replay_prio_load(self._h, int(member), int(slot), leaf.size, leaf.ctypes.data, float(np.float32(top))))
+
+    def replay_prio_batch(self, update, member=0):
+        """what update number `update` would draw from the tree as it stands: (slots [batch_size] int32, weights [batch_size] float32)"""
+        B = self._replay_prio_sizes()[1]
+        idx, w = np.zeros(B, np.int32), np.zeros(B, np.float32)
+        check(self._lib.adc_engine_replay_prio_batch(self._h, int(member), int(update), idx.ctypes.data, w.ctypes.data))
+        return idx, w
+
+    def replay_prio_state(self, member=0, state=None):
+        """a member's priorities.  get (no state): dict of leaf [size] float32 and top; set: such a dict, after the ring was loaded -
+        with the trainer's state and the ring the run continues bit for bit"""
+        if state is None:
+            size = self._replay_prio_sizes()[0]
+            return dict(leaf=self.replay_prio_fetch(member, 0, size) if size else np.zeros(0, np.float32), top=self.replay_prio_info(member)["top"])
+        if np.asarray(state["leaf"]).size:
+            self.replay_prio_load(state["leaf"], state["top"], member)
+
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
         self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)

@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--bid-hi", type=float, default=3.0)
     ap.add_argument("--eval-envs", type=int, default=256)
     ap.add_argument("--print-every", type=int, default=4)
+    ap.add_argument("--prioritized-replay", action="store_true",
+                    help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
     K, days, n, M, budget = args.num_keywords, args.days, args.envs_per_member, args.members, 100000.0
     N = M * n
@@ -68,7 +70,8 @@ def main():
     lo = np.concatenate([[1.0], np.full(K, args.bid_lo)]).astype(np.float32)          # (the budget is overridden during training and evaluation)
     hi = np.concatenate([[budget], np.full(K, args.bid_hi)]).astype(np.float32)
     policies = [two_headed_policy(K, days, args.bid_lo, args.bid_hi, seed=m) for m in range(M)]
-    trainer = sac_trainer.SACPopulationTrainer(eng, policies, configs, lo, hi, horizon=days)
+    trainer = sac_trainer.SACPopulationTrainer(eng, policies, configs, lo, hi, horizon=days,
+                                               prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None)
     scheduler = PBTScheduler(trainer, replace_fraction=0.25, tuned=("actor_lr", "alpha"), bounds={"actor_lr": (LR_LO, LR_HI), "alpha": (ALPHA_LO, ALPHA_HI)},
                              factors=(0.8, 1.25), fitness_ema=0.5, every=args.every, seed=11, with_ring=True)
     print(f"{M} SAC learners x {n} envs x {K} keywords on one engine, actor_lr {lrs[0]:.0e} .. {lrs[-1]:.0e}, alpha {alphas[0]:.2f} .. {alphas[-1]:.2f}, "

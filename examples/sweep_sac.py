@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--bid-lo", type=float, default=0.01)
     ap.add_argument("--bid-hi", type=float, default=3.0)
     ap.add_argument("--eval-envs", type=int, default=256)
+    ap.add_argument("--prioritized-replay", action="store_true",
+                    help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
     K, days, n = args.num_keywords, args.days, args.envs_per_member
     cells = [(float(a), float(t), int(s)) for a, t, s in itertools.product(args.actor_lrs.split(","), args.alpha_lrs.split(","), args.seeds.split(","))]
@@ -69,7 +71,8 @@ def main():
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(np.concatenate([member_planes] * M, axis=1))
     eng.reset()
-    trainer = sac_trainer.SACPopulationTrainer(eng, policy, configs, lo, hi, horizon=days)
+    trainer = sac_trainer.SACPopulationTrainer(eng, policy, configs, lo, hi, horizon=days,
+                                               prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None)
     print(f"{M} SAC learners x {n} envs x {K} keywords on one engine, {days} days and {args.updates} updates per iteration; held-out: {args.eval_envs} envs; "
           f"zero-margin: return {zm_ret.mean():.2f} NCP {zm_ncp:.3f}")
     start, _ = evaluate("mlp", sac_trainer.SquashedPolicy(policy, lo, hi), held_out, days, BUDGET)

@@ -61,6 +61,8 @@ def main():
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter per member; the rings hold raw rows")
     ap.add_argument("--normalize-rewards", action="store_true", help="per member, the reward divided by the discounted return's running standard deviation")
     ap.add_argument("--solo", action="store_true", help="afterwards, the same grid as solo trainers one after another (wall time)")
+    ap.add_argument("--prioritized-replay", action="store_true",
+                    help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
     K, days, n = args.num_keywords, args.days, args.envs_per_member
     cells = list(itertools.product(*([float(x) for x in s.split(",")] for s in (args.actor_lrs, args.critic_lrs, args.sigmas))))
@@ -72,8 +74,10 @@ def main():
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(np.concatenate([member_planes] * M, axis=1))
     eng.reset()
+    prio = dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None
     trainer = td3_trainer.TD3PopulationTrainer(eng, policy, [s for _, _, s in cells], configs, horizon=days,
-                                               normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards)
+                                               normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
+                                               prioritized_replay=prio)
     print(f"{M} TD3 learners x {n} envs x {K} keywords on one engine, {days} days and {args.updates} updates per iteration")
     print("member    " + " ".join(f"{m:>8d}" for m in range(M)))
     print("actor_lr  " + " ".join(f"{a:8.0e}" for a, _, _ in cells))
@@ -98,7 +102,7 @@ def main():
             e.set_all_params(member_planes)
             e.reset()
             tr = td3_trainer.TD3Trainer(e, policy, horizon=days, exploration_sigma=sigma, normalize_observations=args.normalize_observations,
-                                        normalize_rewards=args.normalize_rewards, **cfg)
+                                        normalize_rewards=args.normalize_rewards, prioritized_replay=prio, **cfg)
             c = curves_of(lambda seeds: tr.iteration(days, BUDGET, reset=True, reset_seeds=seeds),
                           lambda: [e.rollout_fetch()["reward"].astype(np.float64).sum(axis=0).mean()], args.iterations, n)
             solo_last.append(c[-5:].mean())

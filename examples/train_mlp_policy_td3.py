@@ -60,6 +60,8 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=1024)
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device; the ring holds raw rows")
     ap.add_argument("--normalize-rewards", action="store_true", help="the reward divided by the discounted return's running standard deviation")
+    ap.add_argument("--prioritized-replay", action="store_true",
+                    help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
@@ -74,7 +76,8 @@ def main():
                              reward_scale=args.reward_scale, gamma=args.gamma, actor_lr=args.actor_lr, action_lo=0.01, action_hi=3.0,
                              action_norm=(np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32)))
     trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days), horizon=days, normalize_observations=args.normalize_observations,
-                                     normalize_rewards=args.normalize_rewards, **config)
+                                     normalize_rewards=args.normalize_rewards,
+                                     prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None, **config)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
     print(f"{0:>10} {'':>12} {'':>9} {ret:10.2f} {ncp:8.3f}")

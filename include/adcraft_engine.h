@@ -1302,6 +1302,56 @@ int adc_td3_norm_rew_host(const adc_td3_norm_config *cfg, int32_t days, int32_t 
 int adc_td3_y_norm_host(const adc_td3_config *td3, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, float scale, float clip,
                         float *y_b);
 
+/* ---- prioritised replay for the TD3 and SAC learners (the law is csrc/adc_per.h) --------------------------------------------------
+ * An add-on of the live adc_engine_td3_init / _sac_init / _td3_pop_init / _sac_pop_init trainer: the batch of an update is drawn in
+ * proportion to the slots' priorities from a radix-64 sum tree that lives on the device next to the ring (one tree, one `top` and
+ * one set of batch buffers per member of a population, one configuration for all), the critics' output deltas and loss pieces are
+ * weighted by the batch's importance weights w_b in (0, 1] (normalised by the batch's largest weight, not the buffer's), and after
+ * the critics' pass the sampled slots' leaves become pa(0.5 (|d_1| + |d_2|) + eps) - the maximum over the batch elements that drew
+ * the slot - and the nodes on their paths are rebuilt from their children.  The actor's step, the temperature's and the other
+ * statistics are unweighted.  A transition written by *_store or *_buffer_load gets leaf = top, the largest leaf any update has
+ * written (1 at init).  An update enqueues 4 + L launches more than without the add-on (sample, weights, priorities, leaves, one
+ * rebuild per level; L = ceil(log64 capacity) >= 1), whatever the batch size and the number of members are, and waits for nothing;
+ * a store 1 + L per contiguous slot range (two when the ring wraps).  Without adc_engine_replay_prio_init every call launches the
+ * kernels it launched and computes the bits it computed.
+ * adc_replay_prio_config_check (host only): struct_size; alpha and beta in [0, 1]; eps > 0 and finite; cap > eps and finite.
+ * adc_engine_replay_prio_init needs a live TD3 or SAC trainer, solo or population (ADC_ESTATE otherwise); a ring that already
+ * holds transitions is fine: its slots get leaf 1.  A second init starts over.  _set_beta (the host's annealing schedule) takes
+ * effect from the next update enqueued.  _info: member's total (the root) and top.  _fetch: the leaves of the slots [slot, slot +
+ * count) inside [0, size).  _load: those leaves from the host (finite and > 0, ADC_EINVAL otherwise) and `top` (finite, > 0); the
+ * nodes are rebuilt.  _batch: what update number `update` would draw from the tree as it stands: the slots idx_b [B] and the
+ * weights weight_b [B] (either may be NULL); ADC_ESTATE on an empty ring.  `member` is 0 for a solo trainer.
+ * While the add-on lives adc_engine_{td3,sac,td3_pop,sac_pop}_batch_indices are refused (ADC_ESTATE): they speak for the uniform
+ * law.  The add-on ends with its trainer, under adc_engine_td3_norm_init's rules.  Copies that carry the ring carry the member's
+ * leaves, nodes and top: adc_engine_td3_pop_copy / _sac_pop_copy with with_ring != 0 and adc_engine_pbt_exploit with rings;
+ * without the ring they leave them alone. */
+typedef struct adc_replay_prio_config {
+    uint32_t struct_size;          /* sizeof(adc_replay_prio_config) */
+    float alpha;                   /* [0, 1]: the priorities' exponent; 0: every leaf is 1 (uniform over the stored slots) */
+    float beta;                    /* [0, 1]: the importance weights' exponent; 0: every weight is 1 */
+    float eps;                     /* > 0, finite: added to the error, and the floor of a priority */
+    float cap;                     /* > eps, finite: the ceiling of a priority */
+} adc_replay_prio_config;
+int adc_replay_prio_config_check(const adc_replay_prio_config *cfg, const char **message);
+int adc_engine_replay_prio_init(adc_engine *e, const adc_replay_prio_config *cfg);
+int adc_engine_replay_prio_set_beta(adc_engine *e, float beta);
+int adc_engine_replay_prio_info(adc_engine *e, int32_t member, double *total, float *top);
+int adc_engine_replay_prio_fetch(adc_engine *e, int32_t member, int64_t slot, int64_t count, float *leaf);
+int adc_engine_replay_prio_load(adc_engine *e, int32_t member, int64_t slot, int64_t count, const float *leaf, float top);
+int adc_engine_replay_prio_batch(adc_engine *e, int32_t member, int64_t update, int32_t *idx_b, float *weight_b);
+/* the host twins: the same code as the device's, on a tree over `capacity` slots built from leaf_c [capacity] (zeros past the
+ * stored slots).  tree: nodes receives the levels 1 .. L one after the other, n_l = ceil(n_{l-1} / 64) values each (counts [7]
+ * receives n_0 .. n_L, zeros after; either may be NULL); returns L, or a negative error.  descend: the slot a descent with m reaches.
+ * sample: idx_b / weight_b of update `update` under the td3 key of `seed` (adc_td3.h) for a ring of `size` stored slots.
+ * priority: pa_b [count] = pa(p) of the unweighted errors d1_b, d2_b.  leaf_update: leaf_c and *top after the batch's slots idx_b
+ * took pa_b (the maximum over duplicates). */
+int adc_per_tree_host(int64_t capacity, const float *leaf_c, double *nodes, int64_t *counts);
+int adc_per_descend_host(int64_t capacity, const float *leaf_c, double m, int64_t *slot);
+int adc_per_sample_host(const adc_replay_prio_config *cfg, int64_t capacity, int64_t size, const float *leaf_c, uint64_t seed, int64_t update, int32_t count,
+                        int32_t *idx_b, float *weight_b);
+int adc_per_priority_host(const adc_replay_prio_config *cfg, int32_t count, const float *d1_b, const float *d2_b, float *pa_b);
+int adc_per_leaf_update_host(int64_t capacity, float *leaf_c, float *top, int32_t count, const int32_t *idx_b, const float *pa_b);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be

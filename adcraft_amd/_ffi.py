@@ -152,6 +152,11 @@ class TD3NormConfig(C.Structure):
                 ("obs_count_cap", C.c_int64), ("rew_min_std", C.c_double), ("rew_count_cap", C.c_int64), ("rew_clip", C.c_float)]
 
 
+class SACNormConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("observations", C.c_int32), ("rewards", C.c_int32), ("per_member", C.c_int32), ("obs_min_std", C.c_double),
+                ("obs_count_cap", C.c_int64), ("rew_min_std", C.c_double), ("rew_count_cap", C.c_int64), ("rew_clip", C.c_float)]
+
+
 class ReplayPrioConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("beta", C.c_float), ("eps", C.c_float), ("cap", C.c_float)]
 
@@ -470,6 +475,15 @@ def lib():
         "adc_engine_td3_norm_copy": ([vp, vp], C.c_int),
         "adc_td3_norm_obs_host": ([C.POINTER(TD3NormConfig), i64, i32, vp, C.POINTER(i64), vp, vp, vp, vp], C.c_int),
         "adc_td3_norm_rew_host": ([C.POINTER(TD3NormConfig), i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32), vp], C.c_int),
+        "adc_sac_norm_config_check": ([C.POINTER(SACNormConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_sac_norm_init": ([vp, C.POINTER(SACNormConfig)], C.c_int),
+        "adc_engine_sac_norm_update": ([vp, C.POINTER(i64)], C.c_int),
+        "adc_engine_sac_norm_state_get": ([vp, i32, C.POINTER(i64), vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64), C.POINTER(f32)], C.c_int),
+        "adc_engine_sac_norm_state_set": ([vp, i32, i64, vp, vp, vp, vp, i64, f64, f64, f32], C.c_int),
+        "adc_engine_sac_norm_returns_get": ([vp, vp], C.c_int),
+        "adc_engine_sac_norm_returns_set": ([vp, vp], C.c_int),
+        "adc_engine_sac_norm_copy": ([vp, vp], C.c_int),
+        "adc_sac_y_norm_host": ([C.POINTER(SACConfig), i32, vp, vp, vp, vp, f32, f32, f32, vp], C.c_int),
         "adc_replay_prio_config_check": ([C.POINTER(ReplayPrioConfig), C.POINTER(C.c_char_p)], C.c_int),
         "adc_engine_replay_prio_init": ([vp, C.POINTER(ReplayPrioConfig)], C.c_int),
         "adc_engine_replay_prio_set_beta": ([vp, f32], C.c_int),

@@ -71,6 +71,9 @@ class PBTScheduler:
             # (a copied TD3 learner takes its donor's observation vectors, moments and reward multiplier with it: one launch; its envs'
             # running returns stay, and the fitness above came from the raw recorded reward)
             self.engine.td3_norm_copy(res["src"])
+        if self.kind == "sac" and (getattr(tr, "normalize_observations", False) or getattr(tr, "normalize_rewards", False)):
+            # (... and so does a copied SAC learner: one launch, whatever the number of members)
+            self.engine.sac_norm_copy(res["src"])
         old_log_std = [t.log_std.copy() for t in tr._templates] if self.kind == "td3" and "sigma" in self.tuned else None
         for m, src in enumerate(res["src"]):
             if src < 0:

@@ -12,7 +12,7 @@ import copy
 
 import numpy as np
 
-from .td3_trainer import PrioritizedReplay, policy_from_actor, random_critics
+from .td3_trainer import NORM_OPTIONS, PrioritizedReplay, _norm_options, _norm_state, _with_vectors, policy_from_actor, random_critics
 
 
 def sac(num_keywords, **overrides):
@@ -37,20 +37,59 @@ class SquashedPolicy:
         engine.mlp_set_squash(self.action_lo, self.action_hi)
 
 
-class SACTrainer(PrioritizedReplay):
+def _sac_norm_options(policies, normalize_observations, normalize_rewards, norm, config):
+    """the normalisers' options: the dict `norm`, or NORM_OPTIONS keys given among a trainer's keyword options (taken out of config)"""
+    loose = {k: config.pop(k) for k in NORM_OPTIONS if k in config}
+    if loose and norm is not None:
+        raise ValueError("the normalisers' options are given either as norm=dict(...) or as keywords, not both")
+    return _norm_options(policies, normalize_observations, normalize_rewards, loose or norm)
+
+
+class _NormalizedSAC:
+    """the trainers' side of normalize_observations / normalize_rewards: running normalisers on the device (StepEngine.sac_norm_*;
+    csrc/adc_sac_norm.h).  The record and the ring then hold raw observations and raw rewards and every batch is normalised as it is
+    sampled, with the statistics updated from every collection BEFORE its updates.  Only the reward is scaled, not the entropy term:
+    target_entropy and alpha then trade against a return of about unit standard deviation.  What the normalisers gain in learning
+    has not been measured."""
+
+    def _norm_on(self):
+        return self.normalize_observations or self.normalize_rewards
+
+    def _norm_carry(self, get_or_set, member, state, envs=None):
+        """get_or_set(state): the trainer's own state call; `norm` (the normaliser's moments, vectors, multiplier and the envs' return
+        carries) rides along, so that a resumed run continues bit for bit"""
+        if state is None:
+            st = get_or_set(None)
+            if self._norm_on():
+                st["norm"] = _norm_state(self.engine, member, None, envs, family="sac")
+            return st
+        state = dict(state)
+        norm = state.pop("norm", None)
+        get_or_set(state)
+        if norm is not None and self._norm_on():
+            _norm_state(self.engine, member, norm, envs, family="sac")
+
+
+class SACTrainer(PrioritizedReplay, _NormalizedSAC):
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (2 (K + 1) outputs, log_std_clamp set; a
     value network is ignored); action_lo / action_hi [K + 1] (or scalars): the squash bounds in the flat action order (budget,
     bids); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection; learning_starts:
     transitions the ring must hold before the first update; updates_per_iteration: updates after every collection.  config:
     sac()'s other keys and StepEngine.sac_config's options, plus critic_seed (random_critics' seed) and critics (two lists of
-    layers, instead).  prioritized_replay: None, or PrioritizedReplay's dict (td3_trainer.py)."""
+    layers, instead).  prioritized_replay: None, or PrioritizedReplay's dict (td3_trainer.py).
+
+    normalize_observations / normalize_rewards: running normalisers on the device (_NormalizedSAC above); their options -
+    obs_min_std, obs_count_cap, rew_min_std, rew_count_cap, rew_clip - as keywords or as norm=dict(...).  state() / load_state()
+    carry the normaliser."""
 
     def __init__(self, engine, policy, action_lo, action_hi, critic_hidden=(256, 256), horizon=10, learning_starts=1500, updates_per_iteration=64,
-                 agent_seeds=None, prioritized_replay=None, **config):
+                 agent_seeds=None, prioritized_replay=None, normalize_observations=False, normalize_rewards=False, norm=None, **config):
+        cfg = dict(config)
+        norm = _sac_norm_options([policy], normalize_observations, normalize_rewards, norm, cfg)
         A = policy.num_keywords + 1
         if policy.output_size != 2 * A or policy.log_std_clamp is None:
             raise ValueError("SAC needs a policy that ends in 2 (K + 1) outputs (means, log-stds) with log_std_clamp set")
-        cfg = dict(config)
+        self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
         critics, critic_seed = cfg.pop("critics", None), cfg.pop("critic_seed", 0)
         self.engine, self.horizon = engine, int(horizon)
         self.learning_starts, self.updates_per_iteration = int(learning_starts), int(updates_per_iteration)
@@ -62,6 +101,8 @@ class SACTrainer(PrioritizedReplay):
         engine.rollout_enable(self.horizon, obs=True)
         engine.sac_init(**self.config)
         engine.sac_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed))
+        if self._norm_on():
+            engine.sac_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self._prio_init(engine, prioritized_replay)
         self.history = []
 
@@ -75,6 +116,8 @@ class SACTrainer(PrioritizedReplay):
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.sac_store()
+        if self._norm_on():
+            e.sac_norm_update()             # (the batches below are scaled by statistics that include the newest days)
         size = e.sac_buffer(fetch=False)["size"]
         if size >= self.learning_starts:
             self._prio_anneal()
@@ -84,13 +127,25 @@ class SACTrainer(PrioritizedReplay):
 
     def policy(self):
         """the trained actor with the squash bounds its actions are meant under"""
-        return SquashedPolicy(policy_from_actor(self._template, self.engine.sac_state()["theta"]), self.action_lo, self.action_hi)
+        pol = policy_from_actor(self._template, self.engine.sac_state()["theta"])
+        if self.normalize_observations:
+            pol = _with_vectors(pol, self.engine.sac_norm_state())      # (the observation filter's current vectors)
+        return SquashedPolicy(pol, self.action_lo, self.action_hi)
 
     def state(self, state=None):
-        return self._prio_state(self.engine.sac_state, 0, state)
+        """the learner's state (StepEngine.sac_state's dict), `replay_prio` under prioritised replay and `norm` under running
+        normalisers; get or set.  With the ring (sac_buffer) a resumed run continues bit for bit"""
+        return self._norm_carry(lambda s: self._prio_state(self.engine.sac_state, 0, s), 0, state)
+
+    def load_state(self, state):
+        self.state(state)
+
+    def norm_state(self, state=None):
+        """the normalisers' state: StepEngine.sac_norm_state's dict plus `returns`, the envs' running discounted returns; get or set"""
+        return _norm_state(self.engine, 0, state, family="sac")
 
 
-class SACPopulationTrainer(PrioritizedReplay):
+class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
     """M independent SAC learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
     actor, twin critics, target critics, temperature, optimiser state, hyperparameters and replay ring, and every launch of a
     store or an update covers all members (StepEngine.sac_pop_*).  What a member computes is bit for bit what SACTrainer computes
@@ -102,12 +157,20 @@ class SACPopulationTrainer(PrioritizedReplay):
     of the two counts; action_lo / action_hi [K + 1] (or scalars): the squash bounds, shared by all members.  critic_hidden,
     batch_size, capacity, target_update_interval, learning_starts (transitions of a member's ring) and updates_per_iteration
     must be equal in all configurations: the members move together.  prioritized_replay: None, or PrioritizedReplay's dict,
-    shared by all members (every member has its own tree)."""
+    shared by all members (every member has its own tree).
+
+    normalize_observations / normalize_rewards: every member has its own running normalisers (per_member; _NormalizedSAC above),
+    fed from its own envs: member m's are bit for bit a single trainer's of its envs.  norm: dict of obs_min_std, obs_count_cap,
+    rew_min_std, rew_count_cap, rew_clip, shared by all members.  state(m) / load_state(m, ...) carry member m's normaliser; a
+    PBTScheduler over this trainer copies the donors' normalisers."""
 
     SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
 
-    def __init__(self, engine, policies, configs, action_lo, action_hi, horizon=10, agent_seeds=None, members=None, prioritized_replay=None):
+    def __init__(self, engine, policies, configs, action_lo, action_hi, horizon=10, agent_seeds=None, members=None, prioritized_replay=None,
+                 normalize_observations=False, normalize_rewards=False, norm=None):
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
+        norm = _norm_options(policies, normalize_observations, normalize_rewards, norm)
+        self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
         configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
         members = max(len(policies), len(configs)) if members is None else int(members)
         if any(len(x) not in (1, members) for x in (policies, configs)) or not policies or not configs:
@@ -145,6 +208,8 @@ class SACPopulationTrainer(PrioritizedReplay):
         engine.sac_pop_init(self.configs)
         for m in range(members):
             engine.sac_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]))
+        if self._norm_on():
+            engine.sac_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self._prio_init(engine, prioritized_replay)
         self.history = []
 
@@ -158,6 +223,8 @@ class SACPopulationTrainer(PrioritizedReplay):
         e.rollout_reset()
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.sac_pop_store()
+        if self._norm_on():
+            e.sac_norm_update()             # (one call for all members, whatever their number)
         size = e.sac_pop_buffer(fetch=False)["size"]
         if size >= self.learning_starts:
             self._prio_anneal()
@@ -167,7 +234,10 @@ class SACPopulationTrainer(PrioritizedReplay):
 
     def policy(self, member):
         """one member's trained actor with the squash bounds its actions are meant under"""
-        return SquashedPolicy(policy_from_actor(self._templates[member], self.engine.sac_pop_state(member)["theta"]), self.action_lo, self.action_hi)
+        pol = policy_from_actor(self._templates[member], self.engine.sac_pop_state(member)["theta"])
+        if self.normalize_observations:
+            pol = _with_vectors(pol, self.engine.sac_norm_state(member))
+        return SquashedPolicy(pol, self.action_lo, self.action_hi)
 
     def returns(self):
         """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days"""
@@ -175,7 +245,17 @@ class SACPopulationTrainer(PrioritizedReplay):
         return r.reshape(self.members, -1).mean(axis=1)
 
     def state(self, member, state=None):
-        return self._prio_state(lambda s: self.engine.sac_pop_state(member, s), member, state)
+        """member's state (StepEngine.sac_pop_state's dict), `replay_prio` under prioritised replay and `norm` under running
+        normalisers; get or set"""
+        envs = self.engine.num_envs // self.members
+        return self._norm_carry(lambda s: self._prio_state(lambda t: self.engine.sac_pop_state(member, t), member, s), member, state, envs)
+
+    def load_state(self, member, state):
+        self.state(member, state)
+
+    def norm_state(self, member, state=None):
+        """member's normalisers' state: StepEngine.sac_norm_state's dict plus `returns`, its envs' running discounted returns"""
+        return _norm_state(self.engine, member, state, self.engine.num_envs // self.members, family="sac")
 
     def copy(self, src, dst, with_ring=False):
         """member src's actor, critics, target critics, moments and temperature into member dst (with_ring: its ring too); dst

@@ -80,20 +80,22 @@ def _with_vectors(policy, state):
     return policy
 
 
-def _norm_state(engine, member, state, envs=None):
-    """StepEngine.td3_norm_state's dict plus `returns`, the (member's) envs' running discounted returns, when rewards are normalised"""
+def _norm_state(engine, member, state, envs=None, family="td3"):
+    """StepEngine.td3_norm_state's dict (family "sac": sac_norm_state's) plus `returns`, the (member's) envs' running discounted
+    returns, when rewards are normalised"""
+    norm_state, norm_returns = getattr(engine, family + "_norm_state"), getattr(engine, family + "_norm_returns")
     n = engine.num_envs if envs is None else envs
     sl = slice(0, n) if envs is None else slice(member * n, (member + 1) * n)
     if state is None:
-        st = engine.td3_norm_state(member)
+        st = norm_state(member)
         if "rew_count" in st:
-            st["returns"] = engine.td3_norm_returns()[sl].copy()
+            st["returns"] = norm_returns()[sl].copy()
         return st
-    engine.td3_norm_state(member, state)
+    norm_state(member, state)
     if "returns" in state:
-        g = engine.td3_norm_returns()
+        g = norm_returns()
         g[sl] = state["returns"]
-        engine.td3_norm_returns(g)
+        norm_returns(g)
 
 
 class PrioritizedReplay:

@@ -64,7 +64,7 @@
 //   parts/kernel_norm.inc         the running normalisers, one set of kernels: the record's batch moments of the observations in one pass,
 //        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
 //        the learner's discount, their moments, the merge, the multiplier, the GAE kernels under a multiplier and a clip (adc_rew_norm.h);
-//        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop normalise as they gather.
+//        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop and of kernel_sac / kernel_sac_pop (adc_sac_norm.h) normalise as they gather.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
 //   parts/pg_kl_api.inc           the entry points of the KL penalty / value-clip add-on and what pg_api.inc calls of it.
 //   parts/pg_shuffle_api.inc      the entry points of the shuffled minibatches / target-KL stop add-on, the updates under it.
@@ -74,7 +74,7 @@
 //   parts/sac_pop_api.inc         the entry points of SAC learner populations, over td3_pop_api.inc's helpers.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over a PG, TD3 or SAC population.
 //   parts/per_api.inc             the entry points of prioritised replay over a TD3 or SAC trainer, and what the trainers' updates call of it.
-//   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners' - over shared helpers.
+//   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners', the SAC learners' - over shared helpers.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>
@@ -105,6 +105,7 @@
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
 #include "adc_td3_norm.h"
+#include "adc_sac_norm.h"
 #include "adc_per.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))

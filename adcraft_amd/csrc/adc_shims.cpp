@@ -26,6 +26,7 @@
 #include "adc_norm.h"
 #include "adc_rew_norm.h"
 #include "adc_td3_norm.h"
+#include "adc_sac_norm.h"
 #include "adc_per.h"
 
 #define ADC_EXPORT extern "C" __attribute__((visibility("default")))
@@ -1038,6 +1039,32 @@ ADC_EXPORT int adc_td3_y_norm_host(const adc_td3_config *td3, int32_t count, con
     if (count < 1 || !r_b || !done_b || !q_b || !y_b || !(clip >= 0.0f)) return ADC_EINVAL;
     const adc::Td3Law law = adc::td3_law_of(*td3);
     for (int32_t b = 0; b < count; ++b) y_b[b] = adc::td3_y_norm(r_b[b], done_b[b], q_b[b], law, scale, clip);
+    return ADC_OK;
+}
+
+// ---- the SAC learners' running normalisers on the host (adc_sac_norm.h; the moments' twins are the TD3 normalisers' above) --------
+ADC_EXPORT int adc_sac_norm_config_check(const adc_sac_norm_config *cfg, const char **message)
+{
+    const char *msg = nullptr;
+    if (!cfg || cfg->struct_size != sizeof(adc_sac_norm_config)) msg = "adc_sac_norm_config: NULL or struct_size mismatch";
+    else if (!cfg->observations && !cfg->rewards) msg = "observations or rewards: at least one must be nonzero";
+    else if (!(cfg->obs_min_std > 0.0 && cfg->obs_min_std < (double)__builtin_inff())) msg = "obs_min_std must be finite and > 0";
+    else if (cfg->obs_count_cap < 0) msg = "obs_count_cap >= 0 (0: no forgetting)";
+    else if (!(cfg->rew_min_std > 0.0 && cfg->rew_min_std < (double)__builtin_inff())) msg = "rew_min_std must be finite and > 0";
+    else if (cfg->rew_count_cap < 0) msg = "rew_count_cap >= 0 (0: no forgetting)";
+    else if (!(cfg->rew_clip >= 0.0f && cfg->rew_clip < __builtin_inff())) msg = "rew_clip must be finite and >= 0 (0: off)";
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+ADC_EXPORT int adc_sac_y_norm_host(const adc_sac_config *sac, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, const float *lp_b,
+                                   float alpha, float scale, float clip, float *y_b)
+{
+    if (adc_sac_config_check(sac, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (count < 1 || !r_b || !done_b || !q_b || !lp_b || !y_b || !(clip >= 0.0f)) return ADC_EINVAL;
+    // (sac_y_norm reads gamma and reward_scale of the law alone)
+    const adc::SacLaw law{sac->gamma, sac->tau, sac->reward_scale, sac->eps_sq, 0.0f, 0.0f};
+    for (int32_t b = 0; b < count; ++b) y_b[b] = adc::sac_y_norm(r_b[b], done_b[b], q_b[b], alpha, lp_b[b], law, scale, clip);
     return ADC_OK;
 }
 

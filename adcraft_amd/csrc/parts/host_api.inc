@@ -241,11 +241,13 @@ struct adc_engine {
     // the PPO / A2C learners (adc_engine_obs_norm_init; the law is adc_norm.h).  rn: their reward normaliser (adc_engine_rew_norm_init;
     // adc_rew_norm.h), which lives with the trainer whose gamma it discounts by.  tn: the TD3 learners' normalisers
     // (adc_engine_td3_norm_init; adc_td3_norm.h), which live with the TD3 trainer; while tn.obs lives the record's obs rows (and so
-    // the ring's) are raw observations
-    NormSet on, rn, tn;
+    // the ring's) are raw observations.  sn: the SAC learners' normalisers (adc_engine_sac_norm_init; adc_sac_norm.h), which live with
+    // the SAC trainer under the same rules; tn and sn never live together (one trainer owns the ring)
+    NormSet on, rn, tn, sn;
     adc_obs_norm_config on_cfg{};
     adc_rew_norm_config rn_cfg{};
     adc_td3_norm_config tn_cfg{};
+    adc_sac_norm_config sn_cfg{};
     // prioritised replay over the live TD3 / SAC trainer's ring(s), solo or population (adc_engine_replay_prio_init; parts/kernel_per.inc,
     // parts/per_api.inc; the law is adc_per.h).  Its device arrays are the trainer's allocations (td3_allocs): they go with it
     bool per_live = false;
@@ -944,7 +946,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->pg_allocs) (void)hipFree(p);
     if (e->pq_host) (void)hipHostFree(e->pq_host);
     for (void *p : e->td3_allocs) (void)hipFree(p);
-    for (NormSet *s : {&e->on, &e->rn, &e->tn}) norm_set_drop(e, *s);
+    for (NormSet *s : {&e->on, &e->rn, &e->tn, &e->sn}) norm_set_drop(e, *s);
     if (e->day_graph) (void)hipGraphExecDestroy(e->day_graph);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1240,9 +1242,9 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
         hipLaunchKernelGGL(k_clear_obs, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->v, d_mask);
         err = hipGetLastError();
     }
-    // (a reset env's running discounted return ends with its episode, the PPO / A2C learners' and the TD3 learners'; nothing is
-    //  enqueued without a reward normaliser)
-    for (const NormSet *s : {&e->rn, &e->tn}) {
+    // (a reset env's running discounted return ends with its episode, the PPO / A2C learners', the TD3 learners' and the SAC
+    //  learners'; nothing is enqueued without a reward normaliser)
+    for (const NormSet *s : {&e->rn, &e->tn, &e->sn}) {
         if (err != hipSuccess || !s->rew.G) continue;
         hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
                            s->rew.G);
@@ -2881,7 +2883,7 @@ inline MlpRecordSlot rollout_slot(const adc_engine *e, bool record, int t, size_
 {
     MlpRecordSlot r{nullptr, nullptr, nullptr, nullptr, 0};
     if (!record) return r;
-    r.raw_obs = e->tn.obs.count ? 1 : 0;
+    r.raw_obs = (e->tn.obs.count || e->sn.obs.count) ? 1 : 0;
     const size_t n = (size_t)e->v.N, row = (size_t)t * n + e0;
     r.action = e->ro_action + row * (size_t)e->mp.A;
     r.logp = e->ro_logp + row;
@@ -2977,6 +2979,7 @@ void pg_drop(adc_engine *e)
 void td3_drop(adc_engine *e)
 {
     norm_set_drop(e, e->tn);            // (the record is back to network inputs)
+    norm_set_drop(e, e->sn);            // (the SAC learners' normalisers end where their trainer ends)
     e->per_live = false; e->per = PerView{};    // (prioritised replay's arrays are among td3_allocs)
     pbt_forget(e, ADC_PBT_TD3);
     pbt_forget(e, ADC_PBT_SAC);         // (a SAC population's scheduler: its arrays are among td3_allocs too)
@@ -3166,7 +3169,7 @@ ADC_EXPORT int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, cons
     if (!e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
     if (!shift_d || !scale_d) return fail(ADC_EINVAL, "shift or scale is NULL");
     ENGINE_GUARD(e);
-    for (const NormSet *s : {&e->on, &e->tn}) {
+    for (const NormSet *s : {&e->on, &e->tn, &e->sn}) {
         if (!s->shared_shift) continue;
         // per-member vectors are in force: every member's row, and the policy's own vectors (the running moments are not touched)
         const size_t D = (size_t)e->mp.D;
@@ -3775,7 +3778,7 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     ENGINE_GUARD(e);
     if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
     e->ro_t = 0;
-    for (NormSet *s : {&e->on, &e->rn, &e->tn}) s->t0 = 0;
+    for (NormSet *s : {&e->on, &e->rn, &e->tn, &e->sn}) s->t0 = 0;
     e->ro_deterministic = false;
     e->pg_adv_ready = false;
     e->td3_stored_t = 0;

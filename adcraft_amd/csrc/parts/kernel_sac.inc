@@ -28,6 +28,16 @@ struct SacView {
     float *xin;                             // [B][D + A] the gathered rows [x | t]
     float *acts, *deltas, *pieces;          // scratch [B][na], [B][nd], [B][kTd3Pieces]
     int na, nd, maxw;
+    // the running normalisers (adc_engine_sac_norm_init; adc_sac_norm.h).  n_shift non-null: the ring's x / x' are raw and are
+    // normalised as they are gathered, with the vectors at n_shift / n_scale + member * n_stride.  r_scale non-null: the target is
+    // sac_y_norm under the multiplier r_scale[member * r_stride] and r_clip.  Both null: the host launches the batch kernels'
+    // NORM = false instantiations, which do not read these fields: their loads and bits are what they were
+    // (the fields stand behind the others, whose places in the kernel arguments are what they were)
+    const float *n_shift, *n_scale;         // [D] or [M][D]
+    size_t n_stride;                        // floats between two members' vectors; 0: shared
+    const float *r_scale;                   // [1] or [M]
+    int r_stride;                           // 1: a multiplier per member; 0: shared
+    float r_clip;
 };
 enum { kSacCellLogAlpha = 0, kSacCellM = 1, kSacCellV = 2, kSacCellAlpha = 3 };
 
@@ -80,6 +90,7 @@ __device__ __forceinline__ void sac_lp(const SacLds &s, int A, float *out)
 }
 
 // y of batch element blockIdx.x
+template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_target(SacView p)
 {
     extern __shared__ __align__(16) float sac_lds[];
@@ -89,7 +100,13 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_target(SacView p)
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
     const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     const float alpha = p.cell[kSacCellAlpha];
-    for (int j = tid; j < D; j += kPgBlock) s.row[j] = p.ring.x2[slot * (size_t)D + j];
+    // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
+    const float r_mult = NORM && p.r_scale ? p.r_scale[0] : 1.0f;
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = p.ring.x2[slot * (size_t)D + j];
+        if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        s.row[j] = xj;
+    }
     __syncthreads();
     td3_forward(p.pol, sh.activation, s.row, s.yp, nullptr);
     sac_heads(p, s, s.yp + adc::td3_hidden(sh.pol), adc::ST_SAC_NEXT, b);
@@ -100,10 +117,15 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_target(SacView p)
         if (tid == 0) s.words[i] = s.yq[qlast];
         __syncthreads();
     }
-    if (tid == 0) p.ybuf[b] = adc::sac_y(p.ring.r[slot], p.ring.done[slot], adc::td3_min(s.words[0], s.words[1]), alpha, s.words[2], p.law);
+    if (tid == 0) {
+        const float q = adc::td3_min(s.words[0], s.words[1]);
+        p.ybuf[b] = NORM && p.r_scale ? adc::sac_y_norm(p.ring.r[slot], p.ring.done[slot], q, alpha, s.words[2], p.law, r_mult, p.r_clip)
+                              : adc::sac_y(p.ring.r[slot], p.ring.done[slot], q, alpha, s.words[2], p.law);
+    }
 }
 
 // forward and backward of both critics on batch element blockIdx.x: k_td3_critic_sample with t = tanh(ring.a) as the action input
+template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
 {
     extern __shared__ __align__(16) float sac_lds[];
@@ -114,7 +136,8 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
     const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     float *xin = p.xin + (size_t)b * (size_t)DA;
     for (int j = tid; j < DA; j += kPgBlock) {
-        const float xj = j < D ? p.ring.x[slot * (size_t)D + j] : adc::mlp_tanh(p.ring.a[slot * (size_t)A + (j - D)]);
+        float xj = j < D ? p.ring.x[slot * (size_t)D + j] : adc::mlp_tanh(p.ring.a[slot * (size_t)A + (j - D)]);
+        if (NORM && p.n_shift && j < D) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
         s.row[j] = xj;
         xin[j] = xj;
     }
@@ -140,6 +163,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
 
 // the actor's forward and head, both critics on [x | t], the smaller one's backward through to the action inputs, the head's
 // deltas for its 2A outputs, the actor's backward
+template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_actor_sample(SacView p)
 {
     extern __shared__ __align__(16) float sac_lds[];
@@ -149,7 +173,11 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_actor_sample(SacView p)
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
     const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
     const float alpha = p.cell[kSacCellAlpha];
-    for (int j = tid; j < D; j += kPgBlock) s.row[j] = p.ring.x[slot * (size_t)D + j];
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = p.ring.x[slot * (size_t)D + j];
+        if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        s.row[j] = xj;
+    }
     __syncthreads();
     float *acts = p.acts + (size_t)b * (size_t)p.na, *deltas = p.deltas + (size_t)b * (size_t)p.nd;
     td3_forward(p.pol, sh.activation, s.row, s.yp, acts);

@@ -18,7 +18,9 @@ struct SacMember {
 
 // The batch kernels: batch element blockIdx.x of member blockIdx.y.  p carries what the members share (the shapes, the ring's
 // size, the update's number, the scratch for all members, na / nd / maxw); p.law, p.pol, p.q, p.q_t, p.cell, p.ring and p.key are
-// not read.  A member's scratch rows, ybuf and pieces start at member * gridDim.x.
+// not read.  A member's scratch rows, ybuf and pieces start at member * gridDim.x.  Under a running normaliser (p.n_shift / p.r_scale
+// non-null; adc_sac_norm.h) the member's vectors are at member * p.n_stride, its multiplier at member * p.r_stride: the NORM = true
+// instantiations; without one the host launches NORM = false, which does not read those fields.
 
 // what sac_heads reads of a view - the sizes, the update's number, the key, the law - with the member's key and law.  (The rest
 // stays zero and is never read: a whole copy of p would have its shape arrays indexed by a loop's counter, in scratch)
@@ -33,6 +35,7 @@ __device__ __forceinline__ SacView sac_pop_heads_view(const SacView &p, uint64_t
 }
 
 // y of the element
+template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_pop_target(SacView p, const MlpLearner *__restrict__ learners, const Td3Member *__restrict__ mem,
                                                              const SacMember *__restrict__ smem)
 {
@@ -48,7 +51,14 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_target(SacView p, const Ml
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
     const size_t slot = p.p_slot ? (size_t)p.p_slot[(size_t)blockIdx.y * gridDim.x + b] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
     const float alpha = smem[blockIdx.y].cell[kSacCellAlpha];
-    for (int j = tid; j < D; j += kPgBlock) s.row[j] = ring.x2[slot * (size_t)D + j];
+    const size_t nv = NORM ? (size_t)blockIdx.y * p.n_stride : 0;          // (the member's row of the normaliser's vectors; 0 whenever they are shared)
+    // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
+    const float r_mult = NORM && p.r_scale ? p.r_scale[(size_t)blockIdx.y * (size_t)p.r_stride] : 1.0f;
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = ring.x2[slot * (size_t)D + j];
+        if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
+        s.row[j] = xj;
+    }
     __syncthreads();
     td3_forward(pol, sh.activation, s.row, s.yp, nullptr);
     sac_heads(sac_pop_heads_view(p, key, law), s, s.yp + adc::td3_hidden(sh.pol), adc::ST_SAC_NEXT, b);
@@ -59,12 +69,16 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_target(SacView p, const Ml
         if (tid == 0) s.words[i] = s.yq[qlast];
         __syncthreads();
     }
-    if (tid == 0)
+    if (tid == 0) {
+        const float q = adc::td3_min(s.words[0], s.words[1]);
         p.ybuf[(size_t)blockIdx.y * gridDim.x + b] =
-            adc::sac_y(ring.r[slot], ring.done[slot], adc::td3_min(s.words[0], s.words[1]), alpha, s.words[2], law);
+            NORM && p.r_scale ? adc::sac_y_norm(ring.r[slot], ring.done[slot], q, alpha, s.words[2], law, r_mult, p.r_clip)
+                      : adc::sac_y(ring.r[slot], ring.done[slot], q, alpha, s.words[2], law);
+    }
 }
 
 // forward and backward of both of the member's critics on the element, t = tanh(ring.a) as the action input
+template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_pop_critic_sample(SacView p, const Td3Member *__restrict__ mem)
 {
     extern __shared__ __align__(16) float sac_lds[];
@@ -77,8 +91,10 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_critic_sample(SacView p, c
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
     const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(me.key, b, p.update, p.size);
     float *xin = p.xin + at * (size_t)DA;
+    const size_t nv = NORM ? (size_t)blockIdx.y * p.n_stride : 0;
     for (int j = tid; j < DA; j += kPgBlock) {
-        const float xj = j < D ? ring.x[slot * (size_t)D + j] : adc::mlp_tanh(ring.a[slot * (size_t)A + (j - D)]);
+        float xj = j < D ? ring.x[slot * (size_t)D + j] : adc::mlp_tanh(ring.a[slot * (size_t)A + (j - D)]);
+        if (NORM && p.n_shift && j < D) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
         s.row[j] = xj;
         xin[j] = xj;
     }
@@ -104,6 +120,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_critic_sample(SacView p, c
 
 // the member's actor forward and head, both of its critics on [x | t], the smaller one's backward through to the action inputs,
 // the head's deltas for its 2A outputs, the actor's backward
+template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_pop_actor_sample(SacView p, const MlpLearner *__restrict__ learners, const Td3Member *__restrict__ mem,
                                                                    const SacMember *__restrict__ smem)
 {
@@ -120,7 +137,12 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_pop_actor_sample(SacView p, co
     const size_t slot = p.p_slot ? (size_t)p.p_slot[(size_t)blockIdx.y * gridDim.x + b] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
     const float alpha = smem[blockIdx.y].cell[kSacCellAlpha];
     const float *rx = me.ring.x;
-    for (int j = tid; j < D; j += kPgBlock) s.row[j] = rx[slot * (size_t)D + j];
+    const size_t nv = NORM ? (size_t)blockIdx.y * p.n_stride : 0;
+    for (int j = tid; j < D; j += kPgBlock) {
+        float xj = rx[slot * (size_t)D + j];
+        if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
+        s.row[j] = xj;
+    }
     __syncthreads();
     float *acts = p.acts + at * (size_t)p.na, *deltas = p.deltas + at * (size_t)p.nd;
     td3_forward(pol, sh.activation, s.row, s.yp, acts);

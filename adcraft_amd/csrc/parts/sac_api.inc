@@ -34,6 +34,15 @@ adc_td3_config sac_as_td3(const adc_sac_config &c)
     t.optimiser = c.optimiser; t.max_grad_norm = c.max_grad_norm; t.seed = c.seed;
     return t;
 }
+// the running normalisers' side of a batch kernel's view (all null without adc_engine_sac_norm_init: sac_norm_on is false and the
+// NORM = false instantiations of the batch kernels are launched, the kernels as they were)
+inline bool sac_norm_on(const SacView &p) { return p.n_shift || p.r_scale; }
+void sac_norm_fill(const adc_engine *e, SacView &p)
+{
+    if (!e->sn.live) return;
+    if (e->sn.obs.count) { p.n_shift = e->mp.shift; p.n_scale = e->mp.scale; p.n_stride = e->mp.norm_stride; }
+    if (e->sn.rew.count) { p.r_scale = e->sn.rew.scale; p.r_stride = e->sn_cfg.per_member ? 1 : 0; p.r_clip = e->sn_cfg.rew_clip; }
+}
 SacView sac_view(const adc_engine *e)
 {
     SacView p{};
@@ -47,6 +56,7 @@ SacView sac_view(const adc_engine *e)
     p.key = e->td3_key;
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(e->td3_shape);
+    sac_norm_fill(e, p);
     td3_per_fill(e, p);
     return p;
 }
@@ -62,14 +72,15 @@ int sac_one_update(adc_engine *e, bool stats_wanted, bool last)
     p.na = 2 * nh; p.nd = 2 * no;
     int rc;
     if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
-    hipLaunchKernelGGL(k_sac_target, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
-    hipLaunchKernelGGL(k_sac_critic_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    const bool norm = sac_norm_on(p);
+    hipLaunchKernelGGL(norm ? k_sac_target<true> : k_sac_target<false>, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    hipLaunchKernelGGL(norm ? k_sac_critic_sample<true> : k_sac_critic_sample<false>, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     for (int i = 0; i < 2; ++i) td3_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
     if (e->per_live && (rc = per_leaves_run(e))) return rc;
     if ((rc = td3_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 8, c.critic_lr, e->td3_updates))) return rc;
     p.na = ph; p.nd = po;
-    hipLaunchKernelGGL(k_sac_actor_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    hipLaunchKernelGGL(norm ? k_sac_actor_sample<true> : k_sac_actor_sample<false>, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     td3_wgrad_launch(e, sh.pol, DA, p.na, 0, p.nd, 0, 0, e->td3_P, B);
     HIP_TRY(hipGetLastError());
     // (the pieces' sums of every update: the temperature's step reads lp's)
@@ -212,7 +223,9 @@ ADC_EXPORT int adc_engine_sac_store(adc_engine *e, int64_t *stored)
                                 "one the envs hold (adc_engine_rollout_reset, collect again)");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;
-    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->mp.shift, e->mp.scale, e->mp.D, e->mp.A, e->ro_obs, e->ro_action,
+    // (raw rows under a running observation normaliser: the last day's x' is the raw row an act would read now)
+    hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->sn.obs.count ? nullptr : e->mp.shift,
+                       e->sn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A, e->ro_obs, e->ro_action,
                        e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
                        (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());

@@ -77,18 +77,20 @@ int sp_one_update(adc_engine *e, int index, bool stats_wanted, bool last, bool a
     p.size = (uint32_t)td3_size(e); p.update = (uint32_t)e->td3_updates;
     p.ybuf = e->td3_ybuf; p.xin = e->td3_xin; p.acts = e->td3_acts; p.deltas = e->td3_deltas; p.pieces = e->td3_pieces;
     p.maxw = adc::td3_max_width(sh);
+    sac_norm_fill(e, p);
     td3_per_fill(e, p);
     p.na = 2 * nh; p.nd = 2 * no;
     int rc;
     if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
-    hipLaunchKernelGGL(k_sac_pop_target, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem, e->sp_dmem);
-    hipLaunchKernelGGL(k_sac_pop_critic_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
+    const bool norm = sac_norm_on(p);
+    hipLaunchKernelGGL(norm ? k_sac_pop_target<true> : k_sac_pop_target<false>, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem, e->sp_dmem);
+    hipLaunchKernelGGL(norm ? k_sac_pop_critic_sample<true> : k_sac_pop_critic_sample<false>, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
     for (int i = 0; i < 2; ++i) tp_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
     if (e->per_live && (rc = per_leaves_run(e))) return rc;
     if ((rc = tp_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 8, 3 * index, any_clip))) return rc;
     p.na = ph; p.nd = po;
-    hipLaunchKernelGGL(k_sac_pop_actor_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem, e->sp_dmem);
+    hipLaunchKernelGGL(norm ? k_sac_pop_actor_sample<true> : k_sac_pop_actor_sample<false>, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem, e->sp_dmem);
     tp_wgrad_launch(e, sh.pol, DA, p.na, 0, p.nd, 0, 0, e->td3_P, B);
     HIP_TRY(hipGetLastError());
     // (the pieces' sums of every update: the temperature's step reads lp's)
@@ -264,7 +266,9 @@ ADC_EXPORT int adc_engine_sac_pop_store(adc_engine *e, int64_t *stored_per_membe
                                 "one the envs hold (adc_engine_rollout_reset, collect again)");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;
-    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->mp.shift, e->mp.scale, e->mp.D, e->mp.A,
+    // (raw rows under a running observation normaliser: the last day's x' is the raw row an act would read now)
+    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->sn.obs.count ? nullptr : e->mp.shift,
+                       e->sn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
                        e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
                        (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
     HIP_TRY(hipGetLastError());

@@ -565,7 +565,7 @@ class StepEngine:
         cfg = policy.config(self.num_keywords, deterministic)
         sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
         check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
-        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
+        self._td3_norm = self._sac_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
         self._mlp = policy
         self._members = 0                   # (a population does not survive a re-initialisation)
         self._learners = 0
@@ -1080,7 +1080,7 @@ class StepEngine:
         options as td3_config's.  theta starts as the device's policy; the critics are uploaded with td3_set_critics."""
         cfg = self.td3_config(**options)
         check(self._lib.adc_engine_td3_init(self._h, C.byref(cfg)))
-        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
+        self._td3_norm = self._sac_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
 
     def td3_set_critics(self, critics, action_norm=None, sync_targets=True):
         """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs; action_norm: (shift, scale) [A]
@@ -1211,7 +1211,7 @@ class StepEngine:
         options.setdefault("num_keywords", self.num_keywords)
         cfg = self.sac_config(**options)
         check(self._lib.adc_engine_sac_init(self._h, C.byref(cfg)))
-        self._td3_norm = None
+        self._td3_norm = self._sac_norm = None
 
     def sac_set_critics(self, critics, sync_targets=True):
         """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs [x | tanh(u)]; sync_targets: the
@@ -1321,7 +1321,7 @@ class StepEngine:
         Every member's theta starts as its device policy; the critics are uploaded with td3_pop_set_critics."""
         arr, count = self.td3_pop_configs(configs, self.num_envs, self._td3_pop_members())
         check(self._lib.adc_engine_td3_pop_init(self._h, arr, count))
-        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
+        self._td3_norm = self._sac_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
 
     def td3_pop_set_critics(self, member, critics, action_norm=None, sync_targets=True):
         """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs); action_norm: (shift, scale) [A],
@@ -1446,7 +1446,7 @@ class StepEngine:
         device policy; the critics are uploaded with sac_pop_set_critics."""
         arr, count = self.sac_pop_configs(configs, self.num_envs, self._td3_pop_members(), self.num_keywords)
         check(self._lib.adc_engine_sac_pop_init(self._h, arr, count))
-        self._td3_norm = None
+        self._td3_norm = self._sac_norm = None
 
     def sac_pop_set_critics(self, member, critics, sync_targets=True):
         """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs [x | tanh(u)]); sync_targets: the
@@ -1769,26 +1769,22 @@ class StepEngine:
         self._td3_norm = dict(members=max(getattr(self, "_learners", 0), 1) if cfg.per_member else 1, observations=bool(cfg.observations),
                               rewards=bool(cfg.rewards))
 
-    def _td3_norm_info(self):
-        """what td3_norm_init set up; without one the engine itself says what is missing"""
-        info = getattr(self, "_td3_norm", None)
+    def _ring_norm_info(self, family):
+        """what {family}_norm_init set up; without one the engine itself says what is missing"""
+        info = getattr(self, f"_{family}_norm", None)
         if info is None:
-            check(self._lib.adc_engine_td3_norm_state_get(self._h, 0, *([None] * 9)))
+            check(getattr(self._lib, f"adc_engine_{family}_norm_state_get")(self._h, 0, *([None] * 9)))
             info = dict(members=1, observations=True, rewards=True)
         return info
 
-    def td3_norm_update(self):
-        """merge the recorded days not yet consumed into the running moments and write the new vectors and multiplier where the
-        next act and the next td3_update read them (after the store, before the updates); returns the samples consumed"""
+    def _ring_norm_update(self, family):
         n = C.c_int64(0)
-        check(self._lib.adc_engine_td3_norm_update(self._h, C.byref(n)))
+        check(getattr(self._lib, f"adc_engine_{family}_norm_update")(self._h, C.byref(n)))
         return n.value
 
-    def td3_norm_state(self, member=0, state=None):
-        """one normaliser's state (member 0: the shared one).  get (no state): dict of the living parts - obs_count, obs_mean,
-        obs_M2 [D] float64, shift, scale [D] float32; rew_count, rew_mean, rew_M2 (float64), rew_scale (float32); set: such a dict -
-        with td3_norm_returns, the trainer's state and the ring the run continues bit for bit"""
-        D, info = 5 * self.num_keywords + 2, self._td3_norm_info()
+    def _ring_norm_state(self, family, member, state):
+        """the state of one normaliser of an off-policy family (td3 / sac): the two families share the entry points' signatures"""
+        D, info = 5 * self.num_keywords + 2, self._ring_norm_info(family)
         okeys = (("obs_mean", np.float64), ("obs_M2", np.float64), ("shift", np.float32), ("scale", np.float32))
         if state is None:
             st = {}
@@ -1798,7 +1794,7 @@ class StepEngine:
                 st.update({k: np.zeros(D, t) for k, t in okeys})
                 optr = [st[k].ctypes.data for k, _ in okeys]
             rptr = [C.byref(rn), C.byref(mean), C.byref(m2), C.byref(sc)] if info["rewards"] else [None] * 4
-            check(self._lib.adc_engine_td3_norm_state_get(self._h, int(member), C.byref(n) if info["observations"] else None, *optr, *rptr))
+            check(getattr(self._lib, f"adc_engine_{family}_norm_state_get")(self._h, int(member), C.byref(n) if info["observations"] else None, *optr, *rptr))
             if info["observations"]:
                 st["obs_count"] = n.value
             if info["rewards"]:
@@ -1808,29 +1804,93 @@ class StepEngine:
         if info["observations"]:
             arr = [np.ascontiguousarray(state[k], dtype=t) for k, t in okeys]
             if any(a.shape != (D,) for a in arr):
-                raise ValueError(f"td3_norm_state: obs_mean, obs_M2, shift and scale have {D} entries")
+                raise ValueError(f"{family}_norm_state: obs_mean, obs_M2, shift and scale have {D} entries")
         rew = (int(state["rew_count"]), float(state["rew_mean"]), float(state["rew_M2"]), float(np.float32(state["rew_scale"]))) if info["rewards"] else (0, 0.0, 0.0, 1.0)
-        check(self._lib.adc_engine_td3_norm_state_set(self._h, int(member), int(state["obs_count"]) if info["observations"] else 0,
-                                                      *(None if a is None else a.ctypes.data for a in arr), *rew))
+        check(getattr(self._lib, f"adc_engine_{family}_norm_state_set")(self._h, int(member), int(state["obs_count"]) if info["observations"] else 0,
+                                                                        *(None if a is None else a.ctypes.data for a in arr), *rew))
 
-    def td3_norm_returns(self, values=None):
-        """the envs' running discounted returns [N] float64 (the reward part's carry).  get (no argument) or set"""
+    def _ring_norm_returns(self, family, values):
         if values is None:
             g = np.zeros(self.num_envs, np.float64)
-            check(self._lib.adc_engine_td3_norm_returns_get(self._h, g.ctypes.data))
+            check(getattr(self._lib, f"adc_engine_{family}_norm_returns_get")(self._h, g.ctypes.data))
             return g
         g = np.ascontiguousarray(values, dtype=np.float64)
         if g.shape != (self.num_envs,):
-            raise ValueError("td3_norm_returns: one value per env")
-        check(self._lib.adc_engine_td3_norm_returns_set(self._h, g.ctypes.data))
+            raise ValueError(f"{family}_norm_returns: one value per env")
+        check(getattr(self._lib, f"adc_engine_{family}_norm_returns_set")(self._h, g.ctypes.data))
+
+    def _ring_norm_copy(self, family, src_of_member):
+        src = np.ascontiguousarray(src_of_member, dtype=np.int32)
+        if src.shape != (self._ring_norm_info(family)["members"],):
+            raise ValueError(f"{family}_norm_copy: one source per member")
+        check(getattr(self._lib, f"adc_engine_{family}_norm_copy")(self._h, src.ctypes.data))
+
+    def _td3_norm_info(self):
+        """what td3_norm_init set up; without one the engine itself says what is missing"""
+        return self._ring_norm_info("td3")
+
+    def td3_norm_update(self):
+        """merge the recorded days not yet consumed into the running moments and write the new vectors and multiplier where the
+        next act and the next td3_update read them (after the store, before the updates); returns the samples consumed"""
+        return self._ring_norm_update("td3")
+
+    def td3_norm_state(self, member=0, state=None):
+        """one normaliser's state (member 0: the shared one).  get (no state): dict of the living parts - obs_count, obs_mean,
+        obs_M2 [D] float64, shift, scale [D] float32; rew_count, rew_mean, rew_M2 (float64), rew_scale (float32); set: such a dict -
+        with td3_norm_returns, the trainer's state and the ring the run continues bit for bit"""
+        return self._ring_norm_state("td3", member, state)
+
+    def td3_norm_returns(self, values=None):
+        """the envs' running discounted returns [N] float64 (the reward part's carry).  get (no argument) or set"""
+        return self._ring_norm_returns("td3", values)
 
     def td3_norm_copy(self, src_of_member):
         """every member's normalisers become those of member src_of_member[m] (m itself or -1: kept) in one launch; no
         destination may also be a source (pbt_exploit's convention).  The envs' running returns stay."""
-        src = np.ascontiguousarray(src_of_member, dtype=np.int32)
-        if src.shape != (self._td3_norm_info()["members"],):
-            raise ValueError("td3_norm_copy: one source per member")
-        check(self._lib.adc_engine_td3_norm_copy(self._h, src.ctypes.data))
+        self._ring_norm_copy("td3", src_of_member)
+
+    # ---- the SAC learners' running normalisers (parts/kernel_norm.inc; the law is csrc/adc_sac_norm.h) ----------------------------
+    @classmethod
+    def sac_norm_config(cls, observations=False, rewards=False, per_member=False, obs_min_std=1e-2, obs_count_cap=0, rew_min_std=1e-2, rew_count_cap=0,
+                        rew_clip=10.0):
+        """an adc_sac_norm_config: td3_norm_config's fields and defaults (configuration, not measurements)"""
+        c = _ffi.SACNormConfig()
+        c.struct_size = C.sizeof(_ffi.SACNormConfig)
+        c.observations, c.rewards, c.per_member = 1 if observations else 0, 1 if rewards else 0, 1 if per_member else 0
+        c.obs_min_std, c.obs_count_cap, c.rew_min_std, c.rew_count_cap, c.rew_clip = float(obs_min_std), int(obs_count_cap), float(rew_min_std), int(rew_count_cap), float(rew_clip)
+        msg = C.c_char_p()
+        if _ffi.lib().adc_sac_norm_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad SAC normaliser configuration").decode())
+        return c
+
+    def sac_norm_init(self, **options):
+        """running normalisers for the live SAC trainer (sac_init or sac_pop_init first, the record and the ring still empty): with
+        observations the record and the ring hold RAW observations from here on and every batch is normalised as it is sampled;
+        with rewards the target's reward is multiplied by the reciprocal running standard deviation of the discounted return - the
+        entropy term is not, so target_entropy / alpha then trade against a return of about unit scale.  per_member=True: one per
+        learner of a population.  Options as sac_norm_config's"""
+        cfg = self.sac_norm_config(**options)
+        check(self._lib.adc_engine_sac_norm_init(self._h, C.byref(cfg)))
+        self._sac_norm = dict(members=max(getattr(self, "_learners", 0), 1) if cfg.per_member else 1, observations=bool(cfg.observations),
+                              rewards=bool(cfg.rewards))
+
+    def sac_norm_update(self):
+        """merge the recorded days not yet consumed into the running moments and write the new vectors and multiplier where the
+        next act and the next sac_update read them (after the store, before the updates); returns the samples consumed"""
+        return self._ring_norm_update("sac")
+
+    def sac_norm_state(self, member=0, state=None):
+        """one normaliser's state, get or set: td3_norm_state's dict"""
+        return self._ring_norm_state("sac", member, state)
+
+    def sac_norm_returns(self, values=None):
+        """the envs' running discounted returns [N] float64 (the reward part's carry).  get (no argument) or set"""
+        return self._ring_norm_returns("sac", values)
+
+    def sac_norm_copy(self, src_of_member):
+        """every member's normalisers become those of member src_of_member[m] (m itself or -1: kept) in one launch; no
+        destination may also be a source (pbt_exploit's convention).  The envs' running returns stay."""
+        self._ring_norm_copy("sac", src_of_member)
 
     # ---- prioritised replay for the TD3 / SAC learners (parts/kernel_per.inc; the law is csrc/adc_per.h) -------------------------
     @classmethod
@@ -1911,7 +1971,7 @@ class StepEngine:
 
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
-        self._td3_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
+        self._td3_norm = self._sac_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
         self._rollout_obs = bool(obs) and int(horizon) > 0
 
     def rollout_reset(self):

@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--bid-hi", type=float, default=3.0)
     ap.add_argument("--eval-envs", type=int, default=256)
     ap.add_argument("--print-every", type=int, default=4)
+    ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter per member; the rings hold raw rows")
+    ap.add_argument("--normalize-rewards", action="store_true",
+                    help="per member, the reward divided by the discounted return's running standard deviation (the entropy term is not scaled); what the normalisers gain here has not been measured")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
@@ -71,6 +74,7 @@ def main():
     hi = np.concatenate([[budget], np.full(K, args.bid_hi)]).astype(np.float32)
     policies = [two_headed_policy(K, days, args.bid_lo, args.bid_hi, seed=m) for m in range(M)]
     trainer = sac_trainer.SACPopulationTrainer(eng, policies, configs, lo, hi, horizon=days,
+                                               normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
                                                prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None)
     scheduler = PBTScheduler(trainer, replace_fraction=0.25, tuned=("actor_lr", "alpha"), bounds={"actor_lr": (LR_LO, LR_HI), "alpha": (ALPHA_LO, ALPHA_HI)},
                              factors=(0.8, 1.25), fitness_ema=0.5, every=args.every, seed=11, with_ring=True)

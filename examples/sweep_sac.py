@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--bid-lo", type=float, default=0.01)
     ap.add_argument("--bid-hi", type=float, default=3.0)
     ap.add_argument("--eval-envs", type=int, default=256)
+    ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter per member; the rings hold raw rows")
+    ap.add_argument("--normalize-rewards", action="store_true",
+                    help="per member, the reward divided by the discounted return's running standard deviation (the entropy term is not scaled); what the normalisers gain here has not been measured")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
@@ -72,6 +75,7 @@ def main():
     eng.set_all_params(np.concatenate([member_planes] * M, axis=1))
     eng.reset()
     trainer = sac_trainer.SACPopulationTrainer(eng, policy, configs, lo, hi, horizon=days,
+                                               normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
                                                prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None)
     print(f"{M} SAC learners x {n} envs x {K} keywords on one engine, {days} days and {args.updates} updates per iteration; held-out: {args.eval_envs} envs; "
           f"zero-margin: return {zm_ret.mean():.2f} NCP {zm_ncp:.3f}")

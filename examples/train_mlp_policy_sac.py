@@ -84,6 +84,9 @@ def main():
     ap.add_argument("--every", type=int, default=10, help="evaluate the policy every this many iterations")
     ap.add_argument("--eval-envs", type=int, default=1024)
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="override a float option of the preset (e.g. actor_lr=1e-5)")
+    ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device; the ring holds raw rows")
+    ap.add_argument("--normalize-rewards", action="store_true",
+                    help="the reward divided by the discounted return's running standard deviation (the entropy term is not scaled); what the normalisers gain here has not been measured")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     args = ap.parse_args()
@@ -102,6 +105,7 @@ def main():
     lo = np.concatenate([[1.0], np.full(K, args.bid_lo)]).astype(np.float32)          # (the budget is overridden during training and evaluation)
     hi = np.concatenate([[budget], np.full(K, args.bid_hi)]).astype(np.float32)
     trainer = sac_trainer.SACTrainer(eng, two_headed_policy(K, days, args.bid_lo, args.bid_hi), lo, hi, horizon=days,
+                                     normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
                                      prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None, **config)
     rng = np.random.default_rng(5)
 

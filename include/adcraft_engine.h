@@ -1302,6 +1302,53 @@ int adc_td3_norm_rew_host(const adc_td3_norm_config *cfg, int32_t days, int32_t 
 int adc_td3_y_norm_host(const adc_td3_config *td3, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, float scale, float clip,
                         float *y_b);
 
+/* ---- running observation and reward normalisers for the SAC learners (the law is csrc/adc_sac_norm.h) ---------------------------
+ * The TD3 normalisers' contract on the soft actor-critic trainer (adc_engine_sac_init / _sac_pop_init): everything said above for
+ * adc_engine_td3_norm_* holds with "SAC" for "TD3", and only the differences follow.  While a normaliser with `observations`
+ * lives the record's obs rows and the ring's x / x' are RAW (adc_engine_sac_buffer_fetch / _load, the _sac_pop_ ones and a PBT
+ * round's ring copy carry raw rows); the three SAC batch kernels normalise x and x' as they gather them with the learner's CURRENT
+ * vectors - the live actor of the target and of the actor step, the critics, the target critics and every weight gradient see the
+ * normalised row.  With `rewards` the target is sac_y_norm: r * reward_scale * scale, clipped to [-rew_clip, rew_clip] when
+ * rew_clip > 0, plus gamma * (q - alpha * lp) * (1 - done).  The entropy term is NOT scaled: under a normalised reward
+ * target_entropy and alpha trade entropy against a return of about unit standard deviation, not against the env's money scale.
+ * The return scan's discount is adc_sac_config.gamma - under a population the env's member's, as in force when the update runs.
+ * Without adc_engine_sac_norm_init every call launches the kernels it launched and computes the bits it computed.
+ * adc_engine_sac_norm_init is refused, the engine staying usable: without a live adc_engine_sac_init / _sac_pop_init trainer
+ * (ADC_ESTATE; a TD3 trainer is not one); per_member without a SAC population (ADC_EINVAL); `observations` on a policy initialised
+ * without normalisation (ADC_EINVAL); a day recorded since adc_engine_rollout_reset or a transition in the ring (ADC_ESTATE).
+ * The normaliser ends with its trainer - adc_engine_mlp_init, adc_engine_rollout_enable, a new adc_engine_sac_init / _sac_pop_init
+ * (or _td3_init / _td3_pop_init), and for a population's trainer adc_engine_mlp_learners / adc_engine_mlp_population - and the record
+ * is back to network inputs.  adc_engine_obs_norm_init, _rew_norm_init and _td3_norm_init keep refusing a SAC trainer; the
+ * adc_engine_td3_norm_* calls do not see a SAC normaliser, and these do not see a TD3 one.  Prioritised replay works with it: the
+ * priorities come from |d| of the normalised inputs and the normalised target, and the tree is not touched by the normaliser.
+ * adc_engine_sac_pop_copy leaves the normalisers alone; adc_engine_sac_norm_copy (adc_engine_pbt_exploit's convention, ONE launch
+ * whatever M is) carries the donors' moments, vectors and multiplier after a PBT round.
+ * adc_sac_y_norm_host: y_b [count] = sac_y_norm of r_b, done_b, q_b (the smaller target critic's value) and lp_b (log pi of the
+ * next action) under sac's gamma and reward_scale, the temperature `alpha`, the multiplier `scale` and `clip`; with scale 1 and
+ * clip 0 these are the plain SAC target's bits.  The moments' host twins are adc_td3_norm_obs_host / adc_td3_norm_rew_host. */
+typedef struct adc_sac_norm_config {
+    uint32_t struct_size;          /* sizeof(adc_sac_norm_config) */
+    int32_t observations, rewards; /* which parts live; at least one nonzero */
+    int32_t per_member;            /* needs adc_engine_sac_pop_*: one normaliser per learner */
+    double obs_min_std;            /* > 0, finite: the floor of a column's standard deviation */
+    int64_t obs_count_cap;         /* > 0: the running count never exceeds it (M2 scaled down with it); 0: off */
+    double rew_min_std;            /* > 0, finite: the floor of the discounted return's standard deviation */
+    int64_t rew_count_cap;
+    float rew_clip;                /* > 0: the normalised reward is clipped to [-rew_clip, rew_clip]; 0: off */
+} adc_sac_norm_config;
+int adc_sac_norm_config_check(const adc_sac_norm_config *cfg, const char **message);
+int adc_engine_sac_norm_init(adc_engine *e, const adc_sac_norm_config *cfg);
+int adc_engine_sac_norm_update(adc_engine *e, int64_t *samples);
+int adc_engine_sac_norm_state_get(adc_engine *e, int32_t member, int64_t *obs_count, double *obs_mean_d, double *obs_m2_d, float *shift_d, float *scale_d,
+                                  int64_t *rew_count, double *rew_mean, double *rew_m2, float *rew_scale);
+int adc_engine_sac_norm_state_set(adc_engine *e, int32_t member, int64_t obs_count, const double *obs_mean_d, const double *obs_m2_d, const float *shift_d,
+                                  const float *scale_d, int64_t rew_count, double rew_mean, double rew_m2, float rew_scale);
+int adc_engine_sac_norm_returns_get(adc_engine *e, double *g_n);
+int adc_engine_sac_norm_returns_set(adc_engine *e, const double *g_n);
+int adc_engine_sac_norm_copy(adc_engine *e, const int32_t *src_of_member_m);
+int adc_sac_y_norm_host(const adc_sac_config *sac, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, const float *lp_b, float alpha,
+                        float scale, float clip, float *y_b);
+
 /* ---- prioritised replay for the TD3 and SAC learners (the law is csrc/adc_per.h) --------------------------------------------------
  * An add-on of the live adc_engine_td3_init / _sac_init / _td3_pop_init / _sac_pop_init trainer: the batch of an update is drawn in
  * proportion to the slots' priorities from a radix-64 sum tree that lives on the device next to the ring (one tree, one `top` and

@@ -69,9 +69,12 @@
 //   parts/pg_kl_api.inc           the entry points of the KL penalty / value-clip add-on and what pg_api.inc calls of it.
 //   parts/pg_shuffle_api.inc      the entry points of the shuffled minibatches / target-KL stop add-on, the updates under it.
 //   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
-//   parts/td3_api.inc             the entry points of off-policy (TD3) training.
-//   parts/td3_pop_api.inc         the entry points of TD3 learner populations.
-//   parts/sac_pop_api.inc         the entry points of SAC learner populations, over td3_pop_api.inc's helpers.
+//   parts/offpolicy_core.inc      what the four off-policy front ends share on the host: the ring, the critic upload, the state
+//                                 vectors, the allocation, an update's launch helpers, the populations' update driver.
+//   parts/td3_api.inc             the entry points of off-policy (TD3) training, over offpolicy_core.inc.
+//   parts/sac_api.inc             the entry points of soft actor-critic training, over offpolicy_core.inc.
+//   parts/td3_pop_api.inc         the entry points of TD3 learner populations, over offpolicy_core.inc.
+//   parts/sac_pop_api.inc         the entry points of SAC learner populations, over offpolicy_core.inc.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over a PG, TD3 or SAC population.
 //   parts/per_api.inc             the entry points of prioritised replay over a TD3 or SAC trainer, and what the trainers' updates call of it.
 //   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners', the SAC learners' - over shared helpers.
@@ -142,6 +145,7 @@ using namespace adck;
 #include "parts/pg_kl_api.inc"
 #include "parts/pg_shuffle_api.inc"
 #include "parts/pg_api.inc"
+#include "parts/offpolicy_core.inc"
 #include "parts/td3_api.inc"
 #include "parts/sac_api.inc"
 #include "parts/td3_pop_api.inc"

@@ -1,7 +1,8 @@
 // sac_api.inc - the extern "C" entry points of soft actor-critic training (include/adcraft_engine.h; the kernels are
 // parts/kernel_sac.inc, the law csrc/adc_sac.h).  The learner lives in the off-policy trainer's fields (host_api.inc: the ring,
-// the critics, their targets, the scratch, the flat vectors and moments), so the helpers of td3_api.inc serve it as they are;
-// SAC and TD3 exclude each other.  Everything here runs on the engine's own stream behind ENGINE_GUARD.
+// the critics, their targets, the scratch, the flat vectors and moments) and shares parts/offpolicy_core.inc with TD3; SAC and TD3
+// exclude each other.  Here are SAC's own refusals, its view, its update, the temperature cell and its statistics.  Everything
+// here runs on the engine's own stream behind ENGINE_GUARD.
 // (part of the single translation unit adc_engine.hip)
 namespace {
 int sac_ready(const adc_engine *e)
@@ -98,6 +99,34 @@ int sac_one_update(adc_engine *e, bool stats_wanted, bool last)
     e->td3_updates += 1;
     return ADC_OK;
 }
+// one learner's statistics from its sums and its temperature cell
+void sac_stats_fill(const adc_engine *e, const double *sums, const float *cell, adc_sac_stats *stats)
+{
+    const double n = (double)e->td3_cfg.batch_size;
+    off_stats_fill(e, sums, stats);
+    stats->actor_loss = sums[adc::kSacPiLoss] / n;
+    stats->logp_mean = sums[adc::kSacLp] / n;
+    stats->alpha = cell[kSacCellAlpha]; stats->log_alpha = cell[kSacCellLogAlpha];
+    stats->critic_grad_norm = std::sqrt(sums[8]);
+    stats->actor_grad_norm = std::sqrt(sums[9]);
+}
+// (flat[kTd3ThetaT] is null: there is no target actor)
+int sac_state_set_check(const float *const flat[4], const float *const mom[4], const float *log_alpha3, int64_t updates)
+{
+    for (int w = 0; w < 4; ++w)
+        if ((!flat[w] && w != kTd3ThetaT) || !mom[w]) return fail(ADC_EINVAL, "a state vector is NULL");
+    if (!log_alpha3) return fail(ADC_EINVAL, "a state vector is NULL");
+    if (updates < 0 || updates >= 0x7FFFFFFFll) return fail(ADC_EINVAL, "updates: 0 to 2^31 - 2");
+    if (!std::isfinite(log_alpha3[0])) return fail(ADC_EINVAL, "log_alpha must be finite");
+    return ADC_OK;
+}
+// a temperature cell {log_alpha, m, v, alpha} from its three state entries; `cell4` is the host's until the stream has been waited for
+int sac_cell_upload(adc_engine *e, float *dcell, const float *log_alpha3, float *cell4)
+{
+    cell4[0] = log_alpha3[0]; cell4[1] = log_alpha3[1]; cell4[2] = log_alpha3[2]; cell4[3] = adc::mlp_exp(log_alpha3[0]);
+    HIP_TRY(hipMemcpyAsync(dcell, cell4, 4 * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    return ADC_OK;
+}
 }  // namespace
 
 ADC_EXPORT int adc_engine_sac_init(adc_engine *e, const adc_sac_config *cfg)
@@ -115,65 +144,33 @@ ADC_EXPORT int adc_engine_sac_init(adc_engine *e, const adc_sac_config *cfg)
     const adc::Td3Shape sh = adc::sac_shape_of(e->mlp_cfg, e->v.K, *cfg);
     if (sac_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for soft actor-critic training (LDS)");
     ENGINE_GUARD(e);
-    const int A = sh.A, D = sh.D, B = cfg->batch_size;
-    const size_t C = (size_t)cfg->capacity, P = (size_t)adc::td3_params(sh.pol), Qc = (size_t)adc::td3_params(sh.q), Q2 = 2 * Qc, Qmax = std::max(P, Q2);
-    const size_t na = (size_t)std::max(std::max(2 * adc::td3_hidden(sh.q), adc::td3_hidden(sh.pol)), 1);
-    const size_t nd = (size_t)std::max(2 * adc::td3_outs(sh.q), adc::td3_outs(sh.pol));
     // (the new state is allocated before the old one goes: a failure leaves the engine as it was)
     std::vector<void *> fresh;
-    int rc = ADC_OK;
     MlpNet nets[4] = {};                    // critic 1, critic 2, target critic 1, target critic 2
-    for (int n = 0; n < 4 && !rc; ++n) {
-        nets[n].layers = sh.q.layers;
-        for (int l = 0; l < sh.q.layers && !rc; ++l) {
-            float *w = nullptr, *b = nullptr;
-            const int n_in = adc::td3_n_in(sh.q, l), n_out = sh.q.n_out[l];
-            if ((rc = mlp_alloc(e, fresh, &w, adc::mlp_weight_count(n_in, n_out))) || (rc = mlp_alloc(e, fresh, &b, (size_t)n_out))) break;
-            nets[n].W[l] = w; nets[n].b[l] = b; nets[n].n_in[l] = n_in; nets[n].n_out[l] = n_out;
-        }
-    }
-    float *flat[4] = {}, *mom[4] = {}, *grad = nullptr, *ybuf = nullptr, *xin = nullptr, *acts = nullptr, *deltas = nullptr, *pieces = nullptr, *cell = nullptr;
-    Td3Ring ring{};
-    int32_t *idx = nullptr;
-    double *part = nullptr, *sums = nullptr, *gpart = nullptr;
-    for (int w = 0; w < 4 && !rc; ++w) {
-        if (w != kTd3ThetaT) rc = mlp_alloc(e, fresh, &flat[w], (w & 1) ? Q2 : P);
-        if (!rc) rc = mlp_alloc(e, fresh, &mom[w], w < 2 ? P : Q2);
-    }
-    if (rc || (rc = mlp_alloc(e, fresh, &grad, Qmax)) || (rc = mlp_alloc(e, fresh, &ybuf, (size_t)B)) ||
-        (rc = mlp_alloc(e, fresh, &xin, (size_t)B * (size_t)(D + A))) || (rc = mlp_alloc(e, fresh, &acts, (size_t)B * na)) ||
-        (rc = mlp_alloc(e, fresh, &deltas, (size_t)B * nd)) || (rc = mlp_alloc(e, fresh, &pieces, (size_t)B * (size_t)adc::kTd3Pieces)) ||
-        (rc = mlp_alloc(e, fresh, &idx, (size_t)B)) || (rc = mlp_alloc(e, fresh, &cell, (size_t)4)) ||
-        (rc = mlp_alloc(e, fresh, &part, (size_t)pg_chunks((long long)std::max((size_t)B, Qmax)) * 8u + 8u)) || (rc = mlp_alloc(e, fresh, &sums, (size_t)16)) ||
-        (rc = mlp_alloc(e, fresh, &gpart, (size_t)pg_chunks(B) * Qmax)) || (rc = mlp_alloc(e, fresh, &ring.x, C * (size_t)D)) ||
-        (rc = mlp_alloc(e, fresh, &ring.a, C * (size_t)A)) || (rc = mlp_alloc(e, fresh, &ring.r, C)) || (rc = mlp_alloc(e, fresh, &ring.done, C)) ||
-        (rc = mlp_alloc(e, fresh, &ring.x2, C * (size_t)D))) {
+    OffBufs o;
+    float *cell = nullptr;
+    int rc;
+    if ((rc = off_solo_nets(e, fresh, sh, nets, 4)) || (rc = mlp_alloc(e, fresh, &cell, (size_t)4)) ||
+        (rc = off_alloc(e, fresh, sh, cfg->batch_size, (size_t)cfg->capacity, 1, false, o))) {
         mlp_free(e, fresh);
         return rc;
     }
     td3_drop(e);
     e->td3_allocs.swap(fresh);
-    e->sac_cfg = *cfg; e->td3_cfg = sac_as_td3(*cfg); e->td3_shape = sh; e->sac_law = adc::sac_law_of(e->mlp_cfg, *cfg);
+    off_install(e, o, sh);
+    e->sac_cfg = *cfg; e->td3_cfg = sac_as_td3(*cfg); e->sac_law = adc::sac_law_of(e->mlp_cfg, *cfg);
     e->td3_key = adc::td3_key(cfg->seed ? cfg->seed : e->cfg.seed);
-    e->td3_P = (int)P; e->td3_Qc = (int)Qc;
     e->td3_q[0] = nets[0]; e->td3_q[1] = nets[1]; e->td3_q_t[0] = nets[2]; e->td3_q_t[1] = nets[3]; e->td3_pol_t = MlpNet{};
     e->td3_lay[kTd3Theta] = td3_layout(&e->mp.pol, 1);
-    e->td3_lay[kTd3Psi] = td3_layout(e->td3_q, 2);
-    e->td3_lay[kTd3ThetaT] = PgLayout{};
-    e->td3_lay[kTd3PsiT] = td3_layout(e->td3_q_t, 2);
-    for (int w = 0; w < 4; ++w) { e->td3_flat[w] = flat[w]; e->td3_mom[w] = mom[w]; }
-    e->td3_a_shift = e->td3_a_scale = nullptr; e->td3_ring = ring;
-    e->td3_grad = grad; e->td3_ybuf = ybuf; e->td3_xin = xin; e->td3_acts = acts; e->td3_deltas = deltas; e->td3_pieces = pieces; e->td3_idx = idx;
-    e->td3_part = part; e->td3_sums = sums; e->td3_gpart = gpart; e->sac_cell = cell;
-    e->td3_stored_t = e->ro_t;              // (days recorded before this call are not the trainer's)
+    off_layouts(e, e->td3_q, e->td3_q_t, e->td3_pol_t);
+    e->td3_a_shift = e->td3_a_scale = nullptr; e->td3_ring = o.ring;
+    e->sac_cell = cell;
     // theta starts as the device's policy; the target critics as copies (zeros until the critics are uploaded and synchronised)
     const float la = adc::sac_log_alpha_init(cfg->init_alpha);
     const float cell0[4] = {la, 0.0f, 0.0f, adc::mlp_exp(la)};
     HIP_TRY(hipMemcpyAsync(cell, cell0, sizeof(cell0), hipMemcpyHostToDevice, e->stream));
     td3_params_copy(e, kTd3Theta, 1);
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3PsiT], e->td3_flat[kTd3Psi], Q2 * 4, hipMemcpyDeviceToDevice, e->stream));
-    td3_params_copy(e, kTd3PsiT, 0);
-    HIP_TRY(hipGetLastError());
+    if ((rc = off_sync_run(e, kOffSolo, 1, 1))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->have_sac = true;
     return ADC_OK;
@@ -183,21 +180,7 @@ ADC_EXPORT int adc_engine_sac_set_critic_layer(adc_engine *e, int32_t critic, in
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
-    if (critic != 0 && critic != 1) return fail(ADC_EINVAL, "critic: 0 or 1");
-    const adc::Td3Net &q = e->td3_shape.q;
-    if (layer < 0 || layer >= q.layers) return fail(ADC_EINVAL, "no such critic layer");
-    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
-    ENGINE_GUARD(e);
-    size_t off = (size_t)critic * (size_t)e->td3_Qc;
-    for (int l = 0; l < layer; ++l) off += (size_t)(adc::td3_n_in(q, l) + 1) * (size_t)q.n_out[l];
-    const size_t nw = (size_t)adc::td3_n_in(q, layer) * (size_t)q.n_out[layer];
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off, weights_in_out, nw * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off + nw, bias_out, (size_t)q.n_out[layer] * 4, hipMemcpyHostToDevice, e->stream));
-    td3_params_copy(e, kTd3Psi, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_critic_set[critic][layer] = true;
-    return ADC_OK;
+    return off_set_critic_layer(e, kOffSolo, critic, layer, weights_in_out, bias_out);
 }
 
 ADC_EXPORT int adc_engine_sac_sync_targets(adc_engine *e)
@@ -205,9 +188,7 @@ ADC_EXPORT int adc_engine_sac_sync_targets(adc_engine *e)
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
     ENGINE_GUARD(e);
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3PsiT], e->td3_flat[kTd3Psi], (size_t)e->td3_Qc * 8, hipMemcpyDeviceToDevice, e->stream));
-    td3_params_copy(e, kTd3PsiT, 0);
-    HIP_TRY(hipGetLastError());
+    if (int rc = off_sync_run(e, kOffSolo, 1, 1)) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ADC_OK;
 }
@@ -216,51 +197,29 @@ ADC_EXPORT int adc_engine_sac_store(adc_engine *e, int64_t *stored)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = sac_ready(e)) || (rc = sac_state_check(e))) return rc;
-    if (e->ro_t <= e->td3_stored_t) return fail(ADC_ESTATE, "no unstored day in the record (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)");
-    if (e->td3_gap || e->env_moves != e->ro_moves)
-        return fail(ADC_ESTATE, "the envs were stepped or reset outside the record since an unstored recorded day: its next observation is not the "
-                                "one the envs hold (adc_engine_rollout_reset, collect again)");
+    if ((rc = sac_ready(e)) || (rc = sac_state_check(e)) || (rc = off_store_check(e))) return rc;
     ENGINE_GUARD(e);
-    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;
-    // (raw rows under a running observation normaliser: the last day's x' is the raw row an act would read now)
+    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;        // (every env is the one learner's)
+    // (raw rows under a running observation normaliser - SAC's set, e->sn: the last day's x' is the raw row an act would read now)
     hipLaunchKernelGGL(k_td3_store, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->sn.obs.count ? nullptr : e->mp.shift,
                        e->sn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A, e->ro_obs, e->ro_action,
                        e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,
                        (unsigned long long)e->td3_cfg.capacity);
-    HIP_TRY(hipGetLastError());
-    if (e->per_live && (rc = per_store_run(e, e->td3_written, count))) return rc;
-    e->td3_written += count;
-    e->td3_stored_t = e->ro_t;
-    if (stored) *stored = count;
-    return ADC_OK;
+    return off_store_done(e, count, stored);
 }
 
 ADC_EXPORT int adc_engine_sac_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
-    if (size) *size = td3_size(e);
-    if (written) *written = e->td3_written;
-    if (capacity) *capacity = e->td3_cfg.capacity;
-    return ADC_OK;
+    return off_buffer_info(e, size, written, capacity, nullptr);
 }
 
 ADC_EXPORT int adc_engine_sac_buffer_fetch(adc_engine *e, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done, float *x2)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
-    if (slot < 0 || count < 1 || slot > td3_size(e) - count) return fail(ADC_EINVAL, "the slot range is not inside [0, size)");
-    ENGINE_GUARD(e);
-    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-    const Td3Ring &g = e->td3_ring;
-    if (x) HIP_TRY(hipMemcpyAsync(x, g.x + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
-    if (a) HIP_TRY(hipMemcpyAsync(a, g.a + s * A, n * A * 4, hipMemcpyDeviceToHost, e->stream));
-    if (r) HIP_TRY(hipMemcpyAsync(r, g.r + s, n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (done) HIP_TRY(hipMemcpyAsync(done, g.done + s, n, hipMemcpyDeviceToHost, e->stream));
-    if (x2) HIP_TRY(hipMemcpyAsync(x2, g.x2 + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return off_ring_fetch(e, kOffSolo, slot, count, x, a, r, done, x2);
 }
 
 ADC_EXPORT int adc_engine_sac_buffer_load(adc_engine *e, int64_t slot, int64_t count, const float *x, const float *a, const float *r, const uint8_t *done,
@@ -268,24 +227,7 @@ ADC_EXPORT int adc_engine_sac_buffer_load(adc_engine *e, int64_t slot, int64_t c
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
-    if (!x || !a || !r || !done || !x2) return fail(ADC_EINVAL, "x, a, r, done or x2 is NULL");
-    if (slot < 0 || count < 1 || slot > (int64_t)e->td3_cfg.capacity - count) return fail(ADC_EINVAL, "the slot range is not inside [0, capacity)");
-    if (written < slot + count) return fail(ADC_EINVAL, "written: at least slot + count");
-    ENGINE_GUARD(e);
-    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-    const Td3Ring &g = e->td3_ring;
-    HIP_TRY(hipMemcpyAsync(g.x + s * D, x, n * D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.a + s * A, a, n * A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.r + s, r, n * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.done + s, done, n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_written = written;
-    if (e->per_live) {
-        if (int rc = per_loaded_run(e, 0, slot, count)) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return ADC_OK;
+    return off_ring_load(e, kOffSolo, slot, count, x, a, r, done, x2, written);
 }
 
 ADC_EXPORT int adc_engine_sac_batch_size(adc_engine *e, int32_t *batch_size)
@@ -300,30 +242,17 @@ ADC_EXPORT int adc_engine_sac_batch_indices(adc_engine *e, int64_t update, int32
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
-    if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
-    if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
-    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_store)");
-    if (e->per_live) return fail(ADC_ESTATE, "prioritised replay is alive on this engine: the batch is adc_engine_replay_prio_batch's, not the uniform law's");
-    ENGINE_GUARD(e);
-    const int B = e->td3_cfg.batch_size;
-    hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->td3_key, (uint32_t)update, (uint32_t)td3_size(e), B, e->td3_idx);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(idx_b, e->td3_idx, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return off_batch_indices(e, e->td3_key, update, idx_b, "the replay buffer is empty (adc_engine_sac_store)");
 }
 
 ADC_EXPORT int adc_engine_sac_update(adc_engine *e, int32_t updates, adc_sac_stats *stats)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = sac_ready(e)) || (rc = sac_state_check(e))) return rc;
-    if (updates < 1 || updates > 65536) return fail(ADC_EINVAL, "updates: 1 to 65536");
-    for (int i = 0; i < 2; ++i)
-        for (int l = 0; l < e->td3_shape.q.layers; ++l)
-            if (!e->td3_critic_set[i][l]) return fail(ADC_ESTATE, "a critic layer has not been uploaded (adc_engine_sac_set_critic_layer)");
-    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_store)");
-    if (e->td3_updates + updates >= 0x7FFFFFFFll) return fail(ADC_ESTATE, "the update counter is exhausted");
+    if ((rc = sac_ready(e)) || (rc = sac_state_check(e)) ||
+        (rc = off_update_check(e, updates, false, "a critic layer has not been uploaded (adc_engine_sac_set_critic_layer)",
+                               "the replay buffer is empty (adc_engine_sac_store)", 0x7FFFFFFFll)))
+        return rc;
     ENGINE_GUARD(e);
     HIP_TRY(hipMemsetAsync(e->td3_sums, 0, 16 * sizeof(double), e->stream));
     // (without a norm clip nothing below waits: every step's Adam constants travel with its launch)
@@ -336,18 +265,7 @@ ADC_EXPORT int adc_engine_sac_update(adc_engine *e, int32_t updates, adc_sac_sta
         HIP_TRY(hipMemcpyAsync(cell, e->sac_cell, sizeof(cell), hipMemcpyDeviceToHost, e->stream));
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (stats) {
-        const double n = (double)e->td3_cfg.batch_size;
-        const double l1 = sums[adc::kTd3Loss1] / n, l2 = sums[adc::kTd3Loss2] / n;
-        stats->updates = e->td3_updates; stats->buffer_size = td3_size(e); stats->samples = e->td3_cfg.batch_size;
-        stats->critic_loss = l1 + l2;
-        stats->q1_mean = sums[adc::kTd3Q1] / n; stats->q2_mean = sums[adc::kTd3Q2] / n; stats->y_mean = sums[adc::kTd3Y] / n;
-        stats->actor_loss = sums[adc::kSacPiLoss] / n;
-        stats->logp_mean = sums[adc::kSacLp] / n;
-        stats->alpha = cell[kSacCellAlpha]; stats->log_alpha = cell[kSacCellLogAlpha];
-        stats->critic_grad_norm = std::sqrt(sums[8]);
-        stats->actor_grad_norm = std::sqrt(sums[9]);
-    }
+    if (stats) sac_stats_fill(e, sums, cell, stats);
     return ADC_OK;
 }
 
@@ -355,9 +273,7 @@ ADC_EXPORT int adc_engine_sac_param_counts(adc_engine *e, int64_t *actor_p, int6
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
-    if (actor_p) *actor_p = e->td3_P;
-    if (critics_2qc) *critics_2qc = 2 * (int64_t)e->td3_Qc;
-    return ADC_OK;
+    return off_param_counts(e, actor_p, critics_2qc);
 }
 
 ADC_EXPORT int adc_engine_sac_state_get(adc_engine *e, float *theta_p, float *psi_q, float *psi_target_q, float *m_theta_p, float *v_theta_p, float *m_psi_q,
@@ -366,12 +282,8 @@ ADC_EXPORT int adc_engine_sac_state_get(adc_engine *e, float *theta_p, float *ps
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sac_ready(e)) return rc;
     ENGINE_GUARD(e);
-    const size_t pb = (size_t)e->td3_P * 4, qb = (size_t)e->td3_Qc * 8;
     float *flat[4] = {theta_p, psi_q, nullptr, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
-    for (int w = 0; w < 4; ++w) {
-        if (flat[w]) HIP_TRY(hipMemcpyAsync(flat[w], e->td3_flat[w], (w & 1) ? qb : pb, hipMemcpyDeviceToHost, e->stream));
-        if (mom[w]) HIP_TRY(hipMemcpyAsync(mom[w], e->td3_mom[w], w < 2 ? pb : qb, hipMemcpyDeviceToHost, e->stream));
-    }
+    if (int rc = off_state_get(e, kOffSolo, flat, mom)) return rc;
     if (log_alpha3) HIP_TRY(hipMemcpyAsync(log_alpha3, e->sac_cell, 3 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (updates) *updates = e->td3_updates;
@@ -382,25 +294,11 @@ ADC_EXPORT int adc_engine_sac_state_set(adc_engine *e, const float *theta_p, con
                                         const float *v_theta_p, const float *m_psi_q, const float *v_psi_q, const float *log_alpha3, int64_t updates)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = sac_ready(e)) return rc;
-    if (!theta_p || !psi_q || !psi_target_q || !m_theta_p || !v_theta_p || !m_psi_q || !v_psi_q || !log_alpha3) return fail(ADC_EINVAL, "a state vector is NULL");
-    if (updates < 0 || updates >= 0x7FFFFFFFll) return fail(ADC_EINVAL, "updates: 0 to 2^31 - 2");
-    if (!std::isfinite(log_alpha3[0])) return fail(ADC_EINVAL, "log_alpha must be finite");
-    ENGINE_GUARD(e);
-    const size_t pb = (size_t)e->td3_P * 4, qb = (size_t)e->td3_Qc * 8;
     const float *flat[4] = {theta_p, psi_q, nullptr, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
-    for (int w = 0; w < 4; ++w) {
-        HIP_TRY(hipMemcpyAsync(e->td3_mom[w], mom[w], w < 2 ? pb : qb, hipMemcpyHostToDevice, e->stream));
-        if (!flat[w]) continue;
-        HIP_TRY(hipMemcpyAsync(e->td3_flat[w], flat[w], (w & 1) ? qb : pb, hipMemcpyHostToDevice, e->stream));
-        td3_params_copy(e, w, 0);           // (the device's policy layers, the critics and the targets follow the flat vectors)
-    }
-    const float cell[4] = {log_alpha3[0], log_alpha3[1], log_alpha3[2], adc::mlp_exp(log_alpha3[0])};
-    HIP_TRY(hipMemcpyAsync(e->sac_cell, cell, sizeof(cell), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_updates = updates;
-    for (int i = 0; i < 2; ++i)
-        for (int l = 0; l < e->td3_shape.q.layers; ++l) e->td3_critic_set[i][l] = true;
-    return ADC_OK;
+    int rc;
+    if ((rc = sac_ready(e)) || (rc = sac_state_set_check(flat, mom, log_alpha3, updates))) return rc;
+    ENGINE_GUARD(e);
+    float cell[4];
+    if ((rc = sac_cell_upload(e, e->sac_cell, log_alpha3, cell))) return rc;
+    return off_state_set(e, kOffSolo, flat, mom, updates);     // (waits: `cell` is the host's until then)
 }

@@ -1,10 +1,11 @@
 // sac_pop_api.inc - the extern "C" entry points of SAC learner populations: M soft actor-critic learners in lock-step on one engine,
 // every launch over all members (include/adcraft_engine.h; the kernels are parts/kernel_sac_pop.inc, the k_td3_pop_* of
 // parts/kernel_td3_pop.inc and the k_pg_pop_* of parts/kernel_pg.inc; the law is csrc/adc_sac.h).  The population lives in the TD3
-// population's engine fields and uses td3_pop_api.inc's helpers as they are (tp_params_copy, tp_csum_launch, tp_wgrad_launch,
-// tp_step_run): td3_flat / td3_mom are [M][P] and [M][2 Qc] (no target actor), the scratch [M][B][...], td3_sums [M][16], tp_cfg
-// what those helpers read of a member's configuration (sac_as_td3), the step table three rows per update (critic, actor,
-// temperature).  What TD3 lacks - the law's SAC constants, the target entropy, the temperature cell - is in SacMember[M].
+// population's engine fields and shares parts/offpolicy_core.inc with the other front ends (the ring, the critic upload, the state
+// vectors, the allocation, tp_params_copy, tp_csum_launch, tp_wgrad_launch, tp_step_run, the update driver): td3_flat / td3_mom
+// are [M][P] and [M][2 Qc] (no target actor), the scratch [M][B][...], td3_sums [M][16], tp_cfg what those helpers read of a
+// member's configuration (sac_as_td3), the step table three rows per update (critic, actor, temperature).  What TD3 lacks - the
+// law's SAC constants, the target entropy, the temperature cell - is in SacMember[M].
 // (part of the single translation unit adc_engine.hip)
 namespace {
 int sp_ready(const adc_engine *e)
@@ -37,15 +38,6 @@ int sp_members_upload(adc_engine *e)
 {
     HIP_TRY(hipMemcpyAsync(e->tp_dmem, e->tp_mem.data(), e->tp_mem.size() * sizeof(Td3Member), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->sp_dmem, e->sp_mem.data(), e->sp_mem.size() * sizeof(SacMember), hipMemcpyHostToDevice, e->stream));
-    return ADC_OK;
-}
-// the target critics of members member0 .. member0 + count - 1 become copies of their critics
-int sp_sync_run(adc_engine *e, int member0, int count)
-{
-    const size_t Q2 = 2 * (size_t)e->td3_Qc, at = (size_t)member0 * Q2;
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3PsiT] + at, e->td3_flat[kTd3Psi] + at, (size_t)count * Q2 * 4, hipMemcpyDeviceToDevice, e->stream));
-    tp_params_copy(e, kTd3PsiT, member0, count, 0);
-    HIP_TRY(hipGetLastError());
     return ADC_OK;
 }
 // rows 3 index .. 3 index + 2 of the step table: every member's constants of update `update`'s critic, actor and temperature steps
@@ -127,95 +119,53 @@ ADC_EXPORT int adc_engine_sac_pop_init(adc_engine *e, const adc_sac_config *cfgs
     const adc::Td3Shape sh = adc::sac_shape_of(e->mlp_cfg, e->v.K, cfgs[0]);
     if (sac_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for soft actor-critic training (LDS)");
     ENGINE_GUARD(e);
-    const int A = sh.A, D = sh.D, B = cfgs[0].batch_size;
-    const size_t Ms = (size_t)M, C = (size_t)cfgs[0].capacity, P = (size_t)adc::td3_params(sh.pol), Qc = (size_t)adc::td3_params(sh.q), Q2 = 2 * Qc,
-                 Qmax = std::max(P, Q2);
-    const size_t na = (size_t)std::max(std::max(2 * adc::td3_hidden(sh.q), adc::td3_hidden(sh.pol)), 1);
-    const size_t nd = (size_t)std::max(2 * adc::td3_outs(sh.q), adc::td3_outs(sh.pol));
-    const size_t part_stride = (size_t)pg_chunks((long long)std::max((size_t)B, Qmax)) * 8u + 8u;
-    // a member's block of stores: critic 1, critic 2, target critic 1, target critic 2, every piece on a 16-byte boundary
-    size_t offW[4][adc::kMlpMaxLayers] = {}, offb[4][adc::kMlpMaxLayers] = {}, stride = 0;
-    for (int n = 0; n < 4; ++n)
-        for (int l = 0; l < sh.q.layers; ++l) {
-            offW[n][l] = stride; stride += adc::mlp_weight_count(adc::td3_n_in(sh.q, l), sh.q.n_out[l]);
-            offb[n][l] = stride; stride += ((size_t)sh.q.n_out[l] + 3u) & ~(size_t)3u;
-        }
+    const size_t Ms = (size_t)M, C = (size_t)cfgs[0].capacity;
+    const OffBlock k = off_block_layout(sh, 4);
     // (the new state is allocated before the old one goes: a failure leaves the engine as it was)
     std::vector<void *> fresh;
-    int rc = ADC_OK;
-    float *block = nullptr, *flat[4] = {}, *mom[4] = {}, *grad = nullptr, *ybuf = nullptr, *xin = nullptr, *acts = nullptr, *deltas = nullptr, *pieces = nullptr,
-          *rx = nullptr, *ra = nullptr, *rr = nullptr, *rx2 = nullptr, *cells = nullptr;
-    uint8_t *rdone = nullptr;
-    int32_t *idx = nullptr;
-    double *part = nullptr, *sums = nullptr, *gpart = nullptr;
+    OffBufs o;
+    float *block = nullptr, *cells = nullptr;
     Td3Member *dmem = nullptr;
     SacMember *smem = nullptr;
     Td3PopStep *dsteps = nullptr;
-    for (int w = 0; w < 4 && !rc; ++w) {
-        if (w != kTd3ThetaT) rc = mlp_alloc(e, fresh, &flat[w], Ms * ((w & 1) ? Q2 : P));
-        if (!rc) rc = mlp_alloc(e, fresh, &mom[w], Ms * (w < 2 ? P : Q2));
-    }
-    if (rc || (rc = mlp_alloc(e, fresh, &block, Ms * stride)) || (rc = mlp_alloc(e, fresh, &grad, Ms * Qmax)) || (rc = mlp_alloc(e, fresh, &ybuf, Ms * (size_t)B)) ||
-        (rc = mlp_alloc(e, fresh, &xin, Ms * (size_t)B * (size_t)(D + A))) || (rc = mlp_alloc(e, fresh, &acts, Ms * (size_t)B * na)) ||
-        (rc = mlp_alloc(e, fresh, &deltas, Ms * (size_t)B * nd)) || (rc = mlp_alloc(e, fresh, &pieces, Ms * (size_t)B * (size_t)adc::kTd3Pieces)) ||
-        (rc = mlp_alloc(e, fresh, &idx, (size_t)B)) || (rc = mlp_alloc(e, fresh, &part, Ms * part_stride)) || (rc = mlp_alloc(e, fresh, &sums, Ms * 16u)) ||
-        (rc = mlp_alloc(e, fresh, &gpart, Ms * (size_t)pg_chunks(B) * Qmax)) || (rc = mlp_alloc(e, fresh, &rx, Ms * C * (size_t)D)) ||
-        (rc = mlp_alloc(e, fresh, &ra, Ms * C * (size_t)A)) || (rc = mlp_alloc(e, fresh, &rr, Ms * C)) || (rc = mlp_alloc(e, fresh, &rdone, Ms * C)) ||
-        (rc = mlp_alloc(e, fresh, &rx2, Ms * C * (size_t)D)) || (rc = mlp_alloc(e, fresh, &dmem, Ms)) || (rc = mlp_alloc(e, fresh, &smem, Ms)) ||
-        (rc = mlp_alloc(e, fresh, &cells, Ms * 4u)) || (rc = mlp_alloc(e, fresh, &dsteps, Ms * 3u * (size_t)kTd3PopBlock))) {
+    int rc;
+    if ((rc = off_alloc(e, fresh, sh, cfgs[0].batch_size, C, Ms, false, o)) || (rc = mlp_alloc(e, fresh, &block, Ms * k.stride)) ||
+        (rc = mlp_alloc(e, fresh, &dmem, Ms)) || (rc = mlp_alloc(e, fresh, &smem, Ms)) || (rc = mlp_alloc(e, fresh, &cells, Ms * 4u)) ||
+        (rc = mlp_alloc(e, fresh, &dsteps, Ms * 3u * (size_t)kTd3PopBlock))) {
         mlp_free(e, fresh);
         return rc;
     }
     td3_drop(e);
     e->td3_allocs.swap(fresh);
-    e->td3_cfg = sac_as_td3(cfgs[0]); e->td3_shape = sh;
-    e->td3_P = (int)P; e->td3_Qc = (int)Qc;
+    off_install(e, o, sh);
+    e->td3_cfg = sac_as_td3(cfgs[0]);
     e->sp_cfg.assign(Ms, cfgs[0]);
     if (count > 1) e->sp_cfg.assign(cfgs, cfgs + M);
     e->tp_cfg.resize(Ms);
     e->tp_mem.assign(Ms, Td3Member{});
     e->sp_mem.assign(Ms, SacMember{});
-    e->tp_dmem = dmem; e->sp_dmem = smem; e->sp_cells = cells; e->tp_dsteps = dsteps; e->tp_part_stride = part_stride;
+    e->tp_dmem = dmem; e->sp_dmem = smem; e->sp_cells = cells; e->tp_dsteps = dsteps; e->tp_part_stride = o.part_stride;
     std::vector<float> cell0(Ms * 4u, 0.0f);
     for (size_t m = 0; m < Ms; ++m) {
-        Td3Member &me = e->tp_mem[m];
         e->tp_cfg[m] = sac_as_td3(e->sp_cfg[m]);
         sp_member_fill(e, m, e->sp_cfg[m]);
         e->sp_mem[m].cell = cells + m * 4u;
-        float *base = block + m * stride;
-        MlpNet *nets[4] = {&me.q[0], &me.q[1], &me.q_t[0], &me.q_t[1]};
-        for (int n = 0; n < 4; ++n) {
-            nets[n]->layers = sh.q.layers;
-            for (int l = 0; l < sh.q.layers; ++l) {
-                nets[n]->W[l] = base + offW[n][l]; nets[n]->b[l] = base + offb[n][l];
-                nets[n]->n_in[l] = adc::td3_n_in(sh.q, l); nets[n]->n_out[l] = sh.q.n_out[l];
-            }
-        }
-        me.ring = Td3Ring{rx + m * C * (size_t)D, ra + m * C * (size_t)A, rr + m * C, rx2 + m * C * (size_t)D, rdone + m * C};
+        off_member_place(e->tp_mem[m], m, k, 4, block, o, sh, C);
         const float la = adc::sac_log_alpha_init(e->sp_cfg[m].init_alpha);
         cell0[m * 4u + kSacCellLogAlpha] = la; cell0[m * 4u + kSacCellAlpha] = adc::mlp_exp(la);
     }
     // member 0's stores against the flat orders; theta's are the learners' policy layers
-    e->td3_lay[kTd3Theta] = e->lrn_lay;
-    e->td3_lay[kTd3Theta].nterms = sh.pol.layers; e->td3_lay[kTd3Theta].Q = (int)P;
-    e->td3_lay[kTd3Psi] = td3_layout(e->tp_mem[0].q, 2);
-    e->td3_lay[kTd3ThetaT] = PgLayout{};
-    e->td3_lay[kTd3PsiT] = td3_layout(e->tp_mem[0].q_t, 2);
-    e->tp_stride[kTd3Theta] = e->lrn_stride;
-    e->tp_stride[kTd3Psi] = e->tp_stride[kTd3ThetaT] = e->tp_stride[kTd3PsiT] = stride;
-    for (int w = 0; w < 4; ++w) { e->td3_flat[w] = flat[w]; e->td3_mom[w] = mom[w]; }
+    tp_theta_layout(e, k.stride);
+    off_layouts(e, e->tp_mem[0].q, e->tp_mem[0].q_t, e->tp_mem[0].pol_t);
     e->td3_a_shift = e->td3_a_scale = nullptr; e->td3_ring = Td3Ring{};
-    e->td3_grad = grad; e->td3_ybuf = ybuf; e->td3_xin = xin; e->td3_acts = acts; e->td3_deltas = deltas; e->td3_pieces = pieces; e->td3_idx = idx;
-    e->td3_part = part; e->td3_sums = sums; e->td3_gpart = gpart;
     e->tp_steps.assign(Ms * 3u * (size_t)kTd3PopBlock, Td3PopStep{});
     e->tp_host_sums.assign(Ms * 16u, 0.0);
-    e->tp_critic_set.assign(Ms * 2u * adc::kMlpMaxLayers, 0);
-    e->td3_stored_t = e->ro_t;              // (days recorded before this call are not the trainer's)
+    e->tp_critic_set.assign(Ms * kOffCriticFlags, 0);
     if ((rc = sp_members_upload(e))) return rc;
     HIP_TRY(hipMemcpyAsync(cells, cell0.data(), cell0.size() * 4, hipMemcpyHostToDevice, e->stream));
     // every member's theta starts as its device policy; the target critics as copies (zeros until the critics are uploaded and synchronised)
     tp_params_copy(e, kTd3Theta, 0, M, 1);
-    if ((rc = sp_sync_run(e, 0, M))) return rc;
+    if ((rc = off_sync_run(e, 0, M, 1))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));       // (cell0 is the host's until here)
     e->have_sac_pop = true;
     return ADC_OK;
@@ -227,21 +177,7 @@ ADC_EXPORT int adc_engine_sac_pop_set_critic_layer(adc_engine *e, int32_t member
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (critic != 0 && critic != 1) return fail(ADC_EINVAL, "critic: 0 or 1");
-    const adc::Td3Net &q = e->td3_shape.q;
-    if (layer < 0 || layer >= q.layers) return fail(ADC_EINVAL, "no such critic layer");
-    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
-    ENGINE_GUARD(e);
-    size_t off = (size_t)member * 2u * (size_t)e->td3_Qc + (size_t)critic * (size_t)e->td3_Qc;
-    for (int l = 0; l < layer; ++l) off += (size_t)(adc::td3_n_in(q, l) + 1) * (size_t)q.n_out[l];
-    const size_t nw = (size_t)adc::td3_n_in(q, layer) * (size_t)q.n_out[layer];
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off, weights_in_out, nw * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off + nw, bias_out, (size_t)q.n_out[layer] * 4, hipMemcpyHostToDevice, e->stream));
-    tp_params_copy(e, kTd3Psi, member, 1, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->tp_critic_set[((size_t)member * 2u + (size_t)critic) * adc::kMlpMaxLayers + (size_t)layer] = 1;
-    return ADC_OK;
+    return off_set_critic_layer(e, member, critic, layer, weights_in_out, bias_out);
 }
 
 ADC_EXPORT int adc_engine_sac_pop_sync_targets(adc_engine *e, int32_t member)
@@ -250,7 +186,7 @@ ADC_EXPORT int adc_engine_sac_pop_sync_targets(adc_engine *e, int32_t member)
     int rc;
     if ((rc = sp_ready(e)) || (member != -1 && (rc = tp_member_check(e, member)))) return rc;
     ENGINE_GUARD(e);
-    if ((rc = member == -1 ? sp_sync_run(e, 0, e->lrn_M) : sp_sync_run(e, member, 1))) return rc;
+    if ((rc = member == -1 ? off_sync_run(e, 0, e->lrn_M, 1) : off_sync_run(e, member, 1, 1))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ADC_OK;
 }
@@ -259,35 +195,22 @@ ADC_EXPORT int adc_engine_sac_pop_store(adc_engine *e, int64_t *stored_per_membe
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = sp_ready(e)) || (rc = sp_state_check(e))) return rc;
-    if (e->ro_t <= e->td3_stored_t) return fail(ADC_ESTATE, "no unstored day in the record (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)");
-    if (e->td3_gap || e->env_moves != e->ro_moves)
-        return fail(ADC_ESTATE, "the envs were stepped or reset outside the record since an unstored recorded day: its next observation is not the "
-                                "one the envs hold (adc_engine_rollout_reset, collect again)");
+    if ((rc = sp_ready(e)) || (rc = sp_state_check(e)) || (rc = off_store_check(e))) return rc;
     ENGINE_GUARD(e);
-    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;
-    // (raw rows under a running observation normaliser: the last day's x' is the raw row an act would read now)
+    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;      // (a member's envs, not the engine's)
+    // (raw rows under a running observation normaliser - SAC's set, e->sn: the last day's x' is the raw row an act would read now)
     hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->sn.obs.count ? nullptr : e->mp.shift,
                        e->sn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
                        e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
                        (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
-    HIP_TRY(hipGetLastError());
-    if (e->per_live && (rc = per_store_run(e, e->td3_written, count))) return rc;
-    e->td3_written += count;
-    e->td3_stored_t = e->ro_t;
-    if (stored_per_member) *stored_per_member = count;
-    return ADC_OK;
+    return off_store_done(e, count, stored_per_member);
 }
 
 ADC_EXPORT int adc_engine_sac_pop_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity, int32_t *batch_size)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sp_ready(e)) return rc;
-    if (size) *size = td3_size(e);
-    if (written) *written = e->td3_written;
-    if (capacity) *capacity = e->td3_cfg.capacity;
-    if (batch_size) *batch_size = e->td3_cfg.batch_size;
-    return ADC_OK;
+    return off_buffer_info(e, size, written, capacity, batch_size);
 }
 
 ADC_EXPORT int adc_engine_sac_pop_buffer_fetch(adc_engine *e, int32_t member, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done,
@@ -296,17 +219,7 @@ ADC_EXPORT int adc_engine_sac_pop_buffer_fetch(adc_engine *e, int32_t member, in
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (slot < 0 || count < 1 || slot > td3_size(e) - count) return fail(ADC_EINVAL, "the slot range is not inside [0, size)");
-    ENGINE_GUARD(e);
-    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-    const Td3Ring &g = e->tp_mem[(size_t)member].ring;
-    if (x) HIP_TRY(hipMemcpyAsync(x, g.x + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
-    if (a) HIP_TRY(hipMemcpyAsync(a, g.a + s * A, n * A * 4, hipMemcpyDeviceToHost, e->stream));
-    if (r) HIP_TRY(hipMemcpyAsync(r, g.r + s, n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (done) HIP_TRY(hipMemcpyAsync(done, g.done + s, n, hipMemcpyDeviceToHost, e->stream));
-    if (x2) HIP_TRY(hipMemcpyAsync(x2, g.x2 + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return off_ring_fetch(e, member, slot, count, x, a, r, done, x2);
 }
 
 ADC_EXPORT int adc_engine_sac_pop_buffer_load(adc_engine *e, int32_t member, int64_t slot, int64_t count, const float *x, const float *a, const float *r,
@@ -315,24 +228,7 @@ ADC_EXPORT int adc_engine_sac_pop_buffer_load(adc_engine *e, int32_t member, int
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (!x || !a || !r || !done || !x2) return fail(ADC_EINVAL, "x, a, r, done or x2 is NULL");
-    if (slot < 0 || count < 1 || slot > (int64_t)e->td3_cfg.capacity - count) return fail(ADC_EINVAL, "the slot range is not inside [0, capacity)");
-    if (written < slot + count) return fail(ADC_EINVAL, "written: at least slot + count");
-    ENGINE_GUARD(e);
-    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-    const Td3Ring &g = e->tp_mem[(size_t)member].ring;
-    HIP_TRY(hipMemcpyAsync(g.x + s * D, x, n * D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.a + s * A, a, n * A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.r + s, r, n * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.done + s, done, n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_written = written;               // (the members' rings move together: one count for all)
-    if (e->per_live) {
-        if ((rc = per_loaded_run(e, member, slot, count))) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return ADC_OK;
+    return off_ring_load(e, member, slot, count, x, a, r, done, x2, written);
 }
 
 ADC_EXPORT int adc_engine_sac_pop_batch_indices(adc_engine *e, int32_t member, int64_t update, int32_t *idx_b)
@@ -340,44 +236,28 @@ ADC_EXPORT int adc_engine_sac_pop_batch_indices(adc_engine *e, int32_t member, i
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
-    if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
-    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_pop_store)");
-    if (e->per_live) return fail(ADC_ESTATE, "prioritised replay is alive on this engine: the batch is adc_engine_replay_prio_batch's, not the uniform law's");
-    ENGINE_GUARD(e);
-    const int B = e->td3_cfg.batch_size;
-    hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->tp_mem[(size_t)member].key, (uint32_t)update,
-                       (uint32_t)td3_size(e), B, e->td3_idx);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(idx_b, e->td3_idx, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return off_batch_indices(e, e->tp_mem[(size_t)member].key, update, idx_b, "the replay buffer is empty (adc_engine_sac_pop_store)");
 }
 
 ADC_EXPORT int adc_engine_sac_pop_update(adc_engine *e, int32_t updates, adc_sac_stats *stats_m)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = sp_ready(e)) || (rc = sp_state_check(e))) return rc;
-    if (updates < 1 || updates > 65536) return fail(ADC_EINVAL, "updates: 1 to 65536");
-    if (!tp_critics_set(e)) return fail(ADC_ESTATE, "a critic layer of a member has not been uploaded (adc_engine_sac_pop_set_critic_layer)");
-    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_sac_pop_store)");
-    if (e->td3_updates + updates >= 0x7FFFFFFFll) return fail(ADC_ESTATE, "the update counter is exhausted");
+    if ((rc = sp_ready(e)) || (rc = sp_state_check(e)) ||
+        (rc = off_update_check(e, updates, true, "a critic layer of a member has not been uploaded (adc_engine_sac_pop_set_critic_layer)",
+                               "the replay buffer is empty (adc_engine_sac_pop_store)", 0x7FFFFFFFll)))
+        return rc;
     ENGINE_GUARD(e);
     const int M = e->lrn_M;
     bool any_clip = false, any_alpha = false;
     for (const adc_sac_config &c : e->sp_cfg) { any_clip = any_clip || c.max_grad_norm > 0.0f; any_alpha = any_alpha || c.alpha_lr > 0.0f; }
-    HIP_TRY(hipMemsetAsync(e->td3_sums, 0, (size_t)M * 16 * sizeof(double), e->stream));
-    for (int u0 = 0; u0 < updates; u0 += kTd3PopBlock) {
-        const int nb = std::min(kTd3PopBlock, updates - u0);
-        // the block's step constants (the Adam bias corrections of every step to come) in one copy; the host's table is free to
-        // write: the call before this one, and the block before this one, ended with a wait
-        if (u0 > 0) HIP_TRY(hipStreamSynchronize(e->stream));
-        for (int i = 0; i < nb; ++i) sp_steps_fill(e, i, e->td3_updates + i);
-        HIP_TRY(hipMemcpyAsync(e->tp_dsteps, e->tp_steps.data(), (size_t)nb * 3u * (size_t)M * sizeof(Td3PopStep), hipMemcpyHostToDevice, e->stream));
-        for (int i = 0; i < nb; ++i)
-            if ((rc = sp_one_update(e, i, stats_m != nullptr, u0 + i + 1 == updates, any_clip, any_alpha))) return rc;
-    }
+    rc = off_pop_updates(
+        e, updates, 3,
+        [&](int nb) {
+            for (int i = 0; i < nb; ++i) sp_steps_fill(e, i, e->td3_updates + i);
+        },
+        [&](int u, int i) { return sp_one_update(e, i, stats_m != nullptr, u + 1 == updates, any_clip, any_alpha); });
+    if (rc) return rc;
     std::vector<float> cells;
     if (stats_m) {
         cells.resize((size_t)M * 4u);
@@ -385,23 +265,8 @@ ADC_EXPORT int adc_engine_sac_pop_update(adc_engine *e, int32_t updates, adc_sac
         HIP_TRY(hipMemcpyAsync(cells.data(), e->sp_cells, cells.size() * 4, hipMemcpyDeviceToHost, e->stream));
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (stats_m) {
-        const double n = (double)e->td3_cfg.batch_size;
-        for (int m = 0; m < M; ++m) {
-            const double *sums = e->tp_host_sums.data() + (size_t)m * 16;
-            const float *cell = cells.data() + (size_t)m * 4u;
-            adc_sac_stats *stats = stats_m + m;
-            const double l1 = sums[adc::kTd3Loss1] / n, l2 = sums[adc::kTd3Loss2] / n;
-            stats->updates = e->td3_updates; stats->buffer_size = td3_size(e); stats->samples = e->td3_cfg.batch_size;
-            stats->critic_loss = l1 + l2;
-            stats->q1_mean = sums[adc::kTd3Q1] / n; stats->q2_mean = sums[adc::kTd3Q2] / n; stats->y_mean = sums[adc::kTd3Y] / n;
-            stats->actor_loss = sums[adc::kSacPiLoss] / n;
-            stats->logp_mean = sums[adc::kSacLp] / n;
-            stats->alpha = cell[kSacCellAlpha]; stats->log_alpha = cell[kSacCellLogAlpha];
-            stats->critic_grad_norm = std::sqrt(sums[8]);
-            stats->actor_grad_norm = std::sqrt(sums[9]);
-        }
-    }
+    if (stats_m)
+        for (int m = 0; m < M; ++m) sac_stats_fill(e, e->tp_host_sums.data() + (size_t)m * 16, cells.data() + (size_t)m * 4u, stats_m + m);
     return ADC_OK;
 }
 
@@ -409,9 +274,7 @@ ADC_EXPORT int adc_engine_sac_pop_param_counts(adc_engine *e, int64_t *actor_p, 
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = sp_ready(e)) return rc;
-    if (actor_p) *actor_p = e->td3_P;
-    if (critics_2qc) *critics_2qc = 2 * (int64_t)e->td3_Qc;
-    return ADC_OK;
+    return off_param_counts(e, actor_p, critics_2qc);
 }
 
 ADC_EXPORT int adc_engine_sac_pop_state_get(adc_engine *e, int32_t member, float *theta_p, float *psi_q, float *psi_target_q, float *m_theta_p,
@@ -421,14 +284,9 @@ ADC_EXPORT int adc_engine_sac_pop_state_get(adc_engine *e, int32_t member, float
     int rc;
     if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
     ENGINE_GUARD(e);
-    const size_t P = (size_t)e->td3_P, Q2 = 2 * (size_t)e->td3_Qc, mi = (size_t)member;
     float *flat[4] = {theta_p, psi_q, nullptr, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
-    for (int w = 0; w < 4; ++w) {
-        const size_t fq = (w & 1) ? Q2 : P, mq = w < 2 ? P : Q2;
-        if (flat[w]) HIP_TRY(hipMemcpyAsync(flat[w], e->td3_flat[w] + mi * fq, fq * 4, hipMemcpyDeviceToHost, e->stream));
-        if (mom[w]) HIP_TRY(hipMemcpyAsync(mom[w], e->td3_mom[w] + mi * mq, mq * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    if (log_alpha3) HIP_TRY(hipMemcpyAsync(log_alpha3, e->sp_cells + mi * 4u, 3 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if ((rc = off_state_get(e, member, flat, mom))) return rc;
+    if (log_alpha3) HIP_TRY(hipMemcpyAsync(log_alpha3, e->sp_cells + (size_t)member * 4u, 3 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (updates) *updates = e->td3_updates;
     return ADC_OK;
@@ -439,28 +297,13 @@ ADC_EXPORT int adc_engine_sac_pop_state_set(adc_engine *e, int32_t member, const
                                             const float *log_alpha3, int64_t updates)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    int rc;
-    if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (!theta_p || !psi_q || !psi_target_q || !m_theta_p || !v_theta_p || !m_psi_q || !v_psi_q || !log_alpha3) return fail(ADC_EINVAL, "a state vector is NULL");
-    if (updates < 0 || updates >= 0x7FFFFFFFll) return fail(ADC_EINVAL, "updates: 0 to 2^31 - 2");
-    if (!std::isfinite(log_alpha3[0])) return fail(ADC_EINVAL, "log_alpha must be finite");
-    ENGINE_GUARD(e);
-    const size_t P = (size_t)e->td3_P, Q2 = 2 * (size_t)e->td3_Qc, mi = (size_t)member;
     const float *flat[4] = {theta_p, psi_q, nullptr, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
-    for (int w = 0; w < 4; ++w) {
-        const size_t fq = (w & 1) ? Q2 : P, mq = w < 2 ? P : Q2;
-        HIP_TRY(hipMemcpyAsync(e->td3_mom[w] + mi * mq, mom[w], mq * 4, hipMemcpyHostToDevice, e->stream));
-        if (!flat[w]) continue;
-        HIP_TRY(hipMemcpyAsync(e->td3_flat[w] + mi * fq, flat[w], fq * 4, hipMemcpyHostToDevice, e->stream));
-        tp_params_copy(e, w, member, 1, 0);         // (the member's policy layers, critics and target critics follow its flat vectors)
-    }
-    const float cell[4] = {log_alpha3[0], log_alpha3[1], log_alpha3[2], adc::mlp_exp(log_alpha3[0])};
-    HIP_TRY(hipMemcpyAsync(e->sp_cells + mi * 4u, cell, sizeof(cell), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_updates = updates;                       // (the members move together: one counter for all)
-    for (size_t i = 0; i < 2u * adc::kMlpMaxLayers; ++i) e->tp_critic_set[mi * 2u * adc::kMlpMaxLayers + i] = 1;
-    return ADC_OK;
+    int rc;
+    if ((rc = sp_ready(e)) || (rc = tp_member_check(e, member)) || (rc = sac_state_set_check(flat, mom, log_alpha3, updates))) return rc;
+    ENGINE_GUARD(e);
+    float cell[4];
+    if ((rc = sac_cell_upload(e, e->sp_cells + (size_t)member * 4u, log_alpha3, cell))) return rc;
+    return off_state_set(e, member, flat, mom, updates);       // (waits: `cell` is the host's until then)
 }
 
 ADC_EXPORT int adc_engine_sac_pop_set_config(adc_engine *e, int32_t member, const adc_sac_config *cfg)
@@ -491,28 +334,6 @@ ADC_EXPORT int adc_engine_sac_pop_copy(adc_engine *e, int32_t src, int32_t dst, 
     if ((rc = sp_ready(e)) || (rc = tp_member_check(e, src)) || (rc = tp_member_check(e, dst))) return rc;
     if (src == dst) return ADC_OK;
     ENGINE_GUARD(e);
-    const size_t P = (size_t)e->td3_P, Q2 = 2 * (size_t)e->td3_Qc, from = (size_t)src, to = (size_t)dst;
-    for (int w = 0; w < 4; ++w) {
-        const size_t fq = (w & 1) ? Q2 : P, mq = w < 2 ? P : Q2;
-        HIP_TRY(hipMemcpyAsync(e->td3_mom[w] + to * mq, e->td3_mom[w] + from * mq, mq * 4, hipMemcpyDeviceToDevice, e->stream));
-        if (w == kTd3ThetaT) continue;
-        HIP_TRY(hipMemcpyAsync(e->td3_flat[w] + to * fq, e->td3_flat[w] + from * fq, fq * 4, hipMemcpyDeviceToDevice, e->stream));
-        tp_params_copy(e, w, dst, 1, 0);
-    }
-    HIP_TRY(hipMemcpyAsync(e->sp_cells + to * 4u, e->sp_cells + from * 4u, 4 * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(hipGetLastError());
-    if (with_ring) {
-        const size_t C = (size_t)e->td3_cfg.capacity, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-        const Td3Ring &s = e->tp_mem[from].ring, &d = e->tp_mem[to].ring;
-        HIP_TRY(hipMemcpyAsync(d.x, s.x, C * D * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.a, s.a, C * A * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.r, s.r, C * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.done, s.done, C, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.x2, s.x2, C * D * 4, hipMemcpyDeviceToDevice, e->stream));
-        if (e->per_live && (rc = per_copy_run(e, src, dst))) return rc;     // (the leaves, nodes and top travel with the ring)
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const size_t per = 2u * adc::kMlpMaxLayers;
-    for (size_t i = 0; i < per; ++i) e->tp_critic_set[to * per + i] = e->tp_critic_set[from * per + i];
-    return ADC_OK;
+    HIP_TRY(hipMemcpyAsync(e->sp_cells + (size_t)dst * 4u, e->sp_cells + (size_t)src * 4u, 4 * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    return off_pop_copy(e, src, dst, with_ring);
 }

@@ -3,6 +3,8 @@
 // parts/kernel_pg.inc, the law csrc/adc_td3.h).  The population shares the solo trainer's engine fields, sized for all members:
 // td3_flat / td3_mom are [M][P] and [M][2 Qc], the scratch [M][B][...], td3_sums [M][16]; td3_cfg holds the shared fields
 // (batch_size, capacity, the critics' shape, policy_delay), td3_lay member 0's stores (a member's tp_stride[w] floats further).
+// The ring, the critic upload, the state vectors, the allocation, the tp_* launch helpers and the update driver are
+// parts/offpolicy_core.inc's; here are the population's refusals, its members' fill, its step table and its update.
 // (part of the single translation unit adc_engine.hip)
 namespace {
 int tp_ready(const adc_engine *e)
@@ -20,12 +22,6 @@ int tp_state_check(const adc_engine *e)
     if (!e->ro_obs) return fail(ADC_ESTATE, "off-policy training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
     return ADC_OK;
 }
-int tp_member_check(const adc_engine *e, int32_t member)
-{
-    if (member < 0 || member >= e->lrn_M) return fail(ADC_EINVAL, "no such member");
-    return ADC_OK;
-}
-inline size_t tp_count(const adc_engine *e, int which) { return (which & 1) ? 2 * (size_t)e->td3_Qc : (size_t)e->td3_P; }
 // a member's law constants and key from its configuration
 void tp_member_fill(const adc_engine *e, Td3Member &m, const adc_td3_config &c)
 {
@@ -37,51 +33,6 @@ int tp_members_upload(adc_engine *e)
     HIP_TRY(hipMemcpyAsync(e->tp_dmem, e->tp_mem.data(), e->tp_mem.size() * sizeof(Td3Member), hipMemcpyHostToDevice, e->stream));
     return ADC_OK;
 }
-// the members member0 .. member0 + count - 1: flat <- stores (to_flat) or stores <- flat, of vector `which`
-void tp_params_copy(adc_engine *e, int which, int member0, int count, int to_flat)
-{
-    const PgLayout &lay = e->td3_lay[which];
-    const size_t Q = tp_count(e, which);
-    hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks(lay.Q), (unsigned)count), dim3(kPgBlock), 0, e->stream, lay, e->tp_stride[which], member0,
-                       e->td3_flat[which] + (size_t)member0 * Q, Q, to_flat);
-}
-int tp_sync_run(adc_engine *e, int member0, int count)
-{
-    for (int w = 0; w < 2; ++w) {
-        const size_t Q = tp_count(e, w), at = (size_t)member0 * Q;
-        HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3ThetaT + w] + at, e->td3_flat[kTd3Theta + w] + at, (size_t)count * Q * 4, hipMemcpyDeviceToDevice, e->stream));
-        tp_params_copy(e, kTd3ThetaT + w, member0, count, 0);
-    }
-    HIP_TRY(hipGetLastError());
-    return ADC_OK;
-}
-// every member's chunked sum of `cols` columns (its rows from member * mstep on) into td3_sums[member * 16 + at ...]
-int tp_csum_launch(adc_engine *e, const float *src, int n, size_t mstep, int stride, int cols, int mode, int at)
-{
-    const int chunks = (int)pg_chunks(n), lanes = chunks * cols, M = e->lrn_M;
-    hipLaunchKernelGGL(k_pg_pop_chunk_sums, dim3((unsigned)((lanes + 255) / 256), (unsigned)M), dim3(256), 0, e->stream, src, n, 0, 0, mstep, stride, cols, mode,
-                       (const PgMember *)nullptr, e->td3_part, e->tp_part_stride);
-    hipLaunchKernelGGL(k_pg_pop_join, dim3((unsigned)M), dim3(64), 0, e->stream, e->td3_part, e->tp_part_stride, chunks, cols, e->td3_sums + at, 16);
-    HIP_TRY(hipGetLastError());
-    return ADC_OK;
-}
-// the weight gradient's partials of one network of every member over its batch
-void tp_wgrad_launch(adc_engine *e, const adc::Td3Net &net, int ldx0, int na, int acts_off, int nd, int d_off, int flat0, int Q, int B)
-{
-    int flat = flat0, ao = acts_off, dof = d_off;
-    for (int l = 0; l < net.layers; ++l) {
-        const int n_in = adc::td3_n_in(net, l), n_out = net.n_out[l];
-        PgTerm t{l == 0 ? e->td3_xin : e->td3_acts + ao, l == 0 ? (size_t)ldx0 : (size_t)na, n_in, n_out, dof, flat, 0};
-        const unsigned tiles = (unsigned)(((n_in + 1 + kPgTile - 1) / kPgTile) * ((n_out + kPgTile - 1) / kPgTile));
-        hipLaunchKernelGGL(k_pg_pop_wgrad, dim3(tiles, (unsigned)pg_chunks(B), (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, t, (long long)B, 1, 1, 0, 0,
-                           e->td3_deltas, nd, e->td3_gpart, Q);
-        flat += (n_in + 1) * n_out;
-        dof += n_out;
-        if (l > 0) ao += n_in;
-    }
-}
-// updates of a call whose step constants go up in one copy (a longer call waits for the stream once per so many updates)
-constexpr int kTd3PopBlock = 64;
 // row `row` of the step table: every member's constants of its next critic (actor = false) or actor step; no clip until a scale is known
 void tp_steps_fill(adc_engine *e, int row, bool actor, int64_t steps_taken)
 {
@@ -92,33 +43,6 @@ void tp_steps_fill(adc_engine *e, int row, bool actor, int64_t steps_taken)
         s.clip = 0; s.scale = 1.0f;
         s.step = td3_step_of(c, actor ? c.actor_lr : c.critic_lr, steps_taken);
     }
-}
-// every member's gradient from the partials, its squared norm into sums[slot] when asked for, the clip's scale, the step
-int tp_step_run(adc_engine *e, int which, float **mom, int Q, int B, bool norm_wanted, int slot, int row, bool any_clip)
-{
-    const int M = e->lrn_M;
-    hipLaunchKernelGGL(k_pg_pop_grad_join, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->td3_gpart, (int)pg_chunks(B), Q, (long long)B,
-                       e->td3_grad);
-    HIP_TRY(hipGetLastError());
-    if (any_clip || norm_wanted)
-        if (int rc = tp_csum_launch(e, e->td3_grad, Q, (size_t)Q, 1, 1, 2, slot)) return rc;
-    Td3PopStep *drow = e->tp_dsteps + (size_t)row * (size_t)M;
-    if (any_clip) {
-        // all members' squared norms in one copy, each scale finished on the host as the solo path's is, the row up in one copy
-        HIP_TRY(hipMemcpyAsync(e->tp_host_sums.data(), e->td3_sums, e->tp_host_sums.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        Td3PopStep *hrow = e->tp_steps.data() + (size_t)row * (size_t)M;
-        for (int m = 0; m < M; ++m) {
-            const float mgn = e->tp_cfg[(size_t)m].max_grad_norm;
-            hrow[m].clip = mgn > 0.0f;
-            hrow[m].scale = hrow[m].clip ? adc::pg_clip_scale(mgn, std::sqrt(e->tp_host_sums[(size_t)m * 16 + (size_t)slot])) : 1.0f;
-        }
-        HIP_TRY(hipMemcpyAsync(drow, hrow, (size_t)M * sizeof(Td3PopStep), hipMemcpyHostToDevice, e->stream));
-    }
-    hipLaunchKernelGGL(k_td3_pop_step, dim3(pg_blocks(Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, e->td3_lay[which], e->tp_stride[which], e->td3_flat[which],
-                       mom[0], mom[1], e->td3_grad, drow);
-    HIP_TRY(hipGetLastError());
-    return ADC_OK;
 }
 // one update of every member; `index`: the update's place in the call's block of kTd3PopBlock (its rows of the step table).
 // The members' sums as in the solo path: [0..4] the critic pieces, [5] the critics' grad^2, [8] Q1(x, mu(x)), [9] the actor's grad^2
@@ -166,15 +90,6 @@ int tp_one_update(adc_engine *e, int index, bool stats_wanted, bool last, bool l
     e->td3_updates += 1;
     return ADC_OK;
 }
-bool tp_critics_set(const adc_engine *e)
-{
-    const size_t per = 2u * adc::kMlpMaxLayers;
-    for (size_t m = 0; m < (size_t)e->lrn_M; ++m)
-        for (int i = 0; i < 2; ++i)
-            for (int l = 0; l < e->td3_shape.q.layers; ++l)
-                if (!e->tp_critic_set[m * per + (size_t)i * adc::kMlpMaxLayers + (size_t)l]) return false;
-    return true;
-}
 }  // namespace
 
 ADC_EXPORT int adc_engine_td3_pop_init(adc_engine *e, const adc_td3_config *cfgs, int32_t count)
@@ -194,88 +109,44 @@ ADC_EXPORT int adc_engine_td3_pop_init(adc_engine *e, const adc_td3_config *cfgs
     const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, cfgs[0], 0);
     if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for off-policy training (LDS)");
     ENGINE_GUARD(e);
-    const int A = sh.A, D = sh.D, B = cfgs[0].batch_size;
-    const size_t Ms = (size_t)M, C = (size_t)cfgs[0].capacity, P = (size_t)adc::td3_params(sh.pol), Qc = (size_t)adc::td3_params(sh.q), Q2 = 2 * Qc,
-                 Qmax = std::max(P, Q2);
-    const size_t na = (size_t)std::max(std::max(2 * adc::td3_hidden(sh.q), adc::td3_hidden(sh.pol)), 1);
-    const size_t nd = (size_t)std::max(2 * adc::td3_outs(sh.q), adc::td3_outs(sh.pol));
-    const size_t part_stride = (size_t)pg_chunks((long long)std::max((size_t)B, Qmax)) * 8u + 8u;
-    // a member's block of stores: critic 1, critic 2, target critic 1, target critic 2, target actor, every piece on a 16-byte boundary
-    size_t offW[5][adc::kMlpMaxLayers] = {}, offb[5][adc::kMlpMaxLayers] = {}, stride = 0;
-    for (int n = 0; n < 5; ++n) {
-        const adc::Td3Net &shape = n < 4 ? sh.q : sh.pol;
-        for (int l = 0; l < shape.layers; ++l) {
-            offW[n][l] = stride; stride += adc::mlp_weight_count(adc::td3_n_in(shape, l), shape.n_out[l]);
-            offb[n][l] = stride; stride += ((size_t)shape.n_out[l] + 3u) & ~(size_t)3u;
-        }
-    }
+    const size_t Ms = (size_t)M, C = (size_t)cfgs[0].capacity;
+    const OffBlock k = off_block_layout(sh, 5);
     // (the new state is allocated before the old one goes: a failure leaves the engine as it was)
     std::vector<void *> fresh;
-    int rc = ADC_OK;
-    float *block = nullptr, *flat[4] = {}, *mom[4] = {}, *shift = nullptr, *scale = nullptr, *grad = nullptr, *ybuf = nullptr, *xin = nullptr, *acts = nullptr,
-          *deltas = nullptr, *pieces = nullptr, *rx = nullptr, *ra = nullptr, *rr = nullptr, *rx2 = nullptr;
-    uint8_t *rdone = nullptr;
-    int32_t *idx = nullptr;
-    double *part = nullptr, *sums = nullptr, *gpart = nullptr;
+    OffBufs o;
+    float *block = nullptr, *shift = nullptr, *scale = nullptr;
     Td3Member *dmem = nullptr;
     Td3PopStep *dsteps = nullptr;
-    for (int w = 0; w < 4 && !rc; ++w)
-        if (!(rc = mlp_alloc(e, fresh, &flat[w], Ms * ((w & 1) ? Q2 : P)))) rc = mlp_alloc(e, fresh, &mom[w], Ms * (w < 2 ? P : Q2));
-    if (rc || (rc = mlp_alloc(e, fresh, &block, Ms * stride)) || (rc = mlp_alloc(e, fresh, &shift, (size_t)A)) || (rc = mlp_alloc(e, fresh, &scale, (size_t)A)) ||
-        (rc = mlp_alloc(e, fresh, &grad, Ms * Qmax)) || (rc = mlp_alloc(e, fresh, &ybuf, Ms * (size_t)B)) ||
-        (rc = mlp_alloc(e, fresh, &xin, Ms * (size_t)B * (size_t)(D + A))) || (rc = mlp_alloc(e, fresh, &acts, Ms * (size_t)B * na)) ||
-        (rc = mlp_alloc(e, fresh, &deltas, Ms * (size_t)B * nd)) || (rc = mlp_alloc(e, fresh, &pieces, Ms * (size_t)B * (size_t)adc::kTd3Pieces)) ||
-        (rc = mlp_alloc(e, fresh, &idx, (size_t)B)) || (rc = mlp_alloc(e, fresh, &part, Ms * part_stride)) || (rc = mlp_alloc(e, fresh, &sums, Ms * 16u)) ||
-        (rc = mlp_alloc(e, fresh, &gpart, Ms * (size_t)pg_chunks(B) * Qmax)) || (rc = mlp_alloc(e, fresh, &rx, Ms * C * (size_t)D)) ||
-        (rc = mlp_alloc(e, fresh, &ra, Ms * C * (size_t)A)) || (rc = mlp_alloc(e, fresh, &rr, Ms * C)) || (rc = mlp_alloc(e, fresh, &rdone, Ms * C)) ||
-        (rc = mlp_alloc(e, fresh, &rx2, Ms * C * (size_t)D)) || (rc = mlp_alloc(e, fresh, &dmem, Ms)) ||
+    int rc;
+    if ((rc = off_alloc(e, fresh, sh, cfgs[0].batch_size, C, Ms, true, o)) || (rc = mlp_alloc(e, fresh, &block, Ms * k.stride)) ||
+        (rc = mlp_alloc(e, fresh, &shift, (size_t)sh.A)) || (rc = mlp_alloc(e, fresh, &scale, (size_t)sh.A)) || (rc = mlp_alloc(e, fresh, &dmem, Ms)) ||
         (rc = mlp_alloc(e, fresh, &dsteps, Ms * 2u * (size_t)kTd3PopBlock))) {
         mlp_free(e, fresh);
         return rc;
     }
     td3_drop(e);
     e->td3_allocs.swap(fresh);
-    e->td3_cfg = cfgs[0]; e->td3_shape = sh;
-    e->td3_P = (int)P; e->td3_Qc = (int)Qc;
+    off_install(e, o, sh);
+    e->td3_cfg = cfgs[0];
     e->tp_cfg.assign(Ms, cfgs[0]);
     if (count > 1) e->tp_cfg.assign(cfgs, cfgs + M);
     e->tp_mem.assign(Ms, Td3Member{});
     for (size_t m = 0; m < Ms; ++m) {
-        Td3Member &me = e->tp_mem[m];
-        tp_member_fill(e, me, e->tp_cfg[m]);
-        float *base = block + m * stride;
-        MlpNet *nets[5] = {&me.q[0], &me.q[1], &me.q_t[0], &me.q_t[1], &me.pol_t};
-        for (int n = 0; n < 5; ++n) {
-            const adc::Td3Net &shape = n < 4 ? sh.q : sh.pol;
-            nets[n]->layers = shape.layers;
-            for (int l = 0; l < shape.layers; ++l) {
-                nets[n]->W[l] = base + offW[n][l]; nets[n]->b[l] = base + offb[n][l];
-                nets[n]->n_in[l] = adc::td3_n_in(shape, l); nets[n]->n_out[l] = shape.n_out[l];
-            }
-        }
-        me.ring = Td3Ring{rx + m * C * (size_t)D, ra + m * C * (size_t)A, rr + m * C, rx2 + m * C * (size_t)D, rdone + m * C};
+        tp_member_fill(e, e->tp_mem[m], e->tp_cfg[m]);
+        off_member_place(e->tp_mem[m], m, k, 5, block, o, sh, C);
     }
     // member 0's stores against the flat orders; theta's are the learners' policy layers
-    e->td3_lay[kTd3Theta] = e->lrn_lay;
-    e->td3_lay[kTd3Theta].nterms = sh.pol.layers; e->td3_lay[kTd3Theta].Q = (int)P;
-    e->td3_lay[kTd3Psi] = td3_layout(e->tp_mem[0].q, 2);
-    e->td3_lay[kTd3ThetaT] = td3_layout(&e->tp_mem[0].pol_t, 1);
-    e->td3_lay[kTd3PsiT] = td3_layout(e->tp_mem[0].q_t, 2);
-    e->tp_stride[kTd3Theta] = e->lrn_stride;
-    e->tp_stride[kTd3Psi] = e->tp_stride[kTd3ThetaT] = e->tp_stride[kTd3PsiT] = stride;
-    for (int w = 0; w < 4; ++w) { e->td3_flat[w] = flat[w]; e->td3_mom[w] = mom[w]; }
+    tp_theta_layout(e, k.stride);
+    off_layouts(e, e->tp_mem[0].q, e->tp_mem[0].q_t, e->tp_mem[0].pol_t);
     e->td3_a_shift = shift; e->td3_a_scale = scale; e->td3_ring = Td3Ring{};
-    e->td3_grad = grad; e->td3_ybuf = ybuf; e->td3_xin = xin; e->td3_acts = acts; e->td3_deltas = deltas; e->td3_pieces = pieces; e->td3_idx = idx;
-    e->td3_part = part; e->td3_sums = sums; e->td3_gpart = gpart;
-    e->tp_dmem = dmem; e->tp_dsteps = dsteps; e->tp_part_stride = part_stride;
+    e->tp_dmem = dmem; e->tp_dsteps = dsteps; e->tp_part_stride = o.part_stride;
     e->tp_steps.assign(Ms * 2u * (size_t)kTd3PopBlock, Td3PopStep{});
     e->tp_host_sums.assign(Ms * 16u, 0.0);
-    e->tp_critic_set.assign(Ms * 2u * adc::kMlpMaxLayers, 0);
-    e->td3_stored_t = e->ro_t;              // (days recorded before this call are not the trainer's)
+    e->tp_critic_set.assign(Ms * kOffCriticFlags, 0);
     if ((rc = tp_members_upload(e))) return rc;
     // every member's theta starts as its device policy; the targets as copies (of the critics too: zeros until they are uploaded and synchronised)
     tp_params_copy(e, kTd3Theta, 0, M, 1);
-    if ((rc = tp_sync_run(e, 0, M))) return rc;
+    if ((rc = off_sync_run(e, 0, M, 0))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->have_td3_pop = true;
     return ADC_OK;
@@ -287,34 +158,14 @@ ADC_EXPORT int adc_engine_td3_pop_set_critic_layer(adc_engine *e, int32_t member
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (critic != 0 && critic != 1) return fail(ADC_EINVAL, "critic: 0 or 1");
-    const adc::Td3Net &q = e->td3_shape.q;
-    if (layer < 0 || layer >= q.layers) return fail(ADC_EINVAL, "no such critic layer");
-    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
-    ENGINE_GUARD(e);
-    size_t off = (size_t)member * 2u * (size_t)e->td3_Qc + (size_t)critic * (size_t)e->td3_Qc;
-    for (int l = 0; l < layer; ++l) off += (size_t)(adc::td3_n_in(q, l) + 1) * (size_t)q.n_out[l];
-    const size_t nw = (size_t)adc::td3_n_in(q, layer) * (size_t)q.n_out[layer];
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off, weights_in_out, nw * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->td3_flat[kTd3Psi] + off + nw, bias_out, (size_t)q.n_out[layer] * 4, hipMemcpyHostToDevice, e->stream));
-    tp_params_copy(e, kTd3Psi, member, 1, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->tp_critic_set[((size_t)member * 2u + (size_t)critic) * adc::kMlpMaxLayers + (size_t)layer] = 1;
-    return ADC_OK;
+    return off_set_critic_layer(e, member, critic, layer, weights_in_out, bias_out);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_set_action_norm(adc_engine *e, const float *shift_a, const float *scale_a)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = tp_ready(e)) return rc;
-    if (!shift_a || !scale_a) return fail(ADC_EINVAL, "shift or scale is NULL");
-    ENGINE_GUARD(e);
-    HIP_TRY(hipMemcpyAsync(e->td3_a_shift, shift_a, (size_t)e->td3_shape.A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->td3_a_scale, scale_a, (size_t)e->td3_shape.A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_norm_set = true;
-    return ADC_OK;
+    return td3_action_norm_run(e, shift_a, scale_a);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_sync_targets(adc_engine *e, int32_t member)
@@ -323,7 +174,7 @@ ADC_EXPORT int adc_engine_td3_pop_sync_targets(adc_engine *e, int32_t member)
     int rc;
     if ((rc = tp_ready(e)) || (member != -1 && (rc = tp_member_check(e, member)))) return rc;
     ENGINE_GUARD(e);
-    if ((rc = member == -1 ? tp_sync_run(e, 0, e->lrn_M) : tp_sync_run(e, member, 1))) return rc;
+    if ((rc = member == -1 ? off_sync_run(e, 0, e->lrn_M, 0) : off_sync_run(e, member, 1, 0))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ADC_OK;
 }
@@ -332,34 +183,22 @@ ADC_EXPORT int adc_engine_td3_pop_store(adc_engine *e, int64_t *stored_per_membe
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = tp_ready(e)) || (rc = tp_state_check(e))) return rc;
-    if (e->ro_t <= e->td3_stored_t) return fail(ADC_ESTATE, "no unstored day in the record (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)");
-    if (e->td3_gap || e->env_moves != e->ro_moves)
-        return fail(ADC_ESTATE, "the envs were stepped or reset outside the record since an unstored recorded day: its next observation is not the "
-                                "one the envs hold (adc_engine_rollout_reset, collect again)");
+    if ((rc = tp_ready(e)) || (rc = tp_state_check(e)) || (rc = off_store_check(e))) return rc;
     ENGINE_GUARD(e);
-    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;
+    const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;      // (a member's envs, not the engine's)
+    // (raw rows under a running observation normaliser - TD3's set, e->tn)
     hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
                        e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
                        e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
                        (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
-    HIP_TRY(hipGetLastError());
-    if (e->per_live && (rc = per_store_run(e, e->td3_written, count))) return rc;
-    e->td3_written += count;
-    e->td3_stored_t = e->ro_t;
-    if (stored_per_member) *stored_per_member = count;
-    return ADC_OK;
+    return off_store_done(e, count, stored_per_member);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_buffer_info(adc_engine *e, int64_t *size, int64_t *written, int64_t *capacity, int32_t *batch_size)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = tp_ready(e)) return rc;
-    if (size) *size = td3_size(e);
-    if (written) *written = e->td3_written;
-    if (capacity) *capacity = e->td3_cfg.capacity;
-    if (batch_size) *batch_size = e->td3_cfg.batch_size;
-    return ADC_OK;
+    return off_buffer_info(e, size, written, capacity, batch_size);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_buffer_fetch(adc_engine *e, int32_t member, int64_t slot, int64_t count, float *x, float *a, float *r, uint8_t *done,
@@ -368,17 +207,7 @@ ADC_EXPORT int adc_engine_td3_pop_buffer_fetch(adc_engine *e, int32_t member, in
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (slot < 0 || count < 1 || slot > td3_size(e) - count) return fail(ADC_EINVAL, "the slot range is not inside [0, size)");
-    ENGINE_GUARD(e);
-    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-    const Td3Ring &g = e->tp_mem[(size_t)member].ring;
-    if (x) HIP_TRY(hipMemcpyAsync(x, g.x + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
-    if (a) HIP_TRY(hipMemcpyAsync(a, g.a + s * A, n * A * 4, hipMemcpyDeviceToHost, e->stream));
-    if (r) HIP_TRY(hipMemcpyAsync(r, g.r + s, n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (done) HIP_TRY(hipMemcpyAsync(done, g.done + s, n, hipMemcpyDeviceToHost, e->stream));
-    if (x2) HIP_TRY(hipMemcpyAsync(x2, g.x2 + s * D, n * D * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return off_ring_fetch(e, member, slot, count, x, a, r, done, x2);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_buffer_load(adc_engine *e, int32_t member, int64_t slot, int64_t count, const float *x, const float *a, const float *r,
@@ -387,24 +216,7 @@ ADC_EXPORT int adc_engine_td3_pop_buffer_load(adc_engine *e, int32_t member, int
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (!x || !a || !r || !done || !x2) return fail(ADC_EINVAL, "x, a, r, done or x2 is NULL");
-    if (slot < 0 || count < 1 || slot > (int64_t)e->td3_cfg.capacity - count) return fail(ADC_EINVAL, "the slot range is not inside [0, capacity)");
-    if (written < slot + count) return fail(ADC_EINVAL, "written: at least slot + count");
-    ENGINE_GUARD(e);
-    const size_t s = (size_t)slot, n = (size_t)count, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-    const Td3Ring &g = e->tp_mem[(size_t)member].ring;
-    HIP_TRY(hipMemcpyAsync(g.x + s * D, x, n * D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.a + s * A, a, n * A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.r + s, r, n * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.done + s, done, n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(g.x2 + s * D, x2, n * D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_written = written;               // (the members' rings move together: one count for all)
-    if (e->per_live) {
-        if ((rc = per_loaded_run(e, member, slot, count))) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return ADC_OK;
+    return off_ring_load(e, member, slot, count, x, a, r, done, x2, written);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_batch_indices(adc_engine *e, int32_t member, int64_t update, int32_t *idx_b)
@@ -412,67 +224,40 @@ ADC_EXPORT int adc_engine_td3_pop_batch_indices(adc_engine *e, int32_t member, i
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (!idx_b) return fail(ADC_EINVAL, "idx_b is NULL");
-    if (update < 0 || update >= 0xFFFFFFFFll) return fail(ADC_EINVAL, "update: 0 to 2^32 - 2");
-    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_td3_pop_store)");
-    if (e->per_live) return fail(ADC_ESTATE, "prioritised replay is alive on this engine: the batch is adc_engine_replay_prio_batch's, not the uniform law's");
-    ENGINE_GUARD(e);
-    const int B = e->td3_cfg.batch_size;
-    hipLaunchKernelGGL(k_td3_indices, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, e->tp_mem[(size_t)member].key, (uint32_t)update,
-                       (uint32_t)td3_size(e), B, e->td3_idx);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(idx_b, e->td3_idx, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return off_batch_indices(e, e->tp_mem[(size_t)member].key, update, idx_b, "the replay buffer is empty (adc_engine_td3_pop_store)");
 }
 
 ADC_EXPORT int adc_engine_td3_pop_update(adc_engine *e, int32_t updates, adc_td3_stats *stats_m)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = tp_ready(e)) || (rc = tp_state_check(e))) return rc;
-    if (updates < 1 || updates > 65536) return fail(ADC_EINVAL, "updates: 1 to 65536");
-    if (!tp_critics_set(e)) return fail(ADC_ESTATE, "a critic layer of a member has not been uploaded (adc_engine_td3_pop_set_critic_layer)");
-    if (td3_size(e) == 0) return fail(ADC_ESTATE, "the replay buffer is empty (adc_engine_td3_pop_store)");
-    if (e->td3_updates + updates >= 0xFFFFFFFFll) return fail(ADC_ESTATE, "the update counter is exhausted");
+    if ((rc = tp_ready(e)) || (rc = tp_state_check(e)) ||
+        (rc = off_update_check(e, updates, true, "a critic layer of a member has not been uploaded (adc_engine_td3_pop_set_critic_layer)",
+                               "the replay buffer is empty (adc_engine_td3_pop_store)", 0xFFFFFFFFll)))
+        return rc;
     ENGINE_GUARD(e);
     const int M = e->lrn_M, delay = e->td3_cfg.policy_delay;
     bool any_clip = false;
     for (const adc_td3_config &c : e->tp_cfg) any_clip = any_clip || c.max_grad_norm > 0.0f;
-    HIP_TRY(hipMemsetAsync(e->td3_sums, 0, (size_t)M * 16 * sizeof(double), e->stream));
-    for (int u0 = 0; u0 < updates; u0 += kTd3PopBlock) {
-        const int nb = std::min(kTd3PopBlock, updates - u0);
-        // the block's step constants (the Adam bias corrections of every step to come) in one copy; the host's table is free to
-        // write: the call before this one, and the block before this one, ended with a wait
-        if (u0 > 0) HIP_TRY(hipStreamSynchronize(e->stream));
-        int64_t actor_steps = e->td3_actor_steps;
-        for (int i = 0; i < nb; ++i) {
-            tp_steps_fill(e, 2 * i, false, e->td3_updates + i);
-            if ((e->td3_updates + i + 1) % delay == 0) tp_steps_fill(e, 2 * i + 1, true, actor_steps++);
-        }
-        HIP_TRY(hipMemcpyAsync(e->tp_dsteps, e->tp_steps.data(), (size_t)nb * 2u * (size_t)M * sizeof(Td3PopStep), hipMemcpyHostToDevice, e->stream));
-        for (int i = 0; i < nb; ++i) {
-            const int left = updates - 1 - (u0 + i);
+    rc = off_pop_updates(
+        e, updates, 2,
+        [&](int nb) {
+            int64_t actor_steps = e->td3_actor_steps;
+            for (int i = 0; i < nb; ++i) {
+                tp_steps_fill(e, 2 * i, false, e->td3_updates + i);
+                if ((e->td3_updates + i + 1) % delay == 0) tp_steps_fill(e, 2 * i + 1, true, actor_steps++);
+            }
+        },
+        [&](int u, int i) {
+            const int left = updates - 1 - u;
             // (the statistics' sums are taken for the call's last update and for its last actor step alone)
-            if ((rc = tp_one_update(e, i, stats_m != nullptr, left == 0, left < delay, any_clip))) return rc;
-        }
-    }
+            return tp_one_update(e, i, stats_m != nullptr, left == 0, left < delay, any_clip);
+        });
+    if (rc) return rc;
     if (stats_m) HIP_TRY(hipMemcpyAsync(e->tp_host_sums.data(), e->td3_sums, (size_t)M * 16 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (stats_m) {
-        const double n = (double)e->td3_cfg.batch_size;
-        for (int m = 0; m < M; ++m) {
-            const double *sums = e->tp_host_sums.data() + (size_t)m * 16;
-            adc_td3_stats *stats = stats_m + m;
-            const double l1 = sums[adc::kTd3Loss1] / n, l2 = sums[adc::kTd3Loss2] / n, qpi = sums[8] / n;
-            stats->updates = e->td3_updates; stats->actor_steps = e->td3_actor_steps; stats->buffer_size = td3_size(e); stats->samples = e->td3_cfg.batch_size;
-            stats->critic_loss = l1 + l2;
-            stats->q1_mean = sums[adc::kTd3Q1] / n; stats->q2_mean = sums[adc::kTd3Q2] / n; stats->y_mean = sums[adc::kTd3Y] / n;
-            stats->actor_loss = -qpi;
-            stats->critic_grad_norm = std::sqrt(sums[5]);
-            stats->actor_grad_norm = std::sqrt(sums[9]);
-        }
-    }
+    if (stats_m)
+        for (int m = 0; m < M; ++m) td3_stats_fill(e, e->tp_host_sums.data() + (size_t)m * 16, stats_m + m);
     return ADC_OK;
 }
 
@@ -480,9 +265,7 @@ ADC_EXPORT int adc_engine_td3_pop_param_counts(adc_engine *e, int64_t *actor_p, 
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (int rc = tp_ready(e)) return rc;
-    if (actor_p) *actor_p = e->td3_P;
-    if (critics_2qc) *critics_2qc = 2 * (int64_t)e->td3_Qc;
-    return ADC_OK;
+    return off_param_counts(e, actor_p, critics_2qc);
 }
 
 ADC_EXPORT int adc_engine_td3_pop_state_get(adc_engine *e, int32_t member, float *theta_p, float *psi_q, float *theta_target_p, float *psi_target_q,
@@ -492,13 +275,8 @@ ADC_EXPORT int adc_engine_td3_pop_state_get(adc_engine *e, int32_t member, float
     int rc;
     if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
     ENGINE_GUARD(e);
-    const size_t P = (size_t)e->td3_P, Q2 = 2 * (size_t)e->td3_Qc, mi = (size_t)member;
     float *flat[4] = {theta_p, psi_q, theta_target_p, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
-    for (int w = 0; w < 4; ++w) {
-        const size_t fq = (w & 1) ? Q2 : P, mq = w < 2 ? P : Q2;
-        if (flat[w]) HIP_TRY(hipMemcpyAsync(flat[w], e->td3_flat[w] + mi * fq, fq * 4, hipMemcpyDeviceToHost, e->stream));
-        if (mom[w]) HIP_TRY(hipMemcpyAsync(mom[w], e->td3_mom[w] + mi * mq, mq * 4, hipMemcpyDeviceToHost, e->stream));
-    }
+    if ((rc = off_state_get(e, member, flat, mom))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (updates) *updates = e->td3_updates;
     if (actor_steps) *actor_steps = e->td3_actor_steps;
@@ -510,23 +288,12 @@ ADC_EXPORT int adc_engine_td3_pop_state_set(adc_engine *e, int32_t member, const
                                             const float *v_psi_q, int64_t updates, int64_t actor_steps)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    int rc;
-    if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member))) return rc;
-    if (!theta_p || !psi_q || !theta_target_p || !psi_target_q || !m_theta_p || !v_theta_p || !m_psi_q || !v_psi_q) return fail(ADC_EINVAL, "a state vector is NULL");
-    if (updates < 0 || updates >= 0x7FFFFFFFll || actor_steps < 0 || actor_steps > updates) return fail(ADC_EINVAL, "updates: 0 to 2^31 - 2; actor_steps: 0 to updates");
-    ENGINE_GUARD(e);
-    const size_t P = (size_t)e->td3_P, Q2 = 2 * (size_t)e->td3_Qc, mi = (size_t)member;
     const float *flat[4] = {theta_p, psi_q, theta_target_p, psi_target_q}, *mom[4] = {m_theta_p, v_theta_p, m_psi_q, v_psi_q};
-    for (int w = 0; w < 4; ++w) {
-        const size_t fq = (w & 1) ? Q2 : P, mq = w < 2 ? P : Q2;
-        HIP_TRY(hipMemcpyAsync(e->td3_flat[w] + mi * fq, flat[w], fq * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->td3_mom[w] + mi * mq, mom[w], mq * 4, hipMemcpyHostToDevice, e->stream));
-        tp_params_copy(e, w, member, 1, 0);         // (the member's policy layers, critics and targets follow its flat vectors)
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->td3_updates = updates; e->td3_actor_steps = actor_steps;         // (the members move together: one pair of counters for all)
-    for (size_t i = 0; i < 2u * adc::kMlpMaxLayers; ++i) e->tp_critic_set[mi * 2u * adc::kMlpMaxLayers + i] = 1;
+    int rc;
+    if ((rc = tp_ready(e)) || (rc = tp_member_check(e, member)) || (rc = td3_state_set_check(flat, mom, updates, actor_steps))) return rc;
+    ENGINE_GUARD(e);
+    if ((rc = off_state_set(e, member, flat, mom, updates))) return rc;
+    e->td3_actor_steps = actor_steps;       // (the members move together: one pair of counters for all)
     return ADC_OK;
 }
 
@@ -556,26 +323,5 @@ ADC_EXPORT int adc_engine_td3_pop_copy(adc_engine *e, int32_t src, int32_t dst, 
     if ((rc = tp_ready(e)) || (rc = tp_member_check(e, src)) || (rc = tp_member_check(e, dst))) return rc;
     if (src == dst) return ADC_OK;
     ENGINE_GUARD(e);
-    const size_t P = (size_t)e->td3_P, Q2 = 2 * (size_t)e->td3_Qc, from = (size_t)src, to = (size_t)dst;
-    for (int w = 0; w < 4; ++w) {
-        const size_t fq = (w & 1) ? Q2 : P, mq = w < 2 ? P : Q2;
-        HIP_TRY(hipMemcpyAsync(e->td3_flat[w] + to * fq, e->td3_flat[w] + from * fq, fq * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->td3_mom[w] + to * mq, e->td3_mom[w] + from * mq, mq * 4, hipMemcpyDeviceToDevice, e->stream));
-        tp_params_copy(e, w, dst, 1, 0);
-    }
-    HIP_TRY(hipGetLastError());
-    if (with_ring) {
-        const size_t C = (size_t)e->td3_cfg.capacity, D = (size_t)e->td3_shape.D, A = (size_t)e->td3_shape.A;
-        const Td3Ring &s = e->tp_mem[from].ring, &d = e->tp_mem[to].ring;
-        HIP_TRY(hipMemcpyAsync(d.x, s.x, C * D * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.a, s.a, C * A * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.r, s.r, C * 4, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.done, s.done, C, hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(d.x2, s.x2, C * D * 4, hipMemcpyDeviceToDevice, e->stream));
-        if (e->per_live && (rc = per_copy_run(e, src, dst))) return rc;     // (the leaves, nodes and top travel with the ring)
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const size_t per = 2u * adc::kMlpMaxLayers;
-    for (size_t i = 0; i < per; ++i) e->tp_critic_set[to * per + i] = e->tp_critic_set[from * per + i];
-    return ADC_OK;
+    return off_pop_copy(e, src, dst, with_ring);
 }

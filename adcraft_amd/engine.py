@@ -1047,7 +1047,104 @@ class StepEngine:
         out = [{k: getattr(x, k) for k, _ in _ffi.PGShuffleStats._fields_} for x in st]
         return out if getattr(self, "_learners", 0) else out[0]
 
-    # ---- off-policy (TD3) training over a replay ring filled from the record (parts/kernel_td3.inc; baselines/td3_trainer.py) ----
+    # ---- what the four off-policy front ends share (parts/offpolicy_core.inc).  `prefix`: td3, sac, td3_pop or sac_pop - the family of
+    # the entry points and the public method's name in a message; `member`: a population's member, None for the solo trainers ----------
+    def _off(self, prefix, name):
+        return getattr(self._lib, f"adc_engine_{prefix}_{name}")
+
+    def _off_set_critics(self, prefix, member, critics, action_norm, sync_targets):
+        if len(critics) != 2:
+            raise ValueError(f"{prefix}_set_critics: two critics")
+        m = () if member is None else (int(member),)
+        for i, layers in enumerate(critics):
+            for l, (w, b) in enumerate(layers):
+                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+                check(self._off(prefix, "set_critic_layer")(self._h, *m, i, l, w.ctypes.data, b.ctypes.data))
+        if action_norm is not None:
+            sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in action_norm)
+            if sh.shape != (self.num_keywords + 1,) or sc.shape != sh.shape:
+                raise ValueError("action_norm: shift and scale of K + 1 entries")
+            check(self._off(prefix, "set_action_norm")(self._h, sh.ctypes.data, sc.ctypes.data))
+        if sync_targets:
+            check(self._off(prefix, "sync_targets")(self._h, *m))
+
+    def _off_store(self, prefix):
+        n = C.c_int64(0)
+        check(self._off(prefix, "store")(self._h, C.byref(n)))
+        return n.value
+
+    def _off_buffer(self, prefix, member, fetch):
+        pop = prefix.endswith("_pop")          # (the populations' buffer_info has the batch size; they fetch a member's ring alone)
+        sz, wr, cap, b = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(self._off(prefix, "buffer_info")(self._h, C.byref(sz), C.byref(wr), C.byref(cap), *((C.byref(b),) if pop else ())))
+        st = dict(size=sz.value, written=wr.value, capacity=cap.value, **(dict(batch_size=b.value) if pop else {}))
+        if fetch and (member is not None or not pop):
+            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
+            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
+                      x2=np.zeros((n, D), np.float32))
+            if n:
+                m = (int(member),) if pop else ()
+                check(self._off(prefix, "buffer_fetch")(self._h, *m, 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
+            st["done"] = st["done"].astype(bool)
+        return st
+
+    def _off_buffer_load(self, prefix, member, buf, slot, written):
+        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
+        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
+        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
+        n = r.shape[0]
+        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
+            raise ValueError(f"{prefix}_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
+        if written is None:
+            written = buf.get("written", slot + n)
+        m = () if member is None else (int(member),)
+        check(self._off(prefix, "buffer_load")(self._h, *m, int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data, x2.ctypes.data,
+                                               int(written)))
+
+    def _off_batch_indices(self, prefix, member, update):
+        if member is None:
+            b = C.c_int32(0)
+            check(self._off(prefix, "batch_size")(self._h, C.byref(b)))       # (the engine says how many slots it will write)
+            size, m = b.value, ()
+        else:
+            size, m = self._off_buffer(prefix, None, False)["batch_size"], (int(member),)
+        idx = np.zeros(size, np.int32)
+        check(self._off(prefix, "batch_indices")(self._h, *m, int(update), idx.ctypes.data))
+        return idx
+
+    def _off_update(self, prefix, stats_type, updates, members=None):
+        """members None: one learner, its statistics dict; 0: a population, nothing fetched; M: a list of M dicts"""
+        if members == 0:
+            check(self._off(prefix, "update")(self._h, int(updates), None))
+            return None
+        st = stats_type() if members is None else (stats_type * members)()
+        check(self._off(prefix, "update")(self._h, int(updates), C.byref(st) if members is None else st))
+        out = [{k: getattr(x, k) for k, _ in stats_type._fields_} for x in ([st] if members is None else st)]
+        return out[0] if members is None else out
+
+    def _off_param_counts(self, prefix):
+        p, q = C.c_int64(0), C.c_int64(0)
+        check(self._off(prefix, "param_counts")(self._h, C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    def _off_state(self, prefix, names, member, state, counters):
+        """names: the state's vectors in the entry points' order (TD3_STATE, SAC_STATE); counters: the integers after them"""
+        P, Q = self._off_param_counts(prefix)
+        size = lambda k: 3 if k == "log_alpha" else Q if "psi" in k else P
+        m = () if member is None else (int(member),)
+        if state is None:
+            st = {k: np.zeros(size(k), np.float32) for k in names}
+            got = [C.c_int64(0) for _ in counters]
+            check(self._off(prefix, "state_get")(self._h, *m, *(st[k].ctypes.data for k in names), *(C.byref(c) for c in got)))
+            st.update((k, c.value) for k, c in zip(counters, got))
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in names]
+        if any(a.shape != (size(k),) for k, a in zip(names, arr)):
+            raise ValueError(f"{prefix}_state: the actor's vectors have {P} entries, the critics' {Q}" + (", log_alpha 3" if "log_alpha" in names else ""))
+        check(self._off(prefix, "state_set")(self._h, *m, *(a.ctypes.data for a in arr), *(int(state[k]) for k in counters)))
+
+    # ---- off-policy (TD3) training over a replay ring filled from the record (parts/kernel_td3.inc, parts/td3_api.inc;
+    # baselines/td3_trainer.py): the configuration and the init are TD3's, the rest wrappers of the _off_* helpers ----
     TD3_OPTIMISERS = {"adam": _ffi.TD3_ADAM, "sgd": _ffi.TD3_SGD}
 
     @classmethod
@@ -1085,96 +1182,45 @@ class StepEngine:
     def td3_set_critics(self, critics, action_norm=None, sync_targets=True):
         """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs; action_norm: (shift, scale) [A]
         for the critics' action inputs; sync_targets: the targets become copies of the actor and the critics"""
-        if len(critics) != 2:
-            raise ValueError("td3_set_critics: two critics")
-        for i, layers in enumerate(critics):
-            for l, (w, b) in enumerate(layers):
-                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-                check(self._lib.adc_engine_td3_set_critic_layer(self._h, i, l, w.ctypes.data, b.ctypes.data))
-        if action_norm is not None:
-            sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in action_norm)
-            if sh.shape != (self.num_keywords + 1,) or sc.shape != sh.shape:
-                raise ValueError("action_norm: shift and scale of K + 1 entries")
-            check(self._lib.adc_engine_td3_set_action_norm(self._h, sh.ctypes.data, sc.ctypes.data))
-        if sync_targets:
-            check(self._lib.adc_engine_td3_sync_targets(self._h))
+        self._off_set_critics("td3", None, critics, action_norm, sync_targets)
 
     def td3_sync_targets(self):
         check(self._lib.adc_engine_td3_sync_targets(self._h))
 
     def td3_store(self):
         """the record's days not yet stored, into the ring; returns the transitions appended"""
-        n = C.c_int64(0)
-        check(self._lib.adc_engine_td3_store(self._h, C.byref(n)))
-        return n.value
+        return self._off_store("td3")
 
     def td3_buffer(self, fetch=True):
         """dict of size, written, capacity and (fetch=True) the ring's slots [0, size): x [size, D], a [size, A], r [size],
         done [size] (bool), x2 [size, D]"""
-        sz, wr, cap = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(self._lib.adc_engine_td3_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap)))
-        st = dict(size=sz.value, written=wr.value, capacity=cap.value)
-        if fetch:
-            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
-            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
-                      x2=np.zeros((n, D), np.float32))
-            if n:
-                check(self._lib.adc_engine_td3_buffer_fetch(self._h, 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
-            st["done"] = st["done"].astype(bool)
-        return st
+        return self._off_buffer("td3", None, fetch)
 
     def td3_buffer_load(self, buf, slot=0, written=None):
         """the arrays of a td3_buffer() dict (or one of its kind) into the slots from `slot` on; written (default: the dict's, or
         slot + the count) becomes the ring's count of transitions stored so far"""
-        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
-        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
-        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
-        n = r.shape[0]
-        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
-            raise ValueError("td3_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
-        if written is None:
-            written = buf.get("written", slot + n)
-        check(self._lib.adc_engine_td3_buffer_load(self._h, int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data, x2.ctypes.data,
-                                                   int(written)))
+        self._off_buffer_load("td3", None, buf, slot, written)
 
     def td3_batch_indices(self, update):
         """the ring slots update number `update` reads at the ring's current size: [batch_size] int32"""
-        b = C.c_int32(0)
-        check(self._lib.adc_engine_td3_batch_size(self._h, C.byref(b)))       # (the engine says how many slots it will write)
-        idx = np.zeros(b.value, np.int32)
-        check(self._lib.adc_engine_td3_batch_indices(self._h, int(update), idx.ctypes.data))
-        return idx
+        return self._off_batch_indices("td3", None, update)
 
     def td3_update(self, updates=1):
         """`updates` critic updates and the delayed actor / target steps among them; the statistics of the last"""
-        st = _ffi.TD3Stats()
-        check(self._lib.adc_engine_td3_update(self._h, int(updates), C.byref(st)))
-        return {k: getattr(st, k) for k, _ in _ffi.TD3Stats._fields_}
+        return self._off_update("td3", _ffi.TD3Stats, updates)
 
     def td3_param_counts(self):
-        p, q = C.c_int64(0), C.c_int64(0)
-        check(self._lib.adc_engine_td3_param_counts(self._h, C.byref(p), C.byref(q)))
-        return p.value, q.value
+        return self._off_param_counts("td3")
 
     TD3_STATE = ("theta", "psi", "theta_target", "psi_target", "m_theta", "v_theta", "m_psi", "v_psi")
 
     def td3_state(self, state=None):
         """get (no argument): dict of theta, theta_target, m_theta, v_theta [P], psi, psi_target, m_psi, v_psi [2 Qc] float32,
         updates and actor_steps; set: such a dict - with the ring (td3_buffer / td3_buffer_load) the run continues bit for bit"""
-        P, Q = self.td3_param_counts()
-        size = lambda k: Q if "psi" in k else P
-        if state is None:
-            st = {k: np.zeros(size(k), np.float32) for k in self.TD3_STATE}
-            u, a = C.c_int64(0), C.c_int64(0)
-            check(self._lib.adc_engine_td3_state_get(self._h, *(st[k].ctypes.data for k in self.TD3_STATE), C.byref(u), C.byref(a)))
-            st["updates"], st["actor_steps"] = u.value, a.value
-            return st
-        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.TD3_STATE]
-        if any(a.shape != (size(k),) for k, a in zip(self.TD3_STATE, arr)):
-            raise ValueError(f"td3_state: the actor's vectors have {P} entries, the critics' {Q}")
-        check(self._lib.adc_engine_td3_state_set(self._h, *(a.ctypes.data for a in arr), int(state["updates"]), int(state["actor_steps"])))
+        return self._off_state("td3", self.TD3_STATE, None, state, ("updates", "actor_steps"))
 
-    # ---- soft actor-critic over the same replay ring (parts/kernel_sac.inc, parts/sac_api.inc; baselines/sac_trainer.py) ----------
+    # ---- soft actor-critic over the same replay ring (parts/kernel_sac.inc, parts/sac_api.inc; baselines/sac_trainer.py): as TD3's,
+    # wrappers of the _off_* helpers around SAC's own configuration and init ----------
     @classmethod
     def sac_config(cls, gamma=0.99, tau=0.005, target_update_interval=1, init_alpha=1.0, target_entropy=None, alpha_lr=3e-4, eps_sq=1e-6,
                    reward_scale=1.0, batch_size=256, capacity=100000, critic_widths=(256, 256, 1), actor_lr=3e-4, critic_lr=3e-4,
@@ -1216,69 +1262,33 @@ class StepEngine:
     def sac_set_critics(self, critics, sync_targets=True):
         """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs [x | tanh(u)]; sync_targets: the
         target critics become copies of the critics"""
-        if len(critics) != 2:
-            raise ValueError("sac_set_critics: two critics")
-        for i, layers in enumerate(critics):
-            for l, (w, b) in enumerate(layers):
-                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-                check(self._lib.adc_engine_sac_set_critic_layer(self._h, i, l, w.ctypes.data, b.ctypes.data))
-        if sync_targets:
-            check(self._lib.adc_engine_sac_sync_targets(self._h))
+        self._off_set_critics("sac", None, critics, None, sync_targets)
 
     def sac_sync_targets(self):
         check(self._lib.adc_engine_sac_sync_targets(self._h))
 
     def sac_store(self):
         """the record's days not yet stored, into the ring; returns the transitions appended"""
-        n = C.c_int64(0)
-        check(self._lib.adc_engine_sac_store(self._h, C.byref(n)))
-        return n.value
+        return self._off_store("sac")
 
     def sac_buffer(self, fetch=True):
         """as td3_buffer: a holds the unsquashed actions u"""
-        sz, wr, cap = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(self._lib.adc_engine_sac_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap)))
-        st = dict(size=sz.value, written=wr.value, capacity=cap.value)
-        if fetch:
-            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
-            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
-                      x2=np.zeros((n, D), np.float32))
-            if n:
-                check(self._lib.adc_engine_sac_buffer_fetch(self._h, 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
-            st["done"] = st["done"].astype(bool)
-        return st
+        return self._off_buffer("sac", None, fetch)
 
     def sac_buffer_load(self, buf, slot=0, written=None):
         """as td3_buffer_load"""
-        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
-        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
-        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
-        n = r.shape[0]
-        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
-            raise ValueError("sac_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
-        if written is None:
-            written = buf.get("written", slot + n)
-        check(self._lib.adc_engine_sac_buffer_load(self._h, int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data, x2.ctypes.data,
-                                                   int(written)))
+        self._off_buffer_load("sac", None, buf, slot, written)
 
     def sac_batch_indices(self, update):
         """the ring slots update number `update` reads at the ring's current size: [batch_size] int32"""
-        b = C.c_int32(0)
-        check(self._lib.adc_engine_sac_batch_size(self._h, C.byref(b)))       # (the engine says how many slots it will write)
-        idx = np.zeros(b.value, np.int32)
-        check(self._lib.adc_engine_sac_batch_indices(self._h, int(update), idx.ctypes.data))
-        return idx
+        return self._off_batch_indices("sac", None, update)
 
     def sac_update(self, updates=1):
         """`updates` updates (critics, actor, temperature, targets); the statistics of the last"""
-        st = _ffi.SACStats()
-        check(self._lib.adc_engine_sac_update(self._h, int(updates), C.byref(st)))
-        return {k: getattr(st, k) for k, _ in _ffi.SACStats._fields_}
+        return self._off_update("sac", _ffi.SACStats, updates)
 
     def sac_param_counts(self):
-        p, q = C.c_int64(0), C.c_int64(0)
-        check(self._lib.adc_engine_sac_param_counts(self._h, C.byref(p), C.byref(q)))
-        return p.value, q.value
+        return self._off_param_counts("sac")
 
     SAC_STATE = ("theta", "psi", "psi_target", "m_theta", "v_theta", "m_psi", "v_psi", "log_alpha")
 
@@ -1286,20 +1296,10 @@ class StepEngine:
         """get (no argument): dict of theta, m_theta, v_theta [P], psi, psi_target, m_psi, v_psi [2 Qc], log_alpha [3] (log_alpha and
         its two moments) float32, and updates; set: such a dict - with the ring (sac_buffer / sac_buffer_load) the run continues bit
         for bit"""
-        P, Q = self.sac_param_counts()
-        size = lambda k: 3 if k == "log_alpha" else Q if "psi" in k else P
-        if state is None:
-            st = {k: np.zeros(size(k), np.float32) for k in self.SAC_STATE}
-            u = C.c_int64(0)
-            check(self._lib.adc_engine_sac_state_get(self._h, *(st[k].ctypes.data for k in self.SAC_STATE), C.byref(u)))
-            st["updates"] = u.value
-            return st
-        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.SAC_STATE]
-        if any(a.shape != (size(k),) for k, a in zip(self.SAC_STATE, arr)):
-            raise ValueError(f"sac_state: the actor's vectors have {P} entries, the critics' {Q}, log_alpha 3")
-        check(self._lib.adc_engine_sac_state_set(self._h, *(a.ctypes.data for a in arr), int(state["updates"])))
+        return self._off_state("sac", self.SAC_STATE, None, state, ("updates",))
 
-    # ---- TD3 learner populations: M off-policy learners in lock-step (parts/td3_pop_api.inc; baselines/td3_trainer.py TD3PopulationTrainer) ----
+    # ---- TD3 learner populations: M off-policy learners in lock-step (parts/td3_pop_api.inc; baselines/td3_trainer.py
+    # TD3PopulationTrainer): the _off_* helpers with a member; set_config and copy are the populations' own ----
     @classmethod
     def td3_pop_configs(cls, configs, num_envs, members):
         """(ctypes array, count) from one dict of td3_config's options or `members` of them, checked by adc_td3_pop_config_check"""
@@ -1326,19 +1326,7 @@ class StepEngine:
     def td3_pop_set_critics(self, member, critics, action_norm=None, sync_targets=True):
         """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs); action_norm: (shift, scale) [A],
         shared by all members; sync_targets: the member's targets become copies of its actor and critics"""
-        if len(critics) != 2:
-            raise ValueError("td3_pop_set_critics: two critics")
-        for i, layers in enumerate(critics):
-            for l, (w, b) in enumerate(layers):
-                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-                check(self._lib.adc_engine_td3_pop_set_critic_layer(self._h, int(member), i, l, w.ctypes.data, b.ctypes.data))
-        if action_norm is not None:
-            sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in action_norm)
-            if sh.shape != (self.num_keywords + 1,) or sc.shape != sh.shape:
-                raise ValueError("action_norm: shift and scale of K + 1 entries")
-            check(self._lib.adc_engine_td3_pop_set_action_norm(self._h, sh.ctypes.data, sc.ctypes.data))
-        if sync_targets:
-            check(self._lib.adc_engine_td3_pop_sync_targets(self._h, int(member)))
+        self._off_set_critics("td3_pop", member, critics, action_norm, sync_targets)
 
     def td3_pop_sync_targets(self, member=None):
         """member None: every member's targets"""
@@ -1346,75 +1334,34 @@ class StepEngine:
 
     def td3_pop_store(self):
         """the record's days not yet stored, into every member's ring; returns the transitions each member appended"""
-        n = C.c_int64(0)
-        check(self._lib.adc_engine_td3_pop_store(self._h, C.byref(n)))
-        return n.value
+        return self._off_store("td3_pop")
 
     def td3_pop_buffer(self, member=None, fetch=True):
         """dict of size, written, capacity, batch_size (the members' rings move together) and - for a member, fetch=True - its
         ring's slots [0, size) as td3_buffer's"""
-        sz, wr, cap, b = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        check(self._lib.adc_engine_td3_pop_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap), C.byref(b)))
-        st = dict(size=sz.value, written=wr.value, capacity=cap.value, batch_size=b.value)
-        if fetch and member is not None:
-            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
-            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
-                      x2=np.zeros((n, D), np.float32))
-            if n:
-                check(self._lib.adc_engine_td3_pop_buffer_fetch(self._h, int(member), 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
-            st["done"] = st["done"].astype(bool)
-        return st
+        return self._off_buffer("td3_pop", member, fetch)
 
     def td3_pop_buffer_load(self, member, buf, slot=0, written=None):
         """the arrays of a td3_pop_buffer(member) dict (or one of its kind) into the member's slots from `slot` on; written
         becomes the count of transitions stored so far of every member's ring"""
-        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
-        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
-        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
-        n = r.shape[0]
-        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
-            raise ValueError("td3_pop_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
-        if written is None:
-            written = buf.get("written", slot + n)
-        check(self._lib.adc_engine_td3_pop_buffer_load(self._h, int(member), int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data,
-                                                       x2.ctypes.data, int(written)))
+        self._off_buffer_load("td3_pop", member, buf, slot, written)
 
     def td3_pop_batch_indices(self, member, update):
         """the slots of the member's ring its update number `update` reads at the ring's current size: [batch_size] int32"""
-        idx = np.zeros(self.td3_pop_buffer(fetch=False)["batch_size"], np.int32)
-        check(self._lib.adc_engine_td3_pop_batch_indices(self._h, int(member), int(update), idx.ctypes.data))
-        return idx
+        return self._off_batch_indices("td3_pop", member, update)
 
     def td3_pop_update(self, updates=1, stats=True):
         """`updates` critic updates of every member and the delayed actor / target steps among them, all members in the same
         launches; a list of M statistics dicts (stats=False: None, and the call fetches nothing)"""
-        if not stats:
-            check(self._lib.adc_engine_td3_pop_update(self._h, int(updates), None))
-            return None
-        st = (_ffi.TD3Stats * self._td3_pop_members())()
-        check(self._lib.adc_engine_td3_pop_update(self._h, int(updates), st))
-        return [{k: getattr(x, k) for k, _ in _ffi.TD3Stats._fields_} for x in st]
+        return self._off_update("td3_pop", _ffi.TD3Stats, updates, self._td3_pop_members() if stats else 0)
 
     def td3_pop_param_counts(self):
         """(P, 2 Qc): the entries of a member's actor vectors and of its critics' vectors"""
-        p, q = C.c_int64(0), C.c_int64(0)
-        check(self._lib.adc_engine_td3_pop_param_counts(self._h, C.byref(p), C.byref(q)))
-        return p.value, q.value
+        return self._off_param_counts("td3_pop")
 
     def td3_pop_state(self, member, state=None):
         """one member's state as td3_state's (the counters are the population's).  get (no state): the dict; set: such a dict"""
-        P, Q = self.td3_pop_param_counts()
-        size = lambda k: Q if "psi" in k else P
-        if state is None:
-            st = {k: np.zeros(size(k), np.float32) for k in self.TD3_STATE}
-            u, a = C.c_int64(0), C.c_int64(0)
-            check(self._lib.adc_engine_td3_pop_state_get(self._h, int(member), *(st[k].ctypes.data for k in self.TD3_STATE), C.byref(u), C.byref(a)))
-            st["updates"], st["actor_steps"] = u.value, a.value
-            return st
-        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.TD3_STATE]
-        if any(a.shape != (size(k),) for k, a in zip(self.TD3_STATE, arr)):
-            raise ValueError(f"td3_pop_state: the actor's vectors have {P} entries, the critics' {Q}")
-        check(self._lib.adc_engine_td3_pop_state_set(self._h, int(member), *(a.ctypes.data for a in arr), int(state["updates"]), int(state["actor_steps"])))
+        return self._off_state("td3_pop", self.TD3_STATE, member, state, ("updates", "actor_steps"))
 
     def td3_pop_set_config(self, member, **options):
         """a member's hyperparameters from the next update on (options as td3_config's; the shared fields may not change)"""
@@ -1426,7 +1373,8 @@ class StepEngine:
         dst keeps its configuration, envs and exploration"""
         check(self._lib.adc_engine_td3_pop_copy(self._h, int(src), int(dst), 1 if with_ring else 0))
 
-    # ---- SAC learner populations: M soft actor-critic learners in lock-step (parts/sac_pop_api.inc; baselines/sac_trainer.py SACPopulationTrainer) ----
+    # ---- SAC learner populations: M soft actor-critic learners in lock-step (parts/sac_pop_api.inc; baselines/sac_trainer.py
+    # SACPopulationTrainer): the _off_* helpers with a member; set_config and copy are the populations' own ----
     @classmethod
     def sac_pop_configs(cls, configs, num_envs, members, num_keywords=None):
         """(ctypes array, count) from one dict of sac_config's options or `members` of them, checked by adc_sac_pop_config_check"""
@@ -1451,14 +1399,7 @@ class StepEngine:
     def sac_pop_set_critics(self, member, critics, sync_targets=True):
         """one member's two critics (lists of (W [n_in, n_out], b [n_out]) on the D + A inputs [x | tanh(u)]); sync_targets: the
         member's target critics become copies of its critics"""
-        if len(critics) != 2:
-            raise ValueError("sac_pop_set_critics: two critics")
-        for i, layers in enumerate(critics):
-            for l, (w, b) in enumerate(layers):
-                w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-                check(self._lib.adc_engine_sac_pop_set_critic_layer(self._h, int(member), i, l, w.ctypes.data, b.ctypes.data))
-        if sync_targets:
-            check(self._lib.adc_engine_sac_pop_sync_targets(self._h, int(member)))
+        self._off_set_critics("sac_pop", member, critics, None, sync_targets)
 
     def sac_pop_sync_targets(self, member=None):
         """member None: every member's target critics"""
@@ -1466,76 +1407,35 @@ class StepEngine:
 
     def sac_pop_store(self):
         """the record's days not yet stored, into every member's ring; returns the transitions each member appended"""
-        n = C.c_int64(0)
-        check(self._lib.adc_engine_sac_pop_store(self._h, C.byref(n)))
-        return n.value
+        return self._off_store("sac_pop")
 
     def sac_pop_buffer(self, member=None, fetch=True):
         """dict of size, written, capacity, batch_size (the members' rings move together) and - for a member, fetch=True - its
         ring's slots [0, size) as sac_buffer's (a holds the unsquashed actions u)"""
-        sz, wr, cap, b = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        check(self._lib.adc_engine_sac_pop_buffer_info(self._h, C.byref(sz), C.byref(wr), C.byref(cap), C.byref(b)))
-        st = dict(size=sz.value, written=wr.value, capacity=cap.value, batch_size=b.value)
-        if fetch and member is not None:
-            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
-            st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
-                      x2=np.zeros((n, D), np.float32))
-            if n:
-                check(self._lib.adc_engine_sac_pop_buffer_fetch(self._h, int(member), 0, n, *(st[k].ctypes.data for k in ("x", "a", "r", "done", "x2"))))
-            st["done"] = st["done"].astype(bool)
-        return st
+        return self._off_buffer("sac_pop", member, fetch)
 
     def sac_pop_buffer_load(self, member, buf, slot=0, written=None):
         """the arrays of a sac_pop_buffer(member) dict (or one of its kind) into the member's slots from `slot` on; written
         becomes the count of transitions stored so far of every member's ring"""
-        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
-        x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
-        done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
-        n = r.shape[0]
-        if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
-            raise ValueError("sac_pop_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
-        if written is None:
-            written = buf.get("written", slot + n)
-        check(self._lib.adc_engine_sac_pop_buffer_load(self._h, int(member), int(slot), n, x.ctypes.data, a.ctypes.data, r.ctypes.data, done.ctypes.data,
-                                                       x2.ctypes.data, int(written)))
+        self._off_buffer_load("sac_pop", member, buf, slot, written)
 
     def sac_pop_batch_indices(self, member, update):
         """the slots of the member's ring its update number `update` reads at the ring's current size: [batch_size] int32"""
-        idx = np.zeros(self.sac_pop_buffer(fetch=False)["batch_size"], np.int32)
-        check(self._lib.adc_engine_sac_pop_batch_indices(self._h, int(member), int(update), idx.ctypes.data))
-        return idx
+        return self._off_batch_indices("sac_pop", member, update)
 
     def sac_pop_update(self, updates=1, stats=True):
         """`updates` updates (critics, actor, temperature, targets) of every member, all members in the same launches; a list of
         M statistics dicts of the last (stats=False: None, and the call fetches nothing)"""
-        if not stats:
-            check(self._lib.adc_engine_sac_pop_update(self._h, int(updates), None))
-            return None
-        st = (_ffi.SACStats * self._td3_pop_members())()
-        check(self._lib.adc_engine_sac_pop_update(self._h, int(updates), st))
-        return [{k: getattr(x, k) for k, _ in _ffi.SACStats._fields_} for x in st]
+        return self._off_update("sac_pop", _ffi.SACStats, updates, self._td3_pop_members() if stats else 0)
 
     def sac_pop_param_counts(self):
         """(P, 2 Qc): the entries of a member's actor vectors and of its critics' vectors"""
-        p, q = C.c_int64(0), C.c_int64(0)
-        check(self._lib.adc_engine_sac_pop_param_counts(self._h, C.byref(p), C.byref(q)))
-        return p.value, q.value
+        return self._off_param_counts("sac_pop")
 
     def sac_pop_state(self, member, state=None):
         """one member's state as sac_state's, log_alpha [3] its temperature cell's (the counter is the population's).  get (no
         state): the dict; set: such a dict"""
-        P, Q = self.sac_pop_param_counts()
-        size = lambda k: 3 if k == "log_alpha" else Q if "psi" in k else P
-        if state is None:
-            st = {k: np.zeros(size(k), np.float32) for k in self.SAC_STATE}
-            u = C.c_int64(0)
-            check(self._lib.adc_engine_sac_pop_state_get(self._h, int(member), *(st[k].ctypes.data for k in self.SAC_STATE), C.byref(u)))
-            st["updates"] = u.value
-            return st
-        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in self.SAC_STATE]
-        if any(a.shape != (size(k),) for k, a in zip(self.SAC_STATE, arr)):
-            raise ValueError(f"sac_pop_state: the actor's vectors have {P} entries, the critics' {Q}, log_alpha 3")
-        check(self._lib.adc_engine_sac_pop_state_set(self._h, int(member), *(a.ctypes.data for a in arr), int(state["updates"])))
+        return self._off_state("sac_pop", self.SAC_STATE, member, state, ("updates",))
 
     def sac_pop_set_config(self, member, **options):
         """a member's hyperparameters from the next update on (options as sac_config's; the shared fields may not change, and

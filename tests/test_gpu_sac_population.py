@@ -680,3 +680,80 @@ def test_lds_overflow_is_refused(amd):
         e.sac_pop_init(dict(critic_widths=(256, 256, 256, 1), batch_size=8, capacity=16))
     e.mlp_act(10.0)                                                    # the engine stays usable
     e.close()
+
+
+def test_wrapped_member_rings_reloaded_at_a_slot_continue_bit_for_bit_and_the_shared_refusals_say_why(amd):
+    """the smallest population whose store wraps the rings (2 members x 2 envs x 3 days into 5 slots): every member's state and
+    ring - the ring loaded in two pieces, the second at slot 2 - carry a fresh engine through two more updates to the bits of the
+    uninterrupted run; then every refusal the off-policy front ends share, by its words, and the engine goes on"""
+    from adcraft_amd import _ffi
+    members, envs, days = 2, 4, 3
+    pols, crits = _members(7, members, widths=(8, 1))
+    opts = _options(5, members, critic_widths=(8, 1), batch_size=4)
+    fresh = lambda: _population(amd, pols, crits, opts, planes=_planes(envs), horizon=days)
+    a = fresh()
+    a.run_days("mlp", days, BUDGET)
+    assert a.sac_pop_store() == 6
+    a.sac_pop_update(1)
+    states, rings = [a.sac_pop_state(m) for m in range(members)], [a.sac_pop_buffer(m) for m in range(members)]
+    assert all((g["size"], g["written"], g["capacity"], g["batch_size"]) == (5, 6, 5, 4) for g in rings)
+    assert not _same(rings[0]["x"], rings[1]["x"])
+    b = fresh()
+    part = lambda g, lo, hi: {k: g[k][lo:hi] for k in ("x", "a", "r", "done", "x2")}
+    for m in range(members):
+        b.sac_pop_buffer_load(m, part(rings[m], 0, 2))
+        b.sac_pop_buffer_load(m, part(rings[m], 2, 5), slot=2, written=6)
+        b.sac_pop_state(m, states[m])
+    assert b.sac_pop_param_counts() == a.sac_pop_param_counts()
+    for m in range(members):
+        _assert_buffer(b.sac_pop_buffer(m), rings[m], m)
+        _assert_state(b.sac_pop_state(m), states[m], m)
+        assert _same(a.sac_pop_batch_indices(m, 1), b.sac_pop_batch_indices(m, 1)) and a.sac_pop_batch_indices(m, 1).shape == (4,)
+    for sa, sb in zip(a.sac_pop_update(2), b.sac_pop_update(2)):
+        _assert_stats(sb, sa)
+    for m in range(members):
+        _assert_state(b.sac_pop_state(m), a.sac_pop_state(m), m)
+    assert b.sac_pop_state(0)["updates"] == 3
+    a.close()
+    lib, h, p = b._lib, b._h, lambda v: v.ctypes.data
+    x, ac, r, dn = np.zeros((4, D), F), np.zeros((4, A), F), np.zeros(4, F), np.zeros(4, np.uint8)
+    (w, bias), idx = crits[0][0][0], np.zeros(4, np.int32)
+    last = [b.sac_pop_state(m) for m in range(members)]
+    vec = [p(last[1][k]) for k in amd.StepEngine.SAC_STATE]
+    refused = (
+        (r"no such member", lambda: lib.adc_engine_sac_pop_buffer_fetch(h, 2, 0, 1, p(x), p(ac), p(r), p(dn), p(x))),
+        (r"no such member", lambda: lib.adc_engine_sac_pop_batch_indices(h, -1, 0, p(idx))),
+        (r"no such member", lambda: lib.adc_engine_sac_pop_copy(h, 0, 2, 1)),
+        (r"slot range is not inside \[0, size\)", lambda: lib.adc_engine_sac_pop_buffer_fetch(h, 1, 4, 2, p(x), p(ac), p(r), p(dn), p(x))),
+        (r"x, a, r, done or x2 is NULL", lambda: lib.adc_engine_sac_pop_buffer_load(h, 1, 0, 4, p(x), None, p(r), p(dn), p(x), 4)),
+        (r"slot range is not inside \[0, capacity\)", lambda: lib.adc_engine_sac_pop_buffer_load(h, 1, 3, 4, p(x), p(ac), p(r), p(dn), p(x), 12)),
+        (r"written: at least slot \+ count", lambda: lib.adc_engine_sac_pop_buffer_load(h, 1, 0, 4, p(x), p(ac), p(r), p(dn), p(x), 3)),
+        (r"critic: 0 or 1", lambda: lib.adc_engine_sac_pop_set_critic_layer(h, 1, 2, 0, p(w), p(bias))),
+        (r"no such critic layer", lambda: lib.adc_engine_sac_pop_set_critic_layer(h, 1, 0, 2, p(w), p(bias))),
+        (r"weights or bias is NULL", lambda: lib.adc_engine_sac_pop_set_critic_layer(h, 1, 0, 0, p(w), None)),
+        (r"idx_b is NULL", lambda: lib.adc_engine_sac_pop_batch_indices(h, 1, 0, None)),
+        (r"update: 0 to 2\^32 - 2", lambda: lib.adc_engine_sac_pop_batch_indices(h, 1, -1, p(idx))),
+        (r"updates: 1 to 65536", lambda: lib.adc_engine_sac_pop_update(h, 0, None)),
+        (r"a state vector is NULL", lambda: lib.adc_engine_sac_pop_state_set(h, 1, *vec[:-1], None, 0)),
+        (r"updates: 0 to 2\^31 - 2", lambda: lib.adc_engine_sac_pop_state_set(h, 1, *vec, 2 ** 31 - 1)),
+    )
+    for words, call in refused:
+        with pytest.raises(ValueError, match=words):
+            _ffi.check(call())
+    # (SAC's update counter ends at 2^31 - 1: the state's largest count leaves no update)
+    b.sac_pop_state(1, dict(last[1], updates=2 ** 31 - 2))
+    with pytest.raises(_ffi.EngineStateError, match="the update counter is exhausted"):
+        b.sac_pop_update(1)
+    b.sac_pop_state(1, last[1])
+    for m in range(members):
+        _assert_buffer(b.sac_pop_buffer(m), rings[m], m)
+        _assert_state(b.sac_pop_state(m), last[m], m)
+    assert b.sac_pop_update(1)[0]["updates"] == 4
+    # one member's targets become copies; the other's stay
+    b.sac_pop_sync_targets(1)
+    synced, other = b.sac_pop_state(1), b.sac_pop_state(0)
+    assert _same(synced["psi_target"], synced["psi"]) and not _same(other["psi_target"], other["psi"])
+    b.replay_prio_init()
+    with pytest.raises(_ffi.EngineStateError, match="prioritised replay is alive"):
+        b.sac_pop_batch_indices(0, 0)
+    b.close()

@@ -552,3 +552,71 @@ def test_it_learns(amd):
     assert np.isfinite(curve).all()
     se = d.std(ddof=1) / np.sqrt(d.size)
     assert d.mean() > 3.0 * se, (d.mean(), se)
+
+
+def test_a_wrapped_ring_reloaded_at_a_slot_continues_bit_for_bit_and_the_shared_refusals_say_why(amd):
+    """the smallest trainer whose store wraps the ring (4 envs x 3 days into 8 slots): its state and its ring - the ring loaded in
+    two pieces, the second at slot 3 - carry a fresh engine through two more updates to the bits of the uninterrupted run; then
+    every refusal the off-policy front ends share, by its words, and the engine goes on"""
+    from adcraft_amd import _ffi
+    N, K, T = 4, 2, 3
+    rng = np.random.default_rng(91)
+    pol = _policy(rng, K, (8,))
+    crit = T3.random_critics_for_tests(rng, K, (8, 1))
+    seeds = rng.integers(0, 2 ** 63, N).astype(np.uint64)
+    opts = T3.options(critic_widths=(8, 1), batch_size=4, capacity=8, seed=9, actor_lr=3e-3, critic_lr=3e-3)
+    fresh = lambda: _trainer(amd, pol, crit, N, K, T, opts, seeds, norm=_action_norm(K), **NO_RESETS)
+    a = fresh()
+    a.run_days("mlp", T, 1000.0)
+    assert a.td3_store() == 12
+    a.td3_update(1)
+    state, ring = a.td3_state(), a.td3_buffer()
+    assert (ring["size"], ring["written"], ring["capacity"]) == (8, 12, 8)
+    b = fresh()
+    part = lambda lo, hi: {k: ring[k][lo:hi] for k in ("x", "a", "r", "done", "x2")}
+    b.td3_buffer_load(part(0, 3))
+    assert b.td3_buffer(fetch=False) == dict(size=3, written=3, capacity=8)
+    b.td3_buffer_load(part(3, 8), slot=3, written=12)
+    b.td3_state(state)
+    _assert_buffer(b.td3_buffer(), ring)
+    _assert_state(b.td3_state(), state)
+    assert b.td3_param_counts() == a.td3_param_counts()
+    assert _same(a.td3_batch_indices(1), b.td3_batch_indices(1)) and a.td3_batch_indices(1).shape == (4,)
+    _assert_stats(b.td3_update(2), a.td3_update(2))
+    _assert_state(b.td3_state(), a.td3_state())
+    assert b.td3_state()["updates"] == 3
+    a.close()
+    lib, h, p = b._lib, b._h, lambda v: v.ctypes.data
+    x, ac, r, dn = np.zeros((4, 5 * K + 2), F), np.zeros((4, K + 1), F), np.zeros(4, F), np.zeros(4, np.uint8)
+    (w, bias), idx = crit[0][0], np.zeros(4, np.int32)
+    last = b.td3_state()
+    vec = [p(last[k]) for k in amd.StepEngine.TD3_STATE]
+    refused = (
+        (r"slot range is not inside \[0, size\)", lambda: lib.adc_engine_td3_buffer_fetch(h, 7, 2, p(x), p(ac), p(r), p(dn), p(x))),
+        (r"x, a, r, done or x2 is NULL", lambda: lib.adc_engine_td3_buffer_load(h, 0, 4, p(x), None, p(r), p(dn), p(x), 4)),
+        (r"slot range is not inside \[0, capacity\)", lambda: lib.adc_engine_td3_buffer_load(h, 6, 4, p(x), p(ac), p(r), p(dn), p(x), 12)),
+        (r"written: at least slot \+ count", lambda: lib.adc_engine_td3_buffer_load(h, 0, 4, p(x), p(ac), p(r), p(dn), p(x), 3)),
+        (r"critic: 0 or 1", lambda: lib.adc_engine_td3_set_critic_layer(h, 2, 0, p(w), p(bias))),
+        (r"no such critic layer", lambda: lib.adc_engine_td3_set_critic_layer(h, 0, 2, p(w), p(bias))),
+        (r"weights or bias is NULL", lambda: lib.adc_engine_td3_set_critic_layer(h, 0, 0, p(w), None)),
+        (r"idx_b is NULL", lambda: lib.adc_engine_td3_batch_indices(h, 0, None)),
+        (r"update: 0 to 2\^32 - 2", lambda: lib.adc_engine_td3_batch_indices(h, -1, p(idx))),
+        (r"updates: 1 to 65536", lambda: lib.adc_engine_td3_update(h, 0, None)),
+        (r"a state vector is NULL", lambda: lib.adc_engine_td3_state_set(h, *vec[:-1], None, 0, 0)),
+        (r"updates: 0 to 2\^31 - 2", lambda: lib.adc_engine_td3_state_set(h, *vec, 2 ** 31 - 1, 0)),
+    )
+    for words, call in refused:
+        with pytest.raises(ValueError, match=words):
+            _ffi.check(call())
+    _assert_buffer(b.td3_buffer(), ring)
+    _assert_state(b.td3_state(), last)
+    assert b.td3_update(1)["updates"] == 4
+    assert not _same(b.td3_state()["psi_target"], b.td3_state()["psi"])
+    b.td3_sync_targets()
+    synced = b.td3_state()
+    assert _same(synced["psi_target"], synced["psi"])
+    assert _same(synced["theta_target"], synced["theta"])
+    b.replay_prio_init()
+    with pytest.raises(_ffi.EngineStateError, match="prioritised replay is alive"):
+        b.td3_batch_indices(0)
+    b.close()

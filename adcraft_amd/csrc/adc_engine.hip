@@ -56,9 +56,14 @@
 //        permutation, the gathered instantiations of the sample pass and the weight gradient (adc_pg_shuffle.h).
 //   parts/kernel_pg_queued.inc    the PPO / A2C learners' queued update: the stop and the clip scale decided on the device (k_pg_decide), the
 //        chain's kernels that read a member's control block and pass a stopped member by.
-//   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h).
-//   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension.
-//   parts/kernel_sac_pop.inc      SAC learner populations: the k_sac_pop_* twins of kernel_sac.inc, the member one more grid dimension.
+//   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h);
+//        the store, the target, the actor's pass and Polyak are td3_*_body functions that the solo kernel and its population twin both call.
+//   parts/kernel_sac.inc          soft actor-critic: the soft target, the critics' pass, the actor's step, the temperature (adc_sac.h);
+//        sac_target_body under k_sac_target and its population twin.
+//   parts/kernel_td3_pop.inc      TD3 learner populations: the k_td3_pop_* twins, the member one more grid dimension; wrappers round
+//        kernel_td3.inc's bodies with the member's row of the device tables.
+//   parts/kernel_sac_pop.inc      SAC learner populations: the k_sac_pop_* twins of kernel_sac.inc, the member one more grid dimension;
+//        the target a wrapper round sac_target_body, the critic and the actor kernel restated.
 //   parts/kernel_per.inc          prioritised replay: the radix-64 sum tree's sample, weights, leaf update and node rebuild (adc_per.h).
 //   parts/kernel_pbt.inc          population-based training over a learner population: the fitness from the record, the batched copy, SAC's temperature cells (adc_pbt.h).
 //   parts/kernel_norm.inc         the running normalisers, one set of kernels: the record's batch moments of the observations in one pass,

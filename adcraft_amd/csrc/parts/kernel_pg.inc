@@ -495,15 +495,17 @@ __global__ __launch_bounds__(kPgBlock) void k_pg_update(PgLayout L, float *__res
     mom_v[p] = v;
     *pg_param_slot(L, p) = t1;
 }
-// ... of every member (blockIdx.y) with its own clip scale and step constants (PgMember, set by the host before the launch);
-// theta, the moments and grad are [M][Q], L member 0's stores and a member's `stride` floats further each
+// ... of every member (blockIdx.y) with its own clip scale and step constants (the clip, scale and step of its Row: PgMember, or
+// the off-policy populations' Td3PopStep; set by the host before the launch); theta, the moments and grad are [M][Q], L member 0's
+// stores and a member's `stride` floats further each
+template <class Row>
 __device__ __forceinline__ void pg_pop_update_body(const PgLayout &L, size_t stride, float *__restrict__ theta, float *__restrict__ mom_m,
-                                                   float *__restrict__ mom_v, const float *__restrict__ grad, const PgMember *__restrict__ mem)
+                                                   float *__restrict__ mom_v, const float *__restrict__ grad, const Row *__restrict__ mem)
 {
     const int p = blockIdx.x * kPgBlock + threadIdx.x;
     if (p >= L.Q) return;
     const size_t member = blockIdx.y, i = member * (size_t)L.Q + (size_t)p;
-    const PgMember &c = mem[member];
+    const Row &c = mem[member];
     float g = grad[i];
     if (c.clip) g = g * c.scale;
     float m = mom_m[i], v = mom_v[i];

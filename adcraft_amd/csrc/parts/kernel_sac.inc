@@ -2,7 +2,10 @@
 // action, the actor's reparameterised step through the smaller critic, and the temperature's step.  The arithmetic is
 // adc_sac.h's law, the code the host twins adc_sac_target_host / adc_sac_critic_grad_host / adc_sac_actor_grad_host /
 // adc_sac_alpha_step_host run.  The ring and its store, the batch indices, the weight gradient, the optimiser step and Polyak
-// are kernel_td3.inc's and kernel_pg.inc's, unchanged.
+// are kernel_td3.inc's and kernel_pg.inc's, unchanged.  The target is written once, as sac_target_body: k_sac_target here and the
+// populations' k_sac_pop_target (kernel_sac_pop.inc) are wrappers that say where a learner's networks, law, key, ring and
+// temperature come from.  The critic and the actor kernel and their population twins are each written out (k_sac_critic_sample and
+// k_sac_actor_sample say why).
 // (part of the single translation unit adc_engine.hip)
 // -------------------------------------------------------------------------------------------------
 // Shape.  The batch kernels are k_td3_*'s shape: one workgroup of 256 lanes per batch element, the element's row [x | t] and
@@ -61,12 +64,12 @@ __device__ __forceinline__ SacLds sac_carve(float *lds, const adc::Td3Shape &sh,
 }
 
 // the actor's head on its outputs o[2A] with the stage's draws: t into the row's action part, the per-component values into LDS
-__device__ __forceinline__ void sac_heads(const SacView &p, const SacLds &s, const float *o, uint32_t stage, uint32_t b)
+__device__ __forceinline__ void sac_heads(int A, int D, uint32_t update, uint64_t key, const adc::SacLaw &law, const SacLds &s, const float *o,
+                                          uint32_t stage, uint32_t b)
 {
-    const int A = p.sh.A, D = p.sh.D;
     for (int a = threadIdx.x; a < A; a += kPgBlock) {
-        const float z = adc::sac_noise(p.key, stage, a, b, p.update);
-        const adc::SacHead h = adc::sac_head(o[a], o[A + a], z, p.law);
+        const float z = adc::sac_noise(key, stage, a, b, update);
+        const adc::SacHead h = adc::sac_head(o[a], o[A + a], z, law);
         s.row[D + a] = h.t;
         s.z[a] = z; s.sd[a] = h.sd; s.w[a] = h.w; s.term[a] = h.term; s.c[a] = h.c;
     }
@@ -89,42 +92,60 @@ __device__ __forceinline__ void sac_lp(const SacLds &s, int A, float *out)
     __syncthreads();
 }
 
-// y of batch element blockIdx.x
+// The target's body: batch element blockIdx.x of one learner, as in kernel_td3.inc.  p carries what a population's members share;
+// what is a learner's own - its networks, law, key, ring and temperature cell - comes as arguments, and `member` moves the
+// element's scratch row to member * gridDim.x + blockIdx.x, the normaliser's vectors to member * p.n_stride and its multiplier to
+// member * p.r_stride.  The solo kernel passes its view's fields and the literal member 0, which folds those three away.  Without
+// a normaliser the host launches the NORM = false instantiations, which do not read the normaliser's fields.
+
+// y of the element
 template <bool NORM>
-__global__ __launch_bounds__(kPgBlock) void k_sac_target(SacView p)
+__device__ __forceinline__ void sac_target_body(const SacView &p, const MlpNet &pol, const MlpNet *q_t, const adc::SacLaw &law, uint64_t key,
+                                                const Td3Ring &ring, const float *cell, uint32_t member)
 {
     extern __shared__ __align__(16) float sac_lds[];
     const adc::Td3Shape &sh = p.sh;
     const int tid = threadIdx.x, D = sh.D;
     const uint32_t b = blockIdx.x;
+    const size_t at = (size_t)member * gridDim.x + b;           // the element's scratch row
     const SacLds s = sac_carve(sac_lds, sh, p.maxw);
-    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
-    const float alpha = p.cell[kSacCellAlpha];
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
+    const float alpha = cell[kSacCellAlpha];
+    const size_t nv = NORM ? (size_t)member * p.n_stride : 0;   // (the member's row of the normaliser's vectors; 0 whenever they are shared)
     // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
-    const float r_mult = NORM && p.r_scale ? p.r_scale[0] : 1.0f;
+    const float r_mult = NORM && p.r_scale ? p.r_scale[(size_t)member * (size_t)p.r_stride] : 1.0f;
     for (int j = tid; j < D; j += kPgBlock) {
-        float xj = p.ring.x2[slot * (size_t)D + j];
-        if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        float xj = ring.x2[slot * (size_t)D + j];
+        if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
         s.row[j] = xj;
     }
     __syncthreads();
-    td3_forward(p.pol, sh.activation, s.row, s.yp, nullptr);
-    sac_heads(p, s, s.yp + adc::td3_hidden(sh.pol), adc::ST_SAC_NEXT, b);
+    td3_forward(pol, sh.activation, s.row, s.yp, nullptr);
+    sac_heads(sh.A, D, p.update, key, law, s, s.yp + adc::td3_hidden(sh.pol), adc::ST_SAC_NEXT, b);
     sac_lp(s, sh.A, s.words + 2);
     const int qlast = adc::td3_hidden(sh.q);
     for (int i = 0; i < 2; ++i) {
-        td3_forward(p.q_t[i], sh.activation, s.row, s.yq, nullptr);
+        td3_forward(q_t[i], sh.activation, s.row, s.yq, nullptr);
         if (tid == 0) s.words[i] = s.yq[qlast];
         __syncthreads();
     }
     if (tid == 0) {
         const float q = adc::td3_min(s.words[0], s.words[1]);
-        p.ybuf[b] = NORM && p.r_scale ? adc::sac_y_norm(p.ring.r[slot], p.ring.done[slot], q, alpha, s.words[2], p.law, r_mult, p.r_clip)
-                              : adc::sac_y(p.ring.r[slot], p.ring.done[slot], q, alpha, s.words[2], p.law);
+        p.ybuf[at] = NORM && p.r_scale ? adc::sac_y_norm(ring.r[slot], ring.done[slot], q, alpha, s.words[2], law, r_mult, p.r_clip)
+                                       : adc::sac_y(ring.r[slot], ring.done[slot], q, alpha, s.words[2], law);
     }
 }
+template <bool NORM>
+__global__ __launch_bounds__(kPgBlock) void k_sac_target(SacView p)
+{
+    sac_target_body<NORM>(p, p.pol, p.q_t, p.law, p.key, p.ring, p.cell, 0u);
+}
 
-// forward and backward of both critics on batch element blockIdx.x: k_td3_critic_sample with t = tanh(ring.a) as the action input
+// forward and backward of both critics on batch element blockIdx.x: k_td3_critic_sample with t = tanh(ring.a) as the action input.
+// This kernel and k_sac_pop_critic_sample stay restated for k_td3_critic_sample's reason: under one sac_critic_body only scalar
+// opcodes moved (the same ones), and this kernel ran 105.8 -> 107.0 us (critics 256,256, batch 256, 1024 x 25; two kernel traces a
+// side, 390 launches each).  (One pass for both families would be a template over the view type, the NORM switch and the
+// transform, handed five carved LDS pointers: more to read than the lines it saves)
 template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
 {
@@ -162,7 +183,12 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_critic_sample(SacView p)
 }
 
 // the actor's forward and head, both critics on [x | t], the smaller one's backward through to the action inputs, the head's
-// deltas for its 2A outputs, the actor's backward
+// deltas for its 2A outputs, the actor's backward.  This kernel and k_sac_pop_actor_sample stay restated: with one sac_actor_body
+// under both, called here with the view's fields and member 0, the compiler no longer reads the picked critic's layers from the
+// kernel arguments at pick's offset but selects between the two critics' values, and this kernel's vector opcodes change (NORM
+// false: v_cndmask_b32 27 -> 26, v_readfirstlane_b32 2 -> 1, v_cmp_gt_i32 3 -> 4; true: v_cndmask_b32 28 -> 27, v_readfirstlane_b32
+// 6 -> 5; registers, scratch and LDS as they were; the twin's vector opcodes did not change), whether the critics came as a
+// pointer, as an array reference or under __restrict__
 template <bool NORM>
 __global__ __launch_bounds__(kPgBlock) void k_sac_actor_sample(SacView p)
 {
@@ -183,7 +209,7 @@ __global__ __launch_bounds__(kPgBlock) void k_sac_actor_sample(SacView p)
     td3_forward(p.pol, sh.activation, s.row, s.yp, acts);
     const int ph = adc::td3_hidden(sh.pol), qh = adc::td3_hidden(sh.q), no = adc::td3_outs(sh.q);
     const float *o = s.yp + ph;
-    sac_heads(p, s, o, adc::ST_SAC_PI, b);
+    sac_heads(A, D, p.update, p.key, p.law, s, o, adc::ST_SAC_PI, b);
     sac_lp(s, A, s.words + 2);
     td3_forward(p.q[0], sh.activation, s.row, s.yq, nullptr);
     td3_forward(p.q[1], sh.activation, s.row, s.yq + no, nullptr);

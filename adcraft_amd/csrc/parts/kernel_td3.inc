@@ -1,7 +1,10 @@
 // kernel_td3.inc - off-policy training on the device: the replay ring filled from the rollout record, the TD3 target, the twin
 // critics' forward and backward pass, the deterministic policy gradient through critic 1's input, and Polyak averaging.  The
 // arithmetic is adc_td3.h's law, the code the host twins adc_td3_target_host / adc_td3_critic_grad_host /
-// adc_td3_actor_grad_host run.
+// adc_td3_actor_grad_host run.  The store, the target, the actor's pass and Polyak are each written once, as a td3_*_body
+// function: the solo kernels k_td3_* here and the populations' k_td3_pop_* (kernel_td3_pop.inc) are wrappers that say where a
+// learner's networks, law, key and ring come from - the view's fields and member 0 here, row blockIdx.y of the members' tables
+// there.  The critic kernel and its twin are each written out (k_td3_critic_sample says why).
 // (part of the single translation unit adc_engine.hip)
 // -------------------------------------------------------------------------------------------------
 // Shape.  The batch kernels are k_pg_sample's shape: one workgroup of 256 lanes per batch element, the element's input row
@@ -108,17 +111,18 @@ __device__ __forceinline__ void td3_input_back(const float *__restrict__ W, int 
     __syncthreads();
 }
 
-// sample s = (t - t0) * N + n of the recorded days [t0, t1) into slot (written + s) mod C
-__global__ __launch_bounds__(kPgBlock) void k_td3_store(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
-                                                        const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
-                                                        const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
-                                                        const uint8_t *__restrict__ ro_trunc, int t0, int t1, Td3Ring ring,
-                                                        unsigned long long written, unsigned long long C)
+// sample s = (t - t0) * n + local env of the recorded days [t0, t1) of the member's envs [member n, (member + 1) n) into slot
+// (written + s) mod C of its ring
+__device__ __forceinline__ void td3_store_body(const View &v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
+                                               const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                               const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                               const uint8_t *__restrict__ ro_trunc, int t0, int t1, int n, int member, const Td3Ring ring,
+                                               unsigned long long written, unsigned long long C)
 {
     const int tid = threadIdx.x, N = v.N, K = v.K;
-    const unsigned long long s = blockIdx.x, count = (unsigned long long)(t1 - t0) * (unsigned long long)N;
+    const unsigned long long s = blockIdx.x, count = (unsigned long long)(t1 - t0) * (unsigned long long)n;
     if (s >= count || s + C < count) return;            // (a later sample of this store lands on the same slot)
-    const int t = t0 + (int)(s / (unsigned long long)N), env = (int)(s % (unsigned long long)N);
+    const int t = t0 + (int)(s / (unsigned long long)n), env = member * n + (int)(s % (unsigned long long)n);
     const size_t slot = (size_t)((written + s) % C), row = (size_t)t * (size_t)N + (size_t)env;
     for (int j = tid; j < D; j += kPgBlock) ring.x[slot * (size_t)D + j] = ro_obs[row * (size_t)D + j];
     for (int a = tid; a < A; a += kPgBlock) ring.a[slot * (size_t)A + a] = ro_action[row * (size_t)A + a];
@@ -142,6 +146,14 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_store(View v, const float *__r
         }
     }
 }
+__global__ __launch_bounds__(kPgBlock) void k_td3_store(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
+                                                        const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                        const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                        const uint8_t *__restrict__ ro_trunc, int t0, int t1, Td3Ring ring,
+                                                        unsigned long long written, unsigned long long C)
+{
+    td3_store_body(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, v.N, 0, ring, written, C);
+}
 
 __global__ void k_td3_indices(uint64_t key, uint32_t update, uint32_t size, int B, int32_t *__restrict__ out)
 {
@@ -149,44 +161,62 @@ __global__ void k_td3_indices(uint64_t key, uint32_t update, uint32_t size, int 
     if (b < B) out[b] = (int32_t)adc::td3_batch_index(key, (uint32_t)b, update, size);
 }
 
-// y of batch element blockIdx.x
-__global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
+// The batch bodies: batch element blockIdx.x of one learner.  p carries what a population's members share (the shapes, the action
+// normalisation, the ring's size, the update's number, the scratch, na / nd / maxw); what is a learner's own - its networks, law,
+// key and ring - comes as arguments, and `member` moves the element's scratch row to member * gridDim.x + blockIdx.x, the
+// normaliser's vectors to member * p.n_stride and its multiplier to member * p.r_stride.  The solo kernels pass their view's
+// fields and the literal member 0, which folds those three away.
+
+// y of the element
+__device__ __forceinline__ void td3_target_body(const Td3View &p, const MlpNet &pol_t, const MlpNet *q_t, const adc::Td3Law &law, uint64_t key,
+                                                const Td3Ring &ring, uint32_t member)
 {
     extern __shared__ __align__(16) float td3_lds[];
     const adc::Td3Shape &sh = p.sh;
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
     const uint32_t b = blockIdx.x;
+    const size_t at = (size_t)member * gridDim.x + b;           // the element's scratch row
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *words = yq + adc::td3_outs(sh.q) + 3 * p.maxw;
-    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
+    const size_t nv = (size_t)member * p.n_stride;              // (the member's row of the normaliser's vectors; 0 whenever they are shared)
     // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
-    const float r_mult = p.r_scale ? p.r_scale[0] : 1.0f;
+    const float r_mult = p.r_scale ? p.r_scale[(size_t)member * (size_t)p.r_stride] : 1.0f;
     for (int j = tid; j < D; j += kPgBlock) {
-        float xj = p.ring.x2[slot * (size_t)D + j];
-        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        float xj = ring.x2[slot * (size_t)D + j];
+        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
         row[j] = xj;
     }
     __syncthreads();
-    td3_forward(p.pol_t, sh.activation, row, yp, nullptr);
+    td3_forward(pol_t, sh.activation, row, yp, nullptr);
     const float *mu = yp + adc::td3_hidden(sh.pol);
     for (int a = tid; a < A; a += kPgBlock) {
-        const float ap = adc::td3_target_action(mu[a], adc::td3_noise(p.key, a, b, p.update), p.law);
+        const float ap = adc::td3_target_action(mu[a], adc::td3_noise(key, a, b, p.update), law);
         row[D + a] = adc::td3_action_norm(ap, p.a_shift, p.a_scale, a, sh.norm);
     }
     __syncthreads();
     const int qlast = adc::td3_hidden(sh.q);
     for (int i = 0; i < 2; ++i) {
-        td3_forward(p.q_t[i], sh.activation, row, yq, nullptr);
+        td3_forward(q_t[i], sh.activation, row, yq, nullptr);
         if (tid == 0) words[i] = yq[qlast];
         __syncthreads();
     }
     if (tid == 0) {
         const float q = adc::td3_min(words[0], words[1]);
-        p.ybuf[b] = p.r_scale ? adc::td3_y_norm(p.ring.r[slot], p.ring.done[slot], q, p.law, r_mult, p.r_clip)
-                              : adc::td3_y(p.ring.r[slot], p.ring.done[slot], q, p.law);
+        p.ybuf[at] = p.r_scale ? adc::td3_y_norm(ring.r[slot], ring.done[slot], q, law, r_mult, p.r_clip)
+                               : adc::td3_y(ring.r[slot], ring.done[slot], q, law);
     }
 }
+__global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
+{
+    td3_target_body(p, p.pol_t, p.q_t, p.law, p.key, p.ring, 0u);
+}
 
-// forward and backward of both critics on batch element blockIdx.x
+// forward and backward of both critics on batch element blockIdx.x.  This kernel and k_td3_pop_critic_sample stay restated: under
+// one td3_critic_body, called here with the view's fields and member 0, registers, scratch, LDS and every vector, LDS and memory
+// opcode count of both kernels were the restated form's and only scalar opcodes moved (here s_add_i32 66 -> 63, s_mul_i32 27 -> 24,
+// s_cbranch_vccnz 16 -> 15, s_cbranch_vccz 5 -> 6, s_and_b64 16 -> 15, s_andn2_b64 16 -> 17), but this kernel ran 115.3 -> 119.6 us
+// (critics 256,256, batch 256, 1024 x 25; two kernel traces a side, 396 launches each) and TD3's per update of 64 went 0.3304 ->
+// 0.3337 ms, outside the restated form's own spread (profiles/pr_offpolicy_kernel_bodies.txt)
 __global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
 {
     extern __shared__ __align__(16) float td3_lds[];
@@ -224,43 +254,57 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
 }
 
 // the actor's forward, critic 1 on [x | norm(mu)], its backward through to the action inputs, the actor's backward
-__global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample(Td3View p)
+__device__ __forceinline__ void td3_actor_body(const Td3View &p, const MlpNet &pol, const MlpNet &q1, uint64_t key, const Td3Ring &ring,
+                                               uint32_t member)
 {
     extern __shared__ __align__(16) float td3_lds[];
     const adc::Td3Shape &sh = p.sh;
     const int tid = threadIdx.x, A = sh.A, D = sh.D;
     const uint32_t b = blockIdx.x;
+    const size_t at = (size_t)member * gridDim.x + b;
     float *row = td3_lds, *yp = row + D + A, *yq = yp + adc::td3_outs(sh.pol), *d0 = yq + adc::td3_outs(sh.q), *d1 = d0 + p.maxw, *dump = d1 + p.maxw;
-    const size_t slot = p.p_slot ? (size_t)p.p_slot[b] : (size_t)adc::td3_batch_index(p.key, b, p.update, p.size);
+    const size_t slot = p.p_slot ? (size_t)p.p_slot[at] : (size_t)adc::td3_batch_index(key, b, p.update, p.size);
+    const size_t nv = (size_t)member * p.n_stride;
     for (int j = tid; j < D; j += kPgBlock) {
-        float xj = p.ring.x[slot * (size_t)D + j];
-        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[j], p.n_scale[j]);
+        float xj = ring.x[slot * (size_t)D + j];
+        if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
         row[j] = xj;
     }
     __syncthreads();
-    float *acts = p.acts + (size_t)b * (size_t)p.na, *deltas = p.deltas + (size_t)b * (size_t)p.nd;
-    td3_forward(p.pol, sh.activation, row, yp, acts);
+    float *acts = p.acts + at * (size_t)p.na, *deltas = p.deltas + at * (size_t)p.nd;
+    td3_forward(pol, sh.activation, row, yp, acts);
     const int ph = adc::td3_hidden(sh.pol), qh = adc::td3_hidden(sh.q);
     for (int a = tid; a < A; a += kPgBlock) row[D + a] = adc::td3_action_norm(yp[ph + a], p.a_shift, p.a_scale, a, sh.norm);
     __syncthreads();
-    td3_forward(p.q[0], sh.activation, row, yq, nullptr);
+    td3_forward(q1, sh.activation, row, yq, nullptr);
     if (tid == 0) {
-        p.pieces[(size_t)b * adc::kTd3Pieces + adc::kTd3QPi] = yq[qh];
+        p.pieces[at * adc::kTd3Pieces + adc::kTd3QPi] = yq[qh];
         d0[0] = 1.0f;
     }
     __syncthreads();
-    float *dq = td3_backward(p.q[0], sh.activation, yq, d0, d1, nullptr, dump);
+    float *dq = td3_backward(q1, sh.activation, yq, d0, d1, nullptr, dump);
     float *dm = dq == d0 ? d1 : d0;
-    td3_input_back(p.q[0].W[0], D, A, sh.q.n_out[0], dq, dm, p.a_scale, sh.norm, deltas + ph);
-    td3_backward(p.pol, sh.activation, yp, dm, dq, deltas, dump);
+    td3_input_back(q1.W[0], D, A, sh.q.n_out[0], dq, dm, p.a_scale, sh.norm, deltas + ph);
+    td3_backward(pol, sh.activation, yp, dm, dq, deltas, dump);
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample(Td3View p)
+{
+    td3_actor_body(p, p.pol, p.q[0], p.key, p.ring, 0u);
 }
 
-// target = target + tau * (param - target) on the flat vectors, the targets' chain-major stores rebuilt from the result
-__global__ __launch_bounds__(kPgBlock) void k_td3_polyak(PgLayout L, float *__restrict__ target, const float *__restrict__ param, float tau)
+// target = target + tau * (param - target) on the member's [Q] of the flat vectors, the targets' chain-major stores (L member 0's,
+// a member's `stride` floats further each) rebuilt from the result
+__device__ __forceinline__ void td3_polyak_body(const PgLayout &L, size_t stride, float *__restrict__ target, const float *__restrict__ param,
+                                                float tau, size_t member)
 {
     const int p = blockIdx.x * kPgBlock + threadIdx.x;
     if (p >= L.Q) return;
-    const float t1 = adc::td3_polyak(target[p], param[p], tau);
-    target[p] = t1;
-    *pg_param_slot(L, p) = t1;
+    const size_t i = member * (size_t)L.Q + (size_t)p;
+    const float t1 = adc::td3_polyak(target[i], param[i], tau);
+    target[i] = t1;
+    *(pg_param_slot(L, p) + member * stride) = t1;
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_polyak(PgLayout L, float *__restrict__ target, const float *__restrict__ param, float tau)
+{
+    td3_polyak_body(L, 0, target, param, tau, 0);
 }

@@ -362,6 +362,55 @@ def test_a_population_member_equals_a_solo_engine_on_its_envs(amd, kind):
 
 
 @pytest.mark.parametrize("kind", ["td3", "sac"])
+def test_a_member_under_replay_and_its_own_normalisers_equals_a_solo_engine(amd, kind):
+    """the population test above with both running normalisers on, one per member, and moved after every store: a batch kernel then
+    takes the member's slots and weights, its vectors and its multiplier in one pass.  Every member's state, normaliser state (the
+    vectors and the multiplier with it), running returns, leaves, top, total and next batch are those of a solo engine of its three
+    envs under the same two add-ons"""
+    rng = np.random.default_rng(16)
+    td3 = kind == "td3"
+    fam = "td3" if td3 else "sac"
+    pols, crits = _members(rng, _td3_policy if td3 else _sac_policy)
+    opts = [(_td3_opts if td3 else _sac_opts)(40, **own) for own in (TD3_OWN if td3 else SAC_OWN)]
+    norm = dict(observations=True, rewards=True, rew_clip=0.8)
+    e = (_td3_pop if td3 else _sac_pop)(amd, pols, crits, opts)
+    getattr(e, fam + "_norm_init")(per_member=True, **norm)
+    e.replay_prio_init(**PER)
+    solos = []
+    for m in range(M):
+        s = (_td3 if td3 else _sac)(amd, pols[m], crits[m], opts[m], env_id_base=m * n, planes=_planes(NP)[:, TP.member_slice(m, n)])
+        getattr(s, fam + "_norm_init")(**norm)
+        s.replay_prio_init(**PER)
+        solos.append(s)
+    keys = T3.STATE_KEYS if td3 else S.STATE_KEYS
+    for rnd in range(2):
+        assert _collect(e, getattr(e, fam + "_pop_store")) == n
+        assert getattr(e, fam + "_norm_update")() == n
+        getattr(e, fam + "_pop_update")(2)
+        returns = getattr(e, fam + "_norm_returns")()
+        for m, s in enumerate(solos):
+            assert _collect(s, getattr(s, fam + "_store")) == n
+            assert getattr(s, fam + "_norm_update")() == n
+            getattr(s, fam + "_update")(2)
+            _assert_keys(getattr(e, fam + "_pop_state")(m), getattr(s, fam + "_state")(), keys, (rnd, m))
+            got, ref = getattr(e, fam + "_norm_state")(m), getattr(s, fam + "_norm_state")()
+            assert set(got) == set(ref) >= {"shift", "scale", "rew_scale"}, (rnd, m)
+            _assert_keys({k: np.asarray(v) for k, v in got.items()}, {k: np.asarray(v) for k, v in ref.items()}, sorted(ref), (rnd, m))
+            assert _same(returns[m * n:(m + 1) * n], getattr(s, fam + "_norm_returns")()), (rnd, m)
+            assert _same(e.replay_prio_fetch(m), s.replay_prio_fetch()), (rnd, m)
+            assert e.replay_prio_info(m) == s.replay_prio_info(), (rnd, m)
+            a, b = e.replay_prio_batch(2 * rnd + 2, m), s.replay_prio_batch(2 * rnd + 2)
+            assert _same(a[0], b[0]) and _same(a[1], b[1]), (rnd, m)
+    v = [getattr(e, fam + "_norm_state")(m) for m in range(M)]
+    assert not _same(v[0]["shift"], v[1]["shift"]) and v[0]["rew_scale"] != v[1]["rew_scale"], "the members' normalisers are their own"
+    assert not _same(v[0]["shift"], pols[0].shift), "the vectors moved"
+    assert not _same(e.replay_prio_fetch(0), e.replay_prio_fetch(1)), "the members' priorities are their own"
+    for s in solos:
+        s.close()
+    e.close()
+
+
+@pytest.mark.parametrize("kind", ["td3", "sac"])
 def test_copies_carry_the_tree_with_the_ring_and_only_with_it(amd, kind):
     """*_pop_copy without the ring leaves the destination's leaves, total and top alone; with it they are the donor's, and the
     destination's next batch is the restatement's on the donor's leaves under its own key; a PBT exploit with rings does the same"""

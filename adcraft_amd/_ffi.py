@@ -295,6 +295,10 @@ def lib():
                                  C.c_double, vp, vp, vp, vp, vp], C.c_int),
         "adc_interp_key_host": ([f32], C.c_double),
         "adc_engine_mlp_init": ([vp, C.POINTER(MLPConfig), vp], C.c_int),
+        "adc_engine_mlp_init_frames": ([vp, C.POINTER(MLPConfig), vp, i32], C.c_int),
+        "adc_engine_mlp_frames": ([vp, vp], C.c_int),
+        "adc_engine_mlp_history_get": ([vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_history_set": ([vp, vp, vp, vp], C.c_int),
         "adc_engine_mlp_set_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_mlp_set_norm": ([vp, vp, vp], C.c_int),
         "adc_engine_mlp_set_log_std": ([vp, vp], C.c_int),
@@ -506,6 +510,7 @@ def lib():
         "adc_td3_actor_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), vp, vp, vp, vp, i32, vp, vp, vp], C.c_int),
         "adc_td3_polyak_host": ([f32, i64, vp, vp], C.c_int),
         "adc_mlp_config_check": ([C.POINTER(MLPConfig), i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_mlp_stack_row_host": ([i32, i32, vp, vp, vp, vp, i32, i32, vp], C.c_int),
         "adc_mlp_act_host": ([C.POINTER(MLPConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
                               vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "adc_mlp_math_host": ([i32, f32], f32),

@@ -30,15 +30,16 @@ def policy_from_flat(policy, flat):
     return out
 
 
-def default_policy(num_keywords, hidden=(32, 32), days=60, seed=0, log_std=-2.0, deterministic=True):
+def default_policy(num_keywords, hidden=(32, 32), days=60, seed=0, log_std=-2.0, deterministic=True, frames=1):
     """the untrained `[32, 32]` tanh policy of examples/evaluate_mlp_policy.py, built in numpy: every Linear layer drawn uniformly
     in +-1 / sqrt(n_in) (weights and biases), the last layer's weights scaled by 0.1 and its biases set to 0.5 - an agent that
     bids about 50 cents everywhere - on observations scaled to O(1) (counts and dollars * 0.1, cumulative profit * 1e-3,
-    days / `days`)"""
+    days / `days`).  frames: the observations its input row holds (MLPPolicy(frames=...)); every frame is scaled alike"""
     from .mlp_policy import MLPPolicy
     rng = np.random.default_rng(seed)
     K = int(num_keywords)
-    D, A = 5 * K + 2, K + 1
+    D0, A = 5 * K + 2, K + 1
+    D = int(frames) * D0
     layers, n_in = [], D
     for n_out in list(hidden) + [A]:
         bound = 1.0 / np.sqrt(n_in)
@@ -46,10 +47,10 @@ def default_policy(num_keywords, hidden=(32, 32), days=60, seed=0, log_std=-2.0,
         n_in = n_out
     layers[-1][0] *= np.float32(0.1)
     layers[-1][1][:] = 0.5
-    scale = np.full(D, 0.1, np.float32)
+    scale = np.full(D0, 0.1, np.float32)
     scale[2 * K], scale[2 * K + 1] = 1.0e-3, 1.0 / days
-    return MLPPolicy([tuple(l) for l in layers], shift=np.zeros(D, np.float32), scale=scale, log_std=np.full(A, log_std, np.float32),
-                     deterministic=deterministic)
+    return MLPPolicy([tuple(l) for l in layers], shift=np.zeros(D, np.float32), scale=np.tile(scale, int(frames)), log_std=np.full(A, log_std, np.float32),
+                     deterministic=deterministic, frames=int(frames))
 
 
 class ESTrainer:
@@ -81,7 +82,8 @@ class ESTrainer:
         return policy_from_flat(self._template, self.engine.mlp_params())
 
     def state(self, state=None):
-        return self.engine.es_state(state)
+        from .mlp_policy import history_carry
+        return history_carry(self.engine, self.engine.es_state, state)
 
 
 __all__ = ["ESTrainer", "default_policy", "flat_params", "policy_from_flat"]

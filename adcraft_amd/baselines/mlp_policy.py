@@ -4,7 +4,10 @@ TD3 (`fcnet_hiddens [32, 32]` on FlatArrayWrapper observations), held as plain f
 
 The observation is the flat row `buyside_clicks[K] | cost[K] | cumulative_profit | days_passed | impressions[K] | revenue[K] |
 sellside_conversions[K]` (D = 5K+2); the action is `[budget, bids...]` (A = K+1).  The policy network ends in A means (with a
-free `log_std[A]`) or in 2A values, means then log-stds."""
+free `log_std[A]`) or in 2A values, means then log-stds.
+
+With `frames=H` (1 to 8) the policy acts on the last H observations: its input is H such rows side by side, the newest first
+(D = H (5K+2)); the engine gathers the older ones from a per-env history on the device (csrc/adc_mlp.h, observation history)."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +15,7 @@ import numpy as np
 from .. import _ffi
 
 ACTIVATIONS = {"tanh": _ffi.MLP_TANH, "relu": _ffi.MLP_RELU}
-MAX_LAYERS, MAX_WIDTH = 4, 256
+MAX_LAYERS, MAX_WIDTH, MAX_FRAMES = 4, 256, 8
 
 
 def _layers(pairs, what):
@@ -31,14 +34,21 @@ def _layers(pairs, what):
 class MLPPolicy:
     """layers / value_layers: lists of (W [n_in, n_out], b [n_out]) - input-major, i.e. torch's `weight.T`.  log_std [A]: the
     free log standard deviations when the policy ends in A means (default zeros); shift / scale [D]: x' = (x - shift) * scale;
-    log_std_clamp (lo, hi); bid_clip: upper clip of the bids in dollars; deterministic: act on the means."""
+    log_std_clamp (lo, hi); bid_clip: upper clip of the bids in dollars; deterministic: act on the means; frames: the number H
+    of observations the input row holds (D = H (5K+2); shift / scale cover all of it)."""
 
     def __init__(self, layers, activation="tanh", value_layers=(), log_std=None, shift=None, scale=None, log_std_clamp=None,
-                 bid_clip=None, deterministic=False):
+                 bid_clip=None, deterministic=False, frames=1):
         if activation not in ACTIVATIONS:
             raise ValueError(f"unknown activation {activation!r}: 'tanh' or 'relu'")
         self.activation = activation
+        if int(frames) != frames or not 1 <= int(frames) <= MAX_FRAMES:
+            raise ValueError(f"frames: 1 to {MAX_FRAMES}")
+        self.frames = int(frames)
         self.layers = _layers(layers, "policy network")
+        if self.input_size % self.frames or (self.input_size // self.frames) % 5 != 2 or self.input_size // self.frames < 7:
+            if self.frames > 1:
+                raise ValueError(f"the first layer reads {self.input_size} inputs: not frames = {self.frames} rows of 5K+2")
         self.value_layers = _layers(value_layers, "value network")
         if not 1 <= len(self.layers) <= MAX_LAYERS or len(self.value_layers) > MAX_LAYERS:
             raise ValueError(f"a network has at most {MAX_LAYERS} layers (and the policy network at least one)")
@@ -52,7 +62,7 @@ class MLPPolicy:
         vec = lambda x, n: None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32), (n,)))
         self.shift, self.scale = vec(shift, self.input_size), vec(scale, self.input_size)
         self.log_std = None
-        if self.input_size % 5 == 2 and self.output_size == self.num_keywords + 1:
+        if (self.input_size // self.frames) % 5 == 2 and self.output_size == self.num_keywords + 1:
             self.log_std = vec(0.0 if log_std is None else log_std, self.output_size)
         elif log_std is not None:
             raise ValueError("log_std belongs to a policy that ends in K+1 means")
@@ -62,13 +72,13 @@ class MLPPolicy:
 
     input_size = property(lambda self: self.layers[0][0].shape[0])
     output_size = property(lambda self: self.layers[-1][0].shape[1])
-    num_keywords = property(lambda self: (self.input_size - 2) // 5)
+    num_keywords = property(lambda self: (self.input_size // self.frames - 2) // 5)
 
     def shapes(self):
         """what StepEngine.mlp_init fixes and mlp_set_weights must find again: every layer's shape, the head's free log_std,
         whether there is a normalisation"""
         return ([w.shape for w, _ in self.layers], [w.shape for w, _ in self.value_layers], self.log_std is not None,
-                self.shift is not None)
+                self.shift is not None) + ((self.frames,) if self.frames > 1 else ())
 
     @classmethod
     def from_arrays(cls, layers, **kw):
@@ -127,12 +137,36 @@ class MLPPolicy:
         c.log_std_lo, c.log_std_hi = self.log_std_clamp or (0.0, 0.0)
         c.bid_clip_hi = self.bid_clip or 0.0
         c.deterministic = 1 if (self.deterministic if deterministic is None else deterministic) else 0
-        if self.input_size != 5 * int(num_keywords) + 2:
-            raise ValueError(f"the policy reads {self.input_size} inputs, the engine's observation has {5 * int(num_keywords) + 2}")
+        if self.input_size != self.frames * (5 * int(num_keywords) + 2):
+            raise ValueError(f"the policy reads {self.input_size} inputs, the engine's observation has {5 * int(num_keywords) + 2}"
+                             + (f" (times frames = {self.frames})" if self.frames > 1 else ""))
         msg = C.c_char_p()
         if _ffi.lib().adc_mlp_config_check(C.byref(c), int(num_keywords), C.byref(msg)) != _ffi.ADC_OK:
             raise ValueError((msg.value or b"bad MLP configuration").decode())
         return c
 
 
-__all__ = ["MLPPolicy"]
+def history_carry(engine, get_or_set, state, member=0, envs=None):
+    """get_or_set(state): a trainer's own state call; the policy's observation history rides along as `obs_history` (all envs',
+    or the `envs` of a member), so that a resumed run continues bit for bit.  Nothing is added without one (frames = 1)."""
+    sl = slice(None) if envs is None else slice(member * envs, (member + 1) * envs)
+    if state is None:
+        st = get_or_set(None)
+        hist = engine.mlp_history_state()
+        if hist is not None:
+            st["obs_history"] = {k: v[sl].copy() for k, v in hist.items()}
+        return st
+    state = dict(state)
+    hist = state.pop("obs_history", None)
+    out = get_or_set(state)
+    if hist is not None:
+        now = engine.mlp_history_state()
+        if now is None:
+            raise ValueError("the state carries an observation history and the policy has none (frames = 1)")
+        for k in now:
+            now[k][sl] = hist[k]
+        engine.mlp_set_history_state(now)
+    return out
+
+
+__all__ = ["MLPPolicy", "history_carry"]

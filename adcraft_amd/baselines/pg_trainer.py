@@ -11,6 +11,8 @@ import copy
 
 import numpy as np
 
+from .mlp_policy import history_carry
+
 
 def flat_params(policy):
     """theta of an MLPPolicy in the trainer's flat order"""
@@ -230,7 +232,14 @@ class PGTrainer:
         return _rew_norm_state(self.engine, 0, state)
 
     def state(self, state=None):
-        """the trainer's state (StepEngine.pg_state's dict; with kl_penalty also `kl_coef`); set: the run continues bit for bit"""
+        """the trainer's state (StepEngine.pg_state's dict; with kl_penalty also `kl_coef`, with MLPPolicy(frames > 1) also
+        `obs_history`); set: the run continues bit for bit"""
+        return history_carry(self.engine, self._state, state)
+
+    def load_state(self, state):
+        self.state(state)
+
+    def _state(self, state):
         if state is None:
             st = self.engine.pg_state()
             if self.kl_penalty is not None:
@@ -375,7 +384,14 @@ class PGPopulationTrainer:
         return r.reshape(self.members, -1).mean(axis=1)
 
     def state(self, member, state=None):
-        """one member's state (StepEngine.pg_pop_state's dict; with kl_penalty also `kl_coef`)"""
+        """one member's state (StepEngine.pg_pop_state's dict; with kl_penalty also `kl_coef`, with MLPPolicy(frames > 1) also
+        `obs_history`, its own envs')"""
+        return history_carry(self.engine, lambda s: self._state(member, s), state, member, self.engine.num_envs // self.members)
+
+    def load_state(self, member, state):
+        self.state(member, state)
+
+    def _state(self, member, state):
         if state is None:
             st = self.engine.pg_pop_state(member)
             if self.kl_penalty is not None:

@@ -12,6 +12,7 @@ import copy
 
 import numpy as np
 
+from .mlp_policy import history_carry
 from .td3_trainer import NORM_OPTIONS, PrioritizedReplay, _norm_options, _norm_state, _with_vectors, policy_from_actor, random_critics
 
 
@@ -100,7 +101,7 @@ class SACTrainer(PrioritizedReplay, _NormalizedSAC):
         engine.mlp_set_squash(self.action_lo, self.action_hi)
         engine.rollout_enable(self.horizon, obs=True)
         engine.sac_init(**self.config)
-        engine.sac_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed))
+        engine.sac_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed, policy.frames))
         if self._norm_on():
             engine.sac_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self._prio_init(engine, prioritized_replay)
@@ -135,7 +136,7 @@ class SACTrainer(PrioritizedReplay, _NormalizedSAC):
     def state(self, state=None):
         """the learner's state (StepEngine.sac_state's dict), `replay_prio` under prioritised replay and `norm` under running
         normalisers; get or set.  With the ring (sac_buffer) a resumed run continues bit for bit"""
-        return self._norm_carry(lambda s: self._prio_state(self.engine.sac_state, 0, s), 0, state)
+        return history_carry(self.engine, lambda t: self._norm_carry(lambda s: self._prio_state(self.engine.sac_state, 0, s), 0, t), state)
 
     def load_state(self, state):
         self.state(state)
@@ -207,7 +208,7 @@ class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
         engine.rollout_enable(self.horizon, obs=True)
         engine.sac_pop_init(self.configs)
         for m in range(members):
-            engine.sac_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]))
+            engine.sac_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m], policies[0].frames))
         if self._norm_on():
             engine.sac_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self._prio_init(engine, prioritized_replay)
@@ -248,7 +249,8 @@ class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
         """member's state (StepEngine.sac_pop_state's dict), `replay_prio` under prioritised replay and `norm` under running
         normalisers; get or set"""
         envs = self.engine.num_envs // self.members
-        return self._norm_carry(lambda s: self._prio_state(lambda t: self.engine.sac_pop_state(member, t), member, s), member, state, envs)
+        return history_carry(self.engine, lambda u: self._norm_carry(lambda s: self._prio_state(lambda t: self.engine.sac_pop_state(member, t), member, s),
+                                                                     member, u, envs), state, member, envs)
 
     def load_state(self, member, state):
         self.state(member, state)

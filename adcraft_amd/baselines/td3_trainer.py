@@ -13,6 +13,8 @@ import copy
 
 import numpy as np
 
+from .mlp_policy import history_carry
+
 
 def td3(**overrides):
     """Fujimoto et al.'s configuration: gamma 0.99, tau 0.005, actor and targets every 2nd update, target noise 0.2 clipped at
@@ -24,12 +26,12 @@ def td3(**overrides):
     return cfg
 
 
-def random_critics(K, hidden, seed=0):
-    """two critics on the 6K + 3 inputs [x | action] with torch's default Linear initialisation: weights and biases uniform in
-    +- 1 / sqrt(n_in)"""
+def random_critics(K, hidden, seed=0, frames=1):
+    """two critics on the frames (5K + 2) + K + 1 inputs [x | action] with torch's default Linear initialisation: weights and
+    biases uniform in +- 1 / sqrt(n_in)"""
     rng, out = np.random.default_rng(seed), []
     for _ in range(2):
-        layers, n_in = [], 6 * K + 3
+        layers, n_in = [], int(frames) * (5 * K + 2) + K + 1
         for n_out in list(hidden) + [1]:
             bound = 1.0 / np.sqrt(n_in)
             layers.append((rng.uniform(-bound, bound, (n_in, n_out)).astype(np.float32), rng.uniform(-bound, bound, n_out).astype(np.float32)))
@@ -178,7 +180,7 @@ class TD3Trainer(PrioritizedReplay):
         engine.mlp_init(self._template, seeds=agent_seeds, deterministic=False)
         engine.rollout_enable(self.horizon, obs=True)
         engine.td3_init(**self.config)
-        engine.td3_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed), action_norm=action_norm)
+        engine.td3_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed, policy.frames), action_norm=action_norm)
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self._prio_init(engine, prioritized_replay)
@@ -215,7 +217,12 @@ class TD3Trainer(PrioritizedReplay):
         return _with_vectors(pol, self.engine.td3_norm_state()) if self.normalize_observations else pol
 
     def state(self, state=None):
-        return self._prio_state(self.engine.td3_state, 0, state)
+        """the learner's state (StepEngine.td3_state's dict), `replay_prio` under prioritised replay and `obs_history` with
+        MLPPolicy(frames > 1); get or set"""
+        return history_carry(self.engine, lambda s: self._prio_state(self.engine.td3_state, 0, s), state)
+
+    def load_state(self, state):
+        self.state(state)
 
     def norm_state(self, state=None):
         """the normalisers' state: StepEngine.td3_norm_state's dict plus `returns`, the envs' running discounted returns; get or set"""
@@ -286,7 +293,7 @@ class TD3PopulationTrainer(PrioritizedReplay):
         engine.rollout_enable(self.horizon, obs=True)
         engine.td3_pop_init(self.configs)
         for m in range(members):
-            engine.td3_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m]), action_norm=norms[0] if m == 0 else None)
+            engine.td3_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m], policies[0].frames), action_norm=norms[0] if m == 0 else None)
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self._prio_init(engine, prioritized_replay)
@@ -329,7 +336,12 @@ class TD3PopulationTrainer(PrioritizedReplay):
         return r.reshape(self.members, -1).mean(axis=1)
 
     def state(self, member, state=None):
-        return self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, state)
+        """member's state; `obs_history` (with MLPPolicy(frames > 1)) holds its own envs'"""
+        return history_carry(self.engine, lambda t: self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, t), state, member,
+                             self.engine.num_envs // self.members)
+
+    def load_state(self, member, state):
+        self.state(member, state)
 
     def norm_state(self, member, state=None):
         """member's normalisers (TD3Trainer.norm_state's dict; `returns` holds the member's own envs')"""

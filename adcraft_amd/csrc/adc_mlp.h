@@ -35,6 +35,23 @@
 //              e[a] = lo[a] + half[a] * (t + 1) (a sum, a product, a sum), half[a] = 0.5 * (hi[a] - lo[a]) formed once on the
 //              host.  The bid and the budget are taken from e as above.  The recorded action, the last act's action and the
 //              log-probability stay those of the unsquashed a; a deterministic act squashes the mean.
+//
+// Observation history (adc_engine_mlp_init_frames, frames = H in 1..8; H = 1 is everything above, untouched).  D0 = 5K+2.
+//   row        D = H * D0; x[f * D0 + j], f < H, j < D0.  Frame 0 is the input above (mlp_obs_at, or zeros when the env's episode
+//              day d is 0).  Frame f >= 1 is the raw frame 0 that the act on episode day d - f read if that frame is valid, else
+//              zeros.
+//   history    hist[N][H][D0], raw float32 (before normalisation).  The act on day d writes its raw frame 0 to slot d mod H after
+//              every read of the workgroup (a barrier; frames 1 .. H-1 read the slots (d - f) mod H, never that one).  A second
+//              act on the same day (replayed normals) writes the same bits.
+//   validity   two words per env: last (the episode day of the last act; -2: none) and from.  At an act on day d:
+//              d == 0: from = 0; else if last is neither d - 1 nor d: from = d.  Frame f is valid iff d - f >= from.  Then
+//              last = d.  So an auto-reset clears the history through day 0, and days stepped without the agent restart it;
+//              an explicit adc_engine_reset sets last = -2 for the envs it resets.  One case is not detected: an auto-reset
+//              followed by exactly last + 1 days without an act reads the old episode's frames as the new one's.
+//   peek       adc_engine_mlp_bootstrap_value and the x' of a trainer's last stored day evaluate the same rule for "the row an
+//              act would read now" and write nothing: not hist, not last, not from.
+//   normalise  per position over the whole row: x[i] = (x[i] - shift[i]) * scale[i], i < D, zero frames included (as the first
+//              day's zeros are).  The record's obs row is all D of it, normalised or raw as above.
 #pragma once
 #include "adc_law.h"
 
@@ -208,6 +225,27 @@ ADC_HD float mlp_obs_at(int j, int K, const int32_t *clk, const float *cost, con
     if (j < K) return (float)imp[j];
     if (j < 2 * K) return rev[j - K];
     return (float)conv[j - 2 * K];
+}
+
+// ---- observation history (the header comment's law) ------------------------------------------------------------------------
+constexpr int kMlpMaxFrames = 8;
+constexpr int32_t kMlpHistNone = -2;       // `last` of an env that has not acted since its explicit reset
+// `from` as an act on episode day d sees it
+ADC_HD int32_t mlp_hist_from(int32_t d, int32_t last, int32_t from)
+{
+    if (d == 0) return 0;
+    if (last != d - 1 && last != d) return d;
+    return from;
+}
+ADC_HD bool mlp_hist_valid(int32_t d, int f, int32_t from) { return d - (int32_t)f >= from; }
+// the slot of the frame that the act on episode day d wrote
+ADC_HD int mlp_hist_slot(int32_t d, int H) { return (int)(d % (int32_t)H); }
+// element i >= D0 of the stacked row of one env: hist is the env's [H][D0]
+ADC_HD float mlp_hist_at(int i, int D0, int H, const float *hist, int32_t d, int32_t from)
+{
+    const int f = i / D0, j = i - f * D0;
+    if (!mlp_hist_valid(d, f, from)) return 0.0f;
+    return hist[(size_t)mlp_hist_slot(d - (int32_t)f, H) * (size_t)D0 + (size_t)j];
 }
 
 // splitmix64

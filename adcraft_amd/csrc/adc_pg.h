@@ -106,12 +106,13 @@ ADC_HD int pg_param_count(const PgShape &s)
     return q;
 }
 
-// from an adc_mlp_config (include/adcraft_engine.h) for num_keywords keywords
+// from an adc_mlp_config (include/adcraft_engine.h) for num_keywords keywords; frames: the policy's observation history
+// (adc_mlp.h), its input row is that many flat observations wide
 template <class MlpConfig>
-inline PgShape pg_shape_of(const MlpConfig &c, int K)
+inline PgShape pg_shape_of(const MlpConfig &c, int K, int frames = 1)
 {
     PgShape s{};
-    s.A = K + 1; s.D = 5 * K + 2;
+    s.A = K + 1; s.D = frames * (5 * K + 2);
     s.activation = c.activation == 0 ? kMlpTanh : kMlpRelu;
     s.clamp = c.clamp_log_std != 0; s.ls_lo = c.log_std_lo; s.ls_hi = c.log_std_hi;
     s.layers[0] = c.n_policy_layers; s.layers[1] = c.n_value_layers;

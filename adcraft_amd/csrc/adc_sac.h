@@ -55,9 +55,9 @@ inline SacLaw sac_law_of(const MlpConfig &m, const SacConfig &c)
 }
 // the networks' shape: adc_td3.h's, with the actor's last width 2A
 template <class MlpConfig, class SacConfig>
-inline Td3Shape sac_shape_of(const MlpConfig &m, int K, const SacConfig &c)
+inline Td3Shape sac_shape_of(const MlpConfig &m, int K, const SacConfig &c, int frames = 1)
 {
-    return td3_shape_of(m, K, c, 0);
+    return td3_shape_of(m, K, c, 0, frames);
 }
 
 ADC_HD float sac_noise(uint64_t key, uint32_t stage, int a, uint32_t b, uint32_t update)

@@ -538,6 +538,22 @@ std::vector<float> mlp_forward_host(const float *x0, int D, int layers, const in
 }
 }  // namespace
 
+ADC_EXPORT int adc_mlp_stack_row_host(int32_t num_keywords, int32_t frames, const float *frame0_d0, float *hist_hd0, int32_t *last, int32_t *from,
+                                      int32_t day, int32_t commit, float *row_d)
+{
+    if (num_keywords < 1 || frames < 1 || frames > adc::kMlpMaxFrames || day < 0 || !hist_hd0 || !last || !from || !row_d) return ADC_EINVAL;
+    const int D0 = 5 * num_keywords + 2, D = frames * D0;
+    const int32_t fr = adc::mlp_hist_from(day, *last, *from);
+    for (int i = 0; i < D; ++i) row_d[i] = i < D0 ? (frame0_d0 && day != 0 ? frame0_d0[i] : 0.0f) : adc::mlp_hist_at(i, D0, frames, hist_hd0, day, fr);
+    if (commit) {
+        float *slot = hist_hd0 + (size_t)adc::mlp_hist_slot(day, frames) * (size_t)D0;
+        for (int j = 0; j < D0; ++j) slot[j] = row_d[j];
+        *last = day;
+        *from = fr;
+    }
+    return ADC_OK;
+}
+
 ADC_EXPORT int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords, const float *obs_d, const float *const *policy_w,
                                 const float *const *policy_b, const float *const *value_w, const float *const *value_b, const float *shift_d,
                                 const float *scale_d, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,

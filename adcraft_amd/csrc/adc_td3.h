@@ -92,12 +92,13 @@ struct Td3Law {
     float gamma, tau, noise, noise_clip, lo, hi, reward_scale;
 };
 
-// from an adc_mlp_config and an adc_td3_config (include/adcraft_engine.h) for num_keywords keywords
+// from an adc_mlp_config and an adc_td3_config (include/adcraft_engine.h) for num_keywords keywords; frames: the policy's
+// observation history (adc_mlp.h), its input row is that many flat observations wide
 template <class MlpConfig, class Td3Config>
-inline Td3Shape td3_shape_of(const MlpConfig &m, int K, const Td3Config &c, int norm)
+inline Td3Shape td3_shape_of(const MlpConfig &m, int K, const Td3Config &c, int norm, int frames = 1)
 {
     Td3Shape s{};
-    s.A = K + 1; s.D = 5 * K + 2; s.norm = norm;
+    s.A = K + 1; s.D = frames * (5 * K + 2); s.norm = norm;
     s.activation = m.activation == 0 ? kMlpTanh : kMlpRelu;
     s.pol.layers = m.n_policy_layers; s.pol.n_in = s.D;
     s.q.layers = c.n_critic_layers; s.q.n_in = s.D + s.A;

@@ -1250,6 +1250,11 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
                            s->rew.G);
         err = hipGetLastError();
     }
+    // (... and so does its observation history; nothing is enqueued without one)
+    if (err == hipSuccess && e->have_mlp && e->mp.hist) {
+        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, d_mask, e->mp.last);
+        err = hipGetLastError();
+    }
     hipError_t err2 = hipStreamSynchronize(e->stream);
     if (d_mask) (void)hipFree(d_mask);
     if (d_seeds) (void)hipFree(d_seeds);
@@ -2843,28 +2848,25 @@ inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
     const size_t oa = e0 * (size_t)p.A;
     p.key += e0; p.tick += e0; p.mean += oa; p.ls += oa; p.action += oa; p.logp += e0; p.value += e0;
     if (p.member) p.member += e0;
+    if (p.hist) { p.hist += e0 * (size_t)p.D; p.last += e0; p.from += e0; }        // (an env's frames are D = frames * (5K+2) floats)
     return p;
 }
+// the frames of the policy's input row (1 before adc_engine_mlp_init)
+inline int mlp_frames(const adc_engine *e) { return e->mp.frames > 1 ? e->mp.frames : 1; }
 void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode, const float *replay_z, float budget_override, float *d_bids,
                        float *d_budget, const MlpRecordSlot &rec, float *value_out)
 {
     // (three instantiations: without members the kernel is the single-policy code, untouched by the members' addressing; learners
-    // have no pop_stride; the squashed forms are instantiations of their own)
-    if (p.member && p.pop_stride == 0 && p.sq_lo)
-        hipLaunchKernelGGL((k_mlp_policy<2, true>), dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
-                           budget_override, d_bids, d_budget, rec, value_out);
-    else if (p.member && p.pop_stride == 0)
-        hipLaunchKernelGGL(k_mlp_policy<2>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
-                           budget_override, d_bids, d_budget, rec, value_out);
-    else if (p.member)
-        hipLaunchKernelGGL(k_mlp_policy<1>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
-                           budget_override, d_bids, d_budget, rec, value_out);
-    else if (p.sq_lo)
-        hipLaunchKernelGGL((k_mlp_policy<0, true>), dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
-                           budget_override, d_bids, d_budget, rec, value_out);
-    else
-        hipLaunchKernelGGL(k_mlp_policy<0>, dim3((unsigned)v.N), dim3(kMlpBlock), mlp_lds_floats(p.D, p.P) * sizeof(float), st, v, p, mode, replay_z,
-                           budget_override, d_bids, d_budget, rec, value_out);
+    // have no pop_stride; the squashed forms are instantiations of their own, and so are the ones with an observation history)
+    const dim3 grid((unsigned)v.N), block(kMlpBlock);
+    const size_t lds = mlp_lds_floats(p.D, p.P) * sizeof(float);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, lds, st, v, p, mode, replay_z, budget_override, d_bids, d_budget, rec, value_out); };
+    const bool hist = p.hist != nullptr;
+    if (p.member && p.pop_stride == 0 && p.sq_lo) hist ? launch(k_mlp_policy<2, true, true>) : launch(k_mlp_policy<2, true>);
+    else if (p.member && p.pop_stride == 0) hist ? launch(k_mlp_policy<2, false, true>) : launch(k_mlp_policy<2>);
+    else if (p.member) hist ? launch(k_mlp_policy<1, false, true>) : launch(k_mlp_policy<1>);
+    else if (p.sq_lo) hist ? launch(k_mlp_policy<0, true, true>) : launch(k_mlp_policy<0, true>);
+    else hist ? launch(k_mlp_policy<0, false, true>) : launch(k_mlp_policy<0>);
 }
 int mlp_ready(const adc_engine *e)
 {
@@ -3052,12 +3054,20 @@ int params_fetch(adc_engine *e, const ParamStore &s, float *flat)
 
 ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n)
 {
+    return adc_engine_mlp_init_frames(e, cfg, seeds_n, 1);
+}
+
+ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t frames)
+{
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     const char *why = nullptr;
     if (adc_mlp_config_check(cfg, e->v.K, &why) != ADC_OK) return fail(ADC_EINVAL, why);
-    const int K = e->v.K, A = K + 1, D = 5 * K + 2;
+    if (frames < 1 || frames > adc::kMlpMaxFrames) return fail(ADC_EINVAL, "frames: 1 to 8");
+    const int K = e->v.K, A = K + 1, D0 = 5 * K + 2, D = frames * D0;
     const int P = cfg->policy_widths[cfg->n_policy_layers - 1];
-    if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
+    if (mlp_lds_floats(D0, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
+    if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u)
+        return fail(ADC_EINVAL, "frames: the stacked input row is too large for the MLP policy (LDS); fewer frames fit");
     ENGINE_GUARD(e);
     population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
     learners_drop(e);
@@ -3118,6 +3128,10 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
         (rc = mlp_alloc(e, e->mlp_allocs, &p.value, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_boot, N)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_sq, (size_t)2 * A)))
         return rc;                      // (squash is off after a re-initialisation: p.sq_lo is null)
+    p.frames = frames;
+    if (frames > 1 && ((rc = mlp_alloc(e, e->mlp_allocs, &p.hist, N * (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.last, N)) ||
+                       (rc = mlp_alloc(e, e->mlp_allocs, &p.from, N))))
+        return rc;
     e->mp = p;
     e->mlp_cfg = *cfg;
     std::memset(e->mlp_layer_set, 0, sizeof(e->mlp_layer_set));
@@ -3130,6 +3144,10 @@ ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, con
     }
     if (err == hipSuccess) {
         hipLaunchKernelGGL(k_mlp_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, e->mp, (int)N, d_seeds, e->cfg.seed, e->cfg.env_id_base);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess && e->mp.hist) {          // no env has acted
+        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, nullptr, e->mp.last);
         err = hipGetLastError();
     }
     const hipError_t err2 = hipStreamSynchronize(e->stream);
@@ -3314,6 +3332,45 @@ ADC_EXPORT int adc_engine_mlp_agent_state(adc_engine *e, uint64_t *keys_n, uint3
     return ADC_OK;
 }
 
+ADC_EXPORT int adc_engine_mlp_frames(adc_engine *e, int32_t *frames)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (!frames) return fail(ADC_EINVAL, "frames is NULL");
+    *frames = mlp_frames(e);
+    return ADC_OK;
+}
+
+// the observation history to the host and back (any pointer may be NULL); without one (frames = 1) there is nothing to move
+ADC_EXPORT int adc_engine_mlp_history_get(adc_engine *e, float *hist_nhd, int32_t *last_n, int32_t *from_n)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (!e->mp.hist) return fail(ADC_ESTATE, "the policy has no observation history (adc_engine_mlp_init_frames, frames > 1)");
+    const size_t n = (size_t)e->v.N;
+    if (hist_nhd) HIP_TRY(hipMemcpyAsync(hist_nhd, e->mp.hist, n * (size_t)e->mp.D * 4, hipMemcpyDeviceToHost, e->stream));
+    if (last_n) HIP_TRY(hipMemcpyAsync(last_n, e->mp.last, n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (from_n) HIP_TRY(hipMemcpyAsync(from_n, e->mp.from, n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_mlp_history_set(adc_engine *e, const float *hist_nhd, const int32_t *last_n, const int32_t *from_n)
+{
+    ENGINE_GUARD(e);
+    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
+    if (!e->mp.hist) return fail(ADC_ESTATE, "the policy has no observation history (adc_engine_mlp_init_frames, frames > 1)");
+    const size_t n = (size_t)e->v.N;
+    // (the kernels index the frames by these words: nothing a history cannot hold gets in)
+    for (size_t i = 0; i < n; ++i)
+        if ((last_n && last_n[i] < adc::kMlpHistNone) || (from_n && from_n[i] < 0)) return fail(ADC_EINVAL, "history: last >= -2 and from >= 0");
+    if (hist_nhd) HIP_TRY(hipMemcpyAsync(e->mp.hist, hist_nhd, n * (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
+    if (last_n) HIP_TRY(hipMemcpyAsync(e->mp.last, last_n, n * 4, hipMemcpyHostToDevice, e->stream));
+    if (from_n) HIP_TRY(hipMemcpyAsync(e->mp.from, from_n, n * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
 ADC_EXPORT int adc_engine_mlp_bootstrap_value(adc_engine *e, float *value_n)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
@@ -3452,7 +3509,7 @@ ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
     ENGINE_GUARD(e);
     if (M == 0) { learners_drop(e); return ADC_OK; }
     // a member's block: the policy layers, the value layers, log_std, each starting on a 16-byte boundary; the flat order against it
-    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K);
+    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K, mlp_frames(e));
     size_t offW[2][adc::kMlpMaxLayers] = {}, offb[2][adc::kMlpMaxLayers] = {}, off_ls = 0;       // floats from the member's base
     PgLayout lay{};
     size_t off = 0;

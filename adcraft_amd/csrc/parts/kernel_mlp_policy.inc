@@ -30,7 +30,7 @@ struct MlpView {
     const float *log_std;                   // [A] free parameter vector (head of A outputs)
     int activation, two_heads, clamp, deterministic;
     float ls_lo, ls_hi, clip_hi;
-    int A, D, P;                            // action size K+1, input size 5K+2, the policy network's outputs (A or 2A)
+    int A, D, P;                            // action size K+1, input size frames * (5K+2), the policy network's outputs (A or 2A)
     uint64_t *key;                          // [N] the agent's own stream (stage ST_MLP)
     uint32_t *tick;                         // [N]
     float *mean, *ls, *action;              // [N][A] of the last act
@@ -49,6 +49,10 @@ struct MlpView {
     // the squashed action (adc_engine_mlp_set_squash; with learners adc_engine_mlp_learners_set_squash): the env is given
     // lo + half * (tanh(a) + 1).  null: off
     const float *sq_lo, *sq_half;           // [A]
+    // the observation history (adc_engine_mlp_init_frames, frames > 1; adc_mlp.h): null / 1 without one
+    float *hist;                            // [N][frames][5K+2] raw frames, slot = episode day mod frames
+    int32_t *last, *from;                   // [N] the episode day of the last act (-2: none); the first day whose frame is valid
+    int frames;
 };
 
 // where one recorded day goes: the slot's rows of the view's first env (null: that field is off)
@@ -127,6 +131,24 @@ __device__ __forceinline__ void mlp_network(const MlpNet &net, const MlpView &p,
     }
 }
 
+// Element i of the raw input row an act of `env` would read now: frame 0 from the engine's output arrays (zeros on the first day
+// of an episode), with a history (kHist) frames 1 .. H-1 from the env's raw frames under `from` (adc::mlp_hist_from of the
+// env's words: the caller reads them once).  The act and mode 1 of the kernels with a history and the trainers' store bodies
+// all form their rows with it (the kernels without one keep the statements they had, which are its kHist = false case);
+// consecutive i are consecutive floats of one frame, so a wavefront's loads are coalesced.
+template <bool kHist>
+__device__ __forceinline__ float mlp_row_raw_at(const View &v, const float *__restrict__ hist, int frames, int env, int i, bool first, double cum,
+                                                int32_t days, int32_t d, int32_t from)
+{
+    const int K = v.K;
+    const size_t o = (size_t)env * K;
+    if constexpr (kHist) {
+        const int D0 = 5 * K + 2;
+        if (i >= D0) return adc::mlp_hist_at(i, D0, frames, hist + (size_t)env * (size_t)frames * (size_t)D0, d, from);
+    }
+    return first ? 0.0f : adc::mlp_obs_at(i, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
+}
+
 // mode 0: act (policy and value networks, sample, actions, record);  mode 1: the value network alone into value_out (the
 // bootstrap value of the observation the last step left) - no draw, no tick, nothing else written.
 // kMembers 0: every env runs `pol`;  1: the env's policy layers are its member's (a population);  2: the policy layers, the
@@ -135,7 +157,9 @@ __device__ __forceinline__ void mlp_network(const MlpNet &net, const MlpView &p,
 // kSquash: the env is given the squashed action (adc::mlp_squash).  The single-policy kernel has that form
 // (adc_engine_mlp_set_squash) and the learners' kernel has it (adc_engine_mlp_learners_set_squash: one pair of bounds for all
 // members); without it the three kernels compute what they computed before there was one.
-template <int kMembers, bool kSquash = false>
+// kHist: the input row is the last `frames` raw observations (adc_mlp.h, observation history); mode 0 then writes this act's
+// raw frame 0 and the env's two validity words, mode 1 writes none of them.  Without it the kernels are the code they were.
+template <int kMembers, bool kSquash = false, bool kHist = false>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int mode, const float *__restrict__ replay_z,
                                                           float budget_override, float *__restrict__ bids, float *__restrict__ budgets,
                                                           MlpRecordSlot rec, float *__restrict__ value_out)
@@ -145,21 +169,37 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
     const int tid = threadIdx.x, K = v.K, D = p.D, A = p.A, env = blockIdx.x;
     // the input row: zeros on the first day of an episode (the reset observation), else the last step's outputs
     {
+        // (without a history the loop below is, statement for statement, the code it was: the instantiations that existed before
+        // the history keep their register allocation)
         const bool first = v.day[env] == 0;
+        const int32_t d = kHist ? v.day[env] : 0;
         const size_t o = (size_t)env * K;
         const double cum = v.cum_profit[env];
         const int32_t days = v.day_out[env];
+        int32_t from = 0;
+        if constexpr (kHist) from = adc::mlp_hist_from(d, p.last[env], p.from[env]);
         // (learners may have a normaliser each: the env's member's row of the vectors; the stride is 0 whenever they are shared)
         const size_t no = kMembers == 2 ? (size_t)p.member[env] * p.norm_stride : 0;
         for (int j = tid; j < D; j += kMlpBlock) {
-            float xj = first ? 0.0f : adc::mlp_obs_at(j, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
+            float xj;
+            if constexpr (kHist) xj = mlp_row_raw_at<true>(v, p.hist, p.frames, env, j, first, cum, days, d, from);
+            else xj = first ? 0.0f : adc::mlp_obs_at(j, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
             const float raw = xj;
             if (p.shift) xj = adc::mlp_normalize(xj, p.shift[no + j], p.scale[no + j]);
             mlp_lds[j] = xj;
             if (mode == 0 && rec.obs) rec.obs[(size_t)env * D + j] = rec.raw_obs ? raw : xj;
         }
+        __syncthreads();
+        if constexpr (kHist) {
+            // every read of the history is behind the barrier: this act's raw frame 0 into slot d mod H, then the validity words
+            if (mode == 0) {
+                const int D0 = 5 * K + 2;
+                float *slot = p.hist + ((size_t)env * (size_t)p.frames + (size_t)adc::mlp_hist_slot(d, p.frames)) * (size_t)D0;
+                for (int j = tid; j < D0; j += kMlpBlock) slot[j] = mlp_row_raw_at<false>(v, nullptr, 1, env, j, first, cum, days, d, 0);
+                if (tid == 0) { p.last[env] = d; p.from[env] = from; }
+            }
+        }
     }
-    __syncthreads();
     float *out = mlp_lds + D + 2 * adc::kMlpMaxWidth;
     const MlpLearner *lm = kMembers == 2 ? p.learners + p.member[env] : nullptr;
     if (p.val.layers > 0) {
@@ -221,6 +261,14 @@ __global__ void k_mlp_record_outcome(View v, float *__restrict__ reward, uint8_t
     reward[env] = (float)v.reward[env];
     term[env] = v.term[env];
     trunc[env] = v.trunc[env];
+}
+
+// an explicit reset forgets the history of the envs it resets (mask null: all)
+__global__ void k_mlp_hist_forget(int N, const uint8_t *__restrict__ mask, int32_t *__restrict__ last)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N || (mask && !mask[env])) return;
+    last[env] = adc::kMlpHistNone;
 }
 
 __global__ void k_mlp_init(MlpView p, int N, const uint64_t *seeds, uint64_t seed, int64_t env_id_base)

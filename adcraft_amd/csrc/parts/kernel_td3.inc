@@ -113,13 +113,17 @@ __device__ __forceinline__ void td3_input_back(const float *__restrict__ W, int 
 
 // sample s = (t - t0) * n + local env of the recorded days [t0, t1) of the member's envs [member n, (member + 1) n) into slot
 // (written + s) mod C of its ring
+// kHist: the policy has an observation history (adc_mlp.h): the last day's x' is the stacked row, peeked (nothing is written)
+template <bool kHist = false>
 __device__ __forceinline__ void td3_store_body(const View &v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
                                                const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
                                                const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
                                                const uint8_t *__restrict__ ro_trunc, int t0, int t1, int n, int member, const Td3Ring ring,
-                                               unsigned long long written, unsigned long long C)
+                                               unsigned long long written, unsigned long long C, const float *__restrict__ hist = nullptr,
+                                               const int32_t *__restrict__ h_last = nullptr, const int32_t *__restrict__ h_from = nullptr,
+                                               int frames = 1)
 {
-    const int tid = threadIdx.x, N = v.N, K = v.K;
+    const int tid = threadIdx.x, N = v.N;
     const unsigned long long s = blockIdx.x, count = (unsigned long long)(t1 - t0) * (unsigned long long)n;
     if (s >= count || s + C < count) return;            // (a later sample of this store lands on the same slot)
     const int t = t0 + (int)(s / (unsigned long long)n), env = member * n + (int)(s % (unsigned long long)n);
@@ -135,12 +139,14 @@ __device__ __forceinline__ void td3_store_body(const View &v, const float *__res
         for (int j = tid; j < D; j += kPgBlock) ring.x2[slot * (size_t)D + j] = ro_obs[next * (size_t)D + j];
     } else {
         // the input row an act would read now (k_mlp_policy's prologue)
-        const bool first = v.day[env] == 0;
-        const size_t o = (size_t)env * K;
+        const int32_t d = v.day[env];
+        const bool first = d == 0;
         const double cum = v.cum_profit[env];
         const int32_t days = v.day_out[env];
+        int32_t from = 0;
+        if constexpr (kHist) from = adc::mlp_hist_from(d, h_last[env], h_from[env]);
         for (int j = tid; j < D; j += kPgBlock) {
-            float xj = first ? 0.0f : adc::mlp_obs_at(j, K, v.clk + o, v.cost + o, v.imp + o, v.rev + o, v.conv + o, cum, days);
+            float xj = mlp_row_raw_at<kHist>(v, hist, frames, env, j, first, cum, days, d, from);
             if (shift) xj = adc::mlp_normalize(xj, shift[j], scale[j]);
             ring.x2[slot * (size_t)D + j] = xj;
         }
@@ -153,6 +159,17 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_store(View v, const float *__r
                                                         unsigned long long written, unsigned long long C)
 {
     td3_store_body(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, v.N, 0, ring, written, C);
+}
+// ... with an observation history (adc_engine_mlp_init_frames, frames > 1)
+__global__ __launch_bounds__(kPgBlock) void k_td3_store_hist(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
+                                                             const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                             const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                             const uint8_t *__restrict__ ro_trunc, int t0, int t1, Td3Ring ring,
+                                                             unsigned long long written, unsigned long long C, const float *__restrict__ hist,
+                                                             const int32_t *__restrict__ h_last, const int32_t *__restrict__ h_from, int frames)
+{
+    td3_store_body<true>(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, v.N, 0, ring, written, C, hist, h_last,
+                         h_from, frames);
 }
 
 __global__ void k_td3_indices(uint64_t key, uint32_t update, uint32_t size, int B, int32_t *__restrict__ out)

@@ -187,11 +187,14 @@ ADC_EXPORT int adc_engine_pg_init(adc_engine *e, const adc_pg_config *cfg)
     const int N = e->v.N, mb = cfg->minibatch_envs == 0 ? N : cfg->minibatch_envs;
     if (mb > N || N % mb != 0) return fail(ADC_EINVAL, "minibatch_envs must divide num_envs");
     if (pg_chunks((long long)e->ro_T * mb) > 65535) return fail(ADC_EINVAL, "horizon x minibatch_envs: at most 65535 x 1024 samples in a minibatch");
-    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K);
+    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K, mlp_frames(e));
     int maxw = 1;
     for (int net = 0; net < 2; ++net)
         for (int l = 0; l < sh.layers[net]; ++l) maxw = std::max(maxw, sh.n_out[net][l]);
-    if (pg_lds_floats(sh, maxw) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for policy-gradient training (LDS)");
+    if (pg_lds_floats(sh, maxw) * sizeof(float) > 64u * 1024u)
+        return fail(ADC_EINVAL, pg_lds_floats(adc::pg_shape_of(e->mlp_cfg, e->v.K), maxw) * sizeof(float) > 64u * 1024u
+                                    ? "num_keywords too large for policy-gradient training (LDS)"
+                                    : "frames: the stacked input row is too large for policy-gradient training (LDS); fewer frames fit");
     ENGINE_GUARD(e);
     // the flat order against the device's stores
     PgLayout lay{};
@@ -543,11 +546,14 @@ ADC_EXPORT int adc_engine_pg_pop_init(adc_engine *e, const adc_pg_config *cfgs, 
     if (pg_chunks((long long)e->ro_T * n) > 65535) return fail(ADC_EINVAL, "horizon x envs of a member: at most 65535 x 1024 samples");
     if (pg_chunks((long long)e->ro_T * mb) > 65535) return fail(ADC_EINVAL, "horizon x minibatch_envs: at most 65535 x 1024 samples in a minibatch");
     // (the member is the grid's y or z: adc_engine_mlp_learners admits at most 65535)
-    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K);
+    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K, mlp_frames(e));
     int maxw = 1;
     for (int net = 0; net < 2; ++net)
         for (int l = 0; l < sh.layers[net]; ++l) maxw = std::max(maxw, sh.n_out[net][l]);
-    if (pg_lds_floats(sh, maxw) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for policy-gradient training (LDS)");
+    if (pg_lds_floats(sh, maxw) * sizeof(float) > 64u * 1024u)
+        return fail(ADC_EINVAL, pg_lds_floats(adc::pg_shape_of(e->mlp_cfg, e->v.K), maxw) * sizeof(float) > 64u * 1024u
+                                    ? "num_keywords too large for policy-gradient training (LDS)"
+                                    : "frames: the stacked input row is too large for policy-gradient training (LDS); fewer frames fit");
     ENGINE_GUARD(e);
     const size_t Q = (size_t)e->lrn_lay.Q, tn = (size_t)e->ro_T * (size_t)N, smax = (size_t)e->ro_T * (size_t)mb, Ms = (size_t)M;
     const size_t part_stride = (size_t)pg_chunks((long long)std::max((size_t)e->ro_T * (size_t)n, Q)) * 8u + 8u;

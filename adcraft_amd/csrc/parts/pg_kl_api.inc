@@ -108,7 +108,10 @@ ADC_EXPORT int adc_engine_pg_kl_init(adc_engine *e, const adc_pg_kl_config *cfgs
         if (adc_pg_kl_config_check(cfgs + i, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     }
     const adc::PgShape &sh = e->pg_shape;
-    if (pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the KL penalty (LDS)");
+    if (pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float) > 64u * 1024u)
+        return fail(ADC_EINVAL, pg_lds_floats(adc::pg_shape_of(e->mlp_cfg, e->v.K), e->pg_maxw, true) * sizeof(float) > 64u * 1024u
+                                    ? "num_keywords too large for the KL penalty (LDS)"
+                                    : "frames: the stacked input row is too large for the KL penalty (LDS); fewer frames fit");
     const size_t tna = (size_t)e->ro_T * (size_t)e->v.N * (size_t)sh.A;
     if ((size_t)e->ro_T * (size_t)e->v.N > 0x7FFFFFFFull) return fail(ADC_EINVAL, "horizon x num_envs: at most 2^31 - 1 recorded rows under the KL penalty");
     ENGINE_GUARD(e);

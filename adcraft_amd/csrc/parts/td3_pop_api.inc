@@ -106,8 +106,11 @@ ADC_EXPORT int adc_engine_td3_pop_init(adc_engine *e, const adc_td3_config *cfgs
         return fail(ADC_ESTATE, "a policy-gradient trainer is alive on this engine: one trainer at a time owns the policy's weights");
     if (e->on.live)
         return fail(ADC_ESTATE, "a running observation normaliser is alive on this engine: the replay ring would hold inputs normalised by older vectors");
-    const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, cfgs[0], 0);
-    if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for off-policy training (LDS)");
+    const adc::Td3Shape sh = adc::td3_shape_of(e->mlp_cfg, e->v.K, cfgs[0], 0, mlp_frames(e));
+    if (td3_lds_floats(sh) * sizeof(float) > 64u * 1024u)
+        return fail(ADC_EINVAL, td3_lds_floats(adc::td3_shape_of(e->mlp_cfg, e->v.K, cfgs[0], 0)) * sizeof(float) > 64u * 1024u
+                                    ? "num_keywords too large for off-policy training (LDS)"
+                                    : "frames: the stacked input row is too large for off-policy training (LDS); fewer frames fit");
     ENGINE_GUARD(e);
     const size_t Ms = (size_t)M, C = (size_t)cfgs[0].capacity;
     const OffBlock k = off_block_layout(sh, 5);
@@ -187,10 +190,18 @@ ADC_EXPORT int adc_engine_td3_pop_store(adc_engine *e, int64_t *stored_per_membe
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;      // (a member's envs, not the engine's)
     // (raw rows under a running observation normaliser - TD3's set, e->tn)
-    hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
-                       e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
-                       e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
-                       (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
+    // (with an observation history the last day's x' is the stacked row, peeked)
+    if (e->mp.frames > 1)
+        hipLaunchKernelGGL(k_td3_pop_store_hist, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
+                           e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
+                           e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
+                           (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity,
+                           e->mp.hist, e->mp.last, e->mp.from, e->mp.frames);
+    else
+        hipLaunchKernelGGL(k_td3_pop_store, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
+                           e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
+                           e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,
+                           (unsigned long long)e->td3_written, (unsigned long long)e->td3_cfg.capacity);
     return off_store_done(e, count, stored_per_member);
 }
 

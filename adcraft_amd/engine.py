@@ -564,9 +564,14 @@ class StepEngine:
         """shapes and options of an MLPPolicy, then its weights; deterministic (if given) overrides the policy's own flag"""
         cfg = policy.config(self.num_keywords, deterministic)
         sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
-        check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
+        frames = int(getattr(policy, "frames", 1))
+        if frames == 1:
+            check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
+        else:
+            check(self._lib.adc_engine_mlp_init_frames(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data, frames))
         self._td3_norm = self._sac_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)
         self._mlp = policy
+        self._frames = frames
         self._members = 0                   # (a population does not survive a re-initialisation)
         self._learners = 0
         self.mlp_set_weights(policy)
@@ -640,12 +645,46 @@ class StepEngine:
         return st
 
     def mlp_set_norm(self, shift, scale):
-        """the policy's normalisation vectors [5K + 2] (every member's under per-member normalisers; running moments are left alone)"""
-        D = 5 * self.num_keywords + 2
+        """the policy's normalisation vectors [D] (every member's under per-member normalisers; running moments are left alone)"""
+        D = self.mlp_input_size()
         sh, sc = (np.ascontiguousarray(a, dtype=np.float32) for a in (shift, scale))
         if sh.shape != (D,) or sc.shape != (D,):
             raise ValueError(f"mlp_set_norm: shift and scale have {D} entries")
         check(self._lib.adc_engine_mlp_set_norm(self._h, sh.ctypes.data, sc.ctypes.data))
+
+    def mlp_frames(self):
+        """the frames of the policy's input row (MLPPolicy(frames=H); 1 without an observation history)"""
+        f = C.c_int32(0)
+        check(self._lib.adc_engine_mlp_frames(self._h, C.byref(f)))
+        return f.value
+
+    def mlp_input_size(self):
+        """D = frames * (5K + 2): the width of the network input, a record's obs row and the normalisation vectors"""
+        return int(getattr(self, "_frames", 1)) * (5 * self.num_keywords + 2)
+
+    def mlp_history_state(self):
+        """the observation history: dict(hist float32 [N, H, 5K+2] raw frames, last, from int32 [N]); None without one (frames = 1)"""
+        h = self.mlp_frames()
+        if h == 1:
+            return None
+        n, d0 = self.num_envs, 5 * self.num_keywords + 2
+        st = {"hist": np.zeros((n, h, d0), np.float32), "last": np.zeros(n, np.int32), "from": np.zeros(n, np.int32)}
+        check(self._lib.adc_engine_mlp_history_get(self._h, st["hist"].ctypes.data, st["last"].ctypes.data, st["from"].ctypes.data))
+        return st
+
+    def mlp_set_history_state(self, state):
+        """restore what mlp_history_state returned (None: nothing to restore); a resumed run continues bit for bit"""
+        h = self.mlp_frames()
+        if state is None:
+            if h != 1:
+                raise ValueError("mlp_set_history_state: the policy has an observation history and the state has none")
+            return
+        n, d0 = self.num_envs, 5 * self.num_keywords + 2
+        hist = np.ascontiguousarray(state["hist"], dtype=np.float32)
+        last, frm = (np.ascontiguousarray(state[k], dtype=np.int32) for k in ("last", "from"))
+        if h == 1 or hist.shape != (n, h, d0) or last.shape != (n,) or frm.shape != (n,):
+            raise ValueError(f"mlp_set_history_state: hist [N, {h}, 5K+2], last and from [N] of a policy with frames = {h}")
+        check(self._lib.adc_engine_mlp_history_set(self._h, hist.ctypes.data, last.ctypes.data, frm.ctypes.data))
 
     def mlp_agent_state(self):
         """(keys uint64 [N], ticks uint32 [N]) of the agents' own streams; every act moves a tick on by one"""
@@ -738,7 +777,9 @@ class StepEngine:
         cfg = self._mlp.config(self.num_keywords)
         if self._lib.adc_pg_param_count_host(C.byref(cfg), self.num_keywords, C.byref(q)) != _ffi.ADC_OK:
             raise ValueError("bad policy configuration")
-        return q.value
+        # (the host twin counts one frame's inputs: an observation history widens both first layers)
+        firsts = [net[0][0].shape[1] for net in (self._mlp.layers, self._mlp.value_layers) if net]
+        return q.value + (self.mlp_input_size() - (5 * self.num_keywords + 2)) * sum(firsts)
 
     ES_SHAPINGS = {"centered_rank": _ffi.ES_CENTERED_RANK, "raw": _ffi.ES_RAW}
     ES_OPTIMISERS = {"adam": _ffi.ES_ADAM, "sgd": _ffi.ES_SGD}
@@ -1079,7 +1120,7 @@ class StepEngine:
         check(self._off(prefix, "buffer_info")(self._h, C.byref(sz), C.byref(wr), C.byref(cap), *((C.byref(b),) if pop else ())))
         st = dict(size=sz.value, written=wr.value, capacity=cap.value, **(dict(batch_size=b.value) if pop else {}))
         if fetch and (member is not None or not pop):
-            n, D, A = sz.value, 5 * self.num_keywords + 2, self.num_keywords + 1
+            n, D, A = sz.value, self.mlp_input_size(), self.num_keywords + 1
             st.update(x=np.zeros((n, D), np.float32), a=np.zeros((n, A), np.float32), r=np.zeros(n, np.float32), done=np.zeros(n, np.uint8),
                       x2=np.zeros((n, D), np.float32))
             if n:
@@ -1089,12 +1130,12 @@ class StepEngine:
         return st
 
     def _off_buffer_load(self, prefix, member, buf, slot, written):
-        D, A = 5 * self.num_keywords + 2, self.num_keywords + 1
+        D, A = self.mlp_input_size(), self.num_keywords + 1
         x, a, r, x2 = (np.ascontiguousarray(buf[k], dtype=np.float32) for k in ("x", "a", "r", "x2"))
         done = np.ascontiguousarray(buf["done"], dtype=np.uint8)
         n = r.shape[0]
         if x.shape != (n, D) or x2.shape != (n, D) or a.shape != (n, A) or done.shape != (n,):
-            raise ValueError(f"{prefix}_buffer_load: x, x2 [n, 5K+2], a [n, K+1], r, done [n]")
+            raise ValueError(f"{prefix}_buffer_load: x, x2 [n, D], a [n, K+1], r, done [n]")
         if written is None:
             written = buf.get("written", slot + n)
         m = () if member is None else (int(member),)
@@ -1567,7 +1608,7 @@ class StepEngine:
     def obs_norm_state(self, member=0, state=None):
         """one normaliser's state (member 0: the shared one).  get (no state): dict of count, mean, M2 [D] float64, shift, scale
         [D] float32; set: such a dict - with the trainer's own state the run continues bit for bit"""
-        D = 5 * self.num_keywords + 2
+        D = self.mlp_input_size()
         if state is None:
             st = dict(mean=np.zeros(D, np.float64), M2=np.zeros(D, np.float64), shift=np.zeros(D, np.float32), scale=np.zeros(D, np.float32))
             n = C.c_int64(0)
@@ -1684,7 +1725,7 @@ class StepEngine:
 
     def _ring_norm_state(self, family, member, state):
         """the state of one normaliser of an off-policy family (td3 / sac): the two families share the entry points' signatures"""
-        D, info = 5 * self.num_keywords + 2, self._ring_norm_info(family)
+        D, info = self.mlp_input_size(), self._ring_norm_info(family)
         okeys = (("obs_mean", np.float64), ("obs_M2", np.float64), ("shift", np.float32), ("scale", np.float32))
         if state is None:
             st = {}
@@ -1879,14 +1920,14 @@ class StepEngine:
 
     def rollout_fetch(self, bootstrap=False):
         """the recorded days so far: dict of action [T, N, K+1], logp, value, reward [T, N] (float32), terminated, truncated
-        [T, N] (bool), obs [T, N, 5K+2] when recorded; bootstrap=True adds bootstrap_value [N]"""
+        [T, N] (bool), obs [T, N, D] when recorded; bootstrap=True adds bootstrap_value [N]"""
         t = C.c_int32(0)
         check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
         T, n, a = t.value, self.num_envs, self.num_keywords + 1
         st = dict(action=np.zeros((T, n, a), np.float32), logp=np.zeros((T, n), np.float32), value=np.zeros((T, n), np.float32),
                   reward=np.zeros((T, n), np.float32), terminated=np.zeros((T, n), np.uint8), truncated=np.zeros((T, n), np.uint8))
         if getattr(self, "_rollout_obs", False):
-            st["obs"] = np.zeros((T, n, 5 * self.num_keywords + 2), np.float32)
+            st["obs"] = np.zeros((T, n, self.mlp_input_size()), np.float32)
         check(self._lib.adc_engine_rollout_fetch(self._h, None, *(st[k].ctypes.data for k in (
             "action", "logp", "value", "reward", "terminated", "truncated")), st["obs"].ctypes.data if "obs" in st else None))
         st["terminated"], st["truncated"] = st["terminated"].astype(bool), st["truncated"].astype(bool)

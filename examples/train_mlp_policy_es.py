@@ -8,6 +8,7 @@ crosses the bus.  Every few generations the centre is evaluated deterministicall
 return and NCP are printed beside the zero-margin agent's.
 
 Usage: python examples/train_mlp_policy_es.py [--generations 100] [--members 512] [--num-envs 4096] [--num-keywords 100]
+                                              [--frames H]
 """
 import argparse
 import sys
@@ -40,6 +41,7 @@ def main():
     ap.add_argument("--members", type=int, default=512)
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--num-keywords", type=int, default=100)
+    ap.add_argument("--frames", type=int, default=1, metavar="H", help="the policy acts on the last H observations (1 to 8), gathered on the device")
     ap.add_argument("--days", type=int, default=60)
     ap.add_argument("--mean-volume", type=float, default=8.0)
     ap.add_argument("--sigma", type=float, default=0.02)
@@ -55,7 +57,7 @@ def main():
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(synthetic.implicit_keyword_planes(N, K, seed=1, mean_volume=args.mean_volume))
     eng.reset()
-    trainer = ESTrainer(eng, default_policy(K, days=days), args.members, sigma=args.sigma, lr=args.lr, seed=11)
+    trainer = ESTrainer(eng, default_policy(K, days=days, frames=args.frames), args.members, sigma=args.sigma, lr=args.lr, seed=11)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
     print(f"{0:>10} {'':>10} {ret:10.2f} {ncp:8.3f}")

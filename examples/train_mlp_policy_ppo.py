@@ -25,7 +25,10 @@ minibatch whose approx_kl exceeds 1.5 T.  --rllib turns on the reference's minib
 Usage: python examples/train_mlp_policy_ppo.py [--iterations 100] [--algo ppo|a2c] [--num-envs 4096] [--num-keywords 100]
                                                [--normalize-observations] [--normalize-rewards]
                                                [--kl-penalty COEF [--kl-target T]] [--vf-clip C] [--rllib]
-                                               [--minibatch-size S [--target-kl T]]
+                                               [--minibatch-size S [--target-kl T]] [--frames H] [--drift]
+
+--frames H (1 to 8): the policy acts on the last H observations, gathered on the device from a per-env history
+(MLPPolicy(frames=H); csrc/adc_mlp.h).
 """
 import argparse
 import sys
@@ -53,10 +56,13 @@ def with_value_network(policy, hidden, seed=1):
     return policy
 
 
+DRIFT = False          # --drift: the held-out sets drift as the training envs do
+
+
 def evaluate(name, policy, planes, days, budget):
     """(mean episode return, mean NCP) of an agent on the held-out keyword sets"""
     N, K = planes.shape[1:]
-    e = StepEngine(N, K, max_days=days, seed=70)
+    e = StepEngine(N, K, max_days=days, seed=70, drift_enabled=DRIFT)
     e.set_all_params(planes)
     e.reset()
     r = run_baseline_episode(e, name, steps=days, budget=budget, default_rpc=1.0, mlp=policy, deterministic=True, per_keyword_sums=False)
@@ -71,6 +77,8 @@ def main():
     ap.add_argument("--algo", choices=["ppo", "a2c"], default="ppo")
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--num-keywords", type=int, default=100)
+    ap.add_argument("--drift", action="store_true", help="non-stationary keywords: the engine's daily parameter drift, in training and on the held-out sets")
+    ap.add_argument("--frames", type=int, default=1, metavar="H", help="the policy acts on the last H observations (1 to 8), gathered on the device")
     ap.add_argument("--days", type=int, default=60)
     ap.add_argument("--mean-volume", type=float, default=8.0)
     ap.add_argument("--lr", type=float, default=None, help="default 1e-3 (--rllib: the preset's 1e-4)")
@@ -87,12 +95,14 @@ def main():
     ap.add_argument("--normalize-observations", action="store_true", help="a running observation filter on the device, from identity vectors")
     ap.add_argument("--normalize-rewards", action="store_true", help="divide the reward by the running std of the discounted return, on the device")
     args = ap.parse_args()
+    global DRIFT
+    DRIFT = args.drift
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
     zm = evaluate("zero_margin", None, held_out, days, budget)
     print(f"{'rllib_ppo' if args.rllib else args.algo}: {N} envs x {K} keywords, {days} days per iteration; held-out: {args.eval_envs} envs")
     print(f"{'iteration':>10} {'kl':>9} {'kl coef':>9} {'ev':>7} {'return':>10} {'NCP':>8}   zero-margin: return {zm[0]:.2f} NCP {zm[1]:.3f}")
-    eng = StepEngine(N, K, max_days=days, seed=7)
+    eng = StepEngine(N, K, max_days=days, seed=7, drift_enabled=args.drift)
     eng.set_all_params(synthetic.implicit_keyword_planes(N, K, seed=1, mean_volume=args.mean_volume))
     eng.reset()
     if args.target_kl is not None and args.minibatch_size is None and not args.rllib:
@@ -116,7 +126,7 @@ def main():
         config["target_kl"] = args.target_kl
     if args.queued_update:
         config["queued_update"] = True
-    policy = with_value_network(default_policy(K, days=days), (32, 32))
+    policy = with_value_network(default_policy(K, days=days, frames=args.frames), (32, 32))
     if args.normalize_observations:
         policy.shift, policy.scale = np.zeros_like(policy.shift), np.ones_like(policy.scale)
     trainer = pg_trainer.PGTrainer(eng, policy, days, normalize_observations=args.normalize_observations,

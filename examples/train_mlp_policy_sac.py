@@ -14,7 +14,7 @@ the held-out envs and its standard error.
 The defaults are the preset's (baselines/sac_trainer.sac: RLlib's SAC defaults).  Whether they learn at a given shape is for a
 run to show; profiles/pr_sac_trainer.txt says what has been run.
 
-Usage: python examples/train_mlp_policy_sac.py [--iterations 100] [--num-envs 1024] [--num-keywords 100]
+Usage: python examples/train_mlp_policy_sac.py [--iterations 100] [--num-envs 1024] [--num-keywords 100] [--frames H]
 """
 import argparse
 import sys
@@ -30,13 +30,13 @@ from adcraft_amd.closed_loop import run_baseline_episode  # noqa: E402
 from adcraft_amd.engine import StepEngine  # noqa: E402
 
 
-def two_headed_policy(K, days, bid_lo, bid_hi, start_bid=0.5, hidden=(32, 32), seed=0, log_std_clamp=(-5.0, 1.0)):
+def two_headed_policy(K, days, bid_lo, bid_hi, start_bid=0.5, hidden=(32, 32), seed=0, log_std_clamp=(-5.0, 1.0), frames=1):
     """means and log-stds from one network on the normalised observation: small last-layer weights and mean biases at
     atanh of start_bid's place in [bid_lo, bid_hi], so that the first bids sit about start_bid (examples/evaluate_mlp_policy.py's
     50 cents) with a standard deviation of exp(-1) before the squash"""
     from adcraft_amd.baselines.es_trainer import default_policy
-    base = default_policy(K, days=days)
-    rng, A, layers, n_in = np.random.default_rng(seed), K + 1, [], 5 * K + 2
+    base = default_policy(K, days=days, frames=frames)
+    rng, A, layers, n_in = np.random.default_rng(seed), K + 1, [], frames * (5 * K + 2)
     for n_out in hidden:
         bound = 1.0 / np.sqrt(n_in)
         layers.append((rng.uniform(-bound, bound, (n_in, n_out)).astype(np.float32), np.zeros(n_out, np.float32)))
@@ -44,7 +44,7 @@ def two_headed_policy(K, days, bid_lo, bid_hi, start_bid=0.5, hidden=(32, 32), s
     u0 = np.arctanh(2.0 * (start_bid - bid_lo) / (bid_hi - bid_lo) - 1.0)
     bias = np.concatenate([np.full(A, u0, np.float32), np.full(A, -1.0, np.float32)])
     layers.append(((rng.standard_normal((n_in, 2 * A)) * 0.01).astype(np.float32), bias))
-    return MLPPolicy(layers, activation="tanh", shift=base.shift, scale=base.scale, log_std_clamp=log_std_clamp)
+    return MLPPolicy(layers, activation="tanh", shift=base.shift, scale=base.scale, log_std_clamp=log_std_clamp, frames=frames)
 
 
 def evaluate(name, squashed, planes, days, budget):
@@ -72,6 +72,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--num-keywords", type=int, default=100)
+    ap.add_argument("--frames", type=int, default=1, metavar="H", help="the policy acts on the last H observations (1 to 8), gathered on the device")
     ap.add_argument("--days", type=int, default=60)
     ap.add_argument("--mean-volume", type=float, default=8.0)
     ap.add_argument("--critic-hidden", default="256,256")
@@ -104,7 +105,7 @@ def main():
     config.update({k: float(v) for k, v in (kv.split("=", 1) for kv in args.set)})
     lo = np.concatenate([[1.0], np.full(K, args.bid_lo)]).astype(np.float32)          # (the budget is overridden during training and evaluation)
     hi = np.concatenate([[budget], np.full(K, args.bid_hi)]).astype(np.float32)
-    trainer = sac_trainer.SACTrainer(eng, two_headed_policy(K, days, args.bid_lo, args.bid_hi), lo, hi, horizon=days,
+    trainer = sac_trainer.SACTrainer(eng, two_headed_policy(K, days, args.bid_lo, args.bid_hi, frames=args.frames), lo, hi, horizon=days,
                                      normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
                                      prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None, **config)
     rng = np.random.default_rng(5)

@@ -13,6 +13,7 @@ TD3's usual 1e-3 the actor outruns the critics there and the return falls.  This
 measured; lower --actor-lr further if the return falls.
 
 Usage: python examples/train_mlp_policy_td3.py [--iterations 100] [--num-envs 1024] [--num-keywords 100] [--warmup-iterations 2]
+                                               [--frames H]
 """
 import argparse
 import sys
@@ -45,6 +46,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--num-keywords", type=int, default=100)
+    ap.add_argument("--frames", type=int, default=1, metavar="H", help="the policy acts on the last H observations (1 to 8), gathered on the device")
     ap.add_argument("--days", type=int, default=60)
     ap.add_argument("--mean-volume", type=float, default=8.0)
     ap.add_argument("--critic-hidden", default="256,256")
@@ -75,7 +77,7 @@ def main():
                              learning_starts=args.warmup_iterations * days * N, updates_per_iteration=args.updates, batch_size=args.batch_size,
                              reward_scale=args.reward_scale, gamma=args.gamma, actor_lr=args.actor_lr, action_lo=0.01, action_hi=3.0,
                              action_norm=(np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32)))
-    trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days), horizon=days, normalize_observations=args.normalize_observations,
+    trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days, frames=args.frames), horizon=days, normalize_observations=args.normalize_observations,
                                      normalize_rewards=args.normalize_rewards,
                                      prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None, **config)
     rng = np.random.default_rng(5)

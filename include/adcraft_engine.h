@@ -501,6 +501,23 @@ typedef struct adc_mlp_config {
 /* shapes and options; every weight, bias and vector starts at zero and must be uploaded before the first act.  seeds_n (may be
  * NULL: keyed by the engine seed and the global env id) seeds the agents' streams, tick 0.  A second call re-initialises. */
 int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n);
+/* Observation history: adc_engine_mlp_init with a frame count `frames` = H in 1..8 (1: adc_engine_mlp_init itself, the same
+ * kernels and bits).  With H > 1 the network input of an env is the concatenation of its last H flat observations,
+ * D = H (5K + 2): x[f D0 + j], frame 0 today's row, frame f >= 1 the raw row that the act on episode day d - f read, or zeros
+ * where the env has no such act in this episode (csrc/adc_mlp.h states the law: the per-env history hist[N][H][5K+2] of raw
+ * frames, slot = episode day mod H, and the two validity words last / from).  The frames are gathered on the device.  Every
+ * first layer has n_in = D; adc_engine_mlp_set_norm takes vectors of length D (normalisation is per position, zero frames
+ * included); the rollout record's obs rows, the replay ring's rows, the running observation normalisers' vectors and the
+ * trainers' shapes are D wide.  An auto-reset clears an env's history through its day 0; days stepped without the agent
+ * restart it; adc_engine_reset forgets it for the envs it resets.  Not detected: an auto-reset followed by exactly last + 1
+ * days without an act.  adc_engine_mlp_bootstrap_value and the trainers' stores read the row an act would read now and write
+ * nothing.  Refused (ADC_EINVAL, the engine stays usable): frames outside 1..8; a stacked row that does not fit the act's LDS. */
+int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t frames);
+int adc_engine_mlp_frames(adc_engine *e, int32_t *frames);
+/* the history to the host and back: hist_nhd [N][H][5K+2] raw frames, last_n / from_n [N] (any may be NULL); a run resumed from
+ * them continues bit for bit.  ADC_ESTATE without a history (frames = 1). */
+int adc_engine_mlp_history_get(adc_engine *e, float *hist_nhd, int32_t *last_n, int32_t *from_n);
+int adc_engine_mlp_history_set(adc_engine *e, const float *hist_nhd, const int32_t *last_n, const int32_t *from_n);
 /* one Linear layer: network 0 = policy, 1 = value; weights_in_out is [n_in][n_out] row-major (input-major: torch's
  * weight.T), bias [n_out].  May be called again at any time between days (a trainer's update); nothing else changes. */
 int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out);
@@ -1515,6 +1532,12 @@ int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords, const floa
                      const float *scale_d, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,
                      float budget_override, float *mean_a, float *log_std_out_a, float *action_a, float *logp, float *value,
                      float *bids_k, float *budget);
+/* the observation history's row law for one env on the host: the same code as the device's (adc_mlp.h).  frame0_d0 [5K+2]: the
+ * raw flat observation an act on episode day `day` reads (NULL, or day 0: zeros); hist_hd0 [frames][5K+2], *last, *from: the env's history.
+ * row_d [frames (5K+2)] receives the raw stacked row.  commit nonzero: an act (frame 0 is written to its slot, *last and *from
+ * move); zero: a peek (nothing is written).  ADC_EINVAL: frames outside 1..8, day < 0, a NULL history or row. */
+int adc_mlp_stack_row_host(int32_t num_keywords, int32_t frames, const float *frame0_d0, float *hist_hd0, int32_t *last, int32_t *from,
+                           int32_t day, int32_t commit, float *row_d);
 /* the evolution strategy on the host: the same code as the device's (adc_es.h).  `seed` is the effective seed (the
  * configuration's, or the engine's when that is 0).  noise: eps(pair, generation)[p0 .. p0 + n).  update: one generation's
  * shaping, gradient estimate and step on theta / m / v [n_params] in place from fitness_m[members]; `generation` is the one

@@ -71,9 +71,13 @@
 //        the learner's discount, their moments, the merge, the multiplier, the GAE kernels under a multiplier and a clip (adc_rew_norm.h);
 //        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop and of kernel_sac / kernel_sac_pop (adc_sac_norm.h) normalise as they gather.
 //   parts/host_api.inc            the engine object and the extern "C" entry points.
-//   parts/pg_kl_api.inc           the entry points of the KL penalty / value-clip add-on and what pg_api.inc calls of it.
-//   parts/pg_shuffle_api.inc      the entry points of the shuffled minibatches / target-KL stop add-on, the updates under it.
-//   parts/pg_api.inc              the entry points of policy-gradient training, of one learner and of a learner population.
+//   parts/pg_core.inc             what the three policy-gradient host files share: the members (a single learner is one member), the
+//                                 entry checks, the sample pass's view, the walk over the gradient's terms, the statistics' sums and
+//                                 means, the LDS refusal, the trainer's allocation, a member's state by its flat offset.
+//   parts/pg_kl_api.inc           the entry points of the KL penalty / value-clip add-on and what pg_api.inc calls of it, over pg_core.inc.
+//   parts/pg_shuffle_api.inc      the entry points of the shuffled minibatches / target-KL stop add-on, the update under it, over pg_core.inc.
+//   parts/pg_api.inc              the entry points of policy-gradient training, one function under the learner and the learner population:
+//                                 the advantages, a minibatch, the host-driven and the queued update, over pg_core.inc.
 //   parts/offpolicy_core.inc      what the four off-policy front ends share on the host: the ring, the critic upload, the state
 //                                 vectors, the allocation, an update's launch helpers, the populations' update driver.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training, over offpolicy_core.inc.
@@ -147,6 +151,7 @@ namespace adck {
 using namespace adck;
 
 #include "parts/host_api.inc"
+#include "parts/pg_core.inc"
 #include "parts/pg_kl_api.inc"
 #include "parts/pg_shuffle_api.inc"
 #include "parts/pg_api.inc"

@@ -126,10 +126,8 @@ struct adc_engine {
     uint8_t *ro_term = nullptr, *ro_trunc = nullptr;
     std::vector<void *> ro_allocs;
     bool ro_deterministic = false;      // a recorded day was collected with the deterministic policy: its log-probabilities mean nothing
-    // policy-gradient training over the record (adc_engine_pg_init; parts/kernel_pg.inc, parts/pg_api.inc)
+    // policy-gradient training over the record (adc_engine_pg_init; parts/kernel_pg.inc, parts/pg_core.inc, parts/pg_api.inc)
     bool have_pg = false, pg_adv_ready = false;
-    adc_pg_config pg_cfg{};
-    int64_t pg_steps = 0;               // optimiser steps taken
     int pg_mb = 0;                      // envs of a minibatch (the scratch's capacity)
     size_t pg_slots = 0;                // samples of a minibatch the scratch holds per member: T * pg_mb, more under shuffled minibatches
     adc::PgShape pg_shape{};
@@ -141,11 +139,12 @@ struct adc_engine {
     double *pg_part = nullptr, *pg_sums = nullptr;                                       // chunk partials; the law's ten sums
     double *pg_gpart = nullptr;                                                          // [chunks][Q] the weight gradient's partials
     std::vector<void *> pg_allocs;
+    // the members' configurations and optimiser steps taken (a single learner is member 0: parts/pg_core.inc)
+    std::vector<adc_pg_config> pgp_cfg;         // [M]
+    std::vector<int64_t> pgp_steps;             // [M]
     // ... and of a learner population (adc_engine_pg_pop_init; it shares the scratch fields above, sized for all members at once:
     // pg_theta / pg_m / pg_v / pg_grad are [M][Q], pg_acts / pg_deltas / pg_pieces [M][T * minibatch envs][...], pg_sums [M][16])
     bool have_pg_pop = false;
-    std::vector<adc_pg_config> pgp_cfg;         // [M]
-    std::vector<int64_t> pgp_steps;             // [M]
     std::vector<PgMember> pgp_mem;              // [M] the host's copy of pgp_dmem
     std::vector<double> pgp_host_sums;          // [M][16]
     PgMember *pgp_dmem = nullptr;
@@ -2973,7 +2972,6 @@ void pg_drop(adc_engine *e)
     if (e->pq_host) (void)hipHostFree(e->pq_host);      // (the queued update's pinned twin; its device block was among pg_allocs)
     e->pq_dev = e->pq_host = nullptr; e->pq_bytes = 0;
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
-    e->pg_steps = 0;
     e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();
     e->pgp_dmem = nullptr;
 }

@@ -351,7 +351,7 @@ ADC_EXPORT int adc_engine_rew_norm_update(adc_engine *e)
     const NormBatch b = norm_batch(e, s);
     ENGINE_GUARD(e);
     const bool pop = e->have_pg_pop;
-    if (int rc = norm_update_rew(e, s, b, adc::NormConfig{e->rn_cfg.min_std, e->rn_cfg.count_cap}, pop ? 0.0f : e->pg_cfg.gamma,
+    if (int rc = norm_update_rew(e, s, b, adc::NormConfig{e->rn_cfg.min_std, e->rn_cfg.count_cap}, pop ? 0.0f : e->pgp_cfg[0].gamma,
                                  pop ? e->pgp_dmem : (const PgMember *)nullptr))
         return rc;
     s.t0 = b.T;

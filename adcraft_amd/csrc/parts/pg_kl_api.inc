@@ -7,7 +7,6 @@
 namespace {
 constexpr const char *kKlNotReady =
     "adc_engine_pg_kl_init has not been called (or the trainer, the policy, the learners or the record were re-initialised since)";
-int kl_members(const adc_engine *e) { return e->have_pg_pop ? e->lrn_M : 1; }
 
 // the members' table from the host's coefficients and configurations, up in one copy (a population's; a single learner has none)
 // (idle: the caller has waited for the stream since the last upload - the queued update's one wait)
@@ -100,7 +99,7 @@ ADC_EXPORT int adc_engine_pg_kl_init(adc_engine *e, const adc_pg_kl_config *cfgs
     if (e->have_td3 || e->have_td3_pop) return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: the KL penalty belongs to the PPO / A2C loss");
     if (!e->have_pg && !e->have_pg_pop)
         return fail(ADC_ESTATE, "the KL penalty is an add-on to a PPO / A2C trainer: adc_engine_pg_init or adc_engine_pg_pop_init first");
-    const int M = kl_members(e);
+    const int M = pg_members(e);
     if (!cfgs) return fail(ADC_EINVAL, "adc_pg_kl_config array is NULL");
     if (count != 1 && count != M) return fail(ADC_EINVAL, "count: 1 (one configuration shared by all members) or the number of members");
     for (int i = 0; i < count; ++i) {
@@ -108,10 +107,7 @@ ADC_EXPORT int adc_engine_pg_kl_init(adc_engine *e, const adc_pg_kl_config *cfgs
         if (adc_pg_kl_config_check(cfgs + i, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     }
     const adc::PgShape &sh = e->pg_shape;
-    if (pg_lds_floats(sh, e->pg_maxw, true) * sizeof(float) > 64u * 1024u)
-        return fail(ADC_EINVAL, pg_lds_floats(adc::pg_shape_of(e->mlp_cfg, e->v.K), e->pg_maxw, true) * sizeof(float) > 64u * 1024u
-                                    ? "num_keywords too large for the KL penalty (LDS)"
-                                    : "frames: the stacked input row is too large for the KL penalty (LDS); fewer frames fit");
+    if (int rc = pg_lds_refuse(e, sh, e->pg_maxw, true)) return rc;
     const size_t tna = (size_t)e->ro_T * (size_t)e->v.N * (size_t)sh.A;
     if ((size_t)e->ro_T * (size_t)e->v.N > 0x7FFFFFFFull) return fail(ADC_EINVAL, "horizon x num_envs: at most 2^31 - 1 recorded rows under the KL penalty");
     ENGINE_GUARD(e);
@@ -153,7 +149,7 @@ ADC_EXPORT int adc_engine_pg_kl_coef_get(adc_engine *e, int32_t member, float *c
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (!e->kl_live) return fail(ADC_ESTATE, kKlNotReady);
-    if (member < 0 || member >= kl_members(e)) return fail(ADC_EINVAL, "no such member");
+    if (member < 0 || member >= pg_members(e)) return fail(ADC_EINVAL, "no such member");
     if (!coef) return fail(ADC_EINVAL, "coef is NULL");
     *coef = e->kl_coef[(size_t)member];
     return ADC_OK;
@@ -163,7 +159,7 @@ ADC_EXPORT int adc_engine_pg_kl_coef_set(adc_engine *e, int32_t member, float co
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (!e->kl_live) return fail(ADC_ESTATE, kKlNotReady);
-    if (member < 0 || member >= kl_members(e)) return fail(ADC_EINVAL, "no such member");
+    if (member < 0 || member >= pg_members(e)) return fail(ADC_EINVAL, "no such member");
     if (!(coef >= 0.0f && coef < __builtin_inff())) return fail(ADC_EINVAL, "coef >= 0 and finite");
     ENGINE_GUARD(e);
     e->kl_coef[(size_t)member] = coef;
@@ -181,7 +177,7 @@ ADC_EXPORT int adc_engine_pg_kl_old_dist_fetch(adc_engine *e, float *mean_old_tn
     ENGINE_GUARD(e);
     const size_t A = (size_t)e->pg_shape.A, tna = (size_t)e->ro_t * (size_t)e->v.N * A;
     if (mean_old_tna) HIP_TRY(hipMemcpyAsync(mean_old_tna, e->kl_mean_old, tna * 4, hipMemcpyDeviceToHost, e->stream));
-    if (ls_old) HIP_TRY(hipMemcpyAsync(ls_old, e->kl_ls_old, (e->pg_shape.two_heads ? tna : (size_t)kl_members(e) * A) * 4, hipMemcpyDeviceToHost, e->stream));
+    if (ls_old) HIP_TRY(hipMemcpyAsync(ls_old, e->kl_ls_old, (e->pg_shape.two_heads ? tna : (size_t)pg_members(e) * A) * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ADC_OK;
 }

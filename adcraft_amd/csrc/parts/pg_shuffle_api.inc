@@ -9,24 +9,6 @@ namespace {
 constexpr const char *kShNotReady =
     "adc_engine_pg_shuffle_init has not been called (or the trainer, the policy, the learners or the record were re-initialised since)";
 
-// a gathered minibatch: S samples per member, member m's record rows at rows + m * stride
-struct PgGather {
-    const uint32_t *rows;
-    size_t stride;
-    long long S;
-};
-// (parts/pg_api.inc)
-int pg_minibatch_run(adc_engine *e, int n0, int B, adc::PgStatsOut *out, const PgGather *g);
-int pgp_minibatch_run(adc_engine *e, int index, adc::PgStatsOut *out_m, const PgGather *g);
-void pg_stats_fill(adc_pg_stats *stats, const adc::PgStatsOut &o, int64_t steps, int64_t samples);
-int pg_state_check(const adc_engine *e);
-int pgp_state_check(const adc_engine *e);
-int pg_record_check(const adc_engine *e);
-inline long long pg_chunks(long long n);
-
-int sh_members(const adc_engine *e) { return e->have_pg_pop ? e->lrn_M : 1; }
-int sh_member_envs(const adc_engine *e) { return e->have_pg_pop ? e->lrn_n : e->v.N; }
-int64_t sh_steps(const adc_engine *e, int m) { return e->have_pg_pop ? e->pgp_steps[(size_t)m] : e->pg_steps; }
 int sh_minibatches(const adc_engine *e) { return (int)(((long long)e->sh_ns + e->sh_mb - 1) / e->sh_mb); }
 
 // the advantages have been computed: a new update begins, no member has stopped, an order has yet to be drawn
@@ -61,11 +43,11 @@ bool sh_all_stopped(const adc_engine *e)
 // the order of a new epoch for every member: its tick is the member's step count now
 int sh_epoch_run(adc_engine *e)
 {
-    const int M = sh_members(e), n = sh_member_envs(e);
+    const int M = pg_members(e), n = pg_member_envs(e);
     const uint32_t n_s = (uint32_t)e->ro_t * (uint32_t)n;
     HIP_TRY(hipStreamSynchronize(e->stream));       // (the last epoch's upload of the host's table may still be in flight)
     for (int m = 0; m < M; ++m) {
-        e->sh_mem[(size_t)m].tick = (uint32_t)((uint64_t)sh_steps(e, m) & 0xFFFFFFFFull);
+        e->sh_mem[(size_t)m].tick = (uint32_t)((uint64_t)e->pgp_steps[(size_t)m] & 0xFFFFFFFFull);
         if (!e->sh_stats[(size_t)m].stopped) e->sh_stats[(size_t)m].epochs_begun += 1;
     }
     HIP_TRY(hipMemcpyAsync(e->sh_dmem, e->sh_mem.data(), e->sh_mem.size() * sizeof(PgShuffleMember), hipMemcpyHostToDevice, e->stream));
@@ -83,25 +65,11 @@ PgGather sh_gather(const adc_engine *e, int j)
     return PgGather{e->sh_rows + at, (size_t)e->sh_ns, left < e->sh_mb ? left : (long long)e->sh_mb};
 }
 
-void sh_stats_add(adc::PgStatsOut &a, const adc::PgStatsOut &o)
-{
-    a.policy_loss = a.policy_loss + o.policy_loss; a.value_loss = a.value_loss + o.value_loss; a.entropy = a.entropy + o.entropy;
-    a.approx_kl = a.approx_kl + o.approx_kl; a.clip_fraction = a.clip_fraction + o.clip_fraction;
-    a.grad_norm = a.grad_norm + o.grad_norm; a.explained_variance = a.explained_variance + o.explained_variance;
-}
-adc::PgStatsOut sh_stats_mean(const adc::PgStatsOut &a, int count)
-{
-    const double c = (double)count;
-    return adc::PgStatsOut{a.policy_loss / c, a.value_loss / c, a.entropy / c, a.approx_kl / c, a.clip_fraction / c, a.grad_norm / c,
-                           a.explained_variance / c};
-}
-
 // adc_engine_pg_update / _pg_pop_update under the add-on, after the advantages: per epoch a new order and its ceil(n_s / mb)
 // minibatches, every member until it stops; the statistics of the last epoch a member began
 int sh_update_run(adc_engine *e, int epochs, adc_pg_stats *stats_m)
 {
-    const int M = sh_members(e);
-    const bool pop = e->have_pg_pop;
+    const int M = pg_members(e);
     std::vector<adc::PgStatsOut> o((size_t)M), acc((size_t)M), mean((size_t)M);
     std::vector<int> cnt((size_t)M, 0);
     std::vector<uint8_t> live((size_t)M, 1);
@@ -117,17 +85,17 @@ int sh_update_run(adc_engine *e, int epochs, adc_pg_stats *stats_m)
         const int count = sh_minibatches(e);
         for (int j = 0; j < count && !sh_all_stopped(e); ++j) {
             const PgGather g = sh_gather(e, j);
-            if ((rc = pop ? pgp_minibatch_run(e, 0, o.data(), &g) : pg_minibatch_run(e, 0, 1, o.data(), &g))) return rc;
+            if ((rc = pg_gathered_run(e, o.data(), &g))) return rc;
             kl.add(e, e->sh_evaluated.data());
             for (int m = 0; m < M; ++m)
-                if (e->sh_evaluated[(size_t)m]) { sh_stats_add(acc[(size_t)m], o[(size_t)m]); cnt[(size_t)m] += 1; }
+                if (e->sh_evaluated[(size_t)m]) { pg_stats_add(acc[(size_t)m], o[(size_t)m]); cnt[(size_t)m] += 1; }
         }
         for (int m = 0; m < M; ++m)
-            if (live[(size_t)m]) mean[(size_t)m] = sh_stats_mean(acc[(size_t)m], cnt[(size_t)m]);
+            if (live[(size_t)m]) mean[(size_t)m] = pg_stats_mean(acc[(size_t)m], cnt[(size_t)m]);
     }
     if (e->kl_live && (rc = kl_update_end(e, kl))) return rc;
     if (stats_m)
-        for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, mean[(size_t)m], sh_steps(e, m), e->sh_last_count[(size_t)m]);
+        for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, mean[(size_t)m], e->pgp_steps[(size_t)m], e->sh_last_count[(size_t)m]);
     return ADC_OK;
 }
 
@@ -149,7 +117,7 @@ ADC_EXPORT int adc_engine_pg_shuffle_init(adc_engine *e, const adc_pg_shuffle_co
         return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: its batches are drawn per update already (shuffled minibatches belong to PPO / A2C)");
     if (!e->have_pg && !e->have_pg_pop)
         return fail(ADC_ESTATE, "shuffled minibatches are an add-on to a PPO / A2C trainer: adc_engine_pg_init or adc_engine_pg_pop_init first");
-    const int M = sh_members(e), n = sh_member_envs(e);
+    const int M = pg_members(e), n = pg_member_envs(e);
     if (!cfgs) return fail(ADC_EINVAL, "adc_pg_shuffle_config array is NULL");
     if (count != 1 && count != M) return fail(ADC_EINVAL, "count: 1 (one configuration shared by all members) or the number of members");
     for (int i = 0; i < count; ++i) {
@@ -165,7 +133,7 @@ ADC_EXPORT int adc_engine_pg_shuffle_init(adc_engine *e, const adc_pg_shuffle_co
     if (pg_chunks((long long)slots) > 65535) return fail(ADC_EINVAL, "minibatch_samples: at most 65535 x 1024 samples in a minibatch");
     ENGINE_GUARD(e);
     const adc::PgShape &sh = e->pg_shape;
-    const size_t Ms = (size_t)M, Q = (size_t)(e->have_pg_pop ? e->lrn_lay.Q : e->pg_lay.Q);
+    const size_t Ms = (size_t)M, Q = (size_t)pg_Q(e);
     // (everything new is allocated before anything old goes: a refused allocation leaves the engine as it was)
     std::vector<void *> fresh;
     float *acts = nullptr, *deltas = nullptr, *pieces = nullptr, *klp = nullptr;
@@ -213,7 +181,7 @@ ADC_EXPORT int adc_engine_pg_shuffle_epoch(adc_engine *e)
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (!e->sh_live) return fail(ADC_ESTATE, kShNotReady);
     int rc;
-    if ((rc = e->have_pg_pop ? pgp_state_check(e) : pg_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if ((rc = pg_state_check(e, e->have_pg_pop)) || (rc = pg_record_check(e))) return rc;
     if (!e->pg_adv_ready)
         return fail(ADC_ESTATE, "adc_engine_pg_advantages / _pg_pop_advantages has not been called since the last recorded day (an update begins with it)");
     ENGINE_GUARD(e);
@@ -225,18 +193,18 @@ ADC_EXPORT int adc_engine_pg_shuffle_minibatch(adc_engine *e, int32_t index, adc
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (!e->sh_live) return fail(ADC_ESTATE, kShNotReady);
     int rc;
-    if ((rc = e->have_pg_pop ? pgp_state_check(e) : pg_state_check(e)) || (rc = pg_record_check(e))) return rc;
+    if ((rc = pg_state_check(e, e->have_pg_pop)) || (rc = pg_record_check(e))) return rc;
     if (!e->pg_adv_ready)
         return fail(ADC_ESTATE, "adc_engine_pg_advantages / _pg_pop_advantages has not been called since the last recorded day");
     if (!e->sh_epoch_ready) return fail(ADC_ESTATE, "adc_engine_pg_shuffle_epoch has not been called since the advantages: no order has been drawn");
     if (index < 0 || index >= sh_minibatches(e)) return fail(ADC_EINVAL, "no such minibatch: 0 to ceil(samples of a member / minibatch_samples) - 1");
     ENGINE_GUARD(e);
-    const int M = sh_members(e);
+    const int M = pg_members(e);
     std::vector<adc::PgStatsOut> o((size_t)M);
     const PgGather g = sh_gather(e, index);
-    if ((rc = e->have_pg_pop ? pgp_minibatch_run(e, 0, o.data(), &g) : pg_minibatch_run(e, 0, 1, o.data(), &g))) return rc;
+    if ((rc = pg_gathered_run(e, o.data(), &g))) return rc;
     if (stats_m)
-        for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, o[(size_t)m], sh_steps(e, m), g.S);
+        for (int m = 0; m < M; ++m) pg_stats_fill(stats_m + m, o[(size_t)m], e->pgp_steps[(size_t)m], g.S);
     return ADC_OK;
 }
 
@@ -249,7 +217,7 @@ ADC_EXPORT int adc_engine_pg_shuffle_order_fetch(adc_engine *e, uint32_t *order,
         return fail(ADC_ESTATE, "the record or the trainer's configuration has changed since the advantages: the order drawn under them is gone");
     if (!e->sh_epoch_ready) return fail(ADC_ESTATE, "adc_engine_pg_shuffle_epoch has not been called since the advantages: no order has been drawn");
     ENGINE_GUARD(e);
-    const size_t bytes = (size_t)sh_members(e) * (size_t)e->sh_ns * 4;
+    const size_t bytes = (size_t)pg_members(e) * (size_t)e->sh_ns * 4;
     if (order) HIP_TRY(hipMemcpyAsync(order, e->sh_order, bytes, hipMemcpyDeviceToHost, e->stream));
     if (rows) HIP_TRY(hipMemcpyAsync(rows, e->sh_rows, bytes, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));

@@ -866,20 +866,48 @@ class StepEngine:
         check(self._lib.adc_engine_pg_param_count(self._h, C.byref(n)))
         return n.value
 
-    def pg_advantages(self, fetch=False):
-        """GAE over the recorded days; fetch=True returns (adv, ret) [T, N] float32"""
-        check(self._lib.adc_engine_pg_advantages(self._h))
+    # (`prefix`: pg or pg_pop - the family of the entry points and the public method's name in a message; `member`: a
+    #  population's member, None for the single learner.  The host side is shared in the same way: parts/pg_core.inc)
+    def _pg(self, prefix, name):
+        return getattr(self._lib, f"adc_engine_{prefix}_{name}")
+
+    def _learner_count(self):
+        return max(getattr(self, "_learners", 0), 1)
+
+    @staticmethod
+    def _pg_stats(st):
+        return {k: getattr(st, k) for k, _ in _ffi.PGStats._fields_}
+
+    def _pg_advantages(self, prefix, fetch):
+        check(self._pg(prefix, "advantages")(self._h))
         if not fetch:
             return None
         t = C.c_int32(0)
         check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
         adv, ret = np.zeros((t.value, self.num_envs), np.float32), np.zeros((t.value, self.num_envs), np.float32)
-        check(self._lib.adc_engine_pg_advantages_fetch(self._h, adv.ctypes.data, ret.ctypes.data))
+        check(self._pg(prefix, "advantages_fetch")(self._h, adv.ctypes.data, ret.ctypes.data))
         return adv, ret
 
-    @staticmethod
-    def _pg_stats(st):
-        return {k: getattr(st, k) for k, _ in _ffi.PGStats._fields_}
+    def _pg_update(self, prefix, st, epochs, queued):
+        check(self._pg(prefix, "update_queued" if queued else "update")(self._h, int(epochs), st))
+
+    def _pg_state(self, prefix, member, state):
+        who = () if member is None else (int(member),)
+        Q = self.pg_param_count() if member is None else self.mlp_learner_param_count()
+        if state is None:
+            st = dict(theta=np.zeros(Q, np.float32), m=np.zeros(Q, np.float32), v=np.zeros(Q, np.float32))
+            n = C.c_int64(0)
+            check(self._pg(prefix, "state_get")(self._h, *who, st["theta"].ctypes.data, st["m"].ctypes.data, st["v"].ctypes.data, C.byref(n)))
+            st["steps"] = n.value
+            return st
+        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in ("theta", "m", "v")]
+        if any(a.shape != (Q,) for a in arr):
+            raise ValueError(f"{prefix}_state: theta, m and v have {Q} entries")
+        check(self._pg(prefix, "state_set")(self._h, *who, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
+
+    def pg_advantages(self, fetch=False):
+        """GAE over the recorded days; fetch=True returns (adv, ret) [T, N] float32"""
+        return self._pg_advantages("pg", fetch)
 
     def pg_minibatch(self, env_begin, env_count):
         """one gradient and one optimiser step over every recorded day of the envs [env_begin, env_begin + env_count)"""
@@ -891,23 +919,12 @@ class StepEngine:
         """advantages, then `epochs` x the minibatches in ascending env order; the last epoch's statistics.  queued=True: the
         whole update enqueued as one chain with one host wait (adc_engine_pg_update_queued) - the same bits"""
         st = _ffi.PGStats()
-        update = self._lib.adc_engine_pg_update_queued if queued else self._lib.adc_engine_pg_update
-        check(update(self._h, int(epochs), C.byref(st)))
+        self._pg_update("pg", C.byref(st), epochs, queued)
         return self._pg_stats(st)
 
     def pg_state(self, state=None):
         """get (no argument): dict of theta, m, v [Q] float32 and steps; set: such a dict - the run continues bit for bit"""
-        Q = self.pg_param_count()
-        if state is None:
-            st = dict(theta=np.zeros(Q, np.float32), m=np.zeros(Q, np.float32), v=np.zeros(Q, np.float32))
-            n = C.c_int64(0)
-            check(self._lib.adc_engine_pg_state_get(self._h, st["theta"].ctypes.data, st["m"].ctypes.data, st["v"].ctypes.data, C.byref(n)))
-            st["steps"] = n.value
-            return st
-        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in ("theta", "m", "v")]
-        if any(a.shape != (Q,) for a in arr):
-            raise ValueError(f"pg_state: theta, m and v have {Q} entries")
-        check(self._lib.adc_engine_pg_state_set(self._h, arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
+        return self._pg_state("pg", None, state)
 
     # ---- learner populations: M PPO / A2C learners in lock-step (parts/pg_api.inc; baselines/pg_trainer.py PGPopulationTrainer) ----
     @classmethod
@@ -925,47 +942,29 @@ class StepEngine:
     def pg_pop_init(self, configs):
         """population training of the learners (mlp_learners, rollout_enable(T, obs=True) first); configs: one dict of
         pg_config's options shared by all members, or one per member.  Every member's theta starts as its device weights."""
-        arr, count = self.pg_pop_configs(configs, self.num_envs, max(getattr(self, "_learners", 0), 1))
+        arr, count = self.pg_pop_configs(configs, self.num_envs, self._learner_count())
         check(self._lib.adc_engine_pg_pop_init(self._h, arr, count))
 
     def pg_pop_advantages(self, fetch=False):
         """GAE per env under its member's configuration; fetch=True returns (adv, ret) [T, N] float32"""
-        check(self._lib.adc_engine_pg_pop_advantages(self._h))
-        if not fetch:
-            return None
-        t = C.c_int32(0)
-        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
-        adv, ret = np.zeros((t.value, self.num_envs), np.float32), np.zeros((t.value, self.num_envs), np.float32)
-        check(self._lib.adc_engine_pg_pop_advantages_fetch(self._h, adv.ctypes.data, ret.ctypes.data))
-        return adv, ret
+        return self._pg_advantages("pg_pop", fetch)
 
     def pg_pop_minibatch(self, index):
         """minibatch `index` of every member in the same launches; a list of M statistics dicts"""
-        st = (_ffi.PGStats * max(getattr(self, "_learners", 0), 1))()
+        st = (_ffi.PGStats * self._learner_count())()
         check(self._lib.adc_engine_pg_pop_minibatch(self._h, int(index), st))
         return [self._pg_stats(x) for x in st]
 
     def pg_pop_update(self, epochs=1, queued=False):
         """advantages, then `epochs` x the minibatches ascending, all members at once; a list of M statistics dicts.
         queued=True: one chain, one host wait (adc_engine_pg_pop_update_queued) - the same bits"""
-        st = (_ffi.PGStats * max(getattr(self, "_learners", 0), 1))()
-        update = self._lib.adc_engine_pg_pop_update_queued if queued else self._lib.adc_engine_pg_pop_update
-        check(update(self._h, int(epochs), st))
+        st = (_ffi.PGStats * self._learner_count())()
+        self._pg_update("pg_pop", st, epochs, queued)
         return [self._pg_stats(x) for x in st]
 
     def pg_pop_state(self, member, state=None):
         """one member's state.  get (no state): dict of theta, m, v [Q] float32 and steps; set: such a dict"""
-        Q = self.mlp_learner_param_count()
-        if state is None:
-            st = dict(theta=np.zeros(Q, np.float32), m=np.zeros(Q, np.float32), v=np.zeros(Q, np.float32))
-            n = C.c_int64(0)
-            check(self._lib.adc_engine_pg_pop_state_get(self._h, int(member), st["theta"].ctypes.data, st["m"].ctypes.data, st["v"].ctypes.data, C.byref(n)))
-            st["steps"] = n.value
-            return st
-        arr = [np.ascontiguousarray(state[k], dtype=np.float32) for k in ("theta", "m", "v")]
-        if any(a.shape != (Q,) for a in arr):
-            raise ValueError(f"pg_pop_state: theta, m and v have {Q} entries")
-        check(self._lib.adc_engine_pg_pop_state_set(self._h, int(member), arr[0].ctypes.data, arr[1].ctypes.data, arr[2].ctypes.data, int(state["steps"])))
+        return self._pg_state("pg_pop", member, state)
 
     def pg_pop_set_config(self, member, **options):
         """a member's hyperparameters from the next call on (options as pg_config's; minibatch_envs may not change)"""
@@ -1000,7 +999,7 @@ class StepEngine:
         built = [self.pg_kl_config(**o) for o in per_member] if per_member is not None else [self.pg_kl_config(**options)]
         arr = (_ffi.PGKLConfig * len(built))(*built)
         check(self._lib.adc_engine_pg_kl_init(self._h, arr, len(built)))
-        self._pg_kl_members = max(getattr(self, "_learners", 0), 1)
+        self._pg_kl_members = self._learner_count()
 
     def pg_kl_stats(self):
         """of the last minibatch or update: dict of kl, vf_clip_fraction, kl_coef (used), kl_coef_next - a list of them, one
@@ -1053,7 +1052,7 @@ class StepEngine:
         built = [self.pg_shuffle_config(**o) for o in per_member] if per_member is not None else [self.pg_shuffle_config(**options)]
         arr = (_ffi.PGShuffleConfig * len(built))(*built)
         check(self._lib.adc_engine_pg_shuffle_init(self._h, arr, len(built)))
-        self._pg_shuffle_members = max(getattr(self, "_learners", 0), 1)
+        self._pg_shuffle_members = self._learner_count()
 
     def pg_shuffle_epoch(self):
         """draw the order of a new epoch for every learner (after pg_advantages / pg_pop_advantages)"""

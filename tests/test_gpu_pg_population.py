@@ -515,3 +515,203 @@ def test_refusals_leave_the_engine_working(amd):
     e.run_days("mlp", T, BUDGET)
     assert e.pg_update(1)["steps"] == 1
     e.close()
+
+
+# ---- 7. the refusals the policy-gradient host files share (parts/pg_core.inc), by their whole sentence: a fragment such as "pg_init"
+# or "learners" is also part of the single learner's sentences ------------------------------------------------------------------------
+SAID = dict(
+    not_initialised="adc_engine_pg_pop_init has not been called (or the policy, the learners or the record were re-initialised since)",
+    no_learners="population training needs learners (adc_engine_mlp_learners)",
+    no_record="policy-gradient training needs a rollout record (adc_engine_rollout_enable)",
+    no_input="policy-gradient training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)",
+    no_day="no day has been recorded (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)",
+    deterministic="the record holds days collected with the deterministic policy: their log-probabilities mean nothing "
+                  "(adc_engine_mlp_set_deterministic(0), adc_engine_rollout_reset, collect again)",
+    no_advantages="adc_engine_pg_pop_advantages has not been called since the last recorded day",
+    td3="an off-policy (TD3) trainer is alive on this engine: one trainer at a time owns the policy's weights",
+    solo="a single-learner trainer is alive on this engine (adc_engine_pg_init)",
+    epochs="epochs: 1 to 65536",
+    minibatch="no such minibatch: 0 to envs of a member / minibatch_envs - 1",
+    shuffled_minibatch="no such minibatch: 0 to ceil(samples of a member / minibatch_samples) - 1",
+    member="no such member",
+    state_null="theta, m or v is NULL",
+    state_steps="steps: 0 to 2^31 - 2",
+    lds_keywords="num_keywords too large for policy-gradient training (LDS)",
+    lds_frames="frames: the stacked input row is too large for policy-gradient training (LDS); fewer frames fit",
+    kl_lds_keywords="num_keywords too large for the KL penalty (LDS)",
+)
+
+
+def _refused(kind, text, call):
+    with pytest.raises(kind) as info:
+        call()
+    assert str(info.value) == text, (str(info.value), text)
+
+
+def test_every_shared_refusal_by_its_whole_sentence_and_which_one_wins(amd):
+    from adcraft_amd import _ffi
+    M, n, K, T = 2, 2, 3, 2
+    N = M * n
+    STATE, VALUE = _ffi.EngineStateError, ValueError
+    pols = _policies(np.random.default_rng(411), K, M, hidden=(8,))
+    opts = P.options(minibatch_envs=1)
+    e = _engine(amd, _planes(N, K), **NO_RESETS)
+    e.mlp_init(pols[0], deterministic=False)
+    # the state an init needs; two at once: the missing learners are named before the missing record
+    _refused(STATE, SAID["no_learners"], lambda: e.pg_pop_init(opts))
+    e.mlp_learners(M)
+    _refused(STATE, SAID["no_record"], lambda: e.pg_pop_init(opts))
+    e.rollout_enable(T)
+    _refused(STATE, SAID["no_input"], lambda: e.pg_pop_init(opts))
+    for call in (lambda: e.pg_pop_advantages(), lambda: e.pg_pop_advantages(fetch=True), lambda: e.pg_pop_minibatch(0), lambda: e.pg_pop_update(1),
+                 lambda: e.pg_pop_update(1, queued=True), lambda: e.pg_pop_state(0), lambda: e.pg_pop_state(M), lambda: e.pg_pop_copy(0, M),
+                 lambda: e.pg_pop_set_config(M), lambda: _ffi.check(e._lib.adc_engine_pg_pop_advantages_fetch(e._h, None, None)),
+                 lambda: _ffi.check(e._lib.adc_engine_pg_pop_state_set(e._h, M, None, None, None, -1))):
+        _refused(STATE, SAID["not_initialised"], call)
+    # another trainer alive: TD3, the single learner (each on the centre policy, before the learners)
+    e.mlp_learners(0)
+    e.rollout_enable(T, obs=True)
+    e.td3_init(batch_size=8, capacity=64, critic_widths=(8, 1))
+    e.mlp_learners(M)
+    _refused(STATE, SAID["td3"], lambda: e.pg_pop_init(opts))
+    e.mlp_learners(0)
+    e.rollout_enable(T, obs=True)                                   # (drops TD3)
+    e.pg_init()
+    e.mlp_learners(M)
+    _refused(STATE, SAID["solo"], lambda: e.pg_pop_init(opts))
+    _refused(STATE, SAID["not_initialised"], lambda: e.pg_pop_update(1))       # (the single learner is not a population)
+    e.mlp_learners(0)
+    e.rollout_enable(T, obs=True)                                   # (drops the single learner)
+    e.mlp_learners(M)
+    for m in range(M):
+        e.mlp_set_learner(m, pols[m])
+    e.pg_pop_init(opts)
+    # the record; two at once: no day is named before the epochs, before the missing advantages and before the index
+    for call in (lambda: e.pg_pop_advantages(), lambda: e.pg_pop_update(1), lambda: e.pg_pop_update(0), lambda: e.pg_pop_update(1, queued=True),
+                 lambda: e.pg_pop_update(0, queued=True), lambda: e.pg_pop_minibatch(0), lambda: e.pg_pop_minibatch(-1)):
+        _refused(STATE, SAID["no_day"], call)
+    e.mlp_set_deterministic(True)
+    e.run_days("mlp", 1, BUDGET)
+    e.mlp_set_deterministic(False)
+    for call in (lambda: e.pg_pop_advantages(), lambda: e.pg_pop_update(1), lambda: e.pg_pop_update(1, queued=True), lambda: e.pg_pop_minibatch(0)):
+        _refused(STATE, SAID["deterministic"], call)
+    e.rollout_reset()
+    e.run_days("mlp", 1, BUDGET)
+    # the advantages (named before a bad index), the index, the epochs
+    for call in (lambda: e.pg_pop_minibatch(0), lambda: e.pg_pop_minibatch(-1),
+                 lambda: _ffi.check(e._lib.adc_engine_pg_pop_advantages_fetch(e._h, None, None))):
+        _refused(STATE, SAID["no_advantages"], call)
+    for epochs in (0, 65537):
+        _refused(VALUE, SAID["epochs"], lambda: e.pg_pop_update(epochs))
+        _refused(VALUE, SAID["epochs"], lambda: e.pg_pop_update(epochs, queued=True))
+    e.pg_pop_advantages()
+    for index in (-1, n):
+        _refused(VALUE, SAID["minibatch"], lambda: e.pg_pop_minibatch(index))
+    # the member, the state's arguments; two at once: the member is named before the arrays, a missing array before the step count
+    st = e.pg_pop_state(0)
+    three = [st[k].ctypes.data for k in ("theta", "m", "v")]
+    for member in (-1, M):
+        for call in (lambda: e.pg_pop_state(member), lambda: e.pg_pop_state(member, st), lambda: e.pg_pop_copy(0, member), lambda: e.pg_pop_copy(member, 0),
+                     lambda: e.pg_pop_set_config(member, **opts),
+                     lambda: _ffi.check(e._lib.adc_engine_pg_pop_state_set(e._h, member, None, None, None, -1))):
+            _refused(VALUE, SAID["member"], call)
+    _refused(VALUE, SAID["state_null"], lambda: _ffi.check(e._lib.adc_engine_pg_pop_state_set(e._h, 1, three[0], three[1], None, -1)))
+    for steps in (-1, 2 ** 31 - 1):
+        _refused(VALUE, SAID["state_steps"], lambda: e.pg_pop_state(1, dict(st, steps=steps)))
+    # the add-ons' member and minibatch indices over the shared count of members
+    e.pg_kl_init()
+    for member in (-1, M):
+        _refused(VALUE, SAID["member"], lambda: e.pg_kl_coef(member))
+        _refused(VALUE, SAID["member"], lambda: e.pg_kl_coef(member, 0.5))
+    e.pg_shuffle_init(minibatch_samples=2)
+    e.pg_pop_advantages()
+    e.pg_shuffle_epoch()
+    for index in (-1, 1):
+        _refused(VALUE, SAID["shuffled_minibatch"], lambda: e.pg_shuffle_minibatch(index))
+    # after all of it the trainer works, and the members' step counts say what was taken
+    assert [e.pg_pop_state(m)["steps"] for m in range(M)] == [0, 0]
+    assert [s["steps"] for s in e.pg_pop_update(1)] == [1, 1]
+    assert [s["steps"] for s in e.pg_pop_update(1, queued=True)] == [2, 2]
+    e.close()
+
+
+def _lds_floats(K, frames, hidden, kl):
+    """kernel_pg.inc's pg_lds_floats for a free-head policy and a value network of one hidden layer each"""
+    D, A = frames * (5 * K + 2), K + 1
+    return D + 2 * max(hidden, A) + (5 if kl else 3) * A + (hidden + A) + (hidden + 1)
+
+
+@pytest.mark.parametrize("K,frames,kl,said", [(1488, 1, False, "lds_keywords"), (1023, 2, False, "lds_frames"), (1259, 1, True, "kl_lds_keywords")])
+def test_the_first_shape_past_64_kib_of_lds_is_refused_in_the_right_words(amd, K, frames, kl, said):
+    """a sample's workgroup holds 11 K + 25 floats (13 K + 27 under the KL penalty) for one frame and one hidden layer of 8:
+    K is the first that passes 16384 floats, K - 1 fits; with two frames one frame of that K still fits, so the frames are named.
+    Two learners of one env each, one recorded day"""
+    from adcraft_amd import _ffi
+    from tests import stack_ref as S
+    M, T, hidden = 2, 1, 8
+    assert _lds_floats(K, frames, hidden, kl) > 16384 >= _lds_floats(K - 1, frames, hidden, kl)
+    assert frames == 1 or _lds_floats(K, 1, hidden, kl) <= 16384   # (one frame of it fits)
+    assert not kl or _lds_floats(K, frames, hidden, False) <= 16384    # (the trainer itself fits: the add-on's two vectors do not)
+    pol = S.random_policy(np.random.default_rng(431), K, frames, (hidden,), value=True)
+    e = _engine(amd, H.implicit_params(M, K, SEED + 1, mean_volume=4, cvr=0.5), **NO_RESETS)
+    e.mlp_init(pol, deterministic=False)
+    e.mlp_learners(M)
+    e.rollout_enable(T, obs=True)
+    if kl:
+        e.pg_pop_init(P.options())
+        _refused(ValueError, SAID[said], lambda: e.pg_kl_init())
+        e.run_days("mlp", 1, BUDGET)
+        assert [s["steps"] for s in e.pg_pop_update(1)] == [1, 1]   # (the trainer goes on without the add-on)
+    else:
+        _refused(ValueError, SAID[said], lambda: e.pg_pop_init(P.options()))
+        _refused(_ffi.EngineStateError, SAID["not_initialised"], lambda: e.pg_pop_state(0))    # (the refused init left no trainer)
+    e.close()
+
+
+# ---- 8. a population of one member is the single learner: the case in which "one configuration" and "one per member" coincide and
+# the per-member vectors of length one are read from both front ends ---------------------------------------------------------------
+@pytest.mark.parametrize("queued", [False, True])
+@pytest.mark.parametrize("addons", [False, True])
+def test_a_population_of_one_is_the_single_learner_bit_for_bit(amd, addons, queued):
+    """4 envs, 3 keywords, horizon 3, minibatches of 2 envs, two iterations of two epochs on twin engines; addons: the KL penalty and
+    shuffled minibatches of 5 of the 12 samples (5, 5 and a tail of 2)"""
+    N, K, T = 4, 3, 3
+    pol = _policies(np.random.default_rng(421), K, 1, hidden=(8,))[0]
+    opts = P.options(minibatch_envs=2)
+
+    def run(pop):
+        e = _engine(amd, _planes(N, K), **NO_RESETS)
+        e.mlp_init(pol, deterministic=False)
+        if pop:
+            e.mlp_learners(1)
+            e.mlp_set_learner(0, pol)
+        e.rollout_enable(T, obs=True)
+        e.pg_pop_init(opts) if pop else e.pg_init(**opts)
+        if addons:
+            e.pg_kl_init(kl_coef=0.3, kl_target=0.001)
+            e.pg_shuffle_init(minibatch_samples=5)
+        one = (lambda x: x[0]) if pop else (lambda x: x)
+        out = []
+        for _ in range(2):
+            e.rollout_reset()
+            e.run_days("mlp", T, BUDGET)
+            stats = one(e.pg_pop_update(2, queued=queued) if pop else e.pg_update(2, queued=queued))
+            it = dict(state=e.pg_pop_state(0) if pop else e.pg_state(), stats=stats)
+            if addons:
+                it.update(kl=one(e.pg_kl_stats()), coef=e.pg_kl_coef(0), shuffle=one(e.pg_shuffle_stats()))
+            out.append(it)
+        e.close()
+        return out
+
+    solo, pop = run(False), run(True)
+    for it, (a, b) in enumerate(zip(solo, pop)):
+        _assert_state(b["state"], a["state"], it)
+        assert a["state"]["steps"] == (it + 1) * 2 * (3 if addons else 2), a["state"]["steps"]
+        assert set(a["stats"]) == set(b["stats"]) and len(a["stats"]) >= 9
+        for k in a["stats"]:
+            assert _same(np.float64(a["stats"][k]), np.float64(b["stats"][k])), (k, a["stats"][k], b["stats"][k], it)
+        if addons:
+            for k in a["kl"]:
+                assert _same(np.float64(a["kl"][k]), np.float64(b["kl"][k])), (k, a["kl"][k], b["kl"][k], it)
+            assert _same(a["coef"], b["coef"]) and a["shuffle"] == b["shuffle"], (a["coef"], b["coef"], a["shuffle"], b["shuffle"])
+    assert not _same(solo[0]["state"]["theta"], solo[1]["state"]["theta"])

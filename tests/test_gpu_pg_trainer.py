@@ -371,6 +371,145 @@ def test_refusals_leave_the_engine_working(amd):
     s.close()
 
 
+# ---- the refusals the three policy-gradient host files share (parts/pg_core.inc), by their whole sentence: a fragment such as
+# "pg_init" is also part of the population's sentences --------------------------------------------------------------------------
+SAID = dict(
+    not_initialised="adc_engine_pg_init has not been called (or the policy / the record was re-initialised since)",
+    population="policy-gradient training with a population active is not supported (adc_engine_mlp_population(0) first)",
+    learners="learners are active: they train through adc_engine_pg_pop_init (adc_engine_mlp_learners(0) first)",
+    no_record="policy-gradient training needs a rollout record (adc_engine_rollout_enable)",
+    no_input="policy-gradient training needs the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)",
+    no_day="no day has been recorded (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)",
+    deterministic="the record holds days collected with the deterministic policy: their log-probabilities mean nothing "
+                  "(adc_engine_mlp_set_deterministic(0), adc_engine_rollout_reset, collect again)",
+    no_advantages="adc_engine_pg_advantages has not been called since the last recorded day",
+    td3="an off-policy (TD3) trainer is alive on this engine: one trainer at a time owns the policy's weights",
+    epochs="epochs: 1 to 65536",
+    env_range="the env range is not inside [0, num_envs)",
+    env_count="env_count exceeds the configuration's minibatch_envs (the scratch was sized for it)",
+    minibatch="no such minibatch: 0 to ceil(samples of a member / minibatch_samples) - 1",
+    member="no such member",
+    state_null="theta, m or v is NULL",
+    state_steps="steps: 0 to 2^31 - 2",
+    lds_keywords="num_keywords too large for policy-gradient training (LDS)",
+    lds_frames="frames: the stacked input row is too large for policy-gradient training (LDS); fewer frames fit",
+    kl_lds_keywords="num_keywords too large for the KL penalty (LDS)",
+    kl_lds_frames="frames: the stacked input row is too large for the KL penalty (LDS); fewer frames fit",
+)
+
+
+def _refused(kind, text, call):
+    with pytest.raises(kind) as info:
+        call()
+    assert str(info.value) == text, (str(info.value), text)
+
+
+def test_every_shared_refusal_by_its_whole_sentence_and_which_one_wins(amd):
+    from adcraft_amd import _ffi
+    N, K, T = 4, 3, 2
+    STATE, VALUE = _ffi.EngineStateError, ValueError
+    pol = _policy(np.random.default_rng(91), K, (8,))
+    e = _engine(amd, N, K, seed=83, **NO_RESETS)
+    e.mlp_init(pol, deterministic=False)
+    # the state an init needs; two at once: the population is named before the missing record
+    _refused(STATE, SAID["no_record"], lambda: e.pg_init())
+    e.mlp_population(2)
+    _refused(STATE, SAID["population"], lambda: e.pg_init())
+    e.mlp_population(0)
+    e.rollout_enable(T)
+    _refused(STATE, SAID["no_input"], lambda: e.pg_init())
+    for call in (lambda: e.pg_advantages(), lambda: e.pg_advantages(fetch=True), lambda: e.pg_minibatch(0, N), lambda: e.pg_update(1),
+                 lambda: e.pg_update(1, queued=True), lambda: e.pg_state(), lambda: e.pg_param_count(),
+                 lambda: _ffi.check(e._lib.adc_engine_pg_advantages_fetch(e._h, None, None)),
+                 lambda: _ffi.check(e._lib.adc_engine_pg_state_set(e._h, None, None, None, 0))):
+        _refused(STATE, SAID["not_initialised"], call)
+    e.rollout_enable(T, obs=True)
+    # another trainer alive
+    e.td3_init(batch_size=8, capacity=64, critic_widths=(8, 1))
+    _refused(STATE, SAID["td3"], lambda: e.pg_init())
+    e.rollout_enable(T, obs=True)                                   # (drops TD3)
+    e.pg_init(minibatch_envs=N // 2)
+    # the record; two at once: no day is named before the epochs, before the missing advantages and before the range
+    for call in (lambda: e.pg_advantages(), lambda: e.pg_update(1), lambda: e.pg_update(0), lambda: e.pg_update(1, queued=True),
+                 lambda: e.pg_update(0, queued=True), lambda: e.pg_minibatch(0, 2), lambda: e.pg_minibatch(-1, 2)):
+        _refused(STATE, SAID["no_day"], call)
+    e.mlp_set_deterministic(True)
+    e.run_days("mlp", 1, 1000.0)
+    e.mlp_set_deterministic(False)
+    for call in (lambda: e.pg_advantages(), lambda: e.pg_update(1), lambda: e.pg_update(1, queued=True), lambda: e.pg_minibatch(0, 2)):
+        _refused(STATE, SAID["deterministic"], call)
+    e.rollout_reset()
+    e.run_days("mlp", 1, 1000.0)
+    # the advantages (named before a bad range), the ranges, the epochs
+    for call in (lambda: e.pg_minibatch(0, 2), lambda: e.pg_minibatch(-1, 2),
+                 lambda: _ffi.check(e._lib.adc_engine_pg_advantages_fetch(e._h, None, None))):
+        _refused(STATE, SAID["no_advantages"], call)
+    for epochs in (0, 65537):
+        _refused(VALUE, SAID["epochs"], lambda: e.pg_update(epochs))
+        _refused(VALUE, SAID["epochs"], lambda: e.pg_update(epochs, queued=True))
+    e.pg_advantages()
+    for n0, B in ((-1, 2), (0, 0), (3, 2)):
+        _refused(VALUE, SAID["env_range"], lambda: e.pg_minibatch(n0, B))
+    _refused(VALUE, SAID["env_count"], lambda: e.pg_minibatch(0, N))
+    # the state's arguments; two at once: the missing array is named before the step count
+    st = e.pg_state()
+    three = [st[k].ctypes.data for k in ("theta", "m", "v")]
+    _refused(VALUE, SAID["state_null"], lambda: _ffi.check(e._lib.adc_engine_pg_state_set(e._h, three[0], None, three[2], -1)))
+    for steps in (-1, 2 ** 31 - 1):
+        _refused(VALUE, SAID["state_steps"], lambda: e.pg_state(dict(st, steps=steps)))
+    # the add-ons' member and minibatch indices over the shared count of members; learners with the trainer alive
+    e.pg_kl_init()
+    for member in (-1, 1):
+        _refused(VALUE, SAID["member"], lambda: e.pg_kl_coef(member))
+        _refused(VALUE, SAID["member"], lambda: e.pg_kl_coef(member, 0.5))
+    e.pg_shuffle_init(minibatch_samples=3)
+    e.pg_advantages()
+    e.pg_shuffle_epoch()
+    for index in (-1, 2):
+        _refused(VALUE, SAID["minibatch"], lambda: e.pg_shuffle_minibatch(index))
+    e.mlp_learners(2)
+    for call in (lambda: e.pg_update(1), lambda: e.pg_update(0, queued=True), lambda: e.pg_advantages(), lambda: e.pg_minibatch(-1, 2)):
+        _refused(STATE, SAID["learners"], call)
+    e.mlp_learners(0)
+    # after all of it the trainer works, and its step count says what was taken
+    assert e.pg_state()["steps"] == 0
+    assert e.pg_update(1)["steps"] == 2
+    assert e.pg_update(1, queued=True)["steps"] == 4
+    e.close()
+
+
+def _lds_floats(K, frames, hidden, kl):
+    """kernel_pg.inc's pg_lds_floats for a free-head policy and a value network of one hidden layer each"""
+    D, A = frames * (5 * K + 2), K + 1
+    return D + 2 * max(hidden, A) + (5 if kl else 3) * A + (hidden + A) + (hidden + 1)
+
+
+@pytest.mark.parametrize("K,frames,kl,said", [(1488, 1, False, "lds_keywords"), (1023, 2, False, "lds_frames"),
+                                              (1259, 1, True, "kl_lds_keywords"), (909, 2, True, "kl_lds_frames")])
+def test_the_first_shape_past_64_kib_of_lds_is_refused_in_the_right_words(amd, K, frames, kl, said):
+    """a sample's workgroup holds 11 K + 25 floats (13 K + 27 under the KL penalty) for one frame and one hidden layer of 8:
+    K is the first that passes 16384 floats, K - 1 fits; with two frames one frame of that K still fits, so the frames are named"""
+    from adcraft_amd import _ffi
+    from tests import stack_ref as S
+    N, T, hidden = 2, 1, 8
+    assert _lds_floats(K, frames, hidden, kl) > 16384 >= _lds_floats(K - 1, frames, hidden, kl)
+    assert frames == 1 or _lds_floats(K, 1, hidden, kl) <= 16384   # (one frame of it fits)
+    assert not kl or _lds_floats(K, frames, hidden, False) <= 16384    # (the trainer itself fits: the add-on's two vectors do not)
+    pol = S.random_policy(np.random.default_rng(97), K, frames, (hidden,), value=True)
+    e = _engine(amd, N, K, seed=85, mean_volume=4, **NO_RESETS)
+    e.mlp_init(pol, deterministic=False)
+    e.rollout_enable(T, obs=True)
+    if kl:
+        e.pg_init()
+        _refused(ValueError, SAID[said], lambda: e.pg_kl_init())
+        e.run_days("mlp", 1, 1000.0)
+        assert e.pg_update(1)["steps"] == 1                         # (the trainer goes on without the add-on)
+    else:
+        _refused(ValueError, SAID[said], lambda: e.pg_init())
+        _refused(_ffi.EngineStateError, SAID["not_initialised"], lambda: e.pg_state())    # (the refused pg_init left no trainer)
+    e.close()
+
+
 # the ES test's small shape (LEARN in tests/test_gpu_es_population.py), and what this trainer was given on it
 LEARN = dict(N=1024, K=25, days=10, budget=100000.0, mean_volume=8.0, hidden=(32, 32), iterations=40,
              config=dict(epochs=4, minibatches=4, lr=1e-3, reward_scale=0.1, normalize_advantages=True))

@@ -495,6 +495,14 @@ def lib():
         "adc_engine_replay_prio_fetch": ([vp, i32, i64, i64, vp], C.c_int),
         "adc_engine_replay_prio_load": ([vp, i32, i64, i64, vp, f32], C.c_int),
         "adc_engine_replay_prio_batch": ([vp, i32, i64, vp, vp], C.c_int),
+        "adc_replay_nstep_check": ([i32, C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_replay_nstep_init": ([vp, i32], C.c_int),
+        "adc_engine_replay_nstep_info": ([vp, C.POINTER(i32)], C.c_int),
+        "adc_engine_replay_nstep_fetch": ([vp, i32, i64, i64, vp], C.c_int),
+        "adc_engine_replay_nstep_load": ([vp, i32, i64, i64, vp], C.c_int),
+        "adc_replay_nstep_host": ([i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_td3_y_nstep_host": ([C.POINTER(TD3Config), i32, vp, vp, vp, vp, f32, f32, vp], C.c_int),
+        "adc_sac_y_nstep_host": ([C.POINTER(SACConfig), i32, vp, vp, vp, vp, vp, f32, f32, f32, vp], C.c_int),
         "adc_per_tree_host": ([i64, vp, vp, vp], C.c_int),
         "adc_per_descend_host": ([i64, vp, f64, C.POINTER(i64)], C.c_int),
         "adc_per_sample_host": ([C.POINTER(ReplayPrioConfig), i64, i64, vp, u64, i64, i32, vp, vp], C.c_int),

@@ -13,7 +13,8 @@ import copy
 import numpy as np
 
 from .mlp_policy import history_carry
-from .td3_trainer import NORM_OPTIONS, PrioritizedReplay, _norm_options, _norm_state, _with_vectors, policy_from_actor, random_critics
+from .td3_trainer import (NORM_OPTIONS, NStepReturns, PrioritizedReplay, _norm_options, _norm_state, _with_vectors, nstep_check, policy_from_actor, random_critics,
+                          shared_nstep)
 
 
 def sac(num_keywords, **overrides):
@@ -71,21 +72,23 @@ class _NormalizedSAC:
             _norm_state(self.engine, member, norm, envs, family="sac")
 
 
-class SACTrainer(PrioritizedReplay, _NormalizedSAC):
+class SACTrainer(PrioritizedReplay, NStepReturns, _NormalizedSAC):
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (2 (K + 1) outputs, log_std_clamp set; a
     value network is ignored); action_lo / action_hi [K + 1] (or scalars): the squash bounds in the flat action order (budget,
     bids); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection; learning_starts:
     transitions the ring must hold before the first update; updates_per_iteration: updates after every collection.  config:
     sac()'s other keys and StepEngine.sac_config's options, plus critic_seed (random_critics' seed) and critics (two lists of
-    layers, instead).  prioritized_replay: None, or PrioritizedReplay's dict (td3_trainer.py).
+    layers, instead).  prioritized_replay: None, or PrioritizedReplay's dict (td3_trainer.py).  n_step: the window of n-step
+    returns, 1 (off) to 16 (NStepReturns, td3_trainer.py); state() carries `replay_nstep`.
 
     normalize_observations / normalize_rewards: running normalisers on the device (_NormalizedSAC above); their options -
     obs_min_std, obs_count_cap, rew_min_std, rew_count_cap, rew_clip - as keywords or as norm=dict(...).  state() / load_state()
     carry the normaliser."""
 
     def __init__(self, engine, policy, action_lo, action_hi, critic_hidden=(256, 256), horizon=10, learning_starts=1500, updates_per_iteration=64,
-                 agent_seeds=None, prioritized_replay=None, normalize_observations=False, normalize_rewards=False, norm=None, **config):
+                 agent_seeds=None, prioritized_replay=None, normalize_observations=False, normalize_rewards=False, norm=None, n_step=1, **config):
         cfg = dict(config)
+        n_step = nstep_check(n_step)
         norm = _sac_norm_options([policy], normalize_observations, normalize_rewards, norm, cfg)
         A = policy.num_keywords + 1
         if policy.output_size != 2 * A or policy.log_std_clamp is None:
@@ -105,6 +108,7 @@ class SACTrainer(PrioritizedReplay, _NormalizedSAC):
         if self._norm_on():
             engine.sac_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self._prio_init(engine, prioritized_replay)
+        self._nstep_init(engine, n_step)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -136,7 +140,8 @@ class SACTrainer(PrioritizedReplay, _NormalizedSAC):
     def state(self, state=None):
         """the learner's state (StepEngine.sac_state's dict), `replay_prio` under prioritised replay and `norm` under running
         normalisers; get or set.  With the ring (sac_buffer) a resumed run continues bit for bit"""
-        return history_carry(self.engine, lambda t: self._norm_carry(lambda s: self._prio_state(self.engine.sac_state, 0, s), 0, t), state)
+        return history_carry(self.engine,
+                             lambda u: self._nstep_state(lambda t: self._norm_carry(lambda s: self._prio_state(self.engine.sac_state, 0, s), 0, t), 0, u), state)
 
     def load_state(self, state):
         self.state(state)
@@ -146,7 +151,7 @@ class SACTrainer(PrioritizedReplay, _NormalizedSAC):
         return _norm_state(self.engine, 0, state, family="sac")
 
 
-class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
+class SACPopulationTrainer(PrioritizedReplay, NStepReturns, _NormalizedSAC):
     """M independent SAC learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
     actor, twin critics, target critics, temperature, optimiser state, hyperparameters and replay ring, and every launch of a
     store or an update covers all members (StepEngine.sac_pop_*).  What a member computes is bit for bit what SACTrainer computes
@@ -156,8 +161,8 @@ class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
     shape (2 (K + 1) outputs, log_std_clamp set); configs: one dict of SACTrainer's keyword options (sac()'s keys and
     StepEngine.sac_config's, plus critic_seed and critics) shared by all members, or M of them - M is `members`, or the larger
     of the two counts; action_lo / action_hi [K + 1] (or scalars): the squash bounds, shared by all members.  critic_hidden,
-    batch_size, capacity, target_update_interval, learning_starts (transitions of a member's ring) and updates_per_iteration
-    must be equal in all configurations: the members move together.  prioritized_replay: None, or PrioritizedReplay's dict,
+    batch_size, capacity, target_update_interval, learning_starts (transitions of a member's ring), updates_per_iteration and
+    n_step (NStepReturns, td3_trainer.py) must be equal in all configurations: the members move together.  prioritized_replay: None, or PrioritizedReplay's dict,
     shared by all members (every member has its own tree).
 
     normalize_observations / normalize_rewards: every member has its own running normalisers (per_member; _NormalizedSAC above),
@@ -173,6 +178,7 @@ class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
         norm = _norm_options(policies, normalize_observations, normalize_rewards, norm)
         self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
         configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
+        n_step = shared_nstep(configs)
         members = max(len(policies), len(configs)) if members is None else int(members)
         if any(len(x) not in (1, members) for x in (policies, configs)) or not policies or not configs:
             raise ValueError("SACPopulationTrainer: policies and configs are each one (shared) or one per member")
@@ -212,6 +218,7 @@ class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
         if self._norm_on():
             engine.sac_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self._prio_init(engine, prioritized_replay)
+        self._nstep_init(engine, n_step)
         self.history = []
 
     def iteration(self, days=None, budget=0.0, reset=False, reset_seeds=None):
@@ -249,8 +256,9 @@ class SACPopulationTrainer(PrioritizedReplay, _NormalizedSAC):
         """member's state (StepEngine.sac_pop_state's dict), `replay_prio` under prioritised replay and `norm` under running
         normalisers; get or set"""
         envs = self.engine.num_envs // self.members
-        return history_carry(self.engine, lambda u: self._norm_carry(lambda s: self._prio_state(lambda t: self.engine.sac_pop_state(member, t), member, s),
-                                                                     member, u, envs), state, member, envs)
+        return history_carry(self.engine, lambda w: self._nstep_state(
+            lambda u: self._norm_carry(lambda s: self._prio_state(lambda t: self.engine.sac_pop_state(member, t), member, s), member, u, envs), member, w),
+            state, member, envs)
 
     def load_state(self, member, state):
         self.state(member, state)

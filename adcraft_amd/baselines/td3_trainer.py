@@ -8,7 +8,8 @@ without a transition leaving HBM.  The arithmetic is csrc/adc_td3.h; StepEngine.
 The actor is the MLPPolicy's policy network with the free log_std head; its mean is the deterministic action and
 mean + exp(log_std) * z, log_std = log(exploration sigma), the exploration.  The reference's pure-random warm-up
 (`random_timesteps`) is covered by collecting under the initial policy with a larger sigma for the first iterations:
-`TD3Trainer.set_exploration(sigma)`, then back."""
+`TD3Trainer.set_exploration(sigma)`, then back.  n_step > 1 turns on n-step returns (StepEngine.replay_nstep_*; the law is
+csrc/adc_td3.h "n-step") for the trainer's ring(s)."""
 import copy
 
 import numpy as np
@@ -148,7 +149,53 @@ class PrioritizedReplay:
             self._prio_iterations = int(prio.get("iterations", self._prio_iterations))
 
 
-class TD3Trainer(PrioritizedReplay):
+def nstep_check(n_step):
+    """n_step as an int in 1..16 (the engine's own refusal, which needs no device)"""
+    import ctypes
+
+    from .. import _ffi
+    if isinstance(n_step, bool) or int(n_step) != n_step:
+        raise ValueError("n_step: an integer from 1 to 16")
+    msg = ctypes.c_char_p()
+    if _ffi.lib().adc_replay_nstep_check(int(n_step), ctypes.byref(msg)) != _ffi.ADC_OK:
+        raise ValueError("n_step: " + (msg.value or b"1 to 16").decode())
+    return int(n_step)
+
+
+def shared_nstep(configs):
+    """n_step of a population's configurations (taken out of them): a shared key, refused when it differs"""
+    steps = [c.pop("n_step", 1) for c in configs]
+    if any(n != steps[0] for n in steps):
+        raise ValueError("n_step is shared by all members (one window for every ring): it must be equal in all configurations")
+    return nstep_check(steps[0])
+
+
+class NStepReturns:
+    """the trainers' side of n_step: with n_step > 1 the store writes n-step returns and the targets bootstrap with the slots' own
+    discounts (StepEngine.replay_nstep_*; csrc/adc_td3.h "n-step"); with n_step == 1 the add-on is never initialised and every call
+    launches what it launched.  A trainer's state() then carries `replay_nstep` - n and the slots' gn - set after the ring was
+    loaded.  What n-step returns gain in learning on this env has not been measured."""
+
+    def _nstep_init(self, engine, n_step):
+        self.n_step = nstep_check(n_step)
+        if self.n_step > 1:
+            engine.replay_nstep_init(self.n_step)
+
+    def _nstep_state(self, get_or_set, member, state):
+        """get_or_set(state): the trainer's own state call; `replay_nstep` rides along"""
+        if state is None:
+            st = get_or_set(None)
+            if self.n_step > 1:
+                st["replay_nstep"] = self.engine.replay_nstep_state(member)
+            return st
+        state = dict(state)
+        nstep = state.pop("replay_nstep", None)
+        get_or_set(state)
+        if nstep is not None and self.n_step > 1:
+            self.engine.replay_nstep_state(member, nstep)
+
+
+class TD3Trainer(PrioritizedReplay, NStepReturns):
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (K + 1 means, free log_std; a value network
     is ignored); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection;
     exploration_sigma: the standard deviation of the collection noise; learning_starts: transitions the ring must hold before
@@ -161,11 +208,12 @@ class TD3Trainer(PrioritizedReplay):
     statistics updated from every collection BEFORE its updates; norm: dict(obs_min_std=..., obs_count_cap=..., rew_min_std=...,
     rew_count_cap=..., rew_clip=...).  What they gain in learning has not been measured.
 
-    prioritized_replay: None, or PrioritizedReplay's dict."""
+    prioritized_replay: None, or PrioritizedReplay's dict.  n_step: the window of n-step returns, 1 (off) to 16 (NStepReturns)."""
 
     def __init__(self, engine, policy, critic_hidden=(256, 256), horizon=10, exploration_sigma=0.1, learning_starts=10000, updates_per_iteration=64,
-                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, prioritized_replay=None, **config):
+                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, prioritized_replay=None, n_step=1, **config):
         norm = _norm_options([policy], normalize_observations, normalize_rewards, norm)
+        n_step = nstep_check(n_step)
         if policy.log_std is None:
             raise ValueError("TD3 needs a policy that ends in K + 1 means with the free log_std vector")
         self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
@@ -184,6 +232,7 @@ class TD3Trainer(PrioritizedReplay):
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self._prio_init(engine, prioritized_replay)
+        self._nstep_init(engine, n_step)
         self.history = []
 
     def set_exploration(self, sigma):
@@ -217,9 +266,9 @@ class TD3Trainer(PrioritizedReplay):
         return _with_vectors(pol, self.engine.td3_norm_state()) if self.normalize_observations else pol
 
     def state(self, state=None):
-        """the learner's state (StepEngine.td3_state's dict), `replay_prio` under prioritised replay and `obs_history` with
-        MLPPolicy(frames > 1); get or set"""
-        return history_carry(self.engine, lambda s: self._prio_state(self.engine.td3_state, 0, s), state)
+        """the learner's state (StepEngine.td3_state's dict), `replay_prio` under prioritised replay, `replay_nstep` under n-step
+        returns and `obs_history` with MLPPolicy(frames > 1); get or set"""
+        return history_carry(self.engine, lambda t: self._nstep_state(lambda s: self._prio_state(self.engine.td3_state, 0, s), 0, t), state)
 
     def load_state(self, state):
         self.state(state)
@@ -229,7 +278,7 @@ class TD3Trainer(PrioritizedReplay):
         return _norm_state(self.engine, 0, state)
 
 
-class TD3PopulationTrainer(PrioritizedReplay):
+class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
     """M independent TD3 learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
     actor, exploration sigma, twin critics, targets, optimiser state, hyperparameters and replay ring, and every launch of a
     store or an update covers all members (StepEngine.td3_pop_*).  What a member computes is bit for bit what TD3Trainer
@@ -239,7 +288,7 @@ class TD3PopulationTrainer(PrioritizedReplay):
     sigmas: one exploration sigma or M, or None: every configuration's exploration_sigma (default 0.1); configs: one dict of
     TD3Trainer's keyword options (td3()'s keys and StepEngine.td3_config's, plus critic_seed, critics, action_norm) shared by
     all members or M of them - M is `members`, or the largest of the three counts.  critic_hidden, batch_size, capacity, policy_delay, learning_starts (transitions of a member's ring),
-    updates_per_iteration and action_norm must be equal in all configurations: the members move together.
+    updates_per_iteration, n_step and action_norm must be equal in all configurations: the members move together.
 
     normalize_observations / normalize_rewards: every member has its own running normalisers (TD3Trainer's, per member: a
     member's statistics are bit for bit a single trainer's of its envs; the reward's discount is the member's own gamma); norm as
@@ -253,6 +302,7 @@ class TD3PopulationTrainer(PrioritizedReplay):
         norm = _norm_options(policies, normalize_observations, normalize_rewards, norm)
         self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
         configs = [dict(configs)] if isinstance(configs, dict) else [dict(c) for c in configs]
+        n_step = shared_nstep(configs)
         own = [c.pop("exploration_sigma", 0.1) for c in configs]
         sigmas = own if sigmas is None else [float(sigmas)] if np.isscalar(sigmas) else [float(s) for s in sigmas]
         members = max(len(policies), len(sigmas), len(configs)) if members is None else int(members)
@@ -297,6 +347,7 @@ class TD3PopulationTrainer(PrioritizedReplay):
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self._prio_init(engine, prioritized_replay)
+        self._nstep_init(engine, n_step)
         self.history = []
 
     def set_exploration(self, sigma, member=None):
@@ -337,8 +388,9 @@ class TD3PopulationTrainer(PrioritizedReplay):
 
     def state(self, member, state=None):
         """member's state; `obs_history` (with MLPPolicy(frames > 1)) holds its own envs'"""
-        return history_carry(self.engine, lambda t: self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, t), state, member,
-                             self.engine.num_envs // self.members)
+        return history_carry(self.engine,
+                             lambda u: self._nstep_state(lambda t: self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, t), member, u),
+                             state, member, self.engine.num_envs // self.members)
 
     def load_state(self, member, state):
         self.state(member, state)
@@ -348,4 +400,4 @@ class TD3PopulationTrainer(PrioritizedReplay):
         return _norm_state(self.engine, member, state, self.engine.num_envs // self.members)
 
 
-__all__ = ["PrioritizedReplay", "TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]
+__all__ = ["NStepReturns", "PrioritizedReplay", "TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]

@@ -86,6 +86,7 @@
 //   parts/sac_pop_api.inc         the entry points of SAC learner populations, over offpolicy_core.inc.
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over a PG, TD3 or SAC population.
 //   parts/per_api.inc             the entry points of prioritised replay over a TD3 or SAC trainer, and what the trainers' updates call of it.
+//   parts/nstep_api.inc           the entry points of n-step returns over a TD3 or SAC trainer (the store's window and the targets' gn are the kernels').
 //   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners', the SAC learners' - over shared helpers.
 //
 // No CPU path exists in this library.
@@ -162,5 +163,6 @@ using namespace adck;
 #include "parts/sac_pop_api.inc"
 #include "parts/pbt_api.inc"
 #include "parts/per_api.inc"
+#include "parts/nstep_api.inc"
 #include "parts/norm_api.inc"
 #include "parts/comm_api.inc"

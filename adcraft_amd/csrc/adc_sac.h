@@ -19,7 +19,7 @@
 //              step: ST_SAC_PI = 21, both addressed (a / 4, stage, b, u) as td3_noise is.  No env or agent stream moves.
 //   target     (mean', ls') = the LIVE actor on x' (no target actor); u', t', lp' as above with z';
 //              q = td3_min(Q1'([x'|t']), Q2'([x'|t'])); al = alpha * lp'; v = q - al; gv = gamma * v; gvn = gv * nt;
-//              y = (r * reward_scale) + gvn.
+//              y = (r * reward_scale) + gvn.  Under n-step returns (adc_td3.h "n-step") r is the slot's R and gv = gn * v.
 //   critic     as adc_td3.h's, on [x | t]; one pg_apply step on psi with critic_lr, t = updates + 1.
 //   actor      every update, after the critic step, same batch: (mean, ls), z, u, t, w, lp; q_i = Q_i([x | t]) for both UPDATED
 //              critics; i* = q_2 < q_1 ? 2 : 1 (a tie takes critic 1); output delta +1 on critic i*, its hidden deltas, one layer
@@ -88,13 +88,15 @@ ADC_HD SacHead sac_head(float mean, float raw, float z, const SacLaw &law)
 }
 ADC_HD float sac_lp_finish(float sum_terms, float sum_c, int A) { return mlp_logp_finish(sum_terms, A) - sum_c; }
 
-ADC_HD float sac_y(float r, int done, float q, float alpha, float lp, const SacLaw &w)
+// g: the bootstrap discount, the law's gamma or the slot's gn (adc_td3.h "n-step": gv = gn * v)
+ADC_HD float sac_y_g(float r, int done, float q, float alpha, float lp, float g, const SacLaw &w)
 {
     const float rs = r * w.reward_scale;
     const float nt = done ? 0.0f : 1.0f;
-    const float al = alpha * lp, v = q - al, gv = w.gamma * v, gvn = gv * nt;
+    const float al = alpha * lp, v = q - al, gv = g * v, gvn = gv * nt;
     return rs + gvn;
 }
+ADC_HD float sac_y(float r, int done, float q, float alpha, float lp, const SacLaw &w) { return sac_y_g(r, done, q, alpha, lp, w.gamma, w); }
 // the loss's derivative by u from gq = dQ / dt
 ADC_HD float sac_du(float t, float w, float gq, float alpha, float eps_sq)
 {

@@ -31,7 +31,7 @@
 
 namespace adc {
 
-ADC_HD float sac_y_norm(float r, int done, float q, float alpha, float lp, const SacLaw &w, float scale, float clip)
+ADC_HD float sac_y_norm_g(float r, int done, float q, float alpha, float lp, float g, const SacLaw &w, float scale, float clip)
 {
     const float rs0 = r * w.reward_scale;
     float rs = rs0 * scale;
@@ -41,8 +41,12 @@ ADC_HD float sac_y_norm(float r, int done, float q, float alpha, float lp, const
         rs = rs > clip ? clip : rs;
     }
     const float nt = done ? 0.0f : 1.0f;
-    const float al = alpha * lp, v = q - al, gv = w.gamma * v, gvn = gv * nt;
+    const float al = alpha * lp, v = q - al, gv = g * v, gvn = gv * nt;
     return rs + gvn;
+}
+ADC_HD float sac_y_norm(float r, int done, float q, float alpha, float lp, const SacLaw &w, float scale, float clip)
+{
+    return sac_y_norm_g(r, done, q, alpha, lp, w.gamma, w, scale, clip);
 }
 
 }  // namespace adc

@@ -1084,6 +1084,52 @@ ADC_EXPORT int adc_sac_y_norm_host(const adc_sac_config *sac, int32_t count, con
     return ADC_OK;
 }
 
+// ---- n-step returns on the host (adc_td3.h "n-step") ------------------------------------------------------------------------------
+ADC_EXPORT int adc_replay_nstep_check(int32_t n, const char **message)
+{
+    const char *msg = (n < 1 || n > adc::kNstepMax) ? "n: 1 to 16 days" : nullptr;
+    if (message) *message = msg;
+    return msg ? ADC_EINVAL : ADC_OK;
+}
+
+ADC_EXPORT int adc_replay_nstep_host(int32_t n, float gamma, int32_t T, int32_t N, int32_t t0, int32_t t1, const float *reward, const uint8_t *term,
+                                     const uint8_t *trunc, float *R, uint8_t *done, float *gn, int32_t *m)
+{
+    if (adc_replay_nstep_check(n, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (T < 1 || N < 1 || t0 < 0 || t1 <= t0 || t1 > T || !reward || !term || !trunc) return ADC_EINVAL;
+    for (int32_t t = t0; t < t1; ++t)
+        for (int32_t e = 0; e < N; ++e) {
+            const size_t row = (size_t)t * (size_t)N + (size_t)e, s = (size_t)(t - t0) * (size_t)N + (size_t)e;
+            const adc::Td3Window w = adc::td3_nstep_window(reward + row, term + row, trunc + row, (size_t)N, t1 - t, n, gamma);
+            if (R) R[s] = w.R;
+            if (done) done[s] = (uint8_t)w.done;
+            if (gn) gn[s] = w.g;
+            if (m) m[s] = w.m;
+        }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_td3_y_nstep_host(const adc_td3_config *td3, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, const float *gn_b,
+                                    float scale, float clip, float *y_b)
+{
+    if (adc_td3_config_check(td3, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (count < 1 || !r_b || !done_b || !q_b || !gn_b || !y_b || !(clip >= 0.0f)) return ADC_EINVAL;
+    const adc::Td3Law law = adc::td3_law_of(*td3);
+    for (int32_t b = 0; b < count; ++b) y_b[b] = adc::td3_y_norm_g(r_b[b], done_b[b], q_b[b], gn_b[b], law, scale, clip);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_sac_y_nstep_host(const adc_sac_config *sac, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, const float *lp_b,
+                                    const float *gn_b, float alpha, float scale, float clip, float *y_b)
+{
+    if (adc_sac_config_check(sac, nullptr) != ADC_OK) return ADC_EINVAL;
+    if (count < 1 || !r_b || !done_b || !q_b || !lp_b || !gn_b || !y_b || !(clip >= 0.0f)) return ADC_EINVAL;
+    // (sac_y_norm_g reads reward_scale of the law alone)
+    const adc::SacLaw law{sac->gamma, sac->tau, sac->reward_scale, sac->eps_sq, 0.0f, 0.0f};
+    for (int32_t b = 0; b < count; ++b) y_b[b] = adc::sac_y_norm_g(r_b[b], done_b[b], q_b[b], alpha, lp_b[b], gn_b[b], law, scale, clip);
+    return ADC_OK;
+}
+
 ADC_EXPORT int adc_pg_param_count_host(const adc_mlp_config *mlp, int32_t num_keywords, int64_t *count)
 {
     if (!count || adc_mlp_config_check(mlp, num_keywords, nullptr) != ADC_OK) return ADC_EINVAL;

@@ -2,7 +2,8 @@
 // smoothing noise, delayed actor and target updates) on top of the deterministic policy gradient (Lillicrap et al. 2016), over
 // a device-resident replay ring filled from the rollout record.  Shared by the device kernels (parts/kernel_td3.inc) and the
 // host twins adc_td3_batch_indices_host / adc_td3_target_host / adc_td3_critic_grad_host / adc_td3_actor_grad_host /
-// adc_td3_polyak_host (adc_shims.cpp); tests/td3_ref.py restates these comments in numpy, bit for bit.
+// adc_td3_polyak_host (adc_shims.cpp); tests/td3_ref.py restates these comments in numpy, bit for bit.  The n-step add-on's twins are
+// adc_replay_nstep_host / adc_td3_y_nstep_host / adc_sac_y_nstep_host, its restatement tests/nstep_ref.py.
 //
 // Every float32 value below is the result of ONE correctly rounded IEEE operation (-ffp-contract=off); "f64" marks what is
 // computed in float64.  sum8, the layers, tanh and mix64 are adc_mlp.h's; the hidden deltas, csum, the norm clip and the Adam /
@@ -33,6 +34,20 @@
 //              a' = mu'[a] + e; with action_hi > action_lo: a' = a' < lo ? lo : a'; a' = a' > hi ? hi : a'.
 //              q = min(Q1'([x' | an']), Q2'([x' | an'])), min(x, y) = x < y ? x : y.  nt = done ? 0 : 1.
 //              y = (r * reward_scale) + ((gamma * q) * nt).
+//   n-step     the add-on adc_engine_replay_nstep_init(n), n in 1..16; off: everything above.  The store covers the record's days
+//              [t0, t1).  For the sample of recorded day t and env e, with the learner's own gamma:
+//                  R = r[t]; g = gamma; m = 1; d = done[t]
+//                  while m < n and not d and t + m < t1:
+//                      p = g * r[t + m]; R = R + p; g = g * gamma; d = done[t + m]; m = m + 1
+//              (a product, a sum, a product per summed day).  The slot's x and a are the transition's; r holds R; done holds d, the
+//              last summed day's flag; a per-slot float gn holds g, the bootstrap discount: gamma multiplied m - 1 times by gamma
+//              (no powf).  x' = the record's obs row (t + m, e) when t + m < t1, else the input row an act would read now (the
+//              transition's rule, history and normalisation included), also when d is set; nt = 0 makes it inert.  A window is cut at
+//              the first day that ends an episode and at the end of the stored fragment: the last n - 1 days of every store carry
+//              m < n, and their gn says so.  The target reads gn[slot] where it reads gamma: y = (R * reward_scale) + ((gn * q) *
+//              nt); the normalisers' multiplier and clip apply to R as they did to r.  With n = 1: R = r, gn = gamma, the ring and
+//              y are the add-on-off bits.  Slots, written, size, the skipped samples, the batch, the noise and the priorities do
+//              not move.  A slot keeps the R and gn it was stored with when its learner's gamma changes later.
 //   critic     per critic i: d = Qi([x | an]) - y; loss piece 0.5 * (d * d); output delta d; hidden deltas as in adc_pg.h.
 //              g[p] = float32(csum(B, b -> f64(x_l,b[j]) * f64(delta_l,b[h])) / f64(B)) over the batch elements in order, for all
 //              of psi.  max_grad_norm > 0: the global norm clip over psi (adc_pg.h).  One pg_apply step with critic_lr,
@@ -142,17 +157,19 @@ ADC_HD float td3_target_action(float mu, float n, const Td3Law &w)
     return a;
 }
 ADC_HD float td3_min(float x, float y) { return x < y ? x : y; }
-ADC_HD float td3_y(float r, int done, float q, const Td3Law &w)
+// g: the bootstrap discount, the law's gamma or the slot's gn (n-step)
+ADC_HD float td3_y_g(float r, int done, float q, float g, const Td3Law &w)
 {
     const float rs = r * w.reward_scale;
     const float nt = done ? 0.0f : 1.0f;
-    const float gq = w.gamma * q, gqn = gq * nt;
+    const float gq = g * q, gqn = gq * nt;
     return rs + gqn;
 }
+ADC_HD float td3_y(float r, int done, float q, const Td3Law &w) { return td3_y_g(r, done, q, w.gamma, w); }
 // td3_y under a running reward normaliser (adc_td3_norm.h): rs = r * reward_scale; rs = rs * scale (the learner's normaliser's
 // current multiplier); with clip > 0: rs = rs < -clip ? -clip : rs; rs = rs > clip ? clip : rs (a NaN passes).  The rest is
 // td3_y, operation for operation; with scale = 1 and clip = 0 these are td3_y's bits (the product with 1.0f is exact).
-ADC_HD float td3_y_norm(float r, int done, float q, const Td3Law &w, float scale, float clip)
+ADC_HD float td3_y_norm_g(float r, int done, float q, float g, const Td3Law &w, float scale, float clip)
 {
     const float rs0 = r * w.reward_scale;
     float rs = rs0 * scale;
@@ -162,8 +179,34 @@ ADC_HD float td3_y_norm(float r, int done, float q, const Td3Law &w, float scale
         rs = rs > clip ? clip : rs;
     }
     const float nt = done ? 0.0f : 1.0f;
-    const float gq = w.gamma * q, gqn = gq * nt;
+    const float gq = g * q, gqn = gq * nt;
     return rs + gqn;
+}
+ADC_HD float td3_y_norm(float r, int done, float q, const Td3Law &w, float scale, float clip)
+{
+    return td3_y_norm_g(r, done, q, w.gamma, w, scale, clip);
+}
+// the n-step window of the sample whose first day's words are at reward / term / trunc (one env: a day is `stride` words further),
+// `left` = t1 - t recorded days from there, left >= 1: R, the bootstrap discount g, the last summed day's flag, m
+constexpr int kNstepMax = 16;
+struct Td3Window {
+    float R, g;
+    int done, m;
+};
+ADC_HD Td3Window td3_nstep_window(const float *reward, const uint8_t *term, const uint8_t *trunc, size_t stride, int left, int n, float gamma)
+{
+    Td3Window w;
+    w.R = reward[0]; w.g = gamma; w.m = 1;
+    w.done = (term[0] | trunc[0]) ? 1 : 0;
+    while (w.m < n && !w.done && w.m < left) {
+        const size_t i = (size_t)w.m * stride;
+        const float p = w.g * reward[i];
+        w.R = w.R + p;
+        w.g = w.g * gamma;
+        w.done = (term[i] | trunc[i]) ? 1 : 0;
+        w.m = w.m + 1;
+    }
+    return w;
 }
 ADC_HD float td3_critic_delta(float q, float y, float &loss)
 {

@@ -252,6 +252,10 @@ struct adc_engine {
     bool per_live = false;
     adc_replay_prio_config per_cfg{};
     PerView per{};                              // all members' trees, tops and batch buffers
+    // n-step returns over the live TD3 / SAC trainer's ring(s) (adc_engine_replay_nstep_init; parts/nstep_api.inc; adc_td3.h "n-step").
+    // nstep_n: the window, 0 while the add-on is off; nstep_gn: the members' gn arrays [M][C], among td3_allocs (the rings' gn point here)
+    int nstep_n = 0;
+    float *nstep_gn = nullptr;
     // how often the envs were stepped or reset, by anyone; ro_moves: that count when the record's last day was recorded
     uint64_t env_moves = 0, ro_moves = 0;
     bool ideal_full_scan = false;       // ADCRAFT_IDEAL_FULL_SCAN=1: evaluate the whole bid grid every step (the checker of the contender lists)
@@ -2981,6 +2985,7 @@ void td3_drop(adc_engine *e)
     norm_set_drop(e, e->tn);            // (the record is back to network inputs)
     norm_set_drop(e, e->sn);            // (the SAC learners' normalisers end where their trainer ends)
     e->per_live = false; e->per = PerView{};    // (prioritised replay's arrays are among td3_allocs)
+    e->nstep_n = 0; e->nstep_gn = nullptr;      // (so are n-step returns'; a new trainer's rings start without gn)
     pbt_forget(e, ADC_PBT_TD3);
     pbt_forget(e, ADC_PBT_SAC);         // (a SAC population's scheduler: its arrays are among td3_allocs too)
     mlp_free(e, e->td3_allocs);

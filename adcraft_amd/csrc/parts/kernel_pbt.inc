@@ -92,7 +92,7 @@ __device__ __forceinline__ void pbt_copy_bytes(uint8_t *d, const uint8_t *s, siz
     for (size_t i = head + 16u * body + lane; i < bytes; i += lanes) d[i] = s[i];
 }
 
-// pair blockIdx.y, ring array blockIdx.z (x, a, r, x2, done) of C slots: src's into dst's.  Rows are D = 5K + 2 and A = K + 1
+// pair blockIdx.y, ring array blockIdx.z (x, a, r, x2, done; 5: gn, launched under n-step returns alone) of C slots: src's into dst's.  Rows are D = 5K + 2 and A = K + 1
 // floats and done is bytes, a member's arrays start C rows after the previous member's: no alignment beyond the element's holds
 __global__ __launch_bounds__(kPbtBlock) void k_pbt_exploit_ring(const Td3Member *__restrict__ mem, const PbtPair *__restrict__ pairs, size_t C, int D, int A)
 {
@@ -107,6 +107,7 @@ __global__ __launch_bounds__(kPbtBlock) void k_pbt_exploit_ring(const Td3Member 
     case 1: dp = reinterpret_cast<uint8_t *>(d.a); sp = reinterpret_cast<const uint8_t *>(s.a); bytes = C * (size_t)A * 4u; break;
     case 2: dp = reinterpret_cast<uint8_t *>(d.r); sp = reinterpret_cast<const uint8_t *>(s.r); bytes = C * 4u; break;
     case 3: dp = reinterpret_cast<uint8_t *>(d.x2); sp = reinterpret_cast<const uint8_t *>(s.x2); bytes = C * (size_t)D * 4u; break;
+    case 5: dp = reinterpret_cast<uint8_t *>(d.gn); sp = reinterpret_cast<const uint8_t *>(s.gn); bytes = C * 4u; break;
     default: dp = d.done; sp = s.done; bytes = C; break;
     }
     pbt_copy_bytes(dp, sp, bytes, lane, lanes);

@@ -114,6 +114,8 @@ __device__ __forceinline__ void sac_target_body(const SacView &p, const MlpNet &
     const size_t nv = NORM ? (size_t)member * p.n_stride : 0;   // (the member's row of the normaliser's vectors; 0 whenever they are shared)
     // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
     const float r_mult = NORM && p.r_scale ? p.r_scale[(size_t)member * (size_t)p.r_stride] : 1.0f;
+    // (n-step returns: the slot's bootstrap discount in gamma's place, read here for the same reason)
+    const float g = ring.gn ? ring.gn[slot] : law.gamma;
     for (int j = tid; j < D; j += kPgBlock) {
         float xj = ring.x2[slot * (size_t)D + j];
         if (NORM && p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
@@ -131,8 +133,8 @@ __device__ __forceinline__ void sac_target_body(const SacView &p, const MlpNet &
     }
     if (tid == 0) {
         const float q = adc::td3_min(s.words[0], s.words[1]);
-        p.ybuf[at] = NORM && p.r_scale ? adc::sac_y_norm(ring.r[slot], ring.done[slot], q, alpha, s.words[2], law, r_mult, p.r_clip)
-                                       : adc::sac_y(ring.r[slot], ring.done[slot], q, alpha, s.words[2], law);
+        p.ybuf[at] = NORM && p.r_scale ? adc::sac_y_norm_g(ring.r[slot], ring.done[slot], q, alpha, s.words[2], g, law, r_mult, p.r_clip)
+                                       : adc::sac_y_g(ring.r[slot], ring.done[slot], q, alpha, s.words[2], g, law);
     }
 }
 template <bool NORM>

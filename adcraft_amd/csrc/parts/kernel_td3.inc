@@ -17,6 +17,7 @@
 struct Td3Ring {
     float *x, *a, *r, *x2;                  // [C][D], [C][A], [C], [C][D]
     uint8_t *done;                          // [C]
+    float *gn;                              // [C] the slot's bootstrap discount (adc_engine_replay_nstep_init; adc_td3.h "n-step"), or null
 };
 
 struct Td3View {
@@ -114,14 +115,16 @@ __device__ __forceinline__ void td3_input_back(const float *__restrict__ W, int 
 // sample s = (t - t0) * n + local env of the recorded days [t0, t1) of the member's envs [member n, (member + 1) n) into slot
 // (written + s) mod C of its ring
 // kHist: the policy has an observation history (adc_mlp.h): the last day's x' is the stacked row, peeked (nothing is written)
-template <bool kHist = false>
+// kNstep: n-step returns (adc_td3.h "n-step"): r, done and gn are the window's of `nstep` days under `gamma`, x' the row m days on.
+// Every lane walks the window (at most nstep dependent loads at workgroup-uniform addresses); without it the code is what it was
+template <bool kHist = false, bool kNstep = false>
 __device__ __forceinline__ void td3_store_body(const View &v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
                                                const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
                                                const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
                                                const uint8_t *__restrict__ ro_trunc, int t0, int t1, int n, int member, const Td3Ring ring,
                                                unsigned long long written, unsigned long long C, const float *__restrict__ hist = nullptr,
                                                const int32_t *__restrict__ h_last = nullptr, const int32_t *__restrict__ h_from = nullptr,
-                                               int frames = 1)
+                                               int frames = 1, int nstep = 1, float gamma = 0.0f)
 {
     const int tid = threadIdx.x, N = v.N;
     const unsigned long long s = blockIdx.x, count = (unsigned long long)(t1 - t0) * (unsigned long long)n;
@@ -130,12 +133,21 @@ __device__ __forceinline__ void td3_store_body(const View &v, const float *__res
     const size_t slot = (size_t)((written + s) % C), row = (size_t)t * (size_t)N + (size_t)env;
     for (int j = tid; j < D; j += kPgBlock) ring.x[slot * (size_t)D + j] = ro_obs[row * (size_t)D + j];
     for (int a = tid; a < A; a += kPgBlock) ring.a[slot * (size_t)A + a] = ro_action[row * (size_t)A + a];
-    if (tid == 0) {
+    int m = 1;
+    if constexpr (kNstep) {
+        const adc::Td3Window w = adc::td3_nstep_window(ro_reward + row, ro_term + row, ro_trunc + row, (size_t)N, t1 - t, nstep, gamma);
+        m = w.m;
+        if (tid == 0) {
+            ring.r[slot] = w.R;
+            ring.done[slot] = (uint8_t)w.done;
+            ring.gn[slot] = w.g;
+        }
+    } else if (tid == 0) {
         ring.r[slot] = ro_reward[row];
         ring.done[slot] = (uint8_t)((ro_term[row] | ro_trunc[row]) ? 1 : 0);
     }
-    if (t + 1 < t1) {
-        const size_t next = row + (size_t)N;
+    if (t + m < t1) {
+        const size_t next = row + (size_t)m * (size_t)N;
         for (int j = tid; j < D; j += kPgBlock) ring.x2[slot * (size_t)D + j] = ro_obs[next * (size_t)D + j];
     } else {
         // the input row an act would read now (k_mlp_policy's prologue)
@@ -172,6 +184,28 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_store_hist(View v, const float
                          h_from, frames);
 }
 
+// ... with n-step returns (adc_engine_replay_nstep_init): the learner's gamma comes with the launch
+__global__ __launch_bounds__(kPgBlock) void k_td3_store_nstep(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
+                                                              const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                              const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                              const uint8_t *__restrict__ ro_trunc, int t0, int t1, Td3Ring ring,
+                                                              unsigned long long written, unsigned long long C, int nstep, float gamma)
+{
+    td3_store_body<false, true>(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, v.N, 0, ring, written, C, nullptr,
+                                nullptr, nullptr, 1, nstep, gamma);
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_store_hist_nstep(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D,
+                                                                   int A, const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                                   const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                                   const uint8_t *__restrict__ ro_trunc, int t0, int t1, Td3Ring ring,
+                                                                   unsigned long long written, unsigned long long C,
+                                                                   const float *__restrict__ hist, const int32_t *__restrict__ h_last,
+                                                                   const int32_t *__restrict__ h_from, int frames, int nstep, float gamma)
+{
+    td3_store_body<true, true>(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, v.N, 0, ring, written, C, hist, h_last,
+                               h_from, frames, nstep, gamma);
+}
+
 __global__ void k_td3_indices(uint64_t key, uint32_t update, uint32_t size, int B, int32_t *__restrict__ out)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -198,6 +232,8 @@ __device__ __forceinline__ void td3_target_body(const Td3View &p, const MlpNet &
     const size_t nv = (size_t)member * p.n_stride;              // (the member's row of the normaliser's vectors; 0 whenever they are shared)
     // (the multiplier is read here, ahead of the networks' dependent rounds, not behind them where y is formed)
     const float r_mult = p.r_scale ? p.r_scale[(size_t)member * (size_t)p.r_stride] : 1.0f;
+    // (n-step returns: the slot's bootstrap discount in gamma's place, read here for the same reason)
+    const float g = ring.gn ? ring.gn[slot] : law.gamma;
     for (int j = tid; j < D; j += kPgBlock) {
         float xj = ring.x2[slot * (size_t)D + j];
         if (p.n_shift) xj = adc::mlp_normalize(xj, p.n_shift[nv + j], p.n_scale[nv + j]);
@@ -219,8 +255,8 @@ __device__ __forceinline__ void td3_target_body(const Td3View &p, const MlpNet &
     }
     if (tid == 0) {
         const float q = adc::td3_min(words[0], words[1]);
-        p.ybuf[at] = p.r_scale ? adc::td3_y_norm(ring.r[slot], ring.done[slot], q, law, r_mult, p.r_clip)
-                               : adc::td3_y(ring.r[slot], ring.done[slot], q, law);
+        p.ybuf[at] = p.r_scale ? adc::td3_y_norm_g(ring.r[slot], ring.done[slot], q, g, law, r_mult, p.r_clip)
+                               : adc::td3_y_g(ring.r[slot], ring.done[slot], q, g, law);
     }
 }
 __global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)

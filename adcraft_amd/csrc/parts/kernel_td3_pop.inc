@@ -47,6 +47,31 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_store_hist(View v, const f
                          mem[blockIdx.y].ring, written, C, hist, h_last, h_from, frames);
 }
 
+// ... with n-step returns (adc_engine_replay_nstep_init): every member's window under its own law.gamma (a SAC member's Td3Member
+// carries its gamma too)
+__global__ __launch_bounds__(kPgBlock) void k_td3_pop_store_nstep(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D, int A,
+                                                                  const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                                  const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                                  const uint8_t *__restrict__ ro_trunc, int t0, int t1, int envs_per_member,
+                                                                  const Td3Member *__restrict__ mem, unsigned long long written,
+                                                                  unsigned long long C, int nstep)
+{
+    td3_store_body<false, true>(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, envs_per_member, blockIdx.y,
+                                mem[blockIdx.y].ring, written, C, nullptr, nullptr, nullptr, 1, nstep, mem[blockIdx.y].law.gamma);
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_pop_store_hist_nstep(View v, const float *__restrict__ shift, const float *__restrict__ scale, int D,
+                                                                       int A, const float *__restrict__ ro_obs, const float *__restrict__ ro_action,
+                                                                       const float *__restrict__ ro_reward, const uint8_t *__restrict__ ro_term,
+                                                                       const uint8_t *__restrict__ ro_trunc, int t0, int t1, int envs_per_member,
+                                                                       const Td3Member *__restrict__ mem, unsigned long long written,
+                                                                       unsigned long long C, const float *__restrict__ hist,
+                                                                       const int32_t *__restrict__ h_last, const int32_t *__restrict__ h_from,
+                                                                       int frames, int nstep)
+{
+    td3_store_body<true, true>(v, shift, scale, D, A, ro_obs, ro_action, ro_reward, ro_term, ro_trunc, t0, t1, envs_per_member, blockIdx.y,
+                               mem[blockIdx.y].ring, written, C, hist, h_last, h_from, frames, nstep, mem[blockIdx.y].law.gamma);
+}
+
 __global__ __launch_bounds__(kPgBlock) void k_td3_pop_target(Td3View p, const Td3Member *__restrict__ mem)
 {
     const Td3Member &me = mem[blockIdx.y];

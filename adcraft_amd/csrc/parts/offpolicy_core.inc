@@ -141,6 +141,30 @@ int off_store_check(const adc_engine *e)
                                 "one the envs hold (adc_engine_rollout_reset, collect again)");
     return ADC_OK;
 }
+// a front end's store launch under n-step returns (adc_engine_replay_nstep_init; adc_td3.h "n-step"): `count` samples per member,
+// pop: over every member's ring under its own gamma; raw: the learners' observation normaliser is alive, the rows stay raw
+void off_store_nstep_launch(adc_engine *e, bool pop, bool raw, long long count)
+{
+    const float *shift = raw ? nullptr : e->mp.shift, *scale = raw ? nullptr : e->mp.scale;
+    const unsigned long long written = (unsigned long long)e->td3_written, C = (unsigned long long)e->td3_cfg.capacity;
+    const bool hist = e->mp.frames > 1;
+    if (pop && hist)
+        hipLaunchKernelGGL(k_td3_pop_store_hist_nstep, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, shift, scale, e->mp.D,
+                           e->mp.A, e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem, written, C,
+                           e->mp.hist, e->mp.last, e->mp.from, e->mp.frames, e->nstep_n);
+    else if (pop)
+        hipLaunchKernelGGL(k_td3_pop_store_nstep, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, shift, scale, e->mp.D, e->mp.A,
+                           e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem, written, C,
+                           e->nstep_n);
+    else if (hist)
+        hipLaunchKernelGGL(k_td3_store_hist_nstep, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, shift, scale, e->mp.D, e->mp.A, e->ro_obs,
+                           e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, written, C, e->mp.hist, e->mp.last,
+                           e->mp.from, e->mp.frames, e->nstep_n, e->td3_cfg.gamma);
+    else
+        hipLaunchKernelGGL(k_td3_store_nstep, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, shift, scale, e->mp.D, e->mp.A, e->ro_obs,
+                           e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, written, C, e->nstep_n,
+                           e->td3_cfg.gamma);     // (a solo SAC learner's gamma is td3_cfg's too: sac_as_td3)
+}
 // after the front end's store launch of `count` transitions (per member): the ring's counters move
 int off_store_done(adc_engine *e, long long count, int64_t *stored)
 {
@@ -271,6 +295,7 @@ int off_pop_copy(adc_engine *e, int src, int dst, int with_ring)
         HIP_TRY(hipMemcpyAsync(d.r, s.r, C * 4, hipMemcpyDeviceToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(d.done, s.done, C, hipMemcpyDeviceToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(d.x2, s.x2, C * D * 4, hipMemcpyDeviceToDevice, e->stream));
+        if (s.gn) HIP_TRY(hipMemcpyAsync(d.gn, s.gn, C * 4, hipMemcpyDeviceToDevice, e->stream));      // (n-step returns: the slots' discounts)
         if (e->per_live)
             if (int rc = per_copy_run(e, src, dst)) return rc;      // (the leaves, nodes and top travel with the ring)
     }
@@ -366,7 +391,7 @@ void off_member_place(Td3Member &me, size_t m, const OffBlock &k, int count, flo
         }
     }
     const size_t D = (size_t)sh.D, A = (size_t)sh.A;
-    me.ring = Td3Ring{o.ring.x + m * C * D, o.ring.a + m * C * A, o.ring.r + m * C, o.ring.x2 + m * C * D, o.ring.done + m * C};
+    me.ring = Td3Ring{o.ring.x + m * C * D, o.ring.a + m * C * A, o.ring.r + m * C, o.ring.x2 + m * C * D, o.ring.done + m * C, nullptr};
 }
 
 // ---- an update's launches ------------------------------------------------------------------------------------------------------

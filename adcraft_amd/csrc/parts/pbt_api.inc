@@ -57,12 +57,12 @@ void pbt_hp_put(adc_engine *e, int m, const float hp[adc::kPbtMaxHp])
     }
 }
 // the five ring arrays of every pair's donor into its destination's, in one launch (TD3 and SAC populations: the members' rings are
-// tp_dmem's either way)
+// tp_dmem's either way); under n-step returns gn travels as a sixth
 void pbt_ring_launch(adc_engine *e, int npairs)
 {
     const size_t C = (size_t)e->td3_cfg.capacity, most = C * (size_t)e->td3_shape.D * 4u;
     const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((most / 16u + kPbtBlock - 1) / kPbtBlock, 1), 256);
-    hipLaunchKernelGGL(k_pbt_exploit_ring, dim3(blocks, (unsigned)npairs, 5u), dim3(kPbtBlock), 0, e->stream, e->tp_dmem, e->pbt_dpairs, C, e->td3_shape.D,
+    hipLaunchKernelGGL(k_pbt_exploit_ring, dim3(blocks, (unsigned)npairs, e->nstep_n ? 6u : 5u), dim3(kPbtBlock), 0, e->stream, e->tp_dmem, e->pbt_dpairs, C, e->td3_shape.D,
                        e->td3_shape.A);
 }
 // the first `npairs` entries of pbt_pairs: up in one copy, then every pair's copy in the same launches

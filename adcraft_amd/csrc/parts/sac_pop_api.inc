@@ -203,7 +203,8 @@ ADC_EXPORT int adc_engine_sac_pop_store(adc_engine *e, int64_t *stored_per_membe
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;      // (a member's envs, not the engine's)
     // (raw rows under a running observation normaliser - SAC's set, e->sn: the last day's x' is the raw row an act would read now)
     // (with an observation history the last day's x' is the stacked row, peeked)
-    if (e->mp.frames > 1)
+    if (e->nstep_n) off_store_nstep_launch(e, true, e->sn.obs.count != 0, count);       // (n-step returns: the window's R, done and gn)
+    else if (e->mp.frames > 1)
         hipLaunchKernelGGL(k_td3_pop_store_hist, dim3((unsigned)count, (unsigned)e->lrn_M), dim3(kPgBlock), 0, e->stream, e->v, e->sn.obs.count ? nullptr : e->mp.shift,
                            e->sn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A,
                            e->ro_obs, e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->lrn_n, e->tp_dmem,

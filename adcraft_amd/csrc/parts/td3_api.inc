@@ -190,7 +190,8 @@ ADC_EXPORT int adc_engine_td3_store(adc_engine *e, int64_t *stored)
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;        // (every env is the one learner's)
     // (raw rows under a running observation normaliser - TD3's set, e->tn: the last day's x' is the raw row an act would read now)
     // (with an observation history the last day's x' is the stacked row, peeked)
-    if (e->mp.frames > 1)
+    if (e->nstep_n) off_store_nstep_launch(e, false, e->tn.obs.count != 0, count);       // (n-step returns: the window's R, done and gn)
+    else if (e->mp.frames > 1)
         hipLaunchKernelGGL(k_td3_store_hist, dim3((unsigned)count), dim3(kPgBlock), 0, e->stream, e->v, e->tn.obs.count ? nullptr : e->mp.shift,
                            e->tn.obs.count ? nullptr : e->mp.scale, e->mp.D, e->mp.A, e->ro_obs,
                            e->ro_action, e->ro_reward, e->ro_term, e->ro_trunc, e->td3_stored_t, e->ro_t, e->td3_ring, (unsigned long long)e->td3_written,

@@ -1909,6 +1909,50 @@ class StepEngine:
         if np.asarray(state["leaf"]).size:
             self.replay_prio_load(state["leaf"], state["top"], member)
 
+    # ---- n-step returns for the TD3 / SAC learners (parts/nstep_api.inc; the law is csrc/adc_td3.h "n-step") ------------------------
+    def replay_nstep_init(self, n):
+        """n-step returns for the live TD3 / SAC trainer, solo or population (td3_init, sac_init, td3_pop_init or sac_pop_init first):
+        from the next store on a slot holds the discounted sum of up to n days' rewards, the last summed day's done flag, the
+        observation after them and its own bootstrap discount gn, which the targets read in gamma's place.  Windows are cut at an
+        episode's end and at the end of the stored days.  n in 1..16, shared by a population's members; a ring that already holds
+        transitions is fine (its slots get gn = gamma); a second call changes the window.  It ends with its trainer"""
+        check(self._lib.adc_engine_replay_nstep_init(self._h, int(n)))
+
+    def replay_nstep_info(self):
+        """the window n, 0 while the add-on is off"""
+        n = C.c_int32(0)
+        check(self._lib.adc_engine_replay_nstep_info(self._h, C.byref(n)))
+        return int(n.value)
+
+    def replay_nstep_fetch(self, member=0, slot=0, count=None):
+        """the bootstrap discounts gn of the slots [slot, slot + count) (default: up to the ring's size): float32"""
+        if count is None:
+            if self.replay_nstep_info() == 0:           # (the engine's own words for what is missing)
+                check(self._lib.adc_engine_replay_nstep_fetch(self._h, int(member), 0, 1, None))
+            count = self._replay_prio_sizes()[0] - int(slot)
+        gn = np.zeros(max(int(count), 0), np.float32)
+        if gn.size or count != 0:
+            check(self._lib.adc_engine_replay_nstep_fetch(self._h, int(member), int(slot), int(count), gn.ctypes.data))
+        return gn
+
+    def replay_nstep_load(self, gn, member=0, slot=0):
+        """bootstrap discounts (finite, >= 0) for the slots from `slot` on, next to *_buffer_load, which moves R and done"""
+        gn = np.ascontiguousarray(gn, dtype=np.float32)
+        if gn.ndim != 1:
+            raise ValueError("replay_nstep_load: gn [count]")
+        check(self._lib.adc_engine_replay_nstep_load(self._h, int(member), int(slot), gn.size, gn.ctypes.data))
+
+    def replay_nstep_state(self, member=0, state=None):
+        """a member's n-step side of the ring.  get (no state): dict of n and gn [size] float32; set: such a dict, after the ring was
+        loaded - with the trainer's state and the ring the run continues bit for bit"""
+        if state is None:
+            size = self._replay_prio_sizes()[0]
+            return dict(n=self.replay_nstep_info(), gn=self.replay_nstep_fetch(member, 0, size) if size else np.zeros(0, np.float32))
+        if int(state["n"]) != self.replay_nstep_info():
+            self.replay_nstep_init(int(state["n"]))
+        if np.asarray(state["gn"]).size:
+            self.replay_nstep_load(state["gn"], member)
+
     def rollout_enable(self, horizon, obs=False):
         check(self._lib.adc_engine_rollout_enable(self._h, int(horizon), 1 if obs else 0))
         self._td3_norm = self._sac_norm = None                   # (the TD3 normalisers, if any, ended with their trainer)

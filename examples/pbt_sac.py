@@ -58,6 +58,8 @@ def main():
                     help="per member, the reward divided by the discounted return's running standard deviation (the entropy term is not scaled); what the normalisers gain here has not been measured")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
+    ap.add_argument("--n-step", type=int, default=1, metavar="N",
+                    help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
     args = ap.parse_args()
     K, days, n, M, budget = args.num_keywords, args.days, args.envs_per_member, args.members, 100000.0
     N = M * n
@@ -69,7 +71,7 @@ def main():
     hidden = tuple(int(w) for w in args.critic_hidden.split(","))
     configs = [sac_trainer.sac(K, critic_hidden=hidden, learning_starts=days * n, updates_per_iteration=args.updates, batch_size=args.batch_size,
                                capacity=args.capacity, reward_scale=args.reward_scale, actor_lr=float(lrs[m]), init_alpha=float(alphas[m]),
-                               alpha_lr=0.0 if m % 2 else 3e-4, critic_seed=m) for m in range(M)]
+                               alpha_lr=0.0 if m % 2 else 3e-4, critic_seed=m, n_step=args.n_step) for m in range(M)]
     lo = np.concatenate([[1.0], np.full(K, args.bid_lo)]).astype(np.float32)          # (the budget is overridden during training and evaluation)
     hi = np.concatenate([[budget], np.full(K, args.bid_hi)]).astype(np.float32)
     policies = [two_headed_policy(K, days, args.bid_lo, args.bid_hi, seed=m) for m in range(M)]

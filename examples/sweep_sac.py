@@ -58,6 +58,8 @@ def main():
                     help="per member, the reward divided by the discounted return's running standard deviation (the entropy term is not scaled); what the normalisers gain here has not been measured")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
+    ap.add_argument("--n-step", type=int, default=1, metavar="N",
+                    help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
     args = ap.parse_args()
     K, days, n = args.num_keywords, args.days, args.envs_per_member
     cells = [(float(a), float(t), int(s)) for a, t, s in itertools.product(args.actor_lrs.split(","), args.alpha_lrs.split(","), args.seeds.split(","))]
@@ -67,7 +69,7 @@ def main():
     zm_ret, zm_ncp = evaluate("zero_margin", None, held_out, days, BUDGET)
     base = sac_trainer.sac(K, critic_hidden=tuple(int(w) for w in args.critic_hidden.split(",")), learning_starts=args.warmup_iterations * days * n,
                            updates_per_iteration=args.updates, batch_size=args.batch_size, reward_scale=args.reward_scale, capacity=100000)
-    configs = [dict(base, actor_lr=alr, alpha_lr=tlr, seed=seed, critic_seed=seed) for alr, tlr, seed in cells]
+    configs = [dict(base, actor_lr=alr, alpha_lr=tlr, seed=seed, critic_seed=seed, n_step=args.n_step) for alr, tlr, seed in cells]
     lo = np.concatenate([[1.0], np.full(K, args.bid_lo)]).astype(np.float32)          # (the budget is overridden during training and evaluation)
     hi = np.concatenate([[BUDGET], np.full(K, args.bid_hi)]).astype(np.float32)
     policy = two_headed_policy(K, days, args.bid_lo, args.bid_hi)

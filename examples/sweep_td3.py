@@ -63,6 +63,8 @@ def main():
     ap.add_argument("--solo", action="store_true", help="afterwards, the same grid as solo trainers one after another (wall time)")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
+    ap.add_argument("--n-step", type=int, default=1, metavar="N",
+                    help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
     args = ap.parse_args()
     K, days, n = args.num_keywords, args.days, args.envs_per_member
     cells = list(itertools.product(*([float(x) for x in s.split(",")] for s in (args.actor_lrs, args.critic_lrs, args.sigmas))))
@@ -70,7 +72,7 @@ def main():
     member_planes = synthetic.implicit_keyword_planes(n, K, seed=1, mean_volume=args.mean_volume)       # (every member learns on the same keyword sets)
     norm = (np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32))
     policy = default_policy(K, hidden=HIDDEN, days=days, seed=0)
-    configs = [dict(base_config(args), actor_lr=alr, critic_lr=clr, action_norm=norm) for alr, clr, _ in cells]
+    configs = [dict(base_config(args), actor_lr=alr, critic_lr=clr, action_norm=norm, n_step=args.n_step) for alr, clr, _ in cells]
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(np.concatenate([member_planes] * M, axis=1))
     eng.reset()

@@ -90,6 +90,8 @@ def main():
                     help="the reward divided by the discounted return's running standard deviation (the entropy term is not scaled); what the normalisers gain here has not been measured")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
+    ap.add_argument("--n-step", type=int, default=1, metavar="N",
+                    help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
@@ -107,7 +109,8 @@ def main():
     hi = np.concatenate([[budget], np.full(K, args.bid_hi)]).astype(np.float32)
     trainer = sac_trainer.SACTrainer(eng, two_headed_policy(K, days, args.bid_lo, args.bid_hi, frames=args.frames), lo, hi, horizon=days,
                                      normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
-                                     prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None, **config)
+                                     prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None,
+                                     n_step=args.n_step, **config)
     rng = np.random.default_rng(5)
 
     def report(it, stats):

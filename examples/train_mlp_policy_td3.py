@@ -64,6 +64,8 @@ def main():
     ap.add_argument("--normalize-rewards", action="store_true", help="the reward divided by the discounted return's running standard deviation")
     ap.add_argument("--prioritized-replay", action="store_true",
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
+    ap.add_argument("--n-step", type=int, default=1, metavar="N",
+                    help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
@@ -79,7 +81,8 @@ def main():
                              action_norm=(np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32)))
     trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days, frames=args.frames), horizon=days, normalize_observations=args.normalize_observations,
                                      normalize_rewards=args.normalize_rewards,
-                                     prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None, **config)
+                                     prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None,
+                                     n_step=args.n_step, **config)
     rng = np.random.default_rng(5)
     ret, ncp = evaluate("mlp", trainer.policy(), held_out, days, budget)
     print(f"{0:>10} {'':>12} {'':>9} {ret:10.2f} {ncp:8.3f}")

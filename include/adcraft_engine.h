@@ -1416,6 +1416,39 @@ int adc_per_sample_host(const adc_replay_prio_config *cfg, int64_t capacity, int
 int adc_per_priority_host(const adc_replay_prio_config *cfg, int32_t count, const float *d1_b, const float *d2_b, float *pa_b);
 int adc_per_leaf_update_host(int64_t capacity, float *leaf_c, float *top, int32_t count, const int32_t *idx_b, const float *pa_b);
 
+/* ---- n-step returns for the TD3 / SAC learners (csrc/adc_td3.h "n-step"; parts/nstep_api.inc) --------------------------------- */
+/* An add-on to a live off-policy trainer, solo or population, in adc_engine_replay_prio_init's sense.  With a window of n days a
+ * store writes, for the sample of recorded day t, r = R = r[t] + gamma r[t+1] + ... over at most n days (each term one product, one
+ * sum), done = the last summed day's flag, x' = the observation m days on (the stored fragment's end: the row an act would read
+ * now) and a per-slot bootstrap discount gn = gamma^m formed by m - 1 products; the targets read gn[slot] where they read gamma.  A
+ * window is cut at the first day that ends an episode and at the end of the stored fragment [t0, t1): the last n - 1 days of every
+ * store carry a shorter window, and their gn says so (no fixed gamma^n).  The normalisers' reward multiplier and clip apply to R.
+ * Slot addressing, the counters, the batch, the noise and the priorities do not move; with n = 1 the ring and the targets are the
+ * add-on-off bits.  Without adc_engine_replay_nstep_init every call launches the kernels it launched and computes the bits it
+ * computed.
+ * _init needs a live TD3 or SAC trainer (ADC_ESTATE otherwise) and n in 1..16 (ADC_EINVAL otherwise); a ring that already holds
+ * transitions is fine: its slots get gn = their member's gamma, being one-step.  A second init changes the window from the next
+ * store on.  n is shared by a population's members, gamma is each member's own.  _info: n, 0 while the add-on is off.  _fetch: gn of
+ * the slots [slot, slot + count) inside [0, size); _load: those inside [0, capacity) from the host (finite and >= 0, ADC_EINVAL
+ * otherwise), next to *_buffer_fetch / _load, which move R and done.  `member` is -1 or 0 for a solo trainer.
+ * adc_engine_td3_pop_set_config, _sac_pop_set_config and a PBT round may change a member's gamma after it has stored: the stored
+ * slots keep the R and gn they were stored with.  Copies that carry the ring carry gn (adc_engine_td3_pop_copy / _sac_pop_copy
+ * with with_ring != 0, adc_engine_pbt_exploit with rings).  The add-on ends with its trainer. */
+int adc_replay_nstep_check(int32_t n, const char **message);
+int adc_engine_replay_nstep_init(adc_engine *e, int32_t n);
+int adc_engine_replay_nstep_info(adc_engine *e, int32_t *n);
+int adc_engine_replay_nstep_fetch(adc_engine *e, int32_t member, int64_t slot, int64_t count, float *gn);
+int adc_engine_replay_nstep_load(adc_engine *e, int32_t member, int64_t slot, int64_t count, const float *gn);
+/* the host twins: the same code as the device's.  nstep: the windows of every sample s = (t - t0) * N + env of the days [t0, t1) of
+ * a record reward / term / trunc [T][N]: R, done, gn and m [(t1 - t0) N] (any may be NULL).  y_nstep: adc_td3_y_norm_host /
+ * adc_sac_y_norm_host with a per-element bootstrap discount gn_b [count]; scale = 1 and clip = 0 give the plain target's bits. */
+int adc_replay_nstep_host(int32_t n, float gamma, int32_t T, int32_t N, int32_t t0, int32_t t1, const float *reward, const uint8_t *term,
+                          const uint8_t *trunc, float *R, uint8_t *done, float *gn, int32_t *m);
+int adc_td3_y_nstep_host(const adc_td3_config *td3, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, const float *gn_b,
+                         float scale, float clip, float *y_b);
+int adc_sac_y_nstep_host(const adc_sac_config *sac, int32_t count, const float *r_b, const uint8_t *done_b, const float *q_b, const float *lp_b,
+                         const float *gn_b, float alpha, float scale, float clip, float *y_b);
+
 /* ---- info["bidding_outcomes"] on demand (src/lib.rs:251-275, adcraft/gymnasium_kw_env.py:247-251) -------------------- */
 /* The fused step kernels keep per-keyword totals, not the per-click lists the reference formats ('costs', 'revenues',
  * 'revenues_per_cost').  Every variate is addressed by (env key; index, stage, keyword, tick), so those lists can be

@@ -545,6 +545,32 @@ ADC_HD float fast_rcp(float x)
 }
 ADC_HD float min_num(float a, float b) { return __builtin_fminf(a, b); }       // the non-NaN operand if one is NaN
 ADC_HD float max_num(float a, float b) { return __builtin_fmaxf(a, b); }
+// float -> uint32: truncation, saturating at both ends, NaN -> 0 (v_cvt_u32_f32 does exactly this; spelled out for the host)
+ADC_HD uint32_t to_word(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)x;
+#else
+    return !(x > 0.0f) ? 0u : x >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)x;
+#endif
+}
+// float -> int32 the same way (v_cvt_i32_f32)
+ADC_HD int32_t to_int(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int32_t)x;
+#else
+    return x != x ? 0 : x >= 2147483648.0f ? 0x7FFFFFFF : x < -2147483648.0f ? (int32_t)0x80000000u : (int32_t)x;
+#endif
+}
+ADC_HD uint32_t sat_add(uint32_t a, uint32_t b)                                                      // v_add_u32 ... clamp
+{
+#if defined(__clang__)
+    return __builtin_elementwise_add_sat(a, b);
+#else
+    return a + b < a ? 0xFFFFFFFFu : a + b;             // (a host build by gcc: oracle/build.py build_shims_host)
+#endif
+}
 
 // min{v in [0, 2^24] : signed_cents_from_v(v) >= target}.  A float estimate of the answer, a window around it that is
 // verified at both ends, bisection inside; if the estimate was off (degenerate parameters) the bisection runs over the
@@ -727,7 +753,9 @@ ADC_HD void lower_bound_pair(int32_t bid_c, float loc, float scale, const LogTab
 }
 
 // min{d in [0, range] : min(mulhi(d, m), 2^24 - 1) >= W} for W in [0, 2^24]; `range` (<= 2^32) if no offset reaches W.
-ADC_HD uint64_t offset_reaching(uint32_t W, uint32_t m, uint64_t range)
+// For 0 < W < 2^24 and m != 0 that is min(ceil(W 2^32 / m), range).  This form takes the quotient from one correctly rounded
+// float64 division and settles its last unit on 64-bit products: the reference of offset_reaching below and its fallback.
+ADC_HD uint64_t offset_reaching_f64(uint32_t W, uint32_t m, uint64_t range)
 {
     if (W == 0u) return 0ull;
     if (W > 0x00FFFFFFu || m == 0u) return range;
@@ -740,30 +768,119 @@ ADC_HD uint64_t offset_reaching(uint32_t W, uint32_t m, uint64_t range)
     return d < range ? d : range;
 }
 
+// The same value without float64.  Per multiplier: the float32 reciprocal and 2 m, 3 m.  Per offset: a float32 quotient d0, the
+// exact residual W 2^32 - d0 m, a float32 correction of it to d1 - then d1's own exact residual decides between d1 - 1, d1 and
+// d1 + 1 by integer compares: with u = W 2^32 + 2 m - d1 m, the offset d = d1 - 1 + k has (d - 1) m < W 2^32 <= d m exactly
+// when k m < u <= (k + 1) m.  Such a d IS ceil(W 2^32 / m), so a trial that is `ok` holds the value of offset_reaching_f64
+// (before the cap at `range`) whatever the float estimates were (tests/test_offset_reaching_host.py); with m >= 2^24 it is
+// below 2^32 - 254.  A trial that is not ok (u outside (0, 3 m], or a multiplier below 2^24: only m = 0 occurs, at click rates
+// of 0 and 1) takes the float64 routine, with its wave.  W = 0 needs no case of its own (d0 = d1 = 0, u = 2 m, d = 0); W = 2^24,
+// which no offset reaches and ordinary keywords have, is a select.
+enum OffsetPath : int { kOffsetCandidate = 0, kOffsetF64 = 1 };
+
+struct OffsetDivisor { uint32_t m; float inv, inv4096; uint64_t m2, m3; };
+
+ADC_HD OffsetDivisor offset_divisor(uint32_t m)
+{
+    const float inv = fast_rcp((float)m);
+    return OffsetDivisor{m, inv, inv * 4096.0f, 2ull * m, 3ull * m};
+}
+
+// ok: d = min(the offset before its cap, 2^32 - 1): all ones where no offset reaches W
+struct OffsetTrial { uint32_t d; bool ok; };
+
+ADC_HD OffsetTrial offset_trial(uint32_t W, const OffsetDivisor &v)
+{
+    const uint32_t d0 = to_word((float)W * 4294967296.0f * v.inv);           // within about 2^10 of the quotient
+    const uint64_t need = (uint64_t)W << 32;
+    const int64_t r0 = (int64_t)(need - (uint64_t)d0 * v.m);                 // |r0| < 2^43: r0 / 2^12 is a 32-bit integer
+    const uint32_t d1 = d0 + (uint32_t)to_int(__builtin_ceilf((float)(int32_t)(r0 >> 12) * v.inv4096));
+    const uint64_t u = need + v.m2 - (uint64_t)d1 * v.m;                     // (W < 2^24: no wrap, d1 m < 2^64 and need + 2 m < 2^57)
+    const uint32_t d = d1 - 1u + (u > (uint64_t)v.m ? 1u : 0u) + (u > v.m2 ? 1u : 0u);
+    const bool none = W > 0x00FFFFFFu;
+    OffsetTrial t;
+    t.ok = none | (((u - 1ull) < v.m3) & (v.m >= 0x01000000u));
+    t.d = none ? 0xFFFFFFFFu : d;
+    return t;
+}
+
+// the trial's value, or the float64 routine's where the trial did not verify (in this lane or another of its wave)
+ADC_HD uint64_t offset_reaching_staged(uint32_t W, uint32_t m, uint64_t range, int &path)
+{
+    const OffsetTrial t = offset_trial(W, offset_divisor(m));
+    uint64_t d = (W > 0x00FFFFFFu || !((uint64_t)t.d < range)) ? range : (uint64_t)t.d;
+    path = kOffsetCandidate;
+    if (any_lane(!t.ok)) {
+        if (!t.ok) { d = offset_reaching_f64(W, m, range); path = kOffsetF64; }
+    }
+    return d;
+}
+
+ADC_HD uint64_t offset_reaching(uint32_t W, uint32_t m, uint64_t range)
+{
+    int path;
+    return offset_reaching_staged(W, m, range, path);
+}
+
 // the two word intervals of a keyword: an auction word w is a clicked win iff (w - c_lo) < c_w, an unclicked win iff
 // (w - n_lo) < n_w (unsigned 32-bit arithmetic; widths fit because the word 2^32 - 1 never wins)
 struct WinIntervals { uint32_t c_lo, c_w, n_lo, n_w; };
 
 // from the two bounds w_lo = lower_bound_v(1 - bid), w_hi = lower_bound_v(bid):  bid > |cents|  <=>  -(bid - 1) <= S <= bid - 1
-ADC_HD WinIntervals win_intervals_of_bounds(uint32_t w_lo, uint32_t w_hi, uint64_t t_click, const AuctionLaw &law)
+// With D = offset_reaching the clicked wins are the words [D(w_lo), min(D(w_hi), top)) and the unclicked ones
+// [T + D(w_lo), min(T + D(w_hi), top)), top = 2^32 - 1 (words at or above it never win).  F64 = true: exactly that, on the four
+// float64 quotients (for a kernel that has no registers for four trials side by side).  F64 = false: the same intervals with
+// every end capped at top first, which changes neither (an end at top or beyond leaves an empty interval either way) and keeps
+// the common path in 32 bits: min(D, top) = min(d, min(T, top)) and min(T + D, top) = the saturating sum of T and d for the
+// uncapped d of an ok trial (T < 2^32 there: m_noclick is not 0).  The four trials share one ballot for the float64 routine,
+// which is one copy in a loop (path = kOffsetF64 if this keyword took it).
+template <bool F64 = false>
+ADC_HD WinIntervals win_intervals_of_bounds(uint32_t w_lo, uint32_t w_hi, uint64_t t_click, const AuctionLaw &law, int *path = nullptr)
 {
     WinIntervals r{0u, 0u, 0u, 0u};
+    if (path) *path = F64 ? kOffsetF64 : kOffsetCandidate;
     if (!(w_lo < w_hi)) return r;
-    const uint64_t top = 0xFFFFFFFFull;                                  // words at or above it never win
-    uint64_t a = offset_reaching(w_lo, law.m_click, t_click), b = offset_reaching(w_hi, law.m_click, t_click);
-    b = b < top ? b : top;
-    if (a < b) { r.c_lo = (uint32_t)a; r.c_w = (uint32_t)(b - a); }
+    const uint64_t top = 0xFFFFFFFFull;
     const uint64_t range_n = 4294967296ull - t_click;
-    a = t_click + offset_reaching(w_lo, law.m_noclick, range_n);
-    b = t_click + offset_reaching(w_hi, law.m_noclick, range_n);
-    b = b < top ? b : top;
-    if (a < b) { r.n_lo = (uint32_t)a; r.n_w = (uint32_t)(b - a); }
+    if constexpr (F64) {
+        uint64_t a = offset_reaching_f64(w_lo, law.m_click, t_click), b = offset_reaching_f64(w_hi, law.m_click, t_click);
+        b = b < top ? b : top;
+        if (a < b) { r.c_lo = (uint32_t)a; r.c_w = (uint32_t)(b - a); }
+        a = t_click + offset_reaching_f64(w_lo, law.m_noclick, range_n);
+        b = t_click + offset_reaching_f64(w_hi, law.m_noclick, range_n);
+        b = b < top ? b : top;
+        if (a < b) { r.n_lo = (uint32_t)a; r.n_w = (uint32_t)(b - a); }
+    } else {
+        const OffsetDivisor vc = offset_divisor(law.m_click), vn = offset_divisor(law.m_noclick);
+        const OffsetTrial ta = offset_trial(w_lo, vc), tb = offset_trial(w_hi, vc), tan = offset_trial(w_lo, vn), tbn = offset_trial(w_hi, vn);
+        const uint32_t t32 = t_click < top ? (uint32_t)t_click : 0xFFFFFFFFu;
+        uint32_t a = ta.d < t32 ? ta.d : t32, b = tb.d < t32 ? tb.d : t32, an = sat_add(t32, tan.d), bn = sat_add(t32, tbn.d);
+        const bool all_ok = ta.ok & tb.ok & tan.ok & tbn.ok;
+        if (any_lane(!all_ok)) {
+#pragma unroll 1
+            for (int i = 0; i < 4; ++i) {
+                const bool click = i < 2, lower = (i & 1) == 0;
+                if (!(i == 0 ? ta.ok : i == 1 ? tb.ok : i == 2 ? tan.ok : tbn.ok)) {
+                    uint64_t d = offset_reaching_f64(lower ? w_lo : w_hi, click ? law.m_click : law.m_noclick, click ? t_click : range_n);
+                    d += click ? 0ull : t_click;
+                    const uint32_t d32 = d < top ? (uint32_t)d : 0xFFFFFFFFu;
+                    a = i == 0 ? d32 : a;
+                    b = i == 1 ? d32 : b;
+                    an = i == 2 ? d32 : an;
+                    bn = i == 3 ? d32 : bn;
+                }
+            }
+            if (path && !all_ok) *path = kOffsetF64;
+        }
+        if (a < b) { r.c_lo = a; r.c_w = b - a; }
+        if (an < bn) { r.n_lo = an; r.n_w = bn - an; }
+    }
     return r;
 }
 
 // SIDE_BY_SIDE = false: one bound after the other (the same values; for kernels that have no registers to spare for eight
-// chains at once and set up a keyword's law rarely)
-template <bool SIDE_BY_SIDE = true>
+// chains at once and set up a keyword's law rarely); OFFSETS_F64: win_intervals_of_bounds<true>, for the same kernels
+template <bool SIDE_BY_SIDE = true, bool OFFSETS_F64 = false>
 ADC_HD WinIntervals win_intervals(int32_t bid_c, float loc, float scale, uint64_t t_click, const AuctionLaw &law, const LogTableEntry *tab)
 {
     uint32_t w_lo, w_hi;
@@ -774,7 +891,7 @@ ADC_HD WinIntervals win_intervals(int32_t bid_c, float loc, float scale, uint64_
         w_lo = lower_bound_v(1 - bid_c, loc, scale, tab);
         w_hi = lower_bound_v(bid_c, loc, scale, tab);
     }
-    return win_intervals_of_bounds(w_lo, w_hi, t_click, law);
+    return win_intervals_of_bounds<OFFSETS_F64>(w_lo, w_hi, t_click, law);
 }
 
 // ---- conservative brackets of the two win intervals (keyword sets with few auctions per keyword) -------------------
@@ -804,16 +921,6 @@ ADC_HD uint32_t sat_sub(uint32_t a, uint32_t b)                                 
     return a > b ? a - b : 0u;          // (a host build by gcc: oracle/build.py build_shims_host)
 #endif
 }
-// float -> uint32: truncation, saturating at both ends, NaN -> 0 (v_cvt_u32_f32 does exactly this; spelled out for the host)
-ADC_HD uint32_t to_word(float x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)x;
-#else
-    return !(x > 0.0f) ? 0u : x >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)x;
-#endif
-}
-
 // v^ and its slack for one target; x_t = (target - 1/2) / 100 is passed in
 ADC_HD void lower_bound_estimate(float x_t, float loc, float inv_s, float &est, float &slack)
 {

@@ -254,6 +254,61 @@ ADC_EXPORT int adc_win_intervals_host(int64_t n, const int32_t *bid_c, const flo
     return ADC_OK;
 }
 
+// adc::offset_reaching for n triples (range <= 2^32 as uint64).  path_out (nullable): adc::OffsetPath, 0 = the verified float32
+// candidate, 1 = the float64 routine
+ADC_EXPORT int adc_offset_reaching_host(int64_t n, const uint32_t *W, const uint32_t *m, const uint64_t *range, uint64_t *d_out, uint8_t *path_out)
+{
+    if (n < 0 || (n > 0 && (!W || !m || !range || !d_out))) return ADC_EINVAL;
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            int path = 0;
+            d_out[i] = adc::offset_reaching_staged(W[i], m[i], range[i], path);
+            if (path_out) path_out[i] = (uint8_t)path;
+        }
+    });
+    return ADC_OK;
+}
+
+// adc::offset_reaching_f64, the routine every earlier result was computed with.  path_out (nullable): 0 = W == 0, 1 = no offset can
+// reach W (W > 2^24 - 1 or m == 0), 2 = the float64 quotient is at or beyond the range, 3 = the quotient settled on the products
+ADC_EXPORT int adc_offset_reaching_f64_host(int64_t n, const uint32_t *W, const uint32_t *m, const uint64_t *range, uint64_t *d_out, uint8_t *path_out)
+{
+    if (n < 0 || (n > 0 && (!W || !m || !range || !d_out))) return ADC_EINVAL;
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            d_out[i] = adc::offset_reaching_f64(W[i], m[i], range[i]);
+            if (path_out)
+                path_out[i] = W[i] == 0u ? 0 : (W[i] > 0x00FFFFFFu || m[i] == 0u) ? 1
+                              : !(((double)W[i] * 4294967296.0) / (double)m[i] < (double)range[i]) ? 2 : 3;
+        }
+    });
+    return ADC_OK;
+}
+
+// adc::win_intervals for n keywords with its offsets by the verified candidate (f64 == 0; path_out: 1 if one of the keyword's
+// four offsets took the float64 routine) or by the float64 routine alone (f64 != 0: the earlier form, the reference)
+ADC_EXPORT int adc_win_intervals_offsets_host(int64_t n, const int32_t *bid_c, const float *cost_loc, const float *cost_scale, const float *buyside_ctr,
+                                              int32_t f64, uint32_t *out4, uint8_t *path_out)
+{
+    if (n < 0 || (n > 0 && (!bid_c || !cost_loc || !cost_scale || !buyside_ctr || !out4))) return ADC_EINVAL;
+    const adc::LogTableEntry *table = host_log_table();
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const adc::AuctionLaw law = adc::make_auction_law(buyside_ctr[i]);
+            const uint64_t t_click = adc::bernoulli_threshold(buyside_ctr[i]);
+            uint32_t w_lo, w_hi;
+            int stage = 0, path = 0;
+            adc::lower_bound_pair(bid_c[i], cost_loc[i], cost_scale[i], table, w_lo, w_hi, stage);
+            const adc::WinIntervals r = f64 ? adc::win_intervals_of_bounds<true>(w_lo, w_hi, t_click, law, &path)
+                                            : adc::win_intervals_of_bounds<false>(w_lo, w_hi, t_click, law, &path);
+            uint32_t *o = out4 + 4 * i;
+            o[0] = r.c_lo; o[1] = r.c_w; o[2] = r.n_lo; o[3] = r.n_w;
+            if (path_out) path_out[i] = (uint8_t)path;
+        }
+    });
+    return ADC_OK;
+}
+
 // ---- what the dense fast pass hoists out of its stages (adc_law.h), next to the routines it replaces there: for
 // tests/test_law_hoists_host.py ----------------------------------------------------------------------------------------------
 // n calls: plain4 = adc::draw, folded4 = adc::draw_folded, kw4 = adc::draw_kw_folded from the keyword's half (four words each)

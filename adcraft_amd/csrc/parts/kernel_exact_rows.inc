@@ -840,7 +840,8 @@ __device__ __forceinline__ RestLaws rest_laws(const View &v, const float *__rest
     L.scale = param_at(v, ADC_P_B, env, k);
     const float bctr = param_at(v, ADC_P_BCTR, env, k);
     L.law = adc::make_auction_law(bctr);
-    L.iv = adc::win_intervals<false>(bid_c, L.loc, L.scale, adc::bernoulli_threshold(bctr), L.law, g_log_table);
+    // (the float64 offsets: four candidate trials side by side cost k_step_rest_of_day<false> four registers and its seventh wave)
+    L.iv = adc::win_intervals<false, true>(bid_c, L.loc, L.scale, adc::bernoulli_threshold(bctr), L.law, g_log_table);
     const int cheap_bid = min(bid_c, (int)(st.R < 0x3FFFFFFFll ? (st.R > 0 ? st.R : 0) : 0x3FFFFFFFll) + 1);
     L.cheap = adc::win_brackets(cheap_bid, L.loc, L.scale, adc::bernoulli_threshold_f32(bctr)).out;
     return L;

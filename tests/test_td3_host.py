@@ -25,7 +25,7 @@ def _same(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
-def _setup(rng, act, widths, norm, size, hidden=(16, 8)):
+def _setup(rng, act, widths, norm, size, hidden=(16, 8), K=K):
     """a policy, a state whose targets and moments differ from the live networks, an action normalisation and a ring of `size` rows"""
     pol = R.random_policy(rng, K, hidden, activation=act)
     critics = T3.random_critics_for_tests(rng, K, widths)

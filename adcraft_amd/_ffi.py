@@ -100,6 +100,17 @@ class PGKLStats(C.Structure):
     _fields_ = [("kl", C.c_double), ("vf_clip_fraction", C.c_double), ("kl_coef", C.c_float), ("kl_coef_next", C.c_float)]
 
 
+class IMConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("beta", C.c_float), ("vf_coef", C.c_float), ("w_max", C.c_float), ("ma_start", C.c_double),
+                ("ma_rate", C.c_double), ("train_log_std", C.c_int32)]
+
+
+class IMStats(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("samples", C.c_int64), ("policy_loss", C.c_double), ("value_loss", C.c_double),
+                ("entropy", C.c_double), ("logp", C.c_double), ("weight", C.c_double), ("grad_norm", C.c_double),
+                ("explained_variance", C.c_double)]
+
+
 class TD3Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_float), ("tau", C.c_float), ("policy_delay", C.c_int32),
                 ("target_noise", C.c_float), ("target_noise_clip", C.c_float), ("action_lo", C.c_float), ("action_hi", C.c_float),
@@ -376,6 +387,16 @@ def lib():
         "adc_pg_decide_host": ([C.POINTER(PGConfig), f32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)], C.c_int),
         "adc_engine_pg_update_queued": ([vp, i32, C.POINTER(PGStats)], C.c_int),
         "adc_engine_pg_pop_update_queued": ([vp, i32, C.POINTER(PGStats)], C.c_int),
+        "adc_engine_teach_days": ([vp, C.c_int, i32, f32], C.c_int),
+        "adc_im_config_check": ([C.POINTER(IMConfig), C.POINTER(C.c_char_p)], C.c_int),
+        "adc_engine_im_init": ([vp, C.POINTER(IMConfig)], C.c_int),
+        "adc_engine_im_advantages": ([vp, vp, vp], C.c_int),
+        "adc_engine_im_minibatch": ([vp, i32, i32, C.POINTER(IMStats)], C.c_int),
+        "adc_engine_im_update": ([vp, i32, C.POINTER(IMStats)], C.c_int),
+        "adc_engine_im_state_get": ([vp, C.POINTER(f64), C.POINTER(i64)], C.c_int),
+        "adc_engine_im_state_set": ([vp, f64, i64], C.c_int),
+        "adc_im_weight_host": ([C.POINTER(IMConfig), i64, vp, C.POINTER(f64), C.POINTER(f32), vp], C.c_int),
+        "adc_im_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(IMConfig), f32, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(IMStats)], C.c_int),
         "adc_engine_td3_init": ([vp, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_td3_set_action_norm": ([vp, vp, vp], C.c_int),

@@ -259,6 +259,18 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
         self.history.append(stats)
         return stats
 
+    def demonstrate(self, teacher, days=None, budget=0.0):
+        """`days` (default: the horizon) teacher days (StepEngine.teach_days) into the ring: the expert's transitions before
+        learning starts, where RLlib's configuration spends random_timesteps on noise.  teacher: "oracle", "interpolation",
+        "zero_margin" or "fixed"; the engine must hold what that teacher needs.  Returns the ring's size."""
+        e = self.engine
+        e.rollout_reset()
+        e.teach_days(teacher, self.horizon if days is None else int(days), budget)
+        e.td3_store()
+        if self.normalize_observations or self.normalize_rewards:
+            e.td3_norm_update()
+        return e.td3_buffer(fetch=False)["size"]
+
     def policy(self):
         """an MLPPolicy holding the trained actor (its log_std the exploration's; under a running observation normaliser its
         shift / scale are the current vectors)"""

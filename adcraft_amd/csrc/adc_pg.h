@@ -287,9 +287,11 @@ inline PgStatsOut pg_stats_finish(const double *sums, int64_t S)
 // ---- the host's side of a sample: forward, head, loss, backward (the kernel runs the same steps, lanes over neurons) -------------
 // theta: flat order.  acts / deltas: pg_acts_floats / pg_deltas_floats values, networks and layers in order (the free log_std's
 // A "deltas" last); pieces: kPgPieces floats
-// `addon` is PgNoAddon, or adc_pg_kl.h's PgKlSampleHost: the KL penalty and the value-loss clip of one sample
+// `addon` is PgNoAddon, or adc_pg_kl.h's PgKlSampleHost: the KL penalty and the value-loss clip of one sample, or adc_imitation.h's
+// ImSampleHost (Addon::im): the surrogate is the imitation loss's, the pieces at kPgKl / kPgClipped are logp and the weight
 struct PgNoAddon {
     static constexpr bool on = false;
+    static constexpr bool im = false;
 };
 template <class Addon>
 inline void pg_sample_host_with(const PgShape &sh, const PgLoss &loss, const float *theta, const float *x, const float *action, float logp_old,
@@ -353,17 +355,21 @@ inline void pg_sample_host_with(const PgShape &sh, const PgLoss &loss, const flo
     }
     const float logp = mlp_logp_finish(sum8(A, [&](int a) { return mlp_logp_term(zs[(size_t)a], lss[(size_t)a]); }), A);
     const float entropy = pg_entropy_finish(sum8(A, [&](int a) { return lss[(size_t)a]; }), A);
-    const float ratio = mlp_exp(logp - logp_old);
-    float pol_loss, val_loss;
-    int clipped;
-    const float g = pg_surrogate(ratio, adv, loss.eps_clip, pol_loss, clipped);
+    float pol_loss, val_loss, g, w = 0.0f;
+    int clipped = 0;
+    if constexpr (Addon::im) g = addon.surrogate(adv, logp, pol_loss, w);
+    else {
+        const float ratio = mlp_exp(logp - logp_old);
+        g = pg_surrogate(ratio, adv, loss.eps_clip, pol_loss, clipped);
+    }
     const float V = sh.layers[1] ? outs[1][0] : 0.0f;
     float dV;
     if constexpr (Addon::on) dV = addon.value(V, ret, loss.vf_coef, val_loss);
     else dV = pg_dvalue(V, ret, loss.vf_coef, val_loss);
     if constexpr (Addon::on) addon.measure(sum8, A, o, lss.data(), sds.data());
-    pieces[kPgPolLoss] = pol_loss; pieces[kPgValLoss] = val_loss; pieces[kPgEntropy] = entropy; pieces[kPgKl] = logp_old - logp;
-    pieces[kPgClipped] = clipped ? 1.0f : 0.0f; pieces[kPgRet] = ret; pieces[kPgErr] = ret - value_old; pieces[7] = 0.0f;
+    pieces[kPgPolLoss] = pol_loss; pieces[kPgValLoss] = val_loss; pieces[kPgEntropy] = entropy;
+    pieces[kPgKl] = Addon::im ? logp : logp_old - logp;
+    pieces[kPgClipped] = Addon::im ? w : clipped ? 1.0f : 0.0f; pieces[kPgRet] = ret; pieces[kPgErr] = ret - value_old; pieces[7] = 0.0f;
     // output deltas
     {
         float *dp = dl[0][sh.layers[0] - 1];
@@ -371,6 +377,7 @@ inline void pg_sample_host_with(const PgShape &sh, const PgLoss &loss, const flo
             dp[a] = pg_dmean(g, zs[(size_t)a], sds[(size_t)a]);
             float d = pg_dls(g, zs[(size_t)a], loss.ent_coef, moved[(size_t)a]);
             if constexpr (Addon::on) addon.penalise(a, o[a], sds[(size_t)a], moved[(size_t)a], dp[a], d);
+            if constexpr (Addon::im) d = addon.dls(d);
             if (sh.two_heads) dp[A + a] = d; else d_free[a] = d;
         }
         if (sh.layers[1]) dl[1][sh.layers[1] - 1][0] = dV;

@@ -105,6 +105,7 @@ inline float pg_kl_adapt(const PgKlAdapt &a, float coef, double kl)
 // (ls_old the shared vector with the free head); pieces: kPgKlPieces floats
 struct PgKlSampleHost {
     static constexpr bool on = true;
+    static constexpr bool im = false;
     PgKl kl;
     const float *mean_old, *ls_old;
     float *pieces;

@@ -126,6 +126,18 @@ struct adc_engine {
     uint8_t *ro_term = nullptr, *ro_trunc = nullptr;
     std::vector<void *> ro_allocs;
     bool ro_deterministic = false;      // a recorded day was collected with the deterministic policy: its log-probabilities mean nothing
+    // teacher days (adc_engine_teach_days; parts/imitation_api.inc): how many of the record's days an expert acted on, and where the
+    // learner's discarded bids and budgets of such a day go ([N][K], then [N]; allocated at the first teacher day)
+    int ro_teacher = 0;
+    float *teach_act = nullptr;
+    std::vector<void *> teach_allocs;
+    // imitation learning over the live single-learner trainer (adc_engine_im_init; parts/kernel_imitation.inc, parts/imitation_api.inc;
+    // the law is adc_imitation.h): the moving scale ma, how often it was updated, the scale c of the last advantages call
+    bool have_im = false, im_adv_ready = false;
+    adc_im_config im_cfg{};
+    double im_ma = 0.0;
+    int64_t im_calls = 0;
+    float im_c = 0.0f;
     // policy-gradient training over the record (adc_engine_pg_init; parts/kernel_pg.inc, parts/pg_core.inc, parts/pg_api.inc)
     bool have_pg = false, pg_adv_ready = false;
     int pg_mb = 0;                      // envs of a minibatch (the scratch's capacity)
@@ -946,6 +958,7 @@ ADC_EXPORT void adc_engine_destroy(adc_engine *e)
     for (void *p : e->lrn_allocs) (void)hipFree(p);
     for (void *p : e->es_allocs) (void)hipFree(p);
     for (void *p : e->ro_allocs) (void)hipFree(p);
+    for (void *p : e->teach_allocs) (void)hipFree(p);
     for (void *p : e->pg_allocs) (void)hipFree(p);
     if (e->pq_host) (void)hipHostFree(e->pq_host);
     for (void *p : e->td3_allocs) (void)hipFree(p);
@@ -2914,7 +2927,7 @@ int mlp_record_outcome_chained(adc_engine *e)
         hipLaunchKernelGGL(k_mlp_record_outcome, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->ro_reward + row, e->ro_term + row,
                            e->ro_trunc + row);
     });
-    if (!rc) { e->ro_t += 1; e->pg_adv_ready = false; e->ro_moves = e->env_moves; }
+    if (!rc) { e->ro_t += 1; e->pg_adv_ready = e->im_adv_ready = false; e->ro_moves = e->env_moves; }
     return rc;
 }
 // the evolution strategy's side of a stepped day: every env's reward added to its return of the generation
@@ -2976,6 +2989,7 @@ void pg_drop(adc_engine *e)
     if (e->pq_host) (void)hipHostFree(e->pq_host);      // (the queued update's pinned twin; its device block was among pg_allocs)
     e->pq_dev = e->pq_host = nullptr; e->pq_bytes = 0;
     e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
+    e->have_im = e->im_adv_ready = false;       // (imitation lives on this trainer's theta and scratch)
     e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();
     e->pgp_dmem = nullptr;
 }
@@ -3159,7 +3173,7 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     HIP_TRY(err2);
     e->have_mlp = true;
     // (a record sized for another action width does not survive a re-initialisation)
-    if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; }
+    if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; e->ro_teacher = 0; }
     return ADC_OK;
 }
 
@@ -3817,6 +3831,7 @@ ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t
     e->ro_T = e->ro_t = 0;
     e->ro_obs = nullptr;
     e->ro_deterministic = false;
+    e->ro_teacher = 0;
     if (horizon == 0) return ADC_OK;
     const size_t tn = (size_t)horizon * (size_t)e->v.N;
     int rc;
@@ -3840,7 +3855,8 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     e->ro_t = 0;
     for (NormSet *s : {&e->on, &e->rn, &e->tn, &e->sn}) s->t0 = 0;
     e->ro_deterministic = false;
-    e->pg_adv_ready = false;
+    e->ro_teacher = 0;
+    e->pg_adv_ready = e->im_adv_ready = false;
     e->td3_stored_t = 0;
     e->td3_gap = false;
     return ADC_OK;

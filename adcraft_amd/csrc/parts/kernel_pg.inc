@@ -249,11 +249,13 @@ __device__ __forceinline__ void pg_layer_back(const float *__restrict__ W, int n
 // the sample's scratch rows are row `slot` of p.acts / p.deltas / p.pieces.  kKl: with adc_pg_kl.h's KL penalty and value-loss clip
 // (k, kl; ls_old_at: where the member's vector starts in k.ls_old with the free head) - the instantiation without is the code
 // it was before there was one.  kGather: the sample's record row is grows[s] (adc_pg_shuffle.h; parts/kernel_pg_shuffle.inc),
-// n0 and p.B are not read - again the instantiations without are the code they were
-template <bool kKl, bool kGather = false>
+// n0 and p.B are not read - again the instantiations without are the code they were.  kIm: the imitation loss of a teacher sample
+// (adc_imitation.h; parts/kernel_imitation.inc) in the surrogate's place, logp and the weight where the KL's and the clip's pieces
+// are - once more the instantiations without are the code they were
+template <bool kKl, bool kGather = false, bool kIm = false>
 __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *nets, const float *log_std, const adc::PgLoss &loss, int n0, size_t s,
                                                size_t slot, const PgKlView &k, const adc::PgKl &kl, size_t ls_old_at,
-                                               const uint32_t *__restrict__ grows = nullptr)
+                                               const uint32_t *__restrict__ grows = nullptr, const adc::ImLaw &im = adc::ImLaw{})
 {
     extern __shared__ __align__(16) float pg_lds[];
     __shared__ float s_g, s_dv;
@@ -328,10 +330,15 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
         if (tid == 0) {
             const float logp = adc::mlp_logp_finish(st, A), entropy = adc::pg_entropy_finish(sl, A);
             const float logp_old = p.logp[row], ret = p.ret[row];
-            const float ratio = adc::mlp_exp(logp - logp_old);
-            float pol_loss, val_loss;
-            int clipped;
-            const float g = adc::pg_surrogate(ratio, p.adv[row], loss.eps_clip, pol_loss, clipped);
+            float pol_loss, val_loss, g, w = 0.0f;
+            int clipped = 0;
+            if constexpr (kIm) {
+                w = adc::im_weight(p.adv[row], im);
+                g = adc::im_surrogate(w, logp, pol_loss);
+            } else {
+                const float ratio = adc::mlp_exp(logp - logp_old);
+                g = adc::pg_surrogate(ratio, p.adv[row], loss.eps_clip, pol_loss, clipped);
+            }
             const float V = sh.layers[1] ? y[1][sh.layers[1] - 1][0] : 0.0f;
             float dv;
             if constexpr (kKl) {
@@ -342,8 +349,8 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
             } else dv = adc::pg_dvalue(V, ret, loss.vf_coef, val_loss);
             s_g = g; s_dv = dv;
             float *pc = p.pieces + slot * (size_t)adc::kPgPieces;
-            pc[adc::kPgPolLoss] = pol_loss; pc[adc::kPgValLoss] = val_loss; pc[adc::kPgEntropy] = entropy; pc[adc::kPgKl] = logp_old - logp;
-            pc[adc::kPgClipped] = clipped ? 1.0f : 0.0f; pc[adc::kPgRet] = ret; pc[adc::kPgErr] = ret - p.value[row]; pc[7] = 0.0f;
+            pc[adc::kPgPolLoss] = pol_loss; pc[adc::kPgValLoss] = val_loss; pc[adc::kPgEntropy] = entropy; pc[adc::kPgKl] = kIm ? logp : logp_old - logp;
+            pc[adc::kPgClipped] = kIm ? w : clipped ? 1.0f : 0.0f; pc[adc::kPgRet] = ret; pc[adc::kPgErr] = ret - p.value[row]; pc[7] = 0.0f;
         }
     }
     __syncthreads();
@@ -361,6 +368,8 @@ __device__ __forceinline__ void pg_sample_body(const PgView &p, const MlpNet *ne
             const int moved = adc::pg_clamp_moved(raw, sh.clamp, sh.ls_lo, sh.ls_hi);
             float dm = adc::pg_dmean(g, zs[a], sds[a]);
             float dl = adc::pg_dls(g, zs[a], loss.ent_coef, moved);
+            if constexpr (kIm)
+                if (!im.train_log_std) dl = 0.0f;
             if constexpr (kKl)
                 if (kl.coef != 0.0f) {          // (wave-uniform; a zero coefficient adds nothing: adc_pg.h's bits)
                     dm = adc::pg_kl_add(dm, kl.coef, adc::pg_kl_dmean(o[a], sds[a], mos[a]));

@@ -225,6 +225,7 @@ ADC_EXPORT int adc_engine_obs_norm_init(adc_engine *e, const adc_obs_norm_config
     if (adc_obs_norm_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
     if (int rc = mlp_ready(e)) return rc;
     if (!e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
+    if (e->have_im) return fail(ADC_ESTATE, "imitation is alive on this trainer (adc_engine_im_init): teacher days are recorded under the static normalisation");
     const bool per_member = cfg->per_member != 0;
     if (per_member && e->lrn_M == 0) return fail(ADC_ESTATE, "per-member normalisers need learners (adc_engine_mlp_learners)");
     if (e->have_td3 || e->have_td3_pop)
@@ -321,6 +322,7 @@ ADC_EXPORT int adc_engine_rew_norm_init(adc_engine *e, const adc_rew_norm_config
         return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: its reward enters at the TD3 target, not through GAE");
     if (!e->have_pg && !e->have_pg_pop)
         return fail(ADC_ESTATE, "the reward normaliser discounts by a PPO / A2C trainer's gamma: adc_engine_pg_init or adc_engine_pg_pop_init first");
+    if (e->have_im) return fail(ADC_ESTATE, "imitation is alive on this trainer (adc_engine_im_init): the teacher's returns are not normalised");
     const bool per_member = cfg->per_member != 0;
     if (per_member && !e->have_pg_pop) return fail(ADC_ESTATE, "per-member normalisers need a learner population (adc_engine_pg_pop_init)");
     ENGINE_GUARD(e);

@@ -39,6 +39,9 @@ int pg_record_check(const adc_engine *e)
     if (e->ro_deterministic)
         return fail(ADC_ESTATE, "the record holds days collected with the deterministic policy: their log-probabilities mean nothing "
                                 "(adc_engine_mlp_set_deterministic(0), adc_engine_rollout_reset, collect again)");
+    if (e->ro_teacher > 0)
+        return fail(ADC_ESTATE, "the record holds teacher days: their actions are an expert's, not the policy's (adc_engine_im_update consumes them; "
+                                "adc_engine_rollout_reset, collect again)");
     return ADC_OK;
 }
 // the preamble of the calls that work on the record: the trainer, the engine's state, the record, an update's epochs

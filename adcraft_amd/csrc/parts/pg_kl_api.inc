@@ -99,6 +99,7 @@ ADC_EXPORT int adc_engine_pg_kl_init(adc_engine *e, const adc_pg_kl_config *cfgs
     if (e->have_td3 || e->have_td3_pop) return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: the KL penalty belongs to the PPO / A2C loss");
     if (!e->have_pg && !e->have_pg_pop)
         return fail(ADC_ESTATE, "the KL penalty is an add-on to a PPO / A2C trainer: adc_engine_pg_init or adc_engine_pg_pop_init first");
+    if (e->have_im) return fail(ADC_ESTATE, "imitation is alive on this trainer (adc_engine_im_init): its loss has no collecting distribution to penalise against");
     const int M = pg_members(e);
     if (!cfgs) return fail(ADC_EINVAL, "adc_pg_kl_config array is NULL");
     if (count != 1 && count != M) return fail(ADC_EINVAL, "count: 1 (one configuration shared by all members) or the number of members");

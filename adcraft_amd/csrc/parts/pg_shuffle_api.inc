@@ -117,6 +117,7 @@ ADC_EXPORT int adc_engine_pg_shuffle_init(adc_engine *e, const adc_pg_shuffle_co
         return fail(ADC_ESTATE, "an off-policy (TD3) trainer is alive on this engine: its batches are drawn per update already (shuffled minibatches belong to PPO / A2C)");
     if (!e->have_pg && !e->have_pg_pop)
         return fail(ADC_ESTATE, "shuffled minibatches are an add-on to a PPO / A2C trainer: adc_engine_pg_init or adc_engine_pg_pop_init first");
+    if (e->have_im) return fail(ADC_ESTATE, "imitation is alive on this trainer (adc_engine_im_init): its updates run over contiguous env minibatches");
     const int M = pg_members(e), n = pg_member_envs(e);
     if (!cfgs) return fail(ADC_EINVAL, "adc_pg_shuffle_config array is NULL");
     if (count != 1 && count != M) return fail(ADC_EINVAL, "count: 1 (one configuration shared by all members) or the number of members");

@@ -201,6 +201,7 @@ ADC_EXPORT int adc_engine_sac_store(adc_engine *e, int64_t *stored)
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = sac_ready(e)) || (rc = sac_state_check(e)) || (rc = off_store_check(e))) return rc;
+    if (e->ro_teacher > 0) return fail(ADC_ESTATE, "the record holds teacher days: a soft actor-critic ring would need the pre-squash action of the teacher");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;        // (every env is the one learner's)
     // (raw rows under a running observation normaliser - SAC's set, e->sn: the last day's x' is the raw row an act would read now)

@@ -2036,6 +2036,71 @@ class StepEngine:
             check(self._lib.adc_engine_day_graph_enable(self._h, 1 if graph else 0))
         check(self._lib.adc_engine_run_days(self._h, self.POLICIES[policy], int(days), float(budget)))
 
+    # ---- imitation learning: teacher days, behaviour cloning and MARWIL (parts/imitation_api.inc; the law is csrc/adc_imitation.h) ----
+    def teach_days(self, teacher, days, budget=100000.0):
+        """`days` teacher days: the learned agent acts (its action thrown away, its input row and value recorded), `teacher` -
+        "fixed", "zero_margin", "oracle" or "interpolation" - acts as run_days has it act, the record keeps the teacher's action
+        (logp +0), the env steps.  Needs mlp_init and rollout_enable(T, obs=True); the env ends where run_days(teacher) leaves it."""
+        if teacher not in self.POLICIES:
+            raise ValueError(f"unknown teacher {teacher!r}: one of {sorted(self.POLICIES)}")
+        check(self._lib.adc_engine_teach_days(self._h, self.POLICIES[teacher], int(days), float(budget)))
+
+    @classmethod
+    def im_config(cls, beta=0.0, vf_coef=1.0, w_max=20.0, ma_start=100.0, ma_rate=1e-8, train_log_std=True):
+        """an adc_im_config: beta 0 is behaviour cloning (w = 1), beta > 0 MARWIL's exp(beta adv / c) capped at w_max (0: no cap);
+        vf_coef 0 drops the value loss; ma_start / ma_rate: the moving scale of the advantages (RLlib's 100 and 1e-8);
+        train_log_std False leaves the free log_std as it is (the user's action scale)"""
+        c = _ffi.IMConfig()
+        c.struct_size = C.sizeof(_ffi.IMConfig)
+        c.beta, c.vf_coef, c.w_max, c.ma_start, c.ma_rate = float(beta), float(vf_coef), float(w_max), float(ma_start), float(ma_rate)
+        c.train_log_std = 1 if train_log_std else 0
+        msg = C.c_char_p()
+        if _ffi.lib().adc_im_config_check(C.byref(c), C.byref(msg)) != _ffi.ADC_OK:
+            raise ValueError((msg.value or b"bad imitation configuration").decode())
+        return c
+
+    def im_init(self, **options):
+        """imitation over the live single-learner trainer (pg_init first): it trains that trainer's theta with its optimiser; options
+        as im_config's"""
+        cfg = self.im_config(**options)
+        check(self._lib.adc_engine_im_init(self._h, C.byref(cfg)))
+
+    def im_advantages(self, fetch=False):
+        """the teacher's discounted returns over the recorded teacher days and the moving scale's update; fetch=True returns
+        (adv, ret) [T, N] float32"""
+        if not fetch:
+            check(self._lib.adc_engine_im_advantages(self._h, None, None))
+            return None
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        adv, ret = np.zeros((t.value, self.num_envs), np.float32), np.zeros((t.value, self.num_envs), np.float32)
+        check(self._lib.adc_engine_im_advantages(self._h, adv.ctypes.data, ret.ctypes.data))
+        return adv, ret
+
+    @staticmethod
+    def _im_stats(st):
+        return {k: getattr(st, k) for k, _ in _ffi.IMStats._fields_}
+
+    def im_minibatch(self, env_begin, env_count):
+        """one gradient of the imitation loss and one optimiser step over every recorded day of the envs [env_begin, env_begin + env_count)"""
+        st = _ffi.IMStats()
+        check(self._lib.adc_engine_im_minibatch(self._h, int(env_begin), int(env_count), C.byref(st)))
+        return self._im_stats(st)
+
+    def im_update(self, epochs=1):
+        """`epochs` x the minibatches of minibatch_envs in ascending env order (im_advantages first); the last epoch's statistics"""
+        st = _ffi.IMStats()
+        check(self._lib.adc_engine_im_update(self._h, int(epochs), C.byref(st)))
+        return self._im_stats(st)
+
+    def im_state(self, state=None):
+        """get (no argument): dict of ma and calls; set: such a dict (theta, m, v and steps are pg_state's)"""
+        if state is None:
+            ma, calls = C.c_double(0.0), C.c_int64(0)
+            check(self._lib.adc_engine_im_state_get(self._h, C.byref(ma), C.byref(calls)))
+            return dict(ma=ma.value, calls=calls.value)
+        check(self._lib.adc_engine_im_state_set(self._h, float(state["ma"]), int(state["calls"])))
+
     def metrics_akncp_ncp(self, days):
         """(AKNCP [N], NCP [N]) of the running episode, reduced on the device (per-env median over the keywords in LDS)"""
         a, b = np.zeros(self.num_envs, np.float64), np.zeros(self.num_envs, np.float64)

@@ -819,6 +819,66 @@ int adc_engine_pg_shuffle_stats(adc_engine *e, adc_pg_shuffle_stats *stats_m);  
 int adc_engine_pg_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats *stats);
 int adc_engine_pg_pop_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats *stats_m);
 
+/* ---- imitation learning on the device: teacher days, behaviour cloning and MARWIL (the law is csrc/adc_imitation.h) -------------
+ * A TEACHER DAY is an act of the learned agent whose action is thrown away and replaced by an expert's.  Per day, chained and
+ * group-compatible like a day of adc_engine_run_days(ADC_POLICY_MLP): the learner acts on the observation the last step left as
+ * adc_engine_mlp_step has it act - static normalisation, observation history, value network, its tick moves on by one - but its
+ * bids and budget go to a scratch buffer; the record's slot gets the network input row and the value.  Then the teacher acts as
+ * adc_engine_run_days has it act for that policy (ADC_POLICY_FIXED_ACTIONS: the action buffers as they are - how labels of any
+ * outside expert get in), the slot's action becomes {budget, bids} the step is about to consume (float32) and its logp +0, and the
+ * env steps.  The env ends a teacher day in exactly the state adc_engine_run_days(teacher) leaves it in.
+ * The engine counts the record's teacher days (cleared by adc_engine_rollout_enable / _reset).  The policy-gradient calls refuse a
+ * record that holds any ("the record holds teacher days"), adc_engine_td3_store accepts them (demonstrations), the SAC stores
+ * refuse them (the ring would need the pre-squash action).  adc_engine_teach_days is refused (ADC_ESTATE / ADC_EINVAL, the engine
+ * stays usable): ADC_POLICY_MLP as the teacher, before adc_engine_mlp_init and its uploads, without a record or without
+ * ADC_ROLLOUT_OBS, without room for `days`, with a population or learners active, with a squash set, with a teacher that has not
+ * been initialised (adc_engine_run_days' messages). */
+int adc_engine_teach_days(adc_engine *e, int teacher_policy, int32_t days, float budget);
+
+/* IMITATION is an add-on to a single-learner adc_engine_pg_init trainer: it shares its theta, Adam moments, lr, max_grad_norm and
+ * minibatch_envs, so the cloned policy is the very theta adc_engine_pg_update goes on training, and the value network arrives
+ * fitted to the teacher's returns.  adc_engine_im_advantages: the discounted returns of the teacher's rewards (GAE with lambda 1
+ * under the trainer's gamma and reward_scale, no normalisation), the moving scale ma updated once over all recorded samples, the
+ * call's scale c; adv_tn / ret_tn [T][N] may be NULL.  adc_engine_im_minibatch: one gradient of -(w logp(teacher action)) + the
+ * value loss over every recorded day of an env range and one optimiser step; adc_engine_im_update: `epochs` times the contiguous
+ * minibatches of minibatch_envs in ascending env order, the last epoch's statistics averaged (it does not compute the advantages:
+ * adc_engine_im_advantages first).  Refused (ADC_ESTATE / ADC_EINVAL): without a single-learner trainer; with the KL or the
+ * shuffle add-on or a running normaliser alive (and those are refused while imitation lives); with a record holding a day that is
+ * not a teacher day ("the record holds days the learner collected"); a minibatch or update before adc_engine_im_advantages since
+ * the last recorded day; beyond the LDS limit.  Imitation ends wherever the trainer ends. */
+typedef struct adc_im_config {
+    uint32_t struct_size;          /* sizeof(adc_im_config) */
+    float beta;                    /* >= 0; 0: behaviour cloning (w = 1, no exp evaluated) */
+    float vf_coef;                 /* >= 0; 0 drops the value loss */
+    float w_max;                   /* > 0: the weight's cap; 0: none */
+    double ma_start, ma_rate;      /* the moving scale: ma_start >= 0 (100), ma_rate in [0, 1] (1e-8) */
+    int32_t train_log_std;         /* 0: dL/dlog_std = +0 (the free log_std stays the user's action scale) */
+} adc_im_config;
+typedef struct adc_im_stats {
+    int64_t steps;                 /* optimiser steps taken so far (the trainer's count) */
+    int64_t samples;               /* samples of the (last) minibatch */
+    double policy_loss, value_loss, entropy;
+    double logp;                   /* mean log-probability of the teacher's actions */
+    double weight;                 /* mean w */
+    double grad_norm;              /* before the clip */
+    double explained_variance;     /* of the value function at collection against the teacher's returns */
+} adc_im_stats;
+int adc_im_config_check(const adc_im_config *cfg, const char **message);                /* host only */
+int adc_engine_im_init(adc_engine *e, const adc_im_config *cfg);
+int adc_engine_im_advantages(adc_engine *e, float *adv_tn, float *ret_tn);
+int adc_engine_im_minibatch(adc_engine *e, int32_t env_begin, int32_t env_count, adc_im_stats *stats);
+int adc_engine_im_update(adc_engine *e, int32_t epochs, adc_im_stats *stats);
+/* ma and the number of advantages calls; theta, m, v and the steps are adc_engine_pg_state_get's */
+int adc_engine_im_state_get(adc_engine *e, double *ma, int64_t *calls);
+int adc_engine_im_state_set(adc_engine *e, double ma, int64_t calls);
+/* host twins (adc_shims.cpp), the code the device runs.  adc_im_weight_host: one advantages call's scale and weights -
+ * *ma (in: the state before, out: after), *c, w_s [count] from adv_s [count] (w_s may be NULL).  adc_im_grad_host: the gradient,
+ * the law's ten sums and the statistics of `count` samples under the scale c, as adc_pg_grad_host */
+int adc_im_weight_host(const adc_im_config *cfg, int64_t count, const float *adv_s, double *ma, float *c, float *w_s);
+int adc_im_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_im_config *cfg, float c, const float *theta_q, int64_t count,
+                     const float *obs_sd, const float *action_sa, const float *adv_s, const float *ret_s, const float *value_old_s, float *grad_q,
+                     double *sums10, adc_im_stats *stats);
+
 /* ---- off-policy training on the device: a replay ring, twin critics, TD3 (the law is csrc/adc_td3.h) --------------------------
  * The actor is the policy network given to adc_engine_mlp_init with the free log_std[A] head; its mean is TD3's deterministic
  * action, and the stochastic act mean + exp(log_std) * z is the exploration (set log_std = log(sigma); TD3 never trains it; a

@@ -317,6 +317,12 @@ def lib():
         "adc_engine_mlp_set_squash": ([vp, vp, vp], C.c_int),
         "adc_engine_mlp_learners_set_squash": ([vp, vp, vp], C.c_int),
         "adc_mlp_squash_host": ([i32, vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_set_bounds": ([vp, vp, vp], C.c_int),
+        "adc_engine_mlp_learners_set_bounds": ([vp, vp, vp], C.c_int),
+        "adc_engine_mlp_set_explore": ([vp, i32], C.c_int),
+        "adc_engine_mlp_get_bounds": ([vp, vp, vp, C.POINTER(i32), C.POINTER(i32)], C.c_int),
+        "adc_mlp_bounded_host": ([i32, vp, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp], C.c_int),
+        "adc_mlp_unbox_host": ([i32, vp, vp, vp, vp], C.c_int),
         "adc_engine_mlp_act": ([vp, f32, vp], C.c_int),
         "adc_engine_mlp_step": ([vp, f32], C.c_int),
         "adc_engine_mlp_last": ([vp, vp, vp, vp, vp, vp], C.c_int),
@@ -400,6 +406,11 @@ def lib():
         "adc_engine_td3_init": ([vp, C.POINTER(TD3Config)], C.c_int),
         "adc_engine_td3_set_critic_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_td3_set_action_norm": ([vp, vp, vp], C.c_int),
+        "adc_engine_td3_set_bounded": ([vp, i32], C.c_int),
+        "adc_engine_td3_pop_set_bounded": ([vp, i32], C.c_int),
+        "adc_engine_td3_get_bounded": ([vp, C.POINTER(i32)], C.c_int),
+        "adc_td3_bounded_target_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), u64, i64, vp, vp, i32, vp, vp, vp, vp], C.c_int),
+        "adc_td3_bounded_actor_grad_host": ([C.POINTER(MLPConfig), i32, C.POINTER(TD3Config), vp, vp, i32, vp, vp, vp], C.c_int),
         "adc_engine_td3_sync_targets": ([vp], C.c_int),
         "adc_engine_td3_store": ([vp, C.POINTER(i64)], C.c_int),
         "adc_engine_td3_buffer_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)], C.c_int),

@@ -9,7 +9,13 @@ The actor is the MLPPolicy's policy network with the free log_std head; its mean
 mean + exp(log_std) * z, log_std = log(exploration sigma), the exploration.  The reference's pure-random warm-up
 (`random_timesteps`) is covered by collecting under the initial policy with a larger sigma for the first iterations:
 `TD3Trainer.set_exploration(sigma)`, then back.  n_step > 1 turns on n-step returns (StepEngine.replay_nstep_*; the law is
-csrc/adc_td3.h "n-step") for the trainer's ring(s)."""
+csrc/adc_td3.h "n-step") for the trainer's ring(s).
+
+action_bounds=(lo, hi) turns on the bounded mode (csrc/adc_mlp.h "bounded", csrc/adc_td3.h "bounded"), the way RLlib's DDPG
+family and Stable-Baselines3 run TD3: the actor is tanh-squashed into the action box, the exploration noise is added to the
+squashed action and clipped to the box, the ring and the critics hold the action in units of the box, and the first
+random_timesteps transitions are collected with actions drawn uniformly from the box.  rllib_td3(lo, hi) is the paper's
+`sem_td3_config` in these terms."""
 import copy
 
 import numpy as np
@@ -25,6 +31,89 @@ def td3(**overrides):
                optimiser="adam")
     cfg.update(overrides)
     return cfg
+
+
+def rllib_td3(lo, hi, **overrides):
+    """TD3Trainer's keyword options for the paper's `sem_td3_config` (RLlib's TD3Config) as far as this trainer expresses it, on
+    the action box [lo, hi] (scalars, or [K + 1] in the flat action order; the reference's own action space has no finite upper
+    bound, so the box is the user's): gamma 0.995, both learning rates 1e-3, batches of 2048, tau 0.005, a ring of 1e6,
+    random_timesteps = learning_starts = 10000, policy_delay 2 and target noise 0.2 clipped at 0.5 (RLlib's TD3 defaults), and
+    RLlib's Gaussian exploration of stddev 0.1 in action units converted to units of the half-range (sigma = 0.1 / (0.5 (hi - lo)):
+    about 0.067 on [0.01, 3]; the bounds must then have one width, or give exploration_sigma yourself).  The critics are
+    (256, 256) where the paper has fcnet_hiddens [400, 300]: hidden widths above 256 are not supported.  The paper's relu
+    activation is the MLPPolicy's to choose."""
+    half = np.unique(0.5 * (np.asarray(hi, np.float64) - np.asarray(lo, np.float64)))
+    cfg = dict(action_bounds=(lo, hi), critic_hidden=(256, 256), learning_starts=10000, random_timesteps=10000, gamma=0.995, tau=0.005,
+               policy_delay=2, target_noise=0.2, target_noise_clip=0.5, batch_size=2048, capacity=1000000, actor_lr=1e-3, critic_lr=1e-3,
+               optimiser="adam")
+    if "exploration_sigma" not in overrides:
+        if half.size != 1 or not half[0] > 0.0:
+            raise ValueError("rllib_td3: the bounds' widths differ (or are not positive): give exploration_sigma in units of the half-range")
+        cfg["exploration_sigma"] = 0.1 / float(half[0])
+    cfg.update(overrides)
+    return cfg
+
+
+def action_box(action_bounds, K):
+    """(lo, hi) float32 [K + 1] from action_bounds = (lo, hi), scalars or vectors in the flat action order; None stays None"""
+    if action_bounds is None:
+        return None
+    if len(action_bounds) != 2:
+        raise ValueError("action_bounds: a pair (lo, hi)")
+    lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (K + 1,))).copy() for v in action_bounds)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi > lo)):
+        raise ValueError("action_bounds: finite, hi > lo")
+    return lo, hi
+
+
+class BoundedActions:
+    """the trainers' side of action_bounds / random_timesteps.  Under bounds exploration_sigma is one scalar in units of the
+    half-range 0.5 (hi - lo) - RLlib's 0.1 dollars on a [0.01, 3] box is about 0.067 - so set_exploration and the PBT scheduler's
+    sigma perturbation work unchanged.  An iteration collects in the act's random mode while fewer than random_timesteps
+    transitions have been stored in (a member's) ring, and in the gaussian mode from then on.  A trainer's state() carries
+    `bounded` - the bounds, the mode and random_timesteps - and refuses a state made under other bounds."""
+
+    def _bounds_check(self, action_bounds, random_timesteps, K, action_norms):
+        self.action_bounds = action_box(action_bounds, K)
+        if isinstance(random_timesteps, bool) or int(random_timesteps) != random_timesteps or int(random_timesteps) < 0:
+            raise ValueError("random_timesteps: an integer >= 0")
+        self.random_timesteps = int(random_timesteps)
+        if self.random_timesteps and self.action_bounds is None:
+            raise ValueError("random_timesteps needs action_bounds: the warm-up's actions are drawn uniformly from the box")
+        if self.action_bounds is not None and any(n is not None for n in action_norms):
+            raise ValueError("action_bounds with action_norm is not supported: the critics read the action in [-1, 1] as stored")
+
+    def _explore_for(self, written):
+        """before a collection: the act's mode from the transitions stored so far"""
+        if self.action_bounds is not None:
+            self.engine.mlp_set_explore("random" if written < self.random_timesteps else "gaussian")
+
+    def _bounded_state(self, get_or_set, state):
+        if state is None:
+            st = get_or_set(None)
+            if self.action_bounds is not None:
+                st["bounded"] = dict(lo=self.action_bounds[0].copy(), hi=self.action_bounds[1].copy(), explore=self.engine.mlp_bounds()["explore"],
+                                     random_timesteps=self.random_timesteps)
+            return st
+        state = dict(state)
+        b = state.pop("bounded", None)
+        if (b is None) != (self.action_bounds is None):
+            raise ValueError("the state was made " + ("without" if b is None else "under") + " action_bounds, and this trainer was not")
+        if b is not None:
+            if not (np.array_equal(b["lo"], self.action_bounds[0]) and np.array_equal(b["hi"], self.action_bounds[1])):
+                raise ValueError("the state was made under other action_bounds: its ring's actions are in units of those")
+            self.random_timesteps = int(b["random_timesteps"])
+        get_or_set(state)
+        if b is not None:
+            self.engine.mlp_set_explore(b["explore"])
+
+    def _squashed(self, pol):
+        """the exported policy: under bounds with the box its actions are meant under (a deterministic act of it through
+        mlp_set_squash gives the env the bits the bounded act gives it)"""
+        if self.action_bounds is None:
+            return pol
+        from .sac_trainer import SquashedPolicy
+        return SquashedPolicy(pol, *self.action_bounds)
 
 
 def random_critics(K, hidden, seed=0, frames=1):
@@ -195,7 +284,7 @@ class NStepReturns:
             self.engine.replay_nstep_state(member, nstep)
 
 
-class TD3Trainer(PrioritizedReplay, NStepReturns):
+class TD3Trainer(PrioritizedReplay, NStepReturns, BoundedActions):
     """engine: a StepEngine that has been reset; policy: the MLPPolicy to start from (K + 1 means, free log_std; a value network
     is ignored); critic_hidden: the critics' hidden widths (each <= 256); horizon: the days of one collection;
     exploration_sigma: the standard deviation of the collection noise; learning_starts: transitions the ring must hold before
@@ -208,10 +297,18 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
     statistics updated from every collection BEFORE its updates; norm: dict(obs_min_std=..., obs_count_cap=..., rew_min_std=...,
     rew_count_cap=..., rew_clip=...).  What they gain in learning has not been measured.
 
-    prioritized_replay: None, or PrioritizedReplay's dict.  n_step: the window of n-step returns, 1 (off) to 16 (NStepReturns)."""
+    prioritized_replay: None, or PrioritizedReplay's dict.  n_step: the window of n-step returns, 1 (off) to 16 (NStepReturns).
+
+    action_bounds: None, or (lo, hi) - scalars or [K + 1] in the flat action order (budget, bids): the bounded mode
+    (BoundedActions).  exploration_sigma is then in units of the half-range 0.5 (hi - lo), one scalar: RLlib's 0.1 dollars on a
+    [0.01, 3] box is about 0.067; target_noise and target_noise_clip are in those units too, as Fujimoto's 0.2 / 0.5 are.
+    action_lo / action_hi and action_norm are refused with it.  random_timesteps: the transitions collected with actions drawn
+    uniformly from the box before the Gaussian exploration starts (RLlib's exploration_config).  policy() then returns
+    sac_trainer's SquashedPolicy (the actor and its bounds)."""
 
     def __init__(self, engine, policy, critic_hidden=(256, 256), horizon=10, exploration_sigma=0.1, learning_starts=10000, updates_per_iteration=64,
-                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, prioritized_replay=None, n_step=1, **config):
+                 agent_seeds=None, normalize_observations=False, normalize_rewards=False, norm=None, prioritized_replay=None, n_step=1,
+                 action_bounds=None, random_timesteps=0, **config):
         norm = _norm_options([policy], normalize_observations, normalize_rewards, norm)
         n_step = nstep_check(n_step)
         if policy.log_std is None:
@@ -220,15 +317,20 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
         cfg = dict(config)
         critics, action_norm = cfg.pop("critics", None), cfg.pop("action_norm", None)
         critic_seed = cfg.pop("critic_seed", 0)
+        self._bounds_check(action_bounds, random_timesteps, policy.num_keywords, [action_norm])
         self.engine, self.horizon = engine, int(horizon)
         self.learning_starts, self.updates_per_iteration = int(learning_starts), int(updates_per_iteration)
         self._template = copy.copy(policy)
         self._template.log_std = np.full(policy.num_keywords + 1, np.log(exploration_sigma), np.float32)
         self.config = dict(cfg, critic_widths=tuple(critic_hidden) + (1,))
         engine.mlp_init(self._template, seeds=agent_seeds, deterministic=False)
+        if self.action_bounds is not None:
+            engine.mlp_set_bounds(*self.action_bounds)
         engine.rollout_enable(self.horizon, obs=True)
         engine.td3_init(**self.config)
         engine.td3_set_critics(critics if critics is not None else random_critics(policy.num_keywords, critic_hidden, critic_seed, policy.frames), action_norm=action_norm)
+        if self.action_bounds is not None:
+            engine.td3_set_bounded(True)
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, **norm)
         self._prio_init(engine, prioritized_replay)
@@ -248,6 +350,8 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
         if reset:
             e.reset(seeds=reset_seeds)
         e.rollout_reset()
+        if self.action_bounds is not None:
+            self._explore_for(e.td3_buffer(fetch=False)["written"])
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.td3_store()
         if self.normalize_observations or self.normalize_rewards:
@@ -261,8 +365,10 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
 
     def demonstrate(self, teacher, days=None, budget=0.0):
         """`days` (default: the horizon) teacher days (StepEngine.teach_days) into the ring: the expert's transitions before
-        learning starts, where RLlib's configuration spends random_timesteps on noise.  teacher: "oracle", "interpolation",
-        "zero_margin" or "fixed"; the engine must hold what that teacher needs.  Returns the ring's size."""
+        learning starts (RLlib's configuration spends random_timesteps on uniform noise there: action_bounds with
+        random_timesteps does that).  teacher: "oracle", "interpolation", "zero_margin" or "fixed"; the engine must hold what that
+        teacher needs.  Under action_bounds the ring holds the teacher's actions in units of the box, clipped to it.  Returns the
+        ring's size."""
         e = self.engine
         e.rollout_reset()
         e.teach_days(teacher, self.horizon if days is None else int(days), budget)
@@ -275,12 +381,13 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
         """an MLPPolicy holding the trained actor (its log_std the exploration's; under a running observation normaliser its
         shift / scale are the current vectors)"""
         pol = policy_from_actor(self._template, self.engine.td3_state()["theta"])
-        return _with_vectors(pol, self.engine.td3_norm_state()) if self.normalize_observations else pol
+        return self._squashed(_with_vectors(pol, self.engine.td3_norm_state()) if self.normalize_observations else pol)
 
     def state(self, state=None):
         """the learner's state (StepEngine.td3_state's dict), `replay_prio` under prioritised replay, `replay_nstep` under n-step
         returns and `obs_history` with MLPPolicy(frames > 1); get or set"""
-        return history_carry(self.engine, lambda t: self._nstep_state(lambda s: self._prio_state(self.engine.td3_state, 0, s), 0, t), state)
+        return history_carry(self.engine,
+                             lambda u: self._bounded_state(lambda t: self._nstep_state(lambda s: self._prio_state(self.engine.td3_state, 0, s), 0, t), u), state)
 
     def load_state(self, state):
         self.state(state)
@@ -290,7 +397,7 @@ class TD3Trainer(PrioritizedReplay, NStepReturns):
         return _norm_state(self.engine, 0, state)
 
 
-class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
+class TD3PopulationTrainer(PrioritizedReplay, NStepReturns, BoundedActions):
     """M independent TD3 learners in lock-step on one engine: member m owns the envs [m n, (m + 1) n), n = N / M, has its own
     actor, exploration sigma, twin critics, targets, optimiser state, hyperparameters and replay ring, and every launch of a
     store or an update covers all members (StepEngine.td3_pop_*).  What a member computes is bit for bit what TD3Trainer
@@ -304,12 +411,15 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
 
     normalize_observations / normalize_rewards: every member has its own running normalisers (TD3Trainer's, per member: a
     member's statistics are bit for bit a single trainer's of its envs; the reward's discount is the member's own gamma); norm as
-    TD3Trainer's.  prioritized_replay: None, or PrioritizedReplay's dict, shared by all members (every member has its own tree)."""
+    TD3Trainer's.  prioritized_replay: None, or PrioritizedReplay's dict, shared by all members (every member has its own tree).
+
+    action_bounds / random_timesteps: TD3Trainer's, one pair of bounds shared by all members; the sigmas are then in units of the
+    half-range.  The members' rings fill together, so the warm-up ends for all at once."""
 
     SHARED = ("critic_hidden", "learning_starts", "updates_per_iteration")
 
     def __init__(self, engine, policies, sigmas, configs, horizon=10, agent_seeds=None, members=None, normalize_observations=False,
-                 normalize_rewards=False, norm=None, prioritized_replay=None):
+                 normalize_rewards=False, norm=None, prioritized_replay=None, action_bounds=None, random_timesteps=0):
         policies = [policies] if not isinstance(policies, (list, tuple)) else list(policies)
         norm = _norm_options(policies, normalize_observations, normalize_rewards, norm)
         self.normalize_observations, self.normalize_rewards = bool(normalize_observations), bool(normalize_rewards)
@@ -341,6 +451,7 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
         for n in norms[1:]:
             if (n is None) != (norms[0] is None) or (n is not None and not all(np.array_equal(a, b) for a, b in zip(n, norms[0]))):
                 raise ValueError("TD3PopulationTrainer: the critics' action normalisation is shared by all members")
+        self._bounds_check(action_bounds, random_timesteps, K, norms)
         self.engine, self.members, self.horizon = engine, members, int(horizon)
         self._templates = []
         for pol, sigma in zip(policies, sigmas):
@@ -352,10 +463,14 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
         engine.mlp_learners(members)
         for m in range(1, members):
             engine.mlp_set_learner(m, self._templates[m])
+        if self.action_bounds is not None:
+            engine.mlp_learners_set_bounds(*self.action_bounds)
         engine.rollout_enable(self.horizon, obs=True)
         engine.td3_pop_init(self.configs)
         for m in range(members):
             engine.td3_pop_set_critics(m, critics[m] if critics[m] is not None else random_critics(K, hidden, seeds[m], policies[0].frames), action_norm=norms[0] if m == 0 else None)
+        if self.action_bounds is not None:
+            engine.td3_pop_set_bounded(True)
         if self.normalize_observations or self.normalize_rewards:
             engine.td3_norm_init(observations=self.normalize_observations, rewards=self.normalize_rewards, per_member=True, **norm)
         self._prio_init(engine, prioritized_replay)
@@ -376,6 +491,8 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
         if reset:
             e.reset(seeds=reset_seeds)
         e.rollout_reset()
+        if self.action_bounds is not None:
+            self._explore_for(e.td3_pop_buffer(fetch=False)["written"])
         e.run_days("mlp", self.horizon if days is None else int(days), budget)
         e.td3_pop_store()
         if self.normalize_observations or self.normalize_rewards:
@@ -391,7 +508,7 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
         """an MLPPolicy holding one member's trained actor (its log_std the member's exploration's; under running observation
         normalisers its shift / scale are the member's current vectors)"""
         pol = policy_from_actor(self._templates[member], self.engine.td3_pop_state(member)["theta"])
-        return _with_vectors(pol, self.engine.td3_norm_state(member)) if self.normalize_observations else pol
+        return self._squashed(_with_vectors(pol, self.engine.td3_norm_state(member)) if self.normalize_observations else pol)
 
     def returns(self):
         """[M] float64: per member the mean over its envs of the recorded reward summed over the recorded days"""
@@ -401,7 +518,8 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
     def state(self, member, state=None):
         """member's state; `obs_history` (with MLPPolicy(frames > 1)) holds its own envs'"""
         return history_carry(self.engine,
-                             lambda u: self._nstep_state(lambda t: self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, t), member, u),
+                             lambda w: self._bounded_state(
+                                 lambda u: self._nstep_state(lambda t: self._prio_state(lambda s: self.engine.td3_pop_state(member, s), member, t), member, u), w),
                              state, member, self.engine.num_envs // self.members)
 
     def load_state(self, member, state):
@@ -412,4 +530,5 @@ class TD3PopulationTrainer(PrioritizedReplay, NStepReturns):
         return _norm_state(self.engine, member, state, self.engine.num_envs // self.members)
 
 
-__all__ = ["NStepReturns", "PrioritizedReplay", "TD3PopulationTrainer", "TD3Trainer", "td3", "random_critics", "actor_params", "policy_from_actor"]
+__all__ = ["BoundedActions", "NStepReturns", "PrioritizedReplay", "TD3PopulationTrainer", "TD3Trainer", "td3", "rllib_td3", "random_critics", "actor_params",
+           "policy_from_actor"]

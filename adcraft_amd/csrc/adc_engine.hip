@@ -166,6 +166,7 @@ using namespace adck;
 #include "parts/td3_api.inc"
 #include "parts/sac_api.inc"
 #include "parts/td3_pop_api.inc"
+#include "parts/td3_bounded_api.inc"
 #include "parts/sac_pop_api.inc"
 #include "parts/pbt_api.inc"
 #include "parts/per_api.inc"

@@ -1,7 +1,8 @@
 // adc_mlp.h - the law of the device-resident MLP policy: a fully connected policy network (and an optional value network) on
 // the flat observation, a diagonal Gaussian head, and the conversion of the sampled action into the env's cent bids.  Shared
 // by the device kernel (parts/kernel_mlp_policy.inc) and the host twin adc_mlp_act_host (adc_shims.cpp), so that CPU tests
-// run the very operations the GPU runs; tests/mlp_ref.py restates these comments in numpy, bit for bit.
+// run the very operations the GPU runs; tests/mlp_ref.py restates these comments in numpy, bit for bit (the bounded act:
+// adc_mlp_bounded_host / adc_mlp_unbox_host and tests/td3_bounded_ref.py).
 //
 // Every float32 value below is the result of ONE correctly rounded IEEE operation (build with -ffp-contract=off: no fused
 // multiply-add is meant anywhere in this file); "f64" marks the few places that compute in float64 and round once.
@@ -35,6 +36,19 @@
 //              e[a] = lo[a] + half[a] * (t + 1) (a sum, a product, a sum), half[a] = 0.5 * (hi[a] - lo[a]) formed once on the
 //              host.  The bid and the budget are taken from e as above.  The recorded action, the last act's action and the
 //              log-probability stay those of the unsquashed a; a deterministic act squashes the mean.
+//   bounded    (adc_engine_mlp_set_bounds; off by default; lo[a] < hi[a] finite, half[a] as for the squash) the deterministic actor
+//              squashed into the action box, TD3's act.  The action n[a] is in units of the box, in [-1, 1]:
+//                  t = tanh(mean[a])
+//                  explore (gaussian):  p = exp(ls[a]) * z; n = t + p; n = n < -1 ? -1 : n; n = n > 1 ? 1 : n    (z: the act's own draw)
+//                  deterministic:       n = t                                      (wins over either exploration mode)
+//                  explore (random):    u = unit_half24(w) of the very word w that z would have been made from (u = (k + 0.5) 2^-24,
+//                                       k = w >> 9); v = u + u; n = (v + v) - 1: exact, uniform on the 2^23 points (4k + 2) 2^-24 - 1,
+//                                       strictly inside (-1, 1); handed-in normals are not read.  The tick moves as for any act.
+//              The env is given e[a] = lo[a] + half[a] * (n + 1): the squash's three operations after its tanh (mlp_box); the bid
+//              and the budget are taken from e as above.  The recorded action and the last act's action are n; mean stays the raw
+//              mean; logp = +0; value as above.  A deterministic bounded act gives the env the bits the squash gives it.
+//              A teacher's action e (the float32 in the action buffers) is recorded as q = (e - lo[a]) * inv_half[a]; n = q - 1;
+//              n = n < -1 ? -1 : n; n = n > 1 ? 1 : n, inv_half[a] = 1 / half[a] formed once on the host (mlp_unbox).
 //
 // Observation history (adc_engine_mlp_init_frames, frames = H in 1..8; H = 1 is everything above, untouched).  D0 = 5K+2.
 //   row        D = H * D0; x[f * D0 + j], f < H, j < D0.  Frame 0 is the input above (mlp_obs_at, or zeros when the env's episode
@@ -157,12 +171,13 @@ ADC_HD float mlp_clamp_log_std(float ls, int clamp, float lo, float hi)
 }
 
 // the standard normal of action component a from the four words of draw(key, a / 4, ST_MLP, 0, tick)
-ADC_HD float mlp_normal(uint64_t key, uint32_t tick, int a)
+ADC_HD uint32_t mlp_word(uint64_t key, uint32_t tick, int a)
 {
     const U4 w = draw(key, (uint32_t)(a >> 2), ST_MLP, 0u, tick);
     const int h = a & 3;
-    return normal_from_word(h == 0 ? w.x : h == 1 ? w.y : h == 2 ? w.z : w.w);
+    return h == 0 ? w.x : h == 1 ? w.y : h == 2 ? w.z : w.w;
 }
+ADC_HD float mlp_normal(uint64_t key, uint32_t tick, int a) { return normal_from_word(mlp_word(key, tick, a)); }
 
 ADC_HD float mlp_sample(float mean, float ls, float z, int deterministic)
 {
@@ -205,12 +220,43 @@ ADC_HD float mlp_squash_half(float lo, float hi)
     const float d = hi - lo;
     return 0.5f * d;
 }
-ADC_HD float mlp_squash(float u, float lo, float half)
+// n in [-1, 1] (units of the box) to the env's units: lo + half * (n + 1)
+ADC_HD float mlp_box(float n, float lo, float half)
 {
-    const float t = mlp_tanh(u);
-    const float s = t + 1.0f;
+    const float s = n + 1.0f;
     const float p = half * s;
     return lo + p;
+}
+ADC_HD float mlp_squash(float u, float lo, float half) { return mlp_box(mlp_tanh(u), lo, half); }
+
+// ---- the bounded act (the header comment's law) ----------------------------------------------------------------------------------
+constexpr int kMlpGaussian = 0, kMlpRandom = 1;        // the act's exploration mode
+ADC_HD float mlp_clamp_unit(float n)
+{
+    n = n < -1.0f ? -1.0f : n;
+    return n > 1.0f ? 1.0f : n;
+}
+// the uniform of the warm-up from the word a normal would have been made from
+ADC_HD float mlp_uniform_unit(uint32_t w)
+{
+    const float u = unit_half24(w), v = u + u;
+    return (v + v) - 1.0f;
+}
+// w: mlp_word of the component (read in random mode alone); z: its normal (read in gaussian mode alone)
+ADC_HD float mlp_bounded_action(float mean, float ls, float z, uint32_t w, int deterministic, int explore)
+{
+    if (!deterministic && explore == kMlpRandom) return mlp_uniform_unit(w);
+    const float t = mlp_tanh(mean);
+    if (deterministic) return t;
+    const float p = mlp_exp(ls) * z;
+    return mlp_clamp_unit(t + p);
+}
+ADC_HD float mlp_inv_half(float half) { return 1.0f / half; }
+// a teacher's action in the env's units to the box's
+ADC_HD float mlp_unbox(float e, float lo, float inv_half)
+{
+    const float d = e - lo, q = d * inv_half;
+    return mlp_clamp_unit(q - 1.0f);
 }
 
 // element j of the flat observation row from the engine's output arrays of one env (what k_flatten_obs writes)

@@ -667,6 +667,32 @@ ADC_EXPORT int adc_mlp_squash_host(int32_t count, const float *u_a, const float 
     return ADC_OK;
 }
 
+ADC_EXPORT int adc_mlp_bounded_host(int32_t count, const float *mean_a, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,
+                                    int32_t mode, const float *lo_a, const float *hi_a, float *n_a, float *env_a)
+{
+    if (count < 1 || !mean_a || !log_std_a || !lo_a || !hi_a || mode < 0 || mode > 2) return ADC_EINVAL;
+    const int deterministic = mode == 1, explore = mode == 2 ? adc::kMlpRandom : adc::kMlpGaussian;
+    for (int a = 0; a < count; ++a) {
+        float z = 0.0f;
+        uint32_t w = 0u;
+        if (!deterministic) {
+            if (explore == adc::kMlpRandom) w = adc::mlp_word(agent_key, tick, a);
+            else z = normals_a ? normals_a[a] : adc::mlp_normal(agent_key, tick, a);
+        }
+        const float n = adc::mlp_bounded_action(mean_a[a], log_std_a[a], z, w, deterministic, explore);
+        if (n_a) n_a[a] = n;
+        if (env_a) env_a[a] = adc::mlp_box(n, lo_a[a], adc::mlp_squash_half(lo_a[a], hi_a[a]));
+    }
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_mlp_unbox_host(int32_t count, const float *e_a, const float *lo_a, const float *hi_a, float *n_a)
+{
+    if (count < 1 || !e_a || !lo_a || !hi_a || !n_a) return ADC_EINVAL;
+    for (int a = 0; a < count; ++a) n_a[a] = adc::mlp_unbox(e_a[a], lo_a[a], adc::mlp_inv_half(adc::mlp_squash_half(lo_a[a], hi_a[a])));
+    return ADC_OK;
+}
+
 ADC_EXPORT uint64_t adc_mlp_agent_key_host(uint64_t seed) { return adc::mlp_agent_key(seed); }
 ADC_EXPORT uint64_t adc_mlp_default_agent_key_host(uint64_t engine_seed, uint64_t global_env_id) { return adc::mlp_default_agent_key(engine_seed, global_env_id); }
 
@@ -1525,9 +1551,11 @@ ADC_EXPORT int adc_td3_batch_indices_host(uint64_t seed, int64_t update, int64_t
     return ADC_OK;
 }
 
-ADC_EXPORT int adc_td3_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
-                                   const float *theta_target_p, const float *psi_target_q, const float *shift_a, const float *scale_a, int32_t count,
-                                   const float *x2_bd, const float *r_b, const uint8_t *done_b, float *y_b)
+namespace {
+// adc_td3_target_host; bounded: under adc_td3.h "bounded" (shift_a and scale_a NULL)
+int td3_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
+                    const float *theta_target_p, const float *psi_target_q, const float *shift_a, const float *scale_a, int32_t count,
+                    const float *x2_bd, const float *r_b, const uint8_t *done_b, float *y_b, bool bounded)
 {
     adc::Td3Shape sh;
     if (!td3_host_shape(mlp, num_keywords, cfg, shift_a != nullptr, &sh)) return ADC_EINVAL;
@@ -1543,7 +1571,9 @@ ADC_EXPORT int adc_td3_target_host(const adc_mlp_config *mlp, int32_t num_keywor
         adc::td3_forward_host(sh.pol, sh.activation, theta_target_p, row.data(), yp.data());
         const float *mu = yp.data() + adc::td3_hidden(sh.pol);
         for (int a = 0; a < sh.A; ++a) {
-            const float ap = adc::td3_target_action(mu[a], adc::td3_noise(key, a, (uint32_t)b, (uint32_t)update), law);
+            const float n = adc::td3_noise(key, a, (uint32_t)b, (uint32_t)update);
+            if (bounded) { row[D + (size_t)a] = adc::td3_target_action(adc::mlp_tanh(mu[a]), n, adc::td3_law_bounded(law)); continue; }
+            const float ap = adc::td3_target_action(mu[a], n, law);
             row[D + (size_t)a] = adc::td3_action_norm(ap, shift_a, scale_a, a, sh.norm);
         }
         float q[2];
@@ -1554,6 +1584,22 @@ ADC_EXPORT int adc_td3_target_host(const adc_mlp_config *mlp, int32_t num_keywor
         y_b[b] = adc::td3_y(r_b[b], done_b[b], adc::td3_min(q[0], q[1]), law);
     }
     return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_td3_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
+                                   const float *theta_target_p, const float *psi_target_q, const float *shift_a, const float *scale_a, int32_t count,
+                                   const float *x2_bd, const float *r_b, const uint8_t *done_b, float *y_b)
+{
+    return td3_target_host(mlp, num_keywords, cfg, seed, update, theta_target_p, psi_target_q, shift_a, scale_a, count, x2_bd, r_b, done_b, y_b, false);
+}
+
+ADC_EXPORT int adc_td3_bounded_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
+                                           const float *theta_target_p, const float *psi_target_q, int32_t count, const float *x2_bd, const float *r_b,
+                                           const uint8_t *done_b, float *y_b)
+{
+    if (cfg && cfg->action_hi > cfg->action_lo) return ADC_EINVAL;          // (the box is [-1, 1])
+    return td3_target_host(mlp, num_keywords, cfg, seed, update, theta_target_p, psi_target_q, nullptr, nullptr, count, x2_bd, r_b, done_b, y_b, true);
 }
 
 ADC_EXPORT int adc_td3_critic_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *psi_q,
@@ -1590,9 +1636,10 @@ ADC_EXPORT int adc_td3_critic_grad_host(const adc_mlp_config *mlp, int32_t num_k
     return ADC_OK;
 }
 
-ADC_EXPORT int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p,
-                                       const float *psi_q, const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p,
-                                       double *sums2)
+namespace {
+// adc_td3_actor_grad_host; bounded: under adc_td3.h "bounded" (shift_a and scale_a NULL)
+int td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p, const float *psi_q,
+                        const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p, double *sums2, bool bounded)
 {
     adc::Td3Shape sh;
     if (!td3_host_shape(mlp, num_keywords, cfg, shift_a != nullptr, &sh)) return ADC_EINVAL;
@@ -1604,13 +1651,16 @@ ADC_EXPORT int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_ke
         float *y = ys.data() + s * po, *d = deltas.data() + s * po;
         std::copy(x_bd + s * D, x_bd + (s + 1) * D, row.begin());
         adc::td3_forward_host(sh.pol, sh.activation, theta_p, row.data(), y);
-        for (int a = 0; a < sh.A; ++a) row[D + (size_t)a] = adc::td3_action_norm(y[ph + (size_t)a], shift_a, scale_a, a, sh.norm);
+        for (int a = 0; a < sh.A; ++a)
+            row[D + (size_t)a] = bounded ? adc::mlp_tanh(y[ph + (size_t)a]) : adc::td3_action_norm(y[ph + (size_t)a], shift_a, scale_a, a, sh.norm);
         adc::td3_forward_host(sh.q, sh.activation, psi_q, row.data(), yq.data());
         qpi[s] = yq[nh];
         dq[nh] = 1.0f;
         adc::td3_backward_host(sh.q, sh.activation, psi_q, yq.data(), dq.data());
         adc::td3_input_delta_host(sh.q, psi_q, dq.data(), sh.D, sh.A, d + ph);
-        for (int a = 0; a < sh.A; ++a) d[ph + (size_t)a] = adc::td3_dmu(d[ph + (size_t)a], sh.norm ? scale_a[a] : 0.0f, sh.norm);
+        for (int a = 0; a < sh.A; ++a)
+            d[ph + (size_t)a] = bounded ? adc::td3_dmu_bounded(d[ph + (size_t)a], row[D + (size_t)a])
+                                        : adc::td3_dmu(d[ph + (size_t)a], sh.norm ? scale_a[a] : 0.0f, sh.norm);
         adc::td3_backward_host(sh.pol, sh.activation, theta_p, y, d);
     }
     td3_net_grad_host(sh.pol, count, x_bd, D, ys.data(), po, 0, deltas.data(), po, 0, grad_p);
@@ -1619,6 +1669,20 @@ ADC_EXPORT int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_ke
         sums2[1] = adc::pg_csum((int64_t)adc::td3_params(sh.pol), [&](double part, int64_t p) { return adc::pg_chain_mac(part, grad_p[p], grad_p[p]); });
     }
     return ADC_OK;
+}
+}  // namespace
+
+ADC_EXPORT int adc_td3_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p,
+                                       const float *psi_q, const float *shift_a, const float *scale_a, int32_t count, const float *x_bd, float *grad_p,
+                                       double *sums2)
+{
+    return td3_actor_grad_host(mlp, num_keywords, cfg, theta_p, psi_q, shift_a, scale_a, count, x_bd, grad_p, sums2, false);
+}
+
+ADC_EXPORT int adc_td3_bounded_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p,
+                                               const float *psi_q, int32_t count, const float *x_bd, float *grad_p, double *sums2)
+{
+    return td3_actor_grad_host(mlp, num_keywords, cfg, theta_p, psi_q, nullptr, nullptr, count, x_bd, grad_p, sums2, true);
 }
 
 ADC_EXPORT int adc_td3_polyak_host(float tau, int64_t n, const float *param_n, float *target_n)

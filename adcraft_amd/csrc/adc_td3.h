@@ -3,7 +3,8 @@
 // a device-resident replay ring filled from the rollout record.  Shared by the device kernels (parts/kernel_td3.inc) and the
 // host twins adc_td3_batch_indices_host / adc_td3_target_host / adc_td3_critic_grad_host / adc_td3_actor_grad_host /
 // adc_td3_polyak_host (adc_shims.cpp); tests/td3_ref.py restates these comments in numpy, bit for bit.  The n-step add-on's twins are
-// adc_replay_nstep_host / adc_td3_y_nstep_host / adc_sac_y_nstep_host, its restatement tests/nstep_ref.py.
+// adc_replay_nstep_host / adc_td3_y_nstep_host / adc_sac_y_nstep_host, its restatement tests/nstep_ref.py.  The bounded law's twins
+// are adc_td3_bounded_target_host / adc_td3_bounded_actor_grad_host, its restatement tests/td3_bounded_ref.py.
 //
 // Every float32 value below is the result of ONE correctly rounded IEEE operation (-ffp-contract=off); "f64" marks what is
 // computed in float64.  sum8, the layers, tanh and mix64 are adc_mlp.h's; the hidden deltas, csum, the norm clip and the Adam /
@@ -61,6 +62,11 @@
 //              Polyak for the target actor and both target critics: t = t + (tau * (p - t)) (a difference, a product, a sum).
 //   statistics f64 csum(B, f64(piece)) / f64(B): critic loss (the sum of the two critics' means), mean Q1, mean Q2, mean y, the
 //              actor loss -mean Q1(x, mu(x)) of the last actor step; both gradient norms before the clip.
+//   bounded    (adc_engine_td3_set_bounded; needs the bounded act of adc_mlp.h, no action normalisation and no action_lo / action_hi)
+//              the ring's action is the act's n in [-1, 1], and the critics' action input is n as stored: no tanh, no normalisation.
+//              target: t' = mlp_tanh(mu'[a]); a' = td3_target_action(t', n, law) with lo = -1 and hi = 1 in the law's place (sigma_t
+//              and c are in units of the half-range).  actor: t = mlp_tanh(mu[a]); critic 1 on [x | t]; din as above;
+//              w = 1 - (t * t) (a product, a difference); dmu[a] = -(din[D + a] * w).  Everything else is as above.
 //   Training draws from the td3 key's stages 16 and 17 alone: the envs' and the agents' streams do not move.
 #pragma once
 #include "adc_pg.h"
@@ -219,6 +225,18 @@ ADC_HD float td3_dmu(float din, float scale, int norm)
     if (!norm) return -din;
     const float p = din * scale;
     return -p;
+}
+// ... of the bounded actor: through t = tanh(mu)
+ADC_HD float td3_dmu_bounded(float din, float t)
+{
+    const float tt = t * t, w = 1.0f - tt, p = din * w;
+    return -p;
+}
+// the law a bounded learner's target action is formed under: the box is [-1, 1]
+ADC_HD Td3Law td3_law_bounded(Td3Law w)
+{
+    w.lo = -1.0f; w.hi = 1.0f;
+    return w;
 }
 ADC_HD float td3_polyak(float t, float p, float tau)
 {

@@ -96,6 +96,9 @@ struct adc_engine {
     bool mlp_norm_set = false, mlp_log_std_set = false;
     float *mlp_boot = nullptr;          // [N] adc_engine_mlp_bootstrap_value's device result
     float *mlp_sq = nullptr;            // [2][A] the squash's lo and half (adc_engine_mlp_set_squash); mp.sq_lo names it while squash is on
+    float *mlp_bd = nullptr;            // [3][A] the bounded act's lo, half and 1 / half (adc_engine_mlp_set_bounds); mp.bd_lo names it while it is on
+    std::vector<float> mlp_bd_host;     // [2][A] the lo and hi they were formed from (empty: off)
+    bool td3_bounded = false;           // adc_engine_td3_set_bounded / adc_engine_td3_pop_set_bounded: the learners' law is the bounded one
     std::vector<void *> mlp_allocs;     // weights, vectors and last-act arrays (re-allocated by every adc_engine_mlp_init)
     // a population of policies (adc_engine_mlp_population) and the evolution strategy over it (adc_engine_es_init; parts/kernel_es.inc)
     ParamLayout pl{};                   // the flat parameter order of the policy network (set by adc_engine_mlp_init)
@@ -2878,7 +2881,10 @@ void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode
     const size_t lds = mlp_lds_floats(p.D, p.P) * sizeof(float);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, lds, st, v, p, mode, replay_z, budget_override, d_bids, d_budget, rec, value_out); };
     const bool hist = p.hist != nullptr;
-    if (p.member && p.pop_stride == 0 && p.sq_lo) hist ? launch(k_mlp_policy<2, true, true>) : launch(k_mlp_policy<2, true>);
+    if (p.bd_lo && !(p.member && p.pop_stride != 0)) {          // (the bounded act: the single policy's or the learners'; never a population's)
+        if (p.member) hist ? launch(k_mlp_policy<2, false, true, true>) : launch(k_mlp_policy<2, false, false, true>);
+        else hist ? launch(k_mlp_policy<0, false, true, true>) : launch(k_mlp_policy<0, false, false, true>);
+    } else if (p.member && p.pop_stride == 0 && p.sq_lo) hist ? launch(k_mlp_policy<2, true, true>) : launch(k_mlp_policy<2, true>);
     else if (p.member && p.pop_stride == 0) hist ? launch(k_mlp_policy<2, false, true>) : launch(k_mlp_policy<2>);
     else if (p.member) hist ? launch(k_mlp_policy<1, false, true>) : launch(k_mlp_policy<1>);
     else if (p.sq_lo) hist ? launch(k_mlp_policy<0, true, true>) : launch(k_mlp_policy<0, true>);
@@ -3003,7 +3009,7 @@ void td3_drop(adc_engine *e)
     pbt_forget(e, ADC_PBT_TD3);
     pbt_forget(e, ADC_PBT_SAC);         // (a SAC population's scheduler: its arrays are among td3_allocs too)
     mlp_free(e, e->td3_allocs);
-    e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = false;
+    e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = e->td3_bounded = false;
     e->have_sac = false;                // (a soft actor-critic learner lives in the same fields, and ends where TD3 ends)
     e->sac_cell = nullptr;
     std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));
@@ -3028,7 +3034,11 @@ void learners_drop(adc_engine *e)
     if (e->have_td3_pop || e->have_sac_pop) td3_drop(e);
     mlp_free(e, e->lrn_allocs);
     // (while learners are active a squash is theirs, adc_engine_mlp_learners_set_squash: it goes with them)
-    if (e->lrn_M != 0) { e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; e->mp.sq_lo = e->mp.sq_half = nullptr; }
+    // (... and so are bounds, adc_engine_mlp_learners_set_bounds)
+    if (e->lrn_M != 0) {
+        e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; e->mp.sq_lo = e->mp.sq_half = nullptr;
+        e->mp.bd_lo = e->mp.bd_half = nullptr; e->mp.explore = adc::kMlpGaussian; e->mlp_bd_host.clear();
+    }
     e->lrn_M = e->lrn_n = 0;
     e->lrn_block = e->lrn_flat = nullptr; e->lrn_tab = nullptr; e->lrn_stride = 0;
 }
@@ -3143,8 +3153,9 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
         (rc = mlp_alloc(e, e->mlp_allocs, &p.mean, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.ls, N * A)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &p.action, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.logp, N)) ||
         (rc = mlp_alloc(e, e->mlp_allocs, &p.value, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_boot, N)) ||
-        (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_sq, (size_t)2 * A)))
-        return rc;                      // (squash is off after a re-initialisation: p.sq_lo is null)
+        (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_sq, (size_t)2 * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_bd, (size_t)3 * A)))
+        return rc;                      // (squash and bounds are off after a re-initialisation: p.sq_lo and p.bd_lo are null)
+    e->mlp_bd_host.clear();
     p.frames = frames;
     if (frames > 1 && ((rc = mlp_alloc(e, e->mlp_allocs, &p.hist, N * (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.last, N)) ||
                        (rc = mlp_alloc(e, e->mlp_allocs, &p.from, N))))
@@ -3253,6 +3264,7 @@ ADC_EXPORT int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const
     if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
     if (e->pop_M != 0) return fail(ADC_ESTATE, "the squashed action with a population active is not supported (adc_engine_mlp_population(0) first)");
     if (e->lrn_M != 0) return fail(ADC_ESTATE, "the squashed action with learners active is not supported (adc_engine_mlp_learners(0) first)");
+    if (lo_a && e->mp.bd_lo) return fail(ADC_ESTATE, "the squashed action together with the bounded act is not supported (adc_engine_mlp_set_bounds(NULL, NULL) first)");
     const int A = e->mp.A;
     std::vector<float> v((size_t)2 * A);
     for (int a = 0; lo_a && a < A; ++a) {
@@ -3276,6 +3288,7 @@ ADC_EXPORT int adc_engine_mlp_learners_set_squash(adc_engine *e, const float *lo
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
     if (e->lrn_M == 0) return fail(ADC_ESTATE, "the learners' squashed action needs learners (adc_engine_mlp_learners)");
+    if (lo_a && e->mp.bd_lo) return fail(ADC_ESTATE, "the squashed action together with the bounded act is not supported (adc_engine_mlp_learners_set_bounds(NULL, NULL) first)");
     if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
     const int A = e->mp.A;
     std::vector<float> v((size_t)2 * A);
@@ -3412,6 +3425,8 @@ ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const i
     // (the single policy's squash: the learners' own, on only while they are active, goes with them below)
     if (M > 0 && e->mp.sq_lo && e->lrn_M == 0)
         return fail(ADC_ESTATE, "a population with the squashed action on is not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
+    if (M > 0 && e->mp.bd_lo)
+        return fail(ADC_ESTATE, "a population with the bounded act on is not supported: it would need a log-probability (adc_engine_mlp_set_bounds(NULL, NULL) first)");
     std::vector<int32_t> map((size_t)N), count((size_t)M, 0);
     if (M > 0) {
         if (!member_of_env_n && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs when no member_of_env map is given");
@@ -3523,6 +3538,8 @@ ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
     // (the single policy's squash: the learners' own, on only while they are active, goes with them below)
     if (M > 0 && e->mp.sq_lo && e->lrn_M == 0)
         return fail(ADC_ESTATE, "learners with the squashed action on are not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
+    if (M > 0 && e->mp.bd_lo && e->lrn_M == 0)
+        return fail(ADC_ESTATE, "learners with the single policy's bounded act on are not supported (adc_engine_mlp_set_bounds(NULL, NULL) first)");
     ENGINE_GUARD(e);
     if (M == 0) { learners_drop(e); return ADC_OK; }
     // a member's block: the policy layers, the value layers, log_std, each starting on a 16-byte boundary; the flat order against it

@@ -34,8 +34,12 @@ int teach_day(adc_engine *e, int teacher, float budget)
     if ((rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
             const size_t row = (size_t)t * (size_t)e->v.N + (size_t)(d_budget - e->d_budget);
             const long long lanes = (long long)v.N * (K + 1);
-            hipLaunchKernelGGL(k_teach_record, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, v.N, K, d_bids, d_budget,
-                               e->ro_action + row * (size_t)(K + 1), e->ro_logp + row);
+            if (e->mp.bd_lo)            // (the bounded act: the teacher's action in units of the box)
+                hipLaunchKernelGGL(k_teach_record_bounded, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, v.N, K, d_bids, d_budget, e->mlp_bd,
+                                   e->mlp_bd + 2 * (size_t)(K + 1), e->ro_action + row * (size_t)(K + 1), e->ro_logp + row);
+            else
+                hipLaunchKernelGGL(k_teach_record, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, v.N, K, d_bids, d_budget,
+                                   e->ro_action + row * (size_t)(K + 1), e->ro_logp + row);
         })))
         return rc;
     // 4. the step and the outcome

@@ -53,6 +53,11 @@ struct MlpView {
     float *hist;                            // [N][frames][5K+2] raw frames, slot = episode day mod frames
     int32_t *last, *from;                   // [N] the episode day of the last act (-2: none); the first day whose frame is valid
     int frames;
+    // the bounded act (adc_engine_mlp_set_bounds; with learners adc_engine_mlp_learners_set_bounds; adc_mlp.h "bounded"): the action is
+    // n in [-1, 1] and the env is given lo + half * (n + 1).  null: off.  explore: adc::kMlpGaussian or adc::kMlpRandom (read by the
+    // bounded kernels alone)
+    const float *bd_lo, *bd_half;           // [A]
+    int explore;
 };
 
 // where one recorded day goes: the slot's rows of the view's first env (null: that field is off)
@@ -159,7 +164,9 @@ __device__ __forceinline__ float mlp_row_raw_at(const View &v, const float *__re
 // members); without it the three kernels compute what they computed before there was one.
 // kHist: the input row is the last `frames` raw observations (adc_mlp.h, observation history); mode 0 then writes this act's
 // raw frame 0 and the env's two validity words, mode 1 writes none of them.  Without it the kernels are the code they were.
-template <int kMembers, bool kSquash = false, bool kHist = false>
+// kBounded: the bounded act (adc_mlp.h "bounded"; kMembers 0 and 2, never with kSquash): the action and the record hold n, the env is
+// given its box image, logp is +0.  Without it the kernels are the code they were.
+template <int kMembers, bool kSquash = false, bool kHist = false, bool kBounded = false>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int mode, const float *__restrict__ replay_z,
                                                           float budget_override, float *__restrict__ bids, float *__restrict__ budgets,
                                                           MlpRecordSlot rec, float *__restrict__ value_out)
@@ -222,14 +229,26 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         const float mean = out[a];
         const float ls = adc::mlp_clamp_log_std(p.two_heads ? out[A + a] : (kMembers == 2 ? lm->log_std : p.log_std)[a], p.clamp, p.ls_lo, p.ls_hi);
         float z = 0.0f;
-        if (!p.deterministic) z = replay_z ? replay_z[(size_t)env * A + a] : adc::mlp_normal(key, tick, a);
-        const float act = adc::mlp_sample(mean, ls, z, p.deterministic);
+        float act;
+        if constexpr (kBounded) {
+            uint32_t w = 0u;
+            if (!p.deterministic) {
+                if (p.explore == adc::kMlpRandom) w = adc::mlp_word(key, tick, a);
+                else z = replay_z ? replay_z[(size_t)env * A + a] : adc::mlp_normal(key, tick, a);
+            }
+            act = adc::mlp_bounded_action(mean, ls, z, w, p.deterministic, p.explore);
+        } else {
+            if (!p.deterministic) z = replay_z ? replay_z[(size_t)env * A + a] : adc::mlp_normal(key, tick, a);
+            act = adc::mlp_sample(mean, ls, z, p.deterministic);
+        }
         const size_t oa = (size_t)env * A + a;
         p.mean[oa] = mean;
         p.ls[oa] = ls;
         p.action[oa] = act;
         if (rec.action) rec.action[oa] = act;
-        const float ea = kSquash ? adc::mlp_squash(act, p.sq_lo[a], p.sq_half[a]) : act;
+        float ea;
+        if constexpr (kBounded) ea = adc::mlp_box(act, p.bd_lo[a], p.bd_half[a]);
+        else ea = kSquash ? adc::mlp_squash(act, p.sq_lo[a], p.sq_half[a]) : act;
         if (a == 0) budgets[env] = adc::mlp_budget(ea, budget_override);
         else bids[(size_t)env * K + (a - 1)] = adc::mlp_bid(ea, p.clip_hi);
         out[a] = adc::mlp_logp_term(z, ls);
@@ -244,7 +263,7 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_policy(View v, MlpView p, int
         s = s + __shfl_xor(s, 2, 64);
         s = s + __shfl_xor(s, 4, 64);
         if (tid == 0) {
-            const float lp = adc::mlp_logp_finish(s, A);
+            const float lp = kBounded ? 0.0f : adc::mlp_logp_finish(s, A);
             p.logp[env] = lp;
             p.value[env] = s_value;
             if (rec.logp) { rec.logp[env] = lp; rec.value[env] = s_value; }

@@ -87,6 +87,9 @@ __device__ __forceinline__ float *td3_backward(const MlpNet &net, int activation
 }
 
 // dmu[a] = -(din[D + a] * a_scale[a]): the first critic layer's deltas carried to the action inputs, no activation derivative
+// kBounded: dmu[a] = -(din[D + a] * (1 - t[a]^2)) through the bounded actor's tanh, `scale` naming the row's t = tanh(mu) (adc_td3.h
+// "bounded"); without it the code is what it was
+template <bool kBounded = false>
 __device__ __forceinline__ void td3_input_back(const float *__restrict__ W, int j0, int n, int n_out, const float *dcur, float *dnew,
                                                const float *__restrict__ scale, int norm, float *__restrict__ g_out)
 {
@@ -104,7 +107,9 @@ __device__ __forceinline__ void td3_input_back(const float *__restrict__ W, int 
         s = s + __shfl_xor(s, 2, 64);
         s = s + __shfl_xor(s, 4, 64);           // adc::mlp_join8
         if (on && c == 0) {
-            const float d = adc::td3_dmu(s, norm ? scale[a] : 0.0f, norm);
+            float d;
+            if constexpr (kBounded) d = adc::td3_dmu_bounded(s, scale[a]);
+            else d = adc::td3_dmu(s, norm ? scale[a] : 0.0f, norm);
             dnew[a] = d;
             g_out[a] = d;
         }
@@ -218,7 +223,9 @@ __global__ void k_td3_indices(uint64_t key, uint32_t update, uint32_t size, int 
 // normaliser's vectors to member * p.n_stride and its multiplier to member * p.r_stride.  The solo kernels pass their view's
 // fields and the literal member 0, which folds those three away.
 
-// y of the element
+// y of the element.  kBounded (adc_td3.h "bounded"): the target actor's mean goes through tanh and the target action is clipped to
+// [-1, 1]; without it the code is what it was
+template <bool kBounded = false>
 __device__ __forceinline__ void td3_target_body(const Td3View &p, const MlpNet &pol_t, const MlpNet *q_t, const adc::Td3Law &law, uint64_t key,
                                                 const Td3Ring &ring, uint32_t member)
 {
@@ -242,9 +249,14 @@ __device__ __forceinline__ void td3_target_body(const Td3View &p, const MlpNet &
     __syncthreads();
     td3_forward(pol_t, sh.activation, row, yp, nullptr);
     const float *mu = yp + adc::td3_hidden(sh.pol);
-    for (int a = tid; a < A; a += kPgBlock) {
-        const float ap = adc::td3_target_action(mu[a], adc::td3_noise(key, a, b, p.update), law);
-        row[D + a] = adc::td3_action_norm(ap, p.a_shift, p.a_scale, a, sh.norm);
+    if constexpr (kBounded) {
+        const adc::Td3Law box = adc::td3_law_bounded(law);
+        for (int a = tid; a < A; a += kPgBlock) row[D + a] = adc::td3_target_action(adc::mlp_tanh(mu[a]), adc::td3_noise(key, a, b, p.update), box);
+    } else {
+        for (int a = tid; a < A; a += kPgBlock) {
+            const float ap = adc::td3_target_action(mu[a], adc::td3_noise(key, a, b, p.update), law);
+            row[D + a] = adc::td3_action_norm(ap, p.a_shift, p.a_scale, a, sh.norm);
+        }
     }
     __syncthreads();
     const int qlast = adc::td3_hidden(sh.q);
@@ -262,6 +274,10 @@ __device__ __forceinline__ void td3_target_body(const Td3View &p, const MlpNet &
 __global__ __launch_bounds__(kPgBlock) void k_td3_target(Td3View p)
 {
     td3_target_body(p, p.pol_t, p.q_t, p.law, p.key, p.ring, 0u);
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_target_bounded(Td3View p)
+{
+    td3_target_body<true>(p, p.pol_t, p.q_t, p.law, p.key, p.ring, 0u);
 }
 
 // forward and backward of both critics on batch element blockIdx.x.  This kernel and k_td3_pop_critic_sample stay restated: under
@@ -307,6 +323,8 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_critic_sample(Td3View p)
 }
 
 // the actor's forward, critic 1 on [x | norm(mu)], its backward through to the action inputs, the actor's backward
+// kBounded (adc_td3.h "bounded"): critic 1 on [x | tanh(mu)], and the tanh's derivative on the way back; without it the code is what it was
+template <bool kBounded = false>
 __device__ __forceinline__ void td3_actor_body(const Td3View &p, const MlpNet &pol, const MlpNet &q1, uint64_t key, const Td3Ring &ring,
                                                uint32_t member)
 {
@@ -327,7 +345,11 @@ __device__ __forceinline__ void td3_actor_body(const Td3View &p, const MlpNet &p
     float *acts = p.acts + at * (size_t)p.na, *deltas = p.deltas + at * (size_t)p.nd;
     td3_forward(pol, sh.activation, row, yp, acts);
     const int ph = adc::td3_hidden(sh.pol), qh = adc::td3_hidden(sh.q);
-    for (int a = tid; a < A; a += kPgBlock) row[D + a] = adc::td3_action_norm(yp[ph + a], p.a_shift, p.a_scale, a, sh.norm);
+    if constexpr (kBounded) {
+        for (int a = tid; a < A; a += kPgBlock) row[D + a] = adc::mlp_tanh(yp[ph + a]);
+    } else {
+        for (int a = tid; a < A; a += kPgBlock) row[D + a] = adc::td3_action_norm(yp[ph + a], p.a_shift, p.a_scale, a, sh.norm);
+    }
     __syncthreads();
     td3_forward(q1, sh.activation, row, yq, nullptr);
     if (tid == 0) {
@@ -337,12 +359,17 @@ __device__ __forceinline__ void td3_actor_body(const Td3View &p, const MlpNet &p
     __syncthreads();
     float *dq = td3_backward(q1, sh.activation, yq, d0, d1, nullptr, dump);
     float *dm = dq == d0 ? d1 : d0;
-    td3_input_back(q1.W[0], D, A, sh.q.n_out[0], dq, dm, p.a_scale, sh.norm, deltas + ph);
+    if constexpr (kBounded) td3_input_back<true>(q1.W[0], D, A, sh.q.n_out[0], dq, dm, row + D, 0, deltas + ph);
+    else td3_input_back(q1.W[0], D, A, sh.q.n_out[0], dq, dm, p.a_scale, sh.norm, deltas + ph);
     td3_backward(pol, sh.activation, yp, dm, dq, deltas, dump);
 }
 __global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample(Td3View p)
 {
     td3_actor_body(p, p.pol, p.q[0], p.key, p.ring, 0u);
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_actor_sample_bounded(Td3View p)
+{
+    td3_actor_body<true>(p, p.pol, p.q[0], p.key, p.ring, 0u);
 }
 
 // target = target + tau * (param - target) on the member's [Q] of the flat vectors, the targets' chain-major stores (L member 0's,

@@ -77,6 +77,11 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_target(Td3View p, const Td
     const Td3Member &me = mem[blockIdx.y];
     td3_target_body(p, me.pol_t, me.q_t, me.law, me.key, me.ring, blockIdx.y);
 }
+__global__ __launch_bounds__(kPgBlock) void k_td3_pop_target_bounded(Td3View p, const Td3Member *__restrict__ mem)
+{
+    const Td3Member &me = mem[blockIdx.y];
+    td3_target_body<true>(p, me.pol_t, me.q_t, me.law, me.key, me.ring, blockIdx.y);
+}
 
 // k_td3_critic_sample restated for member blockIdx.y (see there why the two do not share a body): forward and backward of both of
 // the member's critics on the element; the scratch rows start at member * gridDim.x, the normaliser's vectors at member * p.n_stride
@@ -124,6 +129,12 @@ __global__ __launch_bounds__(kPgBlock) void k_td3_pop_actor_sample(Td3View p, co
 {
     const Td3Member &me = mem[blockIdx.y];
     td3_actor_body(p, learners[blockIdx.y].net[0], me.q[0], me.key, me.ring, blockIdx.y);
+}
+__global__ __launch_bounds__(kPgBlock) void k_td3_pop_actor_sample_bounded(Td3View p, const MlpLearner *__restrict__ learners,
+                                                                           const Td3Member *__restrict__ mem)
+{
+    const Td3Member &me = mem[blockIdx.y];
+    td3_actor_body<true>(p, learners[blockIdx.y].net[0], me.q[0], me.key, me.ring, blockIdx.y);
 }
 
 // the (clipped) gradient's step of every member with its own clip scale and step constants: k_pg_pop_update on a Td3PopStep row

@@ -133,6 +133,19 @@ int off_set_critic_layer(adc_engine *e, int member, int32_t critic, int32_t laye
 }
 
 // ---- the replay ring -----------------------------------------------------------------------------------------------------------
+// the act and a TD3 learner agree on the action's units (adc_td3.h "bounded"): checked at every store and update of the TD3 front ends
+int td3_bounded_check(const adc_engine *e, const adc_td3_config *cfgs, size_t count)
+{
+    if (!e->td3_bounded) {
+        if (e->mp.bd_lo) return fail(ADC_ESTATE, "the act is bounded: its actions are in units of the box, and the learner must be bounded too (adc_engine_td3_set_bounded / adc_engine_td3_pop_set_bounded)");
+        return ADC_OK;
+    }
+    if (!e->mp.bd_lo) return fail(ADC_ESTATE, "bounded TD3 needs the bounded act (adc_engine_mlp_set_bounds, or adc_engine_mlp_learners_set_bounds for a population)");
+    for (size_t m = 0; m < count; ++m)
+        if (cfgs[m].action_hi > cfgs[m].action_lo)
+            return fail(ADC_ESTATE, "bounded TD3 with action_lo / action_hi set is not supported: the target action's box is [-1, 1]");
+    return ADC_OK;
+}
 int off_store_check(const adc_engine *e)
 {
     if (e->ro_t <= e->td3_stored_t) return fail(ADC_ESTATE, "no unstored day in the record (adc_engine_mlp_step / adc_engine_run_days with ADC_POLICY_MLP)");

@@ -57,7 +57,7 @@ int td3_one_update(adc_engine *e, bool stats_wanted, bool last, bool last_actor)
     p.na = 2 * nh; p.nd = 2 * no;
     int rc;
     if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
-    hipLaunchKernelGGL(k_td3_target, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+    hipLaunchKernelGGL(e->td3_bounded ? k_td3_target_bounded : k_td3_target, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     hipLaunchKernelGGL(k_td3_critic_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
     for (int i = 0; i < 2; ++i) td3_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
@@ -66,7 +66,7 @@ int td3_one_update(adc_engine *e, bool stats_wanted, bool last, bool last_actor)
     if ((rc = td3_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 5, c.critic_lr, e->td3_updates))) return rc;
     if ((e->td3_updates + 1) % c.policy_delay == 0) {
         p.na = ph; p.nd = po;
-        hipLaunchKernelGGL(k_td3_actor_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
+        hipLaunchKernelGGL(e->td3_bounded ? k_td3_actor_sample_bounded : k_td3_actor_sample, dim3((unsigned)B), dim3(kPgBlock), lds, e->stream, p);
         td3_wgrad_launch(e, sh.pol, DA, p.na, 0, p.nd, 0, 0, e->td3_P, B);
         HIP_TRY(hipGetLastError());
         if (stats_wanted && last_actor && (rc = td3_csum_launch(e, e->td3_pieces + adc::kTd3QPi, B, adc::kTd3Pieces, 1, 0, e->td3_sums + 8))) return rc;
@@ -86,6 +86,7 @@ int td3_one_update(adc_engine *e, bool stats_wanted, bool last, bool last_actor)
 int td3_action_norm_run(adc_engine *e, const float *shift_a, const float *scale_a)
 {
     if (!shift_a || !scale_a) return fail(ADC_EINVAL, "shift or scale is NULL");
+    if (e->td3_bounded) return fail(ADC_ESTATE, "bounded TD3 with an action normalisation is not supported: the critics read the act's action in [-1, 1] as stored");
     ENGINE_GUARD(e);
     HIP_TRY(hipMemcpyAsync(e->td3_a_shift, shift_a, (size_t)e->td3_shape.A * 4, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->td3_a_scale, scale_a, (size_t)e->td3_shape.A * 4, hipMemcpyHostToDevice, e->stream));
@@ -185,7 +186,7 @@ ADC_EXPORT int adc_engine_td3_store(adc_engine *e, int64_t *stored)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = td3_ready(e)) || (rc = td3_state_check(e)) || (rc = off_store_check(e))) return rc;
+    if ((rc = td3_ready(e)) || (rc = td3_state_check(e)) || (rc = td3_bounded_check(e, &e->td3_cfg, 1)) || (rc = off_store_check(e))) return rc;
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;        // (every env is the one learner's)
     // (raw rows under a running observation normaliser - TD3's set, e->tn: the last day's x' is the raw row an act would read now)
@@ -246,7 +247,7 @@ ADC_EXPORT int adc_engine_td3_update(adc_engine *e, int32_t updates, adc_td3_sta
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = td3_ready(e)) || (rc = td3_state_check(e)) ||
+    if ((rc = td3_ready(e)) || (rc = td3_state_check(e)) || (rc = td3_bounded_check(e, &e->td3_cfg, 1)) ||
         (rc = off_update_check(e, updates, false, "a critic layer has not been uploaded (adc_engine_td3_set_critic_layer)",
                                "the replay buffer is empty (adc_engine_td3_store)", 0xFFFFFFFFll)))
         return rc;

@@ -65,7 +65,7 @@ int tp_one_update(adc_engine *e, int index, bool stats_wanted, bool last, bool l
     p.na = 2 * nh; p.nd = 2 * no;
     int rc;
     if (e->per_live && (rc = per_sample_run(e, p.update))) return rc;
-    hipLaunchKernelGGL(k_td3_pop_target, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
+    hipLaunchKernelGGL(e->td3_bounded ? k_td3_pop_target_bounded : k_td3_pop_target, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
     hipLaunchKernelGGL(k_td3_pop_critic_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->tp_dmem);
     for (int i = 0; i < 2; ++i) tp_wgrad_launch(e, sh.q, DA, p.na, i * nh, p.nd, i * no, i * e->td3_Qc, 2 * e->td3_Qc, B);
     HIP_TRY(hipGetLastError());
@@ -74,7 +74,7 @@ int tp_one_update(adc_engine *e, int index, bool stats_wanted, bool last, bool l
     if ((rc = tp_step_run(e, kTd3Psi, e->td3_mom + 2, 2 * e->td3_Qc, B, stats_wanted && last, 5, 2 * index, any_clip))) return rc;
     if ((e->td3_updates + 1) % e->td3_cfg.policy_delay == 0) {
         p.na = ph; p.nd = po;
-        hipLaunchKernelGGL(k_td3_pop_actor_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem);
+        hipLaunchKernelGGL(e->td3_bounded ? k_td3_pop_actor_sample_bounded : k_td3_pop_actor_sample, grid, dim3(kPgBlock), lds, e->stream, p, e->lrn_tab, e->tp_dmem);
         tp_wgrad_launch(e, sh.pol, DA, p.na, 0, p.nd, 0, 0, e->td3_P, B);
         HIP_TRY(hipGetLastError());
         if (stats_wanted && last_actor && (rc = tp_csum_launch(e, e->td3_pieces + adc::kTd3QPi, B, (size_t)B, adc::kTd3Pieces, 1, 0, 8))) return rc;
@@ -186,7 +186,7 @@ ADC_EXPORT int adc_engine_td3_pop_store(adc_engine *e, int64_t *stored_per_membe
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = tp_ready(e)) || (rc = tp_state_check(e)) || (rc = off_store_check(e))) return rc;
+    if ((rc = tp_ready(e)) || (rc = tp_state_check(e)) || (rc = td3_bounded_check(e, e->tp_cfg.data(), e->tp_cfg.size())) || (rc = off_store_check(e))) return rc;
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->lrn_n;      // (a member's envs, not the engine's)
     // (raw rows under a running observation normaliser - TD3's set, e->tn)
@@ -243,7 +243,7 @@ ADC_EXPORT int adc_engine_td3_pop_update(adc_engine *e, int32_t updates, adc_td3
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
-    if ((rc = tp_ready(e)) || (rc = tp_state_check(e)) ||
+    if ((rc = tp_ready(e)) || (rc = tp_state_check(e)) || (rc = td3_bounded_check(e, e->tp_cfg.data(), e->tp_cfg.size())) ||
         (rc = off_update_check(e, updates, true, "a critic layer of a member has not been uploaded (adc_engine_td3_pop_set_critic_layer)",
                                "the replay buffer is empty (adc_engine_td3_pop_store)", 0xFFFFFFFFll)))
         return rc;

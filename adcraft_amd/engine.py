@@ -626,6 +626,46 @@ class StepEngine:
         lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
         check(self._lib.adc_engine_mlp_learners_set_squash(self._h, lo.ctypes.data, hi.ctypes.data))
 
+    EXPLORE_MODES = {"gaussian": 0, "random": 1}
+
+    def _set_bounds(self, fn, name, lo, hi):
+        if lo is None and hi is None:
+            check(fn(self._h, None, None))
+            return
+        if lo is None or hi is None:
+            raise ValueError(name + ": lo and hi, or neither")
+        a = self.num_keywords + 1
+        lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
+        check(fn(self._h, lo.ctypes.data, hi.ctypes.data))
+
+    def mlp_set_bounds(self, lo=None, hi=None):
+        """the bounded act (csrc/adc_mlp.h "bounded"), TD3's: with lo / hi [K + 1] (or scalars; flat action order: budget, bids)
+        the action is n = clamp(tanh(mean) + exp(log_std) z, -1, 1) in units of the box (tanh(mean) for a deterministic act), the
+        env is given lo + 0.5 (hi - lo) (n + 1), and the record and mlp_last hold n; logp is +0.  Both None: off"""
+        self._set_bounds(self._lib.adc_engine_mlp_set_bounds, "mlp_set_bounds", lo, hi)
+
+    def mlp_learners_set_bounds(self, lo=None, hi=None):
+        """mlp_set_bounds for learners (mlp_learners first): one pair of bounds shared by all members.  Both None: off.
+        mlp_learners, mlp_population and mlp_init drop it."""
+        self._set_bounds(self._lib.adc_engine_mlp_learners_set_bounds, "mlp_learners_set_bounds", lo, hi)
+
+    def mlp_set_explore(self, mode="gaussian"):
+        """the bounded act's exploration: "gaussian", or "random" - the warm-up: n uniform in (-1, 1) from the word the act's
+        normal would have been made from (the ticks move as ever; a deterministic act stays tanh(mean))"""
+        if mode not in self.EXPLORE_MODES:
+            raise ValueError(f"unknown exploration mode {mode!r}: 'gaussian' or 'random'")
+        check(self._lib.adc_engine_mlp_set_explore(self._h, self.EXPLORE_MODES[mode]))
+
+    def mlp_bounds(self):
+        """dict of bounded (bool), explore ("gaussian" / "random") and, while the bounds are on, lo and hi [K + 1]"""
+        a = self.num_keywords + 1
+        lo, hi, on, mode = np.zeros(a, np.float32), np.zeros(a, np.float32), C.c_int32(0), C.c_int32(0)
+        check(self._lib.adc_engine_mlp_get_bounds(self._h, lo.ctypes.data, hi.ctypes.data, C.byref(on), C.byref(mode)))
+        out = dict(bounded=bool(on.value), explore="random" if mode.value == 1 else "gaussian")
+        if on.value:
+            out.update(lo=lo, hi=hi)
+        return out
+
     def mlp_act(self, budget_override=0.0, replay_normals=None):
         z = None
         if replay_normals is not None:
@@ -1223,6 +1263,22 @@ class StepEngine:
         """critics: two lists of (W [n_in, n_out], b [n_out]) float32 layers on the D + A inputs; action_norm: (shift, scale) [A]
         for the critics' action inputs; sync_targets: the targets become copies of the actor and the critics"""
         self._off_set_critics("td3", None, critics, action_norm, sync_targets)
+
+    def td3_set_bounded(self, on=True):
+        """bounded TD3 (csrc/adc_td3.h "bounded"; mlp_set_bounds first, no action_norm, no action_lo / action_hi, an empty
+        ring): the critics read the act's n in [-1, 1], the target action is clamp(tanh(mu') + noise, -1, 1), the actor's
+        gradient goes through tanh(mu)"""
+        check(self._lib.adc_engine_td3_set_bounded(self._h, 1 if on else 0))
+
+    def td3_pop_set_bounded(self, on=True):
+        """td3_set_bounded for a population (mlp_learners_set_bounds first): all members at once"""
+        check(self._lib.adc_engine_td3_pop_set_bounded(self._h, 1 if on else 0))
+
+    def td3_bounded(self):
+        """whether the TD3 learner (or population) on this engine is bounded"""
+        on = C.c_int32(0)
+        check(self._lib.adc_engine_td3_get_bounded(self._h, C.byref(on)))
+        return bool(on.value)
 
     def td3_sync_targets(self):
         check(self._lib.adc_engine_td3_sync_targets(self._h))

@@ -13,6 +13,9 @@ section but for its grid cell; the table printed is each member's training-plane
 the stochastic collection policy), and the verdict compares the mean of the last five iterations with the mean of the first three.
 With --solo the same grid is then run as solo trainers, one engine after another, for the wall time of the sweep done the old way.
 
+--bounded LO,HI runs every member in the bounded mode (the actor squashed into the box, clipped noise, --random-timesteps of uniform
+warm-up; baselines/td3_trainer.py BoundedActions); the sigmas are then in units of the half-range.
+
 Usage: python examples/sweep_td3.py [--actor-lrs 1e-5,1e-3] [--critic-lrs 1e-3,3e-4] [--sigmas 0.1,0.2] [--envs-per-member 256]
                                     [--num-keywords 25] [--days 10] [--iterations 60] [--solo]
 """
@@ -65,7 +68,13 @@ def main():
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     ap.add_argument("--n-step", type=int, default=1, metavar="N",
                     help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
+    ap.add_argument("--bounded", default=None, metavar="LO,HI",
+                    help="the bounded mode (csrc/adc_td3.h \"bounded\"): every member's actor squashed into [LO, HI], shared by all members; "
+                         "--sigmas are then in units of the half-range")
+    ap.add_argument("--random-timesteps", type=int, default=0, metavar="N", help="with --bounded: a member's transitions collected uniformly from the box first")
     args = ap.parse_args()
+    if args.random_timesteps and not args.bounded:
+        ap.error("--random-timesteps needs --bounded")
     K, days, n = args.num_keywords, args.days, args.envs_per_member
     cells = list(itertools.product(*([float(x) for x in s.split(",")] for s in (args.actor_lrs, args.critic_lrs, args.sigmas))))
     M, N = len(cells), len(cells) * n
@@ -73,13 +82,20 @@ def main():
     norm = (np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32))
     policy = default_policy(K, hidden=HIDDEN, days=days, seed=0)
     configs = [dict(base_config(args), actor_lr=alr, critic_lr=clr, action_norm=norm, n_step=args.n_step) for alr, clr, _ in cells]
+    bounded = {}
+    if args.bounded:                    # (the box takes the place of the target's clamp and of the critics' action normalisation)
+        lo, hi = (float(v) for v in args.bounded.split(","))
+        bounded = dict(action_bounds=(lo, hi), random_timesteps=args.random_timesteps)
+        for c in configs:
+            for k in ("action_lo", "action_hi", "action_norm"):
+                del c[k]
     eng = StepEngine(N, K, max_days=days, seed=7)
     eng.set_all_params(np.concatenate([member_planes] * M, axis=1))
     eng.reset()
     prio = dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None
     trainer = td3_trainer.TD3PopulationTrainer(eng, policy, [s for _, _, s in cells], configs, horizon=days,
                                                normalize_observations=args.normalize_observations, normalize_rewards=args.normalize_rewards,
-                                               prioritized_replay=prio)
+                                               prioritized_replay=prio, **bounded)
     print(f"{M} TD3 learners x {n} envs x {K} keywords on one engine, {days} days and {args.updates} updates per iteration")
     print("member    " + " ".join(f"{m:>8d}" for m in range(M)))
     print("actor_lr  " + " ".join(f"{a:8.0e}" for a, _, _ in cells))
@@ -104,7 +120,7 @@ def main():
             e.set_all_params(member_planes)
             e.reset()
             tr = td3_trainer.TD3Trainer(e, policy, horizon=days, exploration_sigma=sigma, normalize_observations=args.normalize_observations,
-                                        normalize_rewards=args.normalize_rewards, prioritized_replay=prio, **cfg)
+                                        normalize_rewards=args.normalize_rewards, prioritized_replay=prio, **bounded, **cfg)
             c = curves_of(lambda seeds: tr.iteration(days, BUDGET, reset=True, reset_seeds=seeds),
                           lambda: [e.rollout_fetch()["reward"].astype(np.float64).sum(axis=0).mean()], args.iterations, n)
             solo_last.append(c[-5:].mean())

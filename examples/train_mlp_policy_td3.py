@@ -12,8 +12,14 @@ The actor's learning rate defaults to 1e-5, the one seen to learn at 256 envs x 
 TD3's usual 1e-3 the actor outruns the critics there and the return falls.  This script's own default shape has not been
 measured; lower --actor-lr further if the return falls.
 
+--bounded LO,HI trains the way RLlib's DDPG family and Stable-Baselines3 run TD3 (csrc/adc_td3.h "bounded"): the actor is
+tanh-squashed into the box [LO, HI] (one pair for the budget and every bid; give --budget-bounds for the budget's own), the noise
+is added to the squashed action and clipped to the box, --sigma and --warmup-sigma are in units of the half-range, and
+--random-timesteps transitions are first collected with actions drawn uniformly from the box.  The critics' action_lo /
+action_hi / action_norm of the default law are then not used.
+
 Usage: python examples/train_mlp_policy_td3.py [--iterations 100] [--num-envs 1024] [--num-keywords 100] [--warmup-iterations 2]
-                                               [--frames H]
+                                               [--frames H] [--bounded LO,HI [--random-timesteps N]]
 """
 import argparse
 import sys
@@ -35,6 +41,16 @@ def evaluate(name, policy, planes, days, budget):
     e = StepEngine(N, K, max_days=days, seed=70)
     e.set_all_params(planes)
     e.reset()
+    if hasattr(policy, "install"):          # (a bounded trainer's SquashedPolicy: the actor and its box, through the squashed act)
+        e.bid_curves_build(2048, None)
+        e.metrics_enable(True)
+        e.metrics_reset()
+        policy.install(e, deterministic=True)
+        e.run_days("mlp", days, budget)
+        ncp = e.metrics_akncp_ncp(float(days))[1]
+        ret = np.asarray(e.fetch()["cumulative_profit"], np.float64).mean()
+        e.close()
+        return ret, float(np.mean(ncp))
     r = run_baseline_episode(e, name, steps=days, budget=budget, default_rpc=1.0, mlp=policy, deterministic=True, per_keyword_sums=False)
     ret = np.asarray(e.fetch()["cumulative_profit"], np.float64).mean()
     e.close()
@@ -66,8 +82,14 @@ def main():
                     help="prioritised replay on the device (alpha 0.6, beta 0.4 annealed to 1 over the run); what it gains here has not been measured")
     ap.add_argument("--n-step", type=int, default=1, metavar="N",
                     help="n-step returns on the device (1: off; up to 16): a slot holds up to N days' discounted rewards and its own bootstrap discount; what it gains here has not been measured")
+    ap.add_argument("--bounded", default=None, metavar="LO,HI",
+                    help="the bounded mode: the actor squashed into [LO, HI]; --sigma / --warmup-sigma are then in units of the half-range")
+    ap.add_argument("--budget-bounds", default=None, metavar="LO,HI", help="with --bounded: the budget component's own box (default: the bids')")
+    ap.add_argument("--random-timesteps", type=int, default=0, metavar="N", help="with --bounded: transitions collected uniformly from the box first")
     args = ap.parse_args()
     N, K, days, budget = args.num_envs, args.num_keywords, args.days, 100000.0
+    if args.random_timesteps and not args.bounded:
+        ap.error("--random-timesteps needs --bounded")
     held_out = synthetic.implicit_keyword_planes(args.eval_envs, K, seed=999, mean_volume=args.mean_volume)
     zm = evaluate("zero_margin", None, held_out, days, budget)
     print(f"td3: {N} envs x {K} keywords, {days} days and {args.updates} updates per iteration; held-out: {args.eval_envs} envs")
@@ -79,6 +101,13 @@ def main():
                              learning_starts=args.warmup_iterations * days * N, updates_per_iteration=args.updates, batch_size=args.batch_size,
                              reward_scale=args.reward_scale, gamma=args.gamma, actor_lr=args.actor_lr, action_lo=0.01, action_hi=3.0,
                              action_norm=(np.full(K + 1, 0.5, np.float32), np.full(K + 1, 2.0, np.float32)))
+    if args.bounded:
+        lo, hi = (np.full(K + 1, float(v), np.float32) for v in args.bounded.split(","))
+        if args.budget_bounds:
+            lo[0], hi[0] = (float(v) for v in args.budget_bounds.split(","))
+        for k in ("action_lo", "action_hi", "action_norm"):
+            del config[k]
+        config.update(action_bounds=(lo, hi), random_timesteps=args.random_timesteps)
     trainer = td3_trainer.TD3Trainer(eng, default_policy(K, days=days, frames=args.frames), horizon=days, normalize_observations=args.normalize_observations,
                                      normalize_rewards=args.normalize_rewards,
                                      prioritized_replay=dict(alpha=0.6, beta=0.4, beta_final=1.0, beta_iterations=args.iterations) if args.prioritized_replay else None,

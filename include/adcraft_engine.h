@@ -539,6 +539,35 @@ int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const float *hi_
  * adc_engine_mlp_population (members > 0) stay refused while the single policy's squash is on: this is the learners' own entry
  * point. */
 int adc_engine_mlp_learners_set_squash(adc_engine *e, const float *lo_a, const float *hi_a);
+/* the bounded act (csrc/adc_mlp.h "bounded"): the deterministic actor squashed into the action box, as RLlib's DDPG family and
+ * Stable-Baselines3 run TD3.  With lo_a / hi_a [K + 1] (flat action order: budget, bids; finite, hi > lo) the action is
+ * n = clamp(tanh(mean) + exp(log_std) z, -1, 1) in units of the box - n = tanh(mean) for a deterministic act - the env is given
+ * e = lo + 0.5 (hi - lo) (n + 1), and the record, adc_engine_mlp_last's action and a trainer's ring hold n; mean stays the raw
+ * mean, the log-probability is +0, the ticks move as ever.  exp(log_std) is so in units of the half-range.  A deterministic
+ * bounded act gives the env the bits adc_engine_mlp_set_squash plus a deterministic act give it.  Both NULL: off (the exploration
+ * mode is back to gaussian), and the act is bit for bit what it was before the call; adc_engine_mlp_init turns it off.
+ * Refused with ADC_ESTATE: together with adc_engine_mlp_set_squash (either order), with a two-headed policy, while a population
+ * is active (adc_engine_mlp_population, and so the evolution strategy, is refused while it is on), while learners are active
+ * (theirs is adc_engine_mlp_learners_set_bounds: one pair shared by all members, accepted only while learners are active, gone
+ * with them), and while a TD3 ring holds transitions (their actions are in units of the bounds as they are).  While it is on,
+ * adc_engine_pg_*, adc_engine_im_* and adc_engine_sac_* are refused (they need a log-probability), and adc_engine_teach_days
+ * records the teacher's action e as n = clamp((e - lo) / half - 1, -1, 1) (the division as a product with 1 / half). */
+int adc_engine_mlp_set_bounds(adc_engine *e, const float *lo_a, const float *hi_a);
+int adc_engine_mlp_learners_set_bounds(adc_engine *e, const float *lo_a, const float *hi_a);
+/* the bounded act's exploration: ADC_MLP_EXPLORE_GAUSSIAN (the default) or ADC_MLP_EXPLORE_RANDOM, the warm-up: n uniform in
+ * (-1, 1) from the very word the normal would have been made from (handed-in normals are not read; the ticks move as ever; a
+ * deterministic act stays tanh(mean)).  ADC_MLP_EXPLORE_RANDOM needs the bounds (ADC_ESTATE otherwise). */
+enum adc_mlp_explore { ADC_MLP_EXPLORE_GAUSSIAN = 0, ADC_MLP_EXPLORE_RANDOM = 1 };
+int adc_engine_mlp_set_explore(adc_engine *e, int32_t mode);
+/* what the two calls above left: lo_a / hi_a [K + 1] (written only while the bounds are on; either may be NULL), *bounded 0 / 1,
+ * *explore - what a checkpoint has to carry */
+int adc_engine_mlp_get_bounds(adc_engine *e, float *lo_a, float *hi_a, int32_t *bounded, int32_t *explore);
+/* host twins (adc_shims.cpp), the code the device runs.  adc_mlp_bounded_host: the bounded act's head on `count` components from
+ * their raw means and log-stds: mode 0 explore (gaussian; normals_a, or NULL: drawn from agent_key / tick), 1 deterministic,
+ * 2 explore (random); n_a the action, env_a its box image (either may be NULL).  adc_mlp_unbox_host: a teacher's actions e_a to n_a */
+int adc_mlp_bounded_host(int32_t count, const float *mean_a, const float *log_std_a, const float *normals_a, uint64_t agent_key, uint32_t tick,
+                         int32_t mode, const float *lo_a, const float *hi_a, float *n_a, float *env_a);
+int adc_mlp_unbox_host(int32_t count, const float *e_a, const float *lo_a, const float *hi_a, float *n_a);
 /* act on the observation the last step left: actions into the engine's action buffers; replay_normals_na (may be NULL)
  * replaces the draws.  Every act moves the agents' ticks on by one.  Not recorded. */
 int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na);
@@ -933,6 +962,24 @@ int adc_engine_td3_init(adc_engine *e, const adc_td3_config *cfg);
 int adc_engine_td3_set_critic_layer(adc_engine *e, int32_t critic, int32_t layer, const float *weights_in_out, const float *bias_out);
 /* an[a] = (action[a] - shift_a[a]) * scale_a[a] for the critics' action inputs; without this call an = action */
 int adc_engine_td3_set_action_norm(adc_engine *e, const float *shift_a, const float *scale_a);
+/* bounded TD3 (csrc/adc_td3.h "bounded"), the learner of the bounded act (adc_engine_mlp_set_bounds): the critics read the ring's
+ * action n in [-1, 1] as stored, the target action is clamp(tanh(mu') + clipped noise, -1, 1) - target_noise and
+ * target_noise_clip are in units of the half-range, as Fujimoto's 0.2 / 0.5 are - and the actor's gradient goes through
+ * tanh(mu).  Everything else (store, batch, noise addresses, critic step, Polyak, statistics, prioritised replay, n-step returns,
+ * the running normalisers, the observation history) is what it was.  bounded = 0: back.  Refused with ADC_ESTATE: without the
+ * bounded act, with an action normalisation uploaded (and adc_engine_td3_set_action_norm is refused afterwards), with action_lo /
+ * action_hi set, and while the ring holds transitions.  adc_engine_td3_store and adc_engine_td3_update are refused while the
+ * act and the learner disagree.  A new adc_engine_td3_init starts unbounded.  adc_engine_td3_pop_set_bounded: the same for a
+ * population, all members at once; adc_engine_td3_get_bounded: of either. */
+int adc_engine_td3_set_bounded(adc_engine *e, int32_t bounded);
+int adc_engine_td3_pop_set_bounded(adc_engine *e, int32_t bounded);
+int adc_engine_td3_get_bounded(adc_engine *e, int32_t *bounded);
+/* host twins of the bounded law: adc_td3_target_host and adc_td3_actor_grad_host without an action normalisation, under it */
+int adc_td3_bounded_target_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, uint64_t seed, int64_t update,
+                                const float *theta_target_p, const float *psi_target_q, int32_t count, const float *x2_bd, const float *r_b,
+                                const uint8_t *done_b, float *y_b);
+int adc_td3_bounded_actor_grad_host(const adc_mlp_config *mlp, int32_t num_keywords, const adc_td3_config *cfg, const float *theta_p,
+                                    const float *psi_q, int32_t count, const float *x_bd, float *grad_p, double *sums2);
 /* the target actor and the target critics become copies of the actor and the critics */
 int adc_engine_td3_sync_targets(adc_engine *e);
 /* the record's days not yet stored, into the ring; *stored (may be NULL): the transitions appended */

@@ -72,7 +72,14 @@
 //        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
 //        the learner's discount, their moments, the merge, the multiplier, the GAE kernels under a multiplier and a clip (adc_rew_norm.h);
 //        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop and of kernel_sac / kernel_sac_pop (adc_sac_norm.h) normalise as they gather.
-//   parts/host_api.inc            the engine object and the extern "C" entry points.
+//   parts/host_api.inc            the engine object and the extern "C" entry points of the engine itself: the step, the tape, metrics,
+//                                 curves, the zero-margin and the interpolation agent.
+//   parts/mlp_core.inc            what the host files of the learned agent and the trainers' files share: owned allocations, the
+//                                 agent's view and launch, a day of the agent, the parameter stores and the flat order against them,
+//                                 the shared entry checks, the layer upload - and the lifetime chain (who ends when what ends).
+//   parts/mlp_api.inc             the entry points of the learned agent: the single policy, populations, learners, squash and bounds.
+//   parts/es_api.inc              the entry points of the evolution strategy over a policy population.
+//   parts/rollout_api.inc         the entry points of the rollout record and of the day loop (adc_engine_run_days).
 //   parts/pg_core.inc             what the three policy-gradient host files share: the members (a single learner is one member), the
 //                                 entry checks, the sample pass's view, the walk over the gradient's terms, the statistics' sums and
 //                                 means, the LDS refusal, the trainer's allocation, a member's state by its flat offset.
@@ -157,6 +164,10 @@ namespace adck {
 using namespace adck;
 
 #include "parts/host_api.inc"
+#include "parts/mlp_core.inc"
+#include "parts/mlp_api.inc"
+#include "parts/es_api.inc"
+#include "parts/rollout_api.inc"
 #include "parts/pg_core.inc"
 #include "parts/pg_kl_api.inc"
 #include "parts/pg_shuffle_api.inc"

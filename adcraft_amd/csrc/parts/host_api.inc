@@ -454,6 +454,7 @@ inline void materialize_drift(adc_engine *e)
 
 constexpr size_t kSmallBlockBytes = 256 * 1024;      // engines whose outputs fit use single-copy host I/O
 
+// (mlp_alloc of parts/mlp_core.inc is the learned agent's twin of this: owned by a list, and with a failure text of its own)
 template <typename T>
 int dev_alloc(adc_engine *e, T **p, size_t count)
 {
@@ -918,7 +919,7 @@ int fetch(adc_engine *e, adc_step_out *out, bool sync = true)
     return ADC_OK;
 }
 
-void norm_set_drop(adc_engine *e, NormSet &s);      // (defined below, next to mlp_free)
+void norm_set_drop(adc_engine *e, NormSet &s);      // (parts/mlp_core.inc, the head of the lifetime chain)
 
 }  // namespace
 
@@ -2829,1212 +2830,6 @@ ADC_EXPORT int adc_engine_interp_entries(adc_engine *e, int32_t *capacity, int32
     if (ave_cpc_cnk) HIP_TRY(hipMemcpyAsync(ave_cpc_cnk, p.cpc_ave, slots * 8, hipMemcpyDeviceToHost, e->stream));
     if (cpc_count_cnk) HIP_TRY(hipMemcpyAsync(cpc_count_cnk, p.cpc_cnt, slots * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-// ---- the MLP policy, one agent per env (parts/kernel_mlp_policy.inc) ------------------------------------------------------
-namespace {
-template <typename T>
-int mlp_alloc(adc_engine *e, std::vector<void *> &owner, T **p, size_t count)
-{
-    void *q = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), sizeof(T));
-    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(ADC_ENOMEM, "hipMalloc failed (MLP policy)"); }
-    owner.push_back(q);
-    if (hipMemsetAsync(q, 0, bytes, e->stream) != hipSuccess) return fail(ADC_EHIP, "hipMemsetAsync failed");
-    *p = static_cast<T *>(q);
-    return ADC_OK;
-}
-inline void mlp_free(adc_engine *e, std::vector<void *> &owner)
-{
-    if (!owner.empty()) (void)hipStreamSynchronize(e->stream);
-    for (void *q : owner) (void)hipFree(q);
-    owner.clear();
-}
-// a set of normalisers goes - with the policy, the learners, the trainer or the record it was set up for, or with the engine: the
-// policy kernel is back to the policy's own vectors, which hold what adc_engine_mlp_set_norm last wrote
-void norm_set_drop(adc_engine *e, NormSet &s)
-{
-    if (s.shared_shift) { e->mp.shift = s.shared_shift; e->mp.scale = s.shared_scale; e->mp.norm_stride = 0; }
-    mlp_free(e, s.allocs);
-    if (s.obs_part_grown) (void)hipFree(s.obs_part);
-    s = NormSet{};
-}
-// the agent's view of the env group that starts at env e0
-inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
-{
-    MlpView p = e->mp;
-    const size_t oa = e0 * (size_t)p.A;
-    p.key += e0; p.tick += e0; p.mean += oa; p.ls += oa; p.action += oa; p.logp += e0; p.value += e0;
-    if (p.member) p.member += e0;
-    if (p.hist) { p.hist += e0 * (size_t)p.D; p.last += e0; p.from += e0; }        // (an env's frames are D = frames * (5K+2) floats)
-    return p;
-}
-// the frames of the policy's input row (1 before adc_engine_mlp_init)
-inline int mlp_frames(const adc_engine *e) { return e->mp.frames > 1 ? e->mp.frames : 1; }
-void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode, const float *replay_z, float budget_override, float *d_bids,
-                       float *d_budget, const MlpRecordSlot &rec, float *value_out)
-{
-    // (three instantiations: without members the kernel is the single-policy code, untouched by the members' addressing; learners
-    // have no pop_stride; the squashed forms are instantiations of their own, and so are the ones with an observation history)
-    const dim3 grid((unsigned)v.N), block(kMlpBlock);
-    const size_t lds = mlp_lds_floats(p.D, p.P) * sizeof(float);
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, lds, st, v, p, mode, replay_z, budget_override, d_bids, d_budget, rec, value_out); };
-    const bool hist = p.hist != nullptr;
-    if (p.bd_lo && !(p.member && p.pop_stride != 0)) {          // (the bounded act: the single policy's or the learners'; never a population's)
-        if (p.member) hist ? launch(k_mlp_policy<2, false, true, true>) : launch(k_mlp_policy<2, false, false, true>);
-        else hist ? launch(k_mlp_policy<0, false, true, true>) : launch(k_mlp_policy<0, false, false, true>);
-    } else if (p.member && p.pop_stride == 0 && p.sq_lo) hist ? launch(k_mlp_policy<2, true, true>) : launch(k_mlp_policy<2, true>);
-    else if (p.member && p.pop_stride == 0) hist ? launch(k_mlp_policy<2, false, true>) : launch(k_mlp_policy<2>);
-    else if (p.member) hist ? launch(k_mlp_policy<1, false, true>) : launch(k_mlp_policy<1>);
-    else if (p.sq_lo) hist ? launch(k_mlp_policy<0, true, true>) : launch(k_mlp_policy<0, true>);
-    else hist ? launch(k_mlp_policy<0, false, true>) : launch(k_mlp_policy<0>);
-}
-int mlp_ready(const adc_engine *e)
-{
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    for (int l = 0; l < e->mp.pol.layers; ++l)
-        if (!e->mlp_layer_set[0][l]) return fail(ADC_ESTATE, "a policy layer has not been uploaded (adc_engine_mlp_set_layer)");
-    for (int l = 0; l < e->mp.val.layers; ++l)
-        if (!e->mlp_layer_set[1][l]) return fail(ADC_ESTATE, "a value layer has not been uploaded (adc_engine_mlp_set_layer)");
-    if (e->mlp_cfg.normalize && !e->mlp_norm_set) return fail(ADC_ESTATE, "the normalisation vectors have not been uploaded (adc_engine_mlp_set_norm)");
-    if (!e->mp.two_heads && !e->mlp_log_std_set) return fail(ADC_ESTATE, "log_std has not been uploaded (adc_engine_mlp_set_log_std)");
-    return ADC_OK;
-}
-inline bool rollout_room(const adc_engine *e, long long more) { return e->ro_T == 0 || (long long)e->ro_t + more <= (long long)e->ro_T; }
-// the record's slot t for the envs from e0 on (all null when `record` is false)
-inline MlpRecordSlot rollout_slot(const adc_engine *e, bool record, int t, size_t e0)
-{
-    MlpRecordSlot r{nullptr, nullptr, nullptr, nullptr, 0};
-    if (!record) return r;
-    r.raw_obs = (e->tn.obs.count || e->sn.obs.count) ? 1 : 0;
-    const size_t n = (size_t)e->v.N, row = (size_t)t * n + e0;
-    r.action = e->ro_action + row * (size_t)e->mp.A;
-    r.logp = e->ro_logp + row;
-    r.value = e->ro_value + row;
-    if (e->ro_obs) r.obs = e->ro_obs + row * (size_t)e->mp.D;
-    return r;
-}
-// act on the engine's last observation, group by group inside a chain; `record`: also into slot ro_t of the record
-// (the callers have checked mlp_ready)
-int mlp_act_chained(adc_engine *e, float budget_override, bool record)
-{
-    const int t = e->ro_t;
-    return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
-        const size_t e0 = (size_t)(d_budget - e->d_budget);       // (the group's first env)
-        mlp_launch_kernel(v, mlp_view_from(e, e0), st, 0, nullptr, budget_override, d_bids, d_budget, rollout_slot(e, record, t, e0), nullptr);
-    });
-}
-int mlp_record_outcome_chained(adc_engine *e)
-{
-    const int t = e->ro_t;
-    const int rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *, float *d_budget) {
-        const size_t row = (size_t)t * (size_t)e->v.N + (size_t)(d_budget - e->d_budget);
-        hipLaunchKernelGGL(k_mlp_record_outcome, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->ro_reward + row, e->ro_term + row,
-                           e->ro_trunc + row);
-    });
-    if (!rc) { e->ro_t += 1; e->pg_adv_ready = e->im_adv_ready = false; e->ro_moves = e->env_moves; }
-    return rc;
-}
-// the evolution strategy's side of a stepped day: every env's reward added to its return of the generation
-int es_accumulate_chained(adc_engine *e)
-{
-    const int rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *, float *d_budget) {
-        hipLaunchKernelGGL(k_es_accumulate, dim3((unsigned)((v.N + 255) / 256)), dim3(256), 0, st, v, e->es_return + (size_t)(d_budget - e->d_budget));
-    });
-    if (!rc) e->es_days += 1;
-    return rc;
-}
-// one day of the learned agent: act (+ the per-step ideal profit when asked for and curves are built), the env's step, the record
-int mlp_day(adc_engine *e, float budget_override, bool with_ideal)
-{
-    const bool record = e->ro_T > 0;
-    if (record && !rollout_room(e, 1)) return fail(ADC_EINVAL, "the rollout record is full: adc_engine_rollout_reset before recording another day");
-    int rc;
-    if (record && e->mp.deterministic) e->ro_deterministic = true;
-    // (a day recorded after the envs moved outside the record does not follow the unstored day before it)
-    if (record && (e->have_td3 || e->have_td3_pop || e->have_sac || e->have_sac_pop) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
-    if ((rc = mlp_act_chained(e, budget_override, record))) return rc;
-    if (with_ideal && e->have_curves && (rc = ideal_step_chained(e))) return rc;
-    if ((rc = launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true))) return rc;
-    if (record && (rc = mlp_record_outcome_chained(e))) return rc;
-    return e->es_accumulate ? es_accumulate_chained(e) : ADC_OK;
-}
-// the scheduler of population-based training goes with the population trainer it sits on
-void pbt_forget(adc_engine *e, int kind)
-{
-    if (!e->have_pbt || e->pbt_kind != kind) return;
-    e->have_pbt = false;
-    e->pbt_round = 0;
-    e->pbt_s.clear(); e->pbt_host_fit.clear(); e->pbt_pairs.clear();
-    e->pbt_ret = e->pbt_fit = nullptr; e->pbt_dpairs = nullptr;
-}
-// the KL add-on ends (its arrays stay the trainer's until that goes: a later adc_engine_pg_kl_init finds them)
-void kl_forget(adc_engine *e)
-{
-    e->kl_live = false;
-    e->kl_cfg.clear(); e->kl_coef.clear(); e->kl_stats.clear(); e->kl_mem.clear();
-}
-// the shuffled-minibatches add-on ends (its arrays stay the trainer's until that goes, as the KL add-on's do)
-void sh_forget(adc_engine *e)
-{
-    e->sh_live = e->sh_epoch_ready = false;
-    e->sh_mb = 0; e->sh_ns = 0;
-    e->sh_cfg.clear(); e->sh_mem.clear(); e->sh_stats.clear(); e->sh_evaluated.clear(); e->sh_last_count.clear();
-}
-// the policy-gradient trainer goes with the policy and the record it was sized for
-void pg_drop(adc_engine *e)
-{
-    norm_set_drop(e, e->rn);            // (it discounts by this trainer's gamma; the GAE kernels are back to k_pg_gae / k_pg_pop_gae)
-    pbt_forget(e, ADC_PBT_PG);
-    kl_forget(e);
-    e->kl_dmem = nullptr; e->kl_mean_old = e->kl_ls_old = e->kl_pieces = nullptr;      // (its arrays are among pg_allocs)
-    sh_forget(e);
-    e->sh_dmem = nullptr; e->sh_order = e->sh_rows = nullptr;
-    mlp_free(e, e->pg_allocs);
-    if (e->pq_host) (void)hipHostFree(e->pq_host);      // (the queued update's pinned twin; its device block was among pg_allocs)
-    e->pq_dev = e->pq_host = nullptr; e->pq_bytes = 0;
-    e->have_pg = e->have_pg_pop = e->pg_adv_ready = false;
-    e->have_im = e->im_adv_ready = false;       // (imitation lives on this trainer's theta and scratch)
-    e->pgp_cfg.clear(); e->pgp_steps.clear(); e->pgp_mem.clear(); e->pgp_host_sums.clear();
-    e->pgp_dmem = nullptr;
-}
-// ... and so does the off-policy trainer (its ring holds rows of that policy's input and action widths)
-void td3_drop(adc_engine *e)
-{
-    norm_set_drop(e, e->tn);            // (the record is back to network inputs)
-    norm_set_drop(e, e->sn);            // (the SAC learners' normalisers end where their trainer ends)
-    e->per_live = false; e->per = PerView{};    // (prioritised replay's arrays are among td3_allocs)
-    e->nstep_n = 0; e->nstep_gn = nullptr;      // (so are n-step returns'; a new trainer's rings start without gn)
-    pbt_forget(e, ADC_PBT_TD3);
-    pbt_forget(e, ADC_PBT_SAC);         // (a SAC population's scheduler: its arrays are among td3_allocs too)
-    mlp_free(e, e->td3_allocs);
-    e->have_td3 = e->have_td3_pop = e->td3_norm_set = e->td3_gap = e->td3_bounded = false;
-    e->have_sac = false;                // (a soft actor-critic learner lives in the same fields, and ends where TD3 ends)
-    e->sac_cell = nullptr;
-    std::memset(e->td3_critic_set, 0, sizeof(e->td3_critic_set));
-    e->td3_updates = e->td3_actor_steps = e->td3_written = 0;
-    e->td3_stored_t = 0;
-    e->tp_cfg.clear(); e->tp_mem.clear(); e->tp_steps.clear(); e->tp_host_sums.clear(); e->tp_critic_set.clear();
-    e->tp_dmem = nullptr; e->tp_dsteps = nullptr;
-    e->have_sac_pop = false;            // (a SAC population lives in the TD3 population's fields)
-    e->sp_cfg.clear(); e->sp_mem.clear();
-    e->sp_dmem = nullptr; e->sp_cells = nullptr;
-}
-// learners and the population trainer over them go with the policy they belong to (the engine is back to the centre policy)
-void learners_drop(adc_engine *e)
-{
-    norm_set_drop(e, e->on);
-    norm_set_drop(e, e->rn);
-    kl_forget(e);                       // (as the reward normaliser: a solo trainer survives, its add-ons do not)
-    sh_forget(e);
-    // (a solo TD3 trainer survives learners and a population, refused while they are active; so do its normalisers, or its raw ring
-    //  would be sampled without them afterwards.  A TD3 population's go with it, below)
-    if (e->have_pg_pop) pg_drop(e);
-    if (e->have_td3_pop || e->have_sac_pop) td3_drop(e);
-    mlp_free(e, e->lrn_allocs);
-    // (while learners are active a squash is theirs, adc_engine_mlp_learners_set_squash: it goes with them)
-    // (... and so are bounds, adc_engine_mlp_learners_set_bounds)
-    if (e->lrn_M != 0) {
-        e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0; e->mp.sq_lo = e->mp.sq_half = nullptr;
-        e->mp.bd_lo = e->mp.bd_half = nullptr; e->mp.explore = adc::kMlpGaussian; e->mlp_bd_host.clear();
-    }
-    e->lrn_M = e->lrn_n = 0;
-    e->lrn_block = e->lrn_flat = nullptr; e->lrn_tab = nullptr; e->lrn_stride = 0;
-}
-// a population and the strategy over it go with the policy they belong to
-void population_drop(adc_engine *e)
-{
-    mlp_free(e, e->pop_allocs);
-    mlp_free(e, e->es_allocs);
-    e->pop_M = 0;
-    e->pop_map.clear();
-    e->pop_count.clear();
-    e->mp.member = nullptr; e->mp.pop = nullptr; e->mp.pop_stride = 0;
-    e->have_es = e->es_accumulate = false;
-    e->es_days = 0;
-}
-inline unsigned es_quad_blocks(int P) { return (unsigned)(((P + 3) / 4 + kEsBlock - 1) / kEsBlock); }
-ParamStore centre_store(const adc_engine *e)
-{
-    ParamStore s{};
-    for (int l = 0; l < e->mp.pol.layers; ++l) { s.W[l] = const_cast<float *>(e->mp.pol.W[l]); s.b[l] = const_cast<float *>(e->mp.pol.b[l]); }
-    return s;
-}
-ParamStore member_store(const adc_engine *e, int member)
-{
-    ParamStore s{};
-    float *base = const_cast<float *>(e->mp.pop) + (size_t)member * e->mp.pop_stride;
-    for (int l = 0; l < e->pl.layers; ++l) { s.W[l] = base + e->pl.offW[l]; s.b[l] = base + e->pl.offb[l]; }
-    return s;
-}
-// the store's parameters in the flat order, to the host
-int params_fetch(adc_engine *e, const ParamStore &s, float *flat)
-{
-    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, s, e->mlp_flat, 1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(flat, e->mlp_flat, (size_t)e->pl.P * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n)
-{
-    return adc_engine_mlp_init_frames(e, cfg, seeds_n, 1);
-}
-
-ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t frames)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const char *why = nullptr;
-    if (adc_mlp_config_check(cfg, e->v.K, &why) != ADC_OK) return fail(ADC_EINVAL, why);
-    if (frames < 1 || frames > adc::kMlpMaxFrames) return fail(ADC_EINVAL, "frames: 1 to 8");
-    const int K = e->v.K, A = K + 1, D0 = 5 * K + 2, D = frames * D0;
-    const int P = cfg->policy_widths[cfg->n_policy_layers - 1];
-    if (mlp_lds_floats(D0, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
-    if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u)
-        return fail(ADC_EINVAL, "frames: the stacked input row is too large for the MLP policy (LDS); fewer frames fit");
-    ENGINE_GUARD(e);
-    population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
-    learners_drop(e);
-    pg_drop(e);
-    td3_drop(e);
-    mlp_free(e, e->mlp_allocs);
-    e->have_mlp = false;
-    MlpView p{};
-    const size_t N = e->v.N;
-    int rc;
-    auto net = [&](MlpNet &n, int layers, const int32_t *widths) {
-        n.layers = layers;
-        int n_in = D;
-        for (int l = 0; l < layers; ++l) {
-            float *w = nullptr, *b = nullptr;
-            if ((rc = mlp_alloc(e, e->mlp_allocs, &w, adc::mlp_weight_count(n_in, widths[l]))) || (rc = mlp_alloc(e, e->mlp_allocs, &b, (size_t)widths[l])))
-                return rc;
-            n.W[l] = w; n.b[l] = b; n.n_in[l] = n_in; n.n_out[l] = widths[l];
-            n_in = widths[l];
-        }
-        return (int)ADC_OK;
-    };
-    if ((rc = net(p.pol, cfg->n_policy_layers, cfg->policy_widths)) || (rc = net(p.val, cfg->n_value_layers, cfg->value_widths))) return rc;
-    float *shift = nullptr, *scale = nullptr, *log_std = nullptr;
-    if (cfg->normalize) {
-        if ((rc = mlp_alloc(e, e->mlp_allocs, &shift, (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &scale, (size_t)D))) return rc;
-    }
-    if ((rc = mlp_alloc(e, e->mlp_allocs, &log_std, (size_t)A))) return rc;
-    p.shift = shift; p.scale = scale; p.log_std = log_std;
-    p.activation = cfg->activation == ADC_MLP_TANH ? adc::kMlpTanh : adc::kMlpRelu;
-    p.two_heads = P == 2 * A;
-    p.clamp = cfg->clamp_log_std != 0; p.ls_lo = cfg->log_std_lo; p.ls_hi = cfg->log_std_hi;
-    p.clip_hi = cfg->bid_clip_hi;
-    p.deterministic = cfg->deterministic != 0;
-    p.A = A; p.D = D; p.P = P;
-    // the flat parameter order, and a member's block: its layers one after the other, each starting on a 16-byte boundary
-    ParamLayout pl{};
-    pl.layers = p.pol.layers;
-    {
-        size_t off = 0;
-        int flat = 0;
-        for (int l = 0; l < pl.layers; ++l) {
-            pl.n_in[l] = p.pol.n_in[l]; pl.n_out[l] = p.pol.n_out[l];
-            pl.flat0[l] = flat;
-            flat += pl.n_in[l] * pl.n_out[l] + pl.n_out[l];
-            pl.offW[l] = (uint32_t)off; off += adc::mlp_weight_count(pl.n_in[l], pl.n_out[l]);
-            pl.offb[l] = (uint32_t)off; off += ((size_t)pl.n_out[l] + 3u) & ~(size_t)3u;
-            p.pop_offW[l] = pl.offW[l]; p.pop_offb[l] = pl.offb[l];
-        }
-        pl.P = flat;
-        pl.stride = (uint32_t)off;
-        e->pl = pl;
-        if ((rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_flat, (size_t)flat))) return rc;
-    }
-    if ((rc = mlp_alloc(e, e->mlp_allocs, &p.key, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.tick, N)) ||
-        (rc = mlp_alloc(e, e->mlp_allocs, &p.mean, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.ls, N * A)) ||
-        (rc = mlp_alloc(e, e->mlp_allocs, &p.action, N * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.logp, N)) ||
-        (rc = mlp_alloc(e, e->mlp_allocs, &p.value, N)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_boot, N)) ||
-        (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_sq, (size_t)2 * A)) || (rc = mlp_alloc(e, e->mlp_allocs, &e->mlp_bd, (size_t)3 * A)))
-        return rc;                      // (squash and bounds are off after a re-initialisation: p.sq_lo and p.bd_lo are null)
-    e->mlp_bd_host.clear();
-    p.frames = frames;
-    if (frames > 1 && ((rc = mlp_alloc(e, e->mlp_allocs, &p.hist, N * (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.last, N)) ||
-                       (rc = mlp_alloc(e, e->mlp_allocs, &p.from, N))))
-        return rc;
-    e->mp = p;
-    e->mlp_cfg = *cfg;
-    std::memset(e->mlp_layer_set, 0, sizeof(e->mlp_layer_set));
-    e->mlp_norm_set = e->mlp_log_std_set = false;
-    uint64_t *d_seeds = nullptr;
-    hipError_t err = hipSuccess;
-    if (seeds_n) {
-        HIP_TRY(hipMalloc((void **)&d_seeds, N * 8));
-        err = hipMemcpyAsync(d_seeds, seeds_n, N * 8, hipMemcpyHostToDevice, e->stream);
-    }
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_mlp_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, e->mp, (int)N, d_seeds, e->cfg.seed, e->cfg.env_id_base);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess && e->mp.hist) {          // no env has acted
-        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, nullptr, e->mp.last);
-        err = hipGetLastError();
-    }
-    const hipError_t err2 = hipStreamSynchronize(e->stream);
-    (void)hipFree(d_seeds);
-    HIP_TRY(err);
-    HIP_TRY(err2);
-    e->have_mlp = true;
-    // (a record sized for another action width does not survive a re-initialisation)
-    if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; e->ro_teacher = 0; }
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (network != 0 && network != 1) return fail(ADC_EINVAL, "network: 0 (policy) or 1 (value)");
-    const MlpNet &n = network == 0 ? e->mp.pol : e->mp.val;
-    if (layer < 0 || layer >= n.layers) return fail(ADC_EINVAL, "no such layer");
-    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
-    ENGINE_GUARD(e);
-    const int n_in = n.n_in[layer], n_out = n.n_out[layer];
-    std::vector<float> w(adc::mlp_weight_count(n_in, n_out), 0.0f);
-    for (int j = 0; j < n_in; ++j)
-        for (int h = 0; h < n_out; ++h) w[adc::mlp_weight_index(j, h, n_out)] = weights_in_out[(size_t)j * n_out + h];
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(n.W[layer]), w.data(), w.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(n.b[layer]), bias_out, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->mlp_layer_set[network][layer] = true;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_norm(adc_engine *e, const float *shift_d, const float *scale_d)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (!e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
-    if (!shift_d || !scale_d) return fail(ADC_EINVAL, "shift or scale is NULL");
-    ENGINE_GUARD(e);
-    for (const NormSet *s : {&e->on, &e->tn, &e->sn}) {
-        if (!s->shared_shift) continue;
-        // per-member vectors are in force: every member's row, and the policy's own vectors (the running moments are not touched)
-        const size_t D = (size_t)e->mp.D;
-        for (int m = 0; m < s->M; ++m) {
-            HIP_TRY(hipMemcpyAsync(s->obs.shift + (size_t)m * D, shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(s->obs.scale + (size_t)m * D, scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        }
-        HIP_TRY(hipMemcpyAsync(const_cast<float *>(s->shared_shift), shift_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(const_cast<float *>(s->shared_scale), scale_d, D * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return ADC_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.shift), shift_d, (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.scale), scale_d, (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->mlp_norm_set = true;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_log_std(adc_engine *e, const float *log_std_a)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (!log_std_a) return fail(ADC_EINVAL, "log_std is NULL");
-    ENGINE_GUARD(e);
-    HIP_TRY(hipMemcpyAsync(const_cast<float *>(e->mp.log_std), log_std_a, (size_t)e->mp.A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->mlp_log_std_set = true;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_deterministic(adc_engine *e, int32_t deterministic)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    ENGINE_GUARD(e);
-    e->mp.deterministic = deterministic != 0;
-    e->mlp_cfg.deterministic = deterministic != 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_squash(adc_engine *e, const float *lo_a, const float *hi_a)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
-    if (e->pop_M != 0) return fail(ADC_ESTATE, "the squashed action with a population active is not supported (adc_engine_mlp_population(0) first)");
-    if (e->lrn_M != 0) return fail(ADC_ESTATE, "the squashed action with learners active is not supported (adc_engine_mlp_learners(0) first)");
-    if (lo_a && e->mp.bd_lo) return fail(ADC_ESTATE, "the squashed action together with the bounded act is not supported (adc_engine_mlp_set_bounds(NULL, NULL) first)");
-    const int A = e->mp.A;
-    std::vector<float> v((size_t)2 * A);
-    for (int a = 0; lo_a && a < A; ++a) {
-        if (!std::isfinite(lo_a[a]) || !std::isfinite(hi_a[a]) || !(hi_a[a] > lo_a[a])) return fail(ADC_EINVAL, "squash bounds: finite, hi > lo");
-        v[(size_t)a] = lo_a[a];
-        v[(size_t)(A + a)] = adc::mlp_squash_half(lo_a[a], hi_a[a]);
-        if (!std::isfinite(v[(size_t)(A + a)])) return fail(ADC_EINVAL, "squash bounds: hi - lo overflows");
-    }
-    ENGINE_GUARD(e);
-    if (!lo_a) { e->mp.sq_lo = e->mp.sq_half = nullptr; return ADC_OK; }
-    HIP_TRY(hipMemcpyAsync(e->mlp_sq, v.data(), v.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->mp.sq_lo = e->mlp_sq; e->mp.sq_half = e->mlp_sq + A;
-    return ADC_OK;
-}
-
-// the learners' squash: one pair of bounds for all members (k_mlp_policy<2, true>).  It lives in the single policy's fields, which
-// are free while learners are active (adc_engine_mlp_set_squash is refused then), and goes with the learners (learners_drop)
-ADC_EXPORT int adc_engine_mlp_learners_set_squash(adc_engine *e, const float *lo_a, const float *hi_a)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (e->lrn_M == 0) return fail(ADC_ESTATE, "the learners' squashed action needs learners (adc_engine_mlp_learners)");
-    if (lo_a && e->mp.bd_lo) return fail(ADC_ESTATE, "the squashed action together with the bounded act is not supported (adc_engine_mlp_learners_set_bounds(NULL, NULL) first)");
-    if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
-    const int A = e->mp.A;
-    std::vector<float> v((size_t)2 * A);
-    for (int a = 0; lo_a && a < A; ++a) {
-        if (!std::isfinite(lo_a[a]) || !std::isfinite(hi_a[a]) || !(hi_a[a] > lo_a[a])) return fail(ADC_EINVAL, "squash bounds: finite, hi > lo");
-        v[(size_t)a] = lo_a[a];
-        v[(size_t)(A + a)] = adc::mlp_squash_half(lo_a[a], hi_a[a]);
-        if (!std::isfinite(v[(size_t)(A + a)])) return fail(ADC_EINVAL, "squash bounds: hi - lo overflows");
-    }
-    ENGINE_GUARD(e);
-    if (!lo_a) { e->mp.sq_lo = e->mp.sq_half = nullptr; return ADC_OK; }
-    HIP_TRY(hipMemcpyAsync(e->mlp_sq, v.data(), v.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->mp.sq_lo = e->mlp_sq; e->mp.sq_half = e->mlp_sq + A;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_act(adc_engine *e, float budget_override, const float *replay_normals_na)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = mlp_ready(e)) return rc;
-    ENGINE_GUARD(e);
-    float *d_z = nullptr;
-    const size_t na = (size_t)e->v.N * (size_t)e->mp.A;
-    hipError_t err = hipSuccess;
-    if (replay_normals_na) {
-        if (hipMalloc((void **)&d_z, na * 4) != hipSuccess) { (void)hipGetLastError(); return fail(ADC_ENOMEM, "hipMalloc failed"); }
-        err = hipMemcpyAsync(d_z, replay_normals_na, na * 4, hipMemcpyHostToDevice, e->stream);
-    }
-    if (err == hipSuccess) {
-        mlp_launch_kernel(e->v, e->mp, e->stream, 0, d_z, budget_override, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, nullptr);
-        err = hipGetLastError();
-    }
-    const hipError_t e2 = hipStreamSynchronize(e->stream);
-    (void)hipFree(d_z);
-    HIP_TRY(err);
-    HIP_TRY(e2);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_step(adc_engine *e, float budget_override)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
-    if (int rc = mlp_ready(e)) return rc;
-    ENGINE_GUARD_STEP(e);
-    return mlp_day(e, budget_override, /* with_ideal = */ false);
-}
-
-ADC_EXPORT int adc_engine_mlp_last(adc_engine *e, float *mean_na, float *log_std_na, float *action_na, float *logp_n, float *value_n)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    const size_t n = (size_t)e->v.N, na = n * (size_t)e->mp.A;
-    if (mean_na) HIP_TRY(hipMemcpyAsync(mean_na, e->mp.mean, na * 4, hipMemcpyDeviceToHost, e->stream));
-    if (log_std_na) HIP_TRY(hipMemcpyAsync(log_std_na, e->mp.ls, na * 4, hipMemcpyDeviceToHost, e->stream));
-    if (action_na) HIP_TRY(hipMemcpyAsync(action_na, e->mp.action, na * 4, hipMemcpyDeviceToHost, e->stream));
-    if (logp_n) HIP_TRY(hipMemcpyAsync(logp_n, e->mp.logp, n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (value_n) HIP_TRY(hipMemcpyAsync(value_n, e->mp.value, n * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_agent_state(adc_engine *e, uint64_t *keys_n, uint32_t *ticks_n)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (keys_n) HIP_TRY(hipMemcpyAsync(keys_n, e->mp.key, (size_t)e->v.N * 8, hipMemcpyDeviceToHost, e->stream));
-    if (ticks_n) HIP_TRY(hipMemcpyAsync(ticks_n, e->mp.tick, (size_t)e->v.N * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_frames(adc_engine *e, int32_t *frames)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (!frames) return fail(ADC_EINVAL, "frames is NULL");
-    *frames = mlp_frames(e);
-    return ADC_OK;
-}
-
-// the observation history to the host and back (any pointer may be NULL); without one (frames = 1) there is nothing to move
-ADC_EXPORT int adc_engine_mlp_history_get(adc_engine *e, float *hist_nhd, int32_t *last_n, int32_t *from_n)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (!e->mp.hist) return fail(ADC_ESTATE, "the policy has no observation history (adc_engine_mlp_init_frames, frames > 1)");
-    const size_t n = (size_t)e->v.N;
-    if (hist_nhd) HIP_TRY(hipMemcpyAsync(hist_nhd, e->mp.hist, n * (size_t)e->mp.D * 4, hipMemcpyDeviceToHost, e->stream));
-    if (last_n) HIP_TRY(hipMemcpyAsync(last_n, e->mp.last, n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (from_n) HIP_TRY(hipMemcpyAsync(from_n, e->mp.from, n * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_history_set(adc_engine *e, const float *hist_nhd, const int32_t *last_n, const int32_t *from_n)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (!e->mp.hist) return fail(ADC_ESTATE, "the policy has no observation history (adc_engine_mlp_init_frames, frames > 1)");
-    const size_t n = (size_t)e->v.N;
-    // (the kernels index the frames by these words: nothing a history cannot hold gets in)
-    for (size_t i = 0; i < n; ++i)
-        if ((last_n && last_n[i] < adc::kMlpHistNone) || (from_n && from_n[i] < 0)) return fail(ADC_EINVAL, "history: last >= -2 and from >= 0");
-    if (hist_nhd) HIP_TRY(hipMemcpyAsync(e->mp.hist, hist_nhd, n * (size_t)e->mp.D * 4, hipMemcpyHostToDevice, e->stream));
-    if (last_n) HIP_TRY(hipMemcpyAsync(e->mp.last, last_n, n * 4, hipMemcpyHostToDevice, e->stream));
-    if (from_n) HIP_TRY(hipMemcpyAsync(e->mp.from, from_n, n * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_bootstrap_value(adc_engine *e, float *value_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!value_n) return fail(ADC_EINVAL, "value_n is NULL");
-    if (int rc = mlp_ready(e)) return rc;
-    if (e->mp.val.layers == 0) return fail(ADC_ESTATE, "the policy has no value network");
-    ENGINE_GUARD(e);
-    mlp_launch_kernel(e->v, e->mp, e->stream, 1, nullptr, 0.0f, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, e->mlp_boot);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(value_n, e->mlp_boot, (size_t)e->v.N * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-// ---- policy populations: per-member weights of the policy network (parts/kernel_es.inc) ---------------------------------------
-ADC_EXPORT int adc_engine_mlp_population(adc_engine *e, int32_t members, const int32_t *member_of_env_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    const int N = e->v.N, M = members;
-    if (M < 0 || M > 65536) return fail(ADC_EINVAL, "members: 0 (off) to 65536");
-    // (the single policy's squash: the learners' own, on only while they are active, goes with them below)
-    if (M > 0 && e->mp.sq_lo && e->lrn_M == 0)
-        return fail(ADC_ESTATE, "a population with the squashed action on is not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
-    if (M > 0 && e->mp.bd_lo)
-        return fail(ADC_ESTATE, "a population with the bounded act on is not supported: it would need a log-probability (adc_engine_mlp_set_bounds(NULL, NULL) first)");
-    std::vector<int32_t> map((size_t)N), count((size_t)M, 0);
-    if (M > 0) {
-        if (!member_of_env_n && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs when no member_of_env map is given");
-        for (int env = 0; env < N; ++env) {
-            const int32_t m = member_of_env_n ? member_of_env_n[env] : env / (N / M);
-            if (m < 0 || m >= M) return fail(ADC_EINVAL, "member_of_env names a member outside [0, members)");
-            map[(size_t)env] = m;
-            count[(size_t)m] += 1;
-        }
-    }
-    ENGINE_GUARD(e);
-    if (M == 0) { population_drop(e); return ADC_OK; }      // (learners, if any, stay: there is no population to turn off then)
-    // (the new population is allocated before the old one goes: a failure leaves the engine as it was)
-    void *block = nullptr, *d_map = nullptr;
-    if (hipMalloc(&block, (size_t)M * e->pl.stride * 4) != hipSuccess || hipMalloc(&d_map, (size_t)N * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        if (block) (void)hipFree(block);
-        return fail(ADC_ENOMEM, "hipMalloc failed (policy population)");
-    }
-    learners_drop(e);                   // (the two kinds of members exclude each other)
-    population_drop(e);
-    e->pop_allocs.push_back(block);
-    e->pop_allocs.push_back(d_map);
-    HIP_TRY(hipMemsetAsync(block, 0, (size_t)M * e->pl.stride * 4, e->stream));       // (the never-read padding too)
-    HIP_TRY(hipMemcpyAsync(d_map, map.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-    // every member starts as the centre
-    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e),
-                       e->mlp_flat, 1);
-    hipLaunchKernelGGL(k_es_perturb, dim3(es_quad_blocks(e->pl.P), (unsigned)((M + 1) / 2)), dim3(kEsBlock), 0, e->stream, e->pl, e->mlp_flat,
-                       static_cast<float *>(block), (size_t)e->pl.stride, M, 0, (uint64_t)0, 0u, 0.0f);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->mp.member = static_cast<const int32_t *>(d_map);
-    e->mp.pop = static_cast<const float *>(block);
-    e->mp.pop_stride = e->pl.stride;
-    e->pop_M = M;
-    e->pop_map.swap(map);
-    e->pop_count.swap(count);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_member_layer(adc_engine *e, int32_t member, int32_t layer, const float *weights_in_out, const float *bias_out)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (e->pop_M == 0) return fail(ADC_ESTATE, "adc_engine_mlp_population has not been called");
-    if (member < 0 || member >= e->pop_M) return fail(ADC_EINVAL, "no such member");
-    if (layer < 0 || layer >= e->pl.layers) return fail(ADC_EINVAL, "no such layer");
-    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
-    ENGINE_GUARD(e);
-    const int n_in = e->pl.n_in[layer], n_out = e->pl.n_out[layer];
-    std::vector<float> w(adc::mlp_weight_count(n_in, n_out), 0.0f);
-    for (int j = 0; j < n_in; ++j)
-        for (int h = 0; h < n_out; ++h) w[adc::mlp_weight_index(j, h, n_out)] = weights_in_out[(size_t)j * n_out + h];
-    const ParamStore s = member_store(e, member);
-    HIP_TRY(hipMemcpyAsync(s.W[layer], w.data(), w.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(s.b[layer], bias_out, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_param_count(adc_engine *e, int64_t *count)
-{
-    if (!e || !count) return fail(ADC_EINVAL, "engine handle or count is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    *count = e->pl.P;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_get_params(adc_engine *e, float *flat_p)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (!flat_p) return fail(ADC_EINVAL, "flat_p is NULL");
-    ENGINE_GUARD(e);
-    return params_fetch(e, centre_store(e), flat_p);
-}
-
-ADC_EXPORT int adc_engine_mlp_get_member_params(adc_engine *e, int32_t member, float *flat_p)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (e->pop_M == 0) return fail(ADC_ESTATE, "adc_engine_mlp_population has not been called");
-    if (member < 0 || member >= e->pop_M) return fail(ADC_EINVAL, "no such member");
-    if (!flat_p) return fail(ADC_EINVAL, "flat_p is NULL");
-    ENGINE_GUARD(e);
-    return params_fetch(e, member_store(e, member), flat_p);
-}
-
-// ---- learners: per-member policy layers, value layers and log_std (the population trainer's members; parts/pg_api.inc) ----------
-namespace {
-int learners_ready(const adc_engine *e, int32_t member)
-{
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (e->lrn_M == 0) return fail(ADC_ESTATE, "adc_engine_mlp_learners has not been called");
-    if (member < 0 || member >= e->lrn_M) return fail(ADC_EINVAL, "no such member");
-    return ADC_OK;
-}
-inline unsigned pg_blocks(int Q) { return (unsigned)((Q + kPgBlock - 1) / kPgBlock); }
-}  // namespace
-
-ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    const int N = e->v.N, M = members;
-    if (M < 0 || M > 65535) return fail(ADC_EINVAL, "members: 0 (off) to 65535");
-    if (M > 0 && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs");
-    // (the single policy's squash: the learners' own, on only while they are active, goes with them below)
-    if (M > 0 && e->mp.sq_lo && e->lrn_M == 0)
-        return fail(ADC_ESTATE, "learners with the squashed action on are not supported (adc_engine_mlp_set_squash(NULL, NULL) first)");
-    if (M > 0 && e->mp.bd_lo && e->lrn_M == 0)
-        return fail(ADC_ESTATE, "learners with the single policy's bounded act on are not supported (adc_engine_mlp_set_bounds(NULL, NULL) first)");
-    ENGINE_GUARD(e);
-    if (M == 0) { learners_drop(e); return ADC_OK; }
-    // a member's block: the policy layers, the value layers, log_std, each starting on a 16-byte boundary; the flat order against it
-    const adc::PgShape sh = adc::pg_shape_of(e->mlp_cfg, e->v.K, mlp_frames(e));
-    size_t offW[2][adc::kMlpMaxLayers] = {}, offb[2][adc::kMlpMaxLayers] = {}, off_ls = 0;       // floats from the member's base
-    PgLayout lay{};
-    size_t off = 0;
-    {
-        int flat = 0, i = 0;
-        for (int net = 0; net < 2; ++net) {
-            const MlpNet &n = net == 0 ? e->mp.pol : e->mp.val;
-            for (int l = 0; l < n.layers; ++l, ++i) {
-                offW[net][l] = off; off += adc::mlp_weight_count(n.n_in[l], n.n_out[l]);
-                offb[net][l] = off; off += ((size_t)n.n_out[l] + 3u) & ~(size_t)3u;
-                lay.flat0[i] = flat; lay.n_in[i] = n.n_in[l]; lay.n_out[i] = n.n_out[l];
-                flat += (n.n_in[l] + 1) * n.n_out[l];
-            }
-        }
-        if (!sh.two_heads) {
-            off_ls = off; off += ((size_t)sh.A + 3u) & ~(size_t)3u;
-            lay.flat0[i] = flat; lay.n_in[i] = 0; lay.n_out[i] = sh.A;
-            flat += sh.A; ++i;
-        }
-        lay.nterms = i; lay.Q = flat;
-    }
-    const size_t stride = off;
-    // (the new members are allocated before the old ones go: a failure leaves the engine as it was)
-    std::vector<void *> fresh;
-    float *block = nullptr, *flat = nullptr;
-    int32_t *d_map = nullptr;
-    MlpLearner *d_tab = nullptr;
-    int rc;
-    if ((rc = mlp_alloc(e, fresh, &block, (size_t)M * stride)) || (rc = mlp_alloc(e, fresh, &flat, (size_t)lay.Q)) ||
-        (rc = mlp_alloc(e, fresh, &d_map, (size_t)N)) || (rc = mlp_alloc(e, fresh, &d_tab, (size_t)M))) {
-        mlp_free(e, fresh);
-        return rc;
-    }
-    population_drop(e);                 // (the two kinds of members exclude each other)
-    learners_drop(e);
-    e->lrn_allocs.swap(fresh);
-    std::vector<MlpLearner> tab((size_t)M);
-    for (size_t m = 0; m < (size_t)M; ++m) {
-        float *base = block + m * stride;
-        tab[m].net[0] = e->mp.pol; tab[m].net[1] = e->mp.val;       // (the shapes; the stores are the member's own)
-        for (int net = 0; net < 2; ++net)
-            for (int l = 0; l < tab[m].net[net].layers; ++l) { tab[m].net[net].W[l] = base + offW[net][l]; tab[m].net[net].b[l] = base + offb[net][l]; }
-        tab[m].log_std = sh.two_heads ? nullptr : base + off_ls;
-    }
-    {
-        int i = 0;
-        for (int net = 0; net < 2; ++net)
-            for (int l = 0; l < tab[0].net[net].layers; ++l, ++i) {
-                lay.W[i] = const_cast<float *>(tab[0].net[net].W[l]); lay.b[i] = const_cast<float *>(tab[0].net[net].b[l]);
-            }
-        if (!sh.two_heads) { lay.W[i] = nullptr; lay.b[i] = const_cast<float *>(tab[0].log_std); }
-    }
-    std::vector<int32_t> map((size_t)N);
-    for (int env = 0; env < N; ++env) map[(size_t)env] = env / (N / M);
-    HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), (size_t)M * sizeof(MlpLearner), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(d_map, map.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-    // every member starts as the centre: the centre's stores to the flat order, the flat order to every member's stores
-    {
-        PgLayout centre = lay;
-        int i = 0;
-        for (int net = 0; net < 2; ++net) {
-            const MlpNet &n = net == 0 ? e->mp.pol : e->mp.val;
-            for (int l = 0; l < n.layers; ++l, ++i) { centre.W[i] = const_cast<float *>(n.W[l]); centre.b[i] = const_cast<float *>(n.b[l]); }
-        }
-        if (!sh.two_heads) centre.b[i] = const_cast<float *>(e->mp.log_std);
-        hipLaunchKernelGGL(k_pg_params_copy, dim3(pg_blocks(lay.Q)), dim3(kPgBlock), 0, e->stream, centre, flat, 1);
-        hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks(lay.Q), (unsigned)M), dim3(kPgBlock), 0, e->stream, lay, stride, 0, flat, (size_t)0, 0);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));       // (tab and map are the host's until here)
-    e->lrn_M = M; e->lrn_n = N / M;
-    e->lrn_block = block; e->lrn_flat = flat; e->lrn_stride = stride; e->lrn_tab = d_tab; e->lrn_lay = lay;
-    e->mp.member = d_map; e->mp.learners = d_tab; e->mp.pop_stride = 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_learner_layer(adc_engine *e, int32_t member, int32_t network, int32_t layer, const float *weights_in_out,
-                                                const float *bias_out)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = learners_ready(e, member)) return rc;
-    if (network != 0 && network != 1) return fail(ADC_EINVAL, "network: 0 (policy) or 1 (value)");
-    const MlpNet &n = network == 0 ? e->mp.pol : e->mp.val;
-    if (layer < 0 || layer >= n.layers) return fail(ADC_EINVAL, "no such layer");
-    if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
-    ENGINE_GUARD(e);
-    const int n_in = n.n_in[layer], n_out = n.n_out[layer], term = (network == 0 ? 0 : e->mp.pol.layers) + layer;
-    std::vector<float> w(adc::mlp_weight_count(n_in, n_out), 0.0f);
-    for (int j = 0; j < n_in; ++j)
-        for (int h = 0; h < n_out; ++h) w[adc::mlp_weight_index(j, h, n_out)] = weights_in_out[(size_t)j * n_out + h];
-    const size_t base = (size_t)member * e->lrn_stride;
-    HIP_TRY(hipMemcpyAsync(e->lrn_lay.W[term] + base, w.data(), w.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->lrn_lay.b[term] + base, bias_out, (size_t)n_out * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_set_learner_log_std(adc_engine *e, int32_t member, const float *log_std_a)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = learners_ready(e, member)) return rc;
-    if (e->mp.two_heads) return fail(ADC_EINVAL, "a two-headed policy has no log_std vector");
-    if (!log_std_a) return fail(ADC_EINVAL, "log_std is NULL");
-    ENGINE_GUARD(e);
-    float *dst = e->lrn_lay.b[e->lrn_lay.nterms - 1] + (size_t)member * e->lrn_stride;
-    HIP_TRY(hipMemcpyAsync(dst, log_std_a, (size_t)e->mp.A * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_mlp_get_learner_params(adc_engine *e, int32_t member, float *theta_q)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = learners_ready(e, member)) return rc;
-    if (!theta_q) return fail(ADC_EINVAL, "theta_q is NULL");
-    ENGINE_GUARD(e);
-    const int Q = e->lrn_lay.Q;
-    hipLaunchKernelGGL(k_pg_pop_params_copy, dim3(pg_blocks(Q), 1u), dim3(kPgBlock), 0, e->stream, e->lrn_lay, e->lrn_stride, (int)member, e->lrn_flat,
-                       (size_t)0, 1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(theta_q, e->lrn_flat, (size_t)Q * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-// ---- the evolution strategy over a population (the law is csrc/adc_es.h) ---------------------------------------------------
-namespace {
-int es_ready(const adc_engine *e)
-{
-    if (!e->have_es) return fail(ADC_ESTATE, "adc_engine_es_init has not been called");
-    return ADC_OK;
-}
-int es_members_have_envs(const adc_engine *e)
-{
-    for (int32_t c : e->pop_count)
-        if (c == 0) return fail(ADC_EINVAL, "a member of the population has no env: it has no fitness");
-    return ADC_OK;
-}
-// a member's fitness: the float64 mean of its envs' returns, envs ascending (the envs' streams have been joined by the guard)
-int es_fitness_fetch(adc_engine *e, double *fitness_m)
-{
-    const size_t N = (size_t)e->v.N;
-    std::vector<double> ret(N);
-    HIP_TRY(hipMemcpyAsync(ret.data(), e->es_return, N * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int m = 0; m < e->pop_M; ++m) fitness_m[m] = 0.0;
-    for (size_t env = 0; env < N; ++env) fitness_m[e->pop_map[env]] = fitness_m[e->pop_map[env]] + ret[env];
-    for (int m = 0; m < e->pop_M; ++m) fitness_m[m] = fitness_m[m] / (double)e->pop_count[(size_t)m];
-    return ADC_OK;
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_es_init(adc_engine *e, const adc_es_config *cfg)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const char *why = nullptr;
-    if (adc_es_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
-    if (int rc = mlp_ready(e)) return rc;
-    if (e->pop_M == 0) return fail(ADC_ESTATE, "the evolution strategy needs a population (adc_engine_mlp_population)");
-    if (e->pop_M & 1) return fail(ADC_EINVAL, "the evolution strategy needs an even number of members (antithetic pairs)");
-    ENGINE_GUARD(e);
-    const size_t P = (size_t)e->pl.P;
-    std::vector<void *> fresh;
-    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
-    double *du = nullptr, *ret = nullptr;
-    int rc;
-    if ((rc = mlp_alloc(e, fresh, &theta, P)) || (rc = mlp_alloc(e, fresh, &m, P)) || (rc = mlp_alloc(e, fresh, &v, P)) ||
-        (rc = mlp_alloc(e, fresh, &grad, P)) || (rc = mlp_alloc(e, fresh, &du, (size_t)e->pop_M / 2)) ||
-        (rc = mlp_alloc(e, fresh, &ret, (size_t)e->v.N))) {
-        mlp_free(e, fresh);
-        return rc;
-    }
-    mlp_free(e, e->es_allocs);
-    e->es_allocs.swap(fresh);
-    e->es_theta = theta; e->es_m = m; e->es_v = v; e->es_grad = grad; e->es_du = du; e->es_return = ret;
-    e->es_cfg = *cfg;
-    e->es_key = adc::es_key(cfg->seed ? cfg->seed : e->cfg.seed);
-    e->es_generation = 0;
-    e->es_days = 0;
-    e->es_accumulate = false;
-    // theta starts as the centre policy
-    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e),
-                       e->es_theta, 1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->have_es = true;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_es_perturb(adc_engine *e)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = es_ready(e)) return rc;
-    ENGINE_GUARD(e);
-    hipLaunchKernelGGL(k_es_perturb, dim3(es_quad_blocks(e->pl.P), (unsigned)(e->pop_M / 2)), dim3(kEsBlock), 0, e->stream, e->pl, e->es_theta,
-                       const_cast<float *>(e->mp.pop), e->mp.pop_stride, e->pop_M, 1, e->es_key, (uint32_t)e->es_generation, e->es_cfg.sigma);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(e->es_return, 0, (size_t)e->v.N * 8, e->stream));
-    e->es_days = 0;
-    e->es_accumulate = true;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_es_fitness(adc_engine *e, double *fitness_m)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!fitness_m) return fail(ADC_EINVAL, "fitness_m is NULL");
-    if (int rc = es_ready(e)) return rc;
-    if (int rc = es_members_have_envs(e)) return rc;
-    ENGINE_GUARD(e);
-    return es_fitness_fetch(e, fitness_m);
-}
-
-ADC_EXPORT int adc_engine_es_update(adc_engine *e, const double *fitness_m, adc_es_stats *stats)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = es_ready(e)) return rc;
-    if (int rc = es_members_have_envs(e)) return rc;
-    if (!fitness_m && e->es_days == 0) return fail(ADC_EINVAL, "no day has been stepped since adc_engine_es_perturb and no fitness was handed in");
-    ENGINE_GUARD(e);
-    const int M = e->pop_M;
-    const size_t P = (size_t)e->pl.P;
-    std::vector<double> fit((size_t)M), du;
-    if (fitness_m) std::copy(fitness_m, fitness_m + M, fit.begin());
-    else if (int rc = es_fitness_fetch(e, fit.data())) return rc;
-    adc::es_shape(e->es_cfg.shaping == ADC_ES_RAW ? adc::kEsRaw : adc::kEsCenteredRank, fit.data(), M, du);
-    const uint32_t t = (uint32_t)(e->es_generation + 1);
-    adc::EsStep step{};
-    step.optimiser = e->es_cfg.optimiser == ADC_ES_SGD ? adc::kEsSgd : adc::kEsAdam;
-    step.lr = e->es_cfg.lr; step.beta1 = e->es_cfg.beta1; step.beta2 = e->es_cfg.beta2; step.eps = e->es_cfg.eps; step.l2 = e->es_cfg.l2;
-    step.c1 = adc::es_bias_correction(step.beta1, t);
-    step.c2 = adc::es_bias_correction(step.beta2, t);
-    HIP_TRY(hipMemcpyAsync(e->es_du, du.data(), du.size() * 8, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_es_update, dim3((unsigned)(((e->pl.P + 3) / 4 + kEsUpdQuads - 1) / kEsUpdQuads)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e), e->es_theta, e->es_m,
-                       e->es_v, e->es_grad, e->es_du, M, e->es_key, (uint32_t)e->es_generation, e->es_cfg.sigma, step);
-    HIP_TRY(hipGetLastError());
-    std::vector<float> g(P), th(P);
-    HIP_TRY(hipMemcpyAsync(g.data(), e->es_grad, P * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(th.data(), e->es_theta, P * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->es_generation += 1;
-    e->es_accumulate = false;
-    e->es_days = 0;
-    if (stats) {
-        double sum = 0.0, mx = fit[0], mn = fit[0], gg = 0.0, tt = 0.0;
-        for (double f : fit) { sum += f; mx = f > mx ? f : mx; mn = f < mn ? f : mn; }
-        for (size_t p = 0; p < P; ++p) { gg += (double)g[p] * (double)g[p]; tt += (double)th[p] * (double)th[p]; }
-        stats->generation = e->es_generation;
-        stats->fitness_mean = sum / (double)M; stats->fitness_max = mx; stats->fitness_min = mn;
-        stats->grad_norm = std::sqrt(gg); stats->theta_norm = std::sqrt(tt);
-    }
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_es_state_get(adc_engine *e, float *theta_p, float *m_p, float *v_p, int64_t *generation)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = es_ready(e)) return rc;
-    ENGINE_GUARD(e);
-    const size_t bytes = (size_t)e->pl.P * 4;
-    if (theta_p) HIP_TRY(hipMemcpyAsync(theta_p, e->es_theta, bytes, hipMemcpyDeviceToHost, e->stream));
-    if (m_p) HIP_TRY(hipMemcpyAsync(m_p, e->es_m, bytes, hipMemcpyDeviceToHost, e->stream));
-    if (v_p) HIP_TRY(hipMemcpyAsync(v_p, e->es_v, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (generation) *generation = e->es_generation;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_es_state_set(adc_engine *e, const float *theta_p, const float *m_p, const float *v_p, int64_t generation)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = es_ready(e)) return rc;
-    if (!theta_p || !m_p || !v_p) return fail(ADC_EINVAL, "theta, m or v is NULL");
-    if (generation < 0 || generation > 0x7FFFFFFFll) return fail(ADC_EINVAL, "generation: 0 to 2^31 - 1");
-    ENGINE_GUARD(e);
-    const size_t bytes = (size_t)e->pl.P * 4;
-    HIP_TRY(hipMemcpyAsync(e->es_theta, theta_p, bytes, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->es_m, m_p, bytes, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->es_v, v_p, bytes, hipMemcpyHostToDevice, e->stream));
-    // (the centre's chain-major copy follows theta, so that evaluation without a population sees it)
-    hipLaunchKernelGGL(k_params_copy, dim3((unsigned)((e->pl.P + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, e->stream, e->pl, centre_store(e),
-                       e->es_theta, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->es_generation = generation;
-    e->es_accumulate = false;
-    e->es_days = 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t fields)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
-    if (horizon < 0 || horizon > (1 << 20)) return fail(ADC_EINVAL, "horizon: 0 (off) to 2^20 days");
-    if (fields & ~ADC_ROLLOUT_OBS) return fail(ADC_EINVAL, "unknown rollout field");
-    ENGINE_GUARD(e);
-    pg_drop(e);                         // (its advantages and scratch were sized for the old record)
-    td3_drop(e);
-    norm_set_drop(e, e->on);
-    mlp_free(e, e->ro_allocs);
-    e->ro_T = e->ro_t = 0;
-    e->ro_obs = nullptr;
-    e->ro_deterministic = false;
-    e->ro_teacher = 0;
-    if (horizon == 0) return ADC_OK;
-    const size_t tn = (size_t)horizon * (size_t)e->v.N;
-    int rc;
-    if ((rc = mlp_alloc(e, e->ro_allocs, &e->ro_action, tn * (size_t)e->mp.A)) || (rc = mlp_alloc(e, e->ro_allocs, &e->ro_logp, tn)) ||
-        (rc = mlp_alloc(e, e->ro_allocs, &e->ro_value, tn)) || (rc = mlp_alloc(e, e->ro_allocs, &e->ro_reward, tn)) ||
-        (rc = mlp_alloc(e, e->ro_allocs, &e->ro_term, tn)) || (rc = mlp_alloc(e, e->ro_allocs, &e->ro_trunc, tn)) ||
-        ((fields & ADC_ROLLOUT_OBS) && (rc = mlp_alloc(e, e->ro_allocs, &e->ro_obs, tn * (size_t)e->mp.D)))) {
-        mlp_free(e, e->ro_allocs);
-        e->ro_obs = nullptr;
-        return rc;
-    }
-    e->ro_T = horizon;
-    e->ro_fields = fields;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
-{
-    ENGINE_GUARD(e);
-    if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
-    e->ro_t = 0;
-    for (NormSet *s : {&e->on, &e->rn, &e->tn, &e->sn}) s->t0 = 0;
-    e->ro_deterministic = false;
-    e->ro_teacher = 0;
-    e->pg_adv_ready = e->im_adv_ready = false;
-    e->td3_stored_t = 0;
-    e->td3_gap = false;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_rollout_fetch(adc_engine *e, int32_t *days_recorded, float *action_tna, float *logp_tn, float *value_tn, float *reward_tn,
-                                        uint8_t *terminated_tn, uint8_t *truncated_tn, float *obs_tnd)
-{
-    ENGINE_GUARD(e);
-    if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
-    if (obs_tnd && !e->ro_obs) return fail(ADC_ESTATE, "the record was enabled without ADC_ROLLOUT_OBS");
-    if (days_recorded) *days_recorded = e->ro_t;
-    const size_t tn = (size_t)e->ro_t * (size_t)e->v.N;
-    if (tn > 0) {
-        if (action_tna) HIP_TRY(hipMemcpyAsync(action_tna, e->ro_action, tn * (size_t)e->mp.A * 4, hipMemcpyDeviceToHost, e->stream));
-        if (logp_tn) HIP_TRY(hipMemcpyAsync(logp_tn, e->ro_logp, tn * 4, hipMemcpyDeviceToHost, e->stream));
-        if (value_tn) HIP_TRY(hipMemcpyAsync(value_tn, e->ro_value, tn * 4, hipMemcpyDeviceToHost, e->stream));
-        if (reward_tn) HIP_TRY(hipMemcpyAsync(reward_tn, e->ro_reward, tn * 4, hipMemcpyDeviceToHost, e->stream));
-        if (terminated_tn) HIP_TRY(hipMemcpyAsync(terminated_tn, e->ro_term, tn, hipMemcpyDeviceToHost, e->stream));
-        if (truncated_tn) HIP_TRY(hipMemcpyAsync(truncated_tn, e->ro_trunc, tn, hipMemcpyDeviceToHost, e->stream));
-        if (obs_tnd) HIP_TRY(hipMemcpyAsync(obs_tnd, e->ro_obs, tn * (size_t)e->mp.D * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-// ---- `days` days of the device-resident loop in one call.  Optionally (adc_engine_day_graph_enable) two consecutive
-// days (both step parities) are captured once as a hipGraph and replayed.  Measured on MI355X at 1-256 envs x 100
-// keywords (tools/measure_small_loop.py): 28-50 us per day either way - the 7 dependent kernels of a day are bound by
-// their ~4.5 us each of device-side latency, not by host launch cost - so replay is off by default. ------------------------
-namespace {
-int one_day(adc_engine *e, int policy, float budget)
-{
-    int rc = ADC_OK;
-    // (the policy kernels and the step are one chain: from the third day on they run group by group where the engine groups at all)
-    if (policy == ADC_POLICY_ZERO_MARGIN) {
-        if ((rc = agent_step_chained(e, budget))) return rc;
-        if (e->have_curves && (rc = ideal_step_chained(e))) return rc;
-    } else if (policy == ADC_POLICY_INTERPOLATION) {
-        if ((rc = interp_step_chained(e, budget))) return rc;
-        if (e->have_curves && (rc = ideal_step_chained(e))) return rc;
-    } else if (policy == ADC_POLICY_ORACLE) {
-        if ((rc = ideal_step_chained(e))) return rc;
-        if ((rc = policy_oracle_chained(e, budget))) return rc;
-    } else if (policy == ADC_POLICY_MLP) {
-        return mlp_day(e, budget, /* with_ideal = */ true);
-    }
-    return launch_step(e, e->d_bids, e->d_budget, nullptr, /* lazy_join = */ true);
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_day_graph_enable(adc_engine *e, int enabled)
-{
-    ENGINE_GUARD(e);
-    e->day_graph_enabled = enabled != 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_run_days(adc_engine *e, int policy, int32_t days, float budget)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
-    if (policy != ADC_POLICY_FIXED_ACTIONS && policy != ADC_POLICY_ZERO_MARGIN && policy != ADC_POLICY_ORACLE &&
-        policy != ADC_POLICY_INTERPOLATION && policy != ADC_POLICY_MLP)
-        return fail(ADC_EINVAL, "unknown policy");
-    if (policy == ADC_POLICY_MLP) {
-        if (int ready = mlp_ready(e)) return ready;
-        if (days > 0 && !rollout_room(e, days)) return fail(ADC_EINVAL, "the rollout record would overflow within these days: adc_engine_rollout_reset first");
-    }
-    if (policy == ADC_POLICY_ZERO_MARGIN && !e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
-    if (policy == ADC_POLICY_INTERPOLATION) {
-        if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-        if (days > 0 && !interp_room(e, days)) return fail(ADC_EINVAL, "the interpolation agent's capacity would overflow within these days");
-    }
-    if (policy == ADC_POLICY_ORACLE && !e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
-    if (days < 0) return fail(ADC_EINVAL, "days < 0");
-    int rc;
-    // profiling brackets kernels with events on the stream: keep that path un-captured
-    bool use_graph = e->day_graph_enabled && !e->profiling && days >= 4 && policy != ADC_POLICY_MLP;    // (the learned agent's days are never captured)
-    if (use_graph && e->v.model == ADC_MODEL_IMPLICIT && e->volume_hint_dirty && !(e->fast_tiles_per_wg && e->fast_variant)) {
-        if ((rc = refresh_volume_hint(e))) return rc;        // (synchronises: must not happen inside a capture)
-    }
-    // (the captured days are one group on the engine's stream; where the plain chain runs as env groups it is the faster of the two -
-    //  cfg2: run_days(zero_margin) 0.414 ms per day as one group, 0.247 in groups - so the graph is for engines that do not group)
-    if (use_graph && !e->stream_exposed) {
-        const adc_engine::StepPlan probe = e->v.model == ADC_MODEL_IMPLICIT ? plan_step(e) : adc_engine::StepPlan{false, false, false};
-        if (stream_groups(e, probe, /* chained = */ true) > 1) use_graph = false;
-    }
-    // The kernel nodes of a captured day hold View and PolicyView BY VALUE (metrics_on, max_days, loss_threshold, drift_*,
-    // flat_obs, the curve / grid pointers, n_bids, ...) and the launch shapes derived from the engine's hints: a graph
-    // captured under other settings would silently replay them (or read freed curve memory), so the cache key is all of it.
-    adc_engine::GraphKey now{};
-    std::memset(&now, 0, sizeof(now));              // (padding bytes too: the key is compared with memcmp)
-    // (the plan of the captured days is taken HERE, once, and handed to launch_step through capture_plan: the graph and its key
-    //  come from the same snapshot of the device's flag words)
-    const adc_engine::StepPlan plan = e->v.model == ADC_MODEL_IMPLICIT ? plan_step(e) : adc_engine::StepPlan{false, false, false};
-    now.v = e->v; now.pol = e->pol;
-    now.have_agent = e->have_agent; now.have_curves = e->have_curves; now.have_ideal = e->have_ideal;
-    now.ip = e->ip; now.have_interp = e->have_interp;
-    now.mean_volume_hint = e->mean_volume_hint; now.fast_tiles_per_wg = e->fast_tiles_per_wg;
-    now.lists = plan.lists;                 // (which variant of the fast pass launch_step picks)
-    now.rest = plan.rest;                   // (... and whether k_step_rest_of_day follows the row kernel)
-    now.direct = plan.direct;               // (... and its at-once variant)
-    if (use_graph && (!e->day_graph || e->day_graph_policy != policy || e->day_graph_budget != budget ||
-                      std::memcmp(&now, &e->day_graph_key, sizeof(now)) != 0)) {
-        if (e->day_graph) { (void)hipGraphExecDestroy(e->day_graph); e->day_graph = nullptr; }
-        if (e->v.model == ADC_MODEL_IMPLICIT && e->v.K <= kRowsMaxK && e->rows_per_cu == 0) {
-            // (the occupancy query of launch_step must not run inside a capture: take one plain day first)
-            if ((rc = one_day(e, policy, budget))) return rc;
-            days -= 1;
-        }
-        const uint32_t serial0 = e->step_serial;
-        const long long stream_steps0 = e->stream_steps;
-        const uint64_t env_moves0 = e->env_moves;
-        const int last_step0 = e->last_step;
-        hipGraph_t graph = nullptr;
-        if ((rc = join_groups(e))) return rc;           // (the plain day above may have run as env groups: nothing of it may still be in flight on their streams)
-        HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeRelaxed));
-        e->capture_plan = plan;
-        e->in_capture = true;
-        rc = one_day(e, policy, budget);
-        if (!rc) rc = one_day(e, policy, budget);
-        e->in_capture = false;
-        const hipError_t cap = hipStreamEndCapture(e->stream, &graph);
-        e->step_serial = serial0;                       // nothing ran: the capture only recorded the launches
-        e->stream_steps = stream_steps0;
-        e->last_step = last_step0;
-        e->env_moves = env_moves0;
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        HIP_TRY(cap);
-        const hipError_t inst = hipGraphInstantiate(&e->day_graph, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        HIP_TRY(inst);
-        e->day_graph_policy = policy;
-        e->day_graph_budget = budget;
-        std::memcpy(&e->day_graph_key, &now, sizeof(now));
-        e->day_graph_parity = (int)(serial0 & 1u);
-    }
-    if (use_graph && days > 0 && (int)(e->step_serial & 1u) != e->day_graph_parity) {
-        if ((rc = one_day(e, policy, budget))) return rc;            // line the step parity up with the captured pair
-        days -= 1;
-    }
-    while (use_graph && days >= 2) {
-        // (the captured days are one group on the engine's stream: whatever ran as env groups before them is joined first, and what
-        //  follows them starts a new chain)
-        if ((rc = join_groups(e))) return rc;
-        e->last_groups = 1;
-        e->needs_fork = e->api_since_step = true;
-        if (policy == ADC_POLICY_INTERPOLATION) e->interp_updates += 2;     // (counted before the launch: a failed one errs on the safe side)
-        HIP_TRY(hipGraphLaunch(e->day_graph, e->stream));
-        e->step_serial += 2;
-        e->stream_steps += 2;
-        e->env_moves += 2;
-        e->last_step = 1;
-        e->drift_applied = false;
-        days -= 2;
-    }
-    while (days > 0) {
-        if ((rc = one_day(e, policy, budget))) return rc;
-        days -= 1;
-    }
     return ADC_OK;
 }
 

@@ -27,27 +27,13 @@ int tp_member_check(const adc_engine *e, int32_t member)
     return ADC_OK;
 }
 
-// ---- flat vectors against the chain-major stores -------------------------------------------------------------------------------
-// the flat order of `count` networks' layers against their chain-major stores
-PgLayout td3_layout(const MlpNet *nets, int count)
-{
-    PgLayout lay{};
-    int flat = 0, i = 0;
-    for (int n = 0; n < count; ++n)
-        for (int l = 0; l < nets[n].layers; ++l, ++i) {
-            lay.flat0[i] = flat; lay.n_in[i] = nets[n].n_in[l]; lay.n_out[i] = nets[n].n_out[l];
-            lay.W[i] = const_cast<float *>(nets[n].W[l]); lay.b[i] = const_cast<float *>(nets[n].b[l]);
-            flat += (nets[n].n_in[l] + 1) * nets[n].n_out[l];
-        }
-    lay.nterms = i; lay.Q = flat;
-    return lay;
-}
+// ---- flat vectors against the chain-major stores (the flat order is flat_layout of parts/mlp_core.inc) -----------------------------
 // the critics', the target actor's (none: SAC) and the target critics' flat orders; theta's is the front end's
 void off_layouts(adc_engine *e, const MlpNet *q, const MlpNet *q_t, const MlpNet &pol_t)
 {
-    e->td3_lay[kTd3Psi] = td3_layout(q, 2);
-    e->td3_lay[kTd3ThetaT] = pol_t.layers ? td3_layout(&pol_t, 1) : PgLayout{};
-    e->td3_lay[kTd3PsiT] = td3_layout(q_t, 2);
+    e->td3_lay[kTd3Psi] = flat_layout(q, 2);
+    e->td3_lay[kTd3ThetaT] = pol_t.layers ? flat_layout(&pol_t, 1) : PgLayout{};
+    e->td3_lay[kTd3PsiT] = flat_layout(q_t, 2);
 }
 // a population's theta: the learners' policy layers; the other vectors' stores are `stride` floats apart
 void tp_theta_layout(adc_engine *e, size_t stride)

@@ -261,24 +261,7 @@ ADC_EXPORT int adc_engine_pg_init(adc_engine *e, const adc_pg_config *cfg)
     const int maxw = pg_max_width(sh);
     if ((rc = pg_lds_refuse(e, sh, maxw, false))) return rc;
     ENGINE_GUARD(e);
-    // the flat order against the device's stores
-    PgLayout lay{};
-    {
-        int flat = 0, i = 0;
-        for (int net = 0; net < 2; ++net) {
-            const MlpNet &n = net == 0 ? e->mp.pol : e->mp.val;
-            for (int l = 0; l < sh.layers[net]; ++l, ++i) {
-                lay.flat0[i] = flat; lay.n_in[i] = n.n_in[l]; lay.n_out[i] = n.n_out[l];
-                lay.W[i] = const_cast<float *>(n.W[l]); lay.b[i] = const_cast<float *>(n.b[l]);
-                flat += (n.n_in[l] + 1) * n.n_out[l];
-            }
-        }
-        if (!sh.two_heads) {
-            lay.flat0[i] = flat; lay.n_in[i] = 0; lay.n_out[i] = sh.A; lay.W[i] = nullptr; lay.b[i] = const_cast<float *>(e->mp.log_std);
-            flat += sh.A; ++i;
-        }
-        lay.nterms = i; lay.Q = flat;
-    }
+    const PgLayout lay = centre_layout(e);      // the flat order against the device's stores
     const size_t Q = (size_t)lay.Q, tn = (size_t)e->ro_T * (size_t)N;
     if ((rc = pg_scratch_alloc(e, sh, maxw, 1, Q, mb, (size_t)pg_chunks((long long)std::max(tn, Q)) * 8u + 8u, false, cfg, 1))) return rc;
     e->pg_lay = lay;

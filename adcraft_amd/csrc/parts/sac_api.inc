@@ -165,7 +165,7 @@ ADC_EXPORT int adc_engine_sac_init(adc_engine *e, const adc_sac_config *cfg)
     e->sac_cfg = *cfg; e->td3_cfg = sac_as_td3(*cfg); e->sac_law = adc::sac_law_of(e->mlp_cfg, *cfg);
     e->td3_key = adc::td3_key(cfg->seed ? cfg->seed : e->cfg.seed);
     e->td3_q[0] = nets[0]; e->td3_q[1] = nets[1]; e->td3_q_t[0] = nets[2]; e->td3_q_t[1] = nets[3]; e->td3_pol_t = MlpNet{};
-    e->td3_lay[kTd3Theta] = td3_layout(&e->mp.pol, 1);
+    e->td3_lay[kTd3Theta] = flat_layout(&e->mp.pol, 1);
     off_layouts(e, e->td3_q, e->td3_q_t, e->td3_pol_t);
     e->td3_a_shift = e->td3_a_scale = nullptr; e->td3_ring = o.ring;
     e->sac_cell = cell;

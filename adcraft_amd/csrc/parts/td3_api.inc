@@ -147,7 +147,7 @@ ADC_EXPORT int adc_engine_td3_init(adc_engine *e, const adc_td3_config *cfg)
     e->td3_cfg = *cfg;
     e->td3_key = adc::td3_key(cfg->seed ? cfg->seed : e->cfg.seed);
     e->td3_q[0] = nets[0]; e->td3_q[1] = nets[1]; e->td3_q_t[0] = nets[2]; e->td3_q_t[1] = nets[3]; e->td3_pol_t = nets[4];
-    e->td3_lay[kTd3Theta] = td3_layout(&e->mp.pol, 1);
+    e->td3_lay[kTd3Theta] = flat_layout(&e->mp.pol, 1);
     off_layouts(e, e->td3_q, e->td3_q_t, e->td3_pol_t);
     e->td3_a_shift = shift; e->td3_a_scale = scale; e->td3_ring = o.ring;
     // theta starts as the device's policy; the targets as copies (of the critics too: zeros until they are uploaded and synchronised)

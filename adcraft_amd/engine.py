@@ -559,7 +559,7 @@ class StepEngine:
         check(self._lib.adc_engine_get_actions(self._h, bids.ctypes.data, budget.ctypes.data))
         return bids, budget
 
-    # ---- the MLP policy, one agent per env (parts/kernel_mlp_policy.inc; baselines/mlp_policy.py builds `policy`) ----------
+    # ---- the MLP policy, one agent per env (parts/kernel_mlp_policy.inc, parts/mlp_api.inc; baselines/mlp_policy.py builds `policy`) ----
     def mlp_init(self, policy, seeds=None, deterministic=None):
         """shapes and options of an MLPPolicy, then its weights; deterministic (if given) overrides the policy's own flag"""
         cfg = policy.config(self.num_keywords, deterministic)
@@ -576,17 +576,25 @@ class StepEngine:
         self._learners = 0
         self.mlp_set_weights(policy)
 
+    def _mlp_policy(self):
+        """the policy given to mlp_init"""
+        if getattr(self, "_mlp", None) is None:
+            raise _ffi.EngineStateError("mlp_init has not been called")
+        return self._mlp
+
+    def _upload_layers(self, set_layer, networks):
+        """every layer of `networks` - pairs of (the arguments that name a network, its layers) - through one set_*_layer function"""
+        for where, layers in networks:
+            for i, (w, b) in enumerate(layers):
+                check(set_layer(self._h, *where, i, w.ctypes.data, b.ctypes.data))
+
     def mlp_set_weights(self, policy):
         """upload every layer, the normalisation vectors and log_std of `policy` (same shapes as at mlp_init): a trainer's
         update between days; nothing else of the agent changes"""
-        if getattr(self, "_mlp", None) is None:
-            raise _ffi.EngineStateError("mlp_init has not been called")
-        if policy.shapes() != self._mlp.shapes():
+        if policy.shapes() != self._mlp_policy().shapes():
             raise ValueError(f"mlp_set_weights: the policy's shapes {policy.shapes()} are not those given to mlp_init "
                              f"{self._mlp.shapes()} (layers, value layers, free log_std, normalisation)")
-        for net, layers in ((0, policy.layers), (1, policy.value_layers)):
-            for i, (w, b) in enumerate(layers):
-                check(self._lib.adc_engine_mlp_set_layer(self._h, net, i, w.ctypes.data, b.ctypes.data))
+        self._upload_layers(self._lib.adc_engine_mlp_set_layer, (((0,), policy.layers), ((1,), policy.value_layers)))
         if policy.shift is not None:
             check(self._lib.adc_engine_mlp_set_norm(self._h, policy.shift.ctypes.data, policy.scale.ctypes.data))
         if policy.log_std is not None:
@@ -605,30 +613,17 @@ class StepEngine:
     def mlp_set_squash(self, lo=None, hi=None):
         """the squashed action: with lo / hi [K + 1] (flat action order: budget, bids) the env is given lo + 0.5 (hi - lo)
         (tanh(u) + 1) in place of the sampled action u; the record, mlp_last and the log-probability keep u.  Both None: off"""
-        if lo is None and hi is None:
-            check(self._lib.adc_engine_mlp_set_squash(self._h, None, None))
-            return
-        if lo is None or hi is None:
-            raise ValueError("mlp_set_squash: lo and hi, or neither")
-        a = self.num_keywords + 1
-        lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
-        check(self._lib.adc_engine_mlp_set_squash(self._h, lo.ctypes.data, hi.ctypes.data))
+        self._set_bounds(self._lib.adc_engine_mlp_set_squash, "mlp_set_squash", lo, hi)
 
     def mlp_learners_set_squash(self, lo=None, hi=None):
         """mlp_set_squash for learners (mlp_learners first): one pair of bounds lo / hi [K + 1] shared by all members.  Both
         None: off.  mlp_learners, mlp_population and mlp_init drop it."""
-        if lo is None and hi is None:
-            check(self._lib.adc_engine_mlp_learners_set_squash(self._h, None, None))
-            return
-        if lo is None or hi is None:
-            raise ValueError("mlp_learners_set_squash: lo and hi, or neither")
-        a = self.num_keywords + 1
-        lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float32), (a,))) for v in (lo, hi))
-        check(self._lib.adc_engine_mlp_learners_set_squash(self._h, lo.ctypes.data, hi.ctypes.data))
+        self._set_bounds(self._lib.adc_engine_mlp_learners_set_squash, "mlp_learners_set_squash", lo, hi)
 
     EXPLORE_MODES = {"gaussian": 0, "random": 1}
 
     def _set_bounds(self, fn, name, lo, hi):
+        """lo / hi [K + 1] (or scalars) through one of the squash or bounds setters; both None: off"""
         if lo is None and hi is None:
             check(fn(self._h, None, None))
             return
@@ -737,7 +732,7 @@ class StepEngine:
         check(self._lib.adc_engine_mlp_bootstrap_value(self._h, v.ctypes.data))
         return v
 
-    # ---- policy populations and the evolution strategy over them (parts/kernel_es.inc; baselines/es_trainer.py drives it) ------
+    # ---- policy populations and the evolution strategy over them (parts/kernel_es.inc, parts/mlp_api.inc, parts/es_api.inc; baselines/es_trainer.py) ----
     def mlp_population(self, members, member_of_env=None):
         """`members` copies of the policy network's layers, each starting as the centre policy; member_of_env [N] (default
         env // (N // members)) says whose weights an env runs.  0 turns the population off.  The value network, log_std and
@@ -752,12 +747,9 @@ class StepEngine:
 
     def mlp_set_member(self, member, policy):
         """the policy layers of `policy` (same shapes as at mlp_init) into one member"""
-        if getattr(self, "_mlp", None) is None:
-            raise _ffi.EngineStateError("mlp_init has not been called")
-        if [w.shape for w, _ in policy.layers] != [w.shape for w, _ in self._mlp.layers]:
+        if [w.shape for w, _ in policy.layers] != [w.shape for w, _ in self._mlp_policy().layers]:
             raise ValueError("mlp_set_member: the policy's layer shapes are not those given to mlp_init")
-        for i, (w, b) in enumerate(policy.layers):
-            check(self._lib.adc_engine_mlp_set_member_layer(self._h, int(member), i, w.ctypes.data, b.ctypes.data))
+        self._upload_layers(self._lib.adc_engine_mlp_set_member_layer, (((int(member),), policy.layers),))
 
     def mlp_param_count(self):
         n = C.c_int64(0)
@@ -775,7 +767,7 @@ class StepEngine:
         check(self._lib.adc_engine_mlp_get_member_params(self._h, int(member), flat.ctypes.data))
         return flat
 
-    # ---- learners: per-member policy layers, value layers and log_std (the members pg_pop_* trains) ----------------------------
+    # ---- learners: per-member policy layers, value layers and log_std (parts/mlp_api.inc; the members pg_pop_* trains) ----------
     def mlp_learners(self, members):
         """`members` learners, each with its own policy layers, value layers and log_std, each starting as the centre policy;
         member m owns the envs [m N / M, (m + 1) N / M).  0 turns the mode off.  Excludes mlp_population."""
@@ -786,13 +778,10 @@ class StepEngine:
 
     def mlp_set_learner(self, member, policy):
         """every layer of both networks and log_std of `policy` (same shapes as at mlp_init) into one learner"""
-        if getattr(self, "_mlp", None) is None:
-            raise _ffi.EngineStateError("mlp_init has not been called")
-        if policy.shapes() != self._mlp.shapes():
+        if policy.shapes() != self._mlp_policy().shapes():
             raise ValueError(f"mlp_set_learner: the policy's shapes {policy.shapes()} are not those given to mlp_init {self._mlp.shapes()}")
-        for net, layers in ((0, policy.layers), (1, policy.value_layers)):
-            for i, (w, b) in enumerate(layers):
-                check(self._lib.adc_engine_mlp_set_learner_layer(self._h, int(member), net, i, w.ctypes.data, b.ctypes.data))
+        m = int(member)
+        self._upload_layers(self._lib.adc_engine_mlp_set_learner_layer, (((m, 0), policy.layers), ((m, 1), policy.value_layers)))
         if policy.log_std is not None:
             check(self._lib.adc_engine_mlp_set_learner_log_std(self._h, int(member), policy.log_std.ctypes.data))
 
@@ -811,10 +800,8 @@ class StepEngine:
 
     def mlp_learner_param_count(self):
         """Q: the parameters of both networks and log_std of the policy given to mlp_init"""
-        if getattr(self, "_mlp", None) is None:
-            raise _ffi.EngineStateError("mlp_init has not been called")
         q = C.c_int64(0)
-        cfg = self._mlp.config(self.num_keywords)
+        cfg = self._mlp_policy().config(self.num_keywords)
         if self._lib.adc_pg_param_count_host(C.byref(cfg), self.num_keywords, C.byref(q)) != _ffi.ADC_OK:
             raise ValueError("bad policy configuration")
         # (the host twin counts one frame's inputs: an observation history widens both first layers)

@@ -203,6 +203,15 @@ def random_policy(rng, K, hidden, activation="tanh", two_heads=False, value=Fals
                      value_layers=net(list(hidden) + [1]) if value else (), **kw)
 
 
+def ragged_policy(rng, K, two_heads=False, hidden=(5, 3), value_hidden=(6,)):
+    """random_policy whose two networks differ in depth and whose hidden widths (and the value head's 1) are no multiple of the
+    4 floats the device's stores are padded to"""
+    pol = random_policy(rng, K, hidden, two_heads=two_heads, value=False)
+    val = random_policy(rng, K, value_hidden, value=True)
+    pol.value_layers = val.value_layers
+    return pol
+
+
 def realistic_obs(rng, B, K):
     """observation rows of the magnitude a day leaves: counts in the tens to thousands, dollars in the tens, some zeros"""
     clicks = rng.poisson(rng.gamma(2.0, 20.0, (B, K))) * (rng.random((B, K)) < 0.8)

@@ -399,3 +399,175 @@ def test_refusals_that_need_an_engine(amd):
     e.rollout_enable(0)
     e.run_days("mlp", 3)                                           # no record: no horizon
     e.close()
+
+
+# ---- the refusals that pass through the helpers the learned agent's host files share (parts/mlp_core.inc: mlp_have,
+# population_member_check, learners_ready, the layer upload's callers; parts/mlp_api.inc: squash_set, bounds_set), by their whole
+# sentence, two set up at once wherever a shared helper could put them in another order -------------------------------------------
+SAID = dict(
+    null="engine handle is NULL",
+    no_init="adc_engine_mlp_init has not been called",
+    network="network: 0 (policy) or 1 (value)",
+    layer="no such layer",
+    weights="weights or bias is NULL",
+    no_population="adc_engine_mlp_population has not been called",
+    no_learners="adc_engine_mlp_learners has not been called",
+    member="no such member",
+    flat_null="flat_p is NULL",
+    theta_null="theta_q is NULL",
+    log_std_null="log_std is NULL",
+    two_heads="a two-headed policy has no log_std vector",
+    squash_pair="lo and hi: both vectors, or both NULL (squash off)",
+    squash_population="the squashed action with a population active is not supported (adc_engine_mlp_population(0) first)",
+    squash_learners="the squashed action with learners active is not supported (adc_engine_mlp_learners(0) first)",
+    squash_bounded="the squashed action together with the bounded act is not supported (adc_engine_mlp_set_bounds(NULL, NULL) first)",
+    squash_needs_learners="the learners' squashed action needs learners (adc_engine_mlp_learners)",
+    squash_learners_bounded="the squashed action together with the bounded act is not supported (adc_engine_mlp_learners_set_bounds(NULL, NULL) first)",
+    squash_order="squash bounds: finite, hi > lo",
+    squash_overflow="squash bounds: hi - lo overflows",
+    bounds_pair="lo and hi: both vectors, or both NULL (bounds off)",
+    bounds_population="the bounded act with a population active is not supported (adc_engine_mlp_population(0) first)",
+    bounds_learners="learners are active: their bounds are set through adc_engine_mlp_learners_set_bounds",
+    bounds_needs_learners="the learners' bounded act needs learners (adc_engine_mlp_learners)",
+    bounds_squashed="the bounded act together with the squashed action is not supported (adc_engine_mlp_set_squash(NULL, NULL) first)",
+    bounds_two_heads="the bounded act needs the policy with the free log_std head: a two-headed policy (2A outputs) is not supported",
+    bounds_order="action bounds: finite, hi > lo",
+    bounds_overflow="action bounds: hi - lo overflows or vanishes",
+    py_no_init="mlp_init has not been called",
+)
+
+
+def _refused(kind, text, call):
+    with pytest.raises(kind) as info:
+        call()
+    assert str(info.value) == text, (str(info.value), text)
+
+
+def _walk_the_refusals(e, pol, two, seeds, refused):
+    """every successful call in order, on any engine; the refusals between them only where `refused` is _refused"""
+    from adcraft_amd import _ffi
+    STATE, VALUE = _ffi.EngineStateError, ValueError
+    K = e.num_keywords
+    lo, hi, big = np.full(K + 1, 0.5, F), np.full(K + 1, 2.0, F), np.full(K + 1, 3.0e38, F)
+    LO, HI = lo.ctypes.data, hi.ctypes.data
+    (w, b), out = pol.layers[0], np.zeros(4096, F)
+    W, B, OUT = w.ctypes.data, b.ctypes.data, out.ctypes.data
+
+    def c(name, *args, h=True):
+        return lambda: _ffi.check(getattr(e._lib, "adc_engine_mlp_" + name)(e._h if h else None, *args))
+
+    # the handle, then the policy, before anything else that is wrong with the call
+    first = (("set_layer", 2, -1, None, None), ("set_member_layer", -1, -1, None, None), ("get_member_params", -1, None),
+             ("set_learner_layer", -1, 2, -1, None, None), ("set_learner_log_std", -1, None), ("get_learner_params", -1, None),
+             ("set_squash", LO, None), ("learners_set_squash", LO, None), ("set_bounds", LO, None), ("learners_set_bounds", LO, None))
+    for name, *args in first:
+        refused(VALUE, SAID["null"], c(name, *args, h=False))
+        refused(STATE, SAID["no_init"], c(name, *args))
+    for call in (lambda: e.mlp_set_weights(pol), lambda: e.mlp_set_member(0, pol), lambda: e.mlp_set_learner(0, pol), lambda: e.mlp_learner_param_count()):
+        refused(STATE, SAID["py_no_init"], call)
+    # a two-headed policy: no log_std vector (named before the NULL vector, after the member), no bounded act
+    e.mlp_init(two, seeds)
+    e.mlp_learners(2)
+    refused(VALUE, SAID["member"], c("set_learner_log_std", 2, None))
+    refused(VALUE, SAID["two_heads"], c("set_learner_log_std", 0, None))
+    refused(STATE, SAID["bounds_two_heads"], lambda: e.mlp_learners_set_bounds(lo, hi))
+    # the single policy
+    e.mlp_init(pol, seeds)
+    refused(VALUE, SAID["network"], c("set_layer", 2, -1, None, None))
+    for net, layer in ((0, -1), (0, 3), (1, 2)):
+        refused(VALUE, SAID["layer"], c("set_layer", net, layer, None, None))
+    for pair in ((None, B), (W, None)):
+        refused(VALUE, SAID["weights"], c("set_layer", 0, 0, *pair))
+    for name, *args in first[1:3]:
+        refused(STATE, SAID["no_population"], c(name, *args))
+    for name, *args in first[3:6]:
+        refused(STATE, SAID["no_learners"], c(name, *args))
+    for name in ("mlp_set_squash", "mlp_learners_set_squash", "mlp_set_bounds", "mlp_learners_set_bounds"):
+        refused(VALUE, name + ": lo and hi, or neither", lambda: getattr(e, name)(lo, None))
+        refused(VALUE, name + ": lo and hi, or neither", lambda: getattr(e, name)(None, hi))
+    refused(STATE, SAID["squash_needs_learners"], c("learners_set_squash", LO, None))
+    refused(VALUE, SAID["bounds_pair"], c("learners_set_bounds", LO, None))
+    refused(STATE, SAID["bounds_needs_learners"], lambda: e.mlp_learners_set_bounds(lo, hi))
+    refused(VALUE, SAID["squash_order"], lambda: e.mlp_set_squash(hi, lo))
+    refused(VALUE, SAID["squash_overflow"], lambda: e.mlp_set_squash(-big, big))
+    refused(VALUE, SAID["bounds_order"], lambda: e.mlp_set_bounds(hi, lo))
+    refused(VALUE, SAID["bounds_overflow"], lambda: e.mlp_set_bounds(-big, big))
+    e.mlp_set_bounds(lo, hi)
+    refused(VALUE, SAID["squash_pair"], c("set_squash", LO, None))              # (the lone vector before the bounded act)
+    refused(STATE, SAID["squash_bounded"], lambda: e.mlp_set_squash(lo, hi))
+    e.mlp_set_bounds()
+    e.mlp_set_squash(lo, hi)
+    refused(STATE, SAID["bounds_squashed"], lambda: e.mlp_set_bounds(lo, hi))
+    e.mlp_set_squash()
+    # a population
+    e.mlp_population(2)
+    refused(VALUE, SAID["squash_pair"], c("set_squash", LO, None))              # (the lone vector before the population)
+    refused(STATE, SAID["squash_population"], lambda: e.mlp_set_squash(lo, hi))
+    refused(VALUE, SAID["bounds_pair"], c("set_bounds", LO, None))
+    refused(STATE, SAID["bounds_population"], lambda: e.mlp_set_bounds(lo, hi))
+    refused(STATE, SAID["squash_needs_learners"], c("learners_set_squash", LO, None))
+    for member in (-1, 2):
+        refused(VALUE, SAID["member"], c("set_member_layer", member, -1, None, None))
+        refused(VALUE, SAID["member"], c("get_member_params", member, None))
+    for layer in (-1, 3):
+        refused(VALUE, SAID["layer"], c("set_member_layer", 0, layer, None, None))
+    for pair in ((None, B), (W, None)):
+        refused(VALUE, SAID["weights"], c("set_member_layer", 1, 0, *pair))
+    refused(VALUE, SAID["flat_null"], c("get_member_params", 1, None))
+    for name, *args in first[3:6]:
+        refused(STATE, SAID["no_learners"], c(name, *args))
+    e.mlp_population(0)
+    # learners
+    e.mlp_learners(2)
+    for member in (-1, 2):
+        refused(VALUE, SAID["member"], c("set_learner_layer", member, 2, -1, None, None))
+        refused(VALUE, SAID["member"], c("set_learner_log_std", member, None))
+        refused(VALUE, SAID["member"], c("get_learner_params", member, None))
+    refused(VALUE, SAID["network"], c("set_learner_layer", 0, 2, -1, None, None))
+    for net, layer in ((0, -1), (0, 3), (1, 2)):
+        refused(VALUE, SAID["layer"], c("set_learner_layer", 1, net, layer, None, None))
+    for pair in ((None, B), (W, None)):
+        refused(VALUE, SAID["weights"], c("set_learner_layer", 1, 0, 0, *pair))
+    refused(VALUE, SAID["log_std_null"], c("set_learner_log_std", 1, None))
+    refused(VALUE, SAID["theta_null"], c("get_learner_params", 1, None))
+    refused(STATE, SAID["no_population"], c("set_member_layer", 0, 0, W, B))
+    refused(STATE, SAID["no_population"], c("get_member_params", 0, OUT))
+    refused(VALUE, SAID["squash_pair"], c("set_squash", LO, None))              # (the lone vector before the learners)
+    refused(STATE, SAID["squash_learners"], lambda: e.mlp_set_squash(lo, hi))
+    refused(STATE, SAID["bounds_learners"], lambda: e.mlp_set_bounds(lo, hi))
+    refused(VALUE, SAID["squash_pair"], c("learners_set_squash", LO, None))
+    refused(VALUE, SAID["squash_order"], lambda: e.mlp_learners_set_squash(hi, lo))
+    refused(VALUE, SAID["bounds_order"], lambda: e.mlp_learners_set_bounds(hi, lo))
+    e.mlp_learners_set_bounds(lo, hi)
+    refused(STATE, SAID["squash_learners_bounded"], c("learners_set_squash", LO, None))     # (the bounded act before the lone vector ...)
+    refused(VALUE, SAID["squash_pair"], c("learners_set_squash", None, HI))                 # (... which is named where no lo asks for a squash)
+    refused(STATE, SAID["squash_learners_bounded"], lambda: e.mlp_learners_set_squash(lo, hi))
+    e.mlp_learners_set_bounds()
+    e.mlp_learners_set_squash(lo, hi)
+    refused(STATE, SAID["bounds_squashed"], lambda: e.mlp_learners_set_bounds(lo, hi))
+    e.mlp_learners_set_squash()
+    e.mlp_learners(0)
+
+
+def test_every_shared_refusal_by_its_whole_sentence_and_which_one_wins(amd):
+    """4 envs, 3 keywords, policy hidden (5, 3) and value hidden (6,), free log_std (two-headed where the sentence is about it).
+    Every expectation is the parent commit's sentence and order, read off its code"""
+    N, K = 4, 3
+    rng = np.random.default_rng(7)
+    pol, two = R.ragged_policy(rng, K), R.ragged_policy(rng, K, two_heads=True)
+    seeds = np.arange(N, dtype=np.uint64) + 5
+    e, twin = (_engine(amd, N, K, seed=19) for _ in range(2))
+    _walk_the_refusals(e, pol, two, seeds, _refused)
+    _walk_the_refusals(twin, pol, two, seeds, lambda *a: None)
+    # after all of it the engine acts, and as the twin that saw no refusal
+    for x in (e, twin):
+        x.mlp_step()
+        x.mlp_act()
+    a, b = e.mlp_last(), twin.mlp_last()
+    for k in a:
+        assert _same(a[k], b[k]), k
+    for x, y in zip(e.get_actions(), twin.get_actions()):
+        assert _same(x, y)
+    assert np.abs(a["action"]).sum() > 0
+    e.close()
+    twin.close()

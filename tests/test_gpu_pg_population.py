@@ -715,3 +715,35 @@ def test_a_population_of_one_is_the_single_learner_bit_for_bit(amd, addons, queu
                 assert _same(np.float64(a["kl"][k]), np.float64(b["kl"][k])), (k, a["kl"][k], b["kl"][k], it)
             assert _same(a["coef"], b["coef"]) and a["shuffle"] == b["shuffle"], (a["coef"], b["coef"], a["shuffle"], b["shuffle"])
     assert not _same(solo[0]["state"]["theta"], solo[1]["state"]["theta"])
+
+
+def test_the_three_layer_uploads_round_trip_at_a_ragged_shape(amd):
+    """the one layer upload under mlp_set_weights, mlp_set_member and mlp_set_learner (parts/mlp_core.inc mlp_layer_upload): 4 envs,
+    3 keywords, policy hidden (5, 3), value hidden (6,), free log_std - the two networks differ in depth and no hidden width is a
+    multiple of the 4 floats the stores are padded to.  Three different policies go in; each comes back in the host's flat order
+    bit for bit, and the member nothing was uploaded to is still the centre"""
+    from tests import es_ref as E
+    N, K = 4, 3
+    rng = np.random.default_rng(611)
+    centre, member, learner = (R.ragged_policy(rng, K) for _ in range(3))
+    planes = _planes(N, K)
+    e, l = _engine(amd, planes), _engine(amd, planes)
+    e.mlp_init(centre)
+    e.mlp_population(2)
+    e.mlp_set_member(1, member)
+    assert _same(e.mlp_params(), E.flat_params(centre))
+    assert _same(e.mlp_member_params(1), E.flat_params(member)) and not _same(E.flat_params(member), E.flat_params(centre))
+    assert _same(e.mlp_member_params(0), E.flat_params(centre)), "the untouched member is the centre"
+    l.mlp_init(centre)
+    l.mlp_learners(2)
+    l.mlp_set_learner(1, learner)
+    assert l.mlp_learner_param_count() == P.flat_params(learner).size
+    assert _same(l.mlp_learner_params(1), P.flat_params(learner)) and not _same(P.flat_params(learner), P.flat_params(centre))
+    assert _same(l.mlp_learner_params(0), P.flat_params(centre)), "the untouched learner is the centre"
+    assert _same(l.mlp_params(), E.flat_params(centre))
+    # a second upload of the centre's weights: what was there goes
+    other = R.ragged_policy(rng, K)
+    e.mlp_set_weights(other)
+    assert _same(e.mlp_params(), E.flat_params(other)) and _same(e.mlp_member_params(1), E.flat_params(member))
+    e.close()
+    l.close()

@@ -826,6 +826,13 @@ ADC_HD uint64_t offset_reaching(uint32_t W, uint32_t m, uint64_t range)
 // (w - n_lo) < n_w (unsigned 32-bit arithmetic; widths fit because the word 2^32 - 1 never wins)
 struct WinIntervals { uint32_t c_lo, c_w, n_lo, n_w; };
 
+// A keyword whose two intervals are both empty wins no auction, whatever its words are: its day is all zeros and no auction of it
+// needs a draw (k_step_implicit_fast deals it no work item).  That is every bid at or below the competitor's lowest price, which
+// the bid 0 an agent says "no bid" with - 1 cent after bid_to_cents - is under every law whose competitor never offers 0 cents.
+// (The auction-by-auction DIRECT form has no such test on the bid alone: a bid is at least 1 cent, and 1 cent beats a competitor
+// at 0.)  tests/test_fast_dead_keywords_host.py: dead => no word wins.
+ADC_HD bool fast_keyword_is_dead(const WinIntervals &iv) { return iv.c_w == 0u && iv.n_w == 0u; }
+
 // from the two bounds w_lo = lower_bound_v(1 - bid), w_hi = lower_bound_v(bid):  bid > |cents|  <=>  -(bid - 1) <= S <= bid - 1
 // With D = offset_reaching the clicked wins are the words [D(w_lo), min(D(w_hi), top)) and the unclicked ones
 // [T + D(w_lo), min(T + D(w_hi), top)), top = 2^32 - 1 (words at or above it never win).  F64 = true: exactly that, on the four

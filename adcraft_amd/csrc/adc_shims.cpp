@@ -310,6 +310,53 @@ ADC_EXPORT int adc_win_intervals_offsets_host(int64_t n, const int32_t *bid_c, c
     return ADC_OK;
 }
 
+// adc::fast_keyword_is_dead for n keywords as phase 1 of k_step_implicit_fast forms it (bid in dollars -> bid_to_cents ->
+// win_intervals), next to what it claims, for tests/test_fast_dead_keywords_host.py: dead_out[i] = 1 if the dense form gives the
+// keyword no work, out4 (nullable) the intervals.
+// wins2 (nullable, two counts per keyword): over the words 0, T - 1, T, 2^32 - 2 (T = the click threshold, clipped to the words
+// there are) and n_random words of a splitmix64 stream of (seed, i), how many win by the auction-by-auction form (adc::auction_outcome
+// + adc::auction_wins: what the DIRECT form and the oracle evaluate for every auction) and how many by the two intervals.
+ADC_EXPORT int adc_fast_dead_keywords_host(int64_t n, const float *bid, const float *cost_loc, const float *cost_scale, const float *buyside_ctr,
+                                           int32_t n_random, uint64_t seed, uint8_t *dead_out, uint32_t *out4, int64_t *wins2)
+{
+    if (n < 0 || n_random < 0 || (n > 0 && (!bid || !cost_loc || !cost_scale || !buyside_ctr || !dead_out))) return ADC_EINVAL;
+    const adc::LogTableEntry *table = host_log_table();
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const int32_t bid_c = (int32_t)adc::bid_to_cents(bid[i]);
+            const adc::AuctionLaw law = adc::make_auction_law(buyside_ctr[i]);
+            const uint64_t t_click = adc::bernoulli_threshold(buyside_ctr[i]);
+            const adc::WinIntervals iv = adc::win_intervals(bid_c, cost_loc[i], cost_scale[i], t_click, law, table);
+            dead_out[i] = adc::fast_keyword_is_dead(iv) ? 1 : 0;
+            if (out4) { uint32_t *o = out4 + 4 * i; o[0] = iv.c_lo; o[1] = iv.c_w; o[2] = iv.n_lo; o[3] = iv.n_w; }
+            if (!wins2) continue;
+            int64_t by_auction = 0, by_interval = 0;
+            auto word = [&](uint32_t w) {
+                bool click;
+                const int32_t comp = adc::auction_outcome(w, law, cost_loc[i], cost_scale[i], table, click);
+                by_auction += adc::auction_wins(w, bid_c, comp) ? 1 : 0;
+                by_interval += ((w - iv.c_lo) < iv.c_w || (w - iv.n_lo) < iv.n_w) ? 1 : 0;
+            };
+            const uint64_t top = 0xFFFFFFFEull;
+            word(0u);
+            word((uint32_t)(t_click == 0 ? 0ull : t_click - 1 < top ? t_click - 1 : top));
+            word((uint32_t)(t_click < top ? t_click : top));
+            word((uint32_t)top);
+            uint64_t s = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);
+            for (int32_t r = 0; r < n_random; ++r) {
+                s += 0x9E3779B97F4A7C15ull;
+                uint64_t z = s;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                word((uint32_t)((z ^ (z >> 31)) >> 32));
+            }
+            wins2[2 * i] = by_auction;
+            wins2[2 * i + 1] = by_interval;
+        }
+    });
+    return ADC_OK;
+}
+
 // ---- what the dense fast pass hoists out of its stages (adc_law.h), next to the routines it replaces there: for
 // tests/test_law_hoists_host.py ----------------------------------------------------------------------------------------------
 // n calls: plain4 = adc::draw, folded4 = adc::draw_folded, kw4 = adc::draw_kw_folded from the keyword's half (four words each)

@@ -39,7 +39,7 @@ union alignas(16) KwWin {                     // per keyword, 16 B
     struct { unsigned int m_noclick, pad0, pad1, pad2; } d; // DIRECT form
 };
 
-// counts of a keyword-day packed in one 64-bit LDS accumulator: impressions | clicks << 21 | conversions << 42
+// counts of a keyword-day packed in one 64-bit LDS accumulator: unclicked wins | clicks << 21 | conversions << 42
 // (each is at most the day's volume <= 2^20 = adc::kVolumeMax)
 constexpr int kClkShift = 21, kConvShift = 42;
 // sh.vol[u] holds the keyword's volume in its low 21 bits and, above them, the exclusive prefix of the keywords' tail calls (at
@@ -231,14 +231,13 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     // work-item size: 16 auctions when the tile has plenty of them; 8 or 4 on sparse tiles, so that the items still
     // number about two per lane.  Results do not depend on it: every draw is addressed by (auction, keyword).
     const int chunk_shift = adc::fast_chunk_shift(tile_volume);
-    const int nch = adc::fast_full_items(V, chunk_shift);       // FULL items; the last V mod chunk auctions are the keyword's tail
-    const int ntc = adc::fast_tail_calls(V, chunk_shift);       // the whole calls of that tail, dealt as items of one call
-    // (both prefixes in one scan: adc::fast_pack_counts - a wave's full items stay below 2^23, its tail calls below 2^8)
-    const int incl = wave_scan_i32(adc::fast_pack_counts(nch, ntc));
-    if (lane == 63) sh.wave_tot[wv] = incl;
-    FSLOT_ADD(1, (unsigned long long)adc::fast_calls_needed(V));
-    // the keyword's law (only keywords with auctions need one)
+    // the keyword's law (only keywords with auctions need one), before the items are counted: a keyword that cannot win an auction
+    // (adc::fast_keyword_is_dead - a bid at or below the competitor's lowest price, as the agent's "no bid" 0 is) has a day of zeros
+    // whatever its words are, and is dealt no item, tail call or partial call.  (tile_volume, tile_live, dense and chunk_shift stay
+    // what the drawn volumes make them: they only choose the form and the item size.  A DIRECT tile has no intervals to ask, and
+    // a bid - at least 1 cent, adc::bid_to_cents - that tells nothing alone.)
     [[maybe_unused]] const unsigned long long t_law = FDBG_T();
+    bool dead = false;
     if (V > 0) {
         const uint64_t t_click = adc::bernoulli_threshold(bctr);
         const adc::AuctionLaw law = adc::make_auction_law(bctr);
@@ -249,7 +248,9 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         lb.sd = sd;
         if (dense) {
             lb.conv = adc::philox_kw_half(adc::ST_CONV, kw_base + (uint32_t)tid, (uint32_t)key);
-            sh.win[tid].iv = adc::win_intervals(bid_c, loc, scale, t_click, law, sh.logtab);
+            const adc::WinIntervals iv = adc::win_intervals(bid_c, loc, scale, t_click, law, sh.logtab);
+            sh.win[tid].iv = iv;
+            dead = adc::fast_keyword_is_dead(iv);
         } else {
             lb.d.t_click = law.t32;
             lb.d.bid_c = bid_c;
@@ -258,6 +259,13 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         sh.law_b[tid] = lb;
     }
     FDBG_ADD(1, FDBG_T() - t_law);
+    const int Vw = dead ? 0 : V;                                // the auctions that are resolved one by one
+    const int nch = adc::fast_full_items(Vw, chunk_shift);      // FULL items; the last Vw mod chunk auctions are the keyword's tail
+    const int ntc = adc::fast_tail_calls(Vw, chunk_shift);      // the whole calls of that tail, dealt as items of one call
+    // (both prefixes in one scan: adc::fast_pack_counts - a wave's full items stay below 2^23, its tail calls below 2^8)
+    const int incl = wave_scan_i32(adc::fast_pack_counts(nch, ntc));
+    if (lane == 63) sh.wave_tot[wv] = incl;
+    FSLOT_ADD(1, (unsigned long long)adc::fast_calls_needed(Vw));
     __syncthreads();
     int wave_base = 0, total = 0, wave_base2 = 0, total2 = 0;
 #pragma unroll
@@ -271,7 +279,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     sh.off[tid] = wave_base + adc::fast_packed_items(incl) - nch;
     {
         const int first_call = wave_base2 + adc::fast_packed_calls(incl) - ntc;
-        sh.vol[tid] = V | (first_call << kVolBits);
+        sh.vol[tid] = Vw | (first_call << kVolBits);         // (0 for a dead keyword: only keywords with auctions to resolve are looked up)
 #pragma unroll
         for (int c = 0; c < adc::kFastTailCallsMax; ++c)
             if (c < ntc) sh.tail_kw[first_call + c] = (unsigned char)tid;
@@ -307,8 +315,14 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     // ds_write_b32 at an 8-byte stride are each a 2-way bank conflict - measured +19 % kernel time).
     const int wq = __builtin_amdgcn_readfirstlane(wv);                      // (wave-uniform: keep the bases scalar)
     unsigned int *const qtag = sh.queue.tag[wq];
-    unsigned int *const qword = sh.queue.word[wq];
-    unsigned int qtail = 0;
+    unsigned int *const qword = qtag + sizeof(sh.queue.tag) / sizeof(unsigned int);      // sh.queue.word[wq], off the tags' own base: a slot's two reads then stay one ds_read2st64_b32
+    // the queue's fill is carried as the LDS byte address of its first free tag slot, qaddr = qbase + 4 qtail: a push forms its
+    // address from it with one v_lshl_add_u32 and advances it with one scalar shift-and-add
+    typedef __attribute__((address_space(3))) unsigned int LdsWord;
+    const unsigned int qbase = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(LdsWord *)qtag);
+    constexpr unsigned int kBatchBytes = kWave * sizeof(unsigned int);
+    static_assert(sizeof(sh.queue.tag) == 8 * 64 * sizeof(unsigned int), "a push writes the word at offset1:8 of ds_write2st64_b32");
+    unsigned int qaddr = qbase;
 
     // direct: the entry carries the price (stage A had to sample it); otherwise the auction word
     auto resolve_click = [&](bool direct) {
@@ -373,25 +387,29 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         } }
     };
     auto drain = [&](bool direct) {
-        if (qtail >= (unsigned int)kWave) {                 // checked after every push: <= 63 + 64 entries wait
+        if (qaddr >= qbase + kBatchBytes) {                 // checked after every push: <= 63 + 64 entries wait
             [[maybe_unused]] const unsigned long long tb = FDBG_T();
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             resolve_click(direct);
             // the entries behind the batch move down (a lane reads and writes only its own slots: no entry is overwritten
             // before its lane has read it)
-            qtail -= kWave;
-            if ((unsigned int)lane < qtail) { qtag[lane] = qtag[kWave + lane]; qword[lane] = qword[kWave + lane]; }
+            qaddr -= kBatchBytes;
+            if ((unsigned int)lane < (qaddr - qbase) / (unsigned int)sizeof(unsigned int)) { qtag[lane] = qtag[kWave + lane]; qword[lane] = qword[kWave + lane]; }
             FDBG_ADD(4, FDBG_T() - tb);
             FDBG_ADD(7, 1);
         }
     };
-    auto push = [&](bool click, unsigned int tagj, unsigned int payload) {
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(click);     // (the mask itself: __ballot() goes through an int)
+    // m = the ballot of the lanes that push.  All 64 lanes are active wherever phase 2 pushes (256-lane workgroups, wave-uniform
+    // control flow), so the pushing lanes are selected by writing the mask to exec around the one LDS write and all ones after it:
+    // no saved mask, and no branch over the write (with ~20 of 64 lanes clicking it is never skipped)
+    auto push = [&](unsigned long long m, unsigned int tagj, unsigned int payload) {
         const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-        // (qtail in the scalar base rather than mbcnt_lo's addend: a VOP3 reads one SGPR, and the mask already is one)
-        if (click) { (qtag + qtail)[rank] = tagj; (qword + qtail)[rank] = payload; }
-        qtail += __popcll(m);
+        // (the fill in the scalar addend rather than mbcnt_lo's: a VOP3 reads one SGPR, and the mask already is one)
+        const unsigned int slot = rank * (unsigned int)sizeof(unsigned int) + qaddr;
+        asm volatile("s_mov_b64 exec, %0\n\tds_write2st64_b32 %1, %2, %3 offset1:8\n\ts_mov_b64 exec, -1"
+                     :: "s"(m), "v"(slot), "v"(tagj), "v"(payload) : "memory");
+        qaddr += (unsigned int)__popcll(m) * (unsigned int)sizeof(unsigned int);
     };
     // one work item: auctions j0 .. j0 + n - 1 of keyword u (n == chunk unless TAIL)
     // (`calls4` = 4 x the Philox calls of the item: chunk for a full item, 4 for a tail call and for the partial call)
@@ -420,8 +438,8 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
                     bool cw = (word - iv.c_lo) < iv.c_w;                           // clicked win
                     bool nw = (word - iv.n_lo) < iv.n_w;                           // unclicked win
                     if (TAIL) { const bool active = i + h < n; cw = cw && active; nw = nw && active; }
-                    add_lane_bit(imp, __builtin_amdgcn_ballot_w64(cw) | __builtin_amdgcn_ballot_w64(nw));
-                    push(cw, tagj0 + (unsigned int)(i + h), word);
+                    add_lane_bit(imp, __builtin_amdgcn_ballot_w64(nw));            // (the clicked wins are counted in stage B: phase 3 adds them)
+                    push(__builtin_amdgcn_ballot_w64(cw), tagj0 + (unsigned int)(i + h), word);     // (the mask itself: __ballot() goes through an int)
                     drain(false);
                 }
             }
@@ -444,8 +462,8 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
                     const int comp = adc::auction_outcome_unless_top_word(word, law, ka.loc, ka.scale, sh.logtab, click_bit);
                     bool win = adc::auction_wins(word, bid_c, comp);               // tie loses (helpers.py:167-170)
                     if (TAIL) win = win && i + h < n;
-                    imp += (unsigned int)win;
-                    push(win && click_bit, tagj0 + (unsigned int)(i + h), (unsigned int)comp);
+                    imp += (unsigned int)(win && !click_bit);
+                    push(__builtin_amdgcn_ballot_w64(win && click_bit), tagj0 + (unsigned int)(i + h), (unsigned int)comp);
                     drain(true);
                 }
             }
@@ -492,14 +510,16 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         }
     }
     // the partial calls: keyword `tid`, its last V mod 4 auctions
-    // (the volume read back: nothing of phase 1 stays in a register over the passes above)
-    if (__syncthreads_or(adc::fast_partial_count(V) != 0)) {
+    // (the volume read back: nothing of phase 1 stays in a register over the passes above.  A wave none of whose 64 keywords has a
+    // partial call skips the call: the test is the wave's own ballot - the queue is per wave - and no barrier stands here)
+    {
         const int Vt = sh.vol[tid] & kVolMask;
-        run_item(std::true_type{}, tid, adc::fast_partial_first(Vt), adc::fast_partial_count(Vt), 1 << adc::kFastCallShift);
+        if (__builtin_amdgcn_ballot_w64(adc::fast_partial_count(Vt) != 0) != 0ull)
+            run_item(std::true_type{}, tid, adc::fast_partial_first(Vt), adc::fast_partial_count(Vt), 1 << adc::kFastCallShift);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if ((unsigned int)lane < qtail) resolve_click(!dense);      // fewer than 64 left
+    if ((unsigned int)lane < (qaddr - qbase) / (unsigned int)sizeof(unsigned int)) resolve_click(!dense);      // fewer than 64 left
     [[maybe_unused]] const unsigned long long t_p3 = FDBG_T();
     FDBG_ADD(3, t_p3 - t_p2);
     __syncthreads();
@@ -512,8 +532,11 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         const long long my_cost = (long long)sh.a_cost[tid];
         const long long r = (long long)sh.a_rev[tid];
         const unsigned int cnt_lo = (unsigned int)cnt, cnt_hi = (unsigned int)(cnt >> 32);      // 21-bit fields at bits 0, 21, 42
-        v.imp[o] = (int)(cnt_lo & 0x1FFFFFu);
-        v.clk[o] = (int)(((cnt_lo >> 21) | (cnt_hi << 11)) & 0x1FFFFFu);
+        // (stage A counts the unclicked wins only; an impression is a win, clicked or not: both counts are at most the day's
+        // volume <= 2^20, and so is their sum, formed here in 32 bits outside the packed word)
+        const unsigned int clicks = ((cnt_lo >> 21) | (cnt_hi << 11)) & 0x1FFFFFu;
+        v.imp[o] = (int)((cnt_lo & 0x1FFFFFu) + clicks);
+        v.clk[o] = (int)clicks;
         v.conv[o] = (int)(cnt_hi >> 10);
         v.cost[o] = adc::cents_to_dollars_f32(my_cost);
         v.rev[o] = adc::cents_to_dollars_f32(r);

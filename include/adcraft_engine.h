@@ -1642,6 +1642,13 @@ int64_t adc_proven_win_price_host(int64_t n, const int32_t *bid_cents_n, const f
  * keywords - 64 of these fill a slot}; info2 (may be NULL) = {log2 of the work-item size, 1 if the tile uses word intervals}. */
 int64_t adc_fast_schedule_host(const int32_t *vol_k, int32_t tile_kw, int32_t tile_index, int32_t *slots7, int64_t cap, int64_t *totals2,
                                int32_t *info2);
+/* diagnostic: the keywords that pass deals no work to (adc_law.h fast_keyword_is_dead: both win intervals empty, a day of zeros
+ * whatever the words are), on the host, for n keywords with the bid in dollars.  dead_n = 1 where the interval form says so;
+ * out4_n (may be NULL) = the intervals.
+ * wins2_n (may be NULL), two counts per keyword over the words 0, T - 1, T, 2^32 - 2 (T = the click threshold) and n_random words
+ * drawn with `seed`: the wins by auction-by-auction resolution, and the wins by the intervals. */
+int adc_fast_dead_keywords_host(int64_t n, const float *bid_n, const float *cost_loc_n, const float *cost_scale_n, const float *buyside_ctr_n,
+                                int32_t n_random, uint64_t seed, uint8_t *dead_n, uint32_t *out4_n, int64_t *wins2_n);
 /* one keyword of the default constructor's keyword set, on the host: exactly what adc_engine_generate_explicit_keywords writes for
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */

@@ -988,6 +988,26 @@ ADC_HD int32_t revenue_cents_tab(uint32_t w, float mu, float sd, const NormTable
     return money_to_cents(x);
 }
 
+// ---- a keyword-day's cost and revenue in one 64-bit accumulator (dense fast pass: cost in the low word, revenue in the high) -----
+// The largest revenue of one conversion, in cents.  |normal_tab| <= z_max = norm_table_node(0), the table's largest node (every
+// interval interpolates from its left node towards a smaller one), so fma32(sd, z, mu) <= fma32(|sd|, z_max, |mu|) (the exact values
+// compare so, and one rounding is monotone), and max(., 0.01) and money_to_cents are monotone.  NaN if mu or sd is.
+ADC_HD float revenue_dollars_max(float mu, float sd, float z_max) { return fma32(__builtin_fabsf(sd), z_max, __builtin_fabsf(mu)); }
+// Whether V auctions of a keyword bid at bid_c cents can never take either half past 32 bits: a clicked win costs at most
+// bid_c - 1 cents (it is a win) and a conversion brings at most r_max, so the day's cost is at most V (bid_c - 1) and its revenue at
+// most V r_max.  Evaluated in float32 (phase 1, once per keyword): V <= 2^20 is exact, the two conversions and the product are
+// off by less than 2^-22 together, and the products are compared with 4.0e9 - 7 % below 2^32 - so no product of 2^32 or more is
+// admitted.  A revenue bound of 1e7 dollars or more (money_to_cents would clamp it), infinite or NaN never packs.
+constexpr float kPackedMoneyLimit = 4.0e9f;
+ADC_HD bool fast_money_packs(int32_t V, int32_t bid_c, float mu, float sd, float z_max)
+{
+    const float r = revenue_dollars_max(mu, sd, z_max);
+    if (!(r < 1.0e7f)) return false;
+    const float fv = (float)V;
+    const float r_max = (float)money_to_cents(r > 0.01f ? r : 0.01f);
+    return fv * r_max < kPackedMoneyLimit && fv * (float)(bid_c - 1) < kPackedMoneyLimit;
+}
+
 ADC_HD int32_t revenue_cents(uint32_t w, float mu, float sd)
 {
     float x = fma32(sd, normal_from_word(w), mu);

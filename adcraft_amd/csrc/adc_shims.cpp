@@ -428,6 +428,46 @@ ADC_EXPORT int64_t adc_proven_win_price_host(int64_t n, const int32_t *bid_c, co
     return bad;
 }
 
+// ---- the packed money accumulator of k_step_implicit_fast (adc_law.h fast_money_packs), for tests/test_fast_packed_money_host.py ----
+struct HostNormTables { adc::NormTableEntry entry[adc::kNormTableEntries]; float node[adc::kNormTableEntries + 1]; };
+static const HostNormTables *host_norm_tables()
+{
+    // (a function-local static built by a lambda: initialised once, whichever thread comes first)
+    static const HostNormTables t = [] {
+        HostNormTables r;
+        for (int i = 0; i < adc::kNormTableEntries; ++i) r.entry[i] = adc::norm_table_entry(i);
+        for (int i = 0; i <= adc::kNormTableEntries; ++i) r.node[i] = adc::norm_table_node(i);
+        return r;
+    }();
+    return &t;
+}
+
+// For n keyword-days (volume, bid in dollars, revenue law), as phase 1 of the kernel asks: packs[i] = adc::fast_money_packs;
+// bid_c[i] = adc::bid_to_cents; r_max[i] = the revenue bound in cents the predicate multiplies (-1 where the bound in dollars is not
+// below 1e7: NaN, infinite or too large to pack at any volume); rev[i * n_words + j] = adc::revenue_cents_tab at words[j].
+// *z_max_out (nullable) = the table's largest node.
+ADC_EXPORT int adc_fast_money_packs_host(int64_t n, const int32_t *volume, const float *bid, const float *rev_mean, const float *rev_std,
+                                         const uint32_t *words, int32_t n_words, uint8_t *packs, int32_t *bid_c, int64_t *r_max, int32_t *rev,
+                                         float *z_max_out)
+{
+    if (n < 0 || n_words < 0 || (n > 0 && (!volume || !bid || !rev_mean || !rev_std || !packs || !bid_c || !r_max)) || (n_words > 0 && (!words || !rev)))
+        return ADC_EINVAL;
+    const HostNormTables *t = host_norm_tables();
+    const float z_max = t->node[0];
+    if (z_max_out) *z_max_out = z_max;
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const int32_t bc = (int32_t)adc::bid_to_cents(bid[i]);
+            bid_c[i] = bc;
+            packs[i] = adc::fast_money_packs(volume[i], bc, rev_mean[i], rev_std[i], z_max) ? 1 : 0;
+            const float r = adc::revenue_dollars_max(rev_mean[i], rev_std[i], z_max);
+            r_max[i] = r < 1.0e7f ? (int64_t)adc::money_to_cents(r > 0.01f ? r : 0.01f) : -1;
+            for (int32_t j = 0; j < n_words; ++j) rev[i * n_words + j] = adc::revenue_cents_tab(words[j], rev_mean[i], rev_std[i], t->entry);
+        }
+    });
+    return ADC_OK;
+}
+
 // ---- the host twin of k_step_implicit_fast's phase-2 schedule (adc_fast_schedule.h: the helpers the kernel calls) ------------
 // For tile number tile_index (env x tiles-per-env + tile: it only rotates which wave takes which part of the items) of tile_kw
 // keywords with the given volumes: every (pass, wave, round, lane) slot the kernel issues, as rows of

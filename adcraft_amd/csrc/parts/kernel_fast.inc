@@ -63,6 +63,7 @@ struct FastShared {
         struct {                                            // phase 1 (before the queues are used)
             unsigned int volw[kFastBlock];                  // volume words of the tile's keywords
             int wave_tot[kFastBlock / kWave], wave_vol[kFastBlock / kWave], wave_live[kFastBlock / kWave];
+            int wave_wide[kFastBlock / kWave];             // 1: a keyword of the wave needs the cost and the revenue in accumulators of their own
         };
     };
     KwWin win[kFastBlock];
@@ -217,16 +218,23 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             if (tid == 0) ls.price_cut = v.click_price_hint[env];
         }
     }
-    // tile volume and number of keywords with auctions -> the form this tile is resolved in, and its work-item size
+    // tile volume and number of keywords with auctions -> the form this tile is resolved in, and its work-item size; and whether
+    // every keyword-day of the tile keeps its cost and its revenue below 2^32 cents each (adc::fast_money_packs: a bound from the
+    // volume, the bid and the revenue law) - a clicked win then adds both with one atomic, the revenue in the high word of a_cost
+    const int bid_c = (int)adc::bid_to_cents(bid);
     {
         const int vsum = wave_sum_i32(V);
         const int live = (int)__popcll(__builtin_amdgcn_ballot_w64(V > 0));
-        if (lane == 0) { sh.wave_vol[wv] = vsum; sh.wave_live[wv] = live; }
+        const bool wide = V > 0 && !adc::fast_money_packs(V, bid_c, mu, sd, sh.normtab[0]);      // (normtab[0]: the largest node)
+        const int any_wide = __builtin_amdgcn_ballot_w64(wide) != 0ull ? 1 : 0;
+        if (lane == 0) { sh.wave_vol[wv] = vsum; sh.wave_live[wv] = live; sh.wave_wide[wv] = any_wide; }
     }
     __syncthreads();
-    int tile_volume = 0, tile_live = 0;
+    int tile_volume = 0, tile_live = 0, tile_wide = 0;
 #pragma unroll
-    for (int i = 0; i < kFastBlock / kWave; ++i) { tile_volume += sh.wave_vol[i]; tile_live += sh.wave_live[i]; }
+    for (int i = 0; i < kFastBlock / kWave; ++i) { tile_volume += sh.wave_vol[i]; tile_live += sh.wave_live[i]; tile_wide |= sh.wave_wide[i]; }
+    // (tile-uniform, in an SGPR: all ones where the tile packs)
+    const unsigned int pack_mask = __builtin_amdgcn_readfirstlane(tile_wide) == 0 ? 0xFFFFFFFFu : 0u;
     const bool dense = adc::fast_tile_dense(tile_volume, tile_live);               // (block-uniform)
     // work-item size: 16 auctions when the tile has plenty of them; 8 or 4 on sparse tiles, so that the items still
     // number about two per lane.  Results do not depend on it: every draw is addressed by (auction, keyword).
@@ -241,7 +249,6 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     if (V > 0) {
         const uint64_t t_click = adc::bernoulli_threshold(bctr);
         const adc::AuctionLaw law = adc::make_auction_law(bctr);
-        const int bid_c = (int)adc::bid_to_cents(bid);
         sh.law_a[tid] = KwLawA{law.m_click, adc::saturate_threshold(adc::bernoulli_threshold(sctr)), loc, scale};
         KwLawB lb;
         lb.mu = mu;
@@ -351,14 +358,17 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
                                   : adc::draw_kw_folded(key, ent.x & 0x00FFFFFFu, kb.conv, tick_k1);
         const bool conv = adc::bernoulli32(w2.x, ka.t_conv);
         unsigned long long cnt = 1ull << kClkShift;
+        unsigned int rev_c = 0u;
         if (conv) {
             float x = adc::fma32(kb.sd, normal_tab_nodes(w2.y, sh.normtab), kb.mu);
             x = x > 0.01f ? x : 0.01f;
-            atomicAdd(acc + 2 * kFastBlock, (unsigned long long)(unsigned int)adc::money_to_cents(x));      // a_rev[uu] (>= 1 cent: no sign to extend)
+            rev_c = (unsigned int)adc::money_to_cents(x);                                       // (>= 1 cent: no sign to extend)
+            if (pack_mask == 0u) atomicAdd(acc + 2 * kFastBlock, (unsigned long long)rev_c);    // a_rev[uu]: only a tile that does not pack
             cnt |= 1ull << kConvShift;
         }
         atomicAdd(acc, cnt);
-        atomicAdd(acc + kFastBlock, (unsigned long long)price);
+        // a_cost[uu]: the price, and in a tile that packs the revenue above it (neither half can carry: adc::fast_money_packs)
+        atomicAdd(acc + kFastBlock, (unsigned long long)price | ((unsigned long long)(rev_c & pack_mask) << 32));
         if constexpr (LISTS) { if (raw.emit) {
             // (block-uniform) the env's budget bound yesterday: list the clicked win for k_step_click_walk, by sub-timestep
             // (adc::cell_range inverted: the quotient estimated in float32 - exact operands below 2^24 - and fixed up)
@@ -529,8 +539,10 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     if (valid) {
         const size_t o = (size_t)env * v.K + k;
         const unsigned long long cnt = sh.a_cnt[tid];
-        const long long my_cost = (long long)sh.a_cost[tid];
-        const long long r = (long long)sh.a_rev[tid];
+        // (a tile that packs: cost | revenue << 32 in a_cost, a_rev unused)
+        const unsigned long long cw = sh.a_cost[tid];
+        const long long my_cost = pack_mask ? (long long)(unsigned int)cw : (long long)cw;
+        const long long r = pack_mask ? (long long)(cw >> 32) : (long long)sh.a_rev[tid];
         const unsigned int cnt_lo = (unsigned int)cnt, cnt_hi = (unsigned int)(cnt >> 32);      // 21-bit fields at bits 0, 21, 42
         // (stage A counts the unclicked wins only; an impression is a win, clicked or not: both counts are at most the day's
         // volume <= 2^20, and so is their sum, formed here in 32 bits outside the packed word)
@@ -550,9 +562,10 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         for (int i = 0; i < kFastBlock / kWave; ++i) {
             const int u = lane + i * kWave;
             if (u < tile_kw && tile * tile_kw + u < v.K) {
-                const long long cc = (long long)sh.a_cost[u];
+                const unsigned long long cw = sh.a_cost[u];
+                const long long cc = pack_mask ? (long long)(unsigned int)cw : (long long)cw;
                 c += cc;
-                p += (long long)sh.a_rev[u] - cc;
+                p += (pack_mask ? (long long)(cw >> 32) : (long long)sh.a_rev[u]) - cc;
             }
         }
         c = wave_sum_i64(c);

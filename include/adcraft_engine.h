@@ -1649,6 +1649,14 @@ int64_t adc_fast_schedule_host(const int32_t *vol_k, int32_t tile_kw, int32_t ti
  * drawn with `seed`: the wins by auction-by-auction resolution, and the wins by the intervals. */
 int adc_fast_dead_keywords_host(int64_t n, const float *bid_n, const float *cost_loc_n, const float *cost_scale_n, const float *buyside_ctr_n,
                                 int32_t n_random, uint64_t seed, uint8_t *dead_n, uint32_t *out4_n, int64_t *wins2_n);
+/* diagnostic: whether that pass keeps a keyword-day's cost and revenue in one 64-bit accumulator (adc_law.h fast_money_packs), on the
+ * host, for n keyword-days (volume, bid in dollars, revenue law).  packs_n = 1 where the predicate says so; bid_c_n = the bid in
+ * cents; r_max_n = the revenue bound of one conversion in cents that the predicate multiplies, -1 where the bound in dollars is NaN,
+ * infinite or 1e7 and more (never packs); rev (may be NULL with n_words 0) = the revenue in cents at each of `words`, [n][n_words];
+ * *z_max_out (may be NULL) = the normal table's largest node. */
+int adc_fast_money_packs_host(int64_t n, const int32_t *volume_n, const float *bid_n, const float *rev_mean_n, const float *rev_std_n,
+                              const uint32_t *words, int32_t n_words, uint8_t *packs_n, int32_t *bid_c_n, int64_t *r_max_n, int32_t *rev,
+                              float *z_max_out);
 /* one keyword of the default constructor's keyword set, on the host: exactly what adc_engine_generate_explicit_keywords writes for
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */

@@ -72,8 +72,15 @@
 //        the merge, the new vectors (adc_norm.h; over raw rows for the TD3 learners, adc_td3_norm.h); the discounted returns' scan under
 //        the learner's discount, their moments, the merge, the multiplier, the GAE kernels under a multiplier and a clip (adc_rew_norm.h);
 //        the batched copy.  The batch kernels of kernel_td3 / kernel_td3_pop and of kernel_sac / kernel_sac_pop (adc_sac_norm.h) normalise as they gather.
-//   parts/host_api.inc            the engine object and the extern "C" entry points of the engine itself: the step, the tape, metrics,
-//                                 curves, the zero-margin and the interpolation agent.
+//   parts/host_api.inc            the engine's core on the host: the engine object, the env groups and their streams, owned allocations and
+//                                 the holder of a call's temporaries (DevTemps), the step's launch and fetch, create and destroy, the
+//                                 entry guards, and the entry points of the step itself.
+//   parts/env_api.inc             the entry points that set or read the envs: parameters, keyword generation, reset, limits, drift, RNG
+//                                 and episode state, buffers, env groups, the stream, flat actions and observations, the profile.
+//   parts/tape_api.inc            the entry points of the tape replay and of the per-click outcome lists.
+//   parts/curves_api.inc          the entry points of the episode metrics, the ideal profit, the bid curves and the oracle bidder.
+//   parts/agent_api.inc           the entry points of the zero-margin agent and of the interpolation agent.
+//   parts/selftest_api.inc        the device self-tests that take a device id and no engine, and the debug readers.
 //   parts/mlp_core.inc            what the host files of the learned agent and the trainers' files share: owned allocations, the
 //                                 agent's view and launch, a day of the agent, the parameter stores and the flat order against them,
 //                                 the shared entry checks, the layer upload - and the lifetime chain (who ends when what ends).
@@ -164,6 +171,11 @@ namespace adck {
 using namespace adck;
 
 #include "parts/host_api.inc"
+#include "parts/env_api.inc"
+#include "parts/tape_api.inc"
+#include "parts/curves_api.inc"
+#include "parts/agent_api.inc"
+#include "parts/selftest_api.inc"
 #include "parts/mlp_core.inc"
 #include "parts/mlp_api.inc"
 #include "parts/es_api.inc"

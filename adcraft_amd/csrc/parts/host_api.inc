@@ -1,8 +1,9 @@
-// host_api.inc - engine object and the extern "C" entry points of include/adcraft_engine.h
+// host_api.inc - the engine's core on the host (include/adcraft_engine.h): the engine object; the env groups, their streams and views;
+// owned allocations (dev_alloc) and the holder of a call's temporaries (DevTemps); the profile flush and the volume hint; the step's
+// plan, launch and fetch, launch_chained; create and destroy; the entry guards; the entry points of the step itself.  What sets or
+// reads the envs is parts/env_api.inc, the tape parts/tape_api.inc, metrics and curves parts/curves_api.inc, the two hand-written
+// agents parts/agent_api.inc, the engine-less self-tests parts/selftest_api.inc: all of them are written over this file.
 // (part of the single translation unit adc_engine.hip; see that file for the overview)
-// -------------------------------------------------------------------------------------------------
-// host side
-// -------------------------------------------------------------------------------------------------
 // a set of running normalisers fed from the rollout record (parts/kernel_norm.inc, parts/norm_api.inc): an observation part, a
 // reward part, or both; a part that does not live has a null count
 struct NormSet {
@@ -467,6 +468,43 @@ int dev_alloc(adc_engine *e, T **p, size_t count)
     *p = static_cast<T *>(q);
     return ADC_OK;
 }
+
+// The device temporaries of one call - host arrays staged for a kernel, scratch a result is copied out of - on the stream the call
+// works on.  get allocates, up allocates and enqueues the upload; neither words an error: the call site has its own sentence.
+// release() frees them, and stands where the call has just waited for that stream itself.  A call that returns before it leaves
+// them to the destructor, which waits for the stream first: nothing is freed under a copy or a kernel in flight, and nothing
+// relies on hipFree's own wait.
+struct DevTemps {
+    hipStream_t stream;
+    std::vector<void *> held;
+    explicit DevTemps(hipStream_t s) : stream(s) {}
+    DevTemps(const DevTemps &) = delete;
+    DevTemps &operator=(const DevTemps &) = delete;
+    ~DevTemps()
+    {
+        if (held.empty()) return;
+        (void)hipStreamSynchronize(stream);
+        release();
+    }
+    template <typename T>
+    hipError_t get(T **p, size_t bytes)
+    {
+        const hipError_t err = hipMalloc((void **)p, bytes);
+        if (err == hipSuccess) held.push_back(*p);
+        return err;
+    }
+    template <typename T>
+    hipError_t up(T **p, const void *host, size_t bytes)
+    {
+        const hipError_t err = get(p, bytes);
+        return err != hipSuccess ? err : hipMemcpyAsync(*p, host, bytes, hipMemcpyHostToDevice, stream);
+    }
+    void release()
+    {
+        for (void *q : held) (void)hipFree(q);
+        held.clear();
+    }
+};
 
 int flush_profile(adc_engine *e)
 {
@@ -1152,272 +1190,6 @@ int launch_chained(adc_engine *e, Launch launch)
 }
 }  // namespace
 
-ADC_EXPORT int adc_engine_set_params(adc_engine *e, int param_id, const float *host_nk)
-{
-    ENGINE_GUARD(e);
-    if (param_id < 0 || param_id >= ADC_P_COUNT || !host_nk) return fail(ADC_EINVAL, "bad param_id or NULL buffer");
-    const size_t NK = (size_t)e->v.N * e->v.K;
-    HIP_TRY(hipMemcpyAsync(e->v.params + (size_t)param_id * NK, host_nk, NK * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (param_id == ADC_P_VOL_MEAN) e->volume_hint_dirty = true;
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_get_params(adc_engine *e, int param_id, float *host_nk)
-{
-    ENGINE_GUARD(e);
-    if (param_id < 0 || param_id >= ADC_P_COUNT || !host_nk) return fail(ADC_EINVAL, "bad param_id or NULL buffer");
-    const size_t NK = (size_t)e->v.N * e->v.K;
-    if (e->v.drift_on) {
-        materialize_drift(e);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(host_nk, e->v.params + (size_t)param_id * NK, NK * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_env_params(adc_engine *e, int env, const float *host_8k)
-{
-    ENGINE_GUARD(e);
-    if (env < 0 || env >= e->v.N || !host_8k) return fail(ADC_EINVAL, "env out of range or NULL buffer");
-    const size_t K = e->v.K, NK = (size_t)e->v.N * K;
-    for (int p = 0; p < ADC_P_COUNT; ++p)
-        HIP_TRY(hipMemcpyAsync(e->v.params + p * NK + env * K, host_8k + p * K, K * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->volume_hint_dirty = true;
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_generate_keywords(adc_engine *e, const adc_quantiles *q, float no_vol_prob, uint32_t serial,
-                                            const uint8_t *env_mask)
-{
-    ENGINE_GUARD(e);
-    if (e->v.model != ADC_MODEL_IMPLICIT) return fail(ADC_EINVAL, "device keyword generation is provided for IMPLICIT keywords");
-    if (!q) return fail(ADC_EINVAL, "quantile tables are NULL");
-    std::vector<void *> tmp;
-    auto cleanup = [&]() { for (void *p : tmp) (void)hipFree(p); };
-    KeygenTables tabs;
-    for (int i = 0; i < 7; ++i) {
-        const int B = q->buckets[i];
-        if (B <= 0 || !q->mins[i] || !q->medians[i] || !q->maxs[i]) { cleanup(); return fail(ADC_EINVAL, "every quantity needs at least one bucket"); }
-        float *d = nullptr;
-        if (hipMalloc((void **)&d, (size_t)B * 12) != hipSuccess) { cleanup(); return fail(ADC_ENOMEM, "hipMalloc (quantiles) failed"); }
-        tmp.push_back(d);
-        if (hipMemcpyAsync(d, q->mins[i], (size_t)B * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(d + B, q->medians[i], (size_t)B * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(d + 2 * B, q->maxs[i], (size_t)B * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess) { cleanup(); return fail(ADC_EHIP, "quantile upload failed"); }
-        tabs.t[i] = adc::QuantileTable{d, d + B, d + 2 * B, B};
-    }
-    uint8_t *d_mask = nullptr;
-    if (env_mask) {
-        if (hipMalloc((void **)&d_mask, (size_t)e->v.N) != hipSuccess) { cleanup(); return fail(ADC_ENOMEM, "hipMalloc (mask) failed"); }
-        tmp.push_back(d_mask);
-        if (hipMemcpyAsync(d_mask, env_mask, (size_t)e->v.N, hipMemcpyHostToDevice, e->stream) != hipSuccess) { cleanup(); return fail(ADC_EHIP, "mask upload failed"); }
-    }
-    hipLaunchKernelGGL(k_generate_keywords, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)e->v.N), dim3(256), 0, e->stream, e->v, tabs,
-                       no_vol_prob, serial, d_mask);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    cleanup();
-    HIP_TRY(err);
-    e->volume_hint_dirty = true;
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_generate_explicit_keywords(adc_engine *e, uint32_t serial, const uint8_t *env_mask)
-{
-    ENGINE_GUARD(e);
-    if (e->v.model != ADC_MODEL_EXPLICIT) return fail(ADC_EINVAL, "sample_random_keywords' law is the EXPLICIT model's (IMPLICIT keywords: adc_engine_generate_keywords)");
-    uint8_t *d_mask = nullptr;
-    if (env_mask) {
-        if (hipMalloc((void **)&d_mask, (size_t)e->v.N) != hipSuccess) { (void)hipGetLastError(); return fail(ADC_ENOMEM, "hipMalloc (mask) failed"); }
-        if (hipMemcpyAsync(d_mask, env_mask, (size_t)e->v.N, hipMemcpyHostToDevice, e->stream) != hipSuccess) { (void)hipFree(d_mask); return fail(ADC_EHIP, "mask upload failed"); }
-    }
-    hipLaunchKernelGGL(k_generate_explicit_keywords, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)e->v.N), dim3(256), 0, e->stream, e->v, serial, d_mask);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (d_mask) (void)hipFree(d_mask);
-    HIP_TRY(err);
-    e->volume_hint_dirty = true;
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const uint64_t *seeds)
-{
-    ENGINE_GUARD(e);
-    const size_t N = e->v.N;
-    uint8_t *d_mask = nullptr;
-    uint64_t *d_seeds = nullptr;
-    if (env_mask) { HIP_TRY(hipMalloc((void **)&d_mask, N)); HIP_TRY(hipMemcpyAsync(d_mask, env_mask, N, hipMemcpyHostToDevice, e->stream)); }
-    if (seeds) { HIP_TRY(hipMalloc((void **)&d_seeds, N * 8)); HIP_TRY(hipMemcpyAsync(d_seeds, seeds, N * 8, hipMemcpyHostToDevice, e->stream)); }
-    hipLaunchKernelGGL(k_reset, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, e->v, d_mask, d_seeds);
-    hipError_t err = hipGetLastError();
-    // the observation reset() returns is all zeros (gymnasium_kw_env.py:329-344): device-resident callers read it
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_clear_obs, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->v, d_mask);
-        err = hipGetLastError();
-    }
-    // (a reset env's running discounted return ends with its episode, the PPO / A2C learners', the TD3 learners' and the SAC
-    //  learners'; nothing is enqueued without a reward normaliser)
-    for (const NormSet *s : {&e->rn, &e->tn, &e->sn}) {
-        if (err != hipSuccess || !s->rew.G) continue;
-        hipLaunchKernelGGL(k_rew_norm_carry_reset, dim3((unsigned)((N + kRewNormBlock - 1) / kRewNormBlock)), dim3(kRewNormBlock), 0, e->stream, (int)N, d_mask,
-                           s->rew.G);
-        err = hipGetLastError();
-    }
-    // (... and so does its observation history; nothing is enqueued without one)
-    if (err == hipSuccess && e->have_mlp && e->mp.hist) {
-        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, d_mask, e->mp.last);
-        err = hipGetLastError();
-    }
-    hipError_t err2 = hipStreamSynchronize(e->stream);
-    if (d_mask) (void)hipFree(d_mask);
-    if (d_seeds) (void)hipFree(d_seeds);
-    HIP_TRY(err);
-    HIP_TRY(err2);
-    e->have_reset = true;
-    e->last_step = 0;
-    e->stream_steps = 0;
-    e->env_moves += 1;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_limits(adc_engine *e, int32_t max_days, double loss_threshold)
-{
-    ENGINE_GUARD(e);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->v.max_days = max_days;
-    e->v.loss_threshold = loss_threshold;
-    e->cfg.max_days = max_days;
-    e->cfg.loss_threshold = loss_threshold;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_drift(adc_engine *e, int32_t enabled, float drift_vol, float drift_ctr, float drift_cvr)
-{
-    ENGINE_GUARD(e);
-    if (!enabled && e->v.drift_on) {      // apply what is pending under the old setting, then switch off
-        materialize_drift(e);
-        HIP_TRY(hipGetLastError());
-        forget_replayable_steps(e);       // (the parameters have moved, and with drift off nothing would say so any more)
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->v.drift_on = enabled ? 1 : 0;
-    e->v.drift_vol = drift_vol; e->v.drift_ctr = drift_ctr; e->v.drift_cvr = drift_cvr;
-    if (!enabled) HIP_TRY(hipMemsetAsync(e->v.drift_pending, 0, (size_t)e->v.N, e->stream));
-    return ADC_OK;
-}
-
-namespace {
-// what adc_engine_set_drift_mask / adc_engine_set_env_drift do before they swap: the pending update_keywords() of every env is
-// the one the previous step scheduled, so it moves the planes under the selection and magnitudes in force when it was
-// scheduled; then nothing in flight reads the old device copy when it is overwritten
-int settle_pending_drift(adc_engine *e)
-{
-    if (e->v.drift_on) {
-        materialize_drift(e);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_set_drift_mask(adc_engine *e, const uint8_t *mask_nk)
-{
-    ENGINE_GUARD(e);
-    { const int rc = settle_pending_drift(e); if (rc) return rc; }
-    if (!mask_nk) { e->v.drift_bits = nullptr; return ADC_OK; }
-    const size_t N = (size_t)e->v.N, K = (size_t)e->v.K, W = (K + 31) / 32;
-    std::vector<uint32_t> bits(N * W, 0u);
-    for (size_t n = 0; n < N; ++n)
-        for (size_t k = 0; k < K; ++k)
-            if (mask_nk[n * K + k]) bits[n * W + k / 32] |= 1u << (k % 32);
-    if (!e->d_drift_bits) { const int rc = dev_alloc(e, &e->d_drift_bits, N * W); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(e->d_drift_bits, bits.data(), N * W * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->v.drift_bits = e->d_drift_bits;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_env_drift(adc_engine *e, const float *rates_n3)
-{
-    ENGINE_GUARD(e);
-    { const int rc = settle_pending_drift(e); if (rc) return rc; }
-    if (!rates_n3) { e->v.drift_rate = nullptr; return ADC_OK; }
-    const size_t N = (size_t)e->v.N;
-    if (!e->d_drift_rate) { const int rc = dev_alloc(e, &e->d_drift_rate, N * 3); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(e->d_drift_rate, rates_n3, N * 3 * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->v.drift_rate = e->d_drift_rate;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_get_rng_state(adc_engine *e, uint64_t *keys_n, uint32_t *ticks_n)
-{
-    ENGINE_GUARD(e);
-    const size_t N = e->v.N;
-    if (keys_n) HIP_TRY(hipMemcpyAsync(keys_n, e->v.key, N * 8, hipMemcpyDeviceToHost, e->stream));
-    if (ticks_n) HIP_TRY(hipMemcpyAsync(ticks_n, e->v.tick, N * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_rng_state(adc_engine *e, const uint64_t *keys_n, const uint32_t *ticks_n)
-{
-    ENGINE_GUARD(e);
-    const size_t N = e->v.N;
-    if (keys_n) HIP_TRY(hipMemcpyAsync(e->v.key, keys_n, N * 8, hipMemcpyHostToDevice, e->stream));
-    if (ticks_n) HIP_TRY(hipMemcpyAsync(e->v.tick, ticks_n, N * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_get_episode_state(adc_engine *e, int32_t *day_n, double *cum_profit_n)
-{
-    ENGINE_GUARD(e);
-    const size_t N = e->v.N;
-    if (day_n) HIP_TRY(hipMemcpyAsync(day_n, e->v.day, N * 4, hipMemcpyDeviceToHost, e->stream));
-    if (cum_profit_n) {
-        if (e->v.model == ADC_MODEL_IMPLICIT) {
-            std::vector<int64_t> c(N);
-            HIP_TRY(hipMemcpyAsync(c.data(), e->v.cum_cents, N * 8, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            for (size_t i = 0; i < N; ++i) cum_profit_n[i] = (double)c[i] / 100.0;
-        } else {
-            HIP_TRY(hipMemcpyAsync(cum_profit_n, e->v.cum, N * 8, hipMemcpyDeviceToHost, e->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_episode_state(adc_engine *e, const int32_t *day_n, const double *cum_profit_n)
-{
-    ENGINE_GUARD(e);
-    const size_t N = e->v.N;
-    if (day_n) HIP_TRY(hipMemcpyAsync(e->v.day, day_n, N * 4, hipMemcpyHostToDevice, e->stream));
-    if (cum_profit_n) {
-        std::vector<int64_t> c(N);
-        for (size_t i = 0; i < N; ++i) c[i] = (int64_t)std::llrint(cum_profit_n[i] * 100.0);
-        HIP_TRY(hipMemcpyAsync(e->v.cum_cents, c.data(), N * 8, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->v.cum, cum_profit_n, N * 8, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->have_reset = true;
-    e->last_step = 0;
-    e->stream_steps = 0;
-    e->env_moves += 1;
-    return ADC_OK;
-}
-
 ADC_EXPORT int adc_engine_step_device(adc_engine *e, const float *d_bids_nk, const float *d_budget_n)
 {
     ENGINE_GUARD_STEP(e);
@@ -1545,1325 +1317,3 @@ ADC_EXPORT int adc_engine_step_flat(adc_engine *e, const float *flat_actions, fl
     HIP_TRY(hipStreamSynchronize(e->stream));
     return ADC_OK;
 }
-
-// The paid clicks of one env-step, one by one (see ReplayOut): a read-only second walk of that env-step in the reference's order
-// by the serial walker - at the stream position the step had (tape == null), or over the caller's tape.
-static int outcomes_walk(adc_engine *e, int32_t env, unsigned int ticks_back, const float *bids_k, float budget, const TapeView *tape, int64_t capacity,
-                         int32_t *keyword, int32_t *timestep, double *cost, double *revenue, int64_t *count, int32_t *share_volume_k)
-{
-    const View &v = e->v;
-    if (env < 0 || env >= v.N) return fail(ADC_EINVAL, "env out of range");
-    if (!bids_k || !count || capacity < 0 || capacity > (1ll << 28)) return fail(ADC_EINVAL, "bids_k / count is NULL or capacity out of range");
-    if (capacity > 0 && (!keyword || !timestep || !cost || !revenue)) return fail(ADC_EINVAL, "output lists are NULL");
-    const size_t K = (size_t)v.K, cap = (size_t)capacity;
-    const size_t lds = K * (4 * 4 + 3 * 8);
-    if (lds > 160 * 1024) return fail(ADC_EINVAL, "num_keywords too large for the walker (LDS)");
-    HIP_TRY(hipStreamSynchronize(e->stream));           // the step itself has finished
-    unsigned char *d = nullptr;
-    const size_t b_rec = (cap ? cap : 1) * sizeof(int4), b_cost = (cap ? cap : 1) * 8, b_bids = K * 4, b_share = K * 4;
-    if (hipMalloc((void **)&d, b_rec + b_cost + b_bids + b_share + 16) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc failed");
-    auto done = [&](int code) { (void)hipFree(d); return code; };
-    ReplayOut rp{};
-    rp.records = reinterpret_cast<int4 *>(d);
-    rp.costs = reinterpret_cast<double *>(d + b_rec);
-    float *d_bids = reinterpret_cast<float *>(d + b_rec + b_cost);
-    rp.share_volume = reinterpret_cast<int *>(d + b_rec + b_cost + b_bids);
-    rp.count = reinterpret_cast<int *>(d + b_rec + b_cost + b_bids + b_share);
-    rp.bids_env = d_bids;
-    rp.budget = budget;
-    rp.capacity = (int)capacity;
-    rp.env = env;
-    rp.ticks_back = ticks_back;
-    if (hipMemcpyAsync(d_bids, bids_k, b_bids, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemsetAsync(rp.share_volume, 0, b_share + 16, e->stream) != hipSuccess)
-        return done(fail(ADC_EHIP, "upload failed"));
-    TapeView none{};
-#define WALK(MODEL) \
-    if (tape) hipLaunchKernelGGL((k_step_exact<MODEL, true>), dim3(1), dim3(kWave), lds, e->stream, v, d_bids, e->d_budget, *tape, 0, rp); \
-    else hipLaunchKernelGGL((k_step_exact<MODEL, false>), dim3(1), dim3(kWave), lds, e->stream, v, d_bids, e->d_budget, none, 0, rp)
-    if (v.model == ADC_MODEL_IMPLICIT) { WALK(ADC_MODEL_IMPLICIT); }
-    else if (v.model == ADC_MODEL_IMPLICIT_GENERAL) { WALK(ADC_MODEL_IMPLICIT_GENERAL); }
-    else { WALK(ADC_MODEL_EXPLICIT); }
-#undef WALK
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return done(fail(ADC_EHIP, "replay kernel failed"));
-    int n = 0;
-    if (hipMemcpy(&n, rp.count, 4, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(ADC_EHIP, "download failed"));
-    *count = n;
-    const size_t m = std::min<size_t>((size_t)std::max(n, 0), cap);
-    if (m) {
-        std::vector<int4> rec(m);
-        if (hipMemcpy(rec.data(), rp.records, m * sizeof(int4), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(cost, rp.costs, m * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return done(fail(ADC_EHIP, "download failed"));
-        for (size_t i = 0; i < m; ++i) {
-            keyword[i] = rec[i].x;
-            timestep[i] = rec[i].y;
-            revenue[i] = rec[i].z < 0 ? -1.0 : (double)rec[i].z / 100.0;
-        }
-    }
-    if (share_volume_k && hipMemcpy(share_volume_k, rp.share_volume, b_share, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(ADC_EHIP, "download failed"));
-    return done(ADC_OK);
-}
-
-ADC_EXPORT int adc_engine_outcomes_replay(adc_engine *e, int32_t env, int32_t steps_back, const float *bids_k, float budget, int64_t capacity,
-                                          int32_t *keyword, int32_t *timestep, double *cost, double *revenue, int64_t *count, int32_t *share_volume_k)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_reset || e->last_step == 0) return fail(ADC_ESTATE, "no step to replay since the reset");
-    if (e->last_step == 2) return fail(ADC_ESTATE, "the last step replayed a tape: its variates are the caller's, not the engine's stream (adc_engine_outcomes_replay_tape)");
-    if (steps_back < 1 || steps_back > e->stream_steps) return fail(ADC_ESTATE, "steps_back reaches behind the last reset / tape replay");
-    if (steps_back > 1 && e->v.drift_on) return fail(ADC_ESTATE, "with drift enabled only the last step can be replayed (the parameters have moved on)");
-    if (e->v.drift_on && e->drift_applied)
-        return fail(ADC_ESTATE, "the last step's update_keywords() has already been applied to the stored parameters (they were read, or the ideal profit "
-                                "evaluated, since the step): its clicks can no longer be regenerated");
-    return outcomes_walk(e, env, (unsigned int)steps_back, bids_k, budget, nullptr, capacity, keyword, timestep, cost, revenue, count, share_volume_k);
-}
-
-// a host adc_tape on the device (adc_engine_step_replay, adc_engine_outcomes_replay_tape); the copies live as long as the object
-struct TapeUpload {
-    adc_engine *e;
-    std::vector<void *> tmp;
-    TapeView tv{};
-    int64_t *d_end = nullptr;
-    explicit TapeUpload(adc_engine *engine) : e(engine) {}
-    ~TapeUpload() { for (void *p : tmp) (void)hipFree(p); }
-    int up(const void *host, size_t bytes, const void **dev)
-    {
-        *dev = nullptr;
-        if (!host) return ADC_OK;
-        void *q = nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc (tape) failed");
-        tmp.push_back(q);
-        if (bytes && hipMemcpyAsync(q, host, bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) return fail(ADC_EHIP, "tape upload failed");
-        *dev = q;
-        return ADC_OK;
-    }
-    int upload(const adc_tape *tape)
-    {
-        const size_t N = e->v.N, K = e->v.K, NK = N * K;
-        for (size_t i = 0; i < NK; ++i)
-            if (tape->volumes[i] < 0 || tape->volumes[i] > adc::kVolumeMax) return fail(ADC_EINVAL, "tape volume out of range [0, 2^20]");
-        int rc = ADC_OK;
-#define UP(field, type, count) if (!rc) rc = up(tape->field, (size_t)(count) * sizeof(type), (const void **)&tv.field)
-        UP(volumes, int32_t, NK);
-        UP(bid_cents, int32_t, tape->len_bid);
-        UP(x_impressions, int32_t, tape->len_ximp);
-        UP(x_cost, double, tape->len_xcost);
-        UP(click, uint8_t, tape->len_click);
-        UP(conv, uint8_t, tape->len_conv);
-        UP(rev_cents, int32_t, tape->len_rev);
-        UP(off_bid, int64_t, N); UP(off_ximp, int64_t, N); UP(off_xcost, int64_t, N);
-        UP(off_click, int64_t, N); UP(off_conv, int64_t, N); UP(off_rev, int64_t, N);
-        if (!rc && tape->drift_uniforms && !e->v.drift_on) rc = fail(ADC_EINVAL, "tape carries drift coefficients but drift is not enabled on this engine");
-        UP(drift_uniforms, float, 3 * NK);
-#undef UP
-        if (!rc && hipMalloc((void **)&d_end, 6 * N * 8 + 8) != hipSuccess) rc = fail(ADC_ENOMEM, "hipMalloc (tape cursors) failed");
-        if (rc) return rc;
-        tmp.push_back(d_end);
-        tv.error = reinterpret_cast<int *>(d_end + 6 * N);
-        if (hipMemsetAsync(tv.error, 0, 8, e->stream) != hipSuccess) return fail(ADC_EHIP, "memset failed");
-        tv.end_bid = d_end; tv.end_ximp = d_end + N; tv.end_xcost = d_end + 2 * N;
-        tv.end_click = d_end + 3 * N; tv.end_conv = d_end + 4 * N; tv.end_rev = d_end + 5 * N;
-        tv.len_bid = tape->len_bid; tv.len_ximp = tape->len_ximp; tv.len_xcost = tape->len_xcost;
-        tv.len_click = tape->len_click; tv.len_conv = tape->len_conv; tv.len_rev = tape->len_rev;
-        return ADC_OK;
-    }
-    int check_exhausted()
-    {
-        int tape_error = 0;
-        if (hipMemcpy(&tape_error, tv.error, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ADC_EHIP, "tape error flag download failed");
-        if (tape_error) return fail(ADC_EINVAL, "tape exhausted: the step needed more variates than a tape holds (outputs are invalid)");
-        return ADC_OK;
-    }
-};
-
-ADC_EXPORT int adc_engine_step_replay(adc_engine *e, const float *bids_nk, const float *budget_n, const adc_tape *tape,
-                                      adc_step_out *out)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
-    if (!bids_nk || !budget_n || !tape || !tape->volumes) return fail(ADC_EINVAL, "bids/budget/tape is NULL");
-    const size_t N = e->v.N, K = e->v.K, NK = N * K;
-    TapeUpload t(e);
-    int rc = t.upload(tape);
-    if (rc) return rc;
-    hipError_t err = hipMemcpyAsync(e->d_bids, bids_nk, NK * 4, hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(e->d_budget, budget_n, N * 4, hipMemcpyHostToDevice, e->stream);
-    if (err != hipSuccess) return fail(ADC_EHIP, "action upload failed");
-    rc = launch_step(e, e->d_bids, e->d_budget, &t.tv);
-    if (!rc) rc = fetch(e, out);
-    if (!rc) rc = t.check_exhausted();
-    if (!rc) {
-        int64_t *dst[6] = {tape->end_bid, tape->end_ximp, tape->end_xcost, tape->end_click, tape->end_conv, tape->end_rev};
-        for (int i = 0; i < 6 && !rc; ++i)
-            if (dst[i] && hipMemcpy(dst[i], t.d_end + i * N, N * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ADC_EHIP, "cursor download failed");
-    }
-    return rc;
-}
-
-// The same lists for a step given as a TAPE (the reference's recorded variates): env `env` is walked over the caller's tape,
-// read-only - no state, output or cursor of the engine is written - with the keyword parameters as they stand.
-ADC_EXPORT int adc_engine_outcomes_replay_tape(adc_engine *e, int32_t env, const float *bids_k, float budget, const adc_tape *tape, int64_t capacity,
-                                               int32_t *keyword, int32_t *timestep, double *cost, double *revenue, int64_t *count, int32_t *share_volume_k)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
-    if (!tape || !tape->volumes) return fail(ADC_EINVAL, "tape is NULL");
-    TapeUpload t(e);
-    int rc = t.upload(tape);
-    if (!rc) rc = outcomes_walk(e, env, 0u, bids_k, budget, &t.tv, capacity, keyword, timestep, cost, revenue, count, share_volume_k);
-    if (!rc) rc = t.check_exhausted();
-    return rc;
-}
-
-ADC_EXPORT int adc_engine_set_general_model(adc_engine *e, int32_t max_bidders, float participation_rate, int32_t num_winners)
-{
-    ENGINE_GUARD(e);
-    if (max_bidders < 0 || max_bidders > 252 || (num_winners != 1 && num_winners != 2)) return fail(ADC_EINVAL, "max_bidders must be in [0, 252] and num_winners 1 or 2");
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->v.max_bidders = max_bidders;
-    e->v.participation_rate = participation_rate;
-    e->v.num_winners = num_winners;
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_update_keywords(adc_engine *e)
-{
-    ENGINE_GUARD(e);
-    if (!e->v.drift_on) return ADC_OK;        // updater_mask is None: no-op (gymnasium_kw_env.py:125-126)
-    materialize_drift(e);
-    hipLaunchKernelGGL(k_force_drift, dim3(e->v.N), dim3(256), 0, e->stream, e->v);     // (advances every env's tick)
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    forget_replayable_steps(e);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_host_alloc(size_t bytes, void **out)
-{
-    if (!out) return fail(ADC_EINVAL, "out is NULL");
-    *out = nullptr;
-    void *p = nullptr;
-    hipError_t err = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
-    if (err != hipSuccess) return fail(ADC_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(err));
-    *out = p;
-    return ADC_OK;
-}
-
-ADC_EXPORT void adc_host_free(void *p)
-{
-    if (p) (void)hipHostFree(p);
-}
-
-ADC_EXPORT int adc_engine_device_buffer(adc_engine *e, int buffer_id, void **dptr, size_t *bytes)
-{
-    ENGINE_GUARD(e);
-    if (!dptr) return fail(ADC_EINVAL, "dptr is NULL");
-    const View &v = e->v;
-    const size_t N = v.N, K = v.K, NK = N * K;
-    void *p = nullptr;
-    size_t b = 0;
-    switch (buffer_id) {
-    case ADC_BUF_PARAMS: p = v.params; b = ADC_P_COUNT * NK * 4; break;
-    case ADC_BUF_BIDS: p = e->d_bids; b = NK * 4; break;
-    case ADC_BUF_BUDGET: p = e->d_budget; b = N * 4; break;
-    case ADC_BUF_IMPRESSIONS: p = v.imp; b = NK * 4; break;
-    case ADC_BUF_CLICKS: p = v.clk; b = NK * 4; break;
-    case ADC_BUF_CONVERSIONS: p = v.conv; b = NK * 4; break;
-    case ADC_BUF_COST: p = v.cost; b = NK * 4; break;
-    case ADC_BUF_REVENUE: p = v.rev; b = NK * 4; break;
-    case ADC_BUF_REWARD: p = v.reward; b = N * 8; break;
-    case ADC_BUF_CUM_PROFIT: p = v.cum_profit; b = N * 8; break;
-    case ADC_BUF_DAYS: p = v.day_out; b = N * 4; break;
-    case ADC_BUF_TERMINATED: p = v.term; b = N; break;
-    case ADC_BUF_TRUNCATED: p = v.trunc; b = N; break;
-    case ADC_BUF_METRIC_PROFIT: p = v.metric_profit; b = K * 8; break;
-    case ADC_BUF_METRIC_SCALARS: p = v.metric_scalars; b = 8 * 8; break;
-    case ADC_BUF_FLAT_OBS:
-        if (!v.flat_obs) return fail(ADC_ESTATE, "flat observations are not enabled (adc_engine_flat_obs_enable)");
-        p = v.flat_obs; b = N * (5 * K + 2) * 4; break;
-    case ADC_BUF_ROLLOUT_ACTION: case ADC_BUF_ROLLOUT_LOGP: case ADC_BUF_ROLLOUT_VALUE: case ADC_BUF_ROLLOUT_REWARD:
-    case ADC_BUF_ROLLOUT_TERMINATED: case ADC_BUF_ROLLOUT_TRUNCATED: case ADC_BUF_ROLLOUT_OBS: {
-        if (e->ro_T == 0) return fail(ADC_ESTATE, "the rollout record is not enabled (adc_engine_rollout_enable)");
-        const size_t tn = (size_t)e->ro_T * N;
-        if (buffer_id == ADC_BUF_ROLLOUT_ACTION) { p = e->ro_action; b = tn * (size_t)e->mp.A * 4; }
-        else if (buffer_id == ADC_BUF_ROLLOUT_LOGP) { p = e->ro_logp; b = tn * 4; }
-        else if (buffer_id == ADC_BUF_ROLLOUT_VALUE) { p = e->ro_value; b = tn * 4; }
-        else if (buffer_id == ADC_BUF_ROLLOUT_REWARD) { p = e->ro_reward; b = tn * 4; }
-        else if (buffer_id == ADC_BUF_ROLLOUT_TERMINATED) { p = e->ro_term; b = tn; }
-        else if (buffer_id == ADC_BUF_ROLLOUT_TRUNCATED) { p = e->ro_trunc; b = tn; }
-        else {
-            if (!e->ro_obs) return fail(ADC_ESTATE, "the record was enabled without ADC_ROLLOUT_OBS");
-            p = e->ro_obs; b = tn * (size_t)e->mp.D * 4;
-        }
-        break;
-    }
-    default: return fail(ADC_EINVAL, "unknown buffer id");
-    }
-    *dptr = p;
-    if (bytes) *bytes = b;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_set_env_groups(adc_engine *e, int32_t groups)
-{
-    ENGINE_GUARD(e);
-    if (groups < 0 || groups > kMaxGroups) return fail(ADC_EINVAL, "env groups: 0 (the engine chooses) or 1..4");
-    e->groups_override = groups;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_env_groups(adc_engine *e, int32_t *groups)
-{
-    ENGINE_GUARD(e);
-    if (!groups) return fail(ADC_EINVAL, "groups is NULL");
-    *groups = e->last_groups;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_stream(adc_engine *e, void **hip_stream)
-{
-    ENGINE_GUARD(e);
-    if (!hip_stream) return fail(ADC_EINVAL, "hip_stream is NULL");
-    *hip_stream = (void *)e->stream;
-    e->stream_exposed = true;           // (from now on the caller may enqueue on it without telling: launch_step)
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_sample_actions(adc_engine *e, float bid_lo, float bid_hi, float budget)
-{
-    ENGINE_GUARD_STEP(e);
-    return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
-        hipLaunchKernelGGL(k_sample_actions, dim3((unsigned)((v.K + 255) / 256), (unsigned)v.N), dim3(256), 0, st, v, bid_lo, bid_hi, budget, d_bids, d_budget);
-    });
-}
-
-ADC_EXPORT int adc_engine_set_flat_actions_device(adc_engine *e, const float *d_flat)
-{
-    ENGINE_GUARD(e);
-    if (!d_flat) return fail(ADC_EINVAL, "flat action pointer is NULL");
-    hipLaunchKernelGGL(k_unflatten_actions, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)e->v.N), dim3(256), 0, e->stream, e->v,
-                       d_flat, e->d_bids, e->d_budget);
-    HIP_TRY(hipGetLastError());
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_flat_obs_enable(adc_engine *e, int enabled)
-{
-    ENGINE_GUARD(e);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (enabled && !e->d_flat_obs) {
-        int rc = dev_alloc(e, &e->d_flat_obs, (size_t)e->v.N * (5 * (size_t)e->v.K + 2));
-        if (rc) return rc;
-    }
-    e->v.flat_obs = enabled ? e->d_flat_obs : nullptr;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_profile_enable(adc_engine *e, int enabled)
-{
-    ENGINE_GUARD(e);
-    if (enabled && e->ev.empty()) {
-        e->ev.resize((size_t)kProfileRing * kProfileMarks);
-        for (auto &ev : e->ev) HIP_TRY(hipEventCreate(&ev));
-    }
-    e->profiling = enabled != 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_profile_sample_every(adc_engine *e, int32_t every)
-{
-    ENGINE_GUARD(e);
-    if (every < 1) return fail(ADC_EINVAL, "profile sampling interval must be >= 1");
-    e->profile_every = every;
-    e->profile_tick = 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_profile_read(adc_engine *e, double *kernel_ms_total, int64_t *launches)
-{
-    ENGINE_GUARD(e);
-    int rc = flush_profile(e);
-    if (rc) return rc;
-    if (kernel_ms_total) for (int j = 0; j < 3; ++j) kernel_ms_total[j] = e->prof_ms[j];
-    if (launches) *launches = e->prof_launches;
-    e->prof_ms[0] = e->prof_ms[1] = e->prof_ms[2] = 0.0;
-    e->prof_launches = 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_profile_records(adc_engine *e, int64_t *event_records)
-{
-    ENGINE_GUARD(e);
-    if (!event_records) return fail(ADC_EINVAL, "event_records is NULL");
-    *event_records = e->event_records;
-    return ADC_OK;
-}
-
-// GPU time of a whole region of the engine's stream with ONE event pair (nothing per step): begin records an event, end records
-// another, waits for it and returns the milliseconds in between - what a caller timing K steps on the host clock can check its
-// figure against (the difference is launch latency and host overhead, not kernel time)
-ADC_EXPORT int adc_engine_region_begin(adc_engine *e)
-{
-    ENGINE_GUARD(e);
-    if (!e->region_ev[0]) for (hipEvent_t &ev : e->region_ev) HIP_TRY(hipEventCreate(&ev));
-    HIP_TRY(hipEventRecord(e->region_ev[0], e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_region_end(adc_engine *e, double *gpu_ms)
-{
-    ENGINE_GUARD(e);
-    if (!gpu_ms) return fail(ADC_EINVAL, "gpu_ms is NULL");
-    if (!e->region_ev[0]) return fail(ADC_ESTATE, "adc_engine_region_begin has not been called");
-    HIP_TRY(hipEventRecord(e->region_ev[1], e->stream));
-    HIP_TRY(hipEventSynchronize(e->region_ev[1]));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e->region_ev[0], e->region_ev[1]));
-    *gpu_ms = ms;
-    return ADC_OK;
-}
-
-ADC_EXPORT const char *adc_engine_step_kernel_name(adc_engine *e)
-{
-    if (!e) return "";
-    return e->step_kernel;
-}
-
-ADC_EXPORT int adc_engine_metrics_enable(adc_engine *e, int enabled)
-{
-    ENGINE_GUARD(e);
-    e->v.metrics_on = enabled ? 1 : 0;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_metrics_reset(adc_engine *e)
-{
-    ENGINE_GUARD(e);
-    HIP_TRY(hipMemsetAsync(e->v.metric_profit, 0, (size_t)e->v.K * 8, e->stream));
-    HIP_TRY(hipMemsetAsync(e->v.metric_scalars, 0, 64, e->stream));
-    HIP_TRY(hipMemsetAsync(e->v.metric_env, 0, (size_t)e->v.N * 32, e->stream));
-    HIP_TRY(hipMemsetAsync(e->v.metric_lo, 0, (size_t)e->v.N * e->v.K * 4, e->stream));
-    HIP_TRY(hipMemsetAsync(e->v.metric_hi, 0, (size_t)e->v.N * e->v.K * 8, e->stream));
-    if (e->have_ideal) {
-        HIP_TRY(hipMemsetAsync(e->pol.sum_ideal, 0, (size_t)e->v.N * e->v.K * 8, e->stream));
-        HIP_TRY(hipMemsetAsync(e->pol.sum_ideal_pos, 0, (size_t)e->v.N * e->v.K * 8, e->stream));
-    }
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_metrics_read(adc_engine *e, int64_t *keyword_profit_cents_k, int64_t *scalars8)
-{
-    ENGINE_GUARD(e);
-    if (keyword_profit_cents_k) {
-        HIP_TRY(hipMemsetAsync(e->v.metric_profit, 0, (size_t)e->v.K * 8, e->stream));
-        hipLaunchKernelGGL(k_metric_columns, dim3((unsigned)((e->v.K + 255) / 256), kColumnSlabs), dim3(256), 0, e->stream, e->v);
-        HIP_TRY(hipGetLastError());
-    }
-    if (keyword_profit_cents_k) HIP_TRY(hipMemcpyAsync(keyword_profit_cents_k, e->v.metric_profit, (size_t)e->v.K * 8, hipMemcpyDeviceToHost, e->stream));
-    if (scalars8) {
-        hipLaunchKernelGGL(k_metric_reduce, dim3(4), dim3(256), 0, e->stream, e->v);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(scalars8, e->v.metric_scalars, 64, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-namespace {
-// the bid curves exist for the two single-competitor models; the reference's estimator on the default ImplicitKeyword's bidder pool
-// sorts s x n bids and divides by n (an impression rate above 1), and no notebook uses it that way
-int curves_model_check(const adc_engine *e, const char *what)
-{
-    if (e->v.model == ADC_MODEL_IMPLICIT || e->v.model == ADC_MODEL_EXPLICIT) return ADC_OK;
-    return fail(ADC_EINVAL, std::string(what) + " is defined for IMPLICIT and EXPLICIT keywords (IMPLICIT_GENERAL: the reference's estimator "
-                                                "on a bidder pool gives impression rates above 1)");
-}
-// EXPLICIT: the grid and its cost law, [3][n_bids] = bid, mu_b, sigma_b (adc::explicit_cost_law, float64 on the host)
-std::vector<double> explicit_grid3(const double *bid_grid, int n_bids)
-{
-    std::vector<double> g(3 * (size_t)n_bids);
-    for (int i = 0; i < n_bids; ++i) {
-        g[i] = bid_grid[i];
-        adc::explicit_cost_law(bid_grid[i], g[n_bids + i], g[2 * (size_t)n_bids + i]);
-    }
-    return g;
-}
-void launch_explicit_curves(const adc_engine *e, int n_samples, const double *d_grid3, int n_bids, double *ideal_out, float4 *curve_out)
-{
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    const dim3 grid(ideal_grid((long long)nk, e->num_cus, kIdealWaves)), block(kWave * kIdealWaves);
-    if (n_samples <= kCachedSamples)
-        hipLaunchKernelGGL(k_explicit_curves<true>, grid, block, 0, e->stream, e->v, n_samples, n_bids, d_grid3, d_grid3 + n_bids,
-                           d_grid3 + 2 * (size_t)n_bids, ideal_out, curve_out, (long long)nk);
-    else
-        hipLaunchKernelGGL(k_explicit_curves<false>, grid, block, 0, e->stream, e->v, n_samples, n_bids, d_grid3, d_grid3 + n_bids,
-                           d_grid3 + 2 * (size_t)n_bids, ideal_out, curve_out, (long long)nk);
-}
-// the per-step ideal on the cached curves: contender lists or (ADCRAFT_IDEAL_FULL_SCAN) the whole grid, for the engine's model
-void launch_ideal_step(const View &v, const PolicyView &p, hipStream_t st, bool full_scan)
-{
-    const size_t nk = (size_t)v.N * v.K;
-    if (v.model == ADC_MODEL_EXPLICIT) {
-        if (full_scan) hipLaunchKernelGGL(k_ideal_from_curves<ADC_MODEL_EXPLICIT>, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, v, p, v.metrics_on);
-        else hipLaunchKernelGGL(k_ideal_from_contenders<ADC_MODEL_EXPLICIT>, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, v, p, v.metrics_on);
-    } else {
-        if (full_scan) hipLaunchKernelGGL(k_ideal_from_curves<ADC_MODEL_IMPLICIT>, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, st, v, p, v.metrics_on);
-        else hipLaunchKernelGGL(k_ideal_from_contenders<ADC_MODEL_IMPLICIT>, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, v, p, v.metrics_on);
-    }
-}
-// the IMPLICIT estimator's limits (k_ideal_profit): 0, or ADC_EINVAL naming the one passed; *lim = the bins the grid keeps
-int implicit_curve_args(int n_samples, const double *bid_grid, int n_bids, int *lim)
-{
-    if (n_samples > kIdealMaxSamples) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for IMPLICIT keywords (the estimator's 32-bit sums)");
-    *lim = ideal_bins_kept(bid_grid, n_bids);
-    if (*lim == 0) return fail(ADC_EINVAL, "bid grid: every bid must be finite and at most $20.46 (2046 cents) for IMPLICIT keywords");
-    return 0;
-}
-void launch_ideal_profit(const View &v, hipStream_t st, int num_cus, int n_samples, int n_bids, const double *d_grid, const int32_t *tape,
-                         double *ideal, double *ir, double *cpc, uint2 *packed, int lim, long long n_items)
-{
-    const int waves = ideal_waves(lim);
-    hipLaunchKernelGGL(k_ideal_profit, dim3(ideal_grid(n_items, num_cus, waves)), dim3(kWave * waves), ideal_lds_bytes(lim, waves), st, v, n_samples,
-                       n_bids, d_grid, tape, ideal, ir, cpc, packed, lim, n_items);
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_ideal_profit(adc_engine *e, int n_samples, const double *bid_grid, int n_bids, double *host_nk)
-{
-    ENGINE_GUARD(e);
-    if (int rc = curves_model_check(e, "ideal profit")) return rc;
-    if (n_samples <= 0 || !host_nk || !bid_grid || n_bids <= 0) return fail(ADC_EINVAL, "bad arguments");
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    if (e->v.model == ADC_MODEL_EXPLICIT) {
-        if (n_samples > (1 << 20)) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for EXPLICIT keywords");
-        if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
-        const std::vector<double> g3 = explicit_grid3(bid_grid, n_bids);
-        double *d_out = nullptr, *d_grid = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_out, nk * 8));
-        hipError_t err = hipMalloc((void **)&d_grid, g3.size() * 8);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_grid, g3.data(), g3.size() * 8, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) {
-            launch_explicit_curves(e, n_samples, d_grid, n_bids, d_out, (float4 *)nullptr);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) err = hipMemcpyAsync(host_nk, d_out, nk * 8, hipMemcpyDeviceToHost, e->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-        (void)hipFree(d_out);
-        (void)hipFree(d_grid);
-        HIP_TRY(err);
-        return ADC_OK;
-    }
-    int lim = 0;
-    if (int rc = implicit_curve_args(n_samples, bid_grid, n_bids, &lim)) return rc;
-    if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
-    double *d_out = nullptr, *d_grid = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_out, nk * 8));
-    hipError_t err = hipMalloc((void **)&d_grid, (size_t)n_bids * 8);
-    if (err == hipSuccess) err = hipMemcpyAsync(d_grid, bid_grid, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess) {
-        launch_ideal_profit(e->v, e->stream, e->num_cus, n_samples, n_bids, d_grid, (const int32_t *)nullptr, d_out, (double *)nullptr, (double *)nullptr,
-                            (uint2 *)nullptr, lim, (long long)nk);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipMemcpyAsync(host_nk, d_out, nk * 8, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    (void)hipFree(d_out);
-    (void)hipFree(d_grid);
-    HIP_TRY(err);
-    return ADC_OK;
-}
-
-// the estimator alone, on caller-supplied samples (cents, >= 0) of ONE keyword and any bid grid the estimator takes (pins the kernel
-// against the reference's get_implicit_kw_bid_cpc_impressions).  Arguments are checked before any HIP call
-ADC_EXPORT int adc_bid_curves_from_samples(int device_id, const int32_t *samples_cents, int32_t n_samples, const double *bid_grid,
-                                           int32_t n_bids, double *impression_rate_out, double *cpc_out)
-{
-    if (!samples_cents || n_samples <= 0 || n_bids <= 0 || !bid_grid || !impression_rate_out || !cpc_out)
-        return fail(ADC_EINVAL, "bad arguments");
-    int lim = 0;
-    if (int rc = implicit_curve_args(n_samples, bid_grid, n_bids, &lim)) return rc;
-    for (int32_t i = 0; i < n_samples; ++i)
-        if (samples_cents[i] < 0) return fail(ADC_EINVAL, "a negative sample (cents)");
-    HIP_TRY(hipSetDevice(device_id));
-    int32_t *d_s = nullptr;
-    double *d_ir = nullptr, *d_cpc = nullptr, *d_grid = nullptr;
-    float *d_p = nullptr;
-    uint64_t *d_key = nullptr;
-    uint32_t *d_tick = nullptr;
-    auto done = [&](int code) { (void)hipFree(d_s); (void)hipFree(d_ir); (void)hipFree(d_cpc); (void)hipFree(d_p); (void)hipFree(d_key); (void)hipFree(d_tick); (void)hipFree(d_grid); return code; };
-    if (hipMalloc((void **)&d_s, (size_t)n_samples * 4) != hipSuccess || hipMalloc((void **)&d_ir, (size_t)n_bids * 8) != hipSuccess ||
-        hipMalloc((void **)&d_cpc, (size_t)n_bids * 8) != hipSuccess || hipMalloc((void **)&d_p, ADC_P_COUNT * 4) != hipSuccess ||
-        hipMalloc((void **)&d_key, 8) != hipSuccess || hipMalloc((void **)&d_tick, 4) != hipSuccess ||
-        hipMalloc((void **)&d_grid, (size_t)n_bids * 8) != hipSuccess)
-        return done(fail(ADC_ENOMEM, "hipMalloc failed"));
-    if (hipMemcpy(d_grid, bid_grid, (size_t)n_bids * 8, hipMemcpyHostToDevice) != hipSuccess) return done(fail(ADC_EHIP, "upload failed"));
-    if (hipMemcpy(d_s, samples_cents, (size_t)n_samples * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_p, 0, ADC_P_COUNT * 4) != hipSuccess ||
-        hipMemset(d_key, 0, 8) != hipSuccess || hipMemset(d_tick, 0, 4) != hipSuccess)
-        return done(fail(ADC_EHIP, "upload failed"));
-    View v;
-    std::memset(&v, 0, sizeof(v));
-    v.N = 1; v.K = 1; v.params = d_p; v.key = d_key; v.tick = d_tick;
-    v.NP = 1;
-    launch_ideal_profit(v, 0, 1, n_samples, n_bids, d_grid, d_s, (double *)nullptr, d_ir, d_cpc, (uint2 *)nullptr, lim, 1LL);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(fail(ADC_EHIP, "k_ideal_profit failed"));
-    if (hipMemcpy(impression_rate_out, d_ir, (size_t)n_bids * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(cpc_out, d_cpc, (size_t)n_bids * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(ADC_EHIP, "download failed"));
-    return done(ADC_OK);
-}
-
-// adc_law.h win_brackets evaluated by the device (k_debug_win_brackets), 8 words per keyword: tests check them against the
-// exact intervals on the host (adc_check_win_brackets)
-ADC_EXPORT int adc_debug_win_brackets_device(int device_id, int64_t n, const float *bid, const float *cost_loc, const float *cost_scale,
-                                             const float *buyside_ctr, uint32_t *out8)
-{
-    if (n < 0 || n > (1 << 26)) return fail(ADC_EINVAL, "n out of range");
-    if (n == 0) return ADC_OK;
-    if (!bid || !cost_loc || !cost_scale || !buyside_ctr || !out8) return fail(ADC_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(device_id));
-    float *d_in = nullptr;
-    uint32_t *d_out = nullptr;
-    auto done = [&](int code) {
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        return code;
-    };
-    const size_t m = (size_t)n;
-    if (hipMalloc((void **)&d_in, 4 * m * 4) != hipSuccess || hipMalloc((void **)&d_out, 8 * m * 4) != hipSuccess) return done(fail(ADC_ENOMEM, "hipMalloc failed"));
-    const float *src[4] = {bid, cost_loc, cost_scale, buyside_ctr};
-    for (int i = 0; i < 4; ++i)
-        if (hipMemcpy(d_in + i * m, src[i], m * 4, hipMemcpyHostToDevice) != hipSuccess) return done(fail(ADC_EHIP, "upload failed"));
-    hipLaunchKernelGGL(k_debug_win_brackets, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, (int)n, d_in, d_in + m, d_in + 2 * m, d_in + 3 * m, d_out);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(fail(ADC_EHIP, "k_debug_win_brackets failed"));
-    if (hipMemcpy(out8, d_out, 8 * m * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(ADC_EHIP, "download failed"));
-    return done(ADC_OK);
-}
-
-// Philox4x32 (the stream's round count) evaluated by the device for n (counter, key) pairs - the GPU side of the stream battery
-ADC_EXPORT int adc_debug_walk_stats(adc_engine *e, int64_t stats[4], int reset)
-{
-    ENGINE_GUARD(e);
-    if (!stats) return fail(ADC_EINVAL, "stats is NULL");
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_walk_stats), sizeof(h)));
-    for (int i = 0; i < 4; ++i) stats[i] = (int64_t)h[i];
-#ifdef ADC_EXP_TIMING
-    {   // timing build: the phase sums go to stderr (setup | sort | walk | commit | gather | second part | groups | candidates)
-        unsigned long long ph[20];
-        HIP_TRY(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_walk_phase), 8 * sizeof(ph[0])));
-        std::fprintf(stderr, "walk phases:");
-        for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %llu", ph[i]);
-        std::fprintf(stderr, "\n");
-        HIP_TRY(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_rest_phase), sizeof(ph)));
-        std::fprintf(stderr, "rest-of-day phases (10 ns ticks: pass over the auctions | of which laws | marked cells | outputs | envs | cells walked | of which paid / marks | - | "
-                             "list of the marks | k_rest_walk: before the walk | chunks resolved | whole env | slowest env | chunk: cells | chain | paid | at-once variant: own cells | chain | commit | envs):");
-        for (int i = 0; i < 20; ++i) std::fprintf(stderr, " %llu", ph[i]);
-        std::fprintf(stderr, "\n");
-        if (reset) {
-            const unsigned long long z8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_walk_phase), z8, sizeof(z8)));
-            const unsigned long long z16[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_rest_phase), z16, sizeof(z16)));
-        }
-    }
-#endif
-    if (reset) {
-        const unsigned long long z[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_walk_stats), z, sizeof(z)));
-    }
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_debug_direct_days(adc_engine *e, int64_t *env_days, int reset)
-{
-    ENGINE_GUARD(e);
-    if (!env_days) return fail(ADC_EINVAL, "env_days is NULL");
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    unsigned long long h = 0;
-    if (e->v.direct_days) {             // (null: this engine never parks an env at once - K > 256, fewer than 1024 envs, another model)
-        HIP_TRY(hipMemcpy(&h, e->v.direct_days, sizeof(h), hipMemcpyDeviceToHost));
-        if (reset) HIP_TRY(hipMemset(e->v.direct_days, 0, sizeof(h)));
-    }
-    *env_days = (int64_t)h;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_debug_philox_device(int device_id, int64_t n, const uint32_t *ctr4, const uint32_t *key2, uint32_t *out4)
-{
-    if (n < 0 || n > (1 << 26)) return fail(ADC_EINVAL, "n out of range");
-    if (n == 0) return ADC_OK;
-    if (!ctr4 || !key2 || !out4) return fail(ADC_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(device_id));
-    uint32_t *d = nullptr;
-    const size_t m = (size_t)n;
-    if (hipMalloc((void **)&d, 10 * m * 4) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc failed");
-    auto done = [&](int code) { (void)hipFree(d); return code; };
-    if (hipMemcpy(d, ctr4, 4 * m * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + 4 * m, key2, 2 * m * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return done(fail(ADC_EHIP, "upload failed"));
-    hipLaunchKernelGGL(k_debug_philox, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, (int)n, d, d + 4 * m, d + 6 * m);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(fail(ADC_EHIP, "k_debug_philox failed"));
-    if (hipMemcpy(out4, d + 6 * m, 4 * m * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(ADC_EHIP, "download failed"));
-    return done(ADC_OK);
-}
-
-ADC_EXPORT int adc_debug_chain_device(int device_id, double r0, int64_t n, const double *x, double *out2)
-{
-    if (n < 0 || n > (1 << 24)) return fail(ADC_EINVAL, "n out of range");
-    if ((n > 0 && !x) || !out2) return fail(ADC_EINVAL, "NULL argument");
-    HIP_TRY(hipSetDevice(device_id));
-    double *d = nullptr;
-    if (hipMalloc((void **)&d, ((size_t)n + 2) * 8) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc failed");
-    auto done = [&](int code) { (void)hipFree(d); return code; };
-    if (n > 0 && hipMemcpy(d + 2, x, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return done(fail(ADC_EHIP, "upload failed"));
-    hipLaunchKernelGGL(k_debug_chain, dim3(1), dim3(kWave), 0, 0, r0, (int)n, d + 2, d);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(fail(ADC_EHIP, "k_debug_chain failed"));
-    if (hipMemcpy(out2, d, 16, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(ADC_EHIP, "download failed"));
-    return done(ADC_OK);
-}
-
-ADC_EXPORT int adc_nth_price_auction(int device_id, double bid, const double *other_bids, int32_t n_auctions, int32_t n_bidders,
-                                     int32_t n, int32_t num_winners, int32_t *impressions, int32_t *placements, double *costs)
-{
-    if (!impressions) return fail(ADC_EINVAL, "impressions is NULL");
-    *impressions = 0;
-    if (n < 1 || num_winners < 1 || n + num_winners > kTopMax) return fail(ADC_EINVAL, "need n >= 1, num_winners >= 1, n + num_winners <= 32");
-    if (n_auctions < 0 || n_bidders < 0) return fail(ADC_EINVAL, "negative shape");
-    if (n_auctions == 0) return ADC_OK;
-    if (n_bidders > 0 && !other_bids) return fail(ADC_EINVAL, "other_bids is NULL");
-    HIP_TRY(hipSetDevice(device_id));
-    double *d_other = nullptr, *d_cost = nullptr;
-    int *d_won = nullptr, *d_place = nullptr;
-    const size_t na = n_auctions, nb = n_bidders;
-    int rc = ADC_OK;
-    auto done = [&](int code) {
-        if (d_other) (void)hipFree(d_other);
-        if (d_cost) (void)hipFree(d_cost);
-        if (d_won) (void)hipFree(d_won);
-        if (d_place) (void)hipFree(d_place);
-        return code;
-    };
-    if (hipMalloc((void **)&d_other, (na * nb ? na * nb : 1) * 8) != hipSuccess || hipMalloc((void **)&d_cost, na * 8) != hipSuccess ||
-        hipMalloc((void **)&d_won, na * 4) != hipSuccess || hipMalloc((void **)&d_place, na * 4) != hipSuccess)
-        return done(fail(ADC_ENOMEM, "hipMalloc failed"));
-    if (na * nb && hipMemcpy(d_other, other_bids, na * nb * 8, hipMemcpyHostToDevice) != hipSuccess) return done(fail(ADC_EHIP, "upload failed"));
-    hipLaunchKernelGGL(k_nth_price, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, 0, bid, d_other, n_auctions, n_bidders, n, num_winners, d_won, d_place, d_cost);
-    if (hipGetLastError() != hipSuccess) return done(fail(ADC_EHIP, "k_nth_price launch failed"));
-    std::vector<int> won(na), place(na);
-    std::vector<double> cost(na);
-    if (hipMemcpy(won.data(), d_won, na * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(place.data(), d_place, na * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(cost.data(), d_cost, na * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(ADC_EHIP, "download failed"));
-    int32_t m = 0;
-    for (size_t a = 0; a < na; ++a)
-        if (won[a]) {
-            if (placements) placements[m] = place[a];
-            if (costs) costs[m] = cost[a];
-            ++m;
-        }
-    *impressions = m;
-    return done(rc);
-}
-
-
-// ---- baseline policies and the per-step ideal, device-resident (kernels_policy.inc) -----------------------------------
-namespace {
-int ensure_ideal_buffers(adc_engine *e)
-{
-    if (e->have_ideal) return ADC_OK;
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    int rc;
-    if ((rc = dev_alloc(e, &e->pol.ideal, nk))) return rc;
-    if ((rc = dev_alloc(e, &e->pol.best, nk))) return rc;
-    if ((rc = dev_alloc(e, &e->pol.sum_ideal, nk))) return rc;
-    if ((rc = dev_alloc(e, &e->pol.sum_ideal_pos, nk))) return rc;
-    e->have_ideal = true;
-    return ADC_OK;
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_agent_init(adc_engine *e, float default_rpc, const uint64_t *seeds_n)
-{
-    ENGINE_GUARD(e);
-    const size_t N = e->v.N, nk = N * e->v.K;
-    if (!e->have_agent) {
-        int rc;
-        if ((rc = dev_alloc(e, &e->pol.ave_rpc, nk))) return rc;
-        if ((rc = dev_alloc(e, &e->pol.n_rpc, nk))) return rc;
-        if ((rc = dev_alloc(e, &e->pol.ave_sctr, nk))) return rc;
-        if ((rc = dev_alloc(e, &e->pol.n_sctr, nk))) return rc;
-        if ((rc = dev_alloc(e, &e->pol.max_bid, nk))) return rc;
-        if ((rc = dev_alloc(e, &e->pol.key, N))) return rc;
-        if ((rc = dev_alloc(e, &e->pol.tick, N))) return rc;
-        e->have_agent = true;
-    }
-    e->pol.default_rpc = default_rpc;
-    uint64_t *d_seeds = nullptr;
-    if (seeds_n) { HIP_TRY(hipMalloc((void **)&d_seeds, N * 8)); HIP_TRY(hipMemcpyAsync(d_seeds, seeds_n, N * 8, hipMemcpyHostToDevice, e->stream)); }
-    hipLaunchKernelGGL(k_agent_init, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->v, e->pol, d_seeds,
-                       e->cfg.seed, e->cfg.env_id_base);
-    hipError_t err = hipGetLastError();
-    hipError_t err2 = hipStreamSynchronize(e->stream);
-    if (d_seeds) (void)hipFree(d_seeds);
-    HIP_TRY(err);
-    HIP_TRY(err2);
-    return ADC_OK;
-}
-
-namespace {
-// update and/or act; host observation arrays (all three or none) are staged through temporaries
-int agent_launch(adc_engine *e, const int32_t *clicks_nk, const int32_t *conv_nk, const float *rev_nk, int do_update, int do_act,
-                 const double *replay_u_nk, float budget_override)
-{
-    if (!e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
-    const int given = (clicks_nk != nullptr) + (conv_nk != nullptr) + (rev_nk != nullptr);
-    if (given != 0 && given != 3) return fail(ADC_EINVAL, "pass all of clicks/conversions/revenue, or none (= the engine's last observation)");
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    int32_t *d_clk = nullptr, *d_conv = nullptr;
-    float *d_rev = nullptr;
-    double *d_u = nullptr;
-    auto done = [&](hipError_t err) {
-        hipError_t e2 = (d_clk || d_u) ? hipStreamSynchronize(e->stream) : hipSuccess;
-        (void)hipFree(d_clk); (void)hipFree(d_conv); (void)hipFree(d_rev); (void)hipFree(d_u);
-        if (err != hipSuccess) return fail(ADC_EHIP, hipGetErrorString(err));
-        if (e2 != hipSuccess) return fail(ADC_EHIP, hipGetErrorString(e2));
-        return (int)ADC_OK;
-    };
-    hipError_t err = hipSuccess;
-    if (given == 3 && do_update) {
-        if (hipMalloc((void **)&d_clk, nk * 4) != hipSuccess || hipMalloc((void **)&d_conv, nk * 4) != hipSuccess ||
-            hipMalloc((void **)&d_rev, nk * 4) != hipSuccess) { (void)done(hipSuccess); return fail(ADC_ENOMEM, "hipMalloc failed"); }
-        err = hipMemcpyAsync(d_clk, clicks_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_conv, conv_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_rev, rev_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-    }
-    if (err == hipSuccess && replay_u_nk && do_act) {
-        if (hipMalloc((void **)&d_u, nk * 8) != hipSuccess) { (void)done(hipSuccess); return fail(ADC_ENOMEM, "hipMalloc failed"); }
-        err = hipMemcpyAsync(d_u, replay_u_nk, nk * 8, hipMemcpyHostToDevice, e->stream);
-    }
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_agent_step, dim3((unsigned)e->v.N), dim3(256), 0, e->stream, e->v, e->pol,
-                           d_clk ? d_clk : e->v.clk, d_conv ? d_conv : e->v.conv, d_rev ? d_rev : e->v.rev, do_update, do_act,
-                           (const double *)d_u, budget_override, e->d_bids, e->d_budget);
-        err = hipGetLastError();
-    }
-    return done(err);
-}
-}  // namespace
-
-namespace {
-// update + act on the engine's last observation (no host arrays): chain-compatible
-int agent_step_chained(adc_engine *e, float budget_override)
-{
-    if (!e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
-    return launch_chained(e, [&](const View &v, const PolicyView &p, hipStream_t st, float *d_bids, float *d_budget) {
-        hipLaunchKernelGGL(k_agent_step, dim3((unsigned)v.N), dim3(256), 0, st, v, p, v.clk, v.conv, v.rev, 1, 1, (const double *)nullptr, budget_override, d_bids, d_budget);
-    });
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_agent_update(adc_engine *e, const int32_t *clicks_nk, const int32_t *conversions_nk, const float *revenue_nk)
-{
-    ENGINE_GUARD(e);
-    return agent_launch(e, clicks_nk, conversions_nk, revenue_nk, 1, 0, nullptr, 0.0f);
-}
-
-ADC_EXPORT int adc_engine_agent_act(adc_engine *e, float budget_override, const double *replay_uniforms_nk)
-{
-    ENGINE_GUARD(e);
-    return agent_launch(e, nullptr, nullptr, nullptr, 0, 1, replay_uniforms_nk, budget_override);
-}
-
-ADC_EXPORT int adc_engine_agent_step(adc_engine *e, float budget_override)
-{
-    ENGINE_GUARD_STEP(e);
-    return agent_step_chained(e, budget_override);
-}
-
-ADC_EXPORT int adc_engine_agent_state(adc_engine *e, float *ave_rpc_nk, int32_t *num_rpc_obs_nk, float *ave_sctr_nk,
-                                      int32_t *num_sctr_obs_nk, double *max_bids_nk)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    if (ave_rpc_nk) HIP_TRY(hipMemcpyAsync(ave_rpc_nk, e->pol.ave_rpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (num_rpc_obs_nk) HIP_TRY(hipMemcpyAsync(num_rpc_obs_nk, e->pol.n_rpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (ave_sctr_nk) HIP_TRY(hipMemcpyAsync(ave_sctr_nk, e->pol.ave_sctr, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (num_sctr_obs_nk) HIP_TRY(hipMemcpyAsync(num_sctr_obs_nk, e->pol.n_sctr, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (max_bids_nk) HIP_TRY(hipMemcpyAsync(max_bids_nk, e->pol.max_bid, nk * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_get_actions(adc_engine *e, float *bids_nk, float *budget_n)
-{
-    ENGINE_GUARD(e);
-    if (bids_nk) HIP_TRY(hipMemcpyAsync(bids_nk, e->d_bids, (size_t)e->v.N * e->v.K * 4, hipMemcpyDeviceToHost, e->stream));
-    if (budget_n) HIP_TRY(hipMemcpyAsync(budget_n, e->d_budget, (size_t)e->v.N * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_bid_curves_build(adc_engine *e, int n_samples, const double *bid_grid, int n_bids)
-{
-    ENGINE_GUARD(e);
-    if (int rc = curves_model_check(e, "bid curves")) return rc;
-    if (n_samples <= 0 || !bid_grid || n_bids <= 0) return fail(ADC_EINVAL, "bad arguments");
-    const bool xp = e->v.model == ADC_MODEL_EXPLICIT;
-    int lim = 0;
-    if (!xp) if (int rc = implicit_curve_args(n_samples, bid_grid, n_bids, &lim)) return rc;      // (before the cached curves are touched)
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (n_samples > (1 << 20)) return fail(ADC_EINVAL, "n_samples > 2^20 is not supported for cached curves");
-    if (!e->have_curves || e->pol.n_bids != n_bids) {
-        for (void *p : e->curve_allocs) (void)hipFree(p);
-        e->curve_allocs.clear();
-        e->have_curves = false;
-        void *curve = nullptr, *grid = nullptr, *cont = nullptr, *ncont = nullptr, *cpos = nullptr;
-        // contender lists: 24 bytes per distinct grid point that can be the argmax (typically half of the grid); curves with more
-        // points than a list holds are evaluated on the whole grid
-        const int cap = std::min(n_bids, 256);
-        // (EXPLICIT: 16 bytes per keyword instead of 8 per grid point, and the grid's cost law beside the grid)
-        const size_t curve_bytes = xp ? nk * sizeof(float4) : nk * n_bids * sizeof(uint2);
-        if (hipMalloc(&curve, curve_bytes) != hipSuccess || hipMalloc(&grid, (size_t)n_bids * 8 * (xp ? 3 : 1)) != hipSuccess ||
-            hipMalloc(&cont, nk * cap * sizeof(ContenderEntry)) != hipSuccess ||
-            hipMalloc(&ncont, nk * sizeof(uint16_t)) != hipSuccess || hipMalloc(&cpos, nk * sizeof(uint16_t)) != hipSuccess) {
-            (void)hipFree(curve); (void)hipFree(grid); (void)hipFree(cont); (void)hipFree(ncont); (void)hipFree(cpos);
-            return fail(ADC_ENOMEM, "bid curves need ~30 bytes x num_envs x num_keywords x n_bids of device memory");
-        }
-        e->curve_allocs = {curve, grid, cont, ncont, cpos};
-        if (xp) {
-            e->pol.xcurve = (float4 *)curve;
-            e->pol.grid_mu = (double *)grid + n_bids;
-            e->pol.grid_sigma = (double *)grid + 2 * (size_t)n_bids;
-        } else {
-            e->pol.curve = (uint2 *)curve;
-        }
-        e->pol.grid = (double *)grid; e->pol.n_bids = n_bids;
-        e->pol.contender = (ContenderEntry *)cont; e->pol.n_contenders = (uint16_t *)ncont;
-        e->pol.cont_pos = (uint16_t *)cpos; e->pol.cont_cap = cap;
-        e->have_curves = true;
-    }
-    e->pol.n_samples = n_samples;
-    int rc = ensure_ideal_buffers(e);
-    if (rc) return rc;
-    if (xp) {
-        const std::vector<double> g3 = explicit_grid3(bid_grid, n_bids);
-        HIP_TRY(hipMemcpyAsync(e->pol.grid, g3.data(), g3.size() * 8, hipMemcpyHostToDevice, e->stream));
-        launch_explicit_curves(e, n_samples, e->pol.grid, n_bids, (double *)nullptr, e->pol.xcurve);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(e->stream));       // (g3 is a host temporary)
-    } else {
-    HIP_TRY(hipMemcpyAsync(e->pol.grid, bid_grid, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream));
-    launch_ideal_profit(e->v, e->stream, e->num_cus, n_samples, n_bids, e->pol.grid, (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr,
-                        (double *)nullptr, e->pol.curve, lim, (long long)nk);
-    HIP_TRY(hipGetLastError());
-    }
-    // which grid points can be the argmax at all (k_curve_contenders): the per-step ideal then evaluates only those
-    HIP_TRY(hipMemsetAsync(e->pol.cont_pos, 0, nk * sizeof(uint16_t), e->stream));
-    if (n_bids <= kContenderLines) {
-        if (xp) hipLaunchKernelGGL(k_curve_contenders<ADC_MODEL_EXPLICIT>, dim3((unsigned)nk), dim3(kWave), sizeof(ContenderScratch), e->stream, e->v, e->pol);
-        else hipLaunchKernelGGL(k_curve_contenders<ADC_MODEL_IMPLICIT>, dim3((unsigned)nk), dim3(kWave), sizeof(ContenderScratch), e->stream, e->v, e->pol);
-        HIP_TRY(hipGetLastError());
-    } else {
-        HIP_TRY(hipMemsetAsync(e->pol.n_contenders, 0xFF, nk * sizeof(uint16_t), e->stream));       // kContenderAll: the whole grid
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));      // (bid_grid is only borrowed)
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_bid_curves_fetch(adc_engine *e, double *impression_rate_host, double *cpc_host)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
-    const size_t n = (size_t)e->v.N * e->v.K * e->pol.n_bids;
-    if (e->v.model == ADC_MODEL_EXPLICIT) {          // the points evaluated on the device, by the function every ideal kernel calls
-        double *d = nullptr;
-        if (hipMalloc((void **)&d, 2 * n * 8) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc failed");
-        const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)e->num_cus * 64));
-        hipLaunchKernelGGL(k_explicit_curve_points, dim3(blocks), dim3(256), 0, e->stream, e->v, e->pol, d, d + n);
-        hipError_t err = hipGetLastError();
-        if (err == hipSuccess && impression_rate_host) err = hipMemcpyAsync(impression_rate_host, d, n * 8, hipMemcpyDeviceToHost, e->stream);
-        if (err == hipSuccess && cpc_host) err = hipMemcpyAsync(cpc_host, d + n, n * 8, hipMemcpyDeviceToHost, e->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-        (void)hipFree(d);
-        HIP_TRY(err);
-        return ADC_OK;
-    }
-    std::vector<uint2> packed(n);
-    HIP_TRY(hipMemcpyAsync(packed.data(), e->pol.curve, n * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const double ns = (double)e->pol.n_samples;
-    for (size_t i = 0; i < n; ++i) {            // the same IEEE operations k_ideal_from_curves applies
-        const unsigned int idx = packed[i].y & 0x7FFFFFFFu;
-        if (impression_rate_host) impression_rate_host[i] = (double)idx / ns;
-        if (cpc_host) cpc_host[i] = ((double)packed[i].x / 100.0) / ((packed[i].y >> 31) ? ns : (double)(idx + 1u));
-    }
-    return ADC_OK;
-}
-
-// the contender lists of the cached curves (k_curve_contenders): n_nk[N*K] (0xFFFF = "the whole grid"), per entry 6 words
-// {margin interval lo, hi (float32 bits), curve point x, y, grid index, 0}
-ADC_EXPORT int adc_engine_bid_curves_contenders(adc_engine *e, uint16_t *n_nk, uint32_t *entries_nkc6, int32_t *cap)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    if (cap) *cap = e->pol.cont_cap;
-    if (n_nk) HIP_TRY(hipMemcpyAsync(n_nk, e->pol.n_contenders, nk * 2, hipMemcpyDeviceToHost, e->stream));
-    if (entries_nkc6) HIP_TRY(hipMemcpyAsync(entries_nkc6, e->pol.contender, nk * e->pol.cont_cap * sizeof(ContenderEntry), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-namespace {
-// the per-step ideal of every keyword into the device-side arrays and running sums (nothing to the host): chain-compatible
-int ideal_step_chained(adc_engine *e)
-{
-    if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
-    const bool full_scan = e->ideal_full_scan;
-    const int rc = launch_chained(e, [&](const View &v, const PolicyView &p, hipStream_t st, float *, float *) {
-        // the reference evaluates env.keyword_params as they stand before the step, i.e. with the last update_keywords applied
-        if (v.drift_on) hipLaunchKernelGGL(k_materialize_drift, dim3(v.N), dim3(256), 0, st, v);
-        launch_ideal_step(v, p, st, full_scan);
-    });
-    if (!rc && e->v.drift_on) e->drift_applied = true;
-    return rc;
-}
-int policy_oracle_chained(adc_engine *e, float budget)
-{
-    if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build / adc_engine_ideal_step have not been called");
-    return launch_chained(e, [&](const View &v, const PolicyView &p, hipStream_t st, float *d_bids, float *d_budget) {
-        hipLaunchKernelGGL(k_policy_oracle, dim3((unsigned)((v.K + 255) / 256), (unsigned)v.N), dim3(256), 0, st, v, p, budget, d_bids, d_budget);
-    });
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_ideal_step(adc_engine *e, double *ideal_host_nk, int32_t *best_index_host_nk)
-{
-    if (e && !ideal_host_nk && !best_index_host_nk) {
-        ENGINE_GUARD_STEP(e);
-        return ideal_step_chained(e);
-    }
-    ENGINE_GUARD(e);
-    if (!e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    // the reference evaluates env.keyword_params as they stand before the step, i.e. with the last update_keywords applied
-    if (e->v.drift_on) { materialize_drift(e); HIP_TRY(hipGetLastError()); }
-    launch_ideal_step(e->v, e->pol, e->stream, e->ideal_full_scan);
-    HIP_TRY(hipGetLastError());
-    if (ideal_host_nk) HIP_TRY(hipMemcpyAsync(ideal_host_nk, e->pol.ideal, nk * 8, hipMemcpyDeviceToHost, e->stream));
-    if (best_index_host_nk) HIP_TRY(hipMemcpyAsync(best_index_host_nk, e->pol.best, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (ideal_host_nk || best_index_host_nk) HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_policy_oracle(adc_engine *e, float budget)
-{
-    ENGINE_GUARD_STEP(e);
-    return policy_oracle_chained(e, budget);
-}
-
-ADC_EXPORT int adc_engine_metrics_read_nk(adc_engine *e, int64_t *profit_cents_nk, double *ideal_sum_nk, double *ideal_pos_sum_nk)
-{
-    ENGINE_GUARD(e);
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    if ((ideal_sum_nk || ideal_pos_sum_nk) && !e->have_ideal) return fail(ADC_ESTATE, "no ideal profit has been accumulated (adc_engine_ideal_step)");
-    std::vector<int32_t> lo;
-    if (profit_cents_nk) {          // the 64-bit spill into the caller's array, the 32-bit words beside it: added below
-        lo.resize(nk);
-        HIP_TRY(hipMemcpyAsync(profit_cents_nk, e->v.metric_hi, nk * 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(lo.data(), e->v.metric_lo, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    if (ideal_sum_nk) HIP_TRY(hipMemcpyAsync(ideal_sum_nk, e->pol.sum_ideal, nk * 8, hipMemcpyDeviceToHost, e->stream));
-    if (ideal_pos_sum_nk) HIP_TRY(hipMemcpyAsync(ideal_pos_sum_nk, e->pol.sum_ideal_pos, nk * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (size_t i = 0; i < lo.size(); ++i) profit_cents_nk[i] += lo[i];
-    return ADC_OK;
-}
-
-// per-env AKNCP and NCP of the running episode, reduced on the device (k_akncp_ncp)
-ADC_EXPORT int adc_engine_metrics_akncp_ncp(adc_engine *e, double days, double *akncp_n, double *ncp_n)
-{
-    ENGINE_GUARD(e);
-    if (!akncp_n || !ncp_n) return fail(ADC_EINVAL, "NULL output");
-    if (!e->have_ideal) return fail(ADC_ESTATE, "no ideal profit has been accumulated (adc_engine_ideal_step)");
-    if (!e->v.metrics_on) return fail(ADC_ESTATE, "metric mode is off (adc_engine_metrics_enable)");
-    if (e->v.K > kMedianMaxK) return fail(ADC_EINVAL, "num_keywords beyond the device-side median (4096): reduce adc_engine_metrics_read_nk on the host");
-    const size_t n = (size_t)e->v.N;
-    double *d = nullptr;
-    if (hipMalloc((void **)&d, 2 * n * 8) != hipSuccess) return fail(ADC_ENOMEM, "hipMalloc failed");
-    int P = 1;
-    while (P < e->v.K) P <<= 1;
-    hipLaunchKernelGGL(k_akncp_ncp, dim3((unsigned)n), dim3(kMedianBlock), (size_t)P * 8, e->stream, e->v, e->pol, days, d, d + n);
-    int rc = ADC_OK;
-    if (hipGetLastError() != hipSuccess) rc = fail(ADC_EHIP, "k_akncp_ncp launch failed");
-    if (!rc && (hipMemcpyAsync(akncp_n, d, n * 8, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                hipMemcpyAsync(ncp_n, d + n, n * 8, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess))
-        rc = fail(ADC_EHIP, "download failed");
-    (void)hipFree(d);
-    return rc;
-}
-
-// ---- NaiveInterpolationStrategy, one agent per env (parts/kernel_interp_agent.inc) ---------------------------------------
-namespace {
-// the agent's view of the env group that starts at env e0: every per-keyword and per-env array moves to that env; the
-// slot-major lists keep the engine's stride
-inline InterpView interp_view_from(const adc_engine *e, size_t e0)
-{
-    InterpView p = e->ip;
-    const size_t o = e0, ok = o * (size_t)e->v.K;
-    auto at = [](auto *&ptr, size_t off) { if (ptr) ptr += off; };
-    at(p.ave_rpc, ok); at(p.n_rpc, ok); at(p.ave_sctr, ok); at(p.n_sctr, ok); at(p.max_obs, ok); at(p.last_bid, ok); at(p.last_index, ok);
-    at(p.n_clk, ok); at(p.n_cpc, ok); at(p.clk_cent, ok); at(p.clk_ave, ok); at(p.clk_cnt, ok);
-    at(p.cpc_cent, ok); at(p.cpc_ave, ok); at(p.cpc_cnt, ok); at(p.kw_cost, ok); at(p.kw_profit, ok);
-    at(p.budget, o); at(p.profit, o); at(p.cost, o); at(p.key, o); at(p.tick, o);
-    return p;
-}
-// `more` further updates fit the lists (a capacity of 300 holds every cent)
-inline bool interp_room(const adc_engine *e, long long more)
-{
-    return e->ip.cap >= adc::kInterpCents || e->interp_updates + more <= (long long)e->ip.cap;
-}
-inline int interp_grid_check(const double *bids, int n)
-{
-    if (!bids || n < 1 || n > adc::kInterpMaxBids) return fail(ADC_EINVAL, "allowed_bids must hold 1 to 2048 values");
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(bids[i])) return fail(ADC_EINVAL, "allowed_bids must be finite");
-    return ADC_OK;
-}
-int interp_step_chained(adc_engine *e, float budget_override)
-{
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    // counted before anything is enqueued, so that a launch failing partway leaves the count high, never low (a captured day
-    // is counted where its graph is launched)
-    if (!e->in_capture) e->interp_updates += 1;
-    return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
-        const InterpView p = interp_view_from(e, (size_t)(d_budget - e->d_budget));      // (the group's first env)
-        hipLaunchKernelGGL(k_interp_step, dim3((unsigned)v.N), dim3(256), 0, st, v, p, (const float *)nullptr, v.clk, v.cost,
-                           v.conv, v.rev, 1, 1, (const double *)nullptr, budget_override, d_bids, d_budget);
-    });
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_interp_init(adc_engine *e, double threshold, double bid_step, const double *allowed_bids, int32_t n_bids,
-                                      int32_t capacity, const uint64_t *seeds_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!std::isfinite(threshold) || !std::isfinite(bid_step)) return fail(ADC_EINVAL, "threshold and bid_step must be finite");
-    if (int rc = interp_grid_check(allowed_bids, n_bids)) return rc;
-    if (capacity < 0 || capacity > adc::kInterpCents) return fail(ADC_EINVAL, "capacity must be 0 (default) to 300");
-    ENGINE_GUARD(e);
-    const int cap = capacity > 0 ? capacity : std::min(adc::kInterpCents, std::max(1, e->v.max_days + 1));
-    const size_t N = e->v.N, nk = N * e->v.K;
-    if (e->have_interp && cap != e->ip.cap) return fail(ADC_EINVAL, "the capacity is fixed by the first adc_engine_interp_init");
-    if (!e->have_interp) {
-        InterpView &p = e->ip;
-        const size_t slots = nk * (size_t)cap;
-        int rc;
-        if ((rc = dev_alloc(e, &p.ave_rpc, nk)) || (rc = dev_alloc(e, &p.n_rpc, nk)) || (rc = dev_alloc(e, &p.ave_sctr, nk)) ||
-            (rc = dev_alloc(e, &p.n_sctr, nk)) || (rc = dev_alloc(e, &p.max_obs, nk)) || (rc = dev_alloc(e, &p.last_bid, nk)) ||
-            (rc = dev_alloc(e, &p.last_index, nk)) ||
-            (rc = dev_alloc(e, &p.n_clk, nk)) || (rc = dev_alloc(e, &p.n_cpc, nk)) || (rc = dev_alloc(e, &p.clk_cent, slots)) ||
-            (rc = dev_alloc(e, &p.clk_ave, slots)) || (rc = dev_alloc(e, &p.clk_cnt, slots)) || (rc = dev_alloc(e, &p.cpc_cent, slots)) ||
-            (rc = dev_alloc(e, &p.cpc_ave, slots)) || (rc = dev_alloc(e, &p.cpc_cnt, slots)) || (rc = dev_alloc(e, &p.kw_cost, nk)) ||
-            (rc = dev_alloc(e, &p.kw_profit, nk)) || (rc = dev_alloc(e, &p.budget, N)) || (rc = dev_alloc(e, &p.profit, N)) ||
-            (rc = dev_alloc(e, &p.cost, N)) || (rc = dev_alloc(e, &p.key, N)) || (rc = dev_alloc(e, &p.tick, N)))
-            return rc;
-        double *grid = nullptr;
-        if ((rc = dev_alloc(e, &grid, (size_t)adc::kInterpMaxBids))) return rc;
-        p.grid = grid;
-        p.cap = cap;
-        p.slot_stride = nk;
-        e->have_interp = true;
-    }
-    e->ip.threshold = threshold;
-    e->ip.bid_step = bid_step;
-    e->ip.n_bids = n_bids;
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(e->ip.grid), allowed_bids, (size_t)n_bids * 8, hipMemcpyHostToDevice, e->stream));
-    e->interp_updates = 0;
-    uint64_t *d_seeds = nullptr;
-    if (seeds_n) { HIP_TRY(hipMalloc((void **)&d_seeds, N * 8)); HIP_TRY(hipMemcpyAsync(d_seeds, seeds_n, N * 8, hipMemcpyHostToDevice, e->stream)); }
-    hipLaunchKernelGGL(k_interp_init, dim3((unsigned)((e->v.K + 255) / 256), (unsigned)N), dim3(256), 0, e->stream, e->ip, e->v.K,
-                       d_seeds, e->cfg.seed, e->cfg.env_id_base);
-    hipError_t err = hipGetLastError();
-    hipError_t err2 = hipStreamSynchronize(e->stream);
-    if (d_seeds) (void)hipFree(d_seeds);
-    HIP_TRY(err);
-    HIP_TRY(err2);
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_interp_set_allowed_bids(adc_engine *e, const double *bids, int32_t n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = interp_grid_check(bids, n)) return rc;
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    ENGINE_GUARD(e);
-    HIP_TRY(hipMemcpyAsync(const_cast<double *>(e->ip.grid), bids, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->ip.n_bids = n;
-    return ADC_OK;
-}
-
-namespace {
-// update (host arrays: all five or none) and/or act on the engine's stream; host inputs are staged through temporaries
-int interp_launch(adc_engine *e, const double *prev_bids_nk, const int32_t *clicks_nk, const float *cost_nk, const int32_t *conv_nk,
-                  const float *rev_nk, int do_update, int do_act, const double *replay_u_nk, float budget_override)
-{
-    const size_t nk = (size_t)e->v.N * e->v.K;
-    std::vector<float> bids32;
-    if (do_update && prev_bids_nk) {
-        bids32.resize(nk);
-        for (size_t i = 0; i < nk; ++i) bids32[i] = (float)prev_bids_nk[i];       // torch.Tensor([prev_bid])
-    }
-    float *d_bid = nullptr, *d_cost = nullptr, *d_rev = nullptr;
-    int32_t *d_clk = nullptr, *d_conv = nullptr;
-    double *d_u = nullptr;
-    auto done = [&](hipError_t err) {
-        hipError_t e2 = hipStreamSynchronize(e->stream);
-        (void)hipFree(d_bid); (void)hipFree(d_cost); (void)hipFree(d_rev); (void)hipFree(d_clk); (void)hipFree(d_conv); (void)hipFree(d_u);
-        if (err != hipSuccess) return fail(ADC_EHIP, hipGetErrorString(err));
-        if (e2 != hipSuccess) return fail(ADC_EHIP, hipGetErrorString(e2));
-        return (int)ADC_OK;
-    };
-    hipError_t err = hipSuccess;
-    if (do_update && prev_bids_nk) {
-        if (hipMalloc((void **)&d_bid, nk * 4) != hipSuccess || hipMalloc((void **)&d_clk, nk * 4) != hipSuccess ||
-            hipMalloc((void **)&d_cost, nk * 4) != hipSuccess || hipMalloc((void **)&d_conv, nk * 4) != hipSuccess ||
-            hipMalloc((void **)&d_rev, nk * 4) != hipSuccess) { (void)done(hipSuccess); return fail(ADC_ENOMEM, "hipMalloc failed"); }
-        err = hipMemcpyAsync(d_bid, bids32.data(), nk * 4, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_clk, clicks_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_cost, cost_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_conv, conv_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_rev, rev_nk, nk * 4, hipMemcpyHostToDevice, e->stream);
-    }
-    if (err == hipSuccess && replay_u_nk && do_act) {
-        if (hipMalloc((void **)&d_u, nk * 8) != hipSuccess) { (void)done(hipSuccess); return fail(ADC_ENOMEM, "hipMalloc failed"); }
-        err = hipMemcpyAsync(d_u, replay_u_nk, nk * 8, hipMemcpyHostToDevice, e->stream);
-    }
-    if (err == hipSuccess) {
-        if (do_update) e->interp_updates += 1;        // (before the launch: a failure leaves the count high, never low)
-        hipLaunchKernelGGL(k_interp_step, dim3((unsigned)e->v.N), dim3(256), 0, e->stream, e->v, e->ip, (const float *)d_bid,
-                           d_clk ? d_clk : e->v.clk, d_cost ? d_cost : e->v.cost, d_conv ? d_conv : e->v.conv, d_rev ? d_rev : e->v.rev,
-                           do_update, do_act, (const double *)d_u, budget_override, e->d_bids, e->d_budget);
-        err = hipGetLastError();
-    }
-    return done(err);
-}
-}  // namespace
-
-ADC_EXPORT int adc_engine_interp_update(adc_engine *e, const double *prev_bids_nk, const int32_t *clicks_nk, const float *cost_nk,
-                                        const int32_t *conversions_nk, const float *revenue_nk)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const int given = (prev_bids_nk != nullptr) + (clicks_nk != nullptr) + (cost_nk != nullptr) + (conversions_nk != nullptr) +
-                      (revenue_nk != nullptr);
-    if (given != 0 && given != 5) return fail(ADC_EINVAL, "pass all of prev_bids/clicks/cost/conversions/revenue, or none");
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    if (prev_bids_nk) {
-        const size_t nk = (size_t)e->v.N * e->v.K;
-        for (size_t i = 0; i < nk; ++i)
-            if (!std::isfinite(prev_bids_nk[i])) return fail(ADC_EINVAL, "previous bids must be finite");
-    }
-    if (!interp_room(e, 1)) return fail(ADC_EINVAL, "the interpolation agent's capacity is full: one more update could overflow it");
-    ENGINE_GUARD(e);
-    return interp_launch(e, prev_bids_nk, clicks_nk, cost_nk, conversions_nk, revenue_nk, 1, 0, nullptr, 0.0f);
-}
-
-ADC_EXPORT int adc_engine_interp_act(adc_engine *e, float budget_override, const double *replay_uniforms_nk)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    ENGINE_GUARD(e);
-    return interp_launch(e, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, replay_uniforms_nk, budget_override);
-}
-
-ADC_EXPORT int adc_engine_interp_step(adc_engine *e, float budget_override)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    if (!interp_room(e, 1)) return fail(ADC_EINVAL, "the interpolation agent's capacity is full: one more update could overflow it");
-    ENGINE_GUARD_STEP(e);
-    return interp_step_chained(e, budget_override);
-}
-
-ADC_EXPORT int adc_engine_interp_state(adc_engine *e, float *ave_rpc_nk, int32_t *num_rpc_obs_nk, float *ave_sctr_nk,
-                                       int32_t *num_sctr_obs_nk, double *max_observed_nk, int32_t *bid_index_nk, double *budget_n, double *profit_beliefs_n,
-                                       double *cost_beliefs_n)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    const size_t n = (size_t)e->v.N, nk = n * e->v.K;
-    const InterpView &p = e->ip;
-    if (ave_rpc_nk) HIP_TRY(hipMemcpyAsync(ave_rpc_nk, p.ave_rpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (num_rpc_obs_nk) HIP_TRY(hipMemcpyAsync(num_rpc_obs_nk, p.n_rpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (ave_sctr_nk) HIP_TRY(hipMemcpyAsync(ave_sctr_nk, p.ave_sctr, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (num_sctr_obs_nk) HIP_TRY(hipMemcpyAsync(num_sctr_obs_nk, p.n_sctr, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (max_observed_nk) HIP_TRY(hipMemcpyAsync(max_observed_nk, p.max_obs, nk * 8, hipMemcpyDeviceToHost, e->stream));
-    if (bid_index_nk) HIP_TRY(hipMemcpyAsync(bid_index_nk, p.last_index, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (budget_n) HIP_TRY(hipMemcpyAsync(budget_n, p.budget, n * 8, hipMemcpyDeviceToHost, e->stream));
-    if (profit_beliefs_n) HIP_TRY(hipMemcpyAsync(profit_beliefs_n, p.profit, n * 8, hipMemcpyDeviceToHost, e->stream));
-    if (cost_beliefs_n) HIP_TRY(hipMemcpyAsync(cost_beliefs_n, p.cost, n * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_interp_entries(adc_engine *e, int32_t *capacity, int32_t *n_clicks_nk, uint16_t *clicks_cent_cnk,
-                                         float *ave_clicks_cnk, int32_t *clicks_count_cnk, int32_t *n_cpc_nk, uint16_t *cpc_cent_cnk,
-                                         double *ave_cpc_cnk, int32_t *cpc_count_cnk)
-{
-    ENGINE_GUARD(e);
-    if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-    const InterpView &p = e->ip;
-    const size_t nk = (size_t)e->v.N * e->v.K, slots = nk * (size_t)p.cap;
-    if (capacity) *capacity = p.cap;
-    if (n_clicks_nk) HIP_TRY(hipMemcpyAsync(n_clicks_nk, p.n_clk, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (clicks_cent_cnk) HIP_TRY(hipMemcpyAsync(clicks_cent_cnk, p.clk_cent, slots * 2, hipMemcpyDeviceToHost, e->stream));
-    if (ave_clicks_cnk) HIP_TRY(hipMemcpyAsync(ave_clicks_cnk, p.clk_ave, slots * 4, hipMemcpyDeviceToHost, e->stream));
-    if (clicks_count_cnk) HIP_TRY(hipMemcpyAsync(clicks_count_cnk, p.clk_cnt, slots * 4, hipMemcpyDeviceToHost, e->stream));
-    if (n_cpc_nk) HIP_TRY(hipMemcpyAsync(n_cpc_nk, p.n_cpc, nk * 4, hipMemcpyDeviceToHost, e->stream));
-    if (cpc_cent_cnk) HIP_TRY(hipMemcpyAsync(cpc_cent_cnk, p.cpc_cent, slots * 2, hipMemcpyDeviceToHost, e->stream));
-    if (ave_cpc_cnk) HIP_TRY(hipMemcpyAsync(ave_cpc_cnk, p.cpc_ave, slots * 8, hipMemcpyDeviceToHost, e->stream));
-    if (cpc_count_cnk) HIP_TRY(hipMemcpyAsync(cpc_count_cnk, p.cpc_cnt, slots * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
-}
-
-#ifdef ADC_EXP_TIMING
-extern "C" __attribute__((visibility("default"))) int adc_debug_read(unsigned long long *out, int reset)
-{
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg), sizeof(unsigned long long) * 16);
-    // slots 8..15: k_step_implicit_fast (wave 0 of every workgroup), summed over the 256 rows of g_fdbg
-    static unsigned long long rows[256][8];
-    hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_fdbg), sizeof(rows));
-    for (int i = 0; i < 8; ++i) { out[8 + i] = 0; for (int r = 0; r < 256; ++r) out[8 + i] += rows[r][i]; }
-    if (reset) {
-        unsigned long long z[16] = {0};
-        hipMemcpyToSymbol(HIP_SYMBOL(g_dbg), z, sizeof(z));
-        std::memset(rows, 0, sizeof(rows));
-        hipMemcpyToSymbol(HIP_SYMBOL(g_fdbg), rows, sizeof(rows));
-    }
-    return 0;
-}
-
-// k_step_implicit_fast, all waves since the last reset: out2 = {Philox calls issued in phase 2 (wave-call-slots), calls that hold at
-// least one auction (lane-calls: 64 of them fill a slot)}
-extern "C" __attribute__((visibility("default"))) int adc_debug_read_fast_slots(unsigned long long *out2, int reset)
-{
-    hipDeviceSynchronize();
-    static unsigned long long rows[256][2];
-    hipMemcpyFromSymbol(rows, HIP_SYMBOL(g_fslots), sizeof(rows));
-    out2[0] = out2[1] = 0;
-    for (int r = 0; r < 256; ++r) { out2[0] += rows[r][0]; out2[1] += rows[r][1]; }
-    if (reset) {
-        std::memset(rows, 0, sizeof(rows));
-        hipMemcpyToSymbol(HIP_SYMBOL(g_fslots), rows, sizeof(rows));
-    }
-    return 0;
-}
-#endif

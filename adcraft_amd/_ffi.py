@@ -394,6 +394,9 @@ def lib():
         "adc_engine_pg_update_queued": ([vp, i32, C.POINTER(PGStats)], C.c_int),
         "adc_engine_pg_pop_update_queued": ([vp, i32, C.POINTER(PGStats)], C.c_int),
         "adc_engine_teach_days": ([vp, C.c_int, i32, f32], C.c_int),
+        "adc_engine_dagger_days": ([vp, C.c_int, i32, f32, f32], C.c_int),
+        "adc_engine_dagger_mask_fetch": ([vp, vp], C.c_int),
+        "adc_dagger_coin_host": ([u64, C.c_uint32, f32], C.c_int),
         "adc_im_config_check": ([C.POINTER(IMConfig), C.POINTER(C.c_char_p)], C.c_int),
         "adc_engine_im_init": ([vp, C.POINTER(IMConfig)], C.c_int),
         "adc_engine_im_advantages": ([vp, vp, vp], C.c_int),

@@ -92,4 +92,93 @@ class ImitationTrainer:
         self.engine.im_state(state)
 
 
-__all__ = ["ImitationTrainer", "bc", "marwil"]
+class DAggerTrainer:
+    """DAgger (Ross, Gordon and Bagnell 2011) over StepEngine.dagger_days: in round i the env is driven, env by env, by the teacher
+    with probability beta_i = beta0 * beta_decay^i and by the learner otherwise, the teacher labels every visited state, and the
+    clone is trained on everything collected so far.  Round 0 at beta0 = 1 is a round of teacher days.
+
+    engine, policy, teacher, epochs, minibatches, budget, agent_seeds, pg_options and the further keywords are ImitationTrainer's
+    ("interpolation" cannot teach a DAgger day); rounds x days is the record's horizon.  aggregate=True keeps every round's days in
+    the record - `im_advantages` / `im_update` run over all of them, so a round's update costs as many samples as have been
+    collected; aggregate=False resets the record before a round and trains on that round alone.  The loss is behaviour cloning:
+    MARWIL's weight has no meaning on days the mixture drove, so beta of im_config is 0; the value loss under `vf_coef` fits the
+    value network to the mixture's returns.  The record lives on the device and is not part of state()."""
+
+    def __init__(self, engine, policy, teacher="oracle", rounds=10, days=10, epochs=4, beta0=1.0, beta_decay=0.5, aggregate=True,
+                 budget=100000.0, minibatches=1, agent_seeds=None, pg_options=None, **options):
+        if minibatches < 1 or engine.num_envs % minibatches:
+            raise ValueError("minibatches must divide the engine's envs")
+        if rounds < 1 or days < 1:
+            raise ValueError("rounds and days: at least 1")
+        if not 0.0 <= beta0 <= 1.0 or not 0.0 <= beta_decay <= 1.0:
+            raise ValueError("beta0 and beta_decay: in [0, 1]")
+        if options.pop("beta", 0.0) != 0.0:
+            raise ValueError("DAgger clones: the imitation loss's beta is 0 (MARWIL's weight needs returns that follow the labelled action)")
+        im = {k: options.pop(k) for k in _IM_KEYS if k in options}
+        im["beta"] = 0.0
+        self.engine, self._template, self.teacher = engine, policy, teacher
+        self.rounds, self.days, self.epochs, self.budget = int(rounds), int(days), int(epochs), float(budget)
+        self.beta0, self.beta_decay, self.aggregate = float(beta0), float(beta_decay), bool(aggregate)
+        self.im_config = im
+        self.config = dict(dict(_PG_DEFAULTS, **options), **dict(pg_options or {}))
+        self.config["minibatch_envs"] = engine.num_envs // int(minibatches)
+        engine.mlp_init(policy, seeds=agent_seeds, deterministic=False)
+        engine.rollout_enable(self.rounds * self.days if self.aggregate else self.days, obs=True)
+        engine.pg_init(**self.config)
+        engine.im_init(**im)
+        self.round, self._recorded = 0, 0
+        self.history = []
+
+    def beta(self, round_index=None):
+        """the teacher's share of round `round_index` (default: the next one)"""
+        return self.beta0 * self.beta_decay ** (self.round if round_index is None else int(round_index))
+
+    def recorded(self):
+        """days in the record after the last round"""
+        return self._recorded
+
+    def iteration(self, reset=False, reset_seeds=None):
+        """(reset), `days` DAgger days at the round's beta, the returns and the update over the record; returns the update's
+        statistics with `round`, `beta`, `teacher_share` (of this round's env-days the teacher drove) and `recorded` (days trained on)"""
+        e = self.engine
+        if self.aggregate and self.round >= self.rounds:
+            raise ValueError("the aggregated record is full: the trainer was built for `rounds` rounds")
+        if reset:
+            e.reset(seeds=reset_seeds)
+        if not self.aggregate:
+            e.rollout_reset()
+        beta = self.beta()
+        e.dagger_days(self.teacher, self.days, beta, self.budget)
+        mask = e.dagger_mask()
+        e.im_advantages()
+        stats = e.im_update(self.epochs)
+        stats.update(round=self.round, beta=beta, teacher_share=float(mask[-self.days:].mean()), recorded=int(mask.shape[0]),
+                     ma=e.im_state()["ma"])
+        self.round, self._recorded = self.round + 1, int(mask.shape[0])
+        self.history.append(stats)
+        return stats
+
+    def policy(self):
+        """an MLPPolicy holding the cloned policy layers, value layers and log_std"""
+        return policy_from_flat(self._template, self.engine.pg_state()["theta"])
+
+    def state(self, state=None):
+        """ImitationTrainer.state's dict plus `round` (the next round's index) and `recorded` (the record's fill level when it was
+        taken); set: theta, the optimiser, the moving scale and the round index continue - the record itself stays the engine's"""
+        return history_carry(self.engine, self._state, state)
+
+    def load_state(self, state):
+        self.state(state)
+
+    def _state(self, state):
+        if state is None:
+            st = self.engine.pg_state()
+            st.update(self.engine.im_state())
+            st.update(round=self.round, recorded=self.recorded())
+            return st
+        self.engine.pg_state(state)
+        self.engine.im_state(state)
+        self.round = int(state.get("round", self.round))
+
+
+__all__ = ["ImitationTrainer", "DAggerTrainer", "bc", "marwil"]

@@ -57,7 +57,8 @@
 //   parts/kernel_pg_queued.inc    the PPO / A2C learners' queued update: the stop and the clip scale decided on the device (k_pg_decide), the
 //        chain's kernels that read a member's control block and pass a stopped member by.
 //   parts/kernel_imitation.inc    imitation learning: the teacher's action into a teacher day's record slot (k_teach_record), the sample pass
-//        of the behaviour-cloning / MARWIL loss (k_im_sample: pg_sample_body's instantiation kIm; adc_imitation.h).
+//        of the behaviour-cloning / MARWIL loss (k_im_sample: pg_sample_body's instantiation kIm; adc_imitation.h), the label,
+//        played action and mask of a DAgger day (k_dagger_mix; adc_dagger.h).
 //   parts/kernel_td3.inc          off-policy training: the replay ring, the TD3 target, the twin critics, the actor's gradient (adc_td3.h);
 //        the store, the target, the actor's pass and Polyak are td3_*_body functions that the solo kernel and its population twin both call.
 //   parts/kernel_sac.inc          soft actor-critic: the soft target, the critics' pass, the actor's step, the temperature (adc_sac.h);
@@ -94,7 +95,7 @@
 //   parts/pg_shuffle_api.inc      the entry points of the shuffled minibatches / target-KL stop add-on, the update under it, over pg_core.inc.
 //   parts/pg_api.inc              the entry points of policy-gradient training, one function under the learner and the learner population:
 //                                 the advantages, a minibatch, the host-driven and the queued update, over pg_core.inc.
-//   parts/imitation_api.inc       the entry points of teacher days and of imitation learning over the single-learner trainer, over pg_core.inc.
+//   parts/imitation_api.inc       the entry points of teacher days, DAgger days and of imitation learning over the single-learner trainer, over pg_core.inc.
 //   parts/offpolicy_core.inc      what the four off-policy front ends share on the host: the ring, the critic upload, the state
 //                                 vectors, the allocation, an update's launch helpers, the populations' update driver.
 //   parts/td3_api.inc             the entry points of off-policy (TD3) training, over offpolicy_core.inc.
@@ -130,6 +131,7 @@
 #include "adc_pg_kl.h"
 #include "adc_pg_shuffle.h"
 #include "adc_imitation.h"
+#include "adc_dagger.h"
 #include "adc_td3.h"
 #include "adc_sac.h"
 #include "adc_pbt.h"

@@ -21,6 +21,7 @@
 #include "adc_pg_kl.h"
 #include "adc_pg_shuffle.h"
 #include "adc_imitation.h"
+#include "adc_dagger.h"
 #include "adc_td3.h"
 #include "adc_sac.h"
 #include "adc_pbt.h"
@@ -1421,6 +1422,12 @@ ADC_EXPORT int adc_im_grad_host(const adc_mlp_config *mlp, int32_t num_keywords,
         stats->weight = st.clip_fraction; stats->grad_norm = st.grad_norm; stats->explained_variance = st.explained_variance;
     }
     return ADC_OK;
+}
+
+// ---- DAgger on the host (adc_dagger.h: the code k_dagger_mix runs): 1 when the env's coin of the day picks the teacher -------------
+ADC_EXPORT int adc_dagger_coin_host(uint64_t key, uint32_t tick, float beta)
+{
+    return adc::dagger_coin(key, tick, adc::bernoulli_threshold(beta)) ? 1 : 0;
 }
 
 // ---- the KL penalty and the value-loss clip on the host (adc_pg_kl.h: the code parts/kernel_pg_kl.inc runs) ---------------------

@@ -135,6 +135,12 @@ struct adc_engine {
     int ro_teacher = 0;
     float *teach_act = nullptr;
     std::vector<void *> teach_allocs;
+    // DAgger days (adc_engine_dagger_days; the law is adc_dagger.h): how many of the record's teacher days the beta-mixture drove, and
+    // one byte per (day, env) of the record - 1: the teacher's action was consumed ([ro_T][N], the record's allocation, made at the
+    // first DAgger day of a record; dg_day[t] says which of the record's days wrote their row)
+    int ro_dagger = 0;
+    uint8_t *dg_mask = nullptr;
+    std::vector<uint8_t> dg_day;        // [ro_T] 1: day t of the record is a DAgger day
     // imitation learning over the live single-learner trainer (adc_engine_im_init; parts/kernel_imitation.inc, parts/imitation_api.inc;
     // the law is adc_imitation.h): the moving scale ma, how often it was updated, the scale c of the last advantages call
     bool have_im = false, im_adv_ready = false;

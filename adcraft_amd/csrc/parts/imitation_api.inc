@@ -1,25 +1,25 @@
 // imitation_api.inc - the extern "C" entry points of imitation learning (include/adcraft_engine.h; the kernels are
 // parts/kernel_imitation.inc, the law csrc/adc_imitation.h): teacher days - days on which an expert acts and the record keeps what
-// the learner would have seen next to what the expert did - and behaviour cloning / MARWIL over such a record as an add-on to the
-// single-learner policy-gradient trainer, whose theta, Adam moments, scratch and update kernels it shares (parts/pg_core.inc).
+// the learner would have seen next to what the expert did -, DAgger days - teacher days on which a per-env coin picks whose action
+// the step consumes (csrc/adc_dagger.h) - and behaviour cloning / MARWIL over such a record as an add-on to the single-learner
+// policy-gradient trainer, whose theta, Adam moments, scratch and update kernels it shares (parts/pg_core.inc).
 // (part of the single translation unit adc_engine.hip)
 namespace {
-// one teacher day: the learner's act with its action thrown away, the teacher's act, the teacher's action into the record, the
-// step, the outcome.  Chained and group-compatible like mlp_day (the callers have checked everything)
-int teach_day(adc_engine *e, int teacher, float budget)
+// the first two steps of a labelled day (a teacher day or a DAgger day; the callers have checked everything):
+// 1. the learner's act on the observation the last step left; its bids and budget go to the scratch, the slot takes obs and value
+int teach_learner_act(adc_engine *e, float budget)
 {
     const int t = e->ro_t, K = e->v.K;
-    int rc;
-    // (a day recorded after the envs moved outside the record does not follow the unstored day before it: as mlp_day)
-    if ((e->have_td3 || e->have_td3_pop || e->have_sac || e->have_sac_pop) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
-    // 1. the learner's act on the observation the last step left; its bids and budget go to the scratch
     float *sbids = e->teach_act, *sbudget = e->teach_act + (size_t)e->v.N * (size_t)K;
-    if ((rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *, float *d_budget) {
-            const size_t e0 = (size_t)(d_budget - e->d_budget);       // (the group's first env)
-            mlp_launch_kernel(v, mlp_view_from(e, e0), st, 0, nullptr, budget, sbids + e0 * (size_t)K, sbudget + e0, rollout_slot(e, true, t, e0), nullptr);
-        })))
-        return rc;
-    // 2. the teacher's act, as one_day has it act (ADC_POLICY_FIXED_ACTIONS: the action buffers as they are)
+    return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *, float *d_budget) {
+        const size_t e0 = (size_t)(d_budget - e->d_budget);       // (the group's first env)
+        mlp_launch_kernel(v, mlp_view_from(e, e0), st, 0, nullptr, budget, sbids + e0 * (size_t)K, sbudget + e0, rollout_slot(e, true, t, e0), nullptr);
+    });
+}
+// 2. the teacher's act, as one_day has it act (ADC_POLICY_FIXED_ACTIONS: the action buffers as they are)
+int teach_teacher_act(adc_engine *e, int teacher, float budget)
+{
+    int rc;
     if (teacher == ADC_POLICY_ZERO_MARGIN) {
         if ((rc = agent_step_chained(e, budget))) return rc;
         if (e->have_curves && (rc = ideal_step_chained(e))) return rc;
@@ -30,6 +30,22 @@ int teach_day(adc_engine *e, int teacher, float budget)
         if ((rc = ideal_step_chained(e))) return rc;
         if ((rc = policy_oracle_chained(e, budget))) return rc;
     }
+    return ADC_OK;
+}
+// (a day recorded after the envs moved outside the record does not follow the unstored day before it: as mlp_day)
+void teach_gap_note(adc_engine *e)
+{
+    if ((e->have_td3 || e->have_td3_pop || e->have_sac || e->have_sac_pop) && e->ro_t > e->td3_stored_t && e->env_moves != e->ro_moves) e->td3_gap = true;
+}
+
+// one teacher day: the learner's act with its action thrown away, the teacher's act, the teacher's action into the record, the
+// step, the outcome.  Chained and group-compatible like mlp_day (the callers have checked everything)
+int teach_day(adc_engine *e, int teacher, float budget)
+{
+    const int t = e->ro_t, K = e->v.K;
+    int rc;
+    teach_gap_note(e);
+    if ((rc = teach_learner_act(e, budget)) || (rc = teach_teacher_act(e, teacher, budget))) return rc;
     // 3. the action the step is about to consume into the slot, logp = +0
     if ((rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
             const size_t row = (size_t)t * (size_t)e->v.N + (size_t)(d_budget - e->d_budget);
@@ -47,6 +63,74 @@ int teach_day(adc_engine *e, int teacher, float budget)
     if ((rc = mlp_record_outcome_chained(e))) return rc;
     e->ro_teacher += 1;
     return e->es_accumulate ? es_accumulate_chained(e) : ADC_OK;
+}
+
+// one DAgger day (adc_dagger.h): both agents act on the same observation, the record keeps the teacher's action as the label, a
+// per-env coin picks whose action the step consumes - the scratch, the teacher's action copied over the learner's where the coin
+// says so.  The engine's action buffers are left holding the teacher's action.  Chained and group-compatible as teach_day is
+int dagger_day(adc_engine *e, int teacher, float budget, float beta)
+{
+    const int t = e->ro_t, K = e->v.K;
+    int rc;
+    teach_gap_note(e);
+    if ((rc = teach_learner_act(e, budget)) || (rc = teach_teacher_act(e, teacher, budget))) return rc;
+    // 3. the label, the played action, the mask
+    float *sbids = e->teach_act, *sbudget = e->teach_act + (size_t)e->v.N * (size_t)K;
+    const uint64_t threshold = adc::bernoulli_threshold(beta);
+    if ((rc = launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
+            const size_t e0 = (size_t)(d_budget - e->d_budget), row = (size_t)t * (size_t)e->v.N + e0;
+            const long long lanes = (long long)v.N * (K + 1);
+            const DaggerMix d{e->mp.key + e0, e->mp.tick + e0, threshold, d_bids, d_budget, sbids + e0 * (size_t)K, sbudget + e0,
+                              e->ro_action + row * (size_t)(K + 1), e->ro_logp + row, e->dg_mask + row};
+            if (e->mp.bd_lo)            // (the bounded act: the label in units of the box)
+                hipLaunchKernelGGL(k_dagger_mix_bounded, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, v.N, K, d, e->mlp_bd,
+                                   e->mlp_bd + 2 * (size_t)(K + 1));
+            else
+                hipLaunchKernelGGL(k_dagger_mix, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, v.N, K, d);
+        })))
+        return rc;
+    // 4. the step consumes the scratch; the outcome
+    if ((rc = launch_step(e, sbids, sbudget, nullptr, /* lazy_join = */ true))) return rc;
+    if ((rc = mlp_record_outcome_chained(e))) return rc;
+    e->dg_day[(size_t)t] = 1;
+    e->ro_teacher += 1;
+    e->ro_dagger += 1;
+    return e->es_accumulate ? es_accumulate_chained(e) : ADC_OK;
+}
+
+// what a call of labelled days opens with, behind its own first checks: adc_engine_teach_days' refusals in their order
+int teach_enter(const adc_engine *e, int teacher_policy, int32_t days)
+{
+    if (teacher_policy == ADC_POLICY_MLP) return fail(ADC_EINVAL, "the learned agent cannot be its own teacher: its days are adc_engine_run_days(ADC_POLICY_MLP)");
+    if (teacher_policy != ADC_POLICY_FIXED_ACTIONS && teacher_policy != ADC_POLICY_ZERO_MARGIN && teacher_policy != ADC_POLICY_ORACLE &&
+        teacher_policy != ADC_POLICY_INTERPOLATION)
+        return fail(ADC_EINVAL, "unknown policy");
+    if (int rc = mlp_ready(e)) return rc;
+    if (e->pop_M != 0) return fail(ADC_ESTATE, "teacher days with a population active are not supported (adc_engine_mlp_population(0) first)");
+    if (e->lrn_M != 0) return fail(ADC_ESTATE, "teacher days with learners active are not supported (adc_engine_mlp_learners(0) first)");
+    if (e->mp.sq_lo) return fail(ADC_ESTATE, "teacher days under a squashed action are not supported: the record would need the pre-squash action of the teacher");
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "teacher days need a rollout record (adc_engine_rollout_enable)");
+    if (!e->ro_obs) return fail(ADC_ESTATE, "teacher days need the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
+    if (days < 0) return fail(ADC_EINVAL, "days < 0");
+    if (days > 0 && !rollout_room(e, days)) return fail(ADC_EINVAL, "the rollout record would overflow within these days: adc_engine_rollout_reset first");
+    if (teacher_policy == ADC_POLICY_ZERO_MARGIN && !e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
+    if (teacher_policy == ADC_POLICY_INTERPOLATION) {
+        if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
+        if (days > 0 && !interp_room(e, days)) return fail(ADC_EINVAL, "the interpolation agent's capacity would overflow within these days");
+    }
+    if (teacher_policy == ADC_POLICY_ORACLE && !e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
+    return ADC_OK;
+}
+// the scratch the learner's bids and budgets of a labelled day go to, allocated at the first such day
+int teach_scratch(adc_engine *e)
+{
+    if (e->teach_act) return ADC_OK;
+    if (int rc = mlp_alloc(e, e->teach_allocs, &e->teach_act, (size_t)e->v.N * ((size_t)e->v.K + 1u))) {
+        mlp_free(e, e->teach_allocs);
+        e->teach_act = nullptr;
+        return rc;
+    }
+    return ADC_OK;
 }
 
 int im_ready(const adc_engine *e)
@@ -69,6 +153,9 @@ int im_enter(const adc_engine *e, int epochs = 1)
     if ((rc = im_ready(e)) || (rc = pg_ready(e, false)) || (rc = pg_state_check(e, false)) || (rc = im_addon_check(e))) return rc;
     if (e->ro_t == 0) return fail(ADC_ESTATE, "no day has been recorded (adc_engine_teach_days)");
     if (e->ro_teacher != e->ro_t) return fail(ADC_ESTATE, "the record holds days the learner collected: imitation needs the teacher's action (adc_engine_rollout_reset, adc_engine_teach_days)");
+    if (e->ro_dagger > 0 && e->im_cfg.beta != 0.0f)
+        return fail(ADC_ESTATE, "the record holds DAgger days: MARWIL's weight needs returns that follow the labelled action, and a DAgger day's follow the "
+                                "mixture that drove it (adc_engine_im_init with beta = 0 clones them)");
     if (epochs < 1 || epochs > 65536) return fail(ADC_EINVAL, "epochs: 1 to 65536");
     return ADC_OK;
 }
@@ -128,33 +215,50 @@ ADC_EXPORT int adc_engine_teach_days(adc_engine *e, int teacher_policy, int32_t 
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
-    if (teacher_policy == ADC_POLICY_MLP) return fail(ADC_EINVAL, "the learned agent cannot be its own teacher: its days are adc_engine_run_days(ADC_POLICY_MLP)");
-    if (teacher_policy != ADC_POLICY_FIXED_ACTIONS && teacher_policy != ADC_POLICY_ZERO_MARGIN && teacher_policy != ADC_POLICY_ORACLE &&
-        teacher_policy != ADC_POLICY_INTERPOLATION)
-        return fail(ADC_EINVAL, "unknown policy");
-    if (int rc = mlp_ready(e)) return rc;
-    if (e->pop_M != 0) return fail(ADC_ESTATE, "teacher days with a population active are not supported (adc_engine_mlp_population(0) first)");
-    if (e->lrn_M != 0) return fail(ADC_ESTATE, "teacher days with learners active are not supported (adc_engine_mlp_learners(0) first)");
-    if (e->mp.sq_lo) return fail(ADC_ESTATE, "teacher days under a squashed action are not supported: the record would need the pre-squash action of the teacher");
-    if (e->ro_T == 0) return fail(ADC_ESTATE, "teacher days need a rollout record (adc_engine_rollout_enable)");
-    if (!e->ro_obs) return fail(ADC_ESTATE, "teacher days need the recorded network input (adc_engine_rollout_enable with ADC_ROLLOUT_OBS)");
-    if (days < 0) return fail(ADC_EINVAL, "days < 0");
-    if (days > 0 && !rollout_room(e, days)) return fail(ADC_EINVAL, "the rollout record would overflow within these days: adc_engine_rollout_reset first");
-    if (teacher_policy == ADC_POLICY_ZERO_MARGIN && !e->have_agent) return fail(ADC_ESTATE, "adc_engine_agent_init has not been called");
-    if (teacher_policy == ADC_POLICY_INTERPOLATION) {
-        if (!e->have_interp) return fail(ADC_ESTATE, "adc_engine_interp_init has not been called");
-        if (days > 0 && !interp_room(e, days)) return fail(ADC_EINVAL, "the interpolation agent's capacity would overflow within these days");
-    }
-    if (teacher_policy == ADC_POLICY_ORACLE && !e->have_curves) return fail(ADC_ESTATE, "adc_engine_bid_curves_build has not been called");
+    if (int rc = teach_enter(e, teacher_policy, days)) return rc;
     ENGINE_GUARD(e);
     int rc;
-    if (!e->teach_act && (rc = mlp_alloc(e, e->teach_allocs, &e->teach_act, (size_t)e->v.N * ((size_t)e->v.K + 1u)))) {
-        mlp_free(e, e->teach_allocs);
-        e->teach_act = nullptr;
-        return rc;
-    }
+    if ((rc = teach_scratch(e))) return rc;
     for (int d = 0; d < days; ++d)
         if ((rc = teach_day(e, teacher_policy, budget))) return rc;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_dagger_days(adc_engine *e, int teacher_policy, int32_t days, float budget, float beta)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!e->have_reset) return fail(ADC_ESTATE, "reset required, need to generate keywords to bid on");
+    if (!(beta >= 0.0f && beta <= 1.0f)) return fail(ADC_EINVAL, "beta: the share of envs the teacher drives, in [0, 1]");
+    if (teacher_policy == ADC_POLICY_INTERPOLATION)
+        return fail(ADC_EINVAL, "the interpolation agent cannot teach a DAgger day: its update keys its points by the bid it returned, which on a "
+                                "learner-driven day is not the bid the outcomes came from (adc_engine_teach_days takes it)");
+    if (int rc = teach_enter(e, teacher_policy, days)) return rc;
+    ENGINE_GUARD(e);
+    int rc;
+    if ((rc = teach_scratch(e))) return rc;
+    if (!e->dg_mask) {                  // (the mask: the record's allocation, gone with it)
+        if ((rc = mlp_alloc(e, e->ro_allocs, &e->dg_mask, (size_t)e->ro_T * (size_t)e->v.N))) return rc;
+        e->dg_day.assign((size_t)e->ro_T, (uint8_t)0);
+    }
+    for (int d = 0; d < days; ++d)
+        if ((rc = dagger_day(e, teacher_policy, budget, beta))) return rc;
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_engine_dagger_mask_fetch(adc_engine *e, uint8_t *out_tn)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (!out_tn) return fail(ADC_EINVAL, "out_tn is NULL");
+    if (e->ro_T == 0) return fail(ADC_ESTATE, "adc_engine_rollout_enable has not been called");
+    if (e->ro_teacher != e->ro_t) return fail(ADC_ESTATE, "the record holds days the learner collected: they have no teacher and no mask (adc_engine_rollout_reset)");
+    ENGINE_GUARD(e);
+    const size_t N = (size_t)e->v.N;
+    if (e->ro_dagger > 0) {
+        HIP_TRY(hipMemcpyAsync(out_tn, e->dg_mask, (size_t)e->ro_t * N, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    for (int t = 0; t < e->ro_t; ++t)       // (a plain teacher day: the teacher drove every env)
+        if (e->ro_dagger == 0 || !e->dg_day[(size_t)t]) std::memset(out_tn + (size_t)t * N, 1, N);
     return ADC_OK;
 }
 

@@ -1,5 +1,5 @@
 // kernel_imitation.inc - imitation learning on the device (adc_imitation.h): the teacher's action into the record's slot of a
-// teacher day, and the sample pass of the imitation loss.
+// teacher day, the label, played action and mask of a DAgger day (adc_dagger.h), and the sample pass of the imitation loss.
 // (part of the single translation unit adc_engine.hip)
 // -------------------------------------------------------------------------------------------------
 // k_im_sample is k_pg_sample with the imitation loss in the surrogate's place: pg_sample_body's instantiation kIm, the same
@@ -36,6 +36,44 @@ __global__ void k_teach_record_bounded(int n, int K, const float *__restrict__ b
     const float ea = a == 0 ? budgets[env] : bids[(size_t)env * (size_t)K + (size_t)(a - 1)];
     action[i] = adc::mlp_unbox(ea, lo[a], inv_half[a]);
     if (a == 0) logp[env] = 0.0f;
+}
+
+// The record's slot of a DAgger day, the played action and the mask (adc_dagger.h).  One lane per (env, component), as above: the
+// label is what k_teach_record / k_teach_record_bounded would write; where the env's coin picks the teacher the teacher's
+// env-ready component goes over the learner's in the scratch the step is about to consume (`sbids` / `sbudget`), elsewhere the
+// scratch keeps the learner's; mask[env] = the coin.  Every lane of an env draws the coin again (one Philox call): nothing is
+// shared between lanes.  `tick` is behind the day's act: the coin's tick is tick[env] - 1.  All pointers start at the view's first env.
+struct DaggerMix {
+    const uint64_t *key;                    // [n] the agents' keys
+    const uint32_t *tick;                   // [n] ... and ticks, moved on by the act
+    uint64_t threshold;                     // bernoulli_threshold(beta)
+    const float *bids, *budgets;            // [n][K], [n] the teacher's action (the engine's action buffers)
+    float *sbids, *sbudget;                 // [n][K], [n] the learner's env-ready action (the scratch)
+    float *action, *logp;                   // [n][K + 1], [n] the record's slot
+    uint8_t *mask;                          // [n] the mask's row
+};
+template <bool kBounded>
+__device__ __forceinline__ void dagger_mix_body(int n, int K, const DaggerMix &d, const float *__restrict__ lo, const float *__restrict__ inv_half)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int A = K + 1;
+    if (i >= (long long)n * A) return;
+    const int env = (int)(i / A), a = (int)(i % A);
+    const size_t kw = (size_t)env * (size_t)K + (size_t)(a > 0 ? a - 1 : 0);
+    const bool teacher = adc::dagger_coin(d.key[env], d.tick[env] - 1u, d.threshold);
+    const float ea = a == 0 ? d.budgets[env] : d.bids[kw];
+    if constexpr (kBounded) d.action[i] = adc::mlp_unbox(ea, lo[a], inv_half[a]);
+    else d.action[i] = ea;
+    if (a == 0) {
+        d.logp[env] = 0.0f;
+        d.mask[env] = teacher ? 1 : 0;
+        if (teacher) d.sbudget[env] = ea;
+    } else if (teacher) d.sbids[kw] = ea;
+}
+__global__ void k_dagger_mix(int n, int K, DaggerMix d) { dagger_mix_body<false>(n, K, d, nullptr, nullptr); }
+__global__ void k_dagger_mix_bounded(int n, int K, DaggerMix d, const float *__restrict__ lo, const float *__restrict__ inv_half)
+{
+    dagger_mix_body<true>(n, K, d, lo, inv_half);
 }
 
 __global__ __launch_bounds__(kPgBlock) void k_im_sample(PgView p, adc::ImLaw im)

@@ -107,7 +107,7 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     HIP_TRY(err2);
     e->have_mlp = true;
     // (a record sized for another action width does not survive a re-initialisation)
-    if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; e->ro_teacher = 0; }
+    if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; e->ro_teacher = e->ro_dagger = 0; e->dg_mask = nullptr; }
     return ADC_OK;
 }
 

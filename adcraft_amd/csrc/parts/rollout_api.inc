@@ -17,7 +17,8 @@ ADC_EXPORT int adc_engine_rollout_enable(adc_engine *e, int32_t horizon, int32_t
     e->ro_T = e->ro_t = 0;
     e->ro_obs = nullptr;
     e->ro_deterministic = false;
-    e->ro_teacher = 0;
+    e->ro_teacher = e->ro_dagger = 0;
+    e->dg_mask = nullptr;               // (the record's allocation: gone with it)
     if (horizon == 0) return ADC_OK;
     const size_t tn = (size_t)horizon * (size_t)e->v.N;
     int rc;
@@ -41,7 +42,8 @@ ADC_EXPORT int adc_engine_rollout_reset(adc_engine *e)
     e->ro_t = 0;
     for (NormSet *s : {&e->on, &e->rn, &e->tn, &e->sn}) s->t0 = 0;
     e->ro_deterministic = false;
-    e->ro_teacher = 0;
+    e->ro_teacher = e->ro_dagger = 0;
+    std::fill(e->dg_day.begin(), e->dg_day.end(), (uint8_t)0);
     e->pg_adv_ready = e->im_adv_ready = false;
     e->td3_stored_t = 0;
     e->td3_gap = false;

@@ -187,6 +187,9 @@ ADC_EXPORT int adc_engine_td3_store(adc_engine *e, int64_t *stored)
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     int rc;
     if ((rc = td3_ready(e)) || (rc = td3_state_check(e)) || (rc = td3_bounded_check(e, &e->td3_cfg, 1)) || (rc = off_store_check(e))) return rc;
+    if (e->ro_dagger > 0)
+        return fail(ADC_ESTATE, "the record holds DAgger days: their recorded action is the teacher's label, not the action the step consumed, so they are "
+                                "not demonstrations (adc_engine_rollout_reset, adc_engine_teach_days)");
     ENGINE_GUARD(e);
     const long long count = (long long)(e->ro_t - e->td3_stored_t) * e->v.N;        // (every env is the one learner's)
     // (raw rows under a running observation normaliser - TD3's set, e->tn: the last day's x' is the raw row an act would read now)

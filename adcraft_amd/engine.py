@@ -2088,6 +2088,24 @@ class StepEngine:
             raise ValueError(f"unknown teacher {teacher!r}: one of {sorted(self.POLICIES)}")
         check(self._lib.adc_engine_teach_days(self._h, self.POLICIES[teacher], int(days), float(budget)))
 
+    def dagger_days(self, teacher, days, beta, budget=100000.0):
+        """`days` DAgger days (csrc/adc_dagger.h): learner and teacher act on the same observation as on a teacher day, the record
+        keeps the teacher's action as the label (logp +0), and a per-env coin - the teacher with probability `beta` - picks whose
+        action the step consumes.  beta 1 is teach_days bit for bit, beta 0 the learner's own day with the teacher's label.
+        `teacher`: "fixed", "zero_margin" or "oracle".  get_actions() afterwards returns the label; dagger_mask() who drove."""
+        if teacher not in self.POLICIES:
+            raise ValueError(f"unknown teacher {teacher!r}: one of {sorted(self.POLICIES)}")
+        check(self._lib.adc_engine_dagger_days(self._h, self.POLICIES[teacher], int(days), float(budget), float(beta)))
+
+    def dagger_mask(self):
+        """uint8 [T_recorded, N]: 1 where the teacher's action was the one the step consumed (rows of plain teacher days read 1)"""
+        t = C.c_int32(0)
+        check(self._lib.adc_engine_rollout_fetch(self._h, C.byref(t), *([None] * 7)))
+        out = np.zeros((t.value, self.num_envs), np.uint8)
+        buf = out if out.size else np.zeros(1, np.uint8)         # (an empty record: still a valid pointer)
+        check(self._lib.adc_engine_dagger_mask_fetch(self._h, buf.ctypes.data))
+        return out
+
     @classmethod
     def im_config(cls, beta=0.0, vf_coef=1.0, w_max=20.0, ma_start=100.0, ma_rate=1e-8, train_log_std=True):
         """an adc_im_config: beta 0 is behaviour cloning (w = 1), beta > 0 MARWIL's exp(beta adv / c) capped at w_max (0: no cap);

@@ -864,6 +864,30 @@ int adc_engine_pg_pop_update_queued(adc_engine *e, int32_t epochs, adc_pg_stats 
  * been initialised (adc_engine_run_days' messages). */
 int adc_engine_teach_days(adc_engine *e, int teacher_policy, int32_t days, float budget);
 
+/* A DAGGER DAY (Ross, Gordon and Bagnell 2011; the law is csrc/adc_dagger.h) is a teacher day on which a per-env coin picks whose
+ * action the step consumes.  Both agents act on the same observation exactly as on a teacher day - the learner into the scratch,
+ * the teacher into the engine's action buffers - then one kernel writes the record's action (the teacher's {budget, bids}: the
+ * LABEL, in units of the box under the bounded act; logp +0), copies the teacher's action over the learner's in the scratch for
+ * the envs whose coin picks the teacher, and notes the coin in a mask; the step consumes the scratch.  The engine's action buffers
+ * are left holding the teacher's action: a ADC_POLICY_FIXED_ACTIONS teacher keeps labelling day after day, and
+ * adc_engine_get_actions after a DAgger day returns the label.  The coin of env e is word x of draw(agent key of e, 0, stage 23,
+ * 0, the agent's tick before the day's act) against round(beta * 2^32): beta = 1 is a teacher day bit for bit, beta = 0 the
+ * learner's own day with the teacher's label.  It adds no state and moves no other stream.
+ * A DAgger day counts as a teacher day (the policy-gradient calls and the SAC stores refuse the record, adc_engine_im_* accept it)
+ * and in a count of its own, cleared with the teacher days': adc_engine_td3_store refuses a record that holds one (the recorded
+ * action is not the one the step consumed), and so do adc_engine_im_advantages / _im_minibatch / _im_update under beta != 0
+ * (MARWIL's weight needs returns that follow the labelled action; the value loss under vf_coef stays allowed and fits the value
+ * network to the mixture's returns).  Dataset aggregation is the record itself: enable it with T = rounds x days and do not reset
+ * it between rounds - adc_engine_im_advantages / _im_update run over all days recorded so far.
+ * Refused as adc_engine_teach_days is, and: beta outside [0, 1] or NaN; ADC_POLICY_INTERPOLATION as the teacher (its update keys
+ * its points by the bid it returned, which on a learner-driven day is not the bid the outcomes came from).
+ * adc_engine_dagger_mask_fetch: out_tn [days recorded][N], 1 where the teacher's action was consumed (rows of plain teacher days
+ * read 1); refused (ADC_ESTATE) when the record holds a day the learner collected. */
+int adc_engine_dagger_days(adc_engine *e, int teacher_policy, int32_t days, float budget, float beta);
+int adc_engine_dagger_mask_fetch(adc_engine *e, uint8_t *out_tn);
+/* host twin (adc_shims.cpp) of the coin: 1 when the teacher's action is consumed */
+int adc_dagger_coin_host(uint64_t key, uint32_t tick, float beta);
+
 /* IMITATION is an add-on to a single-learner adc_engine_pg_init trainer: it shares its theta, Adam moments, lr, max_grad_norm and
  * minibatch_envs, so the cloned policy is the very theta adc_engine_pg_update goes on training, and the value network arrives
  * fitted to the teacher's returns.  adc_engine_im_advantages: the discounted returns of the teacher's rewards (GAE with lambda 1

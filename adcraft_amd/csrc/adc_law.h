@@ -1008,6 +1008,42 @@ ADC_HD bool fast_money_packs(int32_t V, int32_t bid_c, float mu, float sd, float
     return fv * r_max < kPackedMoneyLimit && fv * (float)(bid_c - 1) < kPackedMoneyLimit;
 }
 
+// money_to_cents without its upper clamp, for dollars < 1.0e7f - every revenue of a keyword-day that packs (fast_money_packs asks
+// revenue_dollars_max < 1.0e7f, and a conversion's revenue is at most that bound).  The largest float32 below 1.0e7f is 9 999 999; its
+// exact product with 100, 999 999 900, lies between the neighbouring float32s 999 999 872 and 999 999 936 (64 apart there), so the
+// rounded product is at most 999 999 936 < kMoneyMaxCents = 1.0e9f, an integer already, and the clamp of money_to_cents returns it
+// unchanged.  (Not for other inputs: the conversion of a float32 of 2^31 or more, or of a NaN, is undefined.)
+ADC_HD int32_t money_to_cents_unclamped(float dollars) { return (int32_t)__builtin_rintf(dollars * 100.0f); }
+// revenue_cents_tab for a law with revenue_dollars_max(mu, sd, norm_table_node(0)) < 1.0e7f: the same value
+ADC_HD int32_t revenue_cents_unclamped(uint32_t w, float mu, float sd, const NormTableEntry *tab)
+{
+    float x = fma32(sd, normal_tab(w, tab), mu);
+    x = x > 0.01f ? x : 0.01f;
+    return money_to_cents_unclamped(x);
+}
+// Whether a keyword's conversion test is `word < saturate_threshold(T)` alone: bernoulli32's second compare only acts for the
+// saturated threshold 0xFFFFFFFF, which stands for T = 2^32 (sctr = 1: every click converts, the word 2^32 - 1 included) and for
+// nothing else - below it saturate_threshold(T) = T and (uint64)w < T is w < (uint32)T.  (A NaN rate has T = 0 and would pass; it
+// is refused all the same, so that no law with a NaN anywhere is called plain.)
+ADC_HD bool fast_conversion_plain(float sctr) { return sctr == sctr && bernoulli_threshold(sctr) <= 0xFFFFFFFFull; }
+// A keyword-day is PLAIN when it packs and its conversion test is plain; a tile of plain keyword-days resolves a clicked win without
+// the revenue's upper clamp and without the second compare (kernel_fast.inc, stage B).
+ADC_HD bool fast_keyword_plain(int32_t V, int32_t bid_c, float mu, float sd, float z_max, float sctr)
+{
+    return fast_money_packs(V, bid_c, mu, sd, z_max) && fast_conversion_plain(sctr);
+}
+
+// ---- the tag of a queued clicked win (dense fast pass): auction << 11 | keyword-in-tile << 3 -------------------------------------
+// The keyword sits where its 8-byte accumulator's byte offset is (tag & kFastTagAccMask, one full-rate AND; the law records are at
+// twice that), the auction index above it (tag >> kFastTagAuctionShift, one shift): 256 keywords and auctions up to kVolumeMax fit.
+constexpr int kFastTagKeywordShift = 3, kFastTagAuctionShift = 11;
+constexpr uint32_t kFastTagAccMask = ((1u << kFastTagAuctionShift) - 1u) & ~((1u << kFastTagKeywordShift) - 1u);      // 0x7F8
+static_assert(((uint64_t)kVolumeMax << kFastTagAuctionShift) <= 0xFFFFFFFFull, "an auction index up to kVolumeMax must fit above the keyword");
+ADC_HD uint32_t fast_tag(uint32_t keyword_in_tile, uint32_t auction) { return (auction << kFastTagAuctionShift) | (keyword_in_tile << kFastTagKeywordShift); }
+ADC_HD uint32_t fast_tag_acc_offset(uint32_t tag) { return tag & kFastTagAccMask; }
+ADC_HD uint32_t fast_tag_keyword(uint32_t tag) { return fast_tag_acc_offset(tag) >> kFastTagKeywordShift; }
+ADC_HD uint32_t fast_tag_auction(uint32_t tag) { return tag >> kFastTagAuctionShift; }
+
 ADC_HD int32_t revenue_cents(uint32_t w, float mu, float sd)
 {
     float x = fma32(sd, normal_from_word(w), mu);

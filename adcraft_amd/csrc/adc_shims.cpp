@@ -469,6 +469,74 @@ ADC_EXPORT int adc_fast_money_packs_host(int64_t n, const int32_t *volume, const
     return ADC_OK;
 }
 
+// ---- plain keyword-days of k_step_implicit_fast (adc_law.h fast_keyword_plain), for tests/test_fast_plain_tiles_host.py -----------
+// For n keyword-days (volume, bid in dollars, revenue law, conversion rate): plain[i] = adc::fast_keyword_plain; t32[i] / T[i] = the
+// conversion threshold saturated to 32 bits / as it is (<= 2^32); rev_tab / rev_plain [i * n_words + j] = adc::revenue_cents_tab and
+// adc::revenue_cents_unclamped at words[j], written only where the law is plain (what the unclamped form is defined for), as are
+// rev_rmax2[2 i], [2 i + 1] = adc::money_to_cents and adc::money_to_cents_unclamped at the law's revenue bound in dollars;
+// conv_bad[i] = over the words 0, T - 1, T, 2^32 - 2, 2^32 - 1 and n_random words drawn with `seed`, how many times
+// `word < t32` differs from adc::bernoulli(word, T) (every law, plain or not).
+ADC_EXPORT int adc_fast_plain_tiles_host(int64_t n, const int32_t *volume, const float *bid, const float *rev_mean, const float *rev_std,
+                                         const float *sellside_ctr, const uint32_t *words, int32_t n_words, int32_t n_random, uint64_t seed,
+                                         uint8_t *plain, uint32_t *t32, uint64_t *T, int32_t *rev_tab, int32_t *rev_plain, int32_t *rev_rmax2,
+                                         int32_t *conv_bad)
+{
+    if (n < 0 || n_words < 0 || n_random < 0 || (n > 0 && (!volume || !bid || !rev_mean || !rev_std || !sellside_ctr || !plain || !t32 || !T || !rev_rmax2 || !conv_bad)) ||
+        (n_words > 0 && (!words || !rev_tab || !rev_plain)))
+        return ADC_EINVAL;
+    const HostNormTables *t = host_norm_tables();
+    const float z_max = t->node[0];
+    shim_parallel_for(n, [=](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const int32_t bc = (int32_t)adc::bid_to_cents(bid[i]);
+            const bool p = adc::fast_keyword_plain(volume[i], bc, rev_mean[i], rev_std[i], z_max, sellside_ctr[i]);
+            plain[i] = p ? 1 : 0;
+            const uint64_t Ti = adc::bernoulli_threshold(sellside_ctr[i]);
+            const uint32_t ti = adc::saturate_threshold(Ti);
+            T[i] = Ti;
+            t32[i] = ti;
+            if (p) {
+                for (int32_t j = 0; j < n_words; ++j) {
+                    rev_tab[i * n_words + j] = adc::revenue_cents_tab(words[j], rev_mean[i], rev_std[i], t->entry);
+                    rev_plain[i * n_words + j] = adc::revenue_cents_unclamped(words[j], rev_mean[i], rev_std[i], t->entry);
+                }
+                const float r = adc::revenue_dollars_max(rev_mean[i], rev_std[i], z_max);
+                rev_rmax2[2 * i] = adc::money_to_cents(r);
+                rev_rmax2[2 * i + 1] = adc::money_to_cents_unclamped(r);
+            }
+            const uint32_t fixed[5] = {0u, (uint32_t)(Ti - 1ull), (uint32_t)Ti, 0xFFFFFFFEu, 0xFFFFFFFFu};
+            uint64_t s = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);
+            int32_t bad = 0;
+            for (int32_t j = 0; j < 5 + n_random; ++j) {
+                uint32_t w;
+                if (j < 5) w = fixed[j];
+                else {                                  // splitmix64
+                    s += 0x9E3779B97F4A7C15ull;
+                    uint64_t z = s;
+                    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                    w = (uint32_t)((z ^ (z >> 31)) >> 16);
+                }
+                bad += (w < ti) != adc::bernoulli(w, Ti) ? 1 : 0;
+            }
+            conv_bad[i] = bad;
+        }
+    });
+    return ADC_OK;
+}
+// the queue tag of a clicked win (adc_law.h fast_tag) and what stage B reads back from it: out4 = {tag, accumulator byte offset,
+// keyword, auction}
+ADC_EXPORT int adc_fast_tag_host(uint32_t keyword_in_tile, uint32_t auction, uint32_t *out4)
+{
+    if (!out4 || keyword_in_tile >= (uint32_t)adc::kFastTileLanes || auction > (uint32_t)adc::kVolumeMax) return ADC_EINVAL;
+    const uint32_t tag = adc::fast_tag(keyword_in_tile, auction);
+    out4[0] = tag;
+    out4[1] = adc::fast_tag_acc_offset(tag);
+    out4[2] = adc::fast_tag_keyword(tag);
+    out4[3] = adc::fast_tag_auction(tag);
+    return ADC_OK;
+}
+
 // ---- the host twin of k_step_implicit_fast's phase-2 schedule (adc_fast_schedule.h: the helpers the kernel calls) ------------
 // For tile number tile_index (env x tiles-per-env + tile: it only rotates which wave takes which part of the items) of tile_kw
 // keywords with the given volumes: every (pass, wave, round, lane) slot the kernel issues, as rows of

@@ -49,6 +49,10 @@ constexpr int kVolMask = (1 << kVolBits) - 1;
 constexpr int kTailCallsMax = adc::kFastTailCallsMax * kFastBlock;
 static_assert(adc::kVolumeMax <= kVolMask && kTailCallsMax < (1 << (31 - kVolBits)), "volume and tail-call prefix share a word");
 static_assert(adc::kVolumeMax < (1 << kClkShift), "three counts of up to kVolumeMax must fit 21 bits each");
+// a queued clicked win's tag (adc_law.h fast_tag): the keyword's accumulator offset in bits 3..10, the auction index above them
+static_assert((kFastBlock - 1) * sizeof(unsigned long long) == adc::kFastTagAccMask && sizeof(unsigned long long) == 1u << adc::kFastTagKeywordShift,
+              "the tag's keyword field is the byte offset of a_cnt[keyword]");
+static_assert(((unsigned long long)adc::kVolumeMax << adc::kFastTagAuctionShift) <= 0xFFFFFFFFull, "every auction index of a day fits above the keyword");
 
 // (Keyword sets with few auctions per keyword - the engine's volume hint - go to k_step_implicit_sparse, kernel_sparse.inc; this
 // kernel still decides per tile: a tile that happens to be sparse is resolved auction by auction from the sampled competitor bid.)
@@ -57,13 +61,13 @@ struct FastShared {
     // one ds_write2st64_b32 on the slot's address, with no constant to add)
     union {
         struct {                                            // phase 2: per wave, entry e = {tag[e], word[e]}
-            unsigned int tag[kFastBlock / kWave][kQueueCap];    //   keyword-in-tile << 24 | auction index
+            unsigned int tag[kFastBlock / kWave][kQueueCap];    //   adc::fast_tag: auction index << 11 | keyword-in-tile << 3
             unsigned int word[kFastBlock / kWave][kQueueCap];   //   the auction word (DIRECT: the price)
         } queue;
         struct {                                            // phase 1 (before the queues are used)
             unsigned int volw[kFastBlock];                  // volume words of the tile's keywords
             int wave_tot[kFastBlock / kWave], wave_vol[kFastBlock / kWave], wave_live[kFastBlock / kWave];
-            int wave_wide[kFastBlock / kWave];             // 1: a keyword of the wave needs the cost and the revenue in accumulators of their own
+            int wave_wide[kFastBlock / kWave];             // 1: a keyword of the wave needs the cost and the revenue in accumulators of their own; 2: one converts at every click
         };
     };
     KwWin win[kFastBlock];
@@ -226,15 +230,23 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
         const int vsum = wave_sum_i32(V);
         const int live = (int)__popcll(__builtin_amdgcn_ballot_w64(V > 0));
         const bool wide = V > 0 && !adc::fast_money_packs(V, bid_c, mu, sd, sh.normtab[0]);      // (normtab[0]: the largest node)
-        const int any_wide = __builtin_amdgcn_ballot_w64(wide) != 0ull ? 1 : 0;
+        // and whether every conversion test of the tile is `word < threshold` alone (adc::fast_conversion_plain: no threshold of 2^32)
+        const bool always = V > 0 && !adc::fast_conversion_plain(sctr);
+        const int any_wide =(__builtin_amdgcn_ballot_w64(wide) != 0ull ? 1 : 0) | (__builtin_amdgcn_ballot_w64(always) != 0ull ? 2 : 0);
         if (lane == 0) { sh.wave_vol[wv] = vsum; sh.wave_live[wv] = live; sh.wave_wide[wv] = any_wide; }
     }
     __syncthreads();
     int tile_volume = 0, tile_live = 0, tile_wide = 0;
 #pragma unroll
     for (int i = 0; i < kFastBlock / kWave; ++i) { tile_volume += sh.wave_vol[i]; tile_live += sh.wave_live[i]; tile_wide |= sh.wave_wide[i]; }
-    // (tile-uniform, in an SGPR: all ones where the tile packs)
-    const unsigned int pack_mask = __builtin_amdgcn_readfirstlane(tile_wide) == 0 ? 0xFFFFFFFFu : 0u;
+    // (tile-uniform, in an SGPR: all ones where the tile packs.  One opaque word: as a known all-ones-or-zero value hipcc keeps it as
+    // a lane mask in an SGPR pair and tests it through vcc)
+    const int tile_flags = __builtin_amdgcn_readfirstlane(tile_wide);
+    unsigned int pack_mask = (tile_flags & 1) == 0 ? 0xFFFFFFFFu : 0u;
+    asm volatile("" : "+s"(pack_mask));
+    // a PLAIN tile packs and holds no keyword that converts at every click (adc::fast_keyword_plain for every live keyword): stage B
+    // then needs neither bernoulli32's second compare nor - like every tile that packs - the upper clamp of money_to_cents
+    const bool plain = tile_flags == 0;
     const bool dense = adc::fast_tile_dense(tile_volume, tile_live);               // (block-uniform)
     // work-item size: 16 auctions when the tile has plenty of them; 8 or 4 on sparse tiles, so that the items still
     // number about two per lane.  Results do not depend on it: every draw is addressed by (auction, keyword).
@@ -331,13 +343,19 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     static_assert(sizeof(sh.queue.tag) == 8 * 64 * sizeof(unsigned int), "a push writes the word at offset1:8 of ds_write2st64_b32");
     unsigned int qaddr = qbase;
 
+    // the low word of a clicked win's count operand (one click), in a register of its own through phase 2: stage B sets only the
+    // high word (the conversion) per batch, where the 64-bit constant was rebuilt with two v_mov_b64
+    unsigned int cnt_lo = 1u << kClkShift;
+    asm volatile("" : "+v"(cnt_lo));
     // direct: the entry carries the price (stage A had to sample it); otherwise the auction word
     auto resolve_click = [&](bool direct) {
         const uint2 ent = make_uint2(qtag[lane], qword[lane]);
-        const unsigned int uu = ent.x >> 24;
-        // the keyword's accumulators by one byte offset (left to itself, hipcc forms it as uu * 16 - uu * 8 from the law records' address)
-        unsigned int acc_off = uu * (unsigned int)sizeof(unsigned long long);
+        // the keyword's accumulators by one byte offset, which the tag holds as it is (one full-rate v_and_b32; opaque, or hipcc forms
+        // it again from the law records' address)
+        unsigned int acc_off = adc::fast_tag_acc_offset(ent.x);
         asm volatile("" : "+v"(acc_off));
+        [[maybe_unused]] const unsigned int uu = acc_off >> adc::kFastTagKeywordShift;
+        const unsigned int ent_j = adc::fast_tag_auction(ent.x);
         unsigned long long *const acc = (unsigned long long *)((char *)sh.a_cnt + acc_off);      // a_cnt[uu]; a_cost, a_rev follow at kFastBlock strides
         // the keyword's 16-byte law records by that offset added to itself (a full-rate add; uu * 16 from the tag's byte is a second
         // half-rate shift)
@@ -354,27 +372,41 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             price = (unsigned int)adc::competitor_cents_of_proven_win(vv, ka.loc, ka.scale, sh.logtab);
         }
         // (interval form: the draw starts from the keyword's half of round 1, kept in law_b by phase 1 - the same bits)
-        const adc::U4 w2 = direct ? adc::draw_folded(key, ent.x & 0x00FFFFFFu, adc::ST_CONV, kw_base + uu, tick_k1)
-                                  : adc::draw_kw_folded(key, ent.x & 0x00FFFFFFu, kb.conv, tick_k1);
-        const bool conv = adc::bernoulli32(w2.x, ka.t_conv);
-        unsigned long long cnt = 1ull << kClkShift;
+        const adc::U4 w2 = direct ? adc::draw_folded(key, ent_j, adc::ST_CONV, kw_base + uu, tick_k1)
+                                  : adc::draw_kw_folded(key, ent_j, kb.conv, tick_k1);
+        // adc::bernoulli32: its second compare (the saturated threshold that stands for 2^32) behind a scalar branch that a plain tile
+        // skips (the empty asm keeps it a branch: as a select it is the compare again)
+        bool conv = w2.x < ka.t_conv;
+        if (!plain) {
+            unsigned int t = ka.t_conv;
+            asm volatile("" : "+v"(t));
+            conv |= t == 0xFFFFFFFFu;
+        }
+        unsigned int cnt_hi = 0u;
         unsigned int rev_c = 0u;
         if (conv) {
             float x = adc::fma32(kb.sd, normal_tab_nodes(w2.y, sh.normtab), kb.mu);
             x = x > 0.01f ? x : 0.01f;
-            rev_c = (unsigned int)adc::money_to_cents(x);                                       // (>= 1 cent: no sign to extend)
-            if (pack_mask == 0u) atomicAdd(acc + 2 * kFastBlock, (unsigned long long)rev_c);    // a_rev[uu]: only a tile that does not pack
-            cnt |= 1ull << kConvShift;
+            // a_rev[uu], and the upper clamp of money_to_cents: only a tile that does not pack (its a_cost then takes no revenue).  In
+            // one that packs every revenue is below 1e7 dollars and the clamp is idle (adc::money_to_cents_unclamped); >= 1 cent: no
+            // sign to extend
+            if (pack_mask == 0u) { atomicAdd(acc + 2 * kFastBlock, (unsigned long long)(unsigned int)adc::money_to_cents(x)); x = 0.0f; }
+            rev_c = (unsigned int)adc::money_to_cents_unclamped(x);
+            cnt_hi = 1u << (kConvShift - 32);
         }
-        atomicAdd(acc, cnt);
+        // (both high words opaque: each is then written where its operand pair wants it, next to cnt_lo and to the price, with no
+        // 64-bit select or OR to build the pair)
+        asm volatile("" : "+v"(cnt_hi));
+        atomicAdd(acc, ((unsigned long long)cnt_hi << 32) | cnt_lo);
         // a_cost[uu]: the price, and in a tile that packs the revenue above it (neither half can carry: adc::fast_money_packs)
-        atomicAdd(acc + kFastBlock, (unsigned long long)price | ((unsigned long long)(rev_c & pack_mask) << 32));
+        asm volatile("" : "+v"(rev_c));
+        atomicAdd(acc + kFastBlock, (unsigned long long)price | ((unsigned long long)rev_c << 32));
         if constexpr (LISTS) { if (raw.emit) {
             // (block-uniform) the env's budget bound yesterday: list the clicked win for k_step_click_walk, by sub-timestep
             // (adc::cell_range inverted: the quotient estimated in float32 - exact operands below 2^24 - and fixed up)
             // sub-timesteps up to the row hint are listed completely (jcut), later ones only with the clicks that cost at most the
             // price hint
-            const int j = (int)(ent.x & 0x00FFFFFFu);
+            const int j = (int)ent_j;
             if (j < ls.jcut[uu] || price <= ls.price_cut) {
                 // the click's sub-timestep and index in its cell: adc::cell_range inverted, the quotient estimated in float32
                 // (exact operands below 2^24) and fixed up
@@ -403,9 +435,12 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             __builtin_amdgcn_wave_barrier();
             resolve_click(direct);
             // the entries behind the batch move down (a lane reads and writes only its own slots: no entry is overwritten
-            // before its lane has read it)
+            // before its lane has read it).  All 64 lanes copy, with no test of "lane < entries left": what the others bring down
+            // lands in free slots [qtail, 64), which are written by a push before anything reads them (a drain reads [0, 64) only
+            // once qtail >= 64, the last one only below qtail), and both slots are inside the wave's queue
             qaddr -= kBatchBytes;
-            if ((unsigned int)lane < (qaddr - qbase) / (unsigned int)sizeof(unsigned int)) { qtag[lane] = qtag[kWave + lane]; qword[lane] = qword[kWave + lane]; }
+            qtag[lane] = qtag[kWave + lane];
+            qword[lane] = qword[kWave + lane];
             FDBG_ADD(4, FDBG_T() - tb);
             FDBG_ADD(7, 1);
         }
@@ -426,7 +461,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     auto run_item = [&](auto tail_tag, int u, int j0, int n, int calls4) {
         constexpr bool TAIL = decltype(tail_tag)::value;
         const uint32_t kw = kw_base + (uint32_t)u;
-        const unsigned int tagj0 = ((unsigned int)u << 24) | (unsigned int)j0;
+        const unsigned int tagj0 = adc::fast_tag((unsigned int)u, (unsigned int)j0);
         // the item's first Philox call: j0 is a multiple of 4 on all three paths (full items, tail calls, the partial call -
         // adc_fast_schedule.h), which the compiler cannot see, so the calls of the item are j0 / 4, + 1, ...: one add per call,
         // where (j0 + i) >> 2 is an add and a shift
@@ -449,7 +484,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
                     bool nw = (word - iv.n_lo) < iv.n_w;                           // unclicked win
                     if (TAIL) { const bool active = i + h < n; cw = cw && active; nw = nw && active; }
                     add_lane_bit(imp, __builtin_amdgcn_ballot_w64(nw));            // (the clicked wins are counted in stage B: phase 3 adds them)
-                    push(__builtin_amdgcn_ballot_w64(cw), tagj0 + (unsigned int)(i + h), word);     // (the mask itself: __ballot() goes through an int)
+                    push(__builtin_amdgcn_ballot_w64(cw), tagj0 + ((unsigned int)(i + h) << adc::kFastTagAuctionShift), word);     // (the mask itself: __ballot() goes through an int)
                     drain(false);
                 }
             }
@@ -473,7 +508,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
                     bool win = adc::auction_wins(word, bid_c, comp);               // tie loses (helpers.py:167-170)
                     if (TAIL) win = win && i + h < n;
                     imp += (unsigned int)(win && !click_bit);
-                    push(__builtin_amdgcn_ballot_w64(win && click_bit), tagj0 + (unsigned int)(i + h), (unsigned int)comp);
+                    push(__builtin_amdgcn_ballot_w64(win && click_bit), tagj0 + ((unsigned int)(i + h) << adc::kFastTagAuctionShift), (unsigned int)comp);
                     drain(true);
                 }
             }

@@ -1681,6 +1681,19 @@ int adc_fast_dead_keywords_host(int64_t n, const float *bid_n, const float *cost
 int adc_fast_money_packs_host(int64_t n, const int32_t *volume_n, const float *bid_n, const float *rev_mean_n, const float *rev_std_n,
                               const uint32_t *words, int32_t n_words, uint8_t *packs_n, int32_t *bid_c_n, int64_t *r_max_n, int32_t *rev,
                               float *z_max_out);
+/* diagnostic: the keyword-days whose clicked wins that pass resolves without the revenue's upper clamp and with one compare for the
+ * conversion (adc_law.h fast_keyword_plain: it packs, and its conversion threshold is below 2^32), on the host.  plain_n = 1 where
+ * the predicate says so; t32_n / T_n = the conversion threshold saturated to 32 bits / as it is; rev_tab, rev_plain [n][n_words]
+ * (may be NULL with n_words 0; written for plain laws only) = adc::revenue_cents_tab and the unclamped form at each of `words`;
+ * rev_rmax2_n [n][2] (plain laws only) = money_to_cents and its unclamped form at the law's revenue bound in dollars; conv_bad_n =
+ * how often `word < t32` differs from the 64-bit test over the words 0, T - 1, T, 2^32 - 2, 2^32 - 1 and n_random drawn with `seed`. */
+int adc_fast_plain_tiles_host(int64_t n, const int32_t *volume_n, const float *bid_n, const float *rev_mean_n, const float *rev_std_n,
+                              const float *sellside_ctr_n, const uint32_t *words, int32_t n_words, int32_t n_random, uint64_t seed,
+                              uint8_t *plain_n, uint32_t *t32_n, uint64_t *T_n, int32_t *rev_tab, int32_t *rev_plain, int32_t *rev_rmax2_n,
+                              int32_t *conv_bad_n);
+/* diagnostic: the queue tag of a clicked win in that pass, out4 = {tag, byte offset of the keyword's accumulator, keyword, auction};
+ * keyword_in_tile < 256, auction <= 2^20 */
+int adc_fast_tag_host(uint32_t keyword_in_tile, uint32_t auction, uint32_t *out4);
 /* one keyword of the default constructor's keyword set, on the host: exactly what adc_engine_generate_explicit_keywords writes for
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */

@@ -310,6 +310,13 @@ def lib():
         "adc_engine_mlp_frames": ([vp, vp], C.c_int),
         "adc_engine_mlp_history_get": ([vp, vp, vp, vp], C.c_int),
         "adc_engine_mlp_history_set": ([vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_init_recurrent": ([vp, C.POINTER(MLPConfig), vp, i32], C.c_int),
+        "adc_engine_mlp_gru_width": ([vp, vp], C.c_int),
+        "adc_engine_mlp_set_gru": ([vp, vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_set_member_gru": ([vp, i32, vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_hidden_get": ([vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_hidden_set": ([vp, vp, vp, vp], C.c_int),
+        "adc_engine_mlp_hidden_forget": ([vp], C.c_int),
         "adc_engine_mlp_set_layer": ([vp, i32, i32, vp, vp], C.c_int),
         "adc_engine_mlp_set_norm": ([vp, vp, vp], C.c_int),
         "adc_engine_mlp_set_log_std": ([vp, vp], C.c_int),
@@ -556,6 +563,10 @@ def lib():
         "adc_mlp_stack_row_host": ([i32, i32, vp, vp, vp, vp, i32, i32, vp], C.c_int),
         "adc_mlp_act_host": ([C.POINTER(MLPConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
                               vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_gru_cell_host": ([i32, i32, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_mlp_act_recurrent_host": ([C.POINTER(MLPConfig), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.c_uint32, f32,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "adc_gru_state_host": ([i32, i32, vp, vp, vp, vp, vp], C.c_int),
         "adc_mlp_math_host": ([i32, f32], f32),
         "adc_mlp_math_sweep_host": ([i32, f32, f32, vp, vp], i64),
         "adc_mlp_agent_key_host": ([u64], u64),

@@ -7,7 +7,11 @@ sellside_conversions[K]` (D = 5K+2); the action is `[budget, bids...]` (A = K+1)
 free `log_std[A]`) or in 2A values, means then log-stds.
 
 With `frames=H` (1 to 8) the policy acts on the last H observations: its input is H such rows side by side, the newest first
-(D = H (5K+2)); the engine gathers the older ones from a per-env history on the device (csrc/adc_mlp.h, observation history)."""
+(D = H (5K+2)); the engine gathers the older ones from a per-env history on the device (csrc/adc_mlp.h, observation history).
+
+With `gru=(Wi, bi, Wh, bh)` the policy is recurrent: one GRU cell of width G (torch.nn.GRUCell's arithmetic) stands in front of
+the output layer, reads the trunk's last activation (the input row without a trunk) and the env's state, and the output layer
+reads the new state (csrc/adc_gru.h).  The state lives on the device, per env; the evolution strategy trains such a policy."""
 import ctypes as C
 
 import numpy as np
@@ -16,19 +20,37 @@ from .. import _ffi
 
 ACTIVATIONS = {"tanh": _ffi.MLP_TANH, "relu": _ffi.MLP_RELU}
 MAX_LAYERS, MAX_WIDTH, MAX_FRAMES = 4, 256, 8
+MAX_GRU_WIDTH = 256
 
 
-def _layers(pairs, what):
-    out = []
-    for w, b in pairs:
+def _layers(pairs, what, state_width=0):
+    """state_width: the last layer of a recurrent policy reads the cell's state, not the layer before it"""
+    pairs, out = list(pairs), []
+    for i, (w, b) in enumerate(pairs):
         w = np.ascontiguousarray(w, dtype=np.float32)
         b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
         if w.ndim != 2 or w.shape[1] != b.size:
             raise ValueError(f"{what}: a layer is (W [n_in, n_out], b [n_out])")
-        if out and out[-1][0].shape[1] != w.shape[0]:
+        if state_width and i + 1 == len(pairs):
+            if w.shape[0] != state_width:
+                raise ValueError(f"{what}: the output layer of a recurrent policy reads the cell's state ({state_width} inputs)")
+        elif out and out[-1][0].shape[1] != w.shape[0]:
             raise ValueError(f"{what}: layer inputs do not match the previous layer's outputs")
         out.append((w, b))
     return out
+
+
+def _gru(gru):
+    """(Wi [n_in, 3G], bi [3G], Wh [G, 3G], bh [3G]) as float32, input-major, gate order r | z | n"""
+    if len(gru) != 4:
+        raise ValueError("gru: (Wi [n_in, 3G], bi [3G], Wh [G, 3G], bh [3G])")
+    wi, bi, wh, bh = (np.ascontiguousarray(a, dtype=np.float32) for a in gru)
+    g = wh.shape[0] if wh.ndim == 2 else 0
+    if not 1 <= g <= MAX_GRU_WIDTH:
+        raise ValueError(f"gru: the cell's width is 1 to {MAX_GRU_WIDTH}")
+    if wi.ndim != 2 or wi.shape[1] != 3 * g or wh.shape != (g, 3 * g) or bi.shape != (3 * g,) or bh.shape != (3 * g,):
+        raise ValueError("gru: (Wi [n_in, 3G], bi [3G], Wh [G, 3G], bh [3G])")
+    return wi, bi, wh, bh
 
 
 class MLPPolicy:
@@ -38,14 +60,21 @@ class MLPPolicy:
     of observations the input row holds (D = H (5K+2); shift / scale cover all of it)."""
 
     def __init__(self, layers, activation="tanh", value_layers=(), log_std=None, shift=None, scale=None, log_std_clamp=None,
-                 bid_clip=None, deterministic=False, frames=1):
+                 bid_clip=None, deterministic=False, frames=1, gru=None):
         if activation not in ACTIVATIONS:
             raise ValueError(f"unknown activation {activation!r}: 'tanh' or 'relu'")
         self.activation = activation
         if int(frames) != frames or not 1 <= int(frames) <= MAX_FRAMES:
             raise ValueError(f"frames: 1 to {MAX_FRAMES}")
         self.frames = int(frames)
-        self.layers = _layers(layers, "policy network")
+        self.gru = None if gru is None else _gru(gru)
+        self.layers = _layers(layers, "policy network", self.gru_width)
+        if self.gru is not None:
+            if self.frames > 1:
+                raise ValueError("a recurrent policy together with the observation history (frames > 1) is not supported")
+            n_in = self.layers[-2][0].shape[1] if len(self.layers) > 1 else self.gru[0].shape[0]
+            if self.gru[0].shape[0] != n_in:
+                raise ValueError(f"gru: Wi reads {self.gru[0].shape[0]} inputs, the cell's input has {n_in}")
         if self.input_size % self.frames or (self.input_size // self.frames) % 5 != 2 or self.input_size // self.frames < 7:
             if self.frames > 1:
                 raise ValueError(f"the first layer reads {self.input_size} inputs: not frames = {self.frames} rows of 5K+2")
@@ -70,7 +99,8 @@ class MLPPolicy:
         self.bid_clip = None if bid_clip is None else float(bid_clip)
         self.deterministic = bool(deterministic)
 
-    input_size = property(lambda self: self.layers[0][0].shape[0])
+    gru_width = property(lambda self: 0 if self.gru is None else self.gru[2].shape[0])
+    input_size = property(lambda self: self.layers[0][0].shape[0] if self.gru is None or len(self.layers) > 1 else self.gru[0].shape[0])
     output_size = property(lambda self: self.layers[-1][0].shape[1])
     num_keywords = property(lambda self: (self.input_size // self.frames - 2) // 5)
 
@@ -78,18 +108,35 @@ class MLPPolicy:
         """what StepEngine.mlp_init fixes and mlp_set_weights must find again: every layer's shape, the head's free log_std,
         whether there is a normalisation"""
         return ([w.shape for w, _ in self.layers], [w.shape for w, _ in self.value_layers], self.log_std is not None,
-                self.shift is not None) + ((self.frames,) if self.frames > 1 else ())
+                self.shift is not None) + ((self.frames,) if self.frames > 1 else ()) + ((("gru",) + tuple(a.shape for a in self.gru),) if self.gru else ())
 
     @classmethod
     def from_arrays(cls, layers, **kw):
         return cls(layers, **kw)
 
     @classmethod
-    def from_torch(cls, module, value_module=None, **kw):
+    def from_torch(cls, module, value_module=None, cell=None, head=None, **kw):
         """a torch.nn.Sequential that is exactly Linear, act, Linear, act, ..., Linear with act = Tanh or ReLU (one kind for
         the policy and the value network): what the engine evaluates.  Any other structure - an activation after the last
-        Linear, two Linear in a row, a leading activation - is refused, not converted into a different function."""
+        Linear, two Linear in a row, a leading activation - is refused, not converted into a different function.
+
+        Recurrent: from_torch(trunk, cell=torch.nn.GRUCell, head=torch.nn.Linear).  `trunk` is None (the cell reads the input row)
+        or a Sequential Linear, act, ..., Linear, act - every trunk layer is followed by its activation; torch's [3G, n_in] gate
+        blocks (r | z | n rows) become the input-major [n_in, 3G] the engine holds."""
         import torch
+        if (cell is None) != (head is None):
+            raise ValueError("a recurrent policy is from_torch(trunk, cell=GRUCell, head=Linear): pass both cell and head")
+        if cell is not None:
+            if not isinstance(cell, torch.nn.GRUCell) or not isinstance(head, torch.nn.Linear):
+                raise ValueError(f"unsupported module {type(cell).__name__} / {type(head).__name__}: cell is a GRUCell, head a Linear")
+            if not cell.bias:
+                raise ValueError("the GRUCell must have biases (bias=True)")
+            t = lambda p: p.detach().cpu().numpy()
+            kw["gru"] = (t(cell.weight_ih).T.copy(), t(cell.bias_ih).copy(), t(cell.weight_hh).T.copy(), t(cell.bias_hh).copy())
+            trunk = [] if module is None else list(module)
+            if trunk and not isinstance(trunk[-1], (torch.nn.Tanh, torch.nn.ReLU)):
+                raise ValueError("policy network: a recurrent policy's trunk ends with the activation of its last Linear")
+            module = torch.nn.Sequential(*trunk, head)
 
         def unpack(seq, what):
             mods = list(seq)
@@ -137,6 +184,8 @@ class MLPPolicy:
         c.log_std_lo, c.log_std_hi = self.log_std_clamp or (0.0, 0.0)
         c.bid_clip_hi = self.bid_clip or 0.0
         c.deterministic = 1 if (self.deterministic if deterministic is None else deterministic) else 0
+        if self.gru is not None and self.layers[-1][0].shape[1] not in (int(num_keywords) + 1, 2 * (int(num_keywords) + 1)):
+            raise ValueError("the policy network ends in num_keywords + 1 outputs (means) or twice that (means, log-stds)")
         if self.input_size != self.frames * (5 * int(num_keywords) + 2):
             raise ValueError(f"the policy reads {self.input_size} inputs, the engine's observation has {5 * int(num_keywords) + 2}"
                              + (f" (times frames = {self.frames})" if self.frames > 1 else ""))

@@ -14,7 +14,7 @@ SRC_DIR = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libadcraft_hip.so")
 SOURCES = ["adc_engine.hip", "adc_shims.cpp"]
-HEADERS = ["adc_law.h", "adc_fast_schedule.h", "adc_interp.h", "adc_mlp.h", "adc_es.h", "adc_pg.h", "adc_pg_kl.h", "adc_pg_shuffle.h", "adc_imitation.h", "adc_dagger.h", "adc_td3.h", "adc_sac.h", "adc_pbt.h", "adc_norm.h", "adc_rew_norm.h", "adc_td3_norm.h", "adc_sac_norm.h", "adc_per.h", os.path.join(ROOT, "include", "adcraft_engine.h")] + sorted(
+HEADERS = ["adc_law.h", "adc_fast_schedule.h", "adc_interp.h", "adc_mlp.h", "adc_gru.h", "adc_es.h", "adc_pg.h", "adc_pg_kl.h", "adc_pg_shuffle.h", "adc_imitation.h", "adc_dagger.h", "adc_td3.h", "adc_sac.h", "adc_pbt.h", "adc_norm.h", "adc_rew_norm.h", "adc_td3_norm.h", "adc_sac_norm.h", "adc_per.h", os.path.join(ROOT, "include", "adcraft_engine.h")] + sorted(
     os.path.join("parts", f) for f in os.listdir(os.path.join(SRC_DIR, "parts")) if f.endswith(".inc"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",

@@ -47,6 +47,7 @@
 //   parts/kernel_interp_agent.inc the interpolation agent (NaiveInterpolationStrategy): its caches, update and act
 //        (k_interp_step); the per-keyword act itself is adc_interp.h, shared with the host twin.
 //   parts/kernel_mlp_policy.inc   the learned agent: a fully connected policy (and value) network per env, or per member of a population.
+//   parts/kernel_mlp_gru.inc      the recurrent learned agent: that policy with one GRU cell in front of its output layer, the state per env (adc_gru.h).
 //   parts/kernel_es.inc           policy populations and the evolution strategy: perturbation, returns, gradient estimate + Adam (adc_es.h).
 //   parts/kernel_pg.inc           policy-gradient training: GAE, the networks' backward pass, the weight gradient, the step (adc_pg.h);
 //        the k_pg_pop_* twins run the same bodies for all members of a learner population in one launch.
@@ -86,6 +87,7 @@
 //                                 agent's view and launch, a day of the agent, the parameter stores and the flat order against them,
 //                                 the shared entry checks, the layer upload - and the lifetime chain (who ends when what ends).
 //   parts/mlp_api.inc             the entry points of the learned agent: the single policy, populations, learners, squash and bounds.
+//   parts/gru_api.inc             the entry points of the recurrent policy: its init, the cell's upload, the state's get, set and forget.
 //   parts/es_api.inc              the entry points of the evolution strategy over a policy population.
 //   parts/rollout_api.inc         the entry points of the rollout record and of the day loop (adc_engine_run_days).
 //   parts/pg_core.inc             what the three policy-gradient host files share: the members (a single learner is one member), the
@@ -126,6 +128,7 @@
 #include "adc_fast_schedule.h"
 #include "adc_interp.h"
 #include "adc_mlp.h"
+#include "adc_gru.h"
 #include "adc_es.h"
 #include "adc_pg.h"
 #include "adc_pg_kl.h"
@@ -156,6 +159,7 @@ namespace adck {
 #include "parts/kernel_explicit_curves.inc"
 #include "parts/kernel_interp_agent.inc"
 #include "parts/kernel_mlp_policy.inc"
+#include "parts/kernel_mlp_gru.inc"
 #include "parts/kernel_es.inc"
 #include "parts/kernel_pg.inc"
 #include "parts/kernel_pg_kl.inc"
@@ -180,6 +184,7 @@ using namespace adck;
 #include "parts/selftest_api.inc"
 #include "parts/mlp_core.inc"
 #include "parts/mlp_api.inc"
+#include "parts/gru_api.inc"
 #include "parts/es_api.inc"
 #include "parts/rollout_api.inc"
 #include "parts/pg_core.inc"

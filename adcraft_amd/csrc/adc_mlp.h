@@ -72,6 +72,7 @@
 namespace adc {
 
 constexpr int kMlpMaxLayers = 4;
+constexpr int kMlpMaxTerms = kMlpMaxLayers + 2;    // the (W, b) pairs of a policy's flat order: its layers, and a recurrent policy's Wi and Wh (adc_gru.h)
 constexpr int kMlpMaxWidth = 256;          // widest hidden layer; the output layer may be as wide as 2 (K + 1)
 constexpr int kMlpChains = 8;
 constexpr int kMlpTanh = 0, kMlpRelu = 1;

@@ -16,6 +16,7 @@
 #include "adc_fast_schedule.h"
 #include "adc_interp.h"
 #include "adc_mlp.h"
+#include "adc_gru.h"
 #include "adc_es.h"
 #include "adc_pg.h"
 #include "adc_pg_kl.h"
@@ -748,6 +749,9 @@ std::vector<float> mlp_forward_host(const float *x0, int D, int layers, const in
     }
     return x;
 }
+void mlp_heads_host(const adc_mlp_config *cfg, int K, const std::vector<float> &o, float v, const float *log_std_a, const float *normals_a,
+                    uint64_t agent_key, uint32_t tick, float budget_override, float *mean_a, float *log_std_out_a, float *action_a, float *logp,
+                    float *value, float *bids_k, float *budget);
 }  // namespace
 
 ADC_EXPORT int adc_mlp_stack_row_host(int32_t num_keywords, int32_t frames, const float *frame0_d0, float *hist_hd0, int32_t *last, int32_t *from,
@@ -789,6 +793,18 @@ ADC_EXPORT int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords,
     float v = 0.0f;
     if (cfg->n_value_layers > 0) v = mlp_forward_host(x.data(), D, cfg->n_value_layers, cfg->value_widths, value_w, value_b, activation)[0];
     const std::vector<float> o = mlp_forward_host(x.data(), D, cfg->n_policy_layers, cfg->policy_widths, policy_w, policy_b, activation);
+    mlp_heads_host(cfg, K, o, v, log_std_a, normals_a, agent_key, tick, budget_override, mean_a, log_std_out_a, action_a, logp, value, bids_k, budget);
+    return ADC_OK;
+}
+
+namespace {
+// everything after the policy network's outputs o [P] (adc_mlp.h: heads, sample, log-probability, bids, budget); v: the value
+void mlp_heads_host(const adc_mlp_config *cfg, int K, const std::vector<float> &o, float v, const float *log_std_a, const float *normals_a,
+                    uint64_t agent_key, uint32_t tick, float budget_override, float *mean_a, float *log_std_out_a, float *action_a, float *logp,
+                    float *value, float *bids_k, float *budget)
+{
+    const int A = K + 1;
+    const bool two_heads = cfg->policy_widths[cfg->n_policy_layers - 1] == 2 * A;
     std::vector<float> term((size_t)A);
     for (int a = 0; a < A; ++a) {
         const float mean = o[(size_t)a];
@@ -811,6 +827,86 @@ ADC_EXPORT int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords,
     }
     if (logp) *logp = adc::mlp_logp_finish(adc::mlp_join8(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]), A);
     if (value) *value = v;
+}
+
+// one layer of the law without an activation: y = W x + b, weights [n_in][n_out] row-major
+std::vector<float> mlp_linear_host(const float *x, int n_in, int n_out, const float *w, const float *b)
+{
+    const int32_t widths[1] = {n_out};
+    const float *const ws[1] = {w}, *const bs[1] = {b};
+    return mlp_forward_host(x, n_in, 1, widths, ws, bs, adc::kMlpTanh);
+}
+// the cell (adc_gru.h) on x [n_in] and h [G]
+std::vector<float> gru_cell_host(int n_in, int G, const float *x, const float *h, const float *wi, const float *bi, const float *wh, const float *bh)
+{
+    const std::vector<float> gi = mlp_linear_host(x, n_in, 3 * G, wi, bi), gh = mlp_linear_host(h, G, 3 * G, wh, bh);
+    std::vector<float> out((size_t)G);
+    for (int g = 0; g < G; ++g)
+        out[(size_t)g] = adc::gru_unit(gi[(size_t)g], gh[(size_t)g], gi[(size_t)(G + g)], gh[(size_t)(G + g)], gi[(size_t)(2 * G + g)], gh[(size_t)(2 * G + g)], h[g]);
+    return out;
+}
+}  // namespace
+
+// ---- the recurrent policy on the host (adc_gru.h: the code parts/kernel_mlp_gru.inc runs) ------------------------------------------
+ADC_EXPORT int adc_gru_cell_host(int32_t n_in, int32_t gru_width, const float *x_in, const float *h_g, const float *wi_in_3g, const float *bi_3g,
+                                 const float *wh_g_3g, const float *bh_3g, float *h_out_g)
+{
+    if (n_in < 1 || gru_width < 1 || gru_width > adc::kGruMaxWidth || !x_in || !h_g || !wi_in_3g || !bi_3g || !wh_g_3g || !bh_3g || !h_out_g) return ADC_EINVAL;
+    const std::vector<float> out = gru_cell_host(n_in, gru_width, x_in, h_g, wi_in_3g, bi_3g, wh_g_3g, bh_3g);
+    std::copy(out.begin(), out.end(), h_out_g);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_mlp_act_recurrent_host(const adc_mlp_config *cfg, int32_t num_keywords, int32_t gru_width, const float *obs_d,
+                                          const float *const *policy_w, const float *const *policy_b, const float *wi_in_3g, const float *bi_3g,
+                                          const float *wh_g_3g, const float *bh_3g, const float *const *value_w, const float *const *value_b,
+                                          const float *shift_d, const float *scale_d, const float *log_std_a, const float *normals_a,
+                                          uint64_t agent_key, uint32_t tick, float budget_override, const float *h_in_g, float *mean_a,
+                                          float *log_std_out_a, float *action_a, float *logp, float *value, float *bids_k, float *budget,
+                                          float *h_out_g)
+{
+    if (adc_mlp_config_check(cfg, num_keywords, nullptr) != ADC_OK) return ADC_EINVAL;
+    const int K = num_keywords, A = K + 1, D = 5 * K + 2, G = gru_width, L = cfg->n_policy_layers;
+    const int P = cfg->policy_widths[L - 1];
+    if (G < 1 || G > adc::kGruMaxWidth) return ADC_EINVAL;
+    if (!policy_w || !policy_b || !wi_in_3g || !bi_3g || !wh_g_3g || !bh_3g || (cfg->n_value_layers > 0 && (!value_w || !value_b)) ||
+        (cfg->normalize && (!shift_d || !scale_d)) || (P != 2 * A && !log_std_a))
+        return ADC_EINVAL;
+    const int activation = cfg->activation == ADC_MLP_TANH ? adc::kMlpTanh : adc::kMlpRelu;
+    std::vector<float> x((size_t)D, 0.0f);
+    for (int j = 0; j < D; ++j) {
+        float xj = obs_d ? obs_d[j] : 0.0f;
+        if (cfg->normalize) xj = adc::mlp_normalize(xj, shift_d[j], scale_d[j]);
+        x[(size_t)j] = xj;
+    }
+    float v = 0.0f;
+    if (cfg->n_value_layers > 0) v = mlp_forward_host(x.data(), D, cfg->n_value_layers, cfg->value_widths, value_w, value_b, activation)[0];
+    // the trunk (the activation after each of its layers), the cell, the output layer on the new state
+    for (int l = 0; l + 1 < L; ++l) {
+        std::vector<float> y = mlp_linear_host(x.data(), (int)x.size(), cfg->policy_widths[l], policy_w[l], policy_b[l]);
+        for (float &t : y) t = adc::mlp_act(t, activation);
+        x.swap(y);
+    }
+    const std::vector<float> h0((size_t)G, 0.0f);
+    const std::vector<float> h1 = gru_cell_host((int)x.size(), G, x.data(), h_in_g ? h_in_g : h0.data(), wi_in_3g, bi_3g, wh_g_3g, bh_3g);
+    if (h_out_g) std::copy(h1.begin(), h1.end(), h_out_g);
+    const std::vector<float> o = mlp_linear_host(h1.data(), G, P, policy_w[L - 1], policy_b[L - 1]);
+    mlp_heads_host(cfg, K, o, v, log_std_a, normals_a, agent_key, tick, budget_override, mean_a, log_std_out_a, action_a, logp, value, bids_k, budget);
+    return ADC_OK;
+}
+
+ADC_EXPORT int adc_gru_state_host(int32_t gru_width, int32_t day, float *h_2g, int32_t *last, int32_t *from, float *h_in_g, const float *h_new_g)
+{
+    const int G = gru_width;
+    if (G < 1 || G > adc::kGruMaxWidth || day < 0 || !h_2g || !last || !from || !h_in_g) return ADC_EINVAL;
+    const int32_t fr = adc::mlp_hist_from(day, *last, *from);
+    const bool zeros = adc::gru_starts_from_zeros(day, fr);
+    for (int g = 0; g < G; ++g) h_in_g[g] = zeros ? 0.0f : h_2g[(size_t)adc::gru_read_slot(day) * (size_t)G + (size_t)g];
+    if (h_new_g) {
+        for (int g = 0; g < G; ++g) h_2g[(size_t)adc::gru_write_slot(day) * (size_t)G + (size_t)g] = h_new_g[g];
+        *last = day;
+        *from = fr;
+    }
     return ADC_OK;
 }
 

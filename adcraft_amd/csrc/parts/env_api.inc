@@ -126,6 +126,11 @@ ADC_EXPORT int adc_engine_reset(adc_engine *e, const uint8_t *env_mask, const ui
         hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, d_mask, e->mp.last);
         err = hipGetLastError();
     }
+    // (... and so does the state of a recurrent policy's cell)
+    if (err == hipSuccess && e->have_mlp && e->gv.G) {
+        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, d_mask, e->gv.last);
+        err = hipGetLastError();
+    }
     hipError_t err2 = hipStreamSynchronize(e->stream);
     HIP_TRY(err);
     HIP_TRY(err2);

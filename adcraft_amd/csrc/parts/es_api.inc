@@ -73,6 +73,10 @@ ADC_EXPORT int adc_engine_es_perturb(adc_engine *e)
                        const_cast<float *>(e->mp.pop), e->mp.pop_stride, e->pop_M, 1, e->es_key, (uint32_t)e->es_generation, e->es_cfg.sigma);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(e->es_return, 0, (size_t)e->v.N * 8, e->stream));
+    if (e->gv.G) {                      // (a cell's state was computed under other weights: every env starts its run anew)
+        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((e->v.N + 255) / 256)), dim3(256), 0, e->stream, e->v.N, nullptr, e->gv.last);
+        HIP_TRY(hipGetLastError());
+    }
     e->es_days = 0;
     e->es_accumulate = true;
     return ADC_OK;

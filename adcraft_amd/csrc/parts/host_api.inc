@@ -101,6 +101,8 @@ struct adc_engine {
     std::vector<float> mlp_bd_host;     // [2][A] the lo and hi they were formed from (empty: off)
     bool td3_bounded = false;           // adc_engine_td3_set_bounded / adc_engine_td3_pop_set_bounded: the learners' law is the bounded one
     std::vector<void *> mlp_allocs;     // weights, vectors and last-act arrays (re-allocated by every adc_engine_mlp_init)
+    MlpGruView gv{};                    // the recurrent policy's cell and state (adc_engine_mlp_init_recurrent; gv.G = 0: feed-forward); among mlp_allocs
+    bool gru_set = false;               // the cell uploaded since init (adc_engine_mlp_set_gru)
     // a population of policies (adc_engine_mlp_population) and the evolution strategy over it (adc_engine_es_init; parts/kernel_es.inc)
     ParamLayout pl{};                   // the flat parameter order of the policy network (set by adc_engine_mlp_init)
     float *mlp_flat = nullptr;          // [P] staging of one flat parameter vector

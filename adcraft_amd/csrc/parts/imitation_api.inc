@@ -106,6 +106,7 @@ int teach_enter(const adc_engine *e, int teacher_policy, int32_t days)
         teacher_policy != ADC_POLICY_INTERPOLATION)
         return fail(ADC_EINVAL, "unknown policy");
     if (int rc = mlp_ready(e)) return rc;
+    if (int rc = gru_refuses(e, "a teacher's or a DAgger day")) return rc;
     if (e->pop_M != 0) return fail(ADC_ESTATE, "teacher days with a population active are not supported (adc_engine_mlp_population(0) first)");
     if (e->lrn_M != 0) return fail(ADC_ESTATE, "teacher days with learners active are not supported (adc_engine_mlp_learners(0) first)");
     if (e->mp.sq_lo) return fail(ADC_ESTATE, "teacher days under a squashed action are not supported: the record would need the pre-squash action of the teacher");
@@ -267,6 +268,7 @@ ADC_EXPORT int adc_engine_im_init(adc_engine *e, const adc_im_config *cfg)
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     const char *why = nullptr;
     if (adc_im_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if (int rc = gru_refuses(e, "imitation learning")) return rc;
     if (e->have_pg_pop) return fail(ADC_ESTATE, "imitation is an add-on to a single-learner trainer: a learner population is alive (adc_engine_pg_init)");
     if (!e->have_pg) return fail(ADC_ESTATE, "imitation is an add-on to a single-learner PPO / A2C trainer: adc_engine_pg_init first");
     int rc;

@@ -7,18 +7,19 @@
 // 1024 of them.  k_es_perturb runs one such lane per (quad, pair) and writes both members of the pair; k_es_update regenerates
 // the noise instead of reading it back and adds each parameter's terms in ascending pair order (the law's summation order,
 // whatever the launch shape).  All stores are plain vector stores; nothing here is read by a step kernel.
+// (a "layer" here is a term of the flat order: a recurrent policy's Wi | bi and Wh | bh stand among them as two more, adc_gru.h)
 struct ParamLayout {
     int layers, P;                              // policy layers; flat length
-    int n_in[adc::kMlpMaxLayers], n_out[adc::kMlpMaxLayers];
-    int flat0[adc::kMlpMaxLayers];              // flat index of layer l's W[0][0] (its b[0] follows the weights)
-    uint32_t offW[adc::kMlpMaxLayers], offb[adc::kMlpMaxLayers];    // floats from a member's base to its layer l (multiples of 4)
+    int n_in[adc::kMlpMaxTerms], n_out[adc::kMlpMaxTerms];
+    int flat0[adc::kMlpMaxTerms];               // flat index of layer l's W[0][0] (its b[0] follows the weights)
+    uint32_t offW[adc::kMlpMaxTerms], offb[adc::kMlpMaxTerms];      // floats from a member's base to its layer l (multiples of 4)
     uint32_t stride;                            // floats of a member's block
 };
 
 // one policy's layers: the centre's own allocations, or a member's (base + offW / offb)
 struct ParamStore {
-    float *W[adc::kMlpMaxLayers];
-    float *b[adc::kMlpMaxLayers];
+    float *W[adc::kMlpMaxTerms];
+    float *b[adc::kMlpMaxTerms];
 };
 
 constexpr int kEsBlock = 256;

@@ -5,9 +5,22 @@
 // (part of the single translation unit adc_engine.hip)
 
 // ---- the single policy ---------------------------------------------------------------------------------------------------------------
+namespace {
+int mlp_init_core(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t frames, int32_t G);
+}
 ADC_EXPORT int adc_engine_mlp_init(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n) { return adc_engine_mlp_init_frames(e, cfg, seeds_n, 1); }
 
 ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t frames)
+{
+    return mlp_init_core(e, cfg, seeds_n, frames, 0);
+}
+
+namespace {
+// the init under adc_engine_mlp_init_frames (G = 0) and adc_engine_mlp_init_recurrent (frames = 1, G > 0: parts/gru_api.inc has checked G).
+// With a cell the policy's layers are the trunk and the output layer [G][P], the cell's two stores are the view's (MlpGruView), and
+// the flat order has two more terms - the trunk, Wi | bi, Wh | bh, the output layer (adc_gru.h) - which a population and the strategy
+// walk as they walk layers.
+int mlp_init_core(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t frames, int32_t G)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     const char *why = nullptr;
@@ -18,6 +31,8 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     if (mlp_lds_floats(D0, P) * sizeof(float) > 150u * 1024u) return fail(ADC_EINVAL, "num_keywords too large for the MLP policy (LDS)");
     if (mlp_lds_floats(D, P) * sizeof(float) > 150u * 1024u)
         return fail(ADC_EINVAL, "frames: the stacked input row is too large for the MLP policy (LDS); fewer frames fit");
+    if (G > 0 && mlp_gru_lds_floats(D, P, G) * sizeof(float) > 150u * 1024u)
+        return fail(ADC_EINVAL, "gru_width: the cell's state and gates do not fit beside the input row (LDS); a narrower cell fits");
     ENGINE_GUARD(e);
     population_drop(e);                 // (a population does not survive a re-initialisation, as the rollout record does not)
     learners_drop(e);
@@ -25,13 +40,15 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     td3_drop(e);
     mlp_free(e, e->mlp_allocs);
     e->have_mlp = false;
+    e->gv = MlpGruView{};
     MlpView p{};
     const size_t N = e->v.N;
     int rc;
-    auto net = [&](MlpNet &n, int layers, const int32_t *widths) {
+    auto net = [&](MlpNet &n, int layers, const int32_t *widths, int state_from = adc::kMlpMaxLayers, int state_width = 0) {
         n.layers = layers;
         int n_in = D;
         for (int l = 0; l < layers; ++l) {
+            if (l >= state_from) n_in = state_width;        // (Wh and the output layer of a recurrent policy read the state)
             float *w = nullptr, *b = nullptr;
             if ((rc = mlp_alloc(e, e->mlp_allocs, &w, adc::mlp_weight_count(n_in, widths[l]))) || (rc = mlp_alloc(e, e->mlp_allocs, &b, (size_t)widths[l])))
                 return rc;
@@ -40,7 +57,19 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
         }
         return (int)ADC_OK;
     };
-    if ((rc = net(p.pol, cfg->n_policy_layers, cfg->policy_widths)) || (rc = net(p.val, cfg->n_value_layers, cfg->value_widths))) return rc;
+    // (with a cell the output layer reads the state)
+    const int at = cfg->n_policy_layers - 1;
+    if ((rc = net(p.pol, cfg->n_policy_layers, cfg->policy_widths, G > 0 ? at : adc::kMlpMaxLayers, G))) return rc;
+    if ((rc = net(p.val, cfg->n_value_layers, cfg->value_widths))) return rc;
+    MlpGruView gv{};
+    if (G > 0) {
+        gv.G = G; gv.at = at; gv.n_in = at > 0 ? cfg->policy_widths[at - 1] : D;
+        float *wi = nullptr, *bi = nullptr, *wh = nullptr, *bh = nullptr;
+        if ((rc = mlp_alloc(e, e->mlp_allocs, &wi, adc::mlp_weight_count(gv.n_in, 3 * G))) || (rc = mlp_alloc(e, e->mlp_allocs, &bi, (size_t)3 * G)) ||
+            (rc = mlp_alloc(e, e->mlp_allocs, &wh, adc::mlp_weight_count(G, 3 * G))) || (rc = mlp_alloc(e, e->mlp_allocs, &bh, (size_t)3 * G)))
+            return rc;
+        gv.Wi = wi; gv.bi = bi; gv.Wh = wh; gv.bh = bh;
+    }
     float *shift = nullptr, *scale = nullptr, *log_std = nullptr;
     if (cfg->normalize) {
         if ((rc = mlp_alloc(e, e->mlp_allocs, &shift, (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &scale, (size_t)D))) return rc;
@@ -54,18 +83,28 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     p.deterministic = cfg->deterministic != 0;
     p.A = A; p.D = D; p.P = P;
     // the flat parameter order, and a member's block: its layers one after the other, each starting on a 16-byte boundary
+    // (its terms are the policy's layers; with a cell Wi and Wh stand in front of the output layer, adc_gru.h)
     ParamLayout pl{};
-    pl.layers = p.pol.layers;
+    pl.layers = p.pol.layers + (G > 0 ? 2 : 0);
+    for (int t = 0; t < pl.layers; ++t) {
+        const int l = G > 0 && t > at ? t - 2 : t;          // (the policy layer of a term that is one)
+        if (G > 0 && t == at) { pl.n_in[t] = gv.n_in; pl.n_out[t] = 3 * G; }
+        else if (G > 0 && t == at + 1) { pl.n_in[t] = G; pl.n_out[t] = 3 * G; }
+        else { pl.n_in[t] = p.pol.n_in[l]; pl.n_out[t] = p.pol.n_out[l]; }
+    }
     {
         size_t off = 0;
         int flat = 0;
         for (int l = 0; l < pl.layers; ++l) {
-            pl.n_in[l] = p.pol.n_in[l]; pl.n_out[l] = p.pol.n_out[l];
             pl.flat0[l] = flat;
             flat += pl.n_in[l] * pl.n_out[l] + pl.n_out[l];
             pl.offW[l] = (uint32_t)off; off += adc::mlp_weight_count(pl.n_in[l], pl.n_out[l]);
             pl.offb[l] = (uint32_t)off; off += ((size_t)pl.n_out[l] + 3u) & ~(size_t)3u;
-            p.pop_offW[l] = pl.offW[l]; p.pop_offb[l] = pl.offb[l];
+            if (G == 0 || l < at) { p.pop_offW[l] = pl.offW[l]; p.pop_offb[l] = pl.offb[l]; }
+        }
+        if (G > 0) {
+            gv.pop_Wi = pl.offW[at]; gv.pop_bi = pl.offb[at]; gv.pop_Wh = pl.offW[at + 1]; gv.pop_bh = pl.offb[at + 1];
+            gv.pop_Wo = pl.offW[at + 2]; gv.pop_bo = pl.offb[at + 2];
         }
         pl.P = flat;
         pl.stride = (uint32_t)off;
@@ -83,7 +122,12 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     if (frames > 1 && ((rc = mlp_alloc(e, e->mlp_allocs, &p.hist, N * (size_t)D)) || (rc = mlp_alloc(e, e->mlp_allocs, &p.last, N)) ||
                        (rc = mlp_alloc(e, e->mlp_allocs, &p.from, N))))
         return rc;
+    if (G > 0 && ((rc = mlp_alloc(e, e->mlp_allocs, &gv.h, N * 2u * (size_t)G)) || (rc = mlp_alloc(e, e->mlp_allocs, &gv.last, N)) ||
+                  (rc = mlp_alloc(e, e->mlp_allocs, &gv.from, N))))
+        return rc;
     e->mp = p;
+    e->gv = gv;
+    e->gru_set = false;
     e->mlp_cfg = *cfg;
     std::memset(e->mlp_layer_set, 0, sizeof(e->mlp_layer_set));
     e->mlp_norm_set = e->mlp_log_std_set = false;
@@ -101,6 +145,10 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
         hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, nullptr, e->mp.last);
         err = hipGetLastError();
     }
+    if (err == hipSuccess && e->gv.G) {             // ... and no cell has a state
+        hipLaunchKernelGGL(k_mlp_hist_forget, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, e->stream, (int)N, nullptr, e->gv.last);
+        err = hipGetLastError();
+    }
     const hipError_t err2 = hipStreamSynchronize(e->stream);
     (void)hipFree(d_seeds);
     HIP_TRY(err);
@@ -110,6 +158,7 @@ ADC_EXPORT int adc_engine_mlp_init_frames(adc_engine *e, const adc_mlp_config *c
     if (e->ro_T > 0) { mlp_free(e, e->ro_allocs); e->ro_T = e->ro_t = 0; e->ro_obs = nullptr; e->ro_teacher = e->ro_dagger = 0; e->dg_mask = nullptr; }
     return ADC_OK;
 }
+}  // namespace
 
 ADC_EXPORT int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out)
 {
@@ -178,6 +227,7 @@ namespace {
 int squash_set(adc_engine *e, bool learners, const float *lo_a, const float *hi_a)
 {
     if (int rc = mlp_have(e)) return rc;
+    if (int rc = gru_refuses(e, "the squashed action")) return rc;
     const bool lone = (lo_a == nullptr) != (hi_a == nullptr);
     if (lone && !learners) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (squash off)");
     if (learners) {
@@ -222,7 +272,8 @@ ADC_EXPORT int adc_engine_mlp_act(adc_engine *e, float budget_override, const fl
         err = hipMemcpyAsync(d_z, replay_normals_na, na * 4, hipMemcpyHostToDevice, e->stream);
     }
     if (err == hipSuccess) {
-        mlp_launch_kernel(e->v, e->mp, e->stream, 0, d_z, budget_override, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, nullptr);
+        mlp_launch_kernel(e->v, e->mp, e->stream, 0, d_z, budget_override, e->d_bids, e->d_budget, MlpRecordSlot{nullptr, nullptr, nullptr, nullptr}, nullptr,
+                          &e->gv);
         err = hipGetLastError();
     }
     const hipError_t e2 = hipStreamSynchronize(e->stream);
@@ -374,7 +425,8 @@ ADC_EXPORT int adc_engine_mlp_set_member_layer(adc_engine *e, int32_t member, in
 {
     if (int rc = mlp_have(e)) return rc;
     if (int rc = population_member_check(e, member)) return rc;
-    if (layer < 0 || layer >= e->pl.layers) return fail(ADC_EINVAL, "no such layer");
+    if (layer < 0 || layer >= e->mp.pol.layers) return fail(ADC_EINVAL, "no such layer");
+    layer = policy_term(e, layer);      // (a member's stores are the flat order's terms: a recurrent policy's output layer stands behind the cell's two)
     if (!weights_in_out || !bias_out) return fail(ADC_EINVAL, "weights or bias is NULL");
     ENGINE_GUARD(e);
     const ParamStore s = member_store(e, member);
@@ -410,6 +462,8 @@ ADC_EXPORT int adc_engine_mlp_get_member_params(adc_engine *e, int32_t member, f
 ADC_EXPORT int adc_engine_mlp_learners(adc_engine *e, int32_t members)
 {
     if (int rc = mlp_have(e)) return rc;
+    if (members > 0)
+        if (int rc = gru_refuses(e, "learners")) return rc;
     const int N = e->v.N, M = members;
     if (M < 0 || M > 65535) return fail(ADC_EINVAL, "members: 0 (off) to 65535");
     if (M > 0 && N % M != 0) return fail(ADC_EINVAL, "members must divide num_envs");
@@ -516,6 +570,7 @@ namespace {
 int bounds_set(adc_engine *e, bool learners, const float *lo_a, const float *hi_a)
 {
     if (int rc = mlp_have(e)) return rc;
+    if (int rc = gru_refuses(e, "the bounded act")) return rc;
     if ((lo_a == nullptr) != (hi_a == nullptr)) return fail(ADC_EINVAL, "lo and hi: both vectors, or both NULL (bounds off)");
     if (learners) {
         if (e->lrn_M == 0) return fail(ADC_ESTATE, "the learners' bounded act needs learners (adc_engine_mlp_learners)");

@@ -33,11 +33,33 @@ inline MlpView mlp_view_from(const adc_engine *e, size_t e0)
     if (p.hist) { p.hist += e0 * (size_t)p.D; p.last += e0; p.from += e0; }        // (an env's frames are D = frames * (5K+2) floats)
     return p;
 }
+// the recurrent policy's view of the env group that starts at env e0 (G = 0: the policy is feed-forward)
+inline MlpGruView gru_view_from(const adc_engine *e, size_t e0)
+{
+    MlpGruView g = e->gv;
+    if (g.G) { g.h += e0 * 2u * (size_t)g.G; g.last += e0; g.from += e0; }
+    return g;
+}
+// the term of the flat order that a policy layer is: with a cell the output layer stands behind Wi and Wh
+inline int policy_term(const adc_engine *e, int layer) { return e->gv.G && layer >= e->gv.at ? layer + 2 : layer; }
+// what a recurrent policy does not go together with (adc_gru.h): ADC_ESTATE with a sentence, the engine as it was
+inline int gru_refuses(const adc_engine *e, const char *what)
+{
+    if (!e->gv.G) return ADC_OK;
+    return fail(ADC_ESTATE, std::string(what) + " with a recurrent policy is not supported (adc_engine_mlp_init_recurrent: training it is the evolution strategy's)");
+}
 // the frames of the policy's input row (1 before adc_engine_mlp_init)
 inline int mlp_frames(const adc_engine *e) { return e->mp.frames > 1 ? e->mp.frames : 1; }
 void mlp_launch_kernel(const View &v, const MlpView &p, hipStream_t st, int mode, const float *replay_z, float budget_override, float *d_bids,
-                       float *d_budget, const MlpRecordSlot &rec, float *value_out)
+                       float *d_budget, const MlpRecordSlot &rec, float *value_out, const MlpGruView *gru = nullptr)
 {
+    // (the recurrent act is a kernel of its own, parts/kernel_mlp_gru.inc; the bootstrap value reads no state and is the kernels' below)
+    if (gru && gru->G && mode == 0) {
+        const size_t lds = mlp_gru_lds_floats(p.D, p.P, gru->G) * sizeof(float);
+        if (p.member) hipLaunchKernelGGL(k_mlp_policy_gru<1>, dim3((unsigned)v.N), dim3(kMlpBlock), lds, st, v, p, *gru, replay_z, budget_override, d_bids, d_budget, rec);
+        else hipLaunchKernelGGL(k_mlp_policy_gru<0>, dim3((unsigned)v.N), dim3(kMlpBlock), lds, st, v, p, *gru, replay_z, budget_override, d_bids, d_budget, rec);
+        return;
+    }
     // (three instantiations: without members the kernel is the single-policy code, untouched by the members' addressing; learners
     // have no pop_stride; the squashed forms are instantiations of their own, and so are the ones with an observation history)
     const dim3 grid((unsigned)v.N), block(kMlpBlock);
@@ -58,6 +80,7 @@ int mlp_ready(const adc_engine *e)
     if (!e->have_mlp) return fail(ADC_ESTATE, "adc_engine_mlp_init has not been called");
     for (int l = 0; l < e->mp.pol.layers; ++l)
         if (!e->mlp_layer_set[0][l]) return fail(ADC_ESTATE, "a policy layer has not been uploaded (adc_engine_mlp_set_layer)");
+    if (e->gv.G && !e->gru_set) return fail(ADC_ESTATE, "the cell has not been uploaded (adc_engine_mlp_set_gru)");
     for (int l = 0; l < e->mp.val.layers; ++l)
         if (!e->mlp_layer_set[1][l]) return fail(ADC_ESTATE, "a value layer has not been uploaded (adc_engine_mlp_set_layer)");
     if (e->mlp_cfg.normalize && !e->mlp_norm_set) return fail(ADC_ESTATE, "the normalisation vectors have not been uploaded (adc_engine_mlp_set_norm)");
@@ -85,7 +108,8 @@ int mlp_act_chained(adc_engine *e, float budget_override, bool record)
     const int t = e->ro_t;
     return launch_chained(e, [&](const View &v, const PolicyView &, hipStream_t st, float *d_bids, float *d_budget) {
         const size_t e0 = (size_t)(d_budget - e->d_budget);       // (the group's first env)
-        mlp_launch_kernel(v, mlp_view_from(e, e0), st, 0, nullptr, budget_override, d_bids, d_budget, rollout_slot(e, record, t, e0), nullptr);
+        const MlpGruView g = gru_view_from(e, e0);
+        mlp_launch_kernel(v, mlp_view_from(e, e0), st, 0, nullptr, budget_override, d_bids, d_budget, rollout_slot(e, record, t, e0), nullptr, &g);
     });
 }
 int mlp_record_outcome_chained(adc_engine *e)
@@ -127,7 +151,15 @@ inline unsigned es_quad_blocks(int P) { return (unsigned)(((P + 3) / 4 + kEsBloc
 ParamStore centre_store(const adc_engine *e)
 {
     ParamStore s{};
-    for (int l = 0; l < e->mp.pol.layers; ++l) { s.W[l] = const_cast<float *>(e->mp.pol.W[l]); s.b[l] = const_cast<float *>(e->mp.pol.b[l]); }
+    for (int l = 0; l < e->mp.pol.layers; ++l) {
+        const int t = policy_term(e, l);
+        s.W[t] = const_cast<float *>(e->mp.pol.W[l]); s.b[t] = const_cast<float *>(e->mp.pol.b[l]);
+    }
+    if (e->gv.G) {                      // (the cell's two terms, in front of the output layer)
+        const int at = e->gv.at;
+        s.W[at] = const_cast<float *>(e->gv.Wi); s.b[at] = const_cast<float *>(e->gv.bi);
+        s.W[at + 1] = const_cast<float *>(e->gv.Wh); s.b[at + 1] = const_cast<float *>(e->gv.bh);
+    }
     return s;
 }
 ParamStore member_store(const adc_engine *e, int member)

@@ -23,6 +23,7 @@ int pg_ready(const adc_engine *e, bool pop)
 int pg_state_check(const adc_engine *e, bool pop)
 {
     if (int rc = mlp_ready(e)) return rc;
+    if (int rc = gru_refuses(e, "policy-gradient training")) return rc;
     if (e->mp.bd_lo) return fail(ADC_ESTATE, "policy-gradient training under the bounded act is not supported: it needs a log-probability (adc_engine_mlp_set_bounds(NULL, NULL) first)");
     if (pop) {
         if (e->lrn_M == 0) return fail(ADC_ESTATE, "population training needs learners (adc_engine_mlp_learners)");

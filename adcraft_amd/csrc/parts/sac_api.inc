@@ -14,6 +14,7 @@ int sac_ready(const adc_engine *e)
 int sac_state_check(const adc_engine *e)
 {
     if (int rc = mlp_ready(e)) return rc;
+    if (int rc = gru_refuses(e, "soft actor-critic training")) return rc;
     if (e->mp.bd_lo) return fail(ADC_ESTATE, "soft actor-critic training under the bounded act is not supported: it needs a log-probability (adc_engine_mlp_set_bounds(NULL, NULL) first)");
     if (!e->mp.two_heads) return fail(ADC_ESTATE, "SAC needs the two-headed policy (2A outputs: means, log-stds): the free log_std head is not supported");
     if (!e->mp.clamp) return fail(ADC_ESTATE, "SAC needs clamp_log_std on: the log-std head is unbounded without it");

@@ -14,6 +14,7 @@ int td3_ready(const adc_engine *e)
 int td3_state_check(const adc_engine *e)
 {
     if (int rc = mlp_ready(e)) return rc;
+    if (int rc = gru_refuses(e, "off-policy training")) return rc;
     if (e->mp.two_heads) return fail(ADC_ESTATE, "TD3 needs the policy with the free log_std head: a two-headed policy (2A outputs) is not supported");
     if (e->pop_M != 0) return fail(ADC_ESTATE, "off-policy training with a population active is not supported (adc_engine_mlp_population(0) first)");
     if (e->lrn_M != 0) return fail(ADC_ESTATE, "off-policy training with learners active is not supported (adc_engine_mlp_learners(0) first)");

@@ -565,7 +565,9 @@ class StepEngine:
         cfg = policy.config(self.num_keywords, deterministic)
         sd = None if seeds is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.num_envs,)))
         frames = int(getattr(policy, "frames", 1))
-        if frames == 1:
+        if getattr(policy, "gru", None) is not None:
+            check(self._lib.adc_engine_mlp_init_recurrent(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data, policy.gru_width))
+        elif frames == 1:
             check(self._lib.adc_engine_mlp_init(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data))
         else:
             check(self._lib.adc_engine_mlp_init_frames(self._h, C.byref(cfg), None if sd is None else sd.ctypes.data, frames))
@@ -595,6 +597,8 @@ class StepEngine:
             raise ValueError(f"mlp_set_weights: the policy's shapes {policy.shapes()} are not those given to mlp_init "
                              f"{self._mlp.shapes()} (layers, value layers, free log_std, normalisation)")
         self._upload_layers(self._lib.adc_engine_mlp_set_layer, (((0,), policy.layers), ((1,), policy.value_layers)))
+        if getattr(policy, "gru", None) is not None:
+            check(self._lib.adc_engine_mlp_set_gru(self._h, *(a.ctypes.data for a in policy.gru)))
         if policy.shift is not None:
             check(self._lib.adc_engine_mlp_set_norm(self._h, policy.shift.ctypes.data, policy.scale.ctypes.data))
         if policy.log_std is not None:
@@ -721,6 +725,41 @@ class StepEngine:
             raise ValueError(f"mlp_set_history_state: hist [N, {h}, 5K+2], last and from [N] of a policy with frames = {h}")
         check(self._lib.adc_engine_mlp_history_set(self._h, hist.ctypes.data, last.ctypes.data, frm.ctypes.data))
 
+    # ---- the recurrent policy's state (parts/gru_api.inc; csrc/adc_gru.h) ----
+    def mlp_gru_width(self):
+        """the width G of the policy's GRU cell (MLPPolicy(gru=...)); 0: the policy is feed-forward"""
+        g = C.c_int32(0)
+        check(self._lib.adc_engine_mlp_gru_width(self._h, C.byref(g)))
+        return g.value
+
+    def mlp_hidden_state(self):
+        """the cell's state: dict(h float32 [N, 2, G] (slot = episode day & 1), last, from int32 [N]); None for a feed-forward policy"""
+        g = self.mlp_gru_width()
+        if g == 0:
+            return None
+        n = self.num_envs
+        st = {"h": np.zeros((n, 2, g), np.float32), "last": np.zeros(n, np.int32), "from": np.zeros(n, np.int32)}
+        check(self._lib.adc_engine_mlp_hidden_get(self._h, st["h"].ctypes.data, st["last"].ctypes.data, st["from"].ctypes.data))
+        return st
+
+    def mlp_set_hidden_state(self, state):
+        """restore what mlp_hidden_state returned (None: nothing to restore); a resumed run continues bit for bit"""
+        g = self.mlp_gru_width()
+        if state is None:
+            if g != 0:
+                raise ValueError("mlp_set_hidden_state: the policy is recurrent and the state holds no hidden state")
+            return
+        n = self.num_envs
+        h = np.ascontiguousarray(state["h"], dtype=np.float32)
+        last, frm = (np.ascontiguousarray(state[k], dtype=np.int32) for k in ("last", "from"))
+        if g == 0 or h.shape != (n, 2, g) or last.shape != (n,) or frm.shape != (n,):
+            raise ValueError(f"mlp_set_hidden_state: h [N, 2, {g}], last and from [N] of a policy with a cell of width {g}")
+        check(self._lib.adc_engine_mlp_hidden_set(self._h, h.ctypes.data, last.ctypes.data, frm.ctypes.data))
+
+    def mlp_hidden_forget(self):
+        """every env's next act starts from a zero state (es_perturb does this too)"""
+        check(self._lib.adc_engine_mlp_hidden_forget(self._h))
+
     def mlp_agent_state(self):
         """(keys uint64 [N], ticks uint32 [N]) of the agents' own streams; every act moves a tick on by one"""
         k, t = np.zeros(self.num_envs, np.uint64), np.zeros(self.num_envs, np.uint32)
@@ -749,7 +788,11 @@ class StepEngine:
         """the policy layers of `policy` (same shapes as at mlp_init) into one member"""
         if [w.shape for w, _ in policy.layers] != [w.shape for w, _ in self._mlp_policy().layers]:
             raise ValueError("mlp_set_member: the policy's layer shapes are not those given to mlp_init")
+        if [a.shape for a in (getattr(policy, "gru", None) or ())] != [a.shape for a in (getattr(self._mlp, "gru", None) or ())]:
+            raise ValueError("mlp_set_member: the policy's cell is not the shape of the one given to mlp_init")
         self._upload_layers(self._lib.adc_engine_mlp_set_member_layer, (((int(member),), policy.layers),))
+        if getattr(policy, "gru", None) is not None:
+            check(self._lib.adc_engine_mlp_set_member_gru(self._h, int(member), *(a.ctypes.data for a in policy.gru)))
 
     def mlp_param_count(self):
         n = C.c_int64(0)
@@ -757,7 +800,8 @@ class StepEngine:
         return n.value
 
     def mlp_params(self):
-        """the centre policy's parameters in the flat order (layers in order, W input-major then b)"""
+        """the centre policy's parameters in the flat order (layers in order, W input-major then b; a recurrent policy's cell -
+        Wi, bi, Wh, bh - stands in front of its output layer)"""
         flat = np.zeros(self.mlp_param_count(), np.float32)
         check(self._lib.adc_engine_mlp_get_params(self._h, flat.ctypes.data))
         return flat

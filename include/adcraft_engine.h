@@ -518,6 +518,40 @@ int adc_engine_mlp_frames(adc_engine *e, int32_t *frames);
  * them continues bit for bit.  ADC_ESTATE without a history (frames = 1). */
 int adc_engine_mlp_history_get(adc_engine *e, float *hist_nhd, int32_t *last_n, int32_t *from_n);
 int adc_engine_mlp_history_set(adc_engine *e, const float *hist_nhd, const int32_t *last_n, const int32_t *from_n);
+/* Recurrent policy: adc_engine_mlp_init with one GRU cell of width gru_width = G in 1..256 in front of the policy network's output
+ * layer (0: adc_engine_mlp_init itself, the same kernels and bits).  With n_policy_layers = L, layers 0 .. L-2 are the trunk as
+ * ever, the cell reads the trunk's last activation (the input row when L = 1) and the env's state h[G], and the output layer L-1
+ * has n_in = G and reads the new state; no activation follows the cell.  The cell is torch.nn.GRUCell's arithmetic, gates r, z, n
+ * (csrc/adc_gru.h states the law, every operation one correctly rounded float32 / float64 operation; adc_gru_cell_host and
+ * adc_mlp_act_recurrent_host give the same bits on the host).  Everything after the output layer - heads, sample, log-probability,
+ * bids, budget - and the feed-forward value network on the input row are adc_engine_mlp_init's.
+ * State: h[N][2][G] and two words per env, last and from, under the observation history's rule.  An act on episode day d starts
+ * from zeros on day 0, after an auto-reset, after days stepped without the agent and after an explicit reset (adc_engine_reset
+ * forgets the state of the envs it resets), else from the state the act of day d - 1 left; it writes the new state to slot d & 1,
+ * so a second act on the same day (replayed normals) reads the same input state and writes the same bits.  Not detected, as for
+ * the history: an auto-reset followed by exactly last + 1 days without an act.
+ * adc_engine_mlp_act, _step, adc_engine_run_days(ADC_POLICY_MLP), the rollout record, adc_engine_mlp_last and
+ * adc_engine_mlp_bootstrap_value work unchanged; adc_engine_mlp_set_layer(0, L-1, ...) is the output layer [G][P].
+ * The flat parameter order (adc_engine_mlp_param_count, _get_params, _get_member_params, the evolution strategy) is: the trunk
+ * layers, Wi input-major [n_in][3G], bi [3G], Wh [G][3G], bh [3G], the output layer.  adc_engine_mlp_population and adc_engine_es_*
+ * work over it; adc_engine_es_perturb also forgets every env's state (it was computed under other weights).
+ * Refused with ADC_EINVAL: gru_width outside 0..256; a cell whose state and gates do not fit the act's LDS.  Refused with ADC_ESTATE while the policy is recurrent, the engine staying usable:
+ * adc_engine_mlp_set_squash, _set_bounds, adc_engine_mlp_learners, adc_engine_pg_*, td3_*, sac_*, im_*, adc_engine_teach_days and
+ * adc_engine_dagger_days (training a recurrent policy is the evolution strategy's; an observation history, frames > 1, has no
+ * recurrent init). */
+int adc_engine_mlp_init_recurrent(adc_engine *e, const adc_mlp_config *cfg, const uint64_t *seeds_n, int32_t gru_width);
+int adc_engine_mlp_gru_width(adc_engine *e, int32_t *width);       /* 0: feed-forward */
+/* the cell, input-major as adc_engine_mlp_set_layer's weights: wi_in_3g [n_in][3G] (torch's weight_ih.T), bi_3g, wh_g_3g [G][3G]
+ * (weight_hh.T), bh_3g; columns in gate order r | z | n.  ADC_ESTATE when the policy is not recurrent.  _member_: into one member
+ * of a population. */
+int adc_engine_mlp_set_gru(adc_engine *e, const float *wi_in_3g, const float *bi_3g, const float *wh_g_3g, const float *bh_3g);
+int adc_engine_mlp_set_member_gru(adc_engine *e, int32_t member, const float *wi_in_3g, const float *bi_3g, const float *wh_g_3g,
+                                  const float *bh_3g);
+/* the state to the host and back: h_n2g [N][2][G], last_n / from_n [N] (any may be NULL); a run resumed from them continues bit
+ * for bit.  forget: last = -2 for every env, whose next act starts from zeros.  ADC_ESTATE when the policy is not recurrent. */
+int adc_engine_mlp_hidden_get(adc_engine *e, float *h_n2g, int32_t *last_n, int32_t *from_n);
+int adc_engine_mlp_hidden_set(adc_engine *e, const float *h_n2g, const int32_t *last_n, const int32_t *from_n);
+int adc_engine_mlp_hidden_forget(adc_engine *e);
 /* one Linear layer: network 0 = policy, 1 = value; weights_in_out is [n_in][n_out] row-major (input-major: torch's
  * weight.T), bias [n_out].  May be called again at any time between days (a trainer's update); nothing else changes. */
 int adc_engine_mlp_set_layer(adc_engine *e, int32_t network, int32_t layer, const float *weights_in_out, const float *bias_out);
@@ -1730,6 +1764,25 @@ int adc_mlp_act_host(const adc_mlp_config *cfg, int32_t num_keywords, const floa
  * move); zero: a peek (nothing is written).  ADC_EINVAL: frames outside 1..8, day < 0, a NULL history or row. */
 int adc_mlp_stack_row_host(int32_t num_keywords, int32_t frames, const float *frame0_d0, float *hist_hd0, int32_t *last, int32_t *from,
                            int32_t day, int32_t commit, float *row_d);
+/* the recurrent policy on the host: the same code as the device's (adc_gru.h).
+ * adc_gru_cell_host: one step of the cell, h_out_g = cell(x_in [n_in], h_g [G]) under wi_in_3g, bi_3g, wh_g_3g, bh_3g (input-major,
+ * gate order r | z | n).  ADC_EINVAL: n_in < 1, G outside 1..256, a NULL pointer.
+ * adc_mlp_act_recurrent_host: one env's act as adc_mlp_act_host, with the cell of width gru_width in front of the output layer:
+ * policy_w / policy_b hold the L layers (the last one [G][P]), h_in_g the input state (NULL: zeros), h_out_g (nullable) receives
+ * the new state.
+ * adc_gru_state_host: the state rule for one env.  h_2g [2][G], *last, *from: the env's state; h_in_g [G] receives the input state
+ * of an act on episode day `day`; h_new_g (NULL: a peek, nothing is written) is the new state that act commits: it goes to its
+ * slot, and *last and *from move.  ADC_EINVAL: G outside 1..256, day < 0, a NULL state or h_in_g. */
+int adc_gru_cell_host(int32_t n_in, int32_t gru_width, const float *x_in, const float *h_g, const float *wi_in_3g, const float *bi_3g,
+                      const float *wh_g_3g, const float *bh_3g, float *h_out_g);
+int adc_mlp_act_recurrent_host(const adc_mlp_config *cfg, int32_t num_keywords, int32_t gru_width, const float *obs_d,
+                               const float *const *policy_w, const float *const *policy_b, const float *wi_in_3g, const float *bi_3g,
+                               const float *wh_g_3g, const float *bh_3g, const float *const *value_w, const float *const *value_b,
+                               const float *shift_d, const float *scale_d, const float *log_std_a, const float *normals_a,
+                               uint64_t agent_key, uint32_t tick, float budget_override, const float *h_in_g, float *mean_a,
+                               float *log_std_out_a, float *action_a, float *logp, float *value, float *bids_k, float *budget,
+                               float *h_out_g);
+int adc_gru_state_host(int32_t gru_width, int32_t day, float *h_2g, int32_t *last, int32_t *from, float *h_in_g, const float *h_new_g);
 /* the evolution strategy on the host: the same code as the device's (adc_es.h).  `seed` is the effective seed (the
  * configuration's, or the engine's when that is 0).  noise: eps(pair, generation)[p0 .. p0 + n).  update: one generation's
  * shaping, gradient estimate and step on theta / m / v [n_params] in place from fitness_m[members]; `generation` is the one

@@ -14,17 +14,23 @@ SRC_DIR = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libadcraft_hip.so")
 SOURCES = ["adc_engine.hip", "adc_shims.cpp"]
-HEADERS = ["adc_law.h", "adc_fast_schedule.h", "adc_interp.h", "adc_mlp.h", "adc_gru.h", "adc_es.h", "adc_pg.h", "adc_pg_kl.h", "adc_pg_shuffle.h", "adc_imitation.h", "adc_dagger.h", "adc_td3.h", "adc_sac.h", "adc_pbt.h", "adc_norm.h", "adc_rew_norm.h", "adc_td3_norm.h", "adc_sac_norm.h", "adc_per.h", os.path.join(ROOT, "include", "adcraft_engine.h")] + sorted(
-    os.path.join("parts", f) for f in os.listdir(os.path.join(SRC_DIR, "parts")) if f.endswith(".inc"))
+PUBLIC_HEADER = os.path.join(ROOT, "include", "adcraft_engine.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
          "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt",
          "-Wall", "-Wno-unused-function"]
 
 
+def included_files():
+    """what the sources include, read from the tree: the law headers csrc/adc_*.h, the engine's parts csrc/parts/*.inc, the host
+    twins' parts csrc/shims/*.inc and the public header.  A new header or part is a dependency from the moment it exists"""
+    import glob
+    return sorted(glob.glob(os.path.join(SRC_DIR, "adc_*.h")) + glob.glob(os.path.join(SRC_DIR, "parts", "*.inc")) +
+                  glob.glob(os.path.join(SRC_DIR, "shims", "*.inc"))) + [PUBLIC_HEADER]
+
+
 def _deps():
-    out = [os.path.join(SRC_DIR, s) for s in SOURCES]
-    out += [h if os.path.isabs(h) else os.path.join(SRC_DIR, h) for h in HEADERS]
+    out = [os.path.join(SRC_DIR, s) for s in SOURCES] + included_files()
     return [p for p in out if os.path.exists(p)]
 
 

@@ -107,7 +107,10 @@
 //   parts/pbt_api.inc             the entry points of the population-based training scheduler over a PG, TD3 or SAC population.
 //   parts/per_api.inc             the entry points of prioritised replay over a TD3 or SAC trainer, and what the trainers' updates call of it.
 //   parts/nstep_api.inc           the entry points of n-step returns over a TD3 or SAC trainer (the store's window and the targets' gn are the kernels').
-//   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, the TD3 learners', the SAC learners' - over shared helpers.
+//   parts/norm_api.inc            the entry points of the running normalisers - observations, rewards, and the TD3 and SAC learners' as two
+//                                 families of one front end - over shared helpers.
+// The host-only exports - the `adcraft.rust` scalar shims, the host twins and the configuration checks - are the second source,
+// adc_shims.cpp, in parts of its own: shims/<subsystem>.inc, named after the parts/*_api.inc they twin.
 //
 // No CPU path exists in this library.
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // norm_api.inc - the extern "C" entry points of the running normalisers (include/adcraft_engine.h): the observation normaliser and
-// the reward normaliser of the PPO / A2C learners, the normalisers of the TD3 learners and those of the SAC learners, four thin front
-// ends - their own preconditions and config - over one set of helpers that work on a NormSet (host_api.inc).  The kernels are
+// the reward normaliser of the PPO / A2C learners, each a thin front end with its own preconditions and config, and the normalisers of
+// the TD3 learners and of the SAC learners, two families of a third; all over one set of helpers that work on a NormSet (host_api.inc).  The kernels are
 // parts/kernel_norm.inc, the laws csrc/adc_norm.h, adc_rew_norm.h, adc_td3_norm.h and adc_sac_norm.h.  Everything here runs on the engine's own stream behind ENGINE_GUARD,
 // that is after the env groups - whose streams write the record - have joined, as adc_engine_pg_advantages and adc_engine_td3_store do.
 // (part of the single translation unit adc_engine.hip)
@@ -212,8 +212,6 @@ constexpr const char *kOnNotReady =
     "adc_engine_obs_norm_init has not been called (or the policy, the learners or the record were re-initialised since)";
 constexpr const char *kRnNotReady =
     "adc_engine_rew_norm_init has not been called (or the trainer, the policy, the learners or the record were re-initialised since)";
-constexpr const char *kTnNotReady =
-    "adc_engine_td3_norm_init has not been called (or the TD3 trainer, the policy, the learners or the record were re-initialised since)";
 constexpr const char *kNoNewDay = "no day has been recorded since the last update or adc_engine_rollout_reset";
 }  // namespace
 
@@ -407,27 +405,62 @@ ADC_EXPORT int adc_engine_rew_norm_copy(adc_engine *e, const int32_t *src_of_m)
     return ADC_OK;
 }
 
-// ---- the running normalisers of the TD3 learners (the law is csrc/adc_td3_norm.h) ----------------------------------------------
-ADC_EXPORT int adc_engine_td3_norm_init(adc_engine *e, const adc_td3_norm_config *cfg)
+// ---- the running normalisers of the TD3 learners and of the SAC learners (the laws are csrc/adc_td3_norm.h, adc_sac_norm.h) ---------
+// Two families of one front end: each has its own NormSet, config and trainer, its entry points do not see the other's normaliser, and
+// the sentences name their own calls.  A family is described once (Td3NormFamily, SacNormFamily); ring_norm_* are the entry points over it.
+namespace {
+struct Td3NormFamily {
+    using Config = adc_td3_norm_config;
+    static NormSet &set(adc_engine *e) { return e->tn; }
+    static Config &cfg(adc_engine *e) { return e->tn_cfg; }
+    static int config_check(const Config *c, const char **why) { return adc_td3_norm_config_check(c, why); }
+    static bool solo(const adc_engine *e) { return e->have_td3; }
+    static bool pop(const adc_engine *e) { return e->have_td3_pop; }
+    static int state_check(const adc_engine *e) { return e->have_td3_pop ? tp_state_check(e) : td3_state_check(e); }
+    static float gamma(const adc_engine *e) { return e->td3_cfg.gamma; }
+    static constexpr const char *kNotReady =
+        "adc_engine_td3_norm_init has not been called (or the TD3 trainer, the policy, the learners or the record were re-initialised since)";
+    static constexpr const char *kNoTrainer = "the TD3 normalisers belong to an off-policy trainer: adc_engine_td3_init or adc_engine_td3_pop_init first";
+    static constexpr const char *kPerMember = "per-member normalisers need a TD3 learner population (adc_engine_td3_pop_init)";
+    static constexpr const char *kNotEmpty = "the record and the replay ring must be empty: their rows were written as network inputs (adc_engine_rollout_reset, and "
+                                             "adc_engine_td3_norm_init before the first store)";
+};
+struct SacNormFamily {
+    using Config = adc_sac_norm_config;
+    static NormSet &set(adc_engine *e) { return e->sn; }
+    static Config &cfg(adc_engine *e) { return e->sn_cfg; }
+    static int config_check(const Config *c, const char **why) { return adc_sac_norm_config_check(c, why); }
+    static bool solo(const adc_engine *e) { return e->have_sac; }
+    static bool pop(const adc_engine *e) { return e->have_sac_pop; }
+    static int state_check(const adc_engine *e) { return e->have_sac_pop ? sp_state_check(e) : sac_state_check(e); }
+    static float gamma(const adc_engine *e) { return e->sac_cfg.gamma; }
+    static constexpr const char *kNotReady =
+        "adc_engine_sac_norm_init has not been called over a live adc_engine_sac_init / adc_engine_sac_pop_init trainer (or the trainer, the policy, the "
+        "learners or the record were re-initialised since)";
+    static constexpr const char *kNoTrainer = "the SAC normalisers belong to a soft actor-critic trainer: adc_engine_sac_init or adc_engine_sac_pop_init first";
+    static constexpr const char *kPerMember = "per-member normalisers need a SAC learner population (adc_engine_sac_pop_init)";
+    static constexpr const char *kNotEmpty = "the record and the replay ring must be empty: their rows were written as network inputs (adc_engine_rollout_reset, and "
+                                             "adc_engine_sac_norm_init before the first store)";
+};
+
+template <class Family>
+int ring_norm_init(adc_engine *e, const typename Family::Config *cfg)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
     const char *why = nullptr;
-    if (adc_td3_norm_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
-    if (!e->have_td3 && !e->have_td3_pop)
-        return fail(ADC_ESTATE, "the TD3 normalisers belong to an off-policy trainer: adc_engine_td3_init or adc_engine_td3_pop_init first");
-    const bool pop = e->have_td3_pop, per_member = cfg->per_member != 0, obs = cfg->observations != 0, rew = cfg->rewards != 0;
-    if (int rc = pop ? tp_state_check(e) : td3_state_check(e)) return rc;
-    if (per_member && !pop) return fail(ADC_EINVAL, "per-member normalisers need a TD3 learner population (adc_engine_td3_pop_init)");
+    if (Family::config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
+    if (!Family::solo(e) && !Family::pop(e)) return fail(ADC_ESTATE, Family::kNoTrainer);
+    const bool pop = Family::pop(e), per_member = cfg->per_member != 0, obs = cfg->observations != 0, rew = cfg->rewards != 0;
+    if (int rc = Family::state_check(e)) return rc;
+    if (per_member && !pop) return fail(ADC_EINVAL, Family::kPerMember);
     if (obs && !e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
-    if (e->ro_t != 0 || e->td3_written != 0)
-        return fail(ADC_ESTATE, "the record and the replay ring must be empty: their rows were written as network inputs (adc_engine_rollout_reset, and "
-                                "adc_engine_td3_norm_init before the first store)");
+    if (e->ro_t != 0 || e->td3_written != 0) return fail(ADC_ESTATE, Family::kNotEmpty);
     NormSet s;
     s.M = per_member ? e->lrn_M : 1;
     const size_t chunks = (size_t)pg_chunks((long long)e->ro_T * (long long)(e->v.N / s.M));
     if (chunks > 65535) return fail(ADC_EINVAL, "days x envs of a normaliser: at most 65535 x 1024 samples in an update");
     ENGINE_GUARD(e);
-    norm_set_drop(e, e->tn);            // (a second init starts over from the policy's own vectors)
+    norm_set_drop(e, Family::set(e));            // (a second init starts over from the policy's own vectors)
     // (the chunk partials are sized for the whole record, as the reward part's scratch is)
     int rc = mlp_alloc(e, s.allocs, &s.src, (size_t)s.M);
     if (!rc && obs && !(rc = norm_alloc_obs(e, s, per_member))) rc = mlp_alloc(e, s.allocs, &s.obs_part, (size_t)s.M * chunks * 2u * (size_t)e->mp.D);
@@ -438,23 +471,26 @@ ADC_EXPORT int adc_engine_td3_norm_init(adc_engine *e, const adc_td3_norm_config
         return rc;
     }
     s.live = true;
-    e->tn = std::move(s);
-    e->tn_cfg = *cfg;
+    Family::set(e) = std::move(s);
+    Family::cfg(e) = *cfg;
     return ADC_OK;
 }
 
-ADC_EXPORT int adc_engine_td3_norm_update(adc_engine *e, int64_t *samples)
+template <class Family>
+int ring_norm_update(adc_engine *e, int64_t *samples)
 {
     if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    NormSet &s = e->tn;
-    if (int rc = norm_ready(s, kTnNotReady)) return rc;
+    NormSet &s = Family::set(e);
+    const typename Family::Config &c = Family::cfg(e);
+    if (int rc = norm_ready(s, Family::kNotReady)) return rc;
     if (e->ro_t <= s.t0) return fail(ADC_ESTATE, kNoNewDay);
     const NormBatch b = norm_batch(e, s);
     ENGINE_GUARD(e);
     int rc;
-    if (s.obs.count && (rc = norm_update_obs(e, s, b, adc::NormConfig{e->tn_cfg.obs_min_std, e->tn_cfg.obs_count_cap}, /* raw = */ true))) return rc;
-    const bool pop = e->have_td3_pop;
-    if (s.rew.count && (rc = norm_update_rew(e, s, b, adc::NormConfig{e->tn_cfg.rew_min_std, e->tn_cfg.rew_count_cap}, pop ? 0.0f : e->td3_cfg.gamma,
+    if (s.obs.count && (rc = norm_update_obs(e, s, b, adc::NormConfig{c.obs_min_std, c.obs_count_cap}, /* raw = */ true))) return rc;
+    // (the members of either family's population keep their discount in the TD3 population's table: Td3Member::law.gamma, sp_member_fill)
+    const bool pop = Family::pop(e);
+    if (s.rew.count && (rc = norm_update_rew(e, s, b, adc::NormConfig{c.rew_min_std, c.rew_count_cap}, pop ? 0.0f : Family::gamma(e),
                                              pop ? e->tp_dmem : (const Td3Member *)nullptr)))
         return rc;
     s.t0 = b.T;
@@ -462,176 +498,87 @@ ADC_EXPORT int adc_engine_td3_norm_update(adc_engine *e, int64_t *samples)
     return ADC_OK;
 }
 
+template <class Family>
+int ring_norm_state_get(adc_engine *e, int32_t member, int64_t *obs_count, double *obs_mean_d, double *obs_m2_d, float *shift_d, float *scale_d,
+                        int64_t *rew_count, double *rew_mean, double *rew_m2, float *rew_scale)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const NormSet &s = Family::set(e);
+    int rc;
+    if ((rc = norm_ready(s, Family::kNotReady)) || (rc = norm_member_check(s, member))) return rc;
+    if (!s.obs.count && (obs_count || obs_mean_d || obs_m2_d || shift_d || scale_d))
+        return fail(ADC_ESTATE, "the normaliser was initialised without observations");
+    if (!s.rew.count && (rew_count || rew_mean || rew_m2 || rew_scale)) return fail(ADC_ESTATE, "the normaliser was initialised without rewards");
+    ENGINE_GUARD(e);
+    if ((rc = norm_obs_get(e, s.obs, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d)) ||
+        (rc = norm_rew_get(e, s.rew, member, rew_count, rew_mean, rew_m2, rew_scale)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return ADC_OK;
+}
+
+template <class Family>
+int ring_norm_state_set(adc_engine *e, int32_t member, int64_t obs_count, const double *obs_mean_d, const double *obs_m2_d, const float *shift_d,
+                        const float *scale_d, int64_t rew_count, double rew_mean, double rew_m2, float rew_scale)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    const NormSet &s = Family::set(e);
+    int rc;
+    if ((rc = norm_ready(s, Family::kNotReady)) || (rc = norm_member_check(s, member))) return rc;
+    // (both parts are checked before either is written)
+    if (s.obs.count && (rc = norm_obs_check(s.obs, /* strict = */ true, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d))) return rc;
+    if (s.rew.count && (rc = norm_rew_check(/* strict = */ true, rew_count, rew_mean, rew_m2, rew_scale))) return rc;
+    ENGINE_GUARD(e);
+    if (s.obs.count && (rc = norm_obs_put(e, s.obs, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d))) return rc;
+    if (s.rew.count && (rc = norm_rew_put(e, s.rew, member, rew_count, rew_mean, rew_m2, rew_scale))) return rc;
+    return ADC_OK;
+}
+
+template <class Family>
+int ring_norm_returns(adc_engine *e, double *g_n, bool set)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = norm_ready(Family::set(e), Family::kNotReady)) return rc;
+    return norm_returns(e, Family::set(e), g_n, set);
+}
+
+template <class Family>
+int ring_norm_copy(adc_engine *e, const int32_t *src_of_member_m)
+{
+    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
+    if (int rc = norm_ready(Family::set(e), Family::kNotReady)) return rc;
+    return norm_copy(e, Family::set(e), Family::cfg(e).per_member != 0, src_of_member_m, "src_of_member_m");
+}
+}  // namespace
+
+ADC_EXPORT int adc_engine_td3_norm_init(adc_engine *e, const adc_td3_norm_config *cfg) { return ring_norm_init<Td3NormFamily>(e, cfg); }
+ADC_EXPORT int adc_engine_td3_norm_update(adc_engine *e, int64_t *samples) { return ring_norm_update<Td3NormFamily>(e, samples); }
 ADC_EXPORT int adc_engine_td3_norm_state_get(adc_engine *e, int32_t member, int64_t *obs_count, double *obs_mean_d, double *obs_m2_d, float *shift_d,
                                              float *scale_d, int64_t *rew_count, double *rew_mean, double *rew_m2, float *rew_scale)
 {
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const NormSet &s = e->tn;
-    int rc;
-    if ((rc = norm_ready(s, kTnNotReady)) || (rc = norm_member_check(s, member))) return rc;
-    if (!s.obs.count && (obs_count || obs_mean_d || obs_m2_d || shift_d || scale_d))
-        return fail(ADC_ESTATE, "the normaliser was initialised without observations");
-    if (!s.rew.count && (rew_count || rew_mean || rew_m2 || rew_scale)) return fail(ADC_ESTATE, "the normaliser was initialised without rewards");
-    ENGINE_GUARD(e);
-    if ((rc = norm_obs_get(e, s.obs, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d)) ||
-        (rc = norm_rew_get(e, s.rew, member, rew_count, rew_mean, rew_m2, rew_scale)))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return ring_norm_state_get<Td3NormFamily>(e, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d, rew_count, rew_mean, rew_m2, rew_scale);
 }
-
 ADC_EXPORT int adc_engine_td3_norm_state_set(adc_engine *e, int32_t member, int64_t obs_count, const double *obs_mean_d, const double *obs_m2_d,
                                              const float *shift_d, const float *scale_d, int64_t rew_count, double rew_mean, double rew_m2, float rew_scale)
 {
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const NormSet &s = e->tn;
-    int rc;
-    if ((rc = norm_ready(s, kTnNotReady)) || (rc = norm_member_check(s, member))) return rc;
-    // (both parts are checked before either is written)
-    if (s.obs.count && (rc = norm_obs_check(s.obs, /* strict = */ true, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d))) return rc;
-    if (s.rew.count && (rc = norm_rew_check(/* strict = */ true, rew_count, rew_mean, rew_m2, rew_scale))) return rc;
-    ENGINE_GUARD(e);
-    if (s.obs.count && (rc = norm_obs_put(e, s.obs, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d))) return rc;
-    if (s.rew.count && (rc = norm_rew_put(e, s.rew, member, rew_count, rew_mean, rew_m2, rew_scale))) return rc;
-    return ADC_OK;
+    return ring_norm_state_set<Td3NormFamily>(e, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d, rew_count, rew_mean, rew_m2, rew_scale);
 }
+ADC_EXPORT int adc_engine_td3_norm_returns_get(adc_engine *e, double *g_n) { return ring_norm_returns<Td3NormFamily>(e, g_n, /* set = */ false); }
+ADC_EXPORT int adc_engine_td3_norm_returns_set(adc_engine *e, const double *g_n) { return ring_norm_returns<Td3NormFamily>(e, const_cast<double *>(g_n), /* set = */ true); }
+ADC_EXPORT int adc_engine_td3_norm_copy(adc_engine *e, const int32_t *src_of_member_m) { return ring_norm_copy<Td3NormFamily>(e, src_of_member_m); }
 
-ADC_EXPORT int adc_engine_td3_norm_returns_get(adc_engine *e, double *g_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = norm_ready(e->tn, kTnNotReady)) return rc;
-    return norm_returns(e, e->tn, g_n, /* set = */ false);
-}
-
-ADC_EXPORT int adc_engine_td3_norm_returns_set(adc_engine *e, const double *g_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = norm_ready(e->tn, kTnNotReady)) return rc;
-    return norm_returns(e, e->tn, const_cast<double *>(g_n), /* set = */ true);
-}
-
-ADC_EXPORT int adc_engine_td3_norm_copy(adc_engine *e, const int32_t *src_of_member_m)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = norm_ready(e->tn, kTnNotReady)) return rc;
-    return norm_copy(e, e->tn, e->tn_cfg.per_member != 0, src_of_member_m, "src_of_member_m");
-}
-
-// ---- the running normalisers of the SAC learners (the law is csrc/adc_sac_norm.h) ----------------------------------------------
-// The fourth front end: its own preconditions, config and NormSet (e->sn) over the helpers above; a TD3 normaliser's entry points
-// do not see it, and these do not see a TD3 normaliser.
-namespace {
-constexpr const char *kSnNotReady =
-    "adc_engine_sac_norm_init has not been called over a live adc_engine_sac_init / adc_engine_sac_pop_init trainer (or the trainer, the policy, the "
-    "learners or the record were re-initialised since)";
-}  // namespace
-
-ADC_EXPORT int adc_engine_sac_norm_init(adc_engine *e, const adc_sac_norm_config *cfg)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const char *why = nullptr;
-    if (adc_sac_norm_config_check(cfg, &why) != ADC_OK) return fail(ADC_EINVAL, why);
-    if (!e->have_sac && !e->have_sac_pop)
-        return fail(ADC_ESTATE, "the SAC normalisers belong to a soft actor-critic trainer: adc_engine_sac_init or adc_engine_sac_pop_init first");
-    const bool pop = e->have_sac_pop, per_member = cfg->per_member != 0, obs = cfg->observations != 0, rew = cfg->rewards != 0;
-    if (int rc = pop ? sp_state_check(e) : sac_state_check(e)) return rc;
-    if (per_member && !pop) return fail(ADC_EINVAL, "per-member normalisers need a SAC learner population (adc_engine_sac_pop_init)");
-    if (obs && !e->mp.shift) return fail(ADC_EINVAL, "the policy was initialised without normalisation");
-    if (e->ro_t != 0 || e->td3_written != 0)
-        return fail(ADC_ESTATE, "the record and the replay ring must be empty: their rows were written as network inputs (adc_engine_rollout_reset, and "
-                                "adc_engine_sac_norm_init before the first store)");
-    NormSet s;
-    s.M = per_member ? e->lrn_M : 1;
-    const size_t chunks = (size_t)pg_chunks((long long)e->ro_T * (long long)(e->v.N / s.M));
-    if (chunks > 65535) return fail(ADC_EINVAL, "days x envs of a normaliser: at most 65535 x 1024 samples in an update");
-    ENGINE_GUARD(e);
-    norm_set_drop(e, e->sn);            // (a second init starts over from the policy's own vectors)
-    // (the chunk partials are sized for the whole record, as the reward part's scratch is)
-    int rc = mlp_alloc(e, s.allocs, &s.src, (size_t)s.M);
-    if (!rc && obs && !(rc = norm_alloc_obs(e, s, per_member))) rc = mlp_alloc(e, s.allocs, &s.obs_part, (size_t)s.M * chunks * 2u * (size_t)e->mp.D);
-    if (!rc && rew) rc = norm_alloc_rew(e, s);
-    if (!rc && obs) rc = norm_install_vectors(e, s, per_member);
-    if (rc) {
-        norm_set_drop(e, s);
-        return rc;
-    }
-    s.live = true;
-    e->sn = std::move(s);
-    e->sn_cfg = *cfg;
-    return ADC_OK;
-}
-
-ADC_EXPORT int adc_engine_sac_norm_update(adc_engine *e, int64_t *samples)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    NormSet &s = e->sn;
-    if (int rc = norm_ready(s, kSnNotReady)) return rc;
-    if (e->ro_t <= s.t0) return fail(ADC_ESTATE, kNoNewDay);
-    const NormBatch b = norm_batch(e, s);
-    ENGINE_GUARD(e);
-    int rc;
-    if (s.obs.count && (rc = norm_update_obs(e, s, b, adc::NormConfig{e->sn_cfg.obs_min_std, e->sn_cfg.obs_count_cap}, /* raw = */ true))) return rc;
-    // (a SAC population's members keep their discount in the TD3 population's table: Td3Member::law.gamma, sp_member_fill)
-    const bool pop = e->have_sac_pop;
-    if (s.rew.count && (rc = norm_update_rew(e, s, b, adc::NormConfig{e->sn_cfg.rew_min_std, e->sn_cfg.rew_count_cap}, pop ? 0.0f : e->sac_cfg.gamma,
-                                             pop ? e->tp_dmem : (const Td3Member *)nullptr)))
-        return rc;
-    s.t0 = b.T;
-    if (samples) *samples = b.S;
-    return ADC_OK;
-}
-
+ADC_EXPORT int adc_engine_sac_norm_init(adc_engine *e, const adc_sac_norm_config *cfg) { return ring_norm_init<SacNormFamily>(e, cfg); }
+ADC_EXPORT int adc_engine_sac_norm_update(adc_engine *e, int64_t *samples) { return ring_norm_update<SacNormFamily>(e, samples); }
 ADC_EXPORT int adc_engine_sac_norm_state_get(adc_engine *e, int32_t member, int64_t *obs_count, double *obs_mean_d, double *obs_m2_d, float *shift_d,
                                              float *scale_d, int64_t *rew_count, double *rew_mean, double *rew_m2, float *rew_scale)
 {
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const NormSet &s = e->sn;
-    int rc;
-    if ((rc = norm_ready(s, kSnNotReady)) || (rc = norm_member_check(s, member))) return rc;
-    if (!s.obs.count && (obs_count || obs_mean_d || obs_m2_d || shift_d || scale_d))
-        return fail(ADC_ESTATE, "the normaliser was initialised without observations");
-    if (!s.rew.count && (rew_count || rew_mean || rew_m2 || rew_scale)) return fail(ADC_ESTATE, "the normaliser was initialised without rewards");
-    ENGINE_GUARD(e);
-    if ((rc = norm_obs_get(e, s.obs, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d)) ||
-        (rc = norm_rew_get(e, s.rew, member, rew_count, rew_mean, rew_m2, rew_scale)))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return ADC_OK;
+    return ring_norm_state_get<SacNormFamily>(e, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d, rew_count, rew_mean, rew_m2, rew_scale);
 }
-
 ADC_EXPORT int adc_engine_sac_norm_state_set(adc_engine *e, int32_t member, int64_t obs_count, const double *obs_mean_d, const double *obs_m2_d,
                                              const float *shift_d, const float *scale_d, int64_t rew_count, double rew_mean, double rew_m2, float rew_scale)
 {
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    const NormSet &s = e->sn;
-    int rc;
-    if ((rc = norm_ready(s, kSnNotReady)) || (rc = norm_member_check(s, member))) return rc;
-    // (both parts are checked before either is written)
-    if (s.obs.count && (rc = norm_obs_check(s.obs, /* strict = */ true, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d))) return rc;
-    if (s.rew.count && (rc = norm_rew_check(/* strict = */ true, rew_count, rew_mean, rew_m2, rew_scale))) return rc;
-    ENGINE_GUARD(e);
-    if (s.obs.count && (rc = norm_obs_put(e, s.obs, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d))) return rc;
-    if (s.rew.count && (rc = norm_rew_put(e, s.rew, member, rew_count, rew_mean, rew_m2, rew_scale))) return rc;
-    return ADC_OK;
+    return ring_norm_state_set<SacNormFamily>(e, member, obs_count, obs_mean_d, obs_m2_d, shift_d, scale_d, rew_count, rew_mean, rew_m2, rew_scale);
 }
-
-ADC_EXPORT int adc_engine_sac_norm_returns_get(adc_engine *e, double *g_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = norm_ready(e->sn, kSnNotReady)) return rc;
-    return norm_returns(e, e->sn, g_n, /* set = */ false);
-}
-
-ADC_EXPORT int adc_engine_sac_norm_returns_set(adc_engine *e, const double *g_n)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = norm_ready(e->sn, kSnNotReady)) return rc;
-    return norm_returns(e, e->sn, const_cast<double *>(g_n), /* set = */ true);
-}
-
-ADC_EXPORT int adc_engine_sac_norm_copy(adc_engine *e, const int32_t *src_of_member_m)
-{
-    if (!e) return fail(ADC_EINVAL, "engine handle is NULL");
-    if (int rc = norm_ready(e->sn, kSnNotReady)) return rc;
-    return norm_copy(e, e->sn, e->sn_cfg.per_member != 0, src_of_member_m, "src_of_member_m");
-}
+ADC_EXPORT int adc_engine_sac_norm_returns_get(adc_engine *e, double *g_n) { return ring_norm_returns<SacNormFamily>(e, g_n, /* set = */ false); }
+ADC_EXPORT int adc_engine_sac_norm_returns_set(adc_engine *e, const double *g_n) { return ring_norm_returns<SacNormFamily>(e, const_cast<double *>(g_n), /* set = */ true); }
+ADC_EXPORT int adc_engine_sac_norm_copy(adc_engine *e, const int32_t *src_of_member_m) { return ring_norm_copy<SacNormFamily>(e, src_of_member_m); }

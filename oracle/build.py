@@ -57,8 +57,8 @@ SHIMS_SRC = os.path.join(os.path.dirname(HERE), "adcraft_amd", "csrc", "adc_shim
 
 
 def build_sanitized():
-    """oracle/_san/: the oracle (both variants), the stream battery and a HOST-ONLY g++ build of the product's scalar shims
-    (adcraft_amd/csrc/adc_shims.cpp + adc_law.h, otherwise only ever compiled by hipcc), all with -fsanitize=address,undefined and
+    """oracle/_san/: the oracle (both variants), the stream battery and a HOST-ONLY g++ build of the product's host twins
+    (adcraft_amd/csrc/adc_shims.cpp and its parts, otherwise only ever compiled by hipcc), all with -fsanitize=address,undefined and
     -fno-sanitize-recover.  Loaded instead of the plain builds when ADCRAFT_ORACLE_SANITIZE=1 (python must then run with
     LD_PRELOAD=$(gcc -print-file-name=libasan.so): tools/run_sanitized.sh)."""
     os.makedirs(SAN_DIR, exist_ok=True)
@@ -79,12 +79,16 @@ def build_sanitized():
 
 
 def build_shims_host(sanitize=False):
-    """adc_shims.cpp as plain host C++ (g++, no HIP): the scalar `adcraft.rust` entry points and the word-interval / bracket checkers
-    of adc_law.h, as a library of their own - proof that this file is host code, and the form the sanitizers can see"""
+    """adc_shims.cpp (its parts csrc/shims/*.inc over the law headers csrc/adc_*.h) as plain host C++ (g++, no HIP): the scalar
+    `adcraft.rust` entry points, every host twin and every configuration check as a library of their own - proof that this code is
+    host code, and the form the sanitizers can see.  Rebuilt when any file the library's own build depends on is newer"""
+    import glob
     out_dir = SAN_DIR if sanitize else os.path.join(HERE, "_host")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, "libadc_shims_host.so")
-    deps = [SHIMS_SRC, os.path.join(os.path.dirname(SHIMS_SRC), "adc_law.h")]
+    csrc = os.path.dirname(SHIMS_SRC)           # (adcraft_amd/build.py included_files(), restated: this file imports nothing of the product)
+    deps = [SHIMS_SRC, os.path.join(os.path.dirname(HERE), "include", "adcraft_engine.h")] + [
+        p for pattern in ("adc_*.h", os.path.join("parts", "*.inc"), os.path.join("shims", "*.inc")) for p in glob.glob(os.path.join(csrc, pattern))]
     if not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra",
                                "-Wno-unused-function", "-Wno-unknown-pragmas"] + (SAN_FLAGS if sanitize else ["-O2"]) + [SHIMS_SRC, "-o", out, "-lm"])

@@ -1,4 +1,4 @@
-"""adc_shims.cpp (+ adc_law.h) is plain host C++: compiled by g++ as a library of its own (oracle/build.py build_shims_host - the form
+"""adc_shims.cpp (its parts shims/*.inc over the law headers adc_*.h) is plain host C++: compiled by g++ as a library of its own (oracle/build.py build_shims_host - the form
 the sanitizers see, tools/run_sanitized.sh) it gives the same bits as the copy hipcc builds into libadcraft_hip.so."""
 import ctypes as C
 import os

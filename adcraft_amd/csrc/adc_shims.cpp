@@ -47,7 +47,7 @@ static inline int config_verdict(const char *msg, const char **message)
 
 #include "shims/rust_scalar.inc"   // sigmoid, clamp, threshold_sigmoid, sums, the (seed, counter) samplers
 #include "shims/law.inc"           // word-space win intervals, brackets, win bounds, offsets, dead keywords; the log table, the thread helper
-#include "shims/fast_pass.inc"     // the dense fast pass: folded draws, proven prices, money packs, plain tiles, the queue tag, the schedule
+#include "shims/fast_pass.inc"     // the dense fast pass: folded draws, proven prices, money packs, plain tiles, the queue tag, the schedule, the queue's protocol
 #include "shims/keywords.inc"      // the EXPLICIT keyword sample and its cached bid curve
 #include "shims/interp.inc"        // the interpolation agent's act
 #include "shims/mlp.inc"           // the MLP policy: config check, stacked row, the act and the recurrent act (GRU), squash, bounds, math sweeps

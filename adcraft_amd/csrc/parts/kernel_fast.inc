@@ -328,7 +328,8 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     // to a per-wave LDS queue; whenever 64 are waiting, all 64 lanes evaluate the price paid and draw the conversion /
     // revenue call together - full wavefronts instead of the lanes that happen to click.
     // The queue is linear, not a ring: entries sit at [0, qtail); a drain resolves [0, 64) and moves the 0..63 entries
-    // behind them down to [0, qtail - 64) (one read and one write per lane, per 64 clicked wins), so that a push is
+    // behind them down to [0, qtail - 64) (one read and one write per lane, per 64 clicked wins; the move comes first and the
+    // batch is resolved from registers, see drain), so that a push is
     // mbcnt_lo, mbcnt_hi and one address (qtail goes into its scalar base), plus the tag: no wrap mask, no head.
     // Tags and words are two arrays of 4-byte entries: consecutive slots, conflict-free, and no register pair to build (two
     // ds_write_b32 at an 8-byte stride are each a 2-way bank conflict - measured +19 % kernel time).
@@ -347,9 +348,9 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     // high word (the conversion) per batch, where the 64-bit constant was rebuilt with two v_mov_b64
     unsigned int cnt_lo = 1u << kClkShift;
     asm volatile("" : "+v"(cnt_lo));
+    // ent = the lane's queue entry {tag, word}, read by the caller (a drain has moved the queue down before it resolves)
     // direct: the entry carries the price (stage A had to sample it); otherwise the auction word
-    auto resolve_click = [&](bool direct) {
-        const uint2 ent = make_uint2(qtag[lane], qword[lane]);
+    auto resolve_click = [&](bool direct, const uint2 ent) {
         // the keyword's accumulators by one byte offset, which the tag holds as it is (one full-rate v_and_b32; opaque, or hipcc forms
         // it again from the law records' address)
         unsigned int acc_off = adc::fast_tag_acc_offset(ent.x);
@@ -433,14 +434,23 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
             [[maybe_unused]] const unsigned long long tb = FDBG_T();
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            resolve_click(direct);
-            // the entries behind the batch move down (a lane reads and writes only its own slots: no entry is overwritten
-            // before its lane has read it).  All 64 lanes copy, with no test of "lane < entries left": what the others bring down
-            // lands in free slots [qtail, 64), which are written by a push before anything reads them (a drain reads [0, 64) only
-            // once qtail >= 64, the last one only below qtail), and both slots are inside the wave's queue
+            // The move-down comes FIRST, the batch is resolved from registers after it: the batch [0, 64) is read, then the entries
+            // behind it, which are written to [0, 64), and only then stage B runs.  A wave's LDS operations complete in order, so
+            // a move-down after stage B returned its read - and let the wave go on to the next push - only once stage B's scattered
+            // 64-bit atomics had gone through the LDS pipe, which nothing needs to wait for; now no wait stands between the last
+            // atomic of a drain and the next push.
+            // Why it is safe: a lane reads slot `lane` before it writes it (program order, and one wave's LDS operations execute
+            // in order); the slots the other lanes write are not the ones this lane reads, [0, 64) having been read by all 64 lanes
+            // before the first write (the write needs what the second read returns) and [64, 128) not being written at all; no
+            // entry is overwritten before its lane has read it.  All 64 lanes copy, with no test of "lane < entries left": what
+            // the others bring down lands in free slots [qtail, 64), which are written by a push before anything reads them (a
+            // drain reads [0, 64) only once qtail >= 64, the last one only below qtail), and both slots are inside the wave's queue
+            const uint2 ent = make_uint2(qtag[lane], qword[lane]);
+            const unsigned int next_tag = qtag[kWave + lane], next_word = qword[kWave + lane];
+            qtag[lane] = next_tag;
+            qword[lane] = next_word;
             qaddr -= kBatchBytes;
-            qtag[lane] = qtag[kWave + lane];
-            qword[lane] = qword[kWave + lane];
+            resolve_click(direct, ent);
             FDBG_ADD(4, FDBG_T() - tb);
             FDBG_ADD(7, 1);
         }
@@ -564,7 +574,7 @@ __global__ __launch_bounds__(kFastBlock, 5) void k_step_implicit_fast(View v, co
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if ((unsigned int)lane < (qaddr - qbase) / (unsigned int)sizeof(unsigned int)) resolve_click(!dense);      // fewer than 64 left
+    if ((unsigned int)lane < (qaddr - qbase) / (unsigned int)sizeof(unsigned int)) resolve_click(!dense, make_uint2(qtag[lane], qword[lane]));      // fewer than 64 left: the last batch reads its own entries
     [[maybe_unused]] const unsigned long long t_p3 = FDBG_T();
     FDBG_ADD(3, t_p3 - t_p2);
     __syncthreads();

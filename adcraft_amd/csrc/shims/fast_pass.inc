@@ -1,5 +1,5 @@
 // fast_pass.inc (part of adc_shims.cpp) - what the dense fast pass (parts/kernel_fast.inc) hoists, proves or packs, on the host next to the routines it
-// replaces (adc_law.h, adc_fast_schedule.h): folded draws, proven prices, money packs, plain tiles, the queue tag, the schedule.
+// replaces (adc_law.h, adc_fast_schedule.h): folded draws, proven prices, money packs, plain tiles, the queue tag, the schedule, the queue's protocol.
 // ---- what the dense fast pass hoists out of its stages (adc_law.h), next to the routines it replaces there: for
 // tests/test_law_hoists_host.py ----------------------------------------------------------------------------------------------
 // n calls: plain4 = adc::draw, folded4 = adc::draw_folded, kw4 = adc::draw_kw_folded from the keyword's half (four words each)
@@ -266,4 +266,59 @@ ADC_EXPORT int64_t adc_fast_schedule_host(const int32_t *vol_k, int32_t tile_kw,
     if (totals2) { totals2[0] = issued; totals2[1] = needed; }
     if (info2) { info2[0] = chunk_shift; info2[1] = adc::fast_tile_dense(tile_volume, live) ? 1 : 0; }
     return rows;
+}
+
+// ---- the host twin of k_step_implicit_fast's per-wave queue of clicked wins (parts/kernel_fast.inc: push, drain), for
+// tests/test_fast_queue_order_host.py ---------------------------------------------------------------------------------------------
+// One wave's queue over a sequence of pushes, push p writing the lanes of masks[p] behind the entries that wait (entry = p << 6 |
+// lane; a slot no push has written holds 0xFFFFFFFF).  After every push, while 64 or more wait, a drain runs as the kernel's does, one
+// LDS instruction of the wave after the other, each over all 64 lanes: read the batch [0, 64) into registers, read the slots behind
+// it [64, 128), write those to [0, 64), take 64 off the fill, and only then resolve the batch from the registers.  What is left at the
+// end is one partial batch, resolved by the lanes below the fill.  write_first = 1 places the write before the batch read (the order
+// that is wrong: the test's counter-example).  entries (the first `cap`) = what the batches resolved, batch after batch, in lane
+// order; batches2 (the first `batch_cap` rows) = {entries that waited when the batch started, entries it resolved}; info3 (nullable)
+// = {batches, entries pushed, the largest fill}.  Returns the number of entries resolved, or a negative adc_status.
+ADC_EXPORT int64_t adc_fast_queue_host(const uint64_t *masks, int64_t n_masks, int32_t write_first, uint32_t *entries, int64_t cap, int32_t *batches2,
+                                       int64_t batch_cap, int64_t *info3)
+{
+    constexpr int WL = adc::kFastWaveLanes, kCap = 2 * adc::kFastWaveLanes;      // (kQueueCap of the kernel: <= 63 + 64 ever wait)
+    if (n_masks < 0 || n_masks >= (1ll << 26) || (n_masks > 0 && !masks) || write_first < 0 || write_first > 1 || cap < 0 || batch_cap < 0 ||
+        (cap > 0 && !entries) || (batch_cap > 0 && !batches2))
+        return ADC_EINVAL;
+    uint32_t q[kCap];
+    for (int i = 0; i < kCap; ++i) q[i] = 0xFFFFFFFFu;
+    int fill = 0, max_fill = 0;
+    int64_t resolved = 0, n_batches = 0, pushed = 0;
+    auto resolve = [&](const uint32_t *batch, int lanes, int waited) {        // (what resolve_click is handed: the entry, per lane)
+        for (int lane = 0; lane < lanes; ++lane, ++resolved)
+            if (resolved < cap) entries[resolved] = batch[lane];
+        if (n_batches < batch_cap) { batches2[2 * n_batches] = waited; batches2[2 * n_batches + 1] = lanes; }
+        n_batches += 1;
+    };
+    for (int64_t p = 0; p < n_masks; ++p) {
+        const uint64_t m = masks[p];
+        int rank = 0;
+        for (int lane = 0; lane < WL; ++lane)
+            if ((m >> lane) & 1ull) {
+                if (fill + rank >= kCap) return ADC_EINVAL;          // (cannot happen: fill <= 63 before a push)
+                q[fill + rank] = (uint32_t)(p << 6) | (uint32_t)lane;
+                rank += 1;
+            }
+        fill += rank;
+        pushed += rank;
+        max_fill = fill > max_fill ? fill : max_fill;
+        if (fill >= WL) {                                   // (checked after every push, as the kernel does: one drain brings it below 64)
+            uint32_t batch[WL], behind[WL];
+            const int waited = fill;
+            if (!write_first) for (int lane = 0; lane < WL; ++lane) batch[lane] = q[lane];
+            for (int lane = 0; lane < WL; ++lane) behind[lane] = q[WL + lane];
+            for (int lane = 0; lane < WL; ++lane) q[lane] = behind[lane];
+            if (write_first) for (int lane = 0; lane < WL; ++lane) batch[lane] = q[lane];
+            fill -= WL;
+            resolve(batch, WL, waited);
+        }
+    }
+    if (fill > 0) resolve(q, fill, fill);
+    if (info3) { info3[0] = n_batches; info3[1] = pushed; info3[2] = max_fill; }
+    return resolved;
 }

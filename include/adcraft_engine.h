@@ -1728,6 +1728,17 @@ int adc_fast_plain_tiles_host(int64_t n, const int32_t *volume_n, const float *b
 /* diagnostic: the queue tag of a clicked win in that pass, out4 = {tag, byte offset of the keyword's accumulator, keyword, auction};
  * keyword_in_tile < 256, auction <= 2^20 */
 int adc_fast_tag_host(uint32_t keyword_in_tile, uint32_t auction, uint32_t *out4);
+/* diagnostic: the protocol of that pass's per-wave queue of clicked wins, on the host, for one wave and a sequence of n_masks (< 2^26)
+ * pushes.  Push p writes the lanes of masks[p] behind the entries that wait, entry = p << 6 | lane (a slot no push has written holds
+ * 0xFFFFFFFF); whenever 64 or more wait after a push, a drain reads the batch [0, 64), reads the 64 slots behind it, writes those to
+ * [0, 64) with all 64 lanes, takes 64 off the fill and only then resolves the batch from what it read; what is left after the last
+ * push is one partial batch.  write_first = 1 runs the wrong order instead, the write ahead of the batch read (0 = the kernel's).
+ * entries = what the batches resolved, one batch after the other in lane order (the first `cap` are written; may be NULL with cap 0);
+ * batches2 [batches][2] = {entries that waited when the batch started, entries it resolved} (the first batch_cap rows; may be NULL
+ * with batch_cap 0); info3 (may be NULL) = {batches, entries pushed, the largest number that ever waited}.  Returns the number of
+ * entries resolved, or a negative adc_status. */
+int64_t adc_fast_queue_host(const uint64_t *masks, int64_t n_masks, int32_t write_first, uint32_t *entries, int64_t cap, int32_t *batches2,
+                            int64_t batch_cap, int64_t *info3);
 /* one keyword of the default constructor's keyword set, on the host: exactly what adc_engine_generate_explicit_keywords writes for
  * keyword `keyword` of an env whose Philox key is `key` (adc_engine_get_rng_state) - sample_random_keywords' law
  * (gymnasium_kw_utils.py:113-156); out8 in adc_param order */

@@ -23,6 +23,15 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 SEEDS = MIX_SEEDS
 assert len(SEEDS) == N0 and MIX_DAYS == T0
+# (N, K) of the record kernels' tests - k_teach_record, k_dagger_mix and their bounded forms run one lane per (env, component): the
+# module's shape, 36 lanes of one block; and 5 x 257 = 1285 lanes, six blocks with the last one partial, where the split i / A, i % A
+# runs across blocks, a = 256 reads the last bound, and an env group's pointer offsets fall inside a block's worth of lanes
+RECORD_SHAPES = [(N0, K0), (5, 256)]
+
+
+def _record_policy(rng, K, frames):
+    """the module's policy at its own shape; one head over hidden (31,) at the wide one"""
+    return _policy(rng, K, frames) if K == K0 else _policy(rng, K, frames, hidden=(31,))
 
 
 @pytest.fixture(scope="module")
@@ -138,17 +147,19 @@ def test_beta_zero_is_the_learners_day_with_the_teachers_label(amd, teacher, fra
 
 
 # ---- 3. beta = 0.5 ----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", RECORD_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 @pytest.mark.parametrize("bounded", [False, True])
-def test_a_mixed_day_follows_the_coin_env_by_env(amd, bounded):
-    N, K, T, frames, teacher = N0, K0, T0, 3, "fixed"
-    pol = _policy(np.random.default_rng(27), K, frames)
+def test_a_mixed_day_follows_the_coin_env_by_env(amd, bounded, shape):
+    (N, K), T, frames, teacher = shape, T0, 3, "fixed"
+    pol = _record_policy(np.random.default_rng(27), K, frames)
     bounds = TB.box(K) if bounded else None
-    m, tt, lt = (_learner(amd, pol, teacher, bounds=bounds) for _ in range(3))
+    m, tt, lt = (_learner(amd, pol, teacher, N=N, K=K, bounds=bounds) for _ in range(3))
     fixed = _label(m)
+    assert len(set(fixed[:, K].tolist())) > 1, "component a = K of the label was meant to differ between envs"
     keys, ticks = m.mlp_agent_state()
-    assert np.array_equal(keys, np.array([R.agent_key(s) for s in SEEDS], np.uint64)) and not ticks.any()
+    assert np.array_equal(keys, np.array([R.agent_key(s) for s in SEEDS[:N]], np.uint64)) and not ticks.any()
     want_mask = DR.mask(keys, ticks, T, MIX_BETA)
-    assert want_mask[0].tolist() == [0, 1, 1, 1, 0, 1]
+    assert want_mask[0].tolist() == [0, 1, 1, 1, 0, 1][:N]
     hist = S.History(N, K, frames)
     rows, values = [], []
     # the first day from identical states: an env follows the twin its coin names (envs are independent)
@@ -160,6 +171,7 @@ def test_a_mixed_day_follows_the_coin_env_by_env(amd, bounded):
     lt.run_days("mlp", 1, BUDGET)
     om, ot, ol = m.fetch(), tt.fetch(), lt.fetch()
     pick = want_mask[0].astype(bool)
+    assert pick.any() and not pick.all(), "the coin was meant to pick the teacher in some envs and the learner in others"
     differ = False
     for k in STEP_FIELDS:
         gm, gt, gl = np.asarray(om[k]), np.asarray(ot[k]), np.asarray(ol[k])
@@ -183,6 +195,7 @@ def test_a_mixed_day_follows_the_coin_env_by_env(amd, bounded):
     label = TB.unbox(fixed, *bounds) if bounded else fixed
     assert np.isfinite(label).all() and (not bounded or (np.abs(label) < 1).all()), "the fixed action was meant to lie inside the box"
     assert _same(rec["action"], np.stack([label] * T)), "every day's label is the fixed action (in box units under the bounds)"
+    assert len(set(label[:, K].tolist())) > 1, "component a = K of the recorded label was meant to differ between envs"
     assert _same(rec["logp"], np.zeros((T, N), F))
     assert _same(rec["obs"], np.stack(rows))
     assert _same(rec["value"], np.stack(values))
@@ -365,12 +378,14 @@ def test_the_trainer_aggregates_rounds_and_carries_its_state(amd):
 
 
 # ---- 6. chained days in env groups ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(8, K0), RECORD_SHAPES[1]], ids=lambda s: f"{s[0]}x{s[1]}")
 @pytest.mark.parametrize("teacher", ["zero_margin", "oracle"])
-def test_chained_days_in_env_groups_equal_days_one_call_at_a_time(amd, teacher):
+def test_chained_days_in_env_groups_equal_days_one_call_at_a_time(amd, teacher, shape):
     """8 envs in 4 forced groups (the count tests/test_gpu_obs_history.py groups at): the chain forks once and every kernel of a
-    DAgger day - both acts, k_dagger_mix, the step on the scratch, the outcome - runs group by group on the groups' streams"""
-    N, K, T, groups = 8, K0, T0, 4
-    pol = _policy(np.random.default_rng(57), K, 3)
+    DAgger day - both acts, k_dagger_mix, the step on the scratch, the outcome - runs group by group on the groups' streams.  At
+    5 x 256 the groups are the envs [0], [1], [2], [3, 4]: every group's pointers start inside a block's worth of lanes"""
+    (N, K), T, groups = shape, T0, 4
+    pol = _record_policy(np.random.default_rng(57), K, 3)
     out = []
     for chained in (True, False):
         e = _engine(amd, N, K, **RESETS)
@@ -392,7 +407,10 @@ def test_chained_days_in_env_groups_equal_days_one_call_at_a_time(amd, teacher):
         assert _same(ra[k], rb[k]), k
     keys = np.array([R.agent_key(s) for s in np.arange(N) + 11], np.uint64)
     assert _same(ma, mb) and _same(ma, DR.mask(keys, np.zeros(N, np.int64), T, MIX_BETA))
-    assert all(ma[:, g * 2:(g + 1) * 2].any() and not ma[:, g * 2:(g + 1) * 2].all() for g in range(groups)), "both branches in every group"
+    cut = [N * g // groups for g in range(groups + 1)]               # (a group's envs: [N g / G, N (g + 1) / G), 2 each at N = 8)
+    assert all(ma[:, cut[g]:cut[g + 1]].any() and not ma[:, cut[g]:cut[g + 1]].all() for g in range(groups)), "both branches in every group"
+    assert any(0 < row.sum() < N for row in ma), "the coin was meant to pick the teacher in some envs and the learner in others"
+    assert len(set(la[:, K].tolist())) > 1, "component a = K of the label was meant to differ between envs"
     for k in STEP_FIELDS:
         assert _same(oa[k], ob[k]), k
     assert all(np.array_equal(x, y) for x, y in zip(sa, sb)) and _same(la, lb)

@@ -75,6 +75,15 @@ def _teacher_ready(e, teacher, seeds):
         e.bid_curves_build(256)
     elif teacher == "fixed":
         e.sample_actions(0.3, 1.0, 40.0)
+    elif teacher == "interpolation":
+        e.interp_init(seeds=seeds)
+
+
+def _interp_same(a, b, what=""):
+    """the interpolation agent's own state - caches, last bids, beliefs, interpolation points - of two engines"""
+    for sa, sb in ((a.interp_state(), b.interp_state()), (a.interp_entries(), b.interp_entries())):
+        for k in sa:
+            assert _same(np.asarray(sa[k]), np.asarray(sb[k])), (what, k)
 
 
 def _now(e):
@@ -103,7 +112,7 @@ def _assert_stats(got, ref, what=""):
 
 # ---- 1. the teacher record -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("frames", [1, 3])
-@pytest.mark.parametrize("teacher", ["fixed", "zero_margin", "oracle"])
+@pytest.mark.parametrize("teacher", ["fixed", "zero_margin", "oracle", "interpolation"])
 def test_the_teacher_record_and_the_env_equal_run_days(amd, teacher, frames):
     N, K, T = N0, K0, T0
     rng = np.random.default_rng(7 + frames)
@@ -131,6 +140,8 @@ def test_the_teacher_record_and_the_env_equal_run_days(amd, teacher, frames):
         assert _same(abids, bids) and _same(abudget, budget), "the learner's act reached the engine's action buffers"
         actions.append(np.concatenate([np.asarray(budget, F).reshape(N, 1), np.asarray(bids, F).reshape(N, K)], axis=1))
         assert all(np.array_equal(x, y) for x, y in zip(a.get_rng_state(), b.get_rng_state())), t
+        if teacher == "interpolation":
+            _interp_same(a, b, t)
     rec = a.rollout_fetch()
     assert rec["reward"].shape == (T, N)
     done = rec["terminated"] | rec["truncated"]
@@ -151,6 +162,9 @@ def test_the_teacher_record_and_the_env_equal_run_days(amd, teacher, frames):
         assert _same(rec[k], rc[k]), k
     for k in STEP_FIELDS:
         assert _same(a.fetch()[k], c.fetch()[k]), k
+    if teacher == "interpolation":
+        _interp_same(c, b, "the days in one call")
+        assert c.interp_entries()["n_clicks"].max() > 0, "the interpolation agent was meant to learn from its days"
     with pytest.raises(ValueError, match="overflow"):
         a.teach_days(teacher, 1, BUDGET)
     for e in (a, b, c):

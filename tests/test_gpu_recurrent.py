@@ -122,11 +122,14 @@ def _assert_last(e, ref, what=""):
 
 
 # (N, K, trunk, G): D = 17 with a trunk; D = 37 without one, Wh a block of 32 and a tail, 3G = 99 gate rows; the LDS maximum; the
-# deepest trunk there is (the flat order's six terms), the cell's input in the second activation buffer
-SHAPES = [(8, 3, (5,), 3), (4, 7, (), 33), (2, 2, (256,), 256), (4, 3, (6, 7, 5), 4)]
+# deepest trunk there is (the flat order's six terms), the cell's input in the second activation buffer; A = 257 > 256, where the
+# head loop makes a second pass: two heads (514 outputs) with a value network next to them, and no trunk with a free log_std, where
+# Wi reads the input row of 1282 floats (40 blocks of 32 and a tail of 2)
+SHAPES = [(8, 3, (5,), 3), (4, 7, (), 33), (2, 2, (256,), 256), (4, 3, (6, 7, 5), 4), (2, 256, (31,), 33), (2, 256, (), 5)]
+VALUE_TOO = (4,)                                                       # (the shapes whose two-headed variants have a value network too)
 # activation, deterministic, two-headed log-std
 VARIANTS = [(a, d, t) for a in ("tanh", "relu") for d in (False, True) for t in (False, True)]
-CASES = [(0, v) for v in range(len(VARIANTS))] + [(1, 0), (2, 5), (3, 0)]
+CASES = [(0, v) for v in range(len(VARIANTS))] + [(1, 0), (2, 5), (3, 0), (4, 5), (5, 0)]
 
 
 # ---- 1. the act and the state, day by day ---------------------------------------------------------------------------------------------
@@ -138,7 +141,8 @@ def test_act_and_state_equal_the_twin_over_auto_resets(amd, lib, shape, variant)
     N, K, hidden, width = SHAPES[shape]
     act, det, two = VARIANTS[variant]
     rng = np.random.default_rng(100 * shape + variant)
-    pol = _policy(rng, K, hidden, width, act, two, value=variant % 2 == 0, normalize=variant % 3 != 1)
+    pol = _policy(rng, K, hidden, width, act, two, value=variant % 2 == 0 or shape in VALUE_TOO, normalize=variant % 3 != 1)
+    assert shape < 4 or (K + 1 > 256 and (shape == 4) == (two and bool(pol.value_layers)) and (shape == 5) == (pol.log_std is not None))
     seeds = rng.integers(0, 2 ** 63, N).astype(np.uint64)
     e = _engine(amd, _planes(N, K), **RESETS)
     e.mlp_init(pol, seeds, deterministic=det)

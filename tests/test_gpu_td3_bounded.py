@@ -420,11 +420,16 @@ def test_with_sigma_5_everything_stays_in_the_box(amd):
 
 
 # ---- 10. teacher days -----------------------------------------------------------------------------------------------------------------
-def test_teacher_days_record_the_mapping_of_the_buffers_actions(amd):
+@pytest.mark.parametrize("name,envs", [("B1", 5), ("B3", 5)], ids=["5x6", "5x256"])
+def test_teacher_days_record_the_mapping_of_the_buffers_actions(amd, name, envs):
     """TD3Trainer.demonstrate("fixed") under bounds at B1: the sampled bids (30 cents to 4 dollars: some above the box) and the budget
-    (above its bound) stay in the action buffers; the record's and the ring's actions are their mapping, faces included"""
+    (above its bound) stay in the action buffers; the record's and the ring's actions are their mapping, faces included.  And at
+    B3's network with 5 envs: k_teach_record_bounded's 5 x 257 = 1285 lanes are six blocks, the last one partial - the split
+    i / A, i % A across blocks and the read of lo / inv_half at a = 256, under the box's ragged bounds"""
     from adcraft_amd.baselines.td3_trainer import TD3Trainer
-    c = _case("B1")
+    c = _case(name)
+    c["N"], c["seeds"] = envs, np.arange(envs, dtype=np.uint64) + 5
+    assert (c["N"], c["K"]) in ((5, 6), (5, 256))
     N, K, lo, hi = c["N"], c["K"], c["lo"], c["hi"]
     t = TD3Trainer(_engine(amd, _planes(N, K), **NO_RESETS), c["pol"], critic_hidden=c["critics"][:-1], horizon=3, agent_seeds=c["seeds"], critics=c["crit"],
                    batch_size=8, capacity=24, action_bounds=(lo, hi))
@@ -438,6 +443,7 @@ def test_teacher_days_record_the_mapping_of_the_buffers_actions(amd):
         assert _same(rec["action"][day], want), day
     assert _same(buf["a"], np.concatenate([want] * 3)) and not rec["logp"].any()
     assert np.all(want[:, 0] == 1) and (want[:, 1:] == 1).any() and (np.abs(want[:, 1:]) < 1).any()
+    assert len(set(want[:, K].tolist())) > 1, "component a = K of the label was meant to differ between envs"
     e.td3_update(1)                                                 # (the critics read such a ring)
     e.close()
 

@@ -30,12 +30,18 @@ def noise(seed, pair, generation, P, p0=0):
     return out
 
 
-def members(theta, seed, generation, M, sigma):
-    """[M, P]: member 2i = theta + sigma * eps(i), member 2i + 1 = theta + sigma * (-eps(i))"""
+def noise_rows(seed, generation, pairs, P, p0=0):
+    """[pairs, P - p0]: eps(i, generation)[p0 : P] of the pairs i in order - what members() and update() draw, for a caller that
+    draws it once for both"""
+    return np.stack([noise(seed, i, generation, P, p0) for i in range(pairs)])
+
+
+def members(theta, seed, generation, M, sigma, rows=None):
+    """[M, P]: member 2i = theta + sigma * eps(i), member 2i + 1 = theta + sigma * (-eps(i)); rows: noise_rows, if drawn already"""
     theta = np.asarray(theta, dtype=F)
     out = np.zeros((M, theta.size), dtype=F)
     for i in range(M // 2):
-        e = noise(seed, i, generation, theta.size)
+        e = noise(seed, i, generation, theta.size) if rows is None else rows[i]
         out[2 * i] = theta + F(sigma) * e
         out[2 * i + 1] = theta + F(sigma) * (-e)
     return out
@@ -71,8 +77,10 @@ def bias_correction(beta, t):
 
 
 def update(theta, m, v, fit, seed, generation, sigma=0.02, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, l2=0.0, shaping="centered_rank",
-           optimiser="adam"):
-    """one generation: returns (theta, m, v, g) - new arrays, float32"""
+           optimiser="adam", p0=0, rows=None):
+    """one generation: returns (theta, m, v, g) - new arrays, float32.  A parameter's update reads nothing of another's, so a range
+    of a longer flat vector is restated on its own: p0 > 0 says that theta, m and v are the entries [p0, p0 + theta.size) of one.
+    rows: noise_rows of those entries, if drawn already"""
     theta, m, v = (np.array(a, dtype=F) for a in (theta, m, v))
     fit = np.asarray(fit, dtype=np.float64)
     M, P = fit.size, theta.size
@@ -81,7 +89,8 @@ def update(theta, m, v, fit, seed, generation, sigma=0.02, lr=0.01, beta1=0.9, b
     with np.errstate(all="ignore"):
         for i in range(M // 2):
             du = u[2 * i] - u[2 * i + 1]
-            acc = acc + du * noise(seed, i, generation, P).astype(np.float64)
+            e = noise(seed, i, generation, p0 + P, p0) if rows is None else rows[i]
+            acc = acc + du * e.astype(np.float64)
         g = (acc / (np.float64(M) * np.float64(F(sigma)))).astype(F)
         if l2 > 0:
             g = g - F(l2) * theta
@@ -94,6 +103,20 @@ def update(theta, m, v, fit, seed, generation, sigma=0.02, lr=0.01, beta1=0.9, b
         c1, c2 = bias_correction(beta1, t), bias_correction(beta2, t)
         theta = theta + F(lr) * ((m / c1) / (np.sqrt(v / c2) + F(eps)))
     return theta.astype(F), m.astype(F), v.astype(F), g.astype(F)
+
+
+def draw_fitness(rng, M, ties=False, nans=False, tie_in_pair=True):
+    """[M] float64 as tests/test_es_host.py draws it: normals times 100; ties: two members tied with member 0 - member M - 1 and
+    member 1, or (tie_in_pair off: under raw shaping a tie inside a pair is a pair without a term) member 2; nans: two NaNs (ranked
+    lowest, by index)"""
+    fit = rng.standard_normal(M) * 100
+    if ties:
+        fit[1 if tie_in_pair else 2] = fit[0]
+        fit[M - 1] = fit[0]
+    if nans:
+        fit[M // 2] = np.nan
+        fit[0 if M == 2 else 2] = np.nan
+    return fit
 
 
 def flat_params(policy):

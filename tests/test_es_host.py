@@ -79,6 +79,41 @@ def test_update_twin_equals_the_restatement_bit_for_bit(lib, case):
             tw, ref = t[:3], r[:3]
 
 
+def test_noise_twin_in_the_last_quads_of_a_wide_flat_vector(lib):
+    """P = 127 345 (K = 40, hidden (256, 255, 33): tests/test_gpu_es_shapes.py holds the device to the twin there): the last 65
+    parameters from an aligned start, the last 4 from p0 = 127 341 = 4 * 31 835 + 1 - quad indices above 2^14, an unaligned start,
+    a last quad of one parameter"""
+    P = 127345
+    for seed, pair, generation in ((61, 16, 300), (2 ** 64 - 1, 0, 0), (99, 255, 301)):
+        for p0 in (127280, 127341):
+            got = E.twin_noise(lib, seed, pair, generation, p0, P - p0)
+            assert got.size == P - p0 and _same(got, E.noise(seed, pair, generation, P, p0)), (seed, pair, generation, p0)
+    assert _same(E.twin_noise(lib, 61, 16, 300, 127280, 65)[61:], E.twin_noise(lib, 61, 16, 300, 127341, 4))
+
+
+@pytest.mark.parametrize("M", [34, 66])
+@pytest.mark.parametrize("kw", [dict(), dict(shaping="raw", optimiser="sgd", l2=0.01, lr=0.002)], ids=["adam-ranks", "sgd-raw-l2"])
+def test_update_twin_at_the_pair_counts_the_device_sums_in_rounds(lib, kw, M):
+    """(P, M) = (523, 34) and (523, 66): 17 and 33 pairs, P = 4 * 130 + 3.  The twin is a serial loop and has no rounds; it is the
+    yardstick of the device's rounds in tests/test_gpu_es_shapes.py, and is held to the restatement here at those counts"""
+    P = 523
+    rng = np.random.default_rng(200 + M)
+    tw = ref = (rng.standard_normal(P).astype(F), np.zeros(P, F), np.zeros(P, F))
+    for generation in range(2):
+        ranks = kw.get("shaping", "centered_rank") == "centered_rank"
+        fit = E.draw_fitness(rng, M, ties=generation == 1, nans=ranks and generation == 1, tie_in_pair=ranks)
+        rows = E.noise_rows(77, generation, M // 2, P)
+        t = E.twin_update(lib, *tw, fit, 77, generation, **kw)
+        r = E.update(*ref, fit, 77, generation, rows=rows, **kw)
+        for name, a, b in zip(("theta", "m", "v", "g"), t, r):
+            assert _same(a, b), (kw, M, generation, name)
+        # a range restated on its own is that range of the whole
+        part = E.update(*(a[130:201] for a in ref), fit, 77, generation, p0=130, **kw)
+        assert all(_same(a, b[130:201]) for a, b in zip(part, r)), (kw, M, generation)
+        assert np.all(r[3] != 0) and not _same(t[0], tw[0])
+        tw, ref = t[:3], r[:3]
+
+
 def test_shaping_ranks_ties_by_index_and_nan_lowest():
     u = E.shape(np.array([3.0, np.nan, 3.0, -1.0, np.nan, 9.0]), "centered_rank")
     assert np.array_equal(u, np.array([3, 0, 4, 2, 1, 5]) / 5.0 - 0.5)

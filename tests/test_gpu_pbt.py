@@ -139,6 +139,36 @@ def test_device_fitness_equals_the_restatement_on_the_fetched_record(amd, member
     e.close()
 
 
+def test_device_fitness_with_more_envs_a_member_than_the_block_has_lanes(amd):
+    """2 learners over 600 envs: n = 300 envs a member, so lanes 0 to 43 of k_pbt_fitness take a second pass of its env loop and
+    lane 0 chains over 300 returns.  K = 3, a hidden layer of 4, T = 3 with max_days = 2: an auto-reset inside the record"""
+    members, envs, k, t = 2, 600, 3, 3
+    n = envs // members
+    rng = np.random.default_rng(777)
+    pols = [R.random_policy(rng, k, (4,), "tanh", value=True, scale=0.6) for _ in range(members)]
+    pols[1].layers[-1][1][1:] += F(0.4)                           # (the second member bids higher: the members' returns differ)
+    e = amd.StepEngine(envs, k, seed=SEED, max_days=2, auto_reset=True)
+    e.set_all_params(H.implicit_params(envs, k, SEED + 1, mean_volume=24, cvr=0.5))
+    e.reset()
+    e.mlp_init(pols[0], deterministic=False)
+    e.mlp_learners(members)
+    e.mlp_set_learner(1, pols[1])
+    e.rollout_enable(t, obs=True)
+    e.pg_pop_init([P.options(minibatch_envs=n) for _ in range(members)])
+    e.pbt_init("pg", replace_count=1)
+    e.run_days("mlp", t, BUDGET)
+    rec = e.rollout_fetch()
+    done = rec["terminated"] | rec["truncated"]
+    assert done.any() and not done.all(), "the record was meant to cross an auto-reset"
+    want = B.fitness(rec["reward"], members)
+    first = [float(np.sum(rec["reward"][:, m * n:m * n + 256].astype(np.float64))) / n for m in range(members)]
+    assert all(abs(first[m] - want[m]) > 1e-6 * abs(want[m]) for m in range(members)), "the envs of the second pass matter to both members"
+    got = e.pbt_fitness()
+    assert _same(got, want), (got, want)
+    assert got[0] != got[1]
+    e.close()
+
+
 # ---- 2. the batched exploit equals the primitives (PPO) ----------------------------------------------------------------------------
 def test_batched_exploit_equals_pair_by_pair_copies(amd):
     e1, e2 = _pg_population(amd), _pg_population(amd)

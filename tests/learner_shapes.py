@@ -84,28 +84,28 @@ def pg_lds_floats(K, pol_widths, val_widths, kl=False, frames=1):
     return D + 2 * maxw + (5 if kl else 3) * A + sum(pol_widths) + sum(val_widths)
 
 
-def td3_lds_floats(K, pol_widths, q_widths):
+def td3_lds_floats(K, pol_widths, q_widths, frames=1):
     """row | the actor's outputs | one critic's outputs | two delta rows and a dump row | four words"""
-    D, A = 5 * K + 2, K + 1
+    D, A = frames * (5 * K + 2), K + 1
     maxw = max([A] + list(pol_widths) + list(q_widths))
     return D + A + sum(pol_widths) + sum(q_widths) + 3 * maxw + 4
 
 
-def sac_lds_floats(K, pol_widths, q_widths):
+def sac_lds_floats(K, pol_widths, q_widths, frames=1):
     """row | the actor's outputs | both critics' outputs | two delta rows and a dump row | six head vectors | eight words"""
-    D, A = 5 * K + 2, K + 1
+    D, A = frames * (5 * K + 2), K + 1
     maxw = max([A] + list(pol_widths) + list(q_widths))
     return D + A + sum(pol_widths) + 2 * sum(q_widths) + 3 * maxw + 6 * A + 8
 
 
 def widest_count(family, K, frames=1):
-    """the float count of a sample of K keywords under the widest networks of the family"""
+    """the float count of a sample of K keywords under the widest networks of the family; frames: the stacked row's D = frames (5 K + 2)"""
     h, q, A = list(WIDEST["hidden"]), list(WIDEST["critics"]), K + 1
     if family in ("pg", "pg_kl"):
         return pg_lds_floats(K, h + [2 * A], h + [1], kl=family == "pg_kl", frames=frames)
     if family == "td3":
-        return td3_lds_floats(K, h + [A], q)
-    return sac_lds_floats(K, h + [2 * A], q)
+        return td3_lds_floats(K, h + [A], q, frames)
+    return sac_lds_floats(K, h + [2 * A], q, frames)
 
 
 def boundary_K(family, frames=1):

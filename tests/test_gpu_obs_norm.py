@@ -8,7 +8,9 @@ fails on the parent commit.
 The shapes are the smallest that cross a chunk of 1024 samples, a tile of 256 columns and a member boundary:
 64 envs x 5 keywords (D = 27) x 20 days (S = 1280: a full chunk and one of 256); 8 envs x 60 keywords (D = 302) x 130 days
 (S = 1040: columns past one tile, a tail chunk of 16); 48 envs x 25 keywords (D = 127) x 23 days x 4 learners (n = 12,
-S = 276 per member, whose rows are not contiguous)."""
+S = 276 per member, whose rows are not contiguous).  Members, chunks and column tiles at once - 3 learners x 7 envs x 52 keywords
+x 150 days, where a member's second chunk starts inside a day - live in tests/test_gpu_replay_shapes.py, for this normaliser, the
+reward normaliser beside it and the TD3 / SAC learners' own."""
 import signal
 
 import numpy as np

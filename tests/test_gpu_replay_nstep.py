@@ -4,7 +4,8 @@ auto-resets, a second store and a wrapping ring, with and without an observation
 mixed discounts; the reward normaliser's multiplier and clip; prioritised replay; populations against solo engines, member copies
 and a PBT round with rings; n = 1 and off; the refusals; a resumed trainer.  3 envs per learner x 2 keywords, policy (8,), critics
 (8, 1), batch 8.  The entry points do not exist before this feature: every test but the off-means-off one fails on the parent
-commit."""
+commit.  The wide shapes live in tests/test_gpu_replay_shapes.py: the four forms of the store and the population's at K = 256,
+where a row takes six passes of 256 lanes (twelve with two frames) and an action two."""
 import copy
 import signal
 

@@ -3,7 +3,8 @@ tests/per_ref.py, bit for bit: the tree and the sampler on one, two and three le
 duplicates, the ring's wrap, populations against solo engines, member copies and a PBT exploit with rings, a checkpoint,
 set_beta, every refusal, and the four trainers.  8 envs x 3 keywords, policy (8,), critics (8, 8, 1), batch 16; the
 population tests take 9 envs, so that three members own three each.  None of these symbols exists before this feature:
-every test here fails on the parent commit."""
+every test here fails on the parent commit.  The wide shapes live in tests/test_gpu_replay_shapes.py: a three-level tree
+(capacity 4200) under TD3, SAC and population updates and under a wrapping store."""
 import signal
 
 import numpy as np
